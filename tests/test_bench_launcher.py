@@ -81,6 +81,31 @@ def test_thread_group_is_a_barrier_and_an_all_gather():
         assert got[r] == ([("first", i) for i in range(world)], [i * i for i in range(world)])
 
 
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """Without --full a run measures the headline only (no roofline sample, no other configurations, no CPU baseline)."""
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.full is False and args.sample_in is None and args.dump_outputs is None and args.steps == 7
+    args = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert args.full is True and args.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_records_as_float_arrays(tmp_path):
+    import numpy as np
+    from pose_refine_amd import _lib
+    res = np.zeros(3, _lib.RESULT)
+    res["T"] = np.arange(48, dtype=np.float32).reshape(3, 16)
+    res["fitness"], res["inlier_rmse"] = [0.5, 0.25, 1.0], [1.5, 2.5, 3.5]
+    sizes = np.array([7, 0, 4294967295], np.uint32)
+    bench.dump_outputs(str(tmp_path / "d"), res, sizes)
+    assert sorted(os.listdir(tmp_path / "d")) == ["T.npy", "fitness.npy", "inlier_rmse.npy", "sizes.npy"]
+    T = np.load(tmp_path / "d" / "T.npy")
+    assert T.dtype == np.float32 and T.shape == (3, 16) and np.array_equal(T, res["T"])
+    assert np.array_equal(np.load(tmp_path / "d" / "fitness.npy"), np.float32([0.5, 0.25, 1.0]))
+    assert np.load(tmp_path / "d" / "inlier_rmse.npy").dtype == np.float32
+    got = np.load(tmp_path / "d" / "sizes.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, sizes.astype(np.float64))
+
+
 def _run_bench(extra, env_extra, gpus=2, share=True):
     env = dict(os.environ, **env_extra)
     if share:
@@ -152,13 +177,35 @@ def test_bench_eight_rank_threads_gather_through_the_c_abi_over_the_loopback_lib
 def test_bench_force_comm_runs_the_rccl_gather_with_a_world_of_one():
     """PR_BENCH_FORCE_COMM=1: the whole N > 1 machinery with ONE rank -- torch's process group on the RCCL backend and the library's own
     dlopened RCCL communicator (pr_comm_init_rank, pr_gather_results) in one process, on every round's GPU box."""
-    d = _run_bench([], {"PR_BENCH_FORCE_COMM": "1"}, gpus=1, share=False)
+    d = _run_bench(["--full"], {"PR_BENCH_FORCE_COMM": "1"}, gpus=1, share=False)
     assert d["n_gpus"] == 1 and d["launcher"]["kind"] == "processes"
     assert d["gather"].startswith("pr_gather_results") and d["gather_when"] == "job" and d["gathers_in_timed_region"] == 1
     assert d["gather_bytes_per_rank"] == 72 * 256 * 6 and d["value"] > 1000
     for key in ("step_ms_spread", "host_cpu_ms_per_step", "roofline"):
         assert key in d
     assert d["roofline"]["frac"] <= 1.0 and d["roofline"]["frac_end_to_end"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path, golden_dir):
+    """`bench.py --gpus 1 --dump-outputs DIR`: the headline line alone (no roofline sample, no other configurations, no CPU baseline), and
+    the outputs of its last timed step -- the 256 hypotheses of BASELINE configs[1] -- held to the committed oracle fixture like
+    tests/test_golden_full_gpu.py holds the library's own calls."""
+    import numpy as np
+    d = _run_bench(["--dump-outputs", str(tmp_path)], {}, gpus=1, share=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["step_ms_spread"]["n"] == 6
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 256) < 1e-6 * 256
+    for key in ("roofline", "cpu_baseline", "config2_kdtree", "solve_on_host", "default_criteria", "new_scene_per_frame", "config3_share_512", "config4_share_128"):
+        assert key not in d, key
+    g = np.load(os.path.join(golden_dir, "config1.npz"))
+    T, fit, rmse, sizes = (np.load(tmp_path / (n + ".npy")) for n in ("T", "fitness", "inlier_rmse", "sizes"))
+    assert T.dtype == fit.dtype == rmse.dtype == np.float32 and sizes.dtype == np.float64 and T.shape == (256, 16)
+    assert np.array_equal(sizes, g["fixed20_sizes"].astype(np.float64))
+    assert np.array_equal(fit, g["fixed20_fitness"])
+    assert np.allclose(rmse, g["fixed20_rmse"], rtol=1e-6, atol=0)
+    assert np.abs(T - g["fixed20_T"]).max() <= 1e-4
 
 
 def test_committed_bench_lines_keep_the_contract():

@@ -4,7 +4,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/round; rm -rf $OUT; mkdir -p $OUT                 # (gpurun merges into gpurun_out: start from an empty directory, nothing stale gets copied to profiles/)
-B="timeout 600 python bench.py"
+B="timeout 600 python bench.py --full"
 summ() { python tools/rocpd_summary.py "$1"; }
 # the GPU tests under a kernel trace: test summary + which kernel instantiations of the library they dispatched
 rocprofv3 --kernel-trace --stats -d $OUT/cov -o t -- python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tail -3 > $OUT/pytest_gpu.txt; cat $OUT/pytest_gpu.txt
@@ -21,12 +21,12 @@ $B --steps 60 --poses 1024 --no-cpu-baseline --no-kdtree-extra 2>/dev/null | tai
 $B --steps 60 --poses 512 --no-cpu-baseline --no-kdtree-extra 2>/dev/null | tail -1 > $OUT/bench_p512_proj.json
 $B --steps 20 --warmup 3 --scene nn 2>/dev/null | tail -1 > $OUT/bench_p256_nn.json
 # rocprofv3 kernel stats of the same commands
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench -- python bench.py --no-cpu-baseline --no-kdtree-extra > $OUT/bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench -- python bench.py --full --no-cpu-baseline --no-kdtree-extra > $OUT/bench_under_rocprof.json 2>/dev/null
 summ $OUT/stats/bench_results.db > $OUT/kernel_stats_bench_p256.md
 python tools/step_timeline.py $OUT/stats/bench_results.db > $OUT/step_timeline.md
-rocprofv3 --kernel-trace --stats -d $OUT/stats1 -o bench -- python bench.py --sequential --no-cpu-baseline > $OUT/bench_under_rocprof_sequential.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $OUT/stats1 -o bench -- python bench.py --full --sequential --no-cpu-baseline > $OUT/bench_under_rocprof_sequential.json 2>/dev/null
 summ $OUT/stats1/bench_results.db > $OUT/kernel_stats_bench_p256_sequential.md
-rocprofv3 --kernel-trace --stats -d $OUT/stats2 -o bench -- python bench.py --steps 20 --warmup 3 --scene nn --no-cpu-baseline > $OUT/bench_nn_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $OUT/stats2 -o bench -- python bench.py --full --steps 20 --warmup 3 --scene nn --no-cpu-baseline > $OUT/bench_nn_under_rocprof.json 2>/dev/null
 summ $OUT/stats2/bench_results.db > $OUT/kernel_stats_bench_p256_nn.md
 # PMC passes (each counter set in a run of its own): HBM bytes of the correspondence kernels, projective and kd-tree
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do n=$(echo $c | tr " " "_")
@@ -56,17 +56,17 @@ timeout 600 python tools/config5.py 128 --check > $OUT/config5.txt 2>&1; tail -4
 rocprofv3 --kernel-trace --stats -d $OUT/stats3 -o c5 -- python tools/config5.py 128 > /dev/null 2>&1
 summ $OUT/stats3/c5_results.db > $OUT/kernel_stats_config5.md
 # two ranks on the one GPU of this box, started by bench.py itself: one process per rank under torch.distributed.run, and one host thread per rank
-PR_BENCH_SHARE_DEVICE=1 timeout 600 python bench.py --gpus 2 --steps 40 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_2ranks_share_device_processes.json
-PR_BENCH_SHARE_DEVICE=1 timeout 600 python bench.py --gpus 2 --steps 40 --warmup 5 --launcher threads 2>/dev/null | tail -1 > $OUT/bench_2ranks_share_device_threads.json
+PR_BENCH_SHARE_DEVICE=1 timeout 600 python bench.py --full --gpus 2 --steps 40 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_2ranks_share_device_processes.json
+PR_BENCH_SHARE_DEVICE=1 timeout 600 python bench.py --full --gpus 2 --steps 40 --warmup 5 --launcher threads 2>/dev/null | tail -1 > $OUT/bench_2ranks_share_device_threads.json
 # EIGHT ranks on the one GPU: the driver's SCALE job on this box's 16-CPU cgroup, both launchers; per-rank host CPU over the timed region is in the line
-PR_BENCH_SHARE_DEVICE=1 timeout 900 python bench.py --gpus 8 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_8ranks_share_device_processes.json
-PR_BENCH_SHARE_DEVICE=1 timeout 900 python bench.py --gpus 8 --steps 20 --warmup 5 --launcher threads 2>/dev/null | tail -1 > $OUT/bench_8ranks_share_device_threads.json
+PR_BENCH_SHARE_DEVICE=1 timeout 900 python bench.py --full --gpus 8 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_8ranks_share_device_processes.json
+PR_BENCH_SHARE_DEVICE=1 timeout 900 python bench.py --full --gpus 8 --steps 20 --warmup 5 --launcher threads 2>/dev/null | tail -1 > $OUT/bench_8ranks_share_device_threads.json
 # eight rank THREADS on the one GPU gathering through pr_gather_results' N > 1 branch over the loop-back stand-in for librccl (tests/rccl_loopback)
 hipcc -shared -fPIC -O2 tests/rccl_loopback/loopback_rccl.cpp -o tests/rccl_loopback/librccl_loopback.so 2>/dev/null
-PR_BENCH_SHARE_DEVICE=1 PR_RCCL_LIBRARY=$PWD/tests/rccl_loopback/librccl_loopback.so timeout 900 python bench.py --gpus 8 --steps 20 --warmup 5 --launcher threads 2>/dev/null | tail -1 > $OUT/bench_8ranks_loopback_gather_threads.json
+PR_BENCH_SHARE_DEVICE=1 PR_RCCL_LIBRARY=$PWD/tests/rccl_loopback/librccl_loopback.so timeout 900 python bench.py --full --gpus 8 --steps 20 --warmup 5 --launcher threads 2>/dev/null | tail -1 > $OUT/bench_8ranks_loopback_gather_threads.json
 PR_RCCL_LIBRARY=$PWD/tests/rccl_loopback/librccl_loopback.so timeout 300 python tests/rccl_loopback/run_gather.py 8 2>/dev/null | tail -1 > $OUT/gather_loopback_8ranks.json; cut -c1-300 $OUT/gather_loopback_8ranks.json
 # the whole N > 1 machinery with a world of one: torch's RCCL process group and the library's own dlopened RCCL in one process
-PR_BENCH_FORCE_COMM=1 timeout 300 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_force_comm_world1.json
+PR_BENCH_FORCE_COMM=1 timeout 300 python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_force_comm_world1.json
 # the host-solve pipeline over time from its first step (round 6: one flag per pose group polled by the helper threads), and the device-solve one
 for m in host host device; do timeout 300 python tools/host_warm_probe.py $m 2>/dev/null | tail -1; done > $OUT/pipeline_rate_over_time.txt
 for hp in 0 1 0 1 0 1; do timeout 200 python bench.py --steps 40 --warmup 5 --solve host --no-cpu-baseline --no-kdtree-extra --no-live-pmc --opt host_poll=$hp 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('host_poll $hp: %.0f poses/s, largest step %.2f ms, closing fence %.2f ms' % (d['value'], d['step_ms_spread']['max'], d['step_ms_spread']['closing_fence_ms']))"; done > $OUT/host_poll_ab.txt; cat $OUT/host_poll_ab.txt

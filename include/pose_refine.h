@@ -259,6 +259,32 @@ int pr_refine_submit_roi(int slot, const pr_triangle *tris_dev, size_t n_tris, c
                          pr_result *results_host, pr_result *results_dev, uint32_t *cloud_sizes_host);
 int pr_refine_wait(int slot);
 
+/* ---- verification: render-and-compare scoring of hypotheses against the scene depth ------------ */
+/* Depth-consistency score of one hypothesis: its render compared pixel by pixel with a scene depth image (mm).
+ * r = the hypothesis' rendered depth (pr_render's value at that pixel), s = the scene depth at the same frame pixel, tau = tau_mm.
+ * Only pixels with r > 0 count. */
+typedef struct {
+    uint32_t visible;      /* pixels the hypothesis renders (== its cloud size in pr_refine_batch at the same pose / roi) */
+    uint32_t inlier;       /* s > 0 and |r - s| <= tau                                                                   */
+    uint32_t occluded;     /* s > 0 and s < r - tau : scene surface in front of the model                                */
+    uint32_t violation;    /* s > 0 and s > r + tau : scene seen behind where the model would be (free-space violation)  */
+    uint32_t missing;      /* s <= 0 : no measurement                                                                    */
+    uint32_t reserved;     /* written as 0                                                                               */
+    uint64_t abs_err_sum;  /* sum of |r - s| over the inlier pixels, mm (exact)                                          */
+} pr_pose_score;           /* 32 B; visible == inlier + occluded + violation + missing                                  */
+
+/* Renders every pose (inside `roi` only when one is given, as pr_refine_batch_roi does) and scores it against scene_depth_dev, a dense
+ * width x height frame on the device: int32 when depth_is_i32 is set, uint16 otherwise (the flag of pr_scene_proj_prepare_dev).
+ * scores_host receives n_poses records.  The scene is read on every call (nothing derived from it is kept).  Synchronous, on the
+ * calling thread's context; a batch pending on an asynchronous slot is not disturbed.  PR_ERR_INVALID for tau_mm < 0, null pointers
+ * with n_poses > 0 or a ROI outside the image; n_poses == 0 returns PR_OK and writes nothing.  The counts carry no ranking policy. */
+int  pr_score_poses(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses,
+                    uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi,
+                    const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host);
+/* refined pose of hypothesis i = T'_i * pose_i, where T'_i is results[i].T with its translation (T[3], T[7], T[11]) times 1000.0f:
+ * clouds are in metres (icp.cu:249, depth/1000), poses in mm.  Product in pr_mat4_mul's order.  Host only. */
+void pr_refined_poses(const pr_result *results, const pr_mat4 *poses, uint32_t n, pr_mat4 *refined_out);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

@@ -24,7 +24,10 @@ SOLVE_HOST, SOLVE_DEVICE = 0, 1
 KDNODE = np.dtype([("parent", "<i4"), ("child1", "<i4"), ("child2", "<i4"), ("split_v", "<f4"),
                    ("bbox", "<f4", (6,)), ("split_dim", "<i4"), ("left", "<i4"), ("right", "<i4")])
 RESULT = np.dtype([("T", "<f4", (16,)), ("inlier_rmse", "<f4"), ("fitness", "<f4")])
-assert KDNODE.itemsize == 52 and RESULT.itemsize == 72
+# pr_pose_score: render-and-compare counts of one hypothesis (pr_score_poses)
+SCORE = np.dtype([("visible", "<u4"), ("inlier", "<u4"), ("occluded", "<u4"), ("violation", "<u4"), ("missing", "<u4"),
+                  ("reserved", "<u4"), ("abs_err_sum", "<u8")])
+assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32
 
 
 class PoseRefineError(RuntimeError):
@@ -107,6 +110,8 @@ SIGNATURES = {
     "pr_refine_batch_roi": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, Roi, _vp, _vp]),
     "pr_refine_submit_roi": (_i32, [_i32, _vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, Roi, _vp, _vp, _vp]),
     "pr_refine_wait": (_i32, [_i32]),
+    "pr_score_poses": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp]),
+    "pr_refined_poses": (None, [_vp, _vp, _u32, _vp]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, Criteria, KDNODE, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SOLVE_DEVICE, SOLVE_HOST,
+from ._lib import (COMM_ID_BYTES, Criteria, KDNODE, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -575,6 +575,60 @@ def refine_wait(slot: int):
     check(_lib.load().pr_refine_wait(int(slot)))
     res, sizes, _, _ = _slots().pop(int(slot))
     return res, sizes
+
+
+# ------------------------------------------------------------------------------------------------
+# verification: render-and-compare scoring of (refined) hypotheses
+# ------------------------------------------------------------------------------------------------
+def score_poses(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int,
+                roi: Sequence[int] = (0, 0, 0, 0)) -> np.ndarray:
+    """``pr_score_poses``: render every pose (inside ``roi`` only, when one is given) and compare it pixel by pixel with the scene
+    depth (mm).  ``scene_depth`` is a DeviceVector of ``width * height`` int32 or uint16 values, or a host (height, width) array of
+    either dtype, which is uploaded for the call.  Returns SCORE[P]: visible / inlier / occluded / violation / missing pixel counts and
+    the exact sum of |r - s| over the inliers."""
+    td = _tris_dev(tris)
+    poses = _f32(poses, (-1, 16))
+    pj = _f32(proj, -1)
+    if isinstance(scene_depth, DeviceVector):
+        sd = scene_depth
+    else:
+        arr = np.ascontiguousarray(scene_depth)
+        if arr.dtype not in (np.uint16, np.int32):
+            raise ValueError("scene depth must be CV_16U or CV_32S")
+        sd = DeviceVector.from_host(arr.reshape(-1))
+    if sd.dtype not in (np.uint16, np.int32):
+        raise ValueError("scene depth must be CV_16U or CV_32S")
+    if sd.size() != width * height:
+        raise ValueError(f"scene depth holds {sd.size()} values, expected {width} x {height}")
+    out = np.zeros(len(poses), SCORE)
+    check(_lib.load().pr_score_poses(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                     sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out)))
+    return out
+
+
+def refined_poses(records, poses) -> np.ndarray:
+    """``pr_refined_poses``: the pose each ICP result stands for, ``T' @ pose`` with the result's translation scaled from metres
+    (the clouds) to millimetres (the poses).  float32[P, 4, 4]."""
+    rec = np.ascontiguousarray(records, RESULT)
+    poses = _f32(poses, (-1, 16))
+    if len(rec) != len(poses):
+        raise ValueError(f"{len(rec)} results for {len(poses)} poses")
+    out = np.zeros((len(poses), 4, 4), np.float32)
+    _lib.load().pr_refined_poses(ptr(rec), ptr(poses), len(poses), ptr(out))
+    return out
+
+
+def rank_hypotheses(scores) -> np.ndarray:
+    """Hypothesis indices, best first.  The policy: inlier fraction ``inlier / (visible - occluded)`` in float64, descending --
+    occluded pixels neither count for nor against a hypothesis, missing and violating ones count against it.  Hypotheses with
+    ``visible - occluded == 0`` (nothing rendered, or only occluded pixels) come last.  Ties: more inliers first, then the lower index."""
+    sc = np.asarray(scores)
+    inl = sc["inlier"].astype(np.int64)
+    den = sc["visible"].astype(np.int64) - sc["occluded"].astype(np.int64)
+    empty = den <= 0
+    frac = np.where(empty, 0.0, inl.astype(np.float64) / np.where(empty, 1, den).astype(np.float64))
+    idx = np.arange(len(sc), dtype=np.int64)
+    return np.lexsort((idx, -inl, -frac, empty.astype(np.int8))).astype(np.int64)
 
 
 def eigen_slover_666(A, b) -> np.ndarray:

@@ -84,4 +84,14 @@ __device__ __forceinline__ uint32_t fingerprint_lane(const uint32_t *__restrict_
 
 constexpr uint32_t kBoxRowsPerBlock = 16;                        // rows of a pixel box per workgroup: 4 wavefronts x 4 rows (few, fatter workgroups: dispatch-bound otherwise)
 
+// box_off (fused asynchronous path): the boxes of a sub-batch PACKED one behind the other, each as its own little image (pitch = its width) at
+// box_off[hypothesis] ints -- like the clouds (d2c_pack_starts_kernel), and for the same reason: 290 KB boxes 1.2 MB apart make the render depend
+// on the frame's size (a frame 17 or 32 rows taller: -3 %).  nullptr: full frames [hypothesis][height][width].
+__device__ __forceinline__ int32_t *box_line(int32_t *depth, const uint32_t *box_off, const int4 bb, uint32_t pose, uint32_t row, uint32_t width, uint32_t height)
+{
+    if (!box_off) return depth + ((size_t)pose * height + row) * width;
+    const ptrdiff_t pitch = max(bb.z - bb.x + 1, 0);
+    return depth + box_off[pose] + ((ptrdiff_t)row - (ptrdiff_t)((int)height - 1 - bb.w)) * pitch - (ptrdiff_t)bb.x;      // line[x] for bb.x <= x <= bb.z
+}
+
 }  // namespace prk

@@ -740,6 +740,16 @@ void pr_solve_666(const float A[36], const float b[6], pr_mat4 *T_out) { prs::so
 // mat<4,4,float> * mat<4,4,float> (cuda_icp/geometry.h:292-298): the product the ICP loop accumulates its result with (icp.cu:212);
 // the same source (pr_solver.inl) is compiled for the device-side loop
 void pr_mat4_mul(const pr_mat4 *A, const pr_mat4 *B, pr_mat4 *C_out) { prs::mat4_mul_impl(A->m, B->m, C_out->m); }
+// the ICP result moves the model cloud, which is in metres (icp.cu:249: depth / 1000); a pose moves the mesh, which is in mm
+void pr_refined_poses(const pr_result *results, const pr_mat4 *poses, uint32_t n, pr_mat4 *refined_out)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        float T[16];
+        std::memcpy(T, results[i].T, sizeof T);
+        T[3] *= 1000.0f; T[7] *= 1000.0f; T[11] *= 1000.0f;
+        prs::mat4_mul_impl(T, poses[i].m, refined_out[i].m);
+    }
+}
 
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count)
 {

@@ -170,6 +170,10 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
                                PoseMeta *meta = nullptr, DevIcpState *st = nullptr, uint32_t *arrive = nullptr, uint32_t cloud_stride = 0,
                                const uint32_t *box_off = nullptr,    // box_off: the boxes packed into `depth` at these offsets (ints), each with its own pitch (fill_box_kernel)
                                const BatchCheck *check = nullptr);
+// verify.hip: every box pixel a hypothesis renders (launch_render_boxes' layout) against the scene frame (int32 or uint16, mm), added into
+// records[8 * i] (pr_pose_score words: visible, inlier, occluded, violation, missing, reserved, abs_err_sum lo / hi), which the caller zeroed
+hipError_t launch_score_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
+                              const void *scene, bool scene_i32, int32_t tau, uint32_t *records, hipStream_t s);
 hipError_t launch_pack_export(const DevIcpState *st, pr_result *out, const uint32_t *counts, uint32_t *host_counts, pr_result *host_results,
                               uint32_t n, hipStream_t s);
 hipError_t launch_stage_words(const void *src_host_mapped, void *dst, size_t bytes, hipStream_t s);

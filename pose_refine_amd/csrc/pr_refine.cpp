@@ -10,6 +10,27 @@ bool frame_size_ok(size_t W, size_t H)
     return true;
 }
 
+// the hypotheses' poses into g->poses: through the context's pinned staging array, pulled by a kernel (as the asynchronous path stages its inputs) --
+// a copy command from the caller's pageable array goes through the runtime's bounce buffers and its copy-engine path (see icp_drive's
+// result block: that path is where the host-solve pipeline's one-off multi-millisecond stalls came from)
+int stage_poses(const pr_mat4 *poses_host, size_t n)
+{
+    PR_TRY(g->poses.ensure(sizeof(pr_mat4) * n));
+    PR_TRY(g->h_poses.ensure(sizeof(pr_mat4) * n));
+    std::memcpy(g->h_poses.p, poses_host, sizeof(pr_mat4) * n);
+    void *hp = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&hp, g->h_poses.p, 0));
+    HIP_TRY(prk::launch_stage_words(hp, g->poses.p, sizeof(pr_mat4) * n, g->stream));
+    return PR_OK;
+}
+
+// hypotheses per chunk of a synchronous batch: bound the depth workspace to ~4 GiB per chunk (288 GB of HBM would allow far more; this keeps
+// first-touch cost and the 2^32 element index space comfortable)
+uint32_t depth_chunk(size_t img, uint32_t P)
+{
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(P, ((size_t)4 << 30) / (img * sizeof(int32_t))));
+}
+
 int render_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t P, size_t W, size_t H,
                 const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev, bool zero_empty)
 {
@@ -24,15 +45,8 @@ int render_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
         rw = (size_t)roi.width; rh = (size_t)roi.height;
     }
     if (P == 0) return PR_OK;
-    PR_TRY(g->poses.ensure(sizeof(pr_mat4) * P));
     SpanGuard sp(kSpanRender);
-    {   // poses through the pinned staging array, pulled by a kernel (no copy command from the caller's pageable array: see refine_impl)
-        PR_TRY(g->h_poses.ensure(sizeof(pr_mat4) * P));
-        std::memcpy(g->h_poses.p, poses_host, sizeof(pr_mat4) * P);
-        void *hp = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&hp, g->h_poses.p, 0));
-        HIP_TRY(prk::launch_stage_words(hp, g->poses.p, sizeof(pr_mat4) * P, g->stream));
-    }
+    PR_TRY(stage_poses(poses_host, P));
     HIP_TRY(prk::launch_fill_i32(depth_dev, P * rw * rh, INT32_MAX, g->stream));
     HIP_TRY(prk::launch_raster(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), (uint32_t)P, depth_dev, (uint32_t)W, (uint32_t)H,
                                *proj, roi, (uint32_t)rw, (uint32_t)rh, g->stream));
@@ -88,10 +102,8 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
     trace_mark("refine_impl: enter");
     PR_TRY(make_scene(scene_kind, scene, /*want_packed=*/true, sc, nullptr, nullptr, &cam));
     trace_mark("refine_impl: scene ready");
-    // bound the depth workspace to ~4 GiB per chunk (288 GB of HBM would allow far more; this keeps
-    // first-touch cost and the 2^32 element index space comfortable)
     const size_t img = (size_t)W * H;
-    uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(P, ((size_t)4 << 30) / (img * sizeof(int32_t))));
+    uint32_t chunk = depth_chunk(img, P);
     std::vector<uint32_t> start(chunk), count(chunk);
     // model box: recomputed from the triangle buffer on every call (one pass over the mesh; nothing is cached by address here)
     PR_TRY(g->aabb.ensure(6 * sizeof(float)));
@@ -107,19 +119,10 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
         uint32_t *h_counts = g->h_counts.as<uint32_t>();
         // per-pose pixel boxes; raster + row counts + row scan
         PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));   // boxes, then the offsets of the packed boxes (box_pack_offsets_kernel)
-        PR_TRY(g->poses.ensure(sizeof(pr_mat4) * np));
         uint32_t *box_off = (prk::kBoxPack && opt.raster_mode != 1) ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
         {
             SpanGuard sp(kSpanRender);
-            {   // the hypotheses' poses: through the context's pinned staging array, pulled by a kernel (as the asynchronous path stages its inputs) --
-                // a copy command from the caller's pageable array goes through the runtime's bounce buffers and its copy-engine path (see icp_drive's
-                // result block: that path is where the host-solve pipeline's one-off multi-millisecond stalls came from)
-                PR_TRY(g->h_poses.ensure(sizeof(pr_mat4) * np));
-                std::memcpy(g->h_poses.p, poses_host + p0, sizeof(pr_mat4) * np);
-                void *hp = nullptr;
-                HIP_TRY(hipHostGetDevicePointer(&hp, g->h_poses.p, 0));
-                HIP_TRY(prk::launch_stage_words(hp, g->poses.p, sizeof(pr_mat4) * np, g->stream));
-            }
+            PR_TRY(stage_poses(poses_host + p0, np));
             if (opt.raster_mode == 1)
                 HIP_TRY(prk::launch_render_bands(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
                                                  g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
@@ -162,6 +165,58 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
         PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, crit,
                          results_host ? results_host + p0 : nullptr, results_dev ? results_dev + p0 : nullptr));
     }
+    return PR_OK;
+}
+
+// ---- render-and-compare scoring (pr_score_poses) ---------------------------------------------------------------------------
+// refine_impl's render (staged poses, model box, per-pose pixel boxes packed one behind the other) followed by one kernel that compares every
+// rendered box pixel with the scene frame.  Everything runs on the context's own stream and workspaces, which no asynchronous slot owns, so a
+// batch pending on a slot is neither waited for nor disturbed.  The scene is read as it is on every call: nothing derived from it is kept.
+int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
+               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host)
+{
+    if (tau < 0) { set_error("pr_score_poses: tau_mm must be >= 0 (got %d)", (int)tau); return PR_ERR_INVALID; }
+    if (!proj || W == 0 || H == 0 || (P && (!poses_host || !scene_dev || !scores_host || (!tris_dev && n_tris > 0)))) {
+        set_error("pr_score_poses: bad arguments"); return PR_ERR_INVALID;
+    }
+    if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
+    if (!roi_ok(roi, W, H)) { set_error("pr_score_poses: roi out of image"); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
+    if (P == 0) return PR_OK;
+    constexpr uint32_t kWords = sizeof(pr_pose_score) / sizeof(uint32_t);
+    static_assert(sizeof(pr_pose_score) == 32 && kWords == 8, "pr_pose_score: one 32-byte record");
+    const size_t img = (size_t)W * H;
+    const uint32_t chunk = depth_chunk(img, P);
+    PR_TRY(g->aabb.ensure(6 * sizeof(float)));
+    PR_TRY(g->aabb_keys.ensure(6 * sizeof(uint32_t)));
+    HIP_TRY(prk::launch_model_aabb(tris_dev, (uint32_t)n_tris, g->aabb_keys.as<uint32_t>(), g->aabb.as<float>(), nullptr, nullptr, g->stream));
+    for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
+        const uint32_t np = std::min(chunk, P - p0);
+        PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
+        PR_TRY(g->row_count.ensure(sizeof(uint32_t) * (size_t)H * np));
+        PR_TRY(g->row_off.ensure(sizeof(uint32_t) * (size_t)H * np));
+        PR_TRY(g->counts.ensure(sizeof(uint32_t) * np));
+        PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
+        PR_TRY(g->scores.ensure(sizeof(pr_pose_score) * np));
+        PR_TRY(g->h_scores.ensure(sizeof(pr_pose_score) * np));
+        uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
+        {
+            SpanGuard sp(kSpanRender);
+            PR_TRY(stage_poses(poses_host + p0, np));
+            HIP_TRY(prk::launch_render_boxes(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
+                                             g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
+                                             g->counts.as<uint32_t>(), W, H, *proj, roi, g->stream, /*compute_boxes=*/true, nullptr, nullptr, nullptr, 0, box_off));
+        }
+        // records zeroed by a kernel and read back through the pinned array by a kernel: no memset or copy commands on this path (see refine_impl)
+        HIP_TRY(prk::launch_fill_i32(g->scores.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
+        HIP_TRY(prk::launch_score_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
+                                        g->scores.as<uint32_t>(), g->stream));
+        void *hs = nullptr;
+        HIP_TRY(hipHostGetDevicePointer(&hs, g->h_scores.p, 0));
+        HIP_TRY(prk::launch_copy_words32(g->scores.p, hs, kWords * np, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        std::memcpy(scores_host + p0, g->h_scores.p, sizeof(pr_pose_score) * np);
+    }
+    drain_spans();
     return PR_OK;
 }
 
@@ -828,6 +883,13 @@ int pr_depth2cloud_u16(const uint16_t *depth_dev, uint32_t width, uint32_t heigh
 {
     PR_ENTER();
     return depth2cloud_impl<uint16_t>(depth_dev, width, height, K, stride, tl_x, tl_y, cloud_dev_out, n_points);
+}
+
+int pr_score_poses(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                   const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host)
+{
+    PR_ENTER();
+    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host);
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

@@ -285,6 +285,26 @@ int  pr_score_poses(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *p
  * clouds are in metres (icp.cu:249, depth/1000), poses in mm.  Product in pr_mat4_mul's order.  Host only. */
 void pr_refined_poses(const pr_result *results, const pr_mat4 *poses, uint32_t n, pr_mat4 *refined_out);
 
+/* ---- mixed batches: hypotheses of several meshes in one call ----------------------------------------------------------------------
+ * Hypothesis i is rendered with meshes[mesh_index_host[i]]; everything else is as in the single-mesh call.  For every i the depth image,
+ * the record, the cloud size and the score are byte for byte what pr_render, pr_refine_batch_roi or pr_score_poses return for that mesh
+ * and poses_host[i] with the same roi, scene, criteria and options.  Each mesh is its own device buffer (no concatenation); one pointer
+ * may appear more than once, and an empty mesh (n_tris == 0) gives what the single-mesh calls give for one.  The library groups the
+ * hypotheses by mesh (a stable sort), runs one batch -- one model-box pass over all meshes, one raster launch per chunk for all groups,
+ * one ICP drive -- and returns the outputs in the caller's order.  The fused render always uses the box raster: option "raster_mode" = 1
+ * (LDS bands) does not apply here (both modes give identical results).  Synchronous, on the calling thread's context; a batch pending on an
+ * asynchronous slot is left alone.  PR_ERR_INVALID, with nothing written, for n_meshes == 0, a null pointer or mesh_index_host[i] >=
+ * n_meshes with n_poses > 0, and for the single-mesh calls' frame, ROI and tau_mm checks; n_poses == 0 returns PR_OK and writes nothing. */
+typedef struct { const pr_triangle *tris_dev; size_t n_tris; } pr_mesh_ref;   /* one mesh on the device (16 B) */
+int  pr_render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, size_t n_poses,
+                     size_t width, size_t height, const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev_out);
+int  pr_refine_batch_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                           uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                           const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_host, uint32_t *cloud_sizes_host);
+int  pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                          uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                          int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

@@ -44,6 +44,11 @@ class Criteria(C.Structure):
     _fields_ = [("relative_fitness", C.c_float), ("relative_rmse", C.c_float), ("max_iteration", C.c_int)]
 
 
+class MeshRef(C.Structure):
+    """pr_mesh_ref: one mesh of a mixed batch (pr_*_multi)."""
+    _fields_ = [("tris_dev", C.c_void_p), ("n_tris", C.c_size_t)]
+
+
 class SceneProjDesc(C.Structure):
     _fields_ = [("width", C.c_uint64), ("height", C.c_uint64), ("max_dist_diff", C.c_float), ("K", C.c_float * 9),
                 ("pcd", C.c_void_p), ("normal", C.c_void_p)]
@@ -112,6 +117,9 @@ SIGNATURES = {
     "pr_refine_wait": (_i32, [_i32]),
     "pr_score_poses": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp]),
     "pr_refined_poses": (None, [_vp, _vp, _u32, _vp]),
+    "pr_render_multi": (_i32, [_vp, _u32, _vp, _vp, _sz, _sz, _sz, _vp, Roi, _vp]),
+    "pr_refine_batch_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, Roi, _vp, _vp]),
+    "pr_score_poses_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

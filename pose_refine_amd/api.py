@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, Criteria, KDNODE, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
+from ._lib import (COMM_ID_BYTES, Criteria, KDNODE, MeshRef, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -629,6 +629,104 @@ def rank_hypotheses(scores) -> np.ndarray:
     frac = np.where(empty, 0.0, inl.astype(np.float64) / np.where(empty, 1, den).astype(np.float64))
     idx = np.arange(len(sc), dtype=np.int64)
     return np.lexsort((idx, -inl, -frac, empty.astype(np.int8))).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------
+# mixed batches: hypotheses of several meshes in one call
+# ------------------------------------------------------------------------------------------------
+def _mesh_index(mesh_index, n_poses: int, n_meshes: int) -> np.ndarray:
+    """``mesh_index`` checked before anything reaches the library: integers, one per pose, each in [0, n_meshes)."""
+    a = np.asarray(mesh_index)
+    if a.ndim != 1 or len(a) != n_poses:
+        raise ValueError(f"mesh_index must hold one entry per pose: got shape {a.shape} for {n_poses} poses")
+    if n_poses and a.dtype.kind not in "iu":
+        raise ValueError(f"mesh_index must be an integer array, got {a.dtype}")
+    if n_poses and (a.min() < 0 or a.max() >= n_meshes):
+        raise ValueError(f"mesh_index values must lie in [0, {n_meshes}): got {int(a.min())} .. {int(a.max())}")
+    return np.ascontiguousarray(a, np.uint32)
+
+
+def _mesh_table(meshes):
+    """(pr_mesh_ref array, device buffers kept alive for the call) from a sequence of what ``render`` / ``refine_batch`` accept as ``tris``."""
+    devs = [_tris_dev(m) for m in meshes]
+    table = (MeshRef * max(1, len(devs)))(*[MeshRef(d.data() or None, d.size() // 9) for d in devs])
+    return table, devs
+
+
+def _multi_inputs(meshes, mesh_index, poses):
+    meshes = list(meshes)
+    poses = _f32(poses, (-1, 16))
+    idx = _mesh_index(mesh_index, len(poses), len(meshes))
+    if not meshes and len(poses):
+        raise ValueError("no meshes for the poses")
+    table, devs = _mesh_table(meshes)
+    return table, devs, idx, poses
+
+
+def render_multi(meshes, mesh_index, poses, width: int, height: int, proj, roi: Sequence[int] = (0, 0, 0, 0)) -> DeviceVector:
+    """``pr_render_multi``: ``render`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; images in pose order."""
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    rw, rh = (roi[2], roi[3]) if roi[2] > 0 and roi[3] > 0 else (width, height)
+    out = DeviceVector(len(poses) * rw * rh, np.int32)
+    pj = _f32(proj, -1)
+    check(_lib.load().pr_render_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi), out.data()))
+    return out
+
+
+def refine_batch_multi(meshes, mesh_index, poses, width: int, height: int, proj, K, scene,
+                       criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(), roi: Optional[Sequence[int]] = None):
+    """``pr_refine_batch_multi``: ``refine_batch`` for a batch whose pose i uses ``meshes[mesh_index[i]]`` (a ``Model``, a ``DeviceVector``
+    or a host triangle array each), in one call.  Returns (records[P], cloud sizes[P]) in pose order, each equal to what ``refine_batch``
+    gives that pose with its own mesh."""
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    pj, k = _f32(proj, -1), _f32(K, -1)
+    res = np.zeros(len(poses), RESULT)
+    sizes = np.zeros(len(poses), np.uint32)
+    d = scene.desc()
+    check(_lib.load().pr_refine_batch_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), ptr(k), scene.kind,
+                                            C.addressof(d), criteria.c(), Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(sizes)))
+    return res, sizes
+
+
+def _scene_depth_dev(scene_depth, width: int, height: int) -> DeviceVector:
+    if isinstance(scene_depth, DeviceVector):
+        sd = scene_depth
+    else:
+        arr = np.ascontiguousarray(scene_depth)
+        if arr.dtype not in (np.uint16, np.int32):
+            raise ValueError("scene depth must be CV_16U or CV_32S")
+        sd = DeviceVector.from_host(arr.reshape(-1))
+    if sd.dtype not in (np.uint16, np.int32):
+        raise ValueError("scene depth must be CV_16U or CV_32S")
+    if sd.size() != width * height:
+        raise ValueError(f"scene depth holds {sd.size()} values, expected {width} x {height}")
+    return sd
+
+
+def score_poses_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int,
+                      roi: Sequence[int] = (0, 0, 0, 0)) -> np.ndarray:
+    """``pr_score_poses_multi``: ``score_poses`` for a batch whose pose i uses ``meshes[mesh_index[i]]``.  SCORE[P] in pose order."""
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    out = np.zeros(len(poses), SCORE)
+    check(_lib.load().pr_score_poses_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                           sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out)))
+    return out
+
+
+def rank_hypotheses_per_mesh(scores, mesh_index) -> dict:
+    """``rank_hypotheses`` within each mesh of a mixed batch: {mesh: indices into the whole batch, best first}.  Only meshes that have
+    hypotheses appear."""
+    sc = np.asarray(scores)
+    idx = np.asarray(mesh_index)
+    if idx.ndim != 1 or len(idx) != len(sc):
+        raise ValueError(f"mesh_index must hold one entry per score: got shape {idx.shape} for {len(sc)} scores")
+    out = {}
+    for m in np.unique(idx):
+        members = np.flatnonzero(idx == m)
+        out[int(m)] = members[rank_hypotheses(sc[members])]
+    return out
 
 
 def eigen_slover_666(A, b) -> np.ndarray:

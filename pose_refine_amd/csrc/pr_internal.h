@@ -170,6 +170,26 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
                                PoseMeta *meta = nullptr, DevIcpState *st = nullptr, uint32_t *arrive = nullptr, uint32_t cloud_stride = 0,
                                const uint32_t *box_off = nullptr,    // box_off: the boxes packed into `depth` at these offsets (ints), each with its own pitch (fill_box_kernel)
                                const BatchCheck *check = nullptr);
+// Mixed batches (pr_*_multi): the hypotheses grouped by mesh.  One group of consecutive hypotheses [first, first + count) of a launch that share
+// a mesh; raster_multi_kernel's workgroups [first_wg, first_wg + tri_blocks * ceil(count / run)) are its (triangle block, pose run) pairs.
+// The host fills tris, n_tris, first and count; launch_raster_multi the rest.  48 bytes: staged in 16-byte words.
+struct RasterGroup {
+    const pr_triangle *tris;
+    uint32_t n_tris, first, count, run;
+    uint32_t tri_blocks, reserved0;
+    unsigned long long first_wg, reserved1;
+};
+static_assert(sizeof(RasterGroup) == 48, "RasterGroup: three 16-byte words");
+// keys: 6 x n_meshes words of scratch; aabb_out: 6 floats per mesh (launch_model_aabb's box for each mesh alone)
+hipError_t launch_model_aabb_multi(const pr_mesh_ref *meshes_dev, const pr_mesh_ref *meshes_host, uint32_t n_meshes, uint32_t *keys, float *aabb_out, hipStream_t s);
+// full frames (boxes null; image_of, if given: image of each hypothesis) or boxes as launch_render_boxes lays them out
+hipError_t launch_raster_multi(RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups, RasterGroup *groups_dev, const pr_mat4 *poses_dev,
+                               int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh,
+                               const int4 *boxes, const uint32_t *box_off, const uint32_t *image_of, hipStream_t s);
+hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
+                                     RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, uint32_t *row_count,
+                                     uint32_t *row_off, uint32_t *counts, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s,
+                                     const uint32_t *box_off);
 // verify.hip: every box pixel a hypothesis renders (launch_render_boxes' layout) against the scene frame (int32 or uint16, mm), added into
 // records[8 * i] (pr_pose_score words: visible, inlier, occluded, violation, missing, reserved, abs_err_sum lo / hi), which the caller zeroed
 hipError_t launch_score_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,

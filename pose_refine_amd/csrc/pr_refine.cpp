@@ -89,7 +89,120 @@ bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
     return true;
 }
 
-int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
+// ---- mixed batches (pr_*_multi): the hypotheses of several meshes in one call ---------------------------------------------------
+// The hypotheses grouped by mesh: a stable counting sort of the caller's indices.  Every mesh that has hypotheses is one group (in mesh
+// order); the batch runs in group order and its outputs go back to the caller's order.  Results do not depend on how a batch is composed
+// (each hypothesis equals its single-pose run), so the grouped batch gives every hypothesis what the single-mesh call gives it.
+struct MeshPlan {
+    std::vector<uint32_t> order;          // position in the grouped batch -> the caller's index
+    std::vector<uint32_t> box;            // position -> its group (= which of the groups' model boxes it uses)
+    std::vector<pr_mesh_ref> mesh;        // group -> mesh
+    std::vector<uint32_t> start;          // group -> first position; one more entry: the batch size
+};
+int plan_meshes(const char *fn, const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, size_t P, MeshPlan &pl)
+{
+    if (!meshes || n_meshes == 0 || !mesh_index) { set_error("%s: bad arguments (mesh table or mesh index missing)", fn); return PR_ERR_INVALID; }
+    for (uint32_t m = 0; m < n_meshes; ++m)
+        if (!meshes[m].tris_dev && meshes[m].n_tris > 0) { set_error("%s: mesh %u has %zu triangles and no array", fn, m, meshes[m].n_tris); return PR_ERR_INVALID; }
+    std::vector<uint32_t> first(n_meshes + 1, 0);
+    for (size_t i = 0; i < P; ++i) {
+        if (mesh_index[i] >= n_meshes) { set_error("%s: mesh_index[%zu] = %u, but there are %u meshes", fn, i, mesh_index[i], n_meshes); return PR_ERR_INVALID; }
+        first[mesh_index[i] + 1]++;
+    }
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        if (first[m + 1] > 0) { pl.mesh.push_back(meshes[m]); pl.start.push_back(first[m]); }
+        first[m + 1] += first[m];
+    }
+    pl.start.push_back((uint32_t)P);
+    std::vector<uint32_t> group_of(n_meshes, 0);
+    for (uint32_t k = 0, m = 0; m < n_meshes; ++m) if (first[m + 1] > first[m]) group_of[m] = k++;
+    pl.order.resize(P); pl.box.resize(P);
+    for (size_t i = 0; i < P; ++i) { const uint32_t j = first[mesh_index[i]]++; pl.order[j] = (uint32_t)i; pl.box[j] = group_of[mesh_index[i]]; }
+    return PR_OK;
+}
+// what the shared bodies of refine / score render: one mesh for every hypothesis, or a mixed batch in its plan's order
+struct MeshSource { const pr_triangle *tris; size_t n_tris; const MeshPlan *plan; };
+// the device (g->multi) and pinned (g->h_multi) layout of a mixed batch's tables: [meshes: 16 B per group][box index: 4 B per hypothesis of
+// a chunk][raster groups: one per group at most].  Staged through pinned memory by kernels, like the poses (stage_poses): no copy commands.
+struct MultiLayout { size_t box, groups, bytes; };
+MultiLayout multi_layout(size_t n_groups, size_t chunk)
+{
+    MultiLayout l;
+    l.box = n_groups * sizeof(pr_mesh_ref);
+    l.groups = l.box + ((chunk * sizeof(uint32_t) + 15) & ~(size_t)15);
+    l.bytes = l.groups + n_groups * sizeof(prk::RasterGroup);
+    return l;
+}
+// the model box(es) into g->aabb: 6 floats, or 6 per group of a mixed batch
+int model_boxes(const MeshSource &src, uint32_t chunk)
+{
+    if (!src.plan) {
+        PR_TRY(g->aabb.ensure(6 * sizeof(float)));
+        PR_TRY(g->aabb_keys.ensure(6 * sizeof(uint32_t)));
+        HIP_TRY(prk::launch_model_aabb(src.tris, (uint32_t)src.n_tris, g->aabb_keys.as<uint32_t>(), g->aabb.as<float>(), nullptr, nullptr, g->stream));
+        return PR_OK;
+    }
+    const MeshPlan &pl = *src.plan;
+    const uint32_t G = (uint32_t)pl.mesh.size();
+    const MultiLayout l = multi_layout(G, chunk);
+    PR_TRY(g->aabb.ensure(6 * sizeof(float) * G));
+    PR_TRY(g->aabb_keys.ensure(6 * sizeof(uint32_t) * G));
+    PR_TRY(g->multi.ensure(l.bytes));
+    PR_TRY(g->h_multi.ensure(l.bytes));
+    std::memcpy(g->h_multi.p, pl.mesh.data(), sizeof(pr_mesh_ref) * G);
+    void *hm = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&hm, g->h_multi.p, 0));
+    HIP_TRY(prk::launch_stage_words(hm, g->multi.p, sizeof(pr_mesh_ref) * G, g->stream));
+    HIP_TRY(prk::launch_model_aabb_multi(g->multi.as<pr_mesh_ref>(), pl.mesh.data(), G, g->aabb_keys.as<uint32_t>(), g->aabb.as<float>(), g->stream));
+    return PR_OK;
+}
+// the raster groups of positions [p0, p0 + np) of a mixed batch into `out` (positions relative to p0); returns how many
+uint32_t chunk_groups(const MeshPlan &pl, uint32_t p0, uint32_t np, prk::RasterGroup *out)
+{
+    uint32_t n = 0;
+    for (size_t k = 0; k + 1 < pl.start.size(); ++k) {
+        const uint32_t a = std::max(pl.start[k], p0), b = std::min(pl.start[k + 1], p0 + np);
+        if (a >= b) continue;
+        prk::RasterGroup gr{};
+        gr.tris = pl.mesh[k].tris_dev; gr.n_tris = (uint32_t)pl.mesh[k].n_tris; gr.first = a - p0; gr.count = b - a;
+        out[n++] = gr;
+    }
+    return n;
+}
+// chunk [p0, p0 + np) of a batch rendered into per-pose pixel boxes (raster + row counts + row scan), poses staged first.  box_off: the boxes
+// packed (kBoxPack) or null.  bands: the LDS-band raster (option raster_mode 1) -- single mesh only; a mixed batch always uses the box raster.
+int render_chunk(const MeshSource &src, const pr_mat4 *poses_host, uint32_t p0, uint32_t np, uint32_t chunk, uint32_t W, uint32_t H,
+                 const pr_mat4 *proj, pr_roi roi, uint32_t *box_off, bool bands)
+{
+    PR_TRY(stage_poses(poses_host + p0, np));
+    if (!src.plan) {
+        if (bands)
+            HIP_TRY(prk::launch_render_bands(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
+                                             g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
+                                             g->counts.as<uint32_t>(), W, H, *proj, roi, (uint32_t)g->n_cus, g->stream));
+        else
+            HIP_TRY(prk::launch_render_boxes(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
+                                             g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
+                                             g->counts.as<uint32_t>(), W, H, *proj, roi, g->stream, /*compute_boxes=*/true, nullptr, nullptr, nullptr, 0, box_off));
+        return PR_OK;
+    }
+    const MeshPlan &pl = *src.plan;
+    const MultiLayout l = multi_layout(pl.mesh.size(), chunk);
+    unsigned char *h = g->h_multi.as<unsigned char>(), *d = g->multi.as<unsigned char>();
+    void *hm = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&hm, g->h_multi.p, 0));
+    std::memcpy(h + l.box, pl.box.data() + p0, sizeof(uint32_t) * np);
+    HIP_TRY(prk::launch_stage_words(static_cast<unsigned char *>(hm) + l.box, d + l.box, sizeof(uint32_t) * np, g->stream));
+    prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
+    const uint32_t n_groups = chunk_groups(pl, p0, np, groups);
+    HIP_TRY(prk::launch_render_boxes_multi(g->aabb.as<float>(), reinterpret_cast<const uint32_t *>(d + l.box), groups, static_cast<unsigned char *>(hm) + l.groups,
+                                           n_groups, reinterpret_cast<prk::RasterGroup *>(d + l.groups), g->poses.as<pr_mat4>(), np, g->bbox.as<int4>(),
+                                           g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(), g->counts.as<uint32_t>(),
+                                           W, H, *proj, roi, g->stream, box_off));
+    return PR_OK;
+}
+
+int refine_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
                 const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
                 pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host)
 {
@@ -106,9 +219,7 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
     uint32_t chunk = depth_chunk(img, P);
     std::vector<uint32_t> start(chunk), count(chunk);
     // model box: recomputed from the triangle buffer on every call (one pass over the mesh; nothing is cached by address here)
-    PR_TRY(g->aabb.ensure(6 * sizeof(float)));
-    PR_TRY(g->aabb_keys.ensure(6 * sizeof(uint32_t)));
-    HIP_TRY(prk::launch_model_aabb(tris_dev, (uint32_t)n_tris, g->aabb_keys.as<uint32_t>(), g->aabb.as<float>(), nullptr, nullptr, g->stream));
+    PR_TRY(model_boxes(src, chunk));
     for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
         const uint32_t np = std::min(chunk, P - p0);
         PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
@@ -119,18 +230,10 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
         uint32_t *h_counts = g->h_counts.as<uint32_t>();
         // per-pose pixel boxes; raster + row counts + row scan
         PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));   // boxes, then the offsets of the packed boxes (box_pack_offsets_kernel)
-        uint32_t *box_off = (prk::kBoxPack && opt.raster_mode != 1) ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
+        uint32_t *box_off = (prk::kBoxPack && (src.plan || opt.raster_mode != 1)) ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
         {
             SpanGuard sp(kSpanRender);
-            PR_TRY(stage_poses(poses_host + p0, np));
-            if (opt.raster_mode == 1)
-                HIP_TRY(prk::launch_render_bands(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
-                                                 g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
-                                                 g->counts.as<uint32_t>(), W, H, *proj, roi, (uint32_t)g->n_cus, g->stream));
-            else
-                HIP_TRY(prk::launch_render_boxes(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
-                                                 g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
-                                                 g->counts.as<uint32_t>(), W, H, *proj, roi, g->stream, /*compute_boxes=*/true, nullptr, nullptr, nullptr, 0, box_off));
+            PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, proj, roi, box_off, !src.plan && opt.raster_mode == 1));
         }
         {   // the cloud sizes come back through a kernel's stores into the pinned array, not through a copy command (see icp_drive's result block)
             void *hc = nullptr;
@@ -167,16 +270,22 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
     }
     return PR_OK;
 }
+int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
+                const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
+                pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host)
+{
+    return refine_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, K, scene_kind, scene, crit, roi, results_host, results_dev, sizes_host);
+}
 
 // ---- render-and-compare scoring (pr_score_poses) ---------------------------------------------------------------------------
 // refine_impl's render (staged poses, model box, per-pose pixel boxes packed one behind the other) followed by one kernel that compares every
 // rendered box pixel with the scene frame.  Everything runs on the context's own stream and workspaces, which no asynchronous slot owns, so a
 // batch pending on a slot is neither waited for nor disturbed.  The scene is read as it is on every call: nothing derived from it is kept.
-int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
+int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
                pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host)
 {
     if (tau < 0) { set_error("pr_score_poses: tau_mm must be >= 0 (got %d)", (int)tau); return PR_ERR_INVALID; }
-    if (!proj || W == 0 || H == 0 || (P && (!poses_host || !scene_dev || !scores_host || (!tris_dev && n_tris > 0)))) {
+    if (!proj || W == 0 || H == 0 || (P && (!poses_host || !scene_dev || !scores_host || (!src.tris && src.n_tris > 0)))) {
         set_error("pr_score_poses: bad arguments"); return PR_ERR_INVALID;
     }
     if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
@@ -186,9 +295,7 @@ int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_
     static_assert(sizeof(pr_pose_score) == 32 && kWords == 8, "pr_pose_score: one 32-byte record");
     const size_t img = (size_t)W * H;
     const uint32_t chunk = depth_chunk(img, P);
-    PR_TRY(g->aabb.ensure(6 * sizeof(float)));
-    PR_TRY(g->aabb_keys.ensure(6 * sizeof(uint32_t)));
-    HIP_TRY(prk::launch_model_aabb(tris_dev, (uint32_t)n_tris, g->aabb_keys.as<uint32_t>(), g->aabb.as<float>(), nullptr, nullptr, g->stream));
+    PR_TRY(model_boxes(src, chunk));
     for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
         const uint32_t np = std::min(chunk, P - p0);
         PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
@@ -201,10 +308,7 @@ int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_
         uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
         {
             SpanGuard sp(kSpanRender);
-            PR_TRY(stage_poses(poses_host + p0, np));
-            HIP_TRY(prk::launch_render_boxes(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
-                                             g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
-                                             g->counts.as<uint32_t>(), W, H, *proj, roi, g->stream, /*compute_boxes=*/true, nullptr, nullptr, nullptr, 0, box_off));
+            PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, proj, roi, box_off, /*bands=*/false));
         }
         // records zeroed by a kernel and read back through the pinned array by a kernel: no memset or copy commands on this path (see refine_impl)
         HIP_TRY(prk::launch_fill_i32(g->scores.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
@@ -217,6 +321,89 @@ int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_
         std::memcpy(scores_host + p0, g->h_scores.p, sizeof(pr_pose_score) * np);
     }
     drain_spans();
+    return PR_OK;
+}
+int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
+               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host)
+{
+    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host);
+}
+
+// ---- mixed batches: the entry points' bodies (grouped batch in, outputs scattered back to the caller's order) -----------------------
+std::vector<pr_mat4> grouped_poses(const MeshPlan &pl, const pr_mat4 *poses_host)
+{
+    std::vector<pr_mat4> out(pl.order.size());
+    for (size_t j = 0; j < out.size(); ++j) out[j] = poses_host[pl.order[j]];
+    return out;
+}
+
+int refine_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
+                 const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_host,
+                 uint32_t *sizes_host)
+{
+    if (P == 0) return PR_OK;
+    if (!results_host || !poses_host || !proj || !K || !scene) { set_error("pr_refine_batch_multi: bad arguments"); return PR_ERR_INVALID; }
+    if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
+    if (W == 0 || H == 0 || !frame_size_ok(W, H) || !roi_ok(roi, W, H)) { if (W == 0 || H == 0) set_error("pr_refine_batch_multi: bad arguments"); return PR_ERR_INVALID; }
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_refine_batch_multi", meshes, n_meshes, mesh_index, P, pl));
+    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
+    std::vector<pr_result> res(P);
+    std::vector<uint32_t> sizes(P);
+    PR_TRY(refine_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, K, scene_kind, scene, crit, roi, res.data(), nullptr, sizes.data()));
+    for (uint32_t j = 0; j < P; ++j) {
+        results_host[pl.order[j]] = res[j];
+        if (sizes_host) sizes_host[pl.order[j]] = sizes[j];
+    }
+    return PR_OK;
+}
+
+int score_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
+                const pr_mat4 *proj, pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host)
+{
+    // the single-mesh call's checks first (tau, frame, ROI, pointers), with no hypotheses
+    PR_TRY(score_core(MeshSource{ nullptr, 0, nullptr }, poses_host, 0, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host));
+    if (P == 0) return PR_OK;
+    if (!poses_host || !scene_dev || !scores_host) { set_error("pr_score_poses_multi: bad arguments"); return PR_ERR_INVALID; }
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_score_poses_multi", meshes, n_meshes, mesh_index, P, pl));
+    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
+    std::vector<pr_pose_score> sc(P);
+    PR_TRY(score_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, roi, scene_dev, scene_i32, tau, sc.data()));
+    for (uint32_t j = 0; j < P; ++j) scores_host[pl.order[j]] = sc[j];
+    return PR_OK;
+}
+
+// render_impl for a mixed batch: full frames (or the ROI) in the caller's order -- the raster writes hypothesis j of the grouped batch into image order[j]
+int render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, size_t P, size_t W, size_t H,
+                 const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev)
+{
+    PR_TRY(render_impl(nullptr, 0, poses_host, 0, W, H, proj, roi, depth_dev, true));     // the single-mesh call's checks, with no hypotheses
+    if (P == 0) return PR_OK;
+    if (!poses_host || !depth_dev) { set_error("pr_render_multi: bad arguments"); return PR_ERR_INVALID; }
+    if (P > 0xffffffffull) { set_error("pr_render_multi: more than 2^32 hypotheses"); return PR_ERR_INVALID; }
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_render_multi", meshes, n_meshes, mesh_index, P, pl));
+    const size_t rw = (roi.width > 0 && roi.height > 0) ? (size_t)roi.width : W, rh = (roi.width > 0 && roi.height > 0) ? (size_t)roi.height : H;
+    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
+    SpanGuard sp(kSpanRender);
+    PR_TRY(stage_poses(poses.data(), P));
+    const uint32_t G = (uint32_t)pl.mesh.size();
+    const MultiLayout l = multi_layout(G, P);                      // the box-index slot holds the image of every hypothesis here
+    PR_TRY(g->multi.ensure(l.bytes));
+    PR_TRY(g->h_multi.ensure(l.bytes));
+    unsigned char *h = g->h_multi.as<unsigned char>(), *d = g->multi.as<unsigned char>();
+    void *hm = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&hm, g->h_multi.p, 0));
+    std::memcpy(h + l.box, pl.order.data(), sizeof(uint32_t) * P);
+    HIP_TRY(prk::launch_stage_words(static_cast<unsigned char *>(hm) + l.box, d + l.box, sizeof(uint32_t) * P, g->stream));
+    HIP_TRY(prk::launch_fill_i32(depth_dev, P * rw * rh, INT32_MAX, g->stream));
+    prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
+    const uint32_t n_groups = chunk_groups(pl, 0, (uint32_t)P, groups);
+    HIP_TRY(prk::launch_raster_multi(groups, static_cast<unsigned char *>(hm) + l.groups, n_groups, reinterpret_cast<prk::RasterGroup *>(d + l.groups),
+                                     g->poses.as<pr_mat4>(), depth_dev, (uint32_t)W, (uint32_t)H, *proj, roi, (uint32_t)rw, (uint32_t)rh,
+                                     nullptr, nullptr, reinterpret_cast<const uint32_t *>(d + l.box), g->stream));
+    HIP_TRY(prk::launch_max2zero(depth_dev, P * rw * rh, g->stream));
     return PR_OK;
 }
 
@@ -890,6 +1077,33 @@ int pr_score_poses(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *po
 {
     PR_ENTER();
     return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host);
+}
+
+int pr_render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, size_t n_poses,
+                    size_t width, size_t height, const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev_out)
+{
+    PR_ENTER();
+    if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * ((roi.width > 0 && roi.height > 0) ? (size_t)roi.width * roi.height : width * height));
+    PR_TRY(render_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, depth_dev_out));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    drain_spans();
+    return PR_OK;
+}
+
+int pr_refine_batch_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                          uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                          const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_host, uint32_t *cloud_sizes_host)
+{
+    PR_ENTER();
+    return refine_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene, crit, roi, results_host, cloud_sizes_host);
+}
+
+int pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                         uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                         int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host)
+{
+    PR_ENTER();
+    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host);
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

@@ -271,7 +271,8 @@ struct Ctx {
     // workspaces
     DevBuf aabb, aabb_keys, bbox, poses, depth, row_count, row_off, counts, cloud, meta, partial, sums, nn_prev, dstate, dresults, arrive, conv16, conv8, kd_scratch, kd_tmp, nn_full;
     DevBuf scores;                   // pr_score_poses: the records of a chunk
-    PinBuf h_sums, h_meta, h_counts, h_results, h_dstate, h_poses, h_flags, h_scores;
+    DevBuf multi;                    // mixed batches (pr_*_multi): mesh table, box index / image of each hypothesis, raster groups
+    PinBuf h_sums, h_meta, h_counts, h_results, h_dstate, h_poses, h_flags, h_scores, h_multi;
     PackedCache packed;              // synchronous paths (the asynchronous slots keep their own)
     // kd-tree scenes: what the library derives from a scene (traversal records, wide records, pixel grid) -- kNNSets sets, so that with a NEW scene per
     // frame the batch of one asynchronous slot keeps the set it runs on while the next frame's records are derived into the other (round 5: one set

@@ -249,6 +249,68 @@ __device__ __forceinline__ void raster_batch_check(const float (&tv)[9], bool ha
     __syncthreads();
 }
 
+// the lane's triangle of a raster workgroup (zeros past the end of the mesh)
+__device__ __forceinline__ void load_triangle(const pr_triangle *__restrict__ tris, uint32_t n_tris, uint32_t ti, float (&tv)[9])
+{
+    if (ti < n_tris) {
+        const float *src = reinterpret_cast<const float *>(tris + ti);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) tv[k] = src[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) tv[k] = 0.0f;
+    }
+}
+
+// What one raster_kernel workgroup does with its 256 triangles (tv, lane triangle ti of n_tris), restated line for line for
+// raster_multi_kernel: hypotheses [run * pose_run, +pose_run) of the n_poses at `poses`.  Image of hypothesis `by`: depth + image_of[by] *
+// rw * rh when image_of is given (the caller's order of a mixed batch), depth + by * rw * rh otherwise; packed boxes (box_off): their own
+// pitch.  raster_kernel keeps its own copy: calling this from it reschedules its code, which stays as measured.
+__device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, uint32_t n_tris, uint32_t run,
+                                            const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
+                                            uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi,
+                                            uint32_t rw, uint32_t rh, const int4 *__restrict__ boxes, uint32_t n_poses, uint32_t pose_run,
+                                            const uint32_t *__restrict__ box_off, const uint32_t *__restrict__ image_of,
+                                            float (*sh)[kSetupWords][64], uint32_t (*shq)[192])
+{
+    const uint32_t wave = threadIdx.x >> 6;
+    float rmin0 = 0.0f, rmin1 = 0.0f, rmax0 = (float)(width - 1), rmax1 = (float)(height - 1);
+    if (roi.width > 0 && roi.height > 0) {                       // renderer.cu:106-113 (image is flipped in y)
+        rmin0 = (float)roi.x;
+        rmin1 = (float)((unsigned long long)(height - 1) - (unsigned long long)(long long)(roi.y + roi.height - 1));
+        rmax0 = (float)((roi.x + roi.width) - 1);
+        rmax1 = (float)((unsigned long long)(height - 1) - (unsigned long long)(long long)roi.y);
+    }
+    for (uint32_t k = 0; k < pose_run; ++k) {
+        const uint32_t by = run * pose_run + k;
+        if (by >= n_poses) break;
+        const float *M = poses[by].m;                            // wave-uniform -> scalar loads
+        int32_t *img = depth + (size_t)(image_of ? image_of[by] : by) * rw * rh;
+        float cmin0 = rmin0, cmin1 = rmin1, cmax0 = rmax0, cmax1 = rmax1;
+        uint32_t pitch = rw;                                     // image row pitch; packed boxes (box_off): the box's own width, origin at its top-left pixel
+        if (boxes) {                                             // fused path: the hypothesis' pixel box (already intersected with the caller's ROI,
+            const int4 bb = boxes[by];                           // if any); a conservative box clips nothing, an ROI clips like renderer.cu:106-113
+            cmin0 = (float)bb.x; cmin1 = (float)bb.y; cmax0 = (float)bb.z; cmax1 = (float)bb.w;
+            if (box_off) {
+                pitch = (uint32_t)max(bb.z - bb.x + 1, 0);
+                // pixel (x, image row r) of the box lives at off + (r - r0) * pitch + (x - bb.x), r0 = height - 1 - bb.w: fold the origin into the base
+                img = depth + box_off[by] - ((ptrdiff_t)((int)height - 1 - bb.w) * (ptrdiff_t)pitch + (ptrdiff_t)bb.x);
+            }
+        }
+        TriSetup t;
+        int n = 0;
+        if (ti < n_tris) {
+            tri_setup(tv, M, proj, width, height, cmin0, cmin1, cmax0, cmax1, t);
+            n = t.nx * t.ny;
+        } else { t.nx = t.ny = 0; t.x0 = t.y0 = 0; t.base_inv = 0; for (int j = 0; j < 3; ++j) t.px[j] = t.py[j] = t.w3[j] = 0; }
+        wave_raster(t, n, sh[wave], shq[wave], [&](int x, int y, int d) {
+            const uint32_t xw = (uint32_t)(x - roi.x);
+            const uint32_t yw = (uint32_t)((int)height - 1 - y - roi.y);
+            atomicMin(&img[xw + (size_t)yw * pitch], d);
+        });
+    }
+}
+
 // A workgroup keeps its 256 triangles in registers and walks `pose_run` consecutive hypotheses with them: a mesh that does not fit
 // the L2 (the 1 M-triangle mesh of BASELINE configs[4]: 36 MB) is then streamed from the Infinity Cache / HBM once per pose_run
 // hypotheses instead of once per hypothesis -- at 128 hypotheses that stream (4.6 GB, 3.2 TB/s) was what bounded the kernel.
@@ -310,6 +372,39 @@ __global__ __launch_bounds__(256) void raster_kernel(const pr_triangle *__restri
     }
 }
 
+// A mixed batch (hypotheses of several meshes) in one launch.  The hypotheses come grouped by mesh; group g owns the 1-D workgroup
+// range [first_wg, first_wg + tri_blocks * ceil(count / run)) and each of its workgroups does exactly what raster_kernel's workgroup
+// (triangle block, pose run) does for that group's mesh and hypotheses -- so a 1 M-triangle mesh next to 5 k-triangle ones launches
+// no empty workgroups, and every depth is the same atomicMin of the same fragment as in a single-mesh launch.  The group of a workgroup:
+// a wave-uniform binary search over the groups' first workgroups (scalar loads).  Workgroups beyond the grid loop (64-bit totals).
+__global__ __launch_bounds__(256) void raster_multi_kernel(const RasterGroup *__restrict__ groups, uint32_t n_groups, unsigned long long total_wg,
+                                                           const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
+                                                           uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi, uint32_t rw, uint32_t rh,
+                                                           const int4 *__restrict__ boxes, const uint32_t *__restrict__ box_off,
+                                                           const uint32_t *__restrict__ image_of)
+{
+    __shared__ float sh[4][kSetupWords][64];
+    __shared__ uint32_t shq[4][192];
+    for (unsigned long long wg = blockIdx.x; wg < total_wg; wg += gridDim.x) {
+        uint32_t lo = 0, hi = n_groups;                          // groups[lo].first_wg <= wg < groups[hi].first_wg
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (groups[mid].first_wg <= wg) lo = mid; else hi = mid;
+        }
+        lo = __builtin_amdgcn_readfirstlane(lo);
+        const RasterGroup &gr = groups[lo];
+        const unsigned long long local = wg - gr.first_wg;
+        const uint32_t run = (uint32_t)(local / gr.tri_blocks), block = (uint32_t)(local - (unsigned long long)run * gr.tri_blocks);
+        const uint32_t ti = block * 256 + threadIdx.x;
+        float tv[9];
+        load_triangle(gr.tris, gr.n_tris, ti, tv);
+        // full frames without a caller order: the group's images follow one another from its first hypothesis on
+        int32_t *base = (image_of || box_off) ? depth : depth + (size_t)gr.first * rw * rh;
+        raster_runs(tv, ti, gr.n_tris, run, poses + gr.first, base, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
+                    gr.count, gr.run, box_off ? box_off + gr.first : nullptr, image_of ? image_of + gr.first : nullptr, sh, shq);
+    }
+}
+
 // ================================================================================================
 //  fused-path raster: per-hypothesis screen bounding box + LDS depth bands (no global atomics, no
 //  full-frame clear).  The depth values are produced by exactly the arithmetic of raster_kernel;
@@ -356,12 +451,78 @@ __global__ void model_aabb_finish_kernel(const uint32_t *__restrict__ keys, floa
     }
     if (flag_out) *flag_out = differs ? 1u : 0u;
 }
+// The boxes of several meshes in one launch: blockIdx.y (grid-stride) = mesh, keys[6 * mesh ...] in model_aabb_kernel's encoding.
+// Minima and maxima are exact in any order, so each box equals model_aabb_kernel's for that mesh alone.
+__global__ __launch_bounds__(256) void model_aabb_multi_kernel(const pr_mesh_ref *__restrict__ meshes, uint32_t n_meshes, uint32_t *__restrict__ keys)
+{
+    __shared__ float red[4][6];
+    for (uint32_t m = blockIdx.y; m < n_meshes; m += gridDim.y) {
+        const float *v = reinterpret_cast<const float *>(meshes[m].tris_dev);
+        const uint32_t n_tris = (uint32_t)meshes[m].n_tris;
+        float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+        for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n_tris * 3u; i += gridDim.x * 256) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { const float c = v[(size_t)i * 3 + a]; lo[a] = fminf(lo[a], c); hi[a] = fmaxf(hi[a], c); }
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            for (int off = 32; off > 0; off >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], off)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off)); }
+        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            float r = red[0][threadIdx.x];
+            for (int w = 1; w < 4; ++w) r = (threadIdx.x < 3) ? fminf(r, red[w][threadIdx.x]) : fmaxf(r, red[w][threadIdx.x]);
+            atomicMin(&keys[6 * (size_t)m + threadIdx.x], (threadIdx.x < 3) ? f32_key(r) : ~f32_key(r));
+        }
+        __syncthreads();                                             // red is rewritten for the next mesh
+    }
+}
+// keys -> floats, one lane per (mesh, axis): model_aabb_finish_kernel's conversion (an empty mesh: +FLT_MAX / -FLT_MAX)
+__global__ __launch_bounds__(256) void model_aabb_multi_finish_kernel(const uint32_t *__restrict__ keys, uint32_t n_words, float *__restrict__ aabb_out)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_words) return;
+    const uint32_t a = i % 6, k = keys[i];
+    float v = (a < 3) ? key_f32(k) : key_f32(~k);
+    if (k == 0xffffffffu) v = (a < 3) ? FLT_MAX : -FLT_MAX;
+    aabb_out[i] = v;
+}
 
 // Conservative pixel box {x0,y0,x1,y1} (raster coordinates, y not yet flipped) of the mesh under
 // every pose: the 8 box corners go through the same model / projection / viewport arithmetic as
 // the vertices; the projection of any point of the box lies in the hull of the projected corners
 // as long as all of them are in front of the camera, and 2 pixels of padding cover float rounding.
 // Any corner at or behind the camera plane -> the whole frame.
+// pose_bbox_kernel's box of one pose, operation for operation
+__device__ __forceinline__ int4 pose_pixel_box(const float *__restrict__ aabb, const float *M, const pr_mat4 &proj, uint32_t width, uint32_t height, pr_roi roi)
+{
+    float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
+    bool all_front = true;
+    for (int c = 0; c < 8; ++c) {
+        const float x = aabb[(c & 1) ? 3 : 0], y = aabb[(c & 2) ? 4 : 1], z = aabb[(c & 4) ? 5 : 2];
+        const float lx = M[0] * x + M[1] * y + M[2] * z + M[3];
+        const float ly = M[4] * x + M[5] * y + M[6] * z + M[7];
+        const float lz = M[8] * x + M[9] * y + M[10] * z + M[11];
+        if (!(lz > 1e-3f)) all_front = false;
+        const float cxp = proj.m[0] * lx + proj.m[1] * ly + proj.m[2] * lz + proj.m[3];
+        const float cyp = proj.m[4] * lx + proj.m[5] * ly + proj.m[6] * lz + proj.m[7];
+        const float sx = cxp / lz * (float)width / 2.0f + (float)width / 2.0f;
+        const float sy = cyp / lz * (float)height / 2.0f + (float)height / 2.0f;
+        mnx = fminf(mnx, sx); mxx = fmaxf(mxx, sx); mny = fminf(mny, sy); mxy = fmaxf(mxy, sy);
+    }
+    int x0 = 0, y0 = 0, x1 = (int)width - 1, y1 = (int)height - 1;
+    const bool finite = (mnx > -1e8f) && (mxx < 1e8f) && (mny > -1e8f) && (mxy < 1e8f);
+    if (all_front && finite) {
+        x0 = max(0, (int)floorf(mnx) - 2);  x1 = min((int)width - 1, (int)ceilf(mxx) + 2);
+        y0 = max(0, (int)floorf(mny) - 2);  y1 = min((int)height - 1, (int)ceilf(mxy) + 2);
+    }
+    if (roi.width > 0 && roi.height > 0) {                       // renderer.cu:106-113: the ROI is given in image rows, the raster runs flipped
+        x0 = max(x0, roi.x);  x1 = min(x1, roi.x + roi.width - 1);
+        y0 = max(y0, (int)height - 1 - (roi.y + roi.height - 1));  y1 = min(y1, (int)height - 1 - roi.y);
+    }
+    return make_int4(x0, y0, x1, y1);
+}
 __global__ __launch_bounds__(256) void pose_bbox_kernel(const float *__restrict__ aabb, const pr_mat4 *__restrict__ poses, uint32_t n_poses,
                                                         pr_mat4 proj, uint32_t width, uint32_t height, pr_roi roi, int4 *__restrict__ bbox)
 {
@@ -393,6 +554,16 @@ __global__ __launch_bounds__(256) void pose_bbox_kernel(const float *__restrict_
         y0 = max(y0, (int)height - 1 - (roi.y + roi.height - 1));  y1 = min(y1, (int)height - 1 - roi.y);
     }
     bbox[p] = make_int4(x0, y0, x1, y1);
+}
+// the same box for a mixed batch: hypothesis p uses the box of its own mesh, aabbs[6 * box_index[p] ...] (pose_bbox_kernel's arithmetic,
+// pose_pixel_box; pose_bbox_kernel keeps its own copy so that its code stays as it is)
+__global__ __launch_bounds__(256) void pose_bbox_multi_kernel(const float *__restrict__ aabbs, const uint32_t *__restrict__ box_index,
+                                                              const pr_mat4 *__restrict__ poses, uint32_t n_poses, pr_mat4 proj, uint32_t width,
+                                                              uint32_t height, pr_roi roi, int4 *__restrict__ bbox)
+{
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_poses) return;
+    bbox[p] = pose_pixel_box(aabbs + 6 * (size_t)box_index[p], poses[p].m, proj, width, height, roi);
 }
 
 // INT_MAX-fill and per-row valid counts restricted to each hypothesis' pixel box (image rows are
@@ -663,6 +834,77 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
     }
     if (meta) { hipError_t e = launch_d2c_scan_init(row_count, height, row_off, counts, n_poses, meta, st, arrive, cloud_stride, s); if (e != hipSuccess) return e; }
     else { hipError_t e = launch_d2c_scan(row_count, height, row_off, counts, n_poses, s); if (e != hipSuccess) return e; }
+    return hipGetLastError();
+}
+
+// ---- mixed batches (hypotheses of several meshes in one call) -----------------------------------------------------------------------
+hipError_t launch_model_aabb_multi(const pr_mesh_ref *meshes_dev, const pr_mesh_ref *meshes_host, uint32_t n_meshes, uint32_t *keys, float *aabb_out, hipStream_t s)
+{
+    if (n_meshes == 0) return hipSuccess;
+    hipError_t e = launch_fill_i32(reinterpret_cast<int32_t *>(keys), 6 * (size_t)n_meshes, -1, s);     // all ones: no copy or fill command
+    if (e != hipSuccess) return e;
+    uint32_t most = 0;
+    for (uint32_t m = 0; m < n_meshes; ++m) if ((uint32_t)meshes_host[m].n_tris > most) most = (uint32_t)meshes_host[m].n_tris;
+    if (most > 0) {
+        const uint32_t blocks = (most * 3u + 2047u) / 2048u;               // as launch_model_aabb, sized by the largest mesh
+        hipLaunchKernelGGL(model_aabb_multi_kernel, dim3(blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks), n_meshes < 65535 ? n_meshes : 65535), dim3(256), 0, s,
+                           meshes_dev, n_meshes, keys);
+    }
+    const uint32_t words = 6 * n_meshes;
+    hipLaunchKernelGGL(model_aabb_multi_finish_kernel, dim3((words + 255) / 256), dim3(256), 0, s, keys, words, aabb_out);
+    return hipGetLastError();
+}
+
+// groups_host (pinned; groups_mapped = the same memory as the device sees it): tris, n_tris, first, count of each group of consecutive
+// hypotheses with one mesh.  Completed here (empty groups dropped, run, triangle blocks, first workgroup), staged to groups_dev, launched.
+hipError_t launch_raster_multi(RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups, RasterGroup *groups_dev, const pr_mat4 *poses_dev,
+                               int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh,
+                               const int4 *boxes, const uint32_t *box_off, const uint32_t *image_of, hipStream_t s)
+{
+    uint32_t n = 0;
+    unsigned long long total = 0;
+    for (uint32_t i = 0; i < n_groups; ++i) {
+        RasterGroup gr = groups_host[i];
+        if (gr.n_tris == 0 || gr.count == 0) continue;             // an empty mesh renders nothing
+        gr.run = raster_pose_run(gr.n_tris, gr.count);
+        gr.tri_blocks = (gr.n_tris + 255) / 256;
+        gr.first_wg = total;
+        total += (unsigned long long)gr.tri_blocks * ((gr.count + gr.run - 1) / gr.run);
+        groups_host[n++] = gr;
+    }
+    if (n == 0) return hipSuccess;
+    hipError_t e = launch_stage_words(groups_mapped, groups_dev, sizeof(RasterGroup) * n, s);
+    if (e != hipSuccess) return e;
+    const unsigned long long grid = total < (1ull << 22) ? total : (1ull << 22);
+    hipLaunchKernelGGL(raster_multi_kernel, dim3((uint32_t)grid), dim3(256), 0, s, (const RasterGroup *)groups_dev, n, total, poses_dev, depth,
+                       width, height, proj, roi, rw, rh, boxes, box_off, image_of);
+    return hipGetLastError();
+}
+
+// launch_render_boxes (compute_boxes, no per-batch checks) for a mixed batch: hypothesis p takes the box of mesh box_index[p] (aabbs, 6 floats
+// each) and the raster is one raster_multi_kernel launch over all groups
+hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
+                                     RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, uint32_t *row_count,
+                                     uint32_t *row_off, uint32_t *counts, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s,
+                                     const uint32_t *box_off)
+{
+    if (n_poses == 0) return hipSuccess;
+    hipLaunchKernelGGL(pose_bbox_multi_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabbs, box_index, poses_dev, n_poses, proj, width, height, roi, bbox);
+    if (box_off && kBoxPack) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, (const int4 *)bbox, n_poses, const_cast<uint32_t *>(box_off));
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
+        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
+        hipLaunchKernelGGL(fill_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
+                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, box_off ? box_off + p0 : nullptr);
+    }
+    const pr_roi none{ 0, 0, 0, 0 };
+    { hipError_t e = launch_raster_multi(groups_host, groups_mapped, n_groups, groups_dev, poses_dev, depth, width, height, proj, none, width, height,
+                                         bbox, box_off, nullptr, s); if (e != hipSuccess) return e; }
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
+        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
+        hipLaunchKernelGGL(count_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
+                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, row_count + (size_t)p0 * height, box_off ? box_off + p0 : nullptr);
+    }
+    { hipError_t e = launch_d2c_scan(row_count, height, row_off, counts, n_poses, s); if (e != hipSuccess) return e; }
     return hipGetLastError();
 }
 

@@ -1,0 +1,51 @@
+// pose_box.h -- the conservative pixel box of a mesh under one pose.  The same source is compiled for the device (pose_bbox_kernel,
+// pose_bbox_multi_kernel: PR_HD = __host__ __device__) and for the host (the asynchronous path sizes a batch with it before anything of
+// the batch has run); with contraction disabled both builds produce the same box.
+#pragma once
+#include <float.h>
+#include <math.h>
+
+#include "pr_internal.h"
+
+#ifndef PR_HD
+#define PR_HD
+#endif
+
+namespace prk {
+
+// {x0,y0,x1,y1} (raster coordinates, y not yet flipped) of the mesh box `aabb` {minx,miny,minz,maxx,maxy,maxz} under the model matrix M:
+// the 8 box corners go through the same model / projection / viewport arithmetic as the vertices; the projection of any point of the box
+// lies in the hull of the projected corners as long as all of them are in front of the camera, and 2 pixels of padding cover float
+// rounding.  Any corner at or behind the camera plane -> the whole frame.
+PR_HD inline int4 pose_pixel_box(const float *aabb, const float *M, const pr_mat4 &proj, uint32_t width, uint32_t height, pr_roi roi)
+{
+    float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
+    bool all_front = true;
+    for (int c = 0; c < 8; ++c) {
+        const float x = aabb[(c & 1) ? 3 : 0], y = aabb[(c & 2) ? 4 : 1], z = aabb[(c & 4) ? 5 : 2];
+        const float lx = M[0] * x + M[1] * y + M[2] * z + M[3];
+        const float ly = M[4] * x + M[5] * y + M[6] * z + M[7];
+        const float lz = M[8] * x + M[9] * y + M[10] * z + M[11];
+        if (!(lz > 1e-3f)) all_front = false;
+        const float cxp = proj.m[0] * lx + proj.m[1] * ly + proj.m[2] * lz + proj.m[3];
+        const float cyp = proj.m[4] * lx + proj.m[5] * ly + proj.m[6] * lz + proj.m[7];
+        const float sx = cxp / lz * (float)width / 2.0f + (float)width / 2.0f;
+        const float sy = cyp / lz * (float)height / 2.0f + (float)height / 2.0f;
+        mnx = fminf(mnx, sx); mxx = fmaxf(mxx, sx); mny = fminf(mny, sy); mxy = fmaxf(mxy, sy);
+    }
+    auto imax = [](int a, int b) { return a > b ? a : b; };
+    auto imin = [](int a, int b) { return a < b ? a : b; };
+    int x0 = 0, y0 = 0, x1 = (int)width - 1, y1 = (int)height - 1;
+    const bool finite = (mnx > -1e8f) && (mxx < 1e8f) && (mny > -1e8f) && (mxy < 1e8f);
+    if (all_front && finite) {
+        x0 = imax(0, (int)floorf(mnx) - 2);  x1 = imin((int)width - 1, (int)ceilf(mxx) + 2);
+        y0 = imax(0, (int)floorf(mny) - 2);  y1 = imin((int)height - 1, (int)ceilf(mxy) + 2);
+    }
+    if (roi.width > 0 && roi.height > 0) {                       // renderer.cu:106-113: the ROI is given in image rows, the raster runs flipped
+        x0 = imax(x0, roi.x);  x1 = imin(x1, roi.x + roi.width - 1);
+        y0 = imax(y0, (int)height - 1 - (roi.y + roi.height - 1));  y1 = imin(y1, (int)height - 1 - roi.y);
+    }
+    return make_int4(x0, y0, x1, y1);
+}
+
+}  // namespace prk

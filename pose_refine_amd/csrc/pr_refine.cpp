@@ -1,5 +1,6 @@
 // pr_refine.cpp -- render, depth -> cloud, and the fused batch path render -> cloud -> ICP: synchronous form, two asynchronous slots, helper threads
 #include "pr_runtime.h"
+#include "pose_box.h"
 
 namespace prr {
 
@@ -31,20 +32,30 @@ uint32_t depth_chunk(size_t img, uint32_t P)
     return (uint32_t)std::max<size_t>(1, std::min<size_t>(P, ((size_t)4 << 30) / (img * sizeof(int32_t))));
 }
 
+bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
+{
+    if (roi.width <= 0 || roi.height <= 0) return true;            // no ROI
+    if (roi.x < 0 || roi.y < 0 || (size_t)roi.x + (size_t)roi.width > W || (size_t)roi.y + (size_t)roi.height > H) {
+        set_error("roi out of image");                               // renderer.cu:202-203 asserts
+        return false;
+    }
+    return true;
+}
+// {width, height} of one rendered image: the ROI when one is given, the full frame otherwise
+std::pair<size_t, size_t> image_extent(pr_roi roi, size_t W, size_t H)
+{
+    if (roi.width > 0 && roi.height > 0) return { (size_t)roi.width, (size_t)roi.height };
+    return { W, H };
+}
+
 int render_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t P, size_t W, size_t H,
                 const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev, bool zero_empty)
 {
     if ((!tris_dev && n_tris > 0) || (P && (!poses_host || !depth_dev)) || !proj || W == 0 || H == 0) { set_error("pr_render: bad arguments"); return PR_ERR_INVALID; }   // (an empty model has no array, no hypotheses need none)
     if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
-    size_t rw = W, rh = H;
-    if (roi.width > 0 && roi.height > 0) {
-        if (roi.x < 0 || roi.y < 0 || (size_t)(roi.x + roi.width) > W || (size_t)(roi.y + roi.height) > H) {
-            set_error("pr_render: roi out of image");        // renderer.cu:202-203 asserts
-            return PR_ERR_INVALID;
-        }
-        rw = (size_t)roi.width; rh = (size_t)roi.height;
-    }
+    if (!roi_ok(roi, (uint32_t)W, (uint32_t)H)) { set_error("pr_render: roi out of image"); return PR_ERR_INVALID; }
     if (P == 0) return PR_OK;
+    const auto [rw, rh] = image_extent(roi, W, H);
     SpanGuard sp(kSpanRender);
     PR_TRY(stage_poses(poses_host, P));
     HIP_TRY(prk::launch_fill_i32(depth_dev, P * rw * rh, INT32_MAX, g->stream));
@@ -77,16 +88,6 @@ int depth2cloud_impl(const T *depth_dev, uint32_t W, uint32_t H, const float K[9
     }
     *cloud_out = cloud; *n_out = n;
     return PR_OK;
-}
-
-bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
-{
-    if (roi.width <= 0 || roi.height <= 0) return true;            // no ROI
-    if (roi.x < 0 || roi.y < 0 || (size_t)roi.x + (size_t)roi.width > W || (size_t)roi.y + (size_t)roi.height > H) {
-        set_error("roi out of image");                               // renderer.cu:202-203 asserts
-        return false;
-    }
-    return true;
 }
 
 // ---- mixed batches (pr_*_multi): the hypotheses of several meshes in one call ---------------------------------------------------
@@ -384,7 +385,7 @@ int render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *m
     if (P > 0xffffffffull) { set_error("pr_render_multi: more than 2^32 hypotheses"); return PR_ERR_INVALID; }
     MeshPlan pl;
     PR_TRY(plan_meshes("pr_render_multi", meshes, n_meshes, mesh_index, P, pl));
-    const size_t rw = (roi.width > 0 && roi.height > 0) ? (size_t)roi.width : W, rh = (roi.width > 0 && roi.height > 0) ? (size_t)roi.height : H;
+    const auto [rw, rh] = image_extent(roi, W, H);
     const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
     SpanGuard sp(kSpanRender);
     PR_TRY(stage_poses(poses.data(), P));
@@ -410,7 +411,7 @@ int render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *m
 // ---- asynchronous fused refinement: two slots, everything of a batch enqueued without a host round trip -------------------
 // The synchronous path above reads the cloud sizes back in the middle of a step (they size the cloud stride and the grid),
 // uploads the start state and returns only after the results are in: ≈150 µs of a 1.3 ms step during which the GPU idles.
-// Here the host computes the per-pose pixel boxes itself (same arithmetic as pose_bbox_kernel, 8 corners per pose), which
+// Here the host computes the per-pose pixel boxes itself (pose_pixel_box, the function pose_bbox_kernel runs), which
 // bounds every cloud by its box area, the start state is written by a kernel from the device-side counts, and a batch is
 // only waited for when its results are wanted -- so the next batch can be enqueued while this one runs.
 // The streams of BOTH slots are created together, in one run: main and first side stream of slot 0, then of slot 1.  Which
@@ -528,35 +529,23 @@ int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
     return PR_OK;
 }
 
-// pose_bbox_kernel on the host (same operations in the same order; any conservative box gives the same images and clouds)
-void pose_bbox_host(const float *aabb, const pr_mat4 &pose, const pr_mat4 &proj, uint32_t width, uint32_t height, pr_roi roi, int32_t out[4])
+// a batch's arguments as a re-run needs them (the scene by value: a plain projective scene as a crop at 0, 0)
+Resubmit make_resubmit(const pr_triangle *tris_dev, size_t n_tris, uint32_t W, uint32_t H, const pr_mat4 *proj, const float K[9], int scene_kind,
+                       const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_dev)
 {
-    const float *M = pose.m;
-    float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
-    bool all_front = true;
-    for (int c = 0; c < 8; ++c) {
-        const float x = aabb[(c & 1) ? 3 : 0], y = aabb[(c & 2) ? 4 : 1], z = aabb[(c & 4) ? 5 : 2];
-        const float lx = M[0] * x + M[1] * y + M[2] * z + M[3];
-        const float ly = M[4] * x + M[5] * y + M[6] * z + M[7];
-        const float lz = M[8] * x + M[9] * y + M[10] * z + M[11];
-        if (!(lz > 1e-3f)) all_front = false;
-        const float cxp = proj.m[0] * lx + proj.m[1] * ly + proj.m[2] * lz + proj.m[3];
-        const float cyp = proj.m[4] * lx + proj.m[5] * ly + proj.m[6] * lz + proj.m[7];
-        const float sx = cxp / lz * (float)width / 2.0f + (float)width / 2.0f;
-        const float sy = cyp / lz * (float)height / 2.0f + (float)height / 2.0f;
-        mnx = fminf(mnx, sx); mxx = fmaxf(mxx, sx); mny = fminf(mny, sy); mxy = fmaxf(mxy, sy);
-    }
-    int x0 = 0, y0 = 0, x1 = (int)width - 1, y1 = (int)height - 1;
-    const bool finite = (mnx > -1e8f) && (mxx < 1e8f) && (mny > -1e8f) && (mxy < 1e8f);
-    if (all_front && finite) {
-        x0 = std::max(0, (int)floorf(mnx) - 2);  x1 = std::min((int)width - 1, (int)ceilf(mxx) + 2);
-        y0 = std::max(0, (int)floorf(mny) - 2);  y1 = std::min((int)height - 1, (int)ceilf(mxy) + 2);
-    }
-    if (roi.width > 0 && roi.height > 0) {
-        x0 = std::max(x0, roi.x);  x1 = std::min(x1, roi.x + roi.width - 1);
-        y0 = std::max(y0, (int)height - 1 - (roi.y + roi.height - 1));  y1 = std::min(y1, (int)height - 1 - roi.y);
-    }
-    out[0] = x0; out[1] = y0; out[2] = x1; out[3] = y1;
+    Resubmit r;
+    r.tris = tris_dev; r.n_tris = n_tris; r.W = W; r.H = H; r.proj = *proj; std::memcpy(r.K, K, sizeof r.K);
+    r.scene_kind = scene_kind; r.crit = crit; r.roi = roi; r.results_dev = results_dev;
+    if (scene_kind == PR_SCENE_NN) r.sn = *static_cast<const pr_scene_nn *>(scene);
+    else if (scene_kind == PR_SCENE_PROJ_CROP) r.sp = *static_cast<const pr_scene_proj_crop *>(scene);
+    else { r.sp.view = *static_cast<const pr_scene_proj *>(scene); r.sp.tl_x = r.sp.tl_y = 0; }
+    return r;
+}
+// ... and its scene as refine_impl takes it
+const void *resubmit_scene(const Resubmit &r)
+{
+    if (r.scene_kind == PR_SCENE_NN) return &r.sn;
+    return r.scene_kind == PR_SCENE_PROJ_CROP ? static_cast<const void *>(&r.sp) : static_cast<const void *>(&r.sp.view);
 }
 
 // the synchronous entry points run on whichever slot holds no unfinished batch of the caller's (-1: none)
@@ -595,8 +584,7 @@ int refine_wait(int slot)
         g->packed.valid = false;
         for (NNDerived &d : g->nn_sets) { d.valid = false; d.grid_valid = false; }
         const Resubmit &r = sl.again;
-        const void *scene = (r.scene_kind == PR_SCENE_NN) ? static_cast<const void *>(&r.sn) : static_cast<const void *>(&r.sp);
-        return refine_impl(r.tris, r.n_tris, sl.h_in.as<pr_mat4>(), sl.P, r.W, r.H, &r.proj, r.K, r.scene_kind, scene, r.crit, r.roi,
+        return refine_impl(r.tris, r.n_tris, sl.h_in.as<pr_mat4>(), sl.P, r.W, r.H, &r.proj, r.K, r.scene_kind, resubmit_scene(r), r.crit, r.roi,
                            sl.user_results_host, r.results_dev, sl.user_sizes);
     }
     const uint32_t *h_counts = sl.h_out.as<uint32_t>();
@@ -659,9 +647,7 @@ void slot_worker_main(SlotWorker *w)
             rc = require_ctx();
             if (rc == PR_OK) {
                 const Resubmit &r = w->in;
-                const void *scene = (r.scene_kind == PR_SCENE_NN) ? static_cast<const void *>(&r.sn)
-                                    : (r.scene_kind == PR_SCENE_PROJ_CROP ? static_cast<const void *>(&r.sp) : static_cast<const void *>(&r.sp.view));
-                rc = refine_impl(r.tris, r.n_tris, w->poses.data(), (uint32_t)w->poses.size(), r.W, r.H, &r.proj, r.K, r.scene_kind, scene, r.crit, r.roi,
+                rc = refine_impl(r.tris, r.n_tris, w->poses.data(), (uint32_t)w->poses.size(), r.W, r.H, &r.proj, r.K, r.scene_kind, resubmit_scene(r), r.crit, r.roi,
                                  w->results_host, r.results_dev, w->sizes_host);
             }
         }
@@ -697,12 +683,7 @@ int slot_worker_post(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, const
     SlotWorker &w = *sl.worker;
     {
         std::lock_guard<std::mutex> lk(w.mu);
-        Resubmit &r = w.in;
-        r.tris = tris_dev; r.n_tris = n_tris; r.W = W; r.H = H; r.proj = *proj; std::memcpy(r.K, K, sizeof r.K);
-        r.scene_kind = scene_kind; r.crit = crit; r.roi = roi; r.results_dev = results_dev;
-        if (scene_kind == PR_SCENE_NN) r.sn = *static_cast<const pr_scene_nn *>(scene);
-        else if (scene_kind == PR_SCENE_PROJ_CROP) r.sp = *static_cast<const pr_scene_proj_crop *>(scene);
-        else { r.sp.view = *static_cast<const pr_scene_proj *>(scene); r.sp.tl_x = r.sp.tl_y = 0; }
+        w.in = make_resubmit(tris_dev, n_tris, W, H, proj, K, scene_kind, scene, crit, roi, results_dev);
         w.poses.assign(poses_host, poses_host + P);
         w.results_host = results_host; w.sizes_host = sizes_host;
         w.done = false; w.has_job = true;
@@ -753,12 +734,7 @@ int refine_submit(int slot, const pr_triangle *tris_dev, size_t n_tris, const pr
     const size_t in_bytes = (sizeof(pr_mat4) + sizeof(int4) + sizeof(uint32_t)) * (size_t)P;      // [poses][pixel boxes][box offsets]
     PR_TRY(sl.h_in.ensure(in_bytes + 16));
     std::memcpy(sl.h_in.p, poses_host, sizeof(pr_mat4) * P);
-    Resubmit &r = sl.again;
-    r.tris = tris_dev; r.n_tris = n_tris; r.W = W; r.H = H; r.proj = *proj; std::memcpy(r.K, K, sizeof r.K);
-    r.scene_kind = scene_kind; r.crit = crit; r.roi = roi; r.results_dev = results_dev;
-    if (scene_kind == PR_SCENE_NN) r.sn = *static_cast<const pr_scene_nn *>(scene);
-    else if (scene_kind == PR_SCENE_PROJ_CROP) r.sp = *static_cast<const pr_scene_proj_crop *>(scene);
-    else { r.sp.view = *static_cast<const pr_scene_proj *>(scene); r.sp.tl_x = r.sp.tl_y = 0; }
+    sl.again = make_resubmit(tris_dev, n_tris, W, H, proj, K, scene_kind, scene, crit, roi, results_dev);
     const int rc = refine_submit_async(sl, tris_dev, n_tris, P, W, H, proj, K, scene_kind, scene, crit, roi, results_host, results_dev);
     if (rc != PR_OK) {                                            // part of the batch may already be queued: do not leave it running
         slot_drain(sl);                                           // behind the caller's back (its buffers may go away next)
@@ -836,12 +812,12 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     const size_t in_bytes = (sizeof(pr_mat4) + sizeof(int4) + sizeof(uint32_t)) * (size_t)P;
     PR_TRY(sl.poses_bbox.ensure(in_bytes + 16));
     pr_mat4 *h_poses = sl.h_in.as<pr_mat4>();
-    int32_t *h_box = reinterpret_cast<int32_t *>(h_poses + P);
+    int4 *h_box = reinterpret_cast<int4 *>(h_poses + P);
     size_t max_area = 1;
     for (uint32_t i = 0; i < P; ++i) {
-        pose_bbox_host(g->aabb_host, h_poses[i], *proj, W, H, roi, h_box + 4 * (size_t)i);
-        const int32_t *b = h_box + 4 * (size_t)i;
-        max_area = std::max(max_area, (size_t)std::max(0, b[2] - b[0] + 1) * (size_t)std::max(0, b[3] - b[1] + 1));   // an off-screen pose has an empty box
+        h_box[i] = prk::pose_pixel_box(g->aabb_host, h_poses[i].m, *proj, W, H, roi);
+        const int4 &b = h_box[i];
+        max_area = std::max(max_area, (size_t)std::max(0, b.z - b.x + 1) * (size_t)std::max(0, b.w - b.y + 1));   // an off-screen pose has an empty box
     }
     // capacity per hypothesis (the clouds themselves are packed: PoseMeta::start; a multiple of the packing's alignment, so that no sum of rounded sizes exceeds P x cstride)
     const size_t cstride = prk::kCloudAlign ? ((max_area + prk::kCloudAlign - 1) / prk::kCloudAlign) * prk::kCloudAlign : ((max_area + 3) & ~(size_t)3);
@@ -863,13 +839,13 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     const uint32_t sub = (P + n_sub - 1) / n_sub;
     PR_TRY(sl.depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * sub));
     // the pixel boxes of a sub-batch packed into the depth workspace: box i at h_off[i] ints, its own width as pitch (fill_box_kernel)
-    uint32_t *h_off = reinterpret_cast<uint32_t *>(h_box + 4 * (size_t)P);
+    uint32_t *h_off = reinterpret_cast<uint32_t *>(h_box + P);
     if (prk::kBoxPack) {
         size_t acc = 0;
         for (uint32_t i = 0; i < P; ++i) {
             if (i % sub == 0) acc = 0;
-            const int32_t *b = h_box + 4 * (size_t)i;
-            const size_t area = (size_t)std::max(0, b[2] - b[0] + 1) * (size_t)std::max(0, b[3] - b[1] + 1);
+            const int4 &b = h_box[i];
+            const size_t area = (size_t)std::max(0, b.z - b.x + 1) * (size_t)std::max(0, b.w - b.y + 1);
             h_off[i] = (uint32_t)acc;
             acc += (area + prk::kBoxPack - 1) / prk::kBoxPack * prk::kBoxPack;
         }
@@ -1037,7 +1013,8 @@ int pr_render(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_h
               const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev_out)
 {
     PR_ENTER();
-    if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * ((roi.width > 0 && roi.height > 0) ? (size_t)roi.width * roi.height : width * height));
+    const auto [rw, rh] = image_extent(roi, width, height);
+    if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * rw * rh);
     PR_TRY(render_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, depth_dev_out, true));
     HIP_TRY(hipStreamSynchronize(g->stream));            // renderer.cu:295 cudaDeviceSynchronize
     drain_spans();
@@ -1048,8 +1025,7 @@ int pr_render_to_host(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 
                       const pr_mat4 *proj, pr_roi roi, int32_t *depth_host_out)
 {
     PR_ENTER();
-    size_t rw = width, rh = height;
-    if (roi.width > 0 && roi.height > 0) { rw = (size_t)roi.width; rh = (size_t)roi.height; }
+    const auto [rw, rh] = image_extent(roi, width, height);
     PR_TRY(g->depth.ensure(sizeof(int32_t) * std::max<size_t>(1, n_poses * rw * rh)));
     PR_TRY(render_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, g->depth.as<int32_t>(), true));
     HIP_TRY(hipMemcpyAsync(depth_host_out, g->depth.p, sizeof(int32_t) * n_poses * rw * rh, hipMemcpyDeviceToHost, g->stream));
@@ -1083,7 +1059,8 @@ int pr_render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t
                     size_t width, size_t height, const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev_out)
 {
     PR_ENTER();
-    if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * ((roi.width > 0 && roi.height > 0) ? (size_t)roi.width * roi.height : width * height));
+    const auto [rw, rh] = image_extent(roi, width, height);
+    if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * rw * rh);
     PR_TRY(render_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, depth_dev_out));
     HIP_TRY(hipStreamSynchronize(g->stream));
     drain_spans();

@@ -1,6 +1,8 @@
 // raster.hip -- render_triangle + rasterization (cuda_renderer/renderer.cu:83-187) for a batch of hypotheses: clear, per-hypothesis pixel boxes, triangle raster with int32 atomicMin, row counts
 // gfx950 (CDNA4, wave64); compiled with -ffp-contract=off: every per-element value is bit-identical to the CPU restatement.
 #include "pr_launch.h"
+#define PR_HD __host__ __device__
+#include "pose_box.h"
 
 namespace prk {
 
@@ -203,6 +205,30 @@ __device__ __forceinline__ void wave_raster(const TriSetup &t, int n, float (*w)
 // one lane = one (triangle, hypothesis); depth resolved with int32 atomicMin in global memory (the reference scheme).
 __device__ __forceinline__ uint32_t f32_key(float v) { const uint32_t b = __float_as_uint(v); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ float key_f32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// A mesh box kept as six keys {minx,miny,minz,maxx,maxy,maxz}: a float maps to a key that orders like the float (sign bit flipped for
+// positives, all bits for negatives); minima store the key, maxima its complement, so all six start from 0xffffffff and merge with
+// atomicMin.  box_key_merge: the workgroup's lane minima / maxima into keys[0..5] (red: 4 x 6 floats of LDS).
+__device__ __forceinline__ void box_key_merge(float (&lo)[3], float (&hi)[3], float (*red)[6], uint32_t *keys)
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        for (int off = 32; off > 0; off >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], off)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off)); }
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        float r = red[0][threadIdx.x];
+        for (int w = 1; w < 4; ++w) { const float o = red[w][threadIdx.x]; r = (threadIdx.x < 3) ? fminf(r, o) : fmaxf(r, o); }
+        atomicMin(&keys[threadIdx.x], (threadIdx.x < 3) ? f32_key(r) : ~f32_key(r));
+    }
+}
+// key k of box word a back to its float; a key no vertex reached (an empty mesh) stays +FLT_MAX / -FLT_MAX
+__device__ __forceinline__ float box_key_value(uint32_t k, uint32_t a)
+{
+    float v = key_f32((a < 3) ? k : ~k);
+    if (k == 0xffffffffu) v = (a < 3) ? FLT_MAX : -FLT_MAX;
+    return v;
+}
 // The per-batch safety nets, carried by the raster (BatchCheck, pr_internal.h): called by the workgroups of the launch's first hypothesis with
 // their 256 triangles in registers.  `red` / `part`: LDS scratch (6 x 4 floats, 4 + 1 words).
 __device__ __forceinline__ void raster_batch_check(const float (&tv)[9], bool have, const BatchCheck &chk, float (*red)[6], uint32_t *part)
@@ -221,28 +247,17 @@ __device__ __forceinline__ void raster_batch_check(const float (&tv)[9], bool ha
     for (int a = 0; a < 3; ++a) {
         lo[a] = have ? fminf(fminf(tv[a], tv[3 + a]), tv[6 + a]) : FLT_MAX;
         hi[a] = have ? fmaxf(fmaxf(tv[a], tv[3 + a]), tv[6 + a]) : -FLT_MAX;
-        for (int off = 32; off > 0; off >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], off)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off)); }
     }
-    if (lane == 0) for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float r = red[0][threadIdx.x];
-        for (int w = 1; w < 4; ++w) r = (threadIdx.x < 3) ? fminf(r, red[w][threadIdx.x]) : fmaxf(r, red[w][threadIdx.x]);
-        atomicMin(&chk.keys[threadIdx.x], (threadIdx.x < 3) ? f32_key(r) : ~f32_key(r));
-        __threadfence();                                             // this workgroup's minima are in place before its ticket is drawn
-    }
+    box_key_merge(lo, hi, red, chk.keys);
+    if (threadIdx.x < 6) __threadfence();                            // this workgroup's minima are in place before its ticket is drawn
     __syncthreads();
     if (threadIdx.x == 0) part[4] = (atomicAdd(&chk.keys[6], 1u) == gridDim.x - 1u) ? 1u : 0u;
     __syncthreads();
     if (part[4] != 0u && threadIdx.x == 0) {                         // the last workgroup to arrive: compare, and re-arm the words for the next batch
         __threadfence();
         bool differs = false;
-        for (int a = 0; a < 6; ++a) {
-            const uint32_t k = atomicExch(&chk.keys[a], 0xffffffffu);
-            float val = (a < 3) ? key_f32(k) : key_f32(~k);
-            if (k == 0xffffffffu) val = (a < 3) ? FLT_MAX : -FLT_MAX;
-            if (!(val == chk.expect.v[a])) differs = true;
-        }
+        for (uint32_t a = 0; a < 6; ++a)
+            if (!(box_key_value(atomicExch(&chk.keys[a], 0xffffffffu), a) == chk.expect.v[a])) differs = true;
         atomicExch(&chk.keys[6], 0u);
         if (differs) *chk.flag = 1u;
     }
@@ -262,10 +277,9 @@ __device__ __forceinline__ void load_triangle(const pr_triangle *__restrict__ tr
     }
 }
 
-// What one raster_kernel workgroup does with its 256 triangles (tv, lane triangle ti of n_tris), restated line for line for
-// raster_multi_kernel: hypotheses [run * pose_run, +pose_run) of the n_poses at `poses`.  Image of hypothesis `by`: depth + image_of[by] *
-// rw * rh when image_of is given (the caller's order of a mixed batch), depth + by * rw * rh otherwise; packed boxes (box_off): their own
-// pitch.  raster_kernel keeps its own copy: calling this from it reschedules its code, which stays as measured.
+// What one raster workgroup does with its 256 triangles (tv, lane triangle ti of n_tris): hypotheses [run * pose_run, +pose_run) of the
+// n_poses at `poses`.  Image of hypothesis `by`: depth + image_of[by] * rw * rh when image_of is given (the caller's order of a mixed
+// batch), depth + by * rw * rh otherwise; packed boxes (box_off): their own pitch.
 __device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, uint32_t n_tris, uint32_t run,
                                             const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
                                             uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi,
@@ -322,54 +336,12 @@ __global__ __launch_bounds__(256) void raster_kernel(const pr_triangle *__restri
 {
     __shared__ float sh[4][kSetupWords][64];
     __shared__ uint32_t shq[4][192];                              // per wavefront: 128 words of fragment queue, 64 of run marks (wave_raster)
-    const uint32_t wave = threadIdx.x >> 6;
     const uint32_t ti = blockIdx.x * 256 + threadIdx.x;
     float tv[9];
-    if (ti < n_tris) {
-        const float *src = reinterpret_cast<const float *>(tris + ti);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) tv[k] = src[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) tv[k] = 0.0f;
-    }
+    load_triangle(tris, n_tris, ti, tv);
     if (chk.keys && blockIdx.y == 0)                             // (wave-uniform) the asynchronous path's per-batch checks ride on the first hypothesis' workgroups
         raster_batch_check(tv, ti < n_tris, chk, reinterpret_cast<float (*)[6]>(&sh[0][0][0]), &shq[0][0]);
-    float rmin0 = 0.0f, rmin1 = 0.0f, rmax0 = (float)(width - 1), rmax1 = (float)(height - 1);
-    if (roi.width > 0 && roi.height > 0) {                       // renderer.cu:106-113 (image is flipped in y)
-        rmin0 = (float)roi.x;
-        rmin1 = (float)((unsigned long long)(height - 1) - (unsigned long long)(long long)(roi.y + roi.height - 1));
-        rmax0 = (float)((roi.x + roi.width) - 1);
-        rmax1 = (float)((unsigned long long)(height - 1) - (unsigned long long)(long long)roi.y);
-    }
-    for (uint32_t k = 0; k < pose_run; ++k) {
-        const uint32_t by = blockIdx.y * pose_run + k;
-        if (by >= n_poses) break;
-        const float *M = poses[by].m;                            // wave-uniform -> scalar loads
-        int32_t *img = depth + (size_t)by * rw * rh;
-        float cmin0 = rmin0, cmin1 = rmin1, cmax0 = rmax0, cmax1 = rmax1;
-        uint32_t pitch = rw;                                     // image row pitch; packed boxes (box_off): the box's own width, origin at its top-left pixel
-        if (boxes) {                                             // fused path: the hypothesis' pixel box (already intersected with the caller's ROI,
-            const int4 bb = boxes[by];                           // if any); a conservative box clips nothing, an ROI clips like renderer.cu:106-113
-            cmin0 = (float)bb.x; cmin1 = (float)bb.y; cmax0 = (float)bb.z; cmax1 = (float)bb.w;
-            if (box_off) {
-                pitch = (uint32_t)max(bb.z - bb.x + 1, 0);
-                // pixel (x, image row r) of the box lives at off + (r - r0) * pitch + (x - bb.x), r0 = height - 1 - bb.w: fold the origin into the base
-                img = depth + box_off[by] - ((ptrdiff_t)((int)height - 1 - bb.w) * (ptrdiff_t)pitch + (ptrdiff_t)bb.x);
-            }
-        }
-        TriSetup t;
-        int n = 0;
-        if (ti < n_tris) {
-            tri_setup(tv, M, proj, width, height, cmin0, cmin1, cmax0, cmax1, t);
-            n = t.nx * t.ny;
-        } else { t.nx = t.ny = 0; t.x0 = t.y0 = 0; t.base_inv = 0; for (int j = 0; j < 3; ++j) t.px[j] = t.py[j] = t.w3[j] = 0; }
-        wave_raster(t, n, sh[wave], shq[wave], [&](int x, int y, int d) {
-            const uint32_t xw = (uint32_t)(x - roi.x);
-            const uint32_t yw = (uint32_t)((int)height - 1 - y - roi.y);
-            atomicMin(&img[xw + (size_t)yw * pitch], d);
-        });
-    }
+    raster_runs(tv, ti, n_tris, blockIdx.y, poses, depth, width, height, proj, roi, rw, rh, boxes, n_poses, pose_run, box_off, nullptr, sh, shq);
 }
 
 // A mixed batch (hypotheses of several meshes) in one launch.  The hypotheses come grouped by mesh; group g owns the 1-D workgroup
@@ -412,9 +384,8 @@ __global__ __launch_bounds__(256) void raster_multi_kernel(const RasterGroup *__
 //  touched (the conservative box of the object instead of the whole frame) differ.
 // ================================================================================================
 
-// axis-aligned box of the mesh: {minx,miny,minz,maxx,maxy,maxz}.  Any number of workgroups: each reduces a slice and merges it
-// into six 32-bit keys with atomicMin -- a float maps to a key that orders like the float (sign bit flipped for positives, all
-// bits for negatives); minima store the key, maxima its complement, so all six start from 0xffffffff (one memset).
+// axis-aligned box of the mesh in six keys (box_key_merge).  Any number of workgroups: each reduces a slice and merges it; the keys
+// start from 0xffffffff (one memset).
 __global__ __launch_bounds__(256) void model_aabb_kernel(const pr_triangle *__restrict__ tris, uint32_t n_tris, uint32_t *__restrict__ keys)
 {
     __shared__ float red[4][6];
@@ -424,28 +395,15 @@ __global__ __launch_bounds__(256) void model_aabb_kernel(const pr_triangle *__re
 #pragma unroll
         for (int a = 0; a < 3; ++a) { const float c = v[(size_t)i * 3 + a]; lo[a] = fminf(lo[a], c); hi[a] = fmaxf(hi[a], c); }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        for (int off = 32; off > 0; off >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], off)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off)); }
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float r = red[0][threadIdx.x];
-        for (int w = 1; w < 4; ++w) r = (threadIdx.x < 3) ? fminf(r, red[w][threadIdx.x]) : fmaxf(r, red[w][threadIdx.x]);
-        atomicMin(&keys[threadIdx.x], (threadIdx.x < 3) ? f32_key(r) : ~f32_key(r));
-    }
+    box_key_merge(lo, hi, red, keys);
 }
-// keys -> floats (aabb_out, optional) and/or a check against the box the host assumed (flag_out, optional: 1 = differs).
-// An empty mesh leaves the keys untouched: +FLT_MAX / -FLT_MAX like the single-pass form.
+// keys -> floats (aabb_out, optional) and/or a check against the box the host assumed (flag_out, optional: 1 = differs)
 __global__ void model_aabb_finish_kernel(const uint32_t *__restrict__ keys, float *__restrict__ aabb_out, AabbExpected expect, uint32_t *__restrict__ flag_out)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     bool differs = false;
-    for (int a = 0; a < 6; ++a) {
-        const uint32_t k = keys[a];
-        float v = (a < 3) ? key_f32(k) : key_f32(~k);
-        if (k == 0xffffffffu) v = (a < 3) ? FLT_MAX : -FLT_MAX;
+    for (uint32_t a = 0; a < 6; ++a) {
+        const float v = box_key_value(keys[a], a);
         if (aabb_out) aabb_out[a] = v;
         if (!(v == expect.v[a])) differs = true;
     }
@@ -464,99 +422,27 @@ __global__ __launch_bounds__(256) void model_aabb_multi_kernel(const pr_mesh_ref
 #pragma unroll
             for (int a = 0; a < 3; ++a) { const float c = v[(size_t)i * 3 + a]; lo[a] = fminf(lo[a], c); hi[a] = fmaxf(hi[a], c); }
         }
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            for (int off = 32; off > 0; off >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], off)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off)); }
-        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (lane == 0) for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
-        __syncthreads();
-        if (threadIdx.x < 6) {
-            float r = red[0][threadIdx.x];
-            for (int w = 1; w < 4; ++w) r = (threadIdx.x < 3) ? fminf(r, red[w][threadIdx.x]) : fmaxf(r, red[w][threadIdx.x]);
-            atomicMin(&keys[6 * (size_t)m + threadIdx.x], (threadIdx.x < 3) ? f32_key(r) : ~f32_key(r));
-        }
+        box_key_merge(lo, hi, red, keys + 6 * (size_t)m);
         __syncthreads();                                             // red is rewritten for the next mesh
     }
 }
-// keys -> floats, one lane per (mesh, axis): model_aabb_finish_kernel's conversion (an empty mesh: +FLT_MAX / -FLT_MAX)
+// keys -> floats, one lane per (mesh, axis)
 __global__ __launch_bounds__(256) void model_aabb_multi_finish_kernel(const uint32_t *__restrict__ keys, uint32_t n_words, float *__restrict__ aabb_out)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_words) return;
-    const uint32_t a = i % 6, k = keys[i];
-    float v = (a < 3) ? key_f32(k) : key_f32(~k);
-    if (k == 0xffffffffu) v = (a < 3) ? FLT_MAX : -FLT_MAX;
-    aabb_out[i] = v;
+    aabb_out[i] = box_key_value(keys[i], i % 6);
 }
 
-// Conservative pixel box {x0,y0,x1,y1} (raster coordinates, y not yet flipped) of the mesh under
-// every pose: the 8 box corners go through the same model / projection / viewport arithmetic as
-// the vertices; the projection of any point of the box lies in the hull of the projected corners
-// as long as all of them are in front of the camera, and 2 pixels of padding cover float rounding.
-// Any corner at or behind the camera plane -> the whole frame.
-// pose_bbox_kernel's box of one pose, operation for operation
-__device__ __forceinline__ int4 pose_pixel_box(const float *__restrict__ aabb, const float *M, const pr_mat4 &proj, uint32_t width, uint32_t height, pr_roi roi)
-{
-    float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
-    bool all_front = true;
-    for (int c = 0; c < 8; ++c) {
-        const float x = aabb[(c & 1) ? 3 : 0], y = aabb[(c & 2) ? 4 : 1], z = aabb[(c & 4) ? 5 : 2];
-        const float lx = M[0] * x + M[1] * y + M[2] * z + M[3];
-        const float ly = M[4] * x + M[5] * y + M[6] * z + M[7];
-        const float lz = M[8] * x + M[9] * y + M[10] * z + M[11];
-        if (!(lz > 1e-3f)) all_front = false;
-        const float cxp = proj.m[0] * lx + proj.m[1] * ly + proj.m[2] * lz + proj.m[3];
-        const float cyp = proj.m[4] * lx + proj.m[5] * ly + proj.m[6] * lz + proj.m[7];
-        const float sx = cxp / lz * (float)width / 2.0f + (float)width / 2.0f;
-        const float sy = cyp / lz * (float)height / 2.0f + (float)height / 2.0f;
-        mnx = fminf(mnx, sx); mxx = fmaxf(mxx, sx); mny = fminf(mny, sy); mxy = fmaxf(mxy, sy);
-    }
-    int x0 = 0, y0 = 0, x1 = (int)width - 1, y1 = (int)height - 1;
-    const bool finite = (mnx > -1e8f) && (mxx < 1e8f) && (mny > -1e8f) && (mxy < 1e8f);
-    if (all_front && finite) {
-        x0 = max(0, (int)floorf(mnx) - 2);  x1 = min((int)width - 1, (int)ceilf(mxx) + 2);
-        y0 = max(0, (int)floorf(mny) - 2);  y1 = min((int)height - 1, (int)ceilf(mxy) + 2);
-    }
-    if (roi.width > 0 && roi.height > 0) {                       // renderer.cu:106-113: the ROI is given in image rows, the raster runs flipped
-        x0 = max(x0, roi.x);  x1 = min(x1, roi.x + roi.width - 1);
-        y0 = max(y0, (int)height - 1 - (roi.y + roi.height - 1));  y1 = min(y1, (int)height - 1 - roi.y);
-    }
-    return make_int4(x0, y0, x1, y1);
-}
+// the pixel box of every pose (pose_pixel_box, pose_box.h)
 __global__ __launch_bounds__(256) void pose_bbox_kernel(const float *__restrict__ aabb, const pr_mat4 *__restrict__ poses, uint32_t n_poses,
                                                         pr_mat4 proj, uint32_t width, uint32_t height, pr_roi roi, int4 *__restrict__ bbox)
 {
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n_poses) return;
-    const float *M = poses[p].m;
-    float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
-    bool all_front = true;
-    for (int c = 0; c < 8; ++c) {
-        const float x = aabb[(c & 1) ? 3 : 0], y = aabb[(c & 2) ? 4 : 1], z = aabb[(c & 4) ? 5 : 2];
-        const float lx = M[0] * x + M[1] * y + M[2] * z + M[3];
-        const float ly = M[4] * x + M[5] * y + M[6] * z + M[7];
-        const float lz = M[8] * x + M[9] * y + M[10] * z + M[11];
-        if (!(lz > 1e-3f)) all_front = false;
-        const float cxp = proj.m[0] * lx + proj.m[1] * ly + proj.m[2] * lz + proj.m[3];
-        const float cyp = proj.m[4] * lx + proj.m[5] * ly + proj.m[6] * lz + proj.m[7];
-        const float sx = cxp / lz * (float)width / 2.0f + (float)width / 2.0f;
-        const float sy = cyp / lz * (float)height / 2.0f + (float)height / 2.0f;
-        mnx = fminf(mnx, sx); mxx = fmaxf(mxx, sx); mny = fminf(mny, sy); mxy = fmaxf(mxy, sy);
-    }
-    int x0 = 0, y0 = 0, x1 = (int)width - 1, y1 = (int)height - 1;
-    const bool finite = (mnx > -1e8f) && (mxx < 1e8f) && (mny > -1e8f) && (mxy < 1e8f);
-    if (all_front && finite) {
-        x0 = max(0, (int)floorf(mnx) - 2);  x1 = min((int)width - 1, (int)ceilf(mxx) + 2);
-        y0 = max(0, (int)floorf(mny) - 2);  y1 = min((int)height - 1, (int)ceilf(mxy) + 2);
-    }
-    if (roi.width > 0 && roi.height > 0) {                       // renderer.cu:106-113: the ROI is given in image rows, the raster runs flipped
-        x0 = max(x0, roi.x);  x1 = min(x1, roi.x + roi.width - 1);
-        y0 = max(y0, (int)height - 1 - (roi.y + roi.height - 1));  y1 = min(y1, (int)height - 1 - roi.y);
-    }
-    bbox[p] = make_int4(x0, y0, x1, y1);
+    bbox[p] = pose_pixel_box(aabb, poses[p].m, proj, width, height, roi);
 }
-// the same box for a mixed batch: hypothesis p uses the box of its own mesh, aabbs[6 * box_index[p] ...] (pose_bbox_kernel's arithmetic,
-// pose_pixel_box; pose_bbox_kernel keeps its own copy so that its code stays as it is)
+// the same box for a mixed batch: hypothesis p uses the box of its own mesh, aabbs[6 * box_index[p] ...]
 __global__ __launch_bounds__(256) void pose_bbox_multi_kernel(const float *__restrict__ aabbs, const uint32_t *__restrict__ box_index,
                                                               const pr_mat4 *__restrict__ poses, uint32_t n_poses, pr_mat4 proj, uint32_t width,
                                                               uint32_t height, pr_roi roi, int4 *__restrict__ bbox)
@@ -801,6 +687,38 @@ __global__ __launch_bounds__(256) void box_pack_offsets_kernel(const int4 *__res
         __syncthreads();
     }
 }
+// The steps both box renders share.  box_pack_offsets_kernel (when the boxes are packed); fill_box_kernel / count_box_kernel over hypotheses
+// [p0, p0 + n), in launches of at most 32768 (grid.y is limited to 65535); the closing row scan (launch_d2c_scan_init when the asynchronous
+// path's per-hypothesis records are given).
+static void launch_box_pack(const int4 *bbox, uint32_t n_poses, const uint32_t *box_off, hipStream_t s)
+{
+    if (box_off && kBoxPack) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, bbox, n_poses, const_cast<uint32_t *>(box_off));   // (the caller's scratch: filled here)
+}
+static void launch_fill_boxes(int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height, hipStream_t s)
+{
+    for (const uint32_t end = p0 + n; p0 < end; p0 += 32768) {
+        const uint32_t np = (end - p0 < 32768) ? (end - p0) : 32768;
+        hipLaunchKernelGGL(fill_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
+                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, box_off ? box_off + p0 : nullptr);
+    }
+}
+static void launch_count_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height,
+                               uint32_t *row_count, hipStream_t s)
+{
+    for (const uint32_t end = p0 + n; p0 < end; p0 += 32768) {
+        const uint32_t np = (end - p0 < 32768) ? (end - p0) : 32768;
+        hipLaunchKernelGGL(count_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
+                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, row_count + (size_t)p0 * height, box_off ? box_off + p0 : nullptr);
+    }
+}
+static hipError_t launch_box_scan(const uint32_t *row_count, uint32_t height, uint32_t *row_off, uint32_t *counts, uint32_t n_poses,
+                                  PoseMeta *meta, DevIcpState *st, uint32_t *arrive, uint32_t cloud_stride, hipStream_t s)
+{
+    const hipError_t e = meta ? launch_d2c_scan_init(row_count, height, row_off, counts, n_poses, meta, st, arrive, cloud_stride, s)
+                              : launch_d2c_scan(row_count, height, row_off, counts, n_poses, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
 // fused-path render, reference scheme (global int32 atomicMin) but only inside each hypothesis' box
 hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb,
                                int4 *bbox, int32_t *depth, uint32_t *row_count, uint32_t *row_off, uint32_t *counts,
@@ -810,14 +728,14 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
     if (n_poses == 0) return hipSuccess;
     if (compute_boxes) {
         hipLaunchKernelGGL(pose_bbox_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabb, poses_dev, n_poses, proj, width, height, roi, bbox);
-        if (box_off && kBoxPack) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, (const int4 *)bbox, n_poses, const_cast<uint32_t *>(box_off));   // (the caller's scratch: filled here)
+        launch_box_pack(bbox, n_poses, box_off, s);
     }
     const pr_roi none{ 0, 0, 0, 0 };
     for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
         const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
         const size_t off = box_off ? 0 : (size_t)p0 * width * height;
         const uint32_t *bo = box_off ? box_off + p0 : nullptr;
-        hipLaunchKernelGGL(fill_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s, depth + off, bbox + p0, width, height, bo);
+        launch_fill_boxes(depth, bbox, box_off, p0, np, width, height, s);
         if (n_tris > 0)                                          // an empty mesh renders nothing: every cloud is empty
         { const uint32_t run = raster_pose_run(n_tris, np);
           // PR_RASTER_CHUNKS > 1 (experiment of round 5): the hypotheses of a launch in that many launches one behind the other
@@ -829,12 +747,9 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
                                  depth + off + (bo ? 0 : (size_t)c0 * width * height), width, height, proj, none, width, height, (const int4 *)(bbox + p0 + c0), nc, run,
                                  bo ? bo + c0 : nullptr, (check && p0 == 0 && c == 0) ? *check : BatchCheck{});
           } }
-        hipLaunchKernelGGL(count_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s, depth + off, bbox + p0, width, height,
-                           row_count + (size_t)p0 * height, bo);
+        launch_count_boxes(depth, bbox, box_off, p0, np, width, height, row_count, s);
     }
-    if (meta) { hipError_t e = launch_d2c_scan_init(row_count, height, row_off, counts, n_poses, meta, st, arrive, cloud_stride, s); if (e != hipSuccess) return e; }
-    else { hipError_t e = launch_d2c_scan(row_count, height, row_off, counts, n_poses, s); if (e != hipSuccess) return e; }
-    return hipGetLastError();
+    return launch_box_scan(row_count, height, row_off, counts, n_poses, meta, st, arrive, cloud_stride, s);
 }
 
 // ---- mixed batches (hypotheses of several meshes in one call) -----------------------------------------------------------------------
@@ -890,22 +805,13 @@ hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_ind
 {
     if (n_poses == 0) return hipSuccess;
     hipLaunchKernelGGL(pose_bbox_multi_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabbs, box_index, poses_dev, n_poses, proj, width, height, roi, bbox);
-    if (box_off && kBoxPack) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, (const int4 *)bbox, n_poses, const_cast<uint32_t *>(box_off));
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
-        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
-        hipLaunchKernelGGL(fill_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
-                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, box_off ? box_off + p0 : nullptr);
-    }
+    launch_box_pack(bbox, n_poses, box_off, s);
+    launch_fill_boxes(depth, bbox, box_off, 0, n_poses, width, height, s);
     const pr_roi none{ 0, 0, 0, 0 };
     { hipError_t e = launch_raster_multi(groups_host, groups_mapped, n_groups, groups_dev, poses_dev, depth, width, height, proj, none, width, height,
                                          bbox, box_off, nullptr, s); if (e != hipSuccess) return e; }
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
-        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
-        hipLaunchKernelGGL(count_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
-                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, row_count + (size_t)p0 * height, box_off ? box_off + p0 : nullptr);
-    }
-    { hipError_t e = launch_d2c_scan(row_count, height, row_off, counts, n_poses, s); if (e != hipSuccess) return e; }
-    return hipGetLastError();
+    launch_count_boxes(depth, bbox, box_off, 0, n_poses, width, height, row_count, s);
+    return launch_box_scan(row_count, height, row_off, counts, n_poses, nullptr, nullptr, nullptr, 0, s);
 }
 
 }  // namespace prk

@@ -383,6 +383,13 @@ int  pr_profile_nn(double part_ms[4], uint64_t *passes);
  * point order reproduces the reference's single-thread summation (icp.cpp:139-148), which the product kernel replaces by its fixed tree. */
 int  pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, const void *scene, const float *update16, int want_packed,
                         float *contrib_host);
+/* Audit entry: ONE iteration of icp.cu:178-212 for n hypotheses whose 29 sums are given (n x 29 floats in the pass's order: the 21
+ * upper-triangle entries of A row by row, b[6], r^2, count).  on_device != 0: the wavefront iteration the fused pass tail and
+ * icp_finalize_solve_kernel run (one wavefront per hypothesis); 0: the host-solve loop's iteration (needs no device).  state: in/out
+ * (T, rmse, fitness as the previous iteration left them); update_out: n x 16 (the update E; zeros where the hypothesis stops);
+ * finished_out: n x uint32 (1 = the hypothesis stops here). */
+int  pr_debug_pose_iteration(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, int on_device,
+                             pr_result *state, float *update_out, uint32_t *finished_out);
 /* Two things the library does silently for correctness, counted per context since it was created: asynchronous batches that
  * pr_refine_wait ran a SECOND time because the device-side checks found a stale model box or a scene array that no longer matches its
  * cached form (a caller who sees this grow writes to its buffers behind the library's back: pr_invalidate is the cheap cure), and timed

@@ -512,6 +512,26 @@ def debug_contrib29(model_pcd: DeviceVector, scene, update=None, packed: bool = 
     return out
 
 
+def debug_pose_iteration(sums, n_points, criteria, iteration: int, on_device: bool, state=None):
+    """``pr_debug_pose_iteration``: one ICP iteration (icp.cu:178-212) for every row of ``sums`` (n, 29), on the device (the wavefront
+    iteration of the device-solve loop) or on the host (the host-solve loop's).  ``state``: RESULT records as the previous iteration left
+    them (default: identity, rmse and fitness 0).  Returns (state after the iteration, updates E (n, 4, 4), finished (n,) bool)."""
+    s = _f32(sums, -1).reshape(-1, 29)
+    n = len(s)
+    cnt = np.ascontiguousarray(n_points, dtype=np.uint32).reshape(-1)
+    if len(cnt) != n:
+        raise ValueError(f"n_points: one count per row of sums, got {len(cnt)} for {n}")
+    st = np.zeros(n, RESULT)
+    if state is None:
+        st["T"] = np.eye(4, dtype=np.float32).reshape(16)
+    else:
+        st[:] = np.asarray(state, RESULT).reshape(n)
+    upd = np.zeros((n, 16), np.float32)
+    fin = np.zeros(n, np.uint32)
+    check(_lib.load().pr_debug_pose_iteration(ptr(s), ptr(cnt), n, criteria.c(), int(iteration), int(bool(on_device)), ptr(st), ptr(upd), ptr(fin)))
+    return st, upd.reshape(n, 4, 4), fin.astype(bool)
+
+
 def refine_batch(tris, poses, width: int, height: int, proj, K, scene,
                  criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(), results_dev: Optional[int] = None,
                  roi: Optional[Sequence[int]] = None):

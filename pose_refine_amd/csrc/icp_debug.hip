@@ -1,4 +1,5 @@
-// icp_debug.hip -- audit entry of the correspondence pass: the 29 per-point terms of thrust__pcd2Ab (icp.h:128-209), point by point.
+// icp_debug.hip -- audit entries: the 29 per-point terms of thrust__pcd2Ab (icp.h:128-209), point by point, and one iteration of the
+// device's wavefront solve on given sums.
 // gfx950 (CDNA4, wave64); compiled with -ffp-contract=off: every per-element value is bit-identical to the CPU restatement.
 //
 // The product kernel (icp_pass.hip) adds these terms in its own fixed tree; a test that adds them SEQUENTIALLY on the host reproduces the
@@ -6,6 +7,7 @@
 // per point, the same device functions as the pass: the pending update in the pass' operand order, query(), accumulate() from zero.
 #include "pr_launch.h"
 #include "icp_accumulate.h"
+#include "icp_solve_device.h"
 
 namespace prk {
 
@@ -53,5 +55,39 @@ hipError_t launch_contrib29_proj_packed(pr_vec3 *cloud, uint32_t n, const float 
 { return launch_contrib29_t<SceneProjPacked, false>(cloud, n, update12, sc, out, s); }
 hipError_t launch_contrib29_nn(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneNNDev &sc, float *out, hipStream_t s)
 { return launch_contrib29_t<SceneNNDev, true>(cloud, n, update12, sc, out, s); }
+
+// One wavefront per hypothesis, all 64 lanes active (pose_iteration_wave needs them): lanes 0..28 hold the 29 sums as the pass tail
+// leaves them in `total`; the function itself runs unchanged on a DevIcpState built from the caller's record.
+__global__ __launch_bounds__(64) void pose_iteration_debug_kernel(const float *__restrict__ sums, const uint32_t *__restrict__ n_points,
+                                                                  pr_criteria crit, uint32_t iter, pr_result *__restrict__ state,
+                                                                  float *__restrict__ update, uint32_t *__restrict__ finished)
+{
+    const uint32_t pose = blockIdx.x;
+    const pr_result r = state[pose];
+    DevIcpState s;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s.T[i] = r.T[i];
+    s.fitness = r.fitness; s.rmse = r.inlier_rmse; s.done = 0; s.passes = 0;
+    const float total = (threadIdx.x < 29) ? sums[(size_t)pose * 29 + threadIdx.x] : 0.0f;
+    float E[16];
+    const bool fin = pose_iteration_wave(total, n_points[pose], s, crit, iter, E);
+    if (threadIdx.x != 0) return;
+    pr_result o;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o.T[i] = s.T[i];
+    o.fitness = s.fitness; o.inlier_rmse = s.rmse;
+    state[pose] = o;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) update[(size_t)pose * 16 + i] = fin ? 0.0f : E[i];
+    finished[pose] = fin ? 1u : 0u;
+}
+
+hipError_t launch_pose_iteration_debug(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, pr_result *state,
+                                       float *update, uint32_t *finished, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(pose_iteration_debug_kernel, dim3(n), dim3(64), 0, s, sums, n_points, crit, iter, state, update, finished);
+    return hipGetLastError();
+}
 
 }  // namespace prk

@@ -28,44 +28,16 @@ __device__ __forceinline__ float sum_partials_sys(const float *partial, uint32_t
     return total;
 }
 
-// The per-iteration host logic of icp.cu:178-212 for one hypothesis, on the 29 reduced sums: scores, convergence test,
-// 6x6 solve, accumulation of the transform.  Returns true when the hypothesis is finished; otherwise E holds the update.
-__device__ __forceinline__ bool pose_iteration(const float *Ab, uint32_t n, DevIcpState &s, const pr_criteria &crit, uint32_t iter, float (&E)[16])
-{
-    s.passes += 1;
-    const float cnt = Ab[28], err = Ab[27];
-    if (cnt == 0) return true;                                               // icp.cu:183
-    const float prev_fit = s.fitness, prev_rmse = s.rmse;
-    s.fitness = cnt / (float)n;                                              // icp.cu:185
-    s.rmse = sqrtf(err / cnt);                                               // icp.cu:186
-    if (iter == (uint32_t)crit.max_iteration) return true;                   // icp.cu:189
-    const float df = s.fitness - prev_fit, dr = s.rmse - prev_rmse;
-    if (((df < 0) ? -df : df) < crit.relative_fitness && ((dr < 0) ? -dr : dr) < crit.relative_rmse) return true;   // icp.cu:191-194
-    float A[36], bb[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) bb[i] = Ab[21 + i];
-    {
-        int k = 0;
-#pragma unroll
-        for (int y = 0; y < 6; ++y) {
-#pragma unroll
-            for (int x = y; x < 6; ++x) { A[x + y * 6] = Ab[k]; A[y + x * 6] = Ab[k]; ++k; }
-        }
-    }
-    prs::solve_666_impl(A, bb, E);
-    prs::mat4_mul_impl(E, s.T, s.T);                                         // icp.cu:212
-    return false;
-}
-
-// ---- wave-cooperative form of the same iteration logic ---------------------------------------------------------------
+// ---- the per-iteration logic of icp.cu:178-212 for one hypothesis, wave-cooperative ----------------------------------
 // One lane running prs::solve_666_impl is slow twice over: ~1500 dependent double-precision instructions, and the
 // data-dependent pivoting makes the compiler specialise the code per pivot sequence (hundreds of KB of instructions,
 // fetched cold).  Here the 6x6 lives one element per lane (lane = 6*row + col, the FULL symmetric matrix, so the
 // symmetric pivot swap is a single lane permutation), the column update of a step runs on the lanes of that column,
 // the six back-substitution divisions and the three sin/cos evaluations run side by side, and everything else is
-// computed redundantly (uniformly) by all lanes.  Every element goes through exactly the same sequence of IEEE operations
-// as in prs::ldlt6 / prs::solve_666_impl, so the update is bit-identical to the host solver
-// (tests/test_parity_gpu.py::test_host_and_device_solve_agree).  All 64 lanes of the wavefront must be active.
+// computed redundantly (uniformly) by all lanes.  This is a restatement of prs::ldlt6 / prs::solve_666_impl, not that source
+// compiled for the device: every element is meant to go through exactly the same sequence of IEEE operations, so that the
+// update is bit-identical to the host solver.  tests/test_solve_gpu.py holds it to that over all 720 pivot sequences and the
+// branch edges, through pr_debug_pose_iteration.  All 64 lanes of the wavefront must be active.
 __device__ __forceinline__ double wave_gather_d(double v, int src_lane)
 {
     const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2loint(v));

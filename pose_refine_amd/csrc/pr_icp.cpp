@@ -31,6 +31,28 @@ int ensure_stream(hipStream_t &st, hipEvent_t *ev)
     return PR_OK;
 }
 
+// The host's part of an iteration for one hypothesis whose 29 sums Ab have arrived (icp.cu:178-212): scores, convergence test, 6x6 solve,
+// accumulation of the transform into r.T.  Returns whether the hypothesis goes on; then E holds the update.  (The host-solve loop and
+// pr_debug_pose_iteration both run it.)
+bool pose_iteration_host(const float *Ab, uint32_t n, pr_result &r, const pr_criteria &crit, uint32_t it, float E[16])
+{
+    const float prev_fit = r.fitness, prev_rmse = r.inlier_rmse;
+    const float cnt = Ab[28], err = Ab[27];
+    if (cnt == 0) return false;                                                       // icp.cu:183
+    r.fitness = cnt / (float)n;                                                       // icp.cu:185
+    r.inlier_rmse = std::sqrt(err / cnt);                                             // icp.cu:186
+    if (it == (uint32_t)crit.max_iteration) return false;                             // icp.cu:189
+    if (std::fabs(r.fitness - prev_fit) < crit.relative_fitness &&
+        std::fabs(r.inlier_rmse - prev_rmse) < crit.relative_rmse) return false;     // icp.cu:191-194
+    float A[36], bb[6];
+    for (int k = 0; k < 6; ++k) bb[k] = Ab[21 + k];
+    int sh = 0;
+    for (int y = 0; y < 6; ++y) for (int x = y; x < 6; ++x) { A[x + y * 6] = Ab[sh]; A[y + x * 6] = Ab[sh]; ++sh; }   // icp.cu:196-205
+    prh::solve_666(A, bb, E);
+    prh::mat4_mul(E, r.T, r.T);                                                       // icp.cu:212
+    return true;
+}
+
 // ---- the batched ICP driver -----------------------------------------------------------------------
 // clouds: cloud i = cloud_base[start_h[i] .. start_h[i]+count_h[i]).  start/count must already be in
 // g->start / g->counts on the device when dev_meta_ready, otherwise they are uploaded here.
@@ -273,23 +295,9 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     };
     // the host's part of an iteration for one hypothesis whose 29 sums have arrived (icp.cu:178-212); returns whether the hypothesis goes on
     auto solve_one = [&](uint32_t i, uint32_t it) -> bool {
-        const float *Ab = h_sums + (size_t)i * prk::kAccStride;
-        pr_result &r = res[i];
-        const float prev_fit = r.fitness, prev_rmse = r.inlier_rmse;
-        const float cnt = Ab[28], err = Ab[27];
-        if (cnt == 0) { h_meta[i].state = prk::kSkip; return false; }                         // icp.cu:183
-        r.fitness = cnt / (float)count_h[i];                                              // icp.cu:185
-        r.inlier_rmse = std::sqrt(err / cnt);                                             // icp.cu:186
-        if (it == (uint32_t)crit.max_iteration) { h_meta[i].state = prk::kSkip; return false; }    // icp.cu:189
-        if (std::fabs(r.fitness - prev_fit) < crit.relative_fitness &&
-            std::fabs(r.inlier_rmse - prev_rmse) < crit.relative_rmse) { h_meta[i].state = prk::kSkip; return false; }   // icp.cu:191-194
-        float A[36], bb[6], E[16];
-        for (int k = 0; k < 6; ++k) bb[k] = Ab[21 + k];
-        int sh = 0;
-        for (int y = 0; y < 6; ++y) for (int x = y; x < 6; ++x) { A[x + y * 6] = Ab[sh]; A[y + x * 6] = Ab[sh]; ++sh; }   // icp.cu:196-205
-        prh::solve_666(A, bb, E);
+        float E[16];
+        if (!pose_iteration_host(h_sums + (size_t)i * prk::kAccStride, count_h[i], res[i], crit, it, E)) { h_meta[i].state = prk::kSkip; return false; }
         std::memcpy(h_meta[i].xform, E, sizeof(float) * 12);
-        prh::mat4_mul(E, r.T, r.T);                                                       // icp.cu:212
         h_meta[i].state = prk::kRunWithTransform;
         return true;
     };
@@ -436,6 +444,45 @@ int pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, co
     note_write(cloud_dev, sizeof(pr_vec3) * (size_t)n_points);
     out.release();
     if (e != hipSuccess) { (void)hipGetLastError(); set_error("pr_debug_contrib29: %s", hipGetErrorString(e)); return PR_ERR_HIP; }
+    return PR_OK;
+}
+
+// Audit entry: one iteration of icp.cu:178-212 on given sums, through the device's wavefront iteration (icp_solve_device.h, what the
+// fused pass tail and icp_finalize_solve_kernel run) or through the host-solve loop's pose_iteration_host.
+int pr_debug_pose_iteration(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, int on_device,
+                            pr_result *state, float *update_out, uint32_t *finished_out)
+{
+    if (n == 0) return PR_OK;
+    if (!sums || !n_points || !state || !update_out || !finished_out) { set_error("pr_debug_pose_iteration: null buffer"); return PR_ERR_INVALID; }
+    if (!on_device) {                                            // host code only: no device needed
+        for (uint32_t i = 0; i < n; ++i) {
+            float E[16];
+            const bool go_on = pose_iteration_host(sums + (size_t)i * 29, n_points[i], state[i], crit, iter, E);
+            for (int k = 0; k < 16; ++k) update_out[(size_t)i * 16 + k] = go_on ? E[k] : 0.0f;
+            finished_out[i] = go_on ? 0u : 1u;
+        }
+        return PR_OK;
+    }
+    PR_ENTER();
+    const size_t b_sums = sizeof(float) * 29 * n, b_cnt = sizeof(uint32_t) * n, b_st = sizeof(pr_result) * n, b_upd = sizeof(float) * 16 * n;
+    DevBuf buf;
+    PR_TRY(buf.ensure(b_sums + b_cnt + b_st + b_upd + b_cnt));
+    char *base = static_cast<char *>(buf.p);
+    float *d_sums = reinterpret_cast<float *>(base);
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(base + b_sums);
+    pr_result *d_st = reinterpret_cast<pr_result *>(base + b_sums + b_cnt);
+    float *d_upd = reinterpret_cast<float *>(base + b_sums + b_cnt + b_st);
+    uint32_t *d_fin = reinterpret_cast<uint32_t *>(base + b_sums + b_cnt + b_st + b_upd);
+    hipError_t e = hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cnt, n_points, b_cnt, hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_st, state, b_st, hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = prk::launch_pose_iteration_debug(d_sums, d_cnt, n, crit, iter, d_st, d_upd, d_fin, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(state, d_st, b_st, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(update_out, d_upd, b_upd, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(finished_out, d_fin, b_cnt, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    buf.release();
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("pr_debug_pose_iteration: %s", hipGetErrorString(e)); return PR_ERR_HIP; }
     return PR_OK;
 }
 

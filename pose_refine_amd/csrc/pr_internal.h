@@ -216,6 +216,9 @@ hipError_t launch_icp_pass_nn_winners(const IcpBatch &b, const SceneNNWinners &s
 hipError_t launch_contrib29_proj_aos(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjAoS &sc, float *out, hipStream_t s);
 hipError_t launch_contrib29_proj_packed(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjPacked &sc, float *out, hipStream_t s);
 hipError_t launch_contrib29_nn(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneNNDev &sc, float *out, hipStream_t s);
+// one iteration of pose_iteration_wave per hypothesis on given sums (pr_debug_pose_iteration): one wavefront each
+hipError_t launch_pose_iteration_debug(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, pr_result *state,
+                                       float *update, uint32_t *finished, hipStream_t s);
 // info[0] = 1 when every scene point owns a grid cell (the grid may be used), 0 otherwise
 // grid: gw*gh cells followed by the three pyramid levels (nn_grid_cells(gw, gh) cells in all)
 size_t nn_grid_cells(uint32_t gw, uint32_t gh);

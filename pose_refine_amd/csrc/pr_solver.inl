@@ -7,11 +7,14 @@
 //     |diagonal| entry, pseudo-inverse of D with tolerance 1/DBL_MAX;
 //   * AngleAxisd(z)*AngleAxisd(y)*AngleAxisd(x) -- composed as unit quaternions, then
 //     Quaterniond::toRotationMatrix.
-// The same source is compiled for the host (PR_SOLVE_HOST, pr_solve_666) and for the device
-// (PR_SOLVE_DEVICE finalize kernel).  sin/cos come from the fixed polynomial below rather than
-// libm/ocml so that both builds produce bit-identical updates (all operations are IEEE double
-// add/mul/div with contraction disabled); it is accurate to < 1 ulp on |x| <= pi/4 and uses a
-// two-term Cody-Waite reduction beyond.
+// The host solver (pr_solve_666, the host-solve loop) runs this source as it stands.  The device runs
+// a wavefront-cooperative restatement of ldlt6 / solve_666_impl (icp_solve_device.h,
+// pose_iteration_wave) that shares sincos_d, compose_update and mat4_mul_impl with it and performs
+// the same IEEE operations in the same order; tests/test_solve_gpu.py holds the two to bit identity
+// (pr_debug_pose_iteration).  sin/cos come from the fixed polynomial below rather than libm/ocml so
+// that both builds produce bit-identical updates (all operations are IEEE double add/mul/div with
+// contraction disabled).  Accuracy (tests/test_solve_ref.py): < 1 ulp on |x| <= pi/4; beyond, a
+// four-piece Cody-Waite reduction keeps the error within 1 ulp(1.0) up to the |x| < 1e9 cut-off.
 #pragma once
 
 #ifndef PR_HD
@@ -51,12 +54,16 @@ PR_HD inline void sincos_d(double x, double *s, double *c)
     if (dabs(x) <= quarter_pi) { *s = ksin(x); *c = kcos(x); return; }
     if (!(dabs(x) < 1.0e9)) { *s = 0.0; *c = 1.0; return; }            // non-finite / absurd update
     const double two_over_pi = 0.63661977236758134308;
-    const double pio2_hi = 1.57079632673412561417e+00;                 // first 33 bits of pi/2
-    const double pio2_lo = 6.07710050650619224932e-11;                 // pi/2 - pio2_hi
+    // pi/2 in four pieces (Cody-Waite): the first three hold at most 22 significant bits each, so fn * piece is exact for
+    // |n| < 2^31 and the subtractions lose nothing that matters; the fourth is the double nearest the remainder
+    const double pio2_1 = 0x1.921fb0p+0;
+    const double pio2_2 = 0x1.5110b0p-22;
+    const double pio2_3 = 0x1.184698p-44;
+    const double pio2_4 = 0x1.3198a2e037073p-69;
     double t = x * two_over_pi;
     long long n = (long long)(t < 0 ? t - 0.5 : t + 0.5);
     double fn = (double)n;
-    double r = (x - fn * pio2_hi) - fn * pio2_lo;
+    double r = (((x - fn * pio2_1) - fn * pio2_2) - fn * pio2_3) - fn * pio2_4;
     double sr = ksin(r), cr = kcos(r);
     switch ((int)(n & 3)) {
         case 0:  *s = sr;  *c = cr;  break;

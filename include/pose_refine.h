@@ -305,6 +305,29 @@ int  pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const ui
                           uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
                           int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host);
 
+/* ---- detections from a scored batch: which hypotheses explain the same scene pixels ------------------------------------------------------
+ * The support of hypothesis i is the set of frame pixels pr_score_poses counts as `inlier` for it (rendered, s > 0, |r - s| <= tau_mm).
+ * pr_score_overlap scores a batch exactly as pr_score_poses does -- scores_host is byte for byte the same -- and also returns
+ * overlap_host[i * n_poses + j] = the number of frame pixels in the support of both i and j: symmetric, the diagonal equals
+ * scores_host[i].inlier, rows and columns in the caller's pose order.  In a mixed batch (pr_score_overlap_multi, arguments as
+ * pr_score_poses_multi) hypotheses of different meshes are compared like any other pair.  Argument checks, ROI, scene types and the
+ * synchronous behaviour are those of pr_score_poses / pr_score_poses_multi; n_poses == 0 returns PR_OK and writes nothing; n_poses above
+ * PR_OVERLAP_MAX_POSES is PR_ERR_INVALID.  The device keeps one bit per frame pixel and hypothesis while the call runs
+ * (n_poses x height x ceil(width / 64) x 8 bytes) and the matrix (4 n_poses^2 bytes, once on the device and once in pinned memory). */
+#define PR_OVERLAP_MAX_POSES 4096     /* a 64 MB matrix */
+int  pr_score_overlap(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses,
+                      uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi,
+                      const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host, uint32_t *overlap_host);
+int  pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                            uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                            int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host, uint32_t *overlap_host);
+/* Greedy selection, host only (needs no device).  order: n_order indices, best first, each < n_poses and none twice (else PR_ERR_INVALID);
+ * overlap: an n_poses x n_poses matrix as above.  Walks order; skips i when overlap[i][i] == 0; accepts i unless an already accepted j has
+ * overlap[i][j] * shared_den > shared_num * min(overlap[i][i], overlap[j][j]) (64-bit integers, no floats).  selected_out (room for n_order
+ * indices) receives the accepted ones in acceptance order, *n_selected their number.  shared_den == 0 is PR_ERR_INVALID. */
+int  pr_select_greedy(const uint32_t *order, uint32_t n_order, const uint32_t *overlap, uint32_t n_poses,
+                      uint32_t shared_num, uint32_t shared_den, uint32_t *selected_out, uint32_t *n_selected);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

@@ -120,6 +120,9 @@ SIGNATURES = {
     "pr_render_multi": (_i32, [_vp, _u32, _vp, _vp, _sz, _sz, _sz, _vp, Roi, _vp]),
     "pr_refine_batch_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, Roi, _vp, _vp]),
     "pr_score_poses_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp]),
+    "pr_score_overlap": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),
+    "pr_score_overlap_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),
+    "pr_select_greedy": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, _vp, C.POINTER(_u32)]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

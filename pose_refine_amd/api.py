@@ -735,6 +735,73 @@ def score_poses_multi(meshes, mesh_index, poses, width: int, height: int, proj, 
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# detections: which hypotheses explain the same scene pixels, and a conflict-free choice among them
+# ------------------------------------------------------------------------------------------------
+OVERLAP_MAX_POSES = 4096                # PR_OVERLAP_MAX_POSES
+
+
+def score_overlap(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, roi: Sequence[int] = (0, 0, 0, 0)):
+    """``pr_score_overlap``: ``score_poses`` plus the matrix of shared inlier pixels.  Returns (SCORE[P], uint32[P, P]): the records are
+    ``score_poses``' bytes, ``overlap[i, j]`` counts the frame pixels that are inliers of both i and j (symmetric; the diagonal is
+    ``scores["inlier"]``).  At most ``OVERLAP_MAX_POSES`` hypotheses per call."""
+    td = _tris_dev(tris)
+    poses = _f32(poses, (-1, 16))
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    out = np.zeros(len(poses), SCORE)
+    ov = np.zeros((len(poses), len(poses)), np.uint32)
+    check(_lib.load().pr_score_overlap(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                       sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out), ptr(ov)))
+    return out, ov
+
+
+def score_overlap_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int,
+                        roi: Sequence[int] = (0, 0, 0, 0)):
+    """``pr_score_overlap_multi``: ``score_overlap`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; hypotheses of different
+    meshes are compared like any other pair.  (SCORE[P], uint32[P, P]) in pose order."""
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    out = np.zeros(len(poses), SCORE)
+    ov = np.zeros((len(poses), len(poses)), np.uint32)
+    check(_lib.load().pr_score_overlap_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                             sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out), ptr(ov)))
+    return out, ov
+
+
+def select_greedy(order, overlap, shared_num: int, shared_den: int) -> np.ndarray:
+    """``pr_select_greedy`` (host only): walk ``order`` (indices, best first); skip i when ``overlap[i, i] == 0``; accept i unless an
+    accepted j has ``overlap[i, j] * shared_den > shared_num * min(overlap[i, i], overlap[j, j])``.  Accepted indices in that order."""
+    ov = np.ascontiguousarray(overlap, np.uint32)
+    if ov.ndim != 2 or ov.shape[0] != ov.shape[1]:
+        raise ValueError(f"overlap must be a square matrix, got shape {ov.shape}")
+    od = np.asarray(order)
+    if od.ndim != 1 or (len(od) and (od.dtype.kind not in "iu" or od.min() < 0 or od.max() > 0xffffffff)):
+        raise ValueError("order must be a 1-d array of non-negative integers")
+    if not 0 <= int(shared_num) <= 0xffffffff or not 0 <= int(shared_den) <= 0xffffffff:
+        raise ValueError("shared_num and shared_den must fit 32 unsigned bits")
+    od = np.ascontiguousarray(od, np.uint32)
+    sel = np.zeros(max(1, len(od)), np.uint32)
+    n = C.c_uint32(0)
+    check(_lib.load().pr_select_greedy(ptr(od), len(od), ptr(ov), len(ov), int(shared_num), int(shared_den), ptr(sel), C.byref(n)))
+    return sel[:n.value].astype(np.int64)
+
+
+def select_hypotheses(scores, overlap, max_shared: Sequence[int] = (1, 4), min_fraction: float = 0.0, order=None) -> np.ndarray:
+    """Detections from a scored batch: indices of the hypotheses that survive, best first.  ``order`` defaults to
+    ``rank_hypotheses(scores)``, the one definition of "better".  Hypotheses whose rank fraction ``inlier / (visible - occluded)`` is below
+    ``min_fraction`` leave ``order`` first; the rest go through ``select_greedy``: a hypothesis is dropped when it shares more than
+    ``max_shared = (num, den)`` of the smaller of the two supports with a better one already accepted.  The same call serves a mixed
+    batch: conflicts between meshes are resolved by the one global order."""
+    sc = np.asarray(scores)
+    order = rank_hypotheses(sc) if order is None else np.asarray(order, np.int64)
+    den = sc["visible"].astype(np.int64) - sc["occluded"].astype(np.int64)
+    frac = np.where(den <= 0, 0.0, sc["inlier"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
+    order = order[frac[order] >= float(min_fraction)]
+    return select_greedy(order, overlap, int(max_shared[0]), int(max_shared[1]))
+
+
 def rank_hypotheses_per_mesh(scores, mesh_index) -> dict:
     """``rank_hypotheses`` within each mesh of a mixed batch: {mesh: indices into the whole batch, best first}.  Only meshes that have
     hypotheses appear."""

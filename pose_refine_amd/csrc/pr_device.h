@@ -82,6 +82,18 @@ __device__ __forceinline__ uint32_t fingerprint_lane(const uint32_t *__restrict_
     return h;
 }
 
+// wave64 sum of one uint32 per lane, the same value in every lane: in-row inclusive scan with DPP row shifts (lanes shifted in from outside
+// the row read 0), then the four row totals by readlane (nn_search.hip's prefix sum, total only).  Integer adds: exact in any order.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x)
+{
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);      // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);      // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);      // row_shr:4
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);      // row_shr:8
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 15) + (uint32_t)__builtin_amdgcn_readlane((int)x, 31) +
+           (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+
 constexpr uint32_t kBoxRowsPerBlock = 16;                        // rows of a pixel box per workgroup: 4 wavefronts x 4 rows (few, fatter workgroups: dispatch-bound otherwise)
 
 // box_off (fused asynchronous path): the boxes of a sub-batch PACKED one behind the other, each as its own little image (pitch = its width) at

@@ -751,6 +751,37 @@ void pr_refined_poses(const pr_result *results, const pr_mat4 *poses, uint32_t n
     }
 }
 
+// greedy conflict-free selection over a ranking: integers only, so a selection is reproducible on any host
+int pr_select_greedy(const uint32_t *order, uint32_t n_order, const uint32_t *overlap, uint32_t n_poses, uint32_t shared_num, uint32_t shared_den,
+                     uint32_t *selected_out, uint32_t *n_selected)
+{
+    if (!n_selected || shared_den == 0 || (n_order && (!order || !overlap || !selected_out))) {
+        prh::set_error(shared_den == 0 && n_selected ? "pr_select_greedy: shared_den must not be 0" : "pr_select_greedy: bad arguments");
+        return PR_ERR_INVALID;
+    }
+    std::vector<unsigned char> seen(n_poses, 0);
+    for (uint32_t k = 0; k < n_order; ++k) {
+        if (order[k] >= n_poses) { prh::set_error("pr_select_greedy: order[%u] = %u, but there are %u hypotheses", k, order[k], n_poses); return PR_ERR_INVALID; }
+        if (seen[order[k]]) { prh::set_error("pr_select_greedy: order[%u] = %u appears twice", k, order[k]); return PR_ERR_INVALID; }
+        seen[order[k]] = 1;
+    }
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < n_order; ++k) {
+        const uint32_t i = order[k];
+        const uint64_t own = overlap[(size_t)i * n_poses + i];
+        if (own == 0) continue;                                      // explains no scene pixel
+        bool keep = true;
+        for (uint32_t a = 0; a < n && keep; ++a) {
+            const uint32_t j = selected_out[a];
+            const uint64_t other = overlap[(size_t)j * n_poses + j], shared = overlap[(size_t)i * n_poses + j];
+            keep = !(shared * shared_den > (uint64_t)shared_num * std::min(own, other));      // all factors < 2^32: no overflow
+        }
+        if (keep) selected_out[n++] = i;
+    }
+    *n_selected = n;
+    return PR_OK;
+}
+
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count)
 {
     // contiguous blocks; the first (n % world) ranks take one extra item

@@ -194,6 +194,13 @@ hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_ind
 // records[8 * i] (pr_pose_score words: visible, inlier, occluded, violation, missing, reserved, abs_err_sum lo / hi), which the caller zeroed
 hipError_t launch_score_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
                               const void *scene, bool scene_i32, int32_t tau, uint32_t *records, hipStream_t s);
+// select.hip: the inlier pixels of launch_score_boxes as one bit plane per hypothesis -- dense, height x overlap_words_per_row(width) 64-bit words,
+// bit b of word w of image row y = frame pixel (64 w + b, y); only the words a hypothesis' box touches are written, and only those are read --
+// and mat[i * n + j] = the number of pixels set in both planes, for every pair (bbox: the boxes the planes were written with, all n of them)
+inline uint32_t overlap_words_per_row(uint32_t width) { return (width + 63) / 64; }
+hipError_t launch_support_bits(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
+                               const void *scene, bool scene_i32, int32_t tau, unsigned long long *planes, hipStream_t s);
+hipError_t launch_pair_overlap(const unsigned long long *planes, const int4 *bbox, uint32_t n_poses, uint32_t width, uint32_t height, uint32_t *mat, hipStream_t s);
 hipError_t launch_pack_export(const DevIcpState *st, pr_result *out, const uint32_t *counts, uint32_t *host_counts, pr_result *host_results,
                               uint32_t n, hipStream_t s);
 hipError_t launch_stage_words(const void *src_host_mapped, void *dst, size_t bytes, hipStream_t s);

@@ -282,8 +282,11 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
 // refine_impl's render (staged poses, model box, per-pose pixel boxes packed one behind the other) followed by one kernel that compares every
 // rendered box pixel with the scene frame.  Everything runs on the context's own stream and workspaces, which no asynchronous slot owns, so a
 // batch pending on a slot is neither waited for nor disturbed.  The scene is read as it is on every call: nothing derived from it is kept.
+// overlap_host (pr_score_overlap; null: scores only): the P x P matrix of shared inlier pixels, in the order of poses_host.  Every chunk also leaves
+// its hypotheses' support bits (select.hip) and pixel boxes in workspaces sized for all P -- g->depth and g->bbox belong to the next chunk as soon
+// as this one is scored -- and one launch over all pairs follows the last chunk.  The planes are dense: P x H x ceil(W / 64) words of 8 bytes.
 int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
-               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host)
+               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr)
 {
     if (tau < 0) { set_error("pr_score_poses: tau_mm must be >= 0 (got %d)", (int)tau); return PR_ERR_INVALID; }
     if (!proj || W == 0 || H == 0 || (P && (!poses_host || !scene_dev || !scores_host || (!src.tris && src.n_tris > 0)))) {
@@ -297,6 +300,13 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
     const size_t img = (size_t)W * H;
     const uint32_t chunk = depth_chunk(img, P);
     PR_TRY(model_boxes(src, chunk));
+    const size_t plane_words = (size_t)H * prk::overlap_words_per_row(W);
+    if (overlap_host) {
+        PR_TRY(g->ov_bits.ensure(sizeof(uint64_t) * plane_words * P));
+        PR_TRY(g->ov_box.ensure(sizeof(int4) * P));
+        PR_TRY(g->ov_mat.ensure(sizeof(uint32_t) * (size_t)P * P));
+        PR_TRY(g->h_ov.ensure(sizeof(uint32_t) * (size_t)P * P));
+    }
     for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
         const uint32_t np = std::min(chunk, P - p0);
         PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
@@ -315,19 +325,42 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         HIP_TRY(prk::launch_fill_i32(g->scores.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
         HIP_TRY(prk::launch_score_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
                                         g->scores.as<uint32_t>(), g->stream));
+        if (overlap_host) {
+            HIP_TRY(prk::launch_support_bits(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
+                                             g->ov_bits.as<unsigned long long>() + plane_words * p0, g->stream));
+            HIP_TRY(prk::launch_copy_words32(g->bbox.p, g->ov_box.as<int4>() + p0, 4 * np, g->stream));
+        }
         void *hs = nullptr;
         HIP_TRY(hipHostGetDevicePointer(&hs, g->h_scores.p, 0));
         HIP_TRY(prk::launch_copy_words32(g->scores.p, hs, kWords * np, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         std::memcpy(scores_host + p0, g->h_scores.p, sizeof(pr_pose_score) * np);
     }
+    if (overlap_host) {
+        HIP_TRY(prk::launch_pair_overlap(g->ov_bits.as<unsigned long long>(), g->ov_box.as<int4>(), P, W, H, g->ov_mat.as<uint32_t>(), g->stream));
+        void *ho = nullptr;
+        HIP_TRY(hipHostGetDevicePointer(&ho, g->h_ov.p, 0));
+        HIP_TRY(prk::launch_copy_words32(g->ov_mat.p, ho, P * P, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        std::memcpy(overlap_host, g->h_ov.p, sizeof(uint32_t) * (size_t)P * P);
+    }
     drain_spans();
     return PR_OK;
 }
-int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
-               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host)
+// pr_score_overlap's own condition, checked before anything runs
+int overlap_args_ok(const char *fn, uint32_t P, const uint32_t *overlap_host)
 {
-    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host);
+    if (P > PR_OVERLAP_MAX_POSES) {
+        set_error("%s: %u hypotheses, but the overlap matrix is limited to PR_OVERLAP_MAX_POSES = %u (a 64 MB matrix)", fn, P, (uint32_t)PR_OVERLAP_MAX_POSES);
+        return PR_ERR_INVALID;
+    }
+    if (P && !overlap_host) { set_error("%s: bad arguments (overlap_host is null)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
+               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr)
+{
+    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, overlap_host);
 }
 
 // ---- mixed batches: the entry points' bodies (grouped batch in, outputs scattered back to the caller's order) -----------------------
@@ -360,7 +393,7 @@ int refine_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *m
 }
 
 int score_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                const pr_mat4 *proj, pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host)
+                const pr_mat4 *proj, pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr)
 {
     // the single-mesh call's checks first (tau, frame, ROI, pointers), with no hypotheses
     PR_TRY(score_core(MeshSource{ nullptr, 0, nullptr }, poses_host, 0, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host));
@@ -370,8 +403,12 @@ int score_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *me
     PR_TRY(plan_meshes("pr_score_poses_multi", meshes, n_meshes, mesh_index, P, pl));
     const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
     std::vector<pr_pose_score> sc(P);
-    PR_TRY(score_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, roi, scene_dev, scene_i32, tau, sc.data()));
+    std::vector<uint32_t> ov(overlap_host ? (size_t)P * P : 0);
+    PR_TRY(score_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, roi, scene_dev, scene_i32, tau, sc.data(), overlap_host ? ov.data() : nullptr));
     for (uint32_t j = 0; j < P; ++j) scores_host[pl.order[j]] = sc[j];
+    if (overlap_host)                                            // rows and columns back into the caller's order
+        for (uint32_t a = 0; a < P; ++a)
+            for (uint32_t b = 0; b < P; ++b) overlap_host[(size_t)pl.order[a] * P + pl.order[b]] = ov[(size_t)a * P + b];
     return PR_OK;
 }
 
@@ -1081,6 +1118,25 @@ int pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uin
 {
     PR_ENTER();
     return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host);
+}
+
+int pr_score_overlap(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                     const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host,
+                     uint32_t *overlap_host)
+{
+    PR_ENTER();
+    PR_TRY(overlap_args_ok("pr_score_overlap", n_poses, overlap_host));
+    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host, overlap_host);
+}
+
+int pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                           uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                           int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host, uint32_t *overlap_host)
+{
+    PR_ENTER();
+    PR_TRY(overlap_args_ok("pr_score_overlap_multi", n_poses, overlap_host));
+    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
+                       overlap_host);
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

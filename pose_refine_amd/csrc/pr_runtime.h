@@ -271,6 +271,8 @@ struct Ctx {
     // workspaces
     DevBuf aabb, aabb_keys, bbox, poses, depth, row_count, row_off, counts, cloud, meta, partial, sums, nn_prev, dstate, dresults, arrive, conv16, conv8, kd_scratch, kd_tmp, nn_full;
     DevBuf scores;                   // pr_score_poses: the records of a chunk
+    DevBuf ov_bits, ov_box, ov_mat;  // pr_score_overlap: the support bit planes and pixel boxes of ALL hypotheses of a call (they outlive its depth chunks), the P x P matrix
+    PinBuf h_ov;                     // the matrix on its way to the caller
     DevBuf multi;                    // mixed batches (pr_*_multi): mesh table, box index / image of each hypothesis, raster groups
     PinBuf h_sums, h_meta, h_counts, h_results, h_dstate, h_poses, h_flags, h_scores, h_multi;
     PackedCache packed;              // synchronous paths (the asynchronous slots keep their own)

@@ -4,18 +4,6 @@
 
 namespace prk {
 
-// wave64 sum of one uint32 per lane, the same value in every lane: in-row inclusive scan with DPP row shifts (lanes shifted in from outside
-// the row read 0), then the four row totals by readlane (nn_search.hip's prefix sum, total only).  Integer adds: exact in any order.
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x)
-{
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);      // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);      // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);      // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);      // row_shr:8
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 15) + (uint32_t)__builtin_amdgcn_readlane((int)x, 31) +
-           (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
-
 // One workgroup = 16 image rows of one hypothesis' box (count_box_kernel's shape: 4 wavefronts x 4 rows, lanes along a row).  A box pixel holds
 // the rendered depth r (INT_MAX where nothing was drawn); the frame pixel is (x, row) exactly as d2c_emit_box_kernel maps it, and the scene
 // value s is read from the same frame pixel (the frame stays in L2 / MALL, shared by every hypothesis).  Counts per lane in registers, a wave

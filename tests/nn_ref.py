@@ -1,0 +1,343 @@
+"""Plain reference of Scene_nn::query (pcd_scene.h:60-136) and the hard scenes the kd-tree tests run on (numpy + the CPU oracle only).
+
+BruteForce is the nearest neighbour by exhaustive search in the reference's own float32 arithmetic, ((dx*dx + dy*dy) + dz*dz)
+(pcd_scene.h:86-91): the minimum, every point that attains it, whether it is inside the acceptance radius and how far the runner-up is.
+The families are scenes on which the search's shortcuts -- kept winners, the pixel window and its bounds, the compact and wide records --
+have to hold their exactness arguments: clutter and depth edges, planted exact and near ties, wide-angle / off-centre / small frames, near
+and far depths, a scene searched under a camera it was not made with, distances on both sides of the acceptance radius, and camera-less
+degenerate point sets (coplanar, collinear, one repeated point, far from the origin on either side of the wide walk's frame test).
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+import oracle_lib as O
+from pose_refine_amd import synth
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+F32 = np.float32
+
+
+# ---- the reference ---------------------------------------------------------------------------------------------------------------
+def sq_dist(q, pts):
+    """(len(q), len(pts)) squared distances, float32, in the reference's order of operations (no fused multiply-add: numpy never fuses)."""
+    q = np.asarray(q, F32); pts = np.asarray(pts, F32)
+    dx = q[:, None, 0] - pts[None, :, 0]
+    dy = q[:, None, 1] - pts[None, :, 1]
+    dz = q[:, None, 2] - pts[None, :, 2]
+    return (dx * dx + dy * dy) + dz * dz
+
+
+class BruteForce:
+    """Per query: `d2` the minimum squared distance, `ties` the indices of the points that attain it, `inside` = d2 < max_dist^2
+    (both float32, as the scene computes `accept`), `gap` = runner-up distance minus the minimum (float32; inf for a scene of one
+    distinct distance)."""
+
+    def __init__(self, queries, pts, max_dist, chunk_elems=1 << 22):
+        q = np.ascontiguousarray(queries, F32).reshape(-1, 3)
+        pts = np.ascontiguousarray(pts, F32).reshape(-1, 3)
+        n = len(q)
+        self.d2 = np.empty(n, F32)
+        self.gap = np.empty(n, F32)
+        self.ties = []
+        step = max(1, chunk_elems // max(1, len(pts)))
+        for a in range(0, n, step):
+            d = sq_dist(q[a:a + step], pts)
+            m = d.min(1)
+            eq = d == m[:, None]
+            self.d2[a:a + step] = m
+            self.ties.extend(np.flatnonzero(r) for r in eq)
+            d[eq] = np.inf
+            self.gap[a:a + step] = d.min(1) - m
+        self.accept = F32(max_dist) * F32(max_dist)
+        self.inside = self.d2 < self.accept
+
+    def n_ties(self):
+        return np.array([len(t) for t in self.ties])
+
+
+def gap_ulps(bf):
+    """Runner-up gap of every query in ulps of its minimum (0 for an exact tie)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.where(bf.n_ties() > 1, 0.0, bf.gap / np.spacing(np.maximum(bf.d2, F32(1e-38))))
+
+
+def check_oracle_against_brute_force(oscene, queries, bf):
+    """The reference's stackless walk returns brute force's distance, a point of its tie set, and a correspondence exactly when the
+    minimum is inside the acceptance radius.  Returns the number of queries checked."""
+    for i, q in enumerate(np.asarray(queries, F32)):
+        ok, win, d2, _ = oscene.query(q)
+        assert F32(d2) == bf.d2[i], (i, q, d2, bf.d2[i])
+        assert win in bf.ties[i], (i, q, win, bf.ties[i][:8])
+        assert bool(ok) == bool(bf.inside[i]), (i, q, ok, bf.d2[i], bf.accept)
+    return len(queries)
+
+
+# ---- inputs ----------------------------------------------------------------------------------------------------------------------
+def kvec(fx, fy, cx, cy):
+    return np.array([fx, 0, cx, 0, fy, cy, 0, 0, 1], F32)
+
+
+def obj06():
+    return O.ply_load(os.path.join(GOLDEN, "obj_06.ply"))
+
+
+def frame_inside_wall_rect(W, H, frac):
+    """(x0, x1, y0, y1): the centred rectangle covering `frac` of each side."""
+    mx, my = int(W * (1 - frac) / 2), int(H * (1 - frac) / 2)
+    return mx, W - mx, my, H - my
+
+
+def compose(*layers):
+    """Nearest non-zero depth of several int32 layers (the z-buffer of a scene made of them)."""
+    out = np.zeros_like(layers[0], dtype=np.int64)
+    for L in layers:
+        L = L.astype(np.int64)
+        take = (L > 0) & ((out == 0) | (L < out))
+        out[take] = L[take]
+    return out.astype(np.int32)
+
+
+def wavy(W, H, z0, amp, tilt=(0.0, 0.0), phase=0.0):
+    """A smooth surface with depth edges of its own (a raised box on it is added by the callers): depth (mm, int32) per pixel."""
+    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    z = z0 + amp * np.sin(2 * np.pi * u / W * 1.5 + phase) * np.cos(2 * np.pi * v / H) + tilt[0] * (u - W / 2) + tilt[1] * (v - H / 2)
+    return np.rint(z).astype(np.int32)
+
+
+def box_layer(W, H, rect, z, slope=0.0):
+    x0, x1, y0, y1 = rect
+    out = np.zeros((H, W), np.int32)
+    u = np.arange(x0, x1, dtype=np.float64)
+    out[y0:y1, x0:x1] = np.rint(z + slope * (u - x0))[None, :].astype(np.int32)
+    return out
+
+
+def perturb(depth, rng, frac_noise=0.4, amp=2, frac_holes=0.05):
+    d = depth.astype(np.int64).copy()
+    noisy = rng.random(d.shape) < frac_noise
+    d[noisy] += rng.choice(np.array([-amp, -1, 1, amp]), size=int(noisy.sum()))
+    d[rng.random(d.shape) < frac_holes] = 0
+    d[d < 0] = 0
+    return d.astype(np.int32)
+
+
+def rigid(cloud, deg, shift, rng):
+    """Turn the cloud by `deg` degrees about a random axis through its centroid and move it by `shift` (metres, a random direction)."""
+    a = rng.normal(size=3); a /= np.linalg.norm(a)
+    t = np.deg2rad(deg)
+    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    R = np.eye(3) + np.sin(t) * Kx + (1 - np.cos(t)) * Kx @ Kx
+    d = rng.normal(size=3); d *= shift / np.linalg.norm(d)
+    c = cloud.astype(np.float64).mean(0)
+    return np.ascontiguousarray(((cloud - c) @ R.T + c + d).astype(F32))
+
+
+def surface_clouds(depth, K, rng, n_clouds, dz_mm, deg, shift, max_points=20000):
+    """Clouds near a depth-image surface: the image moved `dz_mm` in depth and a few pixels sideways, turned and shifted a little."""
+    out = []
+    for i in range(n_clouds):
+        d = np.roll(depth, (i + 1, 2 * i - 1), axis=(0, 1)).astype(np.int64)
+        d = np.where(d > 0, d + dz_mm * (1 + i), 0).astype(np.int32)
+        cl = O.depth2cloud(d, K)
+        cl = cl[:: max(1, len(cl) // max_points + 1)]
+        out.append(rigid(cl, deg * (1 + 0.5 * i), shift * (1 + 0.5 * i), rng))
+    return out
+
+
+class Family:
+    """A scene with the clouds to query it with.  Depth families: `depth` (int32 or uint16) + `K`, scene made from the image; the fused
+    families also carry `tris` + `poses` (+ `K_fused`, the hypotheses' camera).  Point families (no camera): `pts`, `nrm`."""
+
+    def __init__(self, name, clouds, max_dist=0.1, depth=None, K=None, pts=None, nrm=None, tris=None, poses=None, K_fused=None, max_leaf=10):
+        self.name, self.clouds, self.max_dist, self.depth, self.K = name, clouds, max_dist, depth, K
+        self.pts, self.nrm, self.tris, self.poses, self.K_fused, self.max_leaf = pts, nrm, tris, poses, K_fused, max_leaf
+        if depth is not None:
+            self.H, self.W = depth.shape
+
+    def as_dtype(self, dtype):
+        """The same family with the depth image stored as `dtype` (int32 / uint16: the depths here fit both)."""
+        assert self.depth is not None and int(self.depth.max()) <= 65535 and int(self.depth.min()) >= 0
+        f = Family(self.name + ("_u16" if dtype == np.uint16 else "_i32"), self.clouds, self.max_dist, self.depth.astype(dtype), self.K,
+                   tris=self.tris, poses=self.poses, K_fused=self.K_fused, max_leaf=self.max_leaf)
+        return f
+
+    def oracle_scene(self):
+        if self.depth is not None:
+            return O.NNScene(self.depth, self.K, self.max_dist, self.max_leaf)
+        return O.NNScene.from_points(self.pts, self.nrm, self.max_dist, self.max_leaf)
+
+
+def render_clouds(tris, poses, K, W, H):
+    depth = O.render(tris, poses, W, H, O.compute_proj(K, W, H))
+    return [O.depth2cloud(d, K) for d in depth]
+
+
+# ---- the families ----------------------------------------------------------------------------------------------------------------
+def f1_clutter(n_hyp=6):
+    """F1: obj_06 at the scene pose in front of a tilted wall ~900 mm behind it and a box of clutter at 450 mm; 40 % of the pixels
+    moved by up to 2 mm, 5 % holes.  Clouds: renders of the hypotheses (synth.hypotheses)."""
+    W, H, K = synth.WIDTH, synth.HEIGHT, synth.K_TEST
+    tris = obj06()
+    obj = O.render(tris, synth.scene_pose()[None], W, H, O.compute_proj(K, W, H))[0]
+    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    wall = np.rint(1220.0 + 0.45 * (u - W / 2) + 0.2 * (v - H / 2)).astype(np.int32)
+    box = box_layer(W, H, (60, 260, 300, 460), 450.0, slope=0.3)
+    depth = perturb(compose(obj, box, wall), np.random.default_rng(11))
+    poses = synth.hypotheses(n_hyp)
+    return Family("F1_clutter", render_clouds(tris, poses, K, W, H), depth=depth, K=K, tris=tris, poses=poses)
+
+
+def f2_ties(near=None):
+    """F2: fronto-parallel plane at 500 mm, integer principal point, holes along the principal column and row; the cloud lies on those
+    lines at 503 mm, so each query has mirror-image nearest points at bitwise equal distance.  `near`: the lines moved to one side --
+    "um": by 2 um, the two candidates differ by a hair; "ulp": by 0.5 nm, their squared distances differ by a few ulps."""
+    W, H = 640, 480
+    K = kvec(600.0, 600.0, 320.0, 240.0)
+    depth = np.full((H, W), 500, np.int32)
+    depth[:, 320] = 0
+    depth[240, :] = 0
+    z = F32(0.503)
+    off = {None: F32(0.0), "um": F32(2e-6), "ulp": F32(5e-10)}[near]
+    v = np.arange(0, H, dtype=F32); u = np.arange(0, W, dtype=F32)
+    col = np.stack([np.full(H, off, F32), (v - F32(240.0)) / F32(600.0) * z, np.full(H, z, F32)], 1)
+    row = np.stack([(u - F32(320.0)) / F32(600.0) * z, np.full(W, off, F32), np.full(W, z, F32)], 1)
+    cloud = np.ascontiguousarray(np.concatenate([col, row]).astype(F32))
+    second = np.ascontiguousarray(cloud[::2].copy())
+    return Family({None: "F2_ties", "um": "F2_near_ties", "ulp": "F2_ulp_ties"}[near], [cloud, second], depth=depth, K=K)
+
+
+def f3_wide():
+    """F3: fx = 0.3 W with the principal point at 10 % of the width: |x| / z up to 3 at the far edge (the window-radius formula)."""
+    W, H = 640, 480
+    K = kvec(0.3 * W, 0.3 * W, 0.1 * W, 0.5 * H + 7.25)
+    depth = compose(box_layer(W, H, (380, 520, 120, 300), 430.0, slope=0.2), wavy(W, H, 600.0, 80.0, tilt=(0.1, -0.05)))
+    depth = perturb(depth, np.random.default_rng(31))
+    return Family("F3_wide", surface_clouds(depth, K, np.random.default_rng(32), 3, 3, 1.0, 0.004), depth=depth, K=K)
+
+
+def f3_small(W, H):
+    """F3: frames below the 320-pixel ring width (the other branch of grid_pyramid_bound)."""
+    K = kvec(1.1 * W, 1.1 * W, 0.5 * W - 0.7, 0.5 * H + 0.4)
+    depth = compose(box_layer(W, H, (W // 5, W // 2, H // 4, 3 * H // 4), 380.0, slope=0.5), wavy(W, H, 520.0, 60.0, tilt=(0.2, 0.1)))
+    depth = perturb(depth, np.random.default_rng(W))
+    return Family(f"F3_{W}x{H}", surface_clouds(depth, K, np.random.default_rng(W + 1), 3, 3, 1.5, 0.003), depth=depth, K=K)
+
+
+def f4_near():
+    """F4: a scene 15-40 mm from the camera: windows many pixels wide, the fallbacks take over."""
+    W, H, K = synth.WIDTH, synth.HEIGHT, synth.K_TEST
+    depth = compose(box_layer(W, H, (100, 260, 80, 240), 16.0, slope=0.02), wavy(W, H, 28.0, 10.0, tilt=(0.004, 0.003)))
+    depth = perturb(depth, np.random.default_rng(41), amp=1)
+    return Family("F4_near", surface_clouds(depth, K, np.random.default_rng(42), 3, 1, 2.0, 0.0005), depth=depth, K=K)
+
+
+def f4_far():
+    """F4: a scene 40-65 m away (uint16 depth near its top)."""
+    W, H, K = synth.WIDTH, synth.HEIGHT, synth.K_TEST
+    depth = compose(box_layer(W, H, (380, 560, 260, 420), 43000.0, slope=10.0), wavy(W, H, 52000.0, 9000.0, tilt=(6.0, 4.0)))
+    depth = np.clip(perturb(depth, np.random.default_rng(43), amp=20), 0, 65000).astype(np.int32)
+    return Family("F4_far", surface_clouds(depth, K, np.random.default_rng(44), 3, 40, 0.3, 0.05), depth=depth, K=K)
+
+
+def f5_mismatch(n_hyp=6):
+    """F5: the scene is made with K; the fused refinement renders and searches with K' (fx + 2 %, cx + 3 px).  The scene keeps clear of
+    the image border, so every scene point still owns a pixel of its own under K'."""
+    W, H, K = synth.WIDTH, synth.HEIGHT, synth.K_TEST
+    Kf = K.copy(); Kf[0] = K[0] * F32(1.02); Kf[2] = K[2] + F32(3.0)
+    tris = obj06()
+    obj = O.render(tris, synth.scene_pose()[None], W, H, O.compute_proj(K, W, H))[0]
+    rect = frame_inside_wall_rect(W, H, 0.8)
+    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    wall = np.rint(1100.0 + 0.3 * (u - W / 2) - 0.2 * (v - H / 2)).astype(np.int32)
+    x0, x1, y0, y1 = rect
+    inside = np.zeros((H, W), bool); inside[y0:y1, x0:x1] = True
+    wall[~inside] = 0
+    box = box_layer(W, H, (120, 250, 300, 380), 460.0, slope=0.25)
+    depth = perturb(compose(obj, box, wall), np.random.default_rng(51), frac_holes=0.03)
+    depth[~inside] = 0
+    poses = synth.hypotheses(n_hyp)
+    return Family("F5_mismatch", render_clouds(tris, poses, Kf, W, H), depth=depth, K=K, tris=tris, poses=poses, K_fused=Kf)
+
+
+def f6_accept():
+    """F6: max_dist_diff = 0.01 and a cloud 10 mm in front of a fronto-parallel plane, spread by +-4 um in depth: the squared
+    distances fall on both sides of accept = 0.01f * 0.01f."""
+    W, H, K = synth.WIDTH, synth.HEIGHT, synth.K_TEST
+    depth = np.full((H, W), 500, np.int32)
+    pcd = O.depth2cloud(depth, K)
+    rng = np.random.default_rng(61)
+    sel = pcd[rng.choice(len(pcd), 6000, replace=False)]
+    cloud = sel.copy()
+    cloud[:, 2] = (sel[:, 2] - F32(0.01) + rng.uniform(-4e-6, 4e-6, len(sel)).astype(F32)).astype(F32)
+    return Family("F6_accept", [np.ascontiguousarray(cloud), np.ascontiguousarray(cloud[::3])], max_dist=0.01, depth=depth, K=K)
+
+
+def _normals(rng, n):
+    nrm = rng.normal(size=(n, 3)).astype(F32)
+    return (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(F32)
+
+
+def _near_clouds(pts, rng, sigma, n=(2000, 1200)):
+    out = []
+    for k in n:
+        c = pts[rng.integers(0, len(pts), k)].astype(np.float64) + rng.normal(size=(k, 3)) * sigma
+        out.append(np.ascontiguousarray(c.astype(F32)))
+    return out
+
+
+def degenerate(kind):
+    """Camera-less point sets for bare ICP: coplanar (z extent 0), collinear (y and z extent 0), one point 500 times, a 0.2 m cube
+    40 m / 60 m from the origin (either side of the wide walk's frame test, info[20])."""
+    rng = np.random.default_rng({"coplanar": 71, "collinear": 72, "repeated": 73, "far40": 74, "far60": 75}[kind])
+    if kind == "coplanar":
+        pts = np.stack([rng.uniform(-0.1, 0.1, 3000), rng.uniform(-0.1, 0.1, 3000), np.full(3000, 0.3)], 1).astype(F32)
+        sigma = 0.004
+    elif kind == "collinear":
+        pts = np.stack([rng.uniform(-0.1, 0.1, 3000), np.full(3000, 0.05), np.full(3000, 0.3)], 1).astype(F32)
+        sigma = 0.004
+    elif kind == "repeated":
+        pts = np.tile(np.array([[0.01, 0.02, 0.3]], F32), (500, 1))
+        sigma = 0.02
+    else:
+        off = 40.0 if kind == "far40" else 60.0
+        pts = (rng.uniform(-0.1, 0.1, size=(3000, 3)) + np.array([off, 0.0, 0.0])).astype(F32)
+        sigma = 0.004
+    clouds = _near_clouds(pts, rng, sigma)
+    return Family("deg_" + kind, clouds, pts=np.ascontiguousarray(pts), nrm=_normals(rng, len(pts)))
+
+
+DEGENERATE = ("coplanar", "collinear", "repeated", "far40", "far60")
+
+
+def wide_frame_ok(nodes, max_dist):
+    """nn_frame_kernel's info[20] restated in float32: may the wide walk's integer box test run on a tree of root box `nodes[0]`?"""
+    bb = np.asarray(nodes[0]["bbox"], F32)
+    lo, hi = bb[0::2], bb[1::2]
+    margin = F32(max_dist) * F32(1.01)
+    edge = F32(max(F32(hi[0] - lo[0]), F32(hi[1] - lo[1]), F32(hi[2] - lo[2]))) + F32(2.0) * margin
+    wsc = F32(F32(edge / F32(65535.0)) * F32(1.000001))
+    cmax = F32(0.0)
+    for a in range(3):
+        cmax = max(cmax, abs(F32(lo[a] - margin)), abs(F32(hi[a] + margin)))
+    return bool(F32(cmax * F32(1.1920929e-7)) <= wsc and cmax < F32(1e30))
+
+
+def all_depth_families():
+    """(name -> Family) of every depth-image family (each once; the uint16 twins come from Family.as_dtype)."""
+    fams = [f1_clutter(), f2_ties(), f2_ties(near="um"), f2_ties(near="ulp"), f3_wide(), f3_small(97, 61), f3_small(300, 200), f4_near(), f4_far(),
+            f5_mismatch(), f6_accept()]
+    return {f.name: f for f in fams}
+
+
+def sample_queries(clouds, per_cloud, seed, which=None):
+    rng = np.random.default_rng(seed)
+    out = []
+    for i, c in enumerate(clouds):
+        if which is not None and i not in which:
+            continue
+        k = min(per_cloud, len(c))
+        out.append(c[np.sort(rng.choice(len(c), k, replace=False))])
+    return np.ascontiguousarray(np.concatenate(out).astype(F32))

@@ -196,6 +196,24 @@ class NNScene:
         self.desc = SceneNN(max_dist_diff, self.pcd.ctypes.data, self.normal.ctypes.data, self.nodes.ctypes.data)
         self.kind = SCENE_NN
 
+    @classmethod
+    def from_points(cls, pcd, normal, max_dist_diff=0.1, max_leaf=10, nodes=None):
+        """A scene of given points (no depth image): with `nodes` = a tree already built over `pcd` in its stored order (pr_kdtree_build's,
+        which reorders its arrays in place), else built here by po_kd_build over copies (reordered the same way)."""
+        out = object.__new__(cls)
+        out.K = None
+        out.pcd = np.array(pcd, dtype=np.float32, order="C", copy=True).reshape(-1, 3)
+        out.normal = np.array(normal, dtype=np.float32, order="C", copy=True).reshape(-1, 3)
+        if nodes is None:
+            buf = np.zeros(2 * len(out.pcd) + 1, KDNODE)
+            cnt = lib().po_kd_build(out.pcd.reshape(-1), out.normal.reshape(-1), len(out.pcd), max_leaf, buf.ctypes.data, len(buf))
+            nodes = buf[:cnt]
+        out.nodes = np.ascontiguousarray(np.asarray(nodes).view(KDNODE))
+        out.max_dist_diff = max_dist_diff
+        out.desc = SceneNN(max_dist_diff, out.pcd.ctypes.data, out.normal.ctypes.data, out.nodes.ctypes.data)
+        out.kind = SCENE_NN
+        return out
+
     def ptr(self):
         return C.addressof(self.desc)
 

@@ -27,8 +27,10 @@
  *
  * Caches and caller-owned memory.  Derived data is cached by the address of the buffers it was derived from: the packed copy
  * of a projective scene (pcd / normal arrays), the traversal records of a kd-tree scene (pcd / nodes arrays) and the model box
- * of a triangle buffer.  The model box is re-verified on the device by every batch that uses it, so a rewritten mesh is never
- * rendered with a stale box.  The scene caches are dropped by every write that goes through this library (pr_memcpy_*,
+ * of a triangle buffer together with a copy of the buffer in spatial order that the asynchronous path rasterises (option "mesh_order").
+ * Both are re-verified on the device by every batch that uses them -- the box, and an order-independent fingerprint of every word of the
+ * caller's buffer -- so a rewritten mesh is never rendered from stale data: its first batch is repeated from the caller's buffer (pr_stats).
+ * The scene caches are dropped by every write that goes through this library (pr_memcpy_*,
  * pr_fill_i32, pr_free, pr_render, the *_prepare_dev / *_build_dev / *_crop_dev functions); a caller that rewrites a scene
  * array by other means (its own kernels, raw hipMemcpy) MUST announce it with pr_invalidate(ptr, bytes) before the next ICP /
  * refine call, or switch the caches off with pr_set_option("scene_cache", 0).
@@ -359,6 +361,8 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *   "sub_batch"        [512]   asynchronous path: hypotheses per sub-batch (cache residency of the clouds)
  *   "overlap_pass"     [-1]    asynchronous path: the other slot's render may start after this pass of a slot's loop (-1 = chosen per batch)
  *   "raster_mode"      [0]     fused render: 0 = global atomicMin inside the pose's pixel box, 1 = LDS depth bands (synchronous path)
+ *   "mesh_order"       [1]     asynchronous path: the raster reads a library-owned copy of the triangle buffer in spatial order (made once per
+ *                              buffer, on its second batch in a row, checked against the caller's buffer by every batch; 36 bytes per triangle of device memory); 0 = the caller's buffer
  *   "nn_stack"         [1]     kd-tree query: per-lane LDS stack (1) or the reference's stackless walk (0)
  *   "nn_compact"       [1]     stack query on 32-byte node records with 16-bit outward-rounded boxes (0: exact 64-byte records)
  *   "host_worker"      [1]     host solve: a batch given to pr_refine_submit runs on a library-owned helper thread of its slot (private context: its own
@@ -413,8 +417,14 @@ int  pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, c
  * finished_out: n x uint32 (1 = the hypothesis stops here). */
 int  pr_debug_pose_iteration(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, int on_device,
                              pr_result *state, float *update_out, uint32_t *finished_out);
+/* Audit entries (no device needed) for the library's ordered copy of a triangle buffer (option "mesh_order"): perm_out[k] = index of the
+ * triangle the copy holds at place k -- a permutation of 0..n_tris-1, a pure function of the triangle data (Morton code of the
+ * centroids, stable; non-finite centroids last) -- and the order-independent 64-bit fingerprint of a buffer (wrapping sum of a mixing
+ * hash of each triangle's nine words) that every asynchronous batch re-derives from the caller's buffer on the device. */
+int  pr_debug_mesh_order(const pr_triangle *tris_host, size_t n_tris, uint32_t *perm_out);
+int  pr_debug_mesh_fingerprint(const pr_triangle *tris_host, size_t n_tris, uint64_t *fingerprint_out);
 /* Two things the library does silently for correctness, counted per context since it was created: asynchronous batches that
- * pr_refine_wait ran a SECOND time because the device-side checks found a stale model box or a scene array that no longer matches its
+ * pr_refine_wait ran a SECOND time because the device-side checks found a stale model box, a triangle buffer whose content changed, or a scene array that no longer matches its
  * cached form (a caller who sees this grow writes to its buffers behind the library's back: pr_invalidate is the cheap cure), and timed
  * spans / batches whose HIP-event timing was dropped because an event could not be created or recorded (the work itself ran). */
 int  pr_stats(uint64_t *batches_repeated, uint64_t *timings_dropped);

@@ -150,6 +150,22 @@ def stats():
     return a.value, b.value
 
 
+def mesh_order(tris) -> np.ndarray:
+    """``pr_debug_mesh_order``: the permutation (uint32, place -> triangle index) of the library's ordered copy of a (T, 3, 3) float32 soup.  No device needed."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+    perm = np.empty(len(t), np.uint32)
+    check(_lib.load().pr_debug_mesh_order(t.ctypes.data, len(t), perm.ctypes.data))
+    return perm
+
+
+def mesh_fingerprint(tris) -> int:
+    """``pr_debug_mesh_fingerprint``: the order-independent 64-bit fingerprint of a (T, 3, 3) float32 soup.  No device needed."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+    v = C.c_uint64()
+    check(_lib.load().pr_debug_mesh_fingerprint(t.ctypes.data, len(t), C.byref(v)))
+    return v.value
+
+
 def gather_profile():
     """HIP-event time of the gathers issued while option ``profile`` was on: (total ms, count).  Waits for the library stream."""
     ms, n = C.c_double(), C.c_uint64()

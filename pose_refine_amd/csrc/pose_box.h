@@ -1,6 +1,7 @@
 // pose_box.h -- the conservative pixel box of a mesh under one pose.  The same source is compiled for the device (pose_bbox_kernel,
 // pose_bbox_multi_kernel: PR_HD = __host__ __device__) and for the host (the asynchronous path sizes a batch with it before anything of
-// the batch has run); with contraction disabled both builds produce the same box.
+// the batch has run); with contraction disabled both builds produce the same box.  Also the hash of one triangle, which the host (fingerprint of a
+// triangle buffer, taken when its ordered copy is made) and the raster's per-batch check of the caller's buffer must form alike.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -46,6 +47,18 @@ PR_HD inline int4 pose_pixel_box(const float *aabb, const float *M, const pr_mat
         y0 = imax(y0, (int)height - 1 - (roi.y + roi.height - 1));  y1 = imin(y1, (int)height - 1 - roi.y);
     }
     return make_int4(x0, y0, x1, y1);
+}
+
+// Mixing hash of one triangle's nine words (bit patterns: -0.0f and 0.0f, or two NaNs, are different content).  The fingerprint of a
+// triangle buffer is the wrapping 64-bit SUM of these over its triangles -- a multiset hash, equal for every order of the same triangles --
+// so the host (when it builds the ordered copy) and the raster's per-batch check (over the caller's buffer, in whatever order the
+// workgroups arrive) form the same number.
+PR_HD inline unsigned long long triangle_hash(const uint32_t (&w)[9])
+{
+    unsigned long long h = 0x9e3779b97f4a7c15ull;
+    for (int k = 0; k < 9; ++k) { h = (h ^ w[k]) * 0xff51afd7ed558ccdull; h ^= h >> 32; }
+    h *= 0xc4ceb9fe1a85ec53ull;
+    return h ^ (h >> 29);
 }
 
 }  // namespace prk

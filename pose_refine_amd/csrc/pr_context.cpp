@@ -70,7 +70,7 @@ void ctx_teardown(Ctx *c)        // c->mu held (or c unreachable); the calling t
     hipStreamSynchronize(c->stream);
     for (Slot &sl : c->slots) slot_release(sl);
     for (DevBuf *b : { &c->aabb, &c->aabb_keys, &c->bbox, &c->poses, &c->depth, &c->row_count, &c->row_off, &c->counts, &c->cloud, &c->meta, &c->partial,
-                       &c->sums, &c->packed.rec, &c->nn_prev, &c->dstate, &c->dresults, &c->arrive, &c->conv16, &c->conv8, &c->kd_scratch, &c->kd_tmp, &c->nn_full, &c->gather_tmp, &c->nn_counters, &c->scores, &c->multi, &c->ov_bits, &c->ov_box, &c->ov_mat }) b->release();
+                       &c->sums, &c->packed.rec, &c->nn_prev, &c->dstate, &c->dresults, &c->arrive, &c->conv16, &c->conv8, &c->kd_scratch, &c->kd_tmp, &c->nn_full, &c->gather_tmp, &c->nn_counters, &c->scores, &c->multi, &c->ov_bits, &c->ov_box, &c->ov_mat, &c->mesh_sorted }) b->release();
     for (NNDerived &d : c->nn_sets) d.release();
     for (PinBuf *b : { &c->h_sums, &c->h_meta, &c->h_counts, &c->h_results, &c->h_dstate, &c->h_poses, &c->h_flags, &c->h_scores, &c->h_multi, &c->h_ov }) b->release();
     c->packed = PackedCache();
@@ -88,7 +88,7 @@ void ctx_teardown(Ctx *c)        // c->mu held (or c unreachable); the calling t
         if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]);
         c->side[i] = nullptr; c->ev_join[i] = nullptr;
     }
-    c->stream = nullptr; c->ready = false; c->mesh_key = nullptr; c->aabb_host_valid = false; c->cloud_hint = 0;
+    c->stream = nullptr; c->ready = false; c->drop_mesh(); c->cloud_hint = 0;
 }
 
 PrivateCtx::~PrivateCtx()               // a thread that ends with a private context releases it
@@ -209,7 +209,7 @@ int pr_free(void *dev_ptr)
         HIP_TRY(hipStreamSynchronize(g->stream));
         for (Slot &sl : g->slots) if (sl.pending && !sl.delivered) slot_drain(sl);
         g_writes.note(dev_ptr, 0);                                     // the address may come back with other content
-        if (dev_ptr == g->mesh_key) { g->mesh_key = nullptr; g->aabb_host_valid = false; }
+        if (dev_ptr == g->mesh_key) g->drop_mesh();
     }
     // ... nor anything another context of this device has in flight (a private-context thread, or another thread on the shared context,
     // may have a batch running on the buffer): every other context is locked -- i.e. between two of its calls, never inside a stream
@@ -255,7 +255,7 @@ static int copy_sync(void *dst, const void *src, size_t bytes, hipMemcpyKind kin
     if (kind != hipMemcpyDeviceToHost) {
         note_write(dst, bytes);
         if (g->mesh_key && reinterpret_cast<uintptr_t>(dst) < reinterpret_cast<uintptr_t>(g->mesh_key) + g->mesh_n * sizeof(pr_triangle) &&
-            reinterpret_cast<uintptr_t>(g->mesh_key) < reinterpret_cast<uintptr_t>(dst) + bytes) { g->mesh_key = nullptr; g->aabb_host_valid = false; }
+            reinterpret_cast<uintptr_t>(g->mesh_key) < reinterpret_cast<uintptr_t>(dst) + bytes) g->drop_mesh();
     }
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
@@ -308,6 +308,7 @@ int pr_set_option(const char *name, int value)
     else if (n == "overlap_pass") opt.overlap_pass = std::max(-1, value);
     else if (n == "pose_groups") opt.pose_groups = std::min(4, std::max(0, value));
     else if (n == "eager_streams") opt.eager_streams = value ? 1 : 0;
+    else if (n == "mesh_order") opt.mesh_order = value ? 1 : 0;
     else if (n == "raster_mode") { if (value < 0 || value > 1) { set_error("raster_mode must be 0 or 1"); return PR_ERR_INVALID; } opt.raster_mode = value; }
     else { set_error("unknown option %s", name); return PR_ERR_INVALID; }
     return PR_OK;
@@ -339,6 +340,7 @@ int pr_get_option(const char *name, int *value)
     else if (n == "host_poll") *value = opt.host_poll;
     else if (n == "stat_flag_overtook") *value = (int)std::min<uint64_t>(g_flag_overtook.load(), 0x7fffffffull);   // read-only
     else if (n == "raster_mode") *value = opt.raster_mode;
+    else if (n == "mesh_order") *value = opt.mesh_order;
     else if (n == "eager_streams") *value = opt.eager_streams;
     else if (n == "graph") *value = opt.use_graph;
     else if (n == "fused_solve") *value = opt.fused_solve;

@@ -17,12 +17,62 @@
 #include <vector>
 
 #include "pr_internal.h"
+#include "pose_box.h"
 #include "pr_solver.inl"
 
 namespace prh {
 void solve_666(const float A[36], const float b[6], float T[16]) { prs::solve_666_impl(A, b, T); }
 void mat4_mul(const float A[16], const float B[16], float C[16]) { prs::mat4_mul_impl(A, B, C); }
 void set_error(const char *fmt, ...);   // pr_context.cpp
+
+// ---- spatial order of a triangle soup -------------------------------------------------------------------------------------------------
+// The raster resolves depth with one atomicMin per fragment, and a wavefront's atomics cost by the number of 64-byte segments they touch.
+// The fragments a wavefront drains together come from 64 consecutive triangles, so triangles that are neighbours in the buffer should be
+// neighbours in space: key = Morton code of the triangle's centroid, 10 bits per axis inside the box of the (finite) centroids; stable, so
+// ties keep their index order; triangles with a non-finite centroid go last, in index order.  Double arithmetic on float input: the same
+// permutation on every host.
+static uint32_t morton_spread(uint32_t v)
+{
+    v = (v | (v << 16)) & 0x030000ffu; v = (v | (v << 8)) & 0x0300f00fu; v = (v | (v << 4)) & 0x030c30c3u; v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+void mesh_order(const pr_triangle *tris, size_t n_tris, uint32_t *perm)
+{
+    const float *f = reinterpret_cast<const float *>(tris);
+    std::vector<double> c(3 * n_tris);
+    double lo[3] = { DBL_MAX, DBL_MAX, DBL_MAX }, hi[3] = { -DBL_MAX, -DBL_MAX, -DBL_MAX };
+    std::vector<unsigned char> finite(n_tris, 1);
+    for (size_t t = 0; t < n_tris; ++t) {
+        for (int a = 0; a < 3; ++a) {
+            c[3 * t + a] = ((double)f[9 * t + a] + (double)f[9 * t + 3 + a] + (double)f[9 * t + 6 + a]) / 3.0;
+            if (!std::isfinite(c[3 * t + a])) finite[t] = 0;
+        }
+        if (finite[t]) for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], c[3 * t + a]); hi[a] = std::max(hi[a], c[3 * t + a]); }
+    }
+    std::vector<uint32_t> key(n_tris);
+    for (size_t t = 0; t < n_tris; ++t) {
+        if (!finite[t]) { key[t] = 0xffffffffu; continue; }
+        uint32_t q[3];
+        for (int a = 0; a < 3; ++a) {
+            const double span = hi[a] - lo[a];
+            const double u = span > 0.0 ? (c[3 * t + a] - lo[a]) / span * 1023.0 : 0.0;
+            q[a] = (uint32_t)std::min(1023.0, std::max(0.0, u));
+        }
+        key[t] = morton_spread(q[0]) | (morton_spread(q[1]) << 1) | (morton_spread(q[2]) << 2);
+    }
+    std::iota(perm, perm + n_tris, 0u);
+    std::stable_sort(perm, perm + n_tris, [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+}
+unsigned long long mesh_fingerprint(const pr_triangle *tris, size_t n_tris)
+{
+    unsigned long long sum = 0;
+    for (size_t t = 0; t < n_tris; ++t) {
+        uint32_t w[9];
+        std::memcpy(w, tris + t, sizeof w);
+        sum += prk::triangle_hash(w);
+    }
+    return sum;
+}
 }  // namespace prh
 
 namespace {
@@ -734,6 +784,20 @@ int pr_scene_nn_prepare(const void *depth, int is_i32, const float K[9], int W, 
     if (n_points) *n_points = (uint32_t)n;
     if (n == 0) { if (n_nodes) *n_nodes = 0; return PR_OK; }
     return pr_kdtree_build(pcd_out, normal_out, n, max_leaf, nodes_out, cap_nodes, n_nodes);
+}
+
+int pr_debug_mesh_order(const pr_triangle *tris_host, size_t n_tris, uint32_t *perm_out)
+{
+    if (n_tris && (!tris_host || !perm_out)) { prh::set_error("pr_debug_mesh_order: null buffer"); return PR_ERR_INVALID; }
+    if (n_tris > 0xffffffffull) { prh::set_error("pr_debug_mesh_order: more than 2^32 - 1 triangles"); return PR_ERR_INVALID; }
+    prh::mesh_order(tris_host, n_tris, perm_out);
+    return PR_OK;
+}
+int pr_debug_mesh_fingerprint(const pr_triangle *tris_host, size_t n_tris, uint64_t *fingerprint_out)
+{
+    if ((n_tris && !tris_host) || !fingerprint_out) { prh::set_error("pr_debug_mesh_fingerprint: null buffer"); return PR_ERR_INVALID; }
+    *fingerprint_out = prh::mesh_fingerprint(tris_host, n_tris);
+    return PR_OK;
 }
 
 void pr_solve_666(const float A[36], const float b[6], pr_mat4 *T_out) { prs::solve_666_impl(A, b, T_out->m); }

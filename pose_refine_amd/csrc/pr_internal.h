@@ -158,9 +158,14 @@ hipError_t launch_render_bands(const pr_triangle *tris, uint32_t n_tris, const p
 // hypothesis fold their triangles' vertices into keys[0..5] (running minima; keys[6] = arrival ticket; armed once by the caller with six
 // words of ones and a zero, re-armed by the last workgroup), the last one compares with the box the host assumed; workgroup (0, 0) takes
 // the sampled fingerprint of the caller's scene arrays (fp_expected null: none).  Both only ever RAISE *flag.  keys null: no check.
+// The raster may run on the library's ordered copy of the mesh (ensure_model_box): the checks read the CALLER's buffer (`caller`, lane triangle
+// ti) and, beside its box, add up its multiset fingerprint (triangle_hash, pose_box.h) in keys[8..9] (one 64-bit word, armed with zero and
+// re-armed like the ticket); the last workgroup compares it with `mesh_hash`, the value of the content the copy was made from.
 struct AabbExpected { float v[6]; };
+constexpr uint32_t kBatchCheckWords = 10;   // keys[0..5] box, [6] ticket, [7] spare, [8..9] fingerprint sum
 struct BatchCheck {
     uint32_t *keys; AabbExpected expect;
+    const pr_triangle *caller; unsigned long long mesh_hash;
     const uint32_t *fa, *fb, *fc; unsigned long long na, nb, nc; const uint32_t *fp_expected;
     uint32_t *flag;
 };
@@ -286,4 +291,8 @@ hipError_t launch_nn_wide_levels(const int4 *topo, const float4 *bmin, const flo
 namespace prh {
 void solve_666(const float A[36], const float b[6], float T[16]);
 void mat4_mul(const float A[16], const float B[16], float C[16]);
+// Spatial order of a triangle soup (pr_debug_mesh_order): perm[k] = index of the triangle that goes to place k.  A pure function of the data.
+void mesh_order(const pr_triangle *tris, size_t n_tris, uint32_t *perm);
+// multiset fingerprint of a triangle buffer: wrapping sum of triangle_hash (pose_box.h)
+unsigned long long mesh_fingerprint(const pr_triangle *tris, size_t n_tris);
 }

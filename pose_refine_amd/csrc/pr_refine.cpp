@@ -547,14 +547,22 @@ void slot_release(Slot &sl)
 }
 
 // Host-side copy of a triangle buffer's box, once per (pointer, size): it feeds the per-pose pixel boxes computed on the host,
-// which size a batch before anything of it has run.  The copy is an ASSUMPTION about memory the caller owns: every batch that
-// uses it re-derives the box on the device (one pass over the mesh, on a stream that is idle at that point) and refine_wait
-// re-runs the batch through the synchronous path if the two differ -- a rewritten mesh costs one repeated batch, never a wrong one.
+// which size a batch before anything of it has run.  With it (option mesh_order; from the buffer's second batch on) comes a copy of the triangles in spatial order
+// (prh::mesh_order) in a buffer the context owns: what the asynchronous path's raster reads, because depth is a per-pixel minimum --
+// no order of the triangles changes a pixel -- while the cost of its atomics is the number of 64-byte segments a wavefront's
+// fragments touch (profiles/mesh_order).  Both are ASSUMPTIONS about memory the caller owns: every batch that uses them re-derives,
+// from the CALLER's buffer on the device (one pass over the mesh, carried by the raster's first workgroups), the box and an
+// order-independent fingerprint of every word (BatchCheck: the box alone would miss a rewrite that keeps the box), and refine_wait
+// re-runs the batch through the synchronous path, which reads the caller's buffer only, if either differs -- a rewritten mesh costs
+// one repeated batch, never a wrong one.
 // (An indexed form of the soup with a per-pose vertex stage was built and measured as well: three divergent 16-byte gathers
 // per triangle cost the texture addresser more than the 170 saved VALU instructions give back -- 1.27 -> 1.32 ms per step.)
 int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
 {
-    if (g->mesh_key == tris_dev && g->mesh_n == n_tris && g->aabb_host_valid) return PR_OK;
+    // The ordered copy costs a host sort (35 ms for obj_06): it is made for a buffer that STAYS -- on the second batch in a row that finds the
+    // same (pointer, size) -- so a caller that alternates between models on one context pays what it paid before (one read-back per batch).
+    const bool seen = g->mesh_key == tris_dev && g->mesh_n == n_tris && g->aabb_host_valid;
+    if (seen && (!opt.mesh_order || g->mesh_sorted_valid)) return PR_OK;
     std::vector<pr_triangle> h(n_tris);
     if (n_tris) HIP_TRY(hipMemcpy(h.data(), tris_dev, sizeof(pr_triangle) * n_tris, hipMemcpyDeviceToHost));
     const float *f = reinterpret_cast<const float *>(h.data());
@@ -562,6 +570,19 @@ int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
     for (size_t v = 0; v < n_tris * 3; ++v)
         for (int d = 0; d < 3; ++d) { lo[d] = fminf(lo[d], f[3 * v + d]); hi[d] = fmaxf(hi[d], f[3 * v + d]); }
     for (int d = 0; d < 3; ++d) { g->aabb_host[d] = lo[d]; g->aabb_host[3 + d] = hi[d]; }
+    g->mesh_hash = prh::mesh_fingerprint(h.data(), n_tris);
+    g->mesh_sorted_valid = false;
+    if (opt.mesh_order && seen && n_tris > 0 && n_tris <= 0xffffffffull) {
+        std::vector<uint32_t> perm(n_tris);
+        prh::mesh_order(h.data(), n_tris, perm.data());
+        std::vector<pr_triangle> sorted(n_tris);
+        for (size_t k = 0; k < n_tris; ++k) sorted[k] = h[perm[k]];
+        // the other slot's batch may still be rastering the previous copy (another mesh, or a rewritten one): let it finish first
+        for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+        PR_TRY(g->mesh_sorted.ensure(sizeof(pr_triangle) * n_tris));
+        HIP_TRY(hipMemcpy(g->mesh_sorted.p, sorted.data(), sizeof(pr_triangle) * n_tris, hipMemcpyHostToDevice));
+        g->mesh_sorted_valid = true;
+    }
     g->mesh_key = tris_dev; g->mesh_n = n_tris; g->aabb_host_valid = true;
     return PR_OK;
 }
@@ -611,9 +632,9 @@ int refine_wait(int slot)
     sl.pending = false;
     const unsigned char *h_out = sl.h_out.as<unsigned char>();
     if (*reinterpret_cast<const volatile uint32_t *>(h_out + sl.flag_off) != 0u) {
-        // the triangle buffer no longer has the box this batch was sized with: forget the host copy and run the batch again,
-        // synchronously (that path derives every box on the device); outputs are overwritten in full
-        g->aabb_host_valid = false; g->mesh_key = nullptr;
+        // the triangle buffer no longer has the box this batch was sized with, or the content its ordered copy was made from: forget both
+        // and run the batch again, synchronously (that path derives every box on the device and reads the caller's buffer); outputs are overwritten in full
+        g->drop_mesh();
         g->stat_repeated++;                                         // (pr_stats: the safety net is not free -- a caller that sees this count grow should call pr_invalidate)
         // (or a scene array no longer has the content its cached form was derived from: same cure)
         drain_all_slots();
@@ -815,16 +836,17 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     // (BatchCheck, pr_internal.h) -- as launches of their own on the scene stream (a memset, two box kernels, the fingerprint kernel) they cost
     // 1.3-1.5 % of the headline whatever their number (skipped: 277.6 against 273.6 k poses/s on one box; fused into one launch: 274.1 k).
     const bool keys_new = sl.aabb_keys.p == nullptr;
-    PR_TRY(sl.aabb_keys.ensure(8 * sizeof(uint32_t)));
+    PR_TRY(sl.aabb_keys.ensure(prk::kBatchCheckWords * sizeof(uint32_t)));
     if (keys_new) {                                               // armed once; the last workgroup of every check re-arms the words itself
         HIP_TRY(hipMemsetAsync(sl.aabb_keys.p, 0xff, 6 * sizeof(uint32_t), sl.stream));
-        HIP_TRY(hipMemsetAsync(sl.aabb_keys.as<uint32_t>() + 6, 0, 2 * sizeof(uint32_t), sl.stream));
+        HIP_TRY(hipMemsetAsync(sl.aabb_keys.as<uint32_t>() + 6, 0, (prk::kBatchCheckWords - 6) * sizeof(uint32_t), sl.stream));
     }
     *reinterpret_cast<volatile uint32_t *>(sl.h_out.as<unsigned char>() + sl.flag_off) = 0u;
     prk::BatchCheck chk{};
     {
         chk.keys = sl.aabb_keys.as<uint32_t>();
         for (int a = 0; a < 6; ++a) chk.expect.v[a] = g->aabb_host[a];
+        chk.caller = tris_dev; chk.mesh_hash = g->mesh_hash;
         chk.flag = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(h_out_dev) + sl.flag_off);
         if (opt.scene_cache) {
             if (scene_kind == PR_SCENE_NN) {
@@ -946,6 +968,8 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     HIP_TRY(prk::launch_stage_words(h_in_dev, d_poses, in_bytes, st));
     const bool fused = opt.fused_solve != 0;
     const pr_roi none{ 0, 0, 0, 0 };                              // the ROI is already part of the host-computed boxes
+    // the raster's triangles: the context's ordered copy (same triangles, same minima; the first render's checks read the caller's buffer)
+    const pr_triangle *raster_tris = (opt.mesh_order && g->mesh_sorted_valid) ? g->mesh_sorted.as<pr_triangle>() : tris_dev;
     for (uint32_t q0 = 0; q0 < P; q0 += sub) {
         const uint32_t nq = std::min(sub, P - q0);
         prk::PoseMeta *meta = sl.meta.as<prk::PoseMeta>() + q0;
@@ -958,7 +982,7 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
         // `exact` flag / tree depth back before it returns, so a rebuild has finished on the host's clock before the render is even enqueued; on a
         // cache hit the event is complete when recorded)
         if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
-        HIP_TRY(prk::launch_render_boxes(tris_dev, (uint32_t)n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
+        HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
                                          sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, *proj, none, st,
                                          /*compute_boxes=*/false, meta, dstate, arrive, (uint32_t)cstride, d_off ? d_off + q0 : nullptr, q0 == 0 ? &chk : nullptr));
         if (timed) { t_end(te, kSpanRender, q0, nq, false); te = t_begin(); }

@@ -157,6 +157,7 @@ struct Options {
                                      // graph, which forfeits the overlap): capture the whole iteration loop in a hipGraph and replay it
     int eager_streams = 1;           // asynchronous path: create the streams of both slots in one run (see slot_streams)
     int raster_mode = 0;             // fused path: 0 = global atomicMin inside the per-pose pixel box (reference scheme), 1 = LDS depth bands (int32); pr_set_option refuses anything else
+    int mesh_order = 1;              // asynchronous fused path: raster the library's spatially ordered copy of the triangle buffer (ensure_model_box); 0 = the caller's buffer
     int scene_cache = 1;             // keep the packed projective scene / kd traversal records of the latest scene between calls (pr_scene_invalidate)
 };
 extern Options opt;
@@ -267,6 +268,10 @@ struct Ctx {
     // the device by every batch that uses it (refine_submit / refine_wait), so a rewritten triangle buffer cannot go unnoticed
     float aabb_host[6] = { 0, 0, 0, 0, 0, 0 }; bool aabb_host_valid = false;
     const void *mesh_key = nullptr; size_t mesh_n = 0;   // triangle buffer aabb_host belongs to
+    // ... and the same buffer's triangles in spatial order (prh::mesh_order), with the multiset fingerprint of the content they were copied from
+    // (BatchCheck::mesh_hash): same key, same life cycle, verified by the same batches
+    DevBuf mesh_sorted; bool mesh_sorted_valid = false; unsigned long long mesh_hash = 0;
+    void drop_mesh() { mesh_key = nullptr; aabb_host_valid = false; mesh_sorted_valid = false; }
     uint32_t cloud_hint = 0;          // largest cloud of the latest finished asynchronous batch: sizes the next batch's grid
     // workspaces
     DevBuf aabb, aabb_keys, bbox, poses, depth, row_count, row_off, counts, cloud, meta, partial, sums, nn_prev, dstate, dresults, arrive, conv16, conv8, kd_scratch, kd_tmp, nn_full;

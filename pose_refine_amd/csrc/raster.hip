@@ -230,10 +230,19 @@ __device__ __forceinline__ float box_key_value(uint32_t k, uint32_t a)
     return v;
 }
 // The per-batch safety nets, carried by the raster (BatchCheck, pr_internal.h): called by the workgroups of the launch's first hypothesis with
-// their 256 triangles in registers.  `red` / `part`: LDS scratch (6 x 4 floats, 4 + 1 words).
+// the CALLER's triangles of their 256 places in registers (the raster itself may read the library's ordered copy).  `red` / `part`: LDS
+// scratch (6 x 4 floats, 16 words: [0..3] scene fingerprint, [4] ticket, [8..15] the wavefronts' mesh fingerprint sums as lo / hi words).
 __device__ __forceinline__ void raster_batch_check(const float (&tv)[9], bool have, const BatchCheck &chk, float (*red)[6], uint32_t *part)
 {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    {   // multiset fingerprint of the caller's buffer: this workgroup's share (read by thread 0 after box_key_merge's barrier)
+        uint32_t w[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) w[k] = __float_as_uint(tv[k]);
+        unsigned long long h = have ? triangle_hash(w) : 0ull;
+        for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off);
+        if (lane == 0) { part[8 + 2 * wave] = (uint32_t)h; part[9 + 2 * wave] = (uint32_t)(h >> 32); }
+    }
     if (blockIdx.x == 0 && chk.fp_expected) {
         uint32_t h = fingerprint_lane(chk.fa, chk.na, chk.fb, chk.nb, chk.fc, chk.nc);
         for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off);
@@ -249,7 +258,13 @@ __device__ __forceinline__ void raster_batch_check(const float (&tv)[9], bool ha
         hi[a] = have ? fmaxf(fmaxf(tv[a], tv[3 + a]), tv[6 + a]) : -FLT_MAX;
     }
     box_key_merge(lo, hi, red, chk.keys);
-    if (threadIdx.x < 6) __threadfence();                            // this workgroup's minima are in place before its ticket is drawn
+    unsigned long long *mesh_sum = reinterpret_cast<unsigned long long *>(chk.keys + 8);
+    if (threadIdx.x == 0) {
+        unsigned long long h = 0;
+        for (int w = 0; w < 4; ++w) h += (unsigned long long)part[8 + 2 * w] | ((unsigned long long)part[9 + 2 * w] << 32);
+        atomicAdd(mesh_sum, h);
+    }
+    if (threadIdx.x < 6) __threadfence();                            // this workgroup's minima and its share of the sum are in place before its ticket is drawn
     __syncthreads();
     if (threadIdx.x == 0) part[4] = (atomicAdd(&chk.keys[6], 1u) == gridDim.x - 1u) ? 1u : 0u;
     __syncthreads();
@@ -258,6 +273,7 @@ __device__ __forceinline__ void raster_batch_check(const float (&tv)[9], bool ha
         bool differs = false;
         for (uint32_t a = 0; a < 6; ++a)
             if (!(box_key_value(atomicExch(&chk.keys[a], 0xffffffffu), a) == chk.expect.v[a])) differs = true;
+        if (atomicExch(mesh_sum, 0ull) != chk.mesh_hash) differs = true;
         atomicExch(&chk.keys[6], 0u);
         if (differs) *chk.flag = 1u;
     }
@@ -339,8 +355,11 @@ __global__ __launch_bounds__(256) void raster_kernel(const pr_triangle *__restri
     const uint32_t ti = blockIdx.x * 256 + threadIdx.x;
     float tv[9];
     load_triangle(tris, n_tris, ti, tv);
-    if (chk.keys && blockIdx.y == 0)                             // (wave-uniform) the asynchronous path's per-batch checks ride on the first hypothesis' workgroups
-        raster_batch_check(tv, ti < n_tris, chk, reinterpret_cast<float (*)[6]>(&sh[0][0][0]), &shq[0][0]);
+    if (chk.keys && blockIdx.y == 0) {                           // (wave-uniform) the asynchronous path's per-batch checks ride on the first hypothesis' workgroups
+        float cv[9];                                             // ... and look at the caller's buffer: `tris` may be the library's ordered copy of it
+        load_triangle(chk.caller, n_tris, ti, cv);
+        raster_batch_check(cv, ti < n_tris, chk, reinterpret_cast<float (*)[6]>(&sh[0][0][0]), &shq[0][0]);
+    }
     raster_runs(tv, ti, n_tris, blockIdx.y, poses, depth, width, height, proj, roi, rw, rh, boxes, n_poses, pose_run, box_off, nullptr, sh, shq);
 }
 

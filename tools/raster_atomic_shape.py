@@ -1,0 +1,125 @@
+"""CPU count of what the raster's depth atomics look like to memory: distinct 64-byte segments per atomic wave instruction, for the
+benchmark's hypotheses of obj_06, with the mesh in file order and in the order the library ships (pr_debug_mesh_order, through the C ABI:
+what is counted is what the raster reads).  The kernel's own structure is followed (workgroup = 256 consecutive triangles, wavefront = 64
+of them, fragments drained 64 at a time in triangle order); the arithmetic is float64 and the edge rule approximated -- statistics, not
+a parity tool.  numpy only, no device.
+
+    python tools/raster_atomic_shape.py [n_hypotheses=6]
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from pose_refine_amd import api, synth  # noqa: E402
+
+PATCH_CAPS = (512, 1024, 2048, 4096, 8192)
+
+
+def load_obj06():
+    return synth.load_ply_triangles(os.path.join(ROOT, "tests", "golden", "obj_06.ply")).astype(np.float32)
+
+
+def shipped_order(tris):
+    """The triangles as the library's ordered copy holds them."""
+    return tris[api.mesh_order(tris)]
+
+
+def fragments_of_pose(tris, M, W=synth.WIDTH, H=synth.HEIGHT, K=synth.K_TEST):
+    """(candidates, triangle index, x, y) of the fragments of one hypothesis."""
+    K = np.asarray(K, np.float64)
+    fx, cx, fy, cy = K[0], K[2], K[4], K[5]
+    v = tris @ M[:3, :3].T + M[:3, 3]
+    px = v[..., 0] / v[..., 2] * fx + cx
+    py = v[..., 1] / v[..., 2] * fy + cy
+    x0 = np.ceil(px.min(1) - 1e-9).astype(int); x1 = np.floor(px.max(1)).astype(int)
+    y0 = np.ceil(py.min(1) - 1e-9).astype(int); y1 = np.floor(py.max(1)).astype(int)
+    x0 = np.clip(x0, 0, W - 1); x1 = np.clip(x1, -1, W - 1); y0 = np.clip(y0, 0, H - 1); y1 = np.clip(y1, -1, H - 1)
+    nx = np.maximum(x1 - x0 + 1, 0); ny = np.maximum(y1 - y0 + 1, 0)
+    n = nx * ny
+    idx = np.nonzero(n)[0]
+    rep = np.repeat(idx, n[idx])
+    start = np.cumsum(n[idx]) - n[idx]
+    k = np.arange(len(rep)) - np.repeat(start, n[idx])
+    xs = x0[rep] + k % nx[rep]; ys = y0[rep] + k // nx[rep]
+    ax, ay = px[rep, 0], py[rep, 0]; bx, by = px[rep, 1], py[rep, 1]; cx_, cy_ = px[rep, 2], py[rep, 2]
+    area = 0.5 * ((cx_ - ax) * (by - ay) - (bx - ax) * (cy_ - ay))
+    with np.errstate(all="ignore"):
+        beta = 0.5 * ((cx_ - ax) * (ys - ay) - (xs - ax) * (cy_ - ay)) / area
+        gamma = 0.5 * ((xs - ax) * (by - ay) - (bx - ax) * (ys - ay)) / area
+    alpha = 1 - beta - gamma
+    inside = (area != 0) & (alpha >= 0) & (beta >= 0) & (gamma >= 0) & (alpha <= 1) & (beta <= 1) & (gamma <= 1)
+    return int(n.sum()), rep[inside], xs[inside], ys[inside]
+
+
+def _segments(addr):
+    return len(np.unique(addr // 16))            # distinct 64-byte segments of int32 addresses
+
+
+def count(tris, poses):
+    """Totals over `poses` for the triangle order given; see report() for the meaning of each."""
+    tris = np.asarray(tris, np.float64)
+    tot = dict(poses=len(poses), cand=0, frag=0, instr=0, seg=0, vis=0, wg_uni=0, wg_rowseg=0, wg_count=0,
+               fits={c: 0 for c in PATCH_CAPS}, wg_frag_in={c: 0 for c in PATCH_CAPS}, boxes=[])
+    for M in np.asarray(poses, np.float64):
+        cand, t, x, y = fragments_of_pose(tris, M)
+        bx0, by0 = x.min() - 2, y.min() - 2
+        pitch = (x.max() + 2 - bx0 + 1 + 31) // 32 * 32                  # rows start on a segment boundary (the packed boxes' own pitch is their width: a statistic)
+        addr = (y - by0) * pitch + (x - bx0)
+        tot["cand"] += cand; tot["frag"] += len(t); tot["vis"] += len(np.unique(addr))
+        wave = t // 64
+        order = np.argsort(wave, kind="stable")
+        wave_s, addr_s = wave[order], addr[order]
+        for a in np.split(addr_s, np.nonzero(np.diff(wave_s))[0] + 1):
+            for i in range(0, len(a), 64):
+                tot["instr"] += 1; tot["seg"] += _segments(a[i:i + 64])
+        wg = t // 256
+        order = np.argsort(wg, kind="stable")
+        bounds = np.nonzero(np.diff(wg[order]))[0] + 1
+        for xa, ya, aa in zip(np.split(x[order], bounds), np.split(y[order], bounds), np.split(addr[order], bounds)):
+            tot["wg_count"] += 1
+            u = np.unique(aa)
+            tot["wg_uni"] += len(u); tot["wg_rowseg"] += _segments(u)
+            w_, h_ = xa.max() - xa.min() + 1, ya.max() - ya.min() + 1
+            tot["boxes"].append((w_, h_, len(aa)))
+            s0 = (xa.min() - bx0) // 16; s1 = (xa.max() - bx0) // 16
+            area = (s1 - s0 + 1) * 16 * h_                              # rows of whole segments covering the workgroup's fragment box
+            for cap in PATCH_CAPS:
+                if area <= cap:
+                    tot["fits"][cap] += 1; tot["wg_frag_in"][cap] += len(aa)
+    return tot
+
+
+def requests_per_hypothesis(tris, poses):
+    """64-byte atomic requests per hypothesis: the sum over atomic wave instructions of the distinct segments their lanes address."""
+    tot = count(tris, poses)
+    return tot["seg"] / tot["poses"]
+
+
+def report(name, tot):
+    P = tot["poses"]
+    print(f"== {name}")
+    print(f"per hypothesis: candidates {tot['cand']/P:.0f}, fragments (lane atomics) {tot['frag']/P:.0f}, visible pixels {tot['vis']/P:.0f}")
+    print(f"atomic wave-instructions {tot['instr']/P:.0f} per hypothesis, distinct 64-B segments per instruction {tot['seg']/tot['instr']:.1f} "
+          f"(lanes per instruction {tot['frag']/tot['instr']:.1f}); 64-B requests per hypothesis {tot['seg']/P:.0f}")
+    print(f"per workgroup (256 triangles): fragments {tot['frag']/tot['wg_count']:.0f}, unique pixels {tot['wg_uni']/tot['wg_count']:.0f}, "
+          f"distinct 64-B segments {tot['wg_rowseg']/tot['wg_count']:.1f}; 64-B requests per hypothesis if each workgroup resolved its own fragments first {tot['wg_rowseg']/P:.0f}")
+    b = np.array(tot["boxes"])
+    print("workgroup fragment box: width pct 50/90/99/max", np.percentile(b[:, 0], [50, 90, 99, 100]), "height", np.percentile(b[:, 1], [50, 90, 99, 100]))
+    for cap in PATCH_CAPS:
+        print(f"patch of <= {cap} pixels ({cap*4//1024} KiB): {100*tot['fits'][cap]/tot['wg_count']:.1f} % of workgroups, {100*tot['wg_frag_in'][cap]/tot['frag']:.1f} % of fragments")
+
+
+def main():
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 6
+    tris = load_obj06()
+    poses = synth.hypotheses(n)
+    print("triangles", len(tris), "hypotheses", n)
+    report("mesh in file order", count(tris, poses))
+    report("mesh in the library's order (pr_debug_mesh_order)", count(shipped_order(tris), poses))
+
+
+if __name__ == "__main__":
+    main()

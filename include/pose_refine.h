@@ -330,6 +330,47 @@ int  pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
 int  pr_select_greedy(const uint32_t *order, uint32_t n_order, const uint32_t *overlap, uint32_t n_poses,
                       uint32_t shared_num, uint32_t shared_den, uint32_t *selected_out, uint32_t *n_selected);
 
+/* ---- contour check: do the depth edges of a hypothesis' render lie on depth edges of the scene? ------------------------------------------
+ * pr_score_poses and the overlap matrix look at the interior of a render; a pose whose surface lies on scene surface (a face against a
+ * wall, an object slid along the table) passes both although its silhouette is nowhere in the image.  All arithmetic is in integers
+ * (differences in 64 bits), depth in mm.  A pixel is EMPTY when its depth is <= 0.  A pixel of a depth image is an EDGE pixel for jump_mm
+ * when its depth d is > 0 and at least one of its four neighbours lies inside the image and is empty or farther by more than the jump
+ * (d_n - d > jump_mm): the nearer side of a discontinuity, "no surface" counting as infinitely far.  Neighbours outside the image are
+ * ignored (an object cut by the border has no contour there).  The image is the whole frame for the scene, and the frame -- or the ROI
+ * window when one is given -- for a render.
+ * pr_scene_edge_distance_dev writes D(x, y), the chessboard (L-infinity) distance from every frame pixel to the nearest scene edge pixel,
+ * one uint8 per pixel, 255 when none lies within `radius` (0 <= radius <= PR_CONTOUR_MAX_RADIUS, jump_mm >= 0; else PR_ERR_INVALID).
+ * scene_depth_dev is a dense width x height frame on the device, int32 when depth_is_i32 is set, uint16 otherwise; dist_dev_out holds
+ * width * height bytes and belongs to the caller: the library keeps nothing by address.  Runs on the calling thread's context (three
+ * kernels, no copy to or from the host) and returns when they are done. */
+#define PR_CONTOUR_MAX_RADIUS 32
+int  pr_scene_edge_distance_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm,
+                                uint32_t radius, uint8_t *dist_dev_out);
+/* Contour record of one hypothesis, over the edge pixels c of its render: r = the rendered depth at c, s = the scene depth and D the
+ * scene edge distance at the same frame pixel, tau = tau_mm. */
+typedef struct {
+    uint32_t contour;      /* edge pixels of the render                                                                  */
+    uint32_t hit;          /* not occluded and D != 255                                                                  */
+    uint32_t occluded;     /* s > 0 and r - s > tau (pr_pose_score's `occluded` test): no scene edge can be expected     */
+    uint32_t miss;         /* not occluded and D == 255                                                                  */
+    uint32_t reserved[2];  /* written as 0                                                                               */
+    uint64_t dist_sum;     /* sum of D over the hit pixels (exact)                                                       */
+} pr_pose_contour;         /* 32 B; contour == hit + occluded + miss                                                     */
+/* pr_score_contours renders every pose once and returns, in the caller's pose order: scores_host, byte for byte what pr_score_poses
+ * returns; contours_host, the records above for jump_mm against edge_dist_dev (pr_scene_edge_distance_dev's output for the same frame;
+ * read on every call, as the scene is); and, when overlap_host is not NULL, pr_score_overlap's matrix (n_poses <= PR_OVERLAP_MAX_POSES
+ * then).  Argument checks, ROI, scene types, chunking and the synchronous behaviour are those of pr_score_poses (pr_score_poses_multi for
+ * pr_score_contours_multi); jump_mm < 0, or a null edge_dist_dev or contours_host with n_poses > 0, is PR_ERR_INVALID with nothing
+ * written; n_poses == 0 returns PR_OK and writes nothing.  The counts carry no policy. */
+int  pr_score_contours(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses,
+                       uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi,
+                       const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint8_t *edge_dist_dev,
+                       pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host);
+int  pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                             uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                             int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint8_t *edge_dist_dev,
+                             pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

@@ -27,7 +27,10 @@ RESULT = np.dtype([("T", "<f4", (16,)), ("inlier_rmse", "<f4"), ("fitness", "<f4
 # pr_pose_score: render-and-compare counts of one hypothesis (pr_score_poses)
 SCORE = np.dtype([("visible", "<u4"), ("inlier", "<u4"), ("occluded", "<u4"), ("violation", "<u4"), ("missing", "<u4"),
                   ("reserved", "<u4"), ("abs_err_sum", "<u8")])
-assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32
+# pr_pose_contour: depth-edge agreement of one hypothesis with the scene (pr_score_contours)
+CONTOUR = np.dtype([("contour", "<u4"), ("hit", "<u4"), ("occluded", "<u4"), ("miss", "<u4"), ("reserved", "<u4", (2,)), ("dist_sum", "<u8")])
+CONTOUR_MAX_RADIUS = 32                  # PR_CONTOUR_MAX_RADIUS
+assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
 
 
 class PoseRefineError(RuntimeError):
@@ -123,6 +126,9 @@ SIGNATURES = {
     "pr_score_overlap": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),
     "pr_score_overlap_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),
     "pr_select_greedy": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, _vp, C.POINTER(_u32)]),
+    "pr_scene_edge_distance_dev": (_i32, [_vp, _i32, _u32, _u32, C.c_int32, _u32, _vp]),
+    "pr_score_contours": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "pr_score_contours_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

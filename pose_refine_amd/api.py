@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, Criteria, KDNODE, MeshRef, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
+from ._lib import (COMM_ID_BYTES, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, KDNODE, MeshRef, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -816,6 +816,78 @@ def select_hypotheses(scores, overlap, max_shared: Sequence[int] = (1, 4), min_f
     frac = np.where(den <= 0, 0.0, sc["inlier"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
     order = order[frac[order] >= float(min_fraction)]
     return select_greedy(order, overlap, int(max_shared[0]), int(max_shared[1]))
+
+
+# ------------------------------------------------------------------------------------------------
+# contour check: do the depth edges of a render lie on depth edges of the scene?
+# ------------------------------------------------------------------------------------------------
+def scene_edge_distance(scene_depth, width: int, height: int, jump_mm: int, radius: int) -> DeviceVector:
+    """``pr_scene_edge_distance_dev``: the chessboard distance of every frame pixel to the nearest scene depth edge (the nearer side of a
+    jump of more than ``jump_mm``, or of a border to "no measurement"), one uint8 per pixel, 255 where none lies within ``radius``
+    (at most ``CONTOUR_MAX_RADIUS``).  ``scene_depth`` as in ``score_poses``.  Made once per frame and handed to ``score_contours``."""
+    sd = _scene_depth_dev(scene_depth, width, height)
+    out = DeviceVector(width * height, np.uint8)
+    check(_lib.load().pr_scene_edge_distance_dev(sd.data(), int(sd.dtype == np.int32), width, height, int(jump_mm), int(radius), out.data()))
+    return out
+
+
+def _edge_dist_dev(edge_dist, width: int, height: int) -> DeviceVector:
+    if not isinstance(edge_dist, DeviceVector) or edge_dist.dtype != np.uint8:
+        raise ValueError("edge_dist must be the DeviceVector(uint8) that scene_edge_distance returns")
+    if edge_dist.size() != width * height:
+        raise ValueError(f"edge_dist holds {edge_dist.size()} values, expected {width} x {height}")
+    return edge_dist
+
+
+def score_contours(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, jump_mm: int, edge_dist,
+                   roi: Sequence[int] = (0, 0, 0, 0), want_overlap: bool = False):
+    """``pr_score_contours``: one render per pose serves ``score_poses``' records, the contour records and, with ``want_overlap``,
+    ``score_overlap``'s matrix.  ``edge_dist`` is ``scene_edge_distance``'s result for the same frame.  Returns (SCORE[P], CONTOUR[P]) or
+    (SCORE[P], CONTOUR[P], uint32[P, P]): per hypothesis the edge pixels of its render (``contour``), those within the distance image's
+    radius of a scene edge (``hit``, with ``dist_sum`` the sum of their distances), those behind scene surface (``occluded``), the rest (``miss``)."""
+    td = _tris_dev(tris)
+    poses = _f32(poses, (-1, 16))
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    ed = _edge_dist_dev(edge_dist, width, height)
+    out = np.zeros(len(poses), SCORE)
+    con = np.zeros(len(poses), CONTOUR)
+    ov = np.zeros((len(poses), len(poses)), np.uint32) if want_overlap else None
+    check(_lib.load().pr_score_contours(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                        sd.data(), int(sd.dtype == np.int32), int(tau_mm), int(jump_mm), ed.data(), ptr(out), ptr(con),
+                                        ptr(ov) if want_overlap else None))
+    return (out, con, ov) if want_overlap else (out, con)
+
+
+def score_contours_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int, jump_mm: int, edge_dist,
+                         roi: Sequence[int] = (0, 0, 0, 0), want_overlap: bool = False):
+    """``pr_score_contours_multi``: ``score_contours`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; everything in pose order."""
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    ed = _edge_dist_dev(edge_dist, width, height)
+    out = np.zeros(len(poses), SCORE)
+    con = np.zeros(len(poses), CONTOUR)
+    ov = np.zeros((len(poses), len(poses)), np.uint32) if want_overlap else None
+    check(_lib.load().pr_score_contours_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                              sd.data(), int(sd.dtype == np.int32), int(tau_mm), int(jump_mm), ed.data(), ptr(out), ptr(con),
+                                              ptr(ov) if want_overlap else None))
+    return (out, con, ov) if want_overlap else (out, con)
+
+
+def contour_fraction(contours) -> np.ndarray:
+    """``hit / (contour - occluded)`` in float64: the share of a render's contour, where one can be expected, that lies near a scene edge.
+    0 where that denominator is 0 (nothing rendered, or only occluded contour)."""
+    c = np.asarray(contours)
+    den = c["contour"].astype(np.int64) - c["occluded"].astype(np.int64)
+    return np.where(den <= 0, 0.0, c["hit"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
+
+
+def filter_by_contour(order, contours, min_fraction: float) -> np.ndarray:
+    """``order`` (indices, best first, e.g. ``rank_hypotheses(scores)``) without the hypotheses whose ``contour_fraction`` is below
+    ``min_fraction``; what remains keeps its order and goes to ``select_hypotheses(order=...)``.  The ranking itself is untouched."""
+    order = np.asarray(order, np.int64)
+    return order[contour_fraction(contours)[order] >= float(min_fraction)]
 
 
 def rank_hypotheses_per_mesh(scores, mesh_index) -> dict:

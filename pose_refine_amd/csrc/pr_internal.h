@@ -206,6 +206,14 @@ inline uint32_t overlap_words_per_row(uint32_t width) { return (width + 63) / 64
 hipError_t launch_support_bits(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
                                const void *scene, bool scene_i32, int32_t tau, unsigned long long *planes, hipStream_t s);
 hipError_t launch_pair_overlap(const unsigned long long *planes, const int4 *bbox, uint32_t n_poses, uint32_t width, uint32_t height, uint32_t *mat, hipStream_t s);
+// contour.hip: the scene's edge pixels (bits: height x overlap_words_per_row(width) words) and their chessboard distance transform (row_dist:
+// scratch, dist: the result, width x height bytes each, 255 = no edge within radius) -- three launches; and the edge pixels of every rendered box
+// counted against them into records[8 * i] (pr_pose_contour words: contour, hit, occluded, miss, reserved x 2, dist_sum lo / hi), which the
+// caller zeroed.  window {x0, row0, x1, row1}: the image the renders live in (the frame or the ROI), in image coordinates
+hipError_t launch_scene_edge_distance(const void *scene, bool scene_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
+                                      unsigned long long *bits, uint8_t *row_dist, uint8_t *dist, hipStream_t s);
+hipError_t launch_contour_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
+                                const void *scene, bool scene_i32, const uint8_t *edge_dist, int32_t tau, int32_t jump_mm, uint32_t *records, hipStream_t s);
 hipError_t launch_pack_export(const DevIcpState *st, pr_result *out, const uint32_t *counts, uint32_t *host_counts, pr_result *host_results,
                               uint32_t n, hipStream_t s);
 hipError_t launch_stage_words(const void *src_host_mapped, void *dst, size_t bytes, hipStream_t s);

@@ -7,6 +7,7 @@ namespace prr {
 // the raster packs pixel coordinates into 13 bits each and enumerates a triangle's candidate pixels with 24-bit arithmetic
 bool frame_size_ok(size_t W, size_t H)
 {
+    // (contour.hip: kMaxFrameSide restates the 8192 -- its 32-bit per-workgroup sum is sized by it)
     if (W > 8192 || H > 8192 || W * H > ((size_t)1 << 24)) { set_error("frames larger than 8192 on a side or 2^24 pixels are not supported (got %zux%zu)", W, H); return false; }
     return true;
 }
@@ -285,16 +286,25 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
 // overlap_host (pr_score_overlap; null: scores only): the P x P matrix of shared inlier pixels, in the order of poses_host.  Every chunk also leaves
 // its hypotheses' support bits (select.hip) and pixel boxes in workspaces sized for all P -- g->depth and g->bbox belong to the next chunk as soon
 // as this one is scored -- and one launch over all pairs follows the last chunk.  The planes are dense: P x H x ceil(W / 64) words of 8 bytes.
+// ct (pr_score_contours; null: none): the contour records of the same renders against the scene's edge distance image (contour.hip), one more
+// kernel over every chunk's boxes right behind the score kernel; the records travel like the scores.
+struct ContourOut { int32_t jump; const uint8_t *edge_dist; pr_pose_contour *out; };
 int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
-               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr)
+               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
+               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses")
 {
-    if (tau < 0) { set_error("pr_score_poses: tau_mm must be >= 0 (got %d)", (int)tau); return PR_ERR_INVALID; }
+    if (tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)tau); return PR_ERR_INVALID; }
     if (!proj || W == 0 || H == 0 || (P && (!poses_host || !scene_dev || !scores_host || (!src.tris && src.n_tris > 0)))) {
-        set_error("pr_score_poses: bad arguments"); return PR_ERR_INVALID;
+        set_error("%s: bad arguments", fn); return PR_ERR_INVALID;
     }
     if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
-    if (!roi_ok(roi, W, H)) { set_error("pr_score_poses: roi out of image"); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
+    if (!roi_ok(roi, W, H)) { set_error("%s: roi out of image", fn); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
+    if (ct && ct->jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)ct->jump); return PR_ERR_INVALID; }
+    if (ct && P && (!ct->edge_dist || !ct->out)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
     if (P == 0) return PR_OK;
+    static_assert(sizeof(pr_pose_contour) == sizeof(pr_pose_score) && offsetof(pr_pose_contour, dist_sum) == 24, "pr_pose_contour: one 32-byte record, the sum in words 6 and 7");
+    const bool has_roi = roi.width > 0 && roi.height > 0;
+    const int4 window = has_roi ? make_int4(roi.x, roi.y, roi.x + roi.width - 1, roi.y + roi.height - 1) : make_int4(0, 0, (int)W - 1, (int)H - 1);
     constexpr uint32_t kWords = sizeof(pr_pose_score) / sizeof(uint32_t);
     static_assert(sizeof(pr_pose_score) == 32 && kWords == 8, "pr_pose_score: one 32-byte record");
     const size_t img = (size_t)W * H;
@@ -316,6 +326,7 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
         PR_TRY(g->scores.ensure(sizeof(pr_pose_score) * np));
         PR_TRY(g->h_scores.ensure(sizeof(pr_pose_score) * np));
+        if (ct) { PR_TRY(g->contours.ensure(sizeof(pr_pose_contour) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_pose_contour) * np)); }
         uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
         {
             SpanGuard sp(kSpanRender);
@@ -325,6 +336,14 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         HIP_TRY(prk::launch_fill_i32(g->scores.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
         HIP_TRY(prk::launch_score_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
                                         g->scores.as<uint32_t>(), g->stream));
+        if (ct) {
+            HIP_TRY(prk::launch_fill_i32(g->contours.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
+            HIP_TRY(prk::launch_contour_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, scene_dev, scene_i32, ct->edge_dist, tau,
+                                              ct->jump, g->contours.as<uint32_t>(), g->stream));
+            void *hc = nullptr;
+            HIP_TRY(hipHostGetDevicePointer(&hc, g->h_contours.p, 0));
+            HIP_TRY(prk::launch_copy_words32(g->contours.p, hc, kWords * np, g->stream));
+        }
         if (overlap_host) {
             HIP_TRY(prk::launch_support_bits(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
                                              g->ov_bits.as<unsigned long long>() + plane_words * p0, g->stream));
@@ -335,6 +354,7 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         HIP_TRY(prk::launch_copy_words32(g->scores.p, hs, kWords * np, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         std::memcpy(scores_host + p0, g->h_scores.p, sizeof(pr_pose_score) * np);
+        if (ct) std::memcpy(ct->out + p0, g->h_contours.p, sizeof(pr_pose_contour) * np);
     }
     if (overlap_host) {
         HIP_TRY(prk::launch_pair_overlap(g->ov_bits.as<unsigned long long>(), g->ov_box.as<int4>(), P, W, H, g->ov_mat.as<uint32_t>(), g->stream));
@@ -358,9 +378,10 @@ int overlap_args_ok(const char *fn, uint32_t P, const uint32_t *overlap_host)
     return PR_OK;
 }
 int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
-               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr)
+               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
+               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses")
 {
-    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, overlap_host);
+    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, overlap_host, ct, fn);
 }
 
 // ---- mixed batches: the entry points' bodies (grouped batch in, outputs scattered back to the caller's order) -----------------------
@@ -393,19 +414,25 @@ int refine_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *m
 }
 
 int score_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                const pr_mat4 *proj, pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr)
+                const pr_mat4 *proj, pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
+                const ContourOut *ct = nullptr, const char *fn = "pr_score_poses_multi")
 {
-    // the single-mesh call's checks first (tau, frame, ROI, pointers), with no hypotheses
-    PR_TRY(score_core(MeshSource{ nullptr, 0, nullptr }, poses_host, 0, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host));
+    // the single-mesh call's checks first (tau, jump, frame, ROI, pointers), with no hypotheses
+    PR_TRY(score_core(MeshSource{ nullptr, 0, nullptr }, poses_host, 0, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, nullptr, ct, fn));
     if (P == 0) return PR_OK;
-    if (!poses_host || !scene_dev || !scores_host) { set_error("pr_score_poses_multi: bad arguments"); return PR_ERR_INVALID; }
+    if (!poses_host || !scene_dev || !scores_host) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
+    if (ct && (!ct->edge_dist || !ct->out)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
     MeshPlan pl;
-    PR_TRY(plan_meshes("pr_score_poses_multi", meshes, n_meshes, mesh_index, P, pl));
+    PR_TRY(plan_meshes(fn, meshes, n_meshes, mesh_index, P, pl));
     const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
     std::vector<pr_pose_score> sc(P);
     std::vector<uint32_t> ov(overlap_host ? (size_t)P * P : 0);
-    PR_TRY(score_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, roi, scene_dev, scene_i32, tau, sc.data(), overlap_host ? ov.data() : nullptr));
+    std::vector<pr_pose_contour> cc(ct ? P : 0);
+    const ContourOut grouped{ ct ? ct->jump : 0, ct ? ct->edge_dist : nullptr, cc.data() };
+    PR_TRY(score_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, roi, scene_dev, scene_i32, tau, sc.data(), overlap_host ? ov.data() : nullptr,
+                      ct ? &grouped : nullptr, fn));
     for (uint32_t j = 0; j < P; ++j) scores_host[pl.order[j]] = sc[j];
+    if (ct) for (uint32_t j = 0; j < P; ++j) ct->out[pl.order[j]] = cc[j];
     if (overlap_host)                                            // rows and columns back into the caller's order
         for (uint32_t a = 0; a < P; ++a)
             for (uint32_t b = 0; b < P; ++b) overlap_host[(size_t)pl.order[a] * P + pl.order[b]] = ov[(size_t)a * P + b];
@@ -1161,6 +1188,51 @@ int pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const u
     PR_TRY(overlap_args_ok("pr_score_overlap_multi", n_poses, overlap_host));
     return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
                        overlap_host);
+}
+
+int pr_scene_edge_distance_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
+                               uint8_t *dist_dev_out)
+{
+    PR_ENTER();
+    if (!scene_depth_dev || !dist_dev_out || width == 0 || height == 0) { set_error("pr_scene_edge_distance_dev: bad arguments"); return PR_ERR_INVALID; }
+    if (!frame_size_ok(width, height)) return PR_ERR_INVALID;
+    if (jump_mm < 0 || radius > PR_CONTOUR_MAX_RADIUS) {
+        set_error("pr_scene_edge_distance_dev: jump_mm must be >= 0 and radius <= PR_CONTOUR_MAX_RADIUS = %d (got %d, %u)", PR_CONTOUR_MAX_RADIUS, (int)jump_mm, radius);
+        return PR_ERR_INVALID;
+    }
+    const size_t img = (size_t)width * height;
+    note_write(dist_dev_out, img);
+    PR_TRY(g->edge_bits.ensure(sizeof(uint64_t) * (size_t)height * prk::overlap_words_per_row(width)));
+    PR_TRY(g->edge_rows.ensure(img));
+    HIP_TRY(prk::launch_scene_edge_distance(scene_depth_dev, depth_is_i32 != 0, width, height, jump_mm, radius, g->edge_bits.as<unsigned long long>(),
+                                            g->edge_rows.as<uint8_t>(), dist_dev_out, g->stream));
+    // the wait makes the call synchronous like every other entry point: the buffer is the caller's, who may hand it to another context (a private
+    // thread context has a stream of its own) or read it with the runtime directly; nothing is copied to or from the host
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return PR_OK;
+}
+
+int pr_score_contours(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                      const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, int32_t jump_mm,
+                      const uint8_t *edge_dist_dev, pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host)
+{
+    PR_ENTER();
+    if (overlap_host) PR_TRY(overlap_args_ok("pr_score_contours", n_poses, overlap_host));
+    const ContourOut ct{ jump_mm, edge_dist_dev, contours_host };
+    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host, overlap_host, &ct,
+                      "pr_score_contours");
+}
+
+int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                            uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                            int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint8_t *edge_dist_dev, pr_pose_score *scores_host,
+                            pr_pose_contour *contours_host, uint32_t *overlap_host)
+{
+    PR_ENTER();
+    if (overlap_host) PR_TRY(overlap_args_ok("pr_score_contours_multi", n_poses, overlap_host));
+    const ContourOut ct{ jump_mm, edge_dist_dev, contours_host };
+    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
+                       overlap_host, &ct, "pr_score_contours_multi");
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

@@ -278,6 +278,9 @@ struct Ctx {
     DevBuf scores;                   // pr_score_poses: the records of a chunk
     DevBuf ov_bits, ov_box, ov_mat;  // pr_score_overlap: the support bit planes and pixel boxes of ALL hypotheses of a call (they outlive its depth chunks), the P x P matrix
     PinBuf h_ov;                     // the matrix on its way to the caller
+    DevBuf contours;                 // pr_score_contours: the contour records of a chunk
+    DevBuf edge_bits, edge_rows;     // pr_scene_edge_distance_dev: the scene's edge bit plane and its row distances (scratch of one call)
+    PinBuf h_contours;
     DevBuf multi;                    // mixed batches (pr_*_multi): mesh table, box index / image of each hypothesis, raster groups
     PinBuf h_sums, h_meta, h_counts, h_results, h_dstate, h_poses, h_flags, h_scores, h_multi;
     PackedCache packed;              // synchronous paths (the asynchronous slots keep their own)

@@ -307,6 +307,36 @@ int  pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const ui
                           uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
                           int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host);
 
+/* ---- coarse-to-fine refinement: a pyramid of strided clouds per hypothesis -------------------------------------------------------------
+ * A pyramid is a table of 1 .. PR_PYRAMID_MAX_LEVELS levels, coarse first by convention (no order of the strides is imposed), each a stride
+ * 1 .. PR_PYRAMID_MAX_STRIDE and the criteria of the ICP run on that level.  Let C1 be a hypothesis' stride-1 cloud exactly as
+ * pr_refine_batch_roi builds it: the rendered pixels inside the ROI, row-major, back-projected with K at their frame coordinates.  The level
+ * cloud of stride s is the subsequence of C1 whose FRAME pixel satisfies x % s == 0 && y % s == 0 -- the grid is anchored on the frame, not
+ * on the ROI, so a window that contains the silhouette does not change the result; the points keep C1's bits and order.  (This is not the
+ * reference's depth2cloud(stride), which back-projects grid indices and so needs the K of a down-sampled image: pr_depth2cloud_* keeps that
+ * meaning.)  The render stays full-size; only the clouds are thinned.
+ * With T_acc = I, level l takes its cloud, transforms it by T_acc when l > 0 (one transform of the original points, transform_pcd's
+ * arithmetic), runs the ICP of pr_refine_batch on it with levels[l].crit -- same kernels, reduction tree, solve modes and early-exit rules --
+ * which gives the level record (T_l, fitness_l, rmse_l), and T_acc = T_l * T_acc in pr_mat4_mul's order.  An empty level cloud, or a first
+ * pass without a correspondence, gives the untouched record (identity, 0, 0) and T_acc carries over.  results_host[i] = T_acc with the
+ * fitness and rmse of the LAST level, so pr_refined_poses and the pr_score_* family take it as they take pr_refine_batch's records.
+ * level_results_host / level_sizes_host (either may be NULL): the records and cloud sizes of every level, [n_levels][n_poses].
+ * One level of stride 1 returns pr_refine_batch_roi's records byte for byte.  Synchronous, on the calling thread's context; a batch pending
+ * on an asynchronous slot finishes first and stays pending.  The level table is checked before any device is touched: PR_ERR_INVALID, with nothing written,
+ * for n_levels == 0 or > PR_PYRAMID_MAX_LEVELS, a stride of 0 or > PR_PYRAMID_MAX_STRIDE, max_iteration < 0, and for levels or results_host
+ * NULL with n_poses > 0; the frame, ROI and (multi) mesh-index checks of pr_refine_batch_roi / pr_refine_batch_multi apply as well.
+ * n_poses == 0 returns PR_OK and writes nothing. */
+#define PR_PYRAMID_MAX_LEVELS 4
+#define PR_PYRAMID_MAX_STRIDE 16
+typedef struct { uint32_t stride; pr_criteria crit; } pr_pyramid_level;   /* 16 B */
+int  pr_refine_pyramid(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                       const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels,
+                       pr_roi roi, pr_result *results_host, pr_result *level_results_host, uint32_t *level_sizes_host);
+int  pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                             uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                             const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
+                             pr_result *level_results_host, uint32_t *level_sizes_host);
+
 /* ---- detections from a scored batch: which hypotheses explain the same scene pixels ------------------------------------------------------
  * The support of hypothesis i is the set of frame pixels pr_score_poses counts as `inlier` for it (rendered, s > 0, |r - s| <= tau_mm).
  * pr_score_overlap scores a batch exactly as pr_score_poses does -- scores_host is byte for byte the same -- and also returns

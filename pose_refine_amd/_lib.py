@@ -47,6 +47,14 @@ class Criteria(C.Structure):
     _fields_ = [("relative_fitness", C.c_float), ("relative_rmse", C.c_float), ("max_iteration", C.c_int)]
 
 
+class PyramidLevel(C.Structure):
+    """pr_pyramid_level: one level of a coarse-to-fine schedule (pr_refine_pyramid): the cloud stride and the ICP criteria run on it."""
+    _fields_ = [("stride", C.c_uint32), ("crit", Criteria)]
+
+
+PYRAMID_MAX_LEVELS, PYRAMID_MAX_STRIDE = 4, 16          # PR_PYRAMID_MAX_LEVELS, PR_PYRAMID_MAX_STRIDE
+
+
 class MeshRef(C.Structure):
     """pr_mesh_ref: one mesh of a mixed batch (pr_*_multi)."""
     _fields_ = [("tris_dev", C.c_void_p), ("n_tris", C.c_size_t)]
@@ -122,6 +130,8 @@ SIGNATURES = {
     "pr_refined_poses": (None, [_vp, _vp, _u32, _vp]),
     "pr_render_multi": (_i32, [_vp, _u32, _vp, _vp, _sz, _sz, _sz, _vp, Roi, _vp]),
     "pr_refine_batch_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, Roi, _vp, _vp]),
+    "pr_refine_pyramid": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, _vp, _u32, Roi, _vp, _vp, _vp]),
+    "pr_refine_pyramid_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, _vp, _u32, Roi, _vp, _vp, _vp]),
     "pr_score_poses_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp]),
     "pr_score_overlap": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),
     "pr_score_overlap_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),

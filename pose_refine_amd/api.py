@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, KDNODE, MeshRef, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
+from ._lib import (COMM_ID_BYTES, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, KDNODE, MeshRef, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -722,6 +722,81 @@ def refine_batch_multi(meshes, mesh_index, poses, width: int, height: int, proj,
     check(_lib.load().pr_refine_batch_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), ptr(k), scene.kind,
                                             C.addressof(d), criteria.c(), Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(sizes)))
     return res, sizes
+
+
+# ------------------------------------------------------------------------------------------------
+# coarse-to-fine refinement: a pyramid of strided clouds per hypothesis
+# ------------------------------------------------------------------------------------------------
+def PyramidLevel(stride: int, criteria) -> _PyramidLevel:
+    """One level of a schedule (``pr_pyramid_level``): every ``stride``-th frame column and row of the rendered cloud, refined with
+    ``criteria`` -- an ``ICPConvergenceCriteria`` or a (relative_fitness, relative_rmse, max_iteration) triple."""
+    c = criteria.c() if isinstance(criteria, ICPConvergenceCriteria) else Criteria(float(criteria[0]), float(criteria[1]), int(criteria[2]))
+    if not 0 <= int(stride) < 2**32:
+        raise ValueError(f"stride {stride} is no uint32")
+    return _PyramidLevel(int(stride), c)
+
+
+PYRAMID_DEFAULT = ((4, (0, 0, 12)), (2, (0, 0, 5)), (1, (0, 0, 3)))
+"""The default schedule, coarse first, as (stride, (relative_fitness, relative_rmse, max_iteration)): 12 iterations on every 4th column
+and row, 5 on every 2nd, 3 at full resolution.  Measured with the CPU oracle on ``synth.hypotheses(48)`` (obj_06 scenario, projective
+scene, canonical sums, 2048 points per block) against 20 full-resolution iterations: 0.301 of the point-passes; for all 43 hypotheses
+that converge (fitness >= 0.9) the final translation differs by at most 0.016 mm and fitness / rmse agree to the 4th digit; the other five
+converge under neither schedule.  Over ``synth.hypotheses(256)`` the same comparison loses 2 of the 218 hypotheses the full run converges on
+(the coarse level walks them into another basin) and keeps 212 within 0.05 mm: a schedule is a trade, and no policy for choosing one is
+part of this module.  What it costs or saves on an MI355X -- a third less time on a kd-tree scene, nothing on a projective one -- is in
+profiles/pyramid/README.md."""
+
+
+def _level_table(levels):
+    lv = [l if isinstance(l, _PyramidLevel) else PyramidLevel(*l) for l in levels]
+    return (_PyramidLevel * max(1, len(lv)))(*lv), len(lv)
+
+
+def _pyramid_outputs(n_levels: int, n_poses: int, levels, return_levels: bool, res, lres, lsizes):
+    if return_levels:
+        return res, lres, lsizes
+    # the stride-1 cloud size when a level has stride 1 (what refine_batch returns), else the LAST level's cloud size
+    strides = [l.stride for l in levels[:n_levels]]
+    row = strides.index(1) if 1 in strides else n_levels - 1
+    return res, lsizes[row].copy()
+
+
+def refine_pyramid(tris, poses, width: int, height: int, proj, K, scene, levels=PYRAMID_DEFAULT, roi: Optional[Sequence[int]] = None,
+                   return_levels: bool = False):
+    """``pr_refine_pyramid``: ``refine_batch`` run coarse to fine.  ``levels``: 1..4 ``PyramidLevel`` (or (stride, criteria) pairs), coarse
+    first; level l refines the cloud of every ``stride``-th FRAME column and row, moved by what the levels before it found.  Returns
+    (records[P], sizes[P]): the accumulated transform with the last level's fitness and rmse, and the stride-1 cloud size as ``refine_batch``
+    returns it when a level has stride 1 -- otherwise the last level's cloud size.  ``return_levels=True``: (records[P],
+    level_records[L, P], level_sizes[L, P]).  One level of stride 1 equals ``refine_batch`` byte for byte."""
+    table, n_levels = _level_table(levels)
+    td = _tris_dev(tris)
+    poses = _f32(poses, (-1, 16))
+    pj, k = _f32(proj, -1), _f32(K, -1)
+    P = len(poses)
+    res = np.zeros(P, RESULT)
+    lres = np.zeros((max(1, n_levels), P), RESULT)
+    lsizes = np.zeros((max(1, n_levels), P), np.uint32)
+    d = scene.desc()
+    check(_lib.load().pr_refine_pyramid(td.data() or None, td.size() // 9, ptr(poses), P, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
+                                        table, n_levels, Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(lres), ptr(lsizes)))
+    return _pyramid_outputs(n_levels, P, table, return_levels, res, lres, lsizes)
+
+
+def refine_pyramid_multi(meshes, mesh_index, poses, width: int, height: int, proj, K, scene, levels=PYRAMID_DEFAULT,
+                         roi: Optional[Sequence[int]] = None, return_levels: bool = False):
+    """``pr_refine_pyramid_multi``: ``refine_pyramid`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; every output in pose
+    order and equal to what ``refine_pyramid`` gives that pose with its own mesh."""
+    table, n_levels = _level_table(levels)
+    mtable, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    pj, k = _f32(proj, -1), _f32(K, -1)
+    P = len(poses)
+    res = np.zeros(P, RESULT)
+    lres = np.zeros((max(1, n_levels), P), RESULT)
+    lsizes = np.zeros((max(1, n_levels), P), np.uint32)
+    d = scene.desc()
+    check(_lib.load().pr_refine_pyramid_multi(mtable, len(devs), ptr(idx), ptr(poses), P, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
+                                              table, n_levels, Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(lres), ptr(lsizes)))
+    return _pyramid_outputs(n_levels, P, table, return_levels, res, lres, lsizes)
 
 
 def _scene_depth_dev(scene_depth, width: int, height: int) -> DeviceVector:

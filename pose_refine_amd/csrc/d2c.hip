@@ -39,12 +39,7 @@ __global__ __launch_bounds__(256) void d2c_emit_box_kernel(const int32_t *__rest
                 const unsigned long long m = __ballot(v);
                 if (v) {
                     const uint32_t k = done + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                    const float z = d / 1000.0f;
-                    pr_vec3 p;
-                    p.x = ((float)(uint32_t)x - cx) / fx * z;
-                    p.y = ((float)row - cy) / fy * z;
-                    p.z = z;
-                    out[k] = p;
+                    out[k] = backproject_pixel(x, row, d, fx, fy, cx, cy);
                 }
                 done += (uint32_t)__popcll(m);
             }

@@ -106,4 +106,25 @@ __device__ __forceinline__ int32_t *box_line(int32_t *depth, const uint32_t *box
     return depth + box_off[pose] + ((ptrdiff_t)row - (ptrdiff_t)((int)height - 1 - bb.w)) * pitch - (ptrdiff_t)bb.x;      // line[x] for bb.x <= x <= bb.z
 }
 
+// depth2cloud's back-projection of frame pixel (x, row) with depth d in mm (icp.cu:249-253: z = d/1000.f; x = (u - cx)/fx*z; y = (v - cy)/fy*z):
+// what every fused-path emit writes for a rendered pixel
+__device__ __forceinline__ pr_vec3 backproject_pixel(int x, uint32_t row, int32_t d, float fx, float fy, float cx, float cy)
+{
+    const float z = d / 1000.0f;
+    pr_vec3 p;
+    p.x = ((float)(uint32_t)x - cx) / fx * z;
+    p.y = ((float)row - cy) / fy * z;
+    p.z = z;
+    return p;
+}
+// transform_pcd (icp.cpp:47-59) of one point by rows 0..2 of a 4x4, in the fused pass' operand order: ((m0*x + m1*y) + m2*z) + m3
+__device__ __forceinline__ pr_vec3 transform_point(const float *M, const pr_vec3 p)
+{
+    pr_vec3 q;
+    q.x = M[0] * p.x + M[1] * p.y + M[2] * p.z + M[3];
+    q.y = M[4] * p.x + M[5] * p.y + M[6] * p.z + M[7];
+    q.z = M[8] * p.x + M[9] * p.y + M[10] * p.z + M[11];
+    return q;
+}
+
 }  // namespace prk

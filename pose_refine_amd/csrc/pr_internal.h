@@ -225,6 +225,20 @@ hipError_t launch_emit_box(const int32_t *depth, uint32_t n_poses, uint32_t widt
                            float cx, float cy, const uint32_t *row_count, const uint32_t *row_off, pr_vec3 *cloud, size_t cloud_stride,
                            hipStream_t s, const PoseMeta *meta = nullptr, const uint32_t *box_off = nullptr);     // meta: cloud i starts at meta[i].start (packed, launch_render_boxes wrote it) instead of i * cloud_stride
 
+// pyramid.hip (pr_refine_pyramid): the strided level clouds of the hypotheses of a chunk, from the depth boxes launch_render_boxes left.
+// PyramidStrides: the levels' strides (unused entries 1).  PyramidCarry: what the emit of ONE level needs per hypothesis -- rows 0..2 of the transform
+// accumulated over the levels before it and where its cloud starts (points, packed like d2c_pack_starts' layout) -- one 64-byte record, staged by the host.
+struct PyramidStrides { uint32_t n; uint32_t s[PR_PYRAMID_MAX_LEVELS]; };
+struct alignas(64) PyramidCarry { float T[12]; uint32_t start; uint32_t pad[3]; };
+static_assert(sizeof(PyramidCarry) == 64, "PyramidCarry must stay one 64-byte record");
+// row_count / row_off: [level][hypothesis][height] words each; counts[level * n_poses + hypothesis] = that level cloud's size.  The depth is read once.
+hipError_t launch_pyramid_counts(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
+                                 const PyramidStrides &lv, uint32_t *row_count, uint32_t *row_off, uint32_t *counts, hipStream_t s);
+// one level: row_count / row_off are that level's [hypothesis][height] plane; apply: every point goes through its hypothesis' carry transform
+hipError_t launch_pyramid_emit(const int32_t *depth, uint32_t n_poses, uint32_t width, uint32_t height, const int4 *bbox, const uint32_t *box_off,
+                               float fx, float fy, float cx, float cy, uint32_t stride, const uint32_t *row_count, const uint32_t *row_off,
+                               const PyramidCarry *carry, bool apply, pr_vec3 *cloud, hipStream_t s);
+
 hipError_t launch_icp_pass_proj_aos(const IcpBatch &b, const SceneProjAoS &sc, uint32_t n_poses, hipStream_t s);
 hipError_t launch_icp_pass_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s);
 hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s);

@@ -204,9 +204,97 @@ int render_chunk(const MeshSource &src, const pr_mat4 *poses_host, uint32_t p0, 
     return PR_OK;
 }
 
+// ---- coarse-to-fine refinement (pr_refine_pyramid): the levels of one rendered chunk -------------------------------------------------------
+// What a pyramid call adds to refine_core: the level table and where the per-level outputs go ([n_levels][P], either may be null).
+struct PyramidPlan { const pr_pyramid_level *levels; uint32_t n_levels; uint32_t P; pr_result *level_results; uint32_t *level_sizes; };
+// the level table's own conditions, checked before any device is touched (a box without a GPU reports a bad table as such)
+int pyramid_levels_ok(const char *fn, const pr_pyramid_level *levels, uint32_t n_levels, uint32_t P, const pr_result *results_host)
+{
+    if (n_levels == 0 || n_levels > PR_PYRAMID_MAX_LEVELS) { set_error("%s: n_levels must be 1..%d (got %u)", fn, PR_PYRAMID_MAX_LEVELS, n_levels); return PR_ERR_INVALID; }
+    if (!levels) { if (P == 0) return PR_OK; set_error("%s: bad arguments (levels is null)", fn); return PR_ERR_INVALID; }
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        if (levels[l].stride == 0 || levels[l].stride > PR_PYRAMID_MAX_STRIDE) { set_error("%s: level %u has stride %u, must be 1..%d", fn, l, levels[l].stride, PR_PYRAMID_MAX_STRIDE); return PR_ERR_INVALID; }
+        if (levels[l].crit.max_iteration < 0) { set_error("%s: level %u: max_iteration must be >= 0", fn, l); return PR_ERR_INVALID; }
+    }
+    if (P && !results_host) { set_error("%s: results_host is null", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+// Hypotheses [p0, p0 + np) are rendered (render_chunk: depth boxes, pixel boxes).  One pass counts every level's samples and the sizes of all levels come
+// back in the chunk's one read-back; then, level by level: the carry records (accumulated transform, cloud start) are staged, the level's clouds emitted
+// through them, icp_drive run on them as on any batch of clouds, and the accumulated transform advanced on the host (T_l * T_acc, pr_mat4_mul) -- both
+// solve modes leave a level's records on the host, and the next level's emit needs them staged either way.
+int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, uint32_t H, const float K[9], const uint32_t *box_off, const SceneSel &sc,
+                  pr_result *results_host)
+{
+    const uint32_t L = py.n_levels;
+    const size_t plane = (size_t)L * np * H;                      // words of row counts; the row offsets follow
+    PR_TRY(g->lvl_rows.ensure(sizeof(uint32_t) * 2 * plane));
+    PR_TRY(g->lvl_counts.ensure(sizeof(uint32_t) * L * np));
+    PR_TRY(g->h_counts.ensure(sizeof(uint32_t) * L * np));
+    PR_TRY(g->lvl_carry.ensure(sizeof(prk::PyramidCarry) * np));
+    PR_TRY(g->h_lvl_carry.ensure(sizeof(prk::PyramidCarry) * np));
+    uint32_t *row_count = g->lvl_rows.as<uint32_t>(), *row_off = row_count + plane;
+    prk::PyramidStrides lv{};
+    lv.n = L;
+    for (uint32_t l = 0; l < PR_PYRAMID_MAX_LEVELS; ++l) lv.s[l] = l < L ? py.levels[l].stride : 1u;
+    uint32_t *h_counts = g->h_counts.as<uint32_t>();
+    {
+        SpanGuard sp(kSpanCloud);
+        HIP_TRY(prk::launch_pyramid_counts(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, lv, row_count, row_off, g->lvl_counts.as<uint32_t>(), g->stream));
+        void *hc = nullptr;                                       // all levels' sizes through a kernel's stores into the pinned array (see refine_core)
+        HIP_TRY(hipHostGetDevicePointer(&hc, h_counts, 0));
+        HIP_TRY(prk::launch_copy_words32(g->lvl_counts.p, hc, L * np, g->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    trace_mark("pyramid_chunk: level sizes on host");
+    // every level's clouds packed one behind the other like the stride-1 clouds of refine_core; the workspace holds the largest level
+    constexpr size_t align = prk::kCloudAlign ? prk::kCloudAlign : 4;
+    size_t most = 4;
+    for (uint32_t l = 0; l < L; ++l) {
+        size_t total = 0;
+        for (uint32_t i = 0; i < np; ++i) total += ((size_t)h_counts[(size_t)l * np + i] + align - 1) / align * align;
+        if (total > 0xffffffffull) { set_error("pr_refine_pyramid: more than 2^32 cloud points in one chunk"); return PR_ERR_INVALID; }
+        most = std::max(most, total);
+    }
+    PR_TRY(g->cloud.ensure(sizeof(pr_vec3) * most));
+    void *carry_mapped = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&carry_mapped, g->h_lvl_carry.p, 0));
+    prk::PyramidCarry *h_carry = g->h_lvl_carry.as<prk::PyramidCarry>();
+    std::vector<pr_result> acc(np), rec(np);
+    std::vector<uint32_t> start(np), count(np);
+    for (uint32_t i = 0; i < np; ++i) { identity16(acc[i].T); acc[i].fitness = 0.0f; acc[i].inlier_rmse = 0.0f; }
+    for (uint32_t l = 0; l < L; ++l) {
+        size_t total = 0;
+        for (uint32_t i = 0; i < np; ++i) {
+            start[i] = (uint32_t)total; count[i] = h_counts[(size_t)l * np + i];
+            total += ((size_t)count[i] + align - 1) / align * align;
+            std::memset(&h_carry[i], 0, sizeof(prk::PyramidCarry));
+            std::memcpy(h_carry[i].T, acc[i].T, sizeof(float) * 12);
+            h_carry[i].start = start[i];
+        }
+        if (total > 0) {
+            SpanGuard sp(kSpanCloud);
+            HIP_TRY(prk::launch_stage_words(carry_mapped, g->lvl_carry.p, sizeof(prk::PyramidCarry) * np, g->stream));
+            HIP_TRY(prk::launch_pyramid_emit(g->depth.as<int32_t>(), np, W, H, g->bbox.as<int4>(), box_off, K[0], K[4], K[2], K[5], py.levels[l].stride,
+                                             row_count + (size_t)l * np * H, row_off + (size_t)l * np * H, g->lvl_carry.as<prk::PyramidCarry>(), l > 0,
+                                             g->cloud.as<pr_vec3>(), g->stream));
+        }
+        trace_mark("pyramid_chunk: level emitted, icp_drive next");
+        PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, py.levels[l].crit, rec.data(), nullptr));     // (returns with the stream drained: the pinned carry records are free again)
+        for (uint32_t i = 0; i < np; ++i) {
+            prh::mat4_mul(rec[i].T, acc[i].T, acc[i].T);
+            acc[i].fitness = rec[i].fitness; acc[i].inlier_rmse = rec[i].inlier_rmse;
+        }
+        if (py.level_results) std::memcpy(py.level_results + (size_t)l * py.P + p0, rec.data(), sizeof(pr_result) * np);
+        if (py.level_sizes) std::memcpy(py.level_sizes + (size_t)l * py.P + p0, count.data(), sizeof(uint32_t) * np);
+    }
+    std::memcpy(results_host, acc.data(), sizeof(pr_result) * np);
+    return PR_OK;
+}
+
 int refine_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
                 const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host)
+                pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host, const PyramidPlan *pyramid = nullptr)
 {
     if (!K || W == 0 || H == 0) { set_error("pr_refine_batch: bad arguments"); return PR_ERR_INVALID; }
     if (!frame_size_ok(W, H) || !roi_ok(roi, W, H)) return PR_ERR_INVALID;
@@ -237,6 +325,7 @@ int refine_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, ui
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, proj, roi, box_off, !src.plan && opt.raster_mode == 1));
         }
+        if (pyramid) { PR_TRY(pyramid_chunk(*pyramid, p0, np, W, H, K, box_off, sc, results_host + p0)); continue; }
         {   // the cloud sizes come back through a kernel's stores into the pinned array, not through a copy command (see icp_drive's result block)
             void *hc = nullptr;
             HIP_TRY(hipHostGetDevicePointer(&hc, h_counts, 0));
@@ -409,6 +498,49 @@ int refine_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *m
     for (uint32_t j = 0; j < P; ++j) {
         results_host[pl.order[j]] = res[j];
         if (sizes_host) sizes_host[pl.order[j]] = sizes[j];
+    }
+    return PR_OK;
+}
+
+// pr_refine_pyramid / pr_refine_pyramid_multi behind their level-table check: the arguments' own checks, then refine_core with the plan
+int pyramid_single(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
+                   const float K[9], int scene_kind, const void *scene, const PyramidPlan &py, pr_roi roi, pr_result *results_host)
+{
+    if (P == 0) return PR_OK;
+    if ((!tris_dev && n_tris > 0) || !poses_host || !proj || !K || !scene) { set_error("pr_refine_pyramid: bad arguments"); return PR_ERR_INVALID; }
+    if (W == 0 || H == 0 || !frame_size_ok(W, H) || !roi_ok(roi, W, H)) { if (W == 0 || H == 0) set_error("pr_refine_pyramid: bad arguments"); return PR_ERR_INVALID; }
+    std::vector<pr_result> res(P);                               // (nothing is written to the caller's arrays unless the whole call succeeds)
+    std::vector<pr_result> lres(py.level_results ? (size_t)py.n_levels * P : 0);
+    std::vector<uint32_t> lsizes(py.level_sizes ? (size_t)py.n_levels * P : 0);
+    const PyramidPlan inner{ py.levels, py.n_levels, P, py.level_results ? lres.data() : nullptr, py.level_sizes ? lsizes.data() : nullptr };
+    PR_TRY(refine_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, res.data(), nullptr,
+                       nullptr, &inner));
+    std::memcpy(results_host, res.data(), sizeof(pr_result) * P);
+    if (py.level_results) std::memcpy(py.level_results, lres.data(), sizeof(pr_result) * lres.size());
+    if (py.level_sizes) std::memcpy(py.level_sizes, lsizes.data(), sizeof(uint32_t) * lsizes.size());
+    return PR_OK;
+}
+int pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
+                  const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const PyramidPlan &py, pr_roi roi, pr_result *results_host)
+{
+    if (P == 0) return PR_OK;
+    if (!poses_host || !proj || !K || !scene) { set_error("pr_refine_pyramid_multi: bad arguments"); return PR_ERR_INVALID; }
+    if (W == 0 || H == 0 || !frame_size_ok(W, H) || !roi_ok(roi, W, H)) { if (W == 0 || H == 0) set_error("pr_refine_pyramid_multi: bad arguments"); return PR_ERR_INVALID; }
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_refine_pyramid_multi", meshes, n_meshes, mesh_index, P, pl));
+    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
+    std::vector<pr_result> res(P);
+    std::vector<pr_result> lres(py.level_results ? (size_t)py.n_levels * P : 0);
+    std::vector<uint32_t> lsizes(py.level_sizes ? (size_t)py.n_levels * P : 0);
+    const PyramidPlan inner{ py.levels, py.n_levels, P, py.level_results ? lres.data() : nullptr, py.level_sizes ? lsizes.data() : nullptr };
+    PR_TRY(refine_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, res.data(), nullptr, nullptr,
+                       &inner));
+    for (uint32_t j = 0; j < P; ++j) {                          // back to the caller's order
+        results_host[pl.order[j]] = res[j];
+        for (uint32_t l = 0; l < py.n_levels; ++l) {
+            if (py.level_results) py.level_results[(size_t)l * P + pl.order[j]] = lres[(size_t)l * P + j];
+            if (py.level_sizes) py.level_sizes[(size_t)l * P + pl.order[j]] = lsizes[(size_t)l * P + j];
+        }
     }
     return PR_OK;
 }
@@ -1161,6 +1293,31 @@ int pr_refine_batch_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const ui
 {
     PR_ENTER();
     return refine_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene, crit, roi, results_host, cloud_sizes_host);
+}
+
+int pr_refine_pyramid(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                      const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels,
+                      pr_roi roi, pr_result *results_host, pr_result *level_results_host, uint32_t *level_sizes_host)
+{
+    PR_TRY(pyramid_levels_ok("pr_refine_pyramid", levels, n_levels, n_poses, results_host));      // before any device use
+    PR_ENTER();
+    // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
+    for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+    const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
+    return pyramid_single(tris_dev, n_tris, poses_host, n_poses, width, height, proj, K, scene_kind, scene, py, roi, results_host);
+}
+
+int pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                            uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                            const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
+                            pr_result *level_results_host, uint32_t *level_sizes_host)
+{
+    PR_TRY(pyramid_levels_ok("pr_refine_pyramid_multi", levels, n_levels, n_poses, results_host));
+    PR_ENTER();
+    // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
+    for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+    const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
+    return pyramid_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene, py, roi, results_host);
 }
 
 int pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,

@@ -53,6 +53,11 @@
 #define PR_BOX_PACK 32                                          // fused asynchronous path: a hypothesis' pixel box is its own little image in the depth workspace, packed behind the one before it, rounded up to this many pixels (0: full frames, rounds 1-4)
 #endif
 
+// ---- coarse-to-fine refinement (pyramid.hip) -----------------------------------------------------------------------------------------
+#ifndef PR_PYRAMID_EMIT_LOADS
+#define PR_PYRAMID_EMIT_LOADS 4                                 // level emit: sampled pixels of a row a lane requests before the first ballot (a 640-pixel row at stride 1 is three steps of 256; at stride 4 one step covers it)
+#endif
+
 // ---- kd-tree search: ordered per-lane walks (nn_query.h) ---------------------------------------------------------------------------
 #ifndef PR_LEAF_BATCH
 #define PR_LEAF_BATCH 10                                        // points of a leaf fetched before the first compare (the reference's max_leaf)

@@ -401,6 +401,53 @@ int  pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const
                              int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint8_t *edge_dist_dev,
                              pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host);
 
+/* ---- composition: the detections of a frame taken together -----------------------------------------------------------------------------
+ * Everything above looks at a hypothesis on its own or at pairs.  pr_compose_detections renders a set of poses -- typically the few that
+ * pr_select_greedy kept -- and composes them: all arithmetic in integers (differences in 64 bits), depth in mm.  r_i(q) is hypothesis i's
+ * rendered depth at frame pixel q (pr_render's value; 0 where nothing is drawn), front(q) the minimum of the positive r_i(q), and owner(q)
+ * the LOWEST index in the caller's pose order that attains it (so duplicates and ties have a defined owner, in mixed batches too).
+ *   labels_dev_out[q] = owner(q), or PR_COMPOSE_NONE where no hypothesis renders;  depth_dev_out[q] = front(q), or 0.
+ * Both are dense width x height frames in the caller's device memory (either may be NULL); with a ROI the pixels outside the window get
+ * PR_COMPOSE_NONE and 0; every pixel of both is written by every call with n_poses > 0.
+ *   scores_host  = byte for byte what pr_score_poses returns (each hypothesis on its own, as if the others were not there);
+ *   visible_host = per hypothesis the frame pixels it owns, by pr_pose_score's four tests with r = r_i(q) = front(q) there;
+ *   frame_host   = the frame (the ROI window when one is given) against the composite, r = front(q).
+ * So scores.visible - owned is what other hypotheses hide of i, scores.inlier - owned_inlier the support it claims under another model;
+ * the sum of owned over i equals covered, of owned_inlier explained, of owned_occluded behind, of owned_violation in_front, of
+ * owned_missing unmeasured.  Argument checks, ROI, scene types, chunking and the synchronous behaviour are those of pr_score_poses
+ * (pr_score_poses_multi for pr_compose_detections_multi); a batch pending on an asynchronous slot is left alone.  n_poses == 0 returns
+ * PR_OK and writes nothing; n_poses > PR_COMPOSE_MAX_POSES is PR_ERR_INVALID (checked before anything else); a null scores_host,
+ * visible_host or frame_host with n_poses > 0 is PR_ERR_INVALID with nothing written.  The device keeps 8 bytes per frame pixel between
+ * calls (a grow-only workspace of the context).  Not offered: an asynchronous form, and re-scoring other hypotheses against the composite. */
+#define PR_COMPOSE_NONE      0xFFFFu
+#define PR_COMPOSE_MAX_POSES 65535u          /* a label is a uint16 */
+typedef struct {
+    uint32_t owned;            /* frame pixels whose front-most render is this hypothesis'                                    */
+    uint32_t owned_inlier;     /* of those: s > 0 and |r - s| <= tau                                                          */
+    uint32_t owned_occluded;   /* s > 0 and r - s > tau                                                                       */
+    uint32_t owned_violation;  /* s > 0 and s - r > tau                                                                       */
+    uint32_t owned_missing;    /* s <= 0                                                                                      */
+    uint32_t reserved[3];      /* written as 0                                                                                */
+} pr_pose_visible;             /* 32 B; owned == owned_inlier + owned_occluded + owned_violation + owned_missing              */
+typedef struct {
+    uint32_t window;           /* pixels of the frame, or of the ROI window                                                   */
+    uint32_t measured;         /* of those: s > 0                                                                             */
+    uint32_t covered;          /* of those: some hypothesis renders there                                                     */
+    uint32_t explained;        /* covered, s > 0 and |front - s| <= tau                                                       */
+    uint32_t in_front;         /* covered, s > 0 and s - front > tau: the composite lies before the measured surface          */
+    uint32_t behind;           /* covered, s > 0 and front - s > tau: it lies behind the measured surface                     */
+    uint32_t unmeasured;       /* covered and s <= 0                                                                          */
+    uint32_t reserved;         /* written as 0                                                                                */
+} pr_frame_explained;          /* 32 B; covered == explained + in_front + behind + unmeasured                                 */
+int  pr_compose_detections(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses,
+                           uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi,
+                           const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out, int32_t *depth_dev_out,
+                           pr_pose_score *scores_host, pr_pose_visible *visible_host, pr_frame_explained *frame_host);
+int  pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                                 uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                                 int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out, int32_t *depth_dev_out,
+                                 pr_pose_score *scores_host, pr_pose_visible *visible_host, pr_frame_explained *frame_host);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

@@ -30,7 +30,14 @@ SCORE = np.dtype([("visible", "<u4"), ("inlier", "<u4"), ("occluded", "<u4"), ("
 # pr_pose_contour: depth-edge agreement of one hypothesis with the scene (pr_score_contours)
 CONTOUR = np.dtype([("contour", "<u4"), ("hit", "<u4"), ("occluded", "<u4"), ("miss", "<u4"), ("reserved", "<u4", (2,)), ("dist_sum", "<u8")])
 CONTOUR_MAX_RADIUS = 32                  # PR_CONTOUR_MAX_RADIUS
+# pr_pose_visible / pr_frame_explained: what a hypothesis keeps once the batch is composed, and what the set explains (pr_compose_detections)
+VISIBLE = np.dtype([("owned", "<u4"), ("owned_inlier", "<u4"), ("owned_occluded", "<u4"), ("owned_violation", "<u4"), ("owned_missing", "<u4"),
+                    ("reserved", "<u4", (3,))])
+FRAME = np.dtype([("window", "<u4"), ("measured", "<u4"), ("covered", "<u4"), ("explained", "<u4"), ("in_front", "<u4"), ("behind", "<u4"),
+                  ("unmeasured", "<u4"), ("reserved", "<u4")])
+COMPOSE_NONE, COMPOSE_MAX_POSES = 0xFFFF, 65535      # PR_COMPOSE_NONE, PR_COMPOSE_MAX_POSES
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
+assert VISIBLE.itemsize == 32 and FRAME.itemsize == 32
 
 
 class PoseRefineError(RuntimeError):
@@ -139,6 +146,8 @@ SIGNATURES = {
     "pr_scene_edge_distance_dev": (_i32, [_vp, _i32, _u32, _u32, C.c_int32, _u32, _vp]),
     "pr_score_contours": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "pr_score_contours_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "pr_compose_detections": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "pr_compose_detections_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

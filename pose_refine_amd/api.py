@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, KDNODE, MeshRef, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -963,6 +963,57 @@ def filter_by_contour(order, contours, min_fraction: float) -> np.ndarray:
     ``min_fraction``; what remains keeps its order and goes to ``select_hypotheses(order=...)``.  The ranking itself is untouched."""
     order = np.asarray(order, np.int64)
     return order[contour_fraction(contours)[order] >= float(min_fraction)]
+
+
+# ------------------------------------------------------------------------------------------------
+# composition: the detections of a frame taken together
+# ------------------------------------------------------------------------------------------------
+def _compose_outputs(n_poses: int, width: int, height: int, want_labels: bool, want_depth: bool):
+    on = n_poses > 0                                                # (a call without hypotheses writes nothing: no frames then)
+    labels = DeviceVector(width * height, np.uint16) if want_labels and on else None
+    depth = DeviceVector(width * height, np.int32) if want_depth and on else None
+    return labels, depth, np.zeros(n_poses, SCORE), np.zeros(n_poses, VISIBLE), np.zeros(1, FRAME)
+
+
+def compose_detections(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, roi: Sequence[int] = (0, 0, 0, 0),
+                       want_labels: bool = True, want_depth: bool = True):
+    """``pr_compose_detections``: the poses -- typically ``select_hypotheses``' detections -- rendered into one frame.  Returns
+    (labels, depth, scores, visible, frame): ``labels`` a DeviceVector(uint16) of width x height with, per frame pixel, the index of the
+    hypothesis whose render is in front there (the lowest index on a tie) or ``COMPOSE_NONE``; ``depth`` a DeviceVector(int32) with that
+    front depth or 0 (each None when not wanted, or when there are no poses); ``scores`` = ``score_poses``' bytes; ``visible`` =
+    VISIBLE[P], the pixels every hypothesis owns by the four tests; ``frame`` = one FRAME record of the frame against the composite.
+    At most ``COMPOSE_MAX_POSES`` hypotheses per call."""
+    td = _tris_dev(tris)
+    poses = _f32(poses, (-1, 16))
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    labels, depth, out, vis, frame = _compose_outputs(len(poses), width, height, want_labels, want_depth)
+    check(_lib.load().pr_compose_detections(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                            sd.data(), int(sd.dtype == np.int32), int(tau_mm), labels.data() if labels else None,
+                                            depth.data() if depth else None, ptr(out), ptr(vis), ptr(frame)))
+    return labels, depth, out, vis, frame[0]
+
+
+def compose_detections_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int,
+                             roi: Sequence[int] = (0, 0, 0, 0), want_labels: bool = True, want_depth: bool = True):
+    """``pr_compose_detections_multi``: ``compose_detections`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; labels, ties and
+    records in pose order."""
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    labels, depth, out, vis, frame = _compose_outputs(len(poses), width, height, want_labels, want_depth)
+    check(_lib.load().pr_compose_detections_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
+                                                  sd.data(), int(sd.dtype == np.int32), int(tau_mm), labels.data() if labels else None,
+                                                  depth.data() if depth else None, ptr(out), ptr(vis), ptr(frame)))
+    return labels, depth, out, vis, frame[0]
+
+
+def visible_fraction(scores, visible) -> np.ndarray:
+    """``owned / visible`` in float64: the share of a hypothesis' render that no other hypothesis of the composed set hides.  0 where
+    nothing is visible."""
+    sc, vi = np.asarray(scores), np.asarray(visible)
+    den = sc["visible"].astype(np.int64)
+    return np.where(den <= 0, 0.0, vi["owned"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
 
 
 def rank_hypotheses_per_mesh(scores, mesh_index) -> dict:

@@ -214,6 +214,18 @@ hipError_t launch_scene_edge_distance(const void *scene, bool scene_i32, uint32_
                                       unsigned long long *bits, uint8_t *row_dist, uint8_t *dist, hipStream_t s);
 hipError_t launch_contour_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
                                 const void *scene, bool scene_i32, const uint8_t *edge_dist, int32_t tau, int32_t jump_mm, uint32_t *records, hipStream_t s);
+// compose.hip: the hypotheses of a call taken together.  keys: width x height 64-bit words, (depth << 32 | caller's index) of the front-most render at every
+// frame pixel, all ones where nothing is drawn; index_of: position in the (grouped) batch -> caller's index, null: index0 + position.
+// launch_compose_tiles: once per depth chunk over launch_render_boxes' layout (first: the call's first chunk, which initialises the whole frame);
+// launch_compose_counts: once per call over the boxes of all n_poses <= PR_COMPOSE_MAX_POSES hypotheses, added into records[8 * caller's index]
+// (pr_pose_visible words), which the caller zeroed; launch_compose_emit: labels / depth_out (either may be null) and frame[0..6] (pr_frame_explained
+// words), zeroed by the caller.  window as for launch_contour_boxes
+hipError_t launch_compose_tiles(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
+                                const uint32_t *index_of, uint32_t index0, unsigned long long *keys, bool first, hipStream_t s);
+hipError_t launch_compose_counts(const unsigned long long *keys, const int4 *bbox, const uint32_t *index_of, uint32_t n_poses, uint32_t width, uint32_t height,
+                                 const void *scene, bool scene_i32, int32_t tau, uint32_t *records, hipStream_t s);
+hipError_t launch_compose_emit(const unsigned long long *keys, uint32_t width, uint32_t height, int4 window, const void *scene, bool scene_i32, int32_t tau,
+                               uint16_t *labels, int32_t *depth_out, uint32_t *frame, hipStream_t s);
 hipError_t launch_pack_export(const DevIcpState *st, pr_result *out, const uint32_t *counts, uint32_t *host_counts, pr_result *host_results,
                               uint32_t n, hipStream_t s);
 hipError_t launch_stage_words(const void *src_host_mapped, void *dst, size_t bytes, hipStream_t s);

@@ -377,10 +377,16 @@ int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses
 // as this one is scored -- and one launch over all pairs follows the last chunk.  The planes are dense: P x H x ceil(W / 64) words of 8 bytes.
 // ct (pr_score_contours; null: none): the contour records of the same renders against the scene's edge distance image (contour.hip), one more
 // kernel over every chunk's boxes right behind the score kernel; the records travel like the scores.
+// cp (pr_compose_detections; null: none): the same renders taken together (compose.hip).  One more kernel over every chunk's boxes folds them into
+// the key frame of the context -- the front-most render of every frame pixel with the CALLER's index of its hypothesis (order: grouped position ->
+// caller's index, null: the identity), so ties and labels need no remapping -- and every chunk leaves its pixel boxes in a workspace sized for
+// all P, as for the overlap matrix.  Behind the last chunk: the counts of what every hypothesis keeps, then one pass over the frame for the labels,
+// the front depth and the frame record.  visible is written in the caller's order whatever `order` is.
 struct ContourOut { int32_t jump; const uint8_t *edge_dist; pr_pose_contour *out; };
+struct ComposeOut { const uint32_t *order; uint16_t *labels_dev; int32_t *depth_dev; pr_pose_visible *visible; pr_frame_explained *frame; };
 int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
                pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
-               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses")
+               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses", const ComposeOut *cp = nullptr)
 {
     if (tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)tau); return PR_ERR_INVALID; }
     if (!proj || W == 0 || H == 0 || (P && (!poses_host || !scene_dev || !scores_host || (!src.tris && src.n_tris > 0)))) {
@@ -390,7 +396,9 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
     if (!roi_ok(roi, W, H)) { set_error("%s: roi out of image", fn); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
     if (ct && ct->jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)ct->jump); return PR_ERR_INVALID; }
     if (ct && P && (!ct->edge_dist || !ct->out)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
+    if (cp && P && (!cp->visible || !cp->frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }
     if (P == 0) return PR_OK;
+    static_assert(sizeof(pr_pose_visible) == sizeof(pr_pose_score) && sizeof(pr_frame_explained) == sizeof(pr_pose_score), "pr_pose_visible, pr_frame_explained: 32-byte records");
     static_assert(sizeof(pr_pose_contour) == sizeof(pr_pose_score) && offsetof(pr_pose_contour, dist_sum) == 24, "pr_pose_contour: one 32-byte record, the sum in words 6 and 7");
     const bool has_roi = roi.width > 0 && roi.height > 0;
     const int4 window = has_roi ? make_int4(roi.x, roi.y, roi.x + roi.width - 1, roi.y + roi.height - 1) : make_int4(0, 0, (int)W - 1, (int)H - 1);
@@ -405,6 +413,22 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         PR_TRY(g->ov_box.ensure(sizeof(int4) * P));
         PR_TRY(g->ov_mat.ensure(sizeof(uint32_t) * (size_t)P * P));
         PR_TRY(g->h_ov.ensure(sizeof(uint32_t) * (size_t)P * P));
+    }
+    // composition: records = P x pr_pose_visible, then the frame's; the pinned block holds them and, behind them, the index table on its way in
+    const size_t cmp_rec_bytes = sizeof(pr_pose_visible) * ((size_t)P + 1), cmp_idx_bytes = (sizeof(uint32_t) * (size_t)P + 15) / 16 * 16;
+    uint32_t *cmp_index = nullptr;                                  // device: grouped position -> caller's index (null: the identity)
+    if (cp) {
+        PR_TRY(g->cmp_keys.ensure(sizeof(uint64_t) * img));
+        PR_TRY(g->cmp_box.ensure(sizeof(int4) * P + cmp_idx_bytes));
+        PR_TRY(g->cmp_rec.ensure(cmp_rec_bytes));
+        PR_TRY(g->h_cmp.ensure(cmp_rec_bytes + cmp_idx_bytes));
+        if (cp->order) {
+            void *hc = nullptr;
+            HIP_TRY(hipHostGetDevicePointer(&hc, g->h_cmp.p, 0));
+            std::memcpy(g->h_cmp.as<unsigned char>() + cmp_rec_bytes, cp->order, sizeof(uint32_t) * P);
+            cmp_index = reinterpret_cast<uint32_t *>(g->cmp_box.as<int4>() + P);
+            HIP_TRY(prk::launch_stage_words(static_cast<unsigned char *>(hc) + cmp_rec_bytes, cmp_index, sizeof(uint32_t) * P, g->stream));
+        }
     }
     for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
         const uint32_t np = std::min(chunk, P - p0);
@@ -438,6 +462,11 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
                                              g->ov_bits.as<unsigned long long>() + plane_words * p0, g->stream));
             HIP_TRY(prk::launch_copy_words32(g->bbox.p, g->ov_box.as<int4>() + p0, 4 * np, g->stream));
         }
+        if (cp) {
+            HIP_TRY(prk::launch_compose_tiles(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, cmp_index ? cmp_index + p0 : nullptr, p0,
+                                              g->cmp_keys.as<unsigned long long>(), p0 == 0, g->stream));
+            HIP_TRY(prk::launch_copy_words32(g->bbox.p, g->cmp_box.as<int4>() + p0, 4 * np, g->stream));
+        }
         void *hs = nullptr;
         HIP_TRY(hipHostGetDevicePointer(&hs, g->h_scores.p, 0));
         HIP_TRY(prk::launch_copy_words32(g->scores.p, hs, kWords * np, g->stream));
@@ -452,6 +481,19 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         HIP_TRY(prk::launch_copy_words32(g->ov_mat.p, ho, P * P, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         std::memcpy(overlap_host, g->h_ov.p, sizeof(uint32_t) * (size_t)P * P);
+    }
+    if (cp) {
+        uint32_t *rec = g->cmp_rec.as<uint32_t>();
+        HIP_TRY(prk::launch_fill_i32(g->cmp_rec.as<int32_t>(), cmp_rec_bytes / sizeof(int32_t), 0, g->stream));
+        HIP_TRY(prk::launch_compose_counts(g->cmp_keys.as<unsigned long long>(), g->cmp_box.as<int4>(), cmp_index, P, W, H, scene_dev, scene_i32, tau, rec, g->stream));
+        HIP_TRY(prk::launch_compose_emit(g->cmp_keys.as<unsigned long long>(), W, H, window, scene_dev, scene_i32, tau, cp->labels_dev, cp->depth_dev,
+                                         rec + (size_t)kWords * P, g->stream));
+        void *hc = nullptr;
+        HIP_TRY(hipHostGetDevicePointer(&hc, g->h_cmp.p, 0));
+        HIP_TRY(prk::launch_copy_words32(rec, hc, (uint32_t)(cmp_rec_bytes / sizeof(uint32_t)), g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        std::memcpy(cp->visible, g->h_cmp.p, sizeof(pr_pose_visible) * P);
+        std::memcpy(cp->frame, g->h_cmp.as<unsigned char>() + sizeof(pr_pose_visible) * P, sizeof(pr_frame_explained));
     }
     drain_spans();
     return PR_OK;
@@ -468,9 +510,18 @@ int overlap_args_ok(const char *fn, uint32_t P, const uint32_t *overlap_host)
 }
 int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
                pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
-               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses")
+               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses", const ComposeOut *cp = nullptr)
 {
-    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, overlap_host, ct, fn);
+    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, overlap_host, ct, fn, cp);
+}
+// pr_compose_detections' own conditions, checked before anything runs
+int compose_args_ok(const char *fn, uint32_t P)
+{
+    if (P > PR_COMPOSE_MAX_POSES) {
+        set_error("%s: %u hypotheses, but a label is a uint16: at most PR_COMPOSE_MAX_POSES = %u", fn, P, (uint32_t)PR_COMPOSE_MAX_POSES);
+        return PR_ERR_INVALID;
+    }
+    return PR_OK;
 }
 
 // ---- mixed batches: the entry points' bodies (grouped batch in, outputs scattered back to the caller's order) -----------------------
@@ -547,13 +598,14 @@ int pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *
 
 int score_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
                 const pr_mat4 *proj, pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
-                const ContourOut *ct = nullptr, const char *fn = "pr_score_poses_multi")
+                const ContourOut *ct = nullptr, const char *fn = "pr_score_poses_multi", const ComposeOut *cp = nullptr)
 {
     // the single-mesh call's checks first (tau, jump, frame, ROI, pointers), with no hypotheses
     PR_TRY(score_core(MeshSource{ nullptr, 0, nullptr }, poses_host, 0, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, nullptr, ct, fn));
     if (P == 0) return PR_OK;
     if (!poses_host || !scene_dev || !scores_host) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
     if (ct && (!ct->edge_dist || !ct->out)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
+    if (cp && (!cp->visible || !cp->frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }
     MeshPlan pl;
     PR_TRY(plan_meshes(fn, meshes, n_meshes, mesh_index, P, pl));
     const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
@@ -561,8 +613,9 @@ int score_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *me
     std::vector<uint32_t> ov(overlap_host ? (size_t)P * P : 0);
     std::vector<pr_pose_contour> cc(ct ? P : 0);
     const ContourOut grouped{ ct ? ct->jump : 0, ct ? ct->edge_dist : nullptr, cc.data() };
+    const ComposeOut composed{ pl.order.data(), cp ? cp->labels_dev : nullptr, cp ? cp->depth_dev : nullptr, cp ? cp->visible : nullptr, cp ? cp->frame : nullptr };
     PR_TRY(score_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, roi, scene_dev, scene_i32, tau, sc.data(), overlap_host ? ov.data() : nullptr,
-                      ct ? &grouped : nullptr, fn));
+                      ct ? &grouped : nullptr, fn, cp ? &composed : nullptr));
     for (uint32_t j = 0; j < P; ++j) scores_host[pl.order[j]] = sc[j];
     if (ct) for (uint32_t j = 0; j < P; ++j) ct->out[pl.order[j]] = cc[j];
     if (overlap_host)                                            // rows and columns back into the caller's order
@@ -1390,6 +1443,33 @@ int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
     const ContourOut ct{ jump_mm, edge_dist_dev, contours_host };
     return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
                        overlap_host, &ct, "pr_score_contours_multi");
+}
+
+int pr_compose_detections(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                          const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out,
+                          int32_t *depth_dev_out, pr_pose_score *scores_host, pr_pose_visible *visible_host, pr_frame_explained *frame_host)
+{
+    PR_TRY(compose_args_ok("pr_compose_detections", n_poses));                                  // before any device use
+    PR_ENTER();
+    if (n_poses && labels_dev_out) note_write(labels_dev_out, sizeof(uint16_t) * (size_t)width * height);
+    if (n_poses && depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * (size_t)width * height);
+    const ComposeOut cp{ nullptr, labels_dev_out, depth_dev_out, visible_host, frame_host };
+    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host, nullptr, nullptr,
+                      "pr_compose_detections", &cp);
+}
+
+int pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                                uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                                int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out, int32_t *depth_dev_out, pr_pose_score *scores_host,
+                                pr_pose_visible *visible_host, pr_frame_explained *frame_host)
+{
+    PR_TRY(compose_args_ok("pr_compose_detections_multi", n_poses));
+    PR_ENTER();
+    if (n_poses && labels_dev_out) note_write(labels_dev_out, sizeof(uint16_t) * (size_t)width * height);
+    if (n_poses && depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * (size_t)width * height);
+    const ComposeOut cp{ nullptr, labels_dev_out, depth_dev_out, visible_host, frame_host };
+    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
+                       nullptr, nullptr, "pr_compose_detections_multi", &cp);
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

@@ -281,6 +281,8 @@ struct Ctx {
     DevBuf contours;                 // pr_score_contours: the contour records of a chunk
     DevBuf edge_bits, edge_rows;     // pr_scene_edge_distance_dev: the scene's edge bit plane and its row distances (scratch of one call)
     PinBuf h_contours;
+    DevBuf cmp_keys, cmp_box, cmp_rec;   // pr_compose_detections: the key frame (8 bytes per frame pixel), the pixel boxes of ALL hypotheses of a call followed by their caller's indices, the records
+    PinBuf h_cmp;                    // the records on their way to the caller, then the index table on its way to the device
     DevBuf lvl_rows, lvl_counts, lvl_carry;   // pr_refine_pyramid: per-row sample counts and offsets of every level of a chunk, the level clouds' sizes, the per-level carry records
     PinBuf h_lvl_carry;
     DevBuf multi;                    // mixed batches (pr_*_multi): mesh table, box index / image of each hypothesis, raster groups

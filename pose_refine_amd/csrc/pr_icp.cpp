@@ -54,8 +54,7 @@ bool pose_iteration_host(const float *Ab, uint32_t n, pr_result &r, const pr_cri
 }
 
 // ---- the batched ICP driver -----------------------------------------------------------------------
-// clouds: cloud i = cloud_base[start_h[i] .. start_h[i]+count_h[i]).  start/count must already be in
-// g->start / g->counts on the device when dev_meta_ready, otherwise they are uploaded here.
+// clouds: cloud i = cloud_base[start_h[i] .. start_h[i]+count_h[i]); start and count reach the device with the per-hypothesis records staged here.
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
               pr_criteria crit, pr_result *results_host, pr_result *results_dev)
 {
@@ -125,65 +124,43 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
         const uint64_t tick = g->sample_clock++;
         const bool sample_call = (opt.profile == 2) && (tick % (uint64_t)std::max(1, opt.sample_period) == 0);
         // Pose groups: the batch is split over up to four streams so that one group's serial solve tail (and the ragged end
-        // of its pass) overlaps another group's pass.  Timed launches (profile 1, the sampled call of profile 2) run as a
-        // single group so that the measured kernel has the chip to itself.
+        // of its pass) overlaps another group's pass -- while the (latency-bound, one wavefront per pose) finalize+solve of one group
+        // runs, the correspondence pass of the other group keeps the chip busy.  Timed launches (profile 1, the sampled call of
+        // profile 2) run as a single group so that the measured kernel has the chip to itself.
         const bool timed_call = (opt.profile == 1 || opt.profile == 3) || sample_call;   // (profile 3 only keeps SUBMITTED batches asynchronous: whatever runs here is a synchronous timed call)
-        const uint32_t n_groups = timed_call ? 1u : std::max(1u, std::min({ pose_groups_for(sc.kind), 4u, P / 32u }));
+        const uint32_t n_groups = pose_group_count(sc.kind, P, timed_call);
+        const Lanes lanes{ g->stream, g->side, g->ev_fork, g->ev_join };
         // the fixed sequence: state upload, (max_iteration+1) x [correspondence pass, finalize+solve], result pack
-        auto enqueue_all = [&](std::vector<hipEvent_t> *, bool host_checks) -> int {
+        auto enqueue_all = [&](bool host_checks) -> int {
             // start state and per-hypothesis records: PULLED from the pinned arrays by a kernel, results pushed into the pinned array by one -- no copy
             // command on a per-call path (round 6: the runtime's copy-engine path is where one-off multi-millisecond stalls came from, see below)
-            void *init_dev = nullptr, *meta_host_dev = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&init_dev, init, 0));
-            HIP_TRY(hipHostGetDevicePointer(&meta_host_dev, h_meta, 0));
-            HIP_TRY(prk::launch_stage_words(init_dev, g->dstate.p, sizeof(prk::DevIcpState) * P, g->stream));
-            HIP_TRY(prk::launch_stage_words(meta_host_dev, g->meta.p, sizeof(prk::PoseMeta) * P, g->stream));
+            HIP_TRY(prk::launch_stage_words(g->h_dstate.dev, g->dstate.p, sizeof(prk::DevIcpState) * P, g->stream));
+            HIP_TRY(prk::launch_stage_words(g->h_meta.dev, g->meta.p, sizeof(prk::PoseMeta) * P, g->stream));
             if (fused) HIP_TRY(prk::launch_fill_i32(g->arrive.as<int32_t>(), P, 0, g->stream));
-            // Two pose groups on two streams: while the (latency-bound, one wavefront per pose) finalize+solve
-            // of one group runs, the correspondence pass of the other group keeps the chip busy.
-            auto group_begin = [&](uint32_t grp) { return (uint32_t)(((uint64_t)P * grp) / n_groups); };
-            if (n_groups > 1) {
-                for (uint32_t k = 1; k < n_groups; ++k) PR_TRY(ensure_stream(g->side[k - 1], &g->ev_join[k - 1]));
-                HIP_TRY(hipEventRecord(g->ev_fork, g->stream));
-                for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamWaitEvent(g->side[k - 1], g->ev_fork, 0));
-            }
-            for (uint32_t it = 0; it <= (uint32_t)crit.max_iteration; ++it) {
-                for (uint32_t grp = 0; grp < n_groups; ++grp) {
-                    const uint32_t p0 = group_begin(grp), np = group_begin(grp + 1) - p0;
-                    hipStream_t st = grp ? g->side[grp - 1] : g->stream;
-                    prk::IcpBatch bb = b;
-                    bb.meta += p0; bb.partial += (size_t)p0 * nblk * prk::kAccStride; if (bb.nn_qcount) bb.nn_qcount += prk::kQCountStride * (size_t)p0;
-                    bb.iter = it;
-                    if (fused) { bb.fused = 1; bb.crit = crit; bb.st = g->dstate.as<prk::DevIcpState>() + p0; bb.arrive = g->arrive.as<uint32_t>() + p0; }
-                    bb.score_only = (it == (uint32_t)crit.max_iteration) ? 1u : 0u;
-                    if (grp == 0 && timed_call) {           // a timed call times every launch of its loop
-                        SpanGuard sp(kSpanIcp); HIP_TRY(launch_pass(bb, sc, np, st));
-                        uint64_t pts = 0; for (uint32_t i = p0; i < p0 + np; ++i) pts += count_h[i];
-                        // algorithmic bytes per point: 12 read + 24 gathered, + 12 written back once a transform is
-                        // pending; the score-only last pass needs the scene point but not its normal (12 + 12 + 12)
-                        const bool first = (it == 0), last = (it == (uint32_t)crit.max_iteration);
-                        g->icp_points += pts; g->icp_bytes += pts * ((first || last) ? 36u : 48u);
-                    } else HIP_TRY(launch_pass(bb, sc, np, st));
-                    if (!fused) HIP_TRY(prk::launch_icp_finalize_solve(bb.partial, g->meta.as<prk::PoseMeta>() + p0, nblk, steps,
-                                                                       g->dstate.as<prk::DevIcpState>() + p0, crit, it, np, st));
-                }
-                if (host_checks && may_exit_early && (it & 3) == 3 && it < (uint32_t)crit.max_iteration) {
-                    for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamSynchronize(g->side[k - 1]));
-                    HIP_TRY(hipMemcpyAsync(h_meta, g->meta.p, sizeof(prk::PoseMeta) * P, hipMemcpyDeviceToHost, g->stream));
-                    HIP_TRY(hipStreamSynchronize(g->stream));
-                    bool any = false;
-                    for (uint32_t i = 0; i < P; ++i) any |= (h_meta[i].state != prk::kSkip);
-                    if (!any) break;
-                }
-            }
-            for (uint32_t k = 1; k < n_groups; ++k) { HIP_TRY(hipEventRecord(g->ev_join[k - 1], g->side[k - 1])); HIP_TRY(hipStreamWaitEvent(g->stream, g->ev_join[k - 1], 0)); }
+            auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t st) -> int {
+                if (!timed_call) { HIP_TRY(launch_pass(bb, sc, np, st)); return PR_OK; }
+                SpanGuard sp(kSpanIcp); HIP_TRY(launch_pass(bb, sc, np, st));       // a timed call times every launch of its loop
+                uint64_t pts = 0; for (uint32_t i = p0; i < p0 + np; ++i) pts += count_h[i];
+                // algorithmic bytes per point: 12 read + 24 gathered, + 12 written back once a transform is
+                // pending; the score-only last pass needs the scene point but not its normal (12 + 12 + 12)
+                const bool first = (bb.iter == 0), last = (bb.iter == (uint32_t)crit.max_iteration);
+                g->icp_points += pts; g->icp_bytes += pts * ((first || last) ? 36u : 48u);
+                return PR_OK;
+            };
+            // every fourth pass, when the criteria can end a hypothesis early and nothing is being captured: has every hypothesis finished?
+            auto after = [&](uint32_t it, bool &stop) -> int {
+                if (!(host_checks && may_exit_early && (it & 3) == 3 && it < (uint32_t)crit.max_iteration)) return PR_OK;
+                for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamSynchronize(g->side[k - 1]));
+                HIP_TRY(hipMemcpyAsync(h_meta, g->meta.p, sizeof(prk::PoseMeta) * P, hipMemcpyDeviceToHost, g->stream));
+                HIP_TRY(hipStreamSynchronize(g->stream));
+                stop = true;
+                for (uint32_t i = 0; i < P; ++i) if (h_meta[i].state != prk::kSkip) stop = false;
+                return PR_OK;
+            };
+            PR_TRY(device_solve_loop(lanes, n_groups, b, P, crit, fused, g->meta.as<prk::PoseMeta>(), g->dstate.as<prk::DevIcpState>(), g->arrive.as<uint32_t>(), pass, after));
             HIP_TRY(prk::launch_pack_results(g->dstate.as<prk::DevIcpState>(), dres, P, g->stream));
             // results go to the pinned staging buffer (a pageable destination is not capturable)
-            if (results_host) {
-                void *res_dev = nullptr;
-                HIP_TRY(hipHostGetDevicePointer(&res_dev, res, 0));
-                HIP_TRY(prk::launch_stage_words64(dres, res_dev, sizeof(pr_result) * P, g->stream));
-            }
+            if (results_host) HIP_TRY(prk::launch_stage_words64(dres, g->h_results.dev, sizeof(pr_result) * P, g->stream));
             return PR_OK;
         };
 
@@ -204,7 +181,7 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
                 CachedGraph c; c.key = key;
                 HIP_TRY(hipStreamSynchronize(g->stream));
                 HIP_TRY(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
-                int rc = enqueue_all(nullptr, /*host_checks=*/false);
+                int rc = enqueue_all(/*host_checks=*/false);
                 hipError_t ce = hipStreamEndCapture(g->stream, &c.graph);
                 if (rc != PR_OK || ce != hipSuccess) { destroy_graph(c); if (rc == PR_OK) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce)); rc = PR_ERR_HIP; } return rc; }
                 HIP_TRY(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
@@ -219,7 +196,7 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
             return PR_OK;
         }
 
-        PR_TRY(enqueue_all(nullptr, /*host_checks=*/true));
+        PR_TRY(enqueue_all(/*host_checks=*/true));
         HIP_TRY(hipStreamSynchronize(g->stream));
         if (results_host) std::memcpy(results_host, res, sizeof(pr_result) * P);
         drain_spans();
@@ -236,30 +213,22 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     const uint64_t host_tick = g->sample_clock++;
     const bool host_sample_call = (opt.profile == 2) && (host_tick % (uint64_t)std::max(1, opt.sample_period) == 0);
     const uint32_t host_sample_it = (uint32_t)(((host_tick / (uint64_t)std::max(1, opt.sample_period)) * 5 + 1) % (uint64_t)(crit.max_iteration + 1));
-    const uint32_t n_groups = (opt.profile == 1 || opt.profile == 3 || host_sample_call) ? 1u : std::max(1u, std::min({ pose_groups_for(sc.kind), 4u, P / 32u }));
-    auto group_begin = [&](uint32_t grp) { return (uint32_t)(((uint64_t)P * grp) / n_groups); };
+    const uint32_t n_groups = pose_group_count(sc.kind, P, opt.profile == 1 || opt.profile == 3 || host_sample_call);
+    const Lanes lanes{ g->stream, g->side, g->ev_fork, g->ev_join };
+    auto group_begin = [&](uint32_t grp) { return prr::group_begin(P, n_groups, grp); };
     if (opt.fused_solve) { PR_TRY(g->arrive.ensure(sizeof(uint32_t) * (P + 4))); HIP_TRY(prk::launch_fill_i32(g->arrive.as<int32_t>(), (size_t)P + 4, 0, g->stream)); }   // (+ one counter per pose group)
-    if (n_groups > 1) {
-        for (uint32_t k = 1; k < n_groups; ++k) PR_TRY(ensure_stream(g->side[k - 1], &g->ev_join[k - 1]));
-        HIP_TRY(hipEventRecord(g->ev_fork, g->stream));               // the groups start behind the render / cloud work of this call
-        for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamWaitEvent(g->side[k - 1], g->ev_fork, 0));
-    }
-    auto group_stream = [&](uint32_t grp) { return grp ? g->side[grp - 1] : g->stream; };
+    PR_TRY(lanes_fork(lanes, n_groups));                              // the groups start behind the render / cloud work of this call
+    auto group_stream = [&](uint32_t grp) { return lane(lanes, grp); };
     // With option fused_solve the pass also adds up the workgroup sums of a hypothesis (the workgroup that arrives last does, as in the
     // device-solve loop) and stores the 29 totals straight into the pinned host array: no finalize launch, no copy command -- two
     // API calls and one copy-engine round trip less per group and iteration on a path that is bound by exactly those.
     const bool host_fused = opt.fused_solve != 0;
-    float *sums_dev = nullptr;
-    if (host_fused) {
-        PR_TRY(g->arrive.ensure(sizeof(uint32_t) * (P + 4)));
-        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&sums_dev), h_sums, 0));
-    }
+    float *sums_dev = host_fused ? g->h_sums.dev_as<float>() : nullptr;
     // Projective scenes also read the per-hypothesis state (64 bytes: cloud span, pending update) from the pinned host array instead
     // of receiving it through a copy command: one uniform load per workgroup over the host link, 1.62 -> 1.54 ms per 256-hypothesis
     // batch.  The four kernels of a kd-tree pass have ten times the workgroups; there the copy is cheaper (8.3 against 8.8 ms).
-    const prk::PoseMeta *meta_dev = nullptr, *h_meta_mapped = nullptr;          // h_meta as the device sees it
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(const_cast<prk::PoseMeta **>(&h_meta_mapped)), h_meta, 0));
-    if (host_fused && sc.kind != PR_SCENE_NN) HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(const_cast<prk::PoseMeta **>(&meta_dev)), h_meta, 0));
+    const prk::PoseMeta *h_meta_mapped = g->h_meta.dev_as<prk::PoseMeta>();     // h_meta as the device sees it
+    const prk::PoseMeta *meta_dev = (host_fused && sc.kind != PR_SCENE_NN) ? h_meta_mapped : nullptr;
     // Round 6: the host waits for a pose group's FLAG in pinned memory (stored by the workgroup that delivers the group's last
     // hypothesis) instead of for the stream -- it solves while the launch winds down.  Option blocking_wait (several ranks sharing few CPUs) and
     // host_poll = 0 keep the stream wait.
@@ -270,10 +239,10 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     auto enqueue_group = [&](uint32_t grp, uint32_t it) -> int {
         const uint32_t p0 = group_begin(grp), np = group_begin(grp + 1) - p0;
         hipStream_t st = group_stream(grp);
-        prk::IcpBatch bb = b;
-        if (meta_dev) bb.meta = meta_dev;                            // the pass reads the 64-byte state of its hypothesis from the pinned host array
+        prk::IcpBatch whole = b;
+        if (meta_dev) whole.meta = meta_dev;                         // the pass reads the 64-byte state of its hypothesis from the pinned host array
         else HIP_TRY(prk::launch_stage_words(h_meta_mapped + p0, g->meta.as<prk::PoseMeta>() + p0, sizeof(prk::PoseMeta) * np, st));   // (pulled by a kernel: no copy command per iteration)
-        bb.meta += p0; bb.partial += (size_t)p0 * nblk * prk::kAccStride; if (bb.nn_qcount) bb.nn_qcount += prk::kQCountStride * (size_t)p0;
+        prk::IcpBatch bb = group_slice(whole, p0);
         bb.iter = it;
         if (host_fused) { bb.fused = 2; bb.arrive = g->arrive.as<uint32_t>() + p0; bb.sums_out = sums_dev + (size_t)p0 * prk::kAccStride; }
         if (poll_flag) {                                             // the group's count and flag (see pass_deliver): how many hypotheses will deliver
@@ -361,9 +330,7 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
         // the records are PULLED from the pinned array by a kernel, not pushed by a copy command: round 6 traced the one-off stall of the host-solve
         // pipeline (one step of 6.5-8.7 ms among forty of 1.0 ms, PR_TRACE) to this 18 KB hipMemcpyAsync -- some batches into a helper thread's life
         // the runtime spends milliseconds inside it, on both helpers at once (its copy-engine path; the kernels around it take microseconds)
-        void *res_dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&res_dev, res, 0));
-        HIP_TRY(prk::launch_stage_words64(res_dev, results_dev, sizeof(pr_result) * P, g->stream));
+        HIP_TRY(prk::launch_stage_words64(g->h_results.dev, results_dev, sizeof(pr_result) * P, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
     }
     drain_spans();

@@ -4,14 +4,6 @@
 
 namespace prr {
 
-// the raster packs pixel coordinates into 13 bits each and enumerates a triangle's candidate pixels with 24-bit arithmetic
-bool frame_size_ok(size_t W, size_t H)
-{
-    // (contour.hip: kMaxFrameSide restates the 8192 -- its 32-bit per-workgroup sum is sized by it)
-    if (W > 8192 || H > 8192 || W * H > ((size_t)1 << 24)) { set_error("frames larger than 8192 on a side or 2^24 pixels are not supported (got %zux%zu)", W, H); return false; }
-    return true;
-}
-
 // the hypotheses' poses into g->poses: through the context's pinned staging array, pulled by a kernel (as the asynchronous path stages its inputs) --
 // a copy command from the caller's pageable array goes through the runtime's bounce buffers and its copy-engine path (see icp_drive's
 // result block: that path is where the host-solve pipeline's one-off multi-millisecond stalls came from)
@@ -20,9 +12,7 @@ int stage_poses(const pr_mat4 *poses_host, size_t n)
     PR_TRY(g->poses.ensure(sizeof(pr_mat4) * n));
     PR_TRY(g->h_poses.ensure(sizeof(pr_mat4) * n));
     std::memcpy(g->h_poses.p, poses_host, sizeof(pr_mat4) * n);
-    void *hp = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&hp, g->h_poses.p, 0));
-    HIP_TRY(prk::launch_stage_words(hp, g->poses.p, sizeof(pr_mat4) * n, g->stream));
+    HIP_TRY(prk::launch_stage_words(g->h_poses.dev, g->poses.p, sizeof(pr_mat4) * n, g->stream));
     return PR_OK;
 }
 
@@ -33,15 +23,6 @@ uint32_t depth_chunk(size_t img, uint32_t P)
     return (uint32_t)std::max<size_t>(1, std::min<size_t>(P, ((size_t)4 << 30) / (img * sizeof(int32_t))));
 }
 
-bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
-{
-    if (roi.width <= 0 || roi.height <= 0) return true;            // no ROI
-    if (roi.x < 0 || roi.y < 0 || (size_t)roi.x + (size_t)roi.width > W || (size_t)roi.y + (size_t)roi.height > H) {
-        set_error("roi out of image");                               // renderer.cu:202-203 asserts
-        return false;
-    }
-    return true;
-}
 // {width, height} of one rendered image: the ROI when one is given, the full frame otherwise
 std::pair<size_t, size_t> image_extent(pr_roi roi, size_t W, size_t H)
 {
@@ -152,9 +133,7 @@ int model_boxes(const MeshSource &src, uint32_t chunk)
     PR_TRY(g->multi.ensure(l.bytes));
     PR_TRY(g->h_multi.ensure(l.bytes));
     std::memcpy(g->h_multi.p, pl.mesh.data(), sizeof(pr_mesh_ref) * G);
-    void *hm = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&hm, g->h_multi.p, 0));
-    HIP_TRY(prk::launch_stage_words(hm, g->multi.p, sizeof(pr_mesh_ref) * G, g->stream));
+    HIP_TRY(prk::launch_stage_words(g->h_multi.dev, g->multi.p, sizeof(pr_mesh_ref) * G, g->stream));
     HIP_TRY(prk::launch_model_aabb_multi(g->multi.as<pr_mesh_ref>(), pl.mesh.data(), G, g->aabb_keys.as<uint32_t>(), g->aabb.as<float>(), g->stream));
     return PR_OK;
 }
@@ -190,14 +169,12 @@ int render_chunk(const MeshSource &src, const pr_mat4 *poses_host, uint32_t p0, 
     }
     const MeshPlan &pl = *src.plan;
     const MultiLayout l = multi_layout(pl.mesh.size(), chunk);
-    unsigned char *h = g->h_multi.as<unsigned char>(), *d = g->multi.as<unsigned char>();
-    void *hm = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&hm, g->h_multi.p, 0));
+    unsigned char *h = g->h_multi.as<unsigned char>(), *hm = g->h_multi.dev_as<unsigned char>(), *d = g->multi.as<unsigned char>();
     std::memcpy(h + l.box, pl.box.data() + p0, sizeof(uint32_t) * np);
-    HIP_TRY(prk::launch_stage_words(static_cast<unsigned char *>(hm) + l.box, d + l.box, sizeof(uint32_t) * np, g->stream));
+    HIP_TRY(prk::launch_stage_words(hm + l.box, d + l.box, sizeof(uint32_t) * np, g->stream));
     prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
     const uint32_t n_groups = chunk_groups(pl, p0, np, groups);
-    HIP_TRY(prk::launch_render_boxes_multi(g->aabb.as<float>(), reinterpret_cast<const uint32_t *>(d + l.box), groups, static_cast<unsigned char *>(hm) + l.groups,
+    HIP_TRY(prk::launch_render_boxes_multi(g->aabb.as<float>(), reinterpret_cast<const uint32_t *>(d + l.box), groups, hm + l.groups,
                                            n_groups, reinterpret_cast<prk::RasterGroup *>(d + l.groups), g->poses.as<pr_mat4>(), np, g->bbox.as<int4>(),
                                            g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(), g->counts.as<uint32_t>(),
                                            W, H, *proj, roi, g->stream, box_off));
@@ -241,9 +218,7 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
     {
         SpanGuard sp(kSpanCloud);
         HIP_TRY(prk::launch_pyramid_counts(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, lv, row_count, row_off, g->lvl_counts.as<uint32_t>(), g->stream));
-        void *hc = nullptr;                                       // all levels' sizes through a kernel's stores into the pinned array (see refine_core)
-        HIP_TRY(hipHostGetDevicePointer(&hc, h_counts, 0));
-        HIP_TRY(prk::launch_copy_words32(g->lvl_counts.p, hc, L * np, g->stream));
+        HIP_TRY(prk::launch_copy_words32(g->lvl_counts.p, g->h_counts.dev, L * np, g->stream));   // all levels' sizes through a kernel's stores into the pinned array (see refine_core)
     }
     HIP_TRY(hipStreamSynchronize(g->stream));
     trace_mark("pyramid_chunk: level sizes on host");
@@ -257,8 +232,6 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
         most = std::max(most, total);
     }
     PR_TRY(g->cloud.ensure(sizeof(pr_vec3) * most));
-    void *carry_mapped = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&carry_mapped, g->h_lvl_carry.p, 0));
     prk::PyramidCarry *h_carry = g->h_lvl_carry.as<prk::PyramidCarry>();
     std::vector<pr_result> acc(np), rec(np);
     std::vector<uint32_t> start(np), count(np);
@@ -274,7 +247,7 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
         }
         if (total > 0) {
             SpanGuard sp(kSpanCloud);
-            HIP_TRY(prk::launch_stage_words(carry_mapped, g->lvl_carry.p, sizeof(prk::PyramidCarry) * np, g->stream));
+            HIP_TRY(prk::launch_stage_words(g->h_lvl_carry.dev, g->lvl_carry.p, sizeof(prk::PyramidCarry) * np, g->stream));
             HIP_TRY(prk::launch_pyramid_emit(g->depth.as<int32_t>(), np, W, H, g->bbox.as<int4>(), box_off, K[0], K[4], K[2], K[5], py.levels[l].stride,
                                              row_count + (size_t)l * np * H, row_off + (size_t)l * np * H, g->lvl_carry.as<prk::PyramidCarry>(), l > 0,
                                              g->cloud.as<pr_vec3>(), g->stream));
@@ -292,18 +265,19 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
     return PR_OK;
 }
 
-int refine_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host, const PyramidPlan *pyramid = nullptr)
+// One synchronous batch: chunk by chunk the hypotheses rendered into their pixel boxes, the clouds emitted (with `pyramid`: every level's, by
+// pyramid_chunk) and icp_drive run on them.  The records go to results_host and to job.results_dev, the cloud sizes to sizes_host; each may be null.
+int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_result *results_host, uint32_t *sizes_host, const PyramidPlan *pyramid = nullptr)
 {
-    if (!K || W == 0 || H == 0) { set_error("pr_refine_batch: bad arguments"); return PR_ERR_INVALID; }
-    if (!frame_size_ok(W, H) || !roi_ok(roi, W, H)) return PR_ERR_INVALID;
     if (P == 0) return PR_OK;
+    const MeshSource src{ job.tris, job.n_tris, job.plan };
+    const uint32_t W = job.W, H = job.H;
+    const float *K = job.K;
     SceneSel sc;
     std::memset(static_cast<void *>(&sc), 0, sizeof sc);           // also zeroes padding: sc is part of the graph-cache key
     const Camera cam{ W, H, K[0], K[4], K[2], K[5] };
     trace_mark("refine_impl: enter");
-    PR_TRY(make_scene(scene_kind, scene, /*want_packed=*/true, sc, nullptr, nullptr, &cam));
+    PR_TRY(make_scene(job.scene_kind, job.scene(), /*want_packed=*/true, sc, nullptr, nullptr, &cam));
     trace_mark("refine_impl: scene ready");
     const size_t img = (size_t)W * H;
     uint32_t chunk = depth_chunk(img, P);
@@ -323,14 +297,11 @@ int refine_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, ui
         uint32_t *box_off = (prk::kBoxPack && (src.plan || opt.raster_mode != 1)) ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
         {
             SpanGuard sp(kSpanRender);
-            PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, proj, roi, box_off, !src.plan && opt.raster_mode == 1));
+            PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, &job.proj, job.roi, box_off, !src.plan && opt.raster_mode == 1));
         }
         if (pyramid) { PR_TRY(pyramid_chunk(*pyramid, p0, np, W, H, K, box_off, sc, results_host + p0)); continue; }
-        {   // the cloud sizes come back through a kernel's stores into the pinned array, not through a copy command (see icp_drive's result block)
-            void *hc = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&hc, h_counts, 0));
-            HIP_TRY(prk::launch_copy_words32(g->counts.p, hc, np, g->stream));
-        }
+        // the cloud sizes come back through a kernel's stores into the pinned array, not through a copy command (see icp_drive's result block)
+        HIP_TRY(prk::launch_copy_words32(g->counts.p, g->h_counts.dev, np, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         trace_mark("refine_impl: render done, counts on host");
         uint32_t max_n = 0;
@@ -356,20 +327,13 @@ int refine_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, ui
         }
         if (sizes_host) std::memcpy(sizes_host + p0, count.data(), sizeof(uint32_t) * np);
         trace_mark("refine_impl: clouds emitted, icp_drive next");
-        PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, crit,
-                         results_host ? results_host + p0 : nullptr, results_dev ? results_dev + p0 : nullptr));
+        PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, job.crit,
+                         results_host ? results_host + p0 : nullptr, job.results_dev ? job.results_dev + p0 : nullptr));
     }
     return PR_OK;
 }
-int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host)
-{
-    return refine_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, K, scene_kind, scene, crit, roi, results_host, results_dev, sizes_host);
-}
-
 // ---- render-and-compare scoring (pr_score_poses) ---------------------------------------------------------------------------
-// refine_impl's render (staged poses, model box, per-pose pixel boxes packed one behind the other) followed by one kernel that compares every
+// refine_core's render (staged poses, model box, per-pose pixel boxes packed one behind the other) followed by one kernel that compares every
 // rendered box pixel with the scene frame.  Everything runs on the context's own stream and workspaces, which no asynchronous slot owns, so a
 // batch pending on a slot is neither waited for nor disturbed.  The scene is read as it is on every call: nothing derived from it is kept.
 // overlap_host (pr_score_overlap; null: scores only): the P x P matrix of shared inlier pixels, in the order of poses_host.  Every chunk also leaves
@@ -423,11 +387,9 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         PR_TRY(g->cmp_rec.ensure(cmp_rec_bytes));
         PR_TRY(g->h_cmp.ensure(cmp_rec_bytes + cmp_idx_bytes));
         if (cp->order) {
-            void *hc = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&hc, g->h_cmp.p, 0));
             std::memcpy(g->h_cmp.as<unsigned char>() + cmp_rec_bytes, cp->order, sizeof(uint32_t) * P);
             cmp_index = reinterpret_cast<uint32_t *>(g->cmp_box.as<int4>() + P);
-            HIP_TRY(prk::launch_stage_words(static_cast<unsigned char *>(hc) + cmp_rec_bytes, cmp_index, sizeof(uint32_t) * P, g->stream));
+            HIP_TRY(prk::launch_stage_words(g->h_cmp.dev_as<unsigned char>() + cmp_rec_bytes, cmp_index, sizeof(uint32_t) * P, g->stream));
         }
     }
     for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
@@ -445,7 +407,7 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, proj, roi, box_off, /*bands=*/false));
         }
-        // records zeroed by a kernel and read back through the pinned array by a kernel: no memset or copy commands on this path (see refine_impl)
+        // records zeroed by a kernel and read back through the pinned array by a kernel: no memset or copy commands on this path (see refine_core)
         HIP_TRY(prk::launch_fill_i32(g->scores.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
         HIP_TRY(prk::launch_score_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
                                         g->scores.as<uint32_t>(), g->stream));
@@ -453,9 +415,7 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
             HIP_TRY(prk::launch_fill_i32(g->contours.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
             HIP_TRY(prk::launch_contour_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, scene_dev, scene_i32, ct->edge_dist, tau,
                                               ct->jump, g->contours.as<uint32_t>(), g->stream));
-            void *hc = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&hc, g->h_contours.p, 0));
-            HIP_TRY(prk::launch_copy_words32(g->contours.p, hc, kWords * np, g->stream));
+            HIP_TRY(prk::launch_copy_words32(g->contours.p, g->h_contours.dev, kWords * np, g->stream));
         }
         if (overlap_host) {
             HIP_TRY(prk::launch_support_bits(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
@@ -467,18 +427,14 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
                                               g->cmp_keys.as<unsigned long long>(), p0 == 0, g->stream));
             HIP_TRY(prk::launch_copy_words32(g->bbox.p, g->cmp_box.as<int4>() + p0, 4 * np, g->stream));
         }
-        void *hs = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&hs, g->h_scores.p, 0));
-        HIP_TRY(prk::launch_copy_words32(g->scores.p, hs, kWords * np, g->stream));
+        HIP_TRY(prk::launch_copy_words32(g->scores.p, g->h_scores.dev, kWords * np, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         std::memcpy(scores_host + p0, g->h_scores.p, sizeof(pr_pose_score) * np);
         if (ct) std::memcpy(ct->out + p0, g->h_contours.p, sizeof(pr_pose_contour) * np);
     }
     if (overlap_host) {
         HIP_TRY(prk::launch_pair_overlap(g->ov_bits.as<unsigned long long>(), g->ov_box.as<int4>(), P, W, H, g->ov_mat.as<uint32_t>(), g->stream));
-        void *ho = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&ho, g->h_ov.p, 0));
-        HIP_TRY(prk::launch_copy_words32(g->ov_mat.p, ho, P * P, g->stream));
+        HIP_TRY(prk::launch_copy_words32(g->ov_mat.p, g->h_ov.dev, P * P, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         std::memcpy(overlap_host, g->h_ov.p, sizeof(uint32_t) * (size_t)P * P);
     }
@@ -488,9 +444,7 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         HIP_TRY(prk::launch_compose_counts(g->cmp_keys.as<unsigned long long>(), g->cmp_box.as<int4>(), cmp_index, P, W, H, scene_dev, scene_i32, tau, rec, g->stream));
         HIP_TRY(prk::launch_compose_emit(g->cmp_keys.as<unsigned long long>(), W, H, window, scene_dev, scene_i32, tau, cp->labels_dev, cp->depth_dev,
                                          rec + (size_t)kWords * P, g->stream));
-        void *hc = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&hc, g->h_cmp.p, 0));
-        HIP_TRY(prk::launch_copy_words32(rec, hc, (uint32_t)(cmp_rec_bytes / sizeof(uint32_t)), g->stream));
+        HIP_TRY(prk::launch_copy_words32(rec, g->h_cmp.dev, (uint32_t)(cmp_rec_bytes / sizeof(uint32_t)), g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         std::memcpy(cp->visible, g->h_cmp.p, sizeof(pr_pose_visible) * P);
         std::memcpy(cp->frame, g->h_cmp.as<unsigned char>() + sizeof(pr_pose_visible) * P, sizeof(pr_frame_explained));
@@ -532,65 +486,25 @@ std::vector<pr_mat4> grouped_poses(const MeshPlan &pl, const pr_mat4 *poses_host
     return out;
 }
 
-int refine_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                 const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_host,
-                 uint32_t *sizes_host)
+// pr_refine_batch_multi and both pr_refine_pyramid entries behind their argument checks: refine_core on the batch in its plan's order (job.plan;
+// none: the caller's) into temporaries -- nothing reaches the caller's arrays unless the whole call succeeded -- and the records, cloud sizes and
+// (py) per-level blocks back to the caller's order.
+int refine_ordered(const RefineJob &job, const PyramidPlan *py, const pr_mat4 *poses_host, uint32_t P, pr_result *results_host, uint32_t *sizes_host)
 {
-    if (P == 0) return PR_OK;
-    if (!results_host || !poses_host || !proj || !K || !scene) { set_error("pr_refine_batch_multi: bad arguments"); return PR_ERR_INVALID; }
-    if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
-    if (W == 0 || H == 0 || !frame_size_ok(W, H) || !roi_ok(roi, W, H)) { if (W == 0 || H == 0) set_error("pr_refine_batch_multi: bad arguments"); return PR_ERR_INVALID; }
-    MeshPlan pl;
-    PR_TRY(plan_meshes("pr_refine_batch_multi", meshes, n_meshes, mesh_index, P, pl));
-    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
-    std::vector<pr_result> res(P);
-    std::vector<uint32_t> sizes(P);
-    PR_TRY(refine_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, K, scene_kind, scene, crit, roi, res.data(), nullptr, sizes.data()));
+    std::vector<pr_mat4> grouped;
+    if (job.plan) { grouped = grouped_poses(*job.plan, poses_host); poses_host = grouped.data(); }
+    const uint32_t L = py ? py->n_levels : 0;
+    std::vector<pr_result> res(P), lres(py && py->level_results ? (size_t)L * P : 0);
+    std::vector<uint32_t> sizes(P), lsizes(py && py->level_sizes ? (size_t)L * P : 0);
+    const PyramidPlan inner{ py ? py->levels : nullptr, L, P, lres.empty() ? nullptr : lres.data(), lsizes.empty() ? nullptr : lsizes.data() };
+    PR_TRY(refine_core(job, poses_host, P, res.data(), sizes.data(), py ? &inner : nullptr));
     for (uint32_t j = 0; j < P; ++j) {
-        results_host[pl.order[j]] = res[j];
-        if (sizes_host) sizes_host[pl.order[j]] = sizes[j];
-    }
-    return PR_OK;
-}
-
-// pr_refine_pyramid / pr_refine_pyramid_multi behind their level-table check: the arguments' own checks, then refine_core with the plan
-int pyramid_single(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
-                   const float K[9], int scene_kind, const void *scene, const PyramidPlan &py, pr_roi roi, pr_result *results_host)
-{
-    if (P == 0) return PR_OK;
-    if ((!tris_dev && n_tris > 0) || !poses_host || !proj || !K || !scene) { set_error("pr_refine_pyramid: bad arguments"); return PR_ERR_INVALID; }
-    if (W == 0 || H == 0 || !frame_size_ok(W, H) || !roi_ok(roi, W, H)) { if (W == 0 || H == 0) set_error("pr_refine_pyramid: bad arguments"); return PR_ERR_INVALID; }
-    std::vector<pr_result> res(P);                               // (nothing is written to the caller's arrays unless the whole call succeeds)
-    std::vector<pr_result> lres(py.level_results ? (size_t)py.n_levels * P : 0);
-    std::vector<uint32_t> lsizes(py.level_sizes ? (size_t)py.n_levels * P : 0);
-    const PyramidPlan inner{ py.levels, py.n_levels, P, py.level_results ? lres.data() : nullptr, py.level_sizes ? lsizes.data() : nullptr };
-    PR_TRY(refine_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, res.data(), nullptr,
-                       nullptr, &inner));
-    std::memcpy(results_host, res.data(), sizeof(pr_result) * P);
-    if (py.level_results) std::memcpy(py.level_results, lres.data(), sizeof(pr_result) * lres.size());
-    if (py.level_sizes) std::memcpy(py.level_sizes, lsizes.data(), sizeof(uint32_t) * lsizes.size());
-    return PR_OK;
-}
-int pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                  const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const PyramidPlan &py, pr_roi roi, pr_result *results_host)
-{
-    if (P == 0) return PR_OK;
-    if (!poses_host || !proj || !K || !scene) { set_error("pr_refine_pyramid_multi: bad arguments"); return PR_ERR_INVALID; }
-    if (W == 0 || H == 0 || !frame_size_ok(W, H) || !roi_ok(roi, W, H)) { if (W == 0 || H == 0) set_error("pr_refine_pyramid_multi: bad arguments"); return PR_ERR_INVALID; }
-    MeshPlan pl;
-    PR_TRY(plan_meshes("pr_refine_pyramid_multi", meshes, n_meshes, mesh_index, P, pl));
-    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
-    std::vector<pr_result> res(P);
-    std::vector<pr_result> lres(py.level_results ? (size_t)py.n_levels * P : 0);
-    std::vector<uint32_t> lsizes(py.level_sizes ? (size_t)py.n_levels * P : 0);
-    const PyramidPlan inner{ py.levels, py.n_levels, P, py.level_results ? lres.data() : nullptr, py.level_sizes ? lsizes.data() : nullptr };
-    PR_TRY(refine_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, res.data(), nullptr, nullptr,
-                       &inner));
-    for (uint32_t j = 0; j < P; ++j) {                          // back to the caller's order
-        results_host[pl.order[j]] = res[j];
-        for (uint32_t l = 0; l < py.n_levels; ++l) {
-            if (py.level_results) py.level_results[(size_t)l * P + pl.order[j]] = lres[(size_t)l * P + j];
-            if (py.level_sizes) py.level_sizes[(size_t)l * P + pl.order[j]] = lsizes[(size_t)l * P + j];
+        const uint32_t o = job.plan ? job.plan->order[j] : j;
+        results_host[o] = res[j];
+        if (sizes_host) sizes_host[o] = sizes[j];
+        for (uint32_t l = 0; l < L; ++l) {
+            if (py->level_results) py->level_results[(size_t)l * P + o] = lres[(size_t)l * P + j];
+            if (py->level_sizes) py->level_sizes[(size_t)l * P + o] = lsizes[(size_t)l * P + j];
         }
     }
     return PR_OK;
@@ -642,15 +556,13 @@ int render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *m
     const MultiLayout l = multi_layout(G, P);                      // the box-index slot holds the image of every hypothesis here
     PR_TRY(g->multi.ensure(l.bytes));
     PR_TRY(g->h_multi.ensure(l.bytes));
-    unsigned char *h = g->h_multi.as<unsigned char>(), *d = g->multi.as<unsigned char>();
-    void *hm = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&hm, g->h_multi.p, 0));
+    unsigned char *h = g->h_multi.as<unsigned char>(), *hm = g->h_multi.dev_as<unsigned char>(), *d = g->multi.as<unsigned char>();
     std::memcpy(h + l.box, pl.order.data(), sizeof(uint32_t) * P);
-    HIP_TRY(prk::launch_stage_words(static_cast<unsigned char *>(hm) + l.box, d + l.box, sizeof(uint32_t) * P, g->stream));
+    HIP_TRY(prk::launch_stage_words(hm + l.box, d + l.box, sizeof(uint32_t) * P, g->stream));
     HIP_TRY(prk::launch_fill_i32(depth_dev, P * rw * rh, INT32_MAX, g->stream));
     prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
     const uint32_t n_groups = chunk_groups(pl, 0, (uint32_t)P, groups);
-    HIP_TRY(prk::launch_raster_multi(groups, static_cast<unsigned char *>(hm) + l.groups, n_groups, reinterpret_cast<prk::RasterGroup *>(d + l.groups),
+    HIP_TRY(prk::launch_raster_multi(groups, hm + l.groups, n_groups, reinterpret_cast<prk::RasterGroup *>(d + l.groups),
                                      g->poses.as<pr_mat4>(), depth_dev, (uint32_t)W, (uint32_t)H, *proj, roi, (uint32_t)rw, (uint32_t)rh,
                                      nullptr, nullptr, reinterpret_cast<const uint32_t *>(d + l.box), g->stream));
     HIP_TRY(prk::launch_max2zero(depth_dev, P * rw * rh, g->stream));
@@ -722,7 +634,7 @@ void drain_slots_reading(const void *p, size_t bytes)
     auto hit = [&](const void *a, size_t ab) { const uintptr_t s = reinterpret_cast<uintptr_t>(a); return a && ab && s < hi && lo < s + ab; };
     for (Slot &sl : g->slots) {
         if (!sl.pending || sl.delivered) continue;
-        const Resubmit &r = (sl.worker_job && sl.worker) ? sl.worker->in : sl.again;     // (a helper thread's job is posted and read under g->mu by this thread only)
+        const RefineJob &r = (sl.worker_job && sl.worker) ? sl.worker->in : sl.again;     // (a helper thread's job is posted and read under g->mu by this thread only)
         bool reads = hit(r.tris, r.n_tris * sizeof(pr_triangle)) || hit(r.results_dev, (size_t)sl.P * sizeof(pr_result));
         if (r.scene_kind == PR_SCENE_NN)
             reads = reads || hit(r.sn.pcd, (size_t)r.sn.n_points * sizeof(pr_vec3)) || hit(r.sn.normal, (size_t)r.sn.n_points * sizeof(pr_vec3)) ||
@@ -799,25 +711,6 @@ int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
     return PR_OK;
 }
 
-// a batch's arguments as a re-run needs them (the scene by value: a plain projective scene as a crop at 0, 0)
-Resubmit make_resubmit(const pr_triangle *tris_dev, size_t n_tris, uint32_t W, uint32_t H, const pr_mat4 *proj, const float K[9], int scene_kind,
-                       const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_dev)
-{
-    Resubmit r;
-    r.tris = tris_dev; r.n_tris = n_tris; r.W = W; r.H = H; r.proj = *proj; std::memcpy(r.K, K, sizeof r.K);
-    r.scene_kind = scene_kind; r.crit = crit; r.roi = roi; r.results_dev = results_dev;
-    if (scene_kind == PR_SCENE_NN) r.sn = *static_cast<const pr_scene_nn *>(scene);
-    else if (scene_kind == PR_SCENE_PROJ_CROP) r.sp = *static_cast<const pr_scene_proj_crop *>(scene);
-    else { r.sp.view = *static_cast<const pr_scene_proj *>(scene); r.sp.tl_x = r.sp.tl_y = 0; }
-    return r;
-}
-// ... and its scene as refine_impl takes it
-const void *resubmit_scene(const Resubmit &r)
-{
-    if (r.scene_kind == PR_SCENE_NN) return &r.sn;
-    return r.scene_kind == PR_SCENE_PROJ_CROP ? static_cast<const void *>(&r.sp) : static_cast<const void *>(&r.sp.view);
-}
-
 // the synchronous entry points run on whichever slot holds no unfinished batch of the caller's (-1: none)
 int free_slot() { for (int i = 0; i < kSlots; ++i) if (!g->slots[i].pending) return i; return -1; }
 
@@ -843,7 +736,8 @@ int refine_wait(int slot)
     }
     sl.pending = false;
     const unsigned char *h_out = sl.h_out.as<unsigned char>();
-    if (*reinterpret_cast<const volatile uint32_t *>(h_out + sl.flag_off) != 0u) {
+    const SlotOut out(sl.P);
+    if (*reinterpret_cast<const volatile uint32_t *>(h_out + out.flag) != 0u) {
         // the triangle buffer no longer has the box this batch was sized with, or the content its ordered copy was made from: forget both
         // and run the batch again, synchronously (that path derives every box on the device and reads the caller's buffer); outputs are overwritten in full
         g->drop_mesh();
@@ -853,9 +747,7 @@ int refine_wait(int slot)
         for (Slot &o : g->slots) o.packed.valid = false;
         g->packed.valid = false;
         for (NNDerived &d : g->nn_sets) { d.valid = false; d.grid_valid = false; }
-        const Resubmit &r = sl.again;
-        return refine_impl(r.tris, r.n_tris, sl.h_in.as<pr_mat4>(), sl.P, r.W, r.H, &r.proj, r.K, r.scene_kind, resubmit_scene(r), r.crit, r.roi,
-                           sl.user_results_host, r.results_dev, sl.user_sizes);
+        return refine_core(sl.again, sl.h_in.as<pr_mat4>(), sl.P, sl.user_results_host, sl.user_sizes);
     }
     const uint32_t *h_counts = sl.h_out.as<uint32_t>();
     uint32_t largest = 1;
@@ -883,13 +775,10 @@ int refine_wait(int slot)
         sl.t_spans.clear(); sl.t_used = 0; sl.timed = false;
     }
     if (sl.user_sizes) std::memcpy(sl.user_sizes, h_counts, sizeof(uint32_t) * sl.P);
-    if (sl.user_results_host) std::memcpy(sl.user_results_host, h_out + (((size_t)sl.P * 4 + 63) & ~(size_t)63), sizeof(pr_result) * sl.P);
+    if (sl.user_results_host) std::memcpy(sl.user_results_host, h_out + out.res, sizeof(pr_result) * sl.P);
     return PR_OK;
 }
 
-int refine_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host);
 // the helper thread of a slot: a private context on the slot's device, then one synchronous batch per job
 void slot_worker_main(SlotWorker *w)
 {
@@ -915,11 +804,7 @@ void slot_worker_main(SlotWorker *w)
         else {
             std::lock_guard<std::mutex> ck(g->mu);
             rc = require_ctx();
-            if (rc == PR_OK) {
-                const Resubmit &r = w->in;
-                rc = refine_impl(r.tris, r.n_tris, w->poses.data(), (uint32_t)w->poses.size(), r.W, r.H, &r.proj, r.K, r.scene_kind, resubmit_scene(r), r.crit, r.roi,
-                                 w->results_host, r.results_dev, w->sizes_host);
-            }
+            if (rc == PR_OK) rc = refine_core(w->in, w->poses.data(), (uint32_t)w->poses.size(), w->results_host, w->sizes_host);
         }
         trace_mark("worker: job done");
         lk.lock();
@@ -932,12 +817,8 @@ void slot_worker_main(SlotWorker *w)
     { std::lock_guard<std::mutex> lk(w->mu); w->alive = false; }
     w->cv.notify_all();
 }
-int slot_worker_post(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                     const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                     pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host)
+int slot_worker_post(Slot &sl, const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_result *results_host, uint32_t *sizes_host)
 {
-    if (scene_kind != PR_SCENE_NN && scene_kind != PR_SCENE_PROJ && scene_kind != PR_SCENE_PROJ_CROP) { set_error("unknown scene kind %d", scene_kind); return PR_ERR_INVALID; }
-    if (!scene) { set_error("pr_refine_submit: null scene"); return PR_ERR_INVALID; }
     if (!sl.worker) {
         // the helpers of ALL slots of this context, one after the other, each with its streams made before the next one starts (see slot_worker_main)
         for (Slot &o : g->slots) {
@@ -953,7 +834,7 @@ int slot_worker_post(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, const
     SlotWorker &w = *sl.worker;
     {
         std::lock_guard<std::mutex> lk(w.mu);
-        w.in = make_resubmit(tris_dev, n_tris, W, H, proj, K, scene_kind, scene, crit, roi, results_dev);
+        w.in = job;
         w.poses.assign(poses_host, poses_host + P);
         w.results_host = results_host; w.sizes_host = sizes_host;
         w.done = false; w.has_job = true;
@@ -962,63 +843,13 @@ int slot_worker_post(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, const
     return PR_OK;
 }
 
-int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, uint32_t P, uint32_t W, uint32_t H,
-                        const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                        pr_result *results_host, pr_result *results_dev);
-
-int refine_submit(int slot, const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                  const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                  pr_result *results_host, pr_result *results_dev, uint32_t *sizes_host)
+// everything of a batch onto the slot's streams; the poses are in sl.h_in already (refine_submit)
+int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *results_host)
 {
-    if (slot < 0 || slot >= kSlots) { set_error("slot must be 0..%d", kSlots - 1); return PR_ERR_INVALID; }
-    Slot &sl = g->slots[slot];
-    if (sl.pending) { set_error("pr_refine_submit: slot %d still holds an unfinished batch (call pr_refine_wait)", slot); return PR_ERR_INVALID; }
-    if ((!tris_dev && n_tris > 0) || !poses_host || !proj || !K || W == 0 || H == 0 || (!results_host && !results_dev)) { set_error("pr_refine_submit: bad arguments"); return PR_ERR_INVALID; }
-    if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
-    if (!frame_size_ok(W, H) || !roi_ok(roi, W, H)) return PR_ERR_INVALID;
-    sl.P = P; sl.user_results_host = results_host; sl.user_sizes = sizes_host; sl.delivered = false;
-    const size_t img = (size_t)W * H;
-    const uint64_t period = (uint64_t)std::max(1, opt.sample_period);
-    const bool sample_call = (opt.profile == 2) && (g->sample_clock % period == 0);
-    const bool proj_scene = (scene_kind == PR_SCENE_PROJ || scene_kind == PR_SCENE_PROJ_CROP);
-    const bool nn_scene = (scene_kind == PR_SCENE_NN) && !opt.nn_count;     // (an instrumented kd-tree run stays synchronous)
-    (void)img;                                                   // (large frames: the asynchronous path sizes its sub-batches to its workspace bound)
-    const bool async_ok = P > 0 && opt.solve_mode == PR_SOLVE_DEVICE && opt.raster_mode == 0 && (proj_scene || nn_scene)
-                          && (opt.profile == 0 || opt.profile == 3 || (opt.profile == 2 && !sample_call));
-    if (!async_ok && P > 0 && opt.solve_mode == PR_SOLVE_HOST && opt.host_worker && opt.profile == 0 && !opt.nn_count) {
-        // host solve, nothing to time: the batch goes to the slot's helper thread (see SlotWorker) and this call returns
-        PR_TRY(slot_worker_post(sl, tris_dev, n_tris, poses_host, P, W, H, proj, K, scene_kind, scene, crit, roi, results_host, results_dev, sizes_host));
-        sl.pending = true; sl.delivered = false; sl.worker_job = true;
-        return PR_OK;
-    }
-    if (!async_ok) {
-        // the synchronous path (host solve, timed calls, oversized batches): let the other slot drain first so
-        // that a timed launch has the chip to itself, then run to completion; pr_refine_wait has nothing left to do
-        for (Slot &o : g->slots) if (o.pending && !o.delivered && o.done) HIP_TRY(hipEventSynchronize(o.done));
-        PR_TRY(refine_impl(tris_dev, n_tris, poses_host, P, W, H, proj, K, scene_kind, scene, crit, roi, results_host, results_dev, sizes_host));
-        sl.pending = true; sl.delivered = true;
-        return PR_OK;
-    }
-    g->sample_clock++;
-    // the host copies of this batch's inputs (the poses are staged from here; the rest is what a re-run needs)
-    const size_t in_bytes = (sizeof(pr_mat4) + sizeof(int4) + sizeof(uint32_t)) * (size_t)P;      // [poses][pixel boxes][box offsets]
-    PR_TRY(sl.h_in.ensure(in_bytes + 16));
-    std::memcpy(sl.h_in.p, poses_host, sizeof(pr_mat4) * P);
-    sl.again = make_resubmit(tris_dev, n_tris, W, H, proj, K, scene_kind, scene, crit, roi, results_dev);
-    const int rc = refine_submit_async(sl, tris_dev, n_tris, P, W, H, proj, K, scene_kind, scene, crit, roi, results_host, results_dev);
-    if (rc != PR_OK) {                                            // part of the batch may already be queued: do not leave it running
-        slot_drain(sl);                                           // behind the caller's back (its buffers may go away next)
-        sl.pending = false;
-        return rc;
-    }
-    sl.pending = true;
-    return PR_OK;
-}
-
-int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, uint32_t P, uint32_t W, uint32_t H,
-                        const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
-                        pr_result *results_host, pr_result *results_dev)
-{
+    const uint32_t W = job.W, H = job.H;
+    const float *K = job.K;
+    const int scene_kind = job.scene_kind;
+    const pr_criteria crit = job.crit;
     const size_t img = (size_t)W * H;
     PR_TRY(slot_streams(sl));
     SceneSel sc;
@@ -1032,16 +863,14 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     // nothing of this batch may run beside the loop of a TIMED batch on the other slot -- not even the small checks on the scene stream
     if (scene_stream != sl.stream)
         for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered && o.timed && o.progress_valid) HIP_TRY(hipStreamWaitEvent(scene_stream, o.progress, 0));
-    PR_TRY(make_scene(scene_kind, scene, /*want_packed=*/true, sc, &sl.packed, scene_stream, scene_kind == PR_SCENE_NN ? &cam : nullptr, /*verify_now=*/false));
+    PR_TRY(make_scene(scene_kind, job.scene(), /*want_packed=*/true, sc, &sl.packed, scene_stream, scene_kind == PR_SCENE_NN ? &cam : nullptr, /*verify_now=*/false));
     sl.nn_set = (scene_kind == PR_SCENE_NN) ? sc.nn_set : -1;        // (what make_scene must not rebuild under this batch while it is in flight)
 
-    PR_TRY(ensure_model_box(tris_dev, n_tris));                 // once per triangle buffer ...
-    const size_t res_off = ((size_t)P * 4 + 63) & ~(size_t)63;
-    sl.flag_off = (res_off + sizeof(pr_result) * P + 63) & ~(size_t)63;
-    PR_TRY(sl.h_out.ensure(sl.flag_off + 64));
-    void *h_in_dev = nullptr, *h_out_dev = nullptr;              // the pinned staging buffers as the device sees them
-    HIP_TRY(hipHostGetDevicePointer(&h_in_dev, sl.h_in.p, 0));
-    HIP_TRY(hipHostGetDevicePointer(&h_out_dev, sl.h_out.p, 0));
+    PR_TRY(ensure_model_box(job.tris, job.n_tris));             // once per triangle buffer ...
+    const SlotIn in(P);
+    const SlotOut out(P);
+    PR_TRY(sl.h_out.ensure(out.bytes));
+    unsigned char *h_out_dev = sl.h_out.dev_as<unsigned char>();  // the pinned block as the device sees it
     HIP_TRY(hipEventRecord(sl.scene_ready, scene_stream));      // (complete as it is recorded unless a cache missed and the scene is being rebuilt on this stream)
     // ... and checked against the buffer's present content by every batch (refine_wait acts on the flag), together with the scene caches: a
     // sampled fingerprint of the caller's arrays against the one taken when the cache was built.  Round 5: both checks ride on the raster launch
@@ -1053,22 +882,22 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
         HIP_TRY(hipMemsetAsync(sl.aabb_keys.p, 0xff, 6 * sizeof(uint32_t), sl.stream));
         HIP_TRY(hipMemsetAsync(sl.aabb_keys.as<uint32_t>() + 6, 0, (prk::kBatchCheckWords - 6) * sizeof(uint32_t), sl.stream));
     }
-    *reinterpret_cast<volatile uint32_t *>(sl.h_out.as<unsigned char>() + sl.flag_off) = 0u;
+    *reinterpret_cast<volatile uint32_t *>(sl.h_out.as<unsigned char>() + out.flag) = 0u;
     prk::BatchCheck chk{};
     {
         chk.keys = sl.aabb_keys.as<uint32_t>();
         for (int a = 0; a < 6; ++a) chk.expect.v[a] = g->aabb_host[a];
-        chk.caller = tris_dev; chk.mesh_hash = g->mesh_hash;
-        chk.flag = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(h_out_dev) + sl.flag_off);
+        chk.caller = job.tris; chk.mesh_hash = g->mesh_hash;
+        chk.flag = reinterpret_cast<uint32_t *>(h_out_dev + out.flag);
         if (opt.scene_cache) {
             if (scene_kind == PR_SCENE_NN) {
-                const pr_scene_nn *sn = static_cast<const pr_scene_nn *>(scene);
+                const pr_scene_nn *sn = &job.sn;
                 chk.fa = reinterpret_cast<const uint32_t *>(sn->pcd); chk.na = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
                 chk.fb = reinterpret_cast<const uint32_t *>(sn->nodes); chk.nb = (size_t)sn->n_nodes * sizeof(pr_kdnode) / 4;
                 chk.fc = reinterpret_cast<const uint32_t *>(sn->normal); chk.nc = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
                 chk.fp_expected = g->nn_sets[sc.nn_set].nndepth.as<uint32_t>() + 12;
             } else if (sl.packed.valid) {
-                const pr_scene_proj *sp = static_cast<const pr_scene_proj *>(scene);
+                const pr_scene_proj *sp = &job.sp.view;
                 const size_t n = (size_t)sp->width * sp->height;
                 const size_t tables = ((sp->width + sp->height) * sizeof(float) + 15) & ~(size_t)15;
                 const uint32_t *exact_dev = reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(sl.packed.rec.as<float4>() + n) + tables);
@@ -1079,14 +908,13 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
         }
     }
 
-    // staging: [poses][boxes][box offsets]; the cloud stride and the grid come from the largest box
-    const size_t in_bytes = (sizeof(pr_mat4) + sizeof(int4) + sizeof(uint32_t)) * (size_t)P;
-    PR_TRY(sl.poses_bbox.ensure(in_bytes + 16));
+    // staging (SlotIn): the cloud stride and the grid come from the largest box
+    PR_TRY(sl.poses_bbox.ensure(in.bytes + 16));
     pr_mat4 *h_poses = sl.h_in.as<pr_mat4>();
-    int4 *h_box = reinterpret_cast<int4 *>(h_poses + P);
+    int4 *h_box = reinterpret_cast<int4 *>(sl.h_in.as<unsigned char>() + in.box);
     size_t max_area = 1;
     for (uint32_t i = 0; i < P; ++i) {
-        h_box[i] = prk::pose_pixel_box(g->aabb_host, h_poses[i].m, *proj, W, H, roi);
+        h_box[i] = prk::pose_pixel_box(g->aabb_host, h_poses[i].m, job.proj, W, H, job.roi);
         const int4 &b = h_box[i];
         max_area = std::max(max_area, (size_t)std::max(0, b.z - b.x + 1) * (size_t)std::max(0, b.w - b.y + 1));   // an off-screen pose has an empty box
     }
@@ -1110,7 +938,7 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     const uint32_t sub = (P + n_sub - 1) / n_sub;
     PR_TRY(sl.depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * sub));
     // the pixel boxes of a sub-batch packed into the depth workspace: box i at h_off[i] ints, its own width as pitch (fill_box_kernel)
-    uint32_t *h_off = reinterpret_cast<uint32_t *>(h_box + P);
+    uint32_t *h_off = reinterpret_cast<uint32_t *>(sl.h_in.as<unsigned char>() + in.off);
     if (prk::kBoxPack) {
         size_t acc = 0;
         for (uint32_t i = 0; i < P; ++i) {
@@ -1129,7 +957,7 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     PR_TRY(sl.partial.ensure(sizeof(float) * prk::kAccStride * (size_t)nblk * sub));
     PR_TRY(sl.dstate.ensure(sizeof(prk::DevIcpState) * P));
     PR_TRY(sl.arrive.ensure(sizeof(uint32_t) * P));
-    pr_result *dres = results_dev;
+    pr_result *dres = job.results_dev;
     if (!dres) { PR_TRY(sl.dresults.ensure(sizeof(pr_result) * P)); dres = sl.dresults.as<pr_result>(); }
     // kd-tree scene: winners | slack | queue | two queue counters per hypothesis, indexed like the clouds of one sub-batch (icp_drive
     // has the same layout); the search kernel's grid comes from the box bound, surplus workgroups exit at once
@@ -1169,19 +997,20 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
     auto t_begin = [&]() -> size_t { const size_t e = t_event(); t_record(e); return e; };
     auto t_end = [&](size_t e0, int kind, uint32_t q0, uint32_t nq, bool edge) { const size_t e1 = t_event(); t_record(e1); if (!t_fail) sl.t_spans.push_back({ e0, e1, kind, q0, nq, edge, false, { 0, 0, 0 } }); };
     pr_mat4 *d_poses = sl.poses_bbox.as<pr_mat4>();
-    int4 *d_box = reinterpret_cast<int4 *>(d_poses + P);
-    const uint32_t *d_off = prk::kBoxPack ? reinterpret_cast<const uint32_t *>(d_box + P) : nullptr;
+    int4 *d_box = reinterpret_cast<int4 *>(sl.poses_bbox.as<unsigned char>() + in.box);
+    const uint32_t *d_off = prk::kBoxPack ? reinterpret_cast<const uint32_t *>(sl.poses_bbox.as<unsigned char>() + in.off) : nullptr;
     // Both phases are bound by the same units, so a batch that renders while the other slot is in the middle of its ICP loop
     // slows that loop by more than it gains; its render is therefore held back until the other slot has issued pass
     // `overlap_pass` of its (last sub-batch's) loop -- late enough to disturb little, early enough that the GPU never idles.
     for (Slot &o : g->slots)
         if (&o != &sl && o.pending && !o.delivered && o.progress_valid) HIP_TRY(hipStreamWaitEvent(st, o.progress, 0));
     sl.progress_valid = false;
-    HIP_TRY(prk::launch_stage_words(h_in_dev, d_poses, in_bytes, st));
+    HIP_TRY(prk::launch_stage_words(sl.h_in.dev, d_poses, in.bytes, st));
     const bool fused = opt.fused_solve != 0;
     const pr_roi none{ 0, 0, 0, 0 };                              // the ROI is already part of the host-computed boxes
+    const Lanes lanes{ sl.stream, sl.side, sl.fork, sl.join };
     // the raster's triangles: the context's ordered copy (same triangles, same minima; the first render's checks read the caller's buffer)
-    const pr_triangle *raster_tris = (opt.mesh_order && g->mesh_sorted_valid) ? g->mesh_sorted.as<pr_triangle>() : tris_dev;
+    const pr_triangle *raster_tris = (opt.mesh_order && g->mesh_sorted_valid) ? g->mesh_sorted.as<pr_triangle>() : job.tris;
     for (uint32_t q0 = 0; q0 < P; q0 += sub) {
         const uint32_t nq = std::min(sub, P - q0);
         prk::PoseMeta *meta = sl.meta.as<prk::PoseMeta>() + q0;
@@ -1194,8 +1023,8 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
         // `exact` flag / tree depth back before it returns, so a rebuild has finished on the host's clock before the render is even enqueued; on a
         // cache hit the event is complete when recorded)
         if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
-        HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
-                                         sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, *proj, none, st,
+        HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)job.n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
+                                         sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, job.proj, none, st,
                                          /*compute_boxes=*/false, meta, dstate, arrive, (uint32_t)cstride, d_off ? d_off + q0 : nullptr, q0 == 0 ? &chk : nullptr));
         if (timed) { t_end(te, kSpanRender, q0, nq, false); te = t_begin(); }
         HIP_TRY(prk::launch_emit_box(sl.depth.as<int32_t>(), nq, W, H, d_box + q0, K[0], K[4], K[2], K[5], sl.row_count.as<uint32_t>(),
@@ -1204,15 +1033,8 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
         if (timed && q0 == 0)                                     // the timed loop starts when the other slot's batch is complete
             for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered && o.done) HIP_TRY(hipStreamWaitEvent(st, o.done, 0));
 
-        // the iteration loop: (max_iteration+1) x [pass (+ fused finalize/solve)], pose groups on the slot's side streams
-        const uint32_t n_groups = timed ? 1u : std::max(1u, std::min({ pose_groups_for(scene_kind), 4u, nq / 32u }));
-        auto group_begin = [&](uint32_t grp) { return (uint32_t)(((uint64_t)nq * grp) / n_groups); };
+        const uint32_t n_groups = pose_group_count(scene_kind, nq, timed);
         if (nn_prev) HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(nn_prev + 6 * nn_span), (size_t)prk::kQCountStride * nq, 0, st));
-        if (n_groups > 1) {
-            for (uint32_t k = 1; k < n_groups; ++k) PR_TRY(ensure_stream(sl.side[k - 1], &sl.join[k - 1]));
-            HIP_TRY(hipEventRecord(sl.fork, st));
-            for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamWaitEvent(sl.side[k - 1], sl.fork, 0));
-        }
         // When may the OTHER slot start rendering?  Measured optimum (21 passes of obj_06, overlap_pass swept per batch size):
         // pass 4 or earlier at 128 hypotheses, 9-10 at 256, 14-16 at 384, 16 at 512 -- i.e. when about 2800 hypothesis-passes of
         // this loop are left (never fewer than 5 passes): that much loop work is what a render hides behind without stretching the
@@ -1220,7 +1042,7 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
         // hypothesis (31 468 and 27 400 there; cloud_hint = the largest cloud of the previous batch).
         uint32_t auto_overlap = 0;
         {
-            const double weight = ((double)std::max<size_t>(n_tris, 1) / 31468.0) * (27400.0 / (double)std::max(g->cloud_hint, 1000u));
+            const double weight = ((double)std::max<size_t>(job.n_tris, 1) / 31468.0) * (27400.0 / (double)std::max(g->cloud_hint, 1000u));
             double left = std::max(5.0, 2800.0 * weight / (double)std::max(nq, 1u));   // passes of this sub-batch's loop still to run
             // Since the clouds are packed (end of round 4) a render disturbs the loop beside it less, as long as the clouds of BOTH slots stay in
             // the 256 MiB Infinity Cache: then the render is released with 13 passes to go (256 hypotheses: passes 5-9 give 272 k poses/s, the rule
@@ -1234,45 +1056,84 @@ int refine_submit_async(Slot &sl, const pr_triangle *tris_dev, size_t n_tris, ui
             if (scene_kind == PR_SCENE_NN) auto_overlap = 0u;
         }
         prk::IcpBatch b{};
-        b.cloud = sl.cloud.as<pr_vec3>(); b.nblk = nblk; b.grid_x = grid_x; b.steps = steps;
+        b.cloud = sl.cloud.as<pr_vec3>(); b.partial = sl.partial.as<float>(); b.nblk = nblk; b.grid_x = grid_x; b.steps = steps;
         if (nn_prev) {
             b.nn_prev = nn_prev; b.nn_slack = reinterpret_cast<float *>(nn_prev + nn_span);
             b.nn_queue = reinterpret_cast<uint2 *>(nn_prev + 2 * nn_span); b.nn_queue2 = reinterpret_cast<uint2 *>(nn_prev + 4 * nn_span); b.nn_qcount = nn_prev + 6 * nn_span;
         }
-        for (uint32_t it = 0; it <= (uint32_t)crit.max_iteration; ++it) {
-            for (uint32_t grp = 0; grp < n_groups; ++grp) {
-                const uint32_t p0 = group_begin(grp), np = group_begin(grp + 1) - p0;
-                hipStream_t gs = grp ? sl.side[grp - 1] : st;
-                prk::IcpBatch bb = b;
-                bb.meta = meta + p0; bb.partial = sl.partial.as<float>() + (size_t)p0 * nblk * prk::kAccStride;
-                if (bb.nn_qcount) bb.nn_qcount += prk::kQCountStride * (size_t)p0;
-                bb.iter = it;
-                if (fused) { bb.fused = 1; bb.crit = crit; bb.st = dstate + p0; bb.arrive = arrive + p0; }
-                bb.score_only = (it == (uint32_t)crit.max_iteration) ? 1u : 0u;
-                if (timed) {                                         // (one group: gs == st)
-                    const size_t e0 = t_begin();
-                    // a kd-tree pass is four kernels: three more events between them give each kernel's own time (pr_profile_nn)
-                    const bool marks = sc.kind == PR_SCENE_NN && sc.nn_split && bb.nn_prev && np <= 32768u;
-                    size_t mi[3] = { 0, 0, 0 }; hipEvent_t me[3] = { nullptr, nullptr, nullptr };
-                    bool marks_ok = marks;
-                    if (marks) for (int k = 0; k < 3; ++k) { mi[k] = t_event(); if (mi[k] == kNoEvent) marks_ok = false; else me[k] = sl.t_events[mi[k]]; }
-                    HIP_TRY(launch_pass(bb, sc, np, gs, marks_ok ? me : nullptr));
-                    t_end(e0, kSpanIcp, q0 + p0, np, it == 0 || it == (uint32_t)crit.max_iteration);
-                    if (marks_ok && !t_fail) { Slot::TSpan &ts = sl.t_spans.back(); ts.marks = true; for (int k = 0; k < 3; ++k) ts.m[k] = mi[k]; }
-                } else HIP_TRY(launch_pass(bb, sc, np, gs));
-                if (!fused) HIP_TRY(prk::launch_icp_finalize_solve(bb.partial, meta + p0, nblk, steps, dstate + p0, crit, it, np, gs));
-            }
-            if (q0 + sub >= P && it == (timed ? (uint32_t)crit.max_iteration : std::min<uint32_t>((uint32_t)crit.max_iteration, (pipeline_start && opt.start_overlap >= 0) ? (uint32_t)opt.start_overlap : (opt.overlap_pass >= 0 ? (uint32_t)opt.overlap_pass : auto_overlap)))) {
-                HIP_TRY(hipEventRecord(sl.progress, st));
-                sl.progress_valid = true;
-            }
-        }
-        for (uint32_t k = 1; k < n_groups; ++k) { HIP_TRY(hipEventRecord(sl.join[k - 1], sl.side[k - 1])); HIP_TRY(hipStreamWaitEvent(st, sl.join[k - 1], 0)); }
+        const uint32_t last_pass = (uint32_t)crit.max_iteration;
+        auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t gs) -> int {
+            if (!timed) { HIP_TRY(launch_pass(bb, sc, np, gs)); return PR_OK; }
+            const size_t e0 = t_begin();                             // (one group: gs == st)
+            // a kd-tree pass is four kernels: three more events between them give each kernel's own time (pr_profile_nn)
+            const bool marks = sc.kind == PR_SCENE_NN && sc.nn_split && bb.nn_prev && np <= 32768u;
+            size_t mi[3] = { 0, 0, 0 }; hipEvent_t me[3] = { nullptr, nullptr, nullptr };
+            bool marks_ok = marks;
+            if (marks) for (int k = 0; k < 3; ++k) { mi[k] = t_event(); if (mi[k] == kNoEvent) marks_ok = false; else me[k] = sl.t_events[mi[k]]; }
+            HIP_TRY(launch_pass(bb, sc, np, gs, marks_ok ? me : nullptr));
+            t_end(e0, kSpanIcp, q0 + p0, np, bb.iter == 0 || bb.iter == last_pass);
+            if (marks_ok && !t_fail) { Slot::TSpan &ts = sl.t_spans.back(); ts.marks = true; for (int k = 0; k < 3; ++k) ts.m[k] = mi[k]; }
+            return PR_OK;
+        };
+        // the pass of the batch's last sub-batch behind which the other slot's render may start: a timed batch's last, else the options, else the rule above
+        const uint32_t release_pass = timed ? last_pass : std::min<uint32_t>(last_pass, (pipeline_start && opt.start_overlap >= 0) ? (uint32_t)opt.start_overlap : (opt.overlap_pass >= 0 ? (uint32_t)opt.overlap_pass : auto_overlap));
+        auto after = [&](uint32_t it, bool &) -> int {
+            if (q0 + sub >= P && it == release_pass) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
+            return PR_OK;
+        };
+        // the iteration loop: (max_iteration+1) x [pass (+ fused finalize/solve)], pose groups on the slot's side streams
+        PR_TRY(device_solve_loop(lanes, n_groups, b, nq, crit, fused, meta, dstate, arrive, pass, after));
     }
-    HIP_TRY(prk::launch_pack_export(sl.dstate.as<prk::DevIcpState>(), dres, sl.counts.as<uint32_t>(), static_cast<uint32_t *>(h_out_dev),
-                                    results_host ? reinterpret_cast<pr_result *>(static_cast<unsigned char *>(h_out_dev) + res_off) : nullptr, P, st));
+    HIP_TRY(prk::launch_pack_export(sl.dstate.as<prk::DevIcpState>(), dres, sl.counts.as<uint32_t>(), reinterpret_cast<uint32_t *>(h_out_dev),
+                                    results_host ? reinterpret_cast<pr_result *>(h_out_dev + out.res) : nullptr, P, st));
     HIP_TRY(hipEventRecord(sl.done, st));
     if (t_fail) { sl.timed = false; sl.t_spans.clear(); sl.t_used = 0; g->stat_timing_dropped++; }   // the batch runs; its timing is dropped, and counted
+    return PR_OK;
+}
+
+// may a batch be submitted on this slot?
+int slot_idle(int slot)
+{
+    if (slot < 0 || slot >= kSlots) { set_error("slot must be 0..%d", kSlots - 1); return PR_ERR_INVALID; }
+    if (g->slots[slot].pending) { set_error("pr_refine_submit: slot %d still holds an unfinished batch (call pr_refine_wait)", slot); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+// a batch onto an idle slot: enqueued on the slot's streams, handed to its helper thread, or run to completion here
+int refine_submit(Slot &sl, const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_result *results_host, uint32_t *sizes_host)
+{
+    if (!poses_host || (!results_host && !job.results_dev)) { set_error("pr_refine_submit: bad arguments"); return PR_ERR_INVALID; }
+    sl.P = P; sl.user_results_host = results_host; sl.user_sizes = sizes_host; sl.delivered = false;
+    const uint64_t period = (uint64_t)std::max(1, opt.sample_period);
+    const bool sample_call = (opt.profile == 2) && (g->sample_clock % period == 0);
+    // (an instrumented kd-tree run stays synchronous; large frames: the asynchronous path sizes its sub-batches to its workspace bound)
+    const bool async_ok = P > 0 && opt.solve_mode == PR_SOLVE_DEVICE && opt.raster_mode == 0 && (job.scene_kind != PR_SCENE_NN || !opt.nn_count)
+                          && (opt.profile == 0 || opt.profile == 3 || (opt.profile == 2 && !sample_call));
+    if (!async_ok && P > 0 && opt.solve_mode == PR_SOLVE_HOST && opt.host_worker && opt.profile == 0 && !opt.nn_count) {
+        // host solve, nothing to time: the batch goes to the slot's helper thread (see SlotWorker) and this call returns
+        PR_TRY(slot_worker_post(sl, job, poses_host, P, results_host, sizes_host));
+        sl.pending = true; sl.delivered = false; sl.worker_job = true;
+        return PR_OK;
+    }
+    if (!async_ok) {
+        // the synchronous path (host solve, timed calls, oversized batches): let the other slot drain first so
+        // that a timed launch has the chip to itself, then run to completion; pr_refine_wait has nothing left to do
+        for (Slot &o : g->slots) if (o.pending && !o.delivered && o.done) HIP_TRY(hipEventSynchronize(o.done));
+        PR_TRY(refine_core(job, poses_host, P, results_host, sizes_host));
+        sl.pending = true; sl.delivered = true;
+        return PR_OK;
+    }
+    g->sample_clock++;
+    // the host copies of this batch's inputs (the poses are staged from here; the rest is what a re-run needs)
+    PR_TRY(sl.h_in.ensure(SlotIn(P).bytes + 16));
+    std::memcpy(sl.h_in.p, poses_host, sizeof(pr_mat4) * P);
+    sl.again = job;
+    const int rc = refine_submit_async(sl, job, P, results_host);
+    if (rc != PR_OK) {                                            // part of the batch may already be queued: do not leave it running
+        slot_drain(sl);                                           // behind the caller's back (its buffers may go away next)
+        sl.pending = false;
+        return rc;
+    }
+    sl.pending = true;
     return PR_OK;
 }
 
@@ -1345,7 +1206,14 @@ int pr_refine_batch_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const ui
                           const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_host, uint32_t *cloud_sizes_host)
 {
     PR_ENTER();
-    return refine_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene, crit, roi, results_host, cloud_sizes_host);
+    if (n_poses == 0) return PR_OK;
+    if (!results_host || !poses_host) { set_error("pr_refine_batch_multi: bad arguments"); return PR_ERR_INVALID; }
+    RefineJob job;
+    PR_TRY(make_job("pr_refine_batch_multi", nullptr, 0, width, height, proj, K, scene_kind, scene, crit, roi, nullptr, job));
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_refine_batch_multi", meshes, n_meshes, mesh_index_host, n_poses, pl));
+    job.plan = &pl;
+    return refine_ordered(job, nullptr, poses_host, n_poses, results_host, cloud_sizes_host);
 }
 
 int pr_refine_pyramid(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
@@ -1356,8 +1224,12 @@ int pr_refine_pyramid(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 
     PR_ENTER();
     // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
     for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+    if (n_poses == 0) return PR_OK;
+    if (!poses_host) { set_error("pr_refine_pyramid: bad arguments"); return PR_ERR_INVALID; }
+    RefineJob job;                                                // (every level brings its own criteria)
+    PR_TRY(make_job("pr_refine_pyramid", tris_dev, n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job));
     const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
-    return pyramid_single(tris_dev, n_tris, poses_host, n_poses, width, height, proj, K, scene_kind, scene, py, roi, results_host);
+    return refine_ordered(job, &py, poses_host, n_poses, results_host, nullptr);
 }
 
 int pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1369,8 +1241,15 @@ int pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
     PR_ENTER();
     // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
     for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+    if (n_poses == 0) return PR_OK;
+    if (!poses_host) { set_error("pr_refine_pyramid_multi: bad arguments"); return PR_ERR_INVALID; }
+    RefineJob job;
+    PR_TRY(make_job("pr_refine_pyramid_multi", nullptr, 0, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job));
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_refine_pyramid_multi", meshes, n_meshes, mesh_index_host, n_poses, pl));
+    job.plan = &pl;
     const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
-    return pyramid_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene, py, roi, results_host);
+    return refine_ordered(job, &py, poses_host, n_poses, results_host, nullptr);
 }
 
 int pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1481,7 +1360,9 @@ int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat
     if (n_poses == 0) return PR_OK;
     const int slot = free_slot();
     if (slot < 0) { set_error("pr_refine_batch: both asynchronous slots hold unfinished batches (pr_refine_wait one of them first)"); return PR_ERR_INVALID; }
-    PR_TRY(refine_submit(slot, tris_dev, n_tris, poses_host, n_poses, width, height, proj, K, scene_kind, scene, crit, roi, results_host, nullptr, cloud_sizes_host));
+    RefineJob job;
+    PR_TRY(make_job("pr_refine_batch", tris_dev, n_tris, width, height, proj, K, scene_kind, scene, crit, roi, nullptr, job));
+    PR_TRY(refine_submit(g->slots[slot], job, poses_host, n_poses, results_host, cloud_sizes_host));
     return refine_wait(slot);
 }
 
@@ -1501,7 +1382,9 @@ int pr_refine_batch_dev(const pr_triangle *tris_dev, size_t n_tris, const pr_mat
     if (n_poses == 0) return PR_OK;
     const int slot = free_slot();
     if (slot < 0) { set_error("pr_refine_batch_dev: both asynchronous slots hold unfinished batches (pr_refine_wait one of them first)"); return PR_ERR_INVALID; }
-    PR_TRY(refine_submit(slot, tris_dev, n_tris, poses_host, n_poses, width, height, proj, K, scene_kind, scene, crit, pr_roi{ 0, 0, 0, 0 }, nullptr, results_dev, cloud_sizes_host));
+    RefineJob job;
+    PR_TRY(make_job("pr_refine_batch_dev", tris_dev, n_tris, width, height, proj, K, scene_kind, scene, crit, pr_roi{ 0, 0, 0, 0 }, results_dev, job));
+    PR_TRY(refine_submit(g->slots[slot], job, poses_host, n_poses, nullptr, cloud_sizes_host));
     return refine_wait(slot);
 }
 
@@ -1511,7 +1394,13 @@ int pr_refine_submit_roi(int slot, const pr_triangle *tris_dev, size_t n_tris, c
 {
     trace_mark("pr_refine_submit: enter");
     int rc;
-    { PR_ENTER(); rc = refine_submit(slot, tris_dev, n_tris, poses_host, n_poses, width, height, proj, K, scene_kind, scene, crit, roi, results_host, results_dev, cloud_sizes_host); }
+    {
+        PR_ENTER();
+        RefineJob job;
+        rc = slot_idle(slot);
+        if (rc == PR_OK) rc = make_job("pr_refine_submit", tris_dev, n_tris, width, height, proj, K, scene_kind, scene, crit, roi, results_dev, job);
+        if (rc == PR_OK) rc = refine_submit(g->slots[slot], job, poses_host, n_poses, results_host, cloud_sizes_host);
+    }
     trace_mark("pr_refine_submit: exit");
     return rc;
 }

@@ -1,5 +1,6 @@
 // pr_runtime.h -- the host-side runtime behind the C ABI, shared by its translation units: contexts and their registry, workspaces, the write
-// log of caller-owned memory, options, slots, profiling spans.  pr_context.cpp (contexts, memory, options, profiling entry points),
+// log of caller-owned memory, options, slots, profiling spans, and what every route of the fused batch path shares: its job record (RefineJob,
+// make_job), the layouts of a slot's pinned blocks, the pose-group lanes and the device-solve iteration loop.  pr_context.cpp (contexts, memory, options, profiling entry points),
 // pr_scene.cpp (scene caches and device-side scene preparation), pr_icp.cpp (the batched ICP driver: device and host solve loops),
 // pr_refine.cpp (render, cloud, the fused batch path with its two asynchronous slots and helper threads), pr_comm.cpp (RCCL gather).
 #pragma once
@@ -24,8 +25,6 @@
 
 #include "pr_internal.h"
 #include "pr_tuning.h"
-
-#include "pr_internal.h"
 
 namespace prh {
 extern thread_local std::string g_err;
@@ -66,20 +65,22 @@ struct DevBuf {                      // grow-only device workspace
     void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
-struct PinBuf {                      // grow-only pinned host staging
-    void *p = nullptr; size_t cap = 0;
+struct PinBuf {                      // grow-only pinned host staging; `dev` = the same bytes as kernels address them (stage_words / copy_words pull from and push to it)
+    void *p = nullptr, *dev = nullptr; size_t cap = 0;
     int ensure(size_t bytes)
     {
         if (bytes <= cap) return PR_OK;
-        if (p) { hipHostFree(p); p = nullptr; cap = 0; }
+        release();
         size_t want = bytes + bytes / 8 + 256;
         hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { set_error("hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e)); p = nullptr; return PR_ERR_NOMEM; }
+        if (e == hipSuccess && (e = hipHostGetDevicePointer(&dev, p, 0)) != hipSuccess) hipHostFree(p);
+        if (e != hipSuccess) { set_error("hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e)); p = dev = nullptr; return PR_ERR_NOMEM; }
         cap = want;
         return PR_OK;
     }
-    void release() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) hipHostFree(p); p = dev = nullptr; cap = 0; }
     template <class T> T *as() const { return static_cast<T *>(p); }
+    template <class T> T *dev_as() const { return static_cast<T *>(dev); }
 };
 
 // ---- which device ranges were written through this library, and when --------------------------------
@@ -175,11 +176,61 @@ struct PackedCache {
     uint64_t gen = 0;
     bool valid = false, exact = false;
 };
-// everything needed to run a submitted batch again (refine_wait does so when the model box the batch assumed turns out stale)
-struct Resubmit {
-    const pr_triangle *tris = nullptr; size_t n_tris = 0; uint32_t W = 0, H = 0; pr_mat4 proj{}; float K[9] = { 0 };
+// ---- the description of one fused batch (render -> cloud -> ICP) -----------------------------------
+// Everything of a batch but what varies from run to run (poses, their number, where the results go on the host), by value: the caller's
+// structs may go away after pr_refine_submit returns, a slot's helper thread runs the batch later, and refine_wait runs it again when the
+// model box it assumed turns out stale.  make_job builds it at the entry points; everything below them takes it as it is.
+// (the raster packs pixel coordinates into 13 bits each and enumerates a triangle's candidate pixels with 24-bit arithmetic;
+// contour.hip: kMaxFrameSide restates the 8192 -- its 32-bit per-workgroup sum is sized by it)
+inline bool frame_size_ok(size_t W, size_t H)
+{
+    if (W > 8192 || H > 8192 || W * H > ((size_t)1 << 24)) { set_error("frames larger than 8192 on a side or 2^24 pixels are not supported (got %zux%zu)", W, H); return false; }
+    return true;
+}
+inline bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
+{
+    if (roi.width <= 0 || roi.height <= 0) return true;            // no ROI
+    if (roi.x < 0 || roi.y < 0 || (size_t)roi.x + (size_t)roi.width > W || (size_t)roi.y + (size_t)roi.height > H) {
+        set_error("roi out of image");                               // renderer.cu:202-203 asserts
+        return false;
+    }
+    return true;
+}
+struct MeshPlan;                     // the hypotheses of a mixed batch grouped by mesh (pr_refine.cpp)
+struct RefineJob {
+    const pr_triangle *tris = nullptr; size_t n_tris = 0;        // one mesh for every hypothesis ...
+    const MeshPlan *plan = nullptr;                              // ... or a mixed batch in its plan's order (synchronous calls only: the plan lives on the entry point's stack)
+    uint32_t W = 0, H = 0; pr_mat4 proj{}; float K[9] = { 0 };
     int scene_kind = 0; pr_scene_proj_crop sp{}; pr_scene_nn sn{}; pr_criteria crit{}; pr_roi roi{ 0, 0, 0, 0 };
     pr_result *results_dev = nullptr;
+    const void *scene() const { return scene_kind == PR_SCENE_NN ? static_cast<const void *>(&sn) : &sp; }   // as make_scene takes it (a crop starts with the plain view)
+};
+// ... from the C arguments, with every check that needs no device.  No HIP call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.
+inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, uint32_t W, uint32_t H, const pr_mat4 *proj, const float K[9], int scene_kind,
+                    const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_dev, RefineJob &job)
+{
+    if ((!tris_dev && n_tris > 0) || !proj || !K || !scene || W == 0 || H == 0) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }   // (an empty model has no array)
+    if (scene_kind != PR_SCENE_NN && scene_kind != PR_SCENE_PROJ && scene_kind != PR_SCENE_PROJ_CROP) { set_error("unknown scene kind %d", scene_kind); return PR_ERR_INVALID; }
+    if (!frame_size_ok(W, H) || !roi_ok(roi, W, H)) return PR_ERR_INVALID;
+    if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
+    job = RefineJob();
+    job.tris = tris_dev; job.n_tris = n_tris; job.W = W; job.H = H; job.proj = *proj; std::memcpy(job.K, K, sizeof job.K);
+    job.scene_kind = scene_kind; job.crit = crit; job.roi = roi; job.results_dev = results_dev;
+    if (scene_kind == PR_SCENE_NN) job.sn = *static_cast<const pr_scene_nn *>(scene);
+    else if (scene_kind == PR_SCENE_PROJ_CROP) job.sp = *static_cast<const pr_scene_proj_crop *>(scene);
+    else job.sp.view = *static_cast<const pr_scene_proj *>(scene);     // (a plain projective scene: a crop at 0, 0)
+    return PR_OK;
+}
+// A slot's pinned blocks, in bytes.  h_in, staged to the device by one kernel: poses | pixel boxes | offsets of the packed boxes.
+// h_out, stored by the batch's last kernels: cloud sizes | result records | the word the device-side model-box check writes (1 = the
+// assumed box or a scene cache was stale), each on a 64-byte line of its own.
+struct SlotIn {
+    size_t box, off, bytes;
+    explicit SlotIn(size_t P) : box(sizeof(pr_mat4) * P), off(box + sizeof(int4) * P), bytes(off + sizeof(uint32_t) * P) {}
+};
+struct SlotOut {
+    size_t res, flag, bytes;
+    explicit SlotOut(size_t P) : res((P * sizeof(uint32_t) + 63) & ~(size_t)63), flag((res + sizeof(pr_result) * P + 63) & ~(size_t)63), bytes(flag + 64) {}
 };
 // A slot's helper thread (PR_SOLVE_HOST): the reference solves on the host (icp.cu:207), which makes a batch a chain of
 // launch -> wait -> solve -> launch that only a host thread can drive; the reference's answer is "many host threads, each refining its own
@@ -193,7 +244,7 @@ struct SlotWorker {
     bool has_job = false, done = false, quit = false, alive = false, started = false;
     int device = 0;
     // the job: every input by value (the caller's arrays of poses may go away after pr_refine_submit returns)
-    Resubmit in;
+    RefineJob in;
     std::vector<pr_mat4> poses;
     pr_result *results_host = nullptr;
     uint32_t *sizes_host = nullptr;
@@ -206,8 +257,7 @@ struct Slot {
     DevBuf poses_bbox, depth, row_count, row_off, counts, cloud, meta, partial, dstate, dresults, arrive, aabb_keys, nn_prev;
     PackedCache packed;
     PinBuf h_in, h_out;
-    Resubmit again;
-    size_t flag_off = 0;             // offset in h_out of the word the device-side model-box check writes (1 = the assumed box was stale)
+    RefineJob again;                 // the batch in flight, as refine_wait runs it again when the model box it assumed turns out stale
     hipStream_t stream = nullptr, side[3] = { nullptr, nullptr, nullptr };
     hipEvent_t fork = nullptr, join[3] = { nullptr, nullptr, nullptr }, done = nullptr, scene_ready = nullptr, progress = nullptr;
     bool progress_valid = false;
@@ -233,14 +283,12 @@ struct GraphKey {                    // every value a captured launch depends on
 };
 struct CachedGraph {
     GraphKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    std::vector<hipEvent_t> events;      // pairs around every correspondence launch when captured with profiling on
     uint64_t stamp = 0;
 };
 inline void destroy_graph(CachedGraph &c)
 {
     if (c.exec) (void)hipGraphExecDestroy(c.exec);
     if (c.graph) (void)hipGraphDestroy(c.graph);
-    for (hipEvent_t e : c.events) (void)hipEventDestroy(e);
     c = CachedGraph();
 }
 
@@ -429,9 +477,7 @@ inline int read_back_words(const void *dev_src, void *host_dst, uint32_t n_words
 {
     if (n_words == 0 || n_words > 64) { set_error("read_back_words: 1..64 words"); return PR_ERR_INVALID; }
     PR_TRY(g->h_flags.ensure(256));
-    void *vd = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&vd, g->h_flags.p, 0));
-    HIP_TRY(prk::launch_copy_words32(dev_src, vd, n_words, st));
+    HIP_TRY(prk::launch_copy_words32(dev_src, g->h_flags.dev, n_words, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::memcpy(host_dst, g->h_flags.p, sizeof(uint32_t) * n_words);
     return PR_OK;
@@ -462,6 +508,64 @@ int make_scene(int kind, const void *scene, bool want_packed, SceneSel &out, Pac
 int kd_build_dev(pr_vec3 *pcd, pr_vec3 *nrm, uint32_t n, int max_leaf, pr_kdnode *nodes, size_t cap, uint32_t *n_nodes);
 hipError_t launch_pass(const prk::IcpBatch &b, const SceneSel &sc, uint32_t P, hipStream_t st = nullptr, hipEvent_t *nn_marks = nullptr);
 int ensure_stream(hipStream_t &st, hipEvent_t *ev = nullptr);
+
+// ---- pose groups: a batch split over up to four streams ------------------------------------------------------------
+// The lanes of one loop: the context's own (icp_drive) or a slot's (refine_submit_async).  Side streams and their join events are created
+// on first use (ensure_stream has the reason), so the arrays are the owner's.
+struct Lanes { hipStream_t main; hipStream_t *side; hipEvent_t fork; hipEvent_t *join; };
+inline hipStream_t lane(const Lanes &l, uint32_t grp) { return grp ? l.side[grp - 1] : l.main; }
+// groups of a batch of n hypotheses.  Launches of different groups overlap: a timed batch is one group, so that the measured kernel has the chip to itself
+inline uint32_t pose_group_count(int scene_kind, uint32_t n, bool timed) { return timed ? 1u : std::max(1u, std::min({ pose_groups_for(scene_kind), 4u, n / 32u })); }
+inline uint32_t group_begin(uint32_t n, uint32_t n_groups, uint32_t grp) { return (uint32_t)(((uint64_t)n * grp) / n_groups); }
+// the side lanes start behind everything the main lane holds so far ...
+inline int lanes_fork(const Lanes &l, uint32_t n_groups)
+{
+    if (n_groups <= 1) return PR_OK;
+    for (uint32_t k = 1; k < n_groups; ++k) PR_TRY(ensure_stream(l.side[k - 1], &l.join[k - 1]));
+    HIP_TRY(hipEventRecord(l.fork, l.main));
+    for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamWaitEvent(l.side[k - 1], l.fork, 0));
+    return PR_OK;
+}
+// ... and the main lane goes on behind all of them
+inline int lanes_join(const Lanes &l, uint32_t n_groups)
+{
+    for (uint32_t k = 1; k < n_groups; ++k) { HIP_TRY(hipEventRecord(l.join[k - 1], l.side[k - 1])); HIP_TRY(hipStreamWaitEvent(l.main, l.join[k - 1], 0)); }
+    return PR_OK;
+}
+// the part of a batch that belongs to the group starting at hypothesis p0 (the clouds themselves are addressed through PoseMeta::start)
+inline prk::IcpBatch group_slice(const prk::IcpBatch &b, uint32_t p0)
+{
+    prk::IcpBatch bb = b;
+    bb.meta += p0; bb.partial += (size_t)p0 * b.nblk * prk::kAccStride; if (bb.nn_qcount) bb.nn_qcount += prk::kQCountStride * (size_t)p0;
+    return bb;
+}
+// The device-solve iteration loop of n hypotheses (meta, dstate, arrive, b.partial and b's kd-tree queue counters at hypothesis 0): fork, (max_iteration + 1) x
+// [pass (+ finalize / solve launch unless the pass' tail does it: fused)] per group, join.  Both the synchronous driver and the asynchronous slots
+// run THIS loop -- the slots' safety net re-runs a batch through the synchronous one and expects the same bytes.  It makes no synchronising call
+// of its own (icp_drive records it into a hipGraph); what differs between the callers comes in as
+//   pass(bb, p0, np, stream) -> rc: launch_pass for one group, with whatever timing the caller keeps around it;
+//   after(it, stop) -> rc:          behind the launches of iteration `it` (an early-exit read-back, a progress event); stop = true ends the loop.
+template <class Pass, class After>
+int device_solve_loop(const Lanes &lanes, uint32_t n_groups, prk::IcpBatch b, uint32_t n, pr_criteria crit, bool fused, prk::PoseMeta *meta,
+                      prk::DevIcpState *dstate, uint32_t *arrive, Pass &&pass, After &&after)
+{
+    b.meta = meta;
+    PR_TRY(lanes_fork(lanes, n_groups));
+    bool stop = false;
+    for (uint32_t it = 0; it <= (uint32_t)crit.max_iteration && !stop; ++it) {
+        for (uint32_t grp = 0; grp < n_groups; ++grp) {
+            const uint32_t p0 = group_begin(n, n_groups, grp), np = group_begin(n, n_groups, grp + 1) - p0;
+            prk::IcpBatch bb = group_slice(b, p0);
+            bb.iter = it;
+            if (fused) { bb.fused = 1; bb.crit = crit; bb.st = dstate + p0; bb.arrive = arrive + p0; }
+            bb.score_only = (it == (uint32_t)crit.max_iteration) ? 1u : 0u;
+            PR_TRY(pass(bb, p0, np, lane(lanes, grp)));
+            if (!fused) HIP_TRY(prk::launch_icp_finalize_solve(bb.partial, meta + p0, b.nblk, b.steps, dstate + p0, crit, it, np, lane(lanes, grp)));
+        }
+        PR_TRY(after(it, stop));
+    }
+    return lanes_join(lanes, n_groups);
+}
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
               pr_criteria crit, pr_result *results_host, pr_result *results_dev);
 void drain_all_slots();

@@ -1,0 +1,78 @@
+// build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
+// Sanitizer harness for the host-only helpers of the fused batch path (pr_runtime.h): make_job with null and out-of-range arguments, the layouts of a
+// slot's pinned blocks (SlotIn, SlotOut), the pose-group split.  None of them calls HIP, so nothing of the runtime is linked.
+#include <cstdio>
+#include "pr_runtime.h"
+namespace prh { void set_error(const char *, ...) {} }
+using namespace prr;
+static long fails = 0;
+#define CHECK(x) do { if (!(x)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); ++fails; } } while (0)
+int main()
+{
+    const pr_triangle *tris = reinterpret_cast<const pr_triangle *>(uintptr_t(0x1000));     // never dereferenced: the job keeps addresses of device memory
+    pr_vec3 *dev = reinterpret_cast<pr_vec3 *>(uintptr_t(0x2000));
+    const float K[9] = { 500, 0, 320, 0, 500, 240, 0, 0, 1 };
+    pr_mat4 proj{};
+    pr_scene_proj sp{}; sp.pcd = dev; sp.normal = dev; sp.width = 640; sp.height = 480; sp.max_dist_diff = 10.0f;
+    pr_scene_proj_crop sc{}; sc.view = sp; sc.tl_x = 7; sc.tl_y = 9;
+    pr_scene_nn sn{}; sn.pcd = dev; sn.normal = dev; sn.n_points = 11;
+    const pr_criteria crit{ 0.0f, 0.0f, 2 };
+    const pr_roi none{ 0, 0, 0, 0 };
+    pr_result *rdev = reinterpret_cast<pr_result *>(uintptr_t(0x3000));
+    RefineJob job;
+    // what must be refused, one mistake at a time; `job` stays as it was
+    job.W = 77;
+    auto refused = [&](const pr_triangle *t, size_t nt, uint32_t W, uint32_t H, const pr_mat4 *p, const float *k, int kind, const void *s, pr_criteria c, pr_roi r) {
+        CHECK(make_job("job_sanitize", t, nt, W, H, p, k, kind, s, c, r, nullptr, job) == PR_ERR_INVALID);
+        CHECK(job.W == 77);
+    };
+    refused(nullptr, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
+    refused(tris, 5, 640, 480, nullptr, K, PR_SCENE_PROJ, &sp, crit, none);
+    refused(tris, 5, 640, 480, &proj, nullptr, PR_SCENE_PROJ, &sp, crit, none);
+    for (int kind : { PR_SCENE_PROJ, PR_SCENE_NN, PR_SCENE_PROJ_CROP }) refused(tris, 5, 640, 480, &proj, K, kind, nullptr, crit, none);
+    for (int kind : { -1, 3, 1 << 30, -2147483647 - 1 }) refused(tris, 5, 640, 480, &proj, K, kind, &sp, crit, none);
+    refused(tris, 5, 0, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
+    refused(tris, 5, 640, 0, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
+    refused(tris, 5, 8193, 1, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
+    refused(tris, 5, 8192, 4096, &proj, K, PR_SCENE_PROJ, &sp, crit, none);              // 2^25 pixels
+    refused(tris, 5, 0xffffffffu, 0xffffffffu, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
+    refused(tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, pr_criteria{ 0.0f, 0.0f, -1 }, none);
+    for (pr_roi r : { pr_roi{ -1, 0, 10, 10 }, pr_roi{ 0, -1, 10, 10 }, pr_roi{ 631, 0, 10, 10 }, pr_roi{ 0, 471, 10, 10 }, pr_roi{ 2147483647, 0, 2147483647, 1 },
+                      pr_roi{ 0, 2147483647, 1, 2147483647 } })
+        refused(tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, r);
+    // what must pass, and what the job then holds
+    CHECK(make_job("job_sanitize", nullptr, 0, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, rdev, job) == PR_OK);      // an empty model has no array
+    CHECK(job.tris == nullptr && job.n_tris == 0 && job.plan == nullptr && job.W == 640 && job.H == 480 && job.results_dev == rdev && job.K[4] == 500.0f);
+    CHECK(job.scene() == &job.sp && job.sp.view.width == 640 && job.sp.tl_x == 0 && job.sp.tl_y == 0);
+    CHECK(make_job("job_sanitize", tris, 5, 8192, 2048, &proj, K, PR_SCENE_PROJ_CROP, &sc, pr_criteria{ 1e-5f, 1e-5f, 0 }, pr_roi{ 630, 470, 10, 10 }, nullptr, job) == PR_OK);
+    CHECK(job.scene() == &job.sp && job.sp.tl_x == 7 && job.sp.tl_y == 9 && job.roi.x == 630 && job.crit.max_iteration == 0 && job.results_dev == nullptr);
+    CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_NN, &sn, crit, pr_roi{ 5, 5, -3, 0 }, nullptr, job) == PR_OK);       // (no ROI)
+    CHECK(job.scene() == &job.sn && job.sn.n_points == 11);
+    // the pinned blocks of a slot: the parts in order, none overlapping, written and read back over their whole length
+    for (size_t P : { size_t(0), size_t(1), size_t(3), size_t(65) }) {
+        const SlotIn in(P);
+        CHECK(in.box == sizeof(pr_mat4) * P && in.off == in.box + sizeof(int4) * P && in.bytes == in.off + sizeof(uint32_t) * P);
+        CHECK(in.box % alignof(int4) == 0 && in.off % alignof(uint32_t) == 0);
+        const SlotOut out(P);
+        CHECK(out.res >= sizeof(uint32_t) * P && out.res % 64 == 0 && out.flag >= out.res + sizeof(pr_result) * P && out.flag % 64 == 0 && out.bytes == out.flag + 64);
+        CHECK(out.res < sizeof(uint32_t) * P + 64 && out.flag < out.res + sizeof(pr_result) * P + 64);
+        std::vector<unsigned char> hin(in.bytes + 16), hout(out.bytes);
+        for (size_t i = 0; i < P; ++i) {
+            reinterpret_cast<pr_mat4 *>(hin.data())[i] = proj;
+            reinterpret_cast<int4 *>(hin.data() + in.box)[i] = int4{ 1, 2, 3, 4 };
+            reinterpret_cast<uint32_t *>(hin.data() + in.off)[i] = (uint32_t)i;
+            reinterpret_cast<uint32_t *>(hout.data())[i] = (uint32_t)i;
+            reinterpret_cast<pr_result *>(hout.data() + out.res)[i] = pr_result{};
+        }
+        *reinterpret_cast<uint32_t *>(hout.data() + out.flag) = 1u;
+        for (size_t i = 0; i < P; ++i) CHECK(reinterpret_cast<uint32_t *>(hin.data() + in.off)[i] == i && reinterpret_cast<uint32_t *>(hout.data())[i] == i);
+        // ... and the pose groups of that many hypotheses: consecutive, complete, at most four
+        for (uint32_t n_groups = 1; n_groups <= 4; ++n_groups) {
+            CHECK(group_begin((uint32_t)P, n_groups, 0) == 0 && group_begin((uint32_t)P, n_groups, n_groups) == P);
+            for (uint32_t k = 0; k < n_groups; ++k) CHECK(group_begin((uint32_t)P, n_groups, k) <= group_begin((uint32_t)P, n_groups, k + 1));
+        }
+    }
+    CHECK(group_begin(0xffffffffu, 4, 4) == 0xffffffffu && group_begin(0xffffffffu, 4, 3) == 0xbfffffffu);
+    std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");
+    return fails ? 1 : 0;
+}

@@ -535,6 +535,20 @@ int  pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, c
  * finished_out: n x uint32 (1 = the hypothesis stops here). */
 int  pr_debug_pose_iteration(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, int on_device,
                              pr_result *state, float *update_out, uint32_t *finished_out);
+/* Audit entry: the 29 sums of EVERY pass, as the product path delivered them to the host-solve loop.  Arms a recorder on the calling
+ * thread (and so on the context that thread is bound to) for its next synchronous ICP call -- pr_icp_batch, pr_icp_proj, pr_icp_nn,
+ * pr_refine_batch, pr_refine_batch_roi -- and for that call only: the recorder is gone when the call returns, error or not.
+ * rows_host = NULL disarms.  While it is armed the loop copies the 29 floats of hypothesis i at iteration it to
+ * rows_host[(it * n_hyp + i) * 29 ..], exactly what the iteration of icp.cu:178-212 is about to consume (layout: see
+ * pr_debug_pose_iteration), whichever way the sums reached the host (options fused_solve, host_poll, pose_groups).  Rows of hypotheses
+ * that are skipped (empty cloud) or already finished are not written: prefill the array to tell them apart.  The traced call returns
+ * PR_ERR_INVALID before it launches anything when the solve is on the device (option solve), when its batch is not n_hyp hypotheses,
+ * or when max_iteration + 1 > n_passes; nothing outside n_passes * n_hyp * 29 floats is ever written.  A traced call is one run of the
+ * loop: a pr_icp_batch list of more than 32768 clouds, or a pr_refine_batch whose depth images do not fit one chunk (4 GiB), is refused
+ * the same way.  Every other entry point (pr_refine_submit, pr_refine_batch_dev, the pyramid and multi calls) neither records nor
+ * disarms: the recorder stays armed until one of the calls above, or a NULL call, takes it, and rows_host must stay alive until then.
+ * Arming needs no device. */
+int  pr_debug_trace_sums(float *rows_host, uint32_t n_hyp, uint32_t n_passes);
 /* Audit entries (no device needed) for the library's ordered copy of a triangle buffer (option "mesh_order"): perm_out[k] = index of the
  * triangle the copy holds at place k -- a permutation of 0..n_tris-1, a pure function of the triangle data (Morton code of the
  * centroids, stable; non-finite centroids last) -- and the order-independent 64-bit fingerprint of a buffer (wrapping sum of a mixing

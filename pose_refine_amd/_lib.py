@@ -166,6 +166,7 @@ SIGNATURES = {
     "pr_profile_nn": (_i32, [_vp, C.POINTER(C.c_uint64)]),
     "pr_debug_contrib29": (_i32, [_vp, _u32, _i32, _vp, _vp, _i32, _vp]),
     "pr_debug_pose_iteration": (_i32, [_vp, _vp, _u32, Criteria, _u32, _i32, _vp, _vp, _vp]),
+    "pr_debug_trace_sums": (_i32, [_vp, _u32, _u32]),
     "pr_debug_mesh_order": (_i32, [_vp, _sz, _vp]),
     "pr_debug_mesh_fingerprint": (_i32, [_vp, _sz, C.POINTER(C.c_uint64)]),
     "pr_stats": (_i32, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

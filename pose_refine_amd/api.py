@@ -548,6 +548,23 @@ def debug_pose_iteration(sums, n_points, criteria, iteration: int, on_device: bo
     return st, upd.reshape(n, 4, 4), fin.astype(bool)
 
 
+def trace_sums(n_hyp: int, n_passes: int) -> np.ndarray:
+    """``pr_debug_trace_sums``: arms the recorder for this thread's next synchronous ICP call (``ICP_Point2Plane[_batch]``, ``refine_batch``
+    under host solve) and returns the NaN-prefilled (n_passes, n_hyp, 29) float32 array that call fills: row (it, i) = the 29 sums
+    hypothesis i's iteration ``it`` consumed; rows of skipped or finished hypotheses stay NaN.  The array is kept alive here until the
+    next ``trace_sums`` / ``trace_sums_off`` of the thread, so dropping the returned reference early is harmless."""
+    rows = np.full((int(n_passes), int(n_hyp), 29), np.nan, np.float32)
+    _tls.trace_rows = rows
+    check(_lib.load().pr_debug_trace_sums(ptr(rows), int(n_hyp), int(n_passes)))
+    return rows
+
+
+def trace_sums_off():
+    """Disarms a recorder that no call has consumed yet (``pr_debug_trace_sums(NULL, 0, 0)``)."""
+    check(_lib.load().pr_debug_trace_sums(None, 0, 0))
+    _tls.trace_rows = None
+
+
 def refine_batch(tris, poses, width: int, height: int, proj, K, scene,
                  criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(), results_dev: Optional[int] = None,
                  roi: Optional[Sequence[int]] = None):

@@ -53,6 +53,18 @@ bool pose_iteration_host(const float *Ab, uint32_t n, pr_result &r, const pr_cri
     return true;
 }
 
+// ---- audit recorder (pr_debug_trace_sums) ----------------------------------------------------------
+thread_local SumsTraceState tl_sums_trace;
+int sums_trace_admits(const char *fn, uint32_t P, const pr_criteria &crit)
+{
+    const SumsTrace &t = tl_sums_trace.active;
+    if (!t.rows) return PR_OK;
+    if (opt.solve_mode == PR_SOLVE_DEVICE) { set_error("%s: pr_debug_trace_sums records the host-solve loop; the solve is on the device (option solve)", fn); return PR_ERR_INVALID; }
+    if (P != t.n_hyp) { set_error("%s: pr_debug_trace_sums was armed for %u hypotheses, the batch has %u", fn, t.n_hyp, P); return PR_ERR_INVALID; }
+    if (crit.max_iteration < 0 || (uint64_t)crit.max_iteration + 1 > t.n_passes) { set_error("%s: pr_debug_trace_sums was armed for %u passes, max_iteration %d needs %lld", fn, t.n_passes, crit.max_iteration, (long long)crit.max_iteration + 1); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+
 // ---- the batched ICP driver -----------------------------------------------------------------------
 // clouds: cloud i = cloud_base[start_h[i] .. start_h[i]+count_h[i]); start and count reach the device with the per-hypothesis records staged here.
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
@@ -61,6 +73,8 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     if (P == 0) return PR_OK;
     SceneSel sc = sc_in;
     if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
+    PR_TRY(sums_trace_admits("icp_drive", P, crit));               // (a recorder that does not fit this batch: refused before anything is launched)
+    const SumsTrace trace = tl_sums_trace.active;
     const uint32_t steps = (uint32_t)std::max(1, opt.steps);
     const uint32_t ppb = steps * prk::kPointsPerStep;
     uint32_t max_n = 0; uint64_t sum_n = 0;
@@ -265,6 +279,7 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     // the host's part of an iteration for one hypothesis whose 29 sums have arrived (icp.cu:178-212); returns whether the hypothesis goes on
     auto solve_one = [&](uint32_t i, uint32_t it) -> bool {
         float E[16];
+        if (trace.rows) std::memcpy(trace.rows + ((size_t)it * trace.n_hyp + i) * 29, h_sums + (size_t)i * prk::kAccStride, sizeof(float) * 29);   // pr_debug_trace_sums: it < n_passes, i < n_hyp (sums_trace_admits)
         if (!pose_iteration_host(h_sums + (size_t)i * prk::kAccStride, count_h[i], res[i], crit, it, E)) { h_meta[i].state = prk::kSkip; return false; }
         std::memcpy(h_meta[i].xform, E, sizeof(float) * 12);
         h_meta[i].state = prk::kRunWithTransform;
@@ -346,9 +361,16 @@ extern "C" {
 int pr_icp_batch(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind, const void *scene,
                  pr_criteria crit, pr_result *results_host)
 {
+    TraceScope traced;                                            // (pr_debug_trace_sums: this call and no other)
     PR_ENTER();
     if (!offsets_host || (n_clouds && !results_host)) { set_error("pr_icp_batch: bad arguments"); return PR_ERR_INVALID; }
     if (n_clouds == 0) return PR_OK;
+#ifndef PR_MAX_CLOUDS_PER_RUN
+#define PR_MAX_CLOUDS_PER_RUN 32768                               // (a larger value in an experiment build exercises the launchers' own split)
+#endif
+    constexpr uint32_t kMaxCloudsPerRun = PR_MAX_CLOUDS_PER_RUN;
+    PR_TRY(sums_trace_admits("pr_icp_batch", n_clouds, crit));     // (pr_debug_trace_sums: the whole list against the recorder, before the scene is touched)
+    if (tl_sums_trace.active.rows && n_clouds > kMaxCloudsPerRun) { set_error("pr_icp_batch: pr_debug_trace_sums records one run of at most %u clouds, the list has %u", kMaxCloudsPerRun, n_clouds); return PR_ERR_INVALID; }
     if (!clouds_dev) {                                            // clouds without a single point come without an array (an empty device_vector):
         if (offsets_host[n_clouds] != offsets_host[0]) { set_error("pr_icp_batch: null cloud array"); return PR_ERR_INVALID; }
         for (uint32_t i = 0; i < n_clouds; ++i) {                 // count == 0 -> identity, fitness 0, rmse 0 (icp.cu:183), like any empty cloud
@@ -366,10 +388,6 @@ int pr_icp_batch(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_c
     }
     // the hypothesis index is the y dimension of every launch of the loop (65 535 at most): longer lists run in pieces, one after the other
     // (the clouds are independent of each other, so the pieces are)
-#ifndef PR_MAX_CLOUDS_PER_RUN
-#define PR_MAX_CLOUDS_PER_RUN 32768                               // (a larger value in an experiment build exercises the launchers' own split)
-#endif
-    constexpr uint32_t kMaxCloudsPerRun = PR_MAX_CLOUDS_PER_RUN;
     for (uint32_t c0 = 0; c0 < n_clouds; c0 += kMaxCloudsPerRun) {
         const uint32_t nc = std::min(kMaxCloudsPerRun, n_clouds - c0);
         PR_TRY(icp_drive(clouds_dev, start.data() + c0, count.data() + c0, nc, sc, crit, results_host + c0, nullptr));
@@ -387,6 +405,19 @@ int pr_icp_nn(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_nn *scene, p
 {
     const uint32_t off[2] = { 0, n_points };
     return pr_icp_batch(cloud_dev, off, 1, PR_SCENE_NN, scene, crit, result_out);
+}
+
+// Audit entry: the 29 sums of every pass of the calling thread's NEXT synchronous ICP call (pr_icp_batch / pr_icp_proj / pr_icp_nn / pr_refine_batch[_roi]), as
+// the host-solve loop received them -- solve_one copies the row of hypothesis i at iteration it to rows_host[(it * n_hyp + i) * 29 ..] right before
+// pose_iteration_host consumes it, whichever way the sums came (pinned-memory stores of the pass tail, finalize launch + copy, flag polling or stream
+// wait, any pose grouping).  Rows of skipped or finished hypotheses are left alone.  NULL disarms.  Host code only: no device needed to arm.
+int pr_debug_trace_sums(float *rows_host, uint32_t n_hyp, uint32_t n_passes)
+{
+    tl_sums_trace.armed = SumsTrace();
+    if (!rows_host) return PR_OK;
+    if (n_hyp == 0 || n_passes == 0) { set_error("pr_debug_trace_sums: n_hyp and n_passes must be positive"); return PR_ERR_INVALID; }
+    tl_sums_trace.armed = SumsTrace{ rows_host, n_hyp, n_passes };
+    return PR_OK;
 }
 
 // Audit entry: what ONE correspondence pass contributes, point by point (29 floats each: the 21 upper-triangle products of J J^T row by

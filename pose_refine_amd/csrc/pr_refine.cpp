@@ -1108,7 +1108,7 @@ int refine_submit(Slot &sl, const RefineJob &job, const pr_mat4 *poses_host, uin
     // (an instrumented kd-tree run stays synchronous; large frames: the asynchronous path sizes its sub-batches to its workspace bound)
     const bool async_ok = P > 0 && opt.solve_mode == PR_SOLVE_DEVICE && opt.raster_mode == 0 && (job.scene_kind != PR_SCENE_NN || !opt.nn_count)
                           && (opt.profile == 0 || opt.profile == 3 || (opt.profile == 2 && !sample_call));
-    if (!async_ok && P > 0 && opt.solve_mode == PR_SOLVE_HOST && opt.host_worker && opt.profile == 0 && !opt.nn_count) {
+    if (!async_ok && P > 0 && opt.solve_mode == PR_SOLVE_HOST && opt.host_worker && opt.profile == 0 && !opt.nn_count && !tl_sums_trace.active.rows) {   // (a traced batch runs on the thread that armed the recorder)
         // host solve, nothing to time: the batch goes to the slot's helper thread (see SlotWorker) and this call returns
         PR_TRY(slot_worker_post(sl, job, poses_host, P, results_host, sizes_host));
         sl.pending = true; sl.delivered = false; sl.worker_job = true;
@@ -1355,9 +1355,15 @@ int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat
                         const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_criteria crit, pr_roi roi,
                         pr_result *results_host, uint32_t *cloud_sizes_host)
 {
+    TraceScope traced;                                            // (pr_debug_trace_sums: this call and no other)
     PR_ENTER();
     if (!results_host) { set_error("pr_refine_batch: results_host is null"); return PR_ERR_INVALID; }
     if (n_poses == 0) return PR_OK;
+    PR_TRY(sums_trace_admits("pr_refine_batch", n_poses, crit));    // (before the render is launched; icp_drive asks again)
+    if (tl_sums_trace.active.rows && n_poses > depth_chunk((size_t)width * height, n_poses)) {   // (rows are indexed within one icp_drive run)
+        set_error("pr_refine_batch: pr_debug_trace_sums records batches that render as one chunk; %u hypotheses at this frame size do not", n_poses);
+        return PR_ERR_INVALID;
+    }
     const int slot = free_slot();
     if (slot < 0) { set_error("pr_refine_batch: both asynchronous slots hold unfinished batches (pr_refine_wait one of them first)"); return PR_ERR_INVALID; }
     RefineJob job;

@@ -568,6 +568,21 @@ int device_solve_loop(const Lanes &lanes, uint32_t n_groups, prk::IcpBatch b, ui
 }
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
               pr_criteria crit, pr_result *results_host, pr_result *results_dev);
+// ---- audit recorder of the host-solve loop's sums (pr_debug_trace_sums, pr_icp.cpp) ---------------------------------
+// Per host thread, hence for the context that thread is bound to: `armed` waits for the thread's next synchronous ICP call, whose
+// entry point opens a TraceScope -- the recorder becomes `active` for exactly that call and is gone when it returns, error or
+// not.  icp_drive reads `active` only; a traced fused batch stays on the caller's thread (refine_submit).
+struct SumsTrace { float *rows = nullptr; uint32_t n_hyp = 0, n_passes = 0; };
+struct SumsTraceState { SumsTrace armed, active; };
+extern thread_local SumsTraceState tl_sums_trace;
+struct TraceScope {
+    TraceScope() { tl_sums_trace.active = tl_sums_trace.armed; tl_sums_trace.armed = SumsTrace(); }
+    ~TraceScope() { tl_sums_trace.active = SumsTrace(); }
+    TraceScope(const TraceScope &) = delete;
+    TraceScope &operator=(const TraceScope &) = delete;
+};
+// with a recorder active: does it fit a batch of P hypotheses under crit?  (PR_ERR_INVALID with a message if not; PR_OK without a recorder)
+int sums_trace_admits(const char *fn, uint32_t P, const pr_criteria &crit);
 void drain_all_slots();
 // a write through the library into caller-owned device memory: logged for the caches (WriteLog) and ordered BEHIND every batch of this context that is still
 // in flight and reads the range as part of its scene, mesh or result block (a scene object re-initialised per frame keeps its arrays, so the

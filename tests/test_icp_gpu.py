@@ -104,6 +104,9 @@ def test_icp_degenerate_clouds(gpu, scenario, gscenes):
     # unaligned cloud starts)
     cl = scenario["cloud"]
     parts = [cl[:1], cl[:0], cl[:4099], cl[5:2054], cl]
+    # the first ~4100 points of the cloud project off the scene (0 inliers): the same shapes once more, taken where the scene is
+    scene_parts = [cl[12001:12002], cl[12001:16100], cl[12006:14055]]
+    parts += scene_parts
     offs = np.cumsum([0] + [len(p) for p in parts]).astype(np.uint32)
     dev = api.DeviceVector.from_host(np.concatenate(parts).reshape(-1))
     crit = (0.0, 0.0, 5)
@@ -112,7 +115,10 @@ def test_icp_degenerate_clouds(gpu, scenario, gscenes):
     for i, p in enumerate(parts):
         o, _, _, _ = O.icp(p, scenario["proj_scene"], crit, O.SUM_CANONICAL, ppb)
         assert res[i]["fitness"] == o["fitness"], i
+        assert res[i]["inlier_rmse"] == o["inlier_rmse"], i
         assert np.allclose(res[i]["T"], o["T"], rtol=0, atol=TOL_T), i
+        if i >= len(parts) - len(scene_parts):
+            assert inliers(o["fitness"], len(p)) > 0, i          # never again compared at zero inliers
 
 
 @pytest.mark.device_solve

@@ -639,24 +639,7 @@ def score_poses(tris, poses, width: int, height: int, proj, scene_depth, tau_mm:
     depth (mm).  ``scene_depth`` is a DeviceVector of ``width * height`` int32 or uint16 values, or a host (height, width) array of
     either dtype, which is uploaded for the call.  Returns SCORE[P]: visible / inlier / occluded / violation / missing pixel counts and
     the exact sum of |r - s| over the inliers."""
-    td = _tris_dev(tris)
-    poses = _f32(poses, (-1, 16))
-    pj = _f32(proj, -1)
-    if isinstance(scene_depth, DeviceVector):
-        sd = scene_depth
-    else:
-        arr = np.ascontiguousarray(scene_depth)
-        if arr.dtype not in (np.uint16, np.int32):
-            raise ValueError("scene depth must be CV_16U or CV_32S")
-        sd = DeviceVector.from_host(arr.reshape(-1))
-    if sd.dtype not in (np.uint16, np.int32):
-        raise ValueError("scene depth must be CV_16U or CV_32S")
-    if sd.size() != width * height:
-        raise ValueError(f"scene depth holds {sd.size()} values, expected {width} x {height}")
-    out = np.zeros(len(poses), SCORE)
-    check(_lib.load().pr_score_poses(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                     sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out)))
-    return out
+    return _score_poses(_one_mesh(tris, poses), width, height, proj, scene_depth, tau_mm, roi)
 
 
 def refined_poses(records, poses) -> np.ndarray:
@@ -831,16 +814,41 @@ def _scene_depth_dev(scene_depth, width: int, height: int) -> DeviceVector:
     return sd
 
 
+# The scoring calls come as pairs, one mesh or a mixed batch, that differ in their leading C arguments only.  A "mesh" below is what
+# _one_mesh / _mesh_batch return: (suffix of the entry point's name, its leading arguments, the poses as float32[P, 16], what those point into).
+def _one_mesh(tris, poses):
+    td = _tris_dev(tris)
+    return "", (td.data(), td.size() // 9), _f32(poses, (-1, 16)), td
+
+
+def _mesh_batch(meshes, mesh_index, poses):
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    return "_multi", (table, len(devs), ptr(idx)), poses, (devs, idx)
+
+
+def _score_call(name: str, mesh, width: int, height: int, proj, scene_depth, tau_mm: int, roi):
+    """(``name`` or ``name_multi`` with the arguments every scoring entry point shares bound -- the caller adds those of its kind --, the number of poses)"""
+    suffix, lead, poses, alive = mesh
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    fn = getattr(_lib.load(), name + suffix)
+
+    def call(*outputs, _alive=(alive, poses, pj, sd)):
+        check(fn(*lead, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi), sd.data(), int(sd.dtype == np.int32), int(tau_mm), *outputs))
+    return call, len(poses)
+
+
+def _score_poses(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, roi) -> np.ndarray:
+    call, n = _score_call("pr_score_poses", mesh, width, height, proj, scene_depth, tau_mm, roi)
+    out = np.zeros(n, SCORE)
+    call(ptr(out))
+    return out
+
+
 def score_poses_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int,
                       roi: Sequence[int] = (0, 0, 0, 0)) -> np.ndarray:
     """``pr_score_poses_multi``: ``score_poses`` for a batch whose pose i uses ``meshes[mesh_index[i]]``.  SCORE[P] in pose order."""
-    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
-    pj = _f32(proj, -1)
-    sd = _scene_depth_dev(scene_depth, width, height)
-    out = np.zeros(len(poses), SCORE)
-    check(_lib.load().pr_score_poses_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                           sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out)))
-    return out
+    return _score_poses(_mesh_batch(meshes, mesh_index, poses), width, height, proj, scene_depth, tau_mm, roi)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -849,33 +857,25 @@ def score_poses_multi(meshes, mesh_index, poses, width: int, height: int, proj, 
 OVERLAP_MAX_POSES = 4096                # PR_OVERLAP_MAX_POSES
 
 
+def _score_overlap(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, roi):
+    call, n = _score_call("pr_score_overlap", mesh, width, height, proj, scene_depth, tau_mm, roi)
+    out, ov = np.zeros(n, SCORE), np.zeros((n, n), np.uint32)
+    call(ptr(out), ptr(ov))
+    return out, ov
+
+
 def score_overlap(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, roi: Sequence[int] = (0, 0, 0, 0)):
     """``pr_score_overlap``: ``score_poses`` plus the matrix of shared inlier pixels.  Returns (SCORE[P], uint32[P, P]): the records are
     ``score_poses``' bytes, ``overlap[i, j]`` counts the frame pixels that are inliers of both i and j (symmetric; the diagonal is
     ``scores["inlier"]``).  At most ``OVERLAP_MAX_POSES`` hypotheses per call."""
-    td = _tris_dev(tris)
-    poses = _f32(poses, (-1, 16))
-    pj = _f32(proj, -1)
-    sd = _scene_depth_dev(scene_depth, width, height)
-    out = np.zeros(len(poses), SCORE)
-    ov = np.zeros((len(poses), len(poses)), np.uint32)
-    check(_lib.load().pr_score_overlap(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                       sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out), ptr(ov)))
-    return out, ov
+    return _score_overlap(_one_mesh(tris, poses), width, height, proj, scene_depth, tau_mm, roi)
 
 
 def score_overlap_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int,
                         roi: Sequence[int] = (0, 0, 0, 0)):
     """``pr_score_overlap_multi``: ``score_overlap`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; hypotheses of different
     meshes are compared like any other pair.  (SCORE[P], uint32[P, P]) in pose order."""
-    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
-    pj = _f32(proj, -1)
-    sd = _scene_depth_dev(scene_depth, width, height)
-    out = np.zeros(len(poses), SCORE)
-    ov = np.zeros((len(poses), len(poses)), np.uint32)
-    check(_lib.load().pr_score_overlap_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                             sd.data(), int(sd.dtype == np.int32), int(tau_mm), ptr(out), ptr(ov)))
-    return out, ov
+    return _score_overlap(_mesh_batch(meshes, mesh_index, poses), width, height, proj, scene_depth, tau_mm, roi)
 
 
 def select_greedy(order, overlap, shared_num: int, shared_den: int) -> np.ndarray:
@@ -931,40 +931,28 @@ def _edge_dist_dev(edge_dist, width: int, height: int) -> DeviceVector:
     return edge_dist
 
 
+def _score_contours(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, jump_mm: int, edge_dist, roi, want_overlap: bool):
+    call, n = _score_call("pr_score_contours", mesh, width, height, proj, scene_depth, tau_mm, roi)
+    ed = _edge_dist_dev(edge_dist, width, height)
+    out, con = np.zeros(n, SCORE), np.zeros(n, CONTOUR)
+    ov = np.zeros((n, n), np.uint32) if want_overlap else None
+    call(int(jump_mm), ed.data(), ptr(out), ptr(con), ptr(ov) if want_overlap else None)
+    return (out, con, ov) if want_overlap else (out, con)
+
+
 def score_contours(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, jump_mm: int, edge_dist,
                    roi: Sequence[int] = (0, 0, 0, 0), want_overlap: bool = False):
     """``pr_score_contours``: one render per pose serves ``score_poses``' records, the contour records and, with ``want_overlap``,
     ``score_overlap``'s matrix.  ``edge_dist`` is ``scene_edge_distance``'s result for the same frame.  Returns (SCORE[P], CONTOUR[P]) or
     (SCORE[P], CONTOUR[P], uint32[P, P]): per hypothesis the edge pixels of its render (``contour``), those within the distance image's
     radius of a scene edge (``hit``, with ``dist_sum`` the sum of their distances), those behind scene surface (``occluded``), the rest (``miss``)."""
-    td = _tris_dev(tris)
-    poses = _f32(poses, (-1, 16))
-    pj = _f32(proj, -1)
-    sd = _scene_depth_dev(scene_depth, width, height)
-    ed = _edge_dist_dev(edge_dist, width, height)
-    out = np.zeros(len(poses), SCORE)
-    con = np.zeros(len(poses), CONTOUR)
-    ov = np.zeros((len(poses), len(poses)), np.uint32) if want_overlap else None
-    check(_lib.load().pr_score_contours(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                        sd.data(), int(sd.dtype == np.int32), int(tau_mm), int(jump_mm), ed.data(), ptr(out), ptr(con),
-                                        ptr(ov) if want_overlap else None))
-    return (out, con, ov) if want_overlap else (out, con)
+    return _score_contours(_one_mesh(tris, poses), width, height, proj, scene_depth, tau_mm, jump_mm, edge_dist, roi, want_overlap)
 
 
 def score_contours_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int, jump_mm: int, edge_dist,
                          roi: Sequence[int] = (0, 0, 0, 0), want_overlap: bool = False):
     """``pr_score_contours_multi``: ``score_contours`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; everything in pose order."""
-    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
-    pj = _f32(proj, -1)
-    sd = _scene_depth_dev(scene_depth, width, height)
-    ed = _edge_dist_dev(edge_dist, width, height)
-    out = np.zeros(len(poses), SCORE)
-    con = np.zeros(len(poses), CONTOUR)
-    ov = np.zeros((len(poses), len(poses)), np.uint32) if want_overlap else None
-    check(_lib.load().pr_score_contours_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                              sd.data(), int(sd.dtype == np.int32), int(tau_mm), int(jump_mm), ed.data(), ptr(out), ptr(con),
-                                              ptr(ov) if want_overlap else None))
-    return (out, con, ov) if want_overlap else (out, con)
+    return _score_contours(_mesh_batch(meshes, mesh_index, poses), width, height, proj, scene_depth, tau_mm, jump_mm, edge_dist, roi, want_overlap)
 
 
 def contour_fraction(contours) -> np.ndarray:
@@ -985,11 +973,13 @@ def filter_by_contour(order, contours, min_fraction: float) -> np.ndarray:
 # ------------------------------------------------------------------------------------------------
 # composition: the detections of a frame taken together
 # ------------------------------------------------------------------------------------------------
-def _compose_outputs(n_poses: int, width: int, height: int, want_labels: bool, want_depth: bool):
-    on = n_poses > 0                                                # (a call without hypotheses writes nothing: no frames then)
-    labels = DeviceVector(width * height, np.uint16) if want_labels and on else None
-    depth = DeviceVector(width * height, np.int32) if want_depth and on else None
-    return labels, depth, np.zeros(n_poses, SCORE), np.zeros(n_poses, VISIBLE), np.zeros(1, FRAME)
+def _compose_detections(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, roi, want_labels: bool, want_depth: bool):
+    call, n = _score_call("pr_compose_detections", mesh, width, height, proj, scene_depth, tau_mm, roi)
+    labels = DeviceVector(width * height, np.uint16) if want_labels and n else None
+    depth = DeviceVector(width * height, np.int32) if want_depth and n else None    # (a call without hypotheses writes nothing: no frames then)
+    out, vis, frame = np.zeros(n, SCORE), np.zeros(n, VISIBLE), np.zeros(1, FRAME)
+    call(labels.data() if labels else None, depth.data() if depth else None, ptr(out), ptr(vis), ptr(frame))
+    return labels, depth, out, vis, frame[0]
 
 
 def compose_detections(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, roi: Sequence[int] = (0, 0, 0, 0),
@@ -1000,29 +990,14 @@ def compose_detections(tris, poses, width: int, height: int, proj, scene_depth, 
     front depth or 0 (each None when not wanted, or when there are no poses); ``scores`` = ``score_poses``' bytes; ``visible`` =
     VISIBLE[P], the pixels every hypothesis owns by the four tests; ``frame`` = one FRAME record of the frame against the composite.
     At most ``COMPOSE_MAX_POSES`` hypotheses per call."""
-    td = _tris_dev(tris)
-    poses = _f32(poses, (-1, 16))
-    pj = _f32(proj, -1)
-    sd = _scene_depth_dev(scene_depth, width, height)
-    labels, depth, out, vis, frame = _compose_outputs(len(poses), width, height, want_labels, want_depth)
-    check(_lib.load().pr_compose_detections(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                            sd.data(), int(sd.dtype == np.int32), int(tau_mm), labels.data() if labels else None,
-                                            depth.data() if depth else None, ptr(out), ptr(vis), ptr(frame)))
-    return labels, depth, out, vis, frame[0]
+    return _compose_detections(_one_mesh(tris, poses), width, height, proj, scene_depth, tau_mm, roi, want_labels, want_depth)
 
 
 def compose_detections_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int,
                              roi: Sequence[int] = (0, 0, 0, 0), want_labels: bool = True, want_depth: bool = True):
     """``pr_compose_detections_multi``: ``compose_detections`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; labels, ties and
     records in pose order."""
-    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
-    pj = _f32(proj, -1)
-    sd = _scene_depth_dev(scene_depth, width, height)
-    labels, depth, out, vis, frame = _compose_outputs(len(poses), width, height, want_labels, want_depth)
-    check(_lib.load().pr_compose_detections_multi(table, len(devs), ptr(idx), ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi),
-                                                  sd.data(), int(sd.dtype == np.int32), int(tau_mm), labels.data() if labels else None,
-                                                  depth.data() if depth else None, ptr(out), ptr(vis), ptr(frame)))
-    return labels, depth, out, vis, frame[0]
+    return _compose_detections(_mesh_batch(meshes, mesh_index, poses), width, height, proj, scene_depth, tau_mm, roi, want_labels, want_depth)
 
 
 def visible_fraction(scores, visible) -> np.ndarray:

@@ -1,6 +1,6 @@
 // compose.hip -- the accepted hypotheses of a frame taken together: which one is in front at every pixel, what each one keeps, what the set explains
 // gfx950 (CDNA4, wave64); compiled with -ffp-contract=off: every per-element value is bit-identical to the CPU restatement.
-#include "pr_launch.h"
+#include "score_walk.h"
 
 namespace prk {
 
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void compose_tile_kernel(const int32_t *__rest
 #pragma unroll
                 for (uint32_t r = 0; r < 4; ++r) {
                     const int32_t v = d[u][r];
-                    const unsigned long long key = (v > 0 && v != INT_MAX) ? ((unsigned long long)(uint32_t)v << 32 | who[u]) : kComposeNoKey;
+                    const unsigned long long key = rendered(v) ? ((unsigned long long)(uint32_t)v << 32 | who[u]) : kComposeNoKey;
                     best[r] = key < best[r] ? key : best[r];
                 }
         }
@@ -86,30 +86,19 @@ __global__ __launch_bounds__(256) void compose_tile_kernel(const int32_t *__rest
     }
 }
 
-// the four tests of pr_pose_score for a rendered depth d > 0 against the scene value s: 0 inlier, 1 occluded, 2 violation, 3 missing
-__device__ __forceinline__ uint32_t compose_class(int32_t d, int32_t s, int64_t tau)
-{
-    if (s <= 0) return 3;
-    const int64_t diff = (int64_t)d - (int64_t)s;                     // 64 bits: no overflow for any int32 pair
-    return diff > tau ? 1u : (diff < -tau ? 2u : 0u);
-}
-
 // What every hypothesis keeps.  score_box_kernel's grid and shape over the boxes of ALL hypotheses of the call (blockIdx.y = position in the
 // grouped batch): the key frame and the scene inside the box, a pixel counts when the key's index is this hypothesis' (the caller's index:
-// index_of, or the position itself), by the four tests.  Registers, wave_sum_u32, LDS over the four wavefronts, one integer atomic per counter
+// index_of, or the position itself), by the four tests (depth_class).  Registers, block_totals, one integer atomic per counter
 // and workgroup into records[8 * caller's index] (pr_pose_visible words: owned, owned_inlier, owned_occluded, owned_violation, owned_missing).
 template <typename SceneT>
 __global__ __launch_bounds__(256) void compose_count_kernel(const unsigned long long *__restrict__ keys, const int4 *__restrict__ bbox, const uint32_t *__restrict__ index_of,
                                                             uint32_t width, uint32_t height, const SceneT *__restrict__ scene, int32_t tau, uint32_t *__restrict__ records)
 {
-    __shared__ uint32_t part[4][5];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int4 bb = bbox[blockIdx.y];
-    const int r_lo = (int)height - 1 - bb.w, r_hi = (int)height - 1 - bb.y;
-    const int blk0 = (int)(blockIdx.x * kBoxRowsPerBlock);
-    if (bb.x > bb.z || bb.x < 0 || bb.z >= (int)width || r_lo < 0 || r_lo > r_hi || blk0 > r_hi || blk0 + (int)kBoxRowsPerBlock - 1 < r_lo) return;   // the whole workgroup, before any barrier
+    const uint32_t lane = threadIdx.x & 63;
+    BoxBlock blk;
+    if (!box_block(bbox, height, blk) || blk.bb.x < 0 || blk.bb.z >= (int)width || blk.r_lo < 0) return;   // (this kernel reads the frame, not the box: clipped to it)
+    const auto [bb, r_lo, r_hi, row0] = blk;
     const uint32_t me = index_of ? index_of[blockIdx.y] : blockIdx.y;
-    const uint32_t row0 = (uint32_t)blk0 + wave * 4;
     const int64_t t = tau;
     uint32_t cnt[5] = { 0, 0, 0, 0, 0 };                              // owned, then its four classes
     for (int x0 = bb.x; x0 <= bb.z; x0 += 128) {
@@ -133,23 +122,14 @@ __global__ __launch_bounds__(256) void compose_count_kernel(const unsigned long 
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 if ((uint32_t)kv[r][j] != me) continue;               // somebody else's pixel, or nobody's
-                const uint32_t c = compose_class((int32_t)(kv[r][j] >> 32), sv[r][j], t);
+                const uint32_t c = depth_class((int32_t)(kv[r][j] >> 32), sv[r][j], t);
                 ++cnt[0];
 #pragma unroll
                 for (uint32_t k = 0; k < 4; ++k) cnt[1 + k] += c == k;
             }
     }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint32_t w = wave_sum_u32(cnt[k]);
-        if (lane == 0) part[wave][k] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const uint32_t k = threadIdx.x;
-        const uint32_t sum = part[0][k] + part[1][k] + part[2][k] + part[3][k];
-        if (sum) atomicAdd(records + (size_t)me * 8 + k, sum);
-    }
+    const uint32_t sum = block_totals(cnt);
+    if (sum) atomicAdd(records + (size_t)me * 8 + threadIdx.x, sum);      // (threads 0..4: the others' totals are 0)
 }
 
 // Labels, front depth and the frame record: one pass over the frame, a workgroup per 256 columns x kEmitRows rows, lanes along a row, the rows'
@@ -161,8 +141,6 @@ __global__ __launch_bounds__(256) void compose_emit_kernel(const unsigned long l
                                                            const SceneT *__restrict__ scene, int32_t tau, uint16_t *__restrict__ labels, int32_t *__restrict__ depth_out,
                                                            uint32_t *__restrict__ frame)
 {
-    __shared__ uint32_t part[4][7];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t t = tau;
     const uint32_t x = blockIdx.x * 256 + threadIdx.x;
     uint32_t cnt[7] = { 0, 0, 0, 0, 0, 0, 0 };
@@ -190,7 +168,7 @@ __global__ __launch_bounds__(256) void compose_emit_kernel(const unsigned long l
         cnt[0] += inside;
         cnt[1] += inside && s > 0;
         if (drawn) {
-            const uint32_t c = compose_class((int32_t)(key >> 32), s, t);
+            const uint32_t c = depth_class((int32_t)(key >> 32), s, t);
             cnt[2] += 1;
             cnt[3] += c == 0;                                         // explained
             cnt[4] += c == 2;                                         // in_front: the composite lies before the measurement by more than tau (`violation`)
@@ -198,17 +176,8 @@ __global__ __launch_bounds__(256) void compose_emit_kernel(const unsigned long l
             cnt[6] += c == 3;                                         // unmeasured
         }
     }
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const uint32_t w = wave_sum_u32(cnt[k]);
-        if (lane == 0) part[wave][k] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const uint32_t k = threadIdx.x;
-        const uint32_t sum = part[0][k] + part[1][k] + part[2][k] + part[3][k];
-        if (sum) atomicAdd(frame + k, sum);
-    }
+    const uint32_t sum = block_totals(cnt);
+    if (sum) atomicAdd(frame + threadIdx.x, sum);                     // (threads 0..6: the others' totals are 0)
 }
 
 hipError_t launch_compose_tiles(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
@@ -224,10 +193,7 @@ hipError_t launch_compose_counts(const unsigned long long *keys, const int4 *bbo
 {
     if (n_poses == 0 || n_poses > PR_COMPOSE_MAX_POSES) return n_poses ? hipErrorInvalidValue : hipSuccess;      // grid.y is limited to 65535: one launch
     const dim3 grid((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, n_poses);
-    if (scene_i32)
-        hipLaunchKernelGGL(compose_count_kernel<int32_t>, grid, dim3(256), 0, s, keys, bbox, index_of, width, height, static_cast<const int32_t *>(scene), tau, records);
-    else
-        hipLaunchKernelGGL(compose_count_kernel<uint16_t>, grid, dim3(256), 0, s, keys, bbox, index_of, width, height, static_cast<const uint16_t *>(scene), tau, records);
+    with_scene(scene, scene_i32, [&](auto *sc) { hipLaunchKernelGGL(compose_count_kernel, grid, dim3(256), 0, s, keys, bbox, index_of, width, height, sc, tau, records); });
     return hipGetLastError();
 }
 
@@ -235,10 +201,7 @@ hipError_t launch_compose_emit(const unsigned long long *keys, uint32_t width, u
                                uint16_t *labels, int32_t *depth_out, uint32_t *frame, hipStream_t s)
 {
     const dim3 grid((width + 255) / 256, (height + kEmitRows - 1) / kEmitRows);
-    if (scene_i32)
-        hipLaunchKernelGGL(compose_emit_kernel<int32_t>, grid, dim3(256), 0, s, keys, width, height, window, static_cast<const int32_t *>(scene), tau, labels, depth_out, frame);
-    else
-        hipLaunchKernelGGL(compose_emit_kernel<uint16_t>, grid, dim3(256), 0, s, keys, width, height, window, static_cast<const uint16_t *>(scene), tau, labels, depth_out, frame);
+    with_scene(scene, scene_i32, [&](auto *sc) { hipLaunchKernelGGL(compose_emit_kernel, grid, dim3(256), 0, s, keys, width, height, window, sc, tau, labels, depth_out, frame); });
     return hipGetLastError();
 }
 

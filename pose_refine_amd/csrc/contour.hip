@@ -1,7 +1,7 @@
 // contour.hip -- depth-edge (contour) agreement: the scene's edge pixels with their chessboard distance transform, made once per frame, and the
 // edge pixels of every rendered box of a batch (launch_render_boxes) counted against it
 // gfx950 (CDNA4, wave64); compiled with -ffp-contract=off like the rest (integer arithmetic only: differences in 64 bits).
-#include "pr_launch.h"
+#include "score_walk.h"
 
 namespace prk {
 
@@ -76,10 +76,7 @@ hipError_t launch_scene_edge_distance(const void *scene, bool scene_i32, uint32_
                                       unsigned long long *bits, uint8_t *row_dist, uint8_t *dist, hipStream_t s)
 {
     const uint32_t wpr = overlap_words_per_row(width), cells = height * wpr;       // frames hold at most 2^24 pixels
-    if (scene_i32)
-        hipLaunchKernelGGL(scene_edge_kernel<int32_t>, dim3((cells + 3) / 4), dim3(256), 0, s, static_cast<const int32_t *>(scene), width, height, jump_mm, bits, wpr);
-    else
-        hipLaunchKernelGGL(scene_edge_kernel<uint16_t>, dim3((cells + 3) / 4), dim3(256), 0, s, static_cast<const uint16_t *>(scene), width, height, jump_mm, bits, wpr);
+    with_scene(scene, scene_i32, [&](auto *sc) { hipLaunchKernelGGL(scene_edge_kernel, dim3((cells + 3) / 4), dim3(256), 0, s, sc, width, height, jump_mm, bits, wpr); });
     const dim3 grid((width + 255) / 256, height);                   // height <= 8192
     hipLaunchKernelGGL(edge_row_dist_kernel, grid, dim3(256), 0, s, bits, width, height, wpr, radius, row_dist);
     hipLaunchKernelGGL(edge_col_dist_kernel, grid, dim3(256), 0, s, row_dist, width, height, radius, dist);
@@ -92,24 +89,21 @@ hipError_t launch_scene_edge_distance(const void *scene, bool scene_i32, uint32_
 // neighbours come from the neighbouring lanes, and one more load per row, by lanes 0 and 63 only, fetches the two columns beside the strip.
 // `win` {x0, row0, x1, row1} is the image the render lives in (the frame, or the ROI window) in image coordinates: a neighbour outside it
 // is ignored, one inside it but outside the packed box is empty by construction.  Only contour pixels (a few per cent) read the scene
-// and the distance image, which stay in L2 and are shared by every hypothesis.  Counts per lane in registers, a wave sum, a sum over the
-// four wavefronts in LDS, one integer atomic per counter and workgroup: exact and independent of chunking and batch composition.
+// and the distance image, which stay in L2 and are shared by every hypothesis.  Counts per lane in registers, summed over the workgroup
+// (block_totals), one integer atomic per counter and workgroup: exact and independent of chunking and batch composition.
 // dist_sum: a workgroup covers kBoxRowsPerBlock rows x <= kMaxFrameSide columns of D <= 255, so its sum stays below 2^25 -- 32 bits per lane
 // and workgroup are enough (no low / high split as abs_err_sum needs), and only the per-hypothesis total needs the 64-bit atomic.
-constexpr uint64_t kMaxFrameSide = 8192;                          // frame_size_ok (pr_refine.cpp) refuses wider or taller frames
+constexpr uint64_t kMaxFrameSide = 8192;                          // frame_size_ok (pr_runtime.h) refuses wider or taller frames
 static_assert(kBoxRowsPerBlock * kMaxFrameSide * 255 < (1ull << 32), "contour_box_kernel: a workgroup's dist_sum must fit 32 bits");
 template <typename SceneT>
 __global__ __launch_bounds__(256) void contour_box_kernel(const int32_t *__restrict__ depth, const int4 *__restrict__ bbox, uint32_t width, uint32_t height,
                                                           const uint32_t *__restrict__ box_off, const int4 win, const SceneT *__restrict__ scene,
                                                           const uint8_t *__restrict__ edge_dist, int32_t tau, int32_t jump_mm, uint32_t *__restrict__ records)
 {
-    __shared__ uint32_t part[4][5];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int4 bb = bbox[blockIdx.y];
-    const int r_lo = (int)height - 1 - bb.w, r_hi = (int)height - 1 - bb.y;            // image rows of the box (raster rows run flipped)
-    const int blk0 = (int)(blockIdx.x * kBoxRowsPerBlock);
-    if (bb.x > bb.z || r_lo > r_hi || blk0 > r_hi || blk0 + (int)kBoxRowsPerBlock - 1 < r_lo) return;     // the whole workgroup, before any barrier
-    const int row0 = blk0 + (int)wave * 4;
+    const uint32_t lane = threadIdx.x & 63;
+    BoxBlock blk;
+    if (!box_block(bbox, height, blk)) return;
+    const auto [bb, r_lo, r_hi, row0] = blk;
     const int64_t t = tau, jump = jump_mm;
     // rows row0 - 1 .. row0 + 4: in the box (a line to load from), else inside the image (empty) or outside it (ignored) -- per wavefront
     const int32_t *line[6];
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(256) void contour_box_kernel(const int32_t *__restr
         line[k] = in_box ? box_line(const_cast<int32_t *>(depth), box_off, bb, blockIdx.y, (uint32_t)row, width, height) : depth;
         off_box[k] = in_box ? 1 : ((row >= win.y && row <= win.w) ? 0 : kNoNeighbour);
     }
-    auto value = [](int32_t d) { return (d > 0 && d != INT_MAX) ? d : 0; };            // nothing drawn -> empty
+    auto value = [](int32_t d) { return rendered(d) ? d : 0; };                         // nothing drawn -> empty
     uint32_t con = 0, hit = 0, occ = 0, mis = 0, dsum = 0;
     for (int x0 = bb.x; x0 <= bb.z; x0 += 64) {
         const int x = x0 + (int)lane;
@@ -146,43 +140,25 @@ __global__ __launch_bounds__(256) void contour_box_kernel(const int32_t *__restr
             const int32_t s = (int32_t)scene[px];
             const uint32_t D = edge_dist[px];
             ++con;
-            if (s > 0 && (int64_t)c - (int64_t)s > t) ++occ;        // scene surface in front of the contour: no edge can be expected
+            if (depth_class(c, s, t) == 1) ++occ;                   // scene surface in front of the contour: no edge can be expected
             else if (D != 255) { ++hit; dsum += D; }
             else ++mis;
         }
     }
     const uint32_t cnt[5] = { con, hit, occ, mis, dsum };
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint32_t w = wave_sum_u32(cnt[k]);
-        if (lane == 0) part[wave][k] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const uint32_t k = threadIdx.x;
-        const uint32_t sum = part[0][k] + part[1][k] + part[2][k] + part[3][k];
-        uint32_t *rec = records + (size_t)blockIdx.y * 8;
-        if (sum && k < 4) atomicAdd(rec + k, sum);
-        else if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(rec + 6), (unsigned long long)sum);
-    }
+    const uint32_t sum = block_totals(cnt), k = threadIdx.x;
+    uint32_t *rec = records + (size_t)blockIdx.y * 8;
+    if (sum && k < 4) atomicAdd(rec + k, sum);
+    else if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(rec + 6), (unsigned long long)sum);      // (k == 4: the others' totals are 0)
 }
 
 hipError_t launch_contour_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
                                 const void *scene, bool scene_i32, const uint8_t *edge_dist, int32_t tau, int32_t jump_mm, uint32_t *records, hipStream_t s)
 {
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {                // grid.y is limited to 65535 (launch_score_boxes splits the same way)
-        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
-        const int32_t *d = box_off ? depth : depth + (size_t)p0 * width * height;
-        const uint32_t *bo = box_off ? box_off + p0 : nullptr;
-        const dim3 grid((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np);
-        if (scene_i32)
-            hipLaunchKernelGGL(contour_box_kernel<int32_t>, grid, dim3(256), 0, s, d, bbox + p0, width, height, bo, window, static_cast<const int32_t *>(scene),
-                               edge_dist, tau, jump_mm, records + (size_t)p0 * 8);
-        else
-            hipLaunchKernelGGL(contour_box_kernel<uint16_t>, grid, dim3(256), 0, s, d, bbox + p0, width, height, bo, window, static_cast<const uint16_t *>(scene),
-                               edge_dist, tau, jump_mm, records + (size_t)p0 * 8);
-    }
-    return hipGetLastError();
+    return for_box_launches(depth, box_off, n_poses, width, height, scene, scene_i32, [&](const BoxLaunch &b, auto *sc) {
+        hipLaunchKernelGGL(contour_box_kernel, b.grid, dim3(256), 0, s, b.depth, bbox + b.p0, width, height, b.box_off, window, sc, edge_dist, tau, jump_mm,
+                           records + (size_t)b.p0 * 8);
+    });
 }
 
 }  // namespace prk

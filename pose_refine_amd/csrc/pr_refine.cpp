@@ -336,43 +336,41 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
 // refine_core's render (staged poses, model box, per-pose pixel boxes packed one behind the other) followed by one kernel that compares every
 // rendered box pixel with the scene frame.  Everything runs on the context's own stream and workspaces, which no asynchronous slot owns, so a
 // batch pending on a slot is neither waited for nor disturbed.  The scene is read as it is on every call: nothing derived from it is kept.
-// overlap_host (pr_score_overlap; null: scores only): the P x P matrix of shared inlier pixels, in the order of poses_host.  Every chunk also leaves
+// A block of records back to the caller: queue() = a kernel's stores into the pinned block (no copy command, see read_back_words), then -- after
+// the caller's one hipStreamSynchronize for everything it queued -- deliver() copies the block's next `bytes` to where they are wanted.
+struct ReadBack {
+    const unsigned char *next = nullptr;
+    int queue(const void *dev, const PinBuf &pinned, uint32_t n_words) { next = pinned.as<unsigned char>(); HIP_TRY(prk::launch_copy_words32(dev, pinned.dev, n_words, g->stream)); return PR_OK; }
+    void deliver(void *host, size_t bytes) { std::memcpy(host, next, bytes); next += bytes; }
+};
+// One request (checked: score_request_ok; P > 0) on the hypotheses as req.poses has them: one mesh, or (req.plan) a mixed batch in its plan's order.
+// kScoreOverlap / req.overlap: the P x P matrix of shared inlier pixels, in the order of req.poses.  Every chunk also leaves
 // its hypotheses' support bits (select.hip) and pixel boxes in workspaces sized for all P -- g->depth and g->bbox belong to the next chunk as soon
 // as this one is scored -- and one launch over all pairs follows the last chunk.  The planes are dense: P x H x ceil(W / 64) words of 8 bytes.
-// ct (pr_score_contours; null: none): the contour records of the same renders against the scene's edge distance image (contour.hip), one more
+// kScoreContours: the contour records of the same renders against the scene's edge distance image (contour.hip), one more
 // kernel over every chunk's boxes right behind the score kernel; the records travel like the scores.
-// cp (pr_compose_detections; null: none): the same renders taken together (compose.hip).  One more kernel over every chunk's boxes folds them into
-// the key frame of the context -- the front-most render of every frame pixel with the CALLER's index of its hypothesis (order: grouped position ->
+// kScoreCompose: the same renders taken together (compose.hip).  One more kernel over every chunk's boxes folds them into
+// the key frame of the context -- the front-most render of every frame pixel with the CALLER's index of its hypothesis (req.order: grouped position ->
 // caller's index, null: the identity), so ties and labels need no remapping -- and every chunk leaves its pixel boxes in a workspace sized for
 // all P, as for the overlap matrix.  Behind the last chunk: the counts of what every hypothesis keeps, then one pass over the frame for the labels,
 // the front depth and the frame record.  visible is written in the caller's order whatever `order` is.
-struct ContourOut { int32_t jump; const uint8_t *edge_dist; pr_pose_contour *out; };
-struct ComposeOut { const uint32_t *order; uint16_t *labels_dev; int32_t *depth_dev; pr_pose_visible *visible; pr_frame_explained *frame; };
-int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
-               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
-               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses", const ComposeOut *cp = nullptr)
+int score_core(const ScoreRequest &req)
 {
-    if (tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)tau); return PR_ERR_INVALID; }
-    if (!proj || W == 0 || H == 0 || (P && (!poses_host || !scene_dev || !scores_host || (!src.tris && src.n_tris > 0)))) {
-        set_error("%s: bad arguments", fn); return PR_ERR_INVALID;
-    }
-    if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
-    if (!roi_ok(roi, W, H)) { set_error("%s: roi out of image", fn); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
-    if (ct && ct->jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)ct->jump); return PR_ERR_INVALID; }
-    if (ct && P && (!ct->edge_dist || !ct->out)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
-    if (cp && P && (!cp->visible || !cp->frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }
-    if (P == 0) return PR_OK;
+    const uint32_t P = req.P, W = req.W, H = req.H;
+    const int32_t tau = req.tau;
+    const bool contours = req.kind == kScoreContours, compose = req.kind == kScoreCompose;
+    const MeshSource src{ req.tris, req.n_tris, req.plan };
     static_assert(sizeof(pr_pose_visible) == sizeof(pr_pose_score) && sizeof(pr_frame_explained) == sizeof(pr_pose_score), "pr_pose_visible, pr_frame_explained: 32-byte records");
     static_assert(sizeof(pr_pose_contour) == sizeof(pr_pose_score) && offsetof(pr_pose_contour, dist_sum) == 24, "pr_pose_contour: one 32-byte record, the sum in words 6 and 7");
-    const bool has_roi = roi.width > 0 && roi.height > 0;
-    const int4 window = has_roi ? make_int4(roi.x, roi.y, roi.x + roi.width - 1, roi.y + roi.height - 1) : make_int4(0, 0, (int)W - 1, (int)H - 1);
+    const bool has_roi = req.roi.width > 0 && req.roi.height > 0;
+    const int4 window = has_roi ? make_int4(req.roi.x, req.roi.y, req.roi.x + req.roi.width - 1, req.roi.y + req.roi.height - 1) : make_int4(0, 0, (int)W - 1, (int)H - 1);
     constexpr uint32_t kWords = sizeof(pr_pose_score) / sizeof(uint32_t);
     static_assert(sizeof(pr_pose_score) == 32 && kWords == 8, "pr_pose_score: one 32-byte record");
     const size_t img = (size_t)W * H;
     const uint32_t chunk = depth_chunk(img, P);
     PR_TRY(model_boxes(src, chunk));
     const size_t plane_words = (size_t)H * prk::overlap_words_per_row(W);
-    if (overlap_host) {
+    if (req.overlap) {
         PR_TRY(g->ov_bits.ensure(sizeof(uint64_t) * plane_words * P));
         PR_TRY(g->ov_box.ensure(sizeof(int4) * P));
         PR_TRY(g->ov_mat.ensure(sizeof(uint32_t) * (size_t)P * P));
@@ -381,13 +379,13 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
     // composition: records = P x pr_pose_visible, then the frame's; the pinned block holds them and, behind them, the index table on its way in
     const size_t cmp_rec_bytes = sizeof(pr_pose_visible) * ((size_t)P + 1), cmp_idx_bytes = (sizeof(uint32_t) * (size_t)P + 15) / 16 * 16;
     uint32_t *cmp_index = nullptr;                                  // device: grouped position -> caller's index (null: the identity)
-    if (cp) {
+    if (compose) {
         PR_TRY(g->cmp_keys.ensure(sizeof(uint64_t) * img));
         PR_TRY(g->cmp_box.ensure(sizeof(int4) * P + cmp_idx_bytes));
         PR_TRY(g->cmp_rec.ensure(cmp_rec_bytes));
         PR_TRY(g->h_cmp.ensure(cmp_rec_bytes + cmp_idx_bytes));
-        if (cp->order) {
-            std::memcpy(g->h_cmp.as<unsigned char>() + cmp_rec_bytes, cp->order, sizeof(uint32_t) * P);
+        if (req.order) {
+            std::memcpy(g->h_cmp.as<unsigned char>() + cmp_rec_bytes, req.order, sizeof(uint32_t) * P);
             cmp_index = reinterpret_cast<uint32_t *>(g->cmp_box.as<int4>() + P);
             HIP_TRY(prk::launch_stage_words(g->h_cmp.dev_as<unsigned char>() + cmp_rec_bytes, cmp_index, sizeof(uint32_t) * P, g->stream));
         }
@@ -401,80 +399,58 @@ int score_core(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uin
         PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
         PR_TRY(g->scores.ensure(sizeof(pr_pose_score) * np));
         PR_TRY(g->h_scores.ensure(sizeof(pr_pose_score) * np));
-        if (ct) { PR_TRY(g->contours.ensure(sizeof(pr_pose_contour) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_pose_contour) * np)); }
+        if (contours) { PR_TRY(g->contours.ensure(sizeof(pr_pose_contour) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_pose_contour) * np)); }
         uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
         {
             SpanGuard sp(kSpanRender);
-            PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, proj, roi, box_off, /*bands=*/false));
+            PR_TRY(render_chunk(src, req.poses, p0, np, chunk, W, H, req.proj, req.roi, box_off, /*bands=*/false));
         }
         // records zeroed by a kernel and read back through the pinned array by a kernel: no memset or copy commands on this path (see refine_core)
+        ReadBack scores_back, contours_back;
         HIP_TRY(prk::launch_fill_i32(g->scores.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
-        HIP_TRY(prk::launch_score_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
+        HIP_TRY(prk::launch_score_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, req.scene, req.scene_i32, tau,
                                         g->scores.as<uint32_t>(), g->stream));
-        if (ct) {
+        if (contours) {
             HIP_TRY(prk::launch_fill_i32(g->contours.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
-            HIP_TRY(prk::launch_contour_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, scene_dev, scene_i32, ct->edge_dist, tau,
-                                              ct->jump, g->contours.as<uint32_t>(), g->stream));
-            HIP_TRY(prk::launch_copy_words32(g->contours.p, g->h_contours.dev, kWords * np, g->stream));
+            HIP_TRY(prk::launch_contour_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, req.scene, req.scene_i32, req.edge_dist, tau,
+                                              req.jump, g->contours.as<uint32_t>(), g->stream));
+            PR_TRY(contours_back.queue(g->contours.p, g->h_contours, kWords * np));
         }
-        if (overlap_host) {
-            HIP_TRY(prk::launch_support_bits(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, scene_dev, scene_i32, tau,
+        if (req.overlap) {
+            HIP_TRY(prk::launch_support_bits(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, req.scene, req.scene_i32, tau,
                                              g->ov_bits.as<unsigned long long>() + plane_words * p0, g->stream));
             HIP_TRY(prk::launch_copy_words32(g->bbox.p, g->ov_box.as<int4>() + p0, 4 * np, g->stream));
         }
-        if (cp) {
+        if (compose) {
             HIP_TRY(prk::launch_compose_tiles(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, cmp_index ? cmp_index + p0 : nullptr, p0,
                                               g->cmp_keys.as<unsigned long long>(), p0 == 0, g->stream));
             HIP_TRY(prk::launch_copy_words32(g->bbox.p, g->cmp_box.as<int4>() + p0, 4 * np, g->stream));
         }
-        HIP_TRY(prk::launch_copy_words32(g->scores.p, g->h_scores.dev, kWords * np, g->stream));
+        PR_TRY(scores_back.queue(g->scores.p, g->h_scores, kWords * np));
         HIP_TRY(hipStreamSynchronize(g->stream));
-        std::memcpy(scores_host + p0, g->h_scores.p, sizeof(pr_pose_score) * np);
-        if (ct) std::memcpy(ct->out + p0, g->h_contours.p, sizeof(pr_pose_contour) * np);
+        scores_back.deliver(req.scores + p0, sizeof(pr_pose_score) * np);
+        if (contours) contours_back.deliver(req.contours + p0, sizeof(pr_pose_contour) * np);
     }
-    if (overlap_host) {
+    if (req.overlap) {
+        ReadBack back;
         HIP_TRY(prk::launch_pair_overlap(g->ov_bits.as<unsigned long long>(), g->ov_box.as<int4>(), P, W, H, g->ov_mat.as<uint32_t>(), g->stream));
-        HIP_TRY(prk::launch_copy_words32(g->ov_mat.p, g->h_ov.dev, P * P, g->stream));
+        PR_TRY(back.queue(g->ov_mat.p, g->h_ov, P * P));
         HIP_TRY(hipStreamSynchronize(g->stream));
-        std::memcpy(overlap_host, g->h_ov.p, sizeof(uint32_t) * (size_t)P * P);
+        back.deliver(req.overlap, sizeof(uint32_t) * (size_t)P * P);
     }
-    if (cp) {
+    if (compose) {
+        ReadBack back;
         uint32_t *rec = g->cmp_rec.as<uint32_t>();
         HIP_TRY(prk::launch_fill_i32(g->cmp_rec.as<int32_t>(), cmp_rec_bytes / sizeof(int32_t), 0, g->stream));
-        HIP_TRY(prk::launch_compose_counts(g->cmp_keys.as<unsigned long long>(), g->cmp_box.as<int4>(), cmp_index, P, W, H, scene_dev, scene_i32, tau, rec, g->stream));
-        HIP_TRY(prk::launch_compose_emit(g->cmp_keys.as<unsigned long long>(), W, H, window, scene_dev, scene_i32, tau, cp->labels_dev, cp->depth_dev,
+        HIP_TRY(prk::launch_compose_counts(g->cmp_keys.as<unsigned long long>(), g->cmp_box.as<int4>(), cmp_index, P, W, H, req.scene, req.scene_i32, tau, rec, g->stream));
+        HIP_TRY(prk::launch_compose_emit(g->cmp_keys.as<unsigned long long>(), W, H, window, req.scene, req.scene_i32, tau, req.labels_dev, req.depth_dev,
                                          rec + (size_t)kWords * P, g->stream));
-        HIP_TRY(prk::launch_copy_words32(rec, g->h_cmp.dev, (uint32_t)(cmp_rec_bytes / sizeof(uint32_t)), g->stream));
+        PR_TRY(back.queue(rec, g->h_cmp, (uint32_t)(cmp_rec_bytes / sizeof(uint32_t))));
         HIP_TRY(hipStreamSynchronize(g->stream));
-        std::memcpy(cp->visible, g->h_cmp.p, sizeof(pr_pose_visible) * P);
-        std::memcpy(cp->frame, g->h_cmp.as<unsigned char>() + sizeof(pr_pose_visible) * P, sizeof(pr_frame_explained));
+        back.deliver(req.visible, sizeof(pr_pose_visible) * P);
+        back.deliver(req.frame, sizeof(pr_frame_explained));
     }
     drain_spans();
-    return PR_OK;
-}
-// pr_score_overlap's own condition, checked before anything runs
-int overlap_args_ok(const char *fn, uint32_t P, const uint32_t *overlap_host)
-{
-    if (P > PR_OVERLAP_MAX_POSES) {
-        set_error("%s: %u hypotheses, but the overlap matrix is limited to PR_OVERLAP_MAX_POSES = %u (a 64 MB matrix)", fn, P, (uint32_t)PR_OVERLAP_MAX_POSES);
-        return PR_ERR_INVALID;
-    }
-    if (P && !overlap_host) { set_error("%s: bad arguments (overlap_host is null)", fn); return PR_ERR_INVALID; }
-    return PR_OK;
-}
-int score_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
-               pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
-               const ContourOut *ct = nullptr, const char *fn = "pr_score_poses", const ComposeOut *cp = nullptr)
-{
-    return score_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, P, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, overlap_host, ct, fn, cp);
-}
-// pr_compose_detections' own conditions, checked before anything runs
-int compose_args_ok(const char *fn, uint32_t P)
-{
-    if (P > PR_COMPOSE_MAX_POSES) {
-        set_error("%s: %u hypotheses, but a label is a uint16: at most PR_COMPOSE_MAX_POSES = %u", fn, P, (uint32_t)PR_COMPOSE_MAX_POSES);
-        return PR_ERR_INVALID;
-    }
     return PR_OK;
 }
 
@@ -510,32 +486,47 @@ int refine_ordered(const RefineJob &job, const PyramidPlan *py, const pr_mat4 *p
     return PR_OK;
 }
 
-int score_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H,
-                const pr_mat4 *proj, pr_roi roi, const void *scene_dev, bool scene_i32, int32_t tau, pr_pose_score *scores_host, uint32_t *overlap_host = nullptr,
-                const ContourOut *ct = nullptr, const char *fn = "pr_score_poses_multi", const ComposeOut *cp = nullptr)
+// Every scoring entry point behind PR_ENTER: the checks, then the request as it is, or -- a mixed batch -- on the batch grouped by mesh into
+// temporaries, and the scores, contours and the matrix back to the caller's order: nothing reaches the caller's arrays unless the call succeeded
+// (the composition's records are written in the caller's order as they are: req.order).
+int score_run(const ScoreRequest &req)
 {
-    // the single-mesh call's checks first (tau, jump, frame, ROI, pointers), with no hypotheses
-    PR_TRY(score_core(MeshSource{ nullptr, 0, nullptr }, poses_host, 0, W, H, proj, roi, scene_dev, scene_i32, tau, scores_host, nullptr, ct, fn));
+    PR_TRY(score_request_ok(req));
+    const uint32_t P = req.P;
     if (P == 0) return PR_OK;
-    if (!poses_host || !scene_dev || !scores_host) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
-    if (ct && (!ct->edge_dist || !ct->out)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
-    if (cp && (!cp->visible || !cp->frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }
+    if (!req.multi) return score_core(req);
     MeshPlan pl;
-    PR_TRY(plan_meshes(fn, meshes, n_meshes, mesh_index, P, pl));
-    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
+    PR_TRY(plan_meshes(req.fn, req.meshes, req.n_meshes, req.mesh_index, P, pl));
+    const std::vector<pr_mat4> poses = grouped_poses(pl, req.poses);
     std::vector<pr_pose_score> sc(P);
-    std::vector<uint32_t> ov(overlap_host ? (size_t)P * P : 0);
-    std::vector<pr_pose_contour> cc(ct ? P : 0);
-    const ContourOut grouped{ ct ? ct->jump : 0, ct ? ct->edge_dist : nullptr, cc.data() };
-    const ComposeOut composed{ pl.order.data(), cp ? cp->labels_dev : nullptr, cp ? cp->depth_dev : nullptr, cp ? cp->visible : nullptr, cp ? cp->frame : nullptr };
-    PR_TRY(score_core(MeshSource{ nullptr, 0, &pl }, poses.data(), P, W, H, proj, roi, scene_dev, scene_i32, tau, sc.data(), overlap_host ? ov.data() : nullptr,
-                      ct ? &grouped : nullptr, fn, cp ? &composed : nullptr));
-    for (uint32_t j = 0; j < P; ++j) scores_host[pl.order[j]] = sc[j];
-    if (ct) for (uint32_t j = 0; j < P; ++j) ct->out[pl.order[j]] = cc[j];
-    if (overlap_host)                                            // rows and columns back into the caller's order
+    std::vector<uint32_t> ov(req.overlap ? (size_t)P * P : 0);
+    std::vector<pr_pose_contour> cc(req.kind == kScoreContours ? P : 0);
+    ScoreRequest grouped = req;
+    grouped.plan = &pl; grouped.order = pl.order.data(); grouped.poses = poses.data();
+    grouped.scores = sc.data(); grouped.overlap = req.overlap ? ov.data() : nullptr; grouped.contours = cc.data();
+    PR_TRY(score_core(grouped));
+    for (uint32_t j = 0; j < P; ++j) req.scores[pl.order[j]] = sc[j];
+    for (uint32_t j = 0; j < cc.size(); ++j) req.contours[pl.order[j]] = cc[j];
+    if (req.overlap)                                             // rows and columns back into the caller's order
         for (uint32_t a = 0; a < P; ++a)
-            for (uint32_t b = 0; b < P; ++b) overlap_host[(size_t)pl.order[a] * P + pl.order[b]] = ov[(size_t)a * P + b];
+            for (uint32_t b = 0; b < P; ++b) req.overlap[(size_t)pl.order[a] * P + pl.order[b]] = ov[(size_t)a * P + b];
     return PR_OK;
+}
+// the request of an entry point from what all eight have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
+ScoreRequest score_request(const char *fn, ScoreKind kind, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, pr_roi roi,
+                           const void *scene_dev, int depth_is_i32, int32_t tau, pr_pose_score *scores_host)
+{
+    ScoreRequest r{};
+    r.fn = fn; r.kind = kind; r.poses = poses_host; r.P = P; r.W = W; r.H = H; r.proj = proj; r.roi = roi;
+    r.scene = scene_dev; r.scene_i32 = depth_is_i32 != 0; r.tau = tau; r.scores = scores_host;
+    return r;
+}
+// (the two images are the caller's device memory, written on this context's stream: call with g->mu held)
+void compose_outputs(ScoreRequest &r, uint16_t *labels_dev, int32_t *depth_dev, pr_pose_visible *visible_host, pr_frame_explained *frame_host)
+{
+    if (r.P && labels_dev) note_write(labels_dev, sizeof(uint16_t) * (size_t)r.W * r.H);
+    if (r.P && depth_dev) note_write(depth_dev, sizeof(int32_t) * (size_t)r.W * r.H);
+    r.labels_dev = labels_dev; r.depth_dev = depth_dev; r.visible = visible_host; r.frame = frame_host;
 }
 
 // render_impl for a mixed batch: full frames (or the ROI) in the caller's order -- the raster writes hypothesis j of the grouped batch into image order[j]
@@ -1186,7 +1177,9 @@ int pr_score_poses(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *po
                    const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host)
 {
     PR_ENTER();
-    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host);
+    ScoreRequest r = score_request("pr_score_poses", kScorePoses, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.tris = tris_dev; r.n_tris = n_tris;
+    return score_run(r);
 }
 
 int pr_render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, size_t n_poses,
@@ -1257,7 +1250,9 @@ int pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uin
                          int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host)
 {
     PR_ENTER();
-    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host);
+    ScoreRequest r = score_request("pr_score_poses_multi", kScorePoses, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
+    return score_run(r);
 }
 
 int pr_score_overlap(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
@@ -1265,8 +1260,10 @@ int pr_score_overlap(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *
                      uint32_t *overlap_host)
 {
     PR_ENTER();
-    PR_TRY(overlap_args_ok("pr_score_overlap", n_poses, overlap_host));
-    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host, overlap_host);
+    ScoreRequest r = score_request("pr_score_overlap", kScoreOverlap, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.tris = tris_dev; r.n_tris = n_tris;
+    r.overlap = overlap_host;
+    return score_run(r);
 }
 
 int pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1274,9 +1271,10 @@ int pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const u
                            int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host, uint32_t *overlap_host)
 {
     PR_ENTER();
-    PR_TRY(overlap_args_ok("pr_score_overlap_multi", n_poses, overlap_host));
-    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
-                       overlap_host);
+    ScoreRequest r = score_request("pr_score_overlap_multi", kScoreOverlap, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
+    r.overlap = overlap_host;
+    return score_run(r);
 }
 
 int pr_scene_edge_distance_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
@@ -1306,10 +1304,10 @@ int pr_score_contours(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 
                       const uint8_t *edge_dist_dev, pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host)
 {
     PR_ENTER();
-    if (overlap_host) PR_TRY(overlap_args_ok("pr_score_contours", n_poses, overlap_host));
-    const ContourOut ct{ jump_mm, edge_dist_dev, contours_host };
-    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host, overlap_host, &ct,
-                      "pr_score_contours");
+    ScoreRequest r = score_request("pr_score_contours", kScoreContours, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.tris = tris_dev; r.n_tris = n_tris;
+    r.jump = jump_mm; r.edge_dist = edge_dist_dev; r.contours = contours_host; r.overlap = overlap_host;
+    return score_run(r);
 }
 
 int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1318,23 +1316,22 @@ int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
                             pr_pose_contour *contours_host, uint32_t *overlap_host)
 {
     PR_ENTER();
-    if (overlap_host) PR_TRY(overlap_args_ok("pr_score_contours_multi", n_poses, overlap_host));
-    const ContourOut ct{ jump_mm, edge_dist_dev, contours_host };
-    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
-                       overlap_host, &ct, "pr_score_contours_multi");
+    ScoreRequest r = score_request("pr_score_contours_multi", kScoreContours, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
+    r.jump = jump_mm; r.edge_dist = edge_dist_dev; r.contours = contours_host; r.overlap = overlap_host;
+    return score_run(r);
 }
 
 int pr_compose_detections(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                           const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out,
                           int32_t *depth_dev_out, pr_pose_score *scores_host, pr_pose_visible *visible_host, pr_frame_explained *frame_host)
 {
-    PR_TRY(compose_args_ok("pr_compose_detections", n_poses));                                  // before any device use
+    PR_TRY(compose_args_ok("pr_compose_detections", n_poses));          // before any device use
     PR_ENTER();
-    if (n_poses && labels_dev_out) note_write(labels_dev_out, sizeof(uint16_t) * (size_t)width * height);
-    if (n_poses && depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * (size_t)width * height);
-    const ComposeOut cp{ nullptr, labels_dev_out, depth_dev_out, visible_host, frame_host };
-    return score_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host, nullptr, nullptr,
-                      "pr_compose_detections", &cp);
+    ScoreRequest r = score_request("pr_compose_detections", kScoreCompose, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.tris = tris_dev; r.n_tris = n_tris;
+    compose_outputs(r, labels_dev_out, depth_dev_out, visible_host, frame_host);
+    return score_run(r);
 }
 
 int pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1342,13 +1339,12 @@ int pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, co
                                 int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out, int32_t *depth_dev_out, pr_pose_score *scores_host,
                                 pr_pose_visible *visible_host, pr_frame_explained *frame_host)
 {
-    PR_TRY(compose_args_ok("pr_compose_detections_multi", n_poses));
+    PR_TRY(compose_args_ok("pr_compose_detections_multi", n_poses));          // before any device use
     PR_ENTER();
-    if (n_poses && labels_dev_out) note_write(labels_dev_out, sizeof(uint16_t) * (size_t)width * height);
-    if (n_poses && depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * (size_t)width * height);
-    const ComposeOut cp{ nullptr, labels_dev_out, depth_dev_out, visible_host, frame_host };
-    return score_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32 != 0, tau_mm, scores_host,
-                       nullptr, nullptr, "pr_compose_detections_multi", &cp);
+    ScoreRequest r = score_request("pr_compose_detections_multi", kScoreCompose, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
+    compose_outputs(r, labels_dev_out, depth_dev_out, visible_host, frame_host);
+    return score_run(r);
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

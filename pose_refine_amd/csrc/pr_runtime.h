@@ -221,6 +221,58 @@ inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, 
     else job.sp.view = *static_cast<const pr_scene_proj *>(scene);     // (a plain projective scene: a crop at 0, 0)
     return PR_OK;
 }
+// ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_contours, pr_compose_detections and their _multi forms) ----
+// What the caller asked for, as the entry point got it; score_run (pr_refine.cpp) takes it from there.  Every member is set by the entry point.
+enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreCompose };
+struct ScoreRequest {
+    const char *fn; ScoreKind kind;                              // the entry point's name (for messages) and what it returns besides the scores
+    const pr_triangle *tris; size_t n_tris;                      // one mesh for every hypothesis ...
+    bool multi; const pr_mesh_ref *meshes; uint32_t n_meshes; const uint32_t *mesh_index;      // ... or (multi) a mesh table and every hypothesis' index into it
+    const pr_mat4 *poses; uint32_t P, W, H; const pr_mat4 *proj; pr_roi roi;
+    const void *scene; bool scene_i32; int32_t tau;
+    pr_pose_score *scores;                                       // host, P records
+    uint32_t *overlap;                                           // host, P x P (kScoreOverlap: required; kScoreContours: null = none)
+    int32_t jump; const uint8_t *edge_dist; pr_pose_contour *contours;                          // kScoreContours: device distance image in, P host records out
+    uint16_t *labels_dev; int32_t *depth_dev; pr_pose_visible *visible; pr_frame_explained *frame;     // kScoreCompose: two optional device images, host records
+    const MeshPlan *plan; const uint32_t *order;                 // score_run's, null from the entry point: the grouped batch (position -> caller's index)
+};
+// pr_score_overlap's own condition
+inline int overlap_args_ok(const char *fn, uint32_t P, const uint32_t *overlap_host)
+{
+    if (P > PR_OVERLAP_MAX_POSES) {
+        set_error("%s: %u hypotheses, but the overlap matrix is limited to PR_OVERLAP_MAX_POSES = %u (a 64 MB matrix)", fn, P, (uint32_t)PR_OVERLAP_MAX_POSES);
+        return PR_ERR_INVALID;
+    }
+    if (P && !overlap_host) { set_error("%s: bad arguments (overlap_host is null)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+// pr_compose_detections' own condition (its entry points ask before any device use as well)
+inline int compose_args_ok(const char *fn, uint32_t P)
+{
+    if (P > PR_COMPOSE_MAX_POSES) {
+        set_error("%s: %u hypotheses, but a label is a uint16: at most PR_COMPOSE_MAX_POSES = %u", fn, P, (uint32_t)PR_COMPOSE_MAX_POSES);
+        return PR_ERR_INVALID;
+    }
+    return PR_OK;
+}
+// Every check of a request that needs no device, in one order for all eight entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
+// call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.  A request without hypotheses needs no arrays.
+inline int score_request_ok(const ScoreRequest &r)
+{
+    const char *fn = r.fn;
+    if (r.kind == kScoreOverlap || (r.kind == kScoreContours && r.overlap)) PR_TRY(overlap_args_ok(fn, r.P, r.overlap));
+    if (r.kind == kScoreCompose) PR_TRY(compose_args_ok(fn, r.P));
+    if (r.tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)r.tau); return PR_ERR_INVALID; }
+    if (!r.proj || r.W == 0 || r.H == 0 || (r.P && (!r.poses || !r.scene || !r.scores || (!r.multi && !r.tris && r.n_tris > 0)))) {
+        set_error("%s: bad arguments", fn); return PR_ERR_INVALID;
+    }
+    if (!frame_size_ok(r.W, r.H)) return PR_ERR_INVALID;
+    if (!roi_ok(r.roi, r.W, r.H)) { set_error("%s: roi out of image", fn); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
+    if (r.kind == kScoreContours && r.jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)r.jump); return PR_ERR_INVALID; }
+    if (r.kind == kScoreContours && r.P && (!r.edge_dist || !r.contours)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
+    if (r.kind == kScoreCompose && r.P && (!r.visible || !r.frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
 // A slot's pinned blocks, in bytes.  h_in, staged to the device by one kernel: poses | pixel boxes | offsets of the packed boxes.
 // h_out, stored by the batch's last kernels: cloud sizes | result records | the word the device-side model-box check writes (1 = the
 // assumed box or a scene cache was stale), each on a 64-byte line of its own.

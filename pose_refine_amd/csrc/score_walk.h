@@ -1,0 +1,71 @@
+// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, contour.hip, compose.hip and nobody else): the workgroup's
+// part of a hypothesis' pixel box, the test of a rendered depth against the scene, the sum of a workgroup's counters, the launchers' loop
+// gfx950 (CDNA4, wave64); integer arithmetic only, differences in 64 bits: every value is bit-identical to the CPU restatement.
+#pragma once
+#include "pr_launch.h"
+
+namespace prk {
+
+// ---- the box walk: one workgroup = kBoxRowsPerBlock image rows of the box of hypothesis blockIdx.y, 4 wavefronts x 4 rows, lanes along a row ----
+struct BoxBlock { int4 bb; int r_lo, r_hi, row0; };                 // the pixel box, its image rows (raster rows run flipped), the first of this wavefront's four rows
+// false: no row of the box in this workgroup -- the same for every thread, so the kernel returns before any barrier
+__device__ __forceinline__ bool box_block(const int4 *__restrict__ bbox, uint32_t height, BoxBlock &b)
+{
+    b.bb = bbox[blockIdx.y];
+    b.r_lo = (int)height - 1 - b.bb.w; b.r_hi = (int)height - 1 - b.bb.y;
+    const int blk0 = (int)(blockIdx.x * kBoxRowsPerBlock);
+    b.row0 = blk0 + (int)(threadIdx.x >> 6) * 4;
+    return !(b.bb.x > b.bb.z || b.r_lo > b.r_hi || blk0 > b.r_hi || blk0 + (int)kBoxRowsPerBlock - 1 < b.r_lo);
+}
+
+// ---- the depth test: what an inlier is for the ranking, the selection, the contour gate and the composition ----
+__device__ __forceinline__ bool rendered(int32_t d) { return d > 0 && d != INT_MAX; }      // something was drawn here (INT_MAX: the render's background)
+// the four tests of pr_pose_score for a rendered depth d against the scene value s: 0 inlier, 1 occluded (s < d - tau), 2 violation (s > d + tau), 3 missing
+__device__ __forceinline__ uint32_t depth_class(int32_t d, int32_t s, int64_t tau)
+{
+    if (s <= 0) return 3;
+    const int64_t diff = (int64_t)d - (int64_t)s;                     // 64 bits: no overflow for any int32 pair
+    return diff > tau ? 1u : (diff < -tau ? 2u : 0u);
+}
+
+// ---- the reduction: N counters per lane -> a wave sum each, the four wavefronts' sums through LDS, one barrier.  Every thread of the 256-thread
+// workgroup calls it; thread k < N gets the workgroup's total of counter k (the others 0) and does its own atomic with it.  Integer adds: exact in any order.
+template <uint32_t N>
+__device__ __forceinline__ uint32_t block_totals(const uint32_t (&v)[N])
+{
+    __shared__ uint32_t part[4][N];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t k = 0; k < N; ++k) {
+        const uint32_t w = wave_sum_u32(v[k]);
+        if (lane == 0) part[wave][k] = w;
+    }
+    __syncthreads();
+    const uint32_t k = threadIdx.x;
+    return k < N ? part[0][k] + part[1][k] + part[2][k] + part[3][k] : 0u;
+}
+
+// ---- the launchers.  launch(scene) with the scene pointer as what it is: kernels templated on the scene type deduce it from the argument
+template <typename Launch>
+static inline void with_scene(const void *scene, bool scene_i32, Launch &&launch)
+{
+    if (scene_i32) launch(static_cast<const int32_t *>(scene));
+    else launch(static_cast<const uint16_t *>(scene));
+}
+// The hypotheses of a rendered batch (launch_render_boxes' layout: full frames, or packed boxes with their offsets) in launches of at most 32768
+// (grid.y is limited to 65535): launch(BoxLaunch, scene) for hypotheses p0 .. p0 + grid.y - 1; what else is per hypothesis the launcher offsets by p0 itself
+struct BoxLaunch { uint32_t p0; dim3 grid; const int32_t *depth; const uint32_t *box_off; };
+template <typename Launch>
+static inline hipError_t for_box_launches(const int32_t *depth, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
+                                          const void *scene, bool scene_i32, Launch &&launch)
+{
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
+        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
+        const BoxLaunch b{ p0, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), box_off ? depth : depth + (size_t)p0 * width * height,
+                           box_off ? box_off + p0 : nullptr };
+        with_scene(scene, scene_i32, [&](auto *sc) { launch(b, sc); });
+    }
+    return hipGetLastError();
+}
+
+}  // namespace prk

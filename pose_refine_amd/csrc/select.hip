@@ -1,6 +1,6 @@
 // select.hip -- which hypotheses explain the same scene pixels: one bit plane of inlier pixels per hypothesis, then popcount(a & b) for every pair
 // gfx950 (CDNA4, wave64); compiled with -ffp-contract=off: every per-element value is bit-identical to the CPU restatement.
-#include "pr_launch.h"
+#include "score_walk.h"
 
 namespace prk {
 
@@ -15,12 +15,10 @@ __global__ __launch_bounds__(256) void support_bits_kernel(const int32_t *__rest
                                                            const uint32_t *__restrict__ box_off, const SceneT *__restrict__ scene, int32_t tau,
                                                            unsigned long long *__restrict__ planes, uint32_t words_per_row)
 {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int4 bb = bbox[blockIdx.y];
-    const int r_lo = (int)height - 1 - bb.w, r_hi = (int)height - 1 - bb.y;            // image rows of the box (raster rows run flipped)
-    const int blk0 = (int)(blockIdx.x * kBoxRowsPerBlock);
-    if (bb.x > bb.z || r_lo > r_hi || blk0 > r_hi || blk0 + (int)kBoxRowsPerBlock - 1 < r_lo) return;
-    const uint32_t row0 = (uint32_t)blk0 + wave * 4;
+    const uint32_t lane = threadIdx.x & 63;
+    BoxBlock blk;
+    if (!box_block(bbox, height, blk)) return;
+    const auto [bb, r_lo, r_hi, row0] = blk;
     unsigned long long *plane = planes + (size_t)blockIdx.y * height * words_per_row;
     const int64_t t = tau;
     const int32_t *line[4];
@@ -47,10 +45,7 @@ __global__ __launch_bounds__(256) void support_bits_kernel(const int32_t *__rest
         unsigned long long mine = 0;
 #pragma unroll
         for (uint32_t r = 0; r < 4; ++r) {
-            const int32_t d = rv[r], s = sv[r];
-            const int64_t diff = (int64_t)d - (int64_t)s;           // 64 bits: no overflow for any int32 pair
-            const bool inl = d > 0 && d != INT_MAX && s > 0 && diff <= t && diff >= -t;
-            const unsigned long long m = __ballot(inl);
+            const unsigned long long m = __ballot(rendered(rv[r]) && depth_class(rv[r], sv[r], t) == 0);
             if (lane == r) mine = m;
         }
         if (my_live)                                                // lane r < 4 stores the word of row r
@@ -62,18 +57,10 @@ hipError_t launch_support_bits(const int32_t *depth, const int4 *bbox, const uin
                                const void *scene, bool scene_i32, int32_t tau, unsigned long long *planes, hipStream_t s)
 {
     const uint32_t wpr = overlap_words_per_row(width);
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {                // grid.y is limited to 65535 (launch_score_boxes splits the same way)
-        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
-        const int32_t *d = box_off ? depth : depth + (size_t)p0 * width * height;
-        const uint32_t *bo = box_off ? box_off + p0 : nullptr;
-        unsigned long long *pl = planes + (size_t)p0 * height * wpr;
-        const dim3 grid((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np);
-        if (scene_i32)
-            hipLaunchKernelGGL(support_bits_kernel<int32_t>, grid, dim3(256), 0, s, d, bbox + p0, width, height, bo, static_cast<const int32_t *>(scene), tau, pl, wpr);
-        else
-            hipLaunchKernelGGL(support_bits_kernel<uint16_t>, grid, dim3(256), 0, s, d, bbox + p0, width, height, bo, static_cast<const uint16_t *>(scene), tau, pl, wpr);
-    }
-    return hipGetLastError();
+    return for_box_launches(depth, box_off, n_poses, width, height, scene, scene_i32, [&](const BoxLaunch &b, auto *sc) {
+        hipLaunchKernelGGL(support_bits_kernel, b.grid, dim3(256), 0, s, b.depth, bbox + b.p0, width, height, b.box_off, sc, tau,
+                           planes + (size_t)b.p0 * height * wpr, wpr);
+    });
 }
 
 // Pair counts.  Workgroup i owns hypothesis i and the pairs (i, i + k mod P) for k = 0 .. P / 2 (for even P the distance P / 2 belongs to the

@@ -9,7 +9,7 @@ import oracle_lib as O
 from pose_refine_amd import _lib, api, synth
 from gpu_common import W, H, raw_h2d
 from contour_ref import (NO_EDGE, assert_contours_equal, contour_ref, edge_distance_ref, edges, jump_only, structured_scene)
-from verify_ref import assert_scores_equal, score_ref
+from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -418,3 +418,15 @@ def test_chunked_batch_matches_small_batches(gpu, model):
     got = _dist_host(ed, Hb, Wb)
     want = edge_distance_ref(scene[Hb // 2 - 160:Hb // 2 + 160], 10, 2)[10:-10]
     assert np.array_equal(got[rows], want) and (want == 0).sum() > 1000
+
+
+def test_batch_of_two_box_launches(gpu):
+    """32768 + 5 hypotheses in one depth chunk: the launches over their boxes are split in two (grid.y is limited).  Every score and contour
+    record is the reference's for its pose, the ones behind the split included; int32 scene, no overlap matrix."""
+    c = launch_split_case()
+    poses = c["poses"][np.arange(c["P"]) % 8]
+    ed = api.scene_edge_distance(c["scene"], c["W"], c["H"], c["jump"], c["radius"])
+    assert np.array_equal(_dist_host(ed, c["H"], c["W"]), c["dist"])
+    scores, got = api.score_contours(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"], c["tau"], c["jump"], ed)
+    assert_records_repeat(got, c["contours"])
+    assert_records_repeat(scores, c["scores"])

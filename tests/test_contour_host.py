@@ -8,6 +8,7 @@ import pytest
 import oracle_lib as O
 from pose_refine_amd import _lib, api, synth
 from contour_ref import (NO_EDGE, contour_ref, distance_brute, distance_from_edges, edge_distance_ref, edges, jump_only, structured_scene)
+from verify_ref import launch_split_case
 
 W, H = synth.WIDTH, synth.HEIGHT
 
@@ -125,6 +126,24 @@ def test_structured_scene_has_every_class(scenario):
     for f in ("hit", "occluded", "miss", "dist_sum"):
         assert (c[f] > 0).all(), f
     assert jump_only(r, 10).sum() > 0
+
+
+def test_launch_split_case_is_pinned():
+    """The inputs of the GPU tests of a batch that needs two launches over its boxes: what the references hold for the 8 distinct poses."""
+    c = launch_split_case()
+    assert (c["W"], c["H"], c["P"]) == (48, 32, 32768 + 5) and c["tris"].shape == (12, 3, 3) and c["poses"].shape == (8, 4, 4)
+    assert len({p.tobytes() for p in c["poses"]}) == 8
+    assert c["scene"].dtype == np.int32 and c["scene"].shape == (32, 48) and 0 <= c["scene"].min() and c["scene"].max() < 2**16
+    sc, con = c["scores"], c["contours"]
+    assert (sc["visible"] > 0).all() and np.count_nonzero((sc["inlier"] > 0) & (con["contour"] > 0)) >= 4
+    assert sc["visible"].tolist() == [301, 394, 272, 176, 172, 123, 161, 670]
+    assert sc["inlier"].tolist() == [107, 252, 109, 51, 103, 0, 6, 0]
+    assert sc["abs_err_sum"].tolist() == [243, 546, 261, 109, 209, 0, 14, 0]
+    assert con["contour"].tolist() == [123, 84, 81, 40, 94, 38, 81, 75] and con["hit"].tolist() == [39, 66, 48, 15, 75, 15, 69, 69]
+    rows = [np.flatnonzero((r > 0).any(1)) for r in c["renders"]]
+    assert sum(ys[0] < 16 <= ys[-1] for ys in rows) >= 4              # boxes that lie in both row blocks
+    drawn = (c["renders"] > 0).any(0)
+    assert drawn[0].any() and drawn[-1].any() and drawn[:, 0].any() and drawn[:, -1].any()
 
 
 def test_device_calls_without_gpu_fail_loudly():

@@ -9,7 +9,7 @@ import pytest
 import oracle_lib as O
 from pose_refine_amd import _lib, api, synth
 from gpu_common import W, H, raw_h2d
-from verify_ref import assert_scores_equal, score_ref
+from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -243,3 +243,12 @@ def test_chunked_batch_matches_small_batches(gpu, model):
     parts = np.concatenate([api.score_poses(model, poses[i:i + 40], Wb, Hb, proj, sd, 4) for i in range(0, 150, 40)])
     assert_scores_equal(whole, parts)
     assert (whole["visible"] > 0).all() and whole["inlier"].sum() > 0
+
+
+def test_batch_of_two_box_launches(gpu):
+    """32768 + 5 hypotheses in one depth chunk: the launch over their boxes is split in two (grid.y is limited).  Every record is the
+    reference's for its pose, the ones behind the split included; uint16 scene."""
+    c = launch_split_case()
+    poses = c["poses"][np.arange(c["P"]) % 8]
+    got = api.score_poses(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"].astype(np.uint16), c["tau"])
+    assert_records_repeat(got, c["scores"])

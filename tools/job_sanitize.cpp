@@ -1,6 +1,6 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
-// Sanitizer harness for the host-only helpers of the fused batch path (pr_runtime.h): make_job with null and out-of-range arguments, the layouts of a
-// slot's pinned blocks (SlotIn, SlotOut), the pose-group split.  None of them calls HIP, so nothing of the runtime is linked.
+// Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job and score_request_ok with null and
+// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut), the pose-group split.  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
 namespace prh { void set_error(const char *, ...) {} }
@@ -48,6 +48,59 @@ int main()
     CHECK(job.scene() == &job.sp && job.sp.tl_x == 7 && job.sp.tl_y == 9 && job.roi.x == 630 && job.crit.max_iteration == 0 && job.results_dev == nullptr);
     CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_NN, &sn, crit, pr_roi{ 5, 5, -3, 0 }, nullptr, job) == PR_OK);       // (no ROI)
     CHECK(job.scene() == &job.sn && job.sn.n_points == 11);
+    // scoring requests: one good one per kind, single mesh and mesh table; then one mistake at a time -- a null array, too many hypotheses, a ROI off the frame
+    const pr_mat4 *poses = reinterpret_cast<const pr_mat4 *>(uintptr_t(0x4000));
+    const pr_mesh_ref *table = reinterpret_cast<const pr_mesh_ref *>(uintptr_t(0x5000));
+    const uint32_t *index = reinterpret_cast<const uint32_t *>(uintptr_t(0x6000));
+    pr_pose_score *scores = reinterpret_cast<pr_pose_score *>(uintptr_t(0x7000));
+    uint32_t *matrix = reinterpret_cast<uint32_t *>(uintptr_t(0x8000));
+    const uint8_t *edges = reinterpret_cast<const uint8_t *>(uintptr_t(0x9000));
+    pr_pose_contour *contours = reinterpret_cast<pr_pose_contour *>(uintptr_t(0xa000));
+    pr_pose_visible *visible = reinterpret_cast<pr_pose_visible *>(uintptr_t(0xb000));
+    pr_frame_explained *frame = reinterpret_cast<pr_frame_explained *>(uintptr_t(0xc000));
+    const pr_roi off_frame{ 631, 0, 10, 10 };
+    for (ScoreKind kind : { kScorePoses, kScoreOverlap, kScoreContours, kScoreCompose })
+        for (bool multi : { false, true }) {
+            ScoreRequest ok{};
+            ok.fn = "job_sanitize"; ok.kind = kind; ok.multi = multi; ok.poses = poses; ok.P = 70; ok.W = 640; ok.H = 480; ok.proj = &proj; ok.roi = pr_roi{ 630, 470, 10, 10 };
+            ok.scene = dev; ok.scene_i32 = true; ok.tau = 0; ok.scores = scores;
+            if (multi) { ok.meshes = table; ok.n_meshes = 2; ok.mesh_index = index; } else { ok.tris = tris; ok.n_tris = 5; }
+            if (kind == kScoreOverlap) ok.overlap = matrix;
+            if (kind == kScoreContours) { ok.jump = 0; ok.edge_dist = edges; ok.contours = contours; }       // (no matrix: it is optional here)
+            if (kind == kScoreCompose) { ok.visible = visible; ok.frame = frame; }                          // (neither image: both are optional)
+            CHECK(score_request_ok(ok) == PR_OK);
+            ScoreRequest none_to_score = ok; none_to_score.P = 0; none_to_score.poses = nullptr; none_to_score.scene = nullptr; none_to_score.scores = nullptr;
+            none_to_score.overlap = nullptr; none_to_score.edge_dist = nullptr; none_to_score.contours = nullptr; none_to_score.visible = nullptr; none_to_score.frame = nullptr;
+            CHECK(score_request_ok(none_to_score) == PR_OK);                                               // no hypotheses need no arrays
+            auto refused_with = [&](auto &&mistake) { ScoreRequest r = ok; mistake(r); CHECK(score_request_ok(r) == PR_ERR_INVALID); };
+            refused_with([](ScoreRequest &r) { r.poses = nullptr; });
+            refused_with([](ScoreRequest &r) { r.scene = nullptr; });
+            refused_with([](ScoreRequest &r) { r.scores = nullptr; });
+            refused_with([](ScoreRequest &r) { r.proj = nullptr; });
+            refused_with([](ScoreRequest &r) { r.tau = -1; });
+            refused_with([&](ScoreRequest &r) { r.roi = off_frame; });
+            refused_with([](ScoreRequest &r) { r.roi = pr_roi{ 2147483647, 0, 2147483647, 1 }; });
+            refused_with([](ScoreRequest &r) { r.W = 8193; r.H = 1; });
+            refused_with([](ScoreRequest &r) { r.W = 0xffffffffu; r.H = 0xffffffffu; });
+            refused_with([](ScoreRequest &r) { r.W = 0; });
+            if (!multi) refused_with([](ScoreRequest &r) { r.tris = nullptr; });
+            if (kind == kScoreOverlap) refused_with([](ScoreRequest &r) { r.overlap = nullptr; });
+            if (kind == kScoreOverlap) refused_with([](ScoreRequest &r) { r.P = PR_OVERLAP_MAX_POSES + 1; });
+            if (kind == kScoreContours) {
+                refused_with([](ScoreRequest &r) { r.edge_dist = nullptr; });
+                refused_with([](ScoreRequest &r) { r.contours = nullptr; });
+                refused_with([](ScoreRequest &r) { r.jump = -2147483647 - 1; });
+                refused_with([&](ScoreRequest &r) { r.overlap = matrix; r.P = PR_OVERLAP_MAX_POSES + 1; });
+                ScoreRequest many = ok; many.P = PR_OVERLAP_MAX_POSES + 1;                                    // without a matrix there is no such limit
+                CHECK(score_request_ok(many) == PR_OK);
+            }
+            if (kind == kScoreCompose) {
+                refused_with([](ScoreRequest &r) { r.visible = nullptr; });
+                refused_with([](ScoreRequest &r) { r.frame = nullptr; });
+                refused_with([](ScoreRequest &r) { r.P = PR_COMPOSE_MAX_POSES + 1; });
+                CHECK(compose_args_ok("job_sanitize", PR_COMPOSE_MAX_POSES) == PR_OK && compose_args_ok("job_sanitize", 0xffffffffu) == PR_ERR_INVALID);
+            }
+        }
     // the pinned blocks of a slot: the parts in order, none overlapping, written and read back over their whole length
     for (size_t P : { size_t(0), size_t(1), size_t(3), size_t(65) }) {
         const SlotIn in(P);

@@ -448,6 +448,59 @@ int  pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, c
                                  int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out, int32_t *depth_dev_out,
                                  pr_pose_score *scores_host, pr_pose_visible *visible_host, pr_frame_explained *frame_host);
 
+/* ---- pose distances: how far apart are two poses? ---------------------------------------------------------------------------------------
+ * Everything above compares a pose with an image.  pr_pose_distance compares poses with each other, by the displacement of the model's
+ * surface points between them (the BOP family of pose errors): its mean (ADD), its maximum (MSSD) and its maximum in the image (MSPD), each
+ * minimised over a finite set of symmetry transforms of the model.  Poses are pr_mat4, row-major, in mm, as everywhere; points are pr_vec3
+ * in model coordinates.  For one pair (A, B) and the candidates k = 0 .. n-1, S_0 .. S_(n-1) = syms_host (n_syms == 0: the identity alone,
+ * which gives the bytes of n_syms == 1 with an identity matrix):
+ *   1. matrices, in double: As = A * S_k, rows 0..2, every entry summed in pr_mat4_mul's order (0 + a3 s3 + a2 s2 + a1 s1 + a0 s0), and
+ *      D = As - B.  Both are rounded to float32 once.  Forming the difference of the MATRICES first keeps near-identical poses accurate: a
+ *      0.03 mm shift at 320 mm gives a maximum of 0.0300007 mm (truth 0.03000069) and a mean of 1966 * 2^-16 = 0.0299988 mm (half a quantum
+ *      off); the difference of two transformed float32 points loses that with |t|.
+ *   2. per point v = (x, y, z), float32, no contraction: d_r = ((D[r][0]*x + D[r][1]*y) + D[r][2]*z) + D[r][3], d2 = (d_0*d_0 + d_1*d_1) + d_2*d_2.
+ *   3. sum_k  = sum over v of (uint64) min(rintf(sqrtf(d2) * 65536.0f), 2^40): the summed displacement in units of 2^-16 mm, an exact integer
+ *      that does not depend on the order of summation (sqrtf correctly rounded; a NaN term counts as 2^40).
+ *   4. maxd_k = max over v of d2, float32, mm^2 (from 0; a NaN d2 is passed over).
+ *   5. only with K: a = As v and b = B v in the three-term form of 2., u = K[0]*X/Z + K[2], w = K[4]*Y/Z + K[5] for both, and
+ *      maxp_k = max over v of (ua-ub)^2 + (wa-wb)^2, px^2 -- or +inf if any point of either pose has Z <= 0.  Two float32 projections are
+ *      subtracted here: the absolute accuracy is about 1e-4 px (5e-5 px measured on the benchmark's hypotheses), whatever the poses.
+ *   6. the record: each of the three minima over k on its own, the lowest k on a tie.
+ * Points must be finite (they cannot be checked without a pass over them), and so must every float32 intermediate be for the maxima to mean
+ * anything: |t| up to 2e7 mm merely saturates the sum's terms.  n_points <= PR_POSE_DIST_MAX_POINTS keeps the sum inside 64 bits.
+ * all_pairs == 0: n_a == n_b and out_host[i] compares a_host[i] with b_host[i].  all_pairs != 0: out_host[i * n_b + j] compares a_host[i]
+ * with b_host[j]; n_b == 1 is "everything against one ground truth".  points_dev is device memory (n_points x 12 bytes), read on every call.
+ * Synchronous, on the calling thread's context; a batch pending on an asynchronous slot is not disturbed.  PR_ERR_INVALID, with nothing
+ * written and BEFORE any device is touched (so also on a machine without one), for: n_a or n_b > PR_POSE_DIST_MAX_POSES, n_syms >
+ * PR_POSE_DIST_MAX_SYMS, n_a != n_b without all_pairs; and, with pairs to compute: n_points == 0 or > PR_POSE_DIST_MAX_POINTS, a null
+ * points_dev, a_host, b_host, out_host (or syms_host with n_syms > 0), a non-finite entry in any pose, symmetry or K, K[0] == 0 or K[4] == 0.
+ * No pairs: PR_OK, nothing written, no device needed.  While a call runs the device holds 96 bytes per (a, symmetry) and 48 per b, and the
+ * host as much pinned memory; larger calls run as several launches of at most 2^18 candidates (pair x symmetry). */
+#define PR_POSE_DIST_MAX_SYMS   64
+#define PR_POSE_DIST_MAX_POSES  4096
+#define PR_POSE_DIST_MAX_POINTS (1u << 24)
+typedef struct {
+    uint64_t disp_sum_q16;   /* min_k sum_k: mean displacement = disp_sum_q16 / 65536 / n_points mm                              */
+    float    max_disp_sq;    /* min_k maxd_k, mm^2                                                                             */
+    float    max_proj_sq;    /* min_k maxp_k, px^2; 0 when K == NULL                                                           */
+    uint16_t sym_sum, sym_disp, sym_proj;   /* the k of each minimum; sym_proj 0 when K == NULL                               */
+    uint16_t reserved;       /* written as 0                                                                                   */
+    uint32_t n_points;
+    uint32_t reserved2;      /* written as 0                                                                                   */
+} pr_pose_dist;              /* 32 B                                                                                           */
+int  pr_pose_distance(const pr_vec3 *points_dev, uint32_t n_points, const pr_mat4 *a_host, uint32_t n_a, const pr_mat4 *b_host, uint32_t n_b,
+                      int all_pairs, const pr_mat4 *syms_host, uint32_t n_syms, const float K[9] /* may be NULL */, pr_pose_dist *out_host);
+/* Greedy merging of duplicates in pose space, host only (needs no device); the shape of pr_select_greedy.  order: n_order indices, best
+ * first, each < n_poses and none twice (else PR_ERR_INVALID); dist: the n_poses x n_poses matrix of an all_pairs call of the poses with
+ * themselves.  Walks order; keeps i unless an already kept j has dist[i][j].max_disp_sq <= max_disp_mm^2 OR dist[j][i].max_disp_sq <=
+ * max_disp_mm^2 (the square formed in float32) -- with symmetries the matrix is not exactly symmetric, because a model's vertex set is only
+ * approximately invariant under them, so both entries are asked.  kept_out (room for n_order indices) receives the kept ones in that
+ * order, *n_kept their number; rep_out (n_poses entries, or NULL) receives for every i in order the kept hypothesis that absorbed it -- the
+ * first such j in kept order, i itself if kept; entries of hypotheses outside order are not written.  A negative or non-finite
+ * max_disp_mm is PR_ERR_INVALID. */
+int  pr_cluster_greedy(const uint32_t *order, uint32_t n_order, const pr_pose_dist *dist, uint32_t n_poses, float max_disp_mm,
+                       uint32_t *kept_out, uint32_t *n_kept, uint32_t *rep_out);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 
@@ -496,7 +549,8 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *                              (first bounds, and an exact window scan once the bound is a few pixels wide)
  *   "nn_lds_nodes"     [1024]  stackless query: leading nodes staged in LDS;  "nn_lds_records" [0]: the same for 64-byte records
  *   "profile"          [0]     see below;  "sample_period" [32]: profile 2 times one call in this many
- *   "scene_cache"      [1]     keep derived scene data between calls (see "Caches" at the top) */
+ *   "scene_cache"      [1]     keep derived scene data between calls (see "Caches" at the top)
+ *   "pose_dist_chunk"  (read-only) model points a workgroup of pr_pose_distance stages at a time: where its point loop has its seams */
 int  pr_set_option(const char *name, int value);
 int  pr_get_option(const char *name, int *value);
 /* HIP-event timing of the correspondence kernel on the library stream: option "profile" = 1 times every launch (all calls run

@@ -36,8 +36,13 @@ VISIBLE = np.dtype([("owned", "<u4"), ("owned_inlier", "<u4"), ("owned_occluded"
 FRAME = np.dtype([("window", "<u4"), ("measured", "<u4"), ("covered", "<u4"), ("explained", "<u4"), ("in_front", "<u4"), ("behind", "<u4"),
                   ("unmeasured", "<u4"), ("reserved", "<u4")])
 COMPOSE_NONE, COMPOSE_MAX_POSES = 0xFFFF, 65535      # PR_COMPOSE_NONE, PR_COMPOSE_MAX_POSES
+# pr_pose_dist: the displacement of the model's points between two poses, minimised over the symmetry candidates (pr_pose_distance)
+POSE_DIST = np.dtype([("disp_sum_q16", "<u8"), ("max_disp_sq", "<f4"), ("max_proj_sq", "<f4"), ("sym_sum", "<u2"), ("sym_disp", "<u2"),
+                      ("sym_proj", "<u2"), ("reserved", "<u2"), ("n_points", "<u4"), ("reserved2", "<u4")])
+POSE_DIST_MAX_SYMS, POSE_DIST_MAX_POSES, POSE_DIST_MAX_POINTS = 64, 4096, 1 << 24     # PR_POSE_DIST_MAX_SYMS, _MAX_POSES, _MAX_POINTS
+POSE_DIST_CHUNK = 256                    # PR_POSE_DIST_CHUNK (pr_tuning.h; the library reports its own as option "pose_dist_chunk")
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
-assert VISIBLE.itemsize == 32 and FRAME.itemsize == 32
+assert VISIBLE.itemsize == 32 and FRAME.itemsize == 32 and POSE_DIST.itemsize == 32
 
 
 class PoseRefineError(RuntimeError):
@@ -148,6 +153,8 @@ SIGNATURES = {
     "pr_score_contours_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "pr_compose_detections": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "pr_compose_detections_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "pr_pose_distance": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, _i32, _vp, _u32, _vp, _vp]),
+    "pr_cluster_greedy": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32), _vp]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -262,12 +262,20 @@ class Model:
                                    ptr(self.faces), ptr(self.bbox_min), ptr(self.bbox_max)))
             self.tris = buf
         self._dev: Optional[DeviceVector] = None
+        self._dev_vertices: Optional[DeviceVector] = None
 
     def device_tris(self) -> DeviceVector:
         """Triangles resident on the device (the ``device_vector_holder<Triangle>`` overloads)."""
         if self._dev is None:
             self._dev = DeviceVector.from_host(self.tris.reshape(-1), np.float32)
         return self._dev
+
+    def device_vertices(self) -> DeviceVector:
+        """``vertices`` resident on the device (3 float32 each): the points ``pose_distance`` measures with.  A file's vertex list as it
+        is (each vertex once); for a model made from ``tris=`` the triangle corners as they are."""
+        if self._dev_vertices is None:
+            self._dev_vertices = DeviceVector.from_host(_f32(self.vertices, -1), np.float32)
+        return self._dev_vertices
 
 
 def compute_proj(K, width: int, height: int, near: float = 10.0, far: float = 10000.0) -> np.ndarray:
@@ -908,6 +916,118 @@ def select_hypotheses(scores, overlap, max_shared: Sequence[int] = (1, 4), min_f
     frac = np.where(den <= 0, 0.0, sc["inlier"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
     order = order[frac[order] >= float(min_fraction)]
     return select_greedy(order, overlap, int(max_shared[0]), int(max_shared[1]))
+
+
+# ------------------------------------------------------------------------------------------------
+# pose distances: how far apart are two poses (ADD / MSSD / MSPD over a symmetry set), duplicates in pose space
+# ------------------------------------------------------------------------------------------------
+def _points_dev(points) -> DeviceVector:
+    if isinstance(points, Model):
+        return points.device_vertices()
+    if isinstance(points, DeviceVector):
+        return points
+    return DeviceVector.from_host(_f32(points, -1))
+
+
+def _poses44(p, name: str) -> np.ndarray:
+    a = _f32(p)
+    if a.size % 16 or (a.ndim >= 2 and a.shape[-2:] != (4, 4) and a.shape[-1] != 16):
+        raise ValueError(f"{name} must hold 4x4 matrices, got shape {a.shape}")
+    return a.reshape(-1, 4, 4)
+
+
+def _pose_distance(points, a: np.ndarray, b: np.ndarray, all_pairs: bool, syms, K) -> np.ndarray:
+    pd = _points_dev(points)
+    if pd.size() % 3:
+        raise ValueError("points must hold 3 float32 per point")
+    sy = np.zeros((0, 4, 4), np.float32) if syms is None else _poses44(syms, "syms")
+    k = None if K is None else _f32(K, -1)
+    if k is not None and k.size != 9:
+        raise ValueError("K must hold 9 values")
+    out = np.zeros(len(a) * len(b) if all_pairs else len(a), POSE_DIST)
+    check(_lib.load().pr_pose_distance(pd.data() or None, pd.size() // 3, ptr(a), len(a), ptr(b), len(b), int(all_pairs), ptr(sy) if len(sy) else None,
+                                       len(sy), None if k is None else ptr(k), ptr(out)))
+    return out
+
+
+def pose_distance(points, a, b, syms=None, K=None) -> np.ndarray:
+    """``pr_pose_distance``, pair by pair: POSE_DIST[n] comparing ``a[i]`` with ``b[i]`` -- or every ``a[i]`` with the one pose ``b`` of
+    shape (4, 4) / (1, 4, 4) ("everything against one ground truth").  ``points``: a ``Model`` (its ``device_vertices()``), a DeviceVector of
+    3 float32 per point, or a host (n, 3) array, uploaded for the call.  Poses in mm; ``syms``: up to ``POSE_DIST_MAX_SYMS`` 4x4 symmetry
+    transforms of the model (None: the identity); ``K``: 9 intrinsics, or None for no image-space distance.  Read the records with
+    ``mean_displacement`` (ADD), ``max_displacement`` (MSSD) and ``max_projection`` (MSPD)."""
+    a, b = _poses44(a, "a"), _poses44(b, "b")
+    if len(b) == 1 and len(a) != 1:
+        return _pose_distance(points, a, b, True, syms, K)
+    if len(a) != len(b):
+        raise ValueError(f"{len(a)} poses against {len(b)}: pair mode takes as many of each (or one b)")
+    return _pose_distance(points, a, b, False, syms, K)
+
+
+def pose_distance_matrix(points, a, b=None, syms=None, K=None) -> np.ndarray:
+    """``pr_pose_distance`` with ``all_pairs``: POSE_DIST[n_a, n_b], entry [i, j] comparing ``a[i]`` with ``b[j]``; ``b=None`` means ``a``
+    (the matrix ``merge_duplicates`` takes).  At most ``POSE_DIST_MAX_POSES`` poses a side.  Arguments as for ``pose_distance``."""
+    a = _poses44(a, "a")
+    b = a if b is None else _poses44(b, "b")
+    return _pose_distance(points, a, b, True, syms, K).reshape(len(a), len(b))
+
+
+def mean_displacement(d) -> np.ndarray:
+    """ADD in mm, float64: ``disp_sum_q16 / 65536 / n_points``."""
+    d = np.asarray(d)
+    return d["disp_sum_q16"].astype(np.float64) / 65536.0 / d["n_points"].astype(np.float64)
+
+
+def max_displacement(d) -> np.ndarray:
+    """MSSD in mm, float64: the square root of ``max_disp_sq``."""
+    return np.sqrt(np.asarray(d)["max_disp_sq"].astype(np.float64))
+
+
+def max_projection(d) -> np.ndarray:
+    """MSPD in pixels, float64: the square root of ``max_proj_sq`` (inf where a pose puts a point at Z <= 0; 0 when no K was given)."""
+    return np.sqrt(np.asarray(d)["max_proj_sq"].astype(np.float64))
+
+
+def symmetry_rotations(axis, n: int, center=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """The ``n`` transforms of an n-fold rotational symmetry, float32[n, 4, 4]: rotation by 2 pi k / n about the line through ``center``
+    along ``axis``, the identity first.  Computed in float64 (Rodrigues' formula) and rounded once."""
+    n = int(n)
+    ax = np.asarray(axis, np.float64).reshape(3)
+    norm = np.linalg.norm(ax)
+    if n < 1 or not np.isfinite(norm) or norm == 0.0:
+        raise ValueError("symmetry_rotations: n >= 1 and a non-zero axis")
+    ax = ax / norm
+    c0 = np.asarray(center, np.float64).reshape(3)
+    kx = np.array([[0.0, -ax[2], ax[1]], [ax[2], 0.0, -ax[0]], [-ax[1], ax[0], 0.0]])
+    out = np.zeros((n, 4, 4), np.float64)
+    for k in range(n):
+        ang = 2.0 * np.pi * k / n
+        r = np.eye(3) if k == 0 else np.eye(3) + np.sin(ang) * kx + (1.0 - np.cos(ang)) * (kx @ kx)
+        out[k, :3, :3] = r
+        out[k, :3, 3] = c0 - r @ c0
+        out[k, 3, 3] = 1.0
+    return out.astype(np.float32)
+
+
+def merge_duplicates(order, dist, max_disp_mm: float):
+    """``pr_cluster_greedy`` (host only): walk ``order`` (indices, best first) and keep i unless an already kept j lies within
+    ``max_disp_mm`` of it by ``max_disp_sq``, asked in both directions of ``dist`` (the POSE_DIST[P, P] of ``pose_distance_matrix(points, poses)``).
+    Returns (kept, representative): the kept indices in that order, and int64[P] with, for every i of ``order``, the kept hypothesis
+    that absorbed it (itself if kept); -1 for hypotheses outside ``order``."""
+    dm = np.ascontiguousarray(dist, POSE_DIST)
+    if dm.ndim != 2 or dm.shape[0] != dm.shape[1]:
+        raise ValueError(f"dist must be a square matrix, got shape {dm.shape}")
+    od = np.asarray(order)
+    if od.ndim != 1 or (len(od) and (od.dtype.kind not in "iu" or od.min() < 0 or od.max() > 0xffffffff)):
+        raise ValueError("order must be a 1-d array of non-negative integers")
+    od = np.ascontiguousarray(od, np.uint32)
+    kept = np.zeros(max(1, len(od)), np.uint32)
+    rep = np.full(max(1, len(dm)), 0xffffffff, np.uint32)
+    n = C.c_uint32(0)
+    check(_lib.load().pr_cluster_greedy(ptr(od), len(od), ptr(dm), len(dm), float(max_disp_mm), ptr(kept), C.byref(n), ptr(rep)))
+    rep = rep[:len(dm)].astype(np.int64)
+    rep[rep == 0xffffffff] = -1
+    return kept[:n.value].astype(np.int64), rep
 
 
 # ------------------------------------------------------------------------------------------------

@@ -846,6 +846,35 @@ int pr_select_greedy(const uint32_t *order, uint32_t n_order, const uint32_t *ov
     return PR_OK;
 }
 
+// greedy merging of duplicates over a ranking, in pose space: pr_select_greedy's walk with a distance test (either direction: with symmetries
+// the matrix is only approximately symmetric) instead of the shared-pixel test
+int pr_cluster_greedy(const uint32_t *order, uint32_t n_order, const pr_pose_dist *dist, uint32_t n_poses, float max_disp_mm, uint32_t *kept_out,
+                      uint32_t *n_kept, uint32_t *rep_out)
+{
+    if (!(max_disp_mm >= 0.0f) || !std::isfinite(max_disp_mm)) { prh::set_error("pr_cluster_greedy: max_disp_mm must be finite and >= 0"); return PR_ERR_INVALID; }
+    if (!n_kept || (n_order && (!order || !dist || !kept_out))) { prh::set_error("pr_cluster_greedy: bad arguments"); return PR_ERR_INVALID; }
+    std::vector<unsigned char> seen(n_poses, 0);
+    for (uint32_t k = 0; k < n_order; ++k) {
+        if (order[k] >= n_poses) { prh::set_error("pr_cluster_greedy: order[%u] = %u, but there are %u hypotheses", k, order[k], n_poses); return PR_ERR_INVALID; }
+        if (seen[order[k]]) { prh::set_error("pr_cluster_greedy: order[%u] = %u appears twice", k, order[k]); return PR_ERR_INVALID; }
+        seen[order[k]] = 1;
+    }
+    const float r2 = max_disp_mm * max_disp_mm;
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < n_order; ++k) {
+        const uint32_t i = order[k];
+        uint32_t rep = i;
+        for (uint32_t a = 0; a < n && rep == i; ++a) {
+            const uint32_t j = kept_out[a];
+            if (dist[(size_t)i * n_poses + j].max_disp_sq <= r2 || dist[(size_t)j * n_poses + i].max_disp_sq <= r2) rep = j;
+        }
+        if (rep == i) kept_out[n++] = i;
+        if (rep_out) rep_out[i] = rep;
+    }
+    *n_kept = n;
+    return PR_OK;
+}
+
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count)
 {
     // contiguous blocks; the first (n % world) ranks take one extra item

@@ -226,6 +226,17 @@ hipError_t launch_compose_counts(const unsigned long long *keys, const int4 *bbo
                                  const void *scene, bool scene_i32, int32_t tau, uint32_t *records, hipStream_t s);
 hipError_t launch_compose_emit(const unsigned long long *keys, uint32_t width, uint32_t height, int4 window, const void *scene, bool scene_i32, int32_t tau,
                                uint16_t *labels, int32_t *depth_out, uint32_t *frame, hipStream_t s);
+// pose_dist.hip: pr_pose_distance for pairs [pair0, pair0 + n_pairs) of a call.  as_rows: rows 0..2 of A_i S_k in double, [i * n_k + k][12];
+// b_rows: rows 0..2 of B_j in float, [j][12]; pair p = (p / n_b, p % n_b) when all_pairs, else (p, p).  cam null: no projection (the variant
+// without divisions).  The points are split over n_rows workgroup rows of chunks_per_row chunks of kPoseDistChunk points each (every row starts
+// inside the range); partials: 16 bytes x n_rows x n_pairs x n_k.  The combine launch folds the rows and takes the three minima over k into records[n_pairs].
+constexpr uint32_t kPoseDistChunk = PR_POSE_DIST_CHUNK;
+struct PoseDistCamera { float fx, cx, fy, cy; };                  // K[0], K[2], K[4], K[5]
+hipError_t launch_pose_dist(const pr_vec3 *points, uint32_t n_points, const double *as_rows, const float *b_rows, uint32_t n_b, uint32_t n_k,
+                            uint32_t pair0, uint32_t n_pairs, bool all_pairs, const PoseDistCamera *cam, uint32_t n_rows, uint32_t chunks_per_row,
+                            void *partials, hipStream_t s);
+hipError_t launch_pose_dist_combine(const void *partials, uint32_t n_rows, uint32_t n_pairs, uint32_t n_k, uint32_t n_points, bool with_proj,
+                                    pr_pose_dist *records, hipStream_t s);
 hipError_t launch_pack_export(const DevIcpState *st, pr_result *out, const uint32_t *counts, uint32_t *host_counts, pr_result *host_results,
                               uint32_t n, hipStream_t s);
 hipError_t launch_stage_words(const void *src_host_mapped, void *dst, size_t bytes, hipStream_t s);

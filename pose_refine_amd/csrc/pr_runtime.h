@@ -273,6 +273,32 @@ inline int score_request_ok(const ScoreRequest &r)
     if (r.kind == kScoreCompose && r.P && (!r.visible || !r.frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }
     return PR_OK;
 }
+// pr_pose_distance's checks, all of them: no device is touched before they pass (no HIP call in here).  *n_pairs_out = 0: nothing to do.
+inline bool finite16(const pr_mat4 &m) { for (float v : m.m) if (!std::isfinite(v)) return false; return true; }
+inline int pose_dist_args_ok(const pr_vec3 *points_dev, uint32_t n_points, const pr_mat4 *a, uint32_t n_a, const pr_mat4 *b, uint32_t n_b, int all_pairs,
+                             const pr_mat4 *syms, uint32_t n_syms, const float *K, const pr_pose_dist *out, uint64_t *n_pairs_out)
+{
+    const char *fn = "pr_pose_distance";
+    *n_pairs_out = 0;
+    if (n_a > PR_POSE_DIST_MAX_POSES || n_b > PR_POSE_DIST_MAX_POSES) {
+        set_error("%s: %u x %u poses, but a side is limited to PR_POSE_DIST_MAX_POSES = %u", fn, n_a, n_b, (uint32_t)PR_POSE_DIST_MAX_POSES); return PR_ERR_INVALID;
+    }
+    if (n_syms > PR_POSE_DIST_MAX_SYMS) { set_error("%s: %u symmetry transforms, at most PR_POSE_DIST_MAX_SYMS = %u", fn, n_syms, (uint32_t)PR_POSE_DIST_MAX_SYMS); return PR_ERR_INVALID; }
+    if (!all_pairs && n_a != n_b) { set_error("%s: %u poses against %u without all_pairs", fn, n_a, n_b); return PR_ERR_INVALID; }
+    const uint64_t n_pairs = all_pairs ? (uint64_t)n_a * n_b : n_a;
+    if (n_pairs == 0) return PR_OK;
+    if (n_points == 0 || n_points > PR_POSE_DIST_MAX_POINTS) { set_error("%s: n_points must be 1 .. PR_POSE_DIST_MAX_POINTS = %u (got %u)", fn, (uint32_t)PR_POSE_DIST_MAX_POINTS, n_points); return PR_ERR_INVALID; }
+    if (!points_dev || !a || !b || !out || (n_syms && !syms)) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_a; ++i) if (!finite16(a[i])) { set_error("%s: a_host[%u] has a non-finite entry", fn, i); return PR_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_b; ++i) if (!finite16(b[i])) { set_error("%s: b_host[%u] has a non-finite entry", fn, i); return PR_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_syms; ++i) if (!finite16(syms[i])) { set_error("%s: syms_host[%u] has a non-finite entry", fn, i); return PR_ERR_INVALID; }
+    if (K) {
+        for (int i = 0; i < 9; ++i) if (!std::isfinite(K[i])) { set_error("%s: K[%d] is not finite", fn, i); return PR_ERR_INVALID; }
+        if (K[0] == 0.0f || K[4] == 0.0f) { set_error("%s: K[0] and K[4] must not be 0", fn); return PR_ERR_INVALID; }
+    }
+    *n_pairs_out = n_pairs;
+    return PR_OK;
+}
 // A slot's pinned blocks, in bytes.  h_in, staged to the device by one kernel: poses | pixel boxes | offsets of the packed boxes.
 // h_out, stored by the batch's last kernels: cloud sizes | result records | the word the device-side model-box check writes (1 = the
 // assumed box or a scene cache was stale), each on a 64-byte line of its own.
@@ -383,6 +409,8 @@ struct Ctx {
     PinBuf h_contours;
     DevBuf cmp_keys, cmp_box, cmp_rec;   // pr_compose_detections: the key frame (8 bytes per frame pixel), the pixel boxes of ALL hypotheses of a call followed by their caller's indices, the records
     PinBuf h_cmp;                    // the records on their way to the caller, then the index table on its way to the device
+    DevBuf pd_mats, pd_part, pd_rec; // pr_pose_distance: rows 0..2 of every A S_k (double) followed by those of every B (float); the partials of a launch; its records
+    PinBuf h_pd_mats, h_pd_rec;      // the matrices on their way in, the records on their way out
     DevBuf lvl_rows, lvl_counts, lvl_carry;   // pr_refine_pyramid: per-row sample counts and offsets of every level of a chunk, the level clouds' sizes, the per-level carry records
     PinBuf h_lvl_carry;
     DevBuf multi;                    // mixed batches (pr_*_multi): mesh table, box index / image of each hypothesis, raster groups

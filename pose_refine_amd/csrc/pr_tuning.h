@@ -142,3 +142,14 @@
 #ifndef PR_WIDE_LCAP
 #define PR_WIDE_LCAP 160                                        // entries of a wavefront's leaf-task queue
 #endif
+
+// ---- pose distances (pose_dist.hip) ----------------------------------------------------------------------------------------------------
+#ifndef PR_POSE_DIST_CHUNK
+#define PR_POSE_DIST_CHUNK 256                                  // model points a workgroup stages in LDS at a time (4 KB as float4); read-only option "pose_dist_chunk".  Not swept yet
+#endif
+#ifndef PR_POSE_DIST_GROUPS
+#define PR_POSE_DIST_GROUPS 2048                                // workgroups a launch aims for: the point range of a call with few candidates is split over grid.y until there are about this many (256 CUs, a few per CU)
+#endif
+#ifndef PR_POSE_DIST_BATCH
+#define PR_POSE_DIST_BATCH (1u << 18)                           // candidates (pair x symmetry) per launch: bounds the partials, the records and their pinned copy to 8 MB each
+#endif

@@ -23,8 +23,9 @@ __device__ __forceinline__ float div_normal_range(float a, float b)
 // Scene_projective::query depth_scene.h:29-48 + pcd2dep common.h:63-73.  The reference converts
 // int(x/z*fx + cx - tl_x + 0.5f) and then tests 0 <= px < width; truncation maps (-1, 0) to pixel 0, and NaN / out-of-range
 // values end up as INT_MIN on x86 (rejected).  The same decision is taken here on the float before converting: valid iff
-// -1 < v < width.  Whenever the quotient is outside the normal range (z = 0, denormal, inf, NaN) the point is rejected on
-// both sides -- by this range test or by the |src.z - dst.z| test -- so the cheaper division above cannot change a result.
+// -1 < v < width.  The cheaper division above is exact while z and the quotient are in the normal range; the operands are scaled so
+// that a denormal z is in it too (a point with a denormal z and a scene surface closer than max_dist_diff is a match in the
+// reference), and a zero, infinite or NaN z is rejected on both sides.
 __device__ __forceinline__ bool proj_pixel(float sx, float sy, float sz, float fx, float fy, float cx, float cy, float tlx, float tly,
                                            uint32_t width, uint32_t height, uint32_t &idx, int &px, int &py)
 {
@@ -33,10 +34,19 @@ __device__ __forceinline__ bool proj_pixel(float sx, float sy, float sz, float f
     // Both coordinates go through div_normal_range's sequence side by side in packed instructions (v_pk_mul_f32 / v_pk_fma_f32 /
     // v_pk_add_f32: two IEEE operations per issue slot, each element rounded exactly like the scalar form); the reciprocal of z and
     // its first refinement are shared.
-    float r = __builtin_amdgcn_rcpf(sz);
-    const float e0 = __builtin_fmaf(-sz, r, 1.0f);
+    // A denormal z has no usable v_rcp_f32 (it reads as zero: r = inf, q = NaN), yet x / z is an ordinary number when x is as small, and with a
+    // scene surface within max_dist_diff of the camera plane the reference ACCEPTS such a point (tests/test_truth_gpu.py).  So x, y and z enter
+    // the division scaled by 2^64: exact, the quotients are the same real numbers, every intermediate of the sequence is the unscaled one
+    // times a power of two, and the smallest denormal z becomes 2^-85.  At the other end a z of 2^62 and beyond loses its reciprocal and
+    // coordinates of 2^64 and beyond overflow; such a point may come out NaN here, and the reference rejects it too, at the depth test (the
+    // callers apply it to the unscaled z; a scene surface is nearer than 65.6).  Two multiplications, no branch: a branch to a full
+    // division for denormal z cost the headline 2 % (profiles/truth/README.md).
+    constexpr float kScale = 0x1p64f;
+    const float zs = sz * kScale;
+    float r = __builtin_amdgcn_rcpf(zs);
+    const float e0 = __builtin_fmaf(-zs, r, 1.0f);
     r = __builtin_fmaf(e0, r, r);
-    const float2v a{ sx, sy }, rr{ r, r }, nz{ -sz, -sz };
+    const float2v a = float2v{ sx, sy } * float2v{ kScale, kScale }, rr{ r, r }, nz{ -zs, -zs };
     float2v q = a * rr;
     const float2v e1 = __builtin_elementwise_fma(nz, q, a);
     q = __builtin_elementwise_fma(e1, rr, q);

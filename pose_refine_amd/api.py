@@ -174,8 +174,9 @@ def gather_profile():
 
 
 def nn_counters(passes: int = 21) -> np.ndarray:
-    """Per-pass work counters of the kd-tree search kernel (option ``nn_count``): (passes, 8) uint64 --
-    queries, settled by window, tree searches, pyramid descents, tree nodes, leaves, leaf points, window cells."""
+    """Per-pass work counters of the kd-tree search kernels (option ``nn_count``): (passes, 8) uint64, the columns of
+    ``enum NNCounter`` (csrc/nn_search.hip) -- 0 kCntQueries, 1 kCntWindow (settled by the pixel window), 2 kCntTree (handed to a tree
+    walk), 3 kCntDescents (pyramid descents), 4 kCntNodes, 5 kCntLeaves, 6 kCntLeafPoints, 7 kCntCells (window cells read)."""
     out = np.zeros((passes, 8), np.uint64)
     check(_lib.load().pr_nn_counters(ptr(out), passes))
     return out

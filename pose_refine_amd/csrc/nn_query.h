@@ -10,8 +10,18 @@ namespace prk {
 // the current node's box.  That prunes a superset of what the reference prunes and can only skip
 // subtrees whose every point is farther than the current best, so winner and distance are
 // identical (DESIGN.md "kd-tree bound").
+constexpr uint32_t kNoPrev = 0xffffffffu;                         // "no scene point": a query without a winner, a search without a seed
 // dequantisation of a compact-record box coordinate (nn_records32_kernel): one multiply, one add
 __device__ __forceinline__ float nn_deq(uint32_t q, float qmin, float qscale) { return qmin + (float)q * qscale; }
+// squared distance of a query to a scene point: pcd_scene.h:88-91, whose operand order IS the parity contract (the unit is compiled with
+// -ffp-contract=off, so every caller gets the same float).  P: pr_vec3 or a {x, y, z, .} record.
+template <class P>
+__device__ __forceinline__ float dist_sq(float sx, float sy, float sz, const P &p) { return (sx - p.x) * (sx - p.x) + (sy - p.y) * (sy - p.y) + (sz - p.z) * (sz - p.z); }
+// Bound a search may start from when a scene point at squared distance d2 is known to exist: inflated by one part in a million so that the point
+// itself -- or an equal one visited earlier -- is still found by the strict '<' of the search (nn_seed_bound has the argument) ...
+__device__ __forceinline__ float seed_bound_of(float d2) { return d2 * 1.000001f + 1e-30f; }
+// ... and from a ring's selection key, which understates its cell's exact distance by up to 2^-17 (ring_key): inflated by 2e-5
+__device__ __forceinline__ float ring_bound_of(float key) { return key * 1.00002f + 1e-30f; }
 __device__ __forceinline__ float box_dist_sq(float sx, float sy, float sz, const float4 lo, const float4 hi)
 {
     float lb = 0;
@@ -21,20 +31,22 @@ __device__ __forceinline__ float box_dist_sq(float sx, float sy, float sz, const
     return lb;
 }
 
+// `best_init`: the bound the walk starts from; `none`: what it reports when no point lies strictly below that bound and the bound itself passes
+// the acceptance test -- the reference (best = FLT_MAX, best_i = 0) then reports point 0, a walk started from a seed bound reports nothing (-1 = kNoPrev).
+// kUseLds: the leading s.lds_nodes entries of `topo` are staged in LDS.  Returns the winner's index, or kNoPrev.
 template <bool kUseLds>
-__device__ __forceinline__ bool query_nn(const SceneNNDev &s, const int4 *lds_topo, float sx, float sy, float sz, Corr &c)
+__device__ __forceinline__ uint32_t nn_walk_stackless(const SceneNNDev &s, const int4 *lds_topo, float sx, float sy, float sz, float best_init, int none)
 {
-    int cur = 0, prev = -1, best_i = 0;
+    int cur = 0, prev = -1, best_i = none;
     bool climbing = false;
-    float best = FLT_MAX;
+    float best = best_init;
     while (cur >= 0) {
         const int4 t = (kUseLds && (uint32_t)cur < s.lds_nodes) ? lds_topo[cur] : s.topo[cur];
         const int parent = (t.w & 0x3fffffff) - 1;
         const bool leaf = t.z < 0;
         if (!climbing && leaf) {
             for (int i = t.x; i < t.y; ++i) {
-                const float4 p = s.pts[i];
-                const float d2 = (sx - p.x) * (sx - p.x) + (sy - p.y) * (sy - p.y) + (sz - p.z) * (sz - p.z);
+                const float d2 = dist_sq(sx, sy, sz, s.pts[i]);
                 if (d2 < best) { best = d2; best_i = i; }
             }
             climbing = true; prev = cur; cur = parent;
@@ -52,11 +64,23 @@ __device__ __forceinline__ bool query_nn(const SceneNNDev &s, const int4 *lds_to
         }
         prev = cur; cur = parent;
     }
-    if (!(best < s.max_dist_diff * s.max_dist_diff)) return false;
+    return (best < s.max_dist_diff * s.max_dist_diff) ? (uint32_t)best_i : kNoPrev;
+}
+// the reference's own query: unbounded, the winner's point and normal
+template <bool kUseLds>
+__device__ __forceinline__ bool query_nn(const SceneNNDev &s, const int4 *lds_topo, float sx, float sy, float sz, Corr &c)
+{
+    const uint32_t best_i = nn_walk_stackless<kUseLds>(s, lds_topo, sx, sy, sz, FLT_MAX, 0);
+    if (best_i == kNoPrev) return false;
     const float *d = reinterpret_cast<const float *>(s.pcd + best_i);
     const float *n = reinterpret_cast<const float *>(s.normal + best_i);
     c.dx = d[0]; c.dy = d[1]; c.dz = d[2]; c.nx = n[0]; c.ny = n[1]; c.nz = n[2];
     return true;
+}
+// started from a bound (an existing point's distance, inflated: seed_bound_of): the ordered walk ties and overflows of the wide search fall back to.  No LDS.
+__device__ __forceinline__ uint32_t query_nn_bounded(const SceneNNDev &s, float sx, float sy, float sz, float best_init)
+{
+    return nn_walk_stackless<false>(s, nullptr, sx, sy, sz, best_init, -1);
 }
 
 // Stack variant of the same search.  The order in which leaves are visited is the reference's
@@ -67,7 +91,6 @@ __device__ __forceinline__ bool query_nn(const SceneNNDev &s, const int4 *lds_to
 // once, as one 64-byte record that already contains both children's boxes.
 //   record = { split_v | left, child1 | right, child2 | -1, dim,  c1.min.xyz c1.max.xyz  c2.min.xyz c2.max.xyz }
 constexpr int kLeafBatch = PR_LEAF_BATCH;
-constexpr uint32_t kNoPrev = 0xffffffffu;
 
 // Bound a search may start from when scene point `seed` is known to exist: its distance, inflated by one part in a million so
 // that the point itself -- or an equal one visited earlier -- is still found by the strict '<' of the search.  The bound only
@@ -77,12 +100,29 @@ __device__ __forceinline__ void nn_seed_bound(const SceneNNDev &s, float sx, flo
 {
     const pr_vec3 p = s.pcd[seed != kNoPrev ? seed : 0u];
     if (seed != kNoPrev) {
-        const float d2 = (sx - p.x) * (sx - p.x) + (sy - p.y) * (sy - p.y) + (sz - p.z) * (sz - p.z);
-        const float b = d2 * 1.000001f + 1e-30f;
+        const float b = seed_bound_of(dist_sq(sx, sy, sz, p));
         if (b < best) best = b;
     }
 }
 
+// the per-lane stack: the next parked node whose bound still admits it (cur), or false when none is left
+__device__ __forceinline__ bool stack_pop(const int *stk_node, const float *stk_lb, int &sp, float best, int &cur)
+{
+    while (sp > 0) {
+        --sp;
+        if (stk_lb[sp * kBlockThreads] <= best) { cur = stk_node[sp * kBlockThreads]; return true; }
+    }
+    return false;
+}
+// distance of the query to a child box of a compact record: three words of 16-bit corners {lo.x | lo.y, lo.z | hi.x, hi.y | hi.z}, dequantised
+__device__ __forceinline__ float compact_box_dist_sq(const SceneNNDev &s, float sx, float sy, float sz, uint32_t u0, uint32_t u1, uint32_t u2)
+{
+    const float4 lo = make_float4(nn_deq(u0 & 0xffffu, s.qmin[0], s.qscale[0]), nn_deq(u0 >> 16, s.qmin[1], s.qscale[1]),
+                                  nn_deq(u1 & 0xffffu, s.qmin[2], s.qscale[2]), 0.0f);
+    const float4 hi = make_float4(nn_deq(u1 >> 16, s.qmin[0], s.qscale[0]), nn_deq(u2 & 0xffffu, s.qmin[1], s.qscale[1]),
+                                  nn_deq(u2 >> 16, s.qmin[2], s.qscale[2]), 0.0f);
+    return box_dist_sq(sx, sy, sz, lo, hi);
+}
 // kCode = stack entries per lane (16 / 24), + 0x100 when the scene's compact 32-byte records are used.
 // best_init: the bound the search starts from (<= max_dist_diff^2, see PR_NN_BOUNDED; tightened by nn_seed_bound).
 // work counters of the search (SURVEY 8d "count its own visits"): per lane, summed into SceneNNDev::counters when that is set
@@ -120,29 +160,15 @@ __device__ __forceinline__ bool query_nn_stack_from(const SceneNNDev &s, const f
                 const int near_c = (int)(left_near ? c1 : c1 + 1u), far_c = (int)(left_near ? c1 + 1u : c1);
                 if (diff * diff <= best && sp < kDepth) {
                     if (!wide) { A = s.rec32[(size_t)cur * 2]; B = s.rec32[(size_t)cur * 2 + 1]; }
-                    const uint32_t u0 = left_near ? B.y : A.z, u1 = left_near ? B.z : A.w, u2 = left_near ? B.w : B.x;
-                    const float4 lo = make_float4(nn_deq(u0 & 0xffffu, s.qmin[0], s.qscale[0]), nn_deq(u0 >> 16, s.qmin[1], s.qscale[1]),
-                                                  nn_deq(u1 & 0xffffu, s.qmin[2], s.qscale[2]), 0.0f);
-                    const float4 hi = make_float4(nn_deq(u1 >> 16, s.qmin[0], s.qscale[0]), nn_deq(u2 & 0xffffu, s.qmin[1], s.qscale[1]),
-                                                  nn_deq(u2 >> 16, s.qmin[2], s.qscale[2]), 0.0f);
-                    const float lb = box_dist_sq(sx, sy, sz, lo, hi);
+                    const float lb = compact_box_dist_sq(s, sx, sy, sz, left_near ? B.y : A.z, left_near ? B.z : A.w, left_near ? B.w : B.x);     // the far child's
                     if (lb <= best) { stk_node[sp * kBlockThreads] = far_c; stk_lb[sp * kBlockThreads] = lb; ++sp; }
                 }
                 // While the bound is wide the record is in registers anyway: the near child is entered only if its own box is
                 // within the bound (the reference walks into it unconditionally and finds nothing there).
                 if (wide) {
-                    const uint32_t v0 = left_near ? A.z : B.y, v1 = left_near ? A.w : B.z, v2 = left_near ? B.x : B.w;
-                    const float4 nlo = make_float4(nn_deq(v0 & 0xffffu, s.qmin[0], s.qscale[0]), nn_deq(v0 >> 16, s.qmin[1], s.qscale[1]),
-                                                   nn_deq(v1 & 0xffffu, s.qmin[2], s.qscale[2]), 0.0f);
-                    const float4 nhi = make_float4(nn_deq(v1 >> 16, s.qmin[0], s.qscale[0]), nn_deq(v2 & 0xffffu, s.qmin[1], s.qscale[1]),
-                                                   nn_deq(v2 >> 16, s.qmin[2], s.qscale[2]), 0.0f);
-                    if (!(box_dist_sq(sx, sy, sz, nlo, nhi) <= best)) {
-                        bool found = false;
-                        while (sp > 0) {
-                            --sp;
-                            if (stk_lb[sp * kBlockThreads] <= best) { cur = stk_node[sp * kBlockThreads]; found = true; break; }
-                        }
-                        if (!found) break;
+                    const float nlb = compact_box_dist_sq(s, sx, sy, sz, left_near ? A.z : B.y, left_near ? A.w : B.z, left_near ? B.x : B.w);
+                    if (!(nlb <= best)) {
+                        if (!stack_pop(stk_node, stk_lb, sp, best, cur)) break;
                         continue;
                     }
                 }
@@ -173,18 +199,13 @@ __device__ __forceinline__ bool query_nn_stack_from(const SceneNNDev &s, const f
                 for (int k = 0; k < kLeafBatch; ++k) {
                     idx[k] = (i + k < hi) ? (i + k) : (hi - 1);
                     const pr_vec3 p = s.pcd[idx[k]];                 // 12-byte points: a quarter fewer bytes through the L1 than the padded copy
-                    d2[k] = (sx - p.x) * (sx - p.x) + (sy - p.y) * (sy - p.y) + (sz - p.z) * (sz - p.z);
+                    d2[k] = dist_sq(sx, sy, sz, p);
                 }
 #pragma unroll
                 for (int k = 0; k < kLeafBatch; ++k)
                     if (d2[k] < best) { best = d2[k]; best_i = idx[k]; }
             }
-            bool found = false;
-            while (sp > 0) {
-                --sp;
-                if (stk_lb[sp * kBlockThreads] <= best) { cur = stk_node[sp * kBlockThreads]; found = true; break; }
-            }
-            if (!found) break;
+            if (!stack_pop(stk_node, stk_lb, sp, best, cur)) break;
         } else {
             const int dim = __float_as_int(h.w);
             const float q = (dim == 0) ? sx : ((dim == 1) ? sy : sz);
@@ -244,48 +265,6 @@ __device__ __forceinline__ bool query_nn_stack(const SceneNNDev &s, const float4
 constexpr uint32_t kWideLeaf = 0x80000000u, kWideEmpty = 0xffffffffu;
 constexpr uint32_t kWideMaxLeafPoints = 15u, kWideFirstMask = 0x07ffffffu;
 __device__ __forceinline__ float nn_deq_fma(uint32_t q, float qmin, float qscale) { return __builtin_fmaf((float)q, qscale, qmin); }
-__device__ __forceinline__ float wide_box_lb(float sx, float sy, float sz, uint32_t u0, uint32_t u1, uint32_t u2, const SceneNNDev &s)
-{
-    const float lox = nn_deq_fma(u0 & 0xffffu, s.qmin[0], s.qscale[0]), loy = nn_deq_fma(u0 >> 16, s.qmin[1], s.qscale[1]);
-    const float loz = nn_deq_fma(u1 & 0xffffu, s.qmin[2], s.qscale[2]), hix = nn_deq_fma(u1 >> 16, s.qmin[0], s.qscale[0]);
-    const float hiy = nn_deq_fma(u2 & 0xffffu, s.qmin[1], s.qscale[1]), hiz = nn_deq_fma(u2 >> 16, s.qmin[2], s.qscale[2]);
-    // = box_dist_sq: per axis (lo - q)^2 below the box, (hi - q)^2 == (q - hi)^2 above it, 0 inside
-    const float dx = fmaxf(fmaxf(lox - sx, sx - hix), 0.0f), dy = fmaxf(fmaxf(loy - sy, sy - hiy), 0.0f), dz = fmaxf(fmaxf(loz - sz, sz - hiz), 0.0f);
-    return dx * dx + dy * dy + dz * dz;
-}
-// Scene_nn::query pcd_scene.h:60-136 as query_nn above, started from a bound (an existing point's distance, inflated: nn_seed_bound) and
-// reporting the winner's index: the ordered walk ties and overflows of the wide search fall back to.  No LDS.
-__device__ __forceinline__ uint32_t query_nn_bounded(const SceneNNDev &s, float sx, float sy, float sz, float best_init)
-{
-    int cur = 0, prev = -1, best_i = -1;
-    bool climbing = false;
-    float best = best_init;
-    while (cur >= 0) {
-        const int4 t = s.topo[cur];
-        const int parent = (t.w & 0x3fffffff) - 1;
-        if (!climbing && t.z < 0) {
-            for (int i = t.x; i < t.y; ++i) {
-                const float4 p = s.pts[i];
-                const float d2 = (sx - p.x) * (sx - p.x) + (sy - p.y) * (sy - p.y) + (sz - p.z) * (sz - p.z);
-                if (d2 < best) { best = d2; best_i = i; }
-            }
-            climbing = true; prev = cur; cur = parent;
-            continue;
-        }
-        const int dim = (int)((uint32_t)t.w >> 30);
-        const float q = (dim == 0) ? sx : ((dim == 1) ? sy : sz);
-        const float diff = q - __int_as_float(t.x);
-        const int near_c = (diff < 0) ? t.y : t.z;
-        const int far_c  = (diff < 0) ? t.z : t.y;
-        if (!climbing) { prev = cur; cur = near_c; continue; }
-        if (prev == near_c) {
-            const float lb = box_dist_sq(sx, sy, sz, s.bmin[far_c], s.bmax[far_c]);
-            if (lb <= best) { prev = cur; cur = far_c; climbing = false; continue; }
-        }
-        prev = cur; cur = parent;
-    }
-    return (best_i >= 0 && best < s.max_dist_diff * s.max_dist_diff) ? (uint32_t)best_i : kNoPrev;
-}
 
 // ---- pixel grid of a kd-tree scene ---------------------------------------------------------------------------------------
 // A Scene_nn is made from a depth image (pcd_scene.cpp:10-29), so its points are the pixels of that image: cell (px, py) of the
@@ -301,6 +280,15 @@ __device__ __forceinline__ void grid_project(const SceneNNDev &s, float x, float
     u = x / z * s.gfx + s.gcx + 0.5f;
     v = y / z * s.gfy + s.gcy + 0.5f;
 }
+// the pixel a point projects into; false when the projection is not finite (a point at the camera's plane, NaN): no pixel then
+__device__ __forceinline__ bool grid_pixel(const SceneNNDev &s, float x, float y, float z, int &px, int &py)
+{
+    float u, v;
+    grid_project(s, x, y, z, u, v);
+    if (!(u > -1e6f && u < 1e6f && v > -1e6f && v < 1e6f)) return false;
+    px = (int)floorf(u); py = (int)floorf(v);
+    return true;
+}
 constexpr int kGridMaxW = PR_GRID_MAXW;                                     // windows up to 5 x 5 cells; larger ones go to the tree
 // half-widths of the pixel window that holds every scene point closer than sqrt(bound); false when it exceeds kGridMaxW
 __device__ __forceinline__ bool grid_window(const SceneNNDev &s, float sx, float sy, float sz, float bound, int &wx, int &wy)
@@ -312,6 +300,14 @@ __device__ __forceinline__ bool grid_window(const SceneNNDev &s, float sx, float
     if (!(du <= (float)kGridMaxW - 1e-3f && dv <= (float)kGridMaxW - 1e-3f)) return false;
     wx = (int)ceilf(du + 1e-3f); wy = (int)ceilf(dv + 1e-3f);
     return true;
+}
+// the largest radius around the query whose window still fits kGridMaxW cells either way: du(r) = fx (z + |x|) r / (z (z - r)) <= W  <=>
+// r <= W z^2 / (fx (z + |x|) + W z).  Approximate is fine: grid_window VERIFIES the window of whatever radius is taken.
+__device__ __forceinline__ float window_cover_radius(const SceneNNDev &s, float sx, float sy, float sz)
+{
+    const float W = (float)kGridMaxW - 4e-3f;
+    const float rx = W * sz * sz * margin_rcp(s.gfx * (sz + fabsf(sx)) + W * sz), ry = W * sz * sz * margin_rcp(s.gfy * (sz + fabsf(sy)) + W * sz);
+    return fminf(rx, ry) * 0.999f;
 }
 // Coarse-to-fine descent through the representative points: the nearest of ALL 64 x 64-block representatives, then the nearest
 // 16 x 16-block representative in and around that block (the block's 4 x 4 children plus the row and column before them: PR_RING_W / PR_RING_OFF), then 4 x 4 blocks, then pixels.
@@ -348,7 +344,7 @@ __device__ __forceinline__ void grid_ring_min(const float4 *__restrict__ level, 
 #pragma unroll
             for (int dx = 0; dx < kW; ++dx) {
                 if (dy0 + r >= kW) continue;
-                const float d2 = (sx - c[r][dx].x) * (sx - c[r][dx].x) + (sy - c[r][dx].y) * (sy - c[r][dx].y) + (sz - c[r][dx].z) * (sz - c[r][dx].z);
+                const float d2 = dist_sq(sx, sy, sz, c[r][dx]);
                 const bool lt = d2 < best;
                 best = lt ? d2 : best; kbest = lt ? (dy0 + r) * kW + dx : kbest;
             }
@@ -419,12 +415,10 @@ __device__ __forceinline__ void grid_pyramid_bound(const SceneNNDev &s, float sx
     // the block's edge): same box, bound 1.58 -> 1.46 ms and walk 2.94 -> 2.80 ms per group-step, configs[2] 50.9 -> 53.2 k poses/s.  A ring that
     // holds no scene point at all (the query projects far off the object) falls through to the blocks of 64 x 64 pixels below.
     if (w16 >= PR_RING16_W && h16 >= PR_RING16_W && w16 >= PR_RING_W && h16 >= PR_RING_W) {
-        float u, v;
-        grid_project(s, sx, sy, sz, u, v);
-        if (u > -1e6f && u < 1e6f && v > -1e6f && v < 1e6f) {
+        int pu, pv;
+        if (grid_pixel(s, sx, sy, sz, pu, pv)) {
             const float2v sxy{ sx, sy };
             uint32_t k = 0xffffffffu;
-            const int pu = (int)floorf(u), pv = (int)floorf(v);
             if (late && PR_DESCENT_LATE == 2) {                  // straight to the 4 x 4-pixel blocks around the projection
                 k = grid_ring_key<PR_RING_W>(s.pyr4, w4, h4, (pu >> 2) - PR_RING_W / 2, (pv >> 2) - PR_RING_W / 2, sxy, sz, bx, by);
             } else {
@@ -435,7 +429,7 @@ __device__ __forceinline__ void grid_pyramid_bound(const SceneNNDev &s, float sx
             if (k < 0x7f800000u) {
                 k = min(k, grid_ring_key<PR_RING_W>(s.grid, (int)s.gw, (int)s.gh, bx * 4 - PR_RING_OFF, by * 4 - PR_RING_OFF, sxy, sz, bx, by));
                 // (a further ring of pixels centred on the landing pixel: walk pass 0 1195 -> 1146 us, bound pass 0 275 -> 355 us -- not kept)
-                const float bk = __uint_as_float(k) * 1.00002f + 1e-30f;     // the landing cell's exact distance is below this (see ring_key)
+                const float bk = ring_bound_of(__uint_as_float(k));          // the landing cell's exact distance is below this (see ring_key)
                 if (bk < best) best = bk;
                 return;
             }
@@ -443,15 +437,14 @@ __device__ __forceinline__ void grid_pyramid_bound(const SceneNNDev &s, float sx
     }
     {   // the 3 x 3 blocks of 64 x 64 pixels around the query's own projection first: a hypothesis within a few centimetres / degrees of the
         // scene pose has its neighbour there; only a query that finds nothing there looks at all blocks
-        float u, v;
-        grid_project(s, sx, sy, sz, u, v);
-        if (u > -1e6f && u < 1e6f && v > -1e6f && v < 1e6f) {
-            const int cx = min(max((int)floorf(u) >> 6, 0), w64 - 1), cy = min(max((int)floorf(v) >> 6, 0), h64 - 1);
+        int pu, pv;
+        if (grid_pixel(s, sx, sy, sz, pu, pv)) {
+            const int cx = min(max(pu >> 6, 0), w64 - 1), cy = min(max(pv >> 6, 0), h64 - 1);
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
                 const int x = min(max(cx + k % 3 - 1, 0), w64 - 1), y = min(max(cy + k / 3 - 1, 0), h64 - 1);
                 const float4 c = s.pyr64[y * w64 + x];
-                const float d2 = (sx - c.x) * (sx - c.x) + (sy - c.y) * (sy - c.y) + (sz - c.z) * (sz - c.z);
+                const float d2 = dist_sq(sx, sy, sz, c);
                 if (d2 < dmin) { dmin = d2; bx = x; by = y; }
             }
         }
@@ -459,7 +452,7 @@ __device__ __forceinline__ void grid_pyramid_bound(const SceneNNDev &s, float sx
     if (!(dmin < 1.0e20f))
     for (int i = 0; i < w64 * h64; ++i) {                          // wave-uniform addresses: every lane reads the same few cache lines
         const float4 c = s.pyr64[i];
-        const float d2 = (sx - c.x) * (sx - c.x) + (sy - c.y) * (sy - c.y) + (sz - c.z) * (sz - c.z);
+        const float d2 = dist_sq(sx, sy, sz, c);
         if (d2 < dmin) { dmin = d2; bx = i % w64; by = i / w64; }
     }
     dall = dmin;
@@ -468,8 +461,8 @@ __device__ __forceinline__ void grid_pyramid_bound(const SceneNNDev &s, float sx
         uint32_t k = grid_ring_key<PR_RING_W>(s.pyr16, w16, h16, bx * 4 - PR_RING_OFF, by * 4 - PR_RING_OFF, sxy, sz, bx, by);
         k = min(k, grid_ring_key<PR_RING_W>(s.pyr4, w4, h4, bx * 4 - PR_RING_OFF, by * 4 - PR_RING_OFF, sxy, sz, bx, by));
         k = min(k, grid_ring_key<PR_RING_W>(s.grid, (int)s.gw, (int)s.gh, bx * 4 - PR_RING_OFF, by * 4 - PR_RING_OFF, sxy, sz, bx, by));
-        const float bk = __uint_as_float(k) * 1.00002f + 1e-30f;     // the landing cell's exact distance is below this (see above); +inf / NaN keys give no bound
-        const float b0 = dall * 1.000001f + 1e-30f;
+        const float bk = ring_bound_of(__uint_as_float(k));          // the landing cell's exact distance is below this (see above); +inf / NaN keys give no bound
+        const float b0 = seed_bound_of(dall);
         if (b0 < best) best = b0;
         if (bk < best) best = bk;
         return;
@@ -478,7 +471,7 @@ __device__ __forceinline__ void grid_pyramid_bound(const SceneNNDev &s, float sx
     grid_ring_min(s.pyr16, w16, h16, bx * 4 - PR_RING_OFF, by * 4 - PR_RING_OFF, PR_RING_W, sx, sy, sz, d, bx, by);   dall = fminf(dall, d);
     grid_ring_min(s.pyr4, w4, h4, bx * 4 - PR_RING_OFF, by * 4 - PR_RING_OFF, PR_RING_W, sx, sy, sz, d, bx, by);       dall = fminf(dall, d);
     grid_ring_min(s.grid, (int)s.gw, (int)s.gh, bx * 4 - PR_RING_OFF, by * 4 - PR_RING_OFF, PR_RING_W, sx, sy, sz, d, bx, by);   dall = fminf(dall, d);
-    const float b = dall * 1.000001f + 1e-30f;                       // empty cells hold huge coordinates: inf
+    const float b = seed_bound_of(dall);                             // empty cells hold huge coordinates: inf
     if (b < best) best = b;
 }
 // `full` (round 5, "window first"): the caller has no tight bound yet -- only a previous winner a few millimetres away.  The LARGEST window is
@@ -492,9 +485,7 @@ __device__ __forceinline__ bool grid_search(const SceneNNDev &s, float sx, float
     int wx, wy;
     float cover_full = 0.0f;
     if (full) {
-        const float W = (float)kGridMaxW - 4e-3f;
-        const float rx = W * sz * sz * margin_rcp(s.gfx * (sz + fabsf(sx)) + W * sz), ry = W * sz * sz * margin_rcp(s.gfy * (sz + fabsf(sy)) + W * sz);
-        const float rc = fminf(rx, ry) * 0.999f;                   // (grid_window below VERIFIES that the window of rc fits: rc itself may be approximate)
+        const float rc = window_cover_radius(s, sx, sy, sz);
         if (!(rc > 0.0f) || !grid_window(s, sx, sy, sz, rc * rc, wx, wy)) return false;
         const float c2 = rc * rc * 0.9999f;
         if (c2 < bound) bound = c2;                                // only points strictly inside the covered radius can win
@@ -504,33 +495,32 @@ __device__ __forceinline__ bool grid_search(const SceneNNDev &s, float sx, float
     // fits it is taken instead: the extra ring costs a few cells and tells how far the RUNNER-UP is (other_sq), which is what lets
     // the following passes keep this winner without searching (nn_search_kernel).  `settle`: the point has (nearly) stopped moving,
     // so whatever margin is found will last for the rest of the loop -- the radius is then not sqrt(bound) + half a millimetre but the
-    // largest the 5 x 5 window covers (du(r) = fx (z + |x|) r / (z (z - r)) <= W  <=>  r <= W z^2 / (fx (z + |x|) + W z)): with the
-    // fixed pad a point whose neighbour is more than half a millimetre away (a quarter of them: the depth image is in whole
-    // millimetres) never got a margin at all and went through the window in every pass.
+    // largest the 5 x 5 window covers (window_cover_radius): with the fixed pad a point whose neighbour is more than half a millimetre
+    // away (a quarter of them: the depth image is in whole millimetres) never got a margin at all and went through the window in every pass.
     float cover = bound;
     if (full) cover = cover_full;
     else if (other_sq) {
         const float rb = margin_sqrt(bound) * 1.000001f;
         float rc = rb + PR_NN_COVER_PAD;
-        if (settle) {
-            const float W = (float)kGridMaxW - 4e-3f;
-            const float rx = W * sz * sz * margin_rcp(s.gfx * (sz + fabsf(sx)) + W * sz), ry = W * sz * sz * margin_rcp(s.gfy * (sz + fabsf(sy)) + W * sz);
-            rc = fminf(rx, ry) * 0.999f;                           // (approximate is fine: grid_window verifies the window of whatever radius is taken)
-        }
+        if (settle) rc = window_cover_radius(s, sx, sy, sz);
         if (rc > rb && grid_window(s, sx, sy, sz, rc * rc, wx, wy)) cover = rc * rc;
         else if (settle) { rc = rb + PR_NN_COVER_PAD; if (grid_window(s, sx, sy, sz, rc * rc, wx, wy)) cover = rc * rc; }
     }
     if (!full && cover == bound && !grid_window(s, sx, sy, sz, bound, wx, wy)) return false;
-    float u, v;
-    grid_project(s, sx, sy, sz, u, v);
-    if (!(u > -1e6f && u < 1e6f && v > -1e6f && v < 1e6f)) return false;
-    const int cx0 = (int)floorf(u), cy0 = (int)floorf(v);
+    int cx0, cy0;
+    if (!grid_pixel(s, sx, sy, sz, cx0, cy0)) return false;
     const int x0 = max(cx0 - wx, 0), x1 = min(cx0 + wx, (int)s.gw - 1);
     const int y0 = max(cy0 - wy, 0), y1 = min(cy0 + wy, (int)s.gh - 1);
     if (x0 > x1 || y0 > y1) return false;
     if (cells) *cells += (uint32_t)((x1 - x0 + 1) * (y1 - y0 + 1));
     float best = bound, second = cover;                           // `second`: smallest squared distance of any scene point other than the winner,
     int best_i = -1, ties = 0;                                    // capped at what the window covers (points outside it are at least that far)
+    auto candidate = [&](const float4 c) {                        // one cell of the window, in the window's visiting order
+        const float d2 = dist_sq(sx, sy, sz, c);
+        if (d2 < best) { if (best_i >= 0) second = best; best = d2; best_i = __float_as_int(c.w); ties = 0; }
+        else if (d2 == best && best_i >= 0) ++ties;
+        else if (d2 < second) second = d2;
+    };
     if (wx <= 1 && wy <= 1) {
         // the common case once aligned (a bound below one pixel): the 3 x 3 cells in ONE round trip instead of one per row
         float4 c[9];
@@ -539,62 +529,32 @@ __device__ __forceinline__ bool grid_search(const SceneNNDev &s, float sx, float
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
             if (x0 + i % 3 > x1 || y0 + i / 3 > y1) continue;    // (clamped repeats must not count as ties)
-            const float d2 = (sx - c[i].x) * (sx - c[i].x) + (sy - c[i].y) * (sy - c[i].y) + (sz - c[i].z) * (sz - c[i].z);
-            if (d2 < best) { if (best_i >= 0) second = best; best = d2; best_i = __float_as_int(c[i].w); ties = 0; }
-            else if (d2 == best && best_i >= 0) ++ties;
-            else if (d2 < second) second = d2;
+            candidate(c[i]);
         }
-        if (best_i < 0 || ties != 0) { if (full && best_sq && best_i >= 0) *best_sq = best; return false; }     // (a tie: still an existing point's distance)
-        winner = (uint32_t)best_i;
-        if (best_sq) *best_sq = best;
-        if (other_sq) *other_sq = second;
-        return true;
-    }
-    constexpr int kWinRows = PR_WIN_ROWS;                           // rows of the window in flight at a time (one round trip per group)
-    for (int y = y0; y <= y1; y += kWinRows) {
-        float4 c[kWinRows][2 * kGridMaxW + 1];
+    } else {
+        constexpr int kWinRows = PR_WIN_ROWS;                       // rows of the window in flight at a time (one round trip per group)
+        for (int y = y0; y <= y1; y += kWinRows) {
+            float4 c[kWinRows][2 * kGridMaxW + 1];
 #pragma unroll
-        for (int r = 0; r < kWinRows; ++r) {
-            const float4 *row = s.grid + (size_t)min(y + r, y1) * s.gw;
+            for (int r = 0; r < kWinRows; ++r) {
+                const float4 *row = s.grid + (size_t)min(y + r, y1) * s.gw;
 #pragma unroll
-            for (int i = 0; i < 2 * kGridMaxW + 1; ++i) c[r][i] = row[min(x0 + i, x1)];
-        }
-#pragma unroll
-        for (int r = 0; r < kWinRows; ++r)
-#pragma unroll
-            for (int i = 0; i < 2 * kGridMaxW + 1; ++i) {
-                if (y + r > y1 || x0 + i > x1) continue;             // (clamped repeats must not count as ties)
-                const float d2 = (sx - c[r][i].x) * (sx - c[r][i].x) + (sy - c[r][i].y) * (sy - c[r][i].y) + (sz - c[r][i].z) * (sz - c[r][i].z);
-                if (d2 < best) { if (best_i >= 0) second = best; best = d2; best_i = __float_as_int(c[r][i].w); ties = 0; }
-                else if (d2 == best && best_i >= 0) ++ties;
-                else if (d2 < second) second = d2;
+                for (int i = 0; i < 2 * kGridMaxW + 1; ++i) c[r][i] = row[min(x0 + i, x1)];
             }
+#pragma unroll
+            for (int r = 0; r < kWinRows; ++r)
+#pragma unroll
+                for (int i = 0; i < 2 * kGridMaxW + 1; ++i) {
+                    if (y + r > y1 || x0 + i > x1) continue;         // (clamped repeats must not count as ties)
+                    candidate(c[r][i]);
+                }
+        }
     }
-    if (best_i < 0 || ties != 0) { if (full && best_sq && best_i >= 0) *best_sq = best; return false; }
+    if (best_i < 0 || ties != 0) { if (full && best_sq && best_i >= 0) *best_sq = best; return false; }     // (a tie: still an existing point's distance)
     winner = (uint32_t)best_i;
     if (best_sq) *best_sq = best;
     if (other_sq) *other_sq = second;
     return true;
-}
-// a first bound for a query nothing is known about yet: the nearest of the scene points in the 3 x 3 cells around its own pixel
-__device__ __forceinline__ void grid_seed_bound(const SceneNNDev &s, float sx, float sy, float sz, float &best)
-{
-    float u, v;
-    grid_project(s, sx, sy, sz, u, v);
-    if (!(u > -1e6f && u < 1e6f && v > -1e6f && v < 1e6f)) return;
-    const int cx0 = (int)floorf(u), cy0 = (int)floorf(v);
-    float4 c[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const int x = min(max(cx0 + (i % 3) - 1, 0), (int)s.gw - 1), y = min(max(cy0 + (i / 3) - 1, 0), (int)s.gh - 1);
-        c[i] = s.grid[(size_t)y * s.gw + x];
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const float d2 = (sx - c[i].x) * (sx - c[i].x) + (sy - c[i].y) * (sy - c[i].y) + (sz - c[i].z) * (sz - c[i].z);
-        const float b = d2 * 1.000001f + 1e-30f;                  // empty cells hold huge coordinates: b = inf
-        if (b < best) best = b;
-    }
 }
 
 }  // namespace prk

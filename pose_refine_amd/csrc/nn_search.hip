@@ -13,14 +13,82 @@ namespace prk {
 //  hypothesis is still centimetres off the surface -- set the pace of the first passes.  The winner of a query does not depend
 //  on how the search is organised, so the search runs here in whatever order suits it and leaves the winners in `nn_prev`;
 //  the pass that follows (icp_pass_kernel<SceneNNWinners>) gathers them in canonical order -- bit-identical sums.
-//    * a lane walks a RUN of consecutive cloud points (image neighbours): every query but the first of a run starts from the
-//      previous one's winner, whose distance is within microns of the answer (the step between neighbours is lateral);
-//    * the previous pass' winner of the same point bounds the search as before;
-//    * the first query of a run takes a bound from the scene points around its own pixel (grid_seed_bound);
-//    * with a bound that tight the candidates are the handful of scene pixels around the query's pixel: grid_search settles the
-//      query without touching the tree unless there is a tie (the tree's visiting order then decides, as in the reference).
-//  The pending rigid update is applied (and written back) here, so the pass reads the cloud as it is.
+//  Four kernels, each handing what it cannot settle to the next through a queue that keeps the points' order:
+//    * nn_search_kernel, one point per lane and chunk: applies (and writes back) the pending rigid update, so the pass reads the cloud as
+//      it is; KEEPS the previous pass' winner where the slack left by that pass proves it is still the strict minimum; queues the rest
+//      with the bound that winner gives                                                                                  -> queue 1
+//    * nn_bound_kernel, dense lanes: the exact pixel-window scan (grid_search) where the bound or the previous winner is near; else the
+//      descent through the representative points (grid_pyramid_bound; without a pixel grid, down the split planes to the query's own
+//      leaf), 256 deferred queries at a time, and the window again; a unique strict minimum in the window is the winner   -> queue 2
+//    * nn_tree_wide_kernel: the order-free task walk over the wide records, 64 queries per wavefront; ties and task-queue overflows are
+//      repeated by the ordered stackless walk (query_nn_bounded)
+//    * nn_tree_kernel, scenes without wide records: bound, window and the per-lane stack walk (query_nn_stack_from) straight from queue 1.
 // ================================================================================================
+
+// ---- instrumented runs (option "nn_count"): the columns of SceneNNDev::counters, one row of kNNCounters per pass ----------------------
+enum NNCounter : int {
+    kCntQueries,                 // cloud points of the pass                                         (nn_search_kernel)
+    kCntWindow,                  // settled by the pixel window                                      (nn_bound_kernel, nn_tree_kernel)
+    kCntTree,                    // handed to a tree walk                                            (nn_tree_wide_kernel, nn_tree_kernel)
+    kCntDescents,                // descents through the representative points                       (nn_bound_kernel, nn_tree_kernel)
+    kCntNodes, kCntLeaves, kCntLeafPoints,   // tree nodes visited, leaves scanned, leaf points tested   (the walks)
+    kCntCells,                   // window cells read                                                (nn_bound_kernel, nn_tree_kernel)
+    kNNCounters
+};
+static_assert(kNNCounters == 8, "pr_nn_counters and api.nn_counters hand out eight columns per pass");
+// a kernel's per-lane counts -> the pass' row: summed over the wavefront, one atomic per wavefront and non-zero column
+__device__ __forceinline__ void nn_flush_counters(unsigned long long *counters, uint32_t iter, const uint32_t (&v)[kNNCounters])
+{
+#pragma unroll
+    for (int i = 0; i < kNNCounters; ++i) {
+        uint32_t t = v[i];
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+        if ((threadIdx.x & 63u) == 0u && t) atomicAdd(&counters[(size_t)iter * kNNCounters + i], (unsigned long long)t);
+    }
+}
+
+// ---- the queues ---------------------------------------------------------------------------------------------------------------------
+// Ordered append: the rank of this lane among the workgroup's `pending` lanes -- waves in order, lanes in order, so a queue filled through
+// it keeps the points' order -- and their number.  Called by every lane of the workgroup; `wave_n` = four words of LDS.  ONE barrier in
+// here, behind the store of the wave counts; the caller adds its base (an atomicAdd on a queue counter, the fill level of a list in LDS)
+// and puts a barrier between its last read of `wave_n` / `total` and the next call with the same `wave_n`.
+__device__ __forceinline__ uint32_t wg_ordered_rank(bool pending, uint32_t *wave_n, uint32_t &total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(pending);
+    if (lane == 0) wave_n[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (uint32_t w2 = 0; w2 < wave; ++w2) rank += wave_n[w2];
+    total = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    return rank;
+}
+// Queue 1 entry = {point, bound bits}; the bound carries two flags: its sign says "no descent needed" (a previous winner and a step below
+// PR_NN_NODESCENT), its lowest mantissa bit says "settle" (the point has stopped moving: take the widest cover the window holds).  Clearing that
+// bit on the way in and setting it on the way out rounds the bound UP by at most an ulp, far inside the 1e-6 by which a seed bound is inflated.
+// Queue 2 entries are plain {point, bound bits}.
+__device__ __forceinline__ uint2 pack_queued(uint32_t point, float bound, bool no_descent, bool settle)
+{
+    return make_uint2(point, (__float_as_uint(bound) & ~1u) | (settle ? 1u : 0u) | (no_descent ? 0x80000000u : 0u));
+}
+__device__ __forceinline__ void unpack_queued(const uint2 e, uint32_t &point, float &bound, bool &no_descent, bool &settle)
+{
+    point = e.x; no_descent = (e.y & 0x80000000u) != 0u; settle = (e.y & 1u) != 0u;
+    bound = __uint_as_float((e.y & 0x7fffffffu) | 1u);
+}
+// Entry of nn_bound_kernel's deferred list = {point | tried << 30 | settle << 31, bound bits}: the two flags in the point's top bits are why a
+// cloud is limited to kNNMaxCloudPoints (launch_nn_search checks; a cloud of 2^30 points is 12 GiB)
+constexpr uint32_t kNNMaxCloudPoints = 1u << 30;
+__device__ __forceinline__ uint2 pack_deferred(uint32_t point, float bound, bool tried, bool settle)
+{
+    return make_uint2(point | (tried ? kNNMaxCloudPoints : 0u) | (settle ? 2u * kNNMaxCloudPoints : 0u), __float_as_uint(bound));
+}
+__device__ __forceinline__ void unpack_deferred(const uint2 e, uint32_t &point, float &bound, bool &tried, bool &settle)
+{
+    point = e.x & (kNNMaxCloudPoints - 1u); tried = (e.x & kNNMaxCloudPoints) != 0u; settle = (e.x & (2u * kNNMaxCloudPoints)) != 0u;
+    bound = __uint_as_float(e.y);
+}
+
 __global__ __launch_bounds__(256) void nn_search_kernel(IcpBatch b, SceneNNDev scene, uint32_t run)
 {
     const uint32_t pose = blockIdx.y;
@@ -39,30 +107,25 @@ __global__ __launch_bounds__(256) void nn_search_kernel(IcpBatch b, SceneNNDev s
     for (int i = 0; i < 12; ++i) M[i] = xf ? pm.xform[i] : 0.0f;
     const float accept = scene.max_dist_diff * scene.max_dist_diff;
 
-    // Two phases.  (1) Every lane takes one point per chunk (lane t of chunk k: point first + 256 k + t -- adjacent lanes hold
-    // adjacent points), applies the pending update and tries the cheap way: the bound from the previous pass' winner and, if that
-    // bound is a pixel or two wide, the exact window scan.  (2) What is left -- a few per cent of the points once aligned, most of
-    // them on the first passes -- is packed into dense lanes (in point order, so neighbours stay neighbours) and only then pays for
-    // the descent through the representative points and the tree search.  Without the packing four of five wavefronts ran a whole
-    // tree search for two or three of their lanes.
-    // the hypothesis' queue lives next to its winners (same indexing, so it can never overflow): (point, bound) per entry, filled
-    // through this pass' counter of the hypothesis (two counters alternate between passes; nn_tree_kernel re-arms the idle one)
+    // Every lane takes one point per chunk (lane t of chunk k: point first + 256 k + t -- adjacent lanes hold adjacent points), applies
+    // the pending update and tries to keep the previous winner.  What is left -- a few per cent of the points once aligned, most of them
+    // on the first passes -- is packed into dense lanes (in point order, so neighbours stay neighbours) for the kernels that follow:
+    // without the packing four of five wavefronts ran a whole tree search for two or three of their lanes.
+    // The hypothesis' queue lives next to its winners (same indexing, so it can never overflow), filled through this pass' counter of
+    // the hypothesis (two counters alternate between passes; the kernel that reads the queue re-arms the idle one).
     uint2 *queue = b.nn_queue + pm.start;
     uint32_t *q_count = b.nn_qcount + kQCountStride * pose + (b.iter & 1u);
-    __shared__ uint32_t wg_count, wg_base;
-    __shared__ uint32_t wave_base[4];
-    if (threadIdx.x == 0) wg_count = 0u;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    __shared__ uint32_t wg_base;
+    __shared__ uint32_t wave_n[4];
     const uint32_t j0 = first + threadIdx.x;
-    NNCount cnt;
-    uint32_t n_query = 0, n_window = 0, n_cells = 0, n_kept = 0;
+    uint32_t n_query = 0;
     float *slk = b.nn_slack + pm.start;
     for (uint32_t k = 0; k < run; ++k) {
         const uint32_t j = j0 + k * kBlockThreads;
         const bool live = j < n;
         bool pending = false;
         float best = accept;
+        uint2 entry = make_uint2(0u, 0u);
         if (live) {
             pr_vec3 q = ld_off<pr_vec3>(cl, j * 12u);
             // (round 6: the point's previous winner and slack are requested together with the point -- behind the write-back below they were two more
@@ -77,7 +140,7 @@ __global__ __launch_bounds__(256) void nn_search_kernel(IcpBatch b, SceneNNDev s
                 const float tx = M[0] * x + M[1] * y + M[2]  * z + M[3];
                 const float ty = M[4] * x + M[5] * y + M[6]  * z + M[7];
                 const float tz = M[8] * x + M[9] * y + M[10] * z + M[11];
-                step_sq = (tx - x) * (tx - x) + (ty - y) * (ty - y) + (tz - z) * (tz - z);
+                step_sq = dist_sq(tx, ty, tz, q);
                 still = step_sq <= PR_NN_STILL;
                 x = tx; y = ty; z = tz;
                 st_off<pr_vec3>(cl, j * 12u, pr_vec3{ x, y, z });
@@ -92,49 +155,31 @@ __global__ __launch_bounds__(256) void nn_search_kernel(IcpBatch b, SceneNNDev s
                 // demanded), the winner is still the unique strict minimum, which is what the reference's search returns under any
                 // visiting order.
                 const pr_vec3 pw = ld_off<pr_vec3>(scene.pcd, prev * 12u);
-                const float d2 = (x - pw.x) * (x - pw.x) + (y - pw.y) * (y - pw.y) + (z - pw.z) * (z - pw.z);
+                const float d2 = dist_sq(x, y, z, pw);
                 const float slack = slack_in - margin_sqrt(step_sq) * 1.000002f;
-                if (d2 < accept && margin_sqrt(d2) * 1.00001f < slack) { kept = true; slk[j] = slack; ++n_kept; }
-                else { const float bnd = d2 * 1.000001f + 1e-30f; if (bnd < best) best = bnd; }              // = nn_seed_bound
+                if (d2 < accept && margin_sqrt(d2) * 1.00001f < slack) { kept = true; slk[j] = slack; }
+                else { const float bnd = seed_bound_of(d2); if (bnd < best) best = bnd; }
             }
             if (!kept) {
                 // Everything else goes to the bound kernel -- the pixel-window scan too (round 4).  Done here, a window scan ran for the few
                 // lanes of a wavefront that needed it while the other lanes waited: with 1 % of the points in the window half of all
                 // wavefronts paid the 400 instructions of a scan, with 25-85 % (passes 2-8) every one did.  Queued, the scans run in dense lanes.
-                // The entry's bound carries two flags: its sign says "no descent needed" (a previous winner and a step below PR_NN_NODESCENT),
-                // its lowest mantissa bit says "settle" (the point has stopped moving: take the widest cover the window holds).  Setting
-                // or clearing that bit moves the bound by one ulp, far inside the 1e-6 by which a seed bound is inflated.
                 pending = true;
-                uint32_t bits = __float_as_uint(best) & ~1u;
-                if (still && PR_NN_SETTLE) bits |= 1u;
-                if (prev != kNoPrev && step_sq <= PR_NN_NODESCENT) bits |= 0x80000000u;
-                best = __uint_as_float(bits);
+                entry = pack_queued(j, best, prev != kNoPrev && step_sq <= PR_NN_NODESCENT, still && PR_NN_SETTLE);
             }
         }
-        // one slot range per workgroup and chunk: waves in order, lanes in order -- the queue keeps the points' order
-        const unsigned long long m = __ballot(pending);
-        if (lane == 0) wave_base[wave] = (uint32_t)__popcll(m);
+        // one slot range per workgroup and chunk
+        uint32_t total;
+        const uint32_t rank = wg_ordered_rank(pending, wave_n, total);
+        if (threadIdx.x == 0) wg_base = total ? atomicAdd(q_count, total) : 0u;
         __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t total = wave_base[0] + wave_base[1] + wave_base[2] + wave_base[3];
-            wg_base = total ? atomicAdd(q_count, total) : 0u;
-        }
-        __syncthreads();
-        if (pending) {
-            uint32_t slot = wg_base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            for (uint32_t w2 = 0; w2 < wave; ++w2) slot += wave_base[w2];
-            queue[slot] = make_uint2(j, __float_as_uint(best));
-        }
+        if (pending) queue[wg_base + rank] = entry;
         __syncthreads();
     }
     if (scene.counters) {                                        // instrumented runs only (option "nn_count")
-        const uint32_t v[8] = { n_query, n_window, 0u, 0u, 0u, 0u, 0u, n_cells };
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            uint32_t t = v[i];
-            for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-            if ((threadIdx.x & 63u) == 0u && t) atomicAdd(&scene.counters[(size_t)b.iter * 8 + i], (unsigned long long)t);
-        }
+        uint32_t v[kNNCounters] = {};
+        v[kCntQueries] = n_query;
+        nn_flush_counters(scene.counters, b.iter, v);
     }
 }
 
@@ -163,10 +208,8 @@ __global__ __launch_bounds__(256) void nn_tree_kernel(IcpBatch b, SceneNNDev sce
     NNCount cnt;
     uint32_t n_window = 0, n_tree = 0, n_pyramid = 0, n_cells = 0;
     for (uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x; i < queued; i += gridDim.x * kBlockThreads) {
-        const uint2 e = queue[i];
-        const uint32_t j = e.x;
-        const bool still = (e.y & 0x80000000u) != 0u, settle = (e.y & 1u) != 0u;     // flags of the entry (nn_search_kernel)
-        float best = __uint_as_float((e.y & 0x7fffffffu) | 1u);
+        uint32_t j; float best; bool still, settle;
+        unpack_queued(queue[i], j, best, still, settle);
         const pr_vec3 q = ld_off<pr_vec3>(cl, j * 12u);          // as nn_search_kernel stored it
         const float x = q.x, y = q.y, z = q.z;
         // A point that has hardly moved still has (nearly) its true neighbour as temporal seed: d_old - step <= d_new <= d_old + step.
@@ -191,13 +234,10 @@ __global__ __launch_bounds__(256) void nn_tree_kernel(IcpBatch b, SceneNNDev sce
         slk[j] = other;                                           // the ordered binary walk does not report its runner-up: no shortcut next pass
     }
     if (scene.counters) {                                        // instrumented runs only (option "nn_count")
-        const uint32_t v[8] = { 0u, n_window, n_tree, n_pyramid, cnt.nodes, cnt.leaves, cnt.leaf_points, n_cells };
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            uint32_t t = v[i];
-            for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-            if ((threadIdx.x & 63u) == 0u) atomicAdd(&scene.counters[(size_t)b.iter * 8 + i], (unsigned long long)t);
-        }
+        uint32_t v[kNNCounters] = {};
+        v[kCntWindow] = n_window; v[kCntTree] = n_tree; v[kCntDescents] = n_pyramid; v[kCntNodes] = cnt.nodes; v[kCntLeaves] = cnt.leaves;
+        v[kCntLeafPoints] = cnt.leaf_points; v[kCntCells] = n_cells;
+        nn_flush_counters(scene.counters, b.iter, v);
     }
 }
 
@@ -228,7 +268,7 @@ constexpr uint32_t kDeferCap = 512;                              // (at most 255
 __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch b, SceneNNDev scene)
 {
     __shared__ uint32_t wave_n[4], wave_d[4], wg_base, s_ndefer;
-    __shared__ uint2 s_defer[kDeferCap];                         // {point | tried << 30 | settle << 31, bound bits}
+    __shared__ uint2 s_defer[kDeferCap];                         // pack_deferred
     const uint32_t pose = blockIdx.y;
     const PoseMeta &pm = b.meta[pose];
     if (pm.state == kSkip) return;
@@ -243,22 +283,16 @@ __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch 
     uint2 *queue2 = b.nn_queue2 + pm.start;
     uint32_t *q2_count = counts + 2u + (b.iter & 1u);
     const float accept = scene.max_dist_diff * scene.max_dist_diff;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t n_window = 0, n_pyramid = 0, n_cells = 0;
     if (threadIdx.x == 0) s_ndefer = 0u;
     __syncthreads();
     // the lanes with `pending` append (point, bound) to queue 2, in lane order (called by every lane of the workgroup)
     auto push_q2 = [&](bool pending, uint32_t j, float bst) {
-        const unsigned long long m = __ballot(pending);
-        if (lane == 0) wave_n[wave] = (uint32_t)__popcll(m);
+        uint32_t total;
+        const uint32_t rank = wg_ordered_rank(pending, wave_n, total);
+        if (threadIdx.x == 0) wg_base = total ? atomicAdd(q2_count, total) : 0u;
         __syncthreads();
-        if (threadIdx.x == 0) { const uint32_t t = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3]; wg_base = t ? atomicAdd(q2_count, t) : 0u; }
-        __syncthreads();
-        if (pending) {
-            uint32_t slot = wg_base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            for (uint32_t w2 = 0; w2 < wave; ++w2) slot += wave_n[w2];
-            queue2[slot] = make_uint2(j, __float_as_uint(bst));
-        }
+        if (pending) queue2[wg_base + rank] = make_uint2(j, __float_as_uint(bst));
         __syncthreads();
     };
     // (B) deferred entries [first, first + n), n <= 256, one per lane: descent through the representative points, the window if it has not been
@@ -267,10 +301,8 @@ __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch 
         bool pending = false;
         uint32_t j = 0; float bst = 0.0f;
         if (threadIdx.x < n) {
-            const uint2 e = s_defer[first + threadIdx.x];
-            j = e.x & 0x3fffffffu;
-            const bool tried = (e.x & 0x40000000u) != 0u, settle = (e.x & 0x80000000u) != 0u;
-            bst = __uint_as_float(e.y);
+            bool tried, settle;
+            unpack_deferred(s_defer[first + threadIdx.x], j, bst, tried, settle);
             const pr_vec3 q = ld_off<pr_vec3>(cl, j * 12u);
             grid_pyramid_bound(scene, q.x, q.y, q.z, bst, b.iter >= 1u); ++n_pyramid;
             uint32_t w = kNoPrev; float bsq = 0.0f, osq = 0.0f;
@@ -286,17 +318,14 @@ __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch 
         bool pending = false, defer = false, tried = false, settle = false;
         uint32_t j = 0; float bst = 0.0f;
         if (i < queued) {
-            const uint2 e = queue[i];
-            j = e.x;
-            const bool still = (e.y & 0x80000000u) != 0u;        // the sign carries "no descent needed", the lowest bit "settle" (nn_search_kernel)
-            settle = (e.y & 1u) != 0u;
-            bst = __uint_as_float((e.y & 0x7fffffffu) | 1u);     // (the flag bit set: the bound rounded UP by at most an ulp)
+            bool still;                                          // "no descent needed"
+            unpack_queued(queue[i], j, bst, still, settle);
             pending = true;
             if (!scene.grid && !still) {
                 // No pixel grid (a bare ICP call has no camera) and the query is new or has moved (its previous winner, centimetres away
                 // now, is a loose bound): the task walk is order-free, so with a loose bound it would open a good part of the tree before
                 // a leaf near the query tightens it.  The classic descent does that first: follow the split planes to the query's own leaf (8 bytes
-                // per level) and take the nearest of its points as the seed -- an existing point's distance, inflated (nn_seed_bound).
+                // per level) and take the nearest of its points as the seed -- an existing point's distance, inflated (seed_bound_of).
                 const pr_vec3 q = ld_off<pr_vec3>(cl, j * 12u);
                 uint32_t cur = 0u;
                 for (int guard = 0; guard < 64; ++guard) {
@@ -305,11 +334,10 @@ __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch 
                     if (tag == 3u) {
                         float dmin = FLT_MAX;
                         for (uint32_t i = d.x; i < (d.y & 0x3fffffffu); ++i) {
-                            const float4 p = scene.pts[i];
-                            const float d2 = (q.x - p.x) * (q.x - p.x) + (q.y - p.y) * (q.y - p.y) + (q.z - p.z) * (q.z - p.z);
+                            const float d2 = dist_sq(q.x, q.y, q.z, scene.pts[i]);
                             dmin = d2 < dmin ? d2 : dmin;
                         }
-                        const float bb = dmin * 1.000001f + 1e-30f;
+                        const float bb = seed_bound_of(dmin);
                         if (bb < bst) bst = bb;
                         break;
                     }
@@ -329,7 +357,7 @@ __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch 
                     // means the window cannot settle this query after a descent either: it is descended (a bound for the tree) and goes to queue 2.
                     tried = true;
                     done = grid_search(scene, q.x, q.y, q.z, bst, w, &n_cells, &bsq, &osq, settle, true);
-                    if (!done && bsq > 0.0f) { const float bb = bsq * 1.000001f + 1e-30f; if (bb < bst) bst = bb; }
+                    if (!done && bsq > 0.0f) { const float bb = seed_bound_of(bsq); if (bb < bst) bst = bb; }
                 }
                 if (done) { pending = false; ++n_window; win[j] = w; slk[j] = margin_sqrt(osq) * 0.99999f; }
                 else if (!still) { pending = false; defer = true; }
@@ -337,17 +365,12 @@ __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch 
         }
         // the deferred queries of this chunk join the list (lane order); thread 0 alone advances the count, between two barriers
         {
-            const unsigned long long md = __ballot(defer);
-            if (lane == 0) wave_d[wave] = (uint32_t)__popcll(md);
-            __syncthreads();
+            uint32_t total;
+            const uint32_t rank = wg_ordered_rank(defer, wave_d, total);
             const uint32_t base = s_ndefer;
-            if (defer) {
-                uint32_t slot = base + (uint32_t)__popcll(md & ((1ull << lane) - 1ull));
-                for (uint32_t w2 = 0; w2 < wave; ++w2) slot += wave_d[w2];
-                s_defer[slot] = make_uint2(j | (tried ? 0x40000000u : 0u) | (settle ? 0x80000000u : 0u), __float_as_uint(bst));
-            }
+            if (defer) s_defer[base + rank] = pack_deferred(j, bst, tried, settle);
             __syncthreads();
-            if (threadIdx.x == 0) s_ndefer = base + wave_d[0] + wave_d[1] + wave_d[2] + wave_d[3];
+            if (threadIdx.x == 0) s_ndefer = base + total;
         }
         push_q2(pending, j, bst);                                // (its barriers also publish the list and its count)
         const uint32_t nd = s_ndefer;
@@ -363,13 +386,9 @@ __global__ __launch_bounds__(256, PR_BOUND_WAVES) void nn_bound_kernel(IcpBatch 
         nd -= n;
     }
     if (scene.counters) {                                        // instrumented runs only (option "nn_count")
-        const uint32_t v[8] = { 0u, n_window, 0u, n_pyramid, 0u, 0u, 0u, n_cells };
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            uint32_t t = v[i];
-            for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-            if ((threadIdx.x & 63u) == 0u && t) atomicAdd(&scene.counters[(size_t)b.iter * 8 + i], (unsigned long long)t);
-        }
+        uint32_t v[kNNCounters] = {};
+        v[kCntWindow] = n_window; v[kCntDescents] = n_pyramid; v[kCntCells] = n_cells;
+        nn_flush_counters(scene.counters, b.iter, v);
     }
 }
 // minimum of two floats that are known not to be NaN: one v_min_f32 (fminf's IEEE minNum semantics cost a canonicalising v_max per operand)
@@ -413,15 +432,15 @@ __device__ __forceinline__ void wide_pair_lb(uint32_t lox, uint32_t loy, uint32_
     lb_a = __builtin_fmaf(az, az, __builtin_fmaf(ay, ay, ax * ax));
     lb_b = __builtin_fmaf(bz, bz, __builtin_fmaf(by, by, bx * bx));
 }
-// Queue 2 -> the task walk.  Wavefronts are independent (no workgroup barrier): each takes 64 queries at a time.  kLanes lanes share a task:
-// 8 / kLanes boxes of a node, or 8 / kLanes points of a leaf per round, per lane; a step pops 64 / kLanes tasks of one kind.
+// Queue 2 -> the task walk.  Wavefronts are independent (no workgroup barrier): each takes 64 queries at a time.  Two lanes share a task (the
+// paired record layout of nn_wide_layout_kernel is made for two): four boxes of a node, or kLeafPer points of a leaf per round, per lane; a
+// step pops 32 tasks of one kind.
 // Box bounds travel through the queues in SQUARED UNITS of the wide records' frame (wide_pair_lb); a query's bound is converted when a task
 // is popped (inflated by 1e-6, plus one unit), the runner-up bound when a step's skipped boxes are folded into `second` (deflated).
-template <int kLanes, bool kCount>
+template <bool kCount>
 __global__ __launch_bounds__(256, PR_WIDE_WAVES) void nn_tree_wide_kernel(IcpBatch b, SceneNNDev scene, uint32_t qbatch)
 {
-    static_assert(kLanes == 2, "the paired record layout (nn_wide_build_kernel, stage D) is made for two lanes per task");
-    constexpr uint32_t kPer = 8u / kLanes, kTasks = 64u / kLanes;
+    constexpr uint32_t kLanes = 2u, kPer = 8u / kLanes, kTasks = 64u / kLanes;
     constexpr uint32_t kLeafPer = PR_WIDE_LEAF_PER;               // points of a leaf per lane and round
     __shared__ uint2 s_taskq[4][kTaskQCap + kTaskLCap];                          // per wavefront: node-task queue, leaf-task queue behind it; {reference, bound bits (low 6 bits cleared: rounded DOWN) | query slot}
     // (Round 5, VERDICT r04 item 1b: the per-query records as six arrays of words instead of 16-byte records -- a step's 32 slots then hit 32 different
@@ -508,7 +527,7 @@ __global__ __launch_bounds__(256, PR_WIDE_WAVES) void nn_tree_wide_kernel(IcpBat
             float sec_u = (active && !alive) ? lb_in : FLT_MAX;      // what this lane rules out: boxes (squared units) ...
             float sec_l = FLT_MAX;                                   // ... and points (squared metres)
             if (!leaf_step) {
-                // ---------------- node tasks: lane c of a group tests the four slots of half c (two pairs, see nn_wide_build_kernel stage D)
+                // ---------------- node tasks: lane c of a group tests the four slots of half c (two pairs, see nn_wide_layout_kernel)
                 // The record is loaded by every lane (a lane without a live task reads wide node 0 and masks the outcome with `alive`): no
                 // zero-initialised copy of the record, no branch around the loads.
                 uint4 r[4];
@@ -611,9 +630,7 @@ __global__ __launch_bounds__(256, PR_WIDE_WAVES) void nn_tree_wide_kernel(IcpBat
             }
             nN = (uint32_t)__builtin_amdgcn_readfirstlane((int)nN); nL = (uint32_t)__builtin_amdgcn_readfirstlane((int)nL);     // wave-uniform by construction
             sec_l = min_f32(sec_l, sec_u < FLT_MAX ? sec_u * w_to_m2 : FLT_MAX);   // boxes: squared units -> squared metres, rounded down
-            float sec_g = sec_l;
-            if (kLanes >= 2) sec_g = min_f32(sec_l, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sec_l), 0xB1, 0xf, 0xf, true)));          // quad_perm [1,0,3,2]
-            if (kLanes == 4) sec_g = min_f32(sec_g, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sec_g), 0x4E, 0xf, 0xf, true)));   // quad_perm [2,3,0,1]
+            const float sec_g = min_f32(sec_l, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sec_l), 0xB1, 0xf, 0xf, true)));   // the task's other lane: quad_perm [1,0,3,2]
             if (c == 0u && sec_g < FLT_MAX) atomicMin(&second[q], __float_as_uint(sec_g));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -627,7 +644,7 @@ __global__ __launch_bounds__(256, PR_WIDE_WAVES) void nn_tree_wide_kernel(IcpBat
                         const unsigned long long key = best[lane];
                         const uint32_t m_bits = (uint32_t)(key >> 32), idx = (uint32_t)key;
                         uint32_t bb = mine.y;                         // (positive float bits order like the floats)
-                        if (idx != kNoIdx && m_bits < bb) { const uint32_t t = __float_as_uint(__uint_as_float(m_bits) * 1.000001f + 1e-30f); if (t < bb) bb = t; }   // = nn_seed_bound
+                        if (idx != kNoIdx && m_bits < bb) { const uint32_t t = __float_as_uint(seed_bound_of(__uint_as_float(m_bits))); if (t < bb) bb = t; }
                         reinterpret_cast<uint32_t *>(&qs[lane])[3] = bb;
                         best[lane] = ((unsigned long long)bb << 32) | kNoIdx;
                         second[lane] = 0x7f7fffffu; tied[lane] = 0xffffffffu; ovf[lane] = 0u;
@@ -644,8 +661,8 @@ __global__ __launch_bounds__(256, PR_WIDE_WAVES) void nn_tree_wide_kernel(IcpBat
             const uint32_t m_bits = (uint32_t)(key >> 32), idx = (uint32_t)key, b0 = bound_now, j = mine.x;
             const bool found = idx != kNoIdx && m_bits < b0;
             if (ovf[lane] != 0u || (found && tied[lane] == m_bits)) {
-                // a tie or a dropped task: the ordered walk, from the minimum found (= nn_seed_bound: an existing point's distance)
-                const float bnd = found ? fminf(__uint_as_float(b0), __uint_as_float(m_bits) * 1.000001f + 1e-30f) : __uint_as_float(b0);
+                // a tie or a dropped task: the ordered walk, from the minimum found (an existing point's distance)
+                const float bnd = found ? fminf(__uint_as_float(b0), seed_bound_of(__uint_as_float(m_bits))) : __uint_as_float(b0);
                 const float4 qp = qs[lane];
                 win[j] = query_nn_bounded(scene, qp.x, qp.y, qp.z, bnd);
                 slk[j] = 0.0f;                                      // an ordered walk does not report its runner-up: no shortcut next pass
@@ -655,14 +672,9 @@ __global__ __launch_bounds__(256, PR_WIDE_WAVES) void nn_tree_wide_kernel(IcpBat
         __builtin_amdgcn_wave_barrier();
     }
     if (kCount && scene.counters) {
-        uint32_t n_pyr = 0u;
-        const uint32_t v[8] = { 0u, 0u, n_tree, n_pyr, n_nodes, n_leaves, n_leaf_points, 0u };
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            uint32_t t = v[i];
-            for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-            if ((threadIdx.x & 63u) == 0u && t) atomicAdd(&scene.counters[(size_t)b.iter * 8 + i], (unsigned long long)t);
-        }
+        uint32_t v[kNNCounters] = {};
+        v[kCntTree] = n_tree; v[kCntNodes] = n_nodes; v[kCntLeaves] = n_leaves; v[kCntLeafPoints] = n_leaf_points;
+        nn_flush_counters(scene.counters, b.iter, v);
     }
 }
 
@@ -673,10 +685,9 @@ __global__ __launch_bounds__(256) void nn_grid_claim_kernel(const pr_vec3 *__res
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_points) return;
     const pr_vec3 p = pcd[i];
-    float u, v;
-    grid_project(g, p.x, p.y, p.z, u, v);
-    if (!(p.z > 0 && u >= 0.0f && u < (float)g.gw && v >= 0.0f && v < (float)g.gh)) { info[0] = 0u; return; }
-    const int cell = (int)floorf(v) * (int)g.gw + (int)floorf(u);
+    int px, py;
+    if (!(p.z > 0 && grid_pixel(g, p.x, p.y, p.z, px, py) && px >= 0 && px < (int)g.gw && py >= 0 && py < (int)g.gh)) { info[0] = 0u; return; }
+    const int cell = py * (int)g.gw + px;
     if (atomicCAS(&cell_idx[cell], -1, (int)i) != -1) info[0] = 0u;
 }
 // one coarser level: cell (bx, by) takes the occupied child cell nearest its centre (children = 4 x 4 cells of the finer level)
@@ -710,7 +721,7 @@ hipError_t launch_nn_search(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_
 {
     if (n_poses == 0 || max_points == 0) return hipSuccess;
     if (!sc.rec32 || (sc.stack_depth != 16 && sc.stack_depth != 24) || !b.nn_prev || !b.nn_slack || !b.nn_queue || !b.nn_queue2 || !b.nn_qcount) return hipErrorInvalidValue;
-    if (max_points >= (1u << 30)) return hipErrorInvalidValue;        // nn_bound_kernel keeps two flags in the top bits of a point's index (a cloud of 2^30 points is 12 GiB)
+    if (max_points >= kNNMaxCloudPoints) return hipErrorInvalidValue; // (pack_deferred)
     if (run == 0) run = 1;
     if (run > 8) run = 8;
     const uint32_t per_block = kBlockThreads * run;
@@ -734,8 +745,8 @@ hipError_t launch_nn_search(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_
             // cloud: 26 k queries = 103 workgroups of 4 x 64): then 16 at a time in four times as many workgroups
             uint32_t qbatch = 64u, walk_gx = tree_gx;
             if ((size_t)np * max_points < (size_t)64 * 4 * 1024) { qbatch = 16u; walk_gx = (max_points + 4u * qbatch - 1u) / (4u * qbatch); if (walk_gx * np > 4096u) walk_gx = (4096u + np - 1u) / np; if (walk_gx < tree_gx) walk_gx = tree_gx; }
-            if (sc.counters) hipLaunchKernelGGL(HIP_KERNEL_NAME(nn_tree_wide_kernel<PR_WIDE_LANES, true>), dim3(walk_gx, np), dim3(kBlockThreads), 0, s, bb, sc, qbatch);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(nn_tree_wide_kernel<PR_WIDE_LANES, false>), dim3(walk_gx, np), dim3(kBlockThreads), 0, s, bb, sc, qbatch);
+            if (sc.counters) hipLaunchKernelGGL(HIP_KERNEL_NAME(nn_tree_wide_kernel<true>), dim3(walk_gx, np), dim3(kBlockThreads), 0, s, bb, sc, qbatch);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(nn_tree_wide_kernel<false>), dim3(walk_gx, np), dim3(kBlockThreads), 0, s, bb, sc, qbatch);
         }
         else if (sc.stack_depth == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(nn_tree_kernel<16 + 0x100>), dim3(tree_gx, np), dim3(kBlockThreads), (size_t)16 * kBlockThreads * 8, s, bb, sc);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(nn_tree_kernel<24 + 0x100>), dim3(tree_gx, np), dim3(kBlockThreads), (size_t)24 * kBlockThreads * 8, s, bb, sc);

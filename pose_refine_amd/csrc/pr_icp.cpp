@@ -91,7 +91,7 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     prk::IcpBatch b{};
     b.cloud = cloud_base; b.meta = g->meta.as<prk::PoseMeta>(); b.partial = g->partial.as<float>();
     b.nblk = nblk; b.steps = steps;
-    sc.nn_split = (sc.kind == PR_SCENE_NN && sc.nn.rec32 && opt.nn_split) ? 1u : 0u;
+    sc.nn_split = nn_split_for(sc);
     sc.nn_max_points = max_n;
     if (sc.nn_split && opt.nn_count) {                            // instrumented run: kCounterPasses x 8 counters, accumulated until read
         const bool fresh = g->nn_counters.p == nullptr;
@@ -102,13 +102,9 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     if (sc.kind == PR_SCENE_NN && sc.nn.rec32 && (opt.nn_seed || sc.nn_split)) {     // winners, indexed like the cloud points
         size_t span = 1;
         for (uint32_t i = 0; i < P; ++i) span = std::max(span, (size_t)start_h[i] + count_h[i]);
-        // winners | slack of the keep-the-winner test | queue 1 and queue 2 of unsettled queries (8 B per entry) | queue counters per hypothesis
-        PR_TRY(g->nn_prev.ensure(sizeof(uint32_t) * (span * prk::kNNWordsPerPoint + prk::kQCountStride * (size_t)P) + 64));
-        b.nn_prev = g->nn_prev.as<uint32_t>();
-        b.nn_slack = reinterpret_cast<float *>(b.nn_prev + span);
-        b.nn_queue = reinterpret_cast<uint2 *>(b.nn_prev + 2 * span);
-        b.nn_queue2 = reinterpret_cast<uint2 *>(b.nn_prev + 4 * span);
-        b.nn_qcount = b.nn_prev + 6 * span;
+        const NNLayout nl = nn_layout(span, P);
+        PR_TRY(g->nn_prev.ensure(nl.bytes));
+        nn_carve(b, g->nn_prev.as<uint32_t>(), nl);
         HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(b.nn_qcount), (size_t)prk::kQCountStride * P, 0, g->stream));     // (a kernel, not a memset command: no runtime copy / fill path on a per-call path, see below)
     }
 
@@ -182,7 +178,7 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
             GraphKey key;
             key.add(P); key.add(nblk); key.add(steps); key.add(crit); key.add(sc); key.add(cloud_base); key.add(g->meta.p); key.add(g->partial.p);
             key.add(g->dstate.p); key.add(dres); key.add(results_host != nullptr); key.add(res); key.add(h_meta); key.add(init); key.add(opt.profile); key.add(pose_groups_for(sc.kind)); key.add(opt.fused_solve); key.add(g->arrive.p); key.add(b.nn_prev);
-            key.add(b.nn_slack); key.add(b.nn_queue); key.add(b.nn_queue2); key.add(b.nn_qcount);    // laid out behind nn_prev at multiples of `span` (max start+count): same P / max_n, other offsets => other addresses
+            key.add(b.nn_slack); key.add(b.nn_queue); key.add(b.nn_queue2); key.add(b.nn_qcount);    // nn_carve: behind nn_prev at multiples of `span` (max start+count) -- same P / max_n, other offsets => other addresses
             CachedGraph *hit = nullptr;
             for (auto &c : g->graphs) if (c.exec && c.key == key) { hit = &c; break; }
             if (!hit) {

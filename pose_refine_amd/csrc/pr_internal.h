@@ -19,7 +19,7 @@ constexpr uint32_t kAccStride      = 32;                        // 29 sums padde
 constexpr uint32_t kCloudAlign     = PR_CLOUD_PACK;                 // fused path: clouds of a sub-batch packed one behind the other, each rounded up to this many points (0: one per fixed stride)
 constexpr uint32_t kBoxPack        = PR_BOX_PACK;                   // fused asynchronous path: depth boxes of a sub-batch packed (each rounded up to this many ints; 0: full frames)
 constexpr uint32_t kQCountStride   = 4;                         // queue counters per hypothesis (IcpBatch::nn_qcount)
-constexpr uint32_t kNNWordsPerPoint = 6;                        // per cloud point: winner | slack | queue 1 (2 words) | queue 2 (2 words)
+constexpr uint32_t kNNWordsPerPoint = 6;                        // per cloud point: winner | slack | queue 1 (2 words) | queue 2 (2 words) -- laid out by nn_layout (pr_runtime.h)
 
 // per-hypothesis run state consumed by the correspondence kernel
 enum : int32_t { kSkip = 0, kRun = 1, kRunWithTransform = 2 };
@@ -109,13 +109,13 @@ struct SceneNNDev {
     // three coarser levels of the same grid: one representative scene point per 4 x 4, 16 x 16 and 64 x 64 pixel block
     // (the occupied sub-block nearest the block's centre, recursively), same {x, y, z, index} cells
     const float4 *pyr4, *pyr16, *pyr64;
-    // wide records (nn_wide_build_kernel): one 128-byte line per wide node = eight slots {subtree box, reference}; null when the tree
+    // wide records (nn_wide_layout_kernel): one 128-byte line per wide node = eight slots {subtree box, reference}; null when the tree
     // cannot be expressed that way (the binary walk of nn_tree_kernel is used)
     const uint4 *wide;
     uint32_t n_wide;
     float wmin[3], wscale;      // frame of the wide records: coordinate = wmin[a] + (float)q * wscale (one scale for the three axes)
-    // instrumented runs (option "nn_count"): per ICP pass (IcpBatch::iter) eight 64-bit counters -- queries, settled by the pixel
-    // window, handed to the tree, pyramid descents, tree nodes visited, leaves scanned, leaf points tested, window cells read; else null
+    // instrumented runs (option "nn_count"): per ICP pass (IcpBatch::iter) a row of eight 64-bit counters, the columns of enum NNCounter
+    // (nn_search.hip): kCntQueries, kCntWindow, kCntTree, kCntDescents, kCntNodes, kCntLeaves, kCntLeafPoints, kCntCells; else null
     unsigned long long *counters;
 };
 // kd-tree scene after the search kernel has run: the correspondence pass only gathers the winners (no search, no transform)

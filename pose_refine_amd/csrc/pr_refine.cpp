@@ -950,15 +950,15 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
     PR_TRY(sl.arrive.ensure(sizeof(uint32_t) * P));
     pr_result *dres = job.results_dev;
     if (!dres) { PR_TRY(sl.dresults.ensure(sizeof(pr_result) * P)); dres = sl.dresults.as<pr_result>(); }
-    // kd-tree scene: winners | slack | queue | two queue counters per hypothesis, indexed like the clouds of one sub-batch (icp_drive
-    // has the same layout); the search kernel's grid comes from the box bound, surplus workgroups exit at once
+    // kd-tree scene: the workspace (nn_layout, as icp_drive) indexed like the clouds of one sub-batch; the search kernel's grid comes from the
+    // box bound, surplus workgroups exit at once
     uint32_t *nn_prev = nullptr;
-    const size_t nn_span = cstride * (size_t)sub;
+    const NNLayout nl = nn_layout(cstride * (size_t)sub, sub);
     if (sc.kind == PR_SCENE_NN) {
-        sc.nn_split = (sc.nn.rec32 && opt.nn_split) ? 1u : 0u;
+        sc.nn_split = nn_split_for(sc);
         sc.nn_max_points = (uint32_t)std::min<size_t>(max_area, 0xffffffffu);
         if (sc.nn.rec32 && (opt.nn_seed || sc.nn_split)) {
-            PR_TRY(sl.nn_prev.ensure(sizeof(uint32_t) * (nn_span * prk::kNNWordsPerPoint + prk::kQCountStride * (size_t)sub) + 64));
+            PR_TRY(sl.nn_prev.ensure(nl.bytes));
             nn_prev = sl.nn_prev.as<uint32_t>();
         }
     }
@@ -1025,7 +1025,7 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
             for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered && o.done) HIP_TRY(hipStreamWaitEvent(st, o.done, 0));
 
         const uint32_t n_groups = pose_group_count(scene_kind, nq, timed);
-        if (nn_prev) HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(nn_prev + 6 * nn_span), (size_t)prk::kQCountStride * nq, 0, st));
+        if (nn_prev) HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(nn_prev + nl.qcount), (size_t)prk::kQCountStride * nq, 0, st));
         // When may the OTHER slot start rendering?  Measured optimum (21 passes of obj_06, overlap_pass swept per batch size):
         // pass 4 or earlier at 128 hypotheses, 9-10 at 256, 14-16 at 384, 16 at 512 -- i.e. when about 2800 hypothesis-passes of
         // this loop are left (never fewer than 5 passes): that much loop work is what a render hides behind without stretching the
@@ -1048,10 +1048,7 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
         }
         prk::IcpBatch b{};
         b.cloud = sl.cloud.as<pr_vec3>(); b.partial = sl.partial.as<float>(); b.nblk = nblk; b.grid_x = grid_x; b.steps = steps;
-        if (nn_prev) {
-            b.nn_prev = nn_prev; b.nn_slack = reinterpret_cast<float *>(nn_prev + nn_span);
-            b.nn_queue = reinterpret_cast<uint2 *>(nn_prev + 2 * nn_span); b.nn_queue2 = reinterpret_cast<uint2 *>(nn_prev + 4 * nn_span); b.nn_qcount = nn_prev + 6 * nn_span;
-        }
+        if (nn_prev) nn_carve(b, nn_prev, nl);
         const uint32_t last_pass = (uint32_t)crit.max_iteration;
         auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t gs) -> int {
             if (!timed) { HIP_TRY(launch_pass(bb, sc, np, gs)); return PR_OK; }

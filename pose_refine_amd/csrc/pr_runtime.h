@@ -310,6 +310,24 @@ struct SlotOut {
     size_t res, flag, bytes;
     explicit SlotOut(size_t P) : res((P * sizeof(uint32_t) + 63) & ~(size_t)63), flag((res + sizeof(pr_result) * P + 63) & ~(size_t)63), bytes(flag + 64) {}
 };
+// The kd-tree workspace of a batch, in 32-bit words behind one base: winners | slack of the keep-the-winner test | queue 1 | queue 2 (8 B per
+// entry) -- one entry each per cloud point, `span` = the largest start + count of the batch -- | kQCountStride queue counters for each of the P
+// hypotheses; `bytes` carries 64 B of slack.  No HIP call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.
+struct NNLayout { size_t winners, slack, queue, queue2, qcount, bytes; };
+inline NNLayout nn_layout(size_t span, size_t P)
+{
+    static_assert(prk::kNNWordsPerPoint == 1 + 1 + 2 + 2, "winner | slack | queue 1 entry | queue 2 entry");
+    NNLayout l{};
+    l.slack = l.winners + span; l.queue = l.slack + span; l.queue2 = l.queue + 2 * span; l.qcount = l.queue2 + 2 * span;
+    l.bytes = sizeof(uint32_t) * (l.qcount + prk::kQCountStride * P) + 64;
+    return l;
+}
+// the nn_* fields of a batch whose workspace starts at `base`
+inline void nn_carve(prk::IcpBatch &b, uint32_t *base, const NNLayout &l)
+{
+    b.nn_prev = base + l.winners; b.nn_slack = reinterpret_cast<float *>(base + l.slack);
+    b.nn_queue = reinterpret_cast<uint2 *>(base + l.queue); b.nn_queue2 = reinterpret_cast<uint2 *>(base + l.queue2); b.nn_qcount = base + l.qcount;
+}
 // A slot's helper thread (PR_SOLVE_HOST): the reference solves on the host (icp.cu:207), which makes a batch a chain of
 // launch -> wait -> solve -> launch that only a host thread can drive; the reference's answer is "many host threads, each refining its own
 // hypothesis" (README.md:15).  A caller that pipelines batches through pr_refine_submit / pr_refine_wait from ONE thread gets the same
@@ -576,6 +594,8 @@ struct SceneSel {
     uint32_t nn_max_points = 0;      // largest cloud of the batch (grid of the search kernel)
     int nn_set = -1;                 // kd-tree scene: which of Ctx::nn_sets the records are in
 };
+// the route of a kd-tree batch: search kernels + winners pass (compact records and option nn_split), else the fused search pass
+inline uint32_t nn_split_for(const SceneSel &sc) { return (sc.kind == PR_SCENE_NN && sc.nn.rec32 && opt.nn_split) ? 1u : 0u; }
 constexpr uint32_t kCounterPasses = 64;
 // camera of the hypotheses (fused paths): lets a kd-tree scene be indexed by pixel as well
 struct Camera { uint32_t w = 0, h = 0; float fx = 0, fy = 0, cx = 0, cy = 0; };

@@ -127,9 +127,6 @@
 #ifndef PR_WIDE_WAVES
 #define PR_WIDE_WAVES 6                                         // wavefronts per SIMD the task walk is compiled for (<= 80 VGPRs; LDS: 26.5 KiB per workgroup)
 #endif
-#ifndef PR_WIDE_LANES
-#define PR_WIDE_LANES 2                                         // lanes per task: the paired record layout is made for 2
-#endif
 #ifndef PR_WIDE_LEAF_PER
 #define PR_WIDE_LEAF_PER 5                                      // points of a leaf a lane tests per round: 2 x 5 = the reference's max_leaf in ONE round (the records allow 15-point leaves: two)
 #endif

@@ -217,7 +217,7 @@ def _counted(c):
 def test_path_counters(gpu, fams, key):
     """Counting does not change the result.  Every query of a pass is kept (no search), settled by the window, or handed to the tree:
     queries >= window + tree in every pass (nn_search_kernel queues what it does not keep; nn_bound_kernel settles a queued query in the
-    window or appends it to queue 2, nn_search.hip:321-352 and the deferred descent)."""
+    window or appends it to queue 2, from its main loop or from the deferred descent)."""
     c = case(fams, key)
     cnt = _counted(c)
     q, win, tree = cnt[:, 0], cnt[:, 1], cnt[:, 2]
@@ -233,6 +233,34 @@ def test_path_counters(gpu, fams, key):
         bf = R.BruteForce(c.fam.clouds[0], c.oscene.pcd, c.fam.max_dist)
         assert np.all(bf.n_ties() > 1)
         assert win[0] == 0 and tree[0] == q[0]
+
+
+@pytest.mark.parametrize("wide", [1, 0])
+@pytest.mark.parametrize("key", ["F3_97x61", "deg_coplanar"])
+def test_all_eight_counter_columns(gpu, fams, key, wide):
+    """Every column of api.nn_counters (enum NNCounter, nn_search.hip), per pass, on the two smallest inputs that reach every flush: F3_97x61
+    (more than one search workgroup, several chunks per bound workgroup, a deferred list that is flushed in mid-loop) and deg_coplanar (no
+    camera: the descent-to-leaf branch of nn_bound_kernel).  wide = 0 runs nn_tree_kernel instead of nn_bound_kernel + nn_tree_wide_kernel;
+    a leaf holds at most 15 points in the wide records, max_leaf in the binary tree."""
+    c = case(fams, key)
+    with options(nn_wide=wide):
+        cnt = _counted(c)
+    q, win, tree, desc, nodes, leaves, leaf_pts, cells = (cnt[:, i] for i in range(8))
+    print(f"\n{key} nn_wide={wide}:\n{cnt.tolist()}")
+    per_leaf = 15 if wide else c.fam.max_leaf
+    assert np.all(q == len(c.fam.clouds[0])), q
+    assert np.all(win + tree <= q) and win[0] + tree[0] == q[0]
+    assert np.all(desc <= win + tree), (desc, win, tree)              # a descent belongs to a query that was not kept
+    if key == "F3_97x61":
+        assert desc[0] > 0
+    if c.fam.depth is None:
+        assert not win.any() and not desc.any() and not cells.any()
+    assert np.all((cells > 0) | (win == 0)), (cells, win)             # a window that settled a query was scanned
+    for p in range(COUNT_PASSES):
+        if tree[p] == 0:
+            assert nodes[p] == 0 and leaves[p] == 0 and leaf_pts[p] == 0, (p, cnt[p])
+        else:
+            assert nodes[p] > 0 and leaves[p] > 0 and leaves[p] <= leaf_pts[p] <= per_leaf * leaves[p], (p, cnt[p])
 
 
 def test_window_tree_and_kept_paths_are_all_taken(gpu, fams):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of library variants built beforehand (PR_BUILD_OUT=pose_refine_amd/lib/variants/X.so python -m pose_refine_amd.build):
 #   [AB_ROUNDS=n] tools/ab_libs.sh nn|proj|bench-nn|bench-proj|bench-host  X.so Y.so ...      (paths relative to the repo; "-" = the in-tree library)
-# nn / proj: per-pass kernel times of one 256-hypothesis batch as one pose group (rocprofv3 --kernel-trace of tools/pmc_workload.py);
+# nn / proj: per-pass kernel times of one 256-hypothesis batch as one pose group and the launch list (rocprofv3 --kernel-trace of tools/pmc_workload.py);
 # bench-*: bench.py throughput (bench-host: the headline configuration with the solve on the host, through the slots' helper threads), the libraries
 # alternating, AB_ROUNDS rounds (default two).  A run that fails ends the script: nothing more is started on a device that may have faulted.
 set -o pipefail
@@ -24,6 +24,10 @@ rows = list(c.execute("select name, start, (end-start)/1000.0 from kernels order
 for key in ("nn_search", "nn_bound", "nn_tree", "icp_pass", "nn_late", "raster_kernel"):
     v = [r[2] for r in rows if key in r[0]]
     if v: print("%-13s us:" % key, " ".join(f"{x:.0f}" for x in v[-21:]), " sum %.2f ms" % (sum(v[-21:]) / 1e3))
+# the launch list: two libraries that launch the same kernels in the same order print the same line
+base = [r[0].split("(")[0].split("<")[0] for r in rows]
+print("launches: %d, md5 of the names in order (template arguments dropped) %s" % (len(base), __import__("hashlib").md5("\n".join(base).encode()).hexdigest()))
+print("kernels:", ", ".join(sorted({r[0].split("(")[0] for r in rows})))
 PY
       rm -rf $OUT/t ;;
     bench-nn) timeout -k 10 300 python bench.py --scene nn --steps 30 --warmup 3 --no-cpu-baseline --no-live-pmc 2>/dev/null | tail -1 | python -c "$P" || exit 1 ;;

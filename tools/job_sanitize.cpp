@@ -1,6 +1,6 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
 // Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job and score_request_ok with null and
-// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut), the pose-group split.  None of them calls HIP, so nothing of the runtime is linked.
+// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split.  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
 namespace prh { void set_error(const char *, ...) {} }
@@ -125,6 +125,27 @@ int main()
             for (uint32_t k = 0; k < n_groups; ++k) CHECK(group_begin((uint32_t)P, n_groups, k) <= group_begin((uint32_t)P, n_groups, k + 1));
         }
     }
+    // the kd-tree workspace: the five regions in order and disjoint, both queues on 8 bytes, the counters at word 6 x span, the size the drivers
+    // always asked for; carved from a block of that size, the last word of every region is inside it
+    for (size_t span : { size_t(1), size_t(31), size_t(32), size_t(1) << 20, (size_t(1) << 30) - 1 })
+        for (size_t P : { size_t(1), size_t(32768) }) {
+            const NNLayout l = nn_layout(span, P);
+            CHECK(l.winners == 0 && l.winners + span <= l.slack && l.slack + span <= l.queue && l.queue + 2 * span <= l.queue2 && l.queue2 + 2 * span <= l.qcount);
+            CHECK(l.qcount == 6 * span && sizeof(uint32_t) * (l.qcount + prk::kQCountStride * P) <= l.bytes);
+            CHECK(l.bytes == 4 * (6 * span + 4 * P) + 64);
+            uint32_t *base = static_cast<uint32_t *>(std::malloc(l.bytes));
+            CHECK(base != nullptr);
+            if (!base) continue;
+            prk::IcpBatch b{};
+            nn_carve(b, base, l);
+            CHECK(b.nn_prev == base && reinterpret_cast<uint32_t *>(b.nn_slack) == base + l.slack && b.nn_qcount == base + l.qcount);
+            CHECK(reinterpret_cast<uintptr_t>(b.nn_queue) % alignof(uint2) == 0 && reinterpret_cast<uintptr_t>(b.nn_queue2) % alignof(uint2) == 0);
+            CHECK(reinterpret_cast<uintptr_t>(b.nn_queue) % 8 == 0 && reinterpret_cast<uintptr_t>(b.nn_queue2) % 8 == 0);
+            b.nn_prev[span - 1] = 1u; b.nn_slack[span - 1] = 2.0f; b.nn_queue[span - 1] = uint2{ 3u, 4u }; b.nn_queue2[span - 1] = uint2{ 5u, 6u };
+            b.nn_qcount[prk::kQCountStride * P - 1] = 7u;
+            CHECK(b.nn_prev[span - 1] == 1u && b.nn_slack[span - 1] == 2.0f && b.nn_queue[span - 1].y == 4u && b.nn_queue2[span - 1].x == 5u && b.nn_qcount[prk::kQCountStride * P - 1] == 7u);
+            std::free(base);
+        }
     CHECK(group_begin(0xffffffffu, 4, 4) == 0xffffffffu && group_begin(0xffffffffu, 4, 3) == 0xbfffffffu);
     std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;

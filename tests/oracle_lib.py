@@ -83,6 +83,7 @@ def lib():
         L.po_kd_build.argtypes = [f32p, f32p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
         L.po_solve666.argtypes = [f32p, f32p, f32p]
         L.po_mat4_mul.argtypes = [f32p, f32p, f32p]
+        L.po_transform_cloud.argtypes = [f32p, C.c_size_t, f32p]
         L.po_icp.restype = C.c_int
         L.po_icp.argtypes = [f32p, C.c_size_t, C.c_int, C.c_void_p, Criteria, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.po_sum29.argtypes = [f32p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_uint32, f32p]
@@ -246,6 +247,13 @@ def solve666(A, b):
     T = np.zeros(16, np.float32)
     lib().po_solve666(_f32(A).reshape(-1), _f32(b).reshape(-1), T)
     return T.reshape(4, 4)
+
+
+def transform_cloud(cloud, T):
+    """po_transform_cloud on a COPY of cloud: the pending update of icp.cpp:47-59."""
+    cl = np.array(cloud, dtype=np.float32, order="C", copy=True)
+    lib().po_transform_cloud(cl.reshape(-1), len(cl), _f32(T).reshape(-1))
+    return cl
 
 
 def set_threads(n=0):

@@ -6,7 +6,8 @@ import pytest
 
 import solve_ref as R
 from pose_refine_amd import api
-from test_solve_ref import float64_truth, same_bits, spd_rows, state_of, truth_bound
+from test_solve_ref import same_bits, spd_rows, state_of, truth_bound
+from truth_ref import float64_truth
 
 pytestmark = pytest.mark.gpu
 

@@ -9,6 +9,7 @@ import pytest
 
 import solve_ref as R
 from pose_refine_amd import api
+from truth_ref import float64_truth
 
 
 @pytest.fixture(scope="module")
@@ -115,20 +116,6 @@ def test_host_iteration_equals_restatement(batches):
     assert seen["thr-0"] == 0 and seen["thr-inf"] == 1 and seen["n-edge"] == 7               # a NaN rmse never counts as converged
     nonzero_cnt = batches[0].sums[:, 28] != 0
     assert seen["solve"] == int((~nonzero_cnt).sum())
-
-
-def float64_truth(s):
-    """np.linalg.solve((A + 0.01 I), b) in float64, then Rz Ry Rx from math.sin / math.cos (icp.cpp:7-27 in exact arithmetic)."""
-    A = R.sums_to_A(s[:21]).astype(np.float64).reshape(6, 6) + 0.01 * np.eye(6)
-    x = np.linalg.solve(A, s[21:27].astype(np.float64))
-    cx, sx, cy, sy, cz, sz = (math.cos(x[0]), math.sin(x[0]), math.cos(x[1]), math.sin(x[1]), math.cos(x[2]), math.sin(x[2]))
-    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
-    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
-    T = np.eye(4)
-    T[:3, :3] = Rz @ Ry @ Rx
-    T[:3, 3] = x[3:]
-    return T, float(np.linalg.cond(A)), x
 
 
 def truth_bound(Tt, kappa, x):

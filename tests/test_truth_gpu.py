@@ -1,13 +1,15 @@
 """GPU tests (-m gpu): the kernels against float64 geometry (tests/truth_ref.py), directly -- not through the oracle, so each stands even if the oracle is wrong.
 Render (render_host, render, render_multi, the fused path's view), depth2cloud, the row convention between the two, device scene preparation and the
-projective lookup point by point.  Each assertion is the one tests/test_truth_host.py applies to the oracle, with the same bound (tests/truth_cases.py,
+projective lookup point by point; and (second half) the refinement loop.  Each assertion is the one tests/test_truth_host.py applies to the oracle, with the same bound (tests/truth_cases.py,
 measured on the oracle: profiles/truth/README.md).  Small shapes only: frames of 64 x 48 to 130 x 77, at most 200 triangles and 5 poses per case."""
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import truth_cases as TC
+import truth_ref as T
 from pose_refine_amd import _lib, api
+from test_pass_sums_gpu import icp_batch, options, ragged
 
 pytestmark = pytest.mark.gpu
 
@@ -153,3 +155,147 @@ def test_lookup_takes_the_pixel_the_projection_says(gpu, name, packed):
     pts, _ = TC.lookup_cloud(name)
     rows = api.debug_contrib29(api.DeviceVector.from_host(pts.reshape(-1)), scene, packed=packed)
     TC.check_lookup(rows, name, f"device packed={packed}", TC.oracle_lookup_rows(name))
+
+
+# =================================================================================================================================================
+#  The refinement loop on the device against the float64 definitions of tests/truth_ref.py: per-point terms, the pending update, the 29 sums of
+#  the product pass, the loop and its fixed point, the fused path.  Assertions and bounds are those of test_truth_host.py (tests/truth_cases.py);
+#  the oracle appears only where that file lets it: one-point clouds inside the association band.  The truth is computed from the scene arrays
+#  the DEVICE holds.  Frames of 96 x 72, clouds of 936 .. 5436 points; the float64 loops are computed once per module and shared read-only.
+# =================================================================================================================================================
+A_W, A_H, A_K, A_MAX = TC.ICP_W, TC.ICP_H, TC.ICP_K, TC.ICP_MAX_DIST
+
+
+def device_scenes(depth):
+    """The projective scene from a host depth image (so that the packed record is allowed) and the kd-tree scene built on the device."""
+    d = np.array(depth, np.int32)
+    proj = api.Scene_projective().init_Scene_projective_cuda(d, A_K, A_W, A_H, A_MAX)
+    nn = api.Scene_nn().init_Scene_nn_device(api.DeviceVector.from_host(d.reshape(-1)), A_K, A_W, A_H, max_dist_diff=A_MAX)
+    return proj, nn
+
+
+def scene_truth(scene, kind, name="whole"):
+    """(float64 association, scene points, scene normals) from the arrays the device holds."""
+    n = scene._n_points if kind == "nn" else scene.width * scene.height
+    pcd = scene.pcd_buffer.to_host()[:3 * n].reshape(-1, 3)
+    nrm = scene.normal_buffer.to_host()[:3 * n].reshape(-1, 3)
+    return (TC.nn_associate(pcd) if kind == "nn" else TC.proj_associate(pcd, TC.ICP_WINDOWS[name])), pcd, nrm
+
+
+@pytest.fixture(scope="module")
+def scenes_a(gpu):
+    proj, nn = device_scenes(TC.scene_a_depth())
+    out = {("proj", "whole"): proj, ("proj", "cropped"): proj.crop(TC.ICP_WINDOWS["cropped"]), ("nn", "whole"): nn}
+    return {k: (s,) + scene_truth(s, *k) for k, s in out.items()}
+
+
+@pytest.fixture(scope="module")
+def loop_truth(scenes_a):
+    main, _ = TC.cloud_a_main()
+    out = {}
+    for kind in ("proj", "nn"):
+        _, assoc, pcd, nrm = scenes_a[kind, "whole"]
+        out[kind] = T.icp(main, assoc, pcd, nrm, max(TC.LOOP_ITERATIONS))
+    return out
+
+
+# ---- (a) terms, point by point ------------------------------------------------------------------------------------------------------------------
+TERM_CASES = [("proj", "whole", False), ("proj", "whole", True), ("proj", "cropped", False), ("proj", "cropped", True), ("nn", "whole", False)]
+
+
+@pytest.mark.parametrize("kind,name,packed", TERM_CASES)
+def test_terms_are_point_to_plane(scenes_a, kind, name, packed):
+    """debug_contrib29 on cloud A with all its blocks: arrays and packed record, whole and cropped; the kd-tree scene built by init_Scene_nn_device."""
+    cloud, block, _ = TC.cloud_a()
+    scene, assoc, pcd, nrm = scenes_a[kind, name]
+    rows = api.debug_contrib29(api.DeviceVector.from_host(cloud.reshape(-1)), scene, packed=packed)
+    truth = TC.truth_terms((kind, name, "a"), cloud, assoc, pcd, nrm)
+    TC.check_terms(rows, cloud, block, truth, f"device {kind} {name} packed={packed}", TC.oracle_rows_of(TC.scene_a_oracle(kind, name)))
+
+
+# ---- (b) the pending update ------------------------------------------------------------------------------------------------------------------------
+def updates(scenes_a):
+    main, _ = TC.cloud_a_main()
+    _, assoc, pcd, nrm = scenes_a["proj", "whole"]
+    return TC.given_updates(T.float64_truth(TC.truth_terms(("proj", "main"), main, assoc, pcd, nrm)[0].sum(0))[0])
+
+
+@pytest.mark.parametrize("which", ["pass0", "20deg"])
+@pytest.mark.parametrize("kind,name,packed", [("proj", "whole", False), ("proj", "whole", True), ("nn", "whole", False)])
+def test_pending_update_moves_the_cloud_and_the_terms_follow(scenes_a, kind, name, packed, which):
+    """debug_contrib29(update=M): the cloud the kernel wrote back is R p + t, and the terms are the float64 terms OF THE FLOAT32 CLOUD IT WROTE BACK
+    (so that the update's rounding is not counted a second time)."""
+    main, _ = TC.cloud_a_main()
+    M = updates(scenes_a)[which]
+    scene, assoc, pcd, nrm = scenes_a[kind, name]
+    dev = api.DeviceVector.from_host(main.reshape(-1))
+    rows = api.debug_contrib29(dev, scene, update=M, packed=packed)
+    moved = dev.to_host().reshape(-1, 3)
+    TC.check_moved(moved, M, main, f"device {kind} packed={packed} {which}", TC.MOVED_GIVEN_UNITS_MEASURED)
+    truth = TC.truth_terms((kind, name, which), moved, assoc, pcd, nrm)
+    TC.check_terms(rows, moved, np.full(len(moved), "main"), truth, f"device {kind} packed={packed} after {which}", TC.oracle_rows_of(TC.scene_a_oracle(kind, name)), min_accept=300)
+
+
+# ---- (c) the 29 sums of the product pass -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ppb", TC.SUM_PPBS)
+@pytest.mark.parametrize("kind,cfg", [("proj", {}), ("nn", {}), ("nn", dict(nn_split=1))], ids=["proj", "nn-default", "nn-split"])
+def test_pass_sums_are_the_sums_of_the_terms(scenes_a, kind, cfg, ppb):
+    """One ragged ICP_Point2Plane_batch of the windows of cloud A under api.trace_sums, criteria (0, 0, 1): row 0 of every window against the float64
+    sum of its float64 terms."""
+    main, _ = TC.cloud_a_main()
+    scene, assoc, pcd, nrm = scenes_a[kind, "whole"]
+    t64, sc, _, _ = TC.truth_terms((kind, "main"), main, assoc, pcd, nrm)
+    sizes = TC.SUM_SIZES + (len(main),)
+    flat, offs = ragged([main[:n] for n in sizes])
+    with options(points_per_block=ppb, **cfg):
+        rows = api.trace_sums(len(sizes), 2)
+        icp_batch(flat, offs, scene, (0.0, 0.0, 1))
+    assert not np.isnan(rows[0]).any()
+    worst = {n: TC.check_sums(rows[0, i], t64[:n], sc[:n], ppb, f"device {kind} {cfg} {n} points") for i, n in enumerate(sizes)}
+    TC.say(f"sums device {kind} {cfg} ppb {ppb}: units of 2^-24 of the summed scales per window {({k: round(v, 3) for k, v in worst.items()})}; max {max(worst.values()):.3f}")
+
+
+# ---- (d) the loop ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("solve", ["host", "device"])
+@pytest.mark.parametrize("kind", ["proj", "nn"])
+def test_loop_follows_the_float64_loop_to_the_known_motion(scenes_a, loop_truth, kind, solve):
+    main, M = TC.cloud_a_main()
+    known = np.linalg.inv(M)
+    scene = scenes_a[kind, "whole"][0]
+    offs = np.array([0, len(main)], np.uint32)
+    with options(points_per_block=TC.ICP_PPB, solve=api.SOLVE_DEVICE if solve == "device" else api.SOLVE_HOST):
+        for N in TC.LOOP_ITERATIONS:
+            rec = icp_batch(main, offs, scene, (0.0, 0.0, N))[0]
+            TC.check_loop(rec["T"], rec["fitness"], rec["inlier_rmse"], loop_truth[kind], N, main, known, f"device {kind} {solve} solve")
+
+
+# ---- (e) the fused path --------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fused_b(gpu):
+    """Scene B on the device, the clouds the device renders of the eight hypotheses and the float64 loop started from each, per scene kind."""
+    sb = TC.scene_b()
+    proj = api.compute_proj(A_K, A_W, A_H)
+    model = api.Model(tris=sb["tris"])
+    clouds = [api.depth2cloud(api.render(model, sb["hyps"][i:i + 1], A_W, A_H, proj), A_W, A_H, A_K).to_host().reshape(-1, 3) for i in range(len(sb["hyps"]))]
+    out = dict(model=model, projection=proj, clouds=clouds)
+    for kind, scene in zip(("proj", "nn"), device_scenes(sb["depth"])):
+        assoc, pcd, nrm = scene_truth(scene, kind)
+        out[kind] = dict(scene=scene, assoc=assoc, pcd=pcd, nrm=nrm, truths=[T.icp(cl, assoc, pcd, nrm, TC.FUSED_ITERATIONS) for cl in clouds])
+    return out
+
+
+@pytest.mark.parametrize("solve", ["host", "device"])
+@pytest.mark.parametrize("kind", ["proj", "nn"])
+def test_fused_path_follows_the_float64_loop(fused_b, kind, solve):
+    """api.refine_batch on scene B, eight hypotheses: the comparison of test_truth_host.py's fused test, started from api.depth2cloud(api.render(...));
+    every compared hypothesis ends nearer to the true pose than it started (ADD over the mesh vertices).  Under host solve the sums of every
+    hypothesis' first pass are held to the float64 sums of its cloud as well."""
+    sb, f = TC.scene_b(), fused_b[kind]
+    crit = api.ICPConvergenceCriteria(0.0, 0.0, TC.FUSED_ITERATIONS)
+    with options(points_per_block=TC.ICP_PPB, solve=api.SOLVE_DEVICE if solve == "device" else api.SOLVE_HOST):
+        rows = api.trace_sums(len(sb["hyps"]), TC.FUSED_ITERATIONS + 1) if solve == "host" else None
+        res, sizes = api.refine_batch(fused_b["model"], sb["hyps"], A_W, A_H, fused_b["projection"], A_K, f["scene"], crit)
+    assert np.array_equal(sizes, [len(c) for c in fused_b["clouds"]])
+    TC.check_fused(res, fused_b["clouds"], f["truths"], kind, f"device {kind} {solve} solve")
+    if rows is not None:
+        TC.check_fused_sums(rows[0], fused_b["clouds"], f["assoc"], f["pcd"], f["nrm"], ("fused", kind), f"device {kind}")

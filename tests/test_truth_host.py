@@ -1,4 +1,5 @@
-"""The oracle against float64 geometry (tests/truth_ref.py): render, back-projection, the row convention between them, normals, the projective lookup.
+"""The oracle against float64 geometry (tests/truth_ref.py): render, back-projection, the row convention between them, normals, the projective lookup,
+and (second half) the refinement loop: per-point terms, pending update, sums, the loop and its fixed point, the fused path.
 No GPU.  Every device test of this suite is a parity test against oracle/pose_oracle.c; this file is what makes those meaningful -- it would notice a
 misunderstanding that oracle and kernels share -- and it is where the bounds of tests/test_truth_gpu.py are measured (tests/truth_cases.py,
 profiles/truth/README.md).  Out of reach of the ray caster and therefore parity-only: triangles with a vertex at or behind z = 1 (dropped from both
@@ -101,3 +102,117 @@ def test_noise_image_reaches_all_256_subsets_of_the_tap_gates():
 def test_oracle_lookup_takes_the_pixel_the_projection_says(name):
     pts, _ = TC.lookup_cloud(name)
     TC.check_lookup(TC.oracle_lookup_rows(name)(pts), name, "oracle")
+
+
+# =================================================================================================================================================
+#  The refinement loop: the oracle's terms, pending update, sums, loop and fused path against the float64 definitions of tests/truth_ref.py.
+#  This is where TERM_UNITS_MEASURED ... FUSED_RMSE_REL_MEASURED of tests/truth_cases.py are measured: every test asserts that the figure it
+#  finds has not grown past its constant (the checks themselves ask for 1.25 times the constant).
+# =================================================================================================================================================
+KINDS = ["proj", "nn"]
+
+
+def scene_arrays(kind, name="whole"):
+    """(oracle scene, float64 association, scene points, scene normals) of scene A."""
+    s = TC.scene_a_oracle(kind, name)
+    assoc = TC.nn_associate(s.pcd) if kind == "nn" else TC.proj_associate(s.pcd, TC.ICP_WINDOWS[name])
+    return s, assoc, s.pcd, s.normal
+
+
+# ---- (a) terms, point by point ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,name", [("proj", "whole"), ("proj", "cropped"), ("nn", "whole")])
+def test_oracle_terms_are_point_to_plane(kind, name):
+    cloud, block, _ = TC.cloud_a()
+    s, assoc, pcd, nrm = scene_arrays(kind, name)
+    truth = TC.truth_terms((kind, name, "a"), cloud, assoc, pcd, nrm)
+    worst, share = TC.check_terms(TC.oracle_rows_of(s)(cloud), cloud, block, truth, f"oracle {kind} {name}")
+    assert worst <= TC.TERM_UNITS_MEASURED, worst
+
+
+def test_kdtree_band_holds_every_disagreement():
+    """The kd-tree band holds every disagreement of a first pass: on cloud A the oracle's winner (the scene point its walk of the tree ends at) differs
+    from brute force in float64 only where the relative gap to the runner-up is below NN_GAP_BAND (on these inputs: nowhere).  How wide the band has to
+    be for the LATER passes of a loop is another matter: profiles/truth/README.md "Bands of the loop"."""
+    cloud, block, _ = TC.cloud_a()
+    s = TC.scene_a_oracle("nn")
+    nn = T.nearest(cloud, s.pcd, TC.ICP_MAX_DIST)
+    win = np.array([s.query(p)[1] for p in cloud])
+    differ = win != nn.winner
+    TC.say(f"kd-tree winners on cloud A: {int(differ.sum())} differ from brute force; their gaps {np.sort(nn.margin_gap[differ])[:8]}; smallest gap of an agreeing point "
+           f"{nn.margin_gap[~differ].min():.3e}; below the band {int((nn.margin_gap < TC.NN_GAP_BAND).sum())}")
+    assert (nn.margin_gap[differ] < TC.NN_GAP_BAND).all()
+
+
+# ---- (b) the pending update ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_oracle_pending_update_moves_the_cloud(kind):
+    """O.icp with one iteration returns the cloud moved by its update of pass 0: R p + t with the float64 update of the float64 sums of pass 0."""
+    main, _ = TC.cloud_a_main()
+    s, assoc, pcd, nrm = scene_arrays(kind)
+    t64, _, _, _ = TC.truth_terms((kind, "main"), main, assoc, pcd, nrm)
+    E, _, _ = T.float64_truth(t64.sum(0))
+    _, passes, moved, _ = O.icp(main, s, (0.0, 0.0, 1), O.SUM_CANONICAL, TC.ICP_PPB)
+    assert passes == 2
+    worst = TC.check_moved(moved, E, main, f"oracle {kind}")
+    assert worst <= TC.MOVED_UNITS_MEASURED, worst
+    # ... and the update alone, given as float32 values: what the device's debug entry is asked
+    for which, M in TC.given_updates(E).items():
+        worst = TC.check_moved(O.transform_cloud(main, M), M, main, f"oracle given {which} ({kind})", TC.MOVED_GIVEN_UNITS_MEASURED)
+        assert worst <= TC.MOVED_GIVEN_UNITS_MEASURED, worst
+
+
+# ---- (c) the 29 sums ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ppb", TC.SUM_PPBS)
+@pytest.mark.parametrize("kind", KINDS)
+def test_oracle_sums_are_the_sums_of_the_terms(kind, ppb):
+    main, _ = TC.cloud_a_main()
+    s, assoc, pcd, nrm = scene_arrays(kind)
+    t64, sc, _, margin = TC.truth_terms((kind, "main"), main, assoc, pcd, nrm)
+    worst = {}
+    for n in TC.SUM_SIZES + (len(main),):
+        worst[n] = TC.check_sums(O.sum29(main[:n], s, O.SUM_CANONICAL, ppb), t64[:n], sc[:n], ppb, f"oracle {kind} {n} points")
+    seq = float(TC.units(O.sum29(main, s, O.SUM_SEQUENTIAL), t64.sum(0), sc.sum(0)).max())
+    TC.say(f"sums oracle {kind} ppb {ppb}: units of 2^-24 of the summed scales per window {({k: round(v, 3) for k, v in worst.items()})}; max {max(worst.values()):.3f}; "
+           f"sequential mode on the whole cloud {seq:.1f}; {int((margin < 1).sum())} of {len(main)} points are band members (the truth's decision is used for them too)")
+    assert max(worst.values()) <= TC.SUM_UNITS_MEASURED[ppb], worst
+
+
+# ---- (d) the loop ------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def loop_truth():
+    main, _ = TC.cloud_a_main()
+    out = {}
+    for kind in KINDS:
+        s, assoc, pcd, nrm = scene_arrays(kind)
+        out[kind] = T.icp(main, assoc, pcd, nrm, max(TC.LOOP_ITERATIONS))
+    return out
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_oracle_loop_follows_the_float64_loop_to_the_known_motion(kind, loop_truth):
+    main, M = TC.cloud_a_main()
+    known = np.linalg.inv(M)
+    s = TC.scene_a_oracle(kind)
+    for N in TC.LOOP_ITERATIONS:
+        rec, passes, _, _ = O.icp(main, s, (0.0, 0.0, N), O.SUM_CANONICAL, TC.ICP_PPB)
+        assert passes == N + 1
+        traj, rel, fixed = TC.check_loop(rec["T"], rec["fitness"], rec["inlier_rmse"], loop_truth[kind], N, main, known, f"oracle {kind}")
+        assert traj <= TC.TRAJ_ADD_MEASURED_MM and rel <= TC.RMSE_REL_MEASURED[N] and fixed <= TC.FIXED_ADD_MEASURED_MM[N], (N, traj, rel, fixed)
+
+
+# ---- (e) the fused path ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_oracle_fused_path_follows_the_float64_loop(kind):
+    sb = TC.scene_b()
+    proj = O.compute_proj(TC.ICP_K, TC.ICP_W, TC.ICP_H)
+    s = (O.NNScene if kind == "nn" else O.ProjScene)(sb["depth"], TC.ICP_K, TC.ICP_MAX_DIST)
+    assoc = TC.nn_associate(s.pcd) if kind == "nn" else TC.proj_associate(s.pcd, TC.ICP_WINDOWS["whole"])
+    clouds = [O.depth2cloud(O.render(sb["tris"], sb["hyps"][i:i + 1], TC.ICP_W, TC.ICP_H, proj)[0], TC.ICP_K) for i in range(len(sb["hyps"]))]
+    truths = [T.icp(cl, assoc, s.pcd, s.normal, TC.FUSED_ITERATIONS) for cl in clouds]
+    res, sizes, _ = O.refine_batch(sb["tris"], sb["hyps"], TC.ICP_W, TC.ICP_H, proj, TC.ICP_K, s, (0.0, 0.0, TC.FUSED_ITERATIONS), O.SUM_CANONICAL, TC.ICP_PPB)
+    assert np.array_equal(sizes, [len(c) for c in clouds])
+    TC.say(f"fused oracle {kind}: cloud sizes {sizes.tolist()}")
+    _, worst, worst_rel = TC.check_fused(res, clouds, truths, kind, f"oracle {kind}")
+    assert worst <= TC.FUSED_ADD_MEASURED_MM and worst_rel <= TC.FUSED_RMSE_REL_MEASURED, (worst, worst_rel)
+    rows0 = [O.sum29(cl, s, O.SUM_CANONICAL, TC.ICP_PPB) for cl in clouds]
+    assert TC.check_fused_sums(rows0, clouds, assoc, s.pcd, s.normal, ("fused", kind), f"oracle {kind}") <= TC.SUM_UNITS_MEASURED[TC.ICP_PPB]

@@ -2,7 +2,7 @@
 
 The oracle restates the reference in its own float32 arithmetic, and the kernels are held to the oracle bit for bit; a misunderstanding
 the two share (a flipped row, a half pixel, a truncation for a rounding, a normal of the wrong sign) is invisible to parity.  What is here
-is the geometry itself: rays, planes, spheres and the pinhole projection in plain numpy, float64 throughout, in whatever operand order
+is the geometry itself: rays, planes, spheres, the pinhole projection, and point-to-plane refinement (terms, nearest neighbour, update, loop) in plain numpy, float64 throughout, in whatever operand order
 numpy likes.  Oracle and kernels are held to it within bounds that are MEASURED on the oracle (profiles/truth/README.md).
 
 Conventions (all from the reference; DESIGN.md section 1 "Image rows"):
@@ -10,6 +10,7 @@ Conventions (all from the reference; DESIGN.md section 1 "Image rows"):
   back-projection and the projective lookup read pixel (u, v) as the ray ((u - cx)/fx, (v - cy)/fy, 1);
   a RENDER's row v holds the surface along the ray of row v + RENDER_ROW_OFFSET.
 """
+import math
 from collections import namedtuple
 
 import numpy as np
@@ -180,3 +181,116 @@ def project(points, K, tl_x, tl_y, W, H, scene_z=None, max_dist_diff=0.1):
         accept = surf & (gate <= max_dist_diff)
         margin_z = np.where(surf, np.abs(gate - max_dist_diff), np.inf)
     return Projection(np.where(inside, px, -1), np.where(inside, py, -1), inside, margin_px, accept, margin_z)
+
+
+# ---- the refinement loop: point-to-plane terms, nearest neighbour, the rigid update -------------------------------------------------------------
+def rigid_apply(M, points):
+    """R p + t for the 4 x 4 (or 16 values, row-major) M and (n, 3) points."""
+    M = np.asarray(M, np.float64).reshape(4, 4)
+    return np.asarray(points, np.float64).reshape(-1, 3) @ M[:3, :3].T + M[:3, 3]
+
+
+_UPPER = [(a, b) for a in range(6) for b in range(a, 6)]          # the 21 slots of the upper triangle, row-major (icp.h:138-206)
+
+
+def point_to_plane_terms(src, dst, nrm):
+    """What one correspondence (source point s, scene point d, scene normal n) adds to the normal equations of point-to-plane ICP, linearised
+    about the identity: the residual r = (d - s) . n and its gradient J = (s x n, n) with respect to (rotation vector, translation).
+    Returns (terms (n, 29), scales (n, 29)).  Slots, the reference's (icp.h:138-206): 0 .. 20 the upper triangle of J J^T row-major,
+    21 .. 26 J r, 27 the squared distance |d - s|^2, 28 the count 1.  A scale is the sum of the magnitudes of what is added and subtracted
+    to form the term: |a_i b_i| summed for a dot or cross product component, the product of the factors' scales for a product; float32
+    arithmetic in any order misses the term by a few units of 2^-24 of its scale, and where the scale is 0 the term is exactly 0."""
+    s = np.asarray(src, np.float64).reshape(-1, 3)
+    d = np.asarray(dst, np.float64).reshape(-1, 3)
+    n = np.asarray(nrm, np.float64).reshape(-1, 3)
+    e = d - s
+    r = np.einsum("ij,ij->i", e, n)
+    r_scale = np.abs(e * n).sum(1)
+    J = np.concatenate([np.cross(s, n), n], 1)
+    roll1, roll2 = np.roll(np.abs(s), -1, 1) * np.roll(np.abs(n), -2, 1), np.roll(np.abs(s), -2, 1) * np.roll(np.abs(n), -1, 1)
+    J_scale = np.concatenate([roll1 + roll2, np.abs(n)], 1)      # component i of s x n is s[i+1] n[i+2] - s[i+2] n[i+1]
+    terms, scales = np.empty((len(s), 29)), np.empty((len(s), 29))
+    for k, (a, b) in enumerate(_UPPER):
+        terms[:, k], scales[:, k] = J[:, a] * J[:, b], J_scale[:, a] * J_scale[:, b]
+    terms[:, 21:27], scales[:, 21:27] = J * r[:, None], J_scale * r_scale[:, None]
+    terms[:, 27] = scales[:, 27] = (e * e).sum(1)
+    terms[:, 28] = scales[:, 28] = 1.0
+    return terms, scales
+
+
+Nearest = namedtuple("Nearest", "winner d2 accept margin_gap margin_gate")
+
+
+def nearest(points, scene_points, max_dist, chunk=256):
+    """Brute force, in chunks of `chunk` queries: for every point the scene point at the smallest squared distance d2 (pcd_scene.h:60-136
+    finds the same one through its tree), accept = d2 < max_dist^2.  margin_gap: (d2 of the runner-up - d2) / d2 of the runner-up, the
+    relative gap that another rounding of the two distances would have to bridge to change the winner (1 for a scene of one point or a
+    point that lies on its winner); margin_gate: |d2 - max_dist^2|."""
+    P = np.asarray(points, np.float64).reshape(-1, 3)
+    Q = np.asarray(scene_points, np.float64).reshape(-1, 3)
+    win, d2, second = np.zeros(len(P), np.int64), np.zeros(len(P)), np.full(len(P), np.inf)
+    for a in range(0, len(P), chunk):
+        D = (P[a:a + chunk, 0, None] - Q[None, :, 0]) ** 2 + (P[a:a + chunk, 1, None] - Q[None, :, 1]) ** 2 + (P[a:a + chunk, 2, None] - Q[None, :, 2]) ** 2
+        w = D.argmin(1)
+        rows = np.arange(len(w))
+        win[a:a + chunk], d2[a:a + chunk] = w, D[rows, w]
+        if len(Q) > 1:
+            D[rows, w] = np.inf
+            second[a:a + chunk] = D.min(1)
+    with np.errstate(invalid="ignore"):
+        gap = np.where(np.isfinite(second) & (second > 0), (second - d2) / np.where(second > 0, second, 1.0), np.where(np.isfinite(second), 0.0, 1.0))
+    g2 = float(max_dist) ** 2
+    return Nearest(win, d2, d2 < g2, gap, np.abs(d2 - g2))
+
+
+def float64_truth(s):
+    """The update of 29 sums: np.linalg.solve(A + 0.01 I, b) in float64, A the symmetric matrix whose upper triangle is s[0:21] row-major and
+    b = s[21:27]; then Rz Ry Rx from math.sin / math.cos and the translation x[3:6] (icp.cpp:7-27 in exact arithmetic).
+    Returns (4 x 4 transform, condition number of A + 0.01 I, x)."""
+    s = np.asarray(s, np.float64).reshape(-1)
+    A = np.zeros((6, 6))
+    for k, (a, b) in enumerate(_UPPER):
+        A[a, b] = A[b, a] = s[k]
+    A += 0.01 * np.eye(6)
+    x = np.linalg.solve(A, s[21:27])
+    cx, sx, cy, sy, cz, sz = (math.cos(x[0]), math.sin(x[0]), math.cos(x[1]), math.sin(x[1]), math.cos(x[2]), math.sin(x[2]))
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    T = np.eye(4)
+    T[:3, :3] = Rz @ Ry @ Rx
+    T[:3, 3] = x[3:]
+    return T, float(np.linalg.cond(A)), x
+
+
+Icp = namedtuple("Icp", "T Ts sums margins in_band fitness rmse")
+
+
+def icp(cloud, associate, scene_points, scene_normals, iterations):
+    """Gauss-Newton point-to-plane refinement in float64 (icp.cpp:125-188 with criteria (0, 0, iterations): `iterations` updates, then one more
+    pass that only scores).  associate(points) -> (index into the scene arrays, accept, margin) per point, the margin in units of the
+    caller's band (below 1: a float32 evaluation may decide otherwise).
+    Returns T: the composed transform; Ts[k]: the composed transform after k updates (Ts[0] = identity); sums[k]: the 29 sums of pass k;
+    margins[k] / in_band[k]: the smallest margin of pass k and how many points were below 1; fitness[k] = count / n and
+    rmse[k] = sqrt(sum 27 / count) of pass k -- the record of a run of k iterations is (Ts[k], fitness[k], rmse[k])."""
+    P = np.asarray(cloud, np.float64).reshape(-1, 3).copy()
+    Q = np.asarray(scene_points, np.float64).reshape(-1, 3)
+    N = np.asarray(scene_normals, np.float64).reshape(-1, 3)
+    T = np.eye(4)
+    Ts, sums, margins, in_band, fitness, rmse = [T], [], [], [], [], []
+    for it in range(iterations + 1):
+        idx, accept, margin = associate(P)
+        terms, _ = point_to_plane_terms(P[accept], Q[idx[accept]], N[idx[accept]])
+        s = terms.sum(0)
+        sums.append(s)
+        margins.append(float(np.min(margin)) if len(P) else np.inf)
+        in_band.append(int((np.asarray(margin) < 1.0).sum()))
+        fitness.append(s[28] / max(len(P), 1))
+        rmse.append(float(np.sqrt(s[27] / s[28])) if s[28] > 0 else 0.0)
+        if it == iterations or s[28] == 0:
+            break
+        E, _, _ = float64_truth(s)
+        P = rigid_apply(E, P)
+        T = E @ T
+        Ts.append(T)
+    return Icp(T, Ts, np.array(sums), np.array(margins), np.array(in_band), np.array(fitness), np.array(rmse))

@@ -501,6 +501,52 @@ int  pr_pose_distance(const pr_vec3 *points_dev, uint32_t n_points, const pr_mat
 int  pr_cluster_greedy(const uint32_t *order, uint32_t n_order, const pr_pose_dist *dist, uint32_t n_poses, float max_disp_mm,
                        uint32_t *kept_out, uint32_t *n_kept, uint32_t *rep_out);
 
+/* ---- visible surface discrepancy (VSD): do an estimate and the truth show the same surface in the measured frame? --------------------------
+ * The third member of the BOP family of pose errors, next to pr_pose_distance's MSSD and MSPD.  Both poses of a pair are rendered, each is
+ * asked where it is visible in the scene depth frame, and the pixels of the two visible surfaces that disagree are counted.  This is the
+ * BOP-2019 convention ("bop19" visibility, step cost) restated from memory: the toolkit was not at hand when this was written, so nothing
+ * here pins it beyond this text.
+ * One mesh; n_est estimated and n_gt ground-truth poses: n_gt == n_est compares est_host[i] with gt_host[i], n_gt == 1 compares every
+ * estimate with the one truth (rendered once per depth chunk, not once per estimate); anything else is invalid.  proj as pr_render takes it;
+ * scene_depth_dev is a dense width x height frame on the device in mm, int32 when depth_is_i32 is set, uint16 otherwise, read on every
+ * call; K = 9 intrinsics or NULL; delta_mm = the visibility tolerance, taus_mm[n_taus] the misalignment tolerances (non-decreasing).  There
+ * is no ROI: an evaluation is full-frame.
+ * For frame pixel (x, y), y the image row as the scene frame stores it, e and g = pr_render's values of the estimate and the truth there,
+ * s = the scene value; everything float32, no contraction, '/' and sqrtf correctly rounded:
+ *   1. ray factor: with K, xn = ((float)x - K[2]) / K[0], yn = ((float)y - K[5]) / K[4], c = sqrtf((xn*xn + yn*yn) + 1.0f); with K == NULL
+ *      c = 1.0f -- distances are then depths, and every quantity below is an integer as long as delta, the taus and the depths are integers
+ *      below 2^24.
+ *   2. distances: E = e > 0 ? (float)e * c : 0, G from g likewise, T = s > 0 ? (float)s * c : 0 (s <= 0: no measurement).
+ *   3. visibility: vg = G > 0 && (T == 0 || G - T <= delta);  ve = E > 0 && (T == 0 || E - T <= delta || vg).
+ *   4. inter = vg && ve, uni = vg || ve, and for every k: far_k = inter && fabsf(G - E) >= tau_k.
+ * The record counts these over the frame; being integers, the counts are exact in any order of summation.  BOP's error for tau_k is
+ * (far[k] + uni - inter) / uni, or 1 when uni == 0; that division is the caller's.
+ * Synchronous, on the calling thread's context and its own stream and workspaces; a batch pending on an asynchronous slot is not disturbed;
+ * nothing derived from the scene is kept.  PR_ERR_INVALID, with nothing written and BEFORE any device is touched (so also on a machine
+ * without one), for: n_gt neither n_est nor 1; n_taus > PR_VSD_MAX_TAUS; delta_mm or a tau negative or not finite; taus not non-decreasing;
+ * a non-finite entry of K, K[0] == 0 or K[4] == 0; width or height 0 or a frame beyond the scoring calls' size limit; and, with pairs to
+ * compute: a non-finite pose entry, a null proj, est_host, gt_host, scene_depth_dev, out_host, taus_mm (n_taus > 0) or tris_dev (n_tris > 0).
+ * n_est == 0 returns PR_OK, writes nothing and needs no device.
+ * pr_pose_vsd_multi: estimate i and its truth are rendered with meshes[mesh_index_host[i]] (the mesh table of the mixed batches above);
+ * n_gt == n_est only; records in the caller's order, each byte for byte what the single-mesh call gives that pair; a mesh index out of
+ * range, n_meshes == 0 or a null table is PR_ERR_INVALID.  Not offered: an asynchronous form, a ROI, the "tlinear" cost, keeping the
+ * truth's render between calls. */
+#define PR_VSD_MAX_TAUS 12
+typedef struct {
+    uint32_t visib_gt;     /* pixels with vg                                                                                  */
+    uint32_t visib_est;    /* pixels with ve                                                                                  */
+    uint32_t inter;        /* vg && ve                                                                                        */
+    uint32_t uni;          /* vg || ve                                                                                        */
+    uint32_t far[PR_VSD_MAX_TAUS];   /* inter && |G - E| >= taus_mm[k]; entries at and beyond n_taus are written as 0        */
+} pr_vsd_counts;           /* 64 B; the record of one pair                                                                    */
+int  pr_pose_vsd(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *est_host, uint32_t n_est, const pr_mat4 *gt_host, uint32_t n_gt,
+                 uint32_t width, uint32_t height, const pr_mat4 *proj, const void *scene_depth_dev, int depth_is_i32,
+                 const float K[9] /* may be NULL */, float delta_mm, const float *taus_mm, uint32_t n_taus, pr_vsd_counts *out_host);
+int  pr_pose_vsd_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *est_host, uint32_t n_est,
+                       const pr_mat4 *gt_host, uint32_t n_gt, uint32_t width, uint32_t height, const pr_mat4 *proj, const void *scene_depth_dev,
+                       int depth_is_i32, const float K[9] /* may be NULL */, float delta_mm, const float *taus_mm, uint32_t n_taus,
+                       pr_vsd_counts *out_host);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

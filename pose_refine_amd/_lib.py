@@ -40,9 +40,12 @@ COMPOSE_NONE, COMPOSE_MAX_POSES = 0xFFFF, 65535      # PR_COMPOSE_NONE, PR_COMPO
 POSE_DIST = np.dtype([("disp_sum_q16", "<u8"), ("max_disp_sq", "<f4"), ("max_proj_sq", "<f4"), ("sym_sum", "<u2"), ("sym_disp", "<u2"),
                       ("sym_proj", "<u2"), ("reserved", "<u2"), ("n_points", "<u4"), ("reserved2", "<u4")])
 POSE_DIST_MAX_SYMS, POSE_DIST_MAX_POSES, POSE_DIST_MAX_POINTS = 64, 4096, 1 << 24     # PR_POSE_DIST_MAX_SYMS, _MAX_POSES, _MAX_POINTS
+# pr_vsd_counts: the visible surfaces of an estimate and a truth against the scene frame, counted (pr_pose_vsd)
+VSD_MAX_TAUS = 12                        # PR_VSD_MAX_TAUS
+VSD = np.dtype([("visib_gt", "<u4"), ("visib_est", "<u4"), ("inter", "<u4"), ("uni", "<u4"), ("far", "<u4", (VSD_MAX_TAUS,))])
 POSE_DIST_CHUNK = 256                    # PR_POSE_DIST_CHUNK (pr_tuning.h; the library reports its own as option "pose_dist_chunk")
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
-assert VISIBLE.itemsize == 32 and FRAME.itemsize == 32 and POSE_DIST.itemsize == 32
+assert VISIBLE.itemsize == 32 and FRAME.itemsize == 32 and POSE_DIST.itemsize == 32 and VSD.itemsize == 64
 
 
 class PoseRefineError(RuntimeError):
@@ -155,6 +158,8 @@ SIGNATURES = {
     "pr_compose_detections_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "pr_pose_distance": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, _i32, _vp, _u32, _vp, _vp]),
     "pr_cluster_greedy": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32), _vp]),
+    "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
+    "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

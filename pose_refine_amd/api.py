@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -917,6 +917,62 @@ def select_hypotheses(scores, overlap, max_shared: Sequence[int] = (1, 4), min_f
     frac = np.where(den <= 0, 0.0, sc["inlier"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
     order = order[frac[order] >= float(min_fraction)]
     return select_greedy(order, overlap, int(max_shared[0]), int(max_shared[1]))
+
+
+# ------------------------------------------------------------------------------------------------
+# visible surface discrepancy (VSD): an estimate and the truth rendered, masked by the scene depth, compared pixel by pixel
+# ------------------------------------------------------------------------------------------------
+VSD_DELTA_BOP = 15.0                                                  # mm: BOP's visibility tolerance
+VSD_TAUS_BOP = tuple(round(0.05 * k, 2) for k in range(1, 11))       # misalignment tolerances as fractions of the model diameter: the caller multiplies
+VSD_THRESHOLDS_BOP = tuple(round(0.05 * k, 2) for k in range(1, 11))  # correctness thresholds on the error
+
+
+def _pose_vsd(mesh_of, est, gt, width: int, height: int, proj, scene_depth, K, delta_mm: float, taus_mm) -> np.ndarray:
+    gt = _poses44(gt, "gt").reshape(-1, 16)                           # (what needs no device is checked first)
+    taus = _f32(taus_mm, -1)
+    k = None if K is None else _f32(K, -1)
+    if k is not None and k.size != 9:
+        raise ValueError("K must hold 9 values")
+    suffix, lead, est, alive = mesh_of(est)
+    pj = _f32(proj, -1)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    out = np.zeros(len(est), VSD)
+    check(getattr(_lib.load(), "pr_pose_vsd" + suffix)(*lead, ptr(est), len(est), ptr(gt), len(gt), width, height, ptr(pj), sd.data(), int(sd.dtype == np.int32),
+                                                       None if k is None else ptr(k), float(delta_mm), ptr(taus) if len(taus) else None, len(taus), ptr(out)))
+    return out
+
+
+def pose_vsd(tris, est, gt, width: int, height: int, proj, scene_depth, K=None, delta_mm: float = VSD_DELTA_BOP, taus_mm=()) -> np.ndarray:
+    """``pr_pose_vsd``: VSD[n] comparing the render of ``est[i]`` with that of ``gt[i]`` -- or of the one pose ``gt`` of shape (4, 4) /
+    (1, 4, 4) -- where each is visible in ``scene_depth`` (as ``score_poses`` takes it: a DeviceVector or a host array, int32 or uint16, mm).
+    ``K``: 9 intrinsics (distances along the ray), or None (depths).  ``taus_mm``: up to ``VSD_MAX_TAUS`` non-decreasing tolerances in mm.
+    Read the records with ``vsd_errors``."""
+    return _pose_vsd(lambda e: _one_mesh(tris, e), est, gt, width, height, proj, scene_depth, K, delta_mm, taus_mm)
+
+
+def pose_vsd_multi(meshes, mesh_index, est, gt, width: int, height: int, proj, scene_depth, K=None, delta_mm: float = VSD_DELTA_BOP,
+                   taus_mm=()) -> np.ndarray:
+    """``pr_pose_vsd_multi``: ``pose_vsd`` for pairs whose pair i uses ``meshes[mesh_index[i]]``; as many truths as estimates.  VSD[n] in pair order."""
+    return _pose_vsd(lambda e: _mesh_batch(meshes, mesh_index, e), est, gt, width, height, proj, scene_depth, K, delta_mm, taus_mm)
+
+
+def vsd_errors(records, n_taus: int) -> np.ndarray:
+    """BOP's VSD error of every record for its first ``n_taus`` tolerances, float64[n, n_taus]: ``(far[k] + uni - inter) / uni``, 1 where ``uni == 0``."""
+    r = np.asarray(records)
+    if not 0 <= int(n_taus) <= VSD_MAX_TAUS:
+        raise ValueError(f"n_taus must lie in 0 .. {VSD_MAX_TAUS}")
+    uni, inter = r["uni"].astype(np.float64)[..., None], r["inter"].astype(np.float64)[..., None]
+    far = r["far"][..., :int(n_taus)].astype(np.float64)
+    return np.where(uni > 0, (far + uni - inter) / np.where(uni > 0, uni, 1.0), 1.0)
+
+
+def vsd_recall(errors, thresholds=VSD_THRESHOLDS_BOP) -> float:
+    """The fraction of (pose, tau, threshold) triples with ``error < threshold``: BOP's average recall over the taus of ``errors`` and ``thresholds``."""
+    e = np.asarray(errors, np.float64)
+    th = np.asarray(thresholds, np.float64).reshape(-1)
+    if e.size == 0 or th.size == 0:
+        return 0.0
+    return float((e[..., None] < th).mean())
 
 
 # ------------------------------------------------------------------------------------------------

@@ -237,6 +237,13 @@ hipError_t launch_pose_dist(const pr_vec3 *points, uint32_t n_points, const doub
                             void *partials, hipStream_t s);
 hipError_t launch_pose_dist_combine(const void *partials, uint32_t n_rows, uint32_t n_pairs, uint32_t n_k, uint32_t n_points, bool with_proj,
                                     pr_pose_dist *records, hipStream_t s);
+// vsd.hip: pr_pose_vsd for the pairs of a rendered chunk (launch_render_boxes' layout).  Pair p compares hypothesis p * est_mul (the estimate) with
+// hypothesis p * gt_mul + gt_add (the truth) of the chunk: {2, 2, 1} = estimates and truths interleaved, {1, 0, n} = every estimate against the one
+// truth rendered behind them.  Added into records[16 * p] (pr_vsd_counts words), which the caller zeroed; entries of tau at and beyond n_taus are not read.
+struct VsdPairing { uint32_t est_mul, gt_mul, gt_add; };
+struct VsdParams { float delta; uint32_t n_taus; float tau[PR_VSD_MAX_TAUS]; uint32_t has_k; float fx, cx, fy, cy; };      // K[0], K[2], K[4], K[5]; has_k 0: ray factor 1
+hipError_t launch_vsd_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_pairs, const VsdPairing &pairing, uint32_t width,
+                            uint32_t height, const void *scene, bool scene_i32, const VsdParams &pm, uint32_t *records, hipStream_t s);
 hipError_t launch_pack_export(const DevIcpState *st, pr_result *out, const uint32_t *counts, uint32_t *host_counts, pr_result *host_results,
                               uint32_t n, hipStream_t s);
 hipError_t launch_stage_words(const void *src_host_mapped, void *dst, size_t bytes, hipStream_t s);

@@ -512,6 +512,64 @@ int score_run(const ScoreRequest &req)
             for (uint32_t b = 0; b < P; ++b) req.overlap[(size_t)pl.order[a] * P + pl.order[b]] = ov[(size_t)a * P + b];
     return PR_OK;
 }
+// ---- visible surface discrepancy (pr_pose_vsd, pr_pose_vsd_multi) ------------------------------------------------------------------------
+// score_core's render (staged poses, model box, packed pixel boxes) of BOTH poses of every pair in one chunk, followed by one kernel that walks the
+// union of a pair's two boxes against the scene frame (vsd.hip); the score kernel does not run and the records are per pair, so this is a
+// small core of its own beside score_core.  Same stream, workspaces and read-back: a batch pending on a slot is neither waited for nor disturbed.
+// renders: the pairs interleaved (estimate, truth, estimate, truth ...: 2 P poses; of a mixed batch, in its plan's order) -- or, with one_gt,
+// the P estimates alone, and every chunk renders the one truth once, behind its estimates.  Chunks hold whole pairs.
+int vsd_core(const MeshSource &src, const pr_mat4 *renders, const pr_mat4 *one_gt, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj,
+             const void *scene, bool scene_i32, const prk::VsdParams &pm, pr_vsd_counts *out)
+{
+    constexpr uint32_t kWords = sizeof(pr_vsd_counts) / sizeof(uint32_t);
+    static_assert(sizeof(pr_vsd_counts) == 64 && kWords == 4 + PR_VSD_MAX_TAUS, "pr_vsd_counts: sixteen counters");
+    const size_t img = (size_t)W * H;
+    const uint32_t cap = depth_chunk(img, one_gt ? P + 1 : 2 * P);                  // renders a chunk may hold: at least 2
+    const uint32_t pairs_chunk = std::max(1u, one_gt ? cap - 1 : cap / 2), chunk = one_gt ? pairs_chunk + 1 : 2 * pairs_chunk;
+    PR_TRY(model_boxes(src, chunk));
+    std::vector<pr_mat4> with_gt(one_gt ? chunk : 0);
+    for (uint32_t q0 = 0; q0 < P; q0 += pairs_chunk) {
+        const uint32_t nq = std::min(pairs_chunk, P - q0), np = one_gt ? nq + 1 : 2 * nq;
+        PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
+        PR_TRY(g->row_count.ensure(sizeof(uint32_t) * (size_t)H * np));
+        PR_TRY(g->row_off.ensure(sizeof(uint32_t) * (size_t)H * np));
+        PR_TRY(g->counts.ensure(sizeof(uint32_t) * np));
+        PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
+        PR_TRY(g->vsd_rec.ensure(sizeof(pr_vsd_counts) * nq));
+        PR_TRY(g->h_vsd.ensure(sizeof(pr_vsd_counts) * nq));
+        uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
+        if (one_gt) { std::copy(renders + q0, renders + q0 + nq, with_gt.begin()); with_gt[nq] = *one_gt; }
+        {
+            SpanGuard sp(kSpanRender);
+            PR_TRY(render_chunk(src, one_gt ? with_gt.data() : renders, one_gt ? 0 : 2 * q0, np, chunk, W, H, proj, pr_roi{ 0, 0, 0, 0 }, box_off, /*bands=*/false));
+        }
+        const prk::VsdPairing pairing = one_gt ? prk::VsdPairing{ 1, 0, nq } : prk::VsdPairing{ 2, 2, 1 };
+        ReadBack back;
+        HIP_TRY(prk::launch_fill_i32(g->vsd_rec.as<int32_t>(), (size_t)kWords * nq, 0, g->stream));
+        HIP_TRY(prk::launch_vsd_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, nq, pairing, W, H, scene, scene_i32, pm, g->vsd_rec.as<uint32_t>(), g->stream));
+        PR_TRY(back.queue(g->vsd_rec.p, g->h_vsd, kWords * nq));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        back.deliver(out + q0, sizeof(pr_vsd_counts) * nq);
+    }
+    drain_spans();
+    return PR_OK;
+}
+prk::VsdParams vsd_params(const float *K, float delta, const float *taus, uint32_t n_taus)
+{
+    prk::VsdParams pm{};
+    pm.delta = delta; pm.n_taus = n_taus;
+    for (uint32_t k = 0; k < n_taus; ++k) pm.tau[k] = taus[k];
+    if (K) { pm.has_k = 1; pm.fx = K[0]; pm.cx = K[2]; pm.fy = K[4]; pm.cy = K[5]; }
+    return pm;
+}
+// estimates and truths of as many pairs interleaved: the batch vsd_core renders
+std::vector<pr_mat4> interleaved_pairs(const pr_mat4 *est, const pr_mat4 *gt, uint32_t P)
+{
+    std::vector<pr_mat4> out(2 * (size_t)P);
+    for (uint32_t i = 0; i < P; ++i) { out[2 * (size_t)i] = est[i]; out[2 * (size_t)i + 1] = gt[i]; }
+    return out;
+}
+
 // the request of an entry point from what all eight have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
 ScoreRequest score_request(const char *fn, ScoreKind kind, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, pr_roi roi,
                            const void *scene_dev, int depth_is_i32, int32_t tau, pr_pose_score *scores_host)
@@ -1342,6 +1400,46 @@ int pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, co
     r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
     compose_outputs(r, labels_dev_out, depth_dev_out, visible_host, frame_host);
     return score_run(r);
+}
+
+int pr_pose_vsd(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *est_host, uint32_t n_est, const pr_mat4 *gt_host, uint32_t n_gt, uint32_t width,
+                uint32_t height, const pr_mat4 *proj, const void *scene_depth_dev, int depth_is_i32, const float K[9], float delta_mm, const float *taus_mm,
+                uint32_t n_taus, pr_vsd_counts *out_host)
+{
+    PR_TRY(vsd_args_ok("pr_pose_vsd", false, tris_dev, n_tris, est_host, n_est, gt_host, n_gt, width, height, proj, scene_depth_dev, K, delta_mm, taus_mm, n_taus,
+                       out_host));                                   // before any device use
+    if (n_est == 0) return PR_OK;
+    PR_ENTER();
+    const MeshSource src{ tris_dev, n_tris, nullptr };
+    const prk::VsdParams pm = vsd_params(K, delta_mm, taus_mm, n_taus);
+    if (n_gt == 1 && n_est != 1) return vsd_core(src, est_host, gt_host, n_est, width, height, proj, scene_depth_dev, depth_is_i32 != 0, pm, out_host);
+    const std::vector<pr_mat4> pairs = interleaved_pairs(est_host, gt_host, n_est);
+    return vsd_core(src, pairs.data(), nullptr, n_est, width, height, proj, scene_depth_dev, depth_is_i32 != 0, pm, out_host);
+}
+
+// A mixed batch: both poses of pair i carry mesh_index_host[i], so the stable grouping keeps them adjacent -- the grouped batch is interleaved pairs
+// again, pair j of it the caller's pair order[2 j] / 2.  Records into a temporary: nothing reaches out_host unless the call succeeded.
+int pr_pose_vsd_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *est_host, uint32_t n_est,
+                      const pr_mat4 *gt_host, uint32_t n_gt, uint32_t width, uint32_t height, const pr_mat4 *proj, const void *scene_depth_dev,
+                      int depth_is_i32, const float K[9], float delta_mm, const float *taus_mm, uint32_t n_taus, pr_vsd_counts *out_host)
+{
+    PR_TRY(vsd_args_ok("pr_pose_vsd_multi", true, nullptr, 0, est_host, n_est, gt_host, n_gt, width, height, proj, scene_depth_dev, K, delta_mm, taus_mm, n_taus,
+                       out_host));                                   // before any device use, like the mesh table's checks below
+    if (n_est == 0) return PR_OK;
+    std::vector<uint32_t> index2(2 * (size_t)n_est);
+    for (uint32_t i = 0; mesh_index_host && i < n_est; ++i) {
+        if (n_meshes && mesh_index_host[i] >= n_meshes) { set_error("pr_pose_vsd_multi: mesh_index[%u] = %u, but there are %u meshes", i, mesh_index_host[i], n_meshes); return PR_ERR_INVALID; }
+        index2[2 * (size_t)i] = index2[2 * (size_t)i + 1] = mesh_index_host[i];
+    }
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_pose_vsd_multi", meshes, n_meshes, mesh_index_host ? index2.data() : nullptr, 2 * (size_t)n_est, pl));
+    PR_ENTER();
+    const std::vector<pr_mat4> pairs = interleaved_pairs(est_host, gt_host, n_est), grouped = grouped_poses(pl, pairs.data());
+    std::vector<pr_vsd_counts> rec(n_est);
+    PR_TRY(vsd_core(MeshSource{ nullptr, 0, &pl }, grouped.data(), nullptr, n_est, width, height, proj, scene_depth_dev, depth_is_i32 != 0,
+                    vsd_params(K, delta_mm, taus_mm, n_taus), rec.data()));
+    for (uint32_t j = 0; j < n_est; ++j) out_host[pl.order[2 * (size_t)j] / 2] = rec[j];
+    return PR_OK;
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

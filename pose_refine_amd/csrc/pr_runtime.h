@@ -299,6 +299,32 @@ inline int pose_dist_args_ok(const pr_vec3 *points_dev, uint32_t n_points, const
     *n_pairs_out = n_pairs;
     return PR_OK;
 }
+// pr_pose_vsd / pr_pose_vsd_multi's checks, all but a mixed batch's mesh table (plan_meshes, which needs no device either): no device is touched
+// before they pass (no HIP call in here; tools/job_sanitize.cpp runs it under ASan / UBSan).  multi: a mesh table instead of tris_dev, pairs only.
+inline int vsd_args_ok(const char *fn, bool multi, const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *est, uint32_t n_est, const pr_mat4 *gt, uint32_t n_gt,
+                       uint32_t W, uint32_t H, const pr_mat4 *proj, const void *scene, const float *K, float delta, const float *taus, uint32_t n_taus,
+                       const pr_vsd_counts *out)
+{
+    if (n_gt != n_est && (multi || n_gt != 1)) { set_error("%s: %u estimates against %u truths (as many of each%s)", fn, n_est, n_gt, multi ? "" : ", or one truth"); return PR_ERR_INVALID; }
+    if (n_est > 0x7fffffffu) { set_error("%s: more than 2^31 - 1 pairs", fn); return PR_ERR_INVALID; }
+    if (n_taus > PR_VSD_MAX_TAUS) { set_error("%s: %u taus, at most PR_VSD_MAX_TAUS = %d", fn, n_taus, PR_VSD_MAX_TAUS); return PR_ERR_INVALID; }
+    if (!(delta >= 0.0f) || !std::isfinite(delta)) { set_error("%s: delta_mm must be finite and >= 0", fn); return PR_ERR_INVALID; }
+    for (uint32_t k = 0; taus && k < n_taus; ++k) {
+        if (!(taus[k] >= 0.0f) || !std::isfinite(taus[k])) { set_error("%s: taus_mm[%u] must be finite and >= 0", fn, k); return PR_ERR_INVALID; }
+        if (k && taus[k] < taus[k - 1]) { set_error("%s: taus_mm must not decrease (entry %u)", fn, k); return PR_ERR_INVALID; }
+    }
+    if (K) {
+        for (int i = 0; i < 9; ++i) if (!std::isfinite(K[i])) { set_error("%s: K[%d] is not finite", fn, i); return PR_ERR_INVALID; }
+        if (K[0] == 0.0f || K[4] == 0.0f) { set_error("%s: K[0] and K[4] must not be 0", fn); return PR_ERR_INVALID; }
+    }
+    if (W == 0 || H == 0) { set_error("%s: bad arguments (an empty frame)", fn); return PR_ERR_INVALID; }
+    if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
+    if (n_est == 0) return PR_OK;
+    if (!proj || !est || !gt || !scene || !out || (n_taus && !taus) || (!multi && !tris_dev && n_tris > 0)) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_est; ++i) if (!finite16(est[i])) { set_error("%s: est_host[%u] has a non-finite entry", fn, i); return PR_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_gt; ++i) if (!finite16(gt[i])) { set_error("%s: gt_host[%u] has a non-finite entry", fn, i); return PR_ERR_INVALID; }
+    return PR_OK;
+}
 // A slot's pinned blocks, in bytes.  h_in, staged to the device by one kernel: poses | pixel boxes | offsets of the packed boxes.
 // h_out, stored by the batch's last kernels: cloud sizes | result records | the word the device-side model-box check writes (1 = the
 // assumed box or a scene cache was stale), each on a 64-byte line of its own.
@@ -429,6 +455,8 @@ struct Ctx {
     PinBuf h_cmp;                    // the records on their way to the caller, then the index table on its way to the device
     DevBuf pd_mats, pd_part, pd_rec; // pr_pose_distance: rows 0..2 of every A S_k (double) followed by those of every B (float); the partials of a launch; its records
     PinBuf h_pd_mats, h_pd_rec;      // the matrices on their way in, the records on their way out
+    DevBuf vsd_rec;                  // pr_pose_vsd: the records of a chunk's pairs
+    PinBuf h_vsd;                    // ... on their way to the caller
     DevBuf lvl_rows, lvl_counts, lvl_carry;   // pr_refine_pyramid: per-row sample counts and offsets of every level of a chunk, the level clouds' sizes, the per-level carry records
     PinBuf h_lvl_carry;
     DevBuf multi;                    // mixed batches (pr_*_multi): mesh table, box index / image of each hypothesis, raster groups

@@ -1,4 +1,4 @@
-// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, contour.hip, compose.hip and nobody else): the workgroup's
+// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, contour.hip, compose.hip, vsd.hip and nobody else): the workgroup's
 // part of a hypothesis' pixel box, the test of a rendered depth against the scene, the sum of a workgroup's counters, the launchers' loop
 // gfx950 (CDNA4, wave64); integer arithmetic only, differences in 64 bits: every value is bit-identical to the CPU restatement.
 #pragma once
@@ -9,14 +9,15 @@ namespace prk {
 // ---- the box walk: one workgroup = kBoxRowsPerBlock image rows of the box of hypothesis blockIdx.y, 4 wavefronts x 4 rows, lanes along a row ----
 struct BoxBlock { int4 bb; int r_lo, r_hi, row0; };                 // the pixel box, its image rows (raster rows run flipped), the first of this wavefront's four rows
 // false: no row of the box in this workgroup -- the same for every thread, so the kernel returns before any barrier
-__device__ __forceinline__ bool box_block(const int4 *__restrict__ bbox, uint32_t height, BoxBlock &b)
+__device__ __forceinline__ bool box_block(const int4 bb, uint32_t height, BoxBlock &b)
 {
-    b.bb = bbox[blockIdx.y];
+    b.bb = bb;
     b.r_lo = (int)height - 1 - b.bb.w; b.r_hi = (int)height - 1 - b.bb.y;
     const int blk0 = (int)(blockIdx.x * kBoxRowsPerBlock);
     b.row0 = blk0 + (int)(threadIdx.x >> 6) * 4;
     return !(b.bb.x > b.bb.z || b.r_lo > b.r_hi || blk0 > b.r_hi || blk0 + (int)kBoxRowsPerBlock - 1 < b.r_lo);
 }
+__device__ __forceinline__ bool box_block(const int4 *__restrict__ bbox, uint32_t height, BoxBlock &b) { return box_block(bbox[blockIdx.y], height, b); }
 
 // ---- the depth test: what an inlier is for the ranking, the selection, the contour gate and the composition ----
 __device__ __forceinline__ bool rendered(int32_t d) { return d > 0 && d != INT_MAX; }      // something was drawn here (INT_MAX: the render's background)

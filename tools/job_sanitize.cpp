@@ -1,5 +1,5 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
-// Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job and score_request_ok with null and
+// Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok and vsd_args_ok with null and
 // out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split.  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
@@ -101,6 +101,53 @@ int main()
                 CHECK(compose_args_ok("job_sanitize", PR_COMPOSE_MAX_POSES) == PR_OK && compose_args_ok("job_sanitize", 0xffffffffu) == PR_ERR_INVALID);
             }
         }
+    // pr_pose_vsd's arguments: a good call of each form, nothing to compute, then one mistake at a time (the poses are read: real arrays)
+    {
+        std::vector<pr_mat4> est(5), gt(5);
+        for (auto *v : { &est, &gt }) for (pr_mat4 &m : *v) identity16(m.m);
+        const float taus[PR_VSD_MAX_TAUS + 1] = { 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11 };
+        pr_vsd_counts *out = reinterpret_cast<pr_vsd_counts *>(uintptr_t(0xd000));
+        auto vsd = [&](bool multi, const pr_triangle *t, const pr_mat4 *e, uint32_t ne, const pr_mat4 *gp, uint32_t ng, uint32_t W, uint32_t H, const pr_mat4 *p, const void *s,
+                       const float *k, float delta, const float *ts, uint32_t nt, const pr_vsd_counts *o) {
+            return vsd_args_ok("job_sanitize", multi, t, 5, e, ne, gp, ng, W, H, p, s, k, delta, ts, nt, o);
+        };
+        for (bool multi : { false, true }) {
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, PR_VSD_MAX_TAUS, out) == PR_OK);
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, nullptr, 0.0f, nullptr, 0, out) == PR_OK);
+            CHECK(vsd(multi, nullptr, nullptr, 0, nullptr, 0, 640, 480, nullptr, nullptr, nullptr, 15.0f, nullptr, 3, nullptr) == PR_OK);       // no pairs need no arrays
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 1, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == (multi ? PR_ERR_INVALID : PR_OK));
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 4, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 0, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 0x80000000u, gt.data(), 0x80000000u, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, PR_VSD_MAX_TAUS + 1, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, 0xffffffffu, out) == PR_ERR_INVALID);
+            for (float bad : { -1.0f, -0.0f - 1e-30f, INFINITY, -INFINITY, NAN }) {
+                CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, bad, taus, 3, out) == PR_ERR_INVALID);
+                float t3[3] = { 1.0f, bad, 3.0f };
+                CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, t3, 3, out) == PR_ERR_INVALID);
+                float k9[9]; std::memcpy(k9, K, sizeof k9); k9[7] = bad;
+                if (!std::isfinite(bad)) CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, k9, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+                std::vector<pr_mat4> e2 = est; e2[4].m[15] = bad;
+                if (!std::isfinite(bad)) CHECK(vsd(multi, tris, e2.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+                if (!std::isfinite(bad)) CHECK(vsd(multi, tris, est.data(), 5, e2.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            }
+            const float down[3] = { 1.0f, 3.0f, 2.0f };
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, down, 3, out) == PR_ERR_INVALID);
+            for (int i : { 0, 4 }) {
+                float k9[9]; std::memcpy(k9, K, sizeof k9); k9[i] = 0.0f;
+                CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, k9, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            }
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, nullptr, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, nullptr, 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 5, nullptr, 5, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, nullptr, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, nullptr, 3, out) == PR_ERR_INVALID);
+            CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, 3, nullptr) == PR_ERR_INVALID);
+            CHECK(vsd(multi, nullptr, est.data(), 5, gt.data(), 5, 640, 480, &proj, dev, K, 15.0f, taus, 3, out) == (multi ? PR_OK : PR_ERR_INVALID));
+            for (auto [W, H] : { std::pair<uint32_t, uint32_t>{ 0, 480 }, { 640, 0 }, { 8193, 1 }, { 8192, 4096 }, { 0xffffffffu, 0xffffffffu } })
+                CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, W, H, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
+        }
+    }
     // the pinned blocks of a slot: the parts in order, none overlapping, written and read back over their whole length
     for (size_t P : { size_t(0), size_t(1), size_t(3), size_t(65) }) {
         const SlotIn in(P);

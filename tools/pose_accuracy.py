@@ -4,7 +4,10 @@ and configs[2] (kd-tree scene), the 256 synth hypotheses of obj_06 at 640x480 ag
   unrefined, refine_batch at (0, 0, 20), refine_pyramid(PYRAMID_DEFAULT)  ->  ADD / MSSD / MSPD (api.pose_distance over the model's
   15 736 vertices, no symmetries: obj_06 has none): median, maximum, how many have ADD < 0.1 x the model diameter and MSSD < 1 mm;
   merge_duplicates at 1 mm in rank_hypotheses' order (score_poses, tau 5): how many distinct poses the batch holds;
-  the pyramid against refine_batch hypothesis by hypothesis (over those refine_batch converges on, fitness >= 0.9).
+  the pyramid against refine_batch hypothesis by hypothesis (over those refine_batch converges on, fitness >= 0.9);
+  VSD (api.pose_vsd against the scene's depth frame, BOP's delta of 15 mm and taus of 0.05 .. 0.5 x the diameter, with K): the median error at
+  tau = 0.2 d, the recall over taus and thresholds (api.vsd_recall), the MSSD and MSPD recalls over BOP's thresholds (0.05 .. 0.5 x the diameter;
+  5 .. 50 px at 640 px width) and the mean of the three -- the field's average recall, for one object in one frame.
 Then the time of pose_distance (256 pairs) and pose_distance_matrix (256 x 256), each with and without K: host clocks around the synchronous
 calls, after warm-up, the four cases interleaved call by call; median / min / max ms.  One JSON line.
 
@@ -52,11 +55,19 @@ def interleaved(cases, calls, warmup):
     return {k: stats(v) for k, v in ms.items()}
 
 
-def errors(model, poses, gt, K, diam):
+def errors(model, poses, gt, K, diam, frame):
     d = api.pose_distance(model, poses, gt, None, K)
     add, mssd, mspd = api.mean_displacement(d), api.max_displacement(d), api.max_projection(d)
     r3 = lambda x: round(float(x), 4)  # noqa: E731
-    return {"add_mm": {"median": r3(np.median(add)), "max": r3(add.max())}, "mssd_mm": {"median": r3(np.median(mssd)), "max": r3(mssd.max())},
+    W, H, proj, depth_dev = frame
+    taus = [t * diam for t in api.VSD_TAUS_BOP]
+    ve = api.vsd_errors(api.pose_vsd(model, poses, gt, W, H, proj, depth_dev, K, api.VSD_DELTA_BOP, taus), len(taus))
+    th = np.asarray(api.VSD_THRESHOLDS_BOP)
+    ar_vsd, ar_mssd = api.vsd_recall(ve), float((mssd[:, None] < th * diam).mean())
+    ar_mspd = float((mspd[:, None] < np.arange(5, 51, 5) * (W / 640.0)).mean())
+    return {"vsd_error_at_0.2_diameter_median": r3(np.median(ve[:, api.VSD_TAUS_BOP.index(0.2)])), "recall_vsd": r3(ar_vsd), "recall_mssd": r3(ar_mssd),
+            "recall_mspd": r3(ar_mspd), "recall_mean": r3((ar_vsd + ar_mssd + ar_mspd) / 3.0),
+            "add_mm": {"median": r3(np.median(add)), "max": r3(add.max())}, "mssd_mm": {"median": r3(np.median(mssd)), "max": r3(mssd.max())},
             "mspd_px": {"median": r3(np.median(mspd)), "max": r3(mspd.max())},
             "add_below_0.1_diameter": int((add < 0.1 * diam).sum()), "mssd_below_1mm": int((mssd < 1.0).sum())}
 
@@ -79,9 +90,10 @@ def main():
     poses = synth.hypotheses(256)
     crit = api.ICPConvergenceCriteria(0.0, 0.0, 20)
     diam = diameter(model.vertices)
+    frame = (W, H, proj, api.DeviceVector.from_host(depth.reshape(-1)))
     out = {"workload": "configs[1] / configs[2]: obj_06.ply (15736 vertices), 256 synth hypotheses, 640x480, against synth.scene_pose(); no symmetries",
            "solve": args.solve, "diameter_mm": round(diam, 3), "schedule": [[s, list(c)] for s, c in api.PYRAMID_DEFAULT],
-           "unrefined": errors(model, poses, gt, K, diam)}
+           "unrefined": errors(model, poses, gt, K, diam, frame)}
     refined_proj = None
     for kind in ("proj", "nn"):
         scene = api.Scene_projective().init_Scene_projective_cuda(depth, K) if kind == "proj" else api.Scene_nn().init_Scene_nn_cuda(depth, K)
@@ -90,7 +102,7 @@ def main():
         r = {}
         sets = {"refine_batch_20": api.refined_poses(a, poses), "refine_pyramid": api.refined_poses(b, poses)}
         for name, ref in sets.items():
-            e = errors(model, ref, gt, K, diam)
+            e = errors(model, ref, gt, K, diam, frame)
             order = api.rank_hypotheses(api.score_poses(model, ref, W, H, proj, depth, 5))
             kept, _ = api.merge_duplicates(order, api.pose_distance_matrix(model, ref), 1.0)
             e["distinct_at_1mm"] = int(len(kept))

@@ -401,6 +401,57 @@ int  pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const
                              int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint8_t *edge_dist_dev,
                              pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host);
 
+/* ---- normal agreement: does the surface of a hypothesis' render face the way the scene's surface does? --------------------------------------
+ * The depth score, the overlap matrix and the contour check are blind to a pose whose surface lies within tau_mm of scene surface with the
+ * wrong orientation or curvature (a box face laid on a wall, a curved part pressed against a table): it collects inliers.  Where the depths
+ * agree, the normals should.  Both normals are estimated from depth, with the same estimator.
+ * Depth is integer mm.  A pixel is empty when its depth is <= 0, or when the render drew nothing there.  Let h = step with
+ * 1 <= h <= PR_NORMAL_MAX_STEP = 8.  Let J = jump_mm >= 0.  Take K row-major as everywhere: fx = K[0], cx = K[2], fy = K[4], cy = K[5],
+ * each converted to double once.
+ * Normal of image d at frame pixel (x, y).  It is defined iff all of these hold:
+ *   - d(x, y) > 0;
+ *   - the four pixels (x +- h, y) and (x, y +- h) lie inside the image;
+ *   - those four pixels are non-empty;
+ *   - each of them differs from d(x, y) by at most J.  The difference is taken in 64-bit integers.
+ * The image is the whole frame for the scene.  For a render it is the frame, or the ROI window when one is given.  A neighbour outside the
+ * image makes the normal undefined.  A neighbour inside the image but outside the render's packed box is empty by construction.
+ * With gu = d(x + h, y) - d(x - h, y), gv = d(x, y + h) - d(x, y - h) and z = d(x, y), all converted to double, the normal is computed in
+ * double in exactly this order with no contraction:
+ *     a = -(fx * gu)
+ *     b = -(fy * gv)
+ *     c = ((2h) * z + (x - cx) * gu) + (y - cy) * gv
+ * The normal is unnormalised and points away from the camera.  It is exact for a fronto-parallel plane.
+ * Agreement.  Take the render normal (a_r, b_r, c_r) and the scene normal (a_s, b_s, c_s) at the same frame pixel.  Compute:
+ *     dot = (a_r * a_s + b_r * b_s) + c_r * c_s
+ *     q   = (a * a + b * b) + c * c          (once per image)
+ *     m   = (double)cos_min
+ * The pixel agrees iff dot >= 0 and dot * dot >= (m * m) * (q_r * q_s).  There is no square root and no division.
+ * Record per hypothesis.  Counts run over the pixels pr_score_poses counts as `inlier`, with the same tau_mm test. */
+#define PR_NORMAL_MAX_STEP 8
+typedef struct {
+    uint32_t tested;            /* inlier pixels where both normals are defined          */
+    uint32_t agree;             /* tested pixels that agree                              */
+    uint32_t disagree;          /* tested pixels that do not                             */
+    uint32_t no_render_normal;  /* inlier pixels, render normal undefined                */
+    uint32_t no_scene_normal;   /* inlier pixels, render normal defined, scene's not     */
+    uint32_t reserved[3];       /* written as 0                                          */
+} pr_pose_normal;               /* 32 B; tested == agree + disagree; scores.inlier == tested + no_render_normal + no_scene_normal */
+/* pr_score_normals renders every pose once and returns, in the caller's pose order: scores_host, byte for byte what pr_score_poses
+ * returns; normals_host, the records above; and, when overlap_host is not NULL, pr_score_overlap's matrix from the same render (n_poses
+ * <= PR_OVERLAP_MAX_POSES then), exactly as pr_score_contours does it.  Argument checks, ROI, scene types, chunking and the synchronous
+ * behaviour are those of pr_score_poses (pr_score_poses_multi for pr_score_normals_multi, which equals one single-mesh call per mesh, byte
+ * for byte).  PR_ERR_INVALID with nothing written for a step of 0 or above PR_NORMAL_MAX_STEP, jump_mm < 0, cos_min outside [0, 1] or NaN
+ * (all three checked before any device use), and for a null K or normals_host with n_poses > 0; n_poses == 0 returns PR_OK and writes
+ * nothing.  The counts carry no policy. */
+int  pr_score_normals(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses,
+                      uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32,
+                      int32_t tau_mm, const float K[9], uint32_t step, int32_t jump_mm, float cos_min,
+                      pr_pose_score *scores_host, pr_pose_normal *normals_host, uint32_t *overlap_host);
+int  pr_score_normals_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                            uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                            int depth_is_i32, int32_t tau_mm, const float K[9], uint32_t step, int32_t jump_mm, float cos_min,
+                            pr_pose_score *scores_host, pr_pose_normal *normals_host, uint32_t *overlap_host);
+
 /* ---- composition: the detections of a frame taken together -----------------------------------------------------------------------------
  * Everything above looks at a hypothesis on its own or at pairs.  pr_compose_detections renders a set of poses -- typically the few that
  * pr_select_greedy kept -- and composes them: all arithmetic in integers (differences in 64 bits), depth in mm.  r_i(q) is hypothesis i's

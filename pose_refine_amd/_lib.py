@@ -30,6 +30,9 @@ SCORE = np.dtype([("visible", "<u4"), ("inlier", "<u4"), ("occluded", "<u4"), ("
 # pr_pose_contour: depth-edge agreement of one hypothesis with the scene (pr_score_contours)
 CONTOUR = np.dtype([("contour", "<u4"), ("hit", "<u4"), ("occluded", "<u4"), ("miss", "<u4"), ("reserved", "<u4", (2,)), ("dist_sum", "<u8")])
 CONTOUR_MAX_RADIUS = 32                  # PR_CONTOUR_MAX_RADIUS
+# pr_pose_normal: surface-normal agreement of one hypothesis with the scene on its inlier pixels (pr_score_normals)
+NORMAL = np.dtype([("tested", "<u4"), ("agree", "<u4"), ("disagree", "<u4"), ("no_render_normal", "<u4"), ("no_scene_normal", "<u4"), ("reserved", "<u4", (3,))])
+NORMAL_MAX_STEP = 8                      # PR_NORMAL_MAX_STEP
 # pr_pose_visible / pr_frame_explained: what a hypothesis keeps once the batch is composed, and what the set explains (pr_compose_detections)
 VISIBLE = np.dtype([("owned", "<u4"), ("owned_inlier", "<u4"), ("owned_occluded", "<u4"), ("owned_violation", "<u4"), ("owned_missing", "<u4"),
                     ("reserved", "<u4", (3,))])
@@ -45,7 +48,7 @@ VSD_MAX_TAUS = 12                        # PR_VSD_MAX_TAUS
 VSD = np.dtype([("visib_gt", "<u4"), ("visib_est", "<u4"), ("inter", "<u4"), ("uni", "<u4"), ("far", "<u4", (VSD_MAX_TAUS,))])
 POSE_DIST_CHUNK = 256                    # PR_POSE_DIST_CHUNK (pr_tuning.h; the library reports its own as option "pose_dist_chunk")
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
-assert VISIBLE.itemsize == 32 and FRAME.itemsize == 32 and POSE_DIST.itemsize == 32 and VSD.itemsize == 64
+assert NORMAL.itemsize == 32 and VISIBLE.itemsize == 32 and FRAME.itemsize == 32 and POSE_DIST.itemsize == 32 and VSD.itemsize == 64
 
 
 class PoseRefineError(RuntimeError):
@@ -154,6 +157,8 @@ SIGNATURES = {
     "pr_scene_edge_distance_dev": (_i32, [_vp, _i32, _u32, _u32, C.c_int32, _u32, _vp]),
     "pr_score_contours": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "pr_score_contours_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "pr_score_normals": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _u32, C.c_int32, C.c_float, _vp, _vp, _vp]),
+    "pr_score_normals_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _u32, C.c_int32, C.c_float, _vp, _vp, _vp]),
     "pr_compose_detections": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "pr_compose_detections_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "pr_pose_distance": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, _i32, _vp, _u32, _vp, _vp]),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -1145,6 +1145,51 @@ def filter_by_contour(order, contours, min_fraction: float) -> np.ndarray:
     ``min_fraction``; what remains keeps its order and goes to ``select_hypotheses(order=...)``.  The ranking itself is untouched."""
     order = np.asarray(order, np.int64)
     return order[contour_fraction(contours)[order] >= float(min_fraction)]
+
+
+# ------------------------------------------------------------------------------------------------
+# normal agreement: does the render's surface face the way the scene's does, where their depths agree?
+# ------------------------------------------------------------------------------------------------
+def _score_normals(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, K, step: int, jump_mm: int, cos_min: float, roi, want_overlap: bool):
+    call, n = _score_call("pr_score_normals", mesh, width, height, proj, scene_depth, tau_mm, roi)
+    k = _f32(K, -1)
+    if k.size != 9:
+        raise ValueError("K must hold 9 values")
+    out, nrm = np.zeros(n, SCORE), np.zeros(n, NORMAL)
+    ov = np.zeros((n, n), np.uint32) if want_overlap else None
+    call(ptr(k), int(step), int(jump_mm), float(cos_min), ptr(out), ptr(nrm), ptr(ov) if want_overlap else None)
+    return (out, nrm, ov) if want_overlap else (out, nrm)
+
+
+def score_normals(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, K, step: int, jump_mm: int, cos_min: float,
+                  roi: Sequence[int] = (0, 0, 0, 0), want_overlap: bool = False):
+    """``pr_score_normals``: one render per pose serves ``score_poses``' records, the normal records and, with ``want_overlap``,
+    ``score_overlap``'s matrix.  On every inlier pixel the normal of the render and that of the scene, both estimated from depth by central
+    differences over ``step`` pixels (1 .. ``NORMAL_MAX_STEP``) from neighbours within ``jump_mm`` of the centre, agree when the angle
+    between them has a cosine of at least ``cos_min``.  Returns (SCORE[P], NORMAL[P]) or (SCORE[P], NORMAL[P], uint32[P, P]): per hypothesis
+    the inlier pixels where both normals exist (``tested`` = ``agree`` + ``disagree``) and those where the render's (``no_render_normal``)
+    or only the scene's (``no_scene_normal``) does not."""
+    return _score_normals(_one_mesh(tris, poses), width, height, proj, scene_depth, tau_mm, K, step, jump_mm, cos_min, roi, want_overlap)
+
+
+def score_normals_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int, K, step: int, jump_mm: int,
+                        cos_min: float, roi: Sequence[int] = (0, 0, 0, 0), want_overlap: bool = False):
+    """``pr_score_normals_multi``: ``score_normals`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; everything in pose order."""
+    return _score_normals(_mesh_batch(meshes, mesh_index, poses), width, height, proj, scene_depth, tau_mm, K, step, jump_mm, cos_min, roi, want_overlap)
+
+
+def normal_fraction(normals) -> np.ndarray:
+    """``agree / tested`` in float64: the share of the inlier pixels with both normals whose normals agree.  0 where ``tested`` is 0."""
+    n = np.asarray(normals)
+    den = n["tested"].astype(np.int64)
+    return np.where(den == 0, 0.0, n["agree"].astype(np.float64) / np.where(den == 0, 1, den).astype(np.float64))
+
+
+def filter_by_normals(order, normals, min_fraction: float) -> np.ndarray:
+    """``order`` (indices, best first, e.g. ``rank_hypotheses(scores)``) without the hypotheses whose ``normal_fraction`` is below
+    ``min_fraction``; what remains keeps its order and goes to ``select_hypotheses(order=...)``.  The ranking itself is untouched."""
+    order = np.asarray(order, np.int64)
+    return order[normal_fraction(normals)[order] >= float(min_fraction)]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -214,6 +214,12 @@ hipError_t launch_scene_edge_distance(const void *scene, bool scene_i32, uint32_
                                       unsigned long long *bits, uint8_t *row_dist, uint8_t *dist, hipStream_t s);
 hipError_t launch_contour_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
                                 const void *scene, bool scene_i32, const uint8_t *edge_dist, int32_t tau, int32_t jump_mm, uint32_t *records, hipStream_t s);
+// normals.hip: on the inlier pixels of every rendered box (launch_score_boxes' test with tau), the render's normal against the scene's, both estimated
+// from depth at distance `step` with neighbours within `jump` (pr_pose_normal's definition), counted into records[8 * i] (pr_pose_normal words: tested,
+// agree, disagree, no_render_normal, no_scene_normal, reserved x 3), which the caller zeroed.  m2 = cos_min squared; window as for launch_contour_boxes
+struct NormalParams { double fx, cx, fy, cy, m2; uint32_t step; int32_t jump, tau; };      // K[0], K[2], K[4], K[5], each converted to double once
+hipError_t launch_normal_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
+                               const void *scene, bool scene_i32, const NormalParams &p, uint32_t *records, hipStream_t s);
 // compose.hip: the hypotheses of a call taken together.  keys: width x height 64-bit words, (depth << 32 | caller's index) of the front-most render at every
 // frame pixel, all ones where nothing is drawn; index_of: position in the (grouped) batch -> caller's index, null: index0 + position.
 // launch_compose_tiles: once per depth chunk over launch_render_boxes' layout (first: the call's first chunk, which initialises the whole frame);

@@ -349,6 +349,8 @@ struct ReadBack {
 // as this one is scored -- and one launch over all pairs follows the last chunk.  The planes are dense: P x H x ceil(W / 64) words of 8 bytes.
 // kScoreContours: the contour records of the same renders against the scene's edge distance image (contour.hip), one more
 // kernel over every chunk's boxes right behind the score kernel; the records travel like the scores.
+// kScoreNormals: the normal records of the same renders against the scene (normals.hip), one more kernel over every chunk's boxes right behind
+// the score kernel; the records travel like the scores.
 // kScoreCompose: the same renders taken together (compose.hip).  One more kernel over every chunk's boxes folds them into
 // the key frame of the context -- the front-most render of every frame pixel with the CALLER's index of its hypothesis (req.order: grouped position ->
 // caller's index, null: the identity), so ties and labels need no remapping -- and every chunk leaves its pixel boxes in a workspace sized for
@@ -358,10 +360,13 @@ int score_core(const ScoreRequest &req)
 {
     const uint32_t P = req.P, W = req.W, H = req.H;
     const int32_t tau = req.tau;
-    const bool contours = req.kind == kScoreContours, compose = req.kind == kScoreCompose;
+    const bool contours = req.kind == kScoreContours, normals = req.kind == kScoreNormals, compose = req.kind == kScoreCompose;
     const MeshSource src{ req.tris, req.n_tris, req.plan };
     static_assert(sizeof(pr_pose_visible) == sizeof(pr_pose_score) && sizeof(pr_frame_explained) == sizeof(pr_pose_score), "pr_pose_visible, pr_frame_explained: 32-byte records");
     static_assert(sizeof(pr_pose_contour) == sizeof(pr_pose_score) && offsetof(pr_pose_contour, dist_sum) == 24, "pr_pose_contour: one 32-byte record, the sum in words 6 and 7");
+    static_assert(sizeof(pr_pose_normal) == sizeof(pr_pose_score), "pr_pose_normal: one 32-byte record");
+    const prk::NormalParams normal_params = normals ? prk::NormalParams{ (double)req.K[0], (double)req.K[2], (double)req.K[4], (double)req.K[5],
+                                                                          (double)req.cos_min * (double)req.cos_min, req.step, req.jump, tau } : prk::NormalParams{};
     const bool has_roi = req.roi.width > 0 && req.roi.height > 0;
     const int4 window = has_roi ? make_int4(req.roi.x, req.roi.y, req.roi.x + req.roi.width - 1, req.roi.y + req.roi.height - 1) : make_int4(0, 0, (int)W - 1, (int)H - 1);
     constexpr uint32_t kWords = sizeof(pr_pose_score) / sizeof(uint32_t);
@@ -400,13 +405,14 @@ int score_core(const ScoreRequest &req)
         PR_TRY(g->scores.ensure(sizeof(pr_pose_score) * np));
         PR_TRY(g->h_scores.ensure(sizeof(pr_pose_score) * np));
         if (contours) { PR_TRY(g->contours.ensure(sizeof(pr_pose_contour) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_pose_contour) * np)); }
+        if (normals) { PR_TRY(g->normals.ensure(sizeof(pr_pose_normal) * np)); PR_TRY(g->h_normals.ensure(sizeof(pr_pose_normal) * np)); }
         uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
         {
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, req.poses, p0, np, chunk, W, H, req.proj, req.roi, box_off, /*bands=*/false));
         }
         // records zeroed by a kernel and read back through the pinned array by a kernel: no memset or copy commands on this path (see refine_core)
-        ReadBack scores_back, contours_back;
+        ReadBack scores_back, contours_back, normals_back;
         HIP_TRY(prk::launch_fill_i32(g->scores.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
         HIP_TRY(prk::launch_score_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, req.scene, req.scene_i32, tau,
                                         g->scores.as<uint32_t>(), g->stream));
@@ -415,6 +421,12 @@ int score_core(const ScoreRequest &req)
             HIP_TRY(prk::launch_contour_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, req.scene, req.scene_i32, req.edge_dist, tau,
                                               req.jump, g->contours.as<uint32_t>(), g->stream));
             PR_TRY(contours_back.queue(g->contours.p, g->h_contours, kWords * np));
+        }
+        if (normals) {
+            HIP_TRY(prk::launch_fill_i32(g->normals.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
+            HIP_TRY(prk::launch_normal_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, req.scene, req.scene_i32, normal_params,
+                                             g->normals.as<uint32_t>(), g->stream));
+            PR_TRY(normals_back.queue(g->normals.p, g->h_normals, kWords * np));
         }
         if (req.overlap) {
             HIP_TRY(prk::launch_support_bits(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, req.scene, req.scene_i32, tau,
@@ -430,6 +442,7 @@ int score_core(const ScoreRequest &req)
         HIP_TRY(hipStreamSynchronize(g->stream));
         scores_back.deliver(req.scores + p0, sizeof(pr_pose_score) * np);
         if (contours) contours_back.deliver(req.contours + p0, sizeof(pr_pose_contour) * np);
+        if (normals) normals_back.deliver(req.normals + p0, sizeof(pr_pose_normal) * np);
     }
     if (req.overlap) {
         ReadBack back;
@@ -487,7 +500,7 @@ int refine_ordered(const RefineJob &job, const PyramidPlan *py, const pr_mat4 *p
 }
 
 // Every scoring entry point behind PR_ENTER: the checks, then the request as it is, or -- a mixed batch -- on the batch grouped by mesh into
-// temporaries, and the scores, contours and the matrix back to the caller's order: nothing reaches the caller's arrays unless the call succeeded
+// temporaries, and the scores, contours, normals and the matrix back to the caller's order: nothing reaches the caller's arrays unless the call succeeded
 // (the composition's records are written in the caller's order as they are: req.order).
 int score_run(const ScoreRequest &req)
 {
@@ -501,12 +514,14 @@ int score_run(const ScoreRequest &req)
     std::vector<pr_pose_score> sc(P);
     std::vector<uint32_t> ov(req.overlap ? (size_t)P * P : 0);
     std::vector<pr_pose_contour> cc(req.kind == kScoreContours ? P : 0);
+    std::vector<pr_pose_normal> nn(req.kind == kScoreNormals ? P : 0);
     ScoreRequest grouped = req;
     grouped.plan = &pl; grouped.order = pl.order.data(); grouped.poses = poses.data();
-    grouped.scores = sc.data(); grouped.overlap = req.overlap ? ov.data() : nullptr; grouped.contours = cc.data();
+    grouped.scores = sc.data(); grouped.overlap = req.overlap ? ov.data() : nullptr; grouped.contours = cc.data(); grouped.normals = nn.data();
     PR_TRY(score_core(grouped));
     for (uint32_t j = 0; j < P; ++j) req.scores[pl.order[j]] = sc[j];
     for (uint32_t j = 0; j < cc.size(); ++j) req.contours[pl.order[j]] = cc[j];
+    for (uint32_t j = 0; j < nn.size(); ++j) req.normals[pl.order[j]] = nn[j];
     if (req.overlap)                                             // rows and columns back into the caller's order
         for (uint32_t a = 0; a < P; ++a)
             for (uint32_t b = 0; b < P; ++b) req.overlap[(size_t)pl.order[a] * P + pl.order[b]] = ov[(size_t)a * P + b];
@@ -570,7 +585,7 @@ std::vector<pr_mat4> interleaved_pairs(const pr_mat4 *est, const pr_mat4 *gt, ui
     return out;
 }
 
-// the request of an entry point from what all eight have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
+// the request of an entry point from what all ten have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
 ScoreRequest score_request(const char *fn, ScoreKind kind, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, pr_roi roi,
                            const void *scene_dev, int depth_is_i32, int32_t tau, pr_pose_score *scores_host)
 {
@@ -1374,6 +1389,31 @@ int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
     ScoreRequest r = score_request("pr_score_contours_multi", kScoreContours, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
     r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
     r.jump = jump_mm; r.edge_dist = edge_dist_dev; r.contours = contours_host; r.overlap = overlap_host;
+    return score_run(r);
+}
+
+int pr_score_normals(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                     const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, const float K[9], uint32_t step,
+                     int32_t jump_mm, float cos_min, pr_pose_score *scores_host, pr_pose_normal *normals_host, uint32_t *overlap_host)
+{
+    PR_TRY(normal_params_ok("pr_score_normals", step, jump_mm, cos_min));          // before any device use
+    PR_ENTER();
+    ScoreRequest r = score_request("pr_score_normals", kScoreNormals, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.tris = tris_dev; r.n_tris = n_tris;
+    r.K = K; r.step = step; r.jump = jump_mm; r.cos_min = cos_min; r.normals = normals_host; r.overlap = overlap_host;
+    return score_run(r);
+}
+
+int pr_score_normals_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                           uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                           int depth_is_i32, int32_t tau_mm, const float K[9], uint32_t step, int32_t jump_mm, float cos_min,
+                           pr_pose_score *scores_host, pr_pose_normal *normals_host, uint32_t *overlap_host)
+{
+    PR_TRY(normal_params_ok("pr_score_normals_multi", step, jump_mm, cos_min));          // before any device use
+    PR_ENTER();
+    ScoreRequest r = score_request("pr_score_normals_multi", kScoreNormals, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
+    r.K = K; r.step = step; r.jump = jump_mm; r.cos_min = cos_min; r.normals = normals_host; r.overlap = overlap_host;
     return score_run(r);
 }
 

@@ -221,9 +221,9 @@ inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, 
     else job.sp.view = *static_cast<const pr_scene_proj *>(scene);     // (a plain projective scene: a crop at 0, 0)
     return PR_OK;
 }
-// ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_contours, pr_compose_detections and their _multi forms) ----
+// ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_contours, pr_score_normals, pr_compose_detections and their _multi forms) ----
 // What the caller asked for, as the entry point got it; score_run (pr_refine.cpp) takes it from there.  Every member is set by the entry point.
-enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreCompose };
+enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose };
 struct ScoreRequest {
     const char *fn; ScoreKind kind;                              // the entry point's name (for messages) and what it returns besides the scores
     const pr_triangle *tris; size_t n_tris;                      // one mesh for every hypothesis ...
@@ -231,8 +231,9 @@ struct ScoreRequest {
     const pr_mat4 *poses; uint32_t P, W, H; const pr_mat4 *proj; pr_roi roi;
     const void *scene; bool scene_i32; int32_t tau;
     pr_pose_score *scores;                                       // host, P records
-    uint32_t *overlap;                                           // host, P x P (kScoreOverlap: required; kScoreContours: null = none)
+    uint32_t *overlap;                                           // host, P x P (kScoreOverlap: required; kScoreContours, kScoreNormals: null = none)
     int32_t jump; const uint8_t *edge_dist; pr_pose_contour *contours;                          // kScoreContours: device distance image in, P host records out
+    const float *K; uint32_t step; float cos_min; pr_pose_normal *normals;                      // kScoreNormals (with jump): intrinsics and the estimator's step in, P host records out
     uint16_t *labels_dev; int32_t *depth_dev; pr_pose_visible *visible; pr_frame_explained *frame;     // kScoreCompose: two optional device images, host records
     const MeshPlan *plan; const uint32_t *order;                 // score_run's, null from the entry point: the grouped batch (position -> caller's index)
 };
@@ -255,12 +256,20 @@ inline int compose_args_ok(const char *fn, uint32_t P)
     }
     return PR_OK;
 }
-// Every check of a request that needs no device, in one order for all eight entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
+// pr_score_normals' own conditions (its entry points ask for the first before any device use as well)
+inline int normal_params_ok(const char *fn, uint32_t step, int32_t jump, float cos_min)
+{
+    if (step == 0 || step > PR_NORMAL_MAX_STEP) { set_error("%s: step must be 1 .. PR_NORMAL_MAX_STEP = %d (got %u)", fn, PR_NORMAL_MAX_STEP, step); return PR_ERR_INVALID; }
+    if (jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)jump); return PR_ERR_INVALID; }
+    if (!(cos_min >= 0.0f && cos_min <= 1.0f)) { set_error("%s: cos_min must lie in [0, 1] (got %g)", fn, (double)cos_min); return PR_ERR_INVALID; }      // (a NaN fails both)
+    return PR_OK;
+}
+// Every check of a request that needs no device, in one order for all ten entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
 // call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.  A request without hypotheses needs no arrays.
 inline int score_request_ok(const ScoreRequest &r)
 {
     const char *fn = r.fn;
-    if (r.kind == kScoreOverlap || (r.kind == kScoreContours && r.overlap)) PR_TRY(overlap_args_ok(fn, r.P, r.overlap));
+    if (r.kind == kScoreOverlap || ((r.kind == kScoreContours || r.kind == kScoreNormals) && r.overlap)) PR_TRY(overlap_args_ok(fn, r.P, r.overlap));
     if (r.kind == kScoreCompose) PR_TRY(compose_args_ok(fn, r.P));
     if (r.tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)r.tau); return PR_ERR_INVALID; }
     if (!r.proj || r.W == 0 || r.H == 0 || (r.P && (!r.poses || !r.scene || !r.scores || (!r.multi && !r.tris && r.n_tris > 0)))) {
@@ -270,6 +279,8 @@ inline int score_request_ok(const ScoreRequest &r)
     if (!roi_ok(r.roi, r.W, r.H)) { set_error("%s: roi out of image", fn); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
     if (r.kind == kScoreContours && r.jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)r.jump); return PR_ERR_INVALID; }
     if (r.kind == kScoreContours && r.P && (!r.edge_dist || !r.contours)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
+    if (r.kind == kScoreNormals) PR_TRY(normal_params_ok(fn, r.step, r.jump, r.cos_min));
+    if (r.kind == kScoreNormals && r.P && (!r.K || !r.normals)) { set_error("%s: bad arguments (K or normals_host is null)", fn); return PR_ERR_INVALID; }
     if (r.kind == kScoreCompose && r.P && (!r.visible || !r.frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }
     return PR_OK;
 }
@@ -449,6 +460,8 @@ struct Ctx {
     DevBuf ov_bits, ov_box, ov_mat;  // pr_score_overlap: the support bit planes and pixel boxes of ALL hypotheses of a call (they outlive its depth chunks), the P x P matrix
     PinBuf h_ov;                     // the matrix on its way to the caller
     DevBuf contours;                 // pr_score_contours: the contour records of a chunk
+    DevBuf normals;                  // pr_score_normals: the normal records of a chunk
+    PinBuf h_normals;                // ... on their way to the caller
     DevBuf edge_bits, edge_rows;     // pr_scene_edge_distance_dev: the scene's edge bit plane and its row distances (scratch of one call)
     PinBuf h_contours;
     DevBuf cmp_keys, cmp_box, cmp_rec;   // pr_compose_detections: the key frame (8 bytes per frame pixel), the pixel boxes of ALL hypotheses of a call followed by their caller's indices, the records

@@ -1,4 +1,4 @@
-// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, contour.hip, compose.hip, vsd.hip and nobody else): the workgroup's
+// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, contour.hip, normals.hip, compose.hip, vsd.hip and nobody else): the workgroup's
 // part of a hypothesis' pixel box, the test of a rendered depth against the scene, the sum of a workgroup's counters, the launchers' loop
 // gfx950 (CDNA4, wave64); integer arithmetic only, differences in 64 bits: every value is bit-identical to the CPU restatement.
 #pragma once
@@ -19,7 +19,7 @@ __device__ __forceinline__ bool box_block(const int4 bb, uint32_t height, BoxBlo
 }
 __device__ __forceinline__ bool box_block(const int4 *__restrict__ bbox, uint32_t height, BoxBlock &b) { return box_block(bbox[blockIdx.y], height, b); }
 
-// ---- the depth test: what an inlier is for the ranking, the selection, the contour gate and the composition ----
+// ---- the depth test: what an inlier is for the ranking, the selection, the contour gate, the normal agreement and the composition ----
 __device__ __forceinline__ bool rendered(int32_t d) { return d > 0 && d != INT_MAX; }      // something was drawn here (INT_MAX: the render's background)
 // the four tests of pr_pose_score for a rendered depth d against the scene value s: 0 inlier, 1 occluded (s < d - tau), 2 violation (s > d + tau), 3 missing
 __device__ __forceinline__ uint32_t depth_class(int32_t d, int32_t s, int64_t tau)

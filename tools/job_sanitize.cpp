@@ -59,7 +59,8 @@ int main()
     pr_pose_visible *visible = reinterpret_cast<pr_pose_visible *>(uintptr_t(0xb000));
     pr_frame_explained *frame = reinterpret_cast<pr_frame_explained *>(uintptr_t(0xc000));
     const pr_roi off_frame{ 631, 0, 10, 10 };
-    for (ScoreKind kind : { kScorePoses, kScoreOverlap, kScoreContours, kScoreCompose })
+    pr_pose_normal *normals = reinterpret_cast<pr_pose_normal *>(uintptr_t(0xe000));
+    for (ScoreKind kind : { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose })
         for (bool multi : { false, true }) {
             ScoreRequest ok{};
             ok.fn = "job_sanitize"; ok.kind = kind; ok.multi = multi; ok.poses = poses; ok.P = 70; ok.W = 640; ok.H = 480; ok.proj = &proj; ok.roi = pr_roi{ 630, 470, 10, 10 };
@@ -67,10 +68,11 @@ int main()
             if (multi) { ok.meshes = table; ok.n_meshes = 2; ok.mesh_index = index; } else { ok.tris = tris; ok.n_tris = 5; }
             if (kind == kScoreOverlap) ok.overlap = matrix;
             if (kind == kScoreContours) { ok.jump = 0; ok.edge_dist = edges; ok.contours = contours; }       // (no matrix: it is optional here)
+            if (kind == kScoreNormals) { ok.K = K; ok.step = PR_NORMAL_MAX_STEP; ok.jump = 0; ok.cos_min = 1.0f; ok.normals = normals; }       // (no matrix: it is optional here)
             if (kind == kScoreCompose) { ok.visible = visible; ok.frame = frame; }                          // (neither image: both are optional)
             CHECK(score_request_ok(ok) == PR_OK);
             ScoreRequest none_to_score = ok; none_to_score.P = 0; none_to_score.poses = nullptr; none_to_score.scene = nullptr; none_to_score.scores = nullptr;
-            none_to_score.overlap = nullptr; none_to_score.edge_dist = nullptr; none_to_score.contours = nullptr; none_to_score.visible = nullptr; none_to_score.frame = nullptr;
+            none_to_score.overlap = nullptr; none_to_score.edge_dist = nullptr; none_to_score.contours = nullptr; none_to_score.K = nullptr; none_to_score.normals = nullptr; none_to_score.visible = nullptr; none_to_score.frame = nullptr;
             CHECK(score_request_ok(none_to_score) == PR_OK);                                               // no hypotheses need no arrays
             auto refused_with = [&](auto &&mistake) { ScoreRequest r = ok; mistake(r); CHECK(score_request_ok(r) == PR_ERR_INVALID); };
             refused_with([](ScoreRequest &r) { r.poses = nullptr; });
@@ -93,6 +95,21 @@ int main()
                 refused_with([&](ScoreRequest &r) { r.overlap = matrix; r.P = PR_OVERLAP_MAX_POSES + 1; });
                 ScoreRequest many = ok; many.P = PR_OVERLAP_MAX_POSES + 1;                                    // without a matrix there is no such limit
                 CHECK(score_request_ok(many) == PR_OK);
+            }
+            if (kind == kScoreNormals) {
+                refused_with([](ScoreRequest &r) { r.K = nullptr; });
+                refused_with([](ScoreRequest &r) { r.normals = nullptr; });
+                refused_with([](ScoreRequest &r) { r.step = 0; });
+                refused_with([](ScoreRequest &r) { r.step = PR_NORMAL_MAX_STEP + 1; });
+                refused_with([](ScoreRequest &r) { r.step = 0xffffffffu; });
+                refused_with([](ScoreRequest &r) { r.jump = -1; });
+                refused_with([](ScoreRequest &r) { r.jump = -2147483647 - 1; });
+                for (float c : { -1e-6f, 1.0001f, NAN, INFINITY, -INFINITY }) refused_with([c](ScoreRequest &r) { r.cos_min = c; });
+                refused_with([&](ScoreRequest &r) { r.overlap = matrix; r.P = PR_OVERLAP_MAX_POSES + 1; });
+                ScoreRequest many = ok; many.P = PR_OVERLAP_MAX_POSES + 1; many.cos_min = 0.0f; many.step = 1; many.jump = 2147483647;      // without a matrix there is no such limit
+                CHECK(score_request_ok(many) == PR_OK);
+                ScoreRequest none_bad = none_to_score; none_bad.step = 0;                                       // the estimator's parameters are checked whatever P is
+                CHECK(score_request_ok(none_bad) == PR_ERR_INVALID);
             }
             if (kind == kScoreCompose) {
                 refused_with([](ScoreRequest &r) { r.visible = nullptr; });

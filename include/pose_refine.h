@@ -360,6 +360,70 @@ int  pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
 int  pr_select_greedy(const uint32_t *order, uint32_t n_order, const uint32_t *overlap, uint32_t n_poses,
                       uint32_t shared_num, uint32_t shared_den, uint32_t *selected_out, uint32_t *n_selected);
 
+/* ---- detections by cumulative cover: what does a hypothesis explain that the better ones have not? ---------------------------------------
+ * pr_select_greedy asks every accepted hypothesis separately; a hypothesis that straddles two accepted detections can pass both tests
+ * although no pixel of its support is new.  The cover rule looks at the accepted set as a whole.  All integers.  The support S_i is as
+ * above: the frame pixels pr_score_poses counts as `inlier` for hypothesis i.  Inputs: order (n_order indices, best first, each < n_poses
+ * and none twice), (new_num, new_den), min_new, max_keep.  Walk order with a claimed set C, empty at the start:
+ *   - skip i when |S_i| == 0: state PR_COVER_EMPTY (whatever has been accepted so far);
+ *   - once max_keep hypotheses are accepted nothing more is: every later i of the walk with |S_i| > 0 is PR_COVER_REJECTED with reason
+ *     PR_COVER_REASON_CAP (max_keep == 0: all of them);
+ *   - otherwise let fresh = |S_i \ C| and accept i when fresh >= min_new and (uint64)fresh * new_den >= (uint64)new_num * |S_i|; on
+ *     acceptance C becomes C u S_i; a hypothesis that is not accepted is PR_COVER_REJECTED with reason PR_COVER_REASON_THRESHOLD.
+ * C only grows, so fresh only shrinks: a hypothesis that fails against some C fails against every later one (the device walks in rounds
+ * on the strength of this, and the bytes it returns do not depend on how).  With new_num == 0 and min_new == 1 a hypothesis is kept
+ * exactly when it explains at least one new pixel.
+ * Outputs: selected_out (room for n_order indices) = the accepted indices in acceptance order, *n_selected their number; one pr_pose_cover
+ * per hypothesis of the batch, in the caller's pose order; one pr_cover_frame.  pr_pose_cover.fresh is the value at its acceptance for an
+ * accepted hypothesis, 0 for an EMPTY one, and for every other one -- rejected for either reason, or not in order at all --
+ * |S_i \ C_final|, counted after the walk against the final claimed set: how much of a dropped hypothesis the detections leave unexplained.
+ * pr_score_cover renders and scores the batch exactly as pr_score_poses does -- scores_host is byte for byte the same -- and walks on
+ * the device.  Argument checks, ROI, scene types, chunking and the synchronous behaviour are those of pr_score_poses
+ * (pr_score_poses_multi for pr_score_cover_multi; hypotheses of different meshes claim pixels like any others).  PR_ERR_INVALID, with nothing
+ * written, for new_den == 0, new_num > new_den, an index >= n_poses or one that appears twice in order, and a null order (with n_order >
+ * 0), scores_host, cover_host, frame_host, selected_out or n_selected with n_poses > 0.  n_poses == 0 returns PR_OK, writes *n_selected
+ * = 0 (when given) and nothing else; n_order == 0 is a walk that accepts nothing (every record NOT_IN_ORDER, fresh = support).
+ * PR_OVERLAP_MAX_POSES does not apply: the device keeps one bit per frame pixel and hypothesis while the call runs (n_poses x height x
+ * ceil(width / 64) x 8 bytes), one more such plane for C, and 24 bytes per hypothesis; a failed allocation is PR_ERR_NOMEM. */
+#define PR_COVER_NOT_IN_ORDER      0u        /* pr_pose_cover.state & PR_COVER_STATE_MASK                                            */
+#define PR_COVER_EMPTY             1u
+#define PR_COVER_ACCEPTED          2u
+#define PR_COVER_REJECTED          3u
+#define PR_COVER_STATE_MASK        0xFFu
+#define PR_COVER_REASON_THRESHOLD  0x100u    /* with PR_COVER_REJECTED: failed min_new or new_num / new_den                          */
+#define PR_COVER_REASON_CAP        0x200u    /* with PR_COVER_REJECTED: max_keep hypotheses were accepted before the walk reached it */
+#define PR_COVER_NO_POSITION       0xFFFFFFFFu
+typedef struct {
+    uint32_t support;          /* |S_i|, equal to scores_host[i].inlier                                                       */
+    uint32_t fresh;            /* see above                                                                                   */
+    uint32_t state;            /* PR_COVER_NOT_IN_ORDER, _EMPTY, _ACCEPTED, or _REJECTED | one PR_COVER_REASON_*              */
+    uint32_t position;         /* the acceptance rank (index into selected_out), PR_COVER_NO_POSITION when not accepted       */
+} pr_pose_cover;               /* 16 B */
+typedef struct {
+    uint32_t claimed;          /* |C_final|: the sum of fresh over the accepted hypotheses                                    */
+    uint32_t n_selected;
+    uint32_t reserved[2];      /* written as 0                                                                                */
+} pr_cover_frame;              /* 16 B */
+int  pr_score_cover(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses,
+                    uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi,
+                    const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm,
+                    const uint32_t *order, uint32_t n_order, uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep,
+                    pr_pose_score *scores_host, pr_pose_cover *cover_host, pr_cover_frame *frame_host,
+                    uint32_t *selected_out, uint32_t *n_selected);
+int  pr_score_cover_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                          uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                          int depth_is_i32, int32_t tau_mm,
+                          const uint32_t *order, uint32_t n_order, uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep,
+                          pr_pose_score *scores_host, pr_pose_cover *cover_host, pr_cover_frame *frame_host,
+                          uint32_t *selected_out, uint32_t *n_selected);
+/* The same rule, host only (needs no device), on supports the caller brings as bit planes: planes[i * plane_words + w] is word w of
+ * hypothesis i's plane, one bit per pixel in any layout the caller likes (the same for every hypothesis); |S_i| is its population count.
+ * The small integer twin of the device walk, as pr_select_greedy is for the matrix.  Checks as above; also PR_ERR_INVALID for planes NULL
+ * with n_poses > 0 and plane_words > 0, and for plane_words > 2^26 (a support must fit 32 bits). */
+int  pr_select_cover_host(const uint64_t *planes, uint32_t n_poses, size_t plane_words, const uint32_t *order, uint32_t n_order,
+                          uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep,
+                          pr_pose_cover *cover_out, pr_cover_frame *frame_out, uint32_t *selected_out, uint32_t *n_selected);
+
 /* ---- contour check: do the depth edges of a hypothesis' render lie on depth edges of the scene? ------------------------------------------
  * pr_score_poses and the overlap matrix look at the interior of a render; a pose whose surface lies on scene surface (a face against a
  * wall, an object slid along the table) passes both although its silhouette is nowhere in the image.  All arithmetic is in integers

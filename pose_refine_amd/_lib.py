@@ -39,6 +39,11 @@ VISIBLE = np.dtype([("owned", "<u4"), ("owned_inlier", "<u4"), ("owned_occluded"
 FRAME = np.dtype([("window", "<u4"), ("measured", "<u4"), ("covered", "<u4"), ("explained", "<u4"), ("in_front", "<u4"), ("behind", "<u4"),
                   ("unmeasured", "<u4"), ("reserved", "<u4")])
 COMPOSE_NONE, COMPOSE_MAX_POSES = 0xFFFF, 65535      # PR_COMPOSE_NONE, PR_COMPOSE_MAX_POSES
+# pr_pose_cover / pr_cover_frame: what a hypothesis adds to the pixels the better ones claim, and what the detections claim together (pr_score_cover)
+COVER = np.dtype([("support", "<u4"), ("fresh", "<u4"), ("state", "<u4"), ("position", "<u4")])
+COVER_FRAME = np.dtype([("claimed", "<u4"), ("n_selected", "<u4"), ("reserved", "<u4", (2,))])
+COVER_NOT_IN_ORDER, COVER_EMPTY, COVER_ACCEPTED, COVER_REJECTED, COVER_STATE_MASK = 0, 1, 2, 3, 0xFF      # PR_COVER_*
+COVER_REASON_THRESHOLD, COVER_REASON_CAP, COVER_NO_POSITION = 0x100, 0x200, 0xFFFFFFFF
 # pr_pose_dist: the displacement of the model's points between two poses, minimised over the symmetry candidates (pr_pose_distance)
 POSE_DIST = np.dtype([("disp_sum_q16", "<u8"), ("max_disp_sq", "<f4"), ("max_proj_sq", "<f4"), ("sym_sum", "<u2"), ("sym_disp", "<u2"),
                       ("sym_proj", "<u2"), ("reserved", "<u2"), ("n_points", "<u4"), ("reserved2", "<u4")])
@@ -48,6 +53,7 @@ VSD_MAX_TAUS = 12                        # PR_VSD_MAX_TAUS
 VSD = np.dtype([("visib_gt", "<u4"), ("visib_est", "<u4"), ("inter", "<u4"), ("uni", "<u4"), ("far", "<u4", (VSD_MAX_TAUS,))])
 POSE_DIST_CHUNK = 256                    # PR_POSE_DIST_CHUNK (pr_tuning.h; the library reports its own as option "pose_dist_chunk")
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
+assert COVER.itemsize == 16 and COVER_FRAME.itemsize == 16
 assert NORMAL.itemsize == 32 and VISIBLE.itemsize == 32 and FRAME.itemsize == 32 and POSE_DIST.itemsize == 32 and VSD.itemsize == 64
 
 
@@ -154,6 +160,9 @@ SIGNATURES = {
     "pr_score_overlap": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),
     "pr_score_overlap_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp]),
     "pr_select_greedy": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, _vp, C.POINTER(_u32)]),
+    "pr_score_cover": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "pr_score_cover_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "pr_select_cover_host": (_i32, [_vp, _u32, _sz, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
     "pr_scene_edge_distance_dev": (_i32, [_vp, _i32, _u32, _u32, C.c_int32, _u32, _vp]),
     "pr_score_contours": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "pr_score_contours_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),

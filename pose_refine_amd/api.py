@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -917,6 +917,87 @@ def select_hypotheses(scores, overlap, max_shared: Sequence[int] = (1, 4), min_f
     frac = np.where(den <= 0, 0.0, sc["inlier"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
     order = order[frac[order] >= float(min_fraction)]
     return select_greedy(order, overlap, int(max_shared[0]), int(max_shared[1]))
+
+
+# ------------------------------------------------------------------------------------------------
+# detections by cumulative cover: keep a hypothesis for the inlier pixels it adds to what the better ones already claim
+# ------------------------------------------------------------------------------------------------
+def _cover_rule(order, n_poses: int, min_new_fraction, min_new: int, max_keep):
+    od = np.asarray(order)
+    if od.ndim != 1 or (len(od) and (od.dtype.kind not in "iu" or od.min() < 0 or od.max() > 0xffffffff)):
+        raise ValueError("order must be a 1-d array of non-negative integers")
+    num, den = int(min_new_fraction[0]), int(min_new_fraction[1])
+    keep = 0xffffffff if max_keep is None else int(max_keep)
+    if not all(0 <= v <= 0xffffffff for v in (num, den, int(min_new), keep)):
+        raise ValueError("min_new_fraction, min_new and max_keep must fit 32 unsigned bits")
+    return np.ascontiguousarray(od, np.uint32), (num, den, int(min_new), keep)
+
+
+def _score_cover(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, order, min_new_fraction, min_new: int, max_keep, roi):
+    call, n = _score_call("pr_score_cover", mesh, width, height, proj, scene_depth, tau_mm, roi)
+    od, rule = _cover_rule(order, n, min_new_fraction, min_new, max_keep)
+    out, cov, frame = np.zeros(n, SCORE), np.zeros(n, COVER), np.zeros(1, COVER_FRAME)
+    sel = np.zeros(max(1, len(od)), np.uint32)
+    ns = C.c_uint32(0)
+    call(ptr(od), len(od), *rule, ptr(out), ptr(cov), ptr(frame), ptr(sel), C.byref(ns))
+    return out, cov, frame[0], sel[:ns.value].astype(np.int64)
+
+
+def score_cover(tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, order, min_new_fraction: Sequence[int] = (1, 2),
+                min_new: int = 1, max_keep: Optional[int] = None, roi: Sequence[int] = (0, 0, 0, 0)):
+    """``pr_score_cover``: ``score_poses`` plus the cover walk on the device.  ``order`` (indices, best first) is walked with a claimed
+    pixel set; a hypothesis with support is accepted while fewer than ``max_keep`` are, when the part of its support that is not claimed
+    yet, ``fresh``, is at least ``min_new`` pixels and at least ``min_new_fraction = (num, den)`` of the support; its support is then
+    claimed.  Returns (SCORE[P], COVER[P], one COVER_FRAME record, selected indices in acceptance order)."""
+    return _score_cover(_one_mesh(tris, poses), width, height, proj, scene_depth, tau_mm, order, min_new_fraction, min_new, max_keep, roi)
+
+
+def score_cover_multi(meshes, mesh_index, poses, width: int, height: int, proj, scene_depth, tau_mm: int, order,
+                      min_new_fraction: Sequence[int] = (1, 2), min_new: int = 1, max_keep: Optional[int] = None, roi: Sequence[int] = (0, 0, 0, 0)):
+    """``pr_score_cover_multi``: ``score_cover`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; hypotheses of different meshes
+    claim pixels like any others.  Everything in pose order."""
+    return _score_cover(_mesh_batch(meshes, mesh_index, poses), width, height, proj, scene_depth, tau_mm, order, min_new_fraction, min_new, max_keep, roi)
+
+
+def _cover_planes(supports) -> np.ndarray:
+    """uint64[P, words]: one bit per pixel.  ``supports``: a boolean array whose first axis is the hypothesis, or a sequence of boolean masks of one shape."""
+    m = np.asarray(supports)
+    if m.dtype != np.bool_ or m.ndim < 1:
+        raise ValueError("supports must be boolean masks, one per hypothesis")
+    m = m.reshape(len(m), int(np.prod(m.shape[1:])))
+    pad = -m.shape[1] % 64
+    bits = np.packbits(np.pad(m, ((0, 0), (0, pad))), axis=1, bitorder="little")
+    return np.ascontiguousarray(bits).view(np.uint64).reshape(len(m), (m.shape[1] + pad) // 64)
+
+
+def select_cover_host(supports, order, min_new_fraction: Sequence[int] = (1, 2), min_new: int = 1, max_keep: Optional[int] = None):
+    """``pr_select_cover_host`` (host only): the cover rule of ``score_cover`` on supports the caller brings -- boolean masks, one per
+    hypothesis (packed to bit planes here), or uint64[P, words] planes.  Returns (COVER[P], one COVER_FRAME record, selected indices)."""
+    planes = np.ascontiguousarray(supports) if getattr(supports, "dtype", None) == np.uint64 and np.ndim(supports) == 2 else _cover_planes(supports)
+    n = len(planes)
+    od, rule = _cover_rule(order, n, min_new_fraction, min_new, max_keep)
+    cov, frame = np.zeros(n, COVER), np.zeros(1, COVER_FRAME)
+    sel = np.zeros(max(1, len(od)), np.uint32)
+    ns = C.c_uint32(0)
+    check(_lib.load().pr_select_cover_host(ptr(planes), n, planes.shape[1] if n else 0, ptr(od), len(od), *rule, ptr(cov), ptr(frame), ptr(sel), C.byref(ns)))
+    return cov, frame[0], sel[:ns.value].astype(np.int64)
+
+
+def select_cover(scores, tris, poses, width: int, height: int, proj, scene_depth, tau_mm: int, min_new_fraction: Sequence[int] = (1, 2),
+                 min_new: int = 1, min_fraction: float = 0.0, order=None, max_keep: Optional[int] = None, roi: Sequence[int] = (0, 0, 0, 0),
+                 mesh_index=None):
+    """Detections from a scored batch by the cover rule, on the device: ``order`` defaults to ``rank_hypotheses(scores)`` and hypotheses
+    whose rank fraction ``inlier / (visible - occluded)`` is below ``min_fraction`` leave it first, exactly as in ``select_hypotheses``;
+    the rest are walked by ``score_cover`` (``score_cover_multi`` with ``tris`` a list of meshes when ``mesh_index`` is given).
+    ``scores`` are the batch's records from any earlier scoring call.  Returns (selected indices best first, COVER[P], COVER_FRAME record)."""
+    sc = np.asarray(scores)
+    order = rank_hypotheses(sc) if order is None else np.asarray(order, np.int64)
+    den = sc["visible"].astype(np.int64) - sc["occluded"].astype(np.int64)
+    frac = np.where(den <= 0, 0.0, sc["inlier"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
+    order = order[frac[order] >= float(min_fraction)]
+    mesh = _one_mesh(tris, poses) if mesh_index is None else _mesh_batch(tris, mesh_index, poses)
+    _, cov, frame, sel = _score_cover(mesh, width, height, proj, scene_depth, tau_mm, order, min_new_fraction, min_new, max_keep, roi)
+    return sel, cov, frame
 
 
 # ------------------------------------------------------------------------------------------------

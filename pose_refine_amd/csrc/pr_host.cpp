@@ -846,6 +846,46 @@ int pr_select_greedy(const uint32_t *order, uint32_t n_order, const uint32_t *ov
     return PR_OK;
 }
 
+// the cover rule (include/pose_refine.h) on bit planes the caller brings: the sequential walk as it is defined, integers only -- what the
+// device's rounds (cover.hip) must reproduce byte for byte
+int pr_select_cover_host(const uint64_t *planes, uint32_t n_poses, size_t plane_words, const uint32_t *order, uint32_t n_order, uint32_t new_num,
+                         uint32_t new_den, uint32_t min_new, uint32_t max_keep, pr_pose_cover *cover_out, pr_cover_frame *frame_out, uint32_t *selected_out,
+                         uint32_t *n_selected)
+{
+    const char *fn = "pr_select_cover_host";
+    if (int rc = prh::cover_rule_ok(fn, order, n_poses ? n_order : 0, n_poses, new_num, new_den)) return rc;
+    if (plane_words > ((size_t)1 << 26)) { prh::set_error("%s: plane_words must not exceed 2^26 (a support must fit 32 bits)", fn); return PR_ERR_INVALID; }
+    if (n_poses == 0) { if (n_selected) *n_selected = 0; return PR_OK; }
+    if ((!planes && plane_words) || !cover_out || !frame_out || !selected_out || !n_selected) { prh::set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    std::vector<uint64_t> claimed(plane_words, 0);
+    const auto fresh_of = [&](uint32_t i) {
+        const uint64_t *s = planes + (size_t)i * plane_words;
+        uint64_t n = 0;
+        for (size_t w = 0; w < plane_words; ++w) n += (uint64_t)__builtin_popcountll(s[w] & ~claimed[w]);
+        return (uint32_t)n;
+    };
+    for (uint32_t i = 0; i < n_poses; ++i) cover_out[i] = pr_pose_cover{ fresh_of(i), 0, PR_COVER_NOT_IN_ORDER, PR_COVER_NO_POSITION };      // (nothing claimed yet: the support)
+    uint32_t n = 0, total = 0;
+    for (uint32_t k = 0; k < n_order; ++k) {
+        const uint32_t i = order[k];
+        pr_pose_cover &c = cover_out[i];
+        if (c.support == 0) { c.state = PR_COVER_EMPTY; continue; }
+        if (n >= max_keep) { c.state = PR_COVER_REJECTED | PR_COVER_REASON_CAP; continue; }
+        const uint32_t fresh = fresh_of(i);
+        if (fresh >= min_new && (uint64_t)fresh * new_den >= (uint64_t)new_num * c.support) {
+            const uint64_t *s = planes + (size_t)i * plane_words;
+            for (size_t w = 0; w < plane_words; ++w) claimed[w] |= s[w];
+            c.fresh = fresh; c.state = PR_COVER_ACCEPTED; c.position = n;
+            selected_out[n++] = i; total += fresh;
+        } else c.state = PR_COVER_REJECTED | PR_COVER_REASON_THRESHOLD;
+    }
+    for (uint32_t i = 0; i < n_poses; ++i)                         // what the detections leave unexplained of everything else
+        if (cover_out[i].state != PR_COVER_ACCEPTED && cover_out[i].state != PR_COVER_EMPTY) cover_out[i].fresh = fresh_of(i);
+    *frame_out = pr_cover_frame{ total, n, { 0, 0 } };
+    *n_selected = n;
+    return PR_OK;
+}
+
 // greedy merging of duplicates over a ranking, in pose space: pr_select_greedy's walk with a distance test (either direction: with symmetries
 // the matrix is only approximately symmetric) instead of the shared-pixel test
 int pr_cluster_greedy(const uint32_t *order, uint32_t n_order, const pr_pose_dist *dist, uint32_t n_poses, float max_disp_mm, uint32_t *kept_out,

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
+#include <vector>
 
 #include "pose_refine.h"
 #include "pr_tuning.h"
@@ -206,6 +207,24 @@ inline uint32_t overlap_words_per_row(uint32_t width) { return (width + 63) / 64
 hipError_t launch_support_bits(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
                                const void *scene, bool scene_i32, int32_t tau, unsigned long long *planes, hipStream_t s);
 hipError_t launch_pair_overlap(const unsigned long long *planes, const int4 *bbox, uint32_t n_poses, uint32_t width, uint32_t height, uint32_t *mat, hipStream_t s);
+// cover.hip: the cover rule (pr_score_cover) walked in rounds over launch_support_bits' planes and the boxes they were written with, all n of them.
+// state: kCoverCtlWords control words (finished, n_selected, claimed, position of the last accepted one), then n pr_pose_cover records, then the
+// order position of every hypothesis (kCoverNoPos: not in order), then the hypothesis at every order position, then the selected list (n_order
+// words).  launch_cover_init: once per depth chunk behind the score kernel (records: its pr_pose_score words) -- support, state and position of
+// hypotheses p0 .. p0 + np - 1, and (p0 == 0) the control words.  launch_cover_round: one gain + commit pair, a no-op once the finished word is set.
+// launch_cover_final: fresh of everything not accepted against the final claimed plane.  claimed: height x overlap_words_per_row(width) words, zeroed by the caller
+constexpr uint32_t kCoverCtlWords = 8, kCoverNoPos = 0xffffffffu;
+struct CoverRule { uint32_t new_num, new_den, min_new, max_keep, n_order; };
+struct CoverState {
+    uint32_t *ctl, *rec, *pos, *at, *selected;
+    static size_t words(size_t n, size_t n_order) { return kCoverCtlWords + 4 * n + n + n_order + n_order; }
+    CoverState(uint32_t *base, size_t n, size_t n_order) : ctl(base), rec(base + kCoverCtlWords), pos(rec + 4 * n), at(pos + n), selected(at + n_order) {}
+};
+hipError_t launch_cover_init(const uint32_t *records, uint32_t p0, uint32_t np, const CoverState &st, hipStream_t s);
+hipError_t launch_cover_round(const unsigned long long *planes, const int4 *bbox, uint32_t n_poses, uint32_t width, uint32_t height, const CoverRule &rule,
+                              const CoverState &st, unsigned long long *claimed, hipStream_t s);
+hipError_t launch_cover_final(const unsigned long long *planes, const int4 *bbox, uint32_t n_poses, uint32_t width, uint32_t height, const CoverState &st,
+                              const unsigned long long *claimed, hipStream_t s);
 // contour.hip: the scene's edge pixels (bits: height x overlap_words_per_row(width) words) and their chessboard distance transform (row_dist:
 // scratch, dist: the result, width x height bytes each, 255 = no edge within radius) -- three launches; and the edge pixels of every rendered box
 // counted against them into records[8 * i] (pr_pose_contour words: contour, hit, occluded, miss, reserved x 2, dist_sum lo / hi), which the
@@ -353,4 +372,19 @@ void mat4_mul(const float A[16], const float B[16], float C[16]);
 void mesh_order(const pr_triangle *tris, size_t n_tris, uint32_t *perm);
 // multiset fingerprint of a triangle buffer: wrapping sum of triangle_hash (pose_box.h)
 unsigned long long mesh_fingerprint(const pr_triangle *tris, size_t n_tris);
+// the cover rule's own conditions (pr_score_cover, pr_select_cover_host): the fraction, and order a list of distinct indices < n_poses.  PR_ERR_INVALID with a message
+void set_error(const char *fmt, ...);   // pr_context.cpp
+inline int cover_rule_ok(const char *fn, const uint32_t *order, uint32_t n_order, uint32_t n_poses, uint32_t new_num, uint32_t new_den)
+{
+    if (new_den == 0) { set_error("%s: new_den must not be 0", fn); return PR_ERR_INVALID; }
+    if (new_num > new_den) { set_error("%s: new_num / new_den must not exceed 1 (got %u / %u)", fn, new_num, new_den); return PR_ERR_INVALID; }
+    if (n_order && !order) { set_error("%s: bad arguments (order is null)", fn); return PR_ERR_INVALID; }
+    std::vector<unsigned char> seen(n_poses, 0);
+    for (uint32_t k = 0; k < n_order; ++k) {
+        if (order[k] >= n_poses) { set_error("%s: order[%u] = %u, but there are %u hypotheses", fn, k, order[k], n_poses); return PR_ERR_INVALID; }
+        if (seen[order[k]]) { set_error("%s: order[%u] = %u appears twice", fn, k, order[k]); return PR_ERR_INVALID; }
+        seen[order[k]] = 1;
+    }
+    return PR_OK;
+}
 }

@@ -356,11 +356,17 @@ struct ReadBack {
 // caller's index, null: the identity), so ties and labels need no remapping -- and every chunk leaves its pixel boxes in a workspace sized for
 // all P, as for the overlap matrix.  Behind the last chunk: the counts of what every hypothesis keeps, then one pass over the frame for the labels,
 // the front depth and the frame record.  visible is written in the caller's order whatever `order` is.
+// kScoreCover: the support bits and boxes as for the matrix, and behind every chunk's score kernel the walk's per-hypothesis state from its records
+// (cover.hip).  Behind the last chunk the walk: rounds of gain + commit, kCoverRoundsPerSync of them enqueued at a time, then the finished word read
+// back -- a round after the end is two launches that return at once, so how many are enqueued changes no byte -- at most min(max_keep, n_order) + 1
+// in all; one more gain pass against the final claimed plane; the whole state back through pinned memory.  cov_order, the records and the selected
+// list are in the order of req.poses (score_run maps a mixed batch).
+constexpr uint32_t kCoverRoundsPerSync = 4;
 int score_core(const ScoreRequest &req)
 {
     const uint32_t P = req.P, W = req.W, H = req.H;
     const int32_t tau = req.tau;
-    const bool contours = req.kind == kScoreContours, normals = req.kind == kScoreNormals, compose = req.kind == kScoreCompose;
+    const bool contours = req.kind == kScoreContours, normals = req.kind == kScoreNormals, compose = req.kind == kScoreCompose, cover = req.kind == kScoreCover;
     const MeshSource src{ req.tris, req.n_tris, req.plan };
     static_assert(sizeof(pr_pose_visible) == sizeof(pr_pose_score) && sizeof(pr_frame_explained) == sizeof(pr_pose_score), "pr_pose_visible, pr_frame_explained: 32-byte records");
     static_assert(sizeof(pr_pose_contour) == sizeof(pr_pose_score) && offsetof(pr_pose_contour, dist_sum) == 24, "pr_pose_contour: one 32-byte record, the sum in words 6 and 7");
@@ -375,9 +381,27 @@ int score_core(const ScoreRequest &req)
     const uint32_t chunk = depth_chunk(img, P);
     PR_TRY(model_boxes(src, chunk));
     const size_t plane_words = (size_t)H * prk::overlap_words_per_row(W);
-    if (req.overlap) {
+    if (req.overlap || cover) {
         PR_TRY(g->ov_bits.ensure(sizeof(uint64_t) * plane_words * P));
         PR_TRY(g->ov_box.ensure(sizeof(int4) * P));
+    }
+    const prk::CoverRule &rule = req.cov_rule;
+    const size_t cov_words = prk::CoverState::words(P, rule.n_order);
+    if (cover) {
+        static_assert(sizeof(pr_pose_cover) == 16 && sizeof(pr_cover_frame) == 16, "pr_pose_cover, pr_cover_frame: 16-byte records");
+        if (cov_words > 0xffffffffull) { set_error("%s: too many hypotheses for one call", req.fn); return PR_ERR_INVALID; }
+        PR_TRY(g->cov_state.ensure(sizeof(uint32_t) * cov_words));
+        PR_TRY(g->cov_claimed.ensure(sizeof(uint64_t) * plane_words));
+        PR_TRY(g->h_cov.ensure(sizeof(uint32_t) * cov_words));
+    }
+    const prk::CoverState cov(g->cov_state.as<uint32_t>(), P, rule.n_order), h_covs(g->h_cov.as<uint32_t>(), P, rule.n_order);
+    if (cover) {                                                     // order position of every hypothesis and its inverse, staged behind whatever the stream holds
+        std::fill(h_covs.pos, h_covs.pos + P, prk::kCoverNoPos);
+        for (uint32_t k = 0; k < rule.n_order; ++k) { h_covs.pos[req.cov_order[k]] = k; h_covs.at[k] = req.cov_order[k]; }
+        HIP_TRY(prk::launch_copy_words32(g->h_cov.dev_as<uint32_t>() + (h_covs.pos - h_covs.ctl), cov.pos, P + rule.n_order, g->stream));
+        HIP_TRY(prk::launch_fill_i32(g->cov_claimed.as<int32_t>(), 2 * plane_words, 0, g->stream));
+    }
+    if (req.overlap) {
         PR_TRY(g->ov_mat.ensure(sizeof(uint32_t) * (size_t)P * P));
         PR_TRY(g->h_ov.ensure(sizeof(uint32_t) * (size_t)P * P));
     }
@@ -428,11 +452,12 @@ int score_core(const ScoreRequest &req)
                                              g->normals.as<uint32_t>(), g->stream));
             PR_TRY(normals_back.queue(g->normals.p, g->h_normals, kWords * np));
         }
-        if (req.overlap) {
+        if (req.overlap || cover) {
             HIP_TRY(prk::launch_support_bits(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, req.scene, req.scene_i32, tau,
                                              g->ov_bits.as<unsigned long long>() + plane_words * p0, g->stream));
             HIP_TRY(prk::launch_copy_words32(g->bbox.p, g->ov_box.as<int4>() + p0, 4 * np, g->stream));
         }
+        if (cover) HIP_TRY(prk::launch_cover_init(g->scores.as<uint32_t>(), p0, np, cov, g->stream));
         if (compose) {
             HIP_TRY(prk::launch_compose_tiles(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, cmp_index ? cmp_index + p0 : nullptr, p0,
                                               g->cmp_keys.as<unsigned long long>(), p0 == 0, g->stream));
@@ -450,6 +475,28 @@ int score_core(const ScoreRequest &req)
         PR_TRY(back.queue(g->ov_mat.p, g->h_ov, P * P));
         HIP_TRY(hipStreamSynchronize(g->stream));
         back.deliver(req.overlap, sizeof(uint32_t) * (size_t)P * P);
+    }
+    if (cover) {
+        const unsigned long long *planes = g->ov_bits.as<unsigned long long>();
+        const uint32_t max_rounds = rule.n_order ? std::min(rule.max_keep, rule.n_order) + 1 : 0;
+        for (uint32_t done = 0; done < max_rounds;) {
+            const uint32_t n = std::min(kCoverRoundsPerSync, max_rounds - done);
+            for (uint32_t k = 0; k < n; ++k)
+                HIP_TRY(prk::launch_cover_round(planes, g->ov_box.as<int4>(), P, W, H, rule, cov, g->cov_claimed.as<unsigned long long>(), g->stream));
+            done += n;
+            uint32_t finished = 1;
+            if (done < max_rounds) PR_TRY(read_back_words(cov.ctl, &finished, 1, g->stream));
+            if (finished) break;
+        }
+        ReadBack back;
+        HIP_TRY(prk::launch_cover_final(planes, g->ov_box.as<int4>(), P, W, H, cov, g->cov_claimed.as<unsigned long long>(), g->stream));
+        PR_TRY(back.queue(cov.ctl, g->h_cov, (uint32_t)cov_words));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        const uint32_t n_sel = h_covs.ctl[1];
+        std::memcpy(req.cover, h_covs.rec, sizeof(pr_pose_cover) * P);
+        *req.cover_frame = pr_cover_frame{ h_covs.ctl[2], n_sel, { 0, 0 } };
+        std::memcpy(req.selected, h_covs.selected, sizeof(uint32_t) * n_sel);
+        *req.n_selected = n_sel;
     }
     if (compose) {
         ReadBack back;
@@ -506,7 +553,7 @@ int score_run(const ScoreRequest &req)
 {
     PR_TRY(score_request_ok(req));
     const uint32_t P = req.P;
-    if (P == 0) return PR_OK;
+    if (P == 0) { if (req.kind == kScoreCover && req.n_selected) *req.n_selected = 0; return PR_OK; }
     if (!req.multi) return score_core(req);
     MeshPlan pl;
     PR_TRY(plan_meshes(req.fn, req.meshes, req.n_meshes, req.mesh_index, P, pl));
@@ -518,7 +565,23 @@ int score_run(const ScoreRequest &req)
     ScoreRequest grouped = req;
     grouped.plan = &pl; grouped.order = pl.order.data(); grouped.poses = poses.data();
     grouped.scores = sc.data(); grouped.overlap = req.overlap ? ov.data() : nullptr; grouped.contours = cc.data(); grouped.normals = nn.data();
+    // the cover walk runs on grouped positions: the order goes in through the inverse of pl.order, records and selected list come back through pl.order
+    const bool cover = req.kind == kScoreCover;
+    std::vector<uint32_t> where(cover ? P : 0), walk(cover ? req.cov_rule.n_order : 0), chosen(walk.size());
+    std::vector<pr_pose_cover> cv(cover ? P : 0);
+    pr_cover_frame cf{};
+    uint32_t n_chosen = 0;
+    if (cover) {
+        for (uint32_t j = 0; j < P; ++j) where[pl.order[j]] = j;
+        for (size_t k = 0; k < walk.size(); ++k) walk[k] = where[req.cov_order[k]];
+        grouped.cov_order = walk.data(); grouped.cover = cv.data(); grouped.cover_frame = &cf; grouped.selected = chosen.data(); grouped.n_selected = &n_chosen;
+    }
     PR_TRY(score_core(grouped));
+    if (cover) {
+        for (uint32_t j = 0; j < P; ++j) req.cover[pl.order[j]] = cv[j];
+        for (uint32_t k = 0; k < n_chosen; ++k) req.selected[k] = pl.order[chosen[k]];
+        *req.cover_frame = cf; *req.n_selected = n_chosen;
+    }
     for (uint32_t j = 0; j < P; ++j) req.scores[pl.order[j]] = sc[j];
     for (uint32_t j = 0; j < cc.size(); ++j) req.contours[pl.order[j]] = cc[j];
     for (uint32_t j = 0; j < nn.size(); ++j) req.normals[pl.order[j]] = nn[j];
@@ -1344,6 +1407,32 @@ int pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const u
     ScoreRequest r = score_request("pr_score_overlap_multi", kScoreOverlap, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
     r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
     r.overlap = overlap_host;
+    return score_run(r);
+}
+
+int pr_score_cover(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                   const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, const uint32_t *order, uint32_t n_order,
+                   uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep, pr_pose_score *scores_host, pr_pose_cover *cover_host,
+                   pr_cover_frame *frame_host, uint32_t *selected_out, uint32_t *n_selected)
+{
+    PR_ENTER();
+    ScoreRequest r = score_request("pr_score_cover", kScoreCover, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.tris = tris_dev; r.n_tris = n_tris;
+    r.cov_order = order; r.cov_rule = prk::CoverRule{ new_num, new_den, min_new, max_keep, n_order };
+    r.cover = cover_host; r.cover_frame = frame_host; r.selected = selected_out; r.n_selected = n_selected;
+    return score_run(r);
+}
+
+int pr_score_cover_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
+                         uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm,
+                         const uint32_t *order, uint32_t n_order, uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep,
+                         pr_pose_score *scores_host, pr_pose_cover *cover_host, pr_cover_frame *frame_host, uint32_t *selected_out, uint32_t *n_selected)
+{
+    PR_ENTER();
+    ScoreRequest r = score_request("pr_score_cover_multi", kScoreCover, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
+    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
+    r.cov_order = order; r.cov_rule = prk::CoverRule{ new_num, new_den, min_new, max_keep, n_order };
+    r.cover = cover_host; r.cover_frame = frame_host; r.selected = selected_out; r.n_selected = n_selected;
     return score_run(r);
 }
 

@@ -221,9 +221,9 @@ inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, 
     else job.sp.view = *static_cast<const pr_scene_proj *>(scene);     // (a plain projective scene: a crop at 0, 0)
     return PR_OK;
 }
-// ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_contours, pr_score_normals, pr_compose_detections and their _multi forms) ----
+// ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_cover, pr_score_contours, pr_score_normals, pr_compose_detections and their _multi forms) ----
 // What the caller asked for, as the entry point got it; score_run (pr_refine.cpp) takes it from there.  Every member is set by the entry point.
-enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose };
+enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose, kScoreCover };
 struct ScoreRequest {
     const char *fn; ScoreKind kind;                              // the entry point's name (for messages) and what it returns besides the scores
     const pr_triangle *tris; size_t n_tris;                      // one mesh for every hypothesis ...
@@ -235,6 +235,7 @@ struct ScoreRequest {
     int32_t jump; const uint8_t *edge_dist; pr_pose_contour *contours;                          // kScoreContours: device distance image in, P host records out
     const float *K; uint32_t step; float cos_min; pr_pose_normal *normals;                      // kScoreNormals (with jump): intrinsics and the estimator's step in, P host records out
     uint16_t *labels_dev; int32_t *depth_dev; pr_pose_visible *visible; pr_frame_explained *frame;     // kScoreCompose: two optional device images, host records
+    const uint32_t *cov_order; prk::CoverRule cov_rule; pr_pose_cover *cover; pr_cover_frame *cover_frame; uint32_t *selected, *n_selected;      // kScoreCover: the walk in (cov_rule.n_order indices), P + 1 host records and the selected list out
     const MeshPlan *plan; const uint32_t *order;                 // score_run's, null from the entry point: the grouped batch (position -> caller's index)
 };
 // pr_score_overlap's own condition
@@ -245,6 +246,15 @@ inline int overlap_args_ok(const char *fn, uint32_t P, const uint32_t *overlap_h
         return PR_ERR_INVALID;
     }
     if (P && !overlap_host) { set_error("%s: bad arguments (overlap_host is null)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+// pr_score_cover's own conditions
+inline int cover_args_ok(const ScoreRequest &r)
+{
+    PR_TRY(prh::cover_rule_ok(r.fn, r.cov_order, r.P ? r.cov_rule.n_order : 0, r.P, r.cov_rule.new_num, r.cov_rule.new_den));      // (no hypotheses: no walk)
+    if (r.P && (!r.cover || !r.cover_frame || !r.selected || !r.n_selected)) {
+        set_error("%s: bad arguments (cover_host, frame_host, selected_out or n_selected is null)", r.fn); return PR_ERR_INVALID;
+    }
     return PR_OK;
 }
 // pr_compose_detections' own condition (its entry points ask before any device use as well)
@@ -264,13 +274,14 @@ inline int normal_params_ok(const char *fn, uint32_t step, int32_t jump, float c
     if (!(cos_min >= 0.0f && cos_min <= 1.0f)) { set_error("%s: cos_min must lie in [0, 1] (got %g)", fn, (double)cos_min); return PR_ERR_INVALID; }      // (a NaN fails both)
     return PR_OK;
 }
-// Every check of a request that needs no device, in one order for all ten entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
+// Every check of a request that needs no device, in one order for all twelve entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
 // call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.  A request without hypotheses needs no arrays.
 inline int score_request_ok(const ScoreRequest &r)
 {
     const char *fn = r.fn;
     if (r.kind == kScoreOverlap || ((r.kind == kScoreContours || r.kind == kScoreNormals) && r.overlap)) PR_TRY(overlap_args_ok(fn, r.P, r.overlap));
     if (r.kind == kScoreCompose) PR_TRY(compose_args_ok(fn, r.P));
+    if (r.kind == kScoreCover) PR_TRY(cover_args_ok(r));
     if (r.tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)r.tau); return PR_ERR_INVALID; }
     if (!r.proj || r.W == 0 || r.H == 0 || (r.P && (!r.poses || !r.scene || !r.scores || (!r.multi && !r.tris && r.n_tris > 0)))) {
         set_error("%s: bad arguments", fn); return PR_ERR_INVALID;
@@ -459,6 +470,8 @@ struct Ctx {
     DevBuf scores;                   // pr_score_poses: the records of a chunk
     DevBuf ov_bits, ov_box, ov_mat;  // pr_score_overlap: the support bit planes and pixel boxes of ALL hypotheses of a call (they outlive its depth chunks), the P x P matrix
     PinBuf h_ov;                     // the matrix on its way to the caller
+    DevBuf cov_state, cov_claimed;   // pr_score_cover (the planes and boxes are ov_bits and ov_box): control words, records, order tables and selected list (prk::CoverState); the claimed plane
+    PinBuf h_cov;                    // the order tables on their way in, then the whole state on its way to the caller
     DevBuf contours;                 // pr_score_contours: the contour records of a chunk
     DevBuf normals;                  // pr_score_normals: the normal records of a chunk
     PinBuf h_normals;                // ... on their way to the caller

@@ -1,4 +1,4 @@
-// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, contour.hip, normals.hip, compose.hip, vsd.hip and nobody else): the workgroup's
+// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, cover.hip, contour.hip, normals.hip, compose.hip, vsd.hip and nobody else): the workgroup's
 // part of a hypothesis' pixel box, the test of a rendered depth against the scene, the sum of a workgroup's counters, the launchers' loop
 // gfx950 (CDNA4, wave64); integer arithmetic only, differences in 64 bits: every value is bit-identical to the CPU restatement.
 #pragma once
@@ -18,6 +18,20 @@ __device__ __forceinline__ bool box_block(const int4 bb, uint32_t height, BoxBlo
     return !(b.bb.x > b.bb.z || b.r_lo > b.r_hi || blk0 > b.r_hi || blk0 + (int)kBoxRowsPerBlock - 1 < b.r_lo);
 }
 __device__ __forceinline__ bool box_block(const int4 *__restrict__ bbox, uint32_t height, BoxBlock &b) { return box_block(bbox[blockIdx.y], height, b); }
+
+// ---- a pixel box in the words of a bit plane (select.hip's planes, cover.hip's claimed plane) ----
+struct WordBox { int r0, r1, w0, w1; };                              // image rows and frame words of a pixel box; empty: r0 > r1
+__device__ __forceinline__ WordBox word_box(const int4 bb, uint32_t height)
+{
+    WordBox b;
+    b.r0 = (int)height - 1 - bb.w; b.r1 = (int)height - 1 - bb.y; b.w0 = bb.x >> 6; b.w1 = bb.z >> 6;
+    if (bb.x > bb.z || bb.x < 0 || b.r0 < 0 || b.r1 >= (int)height) { b.r0 = 1; b.r1 = 0; }      // (boxes are clipped to the frame: the range tests never fire)
+    return b;
+}
+
+// c / d for c * d < 2^32 by one multiply: fast_div_magic(d) = floor(2^32 / d) + 1 errs by less than c * d / 2^32 < 1 (d == 1: the quotient is c)
+__device__ __forceinline__ uint32_t fast_div_magic(uint32_t d) { return d > 1 ? 0xffffffffu / d + 1u : 0u; }
+__device__ __forceinline__ uint32_t fast_div(uint32_t c, uint32_t magic) { return magic ? __umulhi(c, magic) : c; }
 
 // ---- the depth test: what an inlier is for the ranking, the selection, the contour gate, the normal agreement and the composition ----
 __device__ __forceinline__ bool rendered(int32_t d) { return d > 0 && d != INT_MAX; }      // something was drawn here (INT_MAX: the render's background)

@@ -75,19 +75,6 @@ constexpr uint32_t kPairThreads = 1024, kPairWaves = kPairThreads / 64;
 constexpr uint32_t kPairCellsPerLane = 4, kPairMinGroups = 1024, kPairMaxSplits = 8;
 constexpr uint32_t kPairTileWords = 6144;                             // 48 KB of LDS: a 640 x 480 frame (10 x 480 words) in one band; three workgroups per CU
 
-struct WordBox { int r0, r1, w0, w1; };                              // image rows and frame words of a pixel box; empty: r0 > r1
-__device__ __forceinline__ WordBox word_box(const int4 bb, uint32_t height)
-{
-    WordBox b;
-    b.r0 = (int)height - 1 - bb.w; b.r1 = (int)height - 1 - bb.y; b.w0 = bb.x >> 6; b.w1 = bb.z >> 6;
-    if (bb.x > bb.z || bb.x < 0 || b.r0 < 0 || b.r1 >= (int)height) { b.r0 = 1; b.r1 = 0; }      // (boxes are clipped to the frame: the range tests never fire)
-    return b;
-}
-
-// c / d for c * d < 2^32 by one multiply: fast_div_magic(d) = floor(2^32 / d) + 1 errs by less than c * d / 2^32 < 1 (d == 1: the quotient is c)
-__device__ __forceinline__ uint32_t fast_div_magic(uint32_t d) { return d > 1 ? 0xffffffffu / d + 1u : 0u; }
-__device__ __forceinline__ uint32_t fast_div(uint32_t c, uint32_t magic) { return magic ? __umulhi(c, magic) : c; }
-
 __global__ __launch_bounds__(kPairThreads) void pair_overlap_kernel(const unsigned long long *__restrict__ planes, const int4 *__restrict__ bbox, uint32_t n_poses,
                                                                     uint32_t height, uint32_t words_per_row, uint32_t *mat)
 {

@@ -695,6 +695,10 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *   "raster_mode"      [0]     fused render: 0 = global atomicMin inside the pose's pixel box, 1 = LDS depth bands (synchronous path)
  *   "mesh_order"       [1]     asynchronous path: the raster reads a library-owned copy of the triangle buffer in spatial order (made once per
  *                              buffer, on its second batch in a row, checked against the caller's buffer by every batch; 36 bytes per triangle of device memory); 0 = the caller's buffer
+ *   "tight_box"        [1]     asynchronous path: each hypothesis' pixel box is the hull of the mesh's projected vertices (a kernel over the library's
+ *                              list of the buffer's distinct vertices, made and checked with the ordered copy; 16 bytes per distinct vertex) instead of
+ *                              the hull of the projected corners of the mesh's box; 0 = the latter.  Same results either way
+ *                              ("stat_tight_batches", read-only: asynchronous batches of this process that ran on tight boxes)
  *   "nn_stack"         [1]     kd-tree query: per-lane LDS stack (1) or the reference's stackless walk (0)
  *   "nn_compact"       [1]     stack query on 32-byte node records with 16-bit outward-rounded boxes (0: exact 64-byte records)
  *   "host_worker"      [1]     host solve: a batch given to pr_refine_submit runs on a library-owned helper thread of its slot (private context: its own
@@ -770,6 +774,13 @@ int  pr_debug_trace_sums(float *rows_host, uint32_t n_hyp, uint32_t n_passes);
  * hash of each triangle's nine words) that every asynchronous batch re-derives from the caller's buffer on the device. */
 int  pr_debug_mesh_order(const pr_triangle *tris_host, size_t n_tris, uint32_t *perm_out);
 int  pr_debug_mesh_fingerprint(const pr_triangle *tris_host, size_t n_tris, uint64_t *fingerprint_out);
+/* Audit entry (no device needed) for the tight pixel box of the asynchronous path (option "tight_box"): box_out = {x0, y0, x1, y1} in raster
+ * coordinates (y not yet flipped: image row = height - 1 - y), inclusive, empty when x1 < x0 or y1 < y0 -- the hull of the projected
+ * distinct vertices of the soup, padded by 2 pixels, intersected with the box of the projected corners of the mesh's axis-aligned box (the
+ * loose box, which carries the frame and ROI clamps; loose_out, optional, receives it).  The same source as pose_tight_box_kernel, compiled
+ * for the host: a vertex at or behind the camera plane (z <= 1e-3) or a non-finite coordinate leaves the loose box. */
+int  pr_debug_tight_box(const pr_triangle *tris_host, size_t n_tris, const pr_mat4 *pose, const pr_mat4 *proj, uint32_t width, uint32_t height,
+                        pr_roi roi, int32_t box_out[4], int32_t loose_out[4]);
 /* Two things the library does silently for correctness, counted per context since it was created: asynchronous batches that
  * pr_refine_wait ran a SECOND time because the device-side checks found a stale model box, a triangle buffer whose content changed, or a scene array that no longer matches its
  * cached form (a caller who sees this grow writes to its buffers behind the library's back: pr_invalidate is the cheap cure), and timed

@@ -166,6 +166,18 @@ def mesh_fingerprint(tris) -> int:
     return v.value
 
 
+def tight_box(tris, pose, width: int, height: int, proj, roi: Sequence[int] = (0, 0, 0, 0)):
+    """``pr_debug_tight_box``: (tight, loose) pixel boxes ``[x0, y0, x1, y1]`` (int32, raster coordinates, inclusive) of a (T, 3, 3) float32
+    soup under one pose -- what the asynchronous path's box kernel leaves for the hypothesis, and the host's box it started from.  No device needed."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+    m = np.ascontiguousarray(pose, dtype=np.float32).reshape(16)
+    pj = np.ascontiguousarray(proj, dtype=np.float32).reshape(16)
+    tight, loose = np.empty(4, np.int32), np.empty(4, np.int32)
+    check(_lib.load().pr_debug_tight_box(t.ctypes.data, len(t), m.ctypes.data, pj.ctypes.data, width, height, Roi(*roi),
+                                         tight.ctypes.data, loose.ctypes.data))
+    return tight, loose
+
+
 def gather_profile():
     """HIP-event time of the gathers issued while option ``profile`` was on: (total ms, count).  Waits for the library stream."""
     ms, n = C.c_double(), C.c_uint64()

@@ -49,6 +49,51 @@ PR_HD inline int4 pose_pixel_box(const float *aabb, const float *M, const pr_mat
     return make_int4(x0, y0, x1, y1);
 }
 
+// One vertex to the screen: model transform (renderer.h:296-303 mat_mul_v, rows a,b,c), projection rows 0 and 1 (only x and y of the result are
+// used downstream), viewport (renderer.cu:90-98).  THE definition: the raster's triangle setup and the tight pixel box (below) both call it, so with
+// contraction disabled the box is formed from the very floats the raster loops over.
+struct ScreenVertex { float px, py, lz; };
+PR_HD inline ScreenVertex vertex_to_screen(float x, float y, float z, const float *M, const pr_mat4 &proj, uint32_t width, uint32_t height)
+{
+    const float lx = M[0] * x + M[1] * y + M[2] * z + M[3];
+    const float ly = M[4] * x + M[5] * y + M[6] * z + M[7];
+    const float lz = M[8] * x + M[9] * y + M[10] * z + M[11];
+    const float cxp = proj.m[0] * lx + proj.m[1] * ly + proj.m[2] * lz + proj.m[3];
+    const float cyp = proj.m[4] * lx + proj.m[5] * ly + proj.m[6] * lz + proj.m[7];
+    ScreenVertex s;
+    s.px = cxp / lz * (float)width / 2.0f + (float)width / 2.0f;
+    s.py = cyp / lz * (float)height / 2.0f + (float)height / 2.0f;
+    s.lz = lz;
+    return s;
+}
+
+// The tight pixel box of a hypothesis: the hull of the mesh's projected VERTICES instead of the projected corners of its box (the fused
+// asynchronous path, option tight_box).  TightAcc is what a pass over the vertices keeps -- running bounds of px / py and whether any vertex
+// is unusable: at or behind the camera plane, or with a coordinate that is not finite (NaN never enters fminf / fmaxf, so it is counted here).
+// Minima and maxima are exact in any order: every split of the vertices over lanes, merged in any tree, gives the same TightAcc.
+struct TightAcc { float mnx, mny, mxx, mxy; uint32_t bad; };
+PR_HD inline TightAcc tight_acc_empty() { return TightAcc{ FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, 0u }; }
+PR_HD inline void tight_acc_add(TightAcc &a, const ScreenVertex &s)
+{
+    if (!(s.lz > 1e-3f) || !(fabsf(s.px) < 1e8f) || !(fabsf(s.py) < 1e8f)) a.bad = 1u;
+    a.mnx = fminf(a.mnx, s.px); a.mxx = fmaxf(a.mxx, s.px); a.mny = fminf(a.mny, s.py); a.mxy = fmaxf(a.mxy, s.py);
+}
+PR_HD inline void tight_acc_merge(TightAcc &a, const TightAcc &b)
+{
+    a.mnx = fminf(a.mnx, b.mnx); a.mxx = fmaxf(a.mxx, b.mxx); a.mny = fminf(a.mny, b.mny); a.mxy = fmaxf(a.mxy, b.mxy); a.bad |= b.bad;
+}
+// ... and the box it stands for: pose_pixel_box's rounding and padding ({floor(min) - 2, ceil(max) + 2}), intersected with the LOOSE box
+// `loose` (pose_pixel_box: it carries the frame and ROI clamps), so the result is never larger than the box everything was sized with.  An
+// unusable vertex, or no vertex at all, leaves the hypothesis on its loose box.
+PR_HD inline int4 tight_pixel_box(const TightAcc &a, const int4 loose)
+{
+    if (a.bad || !(a.mnx <= a.mxx) || !(a.mny <= a.mxy)) return loose;
+    auto imax = [](int p, int q) { return p > q ? p : q; };
+    auto imin = [](int p, int q) { return p < q ? p : q; };
+    return make_int4(imax(loose.x, (int)floorf(a.mnx) - 2), imax(loose.y, (int)floorf(a.mny) - 2),
+                     imin(loose.z, (int)ceilf(a.mxx) + 2), imin(loose.w, (int)ceilf(a.mxy) + 2));
+}
+
 // Mixing hash of one triangle's nine words (bit patterns: -0.0f and 0.0f, or two NaNs, are different content).  The fingerprint of a
 // triangle buffer is the wrapping 64-bit SUM of these over its triangles -- a multiset hash, equal for every order of the same triangles --
 // so the host (when it builds the ordered copy) and the raster's per-batch check (over the caller's buffer, in whatever order the

@@ -63,6 +63,22 @@ void mesh_order(const pr_triangle *tris, size_t n_tris, uint32_t *perm)
     std::iota(perm, perm + n_tris, 0u);
     std::stable_sort(perm, perm + n_tris, [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
 }
+void mesh_vertices(const pr_triangle *tris, size_t n_tris, std::vector<float4> &out)
+{
+    struct Key { uint32_t w[3]; };
+    std::vector<Key> keys(n_tris * 3);
+    if (n_tris) std::memcpy(static_cast<void *>(keys.data()), tris, sizeof(Key) * keys.size());
+    auto less = [](const Key &a, const Key &b) { return a.w[2] != b.w[2] ? a.w[2] < b.w[2] : (a.w[1] != b.w[1] ? a.w[1] < b.w[1] : a.w[0] < b.w[0]); };
+    auto same = [](const Key &a, const Key &b) { return a.w[0] == b.w[0] && a.w[1] == b.w[1] && a.w[2] == b.w[2]; };
+    std::sort(keys.begin(), keys.end(), less);
+    keys.erase(std::unique(keys.begin(), keys.end(), same), keys.end());
+    out.resize(keys.size());
+    for (size_t i = 0; i < keys.size(); ++i) {
+        float v[3];
+        std::memcpy(v, keys[i].w, sizeof v);
+        out[i] = make_float4(v[0], v[1], v[2], 0.0f);
+    }
+}
 unsigned long long mesh_fingerprint(const pr_triangle *tris, size_t n_tris)
 {
     unsigned long long sum = 0;
@@ -791,6 +807,26 @@ int pr_debug_mesh_order(const pr_triangle *tris_host, size_t n_tris, uint32_t *p
     if (n_tris && (!tris_host || !perm_out)) { prh::set_error("pr_debug_mesh_order: null buffer"); return PR_ERR_INVALID; }
     if (n_tris > 0xffffffffull) { prh::set_error("pr_debug_mesh_order: more than 2^32 - 1 triangles"); return PR_ERR_INVALID; }
     prh::mesh_order(tris_host, n_tris, perm_out);
+    return PR_OK;
+}
+int pr_debug_tight_box(const pr_triangle *tris_host, size_t n_tris, const pr_mat4 *pose, const pr_mat4 *proj, uint32_t width, uint32_t height,
+                       pr_roi roi, int32_t box_out[4], int32_t loose_out[4])
+{
+    if ((n_tris && !tris_host) || !pose || !proj || !box_out) { prh::set_error("pr_debug_tight_box: null argument"); return PR_ERR_INVALID; }
+    // the loose box as the asynchronous path's host forms it (ensure_model_box's fminf / fmaxf box, pose_pixel_box) ...
+    const float *f = reinterpret_cast<const float *>(tris_host);
+    float aabb[6] = { FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX };
+    for (size_t v = 0; v < n_tris * 3; ++v)
+        for (int d = 0; d < 3; ++d) { aabb[d] = fminf(aabb[d], f[3 * v + d]); aabb[3 + d] = fmaxf(aabb[3 + d], f[3 * v + d]); }
+    const int4 loose = prk::pose_pixel_box(aabb, pose->m, *proj, width, height, roi);
+    // ... and the kernel's walk over the distinct vertices, in one lane
+    std::vector<float4> verts;
+    prh::mesh_vertices(tris_host, n_tris, verts);
+    prk::TightAcc a = prk::tight_acc_empty();
+    for (const float4 &v : verts) prk::tight_acc_add(a, prk::vertex_to_screen(v.x, v.y, v.z, pose->m, *proj, width, height));
+    const int4 b = prk::tight_pixel_box(a, loose);
+    box_out[0] = b.x; box_out[1] = b.y; box_out[2] = b.z; box_out[3] = b.w;
+    if (loose_out) { loose_out[0] = loose.x; loose_out[1] = loose.y; loose_out[2] = loose.z; loose_out[3] = loose.w; }
     return PR_OK;
 }
 int pr_debug_mesh_fingerprint(const pr_triangle *tris_host, size_t n_tris, uint64_t *fingerprint_out)

@@ -176,6 +176,11 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
                                PoseMeta *meta = nullptr, DevIcpState *st = nullptr, uint32_t *arrive = nullptr, uint32_t cloud_stride = 0,
                                const uint32_t *box_off = nullptr,    // box_off: the boxes packed into `depth` at these offsets (ints), each with its own pitch (fill_box_kernel)
                                const BatchCheck *check = nullptr);
+// Asynchronous path, option tight_box (pose_tight_box_kernel): bbox[i], the loose box the host uploaded, overwritten by its intersection with the
+// hull of the projected vertices `verts` ({x, y, z, 0}: the mesh's distinct vertices); then, per sub-batch, the packed offsets of those boxes.
+hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_mat4 *poses_dev, uint32_t n_poses, const pr_mat4 &proj,
+                              uint32_t width, uint32_t height, int4 *bbox, hipStream_t s);
+hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, hipStream_t s);
 // Mixed batches (pr_*_multi): the hypotheses grouped by mesh.  One group of consecutive hypotheses [first, first + count) of a launch that share
 // a mesh; raster_multi_kernel's workgroups [first_wg, first_wg + tri_blocks * ceil(count / run)) are its (triangle block, pose run) pairs.
 // The host fills tris, n_tris, first and count; launch_raster_multi the rest.  48 bytes: staged in 16-byte words.
@@ -370,6 +375,9 @@ void solve_666(const float A[36], const float b[6], float T[16]);
 void mat4_mul(const float A[16], const float B[16], float C[16]);
 // Spatial order of a triangle soup (pr_debug_mesh_order): perm[k] = index of the triangle that goes to place k.  A pure function of the data.
 void mesh_order(const pr_triangle *tris, size_t n_tris, uint32_t *perm);
+// The distinct vertices of a triangle soup as {x, y, z, 0}, distinct by bit pattern, in ascending order of the words (z, y, x as unsigned): what
+// pose_tight_box_kernel walks.  A pure function of the data.
+void mesh_vertices(const pr_triangle *tris, size_t n_tris, std::vector<float4> &out);
 // multiset fingerprint of a triangle buffer: wrapping sum of triangle_hash (pose_box.h)
 unsigned long long mesh_fingerprint(const pr_triangle *tris, size_t n_tris);
 // the cover rule's own conditions (pr_score_cover, pr_select_cover_host): the fraction, and order a list of distinct indices < n_poses.  PR_ERR_INVALID with a message

@@ -806,6 +806,8 @@ void slot_release(Slot &sl)
 // order-independent fingerprint of every word (BatchCheck: the box alone would miss a rewrite that keeps the box), and refine_wait
 // re-runs the batch through the synchronous path, which reads the caller's buffer only, if either differs -- a rewritten mesh costs
 // one repeated batch, never a wrong one.
+// Made with the ordered copy, from the same host copy, and valid exactly when it is: the buffer's distinct vertices (prh::mesh_vertices), which option
+// tight_box's box kernel walks.  The fingerprint guards it as it guards the order -- and there it is what keeps a rewritten mesh from being CLIPPED.
 // (An indexed form of the soup with a per-pose vertex stage was built and measured as well: three divergent 16-byte gathers
 // per triangle cost the texture addresser more than the 170 saved VALU instructions give back -- 1.27 -> 1.32 ms per step.)
 int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
@@ -813,7 +815,8 @@ int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
     // The ordered copy costs a host sort (35 ms for obj_06): it is made for a buffer that STAYS -- on the second batch in a row that finds the
     // same (pointer, size) -- so a caller that alternates between models on one context pays what it paid before (one read-back per batch).
     const bool seen = g->mesh_key == tris_dev && g->mesh_n == n_tris && g->aabb_host_valid;
-    if (seen && (!opt.mesh_order || g->mesh_sorted_valid)) return PR_OK;
+    const bool want_copies = opt.mesh_order || opt.tight_box;
+    if (seen && (!want_copies || g->mesh_sorted_valid)) return PR_OK;
     std::vector<pr_triangle> h(n_tris);
     if (n_tris) HIP_TRY(hipMemcpy(h.data(), tris_dev, sizeof(pr_triangle) * n_tris, hipMemcpyDeviceToHost));
     const float *f = reinterpret_cast<const float *>(h.data());
@@ -822,8 +825,8 @@ int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
         for (int d = 0; d < 3; ++d) { lo[d] = fminf(lo[d], f[3 * v + d]); hi[d] = fmaxf(hi[d], f[3 * v + d]); }
     for (int d = 0; d < 3; ++d) { g->aabb_host[d] = lo[d]; g->aabb_host[3 + d] = hi[d]; }
     g->mesh_hash = prh::mesh_fingerprint(h.data(), n_tris);
-    g->mesh_sorted_valid = false;
-    if (opt.mesh_order && seen && n_tris > 0 && n_tris <= 0xffffffffull) {
+    g->mesh_sorted_valid = false; g->mesh_verts_n = 0;
+    if (want_copies && seen && n_tris > 0 && n_tris <= 0xffffffffull) {
         std::vector<uint32_t> perm(n_tris);
         prh::mesh_order(h.data(), n_tris, perm.data());
         std::vector<pr_triangle> sorted(n_tris);
@@ -832,6 +835,12 @@ int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
         for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
         PR_TRY(g->mesh_sorted.ensure(sizeof(pr_triangle) * n_tris));
         HIP_TRY(hipMemcpy(g->mesh_sorted.p, sorted.data(), sizeof(pr_triangle) * n_tris, hipMemcpyHostToDevice));
+        // the buffer's distinct vertices, from the same host copy (option tight_box: what pose_tight_box_kernel walks; obj_06: 94 404 -> 15 736)
+        std::vector<float4> verts;
+        prh::mesh_vertices(h.data(), n_tris, verts);
+        PR_TRY(g->mesh_verts.ensure(sizeof(float4) * verts.size()));
+        HIP_TRY(hipMemcpy(g->mesh_verts.p, verts.data(), sizeof(float4) * verts.size(), hipMemcpyHostToDevice));
+        g->mesh_verts_n = (uint32_t)verts.size();
         g->mesh_sorted_valid = true;
     }
     g->mesh_key = tris_dev; g->mesh_n = n_tris; g->aabb_host_valid = true;
@@ -1133,6 +1142,15 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
         if (&o != &sl && o.pending && !o.delivered && o.progress_valid) HIP_TRY(hipStreamWaitEvent(st, o.progress, 0));
     sl.progress_valid = false;
     HIP_TRY(prk::launch_stage_words(sl.h_in.dev, d_poses, in.bytes, st));
+    // Option tight_box: the uploaded boxes are the LOOSE ones (hull of the projected corners of the mesh's box) -- they sized everything above.  On the
+    // device each is replaced by its intersection with the hull of the mesh's projected vertices (57 % of the pixels for obj_06), and the packed
+    // offsets of each sub-batch are formed again from those: what fill, raster, count and emit then walk.  Never larger than the loose box, so
+    // every capacity holds; no host round trip.  Needs the context's vertex list (ensure_model_box: from the buffer's second batch on).
+    const bool tight = opt.tight_box && g->mesh_sorted_valid && g->mesh_verts_n > 0;
+    if (tight) {
+        HIP_TRY(prk::launch_tight_boxes(g->mesh_verts.as<float4>(), g->mesh_verts_n, d_poses, P, job.proj, W, H, d_box, st));
+        g_tight_batches.fetch_add(1);
+    }
     const bool fused = opt.fused_solve != 0;
     const pr_roi none{ 0, 0, 0, 0 };                              // the ROI is already part of the host-computed boxes
     const Lanes lanes{ sl.stream, sl.side, sl.fork, sl.join };
@@ -1150,6 +1168,7 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
         // `exact` flag / tree depth back before it returns, so a rebuild has finished on the host's clock before the render is even enqueued; on a
         // cache hit the event is complete when recorded)
         if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
+        if (tight && d_off) HIP_TRY(prk::launch_box_pack_offsets(d_box + q0, nq, const_cast<uint32_t *>(d_off) + q0, st));
         HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)job.n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
                                          sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, job.proj, none, st,
                                          /*compute_boxes=*/false, meta, dstate, arrive, (uint32_t)cstride, d_off ? d_off + q0 : nullptr, q0 == 0 ? &chk : nullptr));

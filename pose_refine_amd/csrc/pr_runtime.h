@@ -120,6 +120,7 @@ struct WriteLog {
     }
 };
 extern WriteLog g_writes;
+extern std::atomic<uint64_t> g_tight_batches;     // asynchronous batches whose pixel boxes came from pose_tight_box_kernel (process-wide; read-only option "stat_tight_batches": tests tell the tight path from the loose one by it)
 extern std::atomic<uint64_t> g_flag_overtook;     // PR_SOLVE_HOST: group flags that reached the host before all of their rows (process-wide; expected 0; read-only option "stat_flag_overtook")
 
 // ---- process-wide options (pr_set_option): plain ints, shared by every context ---------------------
@@ -159,6 +160,7 @@ struct Options {
     int eager_streams = 1;           // asynchronous path: create the streams of both slots in one run (see slot_streams)
     int raster_mode = 0;             // fused path: 0 = global atomicMin inside the per-pose pixel box (reference scheme), 1 = LDS depth bands (int32); pr_set_option refuses anything else
     int mesh_order = 1;              // asynchronous fused path: raster the library's spatially ordered copy of the triangle buffer (ensure_model_box); 0 = the caller's buffer
+    int tight_box = 1;               // asynchronous fused path: pixel boxes from the mesh's projected vertices (pose_tight_box_kernel over the library's list of distinct vertices, ensure_model_box) instead of the projected corners of its box; 0 = the latter
     int scene_cache = 1;             // keep the packed projective scene / kd traversal records of the latest scene between calls (pr_scene_invalidate)
 };
 extern Options opt;
@@ -463,7 +465,10 @@ struct Ctx {
     // ... and the same buffer's triangles in spatial order (prh::mesh_order), with the multiset fingerprint of the content they were copied from
     // (BatchCheck::mesh_hash): same key, same life cycle, verified by the same batches
     DevBuf mesh_sorted; bool mesh_sorted_valid = false; unsigned long long mesh_hash = 0;
-    void drop_mesh() { mesh_key = nullptr; aabb_host_valid = false; mesh_sorted_valid = false; }
+    // ... and its distinct vertices as {x, y, z, 0} (prh::mesh_vertices; option tight_box), made from the same host copy in the same place: valid when
+    // mesh_sorted_valid is, and so under the same per-batch fingerprint of the caller's buffer -- a stale list would clip pixels
+    DevBuf mesh_verts; uint32_t mesh_verts_n = 0;
+    void drop_mesh() { mesh_key = nullptr; aabb_host_valid = false; mesh_sorted_valid = false; mesh_verts_n = 0; }
     uint32_t cloud_hint = 0;          // largest cloud of the latest finished asynchronous batch: sizes the next batch's grid
     // workspaces
     DevBuf aabb, aabb_keys, bbox, poses, depth, row_count, row_off, counts, cloud, meta, partial, sums, nn_prev, dstate, dresults, arrive, conv16, conv8, kd_scratch, kd_tmp, nn_full;

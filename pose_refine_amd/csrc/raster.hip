@@ -57,18 +57,11 @@ __device__ __forceinline__ void tri_setup(const float *__restrict__ tv, const fl
 {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float x = tv[3 * k], y = tv[3 * k + 1], z = tv[3 * k + 2];
-        // model transform (renderer.h:296-303 mat_mul_v, rows a,b,c)
-        const float lx = M[0] * x + M[1] * y + M[2] * z + M[3];
-        const float ly = M[4] * x + M[5] * y + M[6] * z + M[7];
-        const float lz = M[8] * x + M[9] * y + M[10] * z + M[11];
-        t.w3[k] = lz;                                            // renderer.cu:177-183 last_row
-        // projection transform: only x and y of the result are used downstream
-        const float cxp = proj.m[0] * lx + proj.m[1] * ly + proj.m[2] * lz + proj.m[3];
-        const float cyp = proj.m[4] * lx + proj.m[5] * ly + proj.m[6] * lz + proj.m[7];
-        // viewport (renderer.cu:90-98)
-        t.px[k] = cxp / lz * (float)width / 2.0f + (float)width / 2.0f;
-        t.py[k] = cyp / lz * (float)height / 2.0f + (float)height / 2.0f;
+        // model, projection and viewport transform (vertex_to_screen, pose_box.h: shared with the tight pixel box)
+        const ScreenVertex s = vertex_to_screen(tv[3 * k], tv[3 * k + 1], tv[3 * k + 2], M, proj, width, height);
+        t.w3[k] = s.lz;                                          // renderer.cu:177-183 last_row
+        t.px[k] = s.px;
+        t.py[k] = s.py;
     }
     float lo0 = FLT_MAX, lo1 = FLT_MAX, hi0 = -FLT_MAX, hi1 = -FLT_MAX;
 #pragma unroll
@@ -471,6 +464,43 @@ __global__ __launch_bounds__(256) void pose_bbox_multi_kernel(const float *__res
     bbox[p] = pose_pixel_box(aabbs + 6 * (size_t)box_index[p], poses[p].m, proj, width, height, roi);
 }
 
+// The tight pixel box of every hypothesis (tight_pixel_box, pose_box.h; asynchronous path, option tight_box): one workgroup per hypothesis
+// walks the mesh's distinct vertices (`verts`: {x, y, z, 0} each, ensure_model_box) through vertex_to_screen -- the floats the raster's
+// triangle setup forms for the same vertex -- and overwrites bbox[hypothesis], which holds the LOOSE box the host sized the batch with, by
+// its intersection with the hull of the projected vertices.  Only ever smaller than the loose box: every offset, pitch and capacity derived
+// from the loose boxes stays an upper bound.  Lane minima / maxima merged like box_key_merge (wave shuffles, then LDS over the waves).
+// 1024 lanes (four waves per SIMD) with four loads in flight each: a lane's chain is a 16-byte load out of L2, then two IEEE divisions that
+// depend on it.  By instruction count the launch is ~6 us of issue time for 256 hypotheses of obj_06's 15 736 vertices; traced it takes 12 us
+// when it has the chip and 32 us on average beside the other slot's passes (profiles/tight_box; as 256 lanes with one load in flight: 35.5 us).
+// A lane past the end re-reads the last vertex: minima, maxima and the flag do not change.
+constexpr uint32_t kTightLanes = 1024, kTightLoads = 4;
+__global__ __launch_bounds__(kTightLanes) void pose_tight_box_kernel(const float4 *__restrict__ verts, uint32_t n_verts, const pr_mat4 *__restrict__ poses,
+                                                                     pr_mat4 proj, uint32_t width, uint32_t height, int4 *__restrict__ bbox)
+{
+    __shared__ TightAcc red[kTightLanes / 64];
+    const float *M = poses[blockIdx.x].m;                            // wave-uniform -> scalar loads
+    TightAcc a = tight_acc_empty();
+    for (uint32_t i0 = threadIdx.x; i0 < n_verts; i0 += kTightLanes * kTightLoads) {
+        float4 v[kTightLoads];
+#pragma unroll
+        for (uint32_t k = 0; k < kTightLoads; ++k) v[k] = verts[min(i0 + k * kTightLanes, n_verts - 1u)];
+#pragma unroll
+        for (uint32_t k = 0; k < kTightLoads; ++k) tight_acc_add(a, vertex_to_screen(v[k].x, v[k].y, v[k].z, M, proj, width, height));
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        TightAcc o;
+        o.mnx = __shfl_xor(a.mnx, off); o.mny = __shfl_xor(a.mny, off); o.mxx = __shfl_xor(a.mxx, off); o.mxy = __shfl_xor(a.mxy, off);
+        o.bad = __shfl_xor(a.bad, off);
+        tight_acc_merge(a, o);
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < kTightLanes / 64; ++w) tight_acc_merge(a, red[w]);
+        bbox[blockIdx.x] = tight_pixel_box(a, bbox[blockIdx.x]);
+    }
+}
+
 // INT_MAX-fill and per-row valid counts restricted to each hypothesis' pixel box (image rows are
 // the flipped raster rows).  One wavefront per image row; rows outside the box only write count 0.
 __global__ __launch_bounds__(256) void fill_box_kernel(int32_t *__restrict__ depth, const int4 *__restrict__ bbox, uint32_t width, uint32_t height,
@@ -712,6 +742,21 @@ __global__ __launch_bounds__(256) void box_pack_offsets_kernel(const int4 *__res
 static void launch_box_pack(const int4 *bbox, uint32_t n_poses, const uint32_t *box_off, hipStream_t s)
 {
     if (box_off && kBoxPack) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, bbox, n_poses, const_cast<uint32_t *>(box_off));   // (the caller's scratch: filled here)
+}
+// Asynchronous path, option tight_box: the uploaded loose boxes of all n_poses hypotheses replaced by their tight ones ...
+hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_mat4 *poses_dev, uint32_t n_poses, const pr_mat4 &proj,
+                              uint32_t width, uint32_t height, int4 *bbox, hipStream_t s)
+{
+    if (n_poses == 0 || n_verts == 0) return hipSuccess;
+    hipLaunchKernelGGL(pose_tight_box_kernel, dim3(n_poses), dim3(kTightLanes), 0, s, verts, n_verts, poses_dev, proj, width, height, bbox);
+    return hipGetLastError();
+}
+// ... and the packed offsets of one sub-batch's boxes formed again from them (the uploaded ones belong to the loose boxes)
+hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, hipStream_t s)
+{
+    if (n_poses == 0) return hipSuccess;
+    launch_box_pack(bbox, n_poses, box_off, s);
+    return hipGetLastError();
 }
 static void launch_fill_boxes(int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height, hipStream_t s)
 {

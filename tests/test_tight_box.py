@@ -1,0 +1,142 @@
+"""The tight pixel box of the asynchronous path (option tight_box) through its host twin, pr_debug_tight_box: the same source as
+pose_tight_box_kernel compiled for the host, no device.  The box must hold every pixel the raster can draw (checked against the oracle's
+raster, tests/oracle_lib.py), must never leave the loose box everything is sized with, and must be what the change is for: clearly smaller."""
+import numpy as np
+import pytest
+
+import oracle_lib as O
+from pose_refine_amd import api, synth
+from gpu_common import random_mesh
+
+W, H = synth.WIDTH, synth.HEIGHT
+NONE = (0, 0, 0, 0)
+f32 = np.float32
+
+
+def area(b):
+    return max(int(b[2]) - int(b[0]) + 1, 0) * max(int(b[3]) - int(b[1]) + 1, 0)
+
+
+def inside(inner, outer):
+    return area(inner) == 0 or (inner[0] >= outer[0] and inner[1] >= outer[1] and inner[2] <= outer[2] and inner[3] <= outer[3])
+
+
+def shifted(pose, dx_mm):
+    p = pose.copy().reshape(4, 4)
+    p[0, 3] += f32(dx_mm)
+    return p
+
+
+def drawn_box(tris, pose, proj, roi=NONE):
+    """{x0, y0, x1, y1} in RASTER coordinates (row flipped back) of the pixels the oracle's raster draws, or None."""
+    img = O.render(tris, pose[None], W, H, proj, roi)[0]
+    rows, cols = np.nonzero(img)
+    if len(rows) == 0:
+        return None
+    rows = rows + (roi[1] if roi[2] > 0 and roi[3] > 0 else 0)
+    cols = cols + (roi[0] if roi[2] > 0 and roi[3] > 0 else 0)
+    return np.array([cols.min(), H - 1 - rows.max(), cols.max(), H - 1 - rows.min()])
+
+
+def numpy_tight_box(tris, pose, proj, loose):
+    """vertex_to_screen / tight_pixel_box (csrc/pose_box.h) restated in float32 numpy, operation by operation."""
+    v = np.ascontiguousarray(tris, f32).reshape(-1, 3)
+    M, P = np.asarray(pose, f32).reshape(16), np.asarray(proj, f32).reshape(16)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    lx = M[0] * x + M[1] * y + M[2] * z + M[3]
+    ly = M[4] * x + M[5] * y + M[6] * z + M[7]
+    lz = M[8] * x + M[9] * y + M[10] * z + M[11]
+    cx = P[0] * lx + P[1] * ly + P[2] * lz + P[3]
+    cy = P[4] * lx + P[5] * ly + P[6] * lz + P[7]
+    with np.errstate(all="ignore"):
+        px = cx / lz * f32(W) / f32(2) + f32(W) / f32(2)
+        py = cy / lz * f32(H) / f32(2) + f32(H) / f32(2)
+        bad = np.any(~(lz > f32(1e-3))) or np.any(~(np.abs(px) < f32(1e8))) or np.any(~(np.abs(py) < f32(1e8)))
+    if bad or len(v) == 0:
+        return np.asarray(loose)
+    return np.array([max(loose[0], int(np.floor(px.min())) - 2), max(loose[1], int(np.floor(py.min())) - 2),
+                     min(loose[2], int(np.ceil(px.max())) + 2), min(loose[3], int(np.ceil(py.max())) + 2)])
+
+
+@pytest.fixture(scope="module")
+def proj():
+    return O.compute_proj(synth.K_TEST, W, H)
+
+
+@pytest.fixture(scope="module")
+def boxes24(obj06_tris, proj):
+    return [api.tight_box(obj06_tris, p, W, H, proj) for p in synth.hypotheses(24)]
+
+
+def test_tight_box_lies_in_the_loose_box_and_holds_every_drawn_pixel(obj06_tris, proj, boxes24):
+    for pose, (tight, loose) in zip(synth.hypotheses(6), boxes24[:6]):
+        assert area(tight) > 0 and inside(tight, loose)
+        assert inside(drawn_box(obj06_tris, pose, proj), tight)
+        assert np.array_equal(tight, numpy_tight_box(obj06_tris, pose, proj, loose))
+
+
+def test_roi_clips_the_tight_box_like_the_loose_one(obj06_tris, proj):
+    roi = (250, 150, 180, 160)
+    pose = synth.hypotheses(1)[0]
+    tight, loose = api.tight_box(obj06_tris, pose, W, H, proj, roi)
+    free, _ = api.tight_box(obj06_tris, pose, W, H, proj)
+    window = np.array([roi[0], H - 1 - (roi[1] + roi[3] - 1), roi[0] + roi[2] - 1, H - 1 - roi[1]])
+    assert inside(tight, loose) and inside(tight, window)
+    assert np.array_equal(tight, [max(free[0], window[0]), max(free[1], window[1]), min(free[2], window[2]), min(free[3], window[3])])
+    drawn = drawn_box(obj06_tris, pose, proj, roi)
+    assert drawn is not None and inside(drawn, tight)
+
+
+def test_frame_edge_cuts_the_tight_box(obj06_tris, proj):
+    pose = shifted(synth.hypotheses(1)[0], 150.0)                 # 150 mm at 300 mm depth: about 290 pixels to the right
+    tight, loose = api.tight_box(obj06_tris, pose, W, H, proj)
+    assert tight[2] == W - 1 and tight[0] > 0 and inside(tight, loose) and area(tight) < area(loose)
+    drawn = drawn_box(obj06_tris, pose, proj)
+    assert drawn is not None and drawn[2] == W - 1 and inside(drawn, tight)
+
+
+def test_tight_boxes_are_clearly_smaller(boxes24):
+    tight = sum(area(t) for t, _ in boxes24)
+    loose = sum(area(l) for _, l in boxes24)
+    print(f"tight / loose pixel-box area over 24 hypotheses: {tight} / {loose} = {tight / loose:.3f}")
+    assert tight / loose <= 0.65
+
+
+def test_vertex_at_the_camera_plane_keeps_the_loose_box(proj):
+    tri = np.array([[[0, 0, 0], [30, 0, 300], [0, 30, 300]]], f32)
+    pose = np.eye(4, dtype=f32)
+    pose[2, 3] = f32(1e-3)                                          # lz of the first vertex = 1e-3: not in front of the plane
+    tight, loose = api.tight_box(tri, pose, W, H, proj)
+    assert np.array_equal(tight, loose) and np.array_equal(loose, [0, 0, W - 1, H - 1])
+    pose[2, 3] = f32(1.0)                                           # ... and just in front of it: a box of its own
+    tight, loose = api.tight_box(tri, pose, W, H, proj)
+    assert inside(tight, loose) and np.array_equal(tight, numpy_tight_box(tri, pose, proj, loose))
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf])
+def test_non_finite_pose_keeps_the_loose_box(obj06_tris, proj, bad):
+    pose = synth.hypotheses(1)[0].copy().reshape(4, 4)
+    pose[0, 3] = bad
+    tight, loose = api.tight_box(obj06_tris[:500], pose, W, H, proj)
+    assert np.array_equal(tight, loose)
+
+
+def test_pose_off_screen_gives_an_empty_box(obj06_tris, proj):
+    tight, loose = api.tight_box(obj06_tris, shifted(synth.hypotheses(1)[0], 2000.0), W, H, proj)
+    assert area(tight) == 0 and area(loose) == 0
+
+
+@pytest.mark.parametrize("n", [1, 2, 85, 86, 1000])                  # 3, 6, 255, 258 and 3000 vertices before deduplication
+def test_small_and_odd_meshes(proj, n):
+    tris = (random_mesh(np.random.default_rng(n), n, 40.0) if n >= 4 else np.random.default_rng(n).normal(scale=30.0, size=(n, 3, 3))).astype(f32)
+    pose = synth.hypotheses(3)[2]
+    tight, loose = api.tight_box(tris, pose, W, H, proj)
+    assert inside(tight, loose)
+    assert np.array_equal(tight, numpy_tight_box(tris, pose, proj, loose))
+    drawn = drawn_box(tris, pose, proj)
+    assert drawn is None or inside(drawn, tight)
+
+
+def test_empty_mesh_keeps_the_loose_box(proj):
+    tight, loose = api.tight_box(np.zeros((0, 3, 3), f32), synth.hypotheses(1)[0], W, H, proj)
+    assert np.array_equal(tight, loose)

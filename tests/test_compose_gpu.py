@@ -1,6 +1,7 @@
 """GPU tests (-m gpu) of pr_compose_detections / pr_compose_detections_multi: labels, front depth, the per-hypothesis records and the frame record
 equal the numpy reference over the oracle's renders (tests/compose_ref.py) element for element, the scores are pr_score_poses' bytes and the
-sums of the records meet -- int32 and uint16 scenes, ties, duplicates, ROI windows, an odd frame width, two depth chunks, mixed batches."""
+sums of the records meet -- int32 and uint16 scenes, ties, duplicates, ROI windows, an odd frame width, two depth chunks, mixed batches, a
+batch of two launches over its boxes."""
 import threading
 
 import numpy as np
@@ -11,6 +12,7 @@ from pose_refine_amd import _lib, api, synth
 from compose_ref import Composite, assert_composites_equal, check_invariants, compose_ref
 from gpu_common import W, H, pathological_hypotheses
 from select_ref import PLANTED_SELECTION, planted_frame
+from verify_ref import assert_records_repeat, launch_split_case
 
 pytestmark = pytest.mark.gpu
 
@@ -381,3 +383,24 @@ def test_planted_frame_end_to_end(gpu, model, scenario):
     frac = api.visible_fraction(scores, got.visible)
     assert frac[0] == 1.0 and frac[1] > 0.99 and 0.7 < frac[2] < 0.8      # instance 0 (last here) stands behind instance 1
     assert int(got.frame["explained"]) / int(got.frame["covered"]) == int(want.frame["explained"]) / int(want.frame["covered"]) > 0.8
+
+
+def test_batch_of_two_box_launches(gpu):
+    """verify_ref.launch_split_case at 32768 + 5 hypotheses (below PR_COMPOSE_MAX_POSES): the launches over the boxes are split in two, and
+    the second's keys carry indices above 32767.  Ties go to the lower index, so every label is below 8 and every later duplicate owns
+    nothing; the records behind the split are the reference's."""
+    c = launch_split_case()
+    P = c["P"]
+    assert P <= api.COMPOSE_MAX_POSES
+    poses = c["poses"][np.arange(P) % 8]
+    want = compose_ref((c["renders"][i % 8] for i in range(P)), c["scene"], c["tau"])
+    out = api.compose_detections(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"], c["tau"])
+    got, scores = _got(out, c["W"], c["H"])
+    assert_composites_equal(got, want)
+    check_invariants(got, scores)
+    assert_records_repeat(scores, c["scores"])
+    drawn = got.labels != api.COMPOSE_NONE
+    assert drawn.any() and (got.labels[drawn] < 8).all()
+    assert not got.visible["owned"][8:].any() and got.visible["owned"][:8].sum() == got.frame["covered"] > 0
+    assert got.visible[32768:].tobytes() == want.visible[32768:].tobytes() == bytes(want.visible[32768:].nbytes)
+    assert (want.ties[drawn] >= P // 8).all()

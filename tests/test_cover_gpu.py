@@ -2,7 +2,7 @@
 records, the frame record and the selected list equal the cover rule in Python integers over the oracle's renders (tests/cover_ref.py) byte
 for byte -- tiny batches and one larger than a wavefront, int32 and uint16 scenes, word and box edges, pathological hypotheses, partial and
 reversed orders, the cap, ROI windows, several depth chunks, mixed batches, a call between submit and wait, a private context, the planted
-frame, the straddler, and a batch beyond PR_OVERLAP_MAX_POSES."""
+frame, the straddler, a batch beyond PR_OVERLAP_MAX_POSES and one of two launches over its boxes."""
 import ctypes as C
 import threading
 
@@ -15,7 +15,7 @@ from cover_ref import (ACCEPTED, EMPTY, KEEP_ALL, NOT_IN_ORDER, PLANTED_FRESH, R
 from gpu_common import W, H, pathological_hypotheses
 from pose_refine_amd import _lib, api, synth
 from select_ref import PLANTED_SELECTION, planted_frame, shift
-from verify_ref import assert_scores_equal, score_ref
+from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -412,3 +412,23 @@ def test_more_hypotheses_than_the_overlap_matrix_allows(gpu, scenario):
         sc, cov, frame, sel = _check(lambda o, f, mn, k: api.score_cover(m, poses, Ws, Hs, proj, scene, 6, o, f, mn, k), sup, n, want_sc,
                                      api.rank_hypotheses(want_sc), frac, min_new, max_keep)
     assert (sel < 5000).all() and frame["n_selected"] == 5 and (cov["state"] == REJ_CAP).sum() > 100
+
+
+@pytest.mark.parametrize("reverse", [False, True])
+def test_batch_of_two_box_launches(gpu, reverse):
+    """verify_ref.launch_split_case at 32768 + 5 hypotheses: the launches over the boxes are split in two, each with its own support bits,
+    planes and records.  In natural order the first of every pose claims its pixels; reversed, the walk starts behind the split.  The
+    selected list and every record are the reference's, the states of the hypotheses behind the split included."""
+    c = launch_split_case()
+    P = c["P"]
+    poses = c["poses"][np.arange(P) % 8]
+    sup8, n = supports_of(c["renders"], c["scene"], c["tau"])
+    sup = [sup8[i % 8] for i in range(P)]
+    order = np.arange(P)[::-1] if reverse else np.arange(P)
+    want = cover_ref(sup, n, order, 1, 4, 1, KEEP_ALL)
+    sc, cov, frame, sel = api.score_cover(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"], c["tau"], order, (1, 4), 1, None)
+    assert_records_repeat(sc, c["scores"])
+    assert_cover_equal((cov, frame, sel), want)
+    assert len(sel) >= 3 and ((np.asarray(sel) >= 32768).any() if reverse else (np.asarray(sel) < 8).all())
+    behind = cov["state"][32768:]
+    assert (behind != NOT_IN_ORDER).all() and ((behind == ACCEPTED).any() if reverse else (behind != ACCEPTED).all())

@@ -1,5 +1,6 @@
 """GPU tests (-m gpu) of the normal agreement: pr_score_normals held to the numpy restatement of the header's definition (tests/normals_ref.py)
-over the oracle's renders -- every record byte for byte, int32 and uint16 scenes, with and without ROI, the scores against pr_score_poses."""
+over the oracle's renders -- every record byte for byte, int32 and uint16 scenes, with and without ROI, the scores against pr_score_poses, a
+frame whose width is no multiple of 64, a batch of several depth chunks and one of two launches over its boxes."""
 import numpy as np
 import pytest
 
@@ -7,7 +8,7 @@ import oracle_lib as O
 from pose_refine_amd import _lib, api, synth
 from gpu_common import raw_h2d
 from normals_ref import assert_identities, assert_normals_equal, normals_ref
-from verify_ref import assert_scores_equal, score_ref
+from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -238,3 +239,54 @@ def test_edge_cases_and_argument_errors(gpu, model, hyps, proj, scene):
     assert e.value.code == _lib.PR_ERR_INVALID and "pr_score_normals_multi: tau_mm" in str(e.value)
     with pytest.raises(ValueError):
         api.score_normals(model, hyps[:4], W, H, pj, sd, 5, K[:8], 4, 20, 0.5)
+
+
+SPLIT_K = np.array([60.0, 0, 23.5, 0, 60.0, 15.5, 0, 0, 1], np.float32)      # the intrinsics launch_split_case's projection is made from
+
+
+@pytest.mark.parametrize("dtype", [np.int32, np.uint16])
+@pytest.mark.parametrize("step", [1, 8])
+def test_parity_on_a_frame_narrower_than_a_strip(gpu, step, dtype):
+    """The 48 x 32 frame of verify_ref.launch_split_case: a width that is no multiple of 64, renders that reach all four borders.  With
+    step 8 most neighbours leave the box, and many the frame."""
+    c = launch_split_case()
+    assert np.array_equal(c["proj"], api.compute_proj(SPLIT_K, c["W"], c["H"]))
+    scene = np.ascontiguousarray(c["scene"].astype(dtype))
+    want = normals_ref(c["renders"], c["scene"], c["tau"], SPLIT_K, step, c["jump"], COS30)
+    scores, got = api.score_normals(c["tris"], c["poses"], c["W"], c["H"], c["proj"], scene, c["tau"], SPLIT_K, step, c["jump"], COS30)
+    assert_normals_equal(got, want)
+    assert_scores_equal(scores, c["scores"])
+    assert_identities(got, scores)
+    assert want["no_render_normal"].sum() > 0 and (step == 8 or want["tested"].sum() > 0)
+
+
+def test_chunked_batch_matches_small_batches(gpu, model):
+    """The 8192 x 2048 frame of test_verify_gpu.py (2^24 pixels): a chunk of the depth workspace holds 64 hypotheses, so 150 span three chunks."""
+    Wb, Hb = 8192, 2048
+    Kb = np.array([1200.0, 0, Wb / 2, 0, 1200.0, Hb / 2, 0, 0, 1], np.float32)
+    pj = api.compute_proj(Kb, Wb, Hb)
+    poses = synth.hypotheses(150, seed=9)
+    sc = api.render_host(model, synth.scene_pose()[None], Wb, Hb, pj)[0]
+    rng = np.random.default_rng(2)
+    sc = np.where(rng.random(sc.shape) < 0.1, 0, sc + rng.integers(-8, 9, sc.shape) * (sc > 0)).astype(np.int32)
+    sd = api.DeviceVector.from_host(sc.reshape(-1))
+    whole = api.score_normals(model, poses, Wb, Hb, pj, sd, 4, Kb, 2, 20, COS30)
+    parts = [api.score_normals(model, poses[i:i + 40], Wb, Hb, pj, sd, 4, Kb, 2, 20, COS30) for i in range(0, 150, 40)]
+    assert_scores_equal(whole[0], np.concatenate([p[0] for p in parts]))
+    assert_normals_equal(whole[1], np.concatenate([p[1] for p in parts]))
+    assert whole[0].tobytes() == api.score_poses(model, poses, Wb, Hb, pj, sd, 4).tobytes()
+    assert_identities(whole[1], whole[0])
+    assert (whole[0]["visible"] > 0).all() and (whole[1]["tested"][64:] > 0).any() and (whole[1]["tested"][128:] > 0).any()
+
+
+def test_batch_of_two_box_launches(gpu):
+    """32768 + 5 hypotheses in one depth chunk: the launches over their boxes are split in two (grid.y is limited), and the second starts at
+    its own records.  Every score and normal record is the reference's for its pose, the ones behind the split included; uint16 scene."""
+    c = launch_split_case()
+    poses = c["poses"][np.arange(c["P"]) % 8]
+    scene = np.ascontiguousarray(c["scene"].astype(np.uint16))
+    want = normals_ref(c["renders"], c["scene"], c["tau"], SPLIT_K, 1, c["jump"], COS30)
+    assert want["tested"].sum() > 0 and len(set(want["tested"].tolist())) > 4      # records that tell the poses apart
+    scores, got = api.score_normals(c["tris"], poses, c["W"], c["H"], c["proj"], scene, c["tau"], SPLIT_K, 1, c["jump"], COS30)
+    assert_records_repeat(got, want)
+    assert_records_repeat(scores, c["scores"])

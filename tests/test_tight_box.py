@@ -4,21 +4,15 @@ raster, tests/oracle_lib.py), must never leave the loose box everything is sized
 import numpy as np
 import pytest
 
+import box_stress
 import oracle_lib as O
+from box_stress import area, inside                                # (the helpers this file introduced live there now, for the frame size given)
 from pose_refine_amd import api, synth
 from gpu_common import random_mesh
 
 W, H = synth.WIDTH, synth.HEIGHT
 NONE = (0, 0, 0, 0)
 f32 = np.float32
-
-
-def area(b):
-    return max(int(b[2]) - int(b[0]) + 1, 0) * max(int(b[3]) - int(b[1]) + 1, 0)
-
-
-def inside(inner, outer):
-    return area(inner) == 0 or (inner[0] >= outer[0] and inner[1] >= outer[1] and inner[2] <= outer[2] and inner[3] <= outer[3])
 
 
 def shifted(pose, dx_mm):
@@ -28,34 +22,11 @@ def shifted(pose, dx_mm):
 
 
 def drawn_box(tris, pose, proj, roi=NONE):
-    """{x0, y0, x1, y1} in RASTER coordinates (row flipped back) of the pixels the oracle's raster draws, or None."""
-    img = O.render(tris, pose[None], W, H, proj, roi)[0]
-    rows, cols = np.nonzero(img)
-    if len(rows) == 0:
-        return None
-    rows = rows + (roi[1] if roi[2] > 0 and roi[3] > 0 else 0)
-    cols = cols + (roi[0] if roi[2] > 0 and roi[3] > 0 else 0)
-    return np.array([cols.min(), H - 1 - rows.max(), cols.max(), H - 1 - rows.min()])
+    return box_stress.drawn_box(tris, pose, proj, roi, W, H)
 
 
 def numpy_tight_box(tris, pose, proj, loose):
-    """vertex_to_screen / tight_pixel_box (csrc/pose_box.h) restated in float32 numpy, operation by operation."""
-    v = np.ascontiguousarray(tris, f32).reshape(-1, 3)
-    M, P = np.asarray(pose, f32).reshape(16), np.asarray(proj, f32).reshape(16)
-    x, y, z = v[:, 0], v[:, 1], v[:, 2]
-    lx = M[0] * x + M[1] * y + M[2] * z + M[3]
-    ly = M[4] * x + M[5] * y + M[6] * z + M[7]
-    lz = M[8] * x + M[9] * y + M[10] * z + M[11]
-    cx = P[0] * lx + P[1] * ly + P[2] * lz + P[3]
-    cy = P[4] * lx + P[5] * ly + P[6] * lz + P[7]
-    with np.errstate(all="ignore"):
-        px = cx / lz * f32(W) / f32(2) + f32(W) / f32(2)
-        py = cy / lz * f32(H) / f32(2) + f32(H) / f32(2)
-        bad = np.any(~(lz > f32(1e-3))) or np.any(~(np.abs(px) < f32(1e8))) or np.any(~(np.abs(py) < f32(1e8)))
-    if bad or len(v) == 0:
-        return np.asarray(loose)
-    return np.array([max(loose[0], int(np.floor(px.min())) - 2), max(loose[1], int(np.floor(py.min())) - 2),
-                     min(loose[2], int(np.ceil(px.max())) + 2), min(loose[3], int(np.ceil(py.max())) + 2)])
+    return box_stress.numpy_tight_box(tris, pose, proj, loose, W, H)
 
 
 @pytest.fixture(scope="module")

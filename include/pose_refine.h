@@ -781,6 +781,35 @@ int  pr_debug_mesh_fingerprint(const pr_triangle *tris_host, size_t n_tris, uint
  * for the host: a vertex at or behind the camera plane (z <= 1e-3) or a non-finite coordinate leaves the loose box. */
 int  pr_debug_tight_box(const pr_triangle *tris_host, size_t n_tris, const pr_mat4 *pose, const pr_mat4 *proj, uint32_t width, uint32_t height,
                         pr_roi roi, int32_t box_out[4], int32_t loose_out[4]);
+/* Audit entry: the bytes the kd-tree searches would read for `scene` -- the traversal data the library derives from the caller's nodes and
+ * points, copied to the host.  The scene is resolved exactly as an ICP call resolves it (the same cache sets, the same waiting for a batch
+ * in flight that reads a set about to be rebuilt, the same rounds of wide levels): a read neither rebuilds what a search would have
+ * reused nor the other way round.  cam_k = {fx, fy, cx, cy} with cam_w x cam_h is the camera of the pixel grid; cam_k == NULL: no grid is
+ * reported (grid_w = grid_h = 0).  Every member of `out` may be NULL (skipped), and so may `out` itself -- a first call that only fills
+ * `counts` tells how large the arrays have to be:
+ *   topo   n_nodes x int4     leaf {first point, end point, -1, w}, internal {split value bits, child1, child2, w}; w = (parent + 1) | dim << 30
+ *   bmin   n_nodes x float4   box minimum; .w = "size" of child1 (squared box diagonal, -1: a leaf).  bmax: the maximum, .w = size of child2
+ *   rec64  n_nodes x 64 bytes {topo.x, topo.y, topo.z, dim | 0}, then child1's and child2's boxes {min.xyz, max.xyz} x 2
+ *   rec32  n_nodes x 32 bytes {split | first point, child1 | dim << 30 (leaf: end point | 3 << 30), 12 x uint16 boxes in the frame info[2..7]}
+ *   desc   n_nodes x 8 bytes  the first two words of rec32
+ *   pts    n_points x float4  {x, y, z, 0}
+ *   info   24 words           [0] depth [1] rec32 usable [2..4] frame origin [5..7] frame scale [8] wide usable [9] wide nodes
+ *                             [16..18] wide frame origin [19] wide scale [20] wide frame admits the integer box test; the rest is the cache's
+ *   wide   n_wide x 128 bytes the wide nodes in the paired layout of the task walk (n_wide = info[9])
+ *   cell_idx  grid_w x grid_h x int32   point of a pixel, -1: none (with a camera only)
+ *   grid   grid_cells x float4          {x, y, z, point index bits}: the pixels, then the three coarser levels (with a camera only)
+ * grid_w = 0 also when the library builds no grid for this scene (no compact records, option nn_grid 0, more than 2^24 pixels);
+ * grid_usable = every point owns a cell: the grid's contents mean nothing otherwise.  A tree the searches refuse (links that do not form a
+ * tree) returns their error and writes nothing, `counts` included. */
+typedef struct {
+    uint32_t n_nodes, n_points, n_wide, grid_w, grid_h, grid_usable;
+    uint64_t grid_cells;
+} pr_nn_records_counts;
+typedef struct {
+    void *topo, *bmin, *bmax, *rec64, *rec32, *desc, *pts, *info, *wide, *cell_idx, *grid;
+} pr_nn_records_out;
+int  pr_debug_nn_records(const pr_scene_nn *scene, uint32_t cam_w, uint32_t cam_h, const float *cam_k, pr_nn_records_counts *counts,
+                         const pr_nn_records_out *out);
 /* Two things the library does silently for correctness, counted per context since it was created: asynchronous batches that
  * pr_refine_wait ran a SECOND time because the device-side checks found a stale model box, a triangle buffer whose content changed, or a scene array that no longer matches its
  * cached form (a caller who sees this grow writes to its buffers behind the library's back: pr_invalidate is the cheap cure), and timed

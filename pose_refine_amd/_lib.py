@@ -102,6 +102,20 @@ class SceneNNDesc(C.Structure):
                 ("cam_fx", C.c_float), ("cam_fy", C.c_float), ("cam_cx", C.c_float), ("cam_cy", C.c_float), ("cam_w", C.c_uint32), ("cam_h", C.c_uint32), ("cam_magic", C.c_uint32)]
 
 
+class NNRecordsCounts(C.Structure):
+    """pr_nn_records_counts: how many elements the arrays of pr_debug_nn_records hold."""
+    _fields_ = [("n_nodes", C.c_uint32), ("n_points", C.c_uint32), ("n_wide", C.c_uint32), ("grid_w", C.c_uint32), ("grid_h", C.c_uint32),
+                ("grid_usable", C.c_uint32), ("grid_cells", C.c_uint64)]
+
+
+NN_RECORDS_FIELDS = ("topo", "bmin", "bmax", "rec64", "rec32", "desc", "pts", "info", "wide", "cell_idx", "grid")
+
+
+class NNRecordsOut(C.Structure):
+    """pr_nn_records_out: host arrays pr_debug_nn_records fills (NULL: skipped)."""
+    _fields_ = [(f, C.c_void_p) for f in NN_RECORDS_FIELDS]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_cabi_symbols.py checks against the header
 _vp, _sz, _u32, _i32 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -196,6 +210,7 @@ SIGNATURES = {
     "pr_debug_mesh_order": (_i32, [_vp, _sz, _vp]),
     "pr_debug_mesh_fingerprint": (_i32, [_vp, _sz, C.POINTER(C.c_uint64)]),
     "pr_debug_tight_box": (_i32, [_vp, _sz, _vp, _vp, _u32, _u32, Roi, _vp, _vp]),
+    "pr_debug_nn_records": (_i32, [_vp, _u32, _u32, _vp, C.POINTER(NNRecordsCounts), C.POINTER(NNRecordsOut)]),
     "pr_stats": (_i32, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 

@@ -586,6 +586,32 @@ def trace_sums_off():
     _tls.trace_rows = None
 
 
+def debug_nn_records(scene: "Scene_nn", camera=None) -> dict:
+    """``pr_debug_nn_records``: the derived search data of a kd-tree scene as numpy arrays -- ``topo`` (n, 4) int32, ``bmin`` / ``bmax`` (n, 4)
+    float32, ``rec64`` (n, 16) float32, ``rec32`` (n, 8) uint32, ``desc`` (n, 2) uint32, ``pts`` (points, 4) float32, ``info`` (24,) uint32,
+    ``wide`` (info[9], 32) uint32 and, with ``camera`` = (w, h, fx, fy, cx, cy), ``cell_idx`` (h, w) int32 and ``grid`` (cells, 4) float32 --
+    plus ``counts`` (the ``pr_nn_records_counts`` fields).  Without a grid ``cell_idx`` and ``grid`` are None."""
+    d = scene.desc()
+    k = None
+    w = h = 0
+    if camera is not None:
+        w, h = int(camera[0]), int(camera[1])
+        k = np.array(camera[2:6], np.float32)
+    lib = _lib.load()
+    cnt = _lib.NNRecordsCounts()
+    check(lib.pr_debug_nn_records(C.addressof(d), w, h, ptr(k) if k is not None else None, C.byref(cnt), None))
+    n, m = cnt.n_nodes, cnt.n_points
+    arrs = {"topo": np.zeros((n, 4), np.int32), "bmin": np.zeros((n, 4), np.float32), "bmax": np.zeros((n, 4), np.float32),
+            "rec64": np.zeros((n, 16), np.float32), "rec32": np.zeros((n, 8), np.uint32), "desc": np.zeros((n, 2), np.uint32),
+            "pts": np.zeros((m, 4), np.float32), "info": np.zeros(24, np.uint32), "wide": np.zeros((cnt.n_wide, 32), np.uint32),
+            "cell_idx": np.zeros((cnt.grid_h, cnt.grid_w), np.int32) if cnt.grid_w else None,
+            "grid": np.zeros((cnt.grid_cells, 4), np.float32) if cnt.grid_w else None}
+    out = _lib.NNRecordsOut(*[(ptr(arrs[f]) if arrs[f] is not None and arrs[f].size else None) for f in _lib.NN_RECORDS_FIELDS])
+    check(lib.pr_debug_nn_records(C.addressof(d), w, h, ptr(k) if k is not None else None, C.byref(cnt), C.byref(out)))
+    arrs["counts"] = {f: int(getattr(cnt, f)) for f, _ in _lib.NNRecordsCounts._fields_}
+    return arrs
+
+
 def refine_batch(tris, poses, width: int, height: int, proj, K, scene,
                  criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(), results_dev: Optional[int] = None,
                  roi: Optional[Sequence[int]] = None):

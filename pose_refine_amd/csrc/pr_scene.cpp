@@ -297,6 +297,41 @@ int pr_scene_nn_prepare_dev(const void *depth_dev, int depth_is_i32, const float
                                             pcd_dev_out, normal_dev_out, nodes_dev_out, cap_nodes, n_points, n_nodes);
 }
 
+// Audit entry: the derived search data of a kd-tree scene, as make_scene hands it to the searches (SceneSel::nn) and keeps it (the picked
+// NNDerived), copied to the host.  make_scene is the only build path: whatever it reuses, rebuilds or waits for, it does here too.
+int pr_debug_nn_records(const pr_scene_nn *scene, uint32_t cam_w, uint32_t cam_h, const float *cam_k, pr_nn_records_counts *counts,
+                        const pr_nn_records_out *out)
+{
+    PR_ENTER();
+    if (!scene) { set_error("pr_debug_nn_records: null scene"); return PR_ERR_INVALID; }
+    if (cam_k && (cam_w == 0 || cam_h == 0)) { set_error("pr_debug_nn_records: a camera of %u x %u pixels", cam_w, cam_h); return PR_ERR_INVALID; }
+    Camera cam{ cam_w, cam_h, cam_k ? cam_k[0] : 0.0f, cam_k ? cam_k[1] : 0.0f, cam_k ? cam_k[2] : 0.0f, cam_k ? cam_k[3] : 0.0f };
+    SceneSel sc;
+    std::memset(static_cast<void *>(&sc), 0, sizeof sc);
+    PR_TRY(make_scene(PR_SCENE_NN, scene, false, sc, nullptr, nullptr, cam_k ? &cam : nullptr));
+    const NNDerived &nc = g->nn_sets[sc.nn_set];
+    const prk::SceneNNDev &nn = sc.nn;
+    const size_t n_nodes = nc.n_nodes, n_points = nc.n_points;
+    const size_t n_wide = std::min<size_t>(nc.info[9], prk::nn_wide_capacity(nc.n_nodes));
+    // the grid of THIS camera (without one make_scene may still have built the grid of the scene's own hint: not what was asked for)
+    const bool grid = cam_k && nc.grid_valid && nc.gw == cam_w && nc.gh == cam_h && std::memcmp(nc.gk, cam_k, sizeof nc.gk) == 0 && nc.nn_cells.p && nc.nn_grid.p;
+    const size_t cells = grid ? (size_t)cam_w * cam_h : 0, grid_cells = grid ? prk::nn_grid_cells(cam_w, cam_h) : 0;
+    if (counts) *counts = pr_nn_records_counts{ nc.n_nodes, nc.n_points, (uint32_t)n_wide, grid ? cam_w : 0u, grid ? cam_h : 0u, (grid && nc.grid_usable) ? 1u : 0u, grid_cells };
+    if (!out) return PR_OK;
+    const struct { void *dst; const void *src; size_t bytes; } copies[] = {
+        { out->topo, nn.topo, n_nodes * sizeof(int4) }, { out->bmin, nn.bmin, n_nodes * sizeof(float4) }, { out->bmax, nn.bmax, n_nodes * sizeof(float4) },
+        { out->rec64, nn.rec, n_nodes * 4 * sizeof(float4) }, { out->rec32, nc.nnrec32.p, n_nodes * 2 * sizeof(uint4) }, { out->desc, nn.desc, n_nodes * sizeof(uint2) },
+        { out->pts, nn.pts, n_points * sizeof(float4) }, { out->wide, nc.nnwide.p, n_wide * 128 },
+        { out->cell_idx, nc.nn_cells.p, cells * sizeof(int32_t) }, { out->grid, nc.nn_grid.p, grid_cells * sizeof(float4) } };
+    hipError_t e = hipSuccess;
+    for (const auto &c : copies)
+        if (e == hipSuccess && c.dst && c.src && c.bytes) e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("pr_debug_nn_records: %s", hipGetErrorString(e)); return PR_ERR_HIP; }
+    if (out->info) std::memcpy(out->info, nc.info, sizeof nc.info);   // (the host's copy: what make_scene itself decides on)
+    return PR_OK;
+}
+
 int pr_raw2depth_mask(const int32_t *raw_dev, size_t count, uint16_t *depth_host_out, uint8_t *mask_host_out)
 {
     PR_ENTER();

@@ -115,6 +115,34 @@ typedef struct {
 #define PR_SCENE_PROJ      0
 #define PR_SCENE_NN        1
 #define PR_SCENE_PROJ_CROP 2      /* scene argument is a pr_scene_proj_crop */
+#define PR_SCENE_GRID      3      /* scene argument is a pr_scene_grid */
+
+/* Closest-point grid (no counterpart in the reference): a voxel field over the scene's volume whose every cell holds the index of the scene
+ * point nearest to the cell's CENTRE -- built once per frame with the exact kd-tree search, after which a nearest-neighbour query of the ICP
+ * is arithmetic, one 4-byte gather and one record gather.  All arithmetic below is float32 without contraction.
+ *   cell of a point p, per axis a:  f = (p[a] - origin[a]) * inv_cell;  inside iff f >= 0.0f && f < (float)dim[a] (NaN, +-inf fail);
+ *                                   i[a] = (int)f;  index = i[0] + dim[0] * (i[1] + dim[1] * i[2])
+ *   centre of a cell:               origin[a] + ((float)i[a] + 0.5f) * cell
+ *   build:  cell_point[index] = a k that minimises ((dx*dx + dy*dy) + dz*dz) between the centre and pcd[k] (pcd_scene.h:87-90; any k of a tie;
+ *           the same inputs give the same bytes), or PR_GRID_NONE unless that minimum is < reach * reach
+ *   query:  a point outside the grid or in a PR_GRID_NONE cell has no correspondence; else w = cell_point[index], (d, n) = rec[w], valid iff
+ *           ((ex*ex + ey*ey) + ez*ez) < max_dist_diff * max_dist_diff with e = d - p; it then contributes like any other scene's correspondence
+ *   bound:  with h = (sqrt(3) / 2) * cell, the point returned for a query inside the grid is at most 2 h farther away than the true nearest
+ *           one, provided the centre's nearest point was within reach; with reach >= max_dist_diff + h no query with a true neighbour within
+ *           max_dist_diff - h lands in a PR_GRID_NONE cell */
+#define PR_GRID_NONE         0xFFFFFFFFu
+#define PR_GRID_MAX_CELLS    (1u << 26)          /* 256 MB of indices */
+typedef struct {
+    float    origin[3];      /* corner of cell (0,0,0), metres, camera frame */
+    float    cell;           /* edge length, > 0, finite */
+    float    inv_cell;       /* 1.0f / cell, computed ONCE by pr_scene_grid_describe in float32; device and references read it, never recompute it */
+    uint32_t dim[3];         /* each >= 1, product <= PR_GRID_MAX_CELLS */
+    float    max_dist_diff;  /* acceptance radius of a correspondence, as Scene_nn (pcd_scene.h:127) */
+    float    reach;          /* a cell whose centre is not nearer than this to any scene point holds PR_GRID_NONE */
+    uint32_t n_points;
+    const uint32_t *cell_point;   /* dev, dim[0]*dim[1]*dim[2], x fastest */
+    const float    *rec;          /* dev, n_points * 8 floats: {px,py,pz,0, nx,ny,nz,0}, written by the build */
+} pr_scene_grid;
 
 /* where the 6x6 solve of every ICP iteration runs (icp.cu:207 does it on the host) */
 #define PR_SOLVE_HOST   0
@@ -188,6 +216,14 @@ int pr_kdtree_build_dev(pr_vec3 *pcd_dev, pr_vec3 *normal_dev, size_t n_points, 
 int pr_scene_nn_prepare_dev(const void *depth_dev, int depth_is_i32, const float K[9], int width, int height, int max_leaf,
                             pr_vec3 *pcd_dev_out, pr_vec3 *normal_dev_out, pr_kdnode *nodes_dev_out, size_t cap_nodes,
                             uint32_t *n_points, uint32_t *n_nodes);
+/* Closest-point grid over the box [lo, hi]: origin = lo, dim[a] = the cells of edge `cell` needed to cover hi[a] - lo[a] (at least 1), inv_cell,
+ * the two radii; the pointers and n_points are left null / 0 for the build.  Pure host code.  PR_ERR_INVALID: a cell, radius or corner that is
+ * not finite (cell, radii: not positive), hi < lo on an axis, a dim beyond 32 bits or more than PR_GRID_MAX_CELLS cells. */
+int pr_scene_grid_describe(const float lo[3], const float hi[3], float cell, float max_dist_diff, float reach, pr_scene_grid *out);
+/* The build: cell_point_dev (dim[0]*dim[1]*dim[2] words) from the exact search of `scene`'s kd-tree, rec_dev (8 floats per scene point) from its
+ * points and normals; sets grid->cell_point, grid->rec and grid->n_points.  The buffers are the caller's and nothing derived from them is
+ * cached by address: a grid rebuilt in place needs no pr_invalidate. */
+int pr_scene_grid_build_dev(const pr_scene_nn *scene, pr_scene_grid *grid, uint32_t *cell_point_dev, float *rec_dev);
 /* eigen_slover_666 icp.cpp:29-45 (public in icp.h:54) */
 void pr_solve_666(const float A[36], const float b[6], pr_mat4 *T_out);
 /* Mat4x4f * Mat4x4f geometry.h:292-298 (entries summed over k = 3,2,1,0): what `result.transformation_ = extrinsic * result.transformation_`
@@ -218,6 +254,7 @@ int pr_depth2cloud_u16(const uint16_t *depth_dev, uint32_t width, uint32_t heigh
 /* One cloud: mutates cloud_dev in place exactly like the reference. */
 int pr_icp_proj(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_proj *scene, pr_criteria crit, pr_result *result_out);
 int pr_icp_nn(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_nn *scene, pr_criteria crit, pr_result *result_out);
+int pr_icp_grid(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_grid *scene, pr_criteria crit, pr_result *result_out);
 /* Many clouds against one scene in one launch per iteration (what the reference needs P host
  * threads + cudaStreamPerThread for, README.md:15): cloud i = clouds_dev[offsets[i] .. offsets[i+1]). */
 int pr_icp_batch(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind,

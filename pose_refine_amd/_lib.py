@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("PR_LIB_PATH") or os.path.join(_HERE, "lib", "libpose_
 
 PR_OK = 0
 PR_ERR_NO_DEVICE, PR_ERR_HIP, PR_ERR_INVALID, PR_ERR_IO, PR_ERR_NOMEM, PR_ERR_COMM = -1, -2, -3, -4, -5, -6
-SCENE_PROJ, SCENE_NN, SCENE_PROJ_CROP = 0, 1, 2
+SCENE_PROJ, SCENE_NN, SCENE_PROJ_CROP, SCENE_GRID = 0, 1, 2, 3
+GRID_NONE, GRID_MAX_CELLS = 0xFFFFFFFF, 1 << 26          # PR_GRID_NONE, PR_GRID_MAX_CELLS
 COMM_ID_BYTES = 128
 SOLVE_HOST, SOLVE_DEVICE = 0, 1
 
@@ -102,6 +103,12 @@ class SceneNNDesc(C.Structure):
                 ("cam_fx", C.c_float), ("cam_fy", C.c_float), ("cam_cx", C.c_float), ("cam_cy", C.c_float), ("cam_w", C.c_uint32), ("cam_h", C.c_uint32), ("cam_magic", C.c_uint32)]
 
 
+class SceneGridDesc(C.Structure):
+    """pr_scene_grid: a closest-point grid over the scene's volume (pr_scene_grid_describe fills the geometry, pr_scene_grid_build_dev the arrays)."""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("inv_cell", C.c_float), ("dim", C.c_uint32 * 3), ("max_dist_diff", C.c_float),
+                ("reach", C.c_float), ("n_points", C.c_uint32), ("cell_point", C.c_void_p), ("rec", C.c_void_p)]
+
+
 class NNRecordsCounts(C.Structure):
     """pr_nn_records_counts: how many elements the arrays of pr_debug_nn_records hold."""
     _fields_ = [("n_nodes", C.c_uint32), ("n_points", C.c_uint32), ("n_wide", C.c_uint32), ("grid_w", C.c_uint32), ("grid_h", C.c_uint32),
@@ -157,6 +164,9 @@ SIGNATURES = {
     "pr_depth2cloud_u16": (_i32, [_vp, _u32, _u32, _vp, _u32, _u32, _u32, C.POINTER(_vp), C.POINTER(_u32)]),
     "pr_icp_proj": (_i32, [_vp, _u32, _vp, Criteria, _vp]),
     "pr_icp_nn": (_i32, [_vp, _u32, _vp, Criteria, _vp]),
+    "pr_icp_grid": (_i32, [_vp, _u32, _vp, Criteria, _vp]),
+    "pr_scene_grid_describe": (_i32, [_vp, _vp, C.c_float, C.c_float, C.c_float, _vp]),
+    "pr_scene_grid_build_dev": (_i32, [_vp, _vp, _vp, _vp]),
     "pr_icp_batch": (_i32, [_vp, _vp, _u32, _i32, _vp, Criteria, _vp]),
     "pr_refine_batch": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp]),
     "pr_refine_batch_dev": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp]),

@@ -24,8 +24,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
-                   PoseRefineError, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+                   PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
 def _f32(a, shape=None):
@@ -513,6 +513,77 @@ class Scene_nn:
                            _lib.SCENE_NN_CAM_MAGIC if cam[4] else 0)
 
 
+class Scene_grid:
+    """Closest-point grid of a ``Scene_nn`` (``pr_scene_grid``; no counterpart in the reference): every cell of a voxel field over the scene's
+    volume holds the scene point nearest to its centre, found once by the exact kd-tree search; an ICP query is then one lookup.  The returned
+    point is at most ``sqrt(3) * cell`` farther away than the true nearest one.  Owns its two device buffers; accepted wherever ``Scene_nn`` is."""
+
+    kind = SCENE_GRID
+
+    def __init__(self):
+        self._desc = SceneGridDesc()
+        self.cell_buffer = self.rec_buffer = None
+        self.max_dist_diff = 0.0
+
+    @classmethod
+    def from_scene_nn(cls, scene_nn: "Scene_nn", cell: float, reach: Optional[float] = None, lo=None, hi=None, margin: Optional[float] = None) -> "Scene_grid":
+        """Box: ``lo`` / ``hi`` (each defaults to the scene points' bounding box grown by ``margin``, default ``max_dist_diff``), shrunk about its
+        centre, with a warning, if it would hold more than ``GRID_MAX_CELLS`` cells.  ``reach`` defaults to ``max_dist_diff + (sqrt(3) / 2) * cell``:
+        no query with a true neighbour inside ``max_dist_diff - (sqrt(3) / 2) * cell`` then lands in an empty cell."""
+        nn = scene_nn.desc()
+        mdd = float(scene_nn.max_dist_diff)
+        cell = float(cell)
+        if not (cell > 0.0 and np.isfinite(cell)):
+            raise ValueError("cell must be finite and positive")
+        if lo is None or hi is None:
+            pts = scene_nn.pcd_host if scene_nn.pcd_host is not None else scene_nn.pcd_buffer.to_host()[:nn.n_points * 3].reshape(-1, 3)
+            if len(pts) == 0:
+                raise ValueError("the scene has no points")
+            m = mdd if margin is None else float(margin)
+            lo = pts.min(axis=0).astype(np.float64) - m if lo is None else lo
+            hi = pts.max(axis=0).astype(np.float64) + m if hi is None else hi
+        lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+        cells = lambda a, b: float(np.prod(np.floor((b - a) / cell) + 1.0))
+        if np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(hi >= lo) and cells(lo, hi) > _lib.GRID_MAX_CELLS:
+            import warnings
+            want = cells(lo, hi)
+            while cells(lo, hi) > _lib.GRID_MAX_CELLS:
+                c, half = (lo + hi) / 2, (hi - lo) / 2 * 0.98
+                lo, hi = c - half, c + half
+            warnings.warn(f"Scene_grid: a box of {want:.3g} cells of {cell} m exceeds GRID_MAX_CELLS = {_lib.GRID_MAX_CELLS}; shrunk about its centre to "
+                          f"{lo.tolist()} .. {hi.tolist()}", RuntimeWarning, stacklevel=2)
+        out = cls()
+        out.max_dist_diff = mdd
+        r = mdd + 0.5 * np.sqrt(3.0) * cell if reach is None else float(reach)
+        lo32, hi32 = _f32(lo, -1), _f32(hi, -1)
+        check(_lib.load().pr_scene_grid_describe(ptr(lo32), ptr(hi32), cell, mdd, r, C.addressof(out._desc)))
+        d = out._desc
+        out.cell_buffer = DeviceVector(int(d.dim[0]) * int(d.dim[1]) * int(d.dim[2]), np.uint32)
+        out.rec_buffer = DeviceVector(int(nn.n_points) * 8, np.float32)
+        check(_lib.load().pr_scene_grid_build_dev(C.addressof(nn), C.addressof(d), out.cell_buffer.data(), out.rec_buffer.data()))
+        return out
+
+    def desc(self) -> SceneGridDesc:
+        return self._desc
+
+    @property
+    def dim(self):
+        return tuple(int(v) for v in self._desc.dim)
+
+    def cell_points(self) -> np.ndarray:
+        """The cells' scene-point indices as a (dim z, dim y, dim x) array (x fastest), ``GRID_NONE`` where a cell is empty."""
+        dx, dy, dz = self.dim
+        return self.cell_buffer.to_host().reshape(dz, dy, dx)
+
+    def records(self) -> np.ndarray:
+        """The (n_points, 8) records {px, py, pz, 0, nx, ny, nz, 0} the build wrote."""
+        return self.rec_buffer.to_host().reshape(-1, 8)
+
+    @property
+    def nbytes(self) -> int:
+        return self.cell_buffer.size() * 4 + self.rec_buffer.size() * 4
+
+
 def ICP_Point2Plane(model_pcd: DeviceVector, scene, criteria: ICPConvergenceCriteria = ICPConvergenceCriteria()) -> RegistrationResult:
     """``cuda_icp::ICP_Point2Plane_cuda<Scene>`` (icp.cu:156-223).  Mutates ``model_pcd`` in place."""
     res = np.zeros(1, RESULT)
@@ -521,7 +592,7 @@ def ICP_Point2Plane(model_pcd: DeviceVector, scene, criteria: ICPConvergenceCrit
         off = np.array([0, model_pcd.size() // 3], np.uint32)
         check(_lib.load().pr_icp_batch(model_pcd.data(), ptr(off), 1, scene.kind, C.addressof(d), criteria.c(), ptr(res)))
         return RegistrationResult.from_record(res[0])
-    fn = _lib.load().pr_icp_nn if scene.kind == SCENE_NN else _lib.load().pr_icp_proj
+    fn = _lib.load().pr_icp_nn if scene.kind == SCENE_NN else _lib.load().pr_icp_grid if scene.kind == SCENE_GRID else _lib.load().pr_icp_proj
     check(fn(model_pcd.data(), model_pcd.size() // 3, C.addressof(d), criteria.c(), ptr(res)))
     return RegistrationResult.from_record(res[0])
 

@@ -17,6 +17,7 @@ hipError_t launch_pass(const prk::IcpBatch &b, const SceneSel &sc, uint32_t P, h
         }
         return prk::launch_icp_pass_nn(b, sc.nn, P, st);
     }
+    if (sc.kind == PR_SCENE_GRID) return prk::launch_icp_pass_grid(b, sc.grid, P, st);
     if (sc.packed) return prk::launch_icp_pass_proj_packed(b, sc.pk, P, st);
     return prk::launch_icp_pass_proj_aos(b, sc.aos, P, st);
 }
@@ -403,6 +404,12 @@ int pr_icp_nn(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_nn *scene, p
     return pr_icp_batch(cloud_dev, off, 1, PR_SCENE_NN, scene, crit, result_out);
 }
 
+int pr_icp_grid(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_grid *scene, pr_criteria crit, pr_result *result_out)
+{
+    const uint32_t off[2] = { 0, n_points };
+    return pr_icp_batch(cloud_dev, off, 1, PR_SCENE_GRID, scene, crit, result_out);
+}
+
 // Audit entry: the 29 sums of every pass of the calling thread's NEXT synchronous ICP call (pr_icp_batch / pr_icp_proj / pr_icp_nn / pr_refine_batch[_roi]), as
 // the host-solve loop received them -- solve_one copies the row of hypothesis i at iteration it to rows_host[(it * n_hyp + i) * 29 ..] right before
 // pose_iteration_host consumes it, whichever way the sums came (pinned-memory stores of the pass tail, finalize launch + copy, flag polling or stream
@@ -430,7 +437,8 @@ int pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, co
     DevBuf out;
     PR_TRY(out.ensure(sizeof(float) * 29 * (size_t)n_points));
     hipError_t e;
-    if (sc.kind == PR_SCENE_NN) e = prk::launch_contrib29_nn(cloud_dev, n_points, update16, sc.nn, out.as<float>(), g->stream);
+    if (sc.kind == PR_SCENE_GRID) e = prk::launch_contrib29_grid(cloud_dev, n_points, update16, sc.grid, out.as<float>(), g->stream);
+    else if (sc.kind == PR_SCENE_NN) e = prk::launch_contrib29_nn(cloud_dev, n_points, update16, sc.nn, out.as<float>(), g->stream);
     else if (sc.packed) e = prk::launch_contrib29_proj_packed(cloud_dev, n_points, update16, sc.pk, out.as<float>(), g->stream);
     else e = prk::launch_contrib29_proj_aos(cloud_dev, n_points, update16, sc.aos, out.as<float>(), g->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(contrib_host, out.p, sizeof(float) * 29 * (size_t)n_points, hipMemcpyDeviceToHost, g->stream);

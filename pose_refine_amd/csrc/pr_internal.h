@@ -127,6 +127,15 @@ struct SceneNNWinners {
     const uint32_t *winner;     // per cloud point (same indexing as IcpBatch::cloud): scene index or 0xffffffff
 };
 
+// closest-point grid scene (pr_scene_grid, include/pose_refine.h) as the kernels of grid_scene.hip take it
+struct SceneGridDev {
+    float origin[3], cell, inv_cell;
+    uint32_t dim[3];
+    float max_dist_diff;
+    const uint32_t *cell_point; // per cell (x fastest): scene point nearest to the cell's centre, or PR_GRID_NONE
+    const float4 *rec;          // per scene point: {px, py, pz, 0}, {nx, ny, nz, 0}
+};
+
 // device-side solver state for PR_SOLVE_DEVICE (one record per hypothesis)
 struct DevIcpState {
     float T[16];
@@ -306,6 +315,11 @@ hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t 
 // marks (or null): three events recorded after the search, the bound and the walk kernel (timed batches; n_poses <= 32768)
 hipError_t launch_nn_search(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, uint32_t max_points, uint32_t run, hipStream_t s, hipEvent_t *marks = nullptr);
 hipError_t launch_icp_pass_nn_winners(const IcpBatch &b, const SceneNNWinners &sc, uint32_t n_poses, hipStream_t s);
+// grid_scene.hip: the closest-point grid's pass, its build (cell_point: every cell written; `tree`: the scene's kd-tree as make_scene derives it) and its audit entry
+hipError_t launch_icp_pass_grid(const IcpBatch &b, const SceneGridDev &sc, uint32_t n_poses, hipStream_t s);
+hipError_t launch_grid_build(const SceneNNDev &tree, float reach, const SceneGridDev &grid, uint32_t *cell_point, hipStream_t s);
+hipError_t launch_grid_records(const pr_vec3 *pcd, const pr_vec3 *normal, uint32_t n, float4 *rec, hipStream_t s);
+hipError_t launch_contrib29_grid(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneGridDev &sc, float *out, hipStream_t s);
 // audit entry (icp_debug.hip): the 29 terms of every point of one cloud, out[n][29]; update12 (rows 0..2 of a 4x4) or null is applied first
 hipError_t launch_contrib29_proj_aos(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjAoS &sc, float *out, hipStream_t s);
 hipError_t launch_contrib29_proj_packed(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjPacked &sc, float *out, hipStream_t s);

@@ -766,6 +766,8 @@ void drain_slots_reading(const void *p, size_t bytes)
         if (r.scene_kind == PR_SCENE_NN)
             reads = reads || hit(r.sn.pcd, (size_t)r.sn.n_points * sizeof(pr_vec3)) || hit(r.sn.normal, (size_t)r.sn.n_points * sizeof(pr_vec3)) ||
                     hit(r.sn.nodes, (size_t)r.sn.n_nodes * sizeof(pr_kdnode));
+        else if (r.scene_kind == PR_SCENE_GRID)
+            reads = reads || hit(r.sg.cell_point, (size_t)r.sg.dim[0] * r.sg.dim[1] * r.sg.dim[2] * sizeof(uint32_t)) || hit(r.sg.rec, (size_t)r.sg.n_points * 8 * sizeof(float));
         else {
             const size_t n = (size_t)r.sp.view.width * r.sp.view.height;
             reads = reads || hit(r.sp.view.pcd, n * sizeof(pr_vec3)) || hit(r.sp.view.normal, n * sizeof(pr_vec3));
@@ -1250,6 +1252,7 @@ int refine_submit(Slot &sl, const RefineJob &job, const pr_mat4 *poses_host, uin
     const bool sample_call = (opt.profile == 2) && (g->sample_clock % period == 0);
     // (an instrumented kd-tree run stays synchronous; large frames: the asynchronous path sizes its sub-batches to its workspace bound)
     const bool async_ok = P > 0 && opt.solve_mode == PR_SOLVE_DEVICE && opt.raster_mode == 0 && (job.scene_kind != PR_SCENE_NN || !opt.nn_count)
+                          && job.scene_kind != PR_SCENE_GRID      // (a grid scene takes the synchronous route: its bytes are pr_refine_batch's by construction)
                           && (opt.profile == 0 || opt.profile == 3 || (opt.profile == 2 && !sample_call));
     if (!async_ok && P > 0 && opt.solve_mode == PR_SOLVE_HOST && opt.host_worker && opt.profile == 0 && !opt.nn_count && !tl_sums_trace.active.rows) {   // (a traced batch runs on the thread that armed the recorder)
         // host solve, nothing to time: the batch goes to the slot's helper thread (see SlotWorker) and this call returns

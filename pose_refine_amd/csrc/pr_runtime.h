@@ -198,27 +198,52 @@ inline bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
     }
     return true;
 }
+// A closest-point grid as a caller hands it over: every check that needs no device (make_job, make_scene, pr_scene_grid_build_dev; `built` = with the
+// arrays the build fills in).  No HIP call in here.
+inline int grid_desc_ok(const char *fn, const pr_scene_grid *gs, bool built)
+{
+    if (!gs) { set_error("%s: null pr_scene_grid", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(gs->cell) || !(gs->cell > 0.0f)) { set_error("%s: pr_scene_grid: cell must be finite and positive (got %g)", fn, (double)gs->cell); return PR_ERR_INVALID; }
+    if (!(gs->inv_cell == 1.0f / gs->cell)) { set_error("%s: pr_scene_grid: inv_cell is not 1.0f / cell (pr_scene_grid_describe computes it)", fn); return PR_ERR_INVALID; }
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(gs->origin[a])) { set_error("%s: pr_scene_grid: origin[%d] is not finite", fn, a); return PR_ERR_INVALID; }
+    uint64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (gs->dim[a] == 0 || gs->dim[a] > PR_GRID_MAX_CELLS) { set_error("%s: pr_scene_grid: dim[%d] = %u (1 .. PR_GRID_MAX_CELLS)", fn, a, gs->dim[a]); return PR_ERR_INVALID; }
+        cells *= gs->dim[a];
+        if (cells > PR_GRID_MAX_CELLS) { set_error("%s: pr_scene_grid: more than PR_GRID_MAX_CELLS = %u cells", fn, (uint32_t)PR_GRID_MAX_CELLS); return PR_ERR_INVALID; }
+    }
+    if (!std::isfinite(gs->max_dist_diff) || !(gs->max_dist_diff > 0.0f) || !std::isfinite(gs->reach) || !(gs->reach > 0.0f)) {
+        set_error("%s: pr_scene_grid: max_dist_diff and reach must be finite and positive (got %g, %g)", fn, (double)gs->max_dist_diff, (double)gs->reach); return PR_ERR_INVALID;
+    }
+    if (built) {
+        if (!gs->cell_point || !gs->rec) { set_error("%s: pr_scene_grid: cell_point or rec is null (pr_scene_grid_build_dev sets them)", fn); return PR_ERR_INVALID; }
+        if (gs->n_points == 0 || gs->n_points >= (1u << 27)) { set_error("%s: pr_scene_grid: n_points must be 1 .. 2^27 - 1 (got %u)", fn, gs->n_points); return PR_ERR_INVALID; }
+    }
+    return PR_OK;
+}
 struct MeshPlan;                     // the hypotheses of a mixed batch grouped by mesh (pr_refine.cpp)
 struct RefineJob {
     const pr_triangle *tris = nullptr; size_t n_tris = 0;        // one mesh for every hypothesis ...
     const MeshPlan *plan = nullptr;                              // ... or a mixed batch in its plan's order (synchronous calls only: the plan lives on the entry point's stack)
     uint32_t W = 0, H = 0; pr_mat4 proj{}; float K[9] = { 0 };
-    int scene_kind = 0; pr_scene_proj_crop sp{}; pr_scene_nn sn{}; pr_criteria crit{}; pr_roi roi{ 0, 0, 0, 0 };
+    int scene_kind = 0; pr_scene_proj_crop sp{}; pr_scene_nn sn{}; pr_scene_grid sg{}; pr_criteria crit{}; pr_roi roi{ 0, 0, 0, 0 };
     pr_result *results_dev = nullptr;
-    const void *scene() const { return scene_kind == PR_SCENE_NN ? static_cast<const void *>(&sn) : &sp; }   // as make_scene takes it (a crop starts with the plain view)
+    const void *scene() const { return scene_kind == PR_SCENE_NN ? static_cast<const void *>(&sn) : scene_kind == PR_SCENE_GRID ? static_cast<const void *>(&sg) : &sp; }   // as make_scene takes it (a crop starts with the plain view)
 };
 // ... from the C arguments, with every check that needs no device.  No HIP call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.
 inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, uint32_t W, uint32_t H, const pr_mat4 *proj, const float K[9], int scene_kind,
                     const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_dev, RefineJob &job)
 {
     if ((!tris_dev && n_tris > 0) || !proj || !K || !scene || W == 0 || H == 0) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }   // (an empty model has no array)
-    if (scene_kind != PR_SCENE_NN && scene_kind != PR_SCENE_PROJ && scene_kind != PR_SCENE_PROJ_CROP) { set_error("unknown scene kind %d", scene_kind); return PR_ERR_INVALID; }
+    if (scene_kind != PR_SCENE_NN && scene_kind != PR_SCENE_PROJ && scene_kind != PR_SCENE_PROJ_CROP && scene_kind != PR_SCENE_GRID) { set_error("unknown scene kind %d", scene_kind); return PR_ERR_INVALID; }
+    if (scene_kind == PR_SCENE_GRID) PR_TRY(grid_desc_ok(fn, static_cast<const pr_scene_grid *>(scene), /*built=*/true));
     if (!frame_size_ok(W, H) || !roi_ok(roi, W, H)) return PR_ERR_INVALID;
     if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
     job = RefineJob();
     job.tris = tris_dev; job.n_tris = n_tris; job.W = W; job.H = H; job.proj = *proj; std::memcpy(job.K, K, sizeof job.K);
     job.scene_kind = scene_kind; job.crit = crit; job.roi = roi; job.results_dev = results_dev;
     if (scene_kind == PR_SCENE_NN) job.sn = *static_cast<const pr_scene_nn *>(scene);
+    else if (scene_kind == PR_SCENE_GRID) job.sg = *static_cast<const pr_scene_grid *>(scene);
     else if (scene_kind == PR_SCENE_PROJ_CROP) job.sp = *static_cast<const pr_scene_proj_crop *>(scene);
     else job.sp.view = *static_cast<const pr_scene_proj *>(scene);     // (a plain projective scene: a crop at 0, 0)
     return PR_OK;
@@ -649,6 +674,7 @@ struct SceneSel {
     prk::SceneProjAoS aos{};
     prk::SceneProjPacked pk{};
     prk::SceneNNDev nn{};
+    prk::SceneGridDev grid{};        // closest-point grid (kind PR_SCENE_GRID): the caller's arrays as they are, nothing derived, nothing cached
     uint32_t nn_split = 0;           // kd-tree scene: search kernel + winners pass instead of the fused search pass
     uint32_t nn_max_points = 0;      // largest cloud of the batch (grid of the search kernel)
     int nn_set = -1;                 // kd-tree scene: which of Ctx::nn_sets the records are in

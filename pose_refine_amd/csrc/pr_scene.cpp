@@ -199,6 +199,14 @@ int make_scene(int kind, const void *scene, bool want_packed, SceneSel &out, Pac
         }
         return PR_OK;
     }
+    if (kind == PR_SCENE_GRID) {
+        // the caller's two arrays as they are: nothing is derived from them and nothing is kept by address
+        const pr_scene_grid *s = static_cast<const pr_scene_grid *>(scene);
+        PR_TRY(grid_desc_ok("pr_scene_grid", s, /*built=*/true));
+        out.grid = prk::SceneGridDev{ { s->origin[0], s->origin[1], s->origin[2] }, s->cell, s->inv_cell, { s->dim[0], s->dim[1], s->dim[2] }, s->max_dist_diff,
+                                      s->cell_point, reinterpret_cast<const float4 *>(s->rec) };
+        return PR_OK;
+    }
     set_error("unknown scene kind %d", kind);
     return PR_ERR_INVALID;
 }
@@ -295,6 +303,60 @@ int pr_scene_nn_prepare_dev(const void *depth_dev, int depth_is_i32, const float
                                                              pcd_dev_out, normal_dev_out, nodes_dev_out, cap_nodes, n_points, n_nodes);
     return scene_nn_prepare_dev_t<uint16_t>(static_cast<const uint16_t *>(depth_dev), K, (uint32_t)width, (uint32_t)height, max_leaf,
                                             pcd_dev_out, normal_dev_out, nodes_dev_out, cap_nodes, n_points, n_nodes);
+}
+
+// pr_scene_grid over the box [lo, hi]: pure host code.  dim[a] = floor((hi[a] - lo[a]) * inv_cell) + 1 in float32, so that hi itself -- and with it the
+// whole box -- lies inside the grid (a point is inside iff (p - origin) * inv_cell < dim), and lo == hi gives one cell.
+int pr_scene_grid_describe(const float lo[3], const float hi[3], float cell, float max_dist_diff, float reach, pr_scene_grid *out)
+{
+    const char *fn = "pr_scene_grid_describe";
+    if (!lo || !hi || !out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(cell) || !(cell > 0.0f)) { set_error("%s: cell must be finite and positive (got %g)", fn, (double)cell); return PR_ERR_INVALID; }
+    const float inv_cell = 1.0f / cell;
+    if (!std::isfinite(inv_cell) || !(inv_cell > 0.0f)) { set_error("%s: 1 / cell is not a positive finite float (cell %g)", fn, (double)cell); return PR_ERR_INVALID; }
+    if (!std::isfinite(max_dist_diff) || !(max_dist_diff > 0.0f) || !std::isfinite(reach) || !(reach > 0.0f)) {
+        set_error("%s: max_dist_diff and reach must be finite and positive (got %g, %g)", fn, (double)max_dist_diff, (double)reach); return PR_ERR_INVALID;
+    }
+    pr_scene_grid gd;
+    std::memset(&gd, 0, sizeof gd);
+    uint64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) { set_error("%s: lo[%d] / hi[%d] is not finite", fn, a, a); return PR_ERR_INVALID; }
+        if (hi[a] < lo[a]) { set_error("%s: hi[%d] = %g is below lo[%d] = %g", fn, a, (double)hi[a], a, (double)lo[a]); return PR_ERR_INVALID; }
+        const volatile float extent = hi[a] - lo[a];              // (volatile: each step rounded to float32, whatever the host compiler's excess precision)
+        const volatile float f = extent * inv_cell;
+        if (!(f < 4294967040.0f)) { set_error("%s: dim[%d] overflows 32 bits (extent %g, cell %g)", fn, a, (double)extent, (double)cell); return PR_ERR_INVALID; }
+        const uint64_t d = (uint64_t)std::floor((float)f) + 1u;
+        cells = (d > PR_GRID_MAX_CELLS) ? (uint64_t)PR_GRID_MAX_CELLS + 1u : cells * d;
+        if (cells > PR_GRID_MAX_CELLS) { set_error("%s: more than PR_GRID_MAX_CELLS = %u cells (a larger cell or a smaller box)", fn, (uint32_t)PR_GRID_MAX_CELLS); return PR_ERR_INVALID; }
+        gd.origin[a] = lo[a]; gd.dim[a] = (uint32_t)d;
+    }
+    gd.cell = cell; gd.inv_cell = inv_cell; gd.max_dist_diff = max_dist_diff; gd.reach = reach;
+    *out = gd;
+    return PR_OK;
+}
+
+// The build of a closest-point grid into the caller's buffers: one exact search of the scene's kd-tree per cell centre (grid_build_kernel), the
+// scene points and normals repacked as 32-byte records.  make_scene derives the tree's traversal arrays, or finds them derived.
+int pr_scene_grid_build_dev(const pr_scene_nn *scene, pr_scene_grid *grid, uint32_t *cell_point_dev, float *rec_dev)
+{
+    PR_ENTER();
+    const char *fn = "pr_scene_grid_build_dev";
+    if (!scene || !cell_point_dev || !rec_dev) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    PR_TRY(grid_desc_ok(fn, grid, /*built=*/false));
+    if (scene->n_points >= (1u << 27)) { set_error("%s: %u scene points, at most 2^27 - 1", fn, scene->n_points); return PR_ERR_INVALID; }
+    SceneSel sc;
+    std::memset(static_cast<void *>(&sc), 0, sizeof sc);
+    PR_TRY(make_scene(PR_SCENE_NN, scene, false, sc));
+    const size_t cells = (size_t)grid->dim[0] * grid->dim[1] * grid->dim[2];
+    note_write(cell_point_dev, cells * sizeof(uint32_t)); note_write(rec_dev, (size_t)scene->n_points * 8 * sizeof(float));
+    const prk::SceneGridDev gd{ { grid->origin[0], grid->origin[1], grid->origin[2] }, grid->cell, grid->inv_cell, { grid->dim[0], grid->dim[1], grid->dim[2] },
+                                grid->max_dist_diff, cell_point_dev, reinterpret_cast<const float4 *>(rec_dev) };
+    HIP_TRY(prk::launch_grid_build(sc.nn, grid->reach, gd, cell_point_dev, g->stream));
+    HIP_TRY(prk::launch_grid_records(scene->pcd, scene->normal, scene->n_points, reinterpret_cast<float4 *>(rec_dev), g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    grid->cell_point = cell_point_dev; grid->rec = rec_dev; grid->n_points = scene->n_points;
+    return PR_OK;
 }
 
 // Audit entry: the derived search data of a kd-tree scene, as make_scene hands it to the searches (SceneSel::nn) and keeps it (the picked

@@ -12,6 +12,9 @@
 #ifndef PR_PASS_WAVES
 #define PR_PASS_WAVES 1                                         // __launch_bounds__ minimum waves per SIMD of icp_pass_kernel: 4, 5 waves run within 0.2 % of the compiler's own choice (round 6: 277.8 / 277.1 k against 278.0 / 277.5 k); 6 spills the accumulators: 162 k
 #endif
+#ifndef PR_GRID_PASS_WAVES
+#define PR_GRID_PASS_WAVES 1                                    // __launch_bounds__ minimum waves per SIMD of icp_pass_grid_kernel: the compiler's own choice, as for icp_pass_kernel (the 32 accumulator registers set the floor)
+#endif
 #ifndef PR_PASS_PREFETCH
 #define PR_PASS_PREFETCH 0                                      // 1: the next 1024-point step's cloud points are loaded before this step's gathers are consumed (12 more VGPRs: 106, four waves per SIMD).  Same box: 262 k against 274 k poses/s -- not kept
 #endif

@@ -30,7 +30,26 @@ int main()
     refused(tris, 5, 640, 480, nullptr, K, PR_SCENE_PROJ, &sp, crit, none);
     refused(tris, 5, 640, 480, &proj, nullptr, PR_SCENE_PROJ, &sp, crit, none);
     for (int kind : { PR_SCENE_PROJ, PR_SCENE_NN, PR_SCENE_PROJ_CROP }) refused(tris, 5, 640, 480, &proj, K, kind, nullptr, crit, none);
-    for (int kind : { -1, 3, 1 << 30, -2147483647 - 1 }) refused(tris, 5, 640, 480, &proj, K, kind, &sp, crit, none);
+    for (int kind : { -1, 4, 1 << 30, -2147483647 - 1 }) refused(tris, 5, 640, 480, &proj, K, kind, &sp, crit, none);
+    // a closest-point grid: one mistake at a time in an otherwise good description
+    pr_scene_grid sg{};
+    sg.cell = 0.25f; sg.inv_cell = 4.0f; sg.dim[0] = 4; sg.dim[1] = 5; sg.dim[2] = 6; sg.max_dist_diff = 0.1f; sg.reach = 0.3f; sg.n_points = 11;
+    sg.cell_point = reinterpret_cast<const uint32_t *>(uintptr_t(0xd000)); sg.rec = reinterpret_cast<const float *>(uintptr_t(0xf000));
+    refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, nullptr, crit, none);
+    { pr_scene_grid b = sg; b.cell_point = nullptr; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.rec = nullptr; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.inv_cell = 3.9999998f; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.cell = 0.0f; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.cell = -0.25f; b.inv_cell = -4.0f; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.cell = NAN; b.inv_cell = NAN; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.origin[1] = INFINITY; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.dim[2] = 0; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.dim[0] = 1u << 13; b.dim[1] = 1u << 13; b.dim[2] = 2; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }      // 2^27 cells
+    { pr_scene_grid b = sg; b.dim[0] = 0xffffffffu; b.dim[1] = 0xffffffffu; b.dim[2] = 0xffffffffu; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.max_dist_diff = 0.0f; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.reach = NAN; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.n_points = 0; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
+    { pr_scene_grid b = sg; b.n_points = 1u << 27; refused(tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none); }
     refused(tris, 5, 0, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
     refused(tris, 5, 640, 0, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
     refused(tris, 5, 8193, 1, &proj, K, PR_SCENE_PROJ, &sp, crit, none);
@@ -48,6 +67,11 @@ int main()
     CHECK(job.scene() == &job.sp && job.sp.tl_x == 7 && job.sp.tl_y == 9 && job.roi.x == 630 && job.crit.max_iteration == 0 && job.results_dev == nullptr);
     CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_NN, &sn, crit, pr_roi{ 5, 5, -3, 0 }, nullptr, job) == PR_OK);       // (no ROI)
     CHECK(job.scene() == &job.sn && job.sn.n_points == 11);
+    { pr_scene_grid b = sg; b.dim[0] = 1u << 13; b.dim[1] = 1u << 13; b.dim[2] = 1;                                    // exactly PR_GRID_MAX_CELLS
+      CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_GRID, &b, crit, none, nullptr, job) == PR_OK); }
+    CHECK(job.scene() == &job.sg && job.sg.dim[0] == (1u << 13) && job.sg.cell_point == sg.cell_point && job.sg.n_points == 11);
+    CHECK(grid_desc_ok("job_sanitize", &sg, false) == PR_OK && grid_desc_ok("job_sanitize", nullptr, false) == PR_ERR_INVALID);
+    { pr_scene_grid b = sg; b.cell_point = nullptr; b.rec = nullptr; b.n_points = 0; CHECK(grid_desc_ok("job_sanitize", &b, false) == PR_OK); }      // (as pr_scene_grid_describe leaves it: good for the build)
     // scoring requests: one good one per kind, single mesh and mesh table; then one mistake at a time -- a null array, too many hypotheses, a ROI off the frame
     const pr_mat4 *poses = reinterpret_cast<const pr_mat4 *>(uintptr_t(0x4000));
     const pr_mesh_ref *table = reinterpret_cast<const pr_mesh_ref *>(uintptr_t(0x5000));

@@ -1,6 +1,8 @@
 // d2c.hip -- depth2mask / exclusive_scan / depth2cloud (cuda_icp/icp.cu:228-291): rows counted, scanned per image, emitted row-major
 // gfx950 (CDNA4, wave64); compiled with -ffp-contract=off: every per-element value is bit-identical to the CPU restatement.
+#define PR_HD __host__ __device__
 #include "pr_launch.h"
+#include "pose_box.h"
 
 namespace prk {
 
@@ -8,13 +10,13 @@ namespace prk {
 __global__ __launch_bounds__(256) void d2c_emit_box_kernel(const int32_t *__restrict__ depth, uint32_t width, uint32_t height,
                                                            const int4 *__restrict__ bbox, float fx, float fy, float cx, float cy,
                                                            const uint32_t *__restrict__ row_count, const uint32_t *__restrict__ row_off,
-                                                           pr_vec3 *__restrict__ cloud, size_t cloud_stride, const PoseMeta *__restrict__ meta,
+                                                           pr_vec3 *__restrict__ cloud, const PoseMeta *__restrict__ meta,
                                                            const uint32_t *__restrict__ box_off)
 {
     const uint32_t lane = threadIdx.x & 63;
     const int4 bb = bbox[blockIdx.y];
-    // where this hypothesis' cloud starts: packed behind the one before it (fused asynchronous path: PoseMeta::start from d2c_pack_starts_kernel), or at a fixed stride
-    const size_t start = meta ? (size_t)meta[blockIdx.y].start : (size_t)blockIdx.y * cloud_stride;
+    // where this hypothesis' cloud starts: packed behind the one before it (PoseMeta::start from d2c_pack_starts_kernel)
+    const size_t start = (size_t)meta[blockIdx.y].start;
     for (uint32_t r = 0; r < 4; ++r) {
         const uint32_t row = blockIdx.x * kBoxRowsPerBlock + (threadIdx.x >> 6) * 4 + r;
         if (row >= height) return;
@@ -74,29 +76,10 @@ __global__ __launch_bounds__(256) void d2c_count_kernel(const T *__restrict__ de
     if (lane == 0) row_count[(size_t)blockIdx.y * gh + row] = cnt;
 }
 
-// one workgroup per image: exclusive scan of the row counts (serial carry over chunks of 256 rows)
-// exclusive scan of one image's row counts (256 lanes, Hillis-Steele per 256-row chunk); returns the total in every lane
+// one workgroup per image: exclusive scan of the row counts (block_exclusive_scan, pr_device.h); returns the total in every lane
 __device__ __forceinline__ uint32_t row_scan_block(const uint32_t *__restrict__ rc, uint32_t *__restrict__ ro, uint32_t gh, uint32_t *buf, uint32_t *carry)
 {
-    if (threadIdx.x == 0) *carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < gh; base += 256) {
-        const uint32_t r = base + threadIdx.x;
-        const uint32_t v = (r < gh) ? rc[r] : 0;
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t off = 1; off < 256; off <<= 1) {           // Hillis-Steele inclusive scan
-            uint32_t t = (threadIdx.x >= off) ? buf[threadIdx.x - off] : 0;
-            __syncthreads();
-            buf[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (r < gh) ro[r] = *carry + buf[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) *carry += buf[255];
-        __syncthreads();
-    }
-    return *carry;
+    return block_exclusive_scan(gh, buf, carry, [&](uint32_t r) { return rc[r]; }, [&](uint32_t r, uint32_t off) { ro[r] = off; });
 }
 __global__ __launch_bounds__(256) void d2c_scan_kernel(const uint32_t *__restrict__ row_count, uint32_t gh,
                                                        uint32_t *__restrict__ row_off, uint32_t *__restrict__ counts)
@@ -111,7 +94,7 @@ __global__ __launch_bounds__(256) void d2c_scan_kernel(const uint32_t *__restric
 // before it starts, icp.cu:183)
 __global__ __launch_bounds__(256) void d2c_scan_init_kernel(const uint32_t *__restrict__ row_count, uint32_t gh, uint32_t *__restrict__ row_off,
                                                             uint32_t *__restrict__ counts, PoseMeta *__restrict__ meta, DevIcpState *__restrict__ st,
-                                                            uint32_t *__restrict__ arrive, uint32_t cloud_stride)
+                                                            uint32_t *__restrict__ arrive)
 {
     __shared__ uint32_t buf[256];
     __shared__ uint32_t carry;
@@ -121,7 +104,7 @@ __global__ __launch_bounds__(256) void d2c_scan_init_kernel(const uint32_t *__re
         counts[i] = c;
         arrive[i] = 0u;
         PoseMeta m;
-        m.start = i * cloud_stride; m.count = c; m.state = c > 0 ? kRun : kSkip; m.pad = 0;       // (start: overwritten by d2c_pack_starts_kernel when the clouds are packed)
+        m.start = 0; m.count = c; m.state = c > 0 ? kRun : kSkip; m.pad = 0;       // (start: d2c_pack_starts_kernel's, right behind this launch)
 #pragma unroll
         for (int k = 0; k < 12; ++k) m.xform[k] = 0.0f;
         meta[i] = m;
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(256) void d2c_scan_init_kernel(const uint32_t *__re
     }
 }
 
-// The clouds of a sub-batch PACKED one behind the other (each rounded up to kCloudAlign points = 128 bytes) instead of one per fixed stride of the
+// The clouds of a sub-batch PACKED one behind the other (each rounded up to kCloudAlign points = 128 bytes: cloud_slot) instead of one per fixed stride of the
 // largest pixel box: exclusive scan of the sizes, one workgroup.  With a stride the 256 clouds of a batch are 264 KB islands 1.2 MB apart, and
 // how those islands fall on the memory system's interleave -- together with where the driver happened to put the two slots' buffers -- decided
 // between 246 and 262 k poses/s for the same process (profiles/r04/README.md, "the spread between processes"); packed, the loop streams one dense range.
@@ -142,24 +125,7 @@ __global__ __launch_bounds__(256) void d2c_pack_starts_kernel(const uint32_t *__
 {
     __shared__ uint32_t buf[256];
     __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = (i < n) ? ((counts[i] + (kCloudAlign - 1u)) & ~(kCloudAlign - 1u)) : 0u;
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t off = 1; off < 256; off <<= 1) {           // Hillis-Steele inclusive scan
-            const uint32_t t = (threadIdx.x >= off) ? buf[threadIdx.x - off] : 0;
-            __syncthreads();
-            buf[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) meta[i].start = carry + buf[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += buf[255];
-        __syncthreads();
-    }
+    block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return cloud_slot(counts[i]); }, [&](uint32_t i, uint32_t start) { meta[i].start = start; });
 }
 
 template <typename T>
@@ -198,15 +164,15 @@ __global__ __launch_bounds__(256) void d2c_emit_kernel(const T *__restrict__ dep
 }
 
 hipError_t launch_emit_box(const int32_t *depth, uint32_t n_poses, uint32_t width, uint32_t height, const int4 *bbox, float fx, float fy,
-                           float cx, float cy, const uint32_t *row_count, const uint32_t *row_off, pr_vec3 *cloud, size_t cloud_stride,
-                           hipStream_t s, const PoseMeta *meta, const uint32_t *box_off)
+                           float cx, float cy, const uint32_t *row_count, const uint32_t *row_off, pr_vec3 *cloud, const PoseMeta *meta,
+                           hipStream_t s, const uint32_t *box_off)
 {
     if (n_poses == 0) return hipSuccess;
     for (uint32_t i0 = 0; i0 < n_poses; i0 += 32768) {
         const uint32_t ni = (n_poses - i0 < 32768) ? (n_poses - i0) : 32768;
         hipLaunchKernelGGL(d2c_emit_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, ni), dim3(256), 0, s, box_off ? depth : depth + (size_t)i0 * width * height, width, height,
                            bbox + i0, fx, fy, cx, cy, row_count + (size_t)i0 * height, row_off + (size_t)i0 * height,
-                           meta ? cloud : cloud + (size_t)i0 * cloud_stride, cloud_stride, meta ? meta + i0 : nullptr, box_off ? box_off + i0 : nullptr);
+                           cloud, meta + i0, box_off ? box_off + i0 : nullptr);
     }
     return hipGetLastError();
 }
@@ -252,16 +218,16 @@ hipError_t launch_d2c_scan(const uint32_t *row_count, uint32_t gh, uint32_t *row
 }
 hipError_t launch_d2c_pack_starts(const uint32_t *counts, uint32_t n, PoseMeta *meta, hipStream_t s)
 {
-    if (n == 0 || !kCloudAlign) return hipSuccess;
+    if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(d2c_pack_starts_kernel, dim3(1), dim3(256), 0, s, counts, n, meta);
     return hipGetLastError();
 }
 hipError_t launch_d2c_scan_init(const uint32_t *row_count, uint32_t gh, uint32_t *row_off, uint32_t *counts, uint32_t n_img,
-                                PoseMeta *meta, DevIcpState *st, uint32_t *arrive, uint32_t cloud_stride, hipStream_t s)
+                                PoseMeta *meta, DevIcpState *st, uint32_t *arrive, hipStream_t s)
 {
     if (n_img == 0) return hipSuccess;
-    hipLaunchKernelGGL(d2c_scan_init_kernel, dim3(n_img), dim3(256), 0, s, row_count, gh, row_off, counts, meta, st, arrive, cloud_stride);
-    if (kCloudAlign) hipLaunchKernelGGL(d2c_pack_starts_kernel, dim3(1), dim3(256), 0, s, counts, n_img, meta);
+    hipLaunchKernelGGL(d2c_scan_init_kernel, dim3(n_img), dim3(256), 0, s, row_count, gh, row_off, counts, meta, st, arrive);
+    hipLaunchKernelGGL(d2c_pack_starts_kernel, dim3(1), dim3(256), 0, s, counts, n_img, meta);
     return hipGetLastError();
 }
 

@@ -49,6 +49,20 @@ PR_HD inline int4 pose_pixel_box(const float *aabb, const float *M, const pr_mat
     return make_int4(x0, y0, x1, y1);
 }
 
+// ---- the packed layouts of a (sub-)batch: THE definition, for the host that sizes and stages a batch and for the kernels that form the same
+// offsets on the device (box_pack_offsets_kernel, d2c_pack_starts_kernel) -- the two must agree byte for byte.  A pixel box is its own little
+// image of box_area ints in the depth workspace, a cloud a run of points; each starts where the one before it ends, rounded up to kBoxPack
+// ints / kCloudAlign points (128-byte lines).  An empty or inverted box (an off-screen pose) has no pixels.
+static_assert(kCloudAlign > 0 && (kCloudAlign & (kCloudAlign - 1)) == 0, "kCloudAlign: a power of two");
+static_assert(kBoxPack > 0 && (kBoxPack & (kBoxPack - 1)) == 0, "kBoxPack: a power of two");
+PR_HD inline uint32_t box_area(const int4 b)
+{
+    const int w = b.z - b.x + 1, h = b.w - b.y + 1;
+    return (uint32_t)(w > 0 ? w : 0) * (uint32_t)(h > 0 ? h : 0);
+}
+PR_HD inline uint32_t box_slot(uint32_t area) { return (area + (kBoxPack - 1u)) & ~(kBoxPack - 1u); }
+PR_HD inline uint32_t cloud_slot(uint32_t count) { return (count + (kCloudAlign - 1u)) & ~(kCloudAlign - 1u); }
+
 // One vertex to the screen: model transform (renderer.h:296-303 mat_mul_v, rows a,b,c), projection rows 0 and 1 (only x and y of the result are
 // used downstream), viewport (renderer.cu:90-98).  THE definition: the raster's triangle setup and the tight pixel box (below) both call it, so with
 // contraction disabled the box is formed from the very floats the raster loops over.

@@ -77,10 +77,9 @@ void ctx_teardown(Ctx *c)        // c->mu held (or c unreachable); the calling t
     c->packed = PackedCache();
     for (auto &gr : c->graphs) destroy_graph(gr);
     c->graphs.clear();
-    for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
+    c->spans.destroy();
     for (auto &e : c->gather_ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     c->gather_ev.clear(); c->gather_ev_used = 0;
-    c->ev_pool.clear(); c->ev_used = 0; c->spans.clear();
     hipStreamDestroy(c->stream);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     c->ev_fork = nullptr;

@@ -94,6 +94,34 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x)
            (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 
+// Exclusive scan of n values in chunks of 256 with a carry, by one 256-lane workgroup (Hillis-Steele per chunk): out(i, value(0) + ... + value(i - 1))
+// for every i < n; returns the total in every lane.  THE scan of the render -> cloud stage: the row offsets of an image (d2c_scan_kernel,
+// d2c_scan_init_kernel), the starts of the packed clouds (d2c_pack_starts_kernel), the offsets of the packed boxes (box_pack_offsets_kernel).
+// buf: 256 words of LDS, carry: one more.
+template <class Value, class Out>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t n, uint32_t *buf, uint32_t *carry, Value &&value, Out &&out)
+{
+    if (threadIdx.x == 0) *carry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < n; base += 256) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = (i < n) ? value(i) : 0u;
+        buf[threadIdx.x] = v;
+        __syncthreads();
+        for (uint32_t off = 1; off < 256; off <<= 1) {           // Hillis-Steele inclusive scan
+            const uint32_t t = (threadIdx.x >= off) ? buf[threadIdx.x - off] : 0;
+            __syncthreads();
+            buf[threadIdx.x] += t;
+            __syncthreads();
+        }
+        if (i < n) out(i, *carry + buf[threadIdx.x] - v);
+        __syncthreads();
+        if (threadIdx.x == 255) *carry += buf[255];
+        __syncthreads();
+    }
+    return *carry;
+}
+
 constexpr uint32_t kBoxRowsPerBlock = 16;                        // rows of a pixel box per workgroup: 4 wavefronts x 4 rows (few, fatter workgroups: dispatch-bound otherwise)
 
 // box_off (fused asynchronous path): the boxes of a sub-batch PACKED one behind the other, each as its own little image (pitch = its width) at

@@ -1,5 +1,14 @@
 // pr_icp.cpp -- the batched ICP driver (cuda_icp/icp.cu:156-217 for many clouds): device-solve loop, host-solve pipeline, graph cache
 #include "pr_runtime.h"
+// what a polling loop does between two looks (HostRun::wait_flag): the pause instruction of x86, yield on aarch64, elsewhere a compiler barrier
+#if defined(__x86_64__) || defined(__i386__)
+#include <immintrin.h>
+#define cpu_relax() _mm_pause()
+#elif defined(__aarch64__)
+#define cpu_relax() __asm__ __volatile__("yield" ::: "memory")
+#else
+#define cpu_relax() __asm__ __volatile__("" ::: "memory")
+#endif
 
 namespace prr {
 
@@ -67,19 +76,283 @@ int sums_trace_admits(const char *fn, uint32_t P, const pr_criteria &crit)
 }
 
 // ---- the batched ICP driver -----------------------------------------------------------------------
+// What icp_drive sets up once for either driver: the batch as the passes take it, the host copies of the per-hypothesis records and results.
+struct IcpRun {
+    prk::IcpBatch b{}; SceneSel sc; pr_criteria crit{}; uint32_t P = 0; const uint32_t *count_h = nullptr; pr_result *results_host = nullptr, *results_dev = nullptr;
+    prk::PoseMeta *h_meta = nullptr; float *h_sums = nullptr; pr_result *res = nullptr;      // pinned: g->h_meta, g->h_sums, g->h_results
+    SumsTrace trace;
+};
+
+// the context's graph of `key`: looked up, or -- the least recently used of 8 evicted -- captured from enqueue() on the context's stream and instantiated; stamped
+template <class Enqueue>
+int cached_graph(const GraphKey &key, Enqueue &&enqueue, CachedGraph *&hit)
+{
+    hit = nullptr;
+    for (auto &c : g->graphs) if (c.exec && c.key == key) { hit = &c; break; }
+    if (!hit) {
+        if (g->graphs.size() >= 8) {                         // evict the least recently used entry
+            size_t lru = 0;
+            for (size_t i = 1; i < g->graphs.size(); ++i) if (g->graphs[i].stamp < g->graphs[lru].stamp) lru = i;
+            destroy_graph(g->graphs[lru]);
+            g->graphs.erase(g->graphs.begin() + lru);
+        }
+        CachedGraph c; c.key = key;
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        HIP_TRY(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
+        int rc = enqueue();
+        hipError_t ce = hipStreamEndCapture(g->stream, &c.graph);
+        if (rc != PR_OK || ce != hipSuccess) { destroy_graph(c); if (rc == PR_OK) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce)); rc = PR_ERR_HIP; } return rc; }
+        HIP_TRY(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
+        g->graphs.push_back(std::move(c));
+        hit = &g->graphs.back();
+    }
+    hit->stamp = ++g->graph_clock;
+    return PR_OK;
+}
+int drive_device(IcpRun &r)
+{
+    const uint32_t P = r.P;
+    const pr_criteria crit = r.crit;
+    PR_TRY(g->dstate.ensure(sizeof(prk::DevIcpState) * P));
+    PR_TRY(g->h_dstate.ensure(sizeof(prk::DevIcpState) * P));
+    prk::DevIcpState *init = g->h_dstate.as<prk::DevIcpState>();
+    for (uint32_t i = 0; i < P; ++i) { identity16(init[i].T); init[i].fitness = 0; init[i].rmse = 0; init[i].done = (r.h_meta[i].state == prk::kSkip); init[i].passes = 0; }
+    pr_result *dres = r.results_dev;
+    if (!dres) { PR_TRY(g->dresults.ensure(sizeof(pr_result) * P)); dres = g->dresults.as<pr_result>(); }
+    const bool fused = opt.fused_solve != 0;
+    if (fused) PR_TRY(g->arrive.ensure(sizeof(uint32_t) * P));
+
+    // profile==2: every sample_period-th call is a timed call -- it runs synchronously, as one pose group, with the other slot
+    // drained, and times every correspondence launch of its loop
+    const uint64_t tick = g->sample_clock++;
+    const bool sample_call = (opt.profile == 2) && (tick % (uint64_t)std::max(1, opt.sample_period) == 0);
+    // Pose groups: the batch is split over up to four streams so that one group's serial solve tail (and the ragged end
+    // of its pass) overlaps another group's pass -- while the (latency-bound, one wavefront per pose) finalize+solve of one group
+    // runs, the correspondence pass of the other group keeps the chip busy.  Timed launches (profile 1, the sampled call of
+    // profile 2) run as a single group so that the measured kernel has the chip to itself.
+    const bool timed_call = (opt.profile == 1 || opt.profile == 3) || sample_call;   // (profile 3 only keeps SUBMITTED batches asynchronous: whatever runs here is a synchronous timed call)
+    const bool may_exit_early = (crit.relative_fitness > 0.0f && crit.relative_rmse > 0.0f);
+    const uint32_t n_groups = pose_group_count(r.sc.kind, P, timed_call);
+    const Lanes lanes{ g->stream, g->side, g->ev_fork, g->ev_join };
+    // the fixed sequence: state upload, (max_iteration+1) x [correspondence pass, finalize+solve], result pack
+    auto enqueue_all = [&](bool host_checks) -> int {
+        // start state and per-hypothesis records: PULLED from the pinned arrays by a kernel, results pushed into the pinned array by one -- no copy
+        // command on a per-call path (round 6: the runtime's copy-engine path is where one-off multi-millisecond stalls came from, see drive_host)
+        HIP_TRY(prk::launch_stage_words(g->h_dstate.dev, g->dstate.p, sizeof(prk::DevIcpState) * P, g->stream));
+        HIP_TRY(prk::launch_stage_words(g->h_meta.dev, g->meta.p, sizeof(prk::PoseMeta) * P, g->stream));
+        if (fused) HIP_TRY(prk::launch_fill_i32(g->arrive.as<int32_t>(), P, 0, g->stream));
+        auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t st) -> int {
+            if (!timed_call) { HIP_TRY(launch_pass(bb, r.sc, np, st)); return PR_OK; }
+            SpanGuard sp(kSpanIcp); HIP_TRY(launch_pass(bb, r.sc, np, st));       // a timed call times every launch of its loop
+            uint64_t pts = 0; for (uint32_t i = p0; i < p0 + np; ++i) pts += r.count_h[i];
+            g->icp_points += pts; g->icp_bytes += icp_span_bytes(pts, bb.iter == 0 || bb.iter == (uint32_t)r.crit.max_iteration);      // (edge: the first or the score-only last pass)
+            return PR_OK;
+        };
+        // every fourth pass, when the criteria can end a hypothesis early and nothing is being captured: has every hypothesis finished?
+        auto after = [&](uint32_t it, bool &stop) -> int {
+            if (!(host_checks && may_exit_early && (it & 3) == 3 && it < (uint32_t)r.crit.max_iteration)) return PR_OK;
+            for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamSynchronize(g->side[k - 1]));
+            HIP_TRY(hipMemcpyAsync(r.h_meta, g->meta.p, sizeof(prk::PoseMeta) * P, hipMemcpyDeviceToHost, g->stream));
+            HIP_TRY(hipStreamSynchronize(g->stream));
+            stop = true;
+            for (uint32_t i = 0; i < P; ++i) if (r.h_meta[i].state != prk::kSkip) stop = false;
+            return PR_OK;
+        };
+        PR_TRY(device_solve_loop(lanes, n_groups, r.b, P, r.crit, fused, g->meta.as<prk::PoseMeta>(), g->dstate.as<prk::DevIcpState>(), g->arrive.as<uint32_t>(), pass, after));
+        HIP_TRY(prk::launch_pack_results(g->dstate.as<prk::DevIcpState>(), dres, P, g->stream));
+        // results go to the pinned staging buffer (a pageable destination is not capturable)
+        if (r.results_host) HIP_TRY(prk::launch_stage_words64(dres, g->h_results.dev, sizeof(pr_result) * P, g->stream));
+        return PR_OK;
+    };
+
+    if (opt.use_graph && n_groups == 1 && (opt.profile == 0 || (opt.profile == 2 && !sample_call))) {   // HIP events recorded inside a captured graph cannot be timed
+        const prk::IcpBatch &b = r.b;
+        GraphKey key;
+        key.add(P); key.add(b.nblk); key.add(b.steps); key.add(crit); key.add(r.sc); key.add(b.cloud); key.add(g->meta.p); key.add(g->partial.p);
+        key.add(g->dstate.p); key.add(dres); key.add(r.results_host != nullptr); key.add(r.res); key.add(r.h_meta); key.add(init); key.add(opt.profile); key.add(pose_groups_for(r.sc.kind)); key.add(opt.fused_solve); key.add(g->arrive.p); key.add(b.nn_prev);
+        key.add(b.nn_slack); key.add(b.nn_queue); key.add(b.nn_queue2); key.add(b.nn_qcount);    // nn_carve: behind nn_prev at multiples of `span` (max start+count) -- same P / max_n, other offsets => other addresses
+        CachedGraph *hit = nullptr;
+        PR_TRY(cached_graph(key, [&] { return enqueue_all(/*host_checks=*/false); }, hit));
+        HIP_TRY(hipGraphLaunch(hit->exec, g->stream));
+    } else
+        PR_TRY(enqueue_all(/*host_checks=*/true));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (r.results_host) std::memcpy(r.results_host, r.res, sizeof(pr_result) * P);
+    drain_spans();
+    return PR_OK;
+}
+
+// ---- PR_SOLVE_HOST: the software pipeline over pose groups ---------------------------------------------------------------------------------
+// Per iteration one launch + one small D2H, then the per-pose logic of icp.cu:178-212 on the host.  The batch runs
+// as up to four pose groups, each on a stream of its own, software-pipelined: while the host waits for, solves and re-arms one
+// group, the correspondence pass of the next group is on the chip -- the host's share of an iteration (copy latency, wake-up,
+// 160 ns per 6x6 solve) is as long as the pass itself, and a single group leaves the GPU idle for all of it.  Results per
+// hypothesis do not depend on the grouping (sums, solve and state are per hypothesis).  A timed call (profile 1) is one group.
+struct HostRun {
+    IcpRun &r; uint32_t n_groups; Lanes lanes;
+    bool host_fused, poll_flag;
+    float *sums_dev;                             // h_sums as the device sees it (host_fused), or null
+    const prk::PoseMeta *h_meta_mapped, *meta_dev;      // h_meta as the device sees it; what the passes read their state from (null: g->meta, staged per iteration)
+    volatile uint32_t *h_flags;                  // one flag per pose group, behind the sums
+    bool sample_call; uint32_t sample_it;        // profile 2: this call times the pass of iteration sample_it
+    uint32_t begin(uint32_t grp) const { return group_begin(r.P, n_groups, grp); }
+    int enqueue_group(uint32_t grp, uint32_t it) const; bool solve_one(uint32_t i, uint32_t it) const; bool wait_flag(uint32_t grp, uint32_t it) const; int finish_group(uint32_t grp, uint32_t it) const;
+};
+// one iteration of one group goes onto its stream: state upload, pass, block sums -> pose sums, download
+int HostRun::enqueue_group(uint32_t grp, uint32_t it) const
+{
+    const uint32_t p0 = begin(grp), np = begin(grp + 1) - p0;
+    hipStream_t st = lane(lanes, grp);
+    prk::IcpBatch whole = r.b;
+    if (meta_dev) whole.meta = meta_dev;                         // the pass reads the 64-byte state of its hypothesis from the pinned host array
+    else HIP_TRY(prk::launch_stage_words(h_meta_mapped + p0, g->meta.as<prk::PoseMeta>() + p0, sizeof(prk::PoseMeta) * np, st));   // (pulled by a kernel: no copy command per iteration)
+    prk::IcpBatch bb = group_slice(whole, p0);
+    bb.iter = it;
+    if (host_fused) { bb.fused = 2; bb.arrive = g->arrive.as<uint32_t>() + p0; bb.sums_out = sums_dev + (size_t)p0 * prk::kAccStride; }
+    if (poll_flag) {                                             // the group's count and flag (see pass_deliver): how many hypotheses will deliver
+        uint32_t expected = 0;
+        for (uint32_t i = p0; i < p0 + np; ++i) expected += (r.h_meta[i].state != prk::kSkip) ? 1u : 0u;
+        bb.grp_count = g->arrive.as<uint32_t>() + r.P + grp; bb.grp_expected = expected;
+        bb.grp_flag = reinterpret_cast<uint32_t *>(sums_dev + (size_t)r.P * prk::kAccStride) + grp;
+    }
+    if (opt.profile == 1 || opt.profile == 3 || (sample_call && it == sample_it)) {
+        SpanGuard sp(kSpanIcp); HIP_TRY(launch_pass(bb, r.sc, np, st));
+        // (edge: the first pass only -- this loop's last pass is not score-only)
+        for (uint32_t i = p0; i < p0 + np; ++i) if (r.h_meta[i].state != prk::kSkip) { g->icp_points += r.count_h[i]; g->icp_bytes += icp_span_bytes(r.count_h[i], it == 0); }
+    } else HIP_TRY(launch_pass(bb, r.sc, np, st));
+    if (!host_fused) {
+        HIP_TRY(prk::launch_icp_finalize(bb.partial, g->meta.as<prk::PoseMeta>() + p0, r.b.nblk, r.b.steps, g->sums.as<float>() + (size_t)p0 * prk::kAccStride, np, st));
+        HIP_TRY(hipMemcpyAsync(r.h_sums + (size_t)p0 * prk::kAccStride, g->sums.as<float>() + (size_t)p0 * prk::kAccStride, sizeof(float) * prk::kAccStride * np,
+                               hipMemcpyDeviceToHost, st));
+    }
+    return PR_OK;
+}
+// the host's part of an iteration for one hypothesis whose 29 sums have arrived (icp.cu:178-212); returns whether the hypothesis goes on
+bool HostRun::solve_one(uint32_t i, uint32_t it) const
+{
+    float E[16];
+    if (r.trace.rows) std::memcpy(r.trace.rows + ((size_t)it * r.trace.n_hyp + i) * 29, r.h_sums + (size_t)i * prk::kAccStride, sizeof(float) * 29);   // pr_debug_trace_sums: it < n_passes, i < n_hyp (sums_trace_admits)
+    if (!pose_iteration_host(r.h_sums + (size_t)i * prk::kAccStride, r.count_h[i], r.res[i], r.crit, it, E)) { r.h_meta[i].state = prk::kSkip; return false; }
+    std::memcpy(r.h_meta[i].xform, E, sizeof(float) * 12);
+    r.h_meta[i].state = prk::kRunWithTransform;
+    return true;
+}
+// until the group's flag carries iteration it's tag and every row that was due has arrived; false: a HIP error
+bool HostRun::wait_flag(uint32_t grp, uint32_t it) const
+{
+    hipStream_t st = lane(lanes, grp);
+    const uint32_t tag = it + 1u;
+    uint32_t idle = 0;
+    bool drained = false;
+    while (h_flags[grp] != tag) {
+        if (drained) { set_error("PR_SOLVE_HOST: the pass of iteration %u ended without completing its pose group", it); return false; }
+        if (++idle >= 20000u) {                              // every few hundred microseconds of fruitless polling: is the stream still alive?
+            idle = 0;
+            const hipError_t q = hipStreamQuery(st);
+            if (q == hipSuccess) drained = true;           // (one more look: the flag was stored before the kernel ended)
+            else if (q != hipErrorNotReady) { (void)hipGetLastError(); set_error("HIP error: %s", hipGetErrorString(q)); return false; }
+        }
+        cpu_relax();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    // every row that was due carries the iteration's tag behind its sums (pass_deliver): a row without it was overtaken by the flag -- wait for the
+    // stream (the end of the launch makes everything visible) instead of solving on stale sums
+    bool all_in = true;
+#if PR_HOST_ROW_TAG
+    for (uint32_t i = begin(grp); i < begin(grp + 1) && all_in; ++i)
+        if (r.h_meta[i].state != prk::kSkip && reinterpret_cast<volatile uint32_t *>(r.h_sums + (size_t)i * prk::kAccStride)[31] != tag) all_in = false;
+#endif
+    if (!all_in) {
+        g_flag_overtook.fetch_add(1);
+        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) { set_error("HIP error: %s", hipGetErrorString(e)); return false; }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return true;
+}
+// returns how many hypotheses of the group go on; < 0: a HIP error
+int HostRun::finish_group(uint32_t grp, uint32_t it) const
+{
+    if (poll_flag) { if (!wait_flag(grp, it)) return -1; }
+    else if (hipError_t e = hipStreamSynchronize(lane(lanes, grp)); e != hipSuccess) { set_error("HIP error: %s", hipGetErrorString(e)); return -1; }
+    int active = 0;
+    for (uint32_t i = begin(grp); i < begin(grp + 1); ++i) if (r.h_meta[i].state != prk::kSkip && solve_one(i, it)) ++active;
+    return active;
+}
+int drive_host(IcpRun &r)
+{
+    const uint32_t P = r.P;
+    const pr_criteria crit = r.crit;
+    // profile 2: one call in sample_period times ONE of its passes (a different iteration from call to call); that call runs as one pose
+    // group like the calls of profile 1 / 3, so that the timed launch has the chip to itself -- the other calls keep their pipeline
+    const uint64_t host_tick = g->sample_clock++;
+    const bool sample_call = (opt.profile == 2) && (host_tick % (uint64_t)std::max(1, opt.sample_period) == 0);
+    const uint32_t sample_it = (uint32_t)(((host_tick / (uint64_t)std::max(1, opt.sample_period)) * 5 + 1) % (uint64_t)(crit.max_iteration + 1));
+    const uint32_t n_groups = pose_group_count(r.sc.kind, P, opt.profile == 1 || opt.profile == 3 || sample_call);
+    const Lanes lanes{ g->stream, g->side, g->ev_fork, g->ev_join };
+    if (opt.fused_solve) { PR_TRY(g->arrive.ensure(sizeof(uint32_t) * (P + 4))); HIP_TRY(prk::launch_fill_i32(g->arrive.as<int32_t>(), (size_t)P + 4, 0, g->stream)); }   // (+ one counter per pose group)
+    PR_TRY(lanes_fork(lanes, n_groups));                              // the groups start behind the render / cloud work of this call
+    // With option fused_solve the pass also adds up the workgroup sums of a hypothesis (the workgroup that arrives last does, as in the
+    // device-solve loop) and stores the 29 totals straight into the pinned host array: no finalize launch, no copy command -- two
+    // API calls and one copy-engine round trip less per group and iteration on a path that is bound by exactly those.
+    const bool host_fused = opt.fused_solve != 0;
+    // Projective scenes also read the per-hypothesis state (64 bytes: cloud span, pending update) from the pinned host array instead
+    // of receiving it through a copy command: one uniform load per workgroup over the host link, 1.62 -> 1.54 ms per 256-hypothesis
+    // batch.  The four kernels of a kd-tree pass have ten times the workgroups; there the copy is cheaper (8.3 against 8.8 ms).
+    const prk::PoseMeta *h_meta_mapped = g->h_meta.dev_as<prk::PoseMeta>();
+    // Round 6 (VERDICT r05 item 5): the host waits for a pose group's FLAG in pinned memory (stored by the workgroup that delivers the group's last
+    // hypothesis) instead of for the stream -- it solves while the launch winds down.  Option blocking_wait (several ranks sharing few CPUs) and
+    // host_poll = 0 keep the stream wait.
+    const HostRun h{ r, n_groups, lanes, host_fused, host_fused && !opt.blocking_wait && opt.host_poll, host_fused ? g->h_sums.dev_as<float>() : nullptr,
+                     h_meta_mapped, (host_fused && r.sc.kind != PR_SCENE_NN) ? h_meta_mapped : nullptr,
+                     reinterpret_cast<volatile uint32_t *>(r.h_sums + (size_t)P * prk::kAccStride), sample_call, sample_it };
+    if (h.poll_flag) { for (int k = 0; k < 4; ++k) h.h_flags[k] = 0u; for (uint32_t i = 0; i < P; ++i) reinterpret_cast<volatile uint32_t *>(r.h_sums + (size_t)i * prk::kAccStride)[31] = 0u; }
+    bool live[4] = { false, false, false, false };
+    int rc_loop = PR_OK;
+    for (uint32_t grp = 0; grp < n_groups && rc_loop == PR_OK; ++grp) {
+        for (uint32_t i = h.begin(grp); i < h.begin(grp + 1); ++i) live[grp] |= (r.h_meta[i].state != prk::kSkip);
+        if (live[grp]) rc_loop = h.enqueue_group(grp, 0);
+    }
+    for (uint32_t it = 0; it <= (uint32_t)crit.max_iteration && rc_loop == PR_OK && (live[0] || live[1] || live[2] || live[3]); ++it) {
+        for (uint32_t grp = 0; grp < n_groups && rc_loop == PR_OK; ++grp) {
+            if (!live[grp]) continue;
+            const int active = h.finish_group(grp, it);
+            if (active < 0) { rc_loop = PR_ERR_HIP; break; }
+            live[grp] = active > 0;
+            if (live[grp]) rc_loop = h.enqueue_group(grp, it + 1);                          // it + 1 <= max_iteration: the last iteration leaves nobody active
+        }
+    }
+    for (uint32_t k = 1; k < n_groups; ++k) (void)hipStreamSynchronize(g->side[k - 1]);  // nothing of this call is left on a side stream, error or not
+    if (h.poll_flag) (void)hipStreamSynchronize(g->stream);         // (a flag arrives before its pass has formally ended: nothing of this call runs on after it returns)
+    trace_mark("icp_drive: host loop done");
+    if (rc_loop != PR_OK) { (void)hipStreamSynchronize(g->stream); drain_spans(); return rc_loop; }
+    if (r.results_host) std::memcpy(r.results_host, r.res, sizeof(pr_result) * P);
+    if (r.results_dev) {
+        // the records are PULLED from the pinned array by a kernel, not pushed by a copy command: round 6 traced the one-off stall of the host-solve
+        // pipeline (one step of 6.5-8.7 ms among forty of 1.0 ms, PR_TRACE) to this 18 KB hipMemcpyAsync -- some batches into a helper thread's life
+        // the runtime spends milliseconds inside it, on both helpers at once (its copy-engine path; the kernels around it take microseconds)
+        HIP_TRY(prk::launch_stage_words64(g->h_results.dev, r.results_dev, sizeof(pr_result) * P, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+    }
+    drain_spans();
+    return PR_OK;
+}
+
 // clouds: cloud i = cloud_base[start_h[i] .. start_h[i]+count_h[i]); start and count reach the device with the per-hypothesis records staged here.
+// The set-up both drivers share -- workspaces, the batch, the kd-tree workspace, the start records and results -- then the driver of option solve.
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
               pr_criteria crit, pr_result *results_host, pr_result *results_dev)
 {
     if (P == 0) return PR_OK;
-    SceneSel sc = sc_in;
     if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
     PR_TRY(sums_trace_admits("icp_drive", P, crit));               // (a recorder that does not fit this batch: refused before anything is launched)
-    const SumsTrace trace = tl_sums_trace.active;
+    IcpRun r;
+    r.sc = sc_in; r.crit = crit; r.P = P; r.count_h = count_h; r.results_host = results_host; r.results_dev = results_dev;
+    r.trace = tl_sums_trace.active;
+    SceneSel &sc = r.sc;
     const uint32_t steps = (uint32_t)std::max(1, opt.steps);
     const uint32_t ppb = steps * prk::kPointsPerStep;
-    uint32_t max_n = 0; uint64_t sum_n = 0;
-    for (uint32_t i = 0; i < P; ++i) { max_n = std::max(max_n, count_h[i]); sum_n += count_h[i]; }
+    uint32_t max_n = 0;
+    for (uint32_t i = 0; i < P; ++i) max_n = std::max(max_n, count_h[i]);
     const uint32_t nblk = (max_n + ppb - 1) / ppb;
 
     PR_TRY(g->meta.ensure(sizeof(prk::PoseMeta) * P));
@@ -89,7 +362,7 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     PR_TRY(g->h_sums.ensure(sizeof(float) * prk::kAccStride * P + 64));        // (+ the pose groups' flags, PR_SOLVE_HOST with host_poll)
     PR_TRY(g->h_results.ensure(sizeof(pr_result) * P));
 
-    prk::IcpBatch b{};
+    prk::IcpBatch &b = r.b;
     b.cloud = cloud_base; b.meta = g->meta.as<prk::PoseMeta>(); b.partial = g->partial.as<float>();
     b.nblk = nblk; b.steps = steps;
     sc.nn_split = nn_split_for(sc);
@@ -106,247 +379,17 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
         const NNLayout nl = nn_layout(span, P);
         PR_TRY(g->nn_prev.ensure(nl.bytes));
         nn_carve(b, g->nn_prev.as<uint32_t>(), nl);
-        HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(b.nn_qcount), (size_t)prk::kQCountStride * P, 0, g->stream));     // (a kernel, not a memset command: no runtime copy / fill path on a per-call path, see below)
+        HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(b.nn_qcount), (size_t)prk::kQCountStride * P, 0, g->stream));     // (a kernel, not a memset command: no runtime copy / fill path on a per-call path, see drive_host)
     }
 
-    prk::PoseMeta *h_meta = g->h_meta.as<prk::PoseMeta>();
-    float *h_sums = g->h_sums.as<float>();
-    pr_result *res = g->h_results.as<pr_result>();
+    r.h_meta = g->h_meta.as<prk::PoseMeta>(); r.h_sums = g->h_sums.as<float>(); r.res = g->h_results.as<pr_result>();
     for (uint32_t i = 0; i < P; ++i) {
-        identity16(res[i].T); res[i].inlier_rmse = 0.0f; res[i].fitness = 0.0f;   // icp.h:29-31
-        std::memset(&h_meta[i], 0, sizeof(prk::PoseMeta));
-        h_meta[i].start = start_h[i]; h_meta[i].count = count_h[i];
-        h_meta[i].state = (count_h[i] > 0) ? prk::kRun : prk::kSkip;    // empty cloud: count==0 -> identity result (icp.cu:183)
+        identity16(r.res[i].T); r.res[i].inlier_rmse = 0.0f; r.res[i].fitness = 0.0f;   // icp.h:29-31
+        std::memset(&r.h_meta[i], 0, sizeof(prk::PoseMeta));
+        r.h_meta[i].start = start_h[i]; r.h_meta[i].count = count_h[i];
+        r.h_meta[i].state = (count_h[i] > 0) ? prk::kRun : prk::kSkip;    // empty cloud: count==0 -> identity result (icp.cu:183)
     }
-
-    if (opt.solve_mode == PR_SOLVE_DEVICE) {
-        PR_TRY(g->dstate.ensure(sizeof(prk::DevIcpState) * P));
-        PR_TRY(g->h_dstate.ensure(sizeof(prk::DevIcpState) * P));
-        prk::DevIcpState *init = g->h_dstate.as<prk::DevIcpState>();
-        for (uint32_t i = 0; i < P; ++i) { identity16(init[i].T); init[i].fitness = 0; init[i].rmse = 0; init[i].done = (h_meta[i].state == prk::kSkip); init[i].passes = 0; }
-        pr_result *dres = results_dev;
-        if (!dres) { PR_TRY(g->dresults.ensure(sizeof(pr_result) * P)); dres = g->dresults.as<pr_result>(); }
-        const bool may_exit_early = (crit.relative_fitness > 0.0f && crit.relative_rmse > 0.0f);
-        const bool fused = opt.fused_solve != 0;
-        if (fused) PR_TRY(g->arrive.ensure(sizeof(uint32_t) * P));
-
-        // profile==2: every sample_period-th call is a timed call -- it runs synchronously, as one pose group, with the other slot
-        // drained, and times every correspondence launch of its loop
-        const uint64_t tick = g->sample_clock++;
-        const bool sample_call = (opt.profile == 2) && (tick % (uint64_t)std::max(1, opt.sample_period) == 0);
-        // Pose groups: the batch is split over up to four streams so that one group's serial solve tail (and the ragged end
-        // of its pass) overlaps another group's pass -- while the (latency-bound, one wavefront per pose) finalize+solve of one group
-        // runs, the correspondence pass of the other group keeps the chip busy.  Timed launches (profile 1, the sampled call of
-        // profile 2) run as a single group so that the measured kernel has the chip to itself.
-        const bool timed_call = (opt.profile == 1 || opt.profile == 3) || sample_call;   // (profile 3 only keeps SUBMITTED batches asynchronous: whatever runs here is a synchronous timed call)
-        const uint32_t n_groups = pose_group_count(sc.kind, P, timed_call);
-        const Lanes lanes{ g->stream, g->side, g->ev_fork, g->ev_join };
-        // the fixed sequence: state upload, (max_iteration+1) x [correspondence pass, finalize+solve], result pack
-        auto enqueue_all = [&](bool host_checks) -> int {
-            // start state and per-hypothesis records: PULLED from the pinned arrays by a kernel, results pushed into the pinned array by one -- no copy
-            // command on a per-call path (round 6: the runtime's copy-engine path is where one-off multi-millisecond stalls came from, see below)
-            HIP_TRY(prk::launch_stage_words(g->h_dstate.dev, g->dstate.p, sizeof(prk::DevIcpState) * P, g->stream));
-            HIP_TRY(prk::launch_stage_words(g->h_meta.dev, g->meta.p, sizeof(prk::PoseMeta) * P, g->stream));
-            if (fused) HIP_TRY(prk::launch_fill_i32(g->arrive.as<int32_t>(), P, 0, g->stream));
-            auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t st) -> int {
-                if (!timed_call) { HIP_TRY(launch_pass(bb, sc, np, st)); return PR_OK; }
-                SpanGuard sp(kSpanIcp); HIP_TRY(launch_pass(bb, sc, np, st));       // a timed call times every launch of its loop
-                uint64_t pts = 0; for (uint32_t i = p0; i < p0 + np; ++i) pts += count_h[i];
-                // algorithmic bytes per point: 12 read + 24 gathered, + 12 written back once a transform is
-                // pending; the score-only last pass needs the scene point but not its normal (12 + 12 + 12)
-                const bool first = (bb.iter == 0), last = (bb.iter == (uint32_t)crit.max_iteration);
-                g->icp_points += pts; g->icp_bytes += pts * ((first || last) ? 36u : 48u);
-                return PR_OK;
-            };
-            // every fourth pass, when the criteria can end a hypothesis early and nothing is being captured: has every hypothesis finished?
-            auto after = [&](uint32_t it, bool &stop) -> int {
-                if (!(host_checks && may_exit_early && (it & 3) == 3 && it < (uint32_t)crit.max_iteration)) return PR_OK;
-                for (uint32_t k = 1; k < n_groups; ++k) HIP_TRY(hipStreamSynchronize(g->side[k - 1]));
-                HIP_TRY(hipMemcpyAsync(h_meta, g->meta.p, sizeof(prk::PoseMeta) * P, hipMemcpyDeviceToHost, g->stream));
-                HIP_TRY(hipStreamSynchronize(g->stream));
-                stop = true;
-                for (uint32_t i = 0; i < P; ++i) if (h_meta[i].state != prk::kSkip) stop = false;
-                return PR_OK;
-            };
-            PR_TRY(device_solve_loop(lanes, n_groups, b, P, crit, fused, g->meta.as<prk::PoseMeta>(), g->dstate.as<prk::DevIcpState>(), g->arrive.as<uint32_t>(), pass, after));
-            HIP_TRY(prk::launch_pack_results(g->dstate.as<prk::DevIcpState>(), dres, P, g->stream));
-            // results go to the pinned staging buffer (a pageable destination is not capturable)
-            if (results_host) HIP_TRY(prk::launch_stage_words64(dres, g->h_results.dev, sizeof(pr_result) * P, g->stream));
-            return PR_OK;
-        };
-
-        if (opt.use_graph && n_groups == 1 && (opt.profile == 0 || (opt.profile == 2 && !sample_call))) {   // HIP events recorded inside a captured graph cannot be timed
-            GraphKey key;
-            key.add(P); key.add(nblk); key.add(steps); key.add(crit); key.add(sc); key.add(cloud_base); key.add(g->meta.p); key.add(g->partial.p);
-            key.add(g->dstate.p); key.add(dres); key.add(results_host != nullptr); key.add(res); key.add(h_meta); key.add(init); key.add(opt.profile); key.add(pose_groups_for(sc.kind)); key.add(opt.fused_solve); key.add(g->arrive.p); key.add(b.nn_prev);
-            key.add(b.nn_slack); key.add(b.nn_queue); key.add(b.nn_queue2); key.add(b.nn_qcount);    // nn_carve: behind nn_prev at multiples of `span` (max start+count) -- same P / max_n, other offsets => other addresses
-            CachedGraph *hit = nullptr;
-            for (auto &c : g->graphs) if (c.exec && c.key == key) { hit = &c; break; }
-            if (!hit) {
-                if (g->graphs.size() >= 8) {                         // evict the least recently used entry
-                    size_t lru = 0;
-                    for (size_t i = 1; i < g->graphs.size(); ++i) if (g->graphs[i].stamp < g->graphs[lru].stamp) lru = i;
-                    destroy_graph(g->graphs[lru]);
-                    g->graphs.erase(g->graphs.begin() + lru);
-                }
-                CachedGraph c; c.key = key;
-                HIP_TRY(hipStreamSynchronize(g->stream));
-                HIP_TRY(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
-                int rc = enqueue_all(/*host_checks=*/false);
-                hipError_t ce = hipStreamEndCapture(g->stream, &c.graph);
-                if (rc != PR_OK || ce != hipSuccess) { destroy_graph(c); if (rc == PR_OK) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce)); rc = PR_ERR_HIP; } return rc; }
-                HIP_TRY(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
-                g->graphs.push_back(std::move(c));
-                hit = &g->graphs.back();
-            }
-            hit->stamp = ++g->graph_clock;
-            HIP_TRY(hipGraphLaunch(hit->exec, g->stream));
-            HIP_TRY(hipStreamSynchronize(g->stream));
-            if (results_host) std::memcpy(results_host, res, sizeof(pr_result) * P);
-            drain_spans();
-            return PR_OK;
-        }
-
-        PR_TRY(enqueue_all(/*host_checks=*/true));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (results_host) std::memcpy(results_host, res, sizeof(pr_result) * P);
-        drain_spans();
-        return PR_OK;
-    }
-
-    // PR_SOLVE_HOST: per iteration one launch + one small D2H, then the per-pose logic of icp.cu:178-212 on the host.  The batch runs
-    // as up to four pose groups, each on a stream of its own, software-pipelined: while the host waits for, solves and re-arms one
-    // group, the correspondence pass of the next group is on the chip -- the host's share of an iteration (copy latency, wake-up,
-    // 160 ns per 6x6 solve) is as long as the pass itself, and a single group leaves the GPU idle for all of it.  Results per
-    // hypothesis do not depend on the grouping (sums, solve and state are per hypothesis).  A timed call (profile 1) is one group.
-    // profile 2: one call in sample_period times ONE of its passes (a different iteration from call to call); that call runs as one pose
-    // group like the calls of profile 1 / 3, so that the timed launch has the chip to itself -- the other calls keep their pipeline
-    const uint64_t host_tick = g->sample_clock++;
-    const bool host_sample_call = (opt.profile == 2) && (host_tick % (uint64_t)std::max(1, opt.sample_period) == 0);
-    const uint32_t host_sample_it = (uint32_t)(((host_tick / (uint64_t)std::max(1, opt.sample_period)) * 5 + 1) % (uint64_t)(crit.max_iteration + 1));
-    const uint32_t n_groups = pose_group_count(sc.kind, P, opt.profile == 1 || opt.profile == 3 || host_sample_call);
-    const Lanes lanes{ g->stream, g->side, g->ev_fork, g->ev_join };
-    auto group_begin = [&](uint32_t grp) { return prr::group_begin(P, n_groups, grp); };
-    if (opt.fused_solve) { PR_TRY(g->arrive.ensure(sizeof(uint32_t) * (P + 4))); HIP_TRY(prk::launch_fill_i32(g->arrive.as<int32_t>(), (size_t)P + 4, 0, g->stream)); }   // (+ one counter per pose group)
-    PR_TRY(lanes_fork(lanes, n_groups));                              // the groups start behind the render / cloud work of this call
-    auto group_stream = [&](uint32_t grp) { return lane(lanes, grp); };
-    // With option fused_solve the pass also adds up the workgroup sums of a hypothesis (the workgroup that arrives last does, as in the
-    // device-solve loop) and stores the 29 totals straight into the pinned host array: no finalize launch, no copy command -- two
-    // API calls and one copy-engine round trip less per group and iteration on a path that is bound by exactly those.
-    const bool host_fused = opt.fused_solve != 0;
-    float *sums_dev = host_fused ? g->h_sums.dev_as<float>() : nullptr;
-    // Projective scenes also read the per-hypothesis state (64 bytes: cloud span, pending update) from the pinned host array instead
-    // of receiving it through a copy command: one uniform load per workgroup over the host link, 1.62 -> 1.54 ms per 256-hypothesis
-    // batch.  The four kernels of a kd-tree pass have ten times the workgroups; there the copy is cheaper (8.3 against 8.8 ms).
-    const prk::PoseMeta *h_meta_mapped = g->h_meta.dev_as<prk::PoseMeta>();     // h_meta as the device sees it
-    const prk::PoseMeta *meta_dev = (host_fused && sc.kind != PR_SCENE_NN) ? h_meta_mapped : nullptr;
-    // Round 6 (VERDICT r05 item 5): the host waits for a pose group's FLAG in pinned memory (stored by the workgroup that delivers the group's last
-    // hypothesis) instead of for the stream -- it solves while the launch winds down.  Option blocking_wait (several ranks sharing few CPUs) and
-    // host_poll = 0 keep the stream wait.
-    const bool poll_flag = host_fused && !opt.blocking_wait && opt.host_poll;
-    volatile uint32_t *h_flags = reinterpret_cast<volatile uint32_t *>(h_sums + (size_t)P * prk::kAccStride);
-    if (poll_flag) { for (int k = 0; k < 4; ++k) h_flags[k] = 0u; for (uint32_t i = 0; i < P; ++i) reinterpret_cast<volatile uint32_t *>(h_sums + (size_t)i * prk::kAccStride)[31] = 0u; }
-    // one iteration of one group goes onto its stream: state upload, pass, block sums -> pose sums, download
-    auto enqueue_group = [&](uint32_t grp, uint32_t it) -> int {
-        const uint32_t p0 = group_begin(grp), np = group_begin(grp + 1) - p0;
-        hipStream_t st = group_stream(grp);
-        prk::IcpBatch whole = b;
-        if (meta_dev) whole.meta = meta_dev;                         // the pass reads the 64-byte state of its hypothesis from the pinned host array
-        else HIP_TRY(prk::launch_stage_words(h_meta_mapped + p0, g->meta.as<prk::PoseMeta>() + p0, sizeof(prk::PoseMeta) * np, st));   // (pulled by a kernel: no copy command per iteration)
-        prk::IcpBatch bb = group_slice(whole, p0);
-        bb.iter = it;
-        if (host_fused) { bb.fused = 2; bb.arrive = g->arrive.as<uint32_t>() + p0; bb.sums_out = sums_dev + (size_t)p0 * prk::kAccStride; }
-        if (poll_flag) {                                             // the group's count and flag (see pass_deliver): how many hypotheses will deliver
-            uint32_t expected = 0;
-            for (uint32_t i = p0; i < p0 + np; ++i) expected += (h_meta[i].state != prk::kSkip) ? 1u : 0u;
-            bb.grp_count = g->arrive.as<uint32_t>() + P + grp; bb.grp_expected = expected;
-            bb.grp_flag = reinterpret_cast<uint32_t *>(sums_dev + (size_t)P * prk::kAccStride) + grp;
-        }
-        if (opt.profile == 1 || opt.profile == 3 || (host_sample_call && it == host_sample_it)) {
-            SpanGuard sp(kSpanIcp); HIP_TRY(launch_pass(bb, sc, np, st));
-            for (uint32_t i = p0; i < p0 + np; ++i) if (h_meta[i].state != prk::kSkip) { g->icp_points += count_h[i]; g->icp_bytes += (uint64_t)count_h[i] * (it == 0 ? 36u : 48u); }
-        } else HIP_TRY(launch_pass(bb, sc, np, st));
-        if (!host_fused) {
-            HIP_TRY(prk::launch_icp_finalize(bb.partial, g->meta.as<prk::PoseMeta>() + p0, nblk, steps, g->sums.as<float>() + (size_t)p0 * prk::kAccStride, np, st));
-            HIP_TRY(hipMemcpyAsync(h_sums + (size_t)p0 * prk::kAccStride, g->sums.as<float>() + (size_t)p0 * prk::kAccStride, sizeof(float) * prk::kAccStride * np,
-                                   hipMemcpyDeviceToHost, st));
-        }
-        return PR_OK;
-    };
-    // the host's part of an iteration for one hypothesis whose 29 sums have arrived (icp.cu:178-212); returns whether the hypothesis goes on
-    auto solve_one = [&](uint32_t i, uint32_t it) -> bool {
-        float E[16];
-        if (trace.rows) std::memcpy(trace.rows + ((size_t)it * trace.n_hyp + i) * 29, h_sums + (size_t)i * prk::kAccStride, sizeof(float) * 29);   // pr_debug_trace_sums: it < n_passes, i < n_hyp (sums_trace_admits)
-        if (!pose_iteration_host(h_sums + (size_t)i * prk::kAccStride, count_h[i], res[i], crit, it, E)) { h_meta[i].state = prk::kSkip; return false; }
-        std::memcpy(h_meta[i].xform, E, sizeof(float) * 12);
-        h_meta[i].state = prk::kRunWithTransform;
-        return true;
-    };
-    // returns how many hypotheses of the group go on; < 0: a HIP error
-    auto finish_group = [&](uint32_t grp, uint32_t it) -> int {
-        if (!poll_flag) {
-            if (hipError_t e = hipStreamSynchronize(group_stream(grp)); e != hipSuccess) { set_error("HIP error: %s", hipGetErrorString(e)); return -1; }
-        } else {
-            const uint32_t tag = it + 1u;
-            uint32_t idle = 0;
-            bool drained = false;
-            while (h_flags[grp] != tag) {
-                if (drained) { set_error("PR_SOLVE_HOST: the pass of iteration %u ended without completing its pose group", it); return -1; }
-                if (++idle >= 20000u) {                              // every few hundred microseconds of fruitless polling: is the stream still alive?
-                    idle = 0;
-                    const hipError_t q = hipStreamQuery(group_stream(grp));
-                    if (q == hipSuccess) drained = true;           // (one more look: the flag was stored before the kernel ended)
-                    else if (q != hipErrorNotReady) { (void)hipGetLastError(); set_error("HIP error: %s", hipGetErrorString(q)); return -1; }
-                }
-                __builtin_ia32_pause();
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-            // every row that was due carries the iteration's tag behind its sums (pass_deliver): a row without it was overtaken by the flag -- wait for the
-            // stream (the end of the launch makes everything visible) instead of solving on stale sums
-            bool all_in = true;
-#if PR_HOST_ROW_TAG
-            for (uint32_t i = group_begin(grp); i < group_begin(grp + 1) && all_in; ++i)
-                if (h_meta[i].state != prk::kSkip && reinterpret_cast<volatile uint32_t *>(h_sums + (size_t)i * prk::kAccStride)[31] != tag) all_in = false;
-#endif
-            if (!all_in) {
-                g_flag_overtook.fetch_add(1);
-                if (hipError_t e = hipStreamSynchronize(group_stream(grp)); e != hipSuccess) { set_error("HIP error: %s", hipGetErrorString(e)); return -1; }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        int active = 0;
-        for (uint32_t i = group_begin(grp); i < group_begin(grp + 1); ++i) if (h_meta[i].state != prk::kSkip && solve_one(i, it)) ++active;
-        return active;
-    };
-    bool live[4] = { false, false, false, false };
-    int rc_loop = PR_OK;
-    for (uint32_t grp = 0; grp < n_groups && rc_loop == PR_OK; ++grp) {
-        for (uint32_t i = group_begin(grp); i < group_begin(grp + 1); ++i) live[grp] |= (h_meta[i].state != prk::kSkip);
-        if (live[grp]) rc_loop = enqueue_group(grp, 0);
-    }
-    for (uint32_t it = 0; it <= (uint32_t)crit.max_iteration && rc_loop == PR_OK && (live[0] || live[1] || live[2] || live[3]); ++it) {
-        for (uint32_t grp = 0; grp < n_groups && rc_loop == PR_OK; ++grp) {
-            if (!live[grp]) continue;
-            const int active = finish_group(grp, it);
-            if (active < 0) { rc_loop = PR_ERR_HIP; break; }
-            live[grp] = active > 0;
-            if (live[grp]) rc_loop = enqueue_group(grp, it + 1);                          // it + 1 <= max_iteration: the last iteration leaves nobody active
-        }
-    }
-    for (uint32_t k = 1; k < n_groups; ++k) (void)hipStreamSynchronize(g->side[k - 1]);  // nothing of this call is left on a side stream, error or not
-    if (poll_flag) (void)hipStreamSynchronize(g->stream);         // (a flag arrives before its pass has formally ended: nothing of this call runs on after it returns)
-    trace_mark("icp_drive: host loop done");
-    if (rc_loop != PR_OK) { (void)hipStreamSynchronize(g->stream); drain_spans(); return rc_loop; }
-    if (results_host) std::memcpy(results_host, res, sizeof(pr_result) * P);
-    if (results_dev) {
-        // the records are PULLED from the pinned array by a kernel, not pushed by a copy command: round 6 traced the one-off stall of the host-solve
-        // pipeline (one step of 6.5-8.7 ms among forty of 1.0 ms, PR_TRACE) to this 18 KB hipMemcpyAsync -- some batches into a helper thread's life
-        // the runtime spends milliseconds inside it, on both helpers at once (its copy-engine path; the kernels around it take microseconds)
-        HIP_TRY(prk::launch_stage_words64(g->h_results.dev, results_dev, sizeof(pr_result) * P, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-    }
-    drain_spans();
-    return PR_OK;
+    return opt.solve_mode == PR_SOLVE_DEVICE ? drive_device(r) : drive_host(r);
 }
 
 }  // namespace prr
@@ -411,7 +454,7 @@ int pr_icp_grid(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_grid *scen
 }
 
 // Audit entry: the 29 sums of every pass of the calling thread's NEXT synchronous ICP call (pr_icp_batch / pr_icp_proj / pr_icp_nn / pr_refine_batch[_roi]), as
-// the host-solve loop received them -- solve_one copies the row of hypothesis i at iteration it to rows_host[(it * n_hyp + i) * 29 ..] right before
+// the host-solve loop received them -- HostRun::solve_one copies the row of hypothesis i at iteration it to rows_host[(it * n_hyp + i) * 29 ..] right before
 // pose_iteration_host consumes it, whichever way the sums came (pinned-memory stores of the pass tail, finalize launch + copy, flag polling or stream
 // wait, any pose grouping).  Rows of skipped or finished hypotheses are left alone.  NULL disarms.  Host code only: no device needed to arm.
 int pr_debug_trace_sums(float *rows_host, uint32_t n_hyp, uint32_t n_passes)

@@ -17,8 +17,8 @@ constexpr uint32_t kBlockThreads   = 256;                       // 4 wavefronts
 constexpr uint32_t kPointsPerLane  = 4;                         // consecutive points per lane per step
 constexpr uint32_t kPointsPerStep  = kBlockThreads * kPointsPerLane;   // 1024
 constexpr uint32_t kAccStride      = 32;                        // 29 sums padded to 32 floats
-constexpr uint32_t kCloudAlign     = PR_CLOUD_PACK;                 // fused path: clouds of a sub-batch packed one behind the other, each rounded up to this many points (0: one per fixed stride)
-constexpr uint32_t kBoxPack        = PR_BOX_PACK;                   // fused asynchronous path: depth boxes of a sub-batch packed (each rounded up to this many ints; 0: full frames)
+constexpr uint32_t kCloudAlign     = 32;                        // fused path: a hypothesis' cloud starts where the one before it ends, rounded up to this many points (128-byte lines; cloud_slot, pose_box.h)
+constexpr uint32_t kBoxPack        = 32;                        // fused path: a hypothesis' pixel box is its own little image in the depth workspace, packed behind the one before it, rounded up to this many ints (box_slot, pose_box.h)
 constexpr uint32_t kQCountStride   = 4;                         // queue counters per hypothesis (IcpBatch::nn_qcount)
 constexpr uint32_t kNNWordsPerPoint = 6;                        // per cloud point: winner | slack | queue 1 (2 words) | queue 2 (2 words) -- laid out by nn_layout (pr_runtime.h)
 
@@ -182,7 +182,7 @@ struct BatchCheck {
 hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb,
                                int4 *bbox, int32_t *depth, uint32_t *row_count, uint32_t *row_off, uint32_t *counts,
                                uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s, bool compute_boxes = true,
-                               PoseMeta *meta = nullptr, DevIcpState *st = nullptr, uint32_t *arrive = nullptr, uint32_t cloud_stride = 0,
+                               PoseMeta *meta = nullptr, DevIcpState *st = nullptr, uint32_t *arrive = nullptr,
                                const uint32_t *box_off = nullptr,    // box_off: the boxes packed into `depth` at these offsets (ints), each with its own pitch (fill_box_kernel)
                                const BatchCheck *check = nullptr);
 // Asynchronous path, option tight_box (pose_tight_box_kernel): bbox[i], the loose box the host uploaded, overwritten by its intersection with the
@@ -291,8 +291,8 @@ hipError_t launch_copy_words32(const void *src, void *dst, uint32_t n_words, hip
 // meta[i].start = exclusive scan of counts[0..i) rounded up to kCloudAlign points each (the packed layout of a batch's clouds)
 hipError_t launch_d2c_pack_starts(const uint32_t *counts, uint32_t n, PoseMeta *meta, hipStream_t s);
 hipError_t launch_emit_box(const int32_t *depth, uint32_t n_poses, uint32_t width, uint32_t height, const int4 *bbox, float fx, float fy,
-                           float cx, float cy, const uint32_t *row_count, const uint32_t *row_off, pr_vec3 *cloud, size_t cloud_stride,
-                           hipStream_t s, const PoseMeta *meta = nullptr, const uint32_t *box_off = nullptr);     // meta: cloud i starts at meta[i].start (packed, launch_render_boxes wrote it) instead of i * cloud_stride
+                           float cx, float cy, const uint32_t *row_count, const uint32_t *row_off, pr_vec3 *cloud, const PoseMeta *meta,
+                           hipStream_t s, const uint32_t *box_off = nullptr);     // cloud i starts at meta[i].start (packed: launch_render_boxes or launch_d2c_pack_starts wrote it)
 
 // pyramid.hip (pr_refine_pyramid): the strided level clouds of the hypotheses of a chunk, from the depth boxes launch_render_boxes left.
 // PyramidStrides: the levels' strides (unused entries 1).  PyramidCarry: what the emit of ONE level needs per hypothesis -- rows 0..2 of the transform

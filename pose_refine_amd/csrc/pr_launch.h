@@ -22,6 +22,6 @@ static inline uint32_t cap_grid(size_t want) { return (uint32_t)(want < 1 ? 1 : 
 // row scans of the depth -> cloud stage (d2c.hip), called from the render and scene launchers of other files
 hipError_t launch_d2c_scan(const uint32_t *row_count, uint32_t gh, uint32_t *row_off, uint32_t *counts, uint32_t n_img, hipStream_t s);
 hipError_t launch_d2c_scan_init(const uint32_t *row_count, uint32_t gh, uint32_t *row_off, uint32_t *counts, uint32_t n_img,
-                                PoseMeta *meta, DevIcpState *st, uint32_t *arrive, uint32_t cloud_stride, hipStream_t s);
+                                PoseMeta *meta, DevIcpState *st, uint32_t *arrive, hipStream_t s);
 
 }  // namespace prk

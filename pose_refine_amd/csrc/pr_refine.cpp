@@ -5,7 +5,7 @@
 namespace prr {
 
 // the hypotheses' poses into g->poses: through the context's pinned staging array, pulled by a kernel (as the asynchronous path stages its inputs) --
-// a copy command from the caller's pageable array goes through the runtime's bounce buffers and its copy-engine path (see icp_drive's
+// a copy command from the caller's pageable array goes through the runtime's bounce buffers and its copy-engine path (see drive_host's
 // result block: that path is where the host-solve pipeline's one-off multi-millisecond stalls came from)
 int stage_poses(const pr_mat4 *poses_host, size_t n)
 {
@@ -164,7 +164,7 @@ int render_chunk(const MeshSource &src, const pr_mat4 *poses_host, uint32_t p0, 
         else
             HIP_TRY(prk::launch_render_boxes(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
                                              g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
-                                             g->counts.as<uint32_t>(), W, H, *proj, roi, g->stream, /*compute_boxes=*/true, nullptr, nullptr, nullptr, 0, box_off));
+                                             g->counts.as<uint32_t>(), W, H, *proj, roi, g->stream, /*compute_boxes=*/true, nullptr, nullptr, nullptr, box_off));
         return PR_OK;
     }
     const MeshPlan &pl = *src.plan;
@@ -223,11 +223,10 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
     HIP_TRY(hipStreamSynchronize(g->stream));
     trace_mark("pyramid_chunk: level sizes on host");
     // every level's clouds packed one behind the other like the stride-1 clouds of refine_core; the workspace holds the largest level
-    constexpr size_t align = prk::kCloudAlign ? prk::kCloudAlign : 4;
     size_t most = 4;
     for (uint32_t l = 0; l < L; ++l) {
         size_t total = 0;
-        for (uint32_t i = 0; i < np; ++i) total += ((size_t)h_counts[(size_t)l * np + i] + align - 1) / align * align;
+        for (uint32_t i = 0; i < np; ++i) total += prk::cloud_slot(h_counts[(size_t)l * np + i]);
         if (total > 0xffffffffull) { set_error("pr_refine_pyramid: more than 2^32 cloud points in one chunk"); return PR_ERR_INVALID; }
         most = std::max(most, total);
     }
@@ -240,7 +239,7 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
         size_t total = 0;
         for (uint32_t i = 0; i < np; ++i) {
             start[i] = (uint32_t)total; count[i] = h_counts[(size_t)l * np + i];
-            total += ((size_t)count[i] + align - 1) / align * align;
+            total += prk::cloud_slot(count[i]);
             std::memset(&h_carry[i], 0, sizeof(prk::PyramidCarry));
             std::memcpy(h_carry[i].T, acc[i].T, sizeof(float) * 12);
             h_carry[i].start = start[i];
@@ -294,13 +293,13 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
         uint32_t *h_counts = g->h_counts.as<uint32_t>();
         // per-pose pixel boxes; raster + row counts + row scan
         PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));   // boxes, then the offsets of the packed boxes (box_pack_offsets_kernel)
-        uint32_t *box_off = (prk::kBoxPack && (src.plan || opt.raster_mode != 1)) ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
+        uint32_t *box_off = (src.plan || opt.raster_mode != 1) ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;       // (the band raster writes full frames)
         {
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, &job.proj, job.roi, box_off, !src.plan && opt.raster_mode == 1));
         }
         if (pyramid) { PR_TRY(pyramid_chunk(*pyramid, p0, np, W, H, K, box_off, sc, results_host + p0)); continue; }
-        // the cloud sizes come back through a kernel's stores into the pinned array, not through a copy command (see icp_drive's result block)
+        // the cloud sizes come back through a kernel's stores into the pinned array, not through a copy command (see drive_host's result block)
         HIP_TRY(prk::launch_copy_words32(g->counts.p, g->h_counts.dev, np, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
         trace_mark("refine_impl: render done, counts on host");
@@ -310,20 +309,16 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
         size_t total = 0;
         for (uint32_t i = 0; i < np; ++i) {
             start[i] = (uint32_t)total; count[i] = h_counts[i];
-            total += prk::kCloudAlign ? ((size_t)h_counts[i] + prk::kCloudAlign - 1) / prk::kCloudAlign * prk::kCloudAlign : (((size_t)max_n + 3) & ~(size_t)3);
+            total += prk::cloud_slot(h_counts[i]);
         }
         if (total > 0xffffffffull) { set_error("pr_refine_batch: more than 2^32 cloud points in one chunk"); return PR_ERR_INVALID; }
-        const size_t cstride = ((size_t)max_n + 3) & ~(size_t)3;           // (fixed-stride layout, kCloudAlign == 0: keeps every cloud 16-byte aligned)
         PR_TRY(g->cloud.ensure(sizeof(pr_vec3) * std::max<size_t>(4, total)));
         if (max_n > 0) {
             SpanGuard sp(kSpanCloud);
-            if (prk::kCloudAlign) {
-                PR_TRY(g->meta.ensure(sizeof(prk::PoseMeta) * np));
-                HIP_TRY(prk::launch_d2c_pack_starts(g->counts.as<uint32_t>(), np, g->meta.as<prk::PoseMeta>(), g->stream));
-            }
+            PR_TRY(g->meta.ensure(sizeof(prk::PoseMeta) * np));
+            HIP_TRY(prk::launch_d2c_pack_starts(g->counts.as<uint32_t>(), np, g->meta.as<prk::PoseMeta>(), g->stream));
             HIP_TRY(prk::launch_emit_box(g->depth.as<int32_t>(), np, W, H, g->bbox.as<int4>(), K[0], K[4], K[2], K[5],
-                                         g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(), g->cloud.as<pr_vec3>(), cstride, g->stream,
-                                         prk::kCloudAlign ? g->meta.as<prk::PoseMeta>() : nullptr, box_off));
+                                         g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(), g->cloud.as<pr_vec3>(), g->meta.as<prk::PoseMeta>(), g->stream, box_off));
         }
         if (sizes_host) std::memcpy(sizes_host + p0, count.data(), sizeof(uint32_t) * np);
         trace_mark("refine_impl: clouds emitted, icp_drive next");
@@ -430,7 +425,7 @@ int score_core(const ScoreRequest &req)
         PR_TRY(g->h_scores.ensure(sizeof(pr_pose_score) * np));
         if (contours) { PR_TRY(g->contours.ensure(sizeof(pr_pose_contour) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_pose_contour) * np)); }
         if (normals) { PR_TRY(g->normals.ensure(sizeof(pr_pose_normal) * np)); PR_TRY(g->h_normals.ensure(sizeof(pr_pose_normal) * np)); }
-        uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
+        uint32_t *box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np);
         {
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, req.poses, p0, np, chunk, W, H, req.proj, req.roi, box_off, /*bands=*/false));
@@ -615,7 +610,7 @@ int vsd_core(const MeshSource &src, const pr_mat4 *renders, const pr_mat4 *one_g
         PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
         PR_TRY(g->vsd_rec.ensure(sizeof(pr_vsd_counts) * nq));
         PR_TRY(g->h_vsd.ensure(sizeof(pr_vsd_counts) * nq));
-        uint32_t *box_off = prk::kBoxPack ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;
+        uint32_t *box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np);
         if (one_gt) { std::copy(renders + q0, renders + q0 + nq, with_gt.begin()); with_gt[nq] = *one_gt; }
         {
             SpanGuard sp(kSpanRender);
@@ -795,8 +790,7 @@ void slot_release(Slot &sl)
     sl.progress = nullptr; sl.progress_valid = false;
     if (sl.stream) hipStreamDestroy(sl.stream);
     sl.fork = sl.done = sl.scene_ready = nullptr; sl.stream = nullptr; sl.pending = false;
-    for (hipEvent_t e : sl.t_events) (void)hipEventDestroy(e);
-    sl.t_events.clear(); sl.t_used = 0; sl.t_spans.clear(); sl.timed = false;
+    sl.spans.destroy(); sl.timed = false;
 }
 
 // Host-side copy of a triangle buffer's box, once per (pointer, size): it feeds the per-pose pixel boxes computed on the host,
@@ -891,27 +885,7 @@ int refine_wait(int slot)
     uint32_t largest = 1;
     for (uint32_t i = 0; i < sl.P; ++i) largest = std::max(largest, h_counts[i]);
     g->cloud_hint = largest;
-    if (sl.timed) {                                              // the batch carried timing events: the same accounts as the synchronous timed path keeps
-        for (const Slot::TSpan &t : sl.t_spans) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, sl.t_events[t.e0], sl.t_events[t.e1]) != hipSuccess) continue;
-            if (t.kind == kSpanRender) g->render_ms += ms;
-            else if (t.kind == kSpanCloud) g->cloud_ms += ms;
-            else {
-                uint64_t pts = 0;
-                for (uint32_t i = t.q0; i < t.q0 + t.nq; ++i) pts += h_counts[i];
-                g->icp_ms += ms; g->icp_launches++; note_launch_us(ms);
-                g->icp_points += pts; g->icp_bytes += pts * (t.edge ? 36u : 48u);
-                if (t.marks) {                                      // kd-tree pass: search | bound | task walk | winners pass
-                    const hipEvent_t ev[5] = { sl.t_events[t.e0], sl.t_events[t.m[0]], sl.t_events[t.m[1]], sl.t_events[t.m[2]], sl.t_events[t.e1] };
-                    float part[4]; bool ok = true;
-                    for (int k = 0; k < 4; ++k) ok = ok && hipEventElapsedTime(&part[k], ev[k], ev[k + 1]) == hipSuccess;
-                    if (ok) { for (int k = 0; k < 4; ++k) g->nn_part_ms[k] += part[k]; g->nn_part_n++; }
-                }
-            }
-        }
-        sl.t_spans.clear(); sl.t_used = 0; sl.timed = false;
-    }
+    if (sl.timed) { sl.spans.drain([&](uint32_t i) { return h_counts[i]; }); sl.timed = false; }     // the batch carried timing events: the same accounts as the synchronous timed path keeps
     if (sl.user_sizes) std::memcpy(sl.user_sizes, h_counts, sizeof(uint32_t) * sl.P);
     if (sl.user_results_host) std::memcpy(sl.user_results_host, h_out + out.res, sizeof(pr_result) * sl.P);
     return PR_OK;
@@ -981,165 +955,103 @@ int slot_worker_post(Slot &sl, const RefineJob &job, const pr_mat4 *poses_host, 
     return PR_OK;
 }
 
-// everything of a batch onto the slot's streams; the poses are in sl.h_in already (refine_submit)
-int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *results_host)
+// ---- refine_submit_async, phase by phase ------------------------------------------------------------------------------------------------
+// The slot's streams, and the batch's scene on the stream that is idle until the loop forks.  The packed copy of the scene does not depend on the
+// render: when it has to be (re)built that happens on the first side stream, the loop waits for it (scene_ready); batches without pose groups
+// build it in line.
+int async_scene(Slot &sl, const RefineJob &job, uint32_t P, SceneSel &sc, hipStream_t &scene_stream)
 {
-    const uint32_t W = job.W, H = job.H;
-    const float *K = job.K;
-    const int scene_kind = job.scene_kind;
-    const pr_criteria crit = job.crit;
-    const size_t img = (size_t)W * H;
     PR_TRY(slot_streams(sl));
-    SceneSel sc;
     std::memset(static_cast<void *>(&sc), 0, sizeof sc);
-    // the packed copy of the scene does not depend on the render: when it has to be (re)built that happens on the first side
-    // stream (idle until the loop forks), the loop waits for it; batches without pose groups build it in line
-    const uint32_t groups_hint = std::max(1u, std::min({ pose_groups_for(scene_kind), 4u, std::min<uint32_t>(P, (uint32_t)std::max(32, opt.sub_batch)) / 32u }));
+    const uint32_t groups_hint = std::max(1u, std::min({ pose_groups_for(job.scene_kind), 4u, std::min<uint32_t>(P, (uint32_t)std::max(32, opt.sub_batch)) / 32u }));
     for (uint32_t k = 1; k < groups_hint; ++k) PR_TRY(ensure_stream(sl.side[k - 1], &sl.join[k - 1]));
-    hipStream_t scene_stream = groups_hint > 1 ? sl.side[0] : sl.stream;
-    const Camera cam{ W, H, K[0], K[4], K[2], K[5] };            // kd-tree scenes: the pixel grid of the scene points under this camera
+    scene_stream = groups_hint > 1 ? sl.side[0] : sl.stream;
+    const Camera cam{ job.W, job.H, job.K[0], job.K[4], job.K[2], job.K[5] };            // kd-tree scenes: the pixel grid of the scene points under this camera
     // nothing of this batch may run beside the loop of a TIMED batch on the other slot -- not even the small checks on the scene stream
     if (scene_stream != sl.stream)
         for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered && o.timed && o.progress_valid) HIP_TRY(hipStreamWaitEvent(scene_stream, o.progress, 0));
-    PR_TRY(make_scene(scene_kind, job.scene(), /*want_packed=*/true, sc, &sl.packed, scene_stream, scene_kind == PR_SCENE_NN ? &cam : nullptr, /*verify_now=*/false));
-    sl.nn_set = (scene_kind == PR_SCENE_NN) ? sc.nn_set : -1;        // (what make_scene must not rebuild under this batch while it is in flight)
-
-    PR_TRY(ensure_model_box(job.tris, job.n_tris));             // once per triangle buffer ...
-    const SlotIn in(P);
-    const SlotOut out(P);
-    PR_TRY(sl.h_out.ensure(out.bytes));
-    unsigned char *h_out_dev = sl.h_out.dev_as<unsigned char>();  // the pinned block as the device sees it
-    HIP_TRY(hipEventRecord(sl.scene_ready, scene_stream));      // (complete as it is recorded unless a cache missed and the scene is being rebuilt on this stream)
-    // ... and checked against the buffer's present content by every batch (refine_wait acts on the flag), together with the scene caches: a
-    // sampled fingerprint of the caller's arrays against the one taken when the cache was built.  Round 5: both checks ride on the raster launch
-    // (BatchCheck, pr_internal.h) -- as launches of their own on the scene stream (a memset, two box kernels, the fingerprint kernel) they cost
-    // 1.3-1.5 % of the headline whatever their number (skipped: 277.6 against 273.6 k poses/s on one box; fused into one launch: 274.1 k).
-    const bool keys_new = sl.aabb_keys.p == nullptr;
-    PR_TRY(sl.aabb_keys.ensure(prk::kBatchCheckWords * sizeof(uint32_t)));
-    if (keys_new) {                                               // armed once; the last workgroup of every check re-arms the words itself
-        HIP_TRY(hipMemsetAsync(sl.aabb_keys.p, 0xff, 6 * sizeof(uint32_t), sl.stream));
-        HIP_TRY(hipMemsetAsync(sl.aabb_keys.as<uint32_t>() + 6, 0, (prk::kBatchCheckWords - 6) * sizeof(uint32_t), sl.stream));
-    }
-    *reinterpret_cast<volatile uint32_t *>(sl.h_out.as<unsigned char>() + out.flag) = 0u;
+    PR_TRY(make_scene(job.scene_kind, job.scene(), /*want_packed=*/true, sc, &sl.packed, scene_stream, job.scene_kind == PR_SCENE_NN ? &cam : nullptr, /*verify_now=*/false));
+    sl.nn_set = (job.scene_kind == PR_SCENE_NN) ? sc.nn_set : -1;        // (what make_scene must not rebuild under this batch while it is in flight)
+    return PR_OK;
+}
+// The record of the batch's stale-cache checks: the model box and the mesh fingerprint the host assumed (ensure_model_box) and, with option
+// scene_cache, the caller's scene arrays against the fingerprint taken when their cached form was built.  Every batch checks both against the
+// buffers' present content (refine_wait acts on the flag).  Round 5: both checks ride on the raster launch (BatchCheck, pr_internal.h) -- as
+// launches of their own on the scene stream (a memset, two box kernels, the fingerprint kernel) they cost 1.3-1.5 % of the headline whatever
+// their number (skipped: 277.6 against 273.6 k poses/s on one box; fused into one launch: 274.1 k).
+prk::BatchCheck batch_check(const Slot &sl, const RefineJob &job, const SceneSel &sc, uint32_t *flag_dev)
+{
     prk::BatchCheck chk{};
-    {
-        chk.keys = sl.aabb_keys.as<uint32_t>();
-        for (int a = 0; a < 6; ++a) chk.expect.v[a] = g->aabb_host[a];
-        chk.caller = job.tris; chk.mesh_hash = g->mesh_hash;
-        chk.flag = reinterpret_cast<uint32_t *>(h_out_dev + out.flag);
-        if (opt.scene_cache) {
-            if (scene_kind == PR_SCENE_NN) {
-                const pr_scene_nn *sn = &job.sn;
-                chk.fa = reinterpret_cast<const uint32_t *>(sn->pcd); chk.na = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
-                chk.fb = reinterpret_cast<const uint32_t *>(sn->nodes); chk.nb = (size_t)sn->n_nodes * sizeof(pr_kdnode) / 4;
-                chk.fc = reinterpret_cast<const uint32_t *>(sn->normal); chk.nc = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
-                chk.fp_expected = g->nn_sets[sc.nn_set].nndepth.as<uint32_t>() + 12;
-            } else if (sl.packed.valid) {
-                const pr_scene_proj *sp = &job.sp.view;
-                const size_t n = (size_t)sp->width * sp->height;
-                const size_t tables = ((sp->width + sp->height) * sizeof(float) + 15) & ~(size_t)15;
-                const uint32_t *exact_dev = reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(sl.packed.rec.as<float4>() + n) + tables);
-                chk.fa = reinterpret_cast<const uint32_t *>(sp->pcd); chk.na = n * sizeof(pr_vec3) / 4;
-                chk.fb = reinterpret_cast<const uint32_t *>(sp->normal); chk.nb = n * sizeof(pr_vec3) / 4;
-                chk.fp_expected = exact_dev + 1;
-            }
-        }
+    chk.keys = sl.aabb_keys.as<uint32_t>();
+    for (int a = 0; a < 6; ++a) chk.expect.v[a] = g->aabb_host[a];
+    chk.caller = job.tris; chk.mesh_hash = g->mesh_hash;
+    chk.flag = flag_dev;
+    if (!opt.scene_cache) return chk;
+    if (job.scene_kind == PR_SCENE_NN) {
+        const pr_scene_nn *sn = &job.sn;
+        chk.fa = reinterpret_cast<const uint32_t *>(sn->pcd); chk.na = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
+        chk.fb = reinterpret_cast<const uint32_t *>(sn->nodes); chk.nb = (size_t)sn->n_nodes * sizeof(pr_kdnode) / 4;
+        chk.fc = reinterpret_cast<const uint32_t *>(sn->normal); chk.nc = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
+        chk.fp_expected = g->nn_sets[sc.nn_set].nndepth.as<uint32_t>() + 12;
+    } else if (sl.packed.valid) {
+        const pr_scene_proj *sp = &job.sp.view;
+        const size_t n = (size_t)sp->width * sp->height;
+        const size_t tables = ((sp->width + sp->height) * sizeof(float) + 15) & ~(size_t)15;
+        const uint32_t *exact_dev = reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(sl.packed.rec.as<float4>() + n) + tables);
+        chk.fa = reinterpret_cast<const uint32_t *>(sp->pcd); chk.na = n * sizeof(pr_vec3) / 4;
+        chk.fb = reinterpret_cast<const uint32_t *>(sp->normal); chk.nb = n * sizeof(pr_vec3) / 4;
+        chk.fp_expected = exact_dev + 1;
     }
-
-    // staging (SlotIn): the cloud stride and the grid come from the largest box
-    PR_TRY(sl.poses_bbox.ensure(in.bytes + 16));
-    pr_mat4 *h_poses = sl.h_in.as<pr_mat4>();
-    int4 *h_box = reinterpret_cast<int4 *>(sl.h_in.as<unsigned char>() + in.box);
-    size_t max_area = 1;
-    for (uint32_t i = 0; i < P; ++i) {
-        h_box[i] = prk::pose_pixel_box(g->aabb_host, h_poses[i].m, job.proj, W, H, job.roi);
-        const int4 &b = h_box[i];
-        max_area = std::max(max_area, (size_t)std::max(0, b.z - b.x + 1) * (size_t)std::max(0, b.w - b.y + 1));   // an off-screen pose has an empty box
-    }
-    // capacity per hypothesis (the clouds themselves are packed: PoseMeta::start; a multiple of the packing's alignment, so that no sum of rounded sizes exceeds P x cstride)
-    const size_t cstride = prk::kCloudAlign ? ((max_area + prk::kCloudAlign - 1) / prk::kCloudAlign) * prk::kCloudAlign : ((max_area + 3) & ~(size_t)3);
-    const uint32_t steps = (uint32_t)std::max(1, opt.steps);
-    const uint32_t ppb = steps * prk::kPointsPerStep;
-    const uint32_t nblk = (uint32_t)((max_area + ppb - 1) / ppb);       // bound from the pixel boxes: capacity of the partial sums
-    // grid: one workgroup per block of the largest cloud of the previous batch (workgroups loop if this batch's clouds are
-    // larger, surplus workgroups exit at once); the box bound itself would launch ~60 % empty workgroups (-2.5 % poses/s)
-    const uint32_t grid_x = g->cloud_hint ? std::min(nblk, (g->cloud_hint + ppb - 1) / ppb) : nblk;
-
-    // Large batches run as consecutive sub-batches that reuse the same depth / cloud / partial-sum memory: the clouds of
-    // <= 512 hypotheses (~140 MB touched) stay in the 256 MiB Infinity Cache over their 21 passes (1024 poses as one batch:
-    // 199 k poses/s, as 2 x 512: see DESIGN.md)
-    // ... and, for large frames, small enough that the depth workspace of a sub-batch stays within ~4 GiB (as the synchronous path
-    // bounds its chunks) and the clouds within 2^30 points (offsets are 32-bit): 64 hypotheses per sub-batch at 4096 x 4096, all 512 up to 2 M pixels
-    uint32_t sub_cap = (uint32_t)std::max(32, opt.sub_batch);
-    sub_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>({ (size_t)sub_cap, ((size_t)4 << 30) / (img * sizeof(int32_t)), ((size_t)1 << 30) / cstride }));     // (2^30 cloud points per sub-batch: 12 GiB of clouds, 24 GiB of kd-tree search state at most)
-    const uint32_t n_sub = (P + sub_cap - 1) / sub_cap;
-    const uint32_t sub = (P + n_sub - 1) / n_sub;
-    PR_TRY(sl.depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * sub));
-    // the pixel boxes of a sub-batch packed into the depth workspace: box i at h_off[i] ints, its own width as pitch (fill_box_kernel)
-    uint32_t *h_off = reinterpret_cast<uint32_t *>(sl.h_in.as<unsigned char>() + in.off);
-    if (prk::kBoxPack) {
-        size_t acc = 0;
-        for (uint32_t i = 0; i < P; ++i) {
-            if (i % sub == 0) acc = 0;
-            const int4 &b = h_box[i];
-            const size_t area = (size_t)std::max(0, b.z - b.x + 1) * (size_t)std::max(0, b.w - b.y + 1);
-            h_off[i] = (uint32_t)acc;
-            acc += (area + prk::kBoxPack - 1) / prk::kBoxPack * prk::kBoxPack;
-        }
-    }
-    PR_TRY(sl.row_count.ensure(sizeof(uint32_t) * (size_t)H * sub));
-    PR_TRY(sl.row_off.ensure(sizeof(uint32_t) * (size_t)H * sub));
+    return chk;
+}
+// What the phases of one asynchronous batch share: the batch, its plan and where its parts live on the device.
+struct AsyncBatch {
+    Slot &sl; const RefineJob &job; uint32_t P;
+    SceneSel sc; AsyncPlan pl{}; NNLayout nl{}; prk::BatchCheck chk{};
+    uint32_t *nn_prev = nullptr;                                  // kd-tree scene: the search workspace (nn_layout), or null
+    pr_result *dres = nullptr;
+    bool timed = false, tight = false, pipeline_start = true;
+    pr_mat4 *d_poses = nullptr; int4 *d_box = nullptr; uint32_t *d_off = nullptr;      // SlotIn on the device
+    const pr_triangle *raster_tris = nullptr;
+    int workspaces(); int stage(); int sub_batch(uint32_t q0, uint32_t nq);
+};
+// the slot's workspaces for the plan (the depth workspace, which the plan's offsets index, first)
+int AsyncBatch::workspaces()
+{
+    const uint32_t sub = pl.sub;
+    PR_TRY(sl.depth.ensure(sizeof(int32_t) * ((size_t)job.W * job.H + prk::kBoxPack) * sub));
+    PR_TRY(sl.row_count.ensure(sizeof(uint32_t) * (size_t)job.H * sub));
+    PR_TRY(sl.row_off.ensure(sizeof(uint32_t) * (size_t)job.H * sub));
     PR_TRY(sl.counts.ensure(sizeof(uint32_t) * P));
-    PR_TRY(sl.cloud.ensure(sizeof(pr_vec3) * cstride * sub));
+    PR_TRY(sl.cloud.ensure(sizeof(pr_vec3) * pl.cstride * sub));
     PR_TRY(sl.meta.ensure(sizeof(prk::PoseMeta) * P));
-    PR_TRY(sl.partial.ensure(sizeof(float) * prk::kAccStride * (size_t)nblk * sub));
+    PR_TRY(sl.partial.ensure(sizeof(float) * prk::kAccStride * (size_t)pl.nblk * sub));
     PR_TRY(sl.dstate.ensure(sizeof(prk::DevIcpState) * P));
     PR_TRY(sl.arrive.ensure(sizeof(uint32_t) * P));
-    pr_result *dres = job.results_dev;
+    dres = job.results_dev;
     if (!dres) { PR_TRY(sl.dresults.ensure(sizeof(pr_result) * P)); dres = sl.dresults.as<pr_result>(); }
     // kd-tree scene: the workspace (nn_layout, as icp_drive) indexed like the clouds of one sub-batch; the search kernel's grid comes from the
     // box bound, surplus workgroups exit at once
-    uint32_t *nn_prev = nullptr;
-    const NNLayout nl = nn_layout(cstride * (size_t)sub, sub);
+    nl = nn_layout(pl.cstride * (size_t)sub, sub);
     if (sc.kind == PR_SCENE_NN) {
         sc.nn_split = nn_split_for(sc);
-        sc.nn_max_points = (uint32_t)std::min<size_t>(max_area, 0xffffffffu);
+        sc.nn_max_points = (uint32_t)std::min<size_t>(pl.max_area, 0xffffffffu);
         if (sc.nn.rec32 && (opt.nn_seed || sc.nn_split)) {
             PR_TRY(sl.nn_prev.ensure(nl.bytes));
             nn_prev = sl.nn_prev.as<uint32_t>();
         }
     }
-
+    return PR_OK;
+}
+// the inputs onto the device, behind the other slot's release point
+int AsyncBatch::stage()
+{
+    const SlotIn in(P);
     hipStream_t st = sl.stream;
-    // A TIMED batch (profile 3) stays asynchronous: its render runs under the other slot's loop like any other, but its own loop waits
-    // until the other slot's batch is complete, runs as ONE pose group, lets the other slot's next render start only when it has
-    // finished, and carries HIP events around every launch -- the timed launches have the chip to themselves as in the synchronous timed
-    // path (profile 1), without that path's host round trips and its idle render.
-    const bool timed = (opt.profile == 3);
-    sl.timed = timed; sl.t_used = 0; sl.t_spans.clear();
-    // A batch submitted while the other slot is idle starts a pipeline.  Option start_overlap says when the NEXT batch's render may start
-    // in that case: -1 (default) = by the rule below, like any other batch; a pass number releases it earlier (see the option's note).
-    bool pipeline_start = true;
-    for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered) pipeline_start = false;
-    // a failed event creation or record drops the TIMING of this batch (never the batch): t_fail, checked when everything is enqueued
-    bool t_fail = false;
-    auto t_event = [&]() -> size_t {
-        if (sl.t_used == sl.t_events.size()) {
-            hipEvent_t e = nullptr;
-            if (hipEventCreate(&e) != hipSuccess || !e) { (void)hipGetLastError(); t_fail = true; return kNoEvent; }
-            sl.t_events.push_back(e);
-        }
-        return sl.t_used++;
-    };
-    auto t_record = [&](size_t e) { if (e == kNoEvent) { t_fail = true; return; } if (hipEventRecord(sl.t_events[e], st) != hipSuccess) { (void)hipGetLastError(); t_fail = true; } };
-    auto t_begin = [&]() -> size_t { const size_t e = t_event(); t_record(e); return e; };
-    auto t_end = [&](size_t e0, int kind, uint32_t q0, uint32_t nq, bool edge) { const size_t e1 = t_event(); t_record(e1); if (!t_fail) sl.t_spans.push_back({ e0, e1, kind, q0, nq, edge, false, { 0, 0, 0 } }); };
-    pr_mat4 *d_poses = sl.poses_bbox.as<pr_mat4>();
-    int4 *d_box = reinterpret_cast<int4 *>(sl.poses_bbox.as<unsigned char>() + in.box);
-    const uint32_t *d_off = prk::kBoxPack ? reinterpret_cast<const uint32_t *>(sl.poses_bbox.as<unsigned char>() + in.off) : nullptr;
-    // Both phases are bound by the same units, so a batch that renders while the other slot is in the middle of its ICP loop
-    // slows that loop by more than it gains; its render is therefore held back until the other slot has issued pass
-    // `overlap_pass` of its (last sub-batch's) loop -- late enough to disturb little, early enough that the GPU never idles.
+    d_poses = sl.poses_bbox.as<pr_mat4>();
+    d_box = reinterpret_cast<int4 *>(sl.poses_bbox.as<unsigned char>() + in.box);
+    d_off = reinterpret_cast<uint32_t *>(sl.poses_bbox.as<unsigned char>() + in.off);
+    // this batch's render is held back until the other slot has issued the release pass of its loop (release_pass_for)
     for (Slot &o : g->slots)
         if (&o != &sl && o.pending && !o.delivered && o.progress_valid) HIP_TRY(hipStreamWaitEvent(st, o.progress, 0));
     sl.progress_valid = false;
@@ -1148,91 +1060,114 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
     // device each is replaced by its intersection with the hull of the mesh's projected vertices (57 % of the pixels for obj_06), and the packed
     // offsets of each sub-batch are formed again from those: what fill, raster, count and emit then walk.  Never larger than the loose box, so
     // every capacity holds; no host round trip.  Needs the context's vertex list (ensure_model_box: from the buffer's second batch on).
-    const bool tight = opt.tight_box && g->mesh_sorted_valid && g->mesh_verts_n > 0;
+    tight = opt.tight_box && g->mesh_sorted_valid && g->mesh_verts_n > 0;
     if (tight) {
-        HIP_TRY(prk::launch_tight_boxes(g->mesh_verts.as<float4>(), g->mesh_verts_n, d_poses, P, job.proj, W, H, d_box, st));
+        HIP_TRY(prk::launch_tight_boxes(g->mesh_verts.as<float4>(), g->mesh_verts_n, d_poses, P, job.proj, job.W, job.H, d_box, st));
         g_tight_batches.fetch_add(1);
     }
-    const bool fused = opt.fused_solve != 0;
-    const pr_roi none{ 0, 0, 0, 0 };                              // the ROI is already part of the host-computed boxes
-    const Lanes lanes{ sl.stream, sl.side, sl.fork, sl.join };
     // the raster's triangles: the context's ordered copy (same triangles, same minima; the first render's checks read the caller's buffer)
-    const pr_triangle *raster_tris = (opt.mesh_order && g->mesh_sorted_valid) ? g->mesh_sorted.as<pr_triangle>() : job.tris;
-    for (uint32_t q0 = 0; q0 < P; q0 += sub) {
-        const uint32_t nq = std::min(sub, P - q0);
-        prk::PoseMeta *meta = sl.meta.as<prk::PoseMeta>() + q0;
-        prk::DevIcpState *dstate = sl.dstate.as<prk::DevIcpState>() + q0;
-        uint32_t *arrive = sl.arrive.as<uint32_t>() + q0;
-        size_t te = timed ? t_begin() : 0;
-        // (the first render carries the batch's checks: the fingerprint's expected value belongs to the scene build, so the scene comes first --
-        // an event that is complete when recorded unless a cache missed)
-        // (ADVICE r05 asked whether this wait costs a rebuilt scene its overlap with the render: it does not -- make_scene reads the rebuilt form's
-        // `exact` flag / tree depth back before it returns, so a rebuild has finished on the host's clock before the render is even enqueued; on a
-        // cache hit the event is complete when recorded)
-        if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
-        if (tight && d_off) HIP_TRY(prk::launch_box_pack_offsets(d_box + q0, nq, const_cast<uint32_t *>(d_off) + q0, st));
-        HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)job.n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
-                                         sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, job.proj, none, st,
-                                         /*compute_boxes=*/false, meta, dstate, arrive, (uint32_t)cstride, d_off ? d_off + q0 : nullptr, q0 == 0 ? &chk : nullptr));
-        if (timed) { t_end(te, kSpanRender, q0, nq, false); te = t_begin(); }
-        HIP_TRY(prk::launch_emit_box(sl.depth.as<int32_t>(), nq, W, H, d_box + q0, K[0], K[4], K[2], K[5], sl.row_count.as<uint32_t>(),
-                                     sl.row_off.as<uint32_t>(), sl.cloud.as<pr_vec3>(), cstride, st, prk::kCloudAlign ? meta : nullptr, d_off ? d_off + q0 : nullptr));
-        if (timed) t_end(te, kSpanCloud, q0, nq, false);
-        if (timed && q0 == 0)                                     // the timed loop starts when the other slot's batch is complete
-            for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered && o.done) HIP_TRY(hipStreamWaitEvent(st, o.done, 0));
+    raster_tris = (opt.mesh_order && g->mesh_sorted_valid) ? g->mesh_sorted.as<pr_triangle>() : job.tris;
+    return PR_OK;
+}
+// one sub-batch, hypotheses [q0, q0 + nq): render, emit, the iteration loop
+int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
+{
+    const uint32_t W = job.W, H = job.H;
+    const float *K = job.K;
+    hipStream_t st = sl.stream;
+    prk::PoseMeta *meta = sl.meta.as<prk::PoseMeta>() + q0;
+    prk::DevIcpState *dstate = sl.dstate.as<prk::DevIcpState>() + q0;
+    uint32_t *arrive = sl.arrive.as<uint32_t>() + q0;
+    const pr_roi none{ 0, 0, 0, 0 };                              // the ROI is already part of the host-computed boxes
+    size_t te = timed ? sl.spans.begin(st) : kNoEvent;
+    // (the first render carries the batch's checks: the fingerprint's expected value belongs to the scene build, so the scene comes first --
+    // an event that is complete when recorded unless a cache missed)
+    // (ADVICE r05 asked whether this wait costs a rebuilt scene its overlap with the render: it does not -- make_scene reads the rebuilt form's
+    // `exact` flag / tree depth back before it returns, so a rebuild has finished on the host's clock before the render is even enqueued; on a
+    // cache hit the event is complete when recorded)
+    if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
+    if (tight) HIP_TRY(prk::launch_box_pack_offsets(d_box + q0, nq, d_off + q0, st));
+    HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)job.n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
+                                     sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, job.proj, none, st,
+                                     /*compute_boxes=*/false, meta, dstate, arrive, d_off + q0, q0 == 0 ? &chk : nullptr));
+    if (timed) { sl.spans.end(te, kSpanRender, q0, nq, false, st); te = sl.spans.begin(st); }
+    HIP_TRY(prk::launch_emit_box(sl.depth.as<int32_t>(), nq, W, H, d_box + q0, K[0], K[4], K[2], K[5], sl.row_count.as<uint32_t>(),
+                                 sl.row_off.as<uint32_t>(), sl.cloud.as<pr_vec3>(), meta, st, d_off + q0));
+    if (timed) sl.spans.end(te, kSpanCloud, q0, nq, false, st);
+    if (timed && q0 == 0)                                     // the timed loop starts when the other slot's batch is complete
+        for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered && o.done) HIP_TRY(hipStreamWaitEvent(st, o.done, 0));
 
-        const uint32_t n_groups = pose_group_count(scene_kind, nq, timed);
-        if (nn_prev) HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(nn_prev + nl.qcount), (size_t)prk::kQCountStride * nq, 0, st));
-        // When may the OTHER slot start rendering?  Measured optimum (21 passes of obj_06, overlap_pass swept per batch size):
-        // pass 4 or earlier at 128 hypotheses, 9-10 at 256, 14-16 at 384, 16 at 512 -- i.e. when about 2800 hypothesis-passes of
-        // this loop are left (never fewer than 5 passes): that much loop work is what a render hides behind without stretching the
-        // passes it runs beside.  The render's own weight scales that figure: triangles per hypothesis against cloud points per
-        // hypothesis (31 468 and 27 400 there; cloud_hint = the largest cloud of the previous batch).
-        uint32_t auto_overlap = 0;
-        {
-            const double weight = ((double)std::max<size_t>(job.n_tris, 1) / 31468.0) * (27400.0 / (double)std::max(g->cloud_hint, 1000u));
-            double left = std::max(5.0, 2800.0 * weight / (double)std::max(nq, 1u));   // passes of this sub-batch's loop still to run
-            // Since the clouds are packed (end of round 4) a render disturbs the loop beside it less, as long as the clouds of BOTH slots stay in
-            // the 256 MiB Infinity Cache: then the render is released with 13 passes to go (256 hypotheses: passes 5-9 give 272 k poses/s, the rule
-            // above -- pass 10 -- 268 k; 384: pass 8 277 k against 272 k at 14; 512, whose two slots' clouds do not fit: 275 k at pass 16, 263 k at 10).
-            if (2.0 * (double)nq * (double)std::max(g->cloud_hint, 1000u) * sizeof(pr_vec3) <= 240.0e6) left = std::max(left, 13.0);
-            const double passes = (double)crit.max_iteration + 1.0;
-            auto_overlap = left >= passes ? 0u : (uint32_t)(passes - left + 0.5);
-            // kd-tree scenes: the loop is seven times a render and its first passes are the heavy ones -- the other slot's render (and with it
-            // that slot's own first passes) should start at once: 37.3 / 37.5 k against 36.0 k poses/s for the rule above (pass 1 / 2 / 3 / 6: 37.2 /
-            // 37.2 / 37.1 / 37.0 k; 10: 35.7 k; 16: 34.0 k)
-            if (scene_kind == PR_SCENE_NN) auto_overlap = 0u;
-        }
-        prk::IcpBatch b{};
-        b.cloud = sl.cloud.as<pr_vec3>(); b.partial = sl.partial.as<float>(); b.nblk = nblk; b.grid_x = grid_x; b.steps = steps;
-        if (nn_prev) nn_carve(b, nn_prev, nl);
-        const uint32_t last_pass = (uint32_t)crit.max_iteration;
-        auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t gs) -> int {
-            if (!timed) { HIP_TRY(launch_pass(bb, sc, np, gs)); return PR_OK; }
-            const size_t e0 = t_begin();                             // (one group: gs == st)
-            // a kd-tree pass is four kernels: three more events between them give each kernel's own time (pr_profile_nn)
-            const bool marks = sc.kind == PR_SCENE_NN && sc.nn_split && bb.nn_prev && np <= 32768u;
-            size_t mi[3] = { 0, 0, 0 }; hipEvent_t me[3] = { nullptr, nullptr, nullptr };
-            bool marks_ok = marks;
-            if (marks) for (int k = 0; k < 3; ++k) { mi[k] = t_event(); if (mi[k] == kNoEvent) marks_ok = false; else me[k] = sl.t_events[mi[k]]; }
-            HIP_TRY(launch_pass(bb, sc, np, gs, marks_ok ? me : nullptr));
-            t_end(e0, kSpanIcp, q0 + p0, np, bb.iter == 0 || bb.iter == last_pass);
-            if (marks_ok && !t_fail) { Slot::TSpan &ts = sl.t_spans.back(); ts.marks = true; for (int k = 0; k < 3; ++k) ts.m[k] = mi[k]; }
-            return PR_OK;
-        };
-        // the pass of the batch's last sub-batch behind which the other slot's render may start: a timed batch's last, else the options, else the rule above
-        const uint32_t release_pass = timed ? last_pass : std::min<uint32_t>(last_pass, (pipeline_start && opt.start_overlap >= 0) ? (uint32_t)opt.start_overlap : (opt.overlap_pass >= 0 ? (uint32_t)opt.overlap_pass : auto_overlap));
-        auto after = [&](uint32_t it, bool &) -> int {
-            if (q0 + sub >= P && it == release_pass) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
-            return PR_OK;
-        };
-        // the iteration loop: (max_iteration+1) x [pass (+ fused finalize/solve)], pose groups on the slot's side streams
-        PR_TRY(device_solve_loop(lanes, n_groups, b, nq, crit, fused, meta, dstate, arrive, pass, after));
+    const uint32_t n_groups = pose_group_count(job.scene_kind, nq, timed);
+    if (nn_prev) HIP_TRY(prk::launch_fill_i32(reinterpret_cast<int32_t *>(nn_prev + nl.qcount), (size_t)prk::kQCountStride * nq, 0, st));
+    prk::IcpBatch b{};
+    b.cloud = sl.cloud.as<pr_vec3>(); b.partial = sl.partial.as<float>(); b.nblk = pl.nblk; b.grid_x = pl.grid_x; b.steps = pl.steps;
+    if (nn_prev) nn_carve(b, nn_prev, nl);
+    const uint32_t last_pass = (uint32_t)job.crit.max_iteration;
+    auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t gs) -> int {
+        if (!timed) { HIP_TRY(launch_pass(bb, sc, np, gs)); return PR_OK; }
+        const size_t e0 = sl.spans.begin(st);                    // (one group: gs == st)
+        // a kd-tree pass is four kernels: three more events between them give each kernel's own time (pr_profile_nn)
+        size_t mi[3] = { 0, 0, 0 }; hipEvent_t me[3] = { nullptr, nullptr, nullptr };
+        const bool marks = sc.kind == PR_SCENE_NN && sc.nn_split && bb.nn_prev && np <= 32768u && sl.spans.reserve_marks(mi, me);
+        HIP_TRY(launch_pass(bb, sc, np, gs, marks ? me : nullptr));
+        sl.spans.end(e0, kSpanIcp, q0 + p0, np, bb.iter == 0 || bb.iter == last_pass, st, marks ? mi : nullptr);
+        return PR_OK;
+    };
+    // the pass of the batch's last sub-batch behind which the other slot's render may start
+    const uint32_t release_pass = release_pass_for(job.n_tris, nq, g->cloud_hint, job.crit, job.scene_kind, timed, pipeline_start, opt.start_overlap, opt.overlap_pass);
+    auto after = [&](uint32_t it, bool &) -> int {
+        if (q0 + pl.sub >= P && it == release_pass) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
+        return PR_OK;
+    };
+    // the iteration loop: (max_iteration+1) x [pass (+ fused finalize/solve)], pose groups on the slot's side streams
+    const Lanes lanes{ sl.stream, sl.side, sl.fork, sl.join };
+    return device_solve_loop(lanes, n_groups, b, nq, job.crit, opt.fused_solve != 0, meta, dstate, arrive, pass, after);
+}
+// everything of a batch onto the slot's streams; the poses are in sl.h_in already (refine_submit).  Streams and scene, plan, workspaces, staging,
+// then sub-batch by sub-batch render -> emit -> loop, the export and the done event.
+int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *results_host)
+{
+    AsyncBatch a{ sl, job, P };
+    hipStream_t scene_stream = nullptr;
+    PR_TRY(async_scene(sl, job, P, a.sc, scene_stream));
+    PR_TRY(ensure_model_box(job.tris, job.n_tris));             // once per triangle buffer ...
+    const SlotIn in(P);
+    const SlotOut out(P);
+    PR_TRY(sl.h_out.ensure(out.bytes));
+    unsigned char *h_out_dev = sl.h_out.dev_as<unsigned char>();  // the pinned block as the device sees it
+    HIP_TRY(hipEventRecord(sl.scene_ready, scene_stream));      // (complete as it is recorded unless a cache missed and the scene is being rebuilt on this stream)
+    // ... and checked against the buffer's present content by every batch, together with the scene caches (batch_check)
+    const bool keys_new = sl.aabb_keys.p == nullptr;
+    PR_TRY(sl.aabb_keys.ensure(prk::kBatchCheckWords * sizeof(uint32_t)));
+    if (keys_new) {                                               // armed once; the last workgroup of every check re-arms the words itself
+        HIP_TRY(hipMemsetAsync(sl.aabb_keys.p, 0xff, 6 * sizeof(uint32_t), sl.stream));
+        HIP_TRY(hipMemsetAsync(sl.aabb_keys.as<uint32_t>() + 6, 0, (prk::kBatchCheckWords - 6) * sizeof(uint32_t), sl.stream));
     }
-    HIP_TRY(prk::launch_pack_export(sl.dstate.as<prk::DevIcpState>(), dres, sl.counts.as<uint32_t>(), reinterpret_cast<uint32_t *>(h_out_dev),
-                                    results_host ? reinterpret_cast<pr_result *>(h_out_dev + out.res) : nullptr, P, st));
-    HIP_TRY(hipEventRecord(sl.done, st));
-    if (t_fail) { sl.timed = false; sl.t_spans.clear(); sl.t_used = 0; g->stat_timing_dropped++; }   // the batch runs; its timing is dropped, and counted
+    *reinterpret_cast<volatile uint32_t *>(sl.h_out.as<unsigned char>() + out.flag) = 0u;
+    a.chk = batch_check(sl, job, a.sc, reinterpret_cast<uint32_t *>(h_out_dev + out.flag));
+
+    // the plan (SlotIn: poses | pixel boxes | offsets of the packed boxes): the host computes the boxes, the largest one sizes the clouds and the grid
+    PR_TRY(sl.poses_bbox.ensure(in.bytes + 16));
+    const pr_mat4 *h_poses = sl.h_in.as<pr_mat4>();
+    int4 *h_box = reinterpret_cast<int4 *>(sl.h_in.as<unsigned char>() + in.box);
+    for (uint32_t i = 0; i < P; ++i) h_box[i] = prk::pose_pixel_box(g->aabb_host, h_poses[i].m, job.proj, job.W, job.H, job.roi);
+    a.pl = plan_async(P, job.W, job.H, h_box, opt.steps, opt.sub_batch, g->cloud_hint, reinterpret_cast<uint32_t *>(sl.h_in.as<unsigned char>() + in.off));
+    PR_TRY(a.workspaces());
+
+    // A TIMED batch (profile 3) stays asynchronous: its render runs under the other slot's loop like any other, but its own loop waits
+    // until the other slot's batch is complete, runs as ONE pose group, lets the other slot's next render start only when it has
+    // finished, and carries HIP events around every launch (sl.spans) -- the timed launches have the chip to themselves as in the synchronous
+    // timed path (profile 1), without that path's host round trips and its idle render.
+    a.timed = sl.timed = (opt.profile == 3);
+    sl.spans.reset();
+    // A batch submitted while the other slot is idle starts a pipeline.  Option start_overlap says when the NEXT batch's render may start
+    // in that case: -1 (default) = by release_pass_for's rule, like any other batch; a pass number releases it earlier (see the option's note).
+    for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered) a.pipeline_start = false;
+    PR_TRY(a.stage());
+    for (uint32_t q0 = 0; q0 < P; q0 += a.pl.sub) PR_TRY(a.sub_batch(q0, std::min(a.pl.sub, P - q0)));
+    HIP_TRY(prk::launch_pack_export(sl.dstate.as<prk::DevIcpState>(), a.dres, sl.counts.as<uint32_t>(), reinterpret_cast<uint32_t *>(h_out_dev),
+                                    results_host ? reinterpret_cast<pr_result *>(h_out_dev + out.res) : nullptr, P, sl.stream));
+    HIP_TRY(hipEventRecord(sl.done, sl.stream));
     return PR_OK;
 }
 

@@ -25,6 +25,7 @@
 
 #include "pr_internal.h"
 #include "pr_tuning.h"
+#include "pose_box.h"
 
 namespace prh {
 extern thread_local std::string g_err;
@@ -144,14 +145,14 @@ struct Options {
     int nn_run = 8;                  // 256-point chunks a workgroup of the search kernel walks (1..8).  Since the window scans left that kernel (round 4) it is a light
                                      // streaming pass and fewer, longer workgroups are a little better: 38.9 k (2) against 39.3 k (8) poses/s over five runs each
     int nn_grid = 1;                 // fused path: pixel grid of the scene points (seeds + window search); 0 = tree only
-    int host_poll = 1;               // PR_SOLVE_HOST with the sums stored straight into pinned memory: 1 = the host polls per-hypothesis tags and solves each hypothesis as its sums arrive; 0 = it waits for the stream, then solves the group (rounds 2-5)
+    int host_poll = 1;               // PR_SOLVE_HOST with the sums stored straight into pinned memory: 1 = the host polls ONE flag per pose group (stored by the workgroup that delivers the group's last hypothesis) and solves the group while its launch winds down; 0 = it waits for the stream, then solves the group (rounds 2-5)
     int nn_count = 0;                // instrumented runs: the search kernel counts its work per pass (pr_nn_counters)
     int start_overlap = -1;          // asynchronous path, a batch submitted while the other slot is idle: the pass after which the next batch's render may start.
                                      // -1 = the per-batch rule of a running pipeline.  Rounds 2-3 released the next render at pass 0 here; with the roofline
                                      // sample out of the timed region that reads 239 / 240 / 251 k against 253 / 253 / 256 k poses/s for the rule in three
                                      // alternating 20-step runs on one box: batches 1 and 2 then finish together and the third finds an empty chip
     int overlap_pass = -1;           // asynchronous path: the other slot's render may start once this slot has issued this pass of its loop; -1 = chosen per batch
-                                     // (refine_submit_async: with 13 passes to go while both slots' clouds fit the Infinity Cache, later by the render's weight when
+                                     // (release_pass_for: with 13 passes to go while both slots' clouds fit the Infinity Cache, later by the render's weight when
                                      // they do not; kd-tree scenes: pass 0)
     int sub_batch = 512;             // asynchronous fused path: hypotheses per sub-batch (cache residency of the clouds)
     int fused_solve = 1;             // PR_SOLVE_DEVICE: the workgroup delivering a hypothesis' last partial sum also runs its finalize + solve (no second launch per iteration)
@@ -403,6 +404,105 @@ inline void nn_carve(prk::IcpBatch &b, uint32_t *base, const NNLayout &l)
     b.nn_prev = base + l.winners; b.nn_slack = reinterpret_cast<float *>(base + l.slack);
     b.nn_queue = reinterpret_cast<uint2 *>(base + l.queue); b.nn_queue2 = reinterpret_cast<uint2 *>(base + l.queue2); b.nn_qcount = base + l.qcount;
 }
+// ---- the sizes of one asynchronous batch, from the host's pixel boxes alone -------------------------------------------------------------
+// What refine_submit_async needs before anything of the batch has run: the capacity of a cloud, the grid of the passes, the sub-batch split and
+// where every box sits in its sub-batch's depth workspace.  No HIP call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.
+struct AsyncPlan {
+    size_t max_area, cstride;        // pixels of the largest box (at least 1), which bounds every cloud; the host's capacity bound per hypothesis, in points (the clouds themselves are packed: PoseMeta::start)
+    uint32_t steps, nblk, grid_x;    // 1024-point steps per workgroup; blocks a hypothesis may have (capacity of the partial sums); workgroups per hypothesis
+    uint32_t sub, n_sub;             // hypotheses per sub-batch, sub-batches
+};
+// boxes: the P host-computed pixel boxes; box_off (P words out): box i at box_off[i] ints of its sub-batch's depth workspace, its own width as
+// pitch (fill_box_kernel) -- the offsets restart at every sub-batch
+inline AsyncPlan plan_async(uint32_t P, uint32_t W, uint32_t H, const int4 *boxes, int opt_steps, int opt_sub_batch, uint32_t cloud_hint, uint32_t *box_off)
+{
+    AsyncPlan pl{};
+    const size_t img = (size_t)W * H;
+    pl.max_area = 1;
+    for (uint32_t i = 0; i < P; ++i) pl.max_area = std::max<size_t>(pl.max_area, prk::box_area(boxes[i]));   // an off-screen pose has an empty box
+    // capacity per hypothesis (a multiple of the packing's alignment, so that no sum of rounded sizes exceeds P x cstride)
+    pl.cstride = prk::cloud_slot((uint32_t)pl.max_area);
+    pl.steps = (uint32_t)std::max(1, opt_steps);
+    const uint32_t ppb = pl.steps * prk::kPointsPerStep;
+    pl.nblk = (uint32_t)((pl.max_area + ppb - 1) / ppb);       // bound from the pixel boxes: capacity of the partial sums
+    // grid: one workgroup per block of the largest cloud of the previous batch (workgroups loop if this batch's clouds are
+    // larger, surplus workgroups exit at once); the box bound itself would launch ~60 % empty workgroups (-2.5 % poses/s)
+    pl.grid_x = cloud_hint ? std::min(pl.nblk, (cloud_hint + ppb - 1) / ppb) : pl.nblk;
+
+    // Large batches run as consecutive sub-batches that reuse the same depth / cloud / partial-sum memory: the clouds of
+    // <= 512 hypotheses (~140 MB touched) stay in the 256 MiB Infinity Cache over their 21 passes (1024 poses as one batch:
+    // 199 k poses/s, as 2 x 512: see DESIGN.md)
+    // ... and, for large frames, small enough that the depth workspace of a sub-batch stays within ~4 GiB (as the synchronous path
+    // bounds its chunks) and the clouds within 2^30 points (offsets are 32-bit): 64 hypotheses per sub-batch at 4096 x 4096, all 512 up to 2 M pixels
+    uint32_t sub_cap = (uint32_t)std::max(32, opt_sub_batch);
+    sub_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>({ (size_t)sub_cap, ((size_t)4 << 30) / (img * sizeof(int32_t)), ((size_t)1 << 30) / pl.cstride }));     // (2^30 cloud points per sub-batch: 12 GiB of clouds, 24 GiB of kd-tree search state at most)
+    pl.n_sub = (P + sub_cap - 1) / sub_cap;
+    pl.sub = pl.n_sub ? (P + pl.n_sub - 1) / pl.n_sub : 0;
+    size_t acc = 0;
+    for (uint32_t i = 0; i < P; ++i) {
+        if (i % pl.sub == 0) acc = 0;
+        box_off[i] = (uint32_t)acc;
+        acc += prk::box_slot(prk::box_area(boxes[i]));
+    }
+    return pl;
+}
+// When may the OTHER slot start rendering?  The pass of a (sub-)batch's loop behind which its render is released: a timed batch's last, else the
+// options (start_overlap for a batch that starts a pipeline, overlap_pass), else the rule below.  No HIP call in here.
+// Both phases are bound by the same units, so a batch that renders while the other slot is in the middle of its ICP loop
+// slows that loop by more than it gains; its render is therefore held back until the other slot has issued this pass
+// of its (last sub-batch's) loop -- late enough to disturb little, early enough that the GPU never idles.
+inline uint32_t release_pass_for(size_t n_tris, uint32_t nq, uint32_t cloud_hint, pr_criteria crit, int scene_kind, bool timed, bool pipeline_start,
+                                 int start_overlap, int overlap_pass)
+{
+    const uint32_t last_pass = (uint32_t)crit.max_iteration;
+    if (timed) return last_pass;
+    if (pipeline_start && start_overlap >= 0) return std::min(last_pass, (uint32_t)start_overlap);
+    if (overlap_pass >= 0) return std::min(last_pass, (uint32_t)overlap_pass);
+    // Measured optimum (21 passes of obj_06, overlap_pass swept per batch size):
+    // pass 4 or earlier at 128 hypotheses, 9-10 at 256, 14-16 at 384, 16 at 512 -- i.e. when about 2800 hypothesis-passes of
+    // this loop are left (never fewer than 5 passes): that much loop work is what a render hides behind without stretching the
+    // passes it runs beside.  The render's own weight scales that figure: triangles per hypothesis against cloud points per
+    // hypothesis (31 468 and 27 400 there; cloud_hint = the largest cloud of the previous batch).
+    const double weight = ((double)std::max<size_t>(n_tris, 1) / 31468.0) * (27400.0 / (double)std::max(cloud_hint, 1000u));
+    double left = std::max(5.0, 2800.0 * weight / (double)std::max(nq, 1u));   // passes of this sub-batch's loop still to run
+    // Since the clouds are packed (end of round 4) a render disturbs the loop beside it less, as long as the clouds of BOTH slots stay in
+    // the 256 MiB Infinity Cache: then the render is released with 13 passes to go (256 hypotheses: passes 5-9 give 272 k poses/s, the rule
+    // above -- pass 10 -- 268 k; 384: pass 8 277 k against 272 k at 14; 512, whose two slots' clouds do not fit: 275 k at pass 16, 263 k at 10).
+    if (2.0 * (double)nq * (double)std::max(cloud_hint, 1000u) * sizeof(pr_vec3) <= 240.0e6) left = std::max(left, 13.0);
+    const double passes = (double)crit.max_iteration + 1.0;
+    uint32_t auto_overlap = left >= passes ? 0u : (uint32_t)(passes - left + 0.5);
+    // kd-tree scenes: the loop is seven times a render and its first passes are the heavy ones -- the other slot's render (and with it
+    // that slot's own first passes) should start at once: 37.3 / 37.5 k against 36.0 k poses/s for the rule above (pass 1 / 2 / 3 / 6: 37.2 /
+    // 37.2 / 37.1 / 37.0 k; 10: 35.7 k; 16: 34.0 k)
+    if (scene_kind == PR_SCENE_NN) auto_overlap = 0u;
+    return std::min(last_pass, auto_overlap);
+}
+// ---- profiling spans: pooled HIP events around launches, turned into the context's accounts -------------------------------------------
+// One recorder for the context's own stream (SpanGuard) and one per asynchronous slot (a TIMED batch, option profile = 3).  A span is a start /
+// stop pair in enqueue order; a kd-tree pass may carry three marks between its four kernels.  drain() -- once the stream has been waited for --
+// adds every span to the calling thread's context (render_ms, cloud_ms, icp_ms, icp_launches, icp_points, icp_bytes, the launch list, the
+// kd-tree parts) and hands the events back to the pool.
+// Failure policy, the same for both owners: a failed event call costs the SPAN it belongs to (failed marks: the span's kd-tree parts), dropped
+// and counted once (pr_stats) -- never the launches between the events: the batch itself always runs.  (HIP_TRY would clear the sticky error
+// and return: the span is dropped HERE instead.)
+enum { kSpanIcp = 0, kSpanRender = 1, kSpanCloud = 2 };
+constexpr size_t kNoEvent = (size_t)-1;
+// algorithmic bytes per point of a correspondence pass: 12 read + 24 gathered, + 12 written back once a transform is pending; an EDGE
+// pass -- the first, or a score-only last one, which needs the scene point but not its normal (12 + 12 + 12) -- moves 36
+inline uint64_t icp_span_bytes(uint64_t points, bool edge) { return points * (edge ? 36u : 48u); }
+struct Spans {
+    struct Span { size_t e0, e1; int kind; uint32_t q0, nq; bool edge, marks; size_t m[3]; };   // q0, nq: the hypotheses of an ICP span (drain's points_of)
+    std::vector<hipEvent_t> pool;    // reused from batch to batch
+    size_t used = 0;
+    std::vector<Span> spans;
+    size_t take();                                               // an event of the pool, or kNoEvent
+    size_t begin(hipStream_t st);                                // ... recorded on st, or kNoEvent (counted)
+    void end(size_t e0, int kind, uint32_t q0, uint32_t nq, bool edge, hipStream_t st, const size_t *marks = nullptr);
+    bool reserve_marks(size_t idx[3], hipEvent_t ev[3]);         // the three mark events of a kd-tree pass (launch_nn_search records them); false: none (counted)
+    template <class PointsOf> void drain(PointsOf &&points_of);  // points_of(i): cloud size of hypothesis i
+    void reset() { spans.clear(); used = 0; }
+    void destroy() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); pool.clear(); reset(); }
+};
 // A slot's helper thread (PR_SOLVE_HOST): the reference solves on the host (icp.cu:207), which makes a batch a chain of
 // launch -> wait -> solve -> launch that only a host thread can drive; the reference's answer is "many host threads, each refining its own
 // hypothesis" (README.md:15).  A caller that pipelines batches through pr_refine_submit / pr_refine_wait from ONE thread gets the same
@@ -438,12 +538,9 @@ struct Slot {
     pr_result *user_results_host = nullptr;
     uint32_t *user_sizes = nullptr;
     // a TIMED asynchronous batch (option profile = 3): HIP events on the slot's stream around its render, its cloud emit and every
-    // correspondence pass (start / stop pairs in enqueue order), read by pr_refine_wait
+    // correspondence pass, drained by pr_refine_wait
     bool timed = false;
-    std::vector<hipEvent_t> t_events;            // pool, reused from batch to batch
-    size_t t_used = 0;
-    struct TSpan { size_t e0, e1; int kind; uint32_t q0, nq; bool edge; bool marks; size_t m[3]; };   // edge: first or last pass (36 B / point instead of 48); marks: events between the kernels of a kd-tree pass
-    std::vector<TSpan> t_spans;
+    Spans spans;
 };
 
 // ---- hipGraph cache for the device-solve iteration loop ------------------------------------------
@@ -525,9 +622,7 @@ struct Ctx {
     uint64_t nn_clock = 0;
     DevBuf nn_counters;
     // profiling
-    std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
-    struct Span { size_t e0, e1; int kind; };
-    std::vector<Span> spans;
+    Spans spans;                     // of the context's own stream (SpanGuard)
     double icp_ms = 0, render_ms = 0, cloud_ms = 0; uint64_t icp_launches = 0, icp_points = 0, icp_bytes = 0, sample_clock = 0;
     std::vector<float> icp_launch_us;                            // the timed launches one by one (pr_profile_launches), bounded
     uint64_t stat_repeated = 0, stat_timing_dropped = 0;         // pr_stats: batches run twice by the stale-cache safety net; timed spans lost to a failed event call
@@ -613,44 +708,58 @@ inline int require_ctx()
     std::lock_guard<std::mutex> lk(g->mu);           \
     PR_TRY(require_ctx())
 
-// ---- profiling spans (HIP events on the library stream) ------------------------------------------
-enum { kSpanIcp = 0, kSpanRender = 1, kSpanCloud = 2 };
-// (a failed event call must not vanish: HIP_TRY clears the sticky error, so the span is dropped HERE and counted -- pr_stats)
-constexpr size_t kNoEvent = (size_t)-1;
-inline size_t take_event()
+// ---- profiling spans: the recorder's bodies (they count into the calling thread's context) and the guard of the context's own stream ---------
+inline size_t Spans::take()
 {
-    if (g->ev_used == g->ev_pool.size()) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess || !e) { (void)hipGetLastError(); g->stat_timing_dropped++; return kNoEvent; }
-        g->ev_pool.push_back(e);
-    }
-    return g->ev_used++;
+    hipEvent_t e = nullptr;
+    if (used == pool.size()) { if (hipEventCreate(&e) != hipSuccess || !e) { (void)hipGetLastError(); return kNoEvent; } pool.push_back(e); }
+    return used++;
 }
-inline bool record_event(size_t e, hipStream_t st)
+inline size_t Spans::begin(hipStream_t st)
 {
-    if (e == kNoEvent) return false;
-    if (hipEventRecord(g->ev_pool[e], st) != hipSuccess) { (void)hipGetLastError(); g->stat_timing_dropped++; return false; }
+    const size_t e = take();
+    if (e != kNoEvent && hipEventRecord(pool[e], st) == hipSuccess) return e;
+    (void)hipGetLastError(); g->stat_timing_dropped++; return kNoEvent;
+}
+inline void Spans::end(size_t e0, int kind, uint32_t q0, uint32_t nq, bool edge, hipStream_t st, const size_t *marks)
+{
+    const size_t e1 = e0 == kNoEvent ? kNoEvent : begin(st);     // (a span without its start was dropped and counted by begin)
+    if (e1 == kNoEvent) return;
+    spans.push_back({ e0, e1, kind, q0, nq, edge, marks != nullptr, { marks ? marks[0] : 0, marks ? marks[1] : 0, marks ? marks[2] : 0 } });
+}
+inline bool Spans::reserve_marks(size_t idx[3], hipEvent_t ev[3])
+{
+    for (int k = 0; k < 3; ++k) { if ((idx[k] = take()) == kNoEvent) { g->stat_timing_dropped++; return false; } ev[k] = pool[idx[k]]; }
     return true;
 }
-struct SpanGuard {
-    bool on; size_t e0 = 0; int kind;
-    explicit SpanGuard(int k) : on(opt.profile != 0), kind(k) { if (on) { e0 = take_event(); on = record_event(e0, g->stream); } }
-    ~SpanGuard() { if (on) { const size_t e1 = take_event(); if (record_event(e1, g->stream)) g->spans.push_back({ e0, e1, kind }); } }
-};
 constexpr size_t kLaunchSamples = 8192;
-inline void note_launch_us(float ms) { if (g->icp_launch_us.size() < kLaunchSamples) g->icp_launch_us.push_back(ms * 1e3f); }
-inline void drain_spans()                   // call after the stream has been synchronised
+template <class PointsOf> inline void Spans::drain(PointsOf &&points_of)      // call after the stream has been synchronised
 {
-    for (const auto &s : g->spans) {
+    for (const Span &s : spans) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, g->ev_pool[s.e0], g->ev_pool[s.e1]) != hipSuccess) continue;
-        if (s.kind == kSpanIcp) { g->icp_ms += ms; g->icp_launches++; note_launch_us(ms); }
-        else if (s.kind == kSpanRender) g->render_ms += ms;
-        else g->cloud_ms += ms;
+        if (hipEventElapsedTime(&ms, pool[s.e0], pool[s.e1]) != hipSuccess) continue;
+        if (s.kind == kSpanRender) { g->render_ms += ms; continue; }
+        if (s.kind == kSpanCloud) { g->cloud_ms += ms; continue; }
+        uint64_t pts = 0;
+        for (uint32_t i = s.q0; i < s.q0 + s.nq; ++i) pts += points_of(i);
+        g->icp_ms += ms; g->icp_launches++; g->icp_points += pts; g->icp_bytes += icp_span_bytes(pts, s.edge);
+        if (g->icp_launch_us.size() < kLaunchSamples) g->icp_launch_us.push_back(ms * 1e3f);
+        if (!s.marks) continue;                                 // kd-tree pass: search | bound | task walk | winners pass
+        const hipEvent_t ev[5] = { pool[s.e0], pool[s.m[0]], pool[s.m[1]], pool[s.m[2]], pool[s.e1] };
+        float part[4]; bool ok = true;
+        for (int k = 0; k < 4; ++k) ok = ok && hipEventElapsedTime(&part[k], ev[k], ev[k + 1]) == hipSuccess;
+        if (ok) { for (int k = 0; k < 4; ++k) g->nn_part_ms[k] += part[k]; g->nn_part_n++; }
     }
-    g->spans.clear();
-    g->ev_used = 0;
+    reset();
 }
+// a span of the context's own stream, for the guard's lifetime (option profile).  The synchronous drivers know their cloud sizes when they enqueue:
+// they add the points and bytes of an ICP span themselves (icp_span_bytes), and the span carries no hypotheses.
+struct SpanGuard {
+    bool on; size_t e0 = kNoEvent; int kind;
+    explicit SpanGuard(int k) : on(opt.profile != 0), kind(k) { if (on) e0 = g->spans.begin(g->stream); }
+    ~SpanGuard() { if (on) g->spans.end(e0, kind, 0, 0, false, g->stream); }
+};
+inline void drain_spans() { g->spans.drain([](uint32_t) { return 0u; }); }      // call after the stream has been synchronised
 
 // A few words from device memory to the host WITHOUT a copy command: a kernel stores them into the context's pinned flag array, the stream is
 // waited for, the host copies them out.  Round 6: copy commands to pageable host memory go through the runtime's bounce buffers and its copy-engine
@@ -727,7 +836,7 @@ inline prk::IcpBatch group_slice(const prk::IcpBatch &b, uint32_t p0)
 // The device-solve iteration loop of n hypotheses (meta, dstate, arrive, b.partial and b's kd-tree queue counters at hypothesis 0): fork, (max_iteration + 1) x
 // [pass (+ finalize / solve launch unless the pass' tail does it: fused)] per group, join.  Both the synchronous driver and the asynchronous slots
 // run THIS loop -- the slots' safety net re-runs a batch through the synchronous one and expects the same bytes.  It makes no synchronising call
-// of its own (icp_drive records it into a hipGraph); what differs between the callers comes in as
+// of its own (drive_device records it into a hipGraph); what differs between the callers comes in as
 //   pass(bb, p0, np, stream) -> rc: launch_pass for one group, with whatever timing the caller keeps around it;
 //   after(it, stop) -> rc:          behind the launches of iteration `it` (an early-exit read-back, a progress event); stop = true ends the loop.
 template <class Pass, class After>

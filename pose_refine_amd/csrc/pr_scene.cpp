@@ -14,7 +14,7 @@ namespace prr {
 int fingerprint_differs(const void *a, size_t ab, const void *b, size_t bb, const void *c, size_t cb, uint32_t *slot, hipStream_t st, bool &differs)
 {
     HIP_TRY(prk::launch_scene_fingerprint_full(a, ab, b, bb, c, cb, slot + 3, st));
-    // both words come back through a kernel's stores into pinned memory (no copy command on the per-batch path: see icp_drive's result block)
+    // both words come back through a kernel's stores into pinned memory (no copy command on the per-batch path: see drive_host's result block)
     uint32_t v[2] = { 0u, 1u };
     PR_TRY(read_back_words(slot + 2, v, 2, st));
     differs = v[0] != v[1];

@@ -42,20 +42,6 @@
 #define PR_GATHER_BATCH 4                                       // projective scene gathers issued back to back before the first is tested (all four points of a lane)
 #endif
 
-// ---- raster (raster.hip) ----------------------------------------------------------------------------------------------------------
-#ifndef PR_RASTER_CHUNKS
-#define PR_RASTER_CHUNKS 1                                      // fused path: the raster of a (sub-)batch as this many launches over consecutive hypotheses.  Same box, 100 steps: 1 -> 274.1 k, 2 -> 271.7 k, 4 -> 271.1 k poses/s -- not kept
-#endif
-
-// ---- render -> cloud (d2c.hip) ----------------------------------------------------------------------------------------------------
-#ifndef PR_CLOUD_PACK
-#define PR_CLOUD_PACK 32                                        // fused path: a hypothesis' cloud starts where the one before it ends, rounded up to this many points (32 = 128-byte lines; 0: fixed stride of the largest pixel box, rounds 1-4)
-#endif
-
-#ifndef PR_BOX_PACK
-#define PR_BOX_PACK 32                                          // fused asynchronous path: a hypothesis' pixel box is its own little image in the depth workspace, packed behind the one before it, rounded up to this many pixels (0: full frames, rounds 1-4)
-#endif
-
 // ---- coarse-to-fine refinement (pyramid.hip) -----------------------------------------------------------------------------------------
 #ifndef PR_PYRAMID_EMIT_LOADS
 #define PR_PYRAMID_EMIT_LOADS 4                                 // level emit: sampled pixels of a row a lane requests before the first ballot (a 640-pixel row at stride 1 is three steps of 256; at stride 4 one step covers it)

@@ -711,37 +711,19 @@ hipError_t launch_render_bands(const pr_triangle *tris, uint32_t n_tris, const p
 }
 
 // offsets of the packed boxes from boxes computed on the device (synchronous path; the asynchronous path's host computes both): exclusive scan of
-// the areas rounded up to kBoxPack pixels, one workgroup
+// the areas rounded up to kBoxPack pixels (box_slot), one workgroup
 __global__ __launch_bounds__(256) void box_pack_offsets_kernel(const int4 *__restrict__ bbox, uint32_t n, uint32_t *__restrict__ off)
 {
     __shared__ uint32_t buf[256];
     __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        uint32_t v = 0;
-        if (i < n) { const int4 b = bbox[i]; const uint32_t area = (uint32_t)max(b.z - b.x + 1, 0) * (uint32_t)max(b.w - b.y + 1, 0); v = (area + (kBoxPack - 1u)) / (kBoxPack ? kBoxPack : 1u) * kBoxPack; }
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t o = 1; o < 256; o <<= 1) {
-            const uint32_t t = (threadIdx.x >= o) ? buf[threadIdx.x - o] : 0;
-            __syncthreads();
-            buf[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) off[i] = carry + buf[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += buf[255];
-        __syncthreads();
-    }
+    block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return box_slot(box_area(bbox[i])); }, [&](uint32_t i, uint32_t o) { off[i] = o; });
 }
 // The steps both box renders share.  box_pack_offsets_kernel (when the boxes are packed); fill_box_kernel / count_box_kernel over hypotheses
 // [p0, p0 + n), in launches of at most 32768 (grid.y is limited to 65535); the closing row scan (launch_d2c_scan_init when the asynchronous
 // path's per-hypothesis records are given).
 static void launch_box_pack(const int4 *bbox, uint32_t n_poses, const uint32_t *box_off, hipStream_t s)
 {
-    if (box_off && kBoxPack) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, bbox, n_poses, const_cast<uint32_t *>(box_off));   // (the caller's scratch: filled here)
+    if (box_off) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, bbox, n_poses, const_cast<uint32_t *>(box_off));   // (the caller's scratch: filled here)
 }
 // Asynchronous path, option tight_box: the uploaded loose boxes of all n_poses hypotheses replaced by their tight ones ...
 hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_mat4 *poses_dev, uint32_t n_poses, const pr_mat4 &proj,
@@ -754,8 +736,7 @@ hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_ma
 // ... and the packed offsets of one sub-batch's boxes formed again from them (the uploaded ones belong to the loose boxes)
 hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, hipStream_t s)
 {
-    if (n_poses == 0) return hipSuccess;
-    launch_box_pack(bbox, n_poses, box_off, s);
+    if (n_poses > 0) launch_box_pack(bbox, n_poses, box_off, s);
     return hipGetLastError();
 }
 static void launch_fill_boxes(int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height, hipStream_t s)
@@ -776,9 +757,9 @@ static void launch_count_boxes(const int32_t *depth, const int4 *bbox, const uin
     }
 }
 static hipError_t launch_box_scan(const uint32_t *row_count, uint32_t height, uint32_t *row_off, uint32_t *counts, uint32_t n_poses,
-                                  PoseMeta *meta, DevIcpState *st, uint32_t *arrive, uint32_t cloud_stride, hipStream_t s)
+                                  PoseMeta *meta, DevIcpState *st, uint32_t *arrive, hipStream_t s)
 {
-    const hipError_t e = meta ? launch_d2c_scan_init(row_count, height, row_off, counts, n_poses, meta, st, arrive, cloud_stride, s)
+    const hipError_t e = meta ? launch_d2c_scan_init(row_count, height, row_off, counts, n_poses, meta, st, arrive, s)
                               : launch_d2c_scan(row_count, height, row_off, counts, n_poses, s);
     return e != hipSuccess ? e : hipGetLastError();
 }
@@ -787,7 +768,7 @@ static hipError_t launch_box_scan(const uint32_t *row_count, uint32_t height, ui
 hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb,
                                int4 *bbox, int32_t *depth, uint32_t *row_count, uint32_t *row_off, uint32_t *counts,
                                uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s, bool compute_boxes,
-                               PoseMeta *meta, DevIcpState *st, uint32_t *arrive, uint32_t cloud_stride, const uint32_t *box_off, const BatchCheck *check)
+                               PoseMeta *meta, DevIcpState *st, uint32_t *arrive, const uint32_t *box_off, const BatchCheck *check)
 {
     if (n_poses == 0) return hipSuccess;
     if (compute_boxes) {
@@ -802,18 +783,12 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
         launch_fill_boxes(depth, bbox, box_off, p0, np, width, height, s);
         if (n_tris > 0)                                          // an empty mesh renders nothing: every cloud is empty
         { const uint32_t run = raster_pose_run(n_tris, np);
-          // PR_RASTER_CHUNKS > 1 (experiment of round 5): the hypotheses of a launch in that many launches one behind the other
-          const uint32_t chunks = (uint32_t)PR_RASTER_CHUNKS < np ? (uint32_t)PR_RASTER_CHUNKS : 1u;
-          for (uint32_t c = 0; c < chunks; ++c) {
-              const uint32_t c0 = (uint32_t)(((uint64_t)np * c) / chunks), c1 = (uint32_t)(((uint64_t)np * (c + 1)) / chunks), nc = c1 - c0;
-              if (nc == 0) continue;
-              hipLaunchKernelGGL(raster_kernel, dim3((n_tris + 255) / 256, (nc + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0 + c0,
-                                 depth + off + (bo ? 0 : (size_t)c0 * width * height), width, height, proj, none, width, height, (const int4 *)(bbox + p0 + c0), nc, run,
-                                 bo ? bo + c0 : nullptr, (check && p0 == 0 && c == 0) ? *check : BatchCheck{});
-          } }
+          hipLaunchKernelGGL(raster_kernel, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
+                             depth + off, width, height, proj, none, width, height, (const int4 *)(bbox + p0), np, run,
+                             bo, (check && p0 == 0) ? *check : BatchCheck{}); }
         launch_count_boxes(depth, bbox, box_off, p0, np, width, height, row_count, s);
     }
-    return launch_box_scan(row_count, height, row_off, counts, n_poses, meta, st, arrive, cloud_stride, s);
+    return launch_box_scan(row_count, height, row_off, counts, n_poses, meta, st, arrive, s);
 }
 
 // ---- mixed batches (hypotheses of several meshes in one call) -----------------------------------------------------------------------
@@ -875,7 +850,7 @@ hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_ind
     { hipError_t e = launch_raster_multi(groups_host, groups_mapped, n_groups, groups_dev, poses_dev, depth, width, height, proj, none, width, height,
                                          bbox, box_off, nullptr, s); if (e != hipSuccess) return e; }
     launch_count_boxes(depth, bbox, box_off, 0, n_poses, width, height, row_count, s);
-    return launch_box_scan(row_count, height, row_off, counts, n_poses, nullptr, nullptr, nullptr, 0, s);
+    return launch_box_scan(row_count, height, row_off, counts, n_poses, nullptr, nullptr, nullptr, s);
 }
 
 }  // namespace prk

@@ -451,3 +451,43 @@ def test_pr_free_on_another_thread_while_helper_threads_come_and_go(gpu, model, 
     api.init(0); api.set_option("solve", api.SOLVE_HOST)
     assert finished and not t.is_alive() and not w.is_alive(), "deadlock between pr_free, a slot's helper thread and its caller"
     assert not errors, errors
+
+
+@pytest.mark.parametrize("P", [257, 513])
+def test_pack_scans_cross_their_carry_on_a_small_frame(gpu, model, P):
+    """The one exclusive scan of the render -> cloud stage (block_exclusive_scan: chunks of 256 with a carry) where every user of it crosses the
+    carry, at the smallest shapes that do: a frame 260 rows high (the row scan carries once), 257 and 513 hypotheses in ONE sub-batch (the
+    starts of the packed clouds and -- from the third batch of a mesh on, when option tight_box rebuilds them on the device -- the offsets of
+    the packed boxes carry once and twice).  Half of the objects sit across row 256.  Records and cloud sizes of the asynchronous batch equal
+    the synchronous path's (profile 1: boxes, offsets and starts all formed on the device) byte for byte, and no batch is repeated."""
+    w, h = 96, 260
+    K = np.array([300.0, 0.0, 48.0, 0.0, 300.0, 130.0, 0.0, 0.0, 1.0], dtype=np.float32)
+    proj = api.compute_proj(K, w, h)
+    poses = synth.hypotheses(P, seed=41).reshape(-1, 4, 4).copy()
+    poses[:, 0, 3] -= 20.0                                        # centred in x; in y alternately some 95 px above and below the centre: one of the two
+    poses[0::2, 1, 3] += 80.0                                     # sets reaches over row 256 of the frame whichever way the raster counts its rows
+    poses[1::2, 1, 3] -= 120.0
+    at = synth.scene_pose().copy()
+    at[0, 3] -= 20.0; at[1, 3] += 80.0
+    scene = api.Scene_projective().init_Scene_projective_cuda(api.render_host(model, at[None], w, h, proj)[0], K, w, h)
+    crit = api.ICPConvergenceCriteria(0.0, 0.0, 2)
+    api.set_option("solve", api.SOLVE_DEVICE)
+    api.set_option("sub_batch", 1024)
+    try:
+        api.set_option("profile", 1)
+        ref, ref_sizes = api.refine_batch(model, poses, w, h, proj, K, scene, crit)
+        api.set_option("profile", 0)
+        repeated, tight = api.stats()[0], api.get_option("stat_tight_batches")
+        for _ in range(3):                                        # the ordered mesh copy and the vertex list exist from the second batch on
+            api.refine_submit(0, model, poses, w, h, proj, K, scene, crit)
+            got, sizes = api.refine_wait(0)
+            assert np.array_equal(sizes, ref_sizes)
+            assert got.tobytes() == ref.tobytes()
+        print("non-empty clouds:", int((ref_sizes > 0).sum()), "of", P, "largest", int(ref_sizes.max()), "tight batches", api.get_option("stat_tight_batches") - tight)
+        assert int((ref_sizes > 0).sum()) >= 200
+        assert api.get_option("stat_tight_batches") > tight        # the packed offsets were rebuilt on the device
+        assert api.stats()[0] == repeated
+    finally:
+        api.set_option("profile", 0)
+        api.set_option("sub_batch", 512)
+        api.set_option("solve", api.SOLVE_HOST)

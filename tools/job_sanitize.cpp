@@ -1,6 +1,6 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
 // Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok and vsd_args_ok with null and
-// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split.  None of them calls HIP, so nothing of the runtime is linked.
+// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) and the byte rule of a timed pass (icp_span_bytes).  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
 namespace prh { void set_error(const char *, ...) {} }
@@ -235,6 +235,72 @@ int main()
             std::free(base);
         }
     CHECK(group_begin(0xffffffffu, 4, 4) == 0xffffffffu && group_begin(0xffffffffu, 4, 3) == 0xbfffffffu);
+    // the packed layouts: an empty or inverted box has no pixels; a slot is a multiple of 32, never smaller than what it holds and less than 32 larger
+    static_assert(prk::kBoxPack == 32 && prk::kCloudAlign == 32, "the values below are written for slots of 32");
+    CHECK(prk::box_area(int4{ 0, 0, 0, 0 }) == 1 && prk::box_area(int4{ 3, 5, 12, 5 }) == 10 && prk::box_area(int4{ 0, 0, 4095, 4095 }) == (1u << 24));
+    for (int4 b : { int4{ 5, 0, 4, 9 }, int4{ 0, 5, 9, 4 }, int4{ 9, 9, 0, 0 }, int4{ 0, 0, -1, -1 }, int4{ 8191, 0, -8191, 0 }, int4{ 100, 100, 3, 200 } }) CHECK(prk::box_area(b) == 0);
+    {
+        const uint32_t in[6] = { 0u, 1u, 31u, 32u, 33u, 0xffffffdfu }, want[6] = { 0u, 32u, 32u, 32u, 64u, 0xffffffe0u };      // (the last: 2^32 - 33)
+        for (int k = 0; k < 6; ++k)
+            for (uint32_t got : { prk::box_slot(in[k]), prk::cloud_slot(in[k]) }) CHECK(got == want[k] && got % 32 == 0 && got >= in[k] && got - in[k] < 32);
+    }
+    // plan_async: the sub-batch split ...
+    {
+        auto plan_of = [](uint32_t P, uint32_t W, uint32_t H, int4 box, int sub_batch, uint32_t hint = 0, int steps = 3) {
+            std::vector<int4> boxes(P, box); std::vector<uint32_t> off(P, 0xdeadbeefu);
+            return plan_async(P, W, H, boxes.data(), steps, sub_batch, hint, off.data());
+        };
+        const int4 small{ 10, 10, 73, 41 };                                                              // 64 x 32 pixels
+        { const AsyncPlan pl = plan_of(96, 640, 480, small, 40); CHECK(pl.n_sub == 3 && pl.sub == 32); }
+        { const AsyncPlan pl = plan_of(96, 640, 480, small, 64); CHECK(pl.n_sub == 2 && pl.sub == 48); }
+        { const AsyncPlan pl = plan_of(512, 4096, 4096, small, 512); CHECK(pl.sub == 64 && pl.n_sub == 8); }                  // 4 GiB / 64 MiB
+        { const AsyncPlan pl = plan_of(512, 2048, 1024, small, 512); CHECK(pl.sub == 512 && pl.n_sub == 1); }                 // 2 M pixels
+        { const AsyncPlan pl = plan_of(1024, 640, 480, int4{ 0, 0, 639, 479 }, 512); CHECK(pl.sub == 512 && pl.n_sub == 2); }
+        { const AsyncPlan pl = plan_of(7, 640, 480, int4{ 9, 9, 0, 0 }, 512); CHECK(pl.max_area == 1 && pl.cstride == 32 && pl.nblk == 1 && pl.grid_x == 1); }      // all boxes empty
+    }
+    // ... and the layout: boxes of many sizes, empty ones among them, over several frames, sub-batch sizes, step counts and cloud hints
+    for (auto [W, H] : { std::pair<uint32_t, uint32_t>{ 96, 260 }, { 640, 480 }, { 1, 1 }, { 4096, 4096 } })
+        for (uint32_t P : { 1u, 31u, 96u, 257u, 513u })
+            for (int sub_batch : { 1, 40, 512 })
+                for (uint32_t hint : { 0u, 1u, 5000u, 1u << 24 })                                   // (a cloud has at most 2^24 points: frame_size_ok)
+                    for (int steps : { 0, 1, 3 }) {
+                        std::vector<int4> boxes(P); std::vector<uint32_t> off(P, 0xdeadbeefu);
+                        uint32_t x = 12345u * W + P;
+                        auto next = [&](uint32_t m) { x = x * 1664525u + 1013904223u; return (int)((x >> 8) % m); };
+                        for (int4 &b : boxes) { b = int4{ next(W), next(H), next(W), next(H) }; if (next(5) == 0) b = int4{ 0, 0, (int)W - 1, (int)H - 1 }; }   // (inverted about half of the time; the whole frame now and then)
+                        const AsyncPlan pl = plan_async(P, W, H, boxes.data(), steps, sub_batch, hint, off.data());
+                        size_t largest = 1;
+                        for (const int4 &b : boxes) largest = std::max<size_t>(largest, prk::box_area(b));
+                        CHECK(pl.max_area == largest && pl.cstride >= pl.max_area && pl.cstride % prk::kCloudAlign == 0);
+                        CHECK(pl.steps == (uint32_t)std::max(1, steps) && (size_t)pl.nblk * pl.steps * prk::kPointsPerStep >= pl.max_area);
+                        CHECK(pl.grid_x >= 1 && pl.grid_x <= pl.nblk && (hint != 0 || pl.grid_x == pl.nblk));
+                        CHECK(pl.sub >= 1 && pl.n_sub >= 1 && (size_t)pl.sub * pl.n_sub >= P && (size_t)pl.sub * (pl.n_sub - 1) < P && pl.sub <= (uint32_t)std::max(32, sub_batch));
+                        CHECK((size_t)pl.sub * W * H * sizeof(int32_t) <= ((size_t)4 << 30) && (size_t)pl.sub * pl.cstride <= ((size_t)1 << 30));
+                        for (uint32_t i = 0; i < P; ++i) {
+                            CHECK(off[i] % prk::kBoxPack == 0);
+                            if (i % pl.sub == 0) CHECK(off[i] == 0);
+                            else CHECK(off[i] >= off[i - 1] && off[i] == off[i - 1] + prk::box_slot(prk::box_area(boxes[i - 1])));
+                            if ((i + 1) % pl.sub == 0 || i + 1 == P) CHECK((size_t)off[i] + prk::box_area(boxes[i]) <= ((size_t)W * H + prk::kBoxPack) * pl.sub);
+                        }
+                    }
+    // release_pass_for: the measured rule at the benchmark's figures, the scene kinds, a timed batch, the two options
+    {
+        const pr_criteria c20{ 0.0f, 0.0f, 20 };
+        auto rule = [&](uint32_t nq, int kind = PR_SCENE_PROJ, bool timed = false, bool start = false, int start_overlap = -1, int overlap_pass = -1) {
+            return release_pass_for(31468, nq, 27400, c20, kind, timed, start, start_overlap, overlap_pass);
+        };
+        CHECK(rule(128) == 0 && rule(256) == 8 && rule(384) == 14 && rule(512) == 16);
+        CHECK(rule(128, PR_SCENE_PROJ_CROP) == 0 && rule(512, PR_SCENE_PROJ_CROP) == 16);
+        for (uint32_t nq : { 128u, 256u, 384u, 512u }) CHECK(rule(nq, PR_SCENE_NN) == 0 && rule(nq, PR_SCENE_PROJ, /*timed=*/true) == 20 && rule(nq, PR_SCENE_NN, true, true, 2, 3) == 20);
+        CHECK(rule(512, PR_SCENE_PROJ, false, false, -1, 3) == 3 && rule(512, PR_SCENE_PROJ, false, true, -1, 3) == 3 && rule(512, PR_SCENE_NN, false, false, -1, 3) == 3);
+        CHECK(rule(512, PR_SCENE_PROJ, false, true, 2) == 2 && rule(512, PR_SCENE_PROJ, false, false, 2) == 16 && rule(512, PR_SCENE_PROJ, false, true, 2, 3) == 2 && rule(512, PR_SCENE_PROJ, false, false, 2, 3) == 3);
+        CHECK(rule(512, PR_SCENE_PROJ, false, false, -1, 99) == 20 && rule(512, PR_SCENE_PROJ, false, true, 99) == 20);                       // never beyond the last pass
+        CHECK(release_pass_for(0, 0, 0, pr_criteria{ 0.0f, 0.0f, 0 }, PR_SCENE_PROJ, false, true, -1, -1) == 0);
+        CHECK(release_pass_for(31468, 512, 27400, pr_criteria{ 0.0f, 0.0f, 2 }, PR_SCENE_PROJ, false, false, -1, -1) == 0);                   // three passes: fewer than the five the rule leaves
+    }
+    // the bytes a timed pass is accounted: 36 per point on an edge pass, 48 otherwise
+    CHECK(icp_span_bytes(0, true) == 0 && icp_span_bytes(1, true) == 36 && icp_span_bytes(1, false) == 48 && icp_span_bytes(27400, true) == 986400 && icp_span_bytes(27400, false) == 1315200);
+    CHECK(icp_span_bytes(uint64_t(1) << 40, false) == (uint64_t(48) << 40));
     std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;
 }

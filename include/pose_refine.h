@@ -260,6 +260,47 @@ int pr_icp_grid(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_grid *scen
 int pr_icp_batch(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind,
                  const void *scene, pr_criteria crit, pr_result *results_host);
 
+/* ---- robust ICP: an M-estimator weight on the point-to-plane residual (no counterpart in the reference) ----------------------------------
+ * The plain pass counts a correspondence fully (e^2 < max_dist_diff^2) or not at all.  A robust pass multiplies the terms of the normal
+ * system (sums 0..26) of every VALID correspondence by a weight w(r) of its residual; which correspondence a point gets and whether it is
+ * valid are exactly what they are in the plain pass -- the weight never changes association or acceptance.
+ *   c       the scale, in metres (the unit of the clouds);  inv_c = 1.0f / c, computed ONCE in float32 by pr_robust_describe: the device and
+ *           the references read it and never recompute it (the precedent: pr_scene_grid.inv_cell).  reserved is 0.
+ *   r       the float32 residual as the pass forms it, (ex*nx + ey*ny) + ez*nz with e = d - p;  J[0..5] = (p x n, n) as in the plain pass.
+ *   w       float32, every operation rounded on its own (no contraction):
+ *             PR_ROBUST_NONE    w = 1.0f
+ *             PR_ROBUST_HUBER   a = fabsf(r);  w = (a <= c) ? 1.0f : c / a                     (correctly rounded IEEE division)
+ *             PR_ROBUST_TUKEY   u = r * inv_c; q = u * u;  w = (q < 1.0f) ? (1.0f - q) * (1.0f - q) : 0.0f
+ *             PR_ROBUST_CAUCHY  u = r * inv_c; q = u * u;  w = 1.0f / (1.0f + q)
+ *   terms   seven values are formed once per point: wJ[a] = w * J[a], a = 0..5, and wr = w * r.  Each of the 27 products takes exactly one
+ *           of them as one factor -- THE FACTOR TABLE (tests/robust_ref.py: WEIGHTED_FACTOR reads the same 27 entries):
+ *             sums  0..20  J[a]*J[b], a <= b, row-major:   wJ[a] * J[b]      (the weight rides on the factor with the LOWER index)
+ *             sums 21..23  J[a]*r, a = 0, 1, 2:            wJ[a] * r         (the weight rides on J[a])
+ *             sums 24..26  J[a]*r, a = 3, 4, 5:            J[a]  * wr        (the weight rides on r)
+ *           (the pairs the packed kernel multiplies -- (J0, J1), (J2, r), (J3, J4), (J5, dz) -- times (w, w) are four packed multiplies; with
+ *           this table every one of the sixteen packed accumulations reads its operands from those pairs without a register move.)
+ *   sums 27 (e^2) and 28 (count) are NOT weighted: fitness, inlier_rmse and the convergence test (icp.cu:178-212) keep their meaning and
+ *           stay comparable with plain runs; a Tukey correspondence with w == 0 still counts as an inlier.
+ * Each term is added to the lane's running sum exactly as in the plain pass: same canonical tree, same points_per_block semantics, same
+ * solve.  When w == 1.0f every weighted product equals the plain product bit for bit, so any kind with a scale so large that w rounds to 1
+ * (c = 1.0e6f) returns the bytes of the plain call.  The last pass of a device-solve run forms sums 27 and 28 only and needs no weight.
+ * kd-tree scenes: a robust call always takes the split route (search kernels, then the pass over the winners) whenever the scene has compact
+ * records, whatever the nn_* options say; results do not depend on those options, as they do not depend on them in plain calls.
+ * pr_robust_describe: host only, needs no device.  PR_ERR_INVALID for a null `out`, an unknown kind and -- for a kind other than
+ * PR_ROBUST_NONE -- a c that is not finite or not positive (or whose 1.0f / c is not a positive finite float). */
+#define PR_ROBUST_NONE   0
+#define PR_ROBUST_HUBER  1
+#define PR_ROBUST_TUKEY  2
+#define PR_ROBUST_CAUCHY 3
+typedef struct { uint32_t kind; float c; float inv_c; uint32_t reserved; } pr_robust;   /* 16 B */
+int pr_robust_describe(uint32_t kind, float c, pr_robust *out);
+/* pr_icp_batch with the weight of `robust` (one descriptor for the call; all four scene kinds).  It takes an armed pr_debug_trace_sums
+ * recorder exactly as pr_icp_batch does.  PR_ERR_INVALID, before any device is touched and with nothing written, for a null robust, a
+ * descriptor pr_robust_describe would not have produced (unknown kind, bad c, inv_c != 1.0f / c, reserved != 0) and pr_icp_batch's own
+ * argument errors.  PR_ROBUST_NONE returns pr_icp_batch's bytes. */
+int pr_icp_batch_robust(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind,
+                        const void *scene, pr_criteria crit, const pr_robust *robust, pr_result *results_host);
+
 /* ---- fused hypothesis refinement: render -> cloud -> ICP for n_poses hypotheses --------------- */
 /* test.cpp:143-172 for a whole batch, everything resident on the device; results on the host.
  * cloud_sizes_host (optional) receives the model-cloud size of every hypothesis.  The synchronous calls (pr_refine_batch, _dev, _roi) run on
@@ -373,6 +414,19 @@ int  pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const
                              uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
                              const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
                              pr_result *level_results_host, uint32_t *level_sizes_host);
+/* The pyramid calls with robust weights (pr_robust above): n_robust == 1 is one descriptor for every level, n_robust == n_levels one per
+ * level -- the annealing use, a wide c on the coarse level and a narrow one on the fine level; any other n_robust is PR_ERR_INVALID, as are
+ * a null table and a descriptor pr_robust_describe would not have produced, all before any device is touched and with nothing written.
+ * One level of stride 1 is the robust form of pr_refine_batch_roi.  With every descriptor PR_ROBUST_NONE the records are pr_refine_pyramid's
+ * bytes.  Like the plain pyramid calls they neither record nor disarm pr_debug_trace_sums.  Synchronous only. */
+int  pr_refine_pyramid_robust(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                              const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels,
+                              pr_roi roi, pr_result *results_host, pr_result *level_results_host, uint32_t *level_sizes_host,
+                              const pr_robust *robust, uint32_t n_robust);
+int  pr_refine_pyramid_robust_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                                    uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                                    const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
+                                    pr_result *level_results_host, uint32_t *level_sizes_host, const pr_robust *robust, uint32_t n_robust);
 
 /* ---- detections from a scored batch: which hypotheses explain the same scene pixels ------------------------------------------------------
  * The support of hypothesis i is the set of frame pixels pr_score_poses counts as `inlier` for it (rendered, s > 0, |r - s| <= tau_mm).
@@ -784,6 +838,13 @@ int  pr_profile_nn(double part_ms[4], uint64_t *passes);
  * point order reproduces the reference's single-thread summation (icp.cpp:139-148), which the product kernel replaces by its fixed tree. */
 int  pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, const void *scene, const float *update16, int want_packed,
                         float *contrib_host);
+/* Audit entry: pr_debug_contrib29 with the WEIGHTED terms of `robust` (pr_robust above) in contrib_host (n_points x 29: columns 0..26
+ * weighted by the factor table, 27 and 28 plain).  corr_host, unless NULL, receives n_points x 8 floats: {dx, dy, dz, valid ? 1.0f : 0.0f,
+ * nx, ny, nz, w} -- the correspondence the pass found for the point and its weight; rows are zero where there is no valid correspondence.
+ * With PR_ROBUST_NONE contrib_host equals pr_debug_contrib29's bytes and w is written as 1.0f.  Null pointers with n_points > 0 and a bad
+ * descriptor are PR_ERR_INVALID before any device is touched, with nothing written. */
+int  pr_debug_robust_terms(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, const void *scene, const float *update16, int want_packed,
+                           const pr_robust *robust, float *contrib_host, float *corr_host);
 /* Audit entry: ONE iteration of icp.cu:178-212 for n hypotheses whose 29 sums are given (n x 29 floats in the pass's order: the 21
  * upper-triangle entries of A row by row, b[6], r^2, count).  on_device != 0: the wavefront iteration the fused pass tail and
  * icp_finalize_solve_kernel run (one wavefront per hypothesis); 0: the host-solve loop's iteration (needs no device).  state: in/out
@@ -792,8 +853,8 @@ int  pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, c
 int  pr_debug_pose_iteration(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, int on_device,
                              pr_result *state, float *update_out, uint32_t *finished_out);
 /* Audit entry: the 29 sums of EVERY pass, as the product path delivered them to the host-solve loop.  Arms a recorder on the calling
- * thread (and so on the context that thread is bound to) for its next synchronous ICP call -- pr_icp_batch, pr_icp_proj, pr_icp_nn,
- * pr_refine_batch, pr_refine_batch_roi -- and for that call only: the recorder is gone when the call returns, error or not.
+ * thread (and so on the context that thread is bound to) for its next synchronous ICP call -- pr_icp_batch, pr_icp_batch_robust, pr_icp_proj,
+ * pr_icp_nn, pr_refine_batch, pr_refine_batch_roi -- and for that call only: the recorder is gone when the call returns, error or not.
  * rows_host = NULL disarms.  While it is armed the loop copies the 29 floats of hypothesis i at iteration it to
  * rows_host[(it * n_hyp + i) * 29 ..], exactly what the iteration of icp.cu:178-212 is about to consume (layout: see
  * pr_debug_pose_iteration), whichever way the sums reached the host (options fused_solve, host_poll, pose_groups).  Rows of hypotheses

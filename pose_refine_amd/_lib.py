@@ -78,6 +78,12 @@ class PyramidLevel(C.Structure):
 
 
 PYRAMID_MAX_LEVELS, PYRAMID_MAX_STRIDE = 4, 16          # PR_PYRAMID_MAX_LEVELS, PR_PYRAMID_MAX_STRIDE
+ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY, ROBUST_CAUCHY = 0, 1, 2, 3      # PR_ROBUST_*
+
+
+class RobustDesc(C.Structure):
+    """pr_robust: an M-estimator weight on the ICP residual (pr_robust_describe fills it: inv_c is computed there, once)."""
+    _fields_ = [("kind", C.c_uint32), ("c", C.c_float), ("inv_c", C.c_float), ("reserved", C.c_uint32)]
 
 
 class MeshRef(C.Structure):
@@ -168,6 +174,11 @@ SIGNATURES = {
     "pr_scene_grid_describe": (_i32, [_vp, _vp, C.c_float, C.c_float, C.c_float, _vp]),
     "pr_scene_grid_build_dev": (_i32, [_vp, _vp, _vp, _vp]),
     "pr_icp_batch": (_i32, [_vp, _vp, _u32, _i32, _vp, Criteria, _vp]),
+    "pr_robust_describe": (_i32, [_u32, C.c_float, _vp]),
+    "pr_icp_batch_robust": (_i32, [_vp, _vp, _u32, _i32, _vp, Criteria, _vp, _vp]),
+    "pr_refine_pyramid_robust": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, _vp, _u32, Roi, _vp, _vp, _vp, _vp, _u32]),
+    "pr_refine_pyramid_robust_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, _vp, _u32, Roi, _vp, _vp, _vp, _vp, _u32]),
+    "pr_debug_robust_terms": (_i32, [_vp, _u32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "pr_refine_batch": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp]),
     "pr_refine_batch_dev": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp]),
     "pr_refine_submit": (_i32, [_i32, _vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp, _vp]),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -597,8 +597,41 @@ def ICP_Point2Plane(model_pcd: DeviceVector, scene, criteria: ICPConvergenceCrit
     return RegistrationResult.from_record(res[0])
 
 
-def ICP_Point2Plane_batch(clouds: DeviceVector, offsets, scene, criteria: ICPConvergenceCriteria = ICPConvergenceCriteria()) -> np.ndarray:
-    """Many clouds against one scene (one launch per iteration).  offsets: P+1 point offsets."""
+class Robust:
+    """``pr_robust``: an M-estimator weight on the point-to-plane residual -- ``Robust(ROBUST_HUBER, 0.005)`` -- with the scale ``c`` in metres.
+    The descriptor comes from ``pr_robust_describe`` (``inv_c`` is computed there, once, in float32); a bad kind or scale raises."""
+
+    def __init__(self, kind: int, c: float = 0.0):
+        self._d = RobustDesc()
+        if not 0 <= int(kind) < 2**32:
+            raise ValueError(f"kind {kind} is no uint32")
+        check(_lib.load().pr_robust_describe(int(kind), float(c), C.addressof(self._d)))
+
+    kind = property(lambda self: int(self._d.kind))
+    c = property(lambda self: np.float32(self._d.c))
+    inv_c = property(lambda self: np.float32(self._d.inv_c))
+
+    def desc(self) -> RobustDesc:
+        return self._d
+
+    def __repr__(self):
+        return f"Robust(kind={self.kind}, c={float(self.c)!r})"
+
+
+def _robust_table(robust, n_levels: int):
+    """(pr_robust array, its length) from one ``Robust`` (every level) or a sequence of them (one per level)."""
+    rs = [robust] if isinstance(robust, Robust) else list(robust)
+    if not rs or not all(isinstance(r, Robust) for r in rs):
+        raise ValueError("robust: a Robust or a sequence of them, one per level")
+    if len(rs) not in (1, n_levels):
+        raise ValueError(f"robust: one descriptor or one per level ({n_levels}), got {len(rs)}")
+    return (RobustDesc * len(rs))(*[r.desc() for r in rs]), len(rs)
+
+
+def ICP_Point2Plane_batch(clouds: DeviceVector, offsets, scene, criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(),
+                          robust: Optional[Robust] = None) -> np.ndarray:
+    """Many clouds against one scene (one launch per iteration).  offsets: P+1 point offsets.  ``robust``: a ``Robust`` weight
+    (``pr_icp_batch_robust``); None is the plain call."""
     offsets = np.ascontiguousarray(offsets, np.uint32)
     if len(offsets) == 0:
         raise ValueError("offsets: P + 1 point offsets (at least one)")
@@ -606,8 +639,25 @@ def ICP_Point2Plane_batch(clouds: DeviceVector, offsets, scene, criteria: ICPCon
         raise ValueError(f"offsets end at point {int(offsets[-1])}, the cloud buffer holds {clouds.size() // 3}")
     res = np.zeros(len(offsets) - 1, RESULT)
     d = scene.desc()
+    if robust is not None:
+        check(_lib.load().pr_icp_batch_robust(clouds.data(), ptr(offsets), len(offsets) - 1, scene.kind, C.addressof(d), criteria.c(),
+                                              C.addressof(robust.desc()), ptr(res)))
+        return res
     check(_lib.load().pr_icp_batch(clouds.data(), ptr(offsets), len(offsets) - 1, scene.kind, C.addressof(d), criteria.c(), ptr(res)))
     return res
+
+
+def debug_robust_terms(model_pcd: DeviceVector, scene, robust: Robust, update=None, packed: bool = False, want_corr: bool = True):
+    """``pr_debug_robust_terms``: ``debug_contrib29`` with the weighted terms of ``robust``.  Returns (terms (n, 29), corr (n, 8) or None):
+    corr rows are {dx, dy, dz, valid, nx, ny, nz, w}, zero where the point has no valid correspondence."""
+    n = model_pcd.size() // 3
+    out = np.zeros((n, 29), np.float32)
+    corr = np.zeros((n, 8), np.float32) if want_corr else None
+    d = scene.desc()
+    u = _f32(update, -1) if update is not None else None
+    check(_lib.load().pr_debug_robust_terms(model_pcd.data(), n, scene.kind, C.addressof(d), ptr(u) if u is not None else None, int(packed),
+                                            C.addressof(robust.desc()), ptr(out), ptr(corr) if corr is not None else None))
+    return out, corr
 
 
 def debug_contrib29(model_pcd: DeviceVector, scene, update=None, packed: bool = False) -> np.ndarray:
@@ -685,10 +735,15 @@ def debug_nn_records(scene: "Scene_nn", camera=None) -> dict:
 
 def refine_batch(tris, poses, width: int, height: int, proj, K, scene,
                  criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(), results_dev: Optional[int] = None,
-                 roi: Optional[Sequence[int]] = None):
+                 roi: Optional[Sequence[int]] = None, robust: Optional[Robust] = None):
     """Fused hypothesis refinement (test.cpp:143-172 for a batch): render -> cloud -> ICP on the device.
     Returns (records[P] of RESULT dtype or None when results_dev is given, cloud sizes[P]).
-    ``roi`` = (x, y, width, height): render only inside the window (renderer.h:199), clouds with tl = (x, y)."""
+    ``roi`` = (x, y, width, height): render only inside the window (renderer.h:199), clouds with tl = (x, y).
+    ``robust``: a ``Robust`` weight -- the call runs as a one-level stride-1 ``refine_pyramid`` (``pr_refine_pyramid_robust``)."""
+    if robust is not None:
+        if results_dev is not None:
+            raise ValueError("robust and results_dev together are not offered")
+        return refine_pyramid(tris, poses, width, height, proj, K, scene, levels=((1, criteria),), roi=roi, robust=robust)
     td = _tris_dev(tris)
     poses = _f32(poses, (-1, 16))
     pj, k = _f32(proj, -1), _f32(K, -1)
@@ -828,10 +883,13 @@ def render_multi(meshes, mesh_index, poses, width: int, height: int, proj, roi: 
 
 
 def refine_batch_multi(meshes, mesh_index, poses, width: int, height: int, proj, K, scene,
-                       criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(), roi: Optional[Sequence[int]] = None):
+                       criteria: ICPConvergenceCriteria = ICPConvergenceCriteria(), roi: Optional[Sequence[int]] = None,
+                       robust: Optional["Robust"] = None):
     """``pr_refine_batch_multi``: ``refine_batch`` for a batch whose pose i uses ``meshes[mesh_index[i]]`` (a ``Model``, a ``DeviceVector``
     or a host triangle array each), in one call.  Returns (records[P], cloud sizes[P]) in pose order, each equal to what ``refine_batch``
-    gives that pose with its own mesh."""
+    gives that pose with its own mesh.  ``robust``: as for ``refine_batch`` (``pr_refine_pyramid_robust_multi``, one level of stride 1)."""
+    if robust is not None:
+        return refine_pyramid_multi(meshes, mesh_index, poses, width, height, proj, K, scene, levels=((1, criteria),), roi=roi, robust=robust)
     table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
     pj, k = _f32(proj, -1), _f32(K, -1)
     res = np.zeros(len(poses), RESULT)
@@ -880,12 +938,13 @@ def _pyramid_outputs(n_levels: int, n_poses: int, levels, return_levels: bool, r
 
 
 def refine_pyramid(tris, poses, width: int, height: int, proj, K, scene, levels=PYRAMID_DEFAULT, roi: Optional[Sequence[int]] = None,
-                   return_levels: bool = False):
+                   return_levels: bool = False, robust=None):
     """``pr_refine_pyramid``: ``refine_batch`` run coarse to fine.  ``levels``: 1..4 ``PyramidLevel`` (or (stride, criteria) pairs), coarse
     first; level l refines the cloud of every ``stride``-th FRAME column and row, moved by what the levels before it found.  Returns
     (records[P], sizes[P]): the accumulated transform with the last level's fitness and rmse, and the stride-1 cloud size as ``refine_batch``
     returns it when a level has stride 1 -- otherwise the last level's cloud size.  ``return_levels=True``: (records[P],
-    level_records[L, P], level_sizes[L, P]).  One level of stride 1 equals ``refine_batch`` byte for byte."""
+    level_records[L, P], level_sizes[L, P]).  One level of stride 1 equals ``refine_batch`` byte for byte.  ``robust``: one ``Robust`` for
+    every level or one per level (``pr_refine_pyramid_robust``); None is the plain call."""
     table, n_levels = _level_table(levels)
     td = _tris_dev(tris)
     poses = _f32(poses, (-1, 16))
@@ -895,15 +954,21 @@ def refine_pyramid(tris, poses, width: int, height: int, proj, K, scene, levels=
     lres = np.zeros((max(1, n_levels), P), RESULT)
     lsizes = np.zeros((max(1, n_levels), P), np.uint32)
     d = scene.desc()
+    if robust is not None:
+        rtable, n_robust = _robust_table(robust, n_levels)
+        check(_lib.load().pr_refine_pyramid_robust(td.data() or None, td.size() // 9, ptr(poses), P, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
+                                                   table, n_levels, Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(lres), ptr(lsizes),
+                                                   rtable, n_robust))
+        return _pyramid_outputs(n_levels, P, table, return_levels, res, lres, lsizes)
     check(_lib.load().pr_refine_pyramid(td.data() or None, td.size() // 9, ptr(poses), P, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
                                         table, n_levels, Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(lres), ptr(lsizes)))
     return _pyramid_outputs(n_levels, P, table, return_levels, res, lres, lsizes)
 
 
 def refine_pyramid_multi(meshes, mesh_index, poses, width: int, height: int, proj, K, scene, levels=PYRAMID_DEFAULT,
-                         roi: Optional[Sequence[int]] = None, return_levels: bool = False):
+                         roi: Optional[Sequence[int]] = None, return_levels: bool = False, robust=None):
     """``pr_refine_pyramid_multi``: ``refine_pyramid`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; every output in pose
-    order and equal to what ``refine_pyramid`` gives that pose with its own mesh."""
+    order and equal to what ``refine_pyramid`` gives that pose with its own mesh.  ``robust``: as for ``refine_pyramid``."""
     table, n_levels = _level_table(levels)
     mtable, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
     pj, k = _f32(proj, -1), _f32(K, -1)
@@ -912,6 +977,12 @@ def refine_pyramid_multi(meshes, mesh_index, poses, width: int, height: int, pro
     lres = np.zeros((max(1, n_levels), P), RESULT)
     lsizes = np.zeros((max(1, n_levels), P), np.uint32)
     d = scene.desc()
+    if robust is not None:
+        rtable, n_robust = _robust_table(robust, n_levels)
+        check(_lib.load().pr_refine_pyramid_robust_multi(mtable, len(devs), ptr(idx), ptr(poses), P, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
+                                                         table, n_levels, Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(lres), ptr(lsizes),
+                                                         rtable, n_robust))
+        return _pyramid_outputs(n_levels, P, table, return_levels, res, lres, lsizes)
     check(_lib.load().pr_refine_pyramid_multi(mtable, len(devs), ptr(idx), ptr(poses), P, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
                                               table, n_levels, Roi(*(roi if roi is not None else (0, 0, 0, 0))), ptr(res), ptr(lres), ptr(lsizes)))
     return _pyramid_outputs(n_levels, P, table, return_levels, res, lres, lsizes)

@@ -84,10 +84,11 @@ hipError_t launch_grid_records(const pr_vec3 *pcd, const pr_vec3 *normal, uint32
 // i = 0..3, of every 1024-point step.  Per step: the four points in (contiguous 12-byte loads), the pending update applied, ALL FOUR cell-index
 // loads issued, then ALL FOUR record loads (two float4 each; record 0 stands in for a lane without a winner), and only then the tests and the
 // accumulation: two dependent memory round trips per step, not eight.
-template <bool kScoreOnly>
+template <bool kScoreOnly, bool kRobust = false>
 __device__ __forceinline__ void grid_vb_accumulate(float (&acc_out)[29], float *cl, uint32_t n, uint32_t first, uint32_t steps, bool xf,
-                                                   const float (&M)[12], const SceneGridDev &scene)
+                                                   const float (&M)[12], const SceneGridDev &scene, const RobustW &rb = RobustW{})
 {
+    (void)rb;
     Acc29 acc;
     acc_clear(acc);
     const uint32_t last = n - 1u;                                // n >= 1 here: the workgroup has points
@@ -152,8 +153,7 @@ __device__ __forceinline__ void grid_vb_accumulate(float (&acc_out)[29], float *
         for (uint32_t i = 0; i < 4; ++i) {
             if (w[i] != PR_GRID_NONE && grid_accept(scene, p[3 * i], p[3 * i + 1], p[3 * i + 2], d[i])) {
                 Corr c; c.dx = d[i].x; c.dy = d[i].y; c.dz = d[i].z; c.nx = nr[i].x; c.ny = nr[i].y; c.nz = nr[i].z;
-                if constexpr (kScoreOnly) accumulate_score(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c);
-                else accumulate(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c);
+                accumulate_point<kScoreOnly, kRobust>(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c, rb);
             }
         }
     }
@@ -161,6 +161,7 @@ __device__ __forceinline__ void grid_vb_accumulate(float (&acc_out)[29], float *
 }
 
 // grid = (workgroups per hypothesis, hypotheses), 256 lanes: icp_pass_kernel's frame (icp_pass.hip) around the grid's own point loop
+template <bool kRobust = false>
 __global__ __launch_bounds__(256, PR_GRID_PASS_WAVES) void icp_pass_grid_kernel(IcpBatch b, SceneGridDev scene)
 {
     __shared__ float wsum[4][kAccStride];
@@ -190,7 +191,8 @@ __global__ __launch_bounds__(256, PR_GRID_PASS_WAVES) void icp_pass_grid_kernel(
             grid_vb_accumulate<true>(acc, cl, n, vb * ppb, b.steps, xf, M, scene);
             t = vb_reduce<true>(acc, wsum);
         } else {
-            grid_vb_accumulate<false>(acc, cl, n, vb * ppb, b.steps, xf, M, scene);
+            if constexpr (kRobust) grid_vb_accumulate<false, true>(acc, cl, n, vb * ppb, b.steps, xf, M, scene, RobustW{ b.robust_kind, b.robust_c, b.robust_inv_c });
+            else grid_vb_accumulate<false>(acc, cl, n, vb * ppb, b.steps, xf, M, scene);
             t = vb_reduce(acc, wsum);
         }
         if (pass_deliver(b, pose, vb, used, n, t)) return;
@@ -208,7 +210,8 @@ hipError_t launch_icp_pass_grid(const IcpBatch &b, const SceneGridDev &sc, uint3
         if (bb.st) bb.st += p0;
         if (bb.arrive) bb.arrive += p0;
         if (bb.sums_out) bb.sums_out += (size_t)p0 * kAccStride;
-        hipLaunchKernelGGL(icp_pass_grid_kernel, dim3(b.grid_x ? b.grid_x : b.nblk, np), dim3(kBlockThreads), 0, s, bb, sc);
+        if (b.robust_kind != PR_ROBUST_NONE) hipLaunchKernelGGL(icp_pass_grid_kernel<true>, dim3(b.grid_x ? b.grid_x : b.nblk, np), dim3(kBlockThreads), 0, s, bb, sc);
+        else hipLaunchKernelGGL(icp_pass_grid_kernel<false>, dim3(b.grid_x ? b.grid_x : b.nblk, np), dim3(kBlockThreads), 0, s, bb, sc);
     }
     return hipGetLastError();
 }
@@ -217,7 +220,8 @@ hipError_t launch_icp_pass_grid(const IcpBatch &b, const SceneGridDev &sc, uint3
 //  audit entry: the 29 terms of every point of one cloud (pr_debug_contrib29), one lane per point
 // ================================================================================================
 struct GridUpdate12 { float m[12]; };
-__global__ __launch_bounds__(256) void contrib29_grid_kernel(pr_vec3 *__restrict__ cloud, uint32_t n, int apply, GridUpdate12 u, SceneGridDev scene, float *__restrict__ out)
+template <bool kRobust = false, class... Robust>                  // Robust: nothing, or (kRobust) one RobustArgs
+__global__ __launch_bounds__(256) void contrib29_grid_kernel(pr_vec3 *__restrict__ cloud, uint32_t n, int apply, GridUpdate12 u, SceneGridDev scene, float *__restrict__ out, Robust... ra)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
@@ -225,6 +229,8 @@ __global__ __launch_bounds__(256) void contrib29_grid_kernel(pr_vec3 *__restrict
     if (apply) { p = transform_point(u.m, p); cloud[i] = p; }    // the fused pass' operand order
     Acc29 acc;
     acc_clear(acc);
+    Corr found{}; float wt = 0.0f; bool valid = false;            // (kRobust: what pr_debug_robust_terms reports beside the terms)
+    (void)found; (void)wt; (void)valid;
     uint32_t idx;
     if (grid_cell_of(scene, p.x, p.y, p.z, idx)) {
         const uint32_t w = scene.cell_point[idx];
@@ -232,10 +238,12 @@ __global__ __launch_bounds__(256) void contrib29_grid_kernel(pr_vec3 *__restrict
             const float4 d = scene.rec[2 * (size_t)w], nr = scene.rec[2 * (size_t)w + 1];
             if (grid_accept(scene, p.x, p.y, p.z, d)) {
                 Corr c; c.dx = d.x; c.dy = d.y; c.dz = d.z; c.nx = nr.x; c.ny = nr.y; c.nz = nr.z;
-                accumulate(acc, p.x, p.y, p.z, c);
+                if constexpr (kRobust) { const RobustArgs &a = (ra, ...); wt = accumulate_weighted(acc, p.x, p.y, p.z, c, RobustW{ a.kind, a.c, a.inv_c }); found = c; valid = true; }
+                else accumulate(acc, p.x, p.y, p.z, c);
             }
         }
     }
+    if constexpr (kRobust) { const RobustArgs &a = (ra, ...); if (a.corr) robust_store_corr(a.corr + (size_t)i * 8, valid, found, wt); }
     float t[29];
     acc_export(acc, t);
 #pragma unroll
@@ -246,7 +254,15 @@ hipError_t launch_contrib29_grid(pr_vec3 *cloud, uint32_t n, const float *update
     if (n == 0) return hipSuccess;
     GridUpdate12 u{};
     if (update12) for (int k = 0; k < 12; ++k) u.m[k] = update12[k];
-    hipLaunchKernelGGL(contrib29_grid_kernel, dim3((n + 255) / 256), dim3(256), 0, s, cloud, n, update12 ? 1 : 0, u, sc, out);
+    hipLaunchKernelGGL(contrib29_grid_kernel<>, dim3((n + 255) / 256), dim3(256), 0, s, cloud, n, update12 ? 1 : 0, u, sc, out);
+    return hipGetLastError();
+}
+hipError_t launch_robust_terms_grid(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneGridDev &sc, const RobustArgs &ra, float *out, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    GridUpdate12 u{};
+    if (update12) for (int k = 0; k < 12; ++k) u.m[k] = update12[k];
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(contrib29_grid_kernel<true, RobustArgs>), dim3((n + 255) / 256), dim3(256), 0, s, cloud, n, update12 ? 1 : 0, u, sc, out, ra);
     return hipGetLastError();
 }
 

@@ -57,6 +57,63 @@ __device__ __forceinline__ void accumulate(Acc29 &acc, float sx, float sy, float
     acc.pk[14] += PR_SEL(N2Z, 0, 0) * N2Z;                        // J5J5, (J5 dz)
     acc.pk[15] += float2v{ e2, 1.0f };
 }
+
+// ---- robust pass (pr_robust, include/pose_refine.h) -----------------------------------------------------------------------------------------
+// The weight of a residual.  `kind` is wavefront-uniform (IcpBatch::robust_kind): the branches are scalar, and this function is the only
+// place that looks at it.  Every operation is a float32 operation of its own (the file is compiled without contraction); '/' is the
+// correctly rounded division.
+struct RobustW { uint32_t kind; float c, inv_c; };
+__device__ __forceinline__ float robust_weight(float r, const RobustW &rb)
+{
+    if (rb.kind == PR_ROBUST_NONE) return 1.0f;
+    if (rb.kind == PR_ROBUST_HUBER) { const float a = fabsf(r); return (a <= rb.c) ? 1.0f : rb.c / a; }
+    const float u = r * rb.inv_c, q = u * u;
+    if (rb.kind == PR_ROBUST_TUKEY) { const float t = 1.0f - q; return (q < 1.0f) ? t * t : 0.0f; }
+    return 1.0f / (1.0f + q);                                    // PR_ROBUST_CAUCHY
+}
+// accumulate() with the weighted terms: the four natural pairs times (w, w) -- four packed multiplies, seven values of which the header's
+// factor table uses (w*dz is surplus) -- then the same sixteen packed accumulations, each with exactly one weighted operand:
+//   sums 0..20 (J[a]*J[b], a <= b): (w*J[a]) * J[b];   sums 21..23 (J[a]*r, a < 3): (w*J[a]) * r;   sums 24..26 (J[a]*r, a >= 3): J[a] * (w*r)
+// so every instruction still takes its operands from the pairs as they stand (op_sel), without a register move.  Sums 27 and 28 are plain.
+// w == 1.0f leaves every product the plain product, bit for bit.  Returns w (the audit kernel reports it).
+__device__ __forceinline__ float accumulate_weighted(Acc29 &acc, float sx, float sy, float sz, const Corr &c, const RobustW &rb)
+{
+    const float ex = c.dx - sx, ey = c.dy - sy, ez = c.dz - sz;
+    const float r = ex * c.nx + ey * c.ny + ez * c.nz;
+    const float2v C01{ c.nz * sy - c.ny * sz, c.nx * sz - c.nz * sx };
+    const float2v C2R{ c.ny * sx - c.nx * sy, r };
+    const float2v N01{ c.nx, c.ny };
+    const float2v N2Z{ c.nz, c.dz };
+    const float e2 = ex * ex + ey * ey + ez * ez;
+    const float w = robust_weight(r, rb);
+    const float2v W{ w, w };
+    const float2v WC01 = W * C01, WC2R = W * C2R, WN01 = W * N01, WN2Z = W * N2Z;      // wJ0 wJ1 | wJ2 wr | wJ3 wJ4 | wJ5 (w dz)
+    acc.pk[0]  += PR_SEL(WC01, 0, 0) * C01;                       // wJ0 J0, wJ0 J1
+    acc.pk[1]  += PR_SEL(WC01, 1, 1) * PR_SEL(C01, 1, 0);         // wJ1 J1, (wJ1 J0)
+    acc.pk[2]  += PR_SEL(WC01, 0, 0) * C2R;                       // wJ0 J2, wJ0 r
+    acc.pk[3]  += PR_SEL(WC01, 1, 1) * C2R;                       // wJ1 J2, wJ1 r
+    acc.pk[4]  += PR_SEL(WC01, 0, 0) * N01;                       // wJ0 J3, wJ0 J4
+    acc.pk[5]  += PR_SEL(WC01, 1, 1) * N01;                       // wJ1 J3, wJ1 J4
+    acc.pk[6]  += WC01 * PR_SEL(N2Z, 0, 0);                       // wJ0 J5, wJ1 J5
+    acc.pk[7]  += PR_SEL(WC2R, 0, 0) * C2R;                       // wJ2 J2, wJ2 r
+    acc.pk[8]  += PR_SEL(WC2R, 0, 0) * N01;                       // wJ2 J3, wJ2 J4
+    acc.pk[9]  += PR_SEL(WC2R, 1, 1) * N01;                       // wr J3,  wr J4
+    acc.pk[10] += WC2R * PR_SEL(N2Z, 0, 0);                       // wJ2 J5, wr J5
+    acc.pk[11] += PR_SEL(WN01, 0, 0) * N01;                       // wJ3 J3, wJ3 J4
+    acc.pk[12] += PR_SEL(WN01, 1, 1) * PR_SEL(N01, 1, 0);         // wJ4 J4, (wJ4 J3)
+    acc.pk[13] += WN01 * PR_SEL(N2Z, 0, 0);                       // wJ3 J5, wJ4 J5
+    acc.pk[14] += PR_SEL(WN2Z, 0, 0) * N2Z;                       // wJ5 J5, (wJ5 dz)
+    acc.pk[15] += float2v{ e2, 1.0f };
+    return w;
+}
+// the row pr_debug_robust_terms reports per point: {dx, dy, dz, valid, nx, ny, nz, w}, zeros without a valid correspondence
+__device__ __forceinline__ void robust_store_corr(float *row, bool valid, const Corr &c, float w)
+{
+    const float4 a = valid ? make_float4(c.dx, c.dy, c.dz, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 b = valid ? make_float4(c.nx, c.ny, c.nz, w) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    reinterpret_cast<float4 *>(row)[0] = a;
+    reinterpret_cast<float4 *>(row)[1] = b;
+}
 #undef PR_SEL
 
 // the last pass of an ICP (iteration == max_iteration, icp.cu:189) only feeds fitness and rmse: sums 27 (squared distance)
@@ -75,12 +132,20 @@ __device__ __forceinline__ void accumulate_score(Acc29 &acc, float sx, float sy,
 
 // One virtual workgroup of the canonical tree: accumulate the 29 sums of points [first, first + steps*1024) of one
 // cloud into the lane's registers (pending transform applied and written back first when xf).
-template <class Scene, bool kNN, int kStack, bool kScoreOnly = false>
+// the point's contribution as the instantiation forms it: score-only (the last pass), weighted (kRobust), or plain
+template <bool kScoreOnly, bool kRobust>
+__device__ __forceinline__ void accumulate_point(Acc29 &acc, float sx, float sy, float sz, const Corr &c, const RobustW &rb)
+{
+    if constexpr (kScoreOnly) accumulate_score(acc, sx, sy, sz, c);
+    else if constexpr (kRobust) (void)accumulate_weighted(acc, sx, sy, sz, c, rb);
+    else accumulate(acc, sx, sy, sz, c);
+}
+template <class Scene, bool kNN, int kStack, bool kScoreOnly = false, bool kRobust = false>
 __device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, uint32_t n, uint32_t first, uint32_t steps, bool xf,
                                               const float (&M)[12], const Scene &scene, const int4 *lds_topo, int *stk_node, float *stk_lb,
-                                              uint32_t *nn_prev = nullptr, bool nn_seeded = false)
+                                              uint32_t *nn_prev = nullptr, bool nn_seeded = false, const RobustW &rb = RobustW{})
 {
-    (void)nn_prev; (void)nn_seeded;
+    (void)nn_prev; (void)nn_seeded; (void)rb;
     struct { uint32_t steps; } b{ steps };
     Acc29 acc;                                                   // the caller's sums start at zero
     acc_clear(acc);
@@ -155,7 +220,7 @@ __device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, u
             for (uint32_t i = 0; i < 4; ++i) {
                 if (w[i] != kNoPrev) {
                     Corr c; c.dx = d[i].x; c.dy = d[i].y; c.dz = d[i].z; c.nx = nx[i]; c.ny = ny[i]; c.nz = nz[i];
-                    if constexpr (kScoreOnly) accumulate_score(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c); else accumulate(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c);
+                    accumulate_point<kScoreOnly, kRobust>(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c, rb);
                 }
             }
         } else if constexpr (kNN) {
@@ -172,7 +237,7 @@ __device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, u
                         if (nn_prev) nn_prev[point_of(j0, i)] = ok ? winner : kNoPrev;
                         if (ok) lane_winner = winner;
                     } else ok = query_nn<true>(scene, lds_topo, p[3 * i], p[3 * i + 1], p[3 * i + 2], c);
-                    if (ok) { if constexpr (kScoreOnly) accumulate_score(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c); else accumulate(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c); }
+                    if (ok) { accumulate_point<kScoreOnly, kRobust>(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c, rb); }
                 }
             }
         } else {
@@ -194,8 +259,7 @@ __device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, u
                     const uint32_t i = i0 + k;
                     Corr c;
                     if (gather_finish(scene, in_img[k], p[3 * i + 2], gth[k], c)) {
-                        if constexpr (kScoreOnly) accumulate_score(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c);
-                        else accumulate(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c);
+                        accumulate_point<kScoreOnly, kRobust>(acc, p[3 * i], p[3 * i + 1], p[3 * i + 2], c, rb);
                     }
                 }
             }

@@ -13,8 +13,9 @@ namespace prk {
 
 struct Update12 { float m[12]; };
 
-template <class Scene, bool kNN>
-__global__ __launch_bounds__(256) void contrib29_kernel(pr_vec3 *__restrict__ cloud, uint32_t n, int apply, Update12 u, Scene scene, float *__restrict__ out)
+// kRobust (pr_debug_robust_terms): the weighted terms of the one RobustArgs in `ra`, and the correspondence and weight beside them
+template <class Scene, bool kNN, bool kRobust = false, class... Robust>
+__global__ __launch_bounds__(256) void contrib29_kernel(pr_vec3 *__restrict__ cloud, uint32_t n, int apply, Update12 u, Scene scene, float *__restrict__ out, Robust... ra)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
@@ -33,7 +34,12 @@ __global__ __launch_bounds__(256) void contrib29_kernel(pr_vec3 *__restrict__ cl
     else ok = query(scene, p.x, p.y, p.z, c);
     Acc29 acc;
     acc_clear(acc);
-    if (ok) accumulate(acc, p.x, p.y, p.z, c);
+    if constexpr (kRobust) {
+        const RobustArgs &a = (ra, ...);
+        float w = 0.0f;
+        if (ok) w = accumulate_weighted(acc, p.x, p.y, p.z, c, RobustW{ a.kind, a.c, a.inv_c });
+        if (a.corr) robust_store_corr(a.corr + (size_t)i * 8, ok, c, w);
+    } else if (ok) accumulate(acc, p.x, p.y, p.z, c);
     float t[29];
     acc_export(acc, t);
 #pragma unroll
@@ -55,6 +61,22 @@ hipError_t launch_contrib29_proj_packed(pr_vec3 *cloud, uint32_t n, const float 
 { return launch_contrib29_t<SceneProjPacked, false>(cloud, n, update12, sc, out, s); }
 hipError_t launch_contrib29_nn(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneNNDev &sc, float *out, hipStream_t s)
 { return launch_contrib29_t<SceneNNDev, true>(cloud, n, update12, sc, out, s); }
+
+template <class Scene, bool kNN>
+static hipError_t launch_robust_terms_t(pr_vec3 *cloud, uint32_t n, const float *update12, const Scene &sc, const RobustArgs &ra, float *out, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    Update12 u{};
+    if (update12) for (int k = 0; k < 12; ++k) u.m[k] = update12[k];
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(contrib29_kernel<Scene, kNN, true, RobustArgs>), dim3((n + 255) / 256), dim3(256), 0, s, cloud, n, update12 ? 1 : 0, u, sc, out, ra);
+    return hipGetLastError();
+}
+hipError_t launch_robust_terms_proj_aos(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjAoS &sc, const RobustArgs &ra, float *out, hipStream_t s)
+{ return launch_robust_terms_t<SceneProjAoS, false>(cloud, n, update12, sc, ra, out, s); }
+hipError_t launch_robust_terms_proj_packed(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjPacked &sc, const RobustArgs &ra, float *out, hipStream_t s)
+{ return launch_robust_terms_t<SceneProjPacked, false>(cloud, n, update12, sc, ra, out, s); }
+hipError_t launch_robust_terms_nn(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneNNDev &sc, const RobustArgs &ra, float *out, hipStream_t s)
+{ return launch_robust_terms_t<SceneNNDev, true>(cloud, n, update12, sc, ra, out, s); }
 
 // One wavefront per hypothesis, all 64 lanes active (pose_iteration_wave needs them): lanes 0..28 hold the 29 sums as the pass tail
 // leaves them in `total`; the function itself runs unchanged on a DevIcpState built from the caller's record.

@@ -10,7 +10,7 @@ namespace prk {
 //  THE hot kernel: pending transform + correspondence + 29-term transform-reduce, all hypotheses
 //  of a batch in one launch.  grid = (workgroups per hypothesis, hypotheses), 256 lanes.
 // ================================================================================================
-template <class Scene, bool kNN, int kStack = 0>
+template <class Scene, bool kNN, int kStack = 0, bool kRobust = false>
 __global__ __launch_bounds__(256, PR_PASS_WAVES) void icp_pass_kernel(IcpBatch b, Scene scene)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -64,7 +64,10 @@ __global__ __launch_bounds__(256, PR_PASS_WAVES) void icp_pass_kernel(IcpBatch b
             vb_accumulate<Scene, kNN, kStack, true>(acc, cl, n, vb * ppb, b.steps, xf, M, scene, lds_topo, stk_node, stk_lb, nn_prev, xf);
             t = vb_reduce<true>(acc, wsum);
         } else {
-            vb_accumulate<Scene, kNN, kStack>(acc, cl, n, vb * ppb, b.steps, xf, M, scene, lds_topo, stk_node, stk_lb, nn_prev, xf);
+            if constexpr (kRobust)                               // the weight of b (uniform); the score-only pass above needs none
+                vb_accumulate<Scene, kNN, kStack, false, true>(acc, cl, n, vb * ppb, b.steps, xf, M, scene, lds_topo, stk_node, stk_lb, nn_prev, xf, RobustW{ b.robust_kind, b.robust_c, b.robust_inv_c });
+            else
+                vb_accumulate<Scene, kNN, kStack>(acc, cl, n, vb * ppb, b.steps, xf, M, scene, lds_topo, stk_node, stk_lb, nn_prev, xf);
             t = vb_reduce(acc, wsum);
         }
         if (pass_deliver(b, pose, vb, used, n, t)) return;
@@ -158,7 +161,7 @@ __global__ void stage_words64_kernel(const uint2 *__restrict__ src, uint2 *__res
     if (i < n8) dst[i] = src[i];
 }
 
-template <class Scene, bool kNN, int kStack = 0>
+template <class Scene, bool kNN, int kStack = 0, bool kRobust = false>
 static hipError_t launch_pass(const IcpBatch &b, const Scene &sc, uint32_t n_poses, size_t lds_bytes, hipStream_t s)
 {
     if (n_poses == 0 || b.nblk == 0) return hipSuccess;
@@ -171,18 +174,21 @@ static hipError_t launch_pass(const IcpBatch &b, const Scene &sc, uint32_t n_pos
         if (bb.arrive) bb.arrive += p0;
         if (bb.sums_out) bb.sums_out += (size_t)p0 * kAccStride;
         if (bb.nn_qcount) bb.nn_qcount += kQCountStride * (size_t)p0;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(icp_pass_kernel<Scene, kNN, kStack>), dim3(b.grid_x ? b.grid_x : b.nblk, np), dim3(kBlockThreads), lds_bytes, s, bb, sc);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(icp_pass_kernel<Scene, kNN, kStack, kRobust>), dim3(b.grid_x ? b.grid_x : b.nblk, np), dim3(kBlockThreads), lds_bytes, s, bb, sc);
     }
     return hipGetLastError();
 }
 hipError_t launch_icp_pass_proj_aos(const IcpBatch &b, const SceneProjAoS &sc, uint32_t n_poses, hipStream_t s)
-{ return launch_pass<SceneProjAoS, false>(b, sc, n_poses, 0, s); }
+{ return b.robust_kind != PR_ROBUST_NONE ? launch_pass<SceneProjAoS, false, 0, true>(b, sc, n_poses, 0, s) : launch_pass<SceneProjAoS, false>(b, sc, n_poses, 0, s); }
 // (Round 5 measured the two tables colf / rowf of the packed scene staged in LDS per workgroup -- two of a point's three gathers off the texture
 // addresser: 0.84 against 0.82 ms per 21 launches, 272 / 263 k against 277 / 276 k poses/s on one box.  Not kept.)
 hipError_t launch_icp_pass_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s)
-{ return launch_pass<SceneProjPacked, false>(b, sc, n_poses, 0, s); }
+{ return b.robust_kind != PR_ROBUST_NONE ? launch_pass<SceneProjPacked, false, 0, true>(b, sc, n_poses, 0, s) : launch_pass<SceneProjPacked, false>(b, sc, n_poses, 0, s); }
 hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s)
 {
+    // a robust pass that searches in the pass (a scene without compact records: with them the driver takes the split route) walks stackless,
+    // the one in-pass walk instantiated with the weight; every walk returns the same winners
+    if (b.robust_kind != PR_ROBUST_NONE) return launch_pass<SceneNNDev, true, 0, true>(b, sc, n_poses, (size_t)sc.lds_nodes * sizeof(int4), s);
     if (sc.stack_depth == 16 && sc.rec32) return launch_pass<SceneNNDev, true, 16 + 0x100>(b, sc, n_poses, (size_t)16 * kBlockThreads * 8, s);
     if (sc.stack_depth == 24 && sc.rec32) return launch_pass<SceneNNDev, true, 24 + 0x100>(b, sc, n_poses, (size_t)24 * kBlockThreads * 8, s);
     if (sc.stack_depth == 16) return launch_pass<SceneNNDev, true, 16>(b, sc, n_poses, (size_t)16 * kBlockThreads * 8 + (size_t)sc.lds_nodes * 64, s);
@@ -191,7 +197,7 @@ hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t 
 }
 
 hipError_t launch_icp_pass_nn_winners(const IcpBatch &b, const SceneNNWinners &sc, uint32_t n_poses, hipStream_t s)
-{ return launch_pass<SceneNNWinners, true, -1>(b, sc, n_poses, 0, s); }
+{ return b.robust_kind != PR_ROBUST_NONE ? launch_pass<SceneNNWinners, true, -1, true>(b, sc, n_poses, 0, s) : launch_pass<SceneNNWinners, true, -1>(b, sc, n_poses, 0, s); }
 
 hipError_t launch_icp_finalize(const float *partial, const PoseMeta *meta, uint32_t nblk,
                                uint32_t steps, float *sums, uint32_t n_poses, hipStream_t s)

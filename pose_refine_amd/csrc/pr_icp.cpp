@@ -170,7 +170,7 @@ int drive_device(IcpRun &r)
         GraphKey key;
         key.add(P); key.add(b.nblk); key.add(b.steps); key.add(crit); key.add(r.sc); key.add(b.cloud); key.add(g->meta.p); key.add(g->partial.p);
         key.add(g->dstate.p); key.add(dres); key.add(r.results_host != nullptr); key.add(r.res); key.add(r.h_meta); key.add(init); key.add(opt.profile); key.add(pose_groups_for(r.sc.kind)); key.add(opt.fused_solve); key.add(g->arrive.p); key.add(b.nn_prev);
-        key.add(b.nn_slack); key.add(b.nn_queue); key.add(b.nn_queue2); key.add(b.nn_qcount);    // nn_carve: behind nn_prev at multiples of `span` (max start+count) -- same P / max_n, other offsets => other addresses
+        key.add(b.nn_slack); key.add(b.nn_queue); key.add(b.nn_queue2); key.add(b.nn_qcount); key.add(b.robust_kind); key.add(b.robust_c); key.add(b.robust_inv_c);    // nn_carve: behind nn_prev at multiples of `span` (max start+count) -- same P / max_n, other offsets => other addresses
         CachedGraph *hit = nullptr;
         PR_TRY(cached_graph(key, [&] { return enqueue_all(/*host_checks=*/false); }, hit));
         HIP_TRY(hipGraphLaunch(hit->exec, g->stream));
@@ -340,7 +340,7 @@ int drive_host(IcpRun &r)
 // clouds: cloud i = cloud_base[start_h[i] .. start_h[i]+count_h[i]); start and count reach the device with the per-hypothesis records staged here.
 // The set-up both drivers share -- workspaces, the batch, the kd-tree workspace, the start records and results -- then the driver of option solve.
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
-              pr_criteria crit, pr_result *results_host, pr_result *results_dev)
+              pr_criteria crit, pr_result *results_host, pr_result *results_dev, const pr_robust &robust)
 {
     if (P == 0) return PR_OK;
     if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
@@ -365,7 +365,11 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
     prk::IcpBatch &b = r.b;
     b.cloud = cloud_base; b.meta = g->meta.as<prk::PoseMeta>(); b.partial = g->partial.as<float>();
     b.nblk = nblk; b.steps = steps;
+    b.robust_kind = robust.kind; b.robust_c = robust.c; b.robust_inv_c = robust.inv_c;       // (the entry points have checked the descriptor)
     sc.nn_split = nn_split_for(sc);
+    // a robust pass over a kd-tree scene takes the split route wherever the scene allows it, whatever option nn_split says: the winners pass is
+    // the one instantiated with the weight (a scene without compact records walks stackless in the pass, launch_icp_pass_nn)
+    if (robust.kind != PR_ROBUST_NONE && sc.kind == PR_SCENE_NN && sc.nn.rec32) sc.nn_split = 1u;
     sc.nn_max_points = max_n;
     if (sc.nn_split && opt.nn_count) {                            // instrumented run: kCounterPasses x 8 counters, accumulated until read
         const bool fresh = g->nn_counters.p == nullptr;
@@ -396,23 +400,22 @@ int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *coun
 
 using namespace prr;
 
-extern "C" {
-
-int pr_icp_batch(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind, const void *scene,
-                 pr_criteria crit, pr_result *results_host)
+// pr_icp_batch and pr_icp_batch_robust (fn: whose messages) behind the latter's descriptor check
+static int icp_batch_impl(const char *fn, pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind, const void *scene,
+                          pr_criteria crit, const pr_robust &robust, pr_result *results_host)
 {
     TraceScope traced;                                            // (pr_debug_trace_sums: this call and no other)
     PR_ENTER();
-    if (!offsets_host || (n_clouds && !results_host)) { set_error("pr_icp_batch: bad arguments"); return PR_ERR_INVALID; }
+    if (!offsets_host || (n_clouds && !results_host)) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
     if (n_clouds == 0) return PR_OK;
 #ifndef PR_MAX_CLOUDS_PER_RUN
 #define PR_MAX_CLOUDS_PER_RUN 32768                               // (a larger value in an experiment build exercises the launchers' own split)
 #endif
     constexpr uint32_t kMaxCloudsPerRun = PR_MAX_CLOUDS_PER_RUN;
-    PR_TRY(sums_trace_admits("pr_icp_batch", n_clouds, crit));     // (pr_debug_trace_sums: the whole list against the recorder, before the scene is touched)
-    if (tl_sums_trace.active.rows && n_clouds > kMaxCloudsPerRun) { set_error("pr_icp_batch: pr_debug_trace_sums records one run of at most %u clouds, the list has %u", kMaxCloudsPerRun, n_clouds); return PR_ERR_INVALID; }
+    PR_TRY(sums_trace_admits(fn, n_clouds, crit));     // (pr_debug_trace_sums: the whole list against the recorder, before the scene is touched)
+    if (tl_sums_trace.active.rows && n_clouds > kMaxCloudsPerRun) { set_error("%s: pr_debug_trace_sums records one run of at most %u clouds, the list has %u", fn, kMaxCloudsPerRun, n_clouds); return PR_ERR_INVALID; }
     if (!clouds_dev) {                                            // clouds without a single point come without an array (an empty device_vector):
-        if (offsets_host[n_clouds] != offsets_host[0]) { set_error("pr_icp_batch: null cloud array"); return PR_ERR_INVALID; }
+        if (offsets_host[n_clouds] != offsets_host[0]) { set_error("%s: null cloud array", fn); return PR_ERR_INVALID; }
         for (uint32_t i = 0; i < n_clouds; ++i) {                 // count == 0 -> identity, fitness 0, rmse 0 (icp.cu:183), like any empty cloud
             identity16(results_host[i].T); results_host[i].fitness = 0.0f; results_host[i].inlier_rmse = 0.0f;
         }
@@ -423,16 +426,43 @@ int pr_icp_batch(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_c
     PR_TRY(make_scene(scene_kind, scene, /*want_packed=*/false, sc));
     std::vector<uint32_t> start(n_clouds), count(n_clouds);
     for (uint32_t i = 0; i < n_clouds; ++i) {
-        if (offsets_host[i + 1] < offsets_host[i]) { set_error("pr_icp_batch: offsets must be non-decreasing"); return PR_ERR_INVALID; }
+        if (offsets_host[i + 1] < offsets_host[i]) { set_error("%s: offsets must be non-decreasing", fn); return PR_ERR_INVALID; }
         start[i] = offsets_host[i]; count[i] = offsets_host[i + 1] - offsets_host[i];
     }
     // the hypothesis index is the y dimension of every launch of the loop (65 535 at most): longer lists run in pieces, one after the other
     // (the clouds are independent of each other, so the pieces are)
     for (uint32_t c0 = 0; c0 < n_clouds; c0 += kMaxCloudsPerRun) {
         const uint32_t nc = std::min(kMaxCloudsPerRun, n_clouds - c0);
-        PR_TRY(icp_drive(clouds_dev, start.data() + c0, count.data() + c0, nc, sc, crit, results_host + c0, nullptr));
+        PR_TRY(icp_drive(clouds_dev, start.data() + c0, count.data() + c0, nc, sc, crit, results_host + c0, nullptr, robust));
     }
     return PR_OK;
+}
+
+extern "C" {
+
+int pr_icp_batch(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind, const void *scene,
+                 pr_criteria crit, pr_result *results_host)
+{
+    return icp_batch_impl("pr_icp_batch", clouds_dev, offsets_host, n_clouds, scene_kind, scene, crit, pr_robust{ PR_ROBUST_NONE, 0.0f, 0.0f, 0 }, results_host);
+}
+
+int pr_robust_describe(uint32_t kind, float c, pr_robust *out)
+{
+    const char *fn = "pr_robust_describe";
+    if (!out) { set_error("%s: bad arguments (out is null)", fn); return PR_ERR_INVALID; }
+    pr_robust rb{ kind, kind == PR_ROBUST_NONE ? 0.0f : c, 0.0f, 0 };
+    if (kind != PR_ROBUST_NONE && kind <= PR_ROBUST_CAUCHY && std::isfinite(c) && c > 0.0f) rb.inv_c = 1.0f / c;     // once, in float32
+    PR_TRY(robust_desc_ok(fn, &rb));
+    *out = rb;
+    return PR_OK;
+}
+
+int pr_icp_batch_robust(pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind, const void *scene,
+                        pr_criteria crit, const pr_robust *robust, pr_result *results_host)
+{
+    PR_TRY(robust_desc_ok("pr_icp_batch_robust", robust));          // before any device is touched
+    if (!offsets_host || (n_clouds && (!results_host || !scene))) { set_error("pr_icp_batch_robust: bad arguments"); return PR_ERR_INVALID; }
+    return icp_batch_impl("pr_icp_batch_robust", clouds_dev, offsets_host, n_clouds, scene_kind, scene, crit, *robust, results_host);
 }
 
 int pr_icp_proj(pr_vec3 *cloud_dev, uint32_t n_points, const pr_scene_proj *scene, pr_criteria crit, pr_result *result_out)
@@ -489,6 +519,36 @@ int pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, co
     note_write(cloud_dev, sizeof(pr_vec3) * (size_t)n_points);
     out.release();
     if (e != hipSuccess) { (void)hipGetLastError(); set_error("pr_debug_contrib29: %s", hipGetErrorString(e)); return PR_ERR_HIP; }
+    return PR_OK;
+}
+
+// Audit entry: pr_debug_contrib29 with the weighted terms of `robust`, and per point the correspondence and weight beside them (corr_host, optional).
+int pr_debug_robust_terms(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, const void *scene, const float *update16, int want_packed,
+                          const pr_robust *robust, float *contrib_host, float *corr_host)
+{
+    PR_TRY(robust_desc_ok("pr_debug_robust_terms", robust));        // before any device is touched
+    if (n_points && (!cloud_dev || !contrib_host || !scene)) { set_error("pr_debug_robust_terms: null buffer"); return PR_ERR_INVALID; }
+    PR_ENTER();
+    if (n_points == 0) return PR_OK;
+    SceneSel sc;
+    std::memset(static_cast<void *>(&sc), 0, sizeof sc);
+    PR_TRY(make_scene(scene_kind, scene, want_packed != 0, sc));
+    DevBuf out;
+    const size_t b_terms = sizeof(float) * 29 * (size_t)n_points, b_corr = corr_host ? sizeof(float) * 8 * (size_t)n_points : 0;
+    PR_TRY(out.ensure(((b_terms + 15) & ~(size_t)15) + b_corr));
+    float *d_corr = corr_host ? reinterpret_cast<float *>(static_cast<char *>(out.p) + ((b_terms + 15) & ~(size_t)15)) : nullptr;      // (16-byte aligned: the rows go out as float4)
+    const prk::RobustArgs ra{ robust->kind, robust->c, robust->inv_c, d_corr };
+    hipError_t e;
+    if (sc.kind == PR_SCENE_GRID) e = prk::launch_robust_terms_grid(cloud_dev, n_points, update16, sc.grid, ra, out.as<float>(), g->stream);
+    else if (sc.kind == PR_SCENE_NN) e = prk::launch_robust_terms_nn(cloud_dev, n_points, update16, sc.nn, ra, out.as<float>(), g->stream);
+    else if (sc.packed) e = prk::launch_robust_terms_proj_packed(cloud_dev, n_points, update16, sc.pk, ra, out.as<float>(), g->stream);
+    else e = prk::launch_robust_terms_proj_aos(cloud_dev, n_points, update16, sc.aos, ra, out.as<float>(), g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(contrib_host, out.p, b_terms, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess && corr_host) e = hipMemcpyAsync(corr_host, d_corr, b_corr, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    note_write(cloud_dev, sizeof(pr_vec3) * (size_t)n_points);
+    out.release();
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("pr_debug_robust_terms: %s", hipGetErrorString(e)); return PR_ERR_HIP; }
     return PR_OK;
 }
 

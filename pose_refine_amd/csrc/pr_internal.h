@@ -67,7 +67,13 @@ struct IcpBatch {
     uint2          *nn_queue2;  // bound kernel -> task walk: what the pixel window could not settle either, (point, bound)
     uint32_t        pre_transformed;   // 1: the pending update has already been applied to the cloud (nn_search_kernel): the pass must not apply it again
     pr_criteria     crit;
+    // robust weight of the pass (pr_robust, include/pose_refine.h), uniform: read by the kRobust instantiations only, which the launchers pick
+    // when robust_kind != PR_ROBUST_NONE.  (Behind every older member: their offsets in the kernel argument stay what they were.)
+    uint32_t        robust_kind;
+    float           robust_c, robust_inv_c;
 };
+// the weight as the per-point audit kernels take it
+struct RobustArgs { uint32_t kind; float c, inv_c; float *corr; };   // corr: null, or n x 8 floats {dx, dy, dz, valid, nx, ny, nz, w}
 
 // projective scene exactly as the reference API hands it over (two Vec3f arrays)
 struct SceneProjAoS {
@@ -324,6 +330,11 @@ hipError_t launch_contrib29_grid(pr_vec3 *cloud, uint32_t n, const float *update
 hipError_t launch_contrib29_proj_aos(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjAoS &sc, float *out, hipStream_t s);
 hipError_t launch_contrib29_proj_packed(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjPacked &sc, float *out, hipStream_t s);
 hipError_t launch_contrib29_nn(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneNNDev &sc, float *out, hipStream_t s);
+// audit entry of the robust pass (pr_debug_robust_terms): the weighted terms of every point, out[n][29], and (ra.corr) its correspondence and weight
+hipError_t launch_robust_terms_proj_aos(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjAoS &sc, const RobustArgs &ra, float *out, hipStream_t s);
+hipError_t launch_robust_terms_proj_packed(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneProjPacked &sc, const RobustArgs &ra, float *out, hipStream_t s);
+hipError_t launch_robust_terms_nn(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneNNDev &sc, const RobustArgs &ra, float *out, hipStream_t s);
+hipError_t launch_robust_terms_grid(pr_vec3 *cloud, uint32_t n, const float *update12, const SceneGridDev &sc, const RobustArgs &ra, float *out, hipStream_t s);
 // one iteration of pose_iteration_wave per hypothesis on given sums (pr_debug_pose_iteration): one wavefront each
 hipError_t launch_pose_iteration_debug(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, pr_result *state,
                                        float *update, uint32_t *finished, hipStream_t s);

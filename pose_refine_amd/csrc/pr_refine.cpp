@@ -201,7 +201,7 @@ int pyramid_levels_ok(const char *fn, const pr_pyramid_level *levels, uint32_t n
 // through them, icp_drive run on them as on any batch of clouds, and the accumulated transform advanced on the host (T_l * T_acc, pr_mat4_mul) -- both
 // solve modes leave a level's records on the host, and the next level's emit needs them staged either way.
 int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, uint32_t H, const float K[9], const uint32_t *box_off, const SceneSel &sc,
-                  pr_result *results_host)
+                  pr_result *results_host, const pr_robust *robust)      // robust: the job's table, one descriptor per level
 {
     const uint32_t L = py.n_levels;
     const size_t plane = (size_t)L * np * H;                      // words of row counts; the row offsets follow
@@ -252,7 +252,7 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
                                              g->cloud.as<pr_vec3>(), g->stream));
         }
         trace_mark("pyramid_chunk: level emitted, icp_drive next");
-        PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, py.levels[l].crit, rec.data(), nullptr));     // (returns with the stream drained: the pinned carry records are free again)
+        PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, py.levels[l].crit, rec.data(), nullptr, robust[l]));     // (returns with the stream drained: the pinned carry records are free again)
         for (uint32_t i = 0; i < np; ++i) {
             prh::mat4_mul(rec[i].T, acc[i].T, acc[i].T);
             acc[i].fitness = rec[i].fitness; acc[i].inlier_rmse = rec[i].inlier_rmse;
@@ -298,7 +298,7 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, &job.proj, job.roi, box_off, !src.plan && opt.raster_mode == 1));
         }
-        if (pyramid) { PR_TRY(pyramid_chunk(*pyramid, p0, np, W, H, K, box_off, sc, results_host + p0)); continue; }
+        if (pyramid) { PR_TRY(pyramid_chunk(*pyramid, p0, np, W, H, K, box_off, sc, results_host + p0, job.robust)); continue; }
         // the cloud sizes come back through a kernel's stores into the pinned array, not through a copy command (see drive_host's result block)
         HIP_TRY(prk::launch_copy_words32(g->counts.p, g->h_counts.dev, np, g->stream));
         HIP_TRY(hipStreamSynchronize(g->stream));
@@ -323,7 +323,7 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
         if (sizes_host) std::memcpy(sizes_host + p0, count.data(), sizeof(uint32_t) * np);
         trace_mark("refine_impl: clouds emitted, icp_drive next");
         PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, job.crit,
-                         results_host ? results_host + p0 : nullptr, job.results_dev ? job.results_dev + p0 : nullptr));
+                         results_host ? results_host + p0 : nullptr, job.results_dev ? job.results_dev + p0 : nullptr, job.robust[0]));
     }
     return PR_OK;
 }
@@ -1299,20 +1299,66 @@ int pr_refine_batch_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const ui
     return refine_ordered(job, nullptr, poses_host, n_poses, results_host, cloud_sizes_host);
 }
 
-int pr_refine_pyramid(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
-                      const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels,
-                      pr_roi roi, pr_result *results_host, pr_result *level_results_host, uint32_t *level_sizes_host)
+// the four pyramid entry points (fn: whose messages; multi: a mixed batch, the mesh table instead of tris_dev; robust: null, or the table of a _robust call)
+static int refine_pyramid_impl(const char *fn, bool multi, const pr_triangle *tris_dev, size_t n_tris, const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host,
+                               const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                               const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
+                               pr_result *level_results_host, uint32_t *level_sizes_host, const pr_robust *robust, uint32_t n_robust)
 {
-    PR_TRY(pyramid_levels_ok("pr_refine_pyramid", levels, n_levels, n_poses, results_host));      // before any device use
+    PR_TRY(pyramid_levels_ok(fn, levels, n_levels, n_poses, results_host));      // before any device use
     PR_ENTER();
     // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
     for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
     if (n_poses == 0) return PR_OK;
-    if (!poses_host) { set_error("pr_refine_pyramid: bad arguments"); return PR_ERR_INVALID; }
+    if (!poses_host) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
     RefineJob job;                                                // (every level brings its own criteria)
-    PR_TRY(make_job("pr_refine_pyramid", tris_dev, n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job));
+    PR_TRY(make_job(fn, tris_dev, n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job, robust, n_robust, n_levels));
+    MeshPlan pl;
+    if (multi) {
+        PR_TRY(plan_meshes(fn, meshes, n_meshes, mesh_index_host, n_poses, pl));
+        job.plan = &pl;
+    }
     const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
     return refine_ordered(job, &py, poses_host, n_poses, results_host, nullptr);
+}
+// what a _robust entry point refuses before it touches a device (so also on a machine without one), with nothing written
+static int robust_call_ok(const char *fn, const pr_pyramid_level *levels, uint32_t n_levels, uint32_t n_poses, const pr_result *results_host,
+                          const pr_robust *robust, uint32_t n_robust, bool pointers_ok)
+{
+    PR_TRY(pyramid_levels_ok(fn, levels, n_levels, n_poses, results_host));
+    PR_TRY(robust_table_ok(fn, robust, n_robust, n_levels));
+    if (n_poses && !pointers_ok) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+
+int pr_refine_pyramid_robust(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                             const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels,
+                             pr_roi roi, pr_result *results_host, pr_result *level_results_host, uint32_t *level_sizes_host,
+                             const pr_robust *robust, uint32_t n_robust)
+{
+    const char *fn = "pr_refine_pyramid_robust";
+    PR_TRY(robust_call_ok(fn, levels, n_levels, n_poses, results_host, robust, n_robust, poses_host && proj && K && scene && (tris_dev || n_tris == 0)));
+    return refine_pyramid_impl(fn, false, tris_dev, n_tris, nullptr, 0, nullptr, poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels, n_levels, roi,
+                               results_host, level_results_host, level_sizes_host, robust, n_robust);
+}
+
+int pr_refine_pyramid_robust_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                                   uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                                   const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
+                                   pr_result *level_results_host, uint32_t *level_sizes_host, const pr_robust *robust, uint32_t n_robust)
+{
+    const char *fn = "pr_refine_pyramid_robust_multi";
+    PR_TRY(robust_call_ok(fn, levels, n_levels, n_poses, results_host, robust, n_robust, poses_host && proj && K && scene && meshes && mesh_index_host));
+    return refine_pyramid_impl(fn, true, nullptr, 0, meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels,
+                               n_levels, roi, results_host, level_results_host, level_sizes_host, robust, n_robust);
+}
+
+int pr_refine_pyramid(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                      const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels,
+                      pr_roi roi, pr_result *results_host, pr_result *level_results_host, uint32_t *level_sizes_host)
+{
+    return refine_pyramid_impl("pr_refine_pyramid", false, tris_dev, n_tris, nullptr, 0, nullptr, poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels,
+                               n_levels, roi, results_host, level_results_host, level_sizes_host, nullptr, 0);
 }
 
 int pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1320,19 +1366,8 @@ int pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
                             const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
                             pr_result *level_results_host, uint32_t *level_sizes_host)
 {
-    PR_TRY(pyramid_levels_ok("pr_refine_pyramid_multi", levels, n_levels, n_poses, results_host));
-    PR_ENTER();
-    // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
-    for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
-    if (n_poses == 0) return PR_OK;
-    if (!poses_host) { set_error("pr_refine_pyramid_multi: bad arguments"); return PR_ERR_INVALID; }
-    RefineJob job;
-    PR_TRY(make_job("pr_refine_pyramid_multi", nullptr, 0, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job));
-    MeshPlan pl;
-    PR_TRY(plan_meshes("pr_refine_pyramid_multi", meshes, n_meshes, mesh_index_host, n_poses, pl));
-    job.plan = &pl;
-    const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
-    return refine_ordered(job, &py, poses_host, n_poses, results_host, nullptr);
+    return refine_pyramid_impl("pr_refine_pyramid_multi", true, nullptr, 0, meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene,
+                               levels, n_levels, roi, results_host, level_results_host, level_sizes_host, nullptr, 0);
 }
 
 int pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,

@@ -222,6 +222,25 @@ inline int grid_desc_ok(const char *fn, const pr_scene_grid *gs, bool built)
     }
     return PR_OK;
 }
+// A robust-weight descriptor as a caller hands it over (pr_robust, include/pose_refine.h): what pr_robust_describe would have produced.  No HIP call in here.
+inline int robust_desc_ok(const char *fn, const pr_robust *rb)
+{
+    if (!rb) { set_error("%s: null pr_robust", fn); return PR_ERR_INVALID; }
+    if (rb->kind > PR_ROBUST_CAUCHY) { set_error("%s: pr_robust: unknown kind %u", fn, rb->kind); return PR_ERR_INVALID; }
+    if (rb->reserved != 0) { set_error("%s: pr_robust: reserved must be 0", fn); return PR_ERR_INVALID; }
+    if (rb->kind == PR_ROBUST_NONE) return PR_OK;
+    if (!std::isfinite(rb->c) || !(rb->c > 0.0f)) { set_error("%s: pr_robust: c must be finite and positive (got %g)", fn, (double)rb->c); return PR_ERR_INVALID; }
+    if (!(rb->inv_c == 1.0f / rb->c) || !std::isfinite(rb->inv_c) || !(rb->inv_c > 0.0f)) { set_error("%s: pr_robust: inv_c is not the positive finite 1.0f / c (pr_robust_describe computes it)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+// a robust table of a call with n_levels levels: one descriptor for all of them, or one each
+inline int robust_table_ok(const char *fn, const pr_robust *robust, uint32_t n_robust, uint32_t n_levels)
+{
+    if (!robust) { set_error("%s: null pr_robust table", fn); return PR_ERR_INVALID; }
+    if (n_robust != 1 && n_robust != n_levels) { set_error("%s: n_robust must be 1 or n_levels = %u (got %u)", fn, n_levels, n_robust); return PR_ERR_INVALID; }
+    for (uint32_t l = 0; l < n_robust; ++l) PR_TRY(robust_desc_ok(fn, robust + l));
+    return PR_OK;
+}
 struct MeshPlan;                     // the hypotheses of a mixed batch grouped by mesh (pr_refine.cpp)
 struct RefineJob {
     const pr_triangle *tris = nullptr; size_t n_tris = 0;        // one mesh for every hypothesis ...
@@ -229,12 +248,16 @@ struct RefineJob {
     uint32_t W = 0, H = 0; pr_mat4 proj{}; float K[9] = { 0 };
     int scene_kind = 0; pr_scene_proj_crop sp{}; pr_scene_nn sn{}; pr_scene_grid sg{}; pr_criteria crit{}; pr_roi roi{ 0, 0, 0, 0 };
     pr_result *results_dev = nullptr;
+    pr_robust robust[PR_PYRAMID_MAX_LEVELS] = {};                // robust weight per pyramid level ([0]: a call without levels); all PR_ROBUST_NONE unless a _robust entry point set them (synchronous calls only)
     const void *scene() const { return scene_kind == PR_SCENE_NN ? static_cast<const void *>(&sn) : scene_kind == PR_SCENE_GRID ? static_cast<const void *>(&sg) : &sp; }   // as make_scene takes it (a crop starts with the plain view)
 };
 // ... from the C arguments, with every check that needs no device.  No HIP call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.
 inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, uint32_t W, uint32_t H, const pr_mat4 *proj, const float K[9], int scene_kind,
-                    const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_dev, RefineJob &job)
+                    const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_dev, RefineJob &job,
+                    const pr_robust *robust = nullptr, uint32_t n_robust = 0, uint32_t n_levels = 1)      // robust: null (plain), or a table for n_levels levels
 {
+    if (n_levels == 0 || n_levels > PR_PYRAMID_MAX_LEVELS) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
+    if (robust || n_robust) PR_TRY(robust_table_ok(fn, robust, n_robust, n_levels));
     if ((!tris_dev && n_tris > 0) || !proj || !K || !scene || W == 0 || H == 0) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }   // (an empty model has no array)
     if (scene_kind != PR_SCENE_NN && scene_kind != PR_SCENE_PROJ && scene_kind != PR_SCENE_PROJ_CROP && scene_kind != PR_SCENE_GRID) { set_error("unknown scene kind %d", scene_kind); return PR_ERR_INVALID; }
     if (scene_kind == PR_SCENE_GRID) PR_TRY(grid_desc_ok(fn, static_cast<const pr_scene_grid *>(scene), /*built=*/true));
@@ -247,6 +270,7 @@ inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, 
     else if (scene_kind == PR_SCENE_GRID) job.sg = *static_cast<const pr_scene_grid *>(scene);
     else if (scene_kind == PR_SCENE_PROJ_CROP) job.sp = *static_cast<const pr_scene_proj_crop *>(scene);
     else job.sp.view = *static_cast<const pr_scene_proj *>(scene);     // (a plain projective scene: a crop at 0, 0)
+    if (robust) for (uint32_t l = 0; l < n_levels; ++l) job.robust[l] = robust[n_robust == 1 ? 0 : l];
     return PR_OK;
 }
 // ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_cover, pr_score_contours, pr_score_normals, pr_compose_detections and their _multi forms) ----
@@ -861,7 +885,7 @@ int device_solve_loop(const Lanes &lanes, uint32_t n_groups, prk::IcpBatch b, ui
     return lanes_join(lanes, n_groups);
 }
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
-              pr_criteria crit, pr_result *results_host, pr_result *results_dev);
+              pr_criteria crit, pr_result *results_host, pr_result *results_dev, const pr_robust &robust = pr_robust{ PR_ROBUST_NONE, 0.0f, 0.0f, 0 });
 // ---- audit recorder of the host-solve loop's sums (pr_debug_trace_sums, pr_icp.cpp) ---------------------------------
 // Per host thread, hence for the context that thread is bound to: `armed` waits for the thread's next synchronous ICP call, whose
 // entry point opens a TraceScope -- the recorder becomes `active` for exactly that call and is gone when it returns, error or

@@ -72,6 +72,29 @@ int main()
     CHECK(job.scene() == &job.sg && job.sg.dim[0] == (1u << 13) && job.sg.cell_point == sg.cell_point && job.sg.n_points == 11);
     CHECK(grid_desc_ok("job_sanitize", &sg, false) == PR_OK && grid_desc_ok("job_sanitize", nullptr, false) == PR_ERR_INVALID);
     { pr_scene_grid b = sg; b.cell_point = nullptr; b.rec = nullptr; b.n_points = 0; CHECK(grid_desc_ok("job_sanitize", &b, false) == PR_OK); }      // (as pr_scene_grid_describe leaves it: good for the build)
+    // robust tables (pr_robust): one descriptor for every level or one per level, each as pr_robust_describe would have made it
+    {
+        const pr_robust huber{ PR_ROBUST_HUBER, 0.02f, 1.0f / 0.02f, 0 }, tukey{ PR_ROBUST_TUKEY, 0.005f, 1.0f / 0.005f, 0 }, plain{ PR_ROBUST_NONE, 0.0f, 0.0f, 0 };
+        const pr_robust two[2] = { huber, tukey };
+        CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job, two, 2, 2) == PR_OK);
+        CHECK(job.robust[0].kind == PR_ROBUST_HUBER && job.robust[1].kind == PR_ROBUST_TUKEY && job.robust[1].inv_c == two[1].inv_c && job.robust[2].kind == PR_ROBUST_NONE);
+        CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job, &tukey, 1, 3) == PR_OK);
+        CHECK(job.robust[0].kind == PR_ROBUST_TUKEY && job.robust[2].kind == PR_ROBUST_TUKEY && job.robust[3].kind == PR_ROBUST_NONE);
+        CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job, &plain, 1, 1) == PR_OK && job.robust[0].kind == PR_ROBUST_NONE);
+        CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job) == PR_OK && job.robust[0].kind == PR_ROBUST_NONE);
+        for (uint32_t n_robust : { 0u, 2u, 4u, 5u })              // neither 1 nor the 3 levels
+            CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job, two, n_robust, 3) == PR_ERR_INVALID);
+        CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job, nullptr, 1, 1) == PR_ERR_INVALID);
+        CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job, two, 2, 5) == PR_ERR_INVALID);      // more levels than a pyramid has
+        for (pr_robust bad : { pr_robust{ 4, 0.02f, 50.0f, 0 }, pr_robust{ PR_ROBUST_HUBER, 0.02f, 1.0f / 0.02f, 1 }, pr_robust{ PR_ROBUST_HUBER, 0.0f, 0.0f, 0 },
+                               pr_robust{ PR_ROBUST_TUKEY, -0.02f, -50.0f, 0 }, pr_robust{ PR_ROBUST_CAUCHY, NAN, 50.0f, 0 }, pr_robust{ PR_ROBUST_CAUCHY, INFINITY, 0.0f, 0 },
+                               pr_robust{ PR_ROBUST_HUBER, 0.02f, std::nextafter(1.0f / 0.02f, 0.0f), 0 } }) {     // (the last: an inv_c one ulp off 1.0f / c)
+            const pr_robust with_bad[2] = { huber, bad };
+            CHECK(robust_desc_ok("job_sanitize", &bad) == PR_ERR_INVALID);
+            CHECK(make_job("job_sanitize", tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, nullptr, job, with_bad, 2, 2) == PR_ERR_INVALID);
+        }
+        CHECK(robust_desc_ok("job_sanitize", nullptr) == PR_ERR_INVALID && robust_desc_ok("job_sanitize", &huber) == PR_OK);
+    }
     // scoring requests: one good one per kind, single mesh and mesh table; then one mistake at a time -- a null array, too many hypotheses, a ROI off the frame
     const pr_mat4 *poses = reinterpret_cast<const pr_mat4 *>(uintptr_t(0x4000));
     const pr_mesh_ref *table = reinterpret_cast<const pr_mesh_ref *>(uintptr_t(0x5000));

@@ -428,6 +428,73 @@ int  pr_refine_pyramid_robust_multi(const pr_mesh_ref *meshes, uint32_t n_meshes
                                     const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
                                     pr_result *level_results_host, uint32_t *level_sizes_host, const pr_robust *robust, uint32_t n_robust);
 
+/* ---- pose observability: the information matrix of a hypothesis and its eigenvectors (no counterpart in the reference) -------------------
+ * How well does the scene constrain a pose?  Per hypothesis: a cloud of n float32 points in the camera frame (metres; never modified), one scene
+ * of any of the four kinds, an optional pr_robust (NULL: plain, w = 1), a centre c (three float32, camera frame) and a radius rho > 0 (float32,
+ * metres).  Every point s that the plain pass would give a valid correspondence (d, n) -- same association, same acceptance -- contributes:
+ *   float32   e = d - s;  r = (ex*nx + ey*ny) + ez*nz;  w = the weight of r (pr_robust above) -- exactly the pass' values
+ *   float64   q = s - c;  a = (qy*nz - qz*ny, qz*nx - qx*nz, qx*ny - qy*nx) / rho;  J = (ax, ay, az, nx, ny, nz);  wJ[i] = w * J[i];  wr = w * r
+ *             H[i][j] += wJ[i] * J[j]  (i <= j);   g[i] += wJ[i] * r;   sum_w += w;   sum_wr2 += wr * r;   sum_r2 += r * r
+ * every operation rounded on its own (no contraction), '/' the correctly rounded division: tests/info_ref.py forms the same terms bit for bit.
+ * The rotational half is divided by rho so that all six coordinates are metres of surface motion at distance rho from c and the eigenvalues
+ * are comparable; rho = 1 gives plain radians.  Taking the moments about c (the object's centre) and not about the camera origin, and in
+ * float64, is what separates "weak" from "unobservable": a direction the data do not constrain at all reads below 1e-15 of the largest
+ * eigenvalue, against 1e-7 for float32 sums about the origin.
+ * Order of addition: lane, wavefront and workgroup sums in a fixed tree, the workgroups' partial sums through memory in block order; no
+ * floating-point atomics.  Two calls on the same inputs return the same bytes.
+ * pr_pose_info (272 B): n_points 0 (the cloud's size), n_valid 4 (correspondences), n_zero_weight 8 (valid ones with w == 0.0f), reserved 12,
+ *   c 16, rho 28, H 32 (21 doubles: i <= j, row-major -- the numbering of sums 0..20), g 200, sum_w 248, sum_wr2 256, sum_r2 264.
+ * pr_pose_eig (344 B): lambda 0 (ascending), V 48 (row-major 6 x 6: V[6 * i + k] = component i of the unit eigenvector of lambda[k]; its
+ *   component of largest magnitude is positive, the lowest index on a tie), sweeps 336, reserved 340.  The decomposition is of the symmetric
+ *   6 x 6 filled from H, by cyclic Jacobi in float64:
+ *     sweep      the 15 rotations (p, q), p < q, in row-major order
+ *     rotation   skipped when A[p][q] == 0 exactly; else theta = (A[q][q] - A[p][p]) / (2 A[p][q]), t = sign(theta) / (|theta| +
+ *                sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c
+ *     stopping   before every sweep: done when max |A[p][q]| (p < q) <= 2^-56 max |A[p][p]|; at most PR_INFO_MAX_SWEEPS sweeps; `sweeps`
+ *                is the number run (a diagonal matrix: 0)
+ *   then the pairs sorted by a fixed 12-comparator network.
+ * An empty cloud or n_valid == 0: every sum and count zero (n_points, c and rho as given), lambda zero, V the identity, sweeps 0. */
+#define PR_INFO_MAX_SWEEPS 16
+typedef struct {
+    uint32_t n_points, n_valid, n_zero_weight, reserved;
+    float c[3], rho;
+    double H[21], g[6], sum_w, sum_wr2, sum_r2;
+} pr_pose_info;                                                    /* 272 B */
+typedef struct { double lambda[6]; double V[36]; uint32_t sweeps, reserved; } pr_pose_eig;      /* 344 B */
+/* Cloud-level form, shaped like pr_icp_batch_robust: cloud i = clouds_dev[offsets_host[i] .. offsets_host[i + 1]), centre
+ * centers_host[3 i .. 3 i + 2], radius radii_host[i]; info_host[n_clouds], eig_host[n_clouds] (or NULL: no decomposition).  All four scene
+ * kinds.  kd-tree scenes with compact records are searched by the kernels an ICP pass uses (the pass reads their winners); a tree without them is
+ * walked point by point with the reference's own ordered walk: the same records, several times the time.
+ * PR_ERR_INVALID, before any device is touched and with nothing written: null offsets, centres, radii, info or scene (with n_clouds > 0), a
+ * null cloud array with points, decreasing offsets, an unknown scene kind, a bad grid descriptor, a centre that is not finite, a radius that
+ * is not finite or not positive, a descriptor pr_robust_describe would not have produced. */
+int  pr_icp_information(const pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind, const void *scene,
+                        const pr_robust *robust_or_null, const float *centers_host, const float *radii_host, pr_pose_info *info_host,
+                        pr_pose_eig *eig_host_or_null);
+/* Fused form: the render and cloud emission of pr_refine_batch_roi, then the information pass in place of the ICP loop -- the clouds are the
+ * ones pr_refine_batch_roi would start from (cloud_sizes_host, optional, receives their sizes), the projective scene is read through its
+ * packed record as there, and large batches run in the same chunks.  One centre and one radius for the mesh: center_model (three floats, model
+ * frame and units) and radius (metres, the clouds' unit).  c_i = poses_host[i] applied to center_model in float64 on the host (rows 0..2:
+ * ((m0*x + m1*y) + m2*z) + m3), divided by 1000.0 in float64 -- the cloud extraction's millimetres to metres -- and rounded to float32.
+ * PR_ERR_INVALID as above, and for pr_refine_batch_roi's own argument errors and a null center_model. */
+int  pr_pose_information(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                         const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_roi roi, const pr_robust *robust_or_null,
+                         const float *center_model, float radius, pr_pose_info *info_host, pr_pose_eig *eig_host_or_null,
+                         uint32_t *cloud_sizes_host_or_null);
+/* The same over a mesh table (pr_refine_batch_multi's): centers_model[3 m .. 3 m + 2] and radii[m] belong to mesh m.  Every record equals the
+ * single-mesh call's. */
+int  pr_pose_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                               uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
+                               const void *scene, pr_roi roi, const pr_robust *robust_or_null, const float *centers_model, const float *radii,
+                               pr_pose_info *info_host, pr_pose_eig *eig_host_or_null, uint32_t *cloud_sizes_host_or_null);
+/* Covariance of the pose from one record pair.  Host only, needs no device.  rank = the number of k with lambda[k] > 0 and lambda[k] >
+ * min_ratio * lambda[5];  cov = sigma2 * sum over those k of v_k v_k^T / lambda[k], in the scaled coordinates of J (cov21_out: i <= j,
+ * row-major, H's numbering);  sigma2 = sigma * sigma when sigma > 0, otherwise (sum_wr2 / sum_w) * n_valid / (n_valid - 6).  cov21_out,
+ * rank_out and sigma2_out may each be NULL.  PR_ERR_INVALID, nothing written: null info or eig, min_ratio negative or not finite, sigma not
+ * finite, and sigma <= 0 with n_valid <= 6 or sum_w == 0. */
+int  pr_info_covariance(const pr_pose_info *info, const pr_pose_eig *eig, double sigma, double min_ratio, double *cov21_out, uint32_t *rank_out,
+                        double *sigma2_out);
+
 /* ---- detections from a scored batch: which hypotheses explain the same scene pixels ------------------------------------------------------
  * The support of hypothesis i is the set of frame pixels pr_score_poses counts as `inlier` for it (rendered, s > 0, |r - s| <= tau_mm).
  * pr_score_overlap scores a batch exactly as pr_score_poses does -- scores_host is byte for byte the same -- and also returns
@@ -845,6 +912,11 @@ int  pr_debug_contrib29(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, c
  * descriptor are PR_ERR_INVALID before any device is touched, with nothing written. */
 int  pr_debug_robust_terms(pr_vec3 *cloud_dev, uint32_t n_points, int scene_kind, const void *scene, const float *update16, int want_packed,
                            const pr_robust *robust, float *contrib_host, float *corr_host);
+/* Audit entry: pr_icp_information with the projective scene read through its packed 16-byte record when want_packed != 0 (the form the fused
+ * calls use), as pr_debug_contrib29 selects it.  want_packed == 0 is pr_icp_information itself. */
+int  pr_debug_icp_information(const pr_vec3 *clouds_dev, const uint32_t *offsets_host, uint32_t n_clouds, int scene_kind, const void *scene,
+                              int want_packed, const pr_robust *robust_or_null, const float *centers_host, const float *radii_host,
+                              pr_pose_info *info_host, pr_pose_eig *eig_host_or_null);
 /* Audit entry: ONE iteration of icp.cu:178-212 for n hypotheses whose 29 sums are given (n x 29 floats in the pass's order: the 21
  * upper-triangle entries of A row by row, b[6], r^2, count).  on_device != 0: the wavefront iteration the fused pass tail and
  * icp_finalize_solve_kernel run (one wavefront per hypothesis); 0: the host-solve loop's iteration (needs no device).  state: in/out

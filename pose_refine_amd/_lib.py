@@ -52,6 +52,12 @@ POSE_DIST_MAX_SYMS, POSE_DIST_MAX_POSES, POSE_DIST_MAX_POINTS = 64, 4096, 1 << 2
 # pr_vsd_counts: the visible surfaces of an estimate and a truth against the scene frame, counted (pr_pose_vsd)
 VSD_MAX_TAUS = 12                        # PR_VSD_MAX_TAUS
 VSD = np.dtype([("visib_gt", "<u4"), ("visib_est", "<u4"), ("inter", "<u4"), ("uni", "<u4"), ("far", "<u4", (VSD_MAX_TAUS,))])
+# pr_pose_info / pr_pose_eig: the float64 information matrix of a hypothesis about a centre, and its Jacobi eigen-decomposition (pr_icp_information)
+POSE_INFO = np.dtype([("n_points", "<u4"), ("n_valid", "<u4"), ("n_zero_weight", "<u4"), ("reserved", "<u4"), ("c", "<f4", (3,)), ("rho", "<f4"),
+                      ("H", "<f8", (21,)), ("g", "<f8", (6,)), ("sum_w", "<f8"), ("sum_wr2", "<f8"), ("sum_r2", "<f8")])
+POSE_EIG = np.dtype([("lambda", "<f8", (6,)), ("V", "<f8", (6, 6)), ("sweeps", "<u4"), ("reserved", "<u4")])
+INFO_MAX_SWEEPS = 16                     # PR_INFO_MAX_SWEEPS
+assert POSE_INFO.itemsize == 272 and POSE_EIG.itemsize == 344
 POSE_DIST_CHUNK = 256                    # PR_POSE_DIST_CHUNK (pr_tuning.h; the library reports its own as option "pose_dist_chunk")
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
 assert COVER.itemsize == 16 and COVER_FRAME.itemsize == 16
@@ -179,6 +185,11 @@ SIGNATURES = {
     "pr_refine_pyramid_robust": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, _vp, _u32, Roi, _vp, _vp, _vp, _vp, _u32]),
     "pr_refine_pyramid_robust_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, _vp, _u32, Roi, _vp, _vp, _vp, _vp, _u32]),
     "pr_debug_robust_terms": (_i32, [_vp, _u32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "pr_icp_information": (_i32, [_vp, _vp, _u32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_debug_icp_information": (_i32, [_vp, _vp, _u32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pr_pose_information": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Roi, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "pr_pose_information_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Roi, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_info_covariance": (_i32, [_vp, _vp, C.c_double, C.c_double, _vp, C.POINTER(_u32), C.POINTER(C.c_double)]),
     "pr_refine_batch": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp]),
     "pr_refine_batch_dev": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp]),
     "pr_refine_submit": (_i32, [_i32, _vp, _sz, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, Criteria, _vp, _vp, _vp]),

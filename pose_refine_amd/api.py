@@ -1454,6 +1454,140 @@ def filter_by_normals(order, normals, min_fraction: float) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------
+# pose observability: the information matrix of a hypothesis and its eigenvectors
+# ------------------------------------------------------------------------------------------------
+def _robust_ptr(robust: Optional["Robust"]):
+    if robust is not None and not isinstance(robust, Robust):
+        raise ValueError("robust: a Robust or None")
+    return C.addressof(robust.desc()) if robust is not None else None
+
+
+def icp_information(clouds: DeviceVector, offsets, scene, centers, radii, robust: Optional[Robust] = None, want_eig: bool = True, packed: bool = False):
+    """``pr_icp_information``: for each cloud (``offsets``: P + 1 point offsets into ``clouds``) the float64 sums of the weighted point-to-plane
+    normal system about ``centers[i]`` with the rotational half scaled by ``radii[i]`` (metres, camera frame), and their eigen-decomposition.
+    Returns (info[P] of POSE_INFO dtype, eig[P] of POSE_EIG dtype or None).  The clouds are not modified.  ``packed``: the audit form, which
+    reads a projective scene through its packed record (``pr_debug_icp_information``)."""
+    offsets = np.ascontiguousarray(offsets, np.uint32)
+    if len(offsets) == 0:
+        raise ValueError("offsets: P + 1 point offsets (at least one)")
+    if int(offsets[-1]) * 3 > clouds.size():
+        raise ValueError(f"offsets end at point {int(offsets[-1])}, the cloud buffer holds {clouds.size() // 3}")
+    n = len(offsets) - 1
+    c, r = _f32(centers, (-1, 3)), _f32(radii, -1)
+    if len(c) != n or len(r) != n:
+        raise ValueError(f"centers and radii: one per cloud ({n}), got {len(c)} and {len(r)}")
+    info = np.zeros(n, _lib.POSE_INFO)
+    eig = np.zeros(n, _lib.POSE_EIG) if want_eig else None
+    d = scene.desc()
+    tail = (_robust_ptr(robust), ptr(c), ptr(r), ptr(info), ptr(eig) if want_eig else None)
+    if packed:
+        check(_lib.load().pr_debug_icp_information(clouds.data() or None, ptr(offsets), n, scene.kind, C.addressof(d), 1, *tail))
+    else:
+        check(_lib.load().pr_icp_information(clouds.data() or None, ptr(offsets), n, scene.kind, C.addressof(d), *tail))
+    return info, eig
+
+
+def _model_center_radius(tris, center, radius):
+    """``center`` (model frame and units) and ``radius`` (metres) of one mesh: given, or -- a ``Model`` -- the midpoint of its bounding box and
+    half the box diagonal (millimetres, hence / 1000)."""
+    if center is None or radius is None:
+        if not isinstance(tris, Model):
+            raise ValueError("center and radius default only for a Model (its bounding box); give both for a triangle array")
+        lo, hi = np.asarray(tris.bbox_min, np.float64), np.asarray(tris.bbox_max, np.float64)
+        if center is None:
+            center = 0.5 * (lo + hi)
+        if radius is None:
+            radius = 0.5 * float(np.linalg.norm(hi - lo)) / 1000.0
+    return _f32(center, 3), float(radius)
+
+
+def pose_information(tris, poses, width: int, height: int, proj, K, scene, center=None, radius=None, roi: Optional[Sequence[int]] = None,
+                     robust: Optional[Robust] = None, want_eig: bool = True):
+    """``pr_pose_information``: ``refine_batch``'s render and clouds, then the information pass: how well the scene constrains each hypothesis.
+    ``center`` (model frame, model units) is moved by each pose; ``radius`` is in metres.  For a ``Model`` they default to the midpoint of
+    ``bbox_min`` / ``bbox_max`` and half the box diagonal.  Returns (info[P], eig[P] or None, cloud sizes[P])."""
+    cm, rad = _model_center_radius(tris, center, radius)
+    td = _tris_dev(tris)
+    poses = _f32(poses, (-1, 16))
+    pj, k = _f32(proj, -1), _f32(K, -1)
+    n = len(poses)
+    info, sizes = np.zeros(n, _lib.POSE_INFO), np.zeros(n, np.uint32)
+    eig = np.zeros(n, _lib.POSE_EIG) if want_eig else None
+    d = scene.desc()
+    check(_lib.load().pr_pose_information(td.data() or None, td.size() // 9, ptr(poses), n, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
+                                          Roi(*(roi if roi is not None else (0, 0, 0, 0))), _robust_ptr(robust), ptr(cm), rad, ptr(info),
+                                          ptr(eig) if want_eig else None, ptr(sizes)))
+    return info, eig, sizes
+
+
+def pose_information_multi(meshes, mesh_index, poses, width: int, height: int, proj, K, scene, centers=None, radii=None,
+                           roi: Optional[Sequence[int]] = None, robust: Optional[Robust] = None, want_eig: bool = True):
+    """``pr_pose_information_multi``: ``pose_information`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; ``centers`` / ``radii``: one per
+    mesh (None: each ``Model``'s defaults).  Every record equals the single-mesh call's."""
+    meshes = list(meshes)
+    cr = [_model_center_radius(m, None if centers is None else centers[i], None if radii is None else radii[i]) for i, m in enumerate(meshes)]
+    cm = _f32([c for c, _ in cr], (-1, 3)) if cr else np.zeros((1, 3), np.float32)
+    rad = _f32([r for _, r in cr], -1) if cr else np.ones(1, np.float32)
+    table, devs, idx, poses = _multi_inputs(meshes, mesh_index, poses)
+    pj, k = _f32(proj, -1), _f32(K, -1)
+    n = len(poses)
+    info, sizes = np.zeros(n, _lib.POSE_INFO), np.zeros(n, np.uint32)
+    eig = np.zeros(n, _lib.POSE_EIG) if want_eig else None
+    d = scene.desc()
+    check(_lib.load().pr_pose_information_multi(table, len(devs), ptr(idx), ptr(poses), n, width, height, ptr(pj), ptr(k), scene.kind, C.addressof(d),
+                                                Roi(*(roi if roi is not None else (0, 0, 0, 0))), _robust_ptr(robust), ptr(cm), ptr(rad), ptr(info),
+                                                ptr(eig) if want_eig else None, ptr(sizes)))
+    return info, eig, sizes
+
+
+def _sym6(v21) -> np.ndarray:
+    m = np.zeros((6, 6))
+    m[np.triu_indices(6)] = np.asarray(v21, np.float64)
+    return m + np.triu(m, 1).T
+
+
+def information_matrix(info) -> np.ndarray:
+    """The symmetric 6 x 6 of one POSE_INFO record (``H`` holds its upper triangle, row-major)."""
+    return _sym6(info["H"])
+
+
+def pose_covariance(info, eig, min_ratio: float, sigma: Optional[float] = None, physical: bool = True):
+    """``pr_info_covariance`` for one record pair: (cov 6 x 6, rank, sigma2).  Eigenpairs with ``lambda <= min_ratio * lambda[5]`` (or
+    ``lambda <= 0``) are left out: the covariance is that of the observable directions alone.  ``sigma`` (metres): the sensor's standard
+    deviation; None: the residual variance ``(sum_wr2 / sum_w) * n_valid / (n_valid - 6)``.  ``physical``: rotational rows and columns divided
+    by ``rho`` -- radians and metres -- instead of the scaled coordinates of the record."""
+    i, e = np.ascontiguousarray(info, _lib.POSE_INFO).reshape(1), np.ascontiguousarray(eig, _lib.POSE_EIG).reshape(1)
+    cov = np.zeros(21, np.float64)
+    rank, s2 = C.c_uint32(), C.c_double()
+    check(_lib.load().pr_info_covariance(ptr(i), ptr(e), float(sigma) if sigma is not None else 0.0, float(min_ratio), ptr(cov), C.byref(rank), C.byref(s2)))
+    m = _sym6(cov)
+    if physical:
+        sc = np.array([1.0 / float(i["rho"][0])] * 3 + [1.0] * 3)
+        m = m * sc[:, None] * sc[None, :]
+    return m, int(rank.value), float(s2.value)
+
+
+def observable_rank(eig, min_ratio: float) -> np.ndarray:
+    """Per POSE_EIG record the number of k with ``lambda[k] > 0`` and ``lambda[k] > min_ratio * lambda[5]`` (``pr_info_covariance``'s rank)."""
+    lam = np.asarray(eig)["lambda"].reshape(-1, 6)
+    return ((lam > 0.0) & (lam > float(min_ratio) * lam[:, 5:6])).sum(1)
+
+
+def weakest_twist(info, eig, k: int = 0):
+    """Eigenvector ``k`` (0: the least constrained motion) of one record pair as a twist about the record's centre: (omega in radians, t in
+    metres), i.e. the rotational half divided by ``rho``."""
+    v = np.asarray(eig["V"], np.float64).reshape(6, 6)[:, int(k)]
+    return v[:3] / float(np.asarray(info["rho"]).reshape(-1)[0]), v[3:].copy()
+
+
+def filter_by_observability(order, eig, min_ratio: float, min_rank: int = 6) -> np.ndarray:
+    """``order`` (indices, best first) without the hypotheses whose ``observable_rank(eig, min_ratio)`` is below ``min_rank``; what remains keeps
+    its order.  The ranking itself is untouched."""
+    order = np.asarray(order, np.int64)
+    return order[observable_rank(eig, min_ratio)[order] >= int(min_rank)]
+
+
+# ------------------------------------------------------------------------------------------------
 # composition: the detections of a frame taken together
 # ------------------------------------------------------------------------------------------------
 def _compose_detections(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, roi, want_labels: bool, want_depth: bool):

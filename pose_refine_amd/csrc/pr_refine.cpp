@@ -266,7 +266,10 @@ int pyramid_chunk(const PyramidPlan &py, uint32_t p0, uint32_t np, uint32_t W, u
 
 // One synchronous batch: chunk by chunk the hypotheses rendered into their pixel boxes, the clouds emitted (with `pyramid`: every level's, by
 // pyramid_chunk) and icp_drive run on them.  The records go to results_host and to job.results_dev, the cloud sizes to sizes_host; each may be null.
-int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_result *results_host, uint32_t *sizes_host, const PyramidPlan *pyramid = nullptr)
+// (info: pr_pose_information -- the information pass on the chunk's clouds in place of icp_drive; centres, radii and records in the batch's order)
+struct InfoPlan { pr_robust robust; const float *centers, *radii; pr_pose_info *info; pr_pose_eig *eig; };
+int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_result *results_host, uint32_t *sizes_host, const PyramidPlan *pyramid = nullptr,
+                const InfoPlan *info = nullptr)
 {
     if (P == 0) return PR_OK;
     const MeshSource src{ job.tris, job.n_tris, job.plan };
@@ -322,6 +325,11 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
         }
         if (sizes_host) std::memcpy(sizes_host + p0, count.data(), sizeof(uint32_t) * np);
         trace_mark("refine_impl: clouds emitted, icp_drive next");
+        if (info) {
+            PR_TRY(info_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, info->robust, info->centers + 3 * (size_t)p0, info->radii + p0,
+                              info->info + p0, info->eig ? info->eig + p0 : nullptr));
+            continue;
+        }
         PR_TRY(icp_drive(g->cloud.as<pr_vec3>(), start.data(), count.data(), np, sc, job.crit,
                          results_host ? results_host + p0 : nullptr, job.results_dev ? job.results_dev + p0 : nullptr, job.robust[0]));
     }
@@ -1561,6 +1569,73 @@ int pr_pose_vsd_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32
                     vsd_params(K, delta_mm, taus_mm, n_taus), rec.data()));
     for (uint32_t j = 0; j < n_est; ++j) out_host[pl.order[2 * (size_t)j] / 2] = rec[j];
     return PR_OK;
+}
+
+// pr_pose_information and its _multi form (multi: the mesh table instead of tris_dev, a centre and a radius per mesh): every check before any device
+// is touched, the centres in the camera frame on the host, refine_core with the information pass on the batch in its plan's order into temporaries,
+// and the records back to the caller's order.
+static int pose_information_impl(const char *fn, bool multi, const pr_triangle *tris_dev, size_t n_tris, const pr_mesh_ref *meshes, uint32_t n_meshes,
+                                 const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj,
+                                 const float K[9], int scene_kind, const void *scene, pr_roi roi, const pr_robust *robust, const float *centers_model,
+                                 const float *radii, pr_pose_info *info_host, pr_pose_eig *eig_host, uint32_t *cloud_sizes_host)
+{
+    if (robust) PR_TRY(robust_desc_ok(fn, robust));
+    RefineJob job;
+    PR_TRY(make_job(fn, tris_dev, n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job));
+    if (!centers_model || !radii || (n_poses && (!poses_host || !info_host))) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    MeshPlan pl;
+    if (multi) {
+        PR_TRY(plan_meshes(fn, meshes, n_meshes, mesh_index_host, n_poses, pl));
+        job.plan = &pl;
+    }
+    PR_TRY(info_center_radius_ok(fn, centers_model, radii, multi ? n_meshes : 1u));
+    // c_i = pose_i applied to the mesh's centre, in float64, millimetres to metres as the cloud extraction converts them, rounded to float32
+    std::vector<float> centers(3 * (size_t)n_poses), rad(n_poses);
+    for (uint32_t j = 0; j < n_poses; ++j) {
+        const uint32_t o = multi ? pl.order[j] : j, m = multi ? mesh_index_host[o] : 0u;
+        const float *M = poses_host[o].m, *cm = centers_model + 3 * (size_t)m;
+        for (int a = 0; a < 3; ++a) {
+            const double v = (((double)M[4 * a] * (double)cm[0] + (double)M[4 * a + 1] * (double)cm[1]) + (double)M[4 * a + 2] * (double)cm[2]) + (double)M[4 * a + 3];
+            centers[3 * (size_t)j + a] = (float)(v / 1000.0);
+        }
+        rad[j] = radii[m];
+    }
+    PR_TRY(info_center_radius_ok(fn, centers.data(), rad.data(), n_poses));      // (a pose with a non-finite entry)
+    if (n_poses == 0) return PR_OK;
+    PR_ENTER();
+    // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
+    for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+    std::vector<pr_mat4> grouped;
+    if (multi) { grouped = grouped_poses(pl, poses_host); poses_host = grouped.data(); }
+    std::vector<pr_pose_info> info(n_poses);
+    std::vector<pr_pose_eig> eig(eig_host ? n_poses : 0);
+    std::vector<uint32_t> sizes(n_poses);
+    const InfoPlan ip{ robust ? *robust : pr_robust{ PR_ROBUST_NONE, 0.0f, 0.0f, 0 }, centers.data(), rad.data(), info.data(), eig_host ? eig.data() : nullptr };
+    PR_TRY(refine_core(job, poses_host, n_poses, nullptr, sizes.data(), nullptr, &ip));
+    for (uint32_t j = 0; j < n_poses; ++j) {
+        const uint32_t o = multi ? pl.order[j] : j;
+        info_host[o] = info[j];
+        if (eig_host) eig_host[o] = eig[j];
+        if (cloud_sizes_host) cloud_sizes_host[o] = sizes[j];
+    }
+    return PR_OK;
+}
+
+int pr_pose_information(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                        const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_roi roi, const pr_robust *robust_or_null,
+                        const float *center_model, float radius, pr_pose_info *info_host, pr_pose_eig *eig_host_or_null, uint32_t *cloud_sizes_host_or_null)
+{
+    return pose_information_impl("pr_pose_information", false, tris_dev, n_tris, nullptr, 0, nullptr, poses_host, n_poses, width, height, proj, K, scene_kind, scene,
+                                 roi, robust_or_null, center_model, &radius, info_host, eig_host_or_null, cloud_sizes_host_or_null);
+}
+
+int pr_pose_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
+                              uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_roi roi,
+                              const pr_robust *robust_or_null, const float *centers_model, const float *radii, pr_pose_info *info_host,
+                              pr_pose_eig *eig_host_or_null, uint32_t *cloud_sizes_host_or_null)
+{
+    return pose_information_impl("pr_pose_information_multi", true, nullptr, 0, meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K,
+                                 scene_kind, scene, roi, robust_or_null, centers_model, radii, info_host, eig_host_or_null, cloud_sizes_host_or_null);
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

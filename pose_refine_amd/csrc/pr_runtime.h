@@ -634,6 +634,8 @@ struct Ctx {
     PinBuf h_pd_mats, h_pd_rec;      // the matrices on their way in, the records on their way out
     DevBuf vsd_rec;                  // pr_pose_vsd: the records of a chunk's pairs
     PinBuf h_vsd;                    // ... on their way to the caller
+    DevBuf info_meta, info_part;     // pr_icp_information / pr_pose_information: the hypotheses' records (cloud, centre, radius) and the workgroups' partial sums
+    PinBuf h_info_meta, h_info_out;  // the records on their way in; pr_pose_info and pr_pose_eig on their way to the caller (stored by the eigen kernel)
     DevBuf lvl_rows, lvl_counts, lvl_carry;   // pr_refine_pyramid: per-row sample counts and offsets of every level of a chunk, the level clouds' sizes, the per-level carry records
     PinBuf h_lvl_carry;
     DevBuf multi;                    // mixed batches (pr_*_multi): mesh table, box index / image of each hypothesis, raster groups
@@ -886,6 +888,57 @@ int device_solve_loop(const Lanes &lanes, uint32_t n_groups, prk::IcpBatch b, ui
 }
 int icp_drive(pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc_in,
               pr_criteria crit, pr_result *results_host, pr_result *results_dev, const pr_robust &robust = pr_robust{ PR_ROBUST_NONE, 0.0f, 0.0f, 0 });
+// The information pass and the eigen kernel (pose_info.hip) on P clouds laid out as icp_drive takes them; centers: 3 floats per cloud, radii: one;
+// info_host[P], eig_host[P] or null (pr_pose_info.cpp).  Returns with the stream drained.  The clouds are only read.
+int info_drive(const pr_vec3 *cloud_base, const uint32_t *start_h, const uint32_t *count_h, uint32_t P, const SceneSel &sc, const pr_robust &robust,
+               const float *centers, const float *radii, pr_pose_info *info_host, pr_pose_eig *eig_host);
+// the information calls' own argument checks, before any device is touched, and the covariance of one record pair.  No HIP call in here:
+// tools/job_sanitize.cpp runs them under ASan / UBSan.
+inline int info_scene_ok(const char *fn, int scene_kind, const void *scene)
+{
+    if (scene_kind != PR_SCENE_NN && scene_kind != PR_SCENE_PROJ && scene_kind != PR_SCENE_PROJ_CROP && scene_kind != PR_SCENE_GRID) { set_error("%s: unknown scene kind %d", fn, scene_kind); return PR_ERR_INVALID; }
+    if (!scene) { set_error("%s: bad arguments (scene is null)", fn); return PR_ERR_INVALID; }
+    if (scene_kind == PR_SCENE_GRID) PR_TRY(grid_desc_ok(fn, static_cast<const pr_scene_grid *>(scene), /*built=*/true));
+    return PR_OK;
+}
+inline int info_center_radius_ok(const char *fn, const float *centers, const float *radii, uint32_t n)
+{
+    if (n && (!centers || !radii)) { set_error("%s: bad arguments (centres or radii null)", fn); return PR_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) if (!std::isfinite(centers[3 * (size_t)i + a])) { set_error("%s: centre %u is not finite", fn, i); return PR_ERR_INVALID; }
+        if (!std::isfinite(radii[i]) || !(radii[i] > 0.0f)) { set_error("%s: radius %u must be finite and positive (got %g)", fn, i, (double)radii[i]); return PR_ERR_INVALID; }
+    }
+    return PR_OK;
+}
+// pr_info_covariance, host only.  The eigenpairs counted: lambda[k] > 0 and lambda[k] > min_ratio * lambda[5]; cov = sigma2 * sum v_k v_k^T / lambda[k], k ascending.
+inline int info_covariance(const pr_pose_info *info, const pr_pose_eig *eig, double sigma, double min_ratio, double *cov21_out, uint32_t *rank_out,
+                           double *sigma2_out)
+{
+    const char *fn = "pr_info_covariance";
+    if (!info || !eig) { set_error("%s: bad arguments (info or eig is null)", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(min_ratio) || min_ratio < 0.0) { set_error("%s: min_ratio must be finite and >= 0", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(sigma)) { set_error("%s: sigma must be finite", fn); return PR_ERR_INVALID; }
+    double sigma2;
+    if (sigma > 0.0) sigma2 = sigma * sigma;
+    else {
+        if (info->n_valid <= 6 || info->sum_w == 0.0) { set_error("%s: no residual variance with n_valid = %u, sum_w = %g (give sigma > 0)", fn, info->n_valid, info->sum_w); return PR_ERR_INVALID; }
+        sigma2 = (info->sum_wr2 / info->sum_w) * (double)info->n_valid / (double)(info->n_valid - 6u);
+    }
+    uint32_t rank = 0;
+    double cov[21] = { 0.0 };
+    for (int k = 0; k < 6; ++k) {
+        const double l = eig->lambda[k];
+        if (!(l > 0.0) || !(l > min_ratio * eig->lambda[5])) continue;
+        ++rank;
+        int idx = 0;
+        for (int i = 0; i < 6; ++i)
+            for (int j = i; j < 6; ++j) cov[idx++] += eig->V[6 * i + k] * eig->V[6 * j + k] / l;
+    }
+    if (cov21_out) for (int i = 0; i < 21; ++i) cov21_out[i] = sigma2 * cov[i];
+    if (rank_out) *rank_out = rank;
+    if (sigma2_out) *sigma2_out = sigma2;
+    return PR_OK;
+}
 // ---- audit recorder of the host-solve loop's sums (pr_debug_trace_sums, pr_icp.cpp) ---------------------------------
 // Per host thread, hence for the context that thread is bound to: `armed` waits for the thread's next synchronous ICP call, whose
 // entry point opens a TraceScope -- the recorder becomes `active` for exactly that call and is gone when it returns, error or

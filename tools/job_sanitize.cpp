@@ -1,6 +1,6 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
 // Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok and vsd_args_ok with null and
-// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) and the byte rule of a timed pass (icp_span_bytes).  None of them calls HIP, so nothing of the runtime is linked.
+// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), and pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance).  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
 namespace prh { void set_error(const char *, ...) {} }
@@ -324,6 +324,35 @@ int main()
     // the bytes a timed pass is accounted: 36 per point on an edge pass, 48 otherwise
     CHECK(icp_span_bytes(0, true) == 0 && icp_span_bytes(1, true) == 36 && icp_span_bytes(1, false) == 48 && icp_span_bytes(27400, true) == 986400 && icp_span_bytes(27400, false) == 1315200);
     CHECK(icp_span_bytes(uint64_t(1) << 40, false) == (uint64_t(48) << 40));
+    // pose observability: the information calls' argument checks and pr_info_covariance's body (info_covariance), with nothing written on a refusal
+    {
+        const float nan = std::nanf(""), inf = INFINITY;
+        float c2[6] = { 0, 0, 0.8f, 0.1f, 0, 0.8f }, r2[2] = { 0.05f, 0.1f };
+        CHECK(info_center_radius_ok("job_sanitize", c2, r2, 2) == PR_OK && info_center_radius_ok("job_sanitize", nullptr, nullptr, 0) == PR_OK);
+        CHECK(info_center_radius_ok("job_sanitize", nullptr, r2, 2) == PR_ERR_INVALID && info_center_radius_ok("job_sanitize", c2, nullptr, 2) == PR_ERR_INVALID);
+        for (float bad : { nan, inf, -inf }) { float c[6]; std::memcpy(c, c2, sizeof c); c[5] = bad; CHECK(info_center_radius_ok("job_sanitize", c, r2, 2) == PR_ERR_INVALID); }
+        for (float bad : { 0.0f, -0.05f, nan, inf }) { float r[2] = { 0.05f, bad }; CHECK(info_center_radius_ok("job_sanitize", c2, r, 2) == PR_ERR_INVALID); }
+        CHECK(info_scene_ok("job_sanitize", PR_SCENE_PROJ, &sp) == PR_OK && info_scene_ok("job_sanitize", PR_SCENE_GRID, &sg) == PR_OK);
+        CHECK(info_scene_ok("job_sanitize", PR_SCENE_PROJ, nullptr) == PR_ERR_INVALID && info_scene_ok("job_sanitize", 9, &sp) == PR_ERR_INVALID);
+        { pr_scene_grid b = sg; b.rec = nullptr; CHECK(info_scene_ok("job_sanitize", PR_SCENE_GRID, &b) == PR_ERR_INVALID); }
+        pr_pose_info pi{}; pr_pose_eig pe{};
+        pi.n_points = pi.n_valid = 100; pi.rho = 0.1f; pi.sum_w = 100.0; pi.sum_wr2 = 1.0e-4;
+        const double lam[6] = { 0.0, -1.0e-20, 1.0e-9, 1.0e-3, 0.5, 1.0 };
+        for (int k = 0; k < 6; ++k) { pe.lambda[k] = lam[k]; pe.V[6 * k + k] = 1.0; }
+        double cov[21]; uint32_t rank = 9; double s2 = 9.0;
+        for (int i = 0; i < 21; ++i) cov[i] = 7.0;
+        auto untouched = [&] { bool same = rank == 9 && s2 == 9.0; for (double v : cov) same = same && v == 7.0; return same; };
+        CHECK(info_covariance(nullptr, &pe, 1.0, 0.0, cov, &rank, &s2) == PR_ERR_INVALID && info_covariance(&pi, nullptr, 1.0, 0.0, cov, &rank, &s2) == PR_ERR_INVALID);
+        for (double bad : { -1.0e-9, (double)nan, (double)inf }) CHECK(info_covariance(&pi, &pe, 1.0, bad, cov, &rank, &s2) == PR_ERR_INVALID);
+        CHECK(info_covariance(&pi, &pe, (double)nan, 0.0, cov, &rank, &s2) == PR_ERR_INVALID);
+        { pr_pose_info few = pi; few.n_valid = 6; CHECK(info_covariance(&few, &pe, 0.0, 0.0, cov, &rank, &s2) == PR_ERR_INVALID && info_covariance(&few, &pe, -1.0, 0.0, cov, &rank, &s2) == PR_ERR_INVALID); }
+        { pr_pose_info empty = pi; empty.sum_w = 0.0; CHECK(info_covariance(&empty, &pe, 0.0, 0.0, cov, &rank, &s2) == PR_ERR_INVALID); }
+        CHECK(untouched());
+        CHECK(info_covariance(&pi, &pe, 0.0, 0.0, nullptr, nullptr, nullptr) == PR_OK);
+        CHECK(info_covariance(&pi, &pe, 2.0, 1.0e-6, cov, &rank, &s2) == PR_OK && rank == 3 && s2 == 4.0);
+        CHECK(cov[0] == 0.0 && cov[6] == 0.0 && cov[11] == 0.0 && cov[15] == 4.0 * (1.0 / 1.0e-3) && cov[18] == 4.0 * (1.0 / 0.5) && cov[20] == 4.0 && cov[1] == 0.0 && cov[19] == 0.0);
+        CHECK(info_covariance(&pi, &pe, 0.0, 0.0, cov, &rank, &s2) == PR_OK && rank == 4 && s2 == (1.0e-4 / 100.0) * 100.0 / 94.0);
+    }
     std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;
 }

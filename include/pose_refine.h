@@ -623,6 +623,73 @@ int  pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const
                              int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint8_t *edge_dist_dev,
                              pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host);
 
+/* ---- contour alignment: the silhouette's normal equations in pr_pose_info's coordinates, and a pose step along the observable directions ------
+ * The surface term (pr_pose_information) leaves free exactly the motions a face on a wall, a part slid along the table or a can spun about its
+ * axis have; depth edges constrain them.  Edge pixels, the image and the occlusion test are the contour check's above.
+ * Scene side, once per frame: pr_scene_edge_nearest_dev writes N(x, y) for every frame pixel: among the scene edge pixels (ex, ey) (the edge
+ * pixels of pr_scene_edge_distance_dev for the same jump_mm) with |ex - x| <= radius and |ey - y| <= radius the one that minimises,
+ * lexicographically, (dx^2 + dy^2, ey, ex), as the word ey << 16 | ex; PR_EDGE_NONE when the window holds no edge pixel -- so N != PR_EDGE_NONE
+ * exactly where D != 255.  nearest_dev_out holds width * height words and belongs to the caller: the library keeps nothing by address.
+ * Arguments, checks and behaviour otherwise as pr_scene_edge_distance_dev (three kernels).
+ * Hypothesis side: pr_contour_information renders every pose once (pr_score_contours' arguments, with nearest_dev in place of the distance
+ * image and no overlap matrix) and returns per hypothesis, in the caller's order: scores_host (may be NULL), byte for byte pr_score_poses'
+ * records; fit_host, the record below; info_host, a pr_pose_info about c_i with radius rho, formed from K, center_model and radius exactly as
+ * pr_pose_information forms them.  A render edge pixel at frame (x, y) with rendered depth r and scene depth s is OCCLUDED when s > 0 and
+ * r - s > tau_mm, USED when it is not occluded and N(x, y) != PR_EDGE_NONE, and a MISS otherwise: contour, used, occluded, miss equal
+ * pr_score_contours' contour, hit, occluded, miss.  sum_d2 = the sum over the used pixels of (ex - x)^2 + (ey - y)^2, exact.  Every used pixel
+ * contributes two rows, in float64 with every operation rounded on its own, fx = K[0], cx = K[2], fy = K[4], cy = K[5] converted to double
+ * once and x, y, ex, ey, r taken as integers:
+ *     Z = r / 1000.0;  s = ((x - cx) * Z / fx, (y - cy) * Z / fy, Z);  q = s - c
+ *     row 1:  n = (1, 0, -(x - cx) / fx),  res = (ex - x) * Z / fx          row 2:  n = (0, 1, -(y - cy) / fy),  res = (ey - y) * Z / fy
+ *     a = (qy*nz - qz*ny, qz*nx - qx*nz, qx*ny - qy*nx) / rho;  J = (a, n);  H[i][j] += J[i] * J[j] (i <= j);  g[i] += J[i] * res
+ *     sum_wr2 = sum_r2 = the sum of res * res;  sum_w = 2 * used;  n_points = contour, n_valid = used, n_zero_weight = 0
+ * the linearised pinhole residuals in metres at the pixel's depth, with pr_pose_info's sign: solving H delta = g moves the render edge towards
+ * the scene edge.  Order of addition as for pr_pose_info: lane, wavefront and workgroup sums in a fixed tree, the workgroups' partial sums
+ * through memory in block order, no floating-point atomics; two calls return the same bytes, and a hypothesis' records depend neither on how
+ * the batch is chunked nor on what else is in it.  An empty render or used == 0: every sum zero (c and rho as given).
+ * Known limit: two rows per pixel count information ALONG a straight edge that the data do not hold (the nearest scene edge pixel says nothing
+ * about a slide along the edge), so such a slide is damped, not free.  Point-to-line rows and a robust weight are not part of this call.
+ * PR_ERR_INVALID, nothing written: pr_score_contours' argument errors (nearest_dev for edge_dist_dev, fit_host for contours_host), a null K,
+ * center_model (centers_model, radii), or info_host with n_poses > 0, a K with a non-finite entry or K[0] or K[4] zero, a centre that is not
+ * finite, a radius that is not finite or not positive.  n_poses == 0 returns PR_OK and writes nothing. */
+#define PR_EDGE_NONE 0xFFFFFFFFu
+int  pr_scene_edge_nearest_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm,
+                               uint32_t radius, uint32_t *nearest_dev_out);
+typedef struct {
+    uint32_t contour;      /* edge pixels of the render                                                                  */
+    uint32_t used;         /* not occluded and N != PR_EDGE_NONE: two rows each                                          */
+    uint32_t occluded;     /* s > 0 and r - s > tau                                                                      */
+    uint32_t miss;         /* not occluded and N == PR_EDGE_NONE                                                         */
+    uint32_t reserved[2];  /* written as 0                                                                               */
+    uint64_t sum_d2;       /* sum over the used pixels of the squared pixel distance to N (exact)                        */
+} pr_contour_fit;          /* 32 B; contour == used + occluded + miss                                                    */
+int  pr_contour_information(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses,
+                            uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi,
+                            const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint32_t *nearest_dev,
+                            const float K[9], const float *center_model, float radius,
+                            pr_pose_score *scores_host_or_null, pr_contour_fit *fit_host, pr_pose_info *info_host);
+int  pr_contour_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                                  uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
+                                  int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint32_t *nearest_dev, const float K[9],
+                                  const float *centers_model, const float *radii,
+                                  pr_pose_score *scores_host_or_null, pr_contour_fit *fit_host, pr_pose_info *info_host);
+/* Host only, float64, no device needed.
+ * pr_info_combine: out = wa * a + wb * b for H, g, sum_w and sum_wr2 (each product rounded, then the sum); sum_r2 and the three counts are
+ * added; c and rho are a's.  PR_ERR_INVALID, nothing written: a null pointer, c or rho not bitwise equal in a and b, a weight that is not
+ * finite or is negative.  out may be a or b.
+ * pr_info_eig: the decomposition of info->H exactly as specified for pr_pose_eig above (sweep order, rotation, stopping rule, sort, sign
+ * rule), on the host.
+ * pr_info_step: keep the eigenpairs k with lambda[k] > 0 and lambda[k] > min_ratio * lambda[5] (pr_info_covariance's rule; rank = their
+ * number); delta = the sum over the kept k, ascending, of v_k * ((v_k . g) / lambda[k]), the dot product summed from component 0 to 5;
+ * theta = delta[0..2] / rho, t = delta[3..5]; R = I + (sin a / a) [theta]x + ((1 - cos a) / a^2) [theta]x^2 with a = |theta| (R = I when
+ * a == 0); E = [R | 1000 * (c - R c + t)] -- the twist about c in metres applied to a pose in millimetres; pose_out = E * pose_in (row 3:
+ * pose_in's) in float64, rounded to float32 once.  rank 0 returns pose_in and delta = 0.  delta6_out and rank_out may be NULL; pose_out may
+ * be pose_in.  PR_ERR_INVALID, nothing written: a null info, eig, pose_in or pose_out, min_ratio negative or not finite. */
+int  pr_info_combine(const pr_pose_info *a, double wa, const pr_pose_info *b, double wb, pr_pose_info *out);
+int  pr_info_eig(const pr_pose_info *info, pr_pose_eig *eig_out);
+int  pr_info_step(const pr_pose_info *info, const pr_pose_eig *eig, double min_ratio, const pr_mat4 *pose_in, pr_mat4 *pose_out,
+                  double *delta6_out, uint32_t *rank_out);
+
 /* ---- normal agreement: does the surface of a hypothesis' render face the way the scene's surface does? --------------------------------------
  * The depth score, the overlap matrix and the contour check are blind to a pose whose surface lies within tau_mm of scene surface with the
  * wrong orientation or curvature (a box face laid on a wall, a curved part pressed against a table): it collects inliers.  Where the depths

@@ -31,6 +31,9 @@ SCORE = np.dtype([("visible", "<u4"), ("inlier", "<u4"), ("occluded", "<u4"), ("
 # pr_pose_contour: depth-edge agreement of one hypothesis with the scene (pr_score_contours)
 CONTOUR = np.dtype([("contour", "<u4"), ("hit", "<u4"), ("occluded", "<u4"), ("miss", "<u4"), ("reserved", "<u4", (2,)), ("dist_sum", "<u8")])
 CONTOUR_MAX_RADIUS = 32                  # PR_CONTOUR_MAX_RADIUS
+# pr_contour_fit: the silhouette of one hypothesis against the scene's nearest-edge map (pr_contour_information)
+CONTOUR_FIT = np.dtype([("contour", "<u4"), ("used", "<u4"), ("occluded", "<u4"), ("miss", "<u4"), ("reserved", "<u4", (2,)), ("sum_d2", "<u8")])
+EDGE_NONE = 0xFFFFFFFF                   # PR_EDGE_NONE
 # pr_pose_normal: surface-normal agreement of one hypothesis with the scene on its inlier pixels (pr_score_normals)
 NORMAL = np.dtype([("tested", "<u4"), ("agree", "<u4"), ("disagree", "<u4"), ("no_render_normal", "<u4"), ("no_scene_normal", "<u4"), ("reserved", "<u4", (3,))])
 NORMAL_MAX_STEP = 8                      # PR_NORMAL_MAX_STEP
@@ -60,7 +63,7 @@ INFO_MAX_SWEEPS = 16                     # PR_INFO_MAX_SWEEPS
 assert POSE_INFO.itemsize == 272 and POSE_EIG.itemsize == 344
 POSE_DIST_CHUNK = 256                    # PR_POSE_DIST_CHUNK (pr_tuning.h; the library reports its own as option "pose_dist_chunk")
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
-assert COVER.itemsize == 16 and COVER_FRAME.itemsize == 16
+assert COVER.itemsize == 16 and COVER_FRAME.itemsize == 16 and CONTOUR_FIT.itemsize == 32
 assert NORMAL.itemsize == 32 and VISIBLE.itemsize == 32 and FRAME.itemsize == 32 and POSE_DIST.itemsize == 32 and VSD.itemsize == 64
 
 
@@ -212,6 +215,12 @@ SIGNATURES = {
     "pr_scene_edge_distance_dev": (_i32, [_vp, _i32, _u32, _u32, C.c_int32, _u32, _vp]),
     "pr_score_contours": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "pr_score_contours_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "pr_scene_edge_nearest_dev": (_i32, [_vp, _i32, _u32, _u32, C.c_int32, _u32, _vp]),
+    "pr_contour_information": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "pr_contour_information_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pr_info_combine": (_i32, [_vp, C.c_double, _vp, C.c_double, _vp]),
+    "pr_info_eig": (_i32, [_vp, _vp]),
+    "pr_info_step": (_i32, [_vp, _vp, C.c_double, _vp, _vp, _vp, C.POINTER(_u32)]),
     "pr_score_normals": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _u32, C.c_int32, C.c_float, _vp, _vp, _vp]),
     "pr_score_normals_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _u32, C.c_int32, C.c_float, _vp, _vp, _vp]),
     "pr_compose_detections": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_MAX_RADIUS, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -1585,6 +1585,156 @@ def filter_by_observability(order, eig, min_ratio: float, min_rank: int = 6) -> 
     its order.  The ranking itself is untouched."""
     order = np.asarray(order, np.int64)
     return order[observable_rank(eig, min_ratio)[order] >= int(min_rank)]
+
+
+# ------------------------------------------------------------------------------------------------
+# contour alignment: the silhouette's normal equations, and a pose step along the observable directions
+# ------------------------------------------------------------------------------------------------
+def scene_edge_nearest(scene_depth, width: int, height: int, jump_mm: int, radius: int) -> DeviceVector:
+    """``pr_scene_edge_nearest_dev``: for every frame pixel the nearest scene depth edge pixel (``scene_edge_distance``'s edge pixels) within
+    the (2 radius + 1)^2 window around it as ``ey << 16 | ex``, ``EDGE_NONE`` where the window holds none; ties go to the smaller squared
+    distance, then the smaller ey, then the smaller ex.  One uint32 per pixel.  Made once per frame and handed to ``contour_information``."""
+    sd = _scene_depth_dev(scene_depth, width, height)
+    out = DeviceVector(width * height, np.uint32)
+    check(_lib.load().pr_scene_edge_nearest_dev(sd.data(), int(sd.dtype == np.int32), width, height, int(jump_mm), int(radius), out.data()))
+    return out
+
+
+def _nearest_dev(nearest, width: int, height: int) -> DeviceVector:
+    if not isinstance(nearest, DeviceVector) or nearest.dtype != np.uint32:
+        raise ValueError("nearest must be the DeviceVector(uint32) that scene_edge_nearest returns")
+    if nearest.size() != width * height:
+        raise ValueError(f"nearest holds {nearest.size()} values, expected {width} x {height}")
+    return nearest
+
+
+def _contour_information(mesh, width: int, height: int, proj, scene_depth, tau_mm: int, jump_mm: int, nearest, K, cm, rad, roi, want_scores: bool):
+    call, n = _score_call("pr_contour_information", mesh, width, height, proj, scene_depth, tau_mm, roi if roi is not None else (0, 0, 0, 0))
+    nd = _nearest_dev(nearest, width, height)
+    k = _f32(K, -1)
+    if k.size != 9:
+        raise ValueError("K must hold 9 values")
+    scores = np.zeros(n, SCORE) if want_scores else None
+    fit, info = np.zeros(n, CONTOUR_FIT), np.zeros(n, _lib.POSE_INFO)
+    call(int(jump_mm), nd.data(), ptr(k), ptr(cm), rad if isinstance(rad, float) else ptr(rad),      # (one mesh: the radius by value; a table: one per mesh)
+         ptr(scores) if want_scores else None, ptr(fit), ptr(info))
+    return scores, fit, info
+
+
+def contour_information(tris, poses, width: int, height: int, proj, K, scene_depth, tau_mm: int, jump_mm: int, nearest, center=None, radius=None,
+                        roi: Optional[Sequence[int]] = None, want_scores: bool = True):
+    """``pr_contour_information``: one render per pose; every edge pixel of the render that is not occluded and has a scene edge pixel in
+    ``nearest`` (``scene_edge_nearest``'s map of the same frame) contributes the two rows of its pixel offset, in metres at its depth, to a
+    float64 information record about the pose's centre -- the coordinates of ``pose_information`` (same ``center`` / ``radius`` defaults), so
+    the two records can go to ``combine_information``.  Returns (SCORE[P] or None, CONTOUR_FIT[P], POSE_INFO[P])."""
+    cm, rad = _model_center_radius(tris, center, radius)
+    return _contour_information(_one_mesh(tris, poses), width, height, proj, scene_depth, tau_mm, jump_mm, nearest, K, cm, rad, roi, want_scores)
+
+
+def contour_information_multi(meshes, mesh_index, poses, width: int, height: int, proj, K, scene_depth, tau_mm: int, jump_mm: int, nearest,
+                              centers=None, radii=None, roi: Optional[Sequence[int]] = None, want_scores: bool = True):
+    """``pr_contour_information_multi``: ``contour_information`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; ``centers`` / ``radii``:
+    one per mesh (None: each ``Model``'s defaults).  Every record equals the single-mesh call's."""
+    meshes = list(meshes)
+    cm, rad = _mesh_centers_radii(meshes, centers, radii)
+    return _contour_information(_mesh_batch(meshes, mesh_index, poses), width, height, proj, scene_depth, tau_mm, jump_mm, nearest, K, cm, rad, roi, want_scores)
+
+
+def _mesh_centers_radii(meshes, centers, radii):
+    cr = [_model_center_radius(m, None if centers is None else centers[i], None if radii is None else radii[i]) for i, m in enumerate(meshes)]
+    cm = _f32([c for c, _ in cr], (-1, 3)) if cr else np.zeros((1, 3), np.float32)
+    rad = _f32([r for _, r in cr], -1) if cr else np.ones(1, np.float32)
+    return cm, rad
+
+
+def combine_information(a, b, wa: float = 1.0, wb: float = 1.0) -> np.ndarray:
+    """``pr_info_combine`` record by record (host only): ``wa * a + wb * b`` for H, g, sum_w and sum_wr2; sum_r2 and the counts are added.  The
+    records of a pair must be about the same centre and radius, bit for bit."""
+    a, b = np.ascontiguousarray(a, _lib.POSE_INFO).reshape(-1), np.ascontiguousarray(b, _lib.POSE_INFO).reshape(-1)
+    if len(a) != len(b):
+        raise ValueError(f"combine_information: {len(a)} records against {len(b)}")
+    out = np.zeros(len(a), _lib.POSE_INFO)
+    lib, sz = _lib.load(), _lib.POSE_INFO.itemsize
+    for i in range(len(a)):
+        check(lib.pr_info_combine(ptr(a) + i * sz, float(wa), ptr(b) + i * sz, float(wb), ptr(out) + i * sz))
+    return out
+
+
+def information_eig(info) -> np.ndarray:
+    """``pr_info_eig`` record by record (host only): the cyclic Jacobi of ``pose_information``'s eigen kernel, on the host.  POSE_EIG[P]."""
+    info = np.ascontiguousarray(info, _lib.POSE_INFO).reshape(-1)
+    out = np.zeros(len(info), _lib.POSE_EIG)
+    lib = _lib.load()
+    for i in range(len(info)):
+        check(lib.pr_info_eig(ptr(info) + i * _lib.POSE_INFO.itemsize, ptr(out) + i * _lib.POSE_EIG.itemsize))
+    return out
+
+
+def information_step(info, eig, poses, min_ratio: float):
+    """``pr_info_step`` record by record (host only): every pose moved by the solution of ``H delta = g`` restricted to the eigenpairs
+    ``observable_rank`` counts -- a twist about the record's centre, rotational half divided by ``rho``.  Returns (poses float32[P, 4, 4],
+    delta float64[P, 6], rank int64[P]); a record of rank 0 leaves its pose as it is."""
+    info = np.ascontiguousarray(info, _lib.POSE_INFO).reshape(-1)
+    eig = np.ascontiguousarray(eig, _lib.POSE_EIG).reshape(-1)
+    pin = _f32(poses, (-1, 16))
+    if not (len(info) == len(eig) == len(pin)):
+        raise ValueError(f"information_step: {len(info)} info records, {len(eig)} eig records, {len(pin)} poses")
+    out, delta, rank = np.zeros_like(pin), np.zeros((len(pin), 6), np.float64), np.zeros(len(pin), np.int64)
+    lib, r = _lib.load(), C.c_uint32()
+    for i in range(len(pin)):
+        check(lib.pr_info_step(ptr(info) + i * _lib.POSE_INFO.itemsize, ptr(eig) + i * _lib.POSE_EIG.itemsize, float(min_ratio), ptr(pin) + i * 64,
+                               ptr(out) + i * 64, ptr(delta) + i * 48, C.byref(r)))
+        rank[i] = r.value
+    return out.reshape(-1, 4, 4), delta, rank
+
+
+def _refine_contours(surface, contour, poses, iterations: int, weight: float, min_ratio: float, min_used: int):
+    """The loop of ``refine_contours``: surface(poses) -> POSE_INFO[P], contour(poses) -> (CONTOUR_FIT[P], POSE_INFO[P])."""
+    poses = _f32(poses, (-1, 16)).reshape(-1, 4, 4).copy()
+    n, iters = len(poses), int(iterations)
+    live = np.ones(n, bool)
+    hist = dict(rank=np.zeros((iters, n), np.int64), used=np.zeros((iters, n), np.int64), rms_px=np.full((iters, n), np.nan))
+    for it in range(iters):
+        surf = surface(poses)
+        fit, con = contour(poses)
+        both = combine_information(surf, con, 1.0, weight)
+        eig = information_eig(both)
+        stepped, _, rank = information_step(both, eig, poses, min_ratio)
+        live &= (fit["used"] >= int(min_used)) & (surf["n_valid"] > 0)
+        poses[live] = stepped[live]
+        used = fit["used"].astype(np.int64)
+        hist["rank"][it], hist["used"][it] = rank, used
+        hist["rms_px"][it] = np.where(used > 0, np.sqrt(fit["sum_d2"].astype(np.float64) / np.maximum(used, 1)), np.nan)
+    return poses, hist
+
+
+def refine_contours(tris, poses, width: int, height: int, proj, K, scene, scene_depth, nearest, tau_mm: int, jump_mm: int, *, iterations: int,
+                    weight: float, min_ratio: float, min_used: int, center=None, radius=None, roi: Optional[Sequence[int]] = None,
+                    robust: Optional[Robust] = None):
+    """Pose steps on the surface and the silhouette together.  Per iteration: ``pose_information`` (``scene``, ``robust``) and
+    ``contour_information`` (``scene_depth``, ``nearest``) at the current poses, ``combine_information(1, weight)``, ``information_eig`` and
+    ``information_step(min_ratio)``: the silhouette pins the motions the surface leaves free, and what neither constrains is not stepped along.
+    A hypothesis with fewer than ``min_used`` used contour pixels, or without a surface correspondence, keeps its pose from then on.  Returns
+    (poses float32[P, 4, 4], history) with ``history["rank"]``, ``["used"]`` and ``["rms_px"]`` (sqrt(sum_d2 / used), the contour's RMS pixel
+    distance; nan without used pixels) of shape (iterations, P), each as found BEFORE that iteration's step."""
+    cm, rad = _model_center_radius(tris, center, radius)
+    return _refine_contours(
+        lambda p: pose_information(tris, p, width, height, proj, K, scene, cm, rad, roi, robust, want_eig=False)[0],
+        lambda p: contour_information(tris, p, width, height, proj, K, scene_depth, tau_mm, jump_mm, nearest, cm, rad, roi, want_scores=False)[1:],
+        poses, iterations, weight, min_ratio, min_used)
+
+
+def refine_contours_multi(meshes, mesh_index, poses, width: int, height: int, proj, K, scene, scene_depth, nearest, tau_mm: int, jump_mm: int, *,
+                          iterations: int, weight: float, min_ratio: float, min_used: int, centers=None, radii=None,
+                          roi: Optional[Sequence[int]] = None, robust: Optional[Robust] = None):
+    """``refine_contours`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; ``centers`` / ``radii``: one per mesh."""
+    meshes = list(meshes)
+    cm, rad = _mesh_centers_radii(meshes, centers, radii)
+    return _refine_contours(
+        lambda p: pose_information_multi(meshes, mesh_index, p, width, height, proj, K, scene, cm, rad, roi, robust, want_eig=False)[0],
+        lambda p: contour_information_multi(meshes, mesh_index, p, width, height, proj, K, scene_depth, tau_mm, jump_mm, nearest, cm, rad, roi,
+                                            want_scores=False)[1:],
+        poses, iterations, weight, min_ratio, min_used)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,17 +1,10 @@
-// contour.hip -- depth-edge (contour) agreement: the scene's edge pixels with their chessboard distance transform, made once per frame, and the
-// edge pixels of every rendered box of a batch (launch_render_boxes) counted against it
+// contour.hip -- depth-edge (contour) agreement: the scene's edge pixels with their chessboard distance transform and their nearest-edge map
+// (contour_fit.hip's input), each made once per frame, and the edge pixels of every rendered box of a batch (launch_render_boxes) counted against
+// the distance transform
 // gfx950 (CDNA4, wave64); compiled with -ffp-contract=off like the rest (integer arithmetic only: differences in 64 bits).
 #include "score_walk.h"
 
 namespace prk {
-
-// The edge rule on normalised values: c > 0 is the pixel's depth; a neighbour is 0 when it is empty (no surface: infinitely far), its depth
-// when it has one, and kNoNeighbour when it lies outside the image (ignored: an object cut by the border has no contour there).
-constexpr int32_t kNoNeighbour = -1;
-__device__ __forceinline__ bool edge_trigger(int32_t c, int32_t n, int64_t jump)
-{
-    return n == 0 || (n > 0 && (int64_t)n - (int64_t)c > jump);     // 64 bits: no overflow for any int32 pair
-}
 
 // ---- scene side: three launches ---------------------------------------------------------------------------------------------------
 // (1) edge bits.  One wavefront per 64-pixel word of a row: bit b of word w of row y is frame pixel (64 w + b, y), 0 beyond the row's end.
@@ -39,19 +32,26 @@ __global__ __launch_bounds__(256) void scene_edge_kernel(const SceneT *__restric
     if (lane == 0) bits[cell] = m;
 }
 
-// (2) distance along the row to the nearest edge pixel, 255 beyond `radius` (<= 32: the pixel's own word and one word on either side hold
-// every candidate).  right: bit k = pixel x + k; left: bit 63 - k = pixel x - k.
+// The distances from pixel x to the nearest edge pixel of its row at or left of it (dl) and at or right of it (dr), 64 when the pixel's own word and
+// one word on either side hold none (radius <= 32: they hold every candidate).  right: bit k = pixel x + k; left: bit 63 - k = pixel x - k.
+__device__ __forceinline__ void row_edge_distances(const unsigned long long *__restrict__ brow, uint32_t x, uint32_t words_per_row, uint32_t &dl, uint32_t &dr)
+{
+    const uint32_t w = x >> 6, b = x & 63;
+    const unsigned long long here = brow[w], prev = w > 0 ? brow[w - 1] : 0ull, next = w + 1 < words_per_row ? brow[w + 1] : 0ull;
+    const unsigned long long right = (here >> b) | (b ? next << (64 - b) : 0ull);
+    const unsigned long long left = (here << (63 - b)) | (b < 63 ? prev >> (b + 1) : 0ull);
+    dr = right ? (uint32_t)__builtin_ctzll(right) : 64u;
+    dl = left ? (uint32_t)__builtin_clzll(left) : 64u;
+}
+
+// (2) distance along the row to the nearest edge pixel, 255 beyond `radius`
 __global__ __launch_bounds__(256) void edge_row_dist_kernel(const unsigned long long *__restrict__ bits, uint32_t width, uint32_t height, uint32_t words_per_row,
                                                             uint32_t radius, uint8_t *__restrict__ row_dist)
 {
     const uint32_t x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= width) return;
-    const unsigned long long *brow = bits + (size_t)y * words_per_row;
-    const uint32_t w = x >> 6, b = x & 63;
-    const unsigned long long here = brow[w], prev = w > 0 ? brow[w - 1] : 0ull, next = w + 1 < words_per_row ? brow[w + 1] : 0ull;
-    const unsigned long long right = (here >> b) | (b ? next << (64 - b) : 0ull);
-    const unsigned long long left = (here << (63 - b)) | (b < 63 ? prev >> (b + 1) : 0ull);
-    const uint32_t dr = right ? (uint32_t)__builtin_ctzll(right) : 64u, dl = left ? (uint32_t)__builtin_clzll(left) : 64u;
+    uint32_t dl, dr;
+    row_edge_distances(bits + (size_t)y * words_per_row, x, words_per_row, dl, dr);
     const uint32_t d = dr < dl ? dr : dl;
     row_dist[(size_t)y * width + x] = (uint8_t)(d <= radius ? d : 255u);
 }
@@ -80,6 +80,51 @@ hipError_t launch_scene_edge_distance(const void *scene, bool scene_i32, uint32_
     const dim3 grid((width + 255) / 256, height);                   // height <= 8192
     hipLaunchKernelGGL(edge_row_dist_kernel, grid, dim3(256), 0, s, bits, width, height, wpr, radius, row_dist);
     hipLaunchKernelGGL(edge_col_dist_kernel, grid, dim3(256), 0, s, row_dist, width, height, radius, dist);
+    return hipGetLastError();
+}
+
+// ---- the nearest scene edge pixel (pr_scene_edge_nearest_dev): the bit plane of (1), then a row and a column pass ------------------------------
+// (2') the signed offset ex - x of the nearest edge pixel of the row within `radius`, the smaller ex (the left one) on a tie; kNoRowEdge when none
+constexpr int kNoRowEdge = 127;                                    // radius <= 32: every offset fits an int8 beside it
+__global__ __launch_bounds__(256) void edge_row_near_kernel(const unsigned long long *__restrict__ bits, uint32_t width, uint32_t height, uint32_t words_per_row,
+                                                            uint32_t radius, int8_t *__restrict__ row_off)
+{
+    const uint32_t x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= width) return;
+    uint32_t dl, dr;
+    row_edge_distances(bits + (size_t)y * words_per_row, x, words_per_row, dl, dr);
+    const int off = dl <= dr ? -(int)dl : (int)dr;                  // (dl == dr == 0: the pixel itself)
+    const uint32_t d = dl <= dr ? dl : dr;
+    row_off[(size_t)y * width + x] = (int8_t)(d <= radius ? off : kNoRowEdge);
+}
+
+// (3') over the rows y - radius .. y + radius inside the frame, ascending, the candidate of least dx^2 + dy^2; the first one on a tie (the smaller
+// ey; within a row (2') already took the smaller ex): the lexicographic minimum of (d^2, ey, ex) over the window, exactly
+__global__ __launch_bounds__(256) void edge_col_near_kernel(const int8_t *__restrict__ row_off, uint32_t width, uint32_t height, uint32_t radius,
+                                                            uint32_t *__restrict__ nearest)
+{
+    const uint32_t x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= width) return;
+    const int y_lo = max((int)y - (int)radius, 0), y_hi = min((int)y + (int)radius, (int)height - 1);
+    uint32_t best_d2 = 0xffffffffu, best = PR_EDGE_NONE;
+    for (int yy = y_lo; yy <= y_hi; ++yy) {
+        const int off = row_off[(size_t)yy * width + x];
+        if (off == kNoRowEdge) continue;
+        const int dy = yy - (int)y;
+        const uint32_t d2 = (uint32_t)(off * off + dy * dy);
+        if (d2 < best_d2) { best_d2 = d2; best = ((uint32_t)yy << 16) | (uint32_t)((int)x + off); }
+    }
+    nearest[(size_t)y * width + x] = best;
+}
+
+hipError_t launch_scene_edge_nearest(const void *scene, bool scene_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
+                                     unsigned long long *bits, int8_t *row_off, uint32_t *nearest, hipStream_t s)
+{
+    const uint32_t wpr = overlap_words_per_row(width), cells = height * wpr;
+    with_scene(scene, scene_i32, [&](auto *sc) { hipLaunchKernelGGL(scene_edge_kernel, dim3((cells + 3) / 4), dim3(256), 0, s, sc, width, height, jump_mm, bits, wpr); });
+    const dim3 grid((width + 255) / 256, height);
+    hipLaunchKernelGGL(edge_row_near_kernel, grid, dim3(256), 0, s, bits, width, height, wpr, radius, row_off);
+    hipLaunchKernelGGL(edge_col_near_kernel, grid, dim3(256), 0, s, row_off, width, height, radius, nearest);
     return hipGetLastError();
 }
 

@@ -251,6 +251,10 @@ hipError_t launch_cover_final(const unsigned long long *planes, const int4 *bbox
 // caller zeroed.  window {x0, row0, x1, row1}: the image the renders live in (the frame or the ROI), in image coordinates
 hipError_t launch_scene_edge_distance(const void *scene, bool scene_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
                                       unsigned long long *bits, uint8_t *row_dist, uint8_t *dist, hipStream_t s);
+// ... and the nearest edge pixel of every frame pixel's (2 radius + 1)^2 window as ey << 16 | ex, PR_EDGE_NONE when it holds none (row_off: scratch,
+// width x height bytes; nearest: width x height words) -- three launches, the first one the distance transform's
+hipError_t launch_scene_edge_nearest(const void *scene, bool scene_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
+                                     unsigned long long *bits, int8_t *row_off, uint32_t *nearest, hipStream_t s);
 hipError_t launch_contour_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height, int4 window,
                                 const void *scene, bool scene_i32, const uint8_t *edge_dist, int32_t tau, int32_t jump_mm, uint32_t *records, hipStream_t s);
 // normals.hip: on the inlier pixels of every rendered box (launch_score_boxes' test with tau), the render's normal against the scene's, both estimated

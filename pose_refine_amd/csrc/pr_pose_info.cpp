@@ -1,5 +1,6 @@
 // pr_pose_info.cpp -- pose observability: the driver of pose_info.hip's two launches (info_drive), pr_icp_information and its audit form, and the
-// host-only covariance pr_info_covariance.  The fused entry points (pr_pose_information, _multi) live in pr_refine.cpp beside refine_core.
+// host-only covariance pr_info_covariance, and the host-only float64 pieces of a combined pose step: pr_info_combine, pr_info_eig (the eigen kernel's
+// Jacobi, restated) and pr_info_step.  The fused entry points (pr_pose_information, _multi) live in pr_refine.cpp beside refine_core.
 #include "pr_runtime.h"
 #include "pose_info.h"
 
@@ -98,6 +99,140 @@ static int icp_information_impl(const char *fn, const pr_vec3 *clouds_dev, const
     return info_drive(clouds_dev, start.data(), count.data(), n_clouds, sc, robust ? *robust : kPlain, centers, radii, info_host, eig_host);
 }
 
+// ---- host only: combine two records, decompose one, step a pose along its observable directions ---------------------------------------------------
+static int info_combine(const pr_pose_info *a, double wa, const pr_pose_info *b, double wb, pr_pose_info *out)
+{
+    const char *fn = "pr_info_combine";
+    if (!a || !b || !out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(wa) || !std::isfinite(wb) || wa < 0.0 || wb < 0.0) { set_error("%s: the weights must be finite and >= 0", fn); return PR_ERR_INVALID; }
+    if (std::memcmp(a->c, b->c, sizeof a->c) != 0 || std::memcmp(&a->rho, &b->rho, sizeof a->rho) != 0) {
+        set_error("%s: the records are about different centres or radii", fn); return PR_ERR_INVALID;
+    }
+    pr_pose_info o = *a;
+    o.n_points = a->n_points + b->n_points; o.n_valid = a->n_valid + b->n_valid; o.n_zero_weight = a->n_zero_weight + b->n_zero_weight; o.reserved = 0;
+    for (int i = 0; i < 21; ++i) o.H[i] = wa * a->H[i] + wb * b->H[i];
+    for (int i = 0; i < 6; ++i) o.g[i] = wa * a->g[i] + wb * b->g[i];
+    o.sum_w = wa * a->sum_w + wb * b->sum_w;
+    o.sum_wr2 = wa * a->sum_wr2 + wb * b->sum_wr2;
+    o.sum_r2 = a->sum_r2 + b->sum_r2;
+    *out = o;
+    return PR_OK;
+}
+
+// pose_info_eigen_kernel's decomposition (pose_info.hip), statement for statement: include/pose_refine.h specifies it
+static void jacobi_rotate(double (&A)[6][6], double (&V)[6][6], int p, int q)
+{
+    const double apq = A[p][q];
+    if (apq == 0.0) return;
+    const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+    const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+    A[p][p] -= t * apq;
+    A[q][q] += t * apq;
+    A[p][q] = 0.0; A[q][p] = 0.0;
+    for (int k = 0; k < 6; ++k) {
+        if (k == p || k == q) continue;
+        const double akp = A[k][p], akq = A[k][q];
+        const double np = c * akp - s * akq, nq = s * akp + c * akq;
+        A[k][p] = np; A[p][k] = np;
+        A[k][q] = nq; A[q][k] = nq;
+    }
+    for (int k = 0; k < 6; ++k) {
+        const double vkp = V[k][p], vkq = V[k][q];
+        V[k][p] = c * vkp - s * vkq;
+        V[k][q] = s * vkp + c * vkq;
+    }
+}
+static int info_eig(const pr_pose_info *info, pr_pose_eig *eig_out)
+{
+    if (!info || !eig_out) { set_error("pr_info_eig: bad arguments (info or eig_out is null)"); return PR_ERR_INVALID; }
+    double A[6][6], V[6][6];
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) { A[i][j] = info->H[k]; A[j][i] = info->H[k]; ++k; }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
+    uint32_t sweeps = 0;
+    for (; sweeps < PR_INFO_MAX_SWEEPS; ++sweeps) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < 6; ++i) {
+            diag = std::fmax(diag, std::fabs(A[i][i]));
+            for (int j = i + 1; j < 6; ++j) off = std::fmax(off, std::fabs(A[i][j]));
+        }
+        if (off <= 0x1p-56 * diag) break;
+        for (int p = 0; p < 5; ++p)
+            for (int q = p + 1; q < 6; ++q) jacobi_rotate(A, V, p, q);
+    }
+    double lam[6];
+    for (int i = 0; i < 6; ++i) lam[i] = A[i][i];
+    // ascending order by the kernel's fixed 12-comparator network (strict: equal eigenvalues keep their places)
+    static const int net[12][2] = { { 1, 2 }, { 4, 5 }, { 0, 2 }, { 3, 5 }, { 0, 1 }, { 3, 4 }, { 2, 5 }, { 0, 3 }, { 1, 4 }, { 2, 4 }, { 1, 3 }, { 2, 3 } };
+    for (const auto &ij : net) {
+        const int i = ij[0], j = ij[1];
+        if (!(lam[i] > lam[j])) continue;
+        std::swap(lam[i], lam[j]);
+        for (int r = 0; r < 6; ++r) std::swap(V[r][i], V[r][j]);
+    }
+    pr_pose_eig e;
+    for (int c = 0; c < 6; ++c) {
+        double big = V[0][c];
+        for (int i = 1; i < 6; ++i) if (std::fabs(V[i][c]) > std::fabs(big)) big = V[i][c];
+        const double sg = (big < 0.0) ? -1.0 : 1.0;
+        e.lambda[c] = lam[c];
+        for (int i = 0; i < 6; ++i) e.V[i * 6 + c] = sg * V[i][c];
+    }
+    e.sweeps = sweeps; e.reserved = 0;
+    *eig_out = e;
+    return PR_OK;
+}
+
+static int info_step(const pr_pose_info *info, const pr_pose_eig *eig, double min_ratio, const pr_mat4 *pose_in, pr_mat4 *pose_out, double *delta6_out,
+                     uint32_t *rank_out)
+{
+    const char *fn = "pr_info_step";
+    if (!info || !eig || !pose_in || !pose_out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(min_ratio) || min_ratio < 0.0) { set_error("%s: min_ratio must be finite and >= 0", fn); return PR_ERR_INVALID; }
+    uint32_t rank = 0;
+    double delta[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    for (int k = 0; k < 6; ++k) {
+        const double l = eig->lambda[k];
+        if (!(l > 0.0) || !(l > min_ratio * eig->lambda[5])) continue;
+        ++rank;
+        double dot = 0.0;
+        for (int i = 0; i < 6; ++i) dot += eig->V[6 * i + k] * info->g[i];
+        const double coef = dot / l;
+        for (int i = 0; i < 6; ++i) delta[i] += eig->V[6 * i + k] * coef;
+    }
+    pr_mat4 out = *pose_in;
+    if (rank > 0) {
+        const double rho = (double)info->rho, c[3] = { (double)info->c[0], (double)info->c[1], (double)info->c[2] };
+        const double th[3] = { delta[0] / rho, delta[1] / rho, delta[2] / rho };
+        const double a2 = (th[0] * th[0] + th[1] * th[1]) + th[2] * th[2], a = std::sqrt(a2);
+        double R[3][3] = { { 1.0, 0.0, 0.0 }, { 0.0, 1.0, 0.0 }, { 0.0, 0.0, 1.0 } };
+        if (a > 0.0) {
+            const double Kx[3][3] = { { 0.0, -th[2], th[1] }, { th[2], 0.0, -th[0] }, { -th[1], th[0], 0.0 } };
+            const double A = std::sin(a) / a, B = (1.0 - std::cos(a)) / a2;
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    const double k2 = (Kx[i][0] * Kx[0][j] + Kx[i][1] * Kx[1][j]) + Kx[i][2] * Kx[2][j];
+                    R[i][j] += A * Kx[i][j] + B * k2;
+                }
+        }
+        double tr[3];                                               // 1000 * (c - R c + t): metres about c to the pose's millimetres
+        for (int i = 0; i < 3; ++i) tr[i] = 1000.0 * ((c[i] - ((R[i][0] * c[0] + R[i][1] * c[1]) + R[i][2] * c[2])) + delta[3 + i]);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 4; ++j) {
+                double v = (R[i][0] * (double)pose_in->m[j] + R[i][1] * (double)pose_in->m[4 + j]) + R[i][2] * (double)pose_in->m[8 + j];
+                if (j == 3) v += tr[i];
+                out.m[4 * i + j] = (float)v;
+            }
+    }
+    *pose_out = out;
+    if (delta6_out) for (int i = 0; i < 6; ++i) delta6_out[i] = delta[i];
+    if (rank_out) *rank_out = rank;
+    return PR_OK;
+}
+
 }  // namespace prr
 
 using namespace prr;
@@ -124,6 +259,16 @@ int pr_info_covariance(const pr_pose_info *info, const pr_pose_eig *eig, double 
                        double *sigma2_out)
 {
     return info_covariance(info, eig, sigma, min_ratio, cov21_out, rank_out, sigma2_out);
+}
+
+int pr_info_combine(const pr_pose_info *a, double wa, const pr_pose_info *b, double wb, pr_pose_info *out) { return info_combine(a, wa, b, wb, out); }
+
+int pr_info_eig(const pr_pose_info *info, pr_pose_eig *eig_out) { return info_eig(info, eig_out); }
+
+int pr_info_step(const pr_pose_info *info, const pr_pose_eig *eig, double min_ratio, const pr_mat4 *pose_in, pr_mat4 *pose_out, double *delta6_out,
+                 uint32_t *rank_out)
+{
+    return info_step(info, eig, min_ratio, pose_in, pose_out, delta6_out, rank_out);
 }
 
 }  // extern "C"

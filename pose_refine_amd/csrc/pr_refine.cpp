@@ -352,6 +352,9 @@ struct ReadBack {
 // as this one is scored -- and one launch over all pairs follows the last chunk.  The planes are dense: P x H x ceil(W / 64) words of 8 bytes.
 // kScoreContours: the contour records of the same renders against the scene's edge distance image (contour.hip), one more
 // kernel over every chunk's boxes right behind the score kernel; the records travel like the scores.
+// kScoreContourFit: the silhouette's normal equations of the same renders against the scene's nearest-edge map (contour_fit.hip): the centres staged
+// through the information pass' pinned block, one kernel over every chunk's boxes and one that adds its partial sums; the fit records travel like the
+// scores, the pr_pose_info records are stored straight into the pinned block (info_drive's way).  req.scores may be null.
 // kScoreNormals: the normal records of the same renders against the scene (normals.hip), one more kernel over every chunk's boxes right behind
 // the score kernel; the records travel like the scores.
 // kScoreCompose: the same renders taken together (compose.hip).  One more kernel over every chunk's boxes folds them into
@@ -370,10 +373,15 @@ int score_core(const ScoreRequest &req)
     const uint32_t P = req.P, W = req.W, H = req.H;
     const int32_t tau = req.tau;
     const bool contours = req.kind == kScoreContours, normals = req.kind == kScoreNormals, compose = req.kind == kScoreCompose, cover = req.kind == kScoreCover;
+    const bool fit = req.kind == kScoreContourFit;
     const MeshSource src{ req.tris, req.n_tris, req.plan };
     static_assert(sizeof(pr_pose_visible) == sizeof(pr_pose_score) && sizeof(pr_frame_explained) == sizeof(pr_pose_score), "pr_pose_visible, pr_frame_explained: 32-byte records");
     static_assert(sizeof(pr_pose_contour) == sizeof(pr_pose_score) && offsetof(pr_pose_contour, dist_sum) == 24, "pr_pose_contour: one 32-byte record, the sum in words 6 and 7");
     static_assert(sizeof(pr_pose_normal) == sizeof(pr_pose_score), "pr_pose_normal: one 32-byte record");
+    static_assert(sizeof(pr_contour_fit) == sizeof(pr_pose_score) && offsetof(pr_contour_fit, sum_d2) == 24, "pr_contour_fit: one 32-byte record, the sum in words 6 and 7");
+    static_assert(sizeof(pr_pose_info) % sizeof(uint32_t) == 0, "pr_pose_info travels in 32-bit words");
+    const prk::FitParams fit_params = fit ? prk::FitParams{ (double)req.K[0], (double)req.K[2], (double)req.K[4], (double)req.K[5], tau, req.jump } : prk::FitParams{};
+    const uint32_t fit_nblk = prk::fit_blocks(H);
     const prk::NormalParams normal_params = normals ? prk::NormalParams{ (double)req.K[0], (double)req.K[2], (double)req.K[4], (double)req.K[5],
                                                                           (double)req.cos_min * (double)req.cos_min, req.step, req.jump, tau } : prk::NormalParams{};
     const bool has_roi = req.roi.width > 0 && req.roi.height > 0;
@@ -433,6 +441,12 @@ int score_core(const ScoreRequest &req)
         PR_TRY(g->h_scores.ensure(sizeof(pr_pose_score) * np));
         if (contours) { PR_TRY(g->contours.ensure(sizeof(pr_pose_contour) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_pose_contour) * np)); }
         if (normals) { PR_TRY(g->normals.ensure(sizeof(pr_pose_normal) * np)); PR_TRY(g->h_normals.ensure(sizeof(pr_pose_normal) * np)); }
+        if (fit) {                                                   // the contour check's record buffers and the information pass' workspaces: neither runs beside this kind
+            PR_TRY(g->contours.ensure(sizeof(pr_contour_fit) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_contour_fit) * np));
+            PR_TRY(g->info_meta.ensure(sizeof(prk::FitMeta) * np)); PR_TRY(g->h_info_meta.ensure(sizeof(prk::FitMeta) * np));
+            PR_TRY(g->info_part.ensure(sizeof(double) * prk::kFitSums * (size_t)fit_nblk * np));
+            PR_TRY(g->h_info_out.ensure(sizeof(pr_pose_info) * np));
+        }
         uint32_t *box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np);
         {
             SpanGuard sp(kSpanRender);
@@ -447,6 +461,15 @@ int score_core(const ScoreRequest &req)
             HIP_TRY(prk::launch_fill_i32(g->contours.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
             HIP_TRY(prk::launch_contour_boxes(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, req.scene, req.scene_i32, req.edge_dist, tau,
                                               req.jump, g->contours.as<uint32_t>(), g->stream));
+            PR_TRY(contours_back.queue(g->contours.p, g->h_contours, kWords * np));
+        }
+        if (fit) {
+            std::memcpy(g->h_info_meta.p, req.fit_meta + p0, sizeof(prk::FitMeta) * np);
+            HIP_TRY(prk::launch_stage_words(g->h_info_meta.dev, g->info_meta.p, sizeof(prk::FitMeta) * np, g->stream));
+            HIP_TRY(prk::launch_fill_i32(g->contours.as<int32_t>(), (size_t)kWords * np, 0, g->stream));
+            HIP_TRY(prk::launch_contour_fit(g->depth.as<int32_t>(), g->bbox.as<int4>(), box_off, np, W, H, window, req.scene, req.scene_i32, req.nearest,
+                                            g->info_meta.as<prk::FitMeta>(), fit_params, g->contours.as<uint32_t>(), g->info_part.as<double>(),
+                                            g->h_info_out.dev_as<pr_pose_info>(), g->stream));
             PR_TRY(contours_back.queue(g->contours.p, g->h_contours, kWords * np));
         }
         if (normals) {
@@ -468,7 +491,11 @@ int score_core(const ScoreRequest &req)
         }
         PR_TRY(scores_back.queue(g->scores.p, g->h_scores, kWords * np));
         HIP_TRY(hipStreamSynchronize(g->stream));
-        scores_back.deliver(req.scores + p0, sizeof(pr_pose_score) * np);
+        if (req.scores) scores_back.deliver(req.scores + p0, sizeof(pr_pose_score) * np);
+        if (fit) {
+            contours_back.deliver(req.fit + p0, sizeof(pr_contour_fit) * np);
+            std::memcpy(req.fit_info + p0, g->h_info_out.p, sizeof(pr_pose_info) * np);
+        }
         if (contours) contours_back.deliver(req.contours + p0, sizeof(pr_pose_contour) * np);
         if (normals) normals_back.deliver(req.normals + p0, sizeof(pr_pose_normal) * np);
     }
@@ -565,9 +592,14 @@ int score_run(const ScoreRequest &req)
     std::vector<uint32_t> ov(req.overlap ? (size_t)P * P : 0);
     std::vector<pr_pose_contour> cc(req.kind == kScoreContours ? P : 0);
     std::vector<pr_pose_normal> nn(req.kind == kScoreNormals ? P : 0);
+    std::vector<pr_contour_fit> ff(req.kind == kScoreContourFit ? P : 0);
+    std::vector<pr_pose_info> fi(ff.size());
     ScoreRequest grouped = req;
     grouped.plan = &pl; grouped.order = pl.order.data(); grouped.poses = poses.data();
     grouped.scores = sc.data(); grouped.overlap = req.overlap ? ov.data() : nullptr; grouped.contours = cc.data(); grouped.normals = nn.data();
+    std::vector<prk::FitMeta> fm(ff.size());
+    for (uint32_t j = 0; j < fm.size(); ++j) fm[j] = req.fit_meta[pl.order[j]];
+    grouped.fit = ff.data(); grouped.fit_info = fi.data(); grouped.fit_meta = fm.data();
     // the cover walk runs on grouped positions: the order goes in through the inverse of pl.order, records and selected list come back through pl.order
     const bool cover = req.kind == kScoreCover;
     std::vector<uint32_t> where(cover ? P : 0), walk(cover ? req.cov_rule.n_order : 0), chosen(walk.size());
@@ -585,7 +617,8 @@ int score_run(const ScoreRequest &req)
         for (uint32_t k = 0; k < n_chosen; ++k) req.selected[k] = pl.order[chosen[k]];
         *req.cover_frame = cf; *req.n_selected = n_chosen;
     }
-    for (uint32_t j = 0; j < P; ++j) req.scores[pl.order[j]] = sc[j];
+    for (uint32_t j = 0; j < P && req.scores; ++j) req.scores[pl.order[j]] = sc[j];
+    for (uint32_t j = 0; j < ff.size(); ++j) { req.fit[pl.order[j]] = ff[j]; req.fit_info[pl.order[j]] = fi[j]; }
     for (uint32_t j = 0; j < cc.size(); ++j) req.contours[pl.order[j]] = cc[j];
     for (uint32_t j = 0; j < nn.size(); ++j) req.normals[pl.order[j]] = nn[j];
     if (req.overlap)                                             // rows and columns back into the caller's order
@@ -651,7 +684,7 @@ std::vector<pr_mat4> interleaved_pairs(const pr_mat4 *est, const pr_mat4 *gt, ui
     return out;
 }
 
-// the request of an entry point from what all ten have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
+// the request of an entry point from what all fourteen have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
 ScoreRequest score_request(const char *fn, ScoreKind kind, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, pr_roi roi,
                            const void *scene_dev, int depth_is_i32, int32_t tau, pr_pose_score *scores_host)
 {
@@ -1479,6 +1512,80 @@ int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
     r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
     r.jump = jump_mm; r.edge_dist = edge_dist_dev; r.contours = contours_host; r.overlap = overlap_host;
     return score_run(r);
+}
+
+int pr_scene_edge_nearest_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
+                              uint32_t *nearest_dev_out)
+{
+    PR_ENTER();
+    if (!scene_depth_dev || !nearest_dev_out || width == 0 || height == 0) { set_error("pr_scene_edge_nearest_dev: bad arguments"); return PR_ERR_INVALID; }
+    if (!frame_size_ok(width, height)) return PR_ERR_INVALID;
+    if (jump_mm < 0 || radius > PR_CONTOUR_MAX_RADIUS) {
+        set_error("pr_scene_edge_nearest_dev: jump_mm must be >= 0 and radius <= PR_CONTOUR_MAX_RADIUS = %d (got %d, %u)", PR_CONTOUR_MAX_RADIUS, (int)jump_mm, radius);
+        return PR_ERR_INVALID;
+    }
+    const size_t img = (size_t)width * height;
+    note_write(nearest_dev_out, sizeof(uint32_t) * img);
+    PR_TRY(g->edge_bits.ensure(sizeof(uint64_t) * (size_t)height * prk::overlap_words_per_row(width)));
+    PR_TRY(g->edge_rows.ensure(img));
+    HIP_TRY(prk::launch_scene_edge_nearest(scene_depth_dev, depth_is_i32 != 0, width, height, jump_mm, radius, g->edge_bits.as<unsigned long long>(),
+                                           g->edge_rows.as<int8_t>(), nearest_dev_out, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                      // synchronous like pr_scene_edge_distance_dev, and for its reasons
+    return PR_OK;
+}
+
+// pr_contour_information and its _multi form (multi: the mesh table instead of tris_dev, a centre and a radius per mesh): the checks that need no
+// request before any device is touched, the centres in the camera frame exactly as pr_pose_information forms them, then score_run
+static int contour_information_impl(ScoreRequest &r, int32_t jump_mm, const uint32_t *nearest_dev, const float K[9], const float *centers_model,
+                                    const float *radii, pr_contour_fit *fit_host, pr_pose_info *info_host)
+{
+    const char *fn = r.fn;
+    PR_TRY(fit_intrinsics_ok(fn, K));
+    const uint32_t n_centers = r.multi ? r.n_meshes : 1u;
+    if (!centers_model || !radii) { set_error("%s: bad arguments (a null centre or radius)", fn); return PR_ERR_INVALID; }
+    PR_TRY(info_center_radius_ok(fn, centers_model, radii, n_centers));
+    if (r.P && (!r.poses || (r.multi && !r.mesh_index))) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
+    if (r.multi) { MeshPlan pl; PR_TRY(plan_meshes(fn, r.meshes, r.n_meshes, r.mesh_index, r.P, pl)); }      // (the mesh table's checks; score_run plans again)
+    std::vector<prk::FitMeta> meta(r.P);
+    std::vector<float> centers(3 * (size_t)r.P), rad(r.P);
+    for (uint32_t j = 0; j < r.P; ++j) {
+        const uint32_t m = r.multi ? r.mesh_index[j] : 0u;
+        if (m >= n_centers) { set_error("%s: mesh_index[%u] = %u, but there are %u meshes", fn, j, m, n_centers); return PR_ERR_INVALID; }
+        const float *M = r.poses[j].m, *cm = centers_model + 3 * (size_t)m;
+        for (int a = 0; a < 3; ++a) {
+            const double v = (((double)M[4 * a] * (double)cm[0] + (double)M[4 * a + 1] * (double)cm[1]) + (double)M[4 * a + 2] * (double)cm[2]) + (double)M[4 * a + 3];
+            centers[3 * (size_t)j + a] = meta[j].c[a] = (float)(v / 1000.0);
+        }
+        rad[j] = meta[j].rho = radii[m];
+    }
+    PR_TRY(info_center_radius_ok(fn, centers.data(), rad.data(), r.P));      // (a pose with a non-finite entry)
+    r.jump = jump_mm; r.nearest = nearest_dev; r.K = K; r.fit_meta = meta.data(); r.fit = fit_host; r.fit_info = info_host;
+    PR_TRY(score_request_ok(r));                                    // every remaining check before the device is touched (score_run asks again)
+    if (r.P == 0) return PR_OK;
+    PR_ENTER();
+    return score_run(r);
+}
+
+int pr_contour_information(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                           const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, int32_t jump_mm,
+                           const uint32_t *nearest_dev, const float K[9], const float *center_model, float radius, pr_pose_score *scores_host_or_null,
+                           pr_contour_fit *fit_host, pr_pose_info *info_host)
+{
+    ScoreRequest r = score_request("pr_contour_information", kScoreContourFit, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm,
+                                   scores_host_or_null);
+    r.tris = tris_dev; r.n_tris = n_tris;
+    return contour_information_impl(r, jump_mm, nearest_dev, K, center_model, &radius, fit_host, info_host);
+}
+
+int pr_contour_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
+                                 uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm,
+                                 int32_t jump_mm, const uint32_t *nearest_dev, const float K[9], const float *centers_model, const float *radii,
+                                 pr_pose_score *scores_host_or_null, pr_contour_fit *fit_host, pr_pose_info *info_host)
+{
+    ScoreRequest r = score_request("pr_contour_information_multi", kScoreContourFit, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32,
+                                   tau_mm, scores_host_or_null);
+    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
+    return contour_information_impl(r, jump_mm, nearest_dev, K, centers_model, radii, fit_host, info_host);
 }
 
 int pr_score_normals(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

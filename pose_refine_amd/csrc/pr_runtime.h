@@ -26,6 +26,7 @@
 #include "pr_internal.h"
 #include "pr_tuning.h"
 #include "pose_box.h"
+#include "contour_fit.h"
 
 namespace prh {
 extern thread_local std::string g_err;
@@ -275,17 +276,18 @@ inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, 
 }
 // ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_cover, pr_score_contours, pr_score_normals, pr_compose_detections and their _multi forms) ----
 // What the caller asked for, as the entry point got it; score_run (pr_refine.cpp) takes it from there.  Every member is set by the entry point.
-enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose, kScoreCover };
+enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose, kScoreCover, kScoreContourFit };
 struct ScoreRequest {
     const char *fn; ScoreKind kind;                              // the entry point's name (for messages) and what it returns besides the scores
     const pr_triangle *tris; size_t n_tris;                      // one mesh for every hypothesis ...
     bool multi; const pr_mesh_ref *meshes; uint32_t n_meshes; const uint32_t *mesh_index;      // ... or (multi) a mesh table and every hypothesis' index into it
     const pr_mat4 *poses; uint32_t P, W, H; const pr_mat4 *proj; pr_roi roi;
     const void *scene; bool scene_i32; int32_t tau;
-    pr_pose_score *scores;                                       // host, P records
+    pr_pose_score *scores;                                       // host, P records (kScoreContourFit: may be null)
     uint32_t *overlap;                                           // host, P x P (kScoreOverlap: required; kScoreContours, kScoreNormals: null = none)
     int32_t jump; const uint8_t *edge_dist; pr_pose_contour *contours;                          // kScoreContours: device distance image in, P host records out
     const float *K; uint32_t step; float cos_min; pr_pose_normal *normals;                      // kScoreNormals (with jump): intrinsics and the estimator's step in, P host records out
+    const uint32_t *nearest; const prk::FitMeta *fit_meta; pr_contour_fit *fit; pr_pose_info *fit_info;      // kScoreContourFit (with jump and K): device nearest-edge map and P host centres (in the order of poses) in, P + P host records out
     uint16_t *labels_dev; int32_t *depth_dev; pr_pose_visible *visible; pr_frame_explained *frame;     // kScoreCompose: two optional device images, host records
     const uint32_t *cov_order; prk::CoverRule cov_rule; pr_pose_cover *cover; pr_cover_frame *cover_frame; uint32_t *selected, *n_selected;      // kScoreCover: the walk in (cov_rule.n_order indices), P + 1 host records and the selected list out
     const MeshPlan *plan; const uint32_t *order;                 // score_run's, null from the entry point: the grouped batch (position -> caller's index)
@@ -326,7 +328,15 @@ inline int normal_params_ok(const char *fn, uint32_t step, int32_t jump, float c
     if (!(cos_min >= 0.0f && cos_min <= 1.0f)) { set_error("%s: cos_min must lie in [0, 1] (got %g)", fn, (double)cos_min); return PR_ERR_INVALID; }      // (a NaN fails both)
     return PR_OK;
 }
-// Every check of a request that needs no device, in one order for all twelve entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
+// pr_contour_information's own condition on K (its entry points ask before any device use as well)
+inline int fit_intrinsics_ok(const char *fn, const float *K)
+{
+    if (!K) { set_error("%s: bad arguments (K is null)", fn); return PR_ERR_INVALID; }
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(K[i])) { set_error("%s: K[%d] is not finite", fn, i); return PR_ERR_INVALID; }
+    if (K[0] == 0.0f || K[4] == 0.0f) { set_error("%s: K[0] and K[4] must not be 0", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+// Every check of a request that needs no device, in one order for all fourteen entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
 // call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.  A request without hypotheses needs no arrays.
 inline int score_request_ok(const ScoreRequest &r)
 {
@@ -335,13 +345,16 @@ inline int score_request_ok(const ScoreRequest &r)
     if (r.kind == kScoreCompose) PR_TRY(compose_args_ok(fn, r.P));
     if (r.kind == kScoreCover) PR_TRY(cover_args_ok(r));
     if (r.tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)r.tau); return PR_ERR_INVALID; }
-    if (!r.proj || r.W == 0 || r.H == 0 || (r.P && (!r.poses || !r.scene || !r.scores || (!r.multi && !r.tris && r.n_tris > 0)))) {
+    if (!r.proj || r.W == 0 || r.H == 0 || (r.P && (!r.poses || !r.scene || (!r.scores && r.kind != kScoreContourFit) || (!r.multi && !r.tris && r.n_tris > 0)))) {
         set_error("%s: bad arguments", fn); return PR_ERR_INVALID;
     }
     if (!frame_size_ok(r.W, r.H)) return PR_ERR_INVALID;
     if (!roi_ok(r.roi, r.W, r.H)) { set_error("%s: roi out of image", fn); return PR_ERR_INVALID; }      // renderer.cu:202-203 asserts
     if (r.kind == kScoreContours && r.jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)r.jump); return PR_ERR_INVALID; }
     if (r.kind == kScoreContours && r.P && (!r.edge_dist || !r.contours)) { set_error("%s: bad arguments (edge_dist_dev or contours_host is null)", fn); return PR_ERR_INVALID; }
+    if (r.kind == kScoreContourFit && r.jump < 0) { set_error("%s: jump_mm must be >= 0 (got %d)", fn, (int)r.jump); return PR_ERR_INVALID; }
+    if (r.kind == kScoreContourFit && r.P && (!r.nearest || !r.fit || !r.fit_info || !r.fit_meta)) { set_error("%s: bad arguments (nearest_dev, fit_host or info_host is null)", fn); return PR_ERR_INVALID; }
+    if (r.kind == kScoreContourFit) PR_TRY(fit_intrinsics_ok(fn, r.K));
     if (r.kind == kScoreNormals) PR_TRY(normal_params_ok(fn, r.step, r.jump, r.cos_min));
     if (r.kind == kScoreNormals && r.P && (!r.K || !r.normals)) { set_error("%s: bad arguments (K or normals_host is null)", fn); return PR_ERR_INVALID; }
     if (r.kind == kScoreCompose && r.P && (!r.visible || !r.frame)) { set_error("%s: bad arguments (visible_host or frame_host is null)", fn); return PR_ERR_INVALID; }

@@ -1,4 +1,4 @@
-// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, cover.hip, contour.hip, normals.hip, compose.hip, vsd.hip and nobody else): the workgroup's
+// score_walk.h -- what the kernels of the scoring path share (verify.hip, select.hip, cover.hip, contour.hip, contour_fit.hip, normals.hip, compose.hip, vsd.hip and nobody else): the workgroup's
 // part of a hypothesis' pixel box, the test of a rendered depth against the scene, the sum of a workgroup's counters, the launchers' loop
 // gfx950 (CDNA4, wave64); integer arithmetic only, differences in 64 bits: every value is bit-identical to the CPU restatement.
 #pragma once
@@ -41,6 +41,15 @@ __device__ __forceinline__ uint32_t depth_class(int32_t d, int32_t s, int64_t ta
     if (s <= 0) return 3;
     const int64_t diff = (int64_t)d - (int64_t)s;                     // 64 bits: no overflow for any int32 pair
     return diff > tau ? 1u : (diff < -tau ? 2u : 0u);
+}
+
+// ---- the edge rule of the contour check and the contour fit (contour.hip, contour_fit.hip), on normalised values: c > 0 is the pixel's depth; a
+// neighbour is 0 when it is empty (no surface: infinitely far), its depth when it has one, and kNoNeighbour when it lies outside the image
+// (ignored: an object cut by the border has no contour there).
+constexpr int32_t kNoNeighbour = -1;
+__device__ __forceinline__ bool edge_trigger(int32_t c, int32_t n, int64_t jump)
+{
+    return n == 0 || (n > 0 && (int64_t)n - (int64_t)c > jump);     // 64 bits: no overflow for any int32 pair
 }
 
 // ---- the reduction: N counters per lane -> a wave sum each, the four wavefronts' sums through LDS, one barrier.  Every thread of the 256-thread

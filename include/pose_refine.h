@@ -924,6 +924,10 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *                              list of the buffer's distinct vertices, made and checked with the ordered copy; 16 bytes per distinct vertex) instead of
  *                              the hull of the projected corners of the mesh's box; 0 = the latter.  Same results either way
  *                              ("stat_tight_batches", read-only: asynchronous batches of this process that ran on tight boxes)
+ *   "box_bands"        [1]     asynchronous path: a hypothesis' depth box interleaves four image rows column by column, so that a 64-byte segment
+ *                              holds a 4x4-pixel patch and the raster's depth atomics make fewer requests; 0 = row-major boxes.  Same results either
+ *                              way ("stat_band_batches", read-only: asynchronous batches of this process that ran on banded boxes; "box_pack",
+ *                              read-only: the ints a box's slot is rounded up to)
  *   "nn_stack"         [1]     kd-tree query: per-lane LDS stack (1) or the reference's stackless walk (0)
  *   "nn_compact"       [1]     stack query on 32-byte node records with 16-bit outward-rounded boxes (0: exact 64-byte records)
  *   "host_worker"      [1]     host solve: a batch given to pr_refine_submit runs on a library-owned helper thread of its slot (private context: its own
@@ -1018,6 +1022,13 @@ int  pr_debug_mesh_fingerprint(const pr_triangle *tris_host, size_t n_tris, uint
  * for the host: a vertex at or behind the camera plane (z <= 1e-3) or a non-finite coordinate leaves the loose box. */
 int  pr_debug_tight_box(const pr_triangle *tris_host, size_t n_tris, const pr_mat4 *pose, const pr_mat4 *proj, uint32_t width, uint32_t height,
                         pr_roi roi, int32_t box_out[4], int32_t loose_out[4]);
+/* Audit entry (no device needed) for the layout of a depth box in the asynchronous path's workspace (option "box_bands"): *slot_out = the ints
+ * the pixel box `box` ({x0, y0, x1, y1}, raster coordinates, inclusive; inside a width x height frame, or empty) occupies, rounded up as the
+ * packed layout rounds it (0 for an empty box), and offsets_out[i] = the int offset, from the start of that slot, of pixel (xs[i], image row
+ * rows[i]) -- which must lie inside the box.  bands != 0: four consecutive image rows interleaved column by column, bands aligned to image rows;
+ * 0: row-major, pitch = the box's width.  The same source as the kernels that fill, raster, count and emit a box, compiled for the host. */
+int  pr_debug_box_layout(const int32_t box[4], uint32_t width, uint32_t height, int bands, const int32_t *xs, const int32_t *rows, size_t n,
+                         uint32_t *slot_out, uint32_t *offsets_out);
 /* Audit entry: the bytes the kd-tree searches would read for `scene` -- the traversal data the library derives from the caller's nodes and
  * points, copied to the host.  The scene is resolved exactly as an ICP call resolves it (the same cache sets, the same waiting for a batch
  * in flight that reads a set about to be rebuilt, the same rounds of wide levels): a read neither rebuilds what a search would have

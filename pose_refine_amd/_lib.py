@@ -251,6 +251,7 @@ SIGNATURES = {
     "pr_debug_mesh_order": (_i32, [_vp, _sz, _vp]),
     "pr_debug_mesh_fingerprint": (_i32, [_vp, _sz, C.POINTER(C.c_uint64)]),
     "pr_debug_tight_box": (_i32, [_vp, _sz, _vp, _vp, _u32, _u32, Roi, _vp, _vp]),
+    "pr_debug_box_layout": (_i32, [_vp, _u32, _u32, _i32, _vp, _vp, _sz, _vp, _vp]),
     "pr_debug_nn_records": (_i32, [_vp, _u32, _u32, _vp, C.POINTER(NNRecordsCounts), C.POINTER(NNRecordsOut)]),
     "pr_stats": (_i32, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }

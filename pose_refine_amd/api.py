@@ -178,6 +178,21 @@ def tight_box(tris, pose, width: int, height: int, proj, roi: Sequence[int] = (0
     return tight, loose
 
 
+def box_layout(box, width: int, height: int, bands: bool, xs=(), rows=()):
+    """``pr_debug_box_layout``: (slot ints, offsets) of the depth box ``[x0, y0, x1, y1]`` (raster coordinates, inclusive) of a width x height
+    frame in the asynchronous path's workspace, banded (four image rows interleaved) or row-major; offsets (uint32) of the pixels
+    (xs[i], image row rows[i]) from the start of the slot.  No device needed."""
+    b = np.ascontiguousarray(box, dtype=np.int32).reshape(4)
+    x = np.ascontiguousarray(xs, dtype=np.int32).reshape(-1)
+    r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    if len(x) != len(r):
+        raise ValueError("xs and rows differ in length")
+    slot, off = C.c_uint32(), np.empty(len(x), np.uint32)
+    check(_lib.load().pr_debug_box_layout(b.ctypes.data, width, height, 1 if bands else 0, x.ctypes.data, r.ctypes.data, len(x),
+                                          C.byref(slot), off.ctypes.data))
+    return slot.value, off
+
+
 def gather_profile():
     """HIP-event time of the gathers issued while option ``profile`` was on: (total ms, count).  Waits for the library stream."""
     ms, n = C.c_double(), C.c_uint64()

@@ -49,6 +49,57 @@ __global__ __launch_bounds__(256) void d2c_emit_box_kernel(const int32_t *__rest
     }
 }
 
+// The same emit from BANDED boxes (pose_box.h, band_box; asynchronous fused path, option box_bands): same grid, a wavefront's four aligned rows
+// are one band.  A lane loads 16-byte words -- a column of the band, its four rows -- four in flight; then, row by row, the ballot / prefix code of
+// the kernel above places the points: ascending row, ascending x, the same backproject_pixel, so a cloud is the same bytes in the same order.
+// Rows of the band outside the box (or past the frame: their row_count / row_off are not read) hold the fill value and emit nothing.
+__global__ __launch_bounds__(256) void d2c_emit_band_kernel(const int32_t *__restrict__ depth, uint32_t height, const int4 *__restrict__ bbox,
+                                                            float fx, float fy, float cx, float cy, const uint32_t *__restrict__ row_count,
+                                                            const uint32_t *__restrict__ row_off, pr_vec3 *__restrict__ cloud,
+                                                            const PoseMeta *__restrict__ meta, const uint32_t *__restrict__ box_off)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const int4 bb = bbox[blockIdx.y];
+    const BandBox k = band_box(bb, height);
+    const uint32_t row0 = blockIdx.x * kBoxRowsPerBlock + (threadIdx.x >> 6) * 4;
+    if (row0 >= height) return;
+    const uint32_t band = (row0 >> 2) - (uint32_t)(k.R >> 2);       // (wraps for a band above the box: not live)
+    if (k.nb == 0 || row0 < (uint32_t)k.R || band >= k.nb) return;
+    pr_vec3 *out[4];
+    uint32_t any = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const bool in = row0 + r < height;
+        const size_t ri = (size_t)blockIdx.y * height + (in ? row0 + r : row0);
+        any |= in ? row_count[ri] : 0u;
+        out[r] = cloud + (size_t)meta[blockIdx.y].start + row_off[ri];
+    }
+    if (any == 0) return;                                            // wave-uniform: an empty band costs its four counts
+    const int4 *line = reinterpret_cast<const int4 *>(depth + box_off[blockIdx.y]) + (size_t)band * (uint32_t)k.w;
+    uint32_t done[4] = { 0, 0, 0, 0 };
+    for (int c0 = 0; c0 < k.w; c0 += 256) {
+        int4 dv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dv[j] = line[min(c0 + 64 * j + (int)lane, k.w - 1)];          // (a lane past the end re-reads the last column: unconditional loads stay in flight together)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = bb.x + c0 + 64 * j + (int)lane;
+            const int32_t d4[4] = { dv[j].x, dv[j].y, dv[j].z, dv[j].w };
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) {
+                const int32_t d = d4[r];
+                const bool v = x <= bb.z && d > 0 && d != INT_MAX;
+                const unsigned long long m = __ballot(v);
+                if (v) {
+                    const uint32_t i = done[r] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                    out[r][i] = backproject_pixel(x, row0 + r, d, fx, fy, cx, cy);
+                }
+                done[r] += (uint32_t)__popcll(m);
+            }
+        }
+    }
+}
+
 // ================================================================================================
 //  depth -> cloud: count per row, scan rows per image, emit in row-major order
 // ================================================================================================
@@ -165,11 +216,17 @@ __global__ __launch_bounds__(256) void d2c_emit_kernel(const T *__restrict__ dep
 
 hipError_t launch_emit_box(const int32_t *depth, uint32_t n_poses, uint32_t width, uint32_t height, const int4 *bbox, float fx, float fy,
                            float cx, float cy, const uint32_t *row_count, const uint32_t *row_off, pr_vec3 *cloud, const PoseMeta *meta,
-                           hipStream_t s, const uint32_t *box_off)
+                           hipStream_t s, const uint32_t *box_off, bool bands)
 {
     if (n_poses == 0) return hipSuccess;
+    if (bands && !box_off) return hipErrorInvalidValue;
     for (uint32_t i0 = 0; i0 < n_poses; i0 += 32768) {
         const uint32_t ni = (n_poses - i0 < 32768) ? (n_poses - i0) : 32768;
+        if (bands) {
+            hipLaunchKernelGGL(d2c_emit_band_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, ni), dim3(256), 0, s, depth, height, bbox + i0,
+                               fx, fy, cx, cy, row_count + (size_t)i0 * height, row_off + (size_t)i0 * height, cloud, meta + i0, box_off + i0);
+            continue;
+        }
         hipLaunchKernelGGL(d2c_emit_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, ni), dim3(256), 0, s, box_off ? depth : depth + (size_t)i0 * width * height, width, height,
                            bbox + i0, fx, fy, cx, cy, row_count + (size_t)i0 * height, row_off + (size_t)i0 * height,
                            cloud, meta + i0, box_off ? box_off + i0 : nullptr);

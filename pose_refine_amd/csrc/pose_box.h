@@ -5,11 +5,13 @@
 #pragma once
 #include <float.h>
 #include <math.h>
+#include <stddef.h>
 
 #include "pr_internal.h"
 
 #ifndef PR_HD
 #define PR_HD
+#define PR_HD_HOST_ONLY 1                                            // (a host translation unit: no device intrinsics below, even in its device pass)
 #endif
 
 namespace prk {
@@ -62,6 +64,58 @@ PR_HD inline uint32_t box_area(const int4 b)
 }
 PR_HD inline uint32_t box_slot(uint32_t area) { return (area + (kBoxPack - 1u)) & ~(kBoxPack - 1u); }
 PR_HD inline uint32_t cloud_slot(uint32_t count) { return (count + (kCloudAlign - 1u)) & ~(kCloudAlign - 1u); }
+
+// ---- the BANDED layout of a depth box (asynchronous fused path, option box_bands): four consecutive image rows interleaved column by column, so
+// that a 64-byte segment holds a 4x4-pixel patch instead of 16 pixels of one row -- the raster's depth atomics cost one request per distinct
+// segment a wave instruction addresses, and the ~30 small triangles a wavefront drains together cover a patch a few pixels high.  Bands are
+// aligned to IMAGE rows (multiples of 4: a wavefront of the box walks owns exactly one), not to the box: box `b` (inclusive, raster y) of a
+// frame `height` rows high has image rows r0 = height - 1 - b.w .. r1 = height - 1 - b.y, its first band starts at R = r0 & ~3 and it has
+// nb = ((r1 | 3) - R + 1) / 4 bands of 4 * w ints, w = its width (no padding).  The up to 3 + 3 rows of the first and last band that lie outside the
+// box hold "nothing drawn" like any pixel no fragment reached, and no fragment addresses them.
+//   Capacity: R >= 0 and (r1 | 3) + 1 <= (height + 3) & ~3, so a box never needs more than width * ((height + 3) & ~3) ints (+ kBoxPack of rounding:
+// the workspace bound per hypothesis).  A box inside another (the tight box inside the loose one) has r0' >= r0, r1' <= r1, hence R' >= R,
+// (r1' | 3) <= (r1 | 3) and nb' <= nb, with w' <= w: its slot is never larger, so every offset and capacity derived from the loose boxes holds.
+struct BandBox { int w, r0, R; uint32_t nb; };                       // (an empty or inverted box: w = 0, nb = 0)
+PR_HD inline BandBox band_box(const int4 b, uint32_t height)
+{
+    BandBox k{ 0, 0, 0, 0u };
+    const int w = b.z - b.x + 1, h = b.w - b.y + 1;
+    if (w <= 0 || h <= 0) return k;
+    const int r1 = (int)height - 1 - b.y;
+    k.w = w; k.r0 = (int)height - 1 - b.w; k.R = k.r0 & ~3;
+    k.nb = (uint32_t)(((r1 | 3) - k.R + 1) / 4);
+    return k;
+}
+// ints a box occupies before rounding, in either layout, and its slot
+PR_HD inline uint32_t box_ints(const int4 b, uint32_t height, bool bands)
+{
+    if (!bands) return box_area(b);
+    const BandBox k = band_box(b, height);
+    return 4u * (uint32_t)k.w * k.nb;
+}
+PR_HD inline uint32_t box_slot_of(const int4 b, uint32_t height, bool bands) { return box_slot(box_ints(b, height, bands)); }
+// The constant part of a banded address: pixel (x, image row r) of box `b` lives at band_origin + band_index(w, x, r) ints from the box's
+// offset -- i.e. at (((r >> 2) - (R >> 2)) * w + (x - b.x)) * 4 + (r & 3).  The raster folds offset + origin into one scalar base.
+PR_HD inline ptrdiff_t band_origin(const BandBox &k, const int4 b) { return -(((ptrdiff_t)(k.R >> 2) * k.w + b.x) * 4); }
+PR_HD inline uint32_t band_index(uint32_t w, uint32_t x, uint32_t r)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PR_HD_HOST_ONLY)
+    return ((__umul24(r >> 2, w) + x) << 2) | (r & 3u);          // a frame side is at most 8192 (frame_size_ok): exact, and full rate where v_mul_lo_u32 is a quarter
+#else
+    return (((r >> 2) * w + x) << 2) | (r & 3u);
+#endif
+}
+PR_HD inline uint32_t band_pixel_offset(const int4 b, uint32_t height, int x, int r)
+{
+    const BandBox k = band_box(b, height);
+    return (uint32_t)(band_origin(k, b) + (ptrdiff_t)band_index((uint32_t)k.w, (uint32_t)x, (uint32_t)r));
+}
+// the same for the row-major box (box_line, pr_device.h): pitch = the box's width, origin at its top-left pixel
+PR_HD inline uint32_t row_pixel_offset(const int4 b, uint32_t height, int x, int r)
+{
+    const int w = b.z - b.x + 1;
+    return (uint32_t)((r - ((int)height - 1 - b.w)) * (w > 0 ? w : 0) + (x - b.x));
+}
 
 // One vertex to the screen: model transform (renderer.h:296-303 mat_mul_v, rows a,b,c), projection rows 0 and 1 (only x and y of the result are
 // used downstream), viewport (renderer.cu:90-98).  THE definition: the raster's triangle setup and the tight pixel box (below) both call it, so with

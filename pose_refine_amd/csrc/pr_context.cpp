@@ -55,6 +55,7 @@ void trace_mark(const char *tag)
 WriteLog g_writes;
 std::atomic<uint64_t> g_flag_overtook{ 0 };
 std::atomic<uint64_t> g_tight_batches{ 0 };
+std::atomic<uint64_t> g_band_batches{ 0 };
 Options opt;
 std::mutex g_reg_mu;
 std::vector<Ctx *> g_shared;         // index = device ordinal
@@ -310,6 +311,7 @@ int pr_set_option(const char *name, int value)
     else if (n == "eager_streams") opt.eager_streams = value ? 1 : 0;
     else if (n == "mesh_order") opt.mesh_order = value ? 1 : 0;
     else if (n == "tight_box") opt.tight_box = value ? 1 : 0;
+    else if (n == "box_bands") opt.box_bands = value ? 1 : 0;
     else if (n == "raster_mode") { if (value < 0 || value > 1) { set_error("raster_mode must be 0 or 1"); return PR_ERR_INVALID; } opt.raster_mode = value; }
     else { set_error("unknown option %s", name); return PR_ERR_INVALID; }
     return PR_OK;
@@ -341,10 +343,13 @@ int pr_get_option(const char *name, int *value)
     else if (n == "host_poll") *value = opt.host_poll;
     else if (n == "stat_flag_overtook") *value = (int)std::min<uint64_t>(g_flag_overtook.load(), 0x7fffffffull);   // read-only
     else if (n == "stat_tight_batches") *value = (int)std::min<uint64_t>(g_tight_batches.load(), 0x7fffffffull);   // read-only
+    else if (n == "box_pack") *value = (int)prk::kBoxPack;                                                                         // read-only
     else if (n == "pose_dist_chunk") *value = (int)prk::kPoseDistChunk;                                                           // read-only
     else if (n == "raster_mode") *value = opt.raster_mode;
     else if (n == "mesh_order") *value = opt.mesh_order;
     else if (n == "tight_box") *value = opt.tight_box;
+    else if (n == "box_bands") *value = opt.box_bands;
+    else if (n == "stat_band_batches") *value = (int)std::min<uint64_t>(g_band_batches.load(), 0x7fffffffull);     // read-only
     else if (n == "eager_streams") *value = opt.eager_streams;
     else if (n == "graph") *value = opt.use_graph;
     else if (n == "fused_solve") *value = opt.fused_solve;

@@ -829,6 +829,21 @@ int pr_debug_tight_box(const pr_triangle *tris_host, size_t n_tris, const pr_mat
     if (loose_out) { loose_out[0] = loose.x; loose_out[1] = loose.y; loose_out[2] = loose.z; loose_out[3] = loose.w; }
     return PR_OK;
 }
+int pr_debug_box_layout(const int32_t box[4], uint32_t width, uint32_t height, int bands, const int32_t *xs, const int32_t *rows, size_t n,
+                        uint32_t *slot_out, uint32_t *offsets_out)
+{
+    if (!box || !slot_out || (n && (!xs || !rows || !offsets_out))) { prh::set_error("pr_debug_box_layout: null argument"); return PR_ERR_INVALID; }
+    const int4 b = make_int4(box[0], box[1], box[2], box[3]);
+    const bool empty = b.z < b.x || b.w < b.y;
+    if (!empty && (b.x < 0 || b.y < 0 || b.z >= (int)width || b.w >= (int)height)) { prh::set_error("pr_debug_box_layout: the box leaves the frame"); return PR_ERR_INVALID; }
+    *slot_out = prk::box_slot_of(b, height, bands != 0);
+    for (size_t i = 0; i < n; ++i) {
+        const int ry = (int)height - 1 - rows[i];                    // raster row of the image row
+        if (empty || xs[i] < b.x || xs[i] > b.z || ry < b.y || ry > b.w) { prh::set_error("pr_debug_box_layout: pixel %zu lies outside the box", i); return PR_ERR_INVALID; }
+        offsets_out[i] = bands ? prk::band_pixel_offset(b, height, xs[i], rows[i]) : prk::row_pixel_offset(b, height, xs[i], rows[i]);
+    }
+    return PR_OK;
+}
 int pr_debug_mesh_fingerprint(const pr_triangle *tris_host, size_t n_tris, uint64_t *fingerprint_out)
 {
     if ((n_tris && !tris_host) || !fingerprint_out) { prh::set_error("pr_debug_mesh_fingerprint: null buffer"); return PR_ERR_INVALID; }

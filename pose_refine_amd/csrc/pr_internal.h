@@ -190,12 +190,13 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
                                uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s, bool compute_boxes = true,
                                PoseMeta *meta = nullptr, DevIcpState *st = nullptr, uint32_t *arrive = nullptr,
                                const uint32_t *box_off = nullptr,    // box_off: the boxes packed into `depth` at these offsets (ints), each with its own pitch (fill_box_kernel)
-                               const BatchCheck *check = nullptr);
+                               const BatchCheck *check = nullptr,
+                               bool bands = false);                  // bands (with box_off, compute_boxes = false): the boxes in the banded layout of pose_box.h (band_box), placed by box_slot_of -- fill, raster and count then address that layout, and so must launch_emit_box
 // Asynchronous path, option tight_box (pose_tight_box_kernel): bbox[i], the loose box the host uploaded, overwritten by its intersection with the
 // hull of the projected vertices `verts` ({x, y, z, 0}: the mesh's distinct vertices); then, per sub-batch, the packed offsets of those boxes.
 hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_mat4 *poses_dev, uint32_t n_poses, const pr_mat4 &proj,
                               uint32_t width, uint32_t height, int4 *bbox, hipStream_t s);
-hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, hipStream_t s);
+hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, uint32_t height, bool bands, hipStream_t s);
 // Mixed batches (pr_*_multi): the hypotheses grouped by mesh.  One group of consecutive hypotheses [first, first + count) of a launch that share
 // a mesh; raster_multi_kernel's workgroups [first_wg, first_wg + tri_blocks * ceil(count / run)) are its (triangle block, pose run) pairs.
 // The host fills tris, n_tris, first and count; launch_raster_multi the rest.  48 bytes: staged in 16-byte words.
@@ -302,7 +303,7 @@ hipError_t launch_copy_words32(const void *src, void *dst, uint32_t n_words, hip
 hipError_t launch_d2c_pack_starts(const uint32_t *counts, uint32_t n, PoseMeta *meta, hipStream_t s);
 hipError_t launch_emit_box(const int32_t *depth, uint32_t n_poses, uint32_t width, uint32_t height, const int4 *bbox, float fx, float fy,
                            float cx, float cy, const uint32_t *row_count, const uint32_t *row_off, pr_vec3 *cloud, const PoseMeta *meta,
-                           hipStream_t s, const uint32_t *box_off = nullptr);     // cloud i starts at meta[i].start (packed: launch_render_boxes or launch_d2c_pack_starts wrote it)
+                           hipStream_t s, const uint32_t *box_off = nullptr, bool bands = false);     // bands: as launch_render_boxes. cloud i starts at meta[i].start (packed: launch_render_boxes or launch_d2c_pack_starts wrote it)
 
 // pyramid.hip (pr_refine_pyramid): the strided level clouds of the hypotheses of a chunk, from the depth boxes launch_render_boxes left.
 // PyramidStrides: the levels' strides (unused entries 1).  PyramidCarry: what the emit of ONE level needs per hypothesis -- rows 0..2 of the transform

@@ -1051,7 +1051,7 @@ struct AsyncBatch {
     SceneSel sc; AsyncPlan pl{}; NNLayout nl{}; prk::BatchCheck chk{};
     uint32_t *nn_prev = nullptr;                                  // kd-tree scene: the search workspace (nn_layout), or null
     pr_result *dres = nullptr;
-    bool timed = false, tight = false, pipeline_start = true;
+    bool timed = false, tight = false, bands = false, pipeline_start = true;
     pr_mat4 *d_poses = nullptr; int4 *d_box = nullptr; uint32_t *d_off = nullptr;      // SlotIn on the device
     const pr_triangle *raster_tris = nullptr;
     int workspaces(); int stage(); int sub_batch(uint32_t q0, uint32_t nq);
@@ -1060,7 +1060,7 @@ struct AsyncBatch {
 int AsyncBatch::workspaces()
 {
     const uint32_t sub = pl.sub;
-    PR_TRY(sl.depth.ensure(sizeof(int32_t) * ((size_t)job.W * job.H + prk::kBoxPack) * sub));
+    PR_TRY(sl.depth.ensure(sizeof(int32_t) * depth_ints_per_pose(job.W, job.H, bands) * sub));
     PR_TRY(sl.row_count.ensure(sizeof(uint32_t) * (size_t)job.H * sub));
     PR_TRY(sl.row_off.ensure(sizeof(uint32_t) * (size_t)job.H * sub));
     PR_TRY(sl.counts.ensure(sizeof(uint32_t) * P));
@@ -1127,13 +1127,13 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
     // `exact` flag / tree depth back before it returns, so a rebuild has finished on the host's clock before the render is even enqueued; on a
     // cache hit the event is complete when recorded)
     if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
-    if (tight) HIP_TRY(prk::launch_box_pack_offsets(d_box + q0, nq, d_off + q0, st));
+    if (tight) HIP_TRY(prk::launch_box_pack_offsets(d_box + q0, nq, d_off + q0, H, bands, st));
     HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)job.n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
                                      sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, job.proj, none, st,
-                                     /*compute_boxes=*/false, meta, dstate, arrive, d_off + q0, q0 == 0 ? &chk : nullptr));
+                                     /*compute_boxes=*/false, meta, dstate, arrive, d_off + q0, q0 == 0 ? &chk : nullptr, bands));
     if (timed) { sl.spans.end(te, kSpanRender, q0, nq, false, st); te = sl.spans.begin(st); }
     HIP_TRY(prk::launch_emit_box(sl.depth.as<int32_t>(), nq, W, H, d_box + q0, K[0], K[4], K[2], K[5], sl.row_count.as<uint32_t>(),
-                                 sl.row_off.as<uint32_t>(), sl.cloud.as<pr_vec3>(), meta, st, d_off + q0));
+                                 sl.row_off.as<uint32_t>(), sl.cloud.as<pr_vec3>(), meta, st, d_off + q0, bands));
     if (timed) sl.spans.end(te, kSpanCloud, q0, nq, false, st);
     if (timed && q0 == 0)                                     // the timed loop starts when the other slot's batch is complete
         for (Slot &o : g->slots) if (&o != &sl && o.pending && !o.delivered && o.done) HIP_TRY(hipStreamWaitEvent(st, o.done, 0));
@@ -1192,7 +1192,11 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
     const pr_mat4 *h_poses = sl.h_in.as<pr_mat4>();
     int4 *h_box = reinterpret_cast<int4 *>(sl.h_in.as<unsigned char>() + in.box);
     for (uint32_t i = 0; i < P; ++i) h_box[i] = prk::pose_pixel_box(g->aabb_host, h_poses[i].m, job.proj, job.W, job.H, job.roi);
-    a.pl = plan_async(P, job.W, job.H, h_box, opt.steps, opt.sub_batch, g->cloud_hint, reinterpret_cast<uint32_t *>(sl.h_in.as<unsigned char>() + in.off));
+    // Option box_bands: the depth boxes of this batch interleave four image rows (pose_box.h, band_box) -- the plan places them, fill, raster, count and
+    // emit address them; private to this path, every output the same bytes as with row-major boxes
+    a.bands = opt.box_bands != 0;
+    if (a.bands) g_band_batches.fetch_add(1);
+    a.pl = plan_async(P, job.W, job.H, h_box, opt.steps, opt.sub_batch, g->cloud_hint, reinterpret_cast<uint32_t *>(sl.h_in.as<unsigned char>() + in.off), a.bands);
     PR_TRY(a.workspaces());
 
     // A TIMED batch (profile 3) stays asynchronous: its render runs under the other slot's loop like any other, but its own loop waits

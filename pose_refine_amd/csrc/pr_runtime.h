@@ -123,6 +123,7 @@ struct WriteLog {
 };
 extern WriteLog g_writes;
 extern std::atomic<uint64_t> g_tight_batches;     // asynchronous batches whose pixel boxes came from pose_tight_box_kernel (process-wide; read-only option "stat_tight_batches": tests tell the tight path from the loose one by it)
+extern std::atomic<uint64_t> g_band_batches;      // asynchronous batches whose depth boxes were banded (option box_bands; read-only option "stat_band_batches": tests tell the banded path from the row-major one by it)
 extern std::atomic<uint64_t> g_flag_overtook;     // PR_SOLVE_HOST: group flags that reached the host before all of their rows (process-wide; expected 0; read-only option "stat_flag_overtook")
 
 // ---- process-wide options (pr_set_option): plain ints, shared by every context ---------------------
@@ -163,6 +164,7 @@ struct Options {
     int raster_mode = 0;             // fused path: 0 = global atomicMin inside the per-pose pixel box (reference scheme), 1 = LDS depth bands (int32); pr_set_option refuses anything else
     int mesh_order = 1;              // asynchronous fused path: raster the library's spatially ordered copy of the triangle buffer (ensure_model_box); 0 = the caller's buffer
     int tight_box = 1;               // asynchronous fused path: pixel boxes from the mesh's projected vertices (pose_tight_box_kernel over the library's list of distinct vertices, ensure_model_box) instead of the projected corners of its box; 0 = the latter
+    int box_bands = 1;               // asynchronous fused path: a hypothesis' depth box interleaves four image rows column by column (pose_box.h, band_box: a 64-byte segment is a 4x4-pixel patch, fewer atomic requests per raster wave instruction); 0 = row-major boxes.  Same results either way
     int scene_cache = 1;             // keep the packed projective scene / kd traversal records of the latest scene between calls (pr_scene_invalidate)
 };
 extern Options opt;
@@ -449,12 +451,15 @@ struct AsyncPlan {
     uint32_t steps, nblk, grid_x;    // 1024-point steps per workgroup; blocks a hypothesis may have (capacity of the partial sums); workgroups per hypothesis
     uint32_t sub, n_sub;             // hypotheses per sub-batch, sub-batches
 };
+// the depth workspace's bound per hypothesis, in ints: a full-frame box and its rounding (banded boxes: the height rounded up to whole bands, pose_box.h "Capacity")
+inline size_t depth_ints_per_pose(uint32_t W, uint32_t H, bool bands) { return (size_t)W * (bands ? (((size_t)H + 3) & ~(size_t)3) : (size_t)H) + prk::kBoxPack; }
 // boxes: the P host-computed pixel boxes; box_off (P words out): box i at box_off[i] ints of its sub-batch's depth workspace, its own width as
-// pitch (fill_box_kernel) -- the offsets restart at every sub-batch
-inline AsyncPlan plan_async(uint32_t P, uint32_t W, uint32_t H, const int4 *boxes, int opt_steps, int opt_sub_batch, uint32_t cloud_hint, uint32_t *box_off)
+// pitch (fill_box_kernel), or -- bands -- in the banded layout of pose_box.h (band_box) -- the offsets restart at every sub-batch
+inline AsyncPlan plan_async(uint32_t P, uint32_t W, uint32_t H, const int4 *boxes, int opt_steps, int opt_sub_batch, uint32_t cloud_hint, uint32_t *box_off,
+                            bool bands = false)
 {
     AsyncPlan pl{};
-    const size_t img = (size_t)W * H;
+    const size_t img = depth_ints_per_pose(W, H, bands) - prk::kBoxPack;
     pl.max_area = 1;
     for (uint32_t i = 0; i < P; ++i) pl.max_area = std::max<size_t>(pl.max_area, prk::box_area(boxes[i]));   // an off-screen pose has an empty box
     // capacity per hypothesis (a multiple of the packing's alignment, so that no sum of rounded sizes exceeds P x cstride)
@@ -479,7 +484,7 @@ inline AsyncPlan plan_async(uint32_t P, uint32_t W, uint32_t H, const int4 *boxe
     for (uint32_t i = 0; i < P; ++i) {
         if (i % pl.sub == 0) acc = 0;
         box_off[i] = (uint32_t)acc;
-        acc += prk::box_slot(prk::box_area(boxes[i]));
+        acc += prk::box_slot_of(boxes[i], H, bands);
     }
     return pl;
 }

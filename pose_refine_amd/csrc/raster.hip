@@ -288,7 +288,9 @@ __device__ __forceinline__ void load_triangle(const pr_triangle *__restrict__ tr
 
 // What one raster workgroup does with its 256 triangles (tv, lane triangle ti of n_tris): hypotheses [run * pose_run, +pose_run) of the
 // n_poses at `poses`.  Image of hypothesis `by`: depth + image_of[by] * rw * rh when image_of is given (the caller's order of a mixed
-// batch), depth + by * rw * rh otherwise; packed boxes (box_off): their own pitch.
+// batch), depth + by * rw * rh otherwise; packed boxes (box_off): their own pitch, or -- kBands, the asynchronous fused path's option box_bands --
+// the banded layout of pose_box.h (band_box), whose per-hypothesis constants are folded into the base as the row-major origin is.
+template <bool kBands>
 __device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, uint32_t n_tris, uint32_t run,
                                             const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
                                             uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi,
@@ -314,7 +316,11 @@ __device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, u
         if (boxes) {                                             // fused path: the hypothesis' pixel box (already intersected with the caller's ROI,
             const int4 bb = boxes[by];                           // if any); a conservative box clips nothing, an ROI clips like renderer.cu:106-113
             cmin0 = (float)bb.x; cmin1 = (float)bb.y; cmax0 = (float)bb.z; cmax1 = (float)bb.w;
-            if (box_off) {
+            if constexpr (kBands) {
+                const BandBox k = band_box(bb, height);
+                pitch = (uint32_t)k.w;
+                img = depth + box_off[by] + band_origin(k, bb);
+            } else if (box_off) {
                 pitch = (uint32_t)max(bb.z - bb.x + 1, 0);
                 // pixel (x, image row r) of the box lives at off + (r - r0) * pitch + (x - bb.x), r0 = height - 1 - bb.w: fold the origin into the base
                 img = depth + box_off[by] - ((ptrdiff_t)((int)height - 1 - bb.w) * (ptrdiff_t)pitch + (ptrdiff_t)bb.x);
@@ -327,9 +333,13 @@ __device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, u
             n = t.nx * t.ny;
         } else { t.nx = t.ny = 0; t.x0 = t.y0 = 0; t.base_inv = 0; for (int j = 0; j < 3; ++j) t.px[j] = t.py[j] = t.w3[j] = 0; }
         wave_raster(t, n, sh[wave], shq[wave], [&](int x, int y, int d) {
-            const uint32_t xw = (uint32_t)(x - roi.x);
-            const uint32_t yw = (uint32_t)((int)height - 1 - y - roi.y);
-            atomicMin(&img[xw + (size_t)yw * pitch], d);
+            if constexpr (kBands) {                              // (launched with packed boxes and no ROI of its own: the fragment lies inside bb)
+                atomicMin(&img[band_index(pitch, (uint32_t)x, height - 1u - (uint32_t)y)], d);
+            } else {
+                const uint32_t xw = (uint32_t)(x - roi.x);
+                const uint32_t yw = (uint32_t)((int)height - 1 - y - roi.y);
+                atomicMin(&img[xw + (size_t)yw * pitch], d);
+            }
         });
     }
 }
@@ -337,6 +347,7 @@ __device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, u
 // A workgroup keeps its 256 triangles in registers and walks `pose_run` consecutive hypotheses with them: a mesh that does not fit
 // the L2 (the 1 M-triangle mesh of BASELINE configs[4]: 36 MB) is then streamed from the Infinity Cache / HBM once per pose_run
 // hypotheses instead of once per hypothesis -- at 128 hypotheses that stream (4.6 GB, 3.2 TB/s) was what bounded the kernel.
+template <bool kBands>
 __global__ __launch_bounds__(256) void raster_kernel(const pr_triangle *__restrict__ tris, uint32_t n_tris,
                                                      const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
                                                      uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi,
@@ -353,7 +364,7 @@ __global__ __launch_bounds__(256) void raster_kernel(const pr_triangle *__restri
         load_triangle(chk.caller, n_tris, ti, cv);
         raster_batch_check(cv, ti < n_tris, chk, reinterpret_cast<float (*)[6]>(&sh[0][0][0]), &shq[0][0]);
     }
-    raster_runs(tv, ti, n_tris, blockIdx.y, poses, depth, width, height, proj, roi, rw, rh, boxes, n_poses, pose_run, box_off, nullptr, sh, shq);
+    raster_runs<kBands>(tv, ti, n_tris, blockIdx.y, poses, depth, width, height, proj, roi, rw, rh, boxes, n_poses, pose_run, box_off, nullptr, sh, shq);
 }
 
 // A mixed batch (hypotheses of several meshes) in one launch.  The hypotheses come grouped by mesh; group g owns the 1-D workgroup
@@ -384,7 +395,7 @@ __global__ __launch_bounds__(256) void raster_multi_kernel(const RasterGroup *__
         load_triangle(gr.tris, gr.n_tris, ti, tv);
         // full frames without a caller order: the group's images follow one another from its first hypothesis on
         int32_t *base = (image_of || box_off) ? depth : depth + (size_t)gr.first * rw * rh;
-        raster_runs(tv, ti, gr.n_tris, run, poses + gr.first, base, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
+        raster_runs<false>(tv, ti, gr.n_tris, run, poses + gr.first, base, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
                     gr.count, gr.run, box_off ? box_off + gr.first : nullptr, image_of ? image_of + gr.first : nullptr, sh, shq);
     }
 }
@@ -547,6 +558,51 @@ __global__ __launch_bounds__(256) void count_box_kernel(const int32_t *__restric
     }
 }
 
+// The same two steps for BANDED boxes (pose_box.h, band_box; asynchronous fused path, option box_bands).  A box is one contiguous run of
+// 4 * w * nb ints at a 128-byte aligned offset: the fill is linear, 16 bytes per store, no row addresses; the workgroups of a hypothesis stride
+// over it.  Box and offset come from device memory, so tight boxes keep their saving.
+__global__ __launch_bounds__(256) void fill_band_kernel(int32_t *__restrict__ depth, const int4 *__restrict__ bbox, uint32_t height,
+                                                        const uint32_t *__restrict__ box_off)
+{
+    const BandBox k = band_box(bbox[blockIdx.y], height);
+    const uint32_t n4 = (uint32_t)k.w * k.nb;                       // 16-byte words: one column of one band each
+    int4 *dst = reinterpret_cast<int4 *>(depth + box_off[blockIdx.y]);
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) dst[i] = make_int4(INT_MAX, INT_MAX, INT_MAX, INT_MAX);
+}
+// Grid as count_box_kernel: 16 image rows per workgroup, four aligned rows per wavefront -- exactly one band.  A lane loads one 16-byte word (a
+// column of the band, its four rows), four words in flight (the 16 values count_box_kernel keeps), one ballot per row.  Rows of the band outside
+// the box hold the fill value and count 0, which is what row_count holds for them; so do the rows of a band the box does not reach.
+__global__ __launch_bounds__(256) void count_band_kernel(const int32_t *__restrict__ depth, const int4 *__restrict__ bbox, uint32_t height,
+                                                         uint32_t *__restrict__ row_count, const uint32_t *__restrict__ box_off)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const BandBox k = band_box(bbox[blockIdx.y], height);
+    const uint32_t row0 = blockIdx.x * kBoxRowsPerBlock + (threadIdx.x >> 6) * 4;
+    if (row0 >= height) return;
+    const uint32_t band = (row0 >> 2) - (uint32_t)(k.R >> 2);       // (wraps for a band above the box: not live)
+    uint32_t cnt[4] = { 0, 0, 0, 0 };
+    if (k.nb > 0 && row0 >= (uint32_t)k.R && band < k.nb) {
+        const int4 *line = reinterpret_cast<const int4 *>(depth + box_off[blockIdx.y]) + (size_t)band * (uint32_t)k.w;
+        for (int c0 = 0; c0 < k.w; c0 += 256) {
+            int4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = line[min(c0 + 64 * j + (int)lane, k.w - 1)];      // (a lane past the end re-reads the last column: unconditional loads stay in flight together)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool in = c0 + 64 * j + (int)lane < k.w;
+                cnt[0] += (uint32_t)__popcll(__ballot(in && v[j].x > 0 && v[j].x != INT_MAX));
+                cnt[1] += (uint32_t)__popcll(__ballot(in && v[j].y > 0 && v[j].y != INT_MAX));
+                cnt[2] += (uint32_t)__popcll(__ballot(in && v[j].z > 0 && v[j].z != INT_MAX));
+                cnt[3] += (uint32_t)__popcll(__ballot(in && v[j].w > 0 && v[j].w != INT_MAX));
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) if (row0 + r < height) row_count[(size_t)blockIdx.y * height + row0 + r] = cnt[r];
+    }
+}
+
 // Persistent workgroups walk the (hypothesis, band) items; a band is a run of raster rows of the
 // hypothesis' box that fits the LDS tile.  Each workgroup rasterises ALL triangles against its band
 // with ds_min, then writes the band (INT_MAX = empty) and its per-row valid counts.
@@ -667,7 +723,7 @@ hipError_t launch_raster(const pr_triangle *tris, uint32_t n_tris, const pr_mat4
     for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
         const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
         const uint32_t run = raster_pose_run(n_tris, np);
-        hipLaunchKernelGGL(raster_kernel, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
+        hipLaunchKernelGGL(raster_kernel<false>, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
                            depth + (size_t)p0 * rw * rh, width, height, proj, roi, rw, rh, (const int4 *)nullptr, np, run, (const uint32_t *)nullptr, BatchCheck{});
     }
     return hipGetLastError();
@@ -712,18 +768,18 @@ hipError_t launch_render_bands(const pr_triangle *tris, uint32_t n_tris, const p
 
 // offsets of the packed boxes from boxes computed on the device (synchronous path; the asynchronous path's host computes both): exclusive scan of
 // the areas rounded up to kBoxPack pixels (box_slot), one workgroup
-__global__ __launch_bounds__(256) void box_pack_offsets_kernel(const int4 *__restrict__ bbox, uint32_t n, uint32_t *__restrict__ off)
+__global__ __launch_bounds__(256) void box_pack_offsets_kernel(const int4 *__restrict__ bbox, uint32_t n, uint32_t *__restrict__ off, uint32_t height, bool bands)
 {
     __shared__ uint32_t buf[256];
     __shared__ uint32_t carry;
-    block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return box_slot(box_area(bbox[i])); }, [&](uint32_t i, uint32_t o) { off[i] = o; });
+    block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return box_slot_of(bbox[i], height, bands); }, [&](uint32_t i, uint32_t o) { off[i] = o; });
 }
 // The steps both box renders share.  box_pack_offsets_kernel (when the boxes are packed); fill_box_kernel / count_box_kernel over hypotheses
 // [p0, p0 + n), in launches of at most 32768 (grid.y is limited to 65535); the closing row scan (launch_d2c_scan_init when the asynchronous
 // path's per-hypothesis records are given).
-static void launch_box_pack(const int4 *bbox, uint32_t n_poses, const uint32_t *box_off, hipStream_t s)
+static void launch_box_pack(const int4 *bbox, uint32_t n_poses, const uint32_t *box_off, hipStream_t s, uint32_t height = 0, bool bands = false)
 {
-    if (box_off) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, bbox, n_poses, const_cast<uint32_t *>(box_off));   // (the caller's scratch: filled here)
+    if (box_off) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, bbox, n_poses, const_cast<uint32_t *>(box_off), height, bands);   // (the caller's scratch: filled here)
 }
 // Asynchronous path, option tight_box: the uploaded loose boxes of all n_poses hypotheses replaced by their tight ones ...
 hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_mat4 *poses_dev, uint32_t n_poses, const pr_mat4 &proj,
@@ -734,24 +790,28 @@ hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_ma
     return hipGetLastError();
 }
 // ... and the packed offsets of one sub-batch's boxes formed again from them (the uploaded ones belong to the loose boxes)
-hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, hipStream_t s)
+hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, uint32_t height, bool bands, hipStream_t s)
 {
-    if (n_poses > 0) launch_box_pack(bbox, n_poses, box_off, s);
+    if (n_poses > 0) launch_box_pack(bbox, n_poses, box_off, s, height, bands);
     return hipGetLastError();
 }
-static void launch_fill_boxes(int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height, hipStream_t s)
+static void launch_fill_boxes(int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height, hipStream_t s,
+                              bool bands = false)
 {
     for (const uint32_t end = p0 + n; p0 < end; p0 += 32768) {
         const uint32_t np = (end - p0 < 32768) ? (end - p0) : 32768;
+        if (bands) { hipLaunchKernelGGL(fill_band_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s, depth, bbox + p0, height, box_off + p0); continue; }
         hipLaunchKernelGGL(fill_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
                            depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, box_off ? box_off + p0 : nullptr);
     }
 }
 static void launch_count_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height,
-                               uint32_t *row_count, hipStream_t s)
+                               uint32_t *row_count, hipStream_t s, bool bands = false)
 {
     for (const uint32_t end = p0 + n; p0 < end; p0 += 32768) {
         const uint32_t np = (end - p0 < 32768) ? (end - p0) : 32768;
+        if (bands) { hipLaunchKernelGGL(count_band_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s, depth, bbox + p0, height,
+                                        row_count + (size_t)p0 * height, box_off + p0); continue; }
         hipLaunchKernelGGL(count_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
                            depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, row_count + (size_t)p0 * height, box_off ? box_off + p0 : nullptr);
     }
@@ -768,9 +828,10 @@ static hipError_t launch_box_scan(const uint32_t *row_count, uint32_t height, ui
 hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb,
                                int4 *bbox, int32_t *depth, uint32_t *row_count, uint32_t *row_off, uint32_t *counts,
                                uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s, bool compute_boxes,
-                               PoseMeta *meta, DevIcpState *st, uint32_t *arrive, const uint32_t *box_off, const BatchCheck *check)
+                               PoseMeta *meta, DevIcpState *st, uint32_t *arrive, const uint32_t *box_off, const BatchCheck *check, bool bands)
 {
     if (n_poses == 0) return hipSuccess;
+    if (bands && (!box_off || compute_boxes)) return hipErrorInvalidValue;      // banded boxes are packed boxes the caller placed (box_slot_of)
     if (compute_boxes) {
         hipLaunchKernelGGL(pose_bbox_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabb, poses_dev, n_poses, proj, width, height, roi, bbox);
         launch_box_pack(bbox, n_poses, box_off, s);
@@ -780,13 +841,14 @@ hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const p
         const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
         const size_t off = box_off ? 0 : (size_t)p0 * width * height;
         const uint32_t *bo = box_off ? box_off + p0 : nullptr;
-        launch_fill_boxes(depth, bbox, box_off, p0, np, width, height, s);
+        launch_fill_boxes(depth, bbox, box_off, p0, np, width, height, s, bands);
         if (n_tris > 0)                                          // an empty mesh renders nothing: every cloud is empty
         { const uint32_t run = raster_pose_run(n_tris, np);
-          hipLaunchKernelGGL(raster_kernel, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
+          auto *kernel = bands ? raster_kernel<true> : raster_kernel<false>;
+          hipLaunchKernelGGL(kernel, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
                              depth + off, width, height, proj, none, width, height, (const int4 *)(bbox + p0), np, run,
                              bo, (check && p0 == 0) ? *check : BatchCheck{}); }
-        launch_count_boxes(depth, bbox, box_off, p0, np, width, height, row_count, s);
+        launch_count_boxes(depth, bbox, box_off, p0, np, width, height, row_count, s, bands);
     }
     return launch_box_scan(row_count, height, row_off, counts, n_poses, meta, st, arrive, s);
 }

@@ -305,6 +305,17 @@ int main()
                             else CHECK(off[i] >= off[i - 1] && off[i] == off[i - 1] + prk::box_slot(prk::box_area(boxes[i - 1])));
                             if ((i + 1) % pl.sub == 0 || i + 1 == P) CHECK((size_t)off[i] + prk::box_area(boxes[i]) <= ((size_t)W * H + prk::kBoxPack) * pl.sub);
                         }
+                        // the same boxes in the banded layout (option box_bands): slots from box_slot_of, the workspace bound with the height rounded up to 4
+                        const AsyncPlan pb = plan_async(P, W, H, boxes.data(), steps, sub_batch, hint, off.data(), /*bands=*/true);
+                        CHECK(pb.max_area == pl.max_area && pb.cstride == pl.cstride && pb.nblk == pl.nblk && pb.grid_x == pl.grid_x && pb.sub >= 1 && pb.sub <= pl.sub);
+                        CHECK((size_t)pb.sub * W * ((H + 3) & ~3u) * sizeof(int32_t) <= ((size_t)4 << 30));
+                        for (uint32_t i = 0; i < P; ++i) {
+                            const uint32_t ints = prk::box_ints(boxes[i], H, true);
+                            CHECK(off[i] % prk::kBoxPack == 0 && ints % 4 == 0 && ints >= prk::box_area(boxes[i]) && (prk::box_area(boxes[i]) > 0 || ints == 0));
+                            if (i % pb.sub == 0) CHECK(off[i] == 0);
+                            else CHECK(off[i] == off[i - 1] + prk::box_slot_of(boxes[i - 1], H, true));
+                            if ((i + 1) % pb.sub == 0 || i + 1 == P) CHECK((size_t)off[i] + ints <= depth_ints_per_pose(W, H, true) * pb.sub);
+                        }
                     }
     // release_pass_for: the measured rule at the benchmark's figures, the scene kinds, a timed batch, the two options
     {

@@ -5,6 +5,10 @@ of them, fragments drained 64 at a time in triangle order); the arithmetic is fl
 a parity tool.  numpy only, no device.
 
     python tools/raster_atomic_shape.py [n_hypotheses=6]
+
+`layout` (count, requests_per_hypothesis): "rows" (default) = a row-major box; "bands" = the asynchronous path's banded box (option box_bands:
+four image rows interleaved column by column, bands aligned to image rows, pitch = the box's width, no padding), addressed through the
+library's own layout function (pr_debug_box_layout).
 """
 import os
 import sys
@@ -58,8 +62,17 @@ def _segments(addr):
     return len(np.unique(addr // 16))            # distinct 64-byte segments of int32 addresses
 
 
-def count(tris, poses):
+def banded_addresses(x, y, H=synth.HEIGHT, W=synth.WIDTH):
+    """int32 addresses of the fragments (x, raster y) in the banded box of their hypothesis: the fragments' hull padded by 2 pixels, clipped to the frame
+    (the tight box's rounding), its slot on a 128-byte boundary as the packed layout places it."""
+    box = [max(x.min() - 2, 0), max(y.min() - 2, 0), min(x.max() + 2, W - 1), min(y.max() + 2, H - 1)]
+    return api.box_layout(box, W, H, True, x, H - 1 - y)[1].astype(np.int64)
+
+
+def count(tris, poses, layout="rows"):
     """Totals over `poses` for the triangle order given; see report() for the meaning of each."""
+    if layout not in ("rows", "bands"):
+        raise ValueError("layout must be 'rows' or 'bands'")
     tris = np.asarray(tris, np.float64)
     tot = dict(poses=len(poses), cand=0, frag=0, instr=0, seg=0, vis=0, wg_uni=0, wg_rowseg=0, wg_count=0,
                fits={c: 0 for c in PATCH_CAPS}, wg_frag_in={c: 0 for c in PATCH_CAPS}, boxes=[])
@@ -67,7 +80,7 @@ def count(tris, poses):
         cand, t, x, y = fragments_of_pose(tris, M)
         bx0, by0 = x.min() - 2, y.min() - 2
         pitch = (x.max() + 2 - bx0 + 1 + 31) // 32 * 32                  # rows start on a segment boundary (the packed boxes' own pitch is their width: a statistic)
-        addr = (y - by0) * pitch + (x - bx0)
+        addr = (y - by0) * pitch + (x - bx0) if layout == "rows" else banded_addresses(x, y)
         tot["cand"] += cand; tot["frag"] += len(t); tot["vis"] += len(np.unique(addr))
         wave = t // 64
         order = np.argsort(wave, kind="stable")
@@ -92,15 +105,19 @@ def count(tris, poses):
     return tot
 
 
-def requests_per_hypothesis(tris, poses):
+def requests_per_hypothesis(tris, poses, layout="rows"):
     """64-byte atomic requests per hypothesis: the sum over atomic wave instructions of the distinct segments their lanes address."""
-    tot = count(tris, poses)
+    tot = count(tris, poses, layout)
     return tot["seg"] / tot["poses"]
 
 
-def report(name, tot):
+def report(name, tot, banded=None):
+    """banded: the same count with layout="bands" -- its requests are printed beside the row-major ones."""
     P = tot["poses"]
     print(f"== {name}")
+    if banded is not None:
+        print(f"banded boxes (4 rows interleaved): distinct 64-B segments per instruction {banded['seg']/banded['instr']:.2f}, 64-B requests per hypothesis "
+              f"{banded['seg']/P:.0f} = {banded['seg']/tot['seg']:.3f} of row-major ({tot['seg']/P:.0f})")
     print(f"per hypothesis: candidates {tot['cand']/P:.0f}, fragments (lane atomics) {tot['frag']/P:.0f}, visible pixels {tot['vis']/P:.0f}")
     print(f"atomic wave-instructions {tot['instr']/P:.0f} per hypothesis, distinct 64-B segments per instruction {tot['seg']/tot['instr']:.1f} "
           f"(lanes per instruction {tot['frag']/tot['instr']:.1f}); 64-B requests per hypothesis {tot['seg']/P:.0f}")
@@ -118,7 +135,8 @@ def main():
     poses = synth.hypotheses(n)
     print("triangles", len(tris), "hypotheses", n)
     report("mesh in file order", count(tris, poses))
-    report("mesh in the library's order (pr_debug_mesh_order)", count(shipped_order(tris), poses))
+    ordered = shipped_order(tris)
+    report("mesh in the library's order (pr_debug_mesh_order)", count(ordered, poses), count(ordered, poses, "bands"))
 
 
 if __name__ == "__main__":

@@ -887,6 +887,61 @@ int  pr_pose_vsd_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint3
                        int depth_is_i32, const float K[9] /* may be NULL */, float delta_mm, const float *taus_mm, uint32_t n_taus,
                        pr_vsd_counts *out_host);
 
+/* ---- interpenetration: do two detections claim the same space? ---------------------------------------------------------------------------
+ * The pixel rules above cannot tell an object that lies BEHIND another (thousands of shared pixels, no shared volume: legitimate) from two
+ * refinements that sank into each other (fewer shared pixels, a lot of shared volume: impossible).  Per pixel a closed mesh occupies the depth
+ * interval [near, far] along the ray, near the nearest and far the farthest fragment the raster produces there; two hypotheses interpenetrate
+ * at a pixel exactly where their intervals overlap.  Everything is integer millimetres.
+ *
+ * pr_render_span: pr_render with a second output.  near_dev_out is byte for byte what pr_render writes for the same arguments (0 where nothing
+ * was drawn); far_dev_out[q] is the largest fragment depth at q -- the maximum of the very int32 values whose minimum is near -- and 0 where
+ * no fragment fell.  Both are n_poses images of the frame (or of the ROI).  Argument checks are pr_render's; far_dev_out == NULL (or
+ * near_dev_out == NULL) with n_poses > 0 is PR_ERR_INVALID.
+ *
+ * pr_pose_penetration: the P x P matrix of pr_pair_solid records of n_poses hypotheses of one mesh, rows and columns in the caller's order.
+ * For frame pixel q and hypotheses i, j, with near / far as the raster leaves them:
+ *   both:   near_i(q) and near_j(q) are both rendered (> 0 and not "nothing drawn");
+ *   len:    min(far_i(q), far_j(q)) - max(near_i(q), near_j(q)), a 64-bit difference;
+ *   inter:  both && len > slack_mm;   sum_mm = the sum of len, max_mm the largest len, over the inter pixels.
+ * The matrix is symmetric.  The diagonal is a hypothesis with itself: both = its rendered pixels, sum_mm = the sum of its own thickness,
+ * its "volume" in mm x pixels; hence sum_mm[i][j] <= min(sum_mm[i][i], sum_mm[j][j]).  Integer sums and maxima with one writer per record:
+ * the same bytes on every call and for every order of the batch (permuted with it).  No scene and no ROI; synchronous, on the calling
+ * thread's context and its own stream and workspaces; a batch pending on an asynchronous slot is not disturbed.
+ * Limits of the definition: the interval is the HULL of the solid along the ray -- exact for objects that are convex along the viewing rays,
+ * an over-estimate for a cup or a bracket with something inside it; silhouette pixels with one fragment have thickness 0; an open mesh has
+ * no volume (its far surface is its near surface where only one sheet is seen).
+ * PR_ERR_INVALID, with nothing written and BEFORE any device is touched (so also on a machine without one), with a message that names the
+ * numbers, for: slack_mm < 0; n_poses > PR_PENETRATION_MAX_POSES; width or height 0 or a frame beyond the scoring calls' size limit;
+ * 2 x n_poses renders of the frame beyond the scoring calls' depth workspace bound (4 GiB: the near and far boxes of a call are resident
+ * together, there is no chunking); and, with n_poses > 0, a null proj, poses_host, pairs_host or tris_dev (n_tris > 0).  n_poses == 0
+ * returns PR_OK and writes nothing.
+ * pr_pose_penetration_multi: hypothesis i is rendered with meshes[mesh_index_host[i]] (the mesh table of the mixed batches above); the
+ * matrix in the caller's order, a one-mesh batch byte for byte the single-mesh call's; a mesh index out of range, n_meshes == 0 or a null
+ * table is PR_ERR_INVALID.  Not offered: exact solids for objects concave along the ray, a ROI, batches beyond one resident workspace. */
+int  pr_render_span(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t n_poses, size_t width, size_t height,
+                    const pr_mat4 *proj, pr_roi roi, int32_t *near_dev_out, int32_t *far_dev_out);
+#define PR_PENETRATION_MAX_POSES 1024
+typedef struct {
+    uint32_t both;      /* frame pixels where i and j both render                                                              */
+    uint32_t inter;     /* of those: len = min(far_i, far_j) - max(near_i, near_j) > slack_mm   (64-bit differences)           */
+    uint32_t max_mm;    /* largest len over the inter pixels, 0 when inter == 0                                                */
+    uint32_t reserved;  /* written as 0                                                                                        */
+    uint64_t sum_mm;    /* exact sum of len over the inter pixels                                                              */
+} pr_pair_solid;        /* 24 B; the record of one pair                                                                        */
+int  pr_pose_penetration(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                         const pr_mat4 *proj, int32_t slack_mm, pr_pair_solid *pairs_host /* n_poses x n_poses */);
+int  pr_pose_penetration_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
+                               uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, int32_t slack_mm,
+                               pr_pair_solid *pairs_host /* n_poses x n_poses */);
+/* Greedy selection of detections that can coexist, host only (needs no device); the shape of pr_select_greedy.  order: n_order indices, best
+ * first; pairs: pr_pose_penetration's n_poses x n_poses records.  i is kept unless an already kept j has
+ *   pairs[i][j].sum_mm * den > num * min(pairs[i][i].sum_mm, pairs[j][j].sum_mm)          (128-bit products)
+ * i.e. shares more than num / den of the smaller of the two volumes; in a matrix of the device a hypothesis without volume never conflicts.
+ * selected_out: room for n_order indices.  PR_ERR_INVALID, with nothing written: an index out of range or twice in order, den == 0, a null
+ * pointer that is needed. */
+int  pr_select_disjoint(const uint32_t *order, uint32_t n_order, const pr_pair_solid *pairs, uint32_t n_poses, uint32_t num, uint32_t den,
+                        uint32_t *selected_out, uint32_t *n_selected);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

@@ -55,6 +55,10 @@ POSE_DIST_MAX_SYMS, POSE_DIST_MAX_POSES, POSE_DIST_MAX_POINTS = 64, 4096, 1 << 2
 # pr_vsd_counts: the visible surfaces of an estimate and a truth against the scene frame, counted (pr_pose_vsd)
 VSD_MAX_TAUS = 12                        # PR_VSD_MAX_TAUS
 VSD = np.dtype([("visib_gt", "<u4"), ("visib_est", "<u4"), ("inter", "<u4"), ("uni", "<u4"), ("far", "<u4", (VSD_MAX_TAUS,))])
+# pr_pair_solid: the shared pixels and the shared depth intervals of two hypotheses (pr_pose_penetration)
+PENETRATION_MAX_POSES = 1024             # PR_PENETRATION_MAX_POSES
+PAIR_SOLID = np.dtype([("both", "<u4"), ("inter", "<u4"), ("max_mm", "<u4"), ("reserved", "<u4"), ("sum_mm", "<u8")])
+assert PAIR_SOLID.itemsize == 24
 # pr_pose_info / pr_pose_eig: the float64 information matrix of a hypothesis about a centre, and its Jacobi eigen-decomposition (pr_icp_information)
 POSE_INFO = np.dtype([("n_points", "<u4"), ("n_valid", "<u4"), ("n_zero_weight", "<u4"), ("reserved", "<u4"), ("c", "<f4", (3,)), ("rho", "<f4"),
                       ("H", "<f8", (21,)), ("g", "<f8", (6,)), ("sum_w", "<f8"), ("sum_wr2", "<f8"), ("sum_r2", "<f8")])
@@ -229,6 +233,10 @@ SIGNATURES = {
     "pr_cluster_greedy": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32), _vp]),
     "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
+    "pr_render_span": (_i32, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, Roi, _vp, _vp]),
+    "pr_pose_penetration": (_i32, [_vp, _sz, _vp, _u32, _u32, _u32, _vp, C.c_int32, _vp]),
+    "pr_pose_penetration_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, C.c_int32, _vp]),
+    "pr_select_disjoint": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, _vp, C.POINTER(_u32)]),
     "pr_comm_id": (_i32, [_vp]),
     "pr_comm_init_rank": (_i32, [_vp, _i32, _i32]),
     "pr_comm_init_all": (_i32, [_i32]),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -331,6 +331,18 @@ def render(tris, poses, width: int, height: int, proj, roi: Sequence[int] = (0, 
     pj = _f32(proj, -1)
     check(_lib.load().pr_render(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi), out.data()))
     return out
+
+
+def render_span(tris, poses, width: int, height: int, proj, roi: Sequence[int] = (0, 0, 0, 0)):
+    """``pr_render_span``: ``render`` with the far surface.  Returns (near, far) device vectors of int32 mm: ``near`` is ``render``'s bytes,
+    ``far`` the largest fragment depth of every pixel, 0 where nothing was drawn."""
+    td = _tris_dev(tris)
+    poses = _f32(poses, (-1, 16))
+    rw, rh = (roi[2], roi[3]) if roi[2] > 0 and roi[3] > 0 else (width, height)
+    near, far = DeviceVector(len(poses) * rw * rh, np.int32), DeviceVector(len(poses) * rw * rh, np.int32)
+    pj = _f32(proj, -1)
+    check(_lib.load().pr_render_span(td.data(), td.size() // 9, ptr(poses), len(poses), width, height, ptr(pj), Roi(*roi), near.data(), far.data()))
+    return near, far
 
 
 def raw2depth_mask(raw: DeviceVector, want_depth: bool = True, want_mask: bool = True):
@@ -1112,6 +1124,57 @@ def select_hypotheses(scores, overlap, max_shared: Sequence[int] = (1, 4), min_f
     frac = np.where(den <= 0, 0.0, sc["inlier"].astype(np.float64) / np.where(den <= 0, 1, den).astype(np.float64))
     order = order[frac[order] >= float(min_fraction)]
     return select_greedy(order, overlap, int(max_shared[0]), int(max_shared[1]))
+
+
+# ------------------------------------------------------------------------------------------------
+# detections that can coexist: the depth intervals two hypotheses share, pixel by pixel, and a choice among them
+# ------------------------------------------------------------------------------------------------
+def _pose_penetration(mesh, width: int, height: int, proj, slack_mm: int) -> np.ndarray:
+    suffix, lead, poses, alive = mesh
+    pj = _f32(proj, -1)
+    out = np.zeros((len(poses), len(poses)), PAIR_SOLID)
+    check(getattr(_lib.load(), "pr_pose_penetration" + suffix)(*lead, ptr(poses), len(poses), width, height, ptr(pj), int(slack_mm), ptr(out)))
+    return out
+
+
+def pose_penetration(tris, poses, width: int, height: int, proj, slack_mm: int = 0) -> np.ndarray:
+    """``pr_pose_penetration``: PAIR_SOLID[P, P].  ``both`` counts the frame pixels two hypotheses both render, ``inter`` those where their
+    depth intervals [near, far] overlap by more than ``slack_mm``, ``sum_mm`` / ``max_mm`` the sum and the largest of those overlaps in mm.
+    Symmetric; the diagonal is a hypothesis' own thickness (its volume).  At most ``PENETRATION_MAX_POSES`` hypotheses per call."""
+    return _pose_penetration(_one_mesh(tris, poses), width, height, proj, slack_mm)
+
+
+def pose_penetration_multi(meshes, mesh_index, poses, width: int, height: int, proj, slack_mm: int = 0) -> np.ndarray:
+    """``pr_pose_penetration_multi``: ``pose_penetration`` for a batch whose pose i uses ``meshes[mesh_index[i]]``; rows and columns in pose order."""
+    return _pose_penetration(_mesh_batch(meshes, mesh_index, poses), width, height, proj, slack_mm)
+
+
+def penetration_fraction(pairs) -> np.ndarray:
+    """``sum_mm[i, j] / min(sum_mm[i, i], sum_mm[j, j])`` as float64[P, P]: the share of the smaller volume two hypotheses have in common;
+    0 where the smaller volume is 0."""
+    s = np.asarray(pairs)["sum_mm"]
+    d = np.diag(s)
+    lim = np.minimum(d[:, None], d[None, :])
+    return np.where(lim == 0, 0.0, s.astype(np.float64) / np.where(lim == 0, 1, lim).astype(np.float64))
+
+
+def select_disjoint(order, pairs, max_fraction: Sequence[int] = (1, 10)) -> np.ndarray:
+    """``pr_select_disjoint`` (host only): walk ``order`` (indices, best first); keep i unless a kept j shares more than
+    ``max_fraction = (num, den)`` of the smaller of the two volumes with it.  Kept indices in that order."""
+    pr = np.ascontiguousarray(pairs, PAIR_SOLID)
+    if pr.ndim != 2 or pr.shape[0] != pr.shape[1]:
+        raise ValueError(f"pairs must be a square matrix, got shape {pr.shape}")
+    od = np.asarray(order)
+    if od.ndim != 1 or (len(od) and (od.dtype.kind not in "iu" or od.min() < 0 or od.max() > 0xffffffff)):
+        raise ValueError("order must be a 1-d array of non-negative integers")
+    num, den = int(max_fraction[0]), int(max_fraction[1])
+    if not 0 <= num <= 0xffffffff or not 0 <= den <= 0xffffffff:
+        raise ValueError("max_fraction must be two integers that fit 32 unsigned bits")
+    od = np.ascontiguousarray(od, np.uint32)
+    sel = np.zeros(max(1, len(od)), np.uint32)
+    n = C.c_uint32(0)
+    check(_lib.load().pr_select_disjoint(ptr(od), len(od), ptr(pr), len(pr), num, den, ptr(sel), C.byref(n)))
+    return sel[:n.value].astype(np.int64)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -897,6 +897,37 @@ int pr_select_greedy(const uint32_t *order, uint32_t n_order, const uint32_t *ov
     return PR_OK;
 }
 
+// pr_select_greedy's walk over pr_pose_penetration's records: a hypothesis is dropped when it shares more than num / den of the smaller of the two
+// volumes with one already kept.  sum_mm reaches 2^55 (2^24 pixels of 2^31 mm) and den 2^32: the products take 128 bits.
+int pr_select_disjoint(const uint32_t *order, uint32_t n_order, const pr_pair_solid *pairs, uint32_t n_poses, uint32_t num, uint32_t den,
+                       uint32_t *selected_out, uint32_t *n_selected)
+{
+    if (!n_selected || den == 0 || (n_order && (!order || !pairs || !selected_out))) {
+        prh::set_error(den == 0 && n_selected ? "pr_select_disjoint: den must not be 0" : "pr_select_disjoint: bad arguments");
+        return PR_ERR_INVALID;
+    }
+    std::vector<unsigned char> seen(n_poses, 0);
+    for (uint32_t k = 0; k < n_order; ++k) {
+        if (order[k] >= n_poses) { prh::set_error("pr_select_disjoint: order[%u] = %u, but there are %u hypotheses", k, order[k], n_poses); return PR_ERR_INVALID; }
+        if (seen[order[k]]) { prh::set_error("pr_select_disjoint: order[%u] = %u appears twice", k, order[k]); return PR_ERR_INVALID; }
+        seen[order[k]] = 1;
+    }
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < n_order; ++k) {
+        const uint32_t i = order[k];
+        const uint64_t own = pairs[(size_t)i * n_poses + i].sum_mm;
+        bool keep = true;                                            // (shared <= min(own, other) in a matrix of the device: a hypothesis without volume never conflicts)
+        for (uint32_t a = 0; a < n && keep; ++a) {
+            const uint32_t j = selected_out[a];
+            const uint64_t other = pairs[(size_t)j * n_poses + j].sum_mm, shared = pairs[(size_t)i * n_poses + j].sum_mm;
+            keep = !((unsigned __int128)shared * den > (unsigned __int128)num * std::min(own, other));
+        }
+        if (keep) selected_out[n++] = i;
+    }
+    *n_selected = n;
+    return PR_OK;
+}
+
 // the cover rule (include/pose_refine.h) on bit planes the caller brings: the sequential walk as it is defined, integers only -- what the
 // device's rounds (cover.hip) must reproduce byte for byte
 int pr_select_cover_host(const uint64_t *planes, uint32_t n_poses, size_t plane_words, const uint32_t *order, uint32_t n_order, uint32_t new_num,

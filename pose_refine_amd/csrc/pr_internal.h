@@ -217,6 +217,21 @@ hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_ind
                                      RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, uint32_t *row_count,
                                      uint32_t *row_off, uint32_t *counts, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s,
                                      const uint32_t *box_off);
+// Span renders (raster.hip): every fragment into a near plane (atomicMin) and a far plane (atomicMax) of one layout.  launch_raster_span: full
+// images the caller filled with INT_MAX / INT_MIN; launch_min2zero: the far plane's INT_MIN to 0.  launch_render_span_boxes(_multi): pixel boxes
+// computed here (no ROI), packed at box_off (written here) in both planes, filled and rastered; at most 32768 hypotheses.
+hipError_t launch_min2zero(int32_t *far, size_t n, hipStream_t s);
+hipError_t launch_raster_span(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, int32_t *depth, int32_t *far,
+                              uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh, hipStream_t s);
+hipError_t launch_render_span_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb, int4 *bbox,
+                                    int32_t *depth, int32_t *far, uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s);
+hipError_t launch_render_span_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
+                                          RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, int32_t *far,
+                                          uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s);
+// solid.hip: pr_pose_penetration's P x P records (6 words each: pr_pair_solid) from the two planes of a span render of all P hypotheses; every
+// record is written, none needs clearing
+hipError_t launch_pair_solid(const int32_t *depth, const int32_t *far, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t height,
+                             int32_t slack, uint32_t *records, hipStream_t s);
 // verify.hip: every box pixel a hypothesis renders (launch_render_boxes' layout) against the scene frame (int32 or uint16, mm), added into
 // records[8 * i] (pr_pose_score words: visible, inlier, occluded, violation, missing, reserved, abs_err_sum lo / hi), which the caller zeroed
 hipError_t launch_score_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,

@@ -684,6 +684,75 @@ std::vector<pr_mat4> interleaved_pairs(const pr_mat4 *est, const pr_mat4 *gt, ui
     return out;
 }
 
+// ---- interpenetration of hypotheses (pr_render_span, pr_pose_penetration, pr_pose_penetration_multi) -----------------------------------------------
+// render_impl with a far plane: both stacks filled by kernels, one raster pass, "nothing drawn" to 0 in both
+int render_span_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t P, size_t W, size_t H, const pr_mat4 *proj, pr_roi roi,
+                     int32_t *near_dev, int32_t *far_dev)
+{
+    PR_TRY(render_impl(tris_dev, n_tris, poses_host, 0, W, H, proj, roi, near_dev, true));      // pr_render's checks, with no hypotheses
+    if (P == 0) return PR_OK;
+    if (!poses_host || !near_dev || !far_dev) { set_error("pr_render_span: bad arguments"); return PR_ERR_INVALID; }
+    const auto [rw, rh] = image_extent(roi, W, H);
+    SpanGuard sp(kSpanRender);
+    PR_TRY(stage_poses(poses_host, P));
+    HIP_TRY(prk::launch_fill_i32(near_dev, P * rw * rh, INT32_MAX, g->stream));
+    HIP_TRY(prk::launch_fill_i32(far_dev, P * rw * rh, INT32_MIN, g->stream));
+    HIP_TRY(prk::launch_raster_span(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), (uint32_t)P, near_dev, far_dev, (uint32_t)W, (uint32_t)H, *proj, roi,
+                                    (uint32_t)rw, (uint32_t)rh, g->stream));
+    HIP_TRY(prk::launch_max2zero(near_dev, P * rw * rh, g->stream));
+    HIP_TRY(prk::launch_min2zero(far_dev, P * rw * rh, g->stream));
+    return PR_OK;
+}
+// render_chunk's layout for ALL P hypotheses of a call, with the far plane (g->solid_far) at the same box_off as the near one (g->depth): poses staged,
+// model_boxes' boxes, packed pixel boxes, both planes filled and rastered in one pass.  No row counts: nothing makes clouds of these renders.
+int render_span_boxes(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, uint32_t *box_off)
+{
+    PR_TRY(stage_poses(poses_host, P));
+    if (!src.plan) {
+        HIP_TRY(prk::launch_render_span_boxes(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), P, g->aabb.as<float>(), g->bbox.as<int4>(),
+                                              g->depth.as<int32_t>(), g->solid_far.as<int32_t>(), W, H, *proj, box_off, g->stream));
+        return PR_OK;
+    }
+    const MeshPlan &pl = *src.plan;
+    const MultiLayout l = multi_layout(pl.mesh.size(), P);
+    unsigned char *h = g->h_multi.as<unsigned char>(), *hm = g->h_multi.dev_as<unsigned char>(), *d = g->multi.as<unsigned char>();
+    std::memcpy(h + l.box, pl.box.data(), sizeof(uint32_t) * P);
+    HIP_TRY(prk::launch_stage_words(hm + l.box, d + l.box, sizeof(uint32_t) * P, g->stream));
+    prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
+    const uint32_t n_groups = chunk_groups(pl, 0, P, groups);
+    HIP_TRY(prk::launch_render_span_boxes_multi(g->aabb.as<float>(), reinterpret_cast<const uint32_t *>(d + l.box), groups, hm + l.groups, n_groups,
+                                                reinterpret_cast<prk::RasterGroup *>(d + l.groups), g->poses.as<pr_mat4>(), P, g->bbox.as<int4>(),
+                                                g->depth.as<int32_t>(), g->solid_far.as<int32_t>(), W, H, *proj, box_off, g->stream));
+    return PR_OK;
+}
+// A small core beside vsd_core: the model box(es), the span render of all P hypotheses (checked: penetration_args_ok -- both planes are resident
+// together, there are no chunks), one pair kernel (solid.hip), the P x P records back through pinned memory.  The context's own stream and workspaces:
+// a batch pending on a slot is neither waited for nor disturbed.  out: in the order of `poses` (of a mixed batch: its plan's).
+int solid_core(const MeshSource &src, const pr_mat4 *poses, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, int32_t slack, pr_pair_solid *out)
+{
+    constexpr uint32_t kWords = sizeof(pr_pair_solid) / sizeof(uint32_t);
+    static_assert(sizeof(pr_pair_solid) == 24 && kWords == 6 && offsetof(pr_pair_solid, sum_mm) == 16, "pr_pair_solid: four counters and a 64-bit sum");
+    const size_t plane = ((size_t)W * H + prk::kBoxPack) * P, n_rec = (size_t)P * P;
+    PR_TRY(model_boxes(src, P));
+    PR_TRY(g->depth.ensure(sizeof(int32_t) * plane));
+    PR_TRY(g->solid_far.ensure(sizeof(int32_t) * plane));
+    PR_TRY(g->bbox.ensure(sizeof(int4) * P + sizeof(uint32_t) * P));
+    PR_TRY(g->solid_rec.ensure(sizeof(pr_pair_solid) * n_rec));
+    PR_TRY(g->h_solid.ensure(sizeof(pr_pair_solid) * n_rec));
+    uint32_t *box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + P);
+    {
+        SpanGuard sp(kSpanRender);
+        PR_TRY(render_span_boxes(src, poses, P, W, H, proj, box_off));
+    }
+    ReadBack back;
+    HIP_TRY(prk::launch_pair_solid(g->depth.as<int32_t>(), g->solid_far.as<int32_t>(), g->bbox.as<int4>(), box_off, P, H, slack, g->solid_rec.as<uint32_t>(), g->stream));
+    PR_TRY(back.queue(g->solid_rec.p, g->h_solid, (uint32_t)(kWords * n_rec)));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    back.deliver(out, sizeof(pr_pair_solid) * n_rec);
+    drain_spans();
+    return PR_OK;
+}
+
 // the request of an entry point from what all fourteen have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
 ScoreRequest score_request(const char *fn, ScoreKind kind, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, pr_roi roi,
                            const void *scene_dev, int depth_is_i32, int32_t tau, pr_pose_score *scores_host)
@@ -1679,6 +1748,47 @@ int pr_pose_vsd_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32
     PR_TRY(vsd_core(MeshSource{ nullptr, 0, &pl }, grouped.data(), nullptr, n_est, width, height, proj, scene_depth_dev, depth_is_i32 != 0,
                     vsd_params(K, delta_mm, taus_mm, n_taus), rec.data()));
     for (uint32_t j = 0; j < n_est; ++j) out_host[pl.order[2 * (size_t)j] / 2] = rec[j];
+    return PR_OK;
+}
+
+int pr_render_span(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t n_poses, size_t width, size_t height,
+                   const pr_mat4 *proj, pr_roi roi, int32_t *near_dev_out, int32_t *far_dev_out)
+{
+    PR_ENTER();
+    const auto [rw, rh] = image_extent(roi, width, height);
+    if (near_dev_out) note_write(near_dev_out, sizeof(int32_t) * n_poses * rw * rh);
+    if (far_dev_out) note_write(far_dev_out, sizeof(int32_t) * n_poses * rw * rh);
+    PR_TRY(render_span_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, near_dev_out, far_dev_out));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    drain_spans();
+    return PR_OK;
+}
+
+int pr_pose_penetration(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                        const pr_mat4 *proj, int32_t slack_mm, pr_pair_solid *pairs_host)
+{
+    PR_TRY(penetration_args_ok("pr_pose_penetration", false, tris_dev, n_tris, poses_host, n_poses, width, height, proj, slack_mm, pairs_host));   // before any device use
+    if (n_poses == 0) return PR_OK;
+    PR_ENTER();
+    return solid_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, n_poses, width, height, proj, slack_mm, pairs_host);
+}
+
+// A mixed batch: grouped by mesh, the records into a temporary (nothing reaches pairs_host unless the call succeeded), rows and columns back
+// to the caller's order as pr_score_overlap_multi's matrix
+int pr_pose_penetration_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
+                              uint32_t width, uint32_t height, const pr_mat4 *proj, int32_t slack_mm, pr_pair_solid *pairs_host)
+{
+    PR_TRY(penetration_args_ok("pr_pose_penetration_multi", true, nullptr, 0, poses_host, n_poses, width, height, proj, slack_mm, pairs_host));
+    if (n_poses == 0) return PR_OK;
+    MeshPlan pl;
+    PR_TRY(plan_meshes("pr_pose_penetration_multi", meshes, n_meshes, mesh_index_host, n_poses, pl));
+    PR_ENTER();
+    const uint32_t P = n_poses;
+    const std::vector<pr_mat4> grouped = grouped_poses(pl, poses_host);
+    std::vector<pr_pair_solid> rec((size_t)P * P);
+    PR_TRY(solid_core(MeshSource{ nullptr, 0, &pl }, grouped.data(), P, width, height, proj, slack_mm, rec.data()));
+    for (uint32_t a = 0; a < P; ++a)
+        for (uint32_t b = 0; b < P; ++b) pairs_host[(size_t)pl.order[a] * P + pl.order[b]] = rec[(size_t)a * P + b];
     return PR_OK;
 }
 

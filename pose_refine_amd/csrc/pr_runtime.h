@@ -414,6 +414,25 @@ inline int vsd_args_ok(const char *fn, bool multi, const pr_triangle *tris_dev, 
     for (uint32_t i = 0; i < n_gt; ++i) if (!finite16(gt[i])) { set_error("%s: gt_host[%u] has a non-finite entry", fn, i); return PR_ERR_INVALID; }
     return PR_OK;
 }
+// pr_pose_penetration / pr_pose_penetration_multi's checks, all but a mixed batch's mesh table (plan_meshes): no device is touched before they pass (no
+// HIP call in here).  The near and far boxes of all P hypotheses are resident together: 2 P renders within the bound depth_chunk (pr_refine.cpp) keeps.
+uint32_t depth_chunk(size_t img, uint32_t P);
+inline int penetration_args_ok(const char *fn, bool multi, const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses, uint32_t P, uint32_t W, uint32_t H,
+                               const pr_mat4 *proj, int32_t slack, const pr_pair_solid *out)
+{
+    if (slack < 0) { set_error("%s: slack_mm = %d must not be negative", fn, slack); return PR_ERR_INVALID; }
+    if (P > PR_PENETRATION_MAX_POSES) { set_error("%s: %u hypotheses, at most PR_PENETRATION_MAX_POSES = %d", fn, P, PR_PENETRATION_MAX_POSES); return PR_ERR_INVALID; }
+    if (W == 0 || H == 0) { set_error("%s: bad arguments (an empty frame)", fn); return PR_ERR_INVALID; }
+    if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
+    if (P == 0) return PR_OK;
+    const uint32_t fit = depth_chunk((size_t)W * H, 2 * P);
+    if (fit < 2 * P) {
+        set_error("%s: %u hypotheses are %u near and far renders of %ux%u resident together, the depth workspace holds at most %u", fn, P, 2 * P, W, H, fit);
+        return PR_ERR_INVALID;
+    }
+    if (!proj || !poses || !out || (!multi && !tris_dev && n_tris > 0)) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
 // A slot's pinned blocks, in bytes.  h_in, staged to the device by one kernel: poses | pixel boxes | offsets of the packed boxes.
 // h_out, stored by the batch's last kernels: cloud sizes | result records | the word the device-side model-box check writes (1 = the
 // assumed box or a scene cache was stale), each on a 64-byte line of its own.
@@ -652,6 +671,8 @@ struct Ctx {
     PinBuf h_pd_mats, h_pd_rec;      // the matrices on their way in, the records on their way out
     DevBuf vsd_rec;                  // pr_pose_vsd: the records of a chunk's pairs
     PinBuf h_vsd;                    // ... on their way to the caller
+    DevBuf solid_far, solid_rec;     // pr_render_span / pr_pose_penetration: the far plane of the boxes in g->depth (same offsets); the P x P pair records
+    PinBuf h_solid;                  // the records on their way to the caller
     DevBuf info_meta, info_part;     // pr_icp_information / pr_pose_information: the hypotheses' records (cloud, centre, radius) and the workgroups' partial sums
     PinBuf h_info_meta, h_info_out;  // the records on their way in; pr_pose_info and pr_pose_eig on their way to the caller (stored by the eigen kernel)
     DevBuf lvl_rows, lvl_counts, lvl_carry;   // pr_refine_pyramid: per-row sample counts and offsets of every level of a chunk, the level clouds' sizes, the per-level carry records

@@ -290,14 +290,17 @@ __device__ __forceinline__ void load_triangle(const pr_triangle *__restrict__ tr
 // n_poses at `poses`.  Image of hypothesis `by`: depth + image_of[by] * rw * rh when image_of is given (the caller's order of a mixed
 // batch), depth + by * rw * rh otherwise; packed boxes (box_off): their own pitch, or -- kBands, the asynchronous fused path's option box_bands --
 // the banded layout of pose_box.h (band_box), whose per-hypothesis constants are folded into the base as the row-major origin is.
-template <bool kBands>
+// kSpan (the span kernels below; never with kBands): `far` is a second plane of the same layout, and every fragment's depth also goes
+// into it with atomicMax -- the farthest fragment of the pixel from the very int32 the nearest is taken from.
+template <bool kBands, bool kSpan = false>
 __device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, uint32_t n_tris, uint32_t run,
                                             const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
                                             uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi,
                                             uint32_t rw, uint32_t rh, const int4 *__restrict__ boxes, uint32_t n_poses, uint32_t pose_run,
                                             const uint32_t *__restrict__ box_off, const uint32_t *__restrict__ image_of,
-                                            float (*sh)[kSetupWords][64], uint32_t (*shq)[192])
+                                            float (*sh)[kSetupWords][64], uint32_t (*shq)[192], int32_t *__restrict__ far = nullptr)
 {
+    static_assert(!(kBands && kSpan), "the span render uses row-major boxes");
     const uint32_t wave = threadIdx.x >> 6;
     float rmin0 = 0.0f, rmin1 = 0.0f, rmax0 = (float)(width - 1), rmax1 = (float)(height - 1);
     if (roi.width > 0 && roi.height > 0) {                       // renderer.cu:106-113 (image is flipped in y)
@@ -339,6 +342,7 @@ __device__ __forceinline__ void raster_runs(const float (&tv)[9], uint32_t ti, u
                 const uint32_t xw = (uint32_t)(x - roi.x);
                 const uint32_t yw = (uint32_t)((int)height - 1 - y - roi.y);
                 atomicMin(&img[xw + (size_t)yw * pitch], d);
+                if constexpr (kSpan) atomicMax(&far[(img - depth) + (ptrdiff_t)(xw + (size_t)yw * pitch)], d);
             }
         });
     }
@@ -397,6 +401,77 @@ __global__ __launch_bounds__(256) void raster_multi_kernel(const RasterGroup *__
         int32_t *base = (image_of || box_off) ? depth : depth + (size_t)gr.first * rw * rh;
         raster_runs<false>(tv, ti, gr.n_tris, run, poses + gr.first, base, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
                     gr.count, gr.run, box_off ? box_off + gr.first : nullptr, image_of ? image_of + gr.first : nullptr, sh, shq);
+    }
+}
+
+// The span forms of raster_kernel<false> and raster_multi_kernel (pr_render_span, pr_pose_penetration): the same workgroups, triangles, hypotheses
+// and fragments, every depth into two planes of one layout -- atomicMin into `depth`, atomicMax into `far` (full frames or packed boxes).
+__global__ __launch_bounds__(256) void raster_span_kernel(const pr_triangle *__restrict__ tris, uint32_t n_tris,
+                                                          const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth, int32_t *__restrict__ far,
+                                                          uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi,
+                                                          uint32_t rw, uint32_t rh, const int4 *__restrict__ boxes, uint32_t n_poses, uint32_t pose_run,
+                                                          const uint32_t *__restrict__ box_off)
+{
+    __shared__ float sh[4][kSetupWords][64];
+    __shared__ uint32_t shq[4][192];
+    const uint32_t ti = blockIdx.x * 256 + threadIdx.x;
+    float tv[9];
+    load_triangle(tris, n_tris, ti, tv);
+    raster_runs<false, true>(tv, ti, n_tris, blockIdx.y, poses, depth, width, height, proj, roi, rw, rh, boxes, n_poses, pose_run, box_off, nullptr, sh, shq, far);
+}
+__global__ __launch_bounds__(256) void raster_span_multi_kernel(const RasterGroup *__restrict__ groups, uint32_t n_groups, unsigned long long total_wg,
+                                                                const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth, int32_t *__restrict__ far,
+                                                                uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi, uint32_t rw, uint32_t rh,
+                                                                const int4 *__restrict__ boxes, const uint32_t *__restrict__ box_off,
+                                                                const uint32_t *__restrict__ image_of)
+{
+    __shared__ float sh[4][kSetupWords][64];
+    __shared__ uint32_t shq[4][192];
+    for (unsigned long long wg = blockIdx.x; wg < total_wg; wg += gridDim.x) {
+        uint32_t lo = 0, hi = n_groups;                          // as raster_multi_kernel
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (groups[mid].first_wg <= wg) lo = mid; else hi = mid;
+        }
+        lo = __builtin_amdgcn_readfirstlane(lo);
+        const RasterGroup &gr = groups[lo];
+        const unsigned long long local = wg - gr.first_wg;
+        const uint32_t run = (uint32_t)(local / gr.tri_blocks), block = (uint32_t)(local - (unsigned long long)run * gr.tri_blocks);
+        const uint32_t ti = block * 256 + threadIdx.x;
+        float tv[9];
+        load_triangle(gr.tris, gr.n_tris, ti, tv);
+        const size_t first = (image_of || box_off) ? 0 : (size_t)gr.first * rw * rh;
+        raster_runs<false, true>(tv, ti, gr.n_tris, run, poses + gr.first, depth + first, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
+                                 gr.count, gr.run, box_off ? box_off + gr.first : nullptr, image_of ? image_of + gr.first : nullptr, sh, shq, far + first);
+    }
+}
+// the far plane's "nothing drawn" (INT_MIN) to 0, as max2zero_kernel does for the near plane's INT_MAX
+__global__ __launch_bounds__(256) void min2zero_kernel(int32_t *d, size_t n)
+{
+    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * 256 * 4;
+    for (; i + 3 < n; i += stride) {
+        int4 v = *reinterpret_cast<int4 *>(d + i);
+        v.x = (v.x == INT_MIN) ? 0 : v.x; v.y = (v.y == INT_MIN) ? 0 : v.y;
+        v.z = (v.z == INT_MIN) ? 0 : v.z; v.w = (v.w == INT_MIN) ? 0 : v.w;
+        *reinterpret_cast<int4 *>(d + i) = v;
+    }
+    if (i < n) for (size_t k = i; k < n && k < i + 4; ++k) if (d[k] == INT_MIN) d[k] = 0;
+}
+// fill_box_kernel for the two planes of a span render: INT_MAX into the near box, INT_MIN into the far one
+__global__ __launch_bounds__(256) void fill_span_box_kernel(int32_t *__restrict__ depth, int32_t *__restrict__ far, const int4 *__restrict__ bbox,
+                                                            uint32_t width, uint32_t height, const uint32_t *__restrict__ box_off)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const int4 bb = bbox[blockIdx.y];
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint32_t row = blockIdx.x * kBoxRowsPerBlock + (threadIdx.x >> 6) * 4 + r;
+        if (row >= height) return;
+        const int ry = (int)height - 1 - (int)row;
+        if (ry < bb.y || ry > bb.w) continue;
+        int32_t *near_line = box_line(depth, box_off, bb, blockIdx.y, row, width, height);
+        int32_t *far_line = box_line(far, box_off, bb, blockIdx.y, row, width, height);
+        for (int x = bb.x + (int)lane; x <= bb.z; x += 64) { near_line[x] = INT_MAX; far_line[x] = INT_MIN; }
     }
 }
 
@@ -871,14 +946,11 @@ hipError_t launch_model_aabb_multi(const pr_mesh_ref *meshes_dev, const pr_mesh_
     return hipGetLastError();
 }
 
-// groups_host (pinned; groups_mapped = the same memory as the device sees it): tris, n_tris, first, count of each group of consecutive
-// hypotheses with one mesh.  Completed here (empty groups dropped, run, triangle blocks, first workgroup), staged to groups_dev, launched.
-hipError_t launch_raster_multi(RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups, RasterGroup *groups_dev, const pr_mat4 *poses_dev,
-                               int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh,
-                               const int4 *boxes, const uint32_t *box_off, const uint32_t *image_of, hipStream_t s)
+// the groups the host filled (tris, n_tris, first, count), completed in place: empty groups dropped, run, triangle blocks, first workgroup; returns how many are left
+static uint32_t complete_raster_groups(RasterGroup *groups_host, uint32_t n_groups, unsigned long long &total)
 {
     uint32_t n = 0;
-    unsigned long long total = 0;
+    total = 0;
     for (uint32_t i = 0; i < n_groups; ++i) {
         RasterGroup gr = groups_host[i];
         if (gr.n_tris == 0 || gr.count == 0) continue;             // an empty mesh renders nothing
@@ -888,6 +960,16 @@ hipError_t launch_raster_multi(RasterGroup *groups_host, const void *groups_mapp
         total += (unsigned long long)gr.tri_blocks * ((gr.count + gr.run - 1) / gr.run);
         groups_host[n++] = gr;
     }
+    return n;
+}
+// groups_host (pinned; groups_mapped = the same memory as the device sees it): tris, n_tris, first, count of each group of consecutive
+// hypotheses with one mesh.  Completed here (complete_raster_groups), staged to groups_dev, launched.
+hipError_t launch_raster_multi(RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups, RasterGroup *groups_dev, const pr_mat4 *poses_dev,
+                               int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh,
+                               const int4 *boxes, const uint32_t *box_off, const uint32_t *image_of, hipStream_t s)
+{
+    unsigned long long total = 0;
+    const uint32_t n = complete_raster_groups(groups_host, n_groups, total);
     if (n == 0) return hipSuccess;
     hipError_t e = launch_stage_words(groups_mapped, groups_dev, sizeof(RasterGroup) * n, s);
     if (e != hipSuccess) return e;
@@ -913,6 +995,72 @@ hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_ind
                                          bbox, box_off, nullptr, s); if (e != hipSuccess) return e; }
     launch_count_boxes(depth, bbox, box_off, 0, n_poses, width, height, row_count, s);
     return launch_box_scan(row_count, height, row_off, counts, n_poses, nullptr, nullptr, nullptr, s);
+}
+
+// ---- span renders: the nearest and the farthest fragment of every pixel (pr_render_span, pr_pose_penetration) ------------------------------------
+hipError_t launch_min2zero(int32_t *far, size_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(min2zero_kernel, dim3(cap_grid((n + 1023) / 1024)), dim3(256), 0, s, far, n);
+    return hipGetLastError();
+}
+// launch_raster into two stacks of full images (the caller filled depth with INT_MAX and far with INT_MIN)
+hipError_t launch_raster_span(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, int32_t *depth, int32_t *far,
+                              uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh, hipStream_t s)
+{
+    if (n_tris == 0 || n_poses == 0) return hipSuccess;
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
+        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
+        const uint32_t run = raster_pose_run(n_tris, np);
+        hipLaunchKernelGGL(raster_span_kernel, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
+                           depth + (size_t)p0 * rw * rh, far + (size_t)p0 * rw * rh, width, height, proj, roi, rw, rh, (const int4 *)nullptr, np, run,
+                           (const uint32_t *)nullptr);
+    }
+    return hipGetLastError();
+}
+// launch_render_boxes' layout (boxes computed here, packed at box_off) with a far plane at the same offsets; no row counts: the pair kernel
+// walks the boxes themselves.  At most 32768 hypotheses (the caller's limit is PR_PENETRATION_MAX_POSES).
+static void launch_fill_span_boxes(int32_t *depth, int32_t *far, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
+                                   hipStream_t s)
+{
+    hipLaunchKernelGGL(fill_span_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, n_poses), dim3(256), 0, s, depth, far, bbox, width, height, box_off);
+}
+hipError_t launch_render_span_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb, int4 *bbox,
+                                    int32_t *depth, int32_t *far, uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s)
+{
+    if (n_poses == 0) return hipSuccess;
+    if (n_poses > 32768 || !box_off) return hipErrorInvalidValue;
+    const pr_roi none{ 0, 0, 0, 0 };
+    hipLaunchKernelGGL(pose_bbox_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabb, poses_dev, n_poses, proj, width, height, none, bbox);
+    launch_box_pack(bbox, n_poses, box_off, s);
+    launch_fill_span_boxes(depth, far, bbox, box_off, n_poses, width, height, s);
+    if (n_tris > 0) {
+        const uint32_t run = raster_pose_run(n_tris, n_poses);
+        hipLaunchKernelGGL(raster_span_kernel, dim3((n_tris + 255) / 256, (n_poses + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev, depth, far,
+                           width, height, proj, none, width, height, (const int4 *)bbox, n_poses, run, (const uint32_t *)box_off);
+    }
+    return hipGetLastError();
+}
+// the same for a mixed batch (launch_render_boxes_multi's tables)
+hipError_t launch_render_span_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
+                                          RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, int32_t *far,
+                                          uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s)
+{
+    if (n_poses == 0) return hipSuccess;
+    if (n_poses > 32768 || !box_off) return hipErrorInvalidValue;
+    const pr_roi none{ 0, 0, 0, 0 };
+    hipLaunchKernelGGL(pose_bbox_multi_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabbs, box_index, poses_dev, n_poses, proj, width, height, none, bbox);
+    launch_box_pack(bbox, n_poses, box_off, s);
+    launch_fill_span_boxes(depth, far, bbox, box_off, n_poses, width, height, s);
+    unsigned long long total = 0;
+    const uint32_t n = complete_raster_groups(groups_host, n_groups, total);
+    if (n == 0) return hipSuccess;
+    hipError_t e = launch_stage_words(groups_mapped, groups_dev, sizeof(RasterGroup) * n, s);
+    if (e != hipSuccess) return e;
+    const unsigned long long grid = total < (1ull << 22) ? total : (1ull << 22);
+    hipLaunchKernelGGL(raster_span_multi_kernel, dim3((uint32_t)grid), dim3(256), 0, s, (const RasterGroup *)groups_dev, n, total, poses_dev, depth, far,
+                       width, height, proj, none, width, height, (const int4 *)bbox, (const uint32_t *)box_off, (const uint32_t *)nullptr);
+    return hipGetLastError();
 }
 
 }  // namespace prk

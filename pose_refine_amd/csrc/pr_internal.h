@@ -152,10 +152,7 @@ struct DevIcpState {
 
 // ---- launchers (all asynchronous on `s`) ----------------------------------------------------------
 hipError_t launch_fill_i32(int32_t *dst, size_t n, int32_t v, hipStream_t s);
-hipError_t launch_raster(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses,
-                         int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi,
-                         uint32_t rw, uint32_t rh, hipStream_t s);
-hipError_t launch_max2zero(int32_t *depth, size_t n, hipStream_t s);
+hipError_t launch_sentinel2zero(int32_t *plane, size_t n, bool far, hipStream_t s);      // "nothing drawn" to 0: INT_MAX of a near plane, INT_MIN of a far one
 
 // depth -> cloud: rows are counted, scanned per image, then emitted in row-major order.
 // images: n_img images of width*height pixels each `img_stride` elements apart; cloud i is written
@@ -185,13 +182,6 @@ struct BatchCheck {
     const uint32_t *fa, *fb, *fc; unsigned long long na, nb, nc; const uint32_t *fp_expected;
     uint32_t *flag;
 };
-hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb,
-                               int4 *bbox, int32_t *depth, uint32_t *row_count, uint32_t *row_off, uint32_t *counts,
-                               uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s, bool compute_boxes = true,
-                               PoseMeta *meta = nullptr, DevIcpState *st = nullptr, uint32_t *arrive = nullptr,
-                               const uint32_t *box_off = nullptr,    // box_off: the boxes packed into `depth` at these offsets (ints), each with its own pitch (fill_box_kernel)
-                               const BatchCheck *check = nullptr,
-                               bool bands = false);                  // bands (with box_off, compute_boxes = false): the boxes in the banded layout of pose_box.h (band_box), placed by box_slot_of -- fill, raster and count then address that layout, and so must launch_emit_box
 // Asynchronous path, option tight_box (pose_tight_box_kernel): bbox[i], the loose box the host uploaded, overwritten by its intersection with the
 // hull of the projected vertices `verts` ({x, y, z, 0}: the mesh's distinct vertices); then, per sub-batch, the packed offsets of those boxes.
 hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_mat4 *poses_dev, uint32_t n_poses, const pr_mat4 &proj,
@@ -199,7 +189,7 @@ hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_ma
 hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t *box_off, uint32_t height, bool bands, hipStream_t s);
 // Mixed batches (pr_*_multi): the hypotheses grouped by mesh.  One group of consecutive hypotheses [first, first + count) of a launch that share
 // a mesh; raster_multi_kernel's workgroups [first_wg, first_wg + tri_blocks * ceil(count / run)) are its (triangle block, pose run) pairs.
-// The host fills tris, n_tris, first and count; launch_raster_multi the rest.  48 bytes: staged in 16-byte words.
+// The host fills tris, n_tris, first and count; launch_raster the rest.  48 bytes: staged in 16-byte words.
 struct RasterGroup {
     const pr_triangle *tris;
     uint32_t n_tris, first, count, run;
@@ -209,25 +199,31 @@ struct RasterGroup {
 static_assert(sizeof(RasterGroup) == 48, "RasterGroup: three 16-byte words");
 // keys: 6 x n_meshes words of scratch; aabb_out: 6 floats per mesh (launch_model_aabb's box for each mesh alone)
 hipError_t launch_model_aabb_multi(const pr_mesh_ref *meshes_dev, const pr_mesh_ref *meshes_host, uint32_t n_meshes, uint32_t *keys, float *aabb_out, hipStream_t s);
-// full frames (boxes null; image_of, if given: image of each hypothesis) or boxes as launch_render_boxes lays them out
-hipError_t launch_raster_multi(RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups, RasterGroup *groups_dev, const pr_mat4 *poses_dev,
-                               int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh,
-                               const int4 *boxes, const uint32_t *box_off, const uint32_t *image_of, hipStream_t s);
-hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
-                                     RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, uint32_t *row_count,
-                                     uint32_t *row_off, uint32_t *counts, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s,
-                                     const uint32_t *box_off);
-// Span renders (raster.hip): every fragment into a near plane (atomicMin) and a far plane (atomicMax) of one layout.  launch_raster_span: full
-// images the caller filled with INT_MAX / INT_MIN; launch_min2zero: the far plane's INT_MIN to 0.  launch_render_span_boxes(_multi): pixel boxes
-// computed here (no ROI), packed at box_off (written here) in both planes, filled and rastered; at most 32768 hypotheses.
-hipError_t launch_min2zero(int32_t *far, size_t n, hipStream_t s);
-hipError_t launch_raster_span(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, int32_t *depth, int32_t *far,
-                              uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh, hipStream_t s);
-hipError_t launch_render_span_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb, int4 *bbox,
-                                    int32_t *depth, int32_t *far, uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s);
-hipError_t launch_render_span_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
-                                          RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, int32_t *far,
-                                          uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s);
+// What a raster draws: one mesh for every hypothesis (tris, n_tris), or -- groups_host given -- a mixed batch's groups (groups_host: pinned, filled by the
+// host; groups_mapped: the same memory as the device sees it; groups_dev: where launch_raster stages the completed groups).  For launch_render_boxes'
+// box front end also the model box(es), 6 floats each, and (mixed batch) the box every hypothesis takes.
+struct RasterMesh {
+    const pr_triangle *tris; uint32_t n_tris;
+    RasterGroup *groups_host; const void *groups_mapped; uint32_t n_groups; RasterGroup *groups_dev;
+    const float *aabb; const uint32_t *box_index;
+};
+// Where the fragments go, under which camera.  depth: the near plane (atomicMin); far: null, or a second plane of the same layout that takes every
+// fragment with atomicMax (span renders).  boxes null: full images of rw x rh (the frame, or the window `roi`), hypothesis i in image i -- of a mixed
+// batch in image image_of[i] when that is given.  boxes: each hypothesis' pixel box, in full frames or (box_off) packed into the plane at these
+// offsets (ints), each with its own pitch; bands: packed in the banded layout of pose_box.h (band_box), placed by box_slot_of -- fill, raster and
+// count then address that layout, and so must launch_emit_box.
+struct RasterTarget {
+    int32_t *depth, *far;
+    const int4 *boxes; const uint32_t *box_off, *image_of;
+    uint32_t rw, rh; pr_roi roi; bool bands;
+    uint32_t width, height; const pr_mat4 *proj;
+};
+// launch_render_boxes' row outputs (all null: none, the boxes are only drawn); meta, st, arrive: the asynchronous path's per-hypothesis records
+struct BoxRows { uint32_t *row_count, *row_off, *counts; PoseMeta *meta; DevIcpState *st; uint32_t *arrive; };
+// the caller filled the plane(s) with "nothing drawn" (INT_MAX; far: INT_MIN); check (one mesh only): rides on the first hypothesis' workgroups
+hipError_t launch_raster(const RasterMesh &mesh, const pr_mat4 *poses_dev, uint32_t n_poses, const RasterTarget &target, const BatchCheck *check, hipStream_t s);
+hipError_t launch_render_boxes(const RasterMesh &mesh, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, const RasterTarget &target, const BoxRows &rows,
+                               hipStream_t s, bool compute_boxes = true, const BatchCheck *check = nullptr);
 // solid.hip: pr_pose_penetration's P x P records (6 words each: pr_pair_solid) from the two planes of a span render of all P hypotheses; every
 // record is written, none needs clearing
 hipError_t launch_pair_solid(const int32_t *depth, const int32_t *far, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t height,

@@ -18,6 +18,16 @@ static bool lds_opt_in(const void *fn, int slot, uint32_t bytes)
     return true;
 }
 static inline uint32_t cap_grid(size_t want) { return (uint32_t)(want < 1 ? 1 : (want > 8192 ? 8192 : want)); }
+// fn(p0, np) over n hypotheses in runs of at most 32768 -- one per grid row, and grid.y is limited to 65535; ends at the first error
+template <class Fn>
+static inline hipError_t for_pose_launches(uint32_t n, Fn fn)
+{
+    for (uint32_t p0 = 0; p0 < n; p0 += 32768) {
+        const hipError_t e = fn(p0, (n - p0 < 32768) ? (n - p0) : 32768u);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 // row scans of the depth -> cloud stage (d2c.hip), called from the render and scene launchers of other files
 hipError_t launch_d2c_scan(const uint32_t *row_count, uint32_t gh, uint32_t *row_off, uint32_t *counts, uint32_t n_img, hipStream_t s);

@@ -30,23 +30,6 @@ std::pair<size_t, size_t> image_extent(pr_roi roi, size_t W, size_t H)
     return { W, H };
 }
 
-int render_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t P, size_t W, size_t H,
-                const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev, bool zero_empty)
-{
-    if ((!tris_dev && n_tris > 0) || (P && (!poses_host || !depth_dev)) || !proj || W == 0 || H == 0) { set_error("pr_render: bad arguments"); return PR_ERR_INVALID; }   // (an empty model has no array, no hypotheses need none)
-    if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
-    if (!roi_ok(roi, (uint32_t)W, (uint32_t)H)) { set_error("pr_render: roi out of image"); return PR_ERR_INVALID; }
-    if (P == 0) return PR_OK;
-    const auto [rw, rh] = image_extent(roi, W, H);
-    SpanGuard sp(kSpanRender);
-    PR_TRY(stage_poses(poses_host, P));
-    HIP_TRY(prk::launch_fill_i32(depth_dev, P * rw * rh, INT32_MAX, g->stream));
-    HIP_TRY(prk::launch_raster(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), (uint32_t)P, depth_dev, (uint32_t)W, (uint32_t)H,
-                               *proj, roi, (uint32_t)rw, (uint32_t)rh, g->stream));
-    if (zero_empty) HIP_TRY(prk::launch_max2zero(depth_dev, P * rw * rh, g->stream));
-    return PR_OK;
-}
-
 template <typename T>
 int depth2cloud_impl(const T *depth_dev, uint32_t W, uint32_t H, const float K[9], uint32_t stride, uint32_t tl_x, uint32_t tl_y,
                      pr_vec3 **cloud_out, uint32_t *n_out)
@@ -150,34 +133,58 @@ uint32_t chunk_groups(const MeshPlan &pl, uint32_t p0, uint32_t np, prk::RasterG
     }
     return n;
 }
-// chunk [p0, p0 + np) of a batch rendered into per-pose pixel boxes (raster + row counts + row scan), poses staged first.  box_off: the boxes
-// packed (kBoxPack) or null.  bands: the LDS-band raster (option raster_mode 1) -- single mesh only; a mixed batch always uses the box raster.
-int render_chunk(const MeshSource &src, const pr_mat4 *poses_host, uint32_t p0, uint32_t np, uint32_t chunk, uint32_t W, uint32_t H,
-                 const pr_mat4 *proj, pr_roi roi, uint32_t *box_off, bool bands)
+// Positions [p0, p0 + np) of a mixed batch as launch_raster and launch_render_boxes take them, through the tables multi_layout lays out for chunks of
+// `chunk` (g->multi, g->h_multi: sized by the caller): `index`, one word per position, is staged into the index slot (mesh.box_index: the box every
+// hypothesis takes, or whatever else the caller keeps per position) and the groups are left in the pinned block for launch_raster to complete and stage.
+int stage_groups(const MeshPlan &pl, uint32_t p0, uint32_t np, uint32_t chunk, const uint32_t *index, prk::RasterMesh &mesh)
 {
-    PR_TRY(stage_poses(poses_host + p0, np));
-    if (!src.plan) {
-        if (bands)
-            HIP_TRY(prk::launch_render_bands(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
-                                             g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
-                                             g->counts.as<uint32_t>(), W, H, *proj, roi, (uint32_t)g->n_cus, g->stream));
-        else
-            HIP_TRY(prk::launch_render_boxes(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
-                                             g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
-                                             g->counts.as<uint32_t>(), W, H, *proj, roi, g->stream, /*compute_boxes=*/true, nullptr, nullptr, nullptr, box_off));
-        return PR_OK;
-    }
-    const MeshPlan &pl = *src.plan;
     const MultiLayout l = multi_layout(pl.mesh.size(), chunk);
     unsigned char *h = g->h_multi.as<unsigned char>(), *hm = g->h_multi.dev_as<unsigned char>(), *d = g->multi.as<unsigned char>();
-    std::memcpy(h + l.box, pl.box.data() + p0, sizeof(uint32_t) * np);
+    std::memcpy(h + l.box, index, sizeof(uint32_t) * np);
     HIP_TRY(prk::launch_stage_words(hm + l.box, d + l.box, sizeof(uint32_t) * np, g->stream));
-    prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
-    const uint32_t n_groups = chunk_groups(pl, p0, np, groups);
-    HIP_TRY(prk::launch_render_boxes_multi(g->aabb.as<float>(), reinterpret_cast<const uint32_t *>(d + l.box), groups, hm + l.groups,
-                                           n_groups, reinterpret_cast<prk::RasterGroup *>(d + l.groups), g->poses.as<pr_mat4>(), np, g->bbox.as<int4>(),
-                                           g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(), g->counts.as<uint32_t>(),
-                                           W, H, *proj, roi, g->stream, box_off));
+    mesh = prk::RasterMesh{};
+    mesh.groups_host = reinterpret_cast<prk::RasterGroup *>(h + l.groups); mesh.groups_mapped = hm + l.groups;
+    mesh.groups_dev = reinterpret_cast<prk::RasterGroup *>(d + l.groups);
+    mesh.n_groups = chunk_groups(pl, p0, np, mesh.groups_host);
+    mesh.box_index = reinterpret_cast<const uint32_t *>(d + l.box);
+    return PR_OK;
+}
+// The workspaces of a chunk of np renders of img = W x H pixels: the depth boxes (packed: kBoxPack), the pixel boxes with the offsets of the packed boxes
+// behind them (box_pack_offsets_kernel) -- returned in box_off -- and (rows) row counts, row offsets and cloud sizes.
+int chunk_workspaces(size_t img, uint32_t H, uint32_t np, uint32_t *&box_off, bool rows = true)
+{
+    PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
+    if (rows) {
+        PR_TRY(g->row_count.ensure(sizeof(uint32_t) * (size_t)H * np));
+        PR_TRY(g->row_off.ensure(sizeof(uint32_t) * (size_t)H * np));
+        PR_TRY(g->counts.ensure(sizeof(uint32_t) * np));
+    }
+    PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
+    box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np);
+    return PR_OK;
+}
+// chunk [p0, p0 + np) of a batch rendered into per-pose pixel boxes (raster + row counts + row scan), poses staged first.  box_off: the boxes
+// packed (kBoxPack) or null.  bands: the LDS-band raster (option raster_mode 1) -- single mesh only; a mixed batch always uses the box raster.
+// far: a second plane at the same box_off as g->depth that takes the farthest fragment of every pixel (span render) -- then no row outputs:
+// nothing makes clouds of these renders.
+int render_chunk(const MeshSource &src, const pr_mat4 *poses_host, uint32_t p0, uint32_t np, uint32_t chunk, uint32_t W, uint32_t H,
+                 const pr_mat4 *proj, pr_roi roi, uint32_t *box_off, bool bands, int32_t *far = nullptr)
+{
+    PR_TRY(stage_poses(poses_host + p0, np));
+    if (!src.plan && bands) {
+        HIP_TRY(prk::launch_render_bands(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), np, g->aabb.as<float>(), g->bbox.as<int4>(),
+                                         g->depth.as<int32_t>(), g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(),
+                                         g->counts.as<uint32_t>(), W, H, *proj, roi, (uint32_t)g->n_cus, g->stream));
+        return PR_OK;
+    }
+    prk::RasterMesh mesh{};
+    if (src.plan) PR_TRY(stage_groups(*src.plan, p0, np, chunk, src.plan->box.data() + p0, mesh));
+    else { mesh.tris = src.tris; mesh.n_tris = (uint32_t)src.n_tris; }
+    mesh.aabb = g->aabb.as<float>();
+    prk::RasterTarget t{};
+    t.depth = g->depth.as<int32_t>(); t.far = far; t.box_off = box_off; t.roi = roi; t.width = W; t.height = H; t.proj = proj;
+    const prk::BoxRows rows = far ? prk::BoxRows{} : prk::BoxRows{ g->row_count.as<uint32_t>(), g->row_off.as<uint32_t>(), g->counts.as<uint32_t>(), nullptr, nullptr, nullptr };
+    HIP_TRY(prk::launch_render_boxes(mesh, g->poses.as<pr_mat4>(), np, g->bbox.as<int4>(), t, rows, g->stream));
     return PR_OK;
 }
 
@@ -288,16 +295,12 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
     PR_TRY(model_boxes(src, chunk));
     for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
         const uint32_t np = std::min(chunk, P - p0);
-        PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
-        PR_TRY(g->row_count.ensure(sizeof(uint32_t) * (size_t)H * np));
-        PR_TRY(g->row_off.ensure(sizeof(uint32_t) * (size_t)H * np));
-        PR_TRY(g->counts.ensure(sizeof(uint32_t) * np));
+        uint32_t *box_off = nullptr;
+        PR_TRY(chunk_workspaces(img, H, np, box_off));
         PR_TRY(g->h_counts.ensure(sizeof(uint32_t) * np));
         uint32_t *h_counts = g->h_counts.as<uint32_t>();
-        // per-pose pixel boxes; raster + row counts + row scan
-        PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));   // boxes, then the offsets of the packed boxes (box_pack_offsets_kernel)
-        uint32_t *box_off = (src.plan || opt.raster_mode != 1) ? reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np) : nullptr;       // (the band raster writes full frames)
-        {
+        if (!src.plan && opt.raster_mode == 1) box_off = nullptr;         // (the band raster writes full frames)
+        {                                                            // per-pose pixel boxes; raster + row counts + row scan
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, poses_host, p0, np, chunk, W, H, &job.proj, job.roi, box_off, !src.plan && opt.raster_mode == 1));
         }
@@ -432,11 +435,8 @@ int score_core(const ScoreRequest &req)
     }
     for (uint32_t p0 = 0; p0 < P; p0 += chunk) {
         const uint32_t np = std::min(chunk, P - p0);
-        PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
-        PR_TRY(g->row_count.ensure(sizeof(uint32_t) * (size_t)H * np));
-        PR_TRY(g->row_off.ensure(sizeof(uint32_t) * (size_t)H * np));
-        PR_TRY(g->counts.ensure(sizeof(uint32_t) * np));
-        PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
+        uint32_t *box_off = nullptr;
+        PR_TRY(chunk_workspaces(img, H, np, box_off));
         PR_TRY(g->scores.ensure(sizeof(pr_pose_score) * np));
         PR_TRY(g->h_scores.ensure(sizeof(pr_pose_score) * np));
         if (contours) { PR_TRY(g->contours.ensure(sizeof(pr_pose_contour) * np)); PR_TRY(g->h_contours.ensure(sizeof(pr_pose_contour) * np)); }
@@ -447,7 +447,6 @@ int score_core(const ScoreRequest &req)
             PR_TRY(g->info_part.ensure(sizeof(double) * prk::kFitSums * (size_t)fit_nblk * np));
             PR_TRY(g->h_info_out.ensure(sizeof(pr_pose_info) * np));
         }
-        uint32_t *box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np);
         {
             SpanGuard sp(kSpanRender);
             PR_TRY(render_chunk(src, req.poses, p0, np, chunk, W, H, req.proj, req.roi, box_off, /*bands=*/false));
@@ -644,14 +643,10 @@ int vsd_core(const MeshSource &src, const pr_mat4 *renders, const pr_mat4 *one_g
     std::vector<pr_mat4> with_gt(one_gt ? chunk : 0);
     for (uint32_t q0 = 0; q0 < P; q0 += pairs_chunk) {
         const uint32_t nq = std::min(pairs_chunk, P - q0), np = one_gt ? nq + 1 : 2 * nq;
-        PR_TRY(g->depth.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * np));
-        PR_TRY(g->row_count.ensure(sizeof(uint32_t) * (size_t)H * np));
-        PR_TRY(g->row_off.ensure(sizeof(uint32_t) * (size_t)H * np));
-        PR_TRY(g->counts.ensure(sizeof(uint32_t) * np));
-        PR_TRY(g->bbox.ensure(sizeof(int4) * np + sizeof(uint32_t) * np));
+        uint32_t *box_off = nullptr;
+        PR_TRY(chunk_workspaces(img, H, np, box_off));
         PR_TRY(g->vsd_rec.ensure(sizeof(pr_vsd_counts) * nq));
         PR_TRY(g->h_vsd.ensure(sizeof(pr_vsd_counts) * nq));
-        uint32_t *box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + np);
         if (one_gt) { std::copy(renders + q0, renders + q0 + nq, with_gt.begin()); with_gt[nq] = *one_gt; }
         {
             SpanGuard sp(kSpanRender);
@@ -685,64 +680,24 @@ std::vector<pr_mat4> interleaved_pairs(const pr_mat4 *est, const pr_mat4 *gt, ui
 }
 
 // ---- interpenetration of hypotheses (pr_render_span, pr_pose_penetration, pr_pose_penetration_multi) -----------------------------------------------
-// render_impl with a far plane: both stacks filled by kernels, one raster pass, "nothing drawn" to 0 in both
-int render_span_impl(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t P, size_t W, size_t H, const pr_mat4 *proj, pr_roi roi,
-                     int32_t *near_dev, int32_t *far_dev)
-{
-    PR_TRY(render_impl(tris_dev, n_tris, poses_host, 0, W, H, proj, roi, near_dev, true));      // pr_render's checks, with no hypotheses
-    if (P == 0) return PR_OK;
-    if (!poses_host || !near_dev || !far_dev) { set_error("pr_render_span: bad arguments"); return PR_ERR_INVALID; }
-    const auto [rw, rh] = image_extent(roi, W, H);
-    SpanGuard sp(kSpanRender);
-    PR_TRY(stage_poses(poses_host, P));
-    HIP_TRY(prk::launch_fill_i32(near_dev, P * rw * rh, INT32_MAX, g->stream));
-    HIP_TRY(prk::launch_fill_i32(far_dev, P * rw * rh, INT32_MIN, g->stream));
-    HIP_TRY(prk::launch_raster_span(tris_dev, (uint32_t)n_tris, g->poses.as<pr_mat4>(), (uint32_t)P, near_dev, far_dev, (uint32_t)W, (uint32_t)H, *proj, roi,
-                                    (uint32_t)rw, (uint32_t)rh, g->stream));
-    HIP_TRY(prk::launch_max2zero(near_dev, P * rw * rh, g->stream));
-    HIP_TRY(prk::launch_min2zero(far_dev, P * rw * rh, g->stream));
-    return PR_OK;
-}
-// render_chunk's layout for ALL P hypotheses of a call, with the far plane (g->solid_far) at the same box_off as the near one (g->depth): poses staged,
-// model_boxes' boxes, packed pixel boxes, both planes filled and rastered in one pass.  No row counts: nothing makes clouds of these renders.
-int render_span_boxes(const MeshSource &src, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, uint32_t *box_off)
-{
-    PR_TRY(stage_poses(poses_host, P));
-    if (!src.plan) {
-        HIP_TRY(prk::launch_render_span_boxes(src.tris, (uint32_t)src.n_tris, g->poses.as<pr_mat4>(), P, g->aabb.as<float>(), g->bbox.as<int4>(),
-                                              g->depth.as<int32_t>(), g->solid_far.as<int32_t>(), W, H, *proj, box_off, g->stream));
-        return PR_OK;
-    }
-    const MeshPlan &pl = *src.plan;
-    const MultiLayout l = multi_layout(pl.mesh.size(), P);
-    unsigned char *h = g->h_multi.as<unsigned char>(), *hm = g->h_multi.dev_as<unsigned char>(), *d = g->multi.as<unsigned char>();
-    std::memcpy(h + l.box, pl.box.data(), sizeof(uint32_t) * P);
-    HIP_TRY(prk::launch_stage_words(hm + l.box, d + l.box, sizeof(uint32_t) * P, g->stream));
-    prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
-    const uint32_t n_groups = chunk_groups(pl, 0, P, groups);
-    HIP_TRY(prk::launch_render_span_boxes_multi(g->aabb.as<float>(), reinterpret_cast<const uint32_t *>(d + l.box), groups, hm + l.groups, n_groups,
-                                                reinterpret_cast<prk::RasterGroup *>(d + l.groups), g->poses.as<pr_mat4>(), P, g->bbox.as<int4>(),
-                                                g->depth.as<int32_t>(), g->solid_far.as<int32_t>(), W, H, *proj, box_off, g->stream));
-    return PR_OK;
-}
 // A small core beside vsd_core: the model box(es), the span render of all P hypotheses (checked: penetration_args_ok -- both planes are resident
-// together, there are no chunks), one pair kernel (solid.hip), the P x P records back through pinned memory.  The context's own stream and workspaces:
-// a batch pending on a slot is neither waited for nor disturbed.  out: in the order of `poses` (of a mixed batch: its plan's).
+// together, there are no chunks: render_chunk's layout for the whole call, the far plane in g->solid_far at the near one's box_off), one pair kernel
+// (solid.hip), the P x P records back through pinned memory.  The context's own stream and workspaces: a batch pending on a slot is neither waited
+// for nor disturbed.  out: in the order of `poses` (of a mixed batch: its plan's).
 int solid_core(const MeshSource &src, const pr_mat4 *poses, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, int32_t slack, pr_pair_solid *out)
 {
     constexpr uint32_t kWords = sizeof(pr_pair_solid) / sizeof(uint32_t);
     static_assert(sizeof(pr_pair_solid) == 24 && kWords == 6 && offsetof(pr_pair_solid, sum_mm) == 16, "pr_pair_solid: four counters and a 64-bit sum");
-    const size_t plane = ((size_t)W * H + prk::kBoxPack) * P, n_rec = (size_t)P * P;
+    const size_t img = (size_t)W * H, n_rec = (size_t)P * P;
+    uint32_t *box_off = nullptr;
     PR_TRY(model_boxes(src, P));
-    PR_TRY(g->depth.ensure(sizeof(int32_t) * plane));
-    PR_TRY(g->solid_far.ensure(sizeof(int32_t) * plane));
-    PR_TRY(g->bbox.ensure(sizeof(int4) * P + sizeof(uint32_t) * P));
+    PR_TRY(chunk_workspaces(img, H, P, box_off, /*rows=*/false));
+    PR_TRY(g->solid_far.ensure(sizeof(int32_t) * (img + prk::kBoxPack) * P));
     PR_TRY(g->solid_rec.ensure(sizeof(pr_pair_solid) * n_rec));
     PR_TRY(g->h_solid.ensure(sizeof(pr_pair_solid) * n_rec));
-    uint32_t *box_off = reinterpret_cast<uint32_t *>(g->bbox.as<int4>() + P);
     {
         SpanGuard sp(kSpanRender);
-        PR_TRY(render_span_boxes(src, poses, P, W, H, proj, box_off));
+        PR_TRY(render_chunk(src, poses, 0, P, P, W, H, proj, pr_roi{ 0, 0, 0, 0 }, box_off, /*bands=*/false, g->solid_far.as<int32_t>()));
     }
     ReadBack back;
     HIP_TRY(prk::launch_pair_solid(g->depth.as<int32_t>(), g->solid_far.as<int32_t>(), g->bbox.as<int4>(), box_off, P, H, slack, g->solid_rec.as<uint32_t>(), g->stream));
@@ -770,34 +725,41 @@ void compose_outputs(ScoreRequest &r, uint16_t *labels_dev, int32_t *depth_dev, 
     r.labels_dev = labels_dev; r.depth_dev = depth_dev; r.visible = visible_host; r.frame = frame_host;
 }
 
-// render_impl for a mixed batch: full frames (or the ROI) in the caller's order -- the raster writes hypothesis j of the grouped batch into image order[j]
-int render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, const pr_mat4 *poses_host, size_t P, size_t W, size_t H,
-                 const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev)
+// pr_render, pr_render_span and pr_render_multi: P full frames (or the ROI) of one mesh, or of a mesh table in the caller's order -- the hypotheses are
+// grouped by mesh and the raster writes hypothesis j of the grouped batch into image order[j].  The planes are filled by kernels, one raster pass draws
+// into near_dev (the nearest fragment of every pixel) and, given far_dev, into it as well (the farthest), and (zero_empty) "nothing drawn" becomes 0
+// in both.  Every check (render_args_ok, then the mesh table's) comes before anything is written.
+struct FrameSource { const pr_triangle *tris; size_t n_tris; bool multi; const pr_mesh_ref *meshes; uint32_t n_meshes; const uint32_t *mesh_index; };
+int render_frames(const char *fn, const FrameSource &src, const pr_mat4 *poses_host, size_t P, size_t W, size_t H, const pr_mat4 *proj, pr_roi roi,
+                  int32_t *near_dev, int32_t *far_dev, bool span, bool zero_empty)
 {
-    PR_TRY(render_impl(nullptr, 0, poses_host, 0, W, H, proj, roi, depth_dev, true));     // the single-mesh call's checks, with no hypotheses
+    PR_TRY(render_args_ok(fn, src.multi, span, src.tris, src.n_tris, poses_host, P, W, H, proj, roi, near_dev, far_dev));
     if (P == 0) return PR_OK;
-    if (!poses_host || !depth_dev) { set_error("pr_render_multi: bad arguments"); return PR_ERR_INVALID; }
-    if (P > 0xffffffffull) { set_error("pr_render_multi: more than 2^32 hypotheses"); return PR_ERR_INVALID; }
     MeshPlan pl;
-    PR_TRY(plan_meshes("pr_render_multi", meshes, n_meshes, mesh_index, P, pl));
+    std::vector<pr_mat4> grouped;
+    if (src.multi) {
+        PR_TRY(plan_meshes(fn, src.meshes, src.n_meshes, src.mesh_index, P, pl));
+        grouped = grouped_poses(pl, poses_host);
+        poses_host = grouped.data();
+    }
     const auto [rw, rh] = image_extent(roi, W, H);
-    const std::vector<pr_mat4> poses = grouped_poses(pl, poses_host);
     SpanGuard sp(kSpanRender);
-    PR_TRY(stage_poses(poses.data(), P));
-    const uint32_t G = (uint32_t)pl.mesh.size();
-    const MultiLayout l = multi_layout(G, P);                      // the box-index slot holds the image of every hypothesis here
-    PR_TRY(g->multi.ensure(l.bytes));
-    PR_TRY(g->h_multi.ensure(l.bytes));
-    unsigned char *h = g->h_multi.as<unsigned char>(), *hm = g->h_multi.dev_as<unsigned char>(), *d = g->multi.as<unsigned char>();
-    std::memcpy(h + l.box, pl.order.data(), sizeof(uint32_t) * P);
-    HIP_TRY(prk::launch_stage_words(hm + l.box, d + l.box, sizeof(uint32_t) * P, g->stream));
-    HIP_TRY(prk::launch_fill_i32(depth_dev, P * rw * rh, INT32_MAX, g->stream));
-    prk::RasterGroup *groups = reinterpret_cast<prk::RasterGroup *>(h + l.groups);
-    const uint32_t n_groups = chunk_groups(pl, 0, (uint32_t)P, groups);
-    HIP_TRY(prk::launch_raster_multi(groups, hm + l.groups, n_groups, reinterpret_cast<prk::RasterGroup *>(d + l.groups),
-                                     g->poses.as<pr_mat4>(), depth_dev, (uint32_t)W, (uint32_t)H, *proj, roi, (uint32_t)rw, (uint32_t)rh,
-                                     nullptr, nullptr, reinterpret_cast<const uint32_t *>(d + l.box), g->stream));
-    HIP_TRY(prk::launch_max2zero(depth_dev, P * rw * rh, g->stream));
+    PR_TRY(stage_poses(poses_host, P));
+    prk::RasterMesh mesh{};
+    prk::RasterTarget t{};
+    t.depth = near_dev; t.far = far_dev; t.rw = (uint32_t)rw; t.rh = (uint32_t)rh; t.roi = roi; t.width = (uint32_t)W; t.height = (uint32_t)H; t.proj = proj;
+    if (src.multi) {
+        const MultiLayout l = multi_layout(pl.mesh.size(), P);     // the box-index slot holds the image of every hypothesis here
+        PR_TRY(g->multi.ensure(l.bytes));
+        PR_TRY(g->h_multi.ensure(l.bytes));
+        PR_TRY(stage_groups(pl, 0, (uint32_t)P, (uint32_t)P, pl.order.data(), mesh));
+        t.image_of = mesh.box_index;
+    } else { mesh.tris = src.tris; mesh.n_tris = (uint32_t)src.n_tris; }
+    HIP_TRY(prk::launch_fill_i32(near_dev, P * rw * rh, INT32_MAX, g->stream));
+    if (far_dev) HIP_TRY(prk::launch_fill_i32(far_dev, P * rw * rh, INT32_MIN, g->stream));
+    HIP_TRY(prk::launch_raster(mesh, g->poses.as<pr_mat4>(), (uint32_t)P, t, nullptr, g->stream));
+    if (zero_empty) HIP_TRY(prk::launch_sentinel2zero(near_dev, P * rw * rh, /*far=*/false, g->stream));
+    if (zero_empty && far_dev) HIP_TRY(prk::launch_sentinel2zero(far_dev, P * rw * rh, /*far=*/true, g->stream));
     return PR_OK;
 }
 
@@ -1197,9 +1159,12 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
     // cache hit the event is complete when recorded)
     if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
     if (tight) HIP_TRY(prk::launch_box_pack_offsets(d_box + q0, nq, d_off + q0, H, bands, st));
-    HIP_TRY(prk::launch_render_boxes(raster_tris, (uint32_t)job.n_tris, d_poses + q0, nq, nullptr, d_box + q0, sl.depth.as<int32_t>(),
-                                     sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, W, H, job.proj, none, st,
-                                     /*compute_boxes=*/false, meta, dstate, arrive, d_off + q0, q0 == 0 ? &chk : nullptr, bands));
+    prk::RasterMesh mesh{};
+    mesh.tris = raster_tris; mesh.n_tris = (uint32_t)job.n_tris;
+    prk::RasterTarget target{};
+    target.depth = sl.depth.as<int32_t>(); target.box_off = d_off + q0; target.roi = none; target.bands = bands; target.width = W; target.height = H; target.proj = &job.proj;
+    const prk::BoxRows rows{ sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, meta, dstate, arrive };
+    HIP_TRY(prk::launch_render_boxes(mesh, d_poses + q0, nq, d_box + q0, target, rows, st, /*compute_boxes=*/false, q0 == 0 ? &chk : nullptr));
     if (timed) { sl.spans.end(te, kSpanRender, q0, nq, false, st); te = sl.spans.begin(st); }
     HIP_TRY(prk::launch_emit_box(sl.depth.as<int32_t>(), nq, W, H, d_box + q0, K[0], K[4], K[2], K[5], sl.row_count.as<uint32_t>(),
                                  sl.row_off.as<uint32_t>(), sl.cloud.as<pr_vec3>(), meta, st, d_off + q0, bands));
@@ -1344,7 +1309,7 @@ int pr_render(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_h
     PR_ENTER();
     const auto [rw, rh] = image_extent(roi, width, height);
     if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * rw * rh);
-    PR_TRY(render_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, depth_dev_out, true));
+    PR_TRY(render_frames("pr_render", FrameSource{ tris_dev, n_tris }, poses_host, n_poses, width, height, proj, roi, depth_dev_out, nullptr, false, true));
     HIP_TRY(hipStreamSynchronize(g->stream));            // renderer.cu:295 cudaDeviceSynchronize
     drain_spans();
     return PR_OK;
@@ -1356,7 +1321,7 @@ int pr_render_to_host(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 
     PR_ENTER();
     const auto [rw, rh] = image_extent(roi, width, height);
     PR_TRY(g->depth.ensure(sizeof(int32_t) * std::max<size_t>(1, n_poses * rw * rh)));
-    PR_TRY(render_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, g->depth.as<int32_t>(), true));
+    PR_TRY(render_frames("pr_render", FrameSource{ tris_dev, n_tris }, poses_host, n_poses, width, height, proj, roi, g->depth.as<int32_t>(), nullptr, false, true));
     HIP_TRY(hipMemcpyAsync(depth_host_out, g->depth.p, sizeof(int32_t) * n_poses * rw * rh, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     drain_spans();
@@ -1392,7 +1357,8 @@ int pr_render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t
     PR_ENTER();
     const auto [rw, rh] = image_extent(roi, width, height);
     if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * rw * rh);
-    PR_TRY(render_multi(meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, roi, depth_dev_out));
+    PR_TRY(render_frames("pr_render_multi", FrameSource{ nullptr, 0, true, meshes, n_meshes, mesh_index_host }, poses_host, n_poses, width, height, proj, roi,
+                         depth_dev_out, nullptr, false, true));
     HIP_TRY(hipStreamSynchronize(g->stream));
     drain_spans();
     return PR_OK;
@@ -1758,7 +1724,7 @@ int pr_render_span(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *po
     const auto [rw, rh] = image_extent(roi, width, height);
     if (near_dev_out) note_write(near_dev_out, sizeof(int32_t) * n_poses * rw * rh);
     if (far_dev_out) note_write(far_dev_out, sizeof(int32_t) * n_poses * rw * rh);
-    PR_TRY(render_span_impl(tris_dev, n_tris, poses_host, n_poses, width, height, proj, roi, near_dev_out, far_dev_out));
+    PR_TRY(render_frames("pr_render_span", FrameSource{ tris_dev, n_tris }, poses_host, n_poses, width, height, proj, roi, near_dev_out, far_dev_out, true, true));
     HIP_TRY(hipStreamSynchronize(g->stream));
     drain_spans();
     return PR_OK;

@@ -202,6 +202,20 @@ inline bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
     }
     return true;
 }
+// pr_render, pr_render_span (span) and pr_render_multi's (multi) checks, all but a mixed batch's mesh table (plan_meshes), in the order and with the
+// messages the three have always had: the frame's under pr_render's name, then -- for P > 0 -- the entry point's own arrays under its own; pr_render
+// itself asks for its arrays with the frame.  An empty model has no array, no hypotheses need none.  No HIP call in here.
+inline int render_args_ok(const char *fn, bool multi, bool span, const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses, size_t P, size_t W, size_t H,
+                          const pr_mat4 *proj, pr_roi roi, const int32_t *near_dev, const int32_t *far_dev)
+{
+    const bool missing = P && (!poses || !near_dev || (span && !far_dev));
+    if ((!multi && !tris_dev && n_tris > 0) || (missing && !multi && !span) || !proj || W == 0 || H == 0) { set_error("pr_render: bad arguments"); return PR_ERR_INVALID; }
+    if (!frame_size_ok(W, H)) return PR_ERR_INVALID;
+    if (!roi_ok(roi, (uint32_t)W, (uint32_t)H)) { set_error("pr_render: roi out of image"); return PR_ERR_INVALID; }
+    if (missing) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
+    if (multi && P > 0xffffffffull) { set_error("%s: more than 2^32 hypotheses", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
 // A closest-point grid as a caller hands it over: every check that needs no device (make_job, make_scene, pr_scene_grid_build_dev; `built` = with the
 // arrays the build fills in).  No HIP call in here.
 inline int grid_desc_ok(const char *fn, const pr_scene_grid *gs, bool built)

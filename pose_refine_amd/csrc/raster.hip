@@ -17,18 +17,20 @@ __global__ __launch_bounds__(256) void fill_i32_kernel(int32_t *dst, size_t n, i
     if (i < n) for (size_t k = i; k < n && k < i + 4; ++k) dst[k] = v;
 }
 
-// renderer.cu:71-80 max2zero_functor over the whole stack of images
+// renderer.cu:71-80 max2zero_functor over the whole stack of images: "nothing drawn" (kSentinel: INT_MAX in a near plane, INT_MIN in the far plane
+// of a span render) to 0.  Both carry the name bench.py's counter calibration and tools/gpu_round.sh select by.
+template <int32_t kSentinel>
 __global__ __launch_bounds__(256) void max2zero_kernel(int32_t *d, size_t n)
 {
     size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     const size_t stride = (size_t)gridDim.x * 256 * 4;
     for (; i + 3 < n; i += stride) {
         int4 v = *reinterpret_cast<int4 *>(d + i);
-        v.x = (v.x == INT_MAX) ? 0 : v.x; v.y = (v.y == INT_MAX) ? 0 : v.y;
-        v.z = (v.z == INT_MAX) ? 0 : v.z; v.w = (v.w == INT_MAX) ? 0 : v.w;
+        v.x = (v.x == kSentinel) ? 0 : v.x; v.y = (v.y == kSentinel) ? 0 : v.y;
+        v.z = (v.z == kSentinel) ? 0 : v.z; v.w = (v.w == kSentinel) ? 0 : v.w;
         *reinterpret_cast<int4 *>(d + i) = v;
     }
-    if (i < n) for (size_t k = i; k < n && k < i + 4; ++k) if (d[k] == INT_MAX) d[k] = 0;
+    if (i < n) for (size_t k = i; k < n && k < i + 4; ++k) if (d[k] == kSentinel) d[k] = 0;
 }
 
 // ================================================================================================
@@ -376,14 +378,14 @@ __global__ __launch_bounds__(256) void raster_kernel(const pr_triangle *__restri
 // (triangle block, pose run) does for that group's mesh and hypotheses -- so a 1 M-triangle mesh next to 5 k-triangle ones launches
 // no empty workgroups, and every depth is the same atomicMin of the same fragment as in a single-mesh launch.  The group of a workgroup:
 // a wave-uniform binary search over the groups' first workgroups (scalar loads).  Workgroups beyond the grid loop (64-bit totals).
-__global__ __launch_bounds__(256) void raster_multi_kernel(const RasterGroup *__restrict__ groups, uint32_t n_groups, unsigned long long total_wg,
-                                                           const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
-                                                           uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi, uint32_t rw, uint32_t rh,
-                                                           const int4 *__restrict__ boxes, const uint32_t *__restrict__ box_off,
-                                                           const uint32_t *__restrict__ image_of)
+// kSpan: raster_runs' second plane, `far`, laid out as `depth`.
+template <bool kSpan>
+__device__ __forceinline__ void raster_group_walk(const RasterGroup *__restrict__ groups, uint32_t n_groups, unsigned long long total_wg,
+                                                  const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth, int32_t *__restrict__ far,
+                                                  uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh,
+                                                  const int4 *__restrict__ boxes, const uint32_t *__restrict__ box_off,
+                                                  const uint32_t *__restrict__ image_of, float (*sh)[kSetupWords][64], uint32_t (*shq)[192])
 {
-    __shared__ float sh[4][kSetupWords][64];
-    __shared__ uint32_t shq[4][192];
     for (unsigned long long wg = blockIdx.x; wg < total_wg; wg += gridDim.x) {
         uint32_t lo = 0, hi = n_groups;                          // groups[lo].first_wg <= wg < groups[hi].first_wg
         while (hi - lo > 1) {
@@ -398,14 +400,26 @@ __global__ __launch_bounds__(256) void raster_multi_kernel(const RasterGroup *__
         float tv[9];
         load_triangle(gr.tris, gr.n_tris, ti, tv);
         // full frames without a caller order: the group's images follow one another from its first hypothesis on
-        int32_t *base = (image_of || box_off) ? depth : depth + (size_t)gr.first * rw * rh;
-        raster_runs<false>(tv, ti, gr.n_tris, run, poses + gr.first, base, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
-                    gr.count, gr.run, box_off ? box_off + gr.first : nullptr, image_of ? image_of + gr.first : nullptr, sh, shq);
+        const size_t first = (image_of || box_off) ? 0 : (size_t)gr.first * rw * rh;
+        raster_runs<false, kSpan>(tv, ti, gr.n_tris, run, poses + gr.first, depth + first, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
+                                  gr.count, gr.run, box_off ? box_off + gr.first : nullptr, image_of ? image_of + gr.first : nullptr, sh, shq,
+                                  kSpan ? far + first : nullptr);
     }
+}
+__global__ __launch_bounds__(256) void raster_multi_kernel(const RasterGroup *__restrict__ groups, uint32_t n_groups, unsigned long long total_wg,
+                                                           const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth,
+                                                           uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi, uint32_t rw, uint32_t rh,
+                                                           const int4 *__restrict__ boxes, const uint32_t *__restrict__ box_off,
+                                                           const uint32_t *__restrict__ image_of)
+{
+    __shared__ float sh[4][kSetupWords][64];
+    __shared__ uint32_t shq[4][192];
+    raster_group_walk<false>(groups, n_groups, total_wg, poses, depth, nullptr, width, height, proj, roi, rw, rh, boxes, box_off, image_of, sh, shq);
 }
 
 // The span forms of raster_kernel<false> and raster_multi_kernel (pr_render_span, pr_pose_penetration): the same workgroups, triangles, hypotheses
-// and fragments, every depth into two planes of one layout -- atomicMin into `depth`, atomicMax into `far` (full frames or packed boxes).
+// and fragments, every depth into two planes of one layout -- atomicMin into `depth`, atomicMax into `far` (full frames or packed boxes; a mixed
+// batch's full frames are never span renders, so its form has no image_of).
 __global__ __launch_bounds__(256) void raster_span_kernel(const pr_triangle *__restrict__ tris, uint32_t n_tris,
                                                           const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth, int32_t *__restrict__ far,
                                                           uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi,
@@ -422,57 +436,11 @@ __global__ __launch_bounds__(256) void raster_span_kernel(const pr_triangle *__r
 __global__ __launch_bounds__(256) void raster_span_multi_kernel(const RasterGroup *__restrict__ groups, uint32_t n_groups, unsigned long long total_wg,
                                                                 const pr_mat4 *__restrict__ poses, int32_t *__restrict__ depth, int32_t *__restrict__ far,
                                                                 uint32_t width, uint32_t height, pr_mat4 proj, pr_roi roi, uint32_t rw, uint32_t rh,
-                                                                const int4 *__restrict__ boxes, const uint32_t *__restrict__ box_off,
-                                                                const uint32_t *__restrict__ image_of)
+                                                                const int4 *__restrict__ boxes, const uint32_t *__restrict__ box_off)
 {
     __shared__ float sh[4][kSetupWords][64];
     __shared__ uint32_t shq[4][192];
-    for (unsigned long long wg = blockIdx.x; wg < total_wg; wg += gridDim.x) {
-        uint32_t lo = 0, hi = n_groups;                          // as raster_multi_kernel
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (groups[mid].first_wg <= wg) lo = mid; else hi = mid;
-        }
-        lo = __builtin_amdgcn_readfirstlane(lo);
-        const RasterGroup &gr = groups[lo];
-        const unsigned long long local = wg - gr.first_wg;
-        const uint32_t run = (uint32_t)(local / gr.tri_blocks), block = (uint32_t)(local - (unsigned long long)run * gr.tri_blocks);
-        const uint32_t ti = block * 256 + threadIdx.x;
-        float tv[9];
-        load_triangle(gr.tris, gr.n_tris, ti, tv);
-        const size_t first = (image_of || box_off) ? 0 : (size_t)gr.first * rw * rh;
-        raster_runs<false, true>(tv, ti, gr.n_tris, run, poses + gr.first, depth + first, width, height, proj, roi, rw, rh, boxes ? boxes + gr.first : nullptr,
-                                 gr.count, gr.run, box_off ? box_off + gr.first : nullptr, image_of ? image_of + gr.first : nullptr, sh, shq, far + first);
-    }
-}
-// the far plane's "nothing drawn" (INT_MIN) to 0, as max2zero_kernel does for the near plane's INT_MAX
-__global__ __launch_bounds__(256) void min2zero_kernel(int32_t *d, size_t n)
-{
-    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    const size_t stride = (size_t)gridDim.x * 256 * 4;
-    for (; i + 3 < n; i += stride) {
-        int4 v = *reinterpret_cast<int4 *>(d + i);
-        v.x = (v.x == INT_MIN) ? 0 : v.x; v.y = (v.y == INT_MIN) ? 0 : v.y;
-        v.z = (v.z == INT_MIN) ? 0 : v.z; v.w = (v.w == INT_MIN) ? 0 : v.w;
-        *reinterpret_cast<int4 *>(d + i) = v;
-    }
-    if (i < n) for (size_t k = i; k < n && k < i + 4; ++k) if (d[k] == INT_MIN) d[k] = 0;
-}
-// fill_box_kernel for the two planes of a span render: INT_MAX into the near box, INT_MIN into the far one
-__global__ __launch_bounds__(256) void fill_span_box_kernel(int32_t *__restrict__ depth, int32_t *__restrict__ far, const int4 *__restrict__ bbox,
-                                                            uint32_t width, uint32_t height, const uint32_t *__restrict__ box_off)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const int4 bb = bbox[blockIdx.y];
-    for (uint32_t r = 0; r < 4; ++r) {
-        const uint32_t row = blockIdx.x * kBoxRowsPerBlock + (threadIdx.x >> 6) * 4 + r;
-        if (row >= height) return;
-        const int ry = (int)height - 1 - (int)row;
-        if (ry < bb.y || ry > bb.w) continue;
-        int32_t *near_line = box_line(depth, box_off, bb, blockIdx.y, row, width, height);
-        int32_t *far_line = box_line(far, box_off, bb, blockIdx.y, row, width, height);
-        for (int x = bb.x + (int)lane; x <= bb.z; x += 64) { near_line[x] = INT_MAX; far_line[x] = INT_MIN; }
-    }
+    raster_group_walk<true>(groups, n_groups, total_wg, poses, depth, far, width, height, proj, roi, rw, rh, boxes, box_off, nullptr, sh, shq);
 }
 
 // ================================================================================================
@@ -589,8 +557,10 @@ __global__ __launch_bounds__(kTightLanes) void pose_tight_box_kernel(const float
 
 // INT_MAX-fill and per-row valid counts restricted to each hypothesis' pixel box (image rows are
 // the flipped raster rows).  One wavefront per image row; rows outside the box only write count 0.
-__global__ __launch_bounds__(256) void fill_box_kernel(int32_t *__restrict__ depth, const int4 *__restrict__ bbox, uint32_t width, uint32_t height,
-                                                       const uint32_t *__restrict__ box_off)
+// kFar: the two planes of a span render -- INT_MAX into the near box, INT_MIN into the far one.
+template <bool kFar>
+__device__ __forceinline__ void fill_box_rows(int32_t *__restrict__ depth, int32_t *__restrict__ far, const int4 *__restrict__ bbox, uint32_t width,
+                                              uint32_t height, const uint32_t *__restrict__ box_off)
 {
     const uint32_t lane = threadIdx.x & 63;
     const int4 bb = bbox[blockIdx.y];
@@ -600,8 +570,19 @@ __global__ __launch_bounds__(256) void fill_box_kernel(int32_t *__restrict__ dep
         const int ry = (int)height - 1 - (int)row;                  // raster row of this image row
         if (ry < bb.y || ry > bb.w) continue;
         int32_t *line = box_line(depth, box_off, bb, blockIdx.y, row, width, height);
-        for (int x = bb.x + (int)lane; x <= bb.z; x += 64) line[x] = INT_MAX;
+        int32_t *far_line = kFar ? box_line(far, box_off, bb, blockIdx.y, row, width, height) : nullptr;
+        for (int x = bb.x + (int)lane; x <= bb.z; x += 64) { line[x] = INT_MAX; if constexpr (kFar) far_line[x] = INT_MIN; }
     }
+}
+__global__ __launch_bounds__(256) void fill_box_kernel(int32_t *__restrict__ depth, const int4 *__restrict__ bbox, uint32_t width, uint32_t height,
+                                                       const uint32_t *__restrict__ box_off)
+{
+    fill_box_rows<false>(depth, nullptr, bbox, width, height, box_off);
+}
+__global__ __launch_bounds__(256) void fill_span_box_kernel(int32_t *__restrict__ depth, int32_t *__restrict__ far, const int4 *__restrict__ bbox,
+                                                            uint32_t width, uint32_t height, const uint32_t *__restrict__ box_off)
+{
+    fill_box_rows<true>(depth, far, bbox, width, height, box_off);
 }
 __global__ __launch_bounds__(256) void count_box_kernel(const int32_t *__restrict__ depth, const int4 *__restrict__ bbox, uint32_t width,
                                                         uint32_t height, uint32_t *__restrict__ row_count, const uint32_t *__restrict__ box_off)
@@ -771,10 +752,11 @@ hipError_t launch_fill_i32(int32_t *dst, size_t n, int32_t v, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_max2zero(int32_t *depth, size_t n, hipStream_t s)
+hipError_t launch_sentinel2zero(int32_t *plane, size_t n, bool far, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(max2zero_kernel, dim3(cap_grid((n + 1023) / 1024)), dim3(256), 0, s, depth, n);
+    auto *kernel = far ? max2zero_kernel<INT_MIN> : max2zero_kernel<INT_MAX>;
+    hipLaunchKernelGGL(kernel, dim3(cap_grid((n + 1023) / 1024)), dim3(256), 0, s, plane, n);
     return hipGetLastError();
 }
 
@@ -789,18 +771,66 @@ static uint32_t raster_pose_run(uint32_t n_tris, uint32_t n_poses)
     if (run > n_poses) run = n_poses ? n_poses : 1u;
     return run;
 }
-hipError_t launch_raster(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses,
-                         int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi,
-                         uint32_t rw, uint32_t rh, hipStream_t s)
+// the groups the host filled (tris, n_tris, first, count), completed in place: empty groups dropped, run, triangle blocks, first workgroup; returns how many are left
+static uint32_t complete_raster_groups(RasterGroup *groups_host, uint32_t n_groups, unsigned long long &total)
 {
-    if (n_tris == 0 || n_poses == 0) return hipSuccess;
-    // grid.y is limited to 65535: split very large batches
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
-        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
-        const uint32_t run = raster_pose_run(n_tris, np);
-        hipLaunchKernelGGL(raster_kernel<false>, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
-                           depth + (size_t)p0 * rw * rh, width, height, proj, roi, rw, rh, (const int4 *)nullptr, np, run, (const uint32_t *)nullptr, BatchCheck{});
+    uint32_t n = 0;
+    total = 0;
+    for (uint32_t i = 0; i < n_groups; ++i) {
+        RasterGroup gr = groups_host[i];
+        if (gr.n_tris == 0 || gr.count == 0) continue;             // an empty mesh renders nothing
+        gr.run = raster_pose_run(gr.n_tris, gr.count);
+        gr.tri_blocks = (gr.n_tris + 255) / 256;
+        gr.first_wg = total;
+        total += (unsigned long long)gr.tri_blocks * ((gr.count + gr.run - 1) / gr.run);
+        groups_host[n++] = gr;
     }
+    return n;
+}
+// the target as hypothesis p0 of it sees it: full frames follow one another, packed boxes keep the base and move on in their offsets
+static RasterTarget target_at(RasterTarget t, uint32_t p0)
+{
+    const size_t first = t.box_off ? 0 : (size_t)p0 * t.rw * t.rh;
+    t.depth += first;
+    if (t.far) t.far += first;
+    if (t.boxes) t.boxes += p0;
+    if (t.box_off) t.box_off += p0;
+    return t;
+}
+// Every raster launch but the LDS-band one.  One mesh: raster_kernel (raster_span_kernel with a far plane) over the hypotheses in runs of at most
+// 32768, `check` riding on the first.  A mixed batch: the groups completed in the pinned block (complete_raster_groups), staged to groups_dev, and
+// one raster_multi_kernel (raster_span_multi_kernel) launch over all of them.  An empty mesh launches nothing.
+hipError_t launch_raster(const RasterMesh &mesh, const pr_mat4 *poses_dev, uint32_t n_poses, const RasterTarget &t, const BatchCheck *check, hipStream_t s)
+{
+    if (mesh.groups_host) {
+        unsigned long long total = 0;
+        const uint32_t n = complete_raster_groups(mesh.groups_host, mesh.n_groups, total);
+        if (n == 0) return hipSuccess;
+        hipError_t e = launch_stage_words(mesh.groups_mapped, mesh.groups_dev, sizeof(RasterGroup) * n, s);
+        if (e != hipSuccess) return e;
+        const dim3 grid((uint32_t)(total < (1ull << 22) ? total : (1ull << 22)));
+        if (t.far)
+            hipLaunchKernelGGL(raster_span_multi_kernel, grid, dim3(256), 0, s, (const RasterGroup *)mesh.groups_dev, n, total, poses_dev, t.depth, t.far,
+                               t.width, t.height, *t.proj, t.roi, t.rw, t.rh, t.boxes, t.box_off);
+        else
+            hipLaunchKernelGGL(raster_multi_kernel, grid, dim3(256), 0, s, (const RasterGroup *)mesh.groups_dev, n, total, poses_dev, t.depth,
+                               t.width, t.height, *t.proj, t.roi, t.rw, t.rh, t.boxes, t.box_off, t.image_of);
+        return hipGetLastError();
+    }
+    if (mesh.n_tris == 0 || n_poses == 0) return hipSuccess;
+    for_pose_launches(n_poses, [&](uint32_t p0, uint32_t np) {
+        const RasterTarget u = target_at(t, p0);
+        const uint32_t run = raster_pose_run(mesh.n_tris, np);
+        const dim3 grid((mesh.n_tris + 255) / 256, (np + run - 1) / run);
+        auto *kernel = u.bands ? raster_kernel<true> : raster_kernel<false>;
+        if (u.far)
+            hipLaunchKernelGGL(raster_span_kernel, grid, dim3(256), 0, s, mesh.tris, mesh.n_tris, poses_dev + p0, u.depth, u.far, u.width, u.height, *u.proj,
+                               u.roi, u.rw, u.rh, u.boxes, np, run, u.box_off);
+        else
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, mesh.tris, mesh.n_tris, poses_dev + p0, u.depth, u.width, u.height, *u.proj, u.roi, u.rw, u.rh,
+                               u.boxes, np, run, u.box_off, (check && p0 == 0) ? *check : BatchCheck{});
+        return hipSuccess;
+    });
     return hipGetLastError();
 }
 
@@ -849,9 +879,7 @@ __global__ __launch_bounds__(256) void box_pack_offsets_kernel(const int4 *__res
     __shared__ uint32_t carry;
     block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return box_slot_of(bbox[i], height, bands); }, [&](uint32_t i, uint32_t o) { off[i] = o; });
 }
-// The steps both box renders share.  box_pack_offsets_kernel (when the boxes are packed); fill_box_kernel / count_box_kernel over hypotheses
-// [p0, p0 + n), in launches of at most 32768 (grid.y is limited to 65535); the closing row scan (launch_d2c_scan_init when the asynchronous
-// path's per-hypothesis records are given).
+// the offsets of the packed boxes (nothing to do when the boxes lie in full frames)
 static void launch_box_pack(const int4 *bbox, uint32_t n_poses, const uint32_t *box_off, hipStream_t s, uint32_t height = 0, bool bands = false)
 {
     if (box_off) hipLaunchKernelGGL(box_pack_offsets_kernel, dim3(1), dim3(256), 0, s, bbox, n_poses, const_cast<uint32_t *>(box_off), height, bands);   // (the caller's scratch: filled here)
@@ -870,62 +898,60 @@ hipError_t launch_box_pack_offsets(const int4 *bbox, uint32_t n_poses, uint32_t 
     if (n_poses > 0) launch_box_pack(bbox, n_poses, box_off, s, height, bands);
     return hipGetLastError();
 }
-static void launch_fill_boxes(int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height, hipStream_t s,
-                              bool bands = false)
+// the boxes of the first n hypotheses of `t` filled with "nothing drawn" (with a far plane: both planes), and their valid pixels counted row by row
+static void launch_fill_boxes(const RasterTarget &t, uint32_t n, hipStream_t s)
 {
-    for (const uint32_t end = p0 + n; p0 < end; p0 += 32768) {
-        const uint32_t np = (end - p0 < 32768) ? (end - p0) : 32768;
-        if (bands) { hipLaunchKernelGGL(fill_band_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s, depth, bbox + p0, height, box_off + p0); continue; }
-        hipLaunchKernelGGL(fill_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
-                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, box_off ? box_off + p0 : nullptr);
-    }
+    for_pose_launches(n, [&](uint32_t p0, uint32_t np) {
+        const RasterTarget u = target_at(t, p0);
+        const dim3 grid((u.height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np);
+        if (u.bands) hipLaunchKernelGGL(fill_band_kernel, grid, dim3(256), 0, s, u.depth, u.boxes, u.height, u.box_off);
+        else if (u.far) hipLaunchKernelGGL(fill_span_box_kernel, grid, dim3(256), 0, s, u.depth, u.far, u.boxes, u.width, u.height, u.box_off);
+        else hipLaunchKernelGGL(fill_box_kernel, grid, dim3(256), 0, s, u.depth, u.boxes, u.width, u.height, u.box_off);
+        return hipSuccess;
+    });
 }
-static void launch_count_boxes(const int32_t *depth, const int4 *bbox, const uint32_t *box_off, uint32_t p0, uint32_t n, uint32_t width, uint32_t height,
-                               uint32_t *row_count, hipStream_t s, bool bands = false)
+static void launch_count_boxes(const RasterTarget &t, uint32_t n, uint32_t *row_count, hipStream_t s)
 {
-    for (const uint32_t end = p0 + n; p0 < end; p0 += 32768) {
-        const uint32_t np = (end - p0 < 32768) ? (end - p0) : 32768;
-        if (bands) { hipLaunchKernelGGL(count_band_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s, depth, bbox + p0, height,
-                                        row_count + (size_t)p0 * height, box_off + p0); continue; }
-        hipLaunchKernelGGL(count_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np), dim3(256), 0, s,
-                           depth + (box_off ? 0 : (size_t)p0 * width * height), bbox + p0, width, height, row_count + (size_t)p0 * height, box_off ? box_off + p0 : nullptr);
-    }
-}
-static hipError_t launch_box_scan(const uint32_t *row_count, uint32_t height, uint32_t *row_off, uint32_t *counts, uint32_t n_poses,
-                                  PoseMeta *meta, DevIcpState *st, uint32_t *arrive, hipStream_t s)
-{
-    const hipError_t e = meta ? launch_d2c_scan_init(row_count, height, row_off, counts, n_poses, meta, st, arrive, s)
-                              : launch_d2c_scan(row_count, height, row_off, counts, n_poses, s);
-    return e != hipSuccess ? e : hipGetLastError();
+    for_pose_launches(n, [&](uint32_t p0, uint32_t np) {
+        const RasterTarget u = target_at(t, p0);
+        const dim3 grid((u.height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, np);
+        uint32_t *rows = row_count + (size_t)p0 * u.height;
+        if (u.bands) hipLaunchKernelGGL(count_band_kernel, grid, dim3(256), 0, s, (const int32_t *)u.depth, u.boxes, u.height, rows, u.box_off);
+        else hipLaunchKernelGGL(count_box_kernel, grid, dim3(256), 0, s, (const int32_t *)u.depth, u.boxes, u.width, u.height, rows, u.box_off);
+        return hipSuccess;
+    });
 }
 
-// fused-path render, reference scheme (global int32 atomicMin) but only inside each hypothesis' box
-hipError_t launch_render_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb,
-                               int4 *bbox, int32_t *depth, uint32_t *row_count, uint32_t *row_off, uint32_t *counts,
-                               uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s, bool compute_boxes,
-                               PoseMeta *meta, DevIcpState *st, uint32_t *arrive, const uint32_t *box_off, const BatchCheck *check, bool bands)
+// Fused-path render, reference scheme (global int32 atomicMin) but only inside each hypothesis' box: the pixel boxes (compute_boxes: from mesh.aabb under
+// t.roi -- hypothesis p takes the box of mesh mesh.box_index[p] when an index is given -- and, packed, their offsets; otherwise the caller placed both),
+// the fill, the raster (launch_raster; a ROI is already part of the boxes), and -- rows.row_count given -- the row counts and the closing row scan
+// (launch_d2c_scan_init when the asynchronous path's per-hypothesis records are given).  One mesh: fill, raster and count per run of 32768 hypotheses.
+// With t.far both planes are filled and rastered (row-major boxes).  t.boxes, t.rw and t.rh are set here.
+hipError_t launch_render_boxes(const RasterMesh &mesh, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, const RasterTarget &target, const BoxRows &rows,
+                               hipStream_t s, bool compute_boxes, const BatchCheck *check)
 {
     if (n_poses == 0) return hipSuccess;
-    if (bands && (!box_off || compute_boxes)) return hipErrorInvalidValue;      // banded boxes are packed boxes the caller placed (box_slot_of)
+    if (target.bands && (!target.box_off || compute_boxes || target.far)) return hipErrorInvalidValue;      // banded boxes are packed boxes the caller placed (box_slot_of)
+    RasterTarget t = target;
+    t.boxes = bbox; t.rw = t.width; t.rh = t.height; t.roi = pr_roi{ 0, 0, 0, 0 };
     if (compute_boxes) {
-        hipLaunchKernelGGL(pose_bbox_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabb, poses_dev, n_poses, proj, width, height, roi, bbox);
-        launch_box_pack(bbox, n_poses, box_off, s);
+        const dim3 grid((n_poses + 255) / 256);
+        if (mesh.box_index) hipLaunchKernelGGL(pose_bbox_multi_kernel, grid, dim3(256), 0, s, mesh.aabb, mesh.box_index, poses_dev, n_poses, *t.proj, t.width, t.height, target.roi, bbox);
+        else hipLaunchKernelGGL(pose_bbox_kernel, grid, dim3(256), 0, s, mesh.aabb, poses_dev, n_poses, *t.proj, t.width, t.height, target.roi, bbox);
+        launch_box_pack(bbox, n_poses, t.box_off, s);
     }
-    const pr_roi none{ 0, 0, 0, 0 };
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
-        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
-        const size_t off = box_off ? 0 : (size_t)p0 * width * height;
-        const uint32_t *bo = box_off ? box_off + p0 : nullptr;
-        launch_fill_boxes(depth, bbox, box_off, p0, np, width, height, s, bands);
-        if (n_tris > 0)                                          // an empty mesh renders nothing: every cloud is empty
-        { const uint32_t run = raster_pose_run(n_tris, np);
-          auto *kernel = bands ? raster_kernel<true> : raster_kernel<false>;
-          hipLaunchKernelGGL(kernel, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
-                             depth + off, width, height, proj, none, width, height, (const int4 *)(bbox + p0), np, run,
-                             bo, (check && p0 == 0) ? *check : BatchCheck{}); }
-        launch_count_boxes(depth, bbox, box_off, p0, np, width, height, row_count, s, bands);
-    }
-    return launch_box_scan(row_count, height, row_off, counts, n_poses, meta, st, arrive, s);
+    auto pass = [&](uint32_t p0, uint32_t np) {
+        const RasterTarget u = target_at(t, p0);
+        launch_fill_boxes(u, np, s);
+        const hipError_t e = launch_raster(mesh, poses_dev + p0, np, u, p0 == 0 ? check : nullptr, s);
+        if (e == hipSuccess && rows.row_count) launch_count_boxes(u, np, rows.row_count + (size_t)p0 * t.height, s);
+        return e;
+    };
+    hipError_t e = mesh.groups_host ? pass(0, n_poses) : for_pose_launches(n_poses, pass);      // (a mixed batch's raster is one launch over all its groups)
+    if (e != hipSuccess || !rows.row_count) return e != hipSuccess ? e : hipGetLastError();
+    e = rows.meta ? launch_d2c_scan_init(rows.row_count, t.height, rows.row_off, rows.counts, n_poses, rows.meta, rows.st, rows.arrive, s)
+                  : launch_d2c_scan(rows.row_count, t.height, rows.row_off, rows.counts, n_poses, s);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // ---- mixed batches (hypotheses of several meshes in one call) -----------------------------------------------------------------------
@@ -943,123 +969,6 @@ hipError_t launch_model_aabb_multi(const pr_mesh_ref *meshes_dev, const pr_mesh_
     }
     const uint32_t words = 6 * n_meshes;
     hipLaunchKernelGGL(model_aabb_multi_finish_kernel, dim3((words + 255) / 256), dim3(256), 0, s, keys, words, aabb_out);
-    return hipGetLastError();
-}
-
-// the groups the host filled (tris, n_tris, first, count), completed in place: empty groups dropped, run, triangle blocks, first workgroup; returns how many are left
-static uint32_t complete_raster_groups(RasterGroup *groups_host, uint32_t n_groups, unsigned long long &total)
-{
-    uint32_t n = 0;
-    total = 0;
-    for (uint32_t i = 0; i < n_groups; ++i) {
-        RasterGroup gr = groups_host[i];
-        if (gr.n_tris == 0 || gr.count == 0) continue;             // an empty mesh renders nothing
-        gr.run = raster_pose_run(gr.n_tris, gr.count);
-        gr.tri_blocks = (gr.n_tris + 255) / 256;
-        gr.first_wg = total;
-        total += (unsigned long long)gr.tri_blocks * ((gr.count + gr.run - 1) / gr.run);
-        groups_host[n++] = gr;
-    }
-    return n;
-}
-// groups_host (pinned; groups_mapped = the same memory as the device sees it): tris, n_tris, first, count of each group of consecutive
-// hypotheses with one mesh.  Completed here (complete_raster_groups), staged to groups_dev, launched.
-hipError_t launch_raster_multi(RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups, RasterGroup *groups_dev, const pr_mat4 *poses_dev,
-                               int32_t *depth, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh,
-                               const int4 *boxes, const uint32_t *box_off, const uint32_t *image_of, hipStream_t s)
-{
-    unsigned long long total = 0;
-    const uint32_t n = complete_raster_groups(groups_host, n_groups, total);
-    if (n == 0) return hipSuccess;
-    hipError_t e = launch_stage_words(groups_mapped, groups_dev, sizeof(RasterGroup) * n, s);
-    if (e != hipSuccess) return e;
-    const unsigned long long grid = total < (1ull << 22) ? total : (1ull << 22);
-    hipLaunchKernelGGL(raster_multi_kernel, dim3((uint32_t)grid), dim3(256), 0, s, (const RasterGroup *)groups_dev, n, total, poses_dev, depth,
-                       width, height, proj, roi, rw, rh, boxes, box_off, image_of);
-    return hipGetLastError();
-}
-
-// launch_render_boxes (compute_boxes, no per-batch checks) for a mixed batch: hypothesis p takes the box of mesh box_index[p] (aabbs, 6 floats
-// each) and the raster is one raster_multi_kernel launch over all groups
-hipError_t launch_render_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
-                                     RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, uint32_t *row_count,
-                                     uint32_t *row_off, uint32_t *counts, uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, hipStream_t s,
-                                     const uint32_t *box_off)
-{
-    if (n_poses == 0) return hipSuccess;
-    hipLaunchKernelGGL(pose_bbox_multi_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabbs, box_index, poses_dev, n_poses, proj, width, height, roi, bbox);
-    launch_box_pack(bbox, n_poses, box_off, s);
-    launch_fill_boxes(depth, bbox, box_off, 0, n_poses, width, height, s);
-    const pr_roi none{ 0, 0, 0, 0 };
-    { hipError_t e = launch_raster_multi(groups_host, groups_mapped, n_groups, groups_dev, poses_dev, depth, width, height, proj, none, width, height,
-                                         bbox, box_off, nullptr, s); if (e != hipSuccess) return e; }
-    launch_count_boxes(depth, bbox, box_off, 0, n_poses, width, height, row_count, s);
-    return launch_box_scan(row_count, height, row_off, counts, n_poses, nullptr, nullptr, nullptr, s);
-}
-
-// ---- span renders: the nearest and the farthest fragment of every pixel (pr_render_span, pr_pose_penetration) ------------------------------------
-hipError_t launch_min2zero(int32_t *far, size_t n, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(min2zero_kernel, dim3(cap_grid((n + 1023) / 1024)), dim3(256), 0, s, far, n);
-    return hipGetLastError();
-}
-// launch_raster into two stacks of full images (the caller filled depth with INT_MAX and far with INT_MIN)
-hipError_t launch_raster_span(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, int32_t *depth, int32_t *far,
-                              uint32_t width, uint32_t height, const pr_mat4 &proj, pr_roi roi, uint32_t rw, uint32_t rh, hipStream_t s)
-{
-    if (n_tris == 0 || n_poses == 0) return hipSuccess;
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += 32768) {
-        const uint32_t np = (n_poses - p0 < 32768) ? (n_poses - p0) : 32768;
-        const uint32_t run = raster_pose_run(n_tris, np);
-        hipLaunchKernelGGL(raster_span_kernel, dim3((n_tris + 255) / 256, (np + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev + p0,
-                           depth + (size_t)p0 * rw * rh, far + (size_t)p0 * rw * rh, width, height, proj, roi, rw, rh, (const int4 *)nullptr, np, run,
-                           (const uint32_t *)nullptr);
-    }
-    return hipGetLastError();
-}
-// launch_render_boxes' layout (boxes computed here, packed at box_off) with a far plane at the same offsets; no row counts: the pair kernel
-// walks the boxes themselves.  At most 32768 hypotheses (the caller's limit is PR_PENETRATION_MAX_POSES).
-static void launch_fill_span_boxes(int32_t *depth, int32_t *far, const int4 *bbox, const uint32_t *box_off, uint32_t n_poses, uint32_t width, uint32_t height,
-                                   hipStream_t s)
-{
-    hipLaunchKernelGGL(fill_span_box_kernel, dim3((height + kBoxRowsPerBlock - 1) / kBoxRowsPerBlock, n_poses), dim3(256), 0, s, depth, far, bbox, width, height, box_off);
-}
-hipError_t launch_render_span_boxes(const pr_triangle *tris, uint32_t n_tris, const pr_mat4 *poses_dev, uint32_t n_poses, const float *aabb, int4 *bbox,
-                                    int32_t *depth, int32_t *far, uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s)
-{
-    if (n_poses == 0) return hipSuccess;
-    if (n_poses > 32768 || !box_off) return hipErrorInvalidValue;
-    const pr_roi none{ 0, 0, 0, 0 };
-    hipLaunchKernelGGL(pose_bbox_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabb, poses_dev, n_poses, proj, width, height, none, bbox);
-    launch_box_pack(bbox, n_poses, box_off, s);
-    launch_fill_span_boxes(depth, far, bbox, box_off, n_poses, width, height, s);
-    if (n_tris > 0) {
-        const uint32_t run = raster_pose_run(n_tris, n_poses);
-        hipLaunchKernelGGL(raster_span_kernel, dim3((n_tris + 255) / 256, (n_poses + run - 1) / run), dim3(256), 0, s, tris, n_tris, poses_dev, depth, far,
-                           width, height, proj, none, width, height, (const int4 *)bbox, n_poses, run, (const uint32_t *)box_off);
-    }
-    return hipGetLastError();
-}
-// the same for a mixed batch (launch_render_boxes_multi's tables)
-hipError_t launch_render_span_boxes_multi(const float *aabbs, const uint32_t *box_index, RasterGroup *groups_host, const void *groups_mapped, uint32_t n_groups,
-                                          RasterGroup *groups_dev, const pr_mat4 *poses_dev, uint32_t n_poses, int4 *bbox, int32_t *depth, int32_t *far,
-                                          uint32_t width, uint32_t height, const pr_mat4 &proj, uint32_t *box_off, hipStream_t s)
-{
-    if (n_poses == 0) return hipSuccess;
-    if (n_poses > 32768 || !box_off) return hipErrorInvalidValue;
-    const pr_roi none{ 0, 0, 0, 0 };
-    hipLaunchKernelGGL(pose_bbox_multi_kernel, dim3((n_poses + 255) / 256), dim3(256), 0, s, aabbs, box_index, poses_dev, n_poses, proj, width, height, none, bbox);
-    launch_box_pack(bbox, n_poses, box_off, s);
-    launch_fill_span_boxes(depth, far, bbox, box_off, n_poses, width, height, s);
-    unsigned long long total = 0;
-    const uint32_t n = complete_raster_groups(groups_host, n_groups, total);
-    if (n == 0) return hipSuccess;
-    hipError_t e = launch_stage_words(groups_mapped, groups_dev, sizeof(RasterGroup) * n, s);
-    if (e != hipSuccess) return e;
-    const unsigned long long grid = total < (1ull << 22) ? total : (1ull << 22);
-    hipLaunchKernelGGL(raster_span_multi_kernel, dim3((uint32_t)grid), dim3(256), 0, s, (const RasterGroup *)groups_dev, n, total, poses_dev, depth, far,
-                       width, height, proj, none, width, height, (const int4 *)bbox, (const uint32_t *)box_off, (const uint32_t *)nullptr);
     return hipGetLastError();
 }
 

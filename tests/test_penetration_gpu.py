@@ -171,6 +171,26 @@ def test_mixed_batch(gpu, model, scenario):
         api.pose_penetration_multi(meshes, [0, 1, 3], poses[:3], W, H, scenario["proj"])
 
 
+def test_mixed_batch_empty_and_unused_meshes(gpu, scenario):
+    """The frame, K, soup and poses of test_span_random_mesh_and_empty_mesh as a mixed batch whose table holds an empty mesh with hypotheses and a mesh
+    with none; then every hypothesis on the empty mesh: no raster launches, yet both planes must be filled -- the workspaces still hold the first
+    call's renders -- so that every byte of every record is zero."""
+    rng = np.random.default_rng(31)
+    w, h = 97, 61
+    K = np.array([1.1 * w, 0, w / 2 + 3.3, 0, 1.2 * w, h / 2 - 2.1, 0, 0, 1], np.float32)
+    proj = O.compute_proj(K, w, h)
+    tris = random_mesh(rng, 400, 40.0)
+    poses = np.stack([random_pose(rng, d) for d in (300.0, 150.0, 90.0, 600.0, 45.0)])
+    poses[4, 2, 3] = 10.0
+    meshes = [tris, np.zeros((0, 3, 3), np.float32), box_mesh(40, 30, 25), synth.uv_sphere_mesh(24, 12)]      # the sphere gets no hypothesis
+    idx = np.array([0, 1, 2, 0, 1], np.uint32)
+    near, far = span_ref_multi(meshes, idx, poses, proj, w, h)
+    for slack in (0, 5):
+        _assert_pairs(api.pose_penetration_multi(meshes, idx, poses, w, h, proj, slack), pairs_ref(near, far, slack))
+    got = api.pose_penetration_multi(meshes, np.ones(5, np.uint32), poses, w, h, proj, 0)
+    assert got.shape == (5, 5) and not got.view(np.uint8).any()
+
+
 # ---- the planted frame end to end ------------------------------------------------------------------------------------------------------------
 def test_planted_frame_end_to_end(gpu, model, scenario):
     scene = scenario["depth"][1]

@@ -184,3 +184,30 @@ def test_degenerate_intrinsics(gpu, name, Kd):
     for scene in (api.Scene_projective().init_Scene_projective_cuda(scene_depth, Kd, W, H), api.Scene_nn().init_Scene_nn_cuda(scene_depth, Kd)):
         res, sizes = api.refine_batch(model, poses, W, H, pj, Kd, scene, crit)
         assert len(res) == 4
+
+
+def test_render_launch_split_full_frames(gpu):
+    """32768 + 5 full frames: pr_render and pr_render_span split their raster over two launches (grid.y is limited).  verify_ref.launch_split_case's
+    8 distinct poses repeated: image i is render i % 8 in the near plane and solid_ref.span_ref's far surface of pose i % 8 in the far plane -- on
+    both sides of the split, at its last and first image, and at the batch's last.  (span_ref's far plane of these 8 poses holds 123 to 667 pixels
+    with far > near each: an unwritten far plane cannot pass.)"""
+    from solid_ref import span_ref
+    from verify_ref import launch_split_case
+    c = launch_split_case()
+    w, h, P = c["W"], c["H"], c["P"]
+    assert P == 32768 + 5
+    poses = c["poses"][np.arange(P) % 8]
+    ref_near, ref_far = span_ref(c["tris"], c["poses"], c["proj"], w, h)
+    assert np.array_equal(ref_near, c["renders"]) and all((ref_far[k] > ref_near[k]).sum() > 100 for k in range(8))
+    m = api.Model(tris=c["tris"])
+
+    def check(plane, ref):
+        got = plane.to_host().reshape(P, h, w)
+        for i in (0, 1, 32767, 32768, 32769, 32772):
+            assert np.array_equal(got[i], ref[i % 8]), i
+        assert got[0].tobytes() == got[32768].tobytes()              # the first image of either launch
+
+    check(api.render(m, poses, w, h, c["proj"]), c["renders"])
+    near, far = api.render_span(m, poses, w, h, c["proj"])
+    check(near, c["renders"])
+    check(far, ref_far)

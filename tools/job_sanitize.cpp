@@ -1,5 +1,5 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
-// Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok and vsd_args_ok with null and
+// Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok, render_args_ok and vsd_args_ok with null and
 // out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), and pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance).  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
@@ -211,6 +211,25 @@ int main()
             for (auto [W, H] : { std::pair<uint32_t, uint32_t>{ 0, 480 }, { 640, 0 }, { 8193, 1 }, { 8192, 4096 }, { 0xffffffffu, 0xffffffffu } })
                 CHECK(vsd(multi, tris, est.data(), 5, gt.data(), 5, W, H, &proj, dev, K, 15.0f, taus, 3, out) == PR_ERR_INVALID);
         }
+    }
+    // the full-frame renders' arguments (render_args_ok): plain, span and mixed; nothing to render needs no arrays; a far plane only where one is written
+    {
+        const int32_t *plane = reinterpret_cast<const int32_t *>(uintptr_t(0xd000));
+        for (bool multi : { false, true })
+            for (bool span : { false, true }) {
+                auto render = [&](const pr_triangle *t, const pr_mat4 *p, size_t P, size_t W, size_t H, const pr_mat4 *pj, pr_roi r, const int32_t *n, const int32_t *f) {
+                    return render_args_ok("job_sanitize", multi, span, t, 5, p, P, W, H, pj, r, n, f);
+                };
+                CHECK(render(tris, poses, 70, 640, 480, &proj, pr_roi{ 630, 470, 10, 10 }, plane, plane) == PR_OK);
+                CHECK(render(tris, nullptr, 0, 640, 480, &proj, none, nullptr, nullptr) == PR_OK);
+                CHECK(render(tris, poses, 70, 640, 480, &proj, none, plane, nullptr) == (span ? PR_ERR_INVALID : PR_OK));
+                CHECK(render(nullptr, poses, 70, 640, 480, &proj, none, plane, plane) == (multi ? PR_OK : PR_ERR_INVALID));
+                CHECK(render(tris, nullptr, 70, 640, 480, &proj, none, plane, plane) == PR_ERR_INVALID && render(tris, poses, 70, 640, 480, &proj, none, nullptr, plane) == PR_ERR_INVALID);
+                CHECK(render(tris, poses, 70, 640, 480, nullptr, none, plane, plane) == PR_ERR_INVALID && render(tris, poses, 70, 640, 480, &proj, off_frame, plane, plane) == PR_ERR_INVALID);
+                for (auto [W, H] : { std::pair<size_t, size_t>{ 0, 480 }, { 640, 0 }, { 8193, 1 }, { 8192, 4096 }, { size_t(1) << 40, size_t(1) << 40 } })
+                    CHECK(render(tris, poses, 70, W, H, &proj, none, plane, plane) == PR_ERR_INVALID);
+                CHECK(render(tris, poses, size_t(1) << 32, 640, 480, &proj, none, plane, plane) == (multi ? PR_ERR_INVALID : PR_OK));
+            }
     }
     // the pinned blocks of a slot: the parts in order, none overlapping, written and read back over their whole length
     for (size_t P : { size_t(0), size_t(1), size_t(3), size_t(65) }) {

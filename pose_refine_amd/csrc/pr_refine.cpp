@@ -55,39 +55,7 @@ int depth2cloud_impl(const T *depth_dev, uint32_t W, uint32_t H, const float K[9
     return PR_OK;
 }
 
-// ---- mixed batches (pr_*_multi): the hypotheses of several meshes in one call ---------------------------------------------------
-// The hypotheses grouped by mesh: a stable counting sort of the caller's indices.  Every mesh that has hypotheses is one group (in mesh
-// order); the batch runs in group order and its outputs go back to the caller's order.  Results do not depend on how a batch is composed
-// (each hypothesis equals its single-pose run), so the grouped batch gives every hypothesis what the single-mesh call gives it.
-struct MeshPlan {
-    std::vector<uint32_t> order;          // position in the grouped batch -> the caller's index
-    std::vector<uint32_t> box;            // position -> its group (= which of the groups' model boxes it uses)
-    std::vector<pr_mesh_ref> mesh;        // group -> mesh
-    std::vector<uint32_t> start;          // group -> first position; one more entry: the batch size
-};
-int plan_meshes(const char *fn, const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, size_t P, MeshPlan &pl)
-{
-    if (!meshes || n_meshes == 0 || !mesh_index) { set_error("%s: bad arguments (mesh table or mesh index missing)", fn); return PR_ERR_INVALID; }
-    for (uint32_t m = 0; m < n_meshes; ++m)
-        if (!meshes[m].tris_dev && meshes[m].n_tris > 0) { set_error("%s: mesh %u has %zu triangles and no array", fn, m, meshes[m].n_tris); return PR_ERR_INVALID; }
-    std::vector<uint32_t> first(n_meshes + 1, 0);
-    for (size_t i = 0; i < P; ++i) {
-        if (mesh_index[i] >= n_meshes) { set_error("%s: mesh_index[%zu] = %u, but there are %u meshes", fn, i, mesh_index[i], n_meshes); return PR_ERR_INVALID; }
-        first[mesh_index[i] + 1]++;
-    }
-    for (uint32_t m = 0; m < n_meshes; ++m) {
-        if (first[m + 1] > 0) { pl.mesh.push_back(meshes[m]); pl.start.push_back(first[m]); }
-        first[m + 1] += first[m];
-    }
-    pl.start.push_back((uint32_t)P);
-    std::vector<uint32_t> group_of(n_meshes, 0);
-    for (uint32_t k = 0, m = 0; m < n_meshes; ++m) if (first[m + 1] > first[m]) group_of[m] = k++;
-    pl.order.resize(P); pl.box.resize(P);
-    for (size_t i = 0; i < P; ++i) { const uint32_t j = first[mesh_index[i]]++; pl.order[j] = (uint32_t)i; pl.box[j] = group_of[mesh_index[i]]; }
-    return PR_OK;
-}
-// what the shared bodies of refine / score render: one mesh for every hypothesis, or a mixed batch in its plan's order
-struct MeshSource { const pr_triangle *tris; size_t n_tris; const MeshPlan *plan; };
+// ---- mixed batches (pr_*_multi): MeshPlan, MeshArg and Batch are pr_runtime.h's; here, what puts a plan on the device --------------------------
 // the device (g->multi) and pinned (g->h_multi) layout of a mixed batch's tables: [meshes: 16 B per group][box index: 4 B per hypothesis of
 // a chunk][raster groups: one per group at most].  Staged through pinned memory by kernels, like the poses (stage_poses): no copy commands.
 struct MultiLayout { size_t box, groups, bytes; };
@@ -279,7 +247,7 @@ int refine_core(const RefineJob &job, const pr_mat4 *poses_host, uint32_t P, pr_
                 const InfoPlan *info = nullptr)
 {
     if (P == 0) return PR_OK;
-    const MeshSource src{ job.tris, job.n_tris, job.plan };
+    const MeshSource &src = job.mesh;
     const uint32_t W = job.W, H = job.H;
     const float *K = job.K;
     SceneSel sc;
@@ -349,7 +317,7 @@ struct ReadBack {
     int queue(const void *dev, const PinBuf &pinned, uint32_t n_words) { next = pinned.as<unsigned char>(); HIP_TRY(prk::launch_copy_words32(dev, pinned.dev, n_words, g->stream)); return PR_OK; }
     void deliver(void *host, size_t bytes) { std::memcpy(host, next, bytes); next += bytes; }
 };
-// One request (checked: score_request_ok; P > 0) on the hypotheses as req.poses has them: one mesh, or (req.plan) a mixed batch in its plan's order.
+// One request (checked: score_request_ok; P > 0) on the hypotheses as req.poses has them: req.batch's, in its order.
 // kScoreOverlap / req.overlap: the P x P matrix of shared inlier pixels, in the order of req.poses.  Every chunk also leaves
 // its hypotheses' support bits (select.hip) and pixel boxes in workspaces sized for all P -- g->depth and g->bbox belong to the next chunk as soon
 // as this one is scored -- and one launch over all pairs follows the last chunk.  The planes are dense: P x H x ceil(W / 64) words of 8 bytes.
@@ -361,7 +329,7 @@ struct ReadBack {
 // kScoreNormals: the normal records of the same renders against the scene (normals.hip), one more kernel over every chunk's boxes right behind
 // the score kernel; the records travel like the scores.
 // kScoreCompose: the same renders taken together (compose.hip).  One more kernel over every chunk's boxes folds them into
-// the key frame of the context -- the front-most render of every frame pixel with the CALLER's index of its hypothesis (req.order: grouped position ->
+// the key frame of the context -- the front-most render of every frame pixel with the CALLER's index of its hypothesis (Batch::order: grouped position ->
 // caller's index, null: the identity), so ties and labels need no remapping -- and every chunk leaves its pixel boxes in a workspace sized for
 // all P, as for the overlap matrix.  Behind the last chunk: the counts of what every hypothesis keeps, then one pass over the frame for the labels,
 // the front depth and the frame record.  visible is written in the caller's order whatever `order` is.
@@ -377,7 +345,8 @@ int score_core(const ScoreRequest &req)
     const int32_t tau = req.tau;
     const bool contours = req.kind == kScoreContours, normals = req.kind == kScoreNormals, compose = req.kind == kScoreCompose, cover = req.kind == kScoreCover;
     const bool fit = req.kind == kScoreContourFit;
-    const MeshSource src{ req.tris, req.n_tris, req.plan };
+    const MeshSource &src = req.batch->src;
+    const uint32_t *order = req.batch->order();                   // grouped position -> caller's index (null: the identity)
     static_assert(sizeof(pr_pose_visible) == sizeof(pr_pose_score) && sizeof(pr_frame_explained) == sizeof(pr_pose_score), "pr_pose_visible, pr_frame_explained: 32-byte records");
     static_assert(sizeof(pr_pose_contour) == sizeof(pr_pose_score) && offsetof(pr_pose_contour, dist_sum) == 24, "pr_pose_contour: one 32-byte record, the sum in words 6 and 7");
     static_assert(sizeof(pr_pose_normal) == sizeof(pr_pose_score), "pr_pose_normal: one 32-byte record");
@@ -427,8 +396,8 @@ int score_core(const ScoreRequest &req)
         PR_TRY(g->cmp_box.ensure(sizeof(int4) * P + cmp_idx_bytes));
         PR_TRY(g->cmp_rec.ensure(cmp_rec_bytes));
         PR_TRY(g->h_cmp.ensure(cmp_rec_bytes + cmp_idx_bytes));
-        if (req.order) {
-            std::memcpy(g->h_cmp.as<unsigned char>() + cmp_rec_bytes, req.order, sizeof(uint32_t) * P);
+        if (order) {
+            std::memcpy(g->h_cmp.as<unsigned char>() + cmp_rec_bytes, order, sizeof(uint32_t) * P);
             cmp_index = reinterpret_cast<uint32_t *>(g->cmp_box.as<int4>() + P);
             HIP_TRY(prk::launch_stage_words(g->h_cmp.dev_as<unsigned char>() + cmp_rec_bytes, cmp_index, sizeof(uint32_t) * P, g->stream));
         }
@@ -543,87 +512,71 @@ int score_core(const ScoreRequest &req)
     return PR_OK;
 }
 
-// ---- mixed batches: the entry points' bodies (grouped batch in, outputs scattered back to the caller's order) -----------------------
-std::vector<pr_mat4> grouped_poses(const MeshPlan &pl, const pr_mat4 *poses_host)
+// ---- mixed batches: the entry points' bodies (a Batch in, outputs scattered back to the caller's order) ------------------------------------
+// pr_refine_batch_multi and the pyramid entries behind their argument checks: refine_core on the batch in its order (job.mesh = b.src) into
+// temporaries -- nothing reaches the caller's arrays unless the whole call succeeded -- and the records, cloud sizes and (py) per-level blocks
+// back to the caller's order.
+int refine_ordered(const RefineJob &job, const Batch &b, const PyramidPlan *py, pr_result *results_host, uint32_t *sizes_host)
 {
-    std::vector<pr_mat4> out(pl.order.size());
-    for (size_t j = 0; j < out.size(); ++j) out[j] = poses_host[pl.order[j]];
-    return out;
-}
-
-// pr_refine_batch_multi and both pr_refine_pyramid entries behind their argument checks: refine_core on the batch in its plan's order (job.plan;
-// none: the caller's) into temporaries -- nothing reaches the caller's arrays unless the whole call succeeded -- and the records, cloud sizes and
-// (py) per-level blocks back to the caller's order.
-int refine_ordered(const RefineJob &job, const PyramidPlan *py, const pr_mat4 *poses_host, uint32_t P, pr_result *results_host, uint32_t *sizes_host)
-{
-    std::vector<pr_mat4> grouped;
-    if (job.plan) { grouped = grouped_poses(*job.plan, poses_host); poses_host = grouped.data(); }
-    const uint32_t L = py ? py->n_levels : 0;
+    const uint32_t P = (uint32_t)b.P, L = py ? py->n_levels : 0;
     std::vector<pr_result> res(P), lres(py && py->level_results ? (size_t)L * P : 0);
     std::vector<uint32_t> sizes(P), lsizes(py && py->level_sizes ? (size_t)L * P : 0);
     const PyramidPlan inner{ py ? py->levels : nullptr, L, P, lres.empty() ? nullptr : lres.data(), lsizes.empty() ? nullptr : lsizes.data() };
-    PR_TRY(refine_core(job, poses_host, P, res.data(), sizes.data(), py ? &inner : nullptr));
-    for (uint32_t j = 0; j < P; ++j) {
-        const uint32_t o = job.plan ? job.plan->order[j] : j;
-        results_host[o] = res[j];
-        if (sizes_host) sizes_host[o] = sizes[j];
-        for (uint32_t l = 0; l < L; ++l) {
-            if (py->level_results) py->level_results[(size_t)l * P + o] = lres[(size_t)l * P + j];
-            if (py->level_sizes) py->level_sizes[(size_t)l * P + o] = lsizes[(size_t)l * P + j];
-        }
-    }
+    PR_TRY(refine_core(job, b.poses, P, res.data(), sizes.data(), py ? &inner : nullptr));
+    b.scatter(res.data(), results_host);
+    b.scatter(sizes.data(), sizes_host);
+    if (py) { b.scatter(lres.data(), py->level_results, L); b.scatter(lsizes.data(), py->level_sizes, L); }
     return PR_OK;
 }
 
-// Every scoring entry point behind PR_ENTER: the checks, then the request as it is, or -- a mixed batch -- on the batch grouped by mesh into
-// temporaries, and the scores, contours, normals and the matrix back to the caller's order: nothing reaches the caller's arrays unless the call succeeded
-// (the composition's records are written in the caller's order as they are: req.order).
-int score_run(const ScoreRequest &req)
+// A checked request (score_request_ok; P > 0) on its prepared batch: score_core with the poses in the batch's order.  One mesh: the request as it
+// is, into the caller's arrays.  A mesh table: into temporaries, and the scores, contours, normals, fit records and the matrix back to the caller's
+// order -- nothing reaches the caller's arrays unless the call succeeded (the composition's records are written in the caller's order as they
+// are: Batch::order).
+int score_run(const ScoreRequest &req, const Batch &b)
 {
-    PR_TRY(score_request_ok(req));
     const uint32_t P = req.P;
-    if (P == 0) { if (req.kind == kScoreCover && req.n_selected) *req.n_selected = 0; return PR_OK; }
-    if (!req.multi) return score_core(req);
-    MeshPlan pl;
-    PR_TRY(plan_meshes(req.fn, req.meshes, req.n_meshes, req.mesh_index, P, pl));
-    const std::vector<pr_mat4> poses = grouped_poses(pl, req.poses);
-    std::vector<pr_pose_score> sc(P);
-    std::vector<uint32_t> ov(req.overlap ? (size_t)P * P : 0);
-    std::vector<pr_pose_contour> cc(req.kind == kScoreContours ? P : 0);
-    std::vector<pr_pose_normal> nn(req.kind == kScoreNormals ? P : 0);
-    std::vector<pr_contour_fit> ff(req.kind == kScoreContourFit ? P : 0);
-    std::vector<pr_pose_info> fi(ff.size());
-    ScoreRequest grouped = req;
-    grouped.plan = &pl; grouped.order = pl.order.data(); grouped.poses = poses.data();
-    grouped.scores = sc.data(); grouped.overlap = req.overlap ? ov.data() : nullptr; grouped.contours = cc.data(); grouped.normals = nn.data();
-    std::vector<prk::FitMeta> fm(ff.size());
-    for (uint32_t j = 0; j < fm.size(); ++j) fm[j] = req.fit_meta[pl.order[j]];
-    grouped.fit = ff.data(); grouped.fit_info = fi.data(); grouped.fit_meta = fm.data();
-    // the cover walk runs on grouped positions: the order goes in through the inverse of pl.order, records and selected list come back through pl.order
-    const bool cover = req.kind == kScoreCover;
-    std::vector<uint32_t> where(cover ? P : 0), walk(cover ? req.cov_rule.n_order : 0), chosen(walk.size());
-    std::vector<pr_pose_cover> cv(cover ? P : 0);
+    ScoreRequest run = req;
+    run.batch = &b; run.poses = b.poses;
+    std::vector<pr_pose_score> sc; std::vector<uint32_t> ov; std::vector<pr_pose_contour> cc; std::vector<pr_pose_normal> nn;
+    std::vector<pr_contour_fit> ff; std::vector<pr_pose_info> fi; std::vector<prk::FitMeta> fm;
+    run.scores = b.temp(sc, P, req.scores);
+    if (req.overlap) run.overlap = b.temp(ov, (size_t)P * P, req.overlap);
+    if (req.contours) run.contours = b.temp(cc, P, req.contours);
+    if (req.normals) run.normals = b.temp(nn, P, req.normals);
+    if (req.fit) { run.fit = b.temp(ff, P, req.fit); run.fit_info = b.temp(fi, P, req.fit_info); run.fit_meta = b.gather(req.fit_meta, fm); }
+    // the cover walk of a mixed batch runs on grouped positions: the order goes in through the inverse, records and selected list come back through Batch::caller
+    const bool walk_mixed = req.kind == kScoreCover && b.mixed;
+    std::vector<uint32_t> walk(walk_mixed ? req.cov_rule.n_order : 0), chosen(walk.size());
+    std::vector<pr_pose_cover> cv(walk_mixed ? P : 0);
     pr_cover_frame cf{};
     uint32_t n_chosen = 0;
-    if (cover) {
-        for (uint32_t j = 0; j < P; ++j) where[pl.order[j]] = j;
+    if (walk_mixed) {
+        const std::vector<uint32_t> where = b.inverse();
         for (size_t k = 0; k < walk.size(); ++k) walk[k] = where[req.cov_order[k]];
-        grouped.cov_order = walk.data(); grouped.cover = cv.data(); grouped.cover_frame = &cf; grouped.selected = chosen.data(); grouped.n_selected = &n_chosen;
+        run.cov_order = walk.data(); run.cover = cv.data(); run.cover_frame = &cf; run.selected = chosen.data(); run.n_selected = &n_chosen;
     }
-    PR_TRY(score_core(grouped));
-    if (cover) {
-        for (uint32_t j = 0; j < P; ++j) req.cover[pl.order[j]] = cv[j];
-        for (uint32_t k = 0; k < n_chosen; ++k) req.selected[k] = pl.order[chosen[k]];
+    PR_TRY(score_core(run));
+    if (walk_mixed) {
+        b.scatter(cv.data(), req.cover);
+        for (uint32_t k = 0; k < n_chosen; ++k) req.selected[k] = b.caller(chosen[k]);
         *req.cover_frame = cf; *req.n_selected = n_chosen;
     }
-    for (uint32_t j = 0; j < P && req.scores; ++j) req.scores[pl.order[j]] = sc[j];
-    for (uint32_t j = 0; j < ff.size(); ++j) { req.fit[pl.order[j]] = ff[j]; req.fit_info[pl.order[j]] = fi[j]; }
-    for (uint32_t j = 0; j < cc.size(); ++j) req.contours[pl.order[j]] = cc[j];
-    for (uint32_t j = 0; j < nn.size(); ++j) req.normals[pl.order[j]] = nn[j];
-    if (req.overlap)                                             // rows and columns back into the caller's order
-        for (uint32_t a = 0; a < P; ++a)
-            for (uint32_t b = 0; b < P; ++b) req.overlap[(size_t)pl.order[a] * P + pl.order[b]] = ov[(size_t)a * P + b];
+    b.scatter(run.scores, req.scores);
+    b.scatter(run.fit, req.fit); b.scatter(run.fit_info, req.fit_info);
+    b.scatter(run.contours, req.contours);
+    b.scatter(run.normals, req.normals);
+    b.scatter_matrix(run.overlap, req.overlap);
     return PR_OK;
+}
+// Every scoring entry point behind PR_ENTER: the checks, then the batch (a mesh table's checks and grouping) and score_run
+int score_call(const ScoreRequest &req)
+{
+    PR_TRY(score_request_ok(req));
+    if (req.P == 0) { if (req.kind == kScoreCover && req.n_selected) *req.n_selected = 0; return PR_OK; }
+    Batch b;
+    PR_TRY(b.make(req.fn, req.mesh, req.poses, req.P));
+    return score_run(req, b);
 }
 // ---- visible surface discrepancy (pr_pose_vsd, pr_pose_vsd_multi) ------------------------------------------------------------------------
 // score_core's render (staged poses, model box, packed pixel boxes) of BOTH poses of every pair in one chunk, followed by one kernel that walks the
@@ -708,51 +661,37 @@ int solid_core(const MeshSource &src, const pr_mat4 *poses, uint32_t P, uint32_t
     return PR_OK;
 }
 
-// the request of an entry point from what all fourteen have in common, in the C arguments' order; the entry point adds its mesh or mesh table and the outputs of its kind
-ScoreRequest score_request(const char *fn, ScoreKind kind, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, pr_roi roi,
+// the request of an entry point from what all fourteen have in common, in the C arguments' order; the entry point's body adds the outputs of its kind
+ScoreRequest score_request(const char *fn, ScoreKind kind, const MeshArg &mesh, const pr_mat4 *poses_host, uint32_t P, uint32_t W, uint32_t H, const pr_mat4 *proj, pr_roi roi,
                            const void *scene_dev, int depth_is_i32, int32_t tau, pr_pose_score *scores_host)
 {
     ScoreRequest r{};
-    r.fn = fn; r.kind = kind; r.poses = poses_host; r.P = P; r.W = W; r.H = H; r.proj = proj; r.roi = roi;
+    r.fn = fn; r.kind = kind; r.mesh = mesh; r.poses = poses_host; r.P = P; r.W = W; r.H = H; r.proj = proj; r.roi = roi;
     r.scene = scene_dev; r.scene_i32 = depth_is_i32 != 0; r.tau = tau; r.scores = scores_host;
     return r;
 }
-// (the two images are the caller's device memory, written on this context's stream: call with g->mu held)
-void compose_outputs(ScoreRequest &r, uint16_t *labels_dev, int32_t *depth_dev, pr_pose_visible *visible_host, pr_frame_explained *frame_host)
-{
-    if (r.P && labels_dev) note_write(labels_dev, sizeof(uint16_t) * (size_t)r.W * r.H);
-    if (r.P && depth_dev) note_write(depth_dev, sizeof(int32_t) * (size_t)r.W * r.H);
-    r.labels_dev = labels_dev; r.depth_dev = depth_dev; r.visible = visible_host; r.frame = frame_host;
-}
-
 // pr_render, pr_render_span and pr_render_multi: P full frames (or the ROI) of one mesh, or of a mesh table in the caller's order -- the hypotheses are
-// grouped by mesh and the raster writes hypothesis j of the grouped batch into image order[j].  The planes are filled by kernels, one raster pass draws
+// grouped by mesh and the raster writes hypothesis j of the grouped batch into image Batch::caller(j).  The planes are filled by kernels, one raster pass draws
 // into near_dev (the nearest fragment of every pixel) and, given far_dev, into it as well (the farthest), and (zero_empty) "nothing drawn" becomes 0
 // in both.  Every check (render_args_ok, then the mesh table's) comes before anything is written.
-struct FrameSource { const pr_triangle *tris; size_t n_tris; bool multi; const pr_mesh_ref *meshes; uint32_t n_meshes; const uint32_t *mesh_index; };
-int render_frames(const char *fn, const FrameSource &src, const pr_mat4 *poses_host, size_t P, size_t W, size_t H, const pr_mat4 *proj, pr_roi roi,
+int render_frames(const char *fn, const MeshArg &src, const pr_mat4 *poses_host, size_t P, size_t W, size_t H, const pr_mat4 *proj, pr_roi roi,
                   int32_t *near_dev, int32_t *far_dev, bool span, bool zero_empty)
 {
     PR_TRY(render_args_ok(fn, src.multi, span, src.tris, src.n_tris, poses_host, P, W, H, proj, roi, near_dev, far_dev));
     if (P == 0) return PR_OK;
-    MeshPlan pl;
-    std::vector<pr_mat4> grouped;
-    if (src.multi) {
-        PR_TRY(plan_meshes(fn, src.meshes, src.n_meshes, src.mesh_index, P, pl));
-        grouped = grouped_poses(pl, poses_host);
-        poses_host = grouped.data();
-    }
+    Batch b;
+    PR_TRY(b.make(fn, src, poses_host, P));
     const auto [rw, rh] = image_extent(roi, W, H);
     SpanGuard sp(kSpanRender);
-    PR_TRY(stage_poses(poses_host, P));
+    PR_TRY(stage_poses(b.poses, P));
     prk::RasterMesh mesh{};
     prk::RasterTarget t{};
     t.depth = near_dev; t.far = far_dev; t.rw = (uint32_t)rw; t.rh = (uint32_t)rh; t.roi = roi; t.width = (uint32_t)W; t.height = (uint32_t)H; t.proj = proj;
-    if (src.multi) {
-        const MultiLayout l = multi_layout(pl.mesh.size(), P);     // the box-index slot holds the image of every hypothesis here
+    if (b.mixed) {
+        const MultiLayout l = multi_layout(b.pl.mesh.size(), P);     // the box-index slot holds the image of every hypothesis here
         PR_TRY(g->multi.ensure(l.bytes));
         PR_TRY(g->h_multi.ensure(l.bytes));
-        PR_TRY(stage_groups(pl, 0, (uint32_t)P, (uint32_t)P, pl.order.data(), mesh));
+        PR_TRY(stage_groups(b.pl, 0, (uint32_t)P, (uint32_t)P, b.order(), mesh));
         t.image_of = mesh.box_index;
     } else { mesh.tris = src.tris; mesh.n_tris = (uint32_t)src.n_tris; }
     HIP_TRY(prk::launch_fill_i32(near_dev, P * rw * rh, INT32_MAX, g->stream));
@@ -829,7 +768,7 @@ void drain_slots_reading(const void *p, size_t bytes)
     for (Slot &sl : g->slots) {
         if (!sl.pending || sl.delivered) continue;
         const RefineJob &r = (sl.worker_job && sl.worker) ? sl.worker->in : sl.again;     // (a helper thread's job is posted and read under g->mu by this thread only)
-        bool reads = hit(r.tris, r.n_tris * sizeof(pr_triangle)) || hit(r.results_dev, (size_t)sl.P * sizeof(pr_result));
+        bool reads = hit(r.mesh.tris, r.mesh.n_tris * sizeof(pr_triangle)) || hit(r.results_dev, (size_t)sl.P * sizeof(pr_result));
         if (r.scene_kind == PR_SCENE_NN)
             reads = reads || hit(r.sn.pcd, (size_t)r.sn.n_points * sizeof(pr_vec3)) || hit(r.sn.normal, (size_t)r.sn.n_points * sizeof(pr_vec3)) ||
                     hit(r.sn.nodes, (size_t)r.sn.n_nodes * sizeof(pr_kdnode));
@@ -878,6 +817,12 @@ void slot_release(Slot &sl)
 // tight_box's box kernel walks.  The fingerprint guards it as it guards the order -- and there it is what keeps a rewritten mesh from being CLIPPED.
 // (An indexed form of the soup with a per-pose vertex stage was built and measured as well: three divergent 16-byte gathers
 // per triangle cost the texture addresser more than the 170 saved VALU instructions give back -- 1.27 -> 1.32 ms per step.)
+// a batch still pending on a slot's streams finishes first (it stays pending: pr_refine_wait collects it; a helper thread's batch runs on a context of its own)
+int wait_pending_slots()
+{
+    for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+    return PR_OK;
+}
 int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
 {
     // The ordered copy costs a host sort (35 ms for obj_06): it is made for a buffer that STAYS -- on the second batch in a row that finds the
@@ -900,7 +845,7 @@ int ensure_model_box(const pr_triangle *tris_dev, size_t n_tris)
         std::vector<pr_triangle> sorted(n_tris);
         for (size_t k = 0; k < n_tris; ++k) sorted[k] = h[perm[k]];
         // the other slot's batch may still be rastering the previous copy (another mesh, or a rewritten one): let it finish first
-        for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
+        PR_TRY(wait_pending_slots());
         PR_TRY(g->mesh_sorted.ensure(sizeof(pr_triangle) * n_tris));
         HIP_TRY(hipMemcpy(g->mesh_sorted.p, sorted.data(), sizeof(pr_triangle) * n_tris, hipMemcpyHostToDevice));
         // the buffer's distinct vertices, from the same host copy (option tight_box: what pose_tight_box_kernel walks; obj_06: 94 404 -> 15 736)
@@ -1056,7 +1001,7 @@ prk::BatchCheck batch_check(const Slot &sl, const RefineJob &job, const SceneSel
     prk::BatchCheck chk{};
     chk.keys = sl.aabb_keys.as<uint32_t>();
     for (int a = 0; a < 6; ++a) chk.expect.v[a] = g->aabb_host[a];
-    chk.caller = job.tris; chk.mesh_hash = g->mesh_hash;
+    chk.caller = job.mesh.tris; chk.mesh_hash = g->mesh_hash;
     chk.flag = flag_dev;
     if (!opt.scene_cache) return chk;
     if (job.scene_kind == PR_SCENE_NN) {
@@ -1138,7 +1083,7 @@ int AsyncBatch::stage()
         g_tight_batches.fetch_add(1);
     }
     // the raster's triangles: the context's ordered copy (same triangles, same minima; the first render's checks read the caller's buffer)
-    raster_tris = (opt.mesh_order && g->mesh_sorted_valid) ? g->mesh_sorted.as<pr_triangle>() : job.tris;
+    raster_tris = (opt.mesh_order && g->mesh_sorted_valid) ? g->mesh_sorted.as<pr_triangle>() : job.mesh.tris;
     return PR_OK;
 }
 // one sub-batch, hypotheses [q0, q0 + nq): render, emit, the iteration loop
@@ -1160,7 +1105,7 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
     if (q0 == 0) HIP_TRY(hipStreamWaitEvent(st, sl.scene_ready, 0));
     if (tight) HIP_TRY(prk::launch_box_pack_offsets(d_box + q0, nq, d_off + q0, H, bands, st));
     prk::RasterMesh mesh{};
-    mesh.tris = raster_tris; mesh.n_tris = (uint32_t)job.n_tris;
+    mesh.tris = raster_tris; mesh.n_tris = (uint32_t)job.mesh.n_tris;
     prk::RasterTarget target{};
     target.depth = sl.depth.as<int32_t>(); target.box_off = d_off + q0; target.roi = none; target.bands = bands; target.width = W; target.height = H; target.proj = &job.proj;
     const prk::BoxRows rows{ sl.row_count.as<uint32_t>(), sl.row_off.as<uint32_t>(), sl.counts.as<uint32_t>() + q0, meta, dstate, arrive };
@@ -1189,7 +1134,7 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
         return PR_OK;
     };
     // the pass of the batch's last sub-batch behind which the other slot's render may start
-    const uint32_t release_pass = release_pass_for(job.n_tris, nq, g->cloud_hint, job.crit, job.scene_kind, timed, pipeline_start, opt.start_overlap, opt.overlap_pass);
+    const uint32_t release_pass = release_pass_for(job.mesh.n_tris, nq, g->cloud_hint, job.crit, job.scene_kind, timed, pipeline_start, opt.start_overlap, opt.overlap_pass);
     auto after = [&](uint32_t it, bool &) -> int {
         if (q0 + pl.sub >= P && it == release_pass) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
         return PR_OK;
@@ -1205,7 +1150,7 @@ int refine_submit_async(Slot &sl, const RefineJob &job, uint32_t P, pr_result *r
     AsyncBatch a{ sl, job, P };
     hipStream_t scene_stream = nullptr;
     PR_TRY(async_scene(sl, job, P, a.sc, scene_stream));
-    PR_TRY(ensure_model_box(job.tris, job.n_tris));             // once per triangle buffer ...
+    PR_TRY(ensure_model_box(job.mesh.tris, job.mesh.n_tris));             // once per triangle buffer ...
     const SlotIn in(P);
     const SlotOut out(P);
     PR_TRY(sl.h_out.ensure(out.bytes));
@@ -1301,18 +1246,197 @@ int refine_submit(Slot &sl, const RefineJob &job, const pr_mat4 *poses_host, uin
 
 using namespace prr;
 
+// ---- the bodies of the entry points that exist for one mesh and for a mesh table: each takes the mesh as a MeshArg, and its extern "C" forms
+// below only name it.  What is PR_TRY'd before PR_ENTER() needs no device and is refused on a machine without one.
+static int render_call(const char *fn, const MeshArg &mesh, const pr_mat4 *poses_host, size_t n_poses, size_t width, size_t height, const pr_mat4 *proj, pr_roi roi,
+                       int32_t *near_dev_out, int32_t *far_dev_out, bool span)
+{
+    PR_ENTER();
+    const auto [rw, rh] = image_extent(roi, width, height);
+    if (near_dev_out) note_write(near_dev_out, sizeof(int32_t) * n_poses * rw * rh);
+    if (far_dev_out) note_write(far_dev_out, sizeof(int32_t) * n_poses * rw * rh);
+    PR_TRY(render_frames(fn, mesh, poses_host, n_poses, width, height, proj, roi, near_dev_out, far_dev_out, span, true));
+    HIP_TRY(hipStreamSynchronize(g->stream));            // renderer.cu:295 cudaDeviceSynchronize
+    drain_spans();
+    return PR_OK;
+}
+// the scoring kinds: the request (score_request) with the outputs of its kind added, then score_call
+static int score_poses(const ScoreRequest &r) { PR_ENTER(); return score_call(r); }
+static int score_overlap(ScoreRequest r, uint32_t *overlap_host) { PR_ENTER(); r.overlap = overlap_host; return score_call(r); }
+static int score_cover(ScoreRequest r, const uint32_t *order, uint32_t n_order, uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep,
+                       pr_pose_cover *cover_host, pr_cover_frame *frame_host, uint32_t *selected_out, uint32_t *n_selected)
+{
+    PR_ENTER();
+    r.cov_order = order; r.cov_rule = prk::CoverRule{ new_num, new_den, min_new, max_keep, n_order };
+    r.cover = cover_host; r.cover_frame = frame_host; r.selected = selected_out; r.n_selected = n_selected;
+    return score_call(r);
+}
+static int score_contours(ScoreRequest r, int32_t jump_mm, const uint8_t *edge_dist_dev, pr_pose_contour *contours_host, uint32_t *overlap_host)
+{
+    PR_ENTER();
+    r.jump = jump_mm; r.edge_dist = edge_dist_dev; r.contours = contours_host; r.overlap = overlap_host;
+    return score_call(r);
+}
+static int score_normals(ScoreRequest r, const float K[9], uint32_t step, int32_t jump_mm, float cos_min, pr_pose_normal *normals_host, uint32_t *overlap_host)
+{
+    PR_TRY(normal_params_ok(r.fn, step, jump_mm, cos_min));          // before any device use
+    PR_ENTER();
+    r.K = K; r.step = step; r.jump = jump_mm; r.cos_min = cos_min; r.normals = normals_host; r.overlap = overlap_host;
+    return score_call(r);
+}
+static int compose_detections(ScoreRequest r, uint16_t *labels_dev_out, int32_t *depth_dev_out, pr_pose_visible *visible_host, pr_frame_explained *frame_host)
+{
+    PR_TRY(compose_args_ok(r.fn, r.P));          // before any device use
+    PR_ENTER();
+    if (r.P && labels_dev_out) note_write(labels_dev_out, sizeof(uint16_t) * (size_t)r.W * r.H);      // (the two images are the caller's device memory, written on this context's stream)
+    if (r.P && depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * (size_t)r.W * r.H);
+    r.labels_dev = labels_dev_out; r.depth_dev = depth_dev_out; r.visible = visible_host; r.frame = frame_host;
+    return score_call(r);
+}
+// pr_scene_edge_distance_dev and pr_scene_edge_nearest_dev: one image of Out per frame pixel from the scene's depth edges; launch(bits, rows, stream): the kind's launcher
+template <class Out, class Launch>
+static int scene_edge_call(const char *fn, const void *scene_depth_dev, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius, Out *out_dev, Launch &&launch)
+{
+    PR_ENTER();
+    if (!scene_depth_dev || !out_dev || width == 0 || height == 0) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
+    if (!frame_size_ok(width, height)) return PR_ERR_INVALID;
+    if (jump_mm < 0 || radius > PR_CONTOUR_MAX_RADIUS) {
+        set_error("%s: jump_mm must be >= 0 and radius <= PR_CONTOUR_MAX_RADIUS = %d (got %d, %u)", fn, PR_CONTOUR_MAX_RADIUS, (int)jump_mm, radius);
+        return PR_ERR_INVALID;
+    }
+    const size_t img = (size_t)width * height;
+    note_write(out_dev, sizeof(Out) * img);
+    PR_TRY(g->edge_bits.ensure(sizeof(uint64_t) * (size_t)height * prk::overlap_words_per_row(width)));
+    PR_TRY(g->edge_rows.ensure(img));
+    HIP_TRY(launch(g->edge_bits.as<unsigned long long>(), g->edge_rows.p, g->stream));
+    // the wait makes the call synchronous like every other entry point: the buffer is the caller's, who may hand it to another context (a private
+    // thread context has a stream of its own) or read it with the runtime directly; nothing is copied to or from the host
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return PR_OK;
+}
+
+// the four pyramid entry points (fn: whose messages; mesh: one mesh or a mesh table; robust: null, or the table of a _robust call)
+static int refine_pyramid_impl(const char *fn, const MeshArg &mesh, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj,
+                               const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
+                               pr_result *level_results_host, uint32_t *level_sizes_host, const pr_robust *robust, uint32_t n_robust)
+{
+    PR_TRY(pyramid_levels_ok(fn, levels, n_levels, n_poses, results_host));      // before any device use
+    PR_ENTER();
+    PR_TRY(wait_pending_slots());                                   // (the scene caches are shared with the asynchronous slots)
+    if (n_poses == 0) return PR_OK;
+    if (!poses_host) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
+    RefineJob job;                                                // (every level brings its own criteria)
+    PR_TRY(make_job(fn, mesh.tris, mesh.n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job, robust, n_robust, n_levels));
+    Batch b;
+    PR_TRY(b.make(fn, mesh, poses_host, n_poses));
+    job.mesh = b.src;
+    const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
+    return refine_ordered(job, b, &py, results_host, nullptr);
+}
+// what a _robust entry point refuses before it touches a device (so also on a machine without one), with nothing written
+static int robust_call_ok(const char *fn, const pr_pyramid_level *levels, uint32_t n_levels, uint32_t n_poses, const pr_result *results_host,
+                          const pr_robust *robust, uint32_t n_robust, bool pointers_ok)
+{
+    PR_TRY(pyramid_levels_ok(fn, levels, n_levels, n_poses, results_host));
+    PR_TRY(robust_table_ok(fn, robust, n_robust, n_levels));
+    if (n_poses && !pointers_ok) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+
+// pr_contour_information and its _multi form (a mesh table: a centre and a radius per mesh): the checks that need no request before any device is
+// touched, the batch, the centres in the camera frame exactly as pr_pose_information forms them (camera_centers; here in the caller's order: score_run
+// gathers them with the poses), then score_run on the batch
+static int contour_information_impl(ScoreRequest r, int32_t jump_mm, const uint32_t *nearest_dev, const float K[9], const float *centers_model,
+                                    const float *radii, pr_contour_fit *fit_host, pr_pose_info *info_host)
+{
+    const char *fn = r.fn;
+    const MeshArg &mesh = r.mesh;
+    PR_TRY(fit_intrinsics_ok(fn, K));
+    if (!centers_model || !radii) { set_error("%s: bad arguments (a null centre or radius)", fn); return PR_ERR_INVALID; }
+    PR_TRY(info_center_radius_ok(fn, centers_model, radii, mesh.multi ? mesh.n_meshes : 1u));
+    if (r.P && (!r.poses || (mesh.multi && !mesh.mesh_index))) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
+    Batch b;
+    PR_TRY(b.make(fn, mesh, r.poses, r.P));
+    std::vector<prk::FitMeta> meta(r.P);
+    std::vector<float> centers(3 * (size_t)r.P), rad(r.P);
+    camera_centers(r.poses, mesh.mesh_index, r.P, centers_model, radii, centers.data(), rad.data());
+    for (uint32_t j = 0; j < r.P; ++j) { std::memcpy(meta[j].c, &centers[3 * (size_t)j], sizeof meta[j].c); meta[j].rho = rad[j]; }
+    PR_TRY(info_center_radius_ok(fn, centers.data(), rad.data(), r.P));      // (a pose with a non-finite entry)
+    r.jump = jump_mm; r.nearest = nearest_dev; r.K = K; r.fit_meta = meta.data(); r.fit = fit_host; r.fit_info = info_host;
+    PR_TRY(score_request_ok(r));                                    // every remaining check before the device is touched
+    if (r.P == 0) return PR_OK;
+    PR_ENTER();
+    return score_run(r, b);
+}
+
+// pr_pose_penetration and its _multi form: the records of a mesh table's batch into a temporary (nothing reaches pairs_host unless the call
+// succeeded), rows and columns back to the caller's order as pr_score_overlap_multi's matrix; one mesh's straight into pairs_host
+static int pose_penetration(const char *fn, const MeshArg &mesh, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj,
+                            int32_t slack_mm, pr_pair_solid *pairs_host)
+{
+    PR_TRY(penetration_args_ok(fn, mesh.multi, mesh.tris, mesh.n_tris, poses_host, n_poses, width, height, proj, slack_mm, pairs_host));   // before any device use, like the mesh table's checks
+    if (n_poses == 0) return PR_OK;
+    Batch b;
+    PR_TRY(b.make(fn, mesh, poses_host, n_poses));
+    PR_ENTER();
+    std::vector<pr_pair_solid> tmp;
+    pr_pair_solid *rec = b.temp(tmp, (size_t)n_poses * n_poses, pairs_host);
+    PR_TRY(solid_core(b.src, b.poses, n_poses, width, height, proj, slack_mm, rec));
+    b.scatter_matrix(rec, pairs_host);
+    return PR_OK;
+}
+
+// pr_pose_information and its _multi form (a mesh table: a centre and a radius per mesh): every check before any device is touched, the centres
+// in the camera frame on the host (in the batch's order, like everything refine_core takes), refine_core with the information pass into
+// temporaries, and the records back to the caller's order.
+static int pose_information_impl(const char *fn, const MeshArg &mesh, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj,
+                                 const float K[9], int scene_kind, const void *scene, pr_roi roi, const pr_robust *robust, const float *centers_model,
+                                 const float *radii, pr_pose_info *info_host, pr_pose_eig *eig_host, uint32_t *cloud_sizes_host)
+{
+    if (robust) PR_TRY(robust_desc_ok(fn, robust));
+    RefineJob job;
+    PR_TRY(make_job(fn, mesh.tris, mesh.n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job));
+    if (!centers_model || !radii || (n_poses && (!poses_host || !info_host))) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    Batch b;
+    PR_TRY(b.make(fn, mesh, poses_host, n_poses));
+    job.mesh = b.src;
+    PR_TRY(info_center_radius_ok(fn, centers_model, radii, mesh.multi ? mesh.n_meshes : 1u));
+    std::vector<uint32_t> mesh_of;
+    std::vector<float> centers(3 * (size_t)n_poses), rad(n_poses);
+    camera_centers(b.poses, mesh.multi ? b.gather(mesh.mesh_index, mesh_of) : nullptr, n_poses, centers_model, radii, centers.data(), rad.data());
+    PR_TRY(info_center_radius_ok(fn, centers.data(), rad.data(), n_poses));      // (a pose with a non-finite entry)
+    if (n_poses == 0) return PR_OK;
+    PR_ENTER();
+    PR_TRY(wait_pending_slots());                                   // (the scene caches are shared with the asynchronous slots)
+    std::vector<pr_pose_info> info(n_poses);
+    std::vector<pr_pose_eig> eig(eig_host ? n_poses : 0);
+    std::vector<uint32_t> sizes(n_poses);
+    const InfoPlan ip{ robust ? *robust : pr_robust{ PR_ROBUST_NONE, 0.0f, 0.0f, 0 }, centers.data(), rad.data(), info.data(), eig_host ? eig.data() : nullptr };
+    PR_TRY(refine_core(job, b.poses, n_poses, nullptr, sizes.data(), nullptr, &ip));
+    b.scatter(info.data(), info_host);
+    b.scatter(eig.data(), eig_host);
+    b.scatter(sizes.data(), cloud_sizes_host);
+    return PR_OK;
+}
+
 extern "C" {
 
 int pr_render(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t n_poses, size_t width, size_t height,
               const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev_out)
 {
-    PR_ENTER();
-    const auto [rw, rh] = image_extent(roi, width, height);
-    if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * rw * rh);
-    PR_TRY(render_frames("pr_render", FrameSource{ tris_dev, n_tris }, poses_host, n_poses, width, height, proj, roi, depth_dev_out, nullptr, false, true));
-    HIP_TRY(hipStreamSynchronize(g->stream));            // renderer.cu:295 cudaDeviceSynchronize
-    drain_spans();
-    return PR_OK;
+    return render_call("pr_render", MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, depth_dev_out, nullptr, false);
+}
+
+int pr_render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, size_t n_poses,
+                    size_t width, size_t height, const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev_out)
+{
+    return render_call("pr_render_multi", MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi, depth_dev_out, nullptr, false);
+}
+
+int pr_render_span(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t n_poses, size_t width, size_t height,
+                   const pr_mat4 *proj, pr_roi roi, int32_t *near_dev_out, int32_t *far_dev_out)
+{
+    return render_call("pr_render_span", MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, near_dev_out, far_dev_out, true);
 }
 
 int pr_render_to_host(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t n_poses, size_t width, size_t height,
@@ -1321,7 +1445,7 @@ int pr_render_to_host(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 
     PR_ENTER();
     const auto [rw, rh] = image_extent(roi, width, height);
     PR_TRY(g->depth.ensure(sizeof(int32_t) * std::max<size_t>(1, n_poses * rw * rh)));
-    PR_TRY(render_frames("pr_render", FrameSource{ tris_dev, n_tris }, poses_host, n_poses, width, height, proj, roi, g->depth.as<int32_t>(), nullptr, false, true));
+    PR_TRY(render_frames("pr_render", MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, g->depth.as<int32_t>(), nullptr, false, true));
     HIP_TRY(hipMemcpyAsync(depth_host_out, g->depth.p, sizeof(int32_t) * n_poses * rw * rh, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     drain_spans();
@@ -1342,28 +1466,6 @@ int pr_depth2cloud_u16(const uint16_t *depth_dev, uint32_t width, uint32_t heigh
     return depth2cloud_impl<uint16_t>(depth_dev, width, height, K, stride, tl_x, tl_y, cloud_dev_out, n_points);
 }
 
-int pr_score_poses(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
-                   const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host)
-{
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_poses", kScorePoses, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.tris = tris_dev; r.n_tris = n_tris;
-    return score_run(r);
-}
-
-int pr_render_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, size_t n_poses,
-                    size_t width, size_t height, const pr_mat4 *proj, pr_roi roi, int32_t *depth_dev_out)
-{
-    PR_ENTER();
-    const auto [rw, rh] = image_extent(roi, width, height);
-    if (depth_dev_out) note_write(depth_dev_out, sizeof(int32_t) * n_poses * rw * rh);
-    PR_TRY(render_frames("pr_render_multi", FrameSource{ nullptr, 0, true, meshes, n_meshes, mesh_index_host }, poses_host, n_poses, width, height, proj, roi,
-                         depth_dev_out, nullptr, false, true));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    drain_spans();
-    return PR_OK;
-}
-
 int pr_refine_batch_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
                           uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
                           const void *scene, pr_criteria crit, pr_roi roi, pr_result *results_host, uint32_t *cloud_sizes_host)
@@ -1373,42 +1475,10 @@ int pr_refine_batch_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const ui
     if (!results_host || !poses_host) { set_error("pr_refine_batch_multi: bad arguments"); return PR_ERR_INVALID; }
     RefineJob job;
     PR_TRY(make_job("pr_refine_batch_multi", nullptr, 0, width, height, proj, K, scene_kind, scene, crit, roi, nullptr, job));
-    MeshPlan pl;
-    PR_TRY(plan_meshes("pr_refine_batch_multi", meshes, n_meshes, mesh_index_host, n_poses, pl));
-    job.plan = &pl;
-    return refine_ordered(job, nullptr, poses_host, n_poses, results_host, cloud_sizes_host);
-}
-
-// the four pyramid entry points (fn: whose messages; multi: a mixed batch, the mesh table instead of tris_dev; robust: null, or the table of a _robust call)
-static int refine_pyramid_impl(const char *fn, bool multi, const pr_triangle *tris_dev, size_t n_tris, const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host,
-                               const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, const float K[9], int scene_kind,
-                               const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
-                               pr_result *level_results_host, uint32_t *level_sizes_host, const pr_robust *robust, uint32_t n_robust)
-{
-    PR_TRY(pyramid_levels_ok(fn, levels, n_levels, n_poses, results_host));      // before any device use
-    PR_ENTER();
-    // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
-    for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
-    if (n_poses == 0) return PR_OK;
-    if (!poses_host) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
-    RefineJob job;                                                // (every level brings its own criteria)
-    PR_TRY(make_job(fn, tris_dev, n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job, robust, n_robust, n_levels));
-    MeshPlan pl;
-    if (multi) {
-        PR_TRY(plan_meshes(fn, meshes, n_meshes, mesh_index_host, n_poses, pl));
-        job.plan = &pl;
-    }
-    const PyramidPlan py{ levels, n_levels, n_poses, level_results_host, level_sizes_host };
-    return refine_ordered(job, &py, poses_host, n_poses, results_host, nullptr);
-}
-// what a _robust entry point refuses before it touches a device (so also on a machine without one), with nothing written
-static int robust_call_ok(const char *fn, const pr_pyramid_level *levels, uint32_t n_levels, uint32_t n_poses, const pr_result *results_host,
-                          const pr_robust *robust, uint32_t n_robust, bool pointers_ok)
-{
-    PR_TRY(pyramid_levels_ok(fn, levels, n_levels, n_poses, results_host));
-    PR_TRY(robust_table_ok(fn, robust, n_robust, n_levels));
-    if (n_poses && !pointers_ok) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
-    return PR_OK;
+    Batch b;
+    PR_TRY(b.make("pr_refine_batch_multi", MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses));
+    job.mesh = b.src;
+    return refine_ordered(job, b, nullptr, results_host, cloud_sizes_host);
 }
 
 int pr_refine_pyramid_robust(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
@@ -1418,8 +1488,8 @@ int pr_refine_pyramid_robust(const pr_triangle *tris_dev, size_t n_tris, const p
 {
     const char *fn = "pr_refine_pyramid_robust";
     PR_TRY(robust_call_ok(fn, levels, n_levels, n_poses, results_host, robust, n_robust, poses_host && proj && K && scene && (tris_dev || n_tris == 0)));
-    return refine_pyramid_impl(fn, false, tris_dev, n_tris, nullptr, 0, nullptr, poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels, n_levels, roi,
-                               results_host, level_results_host, level_sizes_host, robust, n_robust);
+    return refine_pyramid_impl(fn, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels, n_levels, roi, results_host, level_results_host,
+                               level_sizes_host, robust, n_robust);
 }
 
 int pr_refine_pyramid_robust_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1429,16 +1499,16 @@ int pr_refine_pyramid_robust_multi(const pr_mesh_ref *meshes, uint32_t n_meshes,
 {
     const char *fn = "pr_refine_pyramid_robust_multi";
     PR_TRY(robust_call_ok(fn, levels, n_levels, n_poses, results_host, robust, n_robust, poses_host && proj && K && scene && meshes && mesh_index_host));
-    return refine_pyramid_impl(fn, true, nullptr, 0, meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels,
-                               n_levels, roi, results_host, level_results_host, level_sizes_host, robust, n_robust);
+    return refine_pyramid_impl(fn, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels, n_levels, roi, results_host,
+                               level_results_host, level_sizes_host, robust, n_robust);
 }
 
 int pr_refine_pyramid(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                       const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, const pr_pyramid_level *levels, uint32_t n_levels,
                       pr_roi roi, pr_result *results_host, pr_result *level_results_host, uint32_t *level_sizes_host)
 {
-    return refine_pyramid_impl("pr_refine_pyramid", false, tris_dev, n_tris, nullptr, 0, nullptr, poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels,
-                               n_levels, roi, results_host, level_results_host, level_sizes_host, nullptr, 0);
+    return refine_pyramid_impl("pr_refine_pyramid", MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels, n_levels, roi, results_host,
+                               level_results_host, level_sizes_host, nullptr, 0);
 }
 
 int pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1446,40 +1516,38 @@ int pr_refine_pyramid_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
                             const void *scene, const pr_pyramid_level *levels, uint32_t n_levels, pr_roi roi, pr_result *results_host,
                             pr_result *level_results_host, uint32_t *level_sizes_host)
 {
-    return refine_pyramid_impl("pr_refine_pyramid_multi", true, nullptr, 0, meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K, scene_kind, scene,
-                               levels, n_levels, roi, results_host, level_results_host, level_sizes_host, nullptr, 0);
+    return refine_pyramid_impl("pr_refine_pyramid_multi", MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, K, scene_kind, scene, levels, n_levels, roi,
+                               results_host, level_results_host, level_sizes_host, nullptr, 0);
+}
+
+int pr_score_poses(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
+                   const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host)
+{
+    return score_poses(score_request("pr_score_poses", kScorePoses, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host));
 }
 
 int pr_score_poses_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
                          uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
                          int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host)
 {
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_poses_multi", kScorePoses, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
-    return score_run(r);
+    return score_poses(score_request("pr_score_poses_multi", kScorePoses, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi, scene_depth_dev,
+                       depth_is_i32, tau_mm, scores_host));
 }
 
 int pr_score_overlap(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                      const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host,
                      uint32_t *overlap_host)
 {
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_overlap", kScoreOverlap, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.tris = tris_dev; r.n_tris = n_tris;
-    r.overlap = overlap_host;
-    return score_run(r);
+    return score_overlap(score_request("pr_score_overlap", kScoreOverlap, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm,
+                         scores_host), overlap_host);
 }
 
 int pr_score_overlap_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
                            uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev,
                            int depth_is_i32, int32_t tau_mm, pr_pose_score *scores_host, uint32_t *overlap_host)
 {
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_overlap_multi", kScoreOverlap, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
-    r.overlap = overlap_host;
-    return score_run(r);
+    return score_overlap(score_request("pr_score_overlap_multi", kScoreOverlap, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi, scene_depth_dev,
+                         depth_is_i32, tau_mm, scores_host), overlap_host);
 }
 
 int pr_score_cover(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
@@ -1487,12 +1555,8 @@ int pr_score_cover(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *po
                    uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep, pr_pose_score *scores_host, pr_pose_cover *cover_host,
                    pr_cover_frame *frame_host, uint32_t *selected_out, uint32_t *n_selected)
 {
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_cover", kScoreCover, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.tris = tris_dev; r.n_tris = n_tris;
-    r.cov_order = order; r.cov_rule = prk::CoverRule{ new_num, new_den, min_new, max_keep, n_order };
-    r.cover = cover_host; r.cover_frame = frame_host; r.selected = selected_out; r.n_selected = n_selected;
-    return score_run(r);
+    return score_cover(score_request("pr_score_cover", kScoreCover, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host),
+                       order, n_order, new_num, new_den, min_new, max_keep, cover_host, frame_host, selected_out, n_selected);
 }
 
 int pr_score_cover_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
@@ -1500,45 +1564,32 @@ int pr_score_cover_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uin
                          const uint32_t *order, uint32_t n_order, uint32_t new_num, uint32_t new_den, uint32_t min_new, uint32_t max_keep,
                          pr_pose_score *scores_host, pr_pose_cover *cover_host, pr_cover_frame *frame_host, uint32_t *selected_out, uint32_t *n_selected)
 {
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_cover_multi", kScoreCover, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
-    r.cov_order = order; r.cov_rule = prk::CoverRule{ new_num, new_den, min_new, max_keep, n_order };
-    r.cover = cover_host; r.cover_frame = frame_host; r.selected = selected_out; r.n_selected = n_selected;
-    return score_run(r);
+    return score_cover(score_request("pr_score_cover_multi", kScoreCover, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi, scene_depth_dev,
+                       depth_is_i32, tau_mm, scores_host), order, n_order, new_num, new_den, min_new, max_keep, cover_host, frame_host, selected_out, n_selected);
 }
 
 int pr_scene_edge_distance_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
                                uint8_t *dist_dev_out)
 {
-    PR_ENTER();
-    if (!scene_depth_dev || !dist_dev_out || width == 0 || height == 0) { set_error("pr_scene_edge_distance_dev: bad arguments"); return PR_ERR_INVALID; }
-    if (!frame_size_ok(width, height)) return PR_ERR_INVALID;
-    if (jump_mm < 0 || radius > PR_CONTOUR_MAX_RADIUS) {
-        set_error("pr_scene_edge_distance_dev: jump_mm must be >= 0 and radius <= PR_CONTOUR_MAX_RADIUS = %d (got %d, %u)", PR_CONTOUR_MAX_RADIUS, (int)jump_mm, radius);
-        return PR_ERR_INVALID;
-    }
-    const size_t img = (size_t)width * height;
-    note_write(dist_dev_out, img);
-    PR_TRY(g->edge_bits.ensure(sizeof(uint64_t) * (size_t)height * prk::overlap_words_per_row(width)));
-    PR_TRY(g->edge_rows.ensure(img));
-    HIP_TRY(prk::launch_scene_edge_distance(scene_depth_dev, depth_is_i32 != 0, width, height, jump_mm, radius, g->edge_bits.as<unsigned long long>(),
-                                            g->edge_rows.as<uint8_t>(), dist_dev_out, g->stream));
-    // the wait makes the call synchronous like every other entry point: the buffer is the caller's, who may hand it to another context (a private
-    // thread context has a stream of its own) or read it with the runtime directly; nothing is copied to or from the host
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return PR_OK;
+    return scene_edge_call("pr_scene_edge_distance_dev", scene_depth_dev, width, height, jump_mm, radius, dist_dev_out, [&](unsigned long long *bits, void *rows, hipStream_t st) {
+        return prk::launch_scene_edge_distance(scene_depth_dev, depth_is_i32 != 0, width, height, jump_mm, radius, bits, static_cast<uint8_t *>(rows), dist_dev_out, st);
+    });
+}
+
+int pr_scene_edge_nearest_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
+                              uint32_t *nearest_dev_out)
+{
+    return scene_edge_call("pr_scene_edge_nearest_dev", scene_depth_dev, width, height, jump_mm, radius, nearest_dev_out, [&](unsigned long long *bits, void *rows, hipStream_t st) {
+        return prk::launch_scene_edge_nearest(scene_depth_dev, depth_is_i32 != 0, width, height, jump_mm, radius, bits, static_cast<int8_t *>(rows), nearest_dev_out, st);
+    });
 }
 
 int pr_score_contours(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                       const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, int32_t jump_mm,
                       const uint8_t *edge_dist_dev, pr_pose_score *scores_host, pr_pose_contour *contours_host, uint32_t *overlap_host)
 {
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_contours", kScoreContours, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.tris = tris_dev; r.n_tris = n_tris;
-    r.jump = jump_mm; r.edge_dist = edge_dist_dev; r.contours = contours_host; r.overlap = overlap_host;
-    return score_run(r);
+    return score_contours(score_request("pr_score_contours", kScoreContours, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm,
+                          scores_host), jump_mm, edge_dist_dev, contours_host, overlap_host);
 }
 
 int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1546,63 +1597,8 @@ int pr_score_contours_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const 
                             int depth_is_i32, int32_t tau_mm, int32_t jump_mm, const uint8_t *edge_dist_dev, pr_pose_score *scores_host,
                             pr_pose_contour *contours_host, uint32_t *overlap_host)
 {
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_contours_multi", kScoreContours, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
-    r.jump = jump_mm; r.edge_dist = edge_dist_dev; r.contours = contours_host; r.overlap = overlap_host;
-    return score_run(r);
-}
-
-int pr_scene_edge_nearest_dev(const void *scene_depth_dev, int depth_is_i32, uint32_t width, uint32_t height, int32_t jump_mm, uint32_t radius,
-                              uint32_t *nearest_dev_out)
-{
-    PR_ENTER();
-    if (!scene_depth_dev || !nearest_dev_out || width == 0 || height == 0) { set_error("pr_scene_edge_nearest_dev: bad arguments"); return PR_ERR_INVALID; }
-    if (!frame_size_ok(width, height)) return PR_ERR_INVALID;
-    if (jump_mm < 0 || radius > PR_CONTOUR_MAX_RADIUS) {
-        set_error("pr_scene_edge_nearest_dev: jump_mm must be >= 0 and radius <= PR_CONTOUR_MAX_RADIUS = %d (got %d, %u)", PR_CONTOUR_MAX_RADIUS, (int)jump_mm, radius);
-        return PR_ERR_INVALID;
-    }
-    const size_t img = (size_t)width * height;
-    note_write(nearest_dev_out, sizeof(uint32_t) * img);
-    PR_TRY(g->edge_bits.ensure(sizeof(uint64_t) * (size_t)height * prk::overlap_words_per_row(width)));
-    PR_TRY(g->edge_rows.ensure(img));
-    HIP_TRY(prk::launch_scene_edge_nearest(scene_depth_dev, depth_is_i32 != 0, width, height, jump_mm, radius, g->edge_bits.as<unsigned long long>(),
-                                           g->edge_rows.as<int8_t>(), nearest_dev_out, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));                      // synchronous like pr_scene_edge_distance_dev, and for its reasons
-    return PR_OK;
-}
-
-// pr_contour_information and its _multi form (multi: the mesh table instead of tris_dev, a centre and a radius per mesh): the checks that need no
-// request before any device is touched, the centres in the camera frame exactly as pr_pose_information forms them, then score_run
-static int contour_information_impl(ScoreRequest &r, int32_t jump_mm, const uint32_t *nearest_dev, const float K[9], const float *centers_model,
-                                    const float *radii, pr_contour_fit *fit_host, pr_pose_info *info_host)
-{
-    const char *fn = r.fn;
-    PR_TRY(fit_intrinsics_ok(fn, K));
-    const uint32_t n_centers = r.multi ? r.n_meshes : 1u;
-    if (!centers_model || !radii) { set_error("%s: bad arguments (a null centre or radius)", fn); return PR_ERR_INVALID; }
-    PR_TRY(info_center_radius_ok(fn, centers_model, radii, n_centers));
-    if (r.P && (!r.poses || (r.multi && !r.mesh_index))) { set_error("%s: bad arguments", fn); return PR_ERR_INVALID; }
-    if (r.multi) { MeshPlan pl; PR_TRY(plan_meshes(fn, r.meshes, r.n_meshes, r.mesh_index, r.P, pl)); }      // (the mesh table's checks; score_run plans again)
-    std::vector<prk::FitMeta> meta(r.P);
-    std::vector<float> centers(3 * (size_t)r.P), rad(r.P);
-    for (uint32_t j = 0; j < r.P; ++j) {
-        const uint32_t m = r.multi ? r.mesh_index[j] : 0u;
-        if (m >= n_centers) { set_error("%s: mesh_index[%u] = %u, but there are %u meshes", fn, j, m, n_centers); return PR_ERR_INVALID; }
-        const float *M = r.poses[j].m, *cm = centers_model + 3 * (size_t)m;
-        for (int a = 0; a < 3; ++a) {
-            const double v = (((double)M[4 * a] * (double)cm[0] + (double)M[4 * a + 1] * (double)cm[1]) + (double)M[4 * a + 2] * (double)cm[2]) + (double)M[4 * a + 3];
-            centers[3 * (size_t)j + a] = meta[j].c[a] = (float)(v / 1000.0);
-        }
-        rad[j] = meta[j].rho = radii[m];
-    }
-    PR_TRY(info_center_radius_ok(fn, centers.data(), rad.data(), r.P));      // (a pose with a non-finite entry)
-    r.jump = jump_mm; r.nearest = nearest_dev; r.K = K; r.fit_meta = meta.data(); r.fit = fit_host; r.fit_info = info_host;
-    PR_TRY(score_request_ok(r));                                    // every remaining check before the device is touched (score_run asks again)
-    if (r.P == 0) return PR_OK;
-    PR_ENTER();
-    return score_run(r);
+    return score_contours(score_request("pr_score_contours_multi", kScoreContours, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi, scene_depth_dev,
+                          depth_is_i32, tau_mm, scores_host), jump_mm, edge_dist_dev, contours_host, overlap_host);
 }
 
 int pr_contour_information(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
@@ -1610,10 +1606,8 @@ int pr_contour_information(const pr_triangle *tris_dev, size_t n_tris, const pr_
                            const uint32_t *nearest_dev, const float K[9], const float *center_model, float radius, pr_pose_score *scores_host_or_null,
                            pr_contour_fit *fit_host, pr_pose_info *info_host)
 {
-    ScoreRequest r = score_request("pr_contour_information", kScoreContourFit, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm,
-                                   scores_host_or_null);
-    r.tris = tris_dev; r.n_tris = n_tris;
-    return contour_information_impl(r, jump_mm, nearest_dev, K, center_model, &radius, fit_host, info_host);
+    return contour_information_impl(score_request("pr_contour_information", kScoreContourFit, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, scene_depth_dev,
+                                    depth_is_i32, tau_mm, scores_host_or_null), jump_mm, nearest_dev, K, center_model, &radius, fit_host, info_host);
 }
 
 int pr_contour_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
@@ -1621,22 +1615,16 @@ int pr_contour_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, c
                                  int32_t jump_mm, const uint32_t *nearest_dev, const float K[9], const float *centers_model, const float *radii,
                                  pr_pose_score *scores_host_or_null, pr_contour_fit *fit_host, pr_pose_info *info_host)
 {
-    ScoreRequest r = score_request("pr_contour_information_multi", kScoreContourFit, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32,
-                                   tau_mm, scores_host_or_null);
-    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
-    return contour_information_impl(r, jump_mm, nearest_dev, K, centers_model, radii, fit_host, info_host);
+    return contour_information_impl(score_request("pr_contour_information_multi", kScoreContourFit, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi,
+                                    scene_depth_dev, depth_is_i32, tau_mm, scores_host_or_null), jump_mm, nearest_dev, K, centers_model, radii, fit_host, info_host);
 }
 
 int pr_score_normals(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                      const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, const float K[9], uint32_t step,
                      int32_t jump_mm, float cos_min, pr_pose_score *scores_host, pr_pose_normal *normals_host, uint32_t *overlap_host)
 {
-    PR_TRY(normal_params_ok("pr_score_normals", step, jump_mm, cos_min));          // before any device use
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_normals", kScoreNormals, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.tris = tris_dev; r.n_tris = n_tris;
-    r.K = K; r.step = step; r.jump = jump_mm; r.cos_min = cos_min; r.normals = normals_host; r.overlap = overlap_host;
-    return score_run(r);
+    return score_normals(score_request("pr_score_normals", kScoreNormals, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm,
+                         scores_host), K, step, jump_mm, cos_min, normals_host, overlap_host);
 }
 
 int pr_score_normals_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1644,24 +1632,16 @@ int pr_score_normals_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const u
                            int depth_is_i32, int32_t tau_mm, const float K[9], uint32_t step, int32_t jump_mm, float cos_min,
                            pr_pose_score *scores_host, pr_pose_normal *normals_host, uint32_t *overlap_host)
 {
-    PR_TRY(normal_params_ok("pr_score_normals_multi", step, jump_mm, cos_min));          // before any device use
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_score_normals_multi", kScoreNormals, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
-    r.K = K; r.step = step; r.jump = jump_mm; r.cos_min = cos_min; r.normals = normals_host; r.overlap = overlap_host;
-    return score_run(r);
+    return score_normals(score_request("pr_score_normals_multi", kScoreNormals, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi, scene_depth_dev,
+                         depth_is_i32, tau_mm, scores_host), K, step, jump_mm, cos_min, normals_host, overlap_host);
 }
 
 int pr_compose_detections(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                           const pr_mat4 *proj, pr_roi roi, const void *scene_depth_dev, int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out,
                           int32_t *depth_dev_out, pr_pose_score *scores_host, pr_pose_visible *visible_host, pr_frame_explained *frame_host)
 {
-    PR_TRY(compose_args_ok("pr_compose_detections", n_poses));          // before any device use
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_compose_detections", kScoreCompose, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.tris = tris_dev; r.n_tris = n_tris;
-    compose_outputs(r, labels_dev_out, depth_dev_out, visible_host, frame_host);
-    return score_run(r);
+    return compose_detections(score_request("pr_compose_detections", kScoreCompose, MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32,
+                              tau_mm, scores_host), labels_dev_out, depth_dev_out, visible_host, frame_host);
 }
 
 int pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host,
@@ -1669,12 +1649,8 @@ int pr_compose_detections_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, co
                                 int depth_is_i32, int32_t tau_mm, uint16_t *labels_dev_out, int32_t *depth_dev_out, pr_pose_score *scores_host,
                                 pr_pose_visible *visible_host, pr_frame_explained *frame_host)
 {
-    PR_TRY(compose_args_ok("pr_compose_detections_multi", n_poses));          // before any device use
-    PR_ENTER();
-    ScoreRequest r = score_request("pr_compose_detections_multi", kScoreCompose, poses_host, n_poses, width, height, proj, roi, scene_depth_dev, depth_is_i32, tau_mm, scores_host);
-    r.multi = true; r.meshes = meshes; r.n_meshes = n_meshes; r.mesh_index = mesh_index_host;
-    compose_outputs(r, labels_dev_out, depth_dev_out, visible_host, frame_host);
-    return score_run(r);
+    return compose_detections(score_request("pr_compose_detections_multi", kScoreCompose, MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, roi,
+                              scene_depth_dev, depth_is_i32, tau_mm, scores_host), labels_dev_out, depth_dev_out, visible_host, frame_host);
 }
 
 int pr_pose_vsd(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *est_host, uint32_t n_est, const pr_mat4 *gt_host, uint32_t n_gt, uint32_t width,
@@ -1692,8 +1668,8 @@ int pr_pose_vsd(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *est_h
     return vsd_core(src, pairs.data(), nullptr, n_est, width, height, proj, scene_depth_dev, depth_is_i32 != 0, pm, out_host);
 }
 
-// A mixed batch: both poses of pair i carry mesh_index_host[i], so the stable grouping keeps them adjacent -- the grouped batch is interleaved pairs
-// again, pair j of it the caller's pair order[2 j] / 2.  Records into a temporary: nothing reaches out_host unless the call succeeded.
+// A mixed batch: both poses of pair i carry mesh_index_host[i], so the stable grouping keeps them adjacent -- the batch of 2 n_est renders is interleaved
+// pairs again, pair j of it the caller's pair caller(2 j) / 2.  Records into a temporary: nothing reaches out_host unless the call succeeded.
 int pr_pose_vsd_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *est_host, uint32_t n_est,
                       const pr_mat4 *gt_host, uint32_t n_gt, uint32_t width, uint32_t height, const pr_mat4 *proj, const void *scene_depth_dev,
                       int depth_is_i32, const float K[9], float delta_mm, const float *taus_mm, uint32_t n_taus, pr_vsd_counts *out_host)
@@ -1706,114 +1682,34 @@ int pr_pose_vsd_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32
         if (n_meshes && mesh_index_host[i] >= n_meshes) { set_error("pr_pose_vsd_multi: mesh_index[%u] = %u, but there are %u meshes", i, mesh_index_host[i], n_meshes); return PR_ERR_INVALID; }
         index2[2 * (size_t)i] = index2[2 * (size_t)i + 1] = mesh_index_host[i];
     }
-    MeshPlan pl;
-    PR_TRY(plan_meshes("pr_pose_vsd_multi", meshes, n_meshes, mesh_index_host ? index2.data() : nullptr, 2 * (size_t)n_est, pl));
+    const std::vector<pr_mat4> pairs = interleaved_pairs(est_host, gt_host, n_est);
+    Batch b;
+    PR_TRY(b.make("pr_pose_vsd_multi", MeshArg::table(meshes, n_meshes, mesh_index_host ? index2.data() : nullptr), pairs.data(), 2 * (size_t)n_est));
     PR_ENTER();
-    const std::vector<pr_mat4> pairs = interleaved_pairs(est_host, gt_host, n_est), grouped = grouped_poses(pl, pairs.data());
     std::vector<pr_vsd_counts> rec(n_est);
-    PR_TRY(vsd_core(MeshSource{ nullptr, 0, &pl }, grouped.data(), nullptr, n_est, width, height, proj, scene_depth_dev, depth_is_i32 != 0,
-                    vsd_params(K, delta_mm, taus_mm, n_taus), rec.data()));
-    for (uint32_t j = 0; j < n_est; ++j) out_host[pl.order[2 * (size_t)j] / 2] = rec[j];
-    return PR_OK;
-}
-
-int pr_render_span(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, size_t n_poses, size_t width, size_t height,
-                   const pr_mat4 *proj, pr_roi roi, int32_t *near_dev_out, int32_t *far_dev_out)
-{
-    PR_ENTER();
-    const auto [rw, rh] = image_extent(roi, width, height);
-    if (near_dev_out) note_write(near_dev_out, sizeof(int32_t) * n_poses * rw * rh);
-    if (far_dev_out) note_write(far_dev_out, sizeof(int32_t) * n_poses * rw * rh);
-    PR_TRY(render_frames("pr_render_span", FrameSource{ tris_dev, n_tris }, poses_host, n_poses, width, height, proj, roi, near_dev_out, far_dev_out, true, true));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    drain_spans();
+    PR_TRY(vsd_core(b.src, b.poses, nullptr, n_est, width, height, proj, scene_depth_dev, depth_is_i32 != 0, vsd_params(K, delta_mm, taus_mm, n_taus), rec.data()));
+    for (uint32_t j = 0; j < n_est; ++j) out_host[b.caller(2 * (size_t)j) / 2] = rec[j];
     return PR_OK;
 }
 
 int pr_pose_penetration(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                         const pr_mat4 *proj, int32_t slack_mm, pr_pair_solid *pairs_host)
 {
-    PR_TRY(penetration_args_ok("pr_pose_penetration", false, tris_dev, n_tris, poses_host, n_poses, width, height, proj, slack_mm, pairs_host));   // before any device use
-    if (n_poses == 0) return PR_OK;
-    PR_ENTER();
-    return solid_core(MeshSource{ tris_dev, n_tris, nullptr }, poses_host, n_poses, width, height, proj, slack_mm, pairs_host);
+    return pose_penetration("pr_pose_penetration", MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, slack_mm, pairs_host);
 }
 
-// A mixed batch: grouped by mesh, the records into a temporary (nothing reaches pairs_host unless the call succeeded), rows and columns back
-// to the caller's order as pr_score_overlap_multi's matrix
 int pr_pose_penetration_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
                               uint32_t width, uint32_t height, const pr_mat4 *proj, int32_t slack_mm, pr_pair_solid *pairs_host)
 {
-    PR_TRY(penetration_args_ok("pr_pose_penetration_multi", true, nullptr, 0, poses_host, n_poses, width, height, proj, slack_mm, pairs_host));
-    if (n_poses == 0) return PR_OK;
-    MeshPlan pl;
-    PR_TRY(plan_meshes("pr_pose_penetration_multi", meshes, n_meshes, mesh_index_host, n_poses, pl));
-    PR_ENTER();
-    const uint32_t P = n_poses;
-    const std::vector<pr_mat4> grouped = grouped_poses(pl, poses_host);
-    std::vector<pr_pair_solid> rec((size_t)P * P);
-    PR_TRY(solid_core(MeshSource{ nullptr, 0, &pl }, grouped.data(), P, width, height, proj, slack_mm, rec.data()));
-    for (uint32_t a = 0; a < P; ++a)
-        for (uint32_t b = 0; b < P; ++b) pairs_host[(size_t)pl.order[a] * P + pl.order[b]] = rec[(size_t)a * P + b];
-    return PR_OK;
-}
-
-// pr_pose_information and its _multi form (multi: the mesh table instead of tris_dev, a centre and a radius per mesh): every check before any device
-// is touched, the centres in the camera frame on the host, refine_core with the information pass on the batch in its plan's order into temporaries,
-// and the records back to the caller's order.
-static int pose_information_impl(const char *fn, bool multi, const pr_triangle *tris_dev, size_t n_tris, const pr_mesh_ref *meshes, uint32_t n_meshes,
-                                 const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height, const pr_mat4 *proj,
-                                 const float K[9], int scene_kind, const void *scene, pr_roi roi, const pr_robust *robust, const float *centers_model,
-                                 const float *radii, pr_pose_info *info_host, pr_pose_eig *eig_host, uint32_t *cloud_sizes_host)
-{
-    if (robust) PR_TRY(robust_desc_ok(fn, robust));
-    RefineJob job;
-    PR_TRY(make_job(fn, tris_dev, n_tris, width, height, proj, K, scene_kind, scene, pr_criteria{ 0.0f, 0.0f, 0 }, roi, nullptr, job));
-    if (!centers_model || !radii || (n_poses && (!poses_host || !info_host))) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
-    MeshPlan pl;
-    if (multi) {
-        PR_TRY(plan_meshes(fn, meshes, n_meshes, mesh_index_host, n_poses, pl));
-        job.plan = &pl;
-    }
-    PR_TRY(info_center_radius_ok(fn, centers_model, radii, multi ? n_meshes : 1u));
-    // c_i = pose_i applied to the mesh's centre, in float64, millimetres to metres as the cloud extraction converts them, rounded to float32
-    std::vector<float> centers(3 * (size_t)n_poses), rad(n_poses);
-    for (uint32_t j = 0; j < n_poses; ++j) {
-        const uint32_t o = multi ? pl.order[j] : j, m = multi ? mesh_index_host[o] : 0u;
-        const float *M = poses_host[o].m, *cm = centers_model + 3 * (size_t)m;
-        for (int a = 0; a < 3; ++a) {
-            const double v = (((double)M[4 * a] * (double)cm[0] + (double)M[4 * a + 1] * (double)cm[1]) + (double)M[4 * a + 2] * (double)cm[2]) + (double)M[4 * a + 3];
-            centers[3 * (size_t)j + a] = (float)(v / 1000.0);
-        }
-        rad[j] = radii[m];
-    }
-    PR_TRY(info_center_radius_ok(fn, centers.data(), rad.data(), n_poses));      // (a pose with a non-finite entry)
-    if (n_poses == 0) return PR_OK;
-    PR_ENTER();
-    // the scene caches are shared with the asynchronous slots: a batch still running on one finishes first (it stays pending: pr_refine_wait collects it)
-    for (Slot &o : g->slots) if (o.pending && !o.delivered && !o.worker_job && o.done) HIP_TRY(hipEventSynchronize(o.done));
-    std::vector<pr_mat4> grouped;
-    if (multi) { grouped = grouped_poses(pl, poses_host); poses_host = grouped.data(); }
-    std::vector<pr_pose_info> info(n_poses);
-    std::vector<pr_pose_eig> eig(eig_host ? n_poses : 0);
-    std::vector<uint32_t> sizes(n_poses);
-    const InfoPlan ip{ robust ? *robust : pr_robust{ PR_ROBUST_NONE, 0.0f, 0.0f, 0 }, centers.data(), rad.data(), info.data(), eig_host ? eig.data() : nullptr };
-    PR_TRY(refine_core(job, poses_host, n_poses, nullptr, sizes.data(), nullptr, &ip));
-    for (uint32_t j = 0; j < n_poses; ++j) {
-        const uint32_t o = multi ? pl.order[j] : j;
-        info_host[o] = info[j];
-        if (eig_host) eig_host[o] = eig[j];
-        if (cloud_sizes_host) cloud_sizes_host[o] = sizes[j];
-    }
-    return PR_OK;
+    return pose_penetration("pr_pose_penetration_multi", MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, slack_mm, pairs_host);
 }
 
 int pr_pose_information(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,
                         const pr_mat4 *proj, const float K[9], int scene_kind, const void *scene, pr_roi roi, const pr_robust *robust_or_null,
                         const float *center_model, float radius, pr_pose_info *info_host, pr_pose_eig *eig_host_or_null, uint32_t *cloud_sizes_host_or_null)
 {
-    return pose_information_impl("pr_pose_information", false, tris_dev, n_tris, nullptr, 0, nullptr, poses_host, n_poses, width, height, proj, K, scene_kind, scene,
-                                 roi, robust_or_null, center_model, &radius, info_host, eig_host_or_null, cloud_sizes_host_or_null);
+    return pose_information_impl("pr_pose_information", MeshArg::one(tris_dev, n_tris), poses_host, n_poses, width, height, proj, K, scene_kind, scene, roi, robust_or_null, center_model, &radius,
+                                 info_host, eig_host_or_null, cloud_sizes_host_or_null);
 }
 
 int pr_pose_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host, const pr_mat4 *poses_host, uint32_t n_poses,
@@ -1821,8 +1717,8 @@ int pr_pose_information_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, cons
                               const pr_robust *robust_or_null, const float *centers_model, const float *radii, pr_pose_info *info_host,
                               pr_pose_eig *eig_host_or_null, uint32_t *cloud_sizes_host_or_null)
 {
-    return pose_information_impl("pr_pose_information_multi", true, nullptr, 0, meshes, n_meshes, mesh_index_host, poses_host, n_poses, width, height, proj, K,
-                                 scene_kind, scene, roi, robust_or_null, centers_model, radii, info_host, eig_host_or_null, cloud_sizes_host_or_null);
+    return pose_information_impl("pr_pose_information_multi", MeshArg::table(meshes, n_meshes, mesh_index_host), poses_host, n_poses, width, height, proj, K, scene_kind, scene, roi, robust_or_null,
+                                 centers_model, radii, info_host, eig_host_or_null, cloud_sizes_host_or_null);
 }
 
 int pr_refine_batch_roi(const pr_triangle *tris_dev, size_t n_tris, const pr_mat4 *poses_host, uint32_t n_poses, uint32_t width, uint32_t height,

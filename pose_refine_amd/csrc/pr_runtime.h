@@ -1,6 +1,6 @@
 // pr_runtime.h -- the host-side runtime behind the C ABI, shared by its translation units: contexts and their registry, workspaces, the write
 // log of caller-owned memory, options, slots, profiling spans, and what every route of the fused batch path shares: its job record (RefineJob,
-// make_job), the layouts of a slot's pinned blocks, the pose-group lanes and the device-solve iteration loop.  pr_context.cpp (contexts, memory, options, profiling entry points),
+// make_job), the mesh argument and the grouped batch of the calls that take a mesh table (MeshArg, Batch), the layouts of a slot's pinned blocks, the pose-group lanes and the device-solve iteration loop.  pr_context.cpp (contexts, memory, options, profiling entry points),
 // pr_scene.cpp (scene caches and device-side scene preparation), pr_icp.cpp (the batched ICP driver: device and host solve loops),
 // pr_refine.cpp (render, cloud, the fused batch path with its two asynchronous slots and helper threads), pr_comm.cpp (RCCL gather).
 #pragma once
@@ -258,10 +258,97 @@ inline int robust_table_ok(const char *fn, const pr_robust *robust, uint32_t n_r
     for (uint32_t l = 0; l < n_robust; ++l) PR_TRY(robust_desc_ok(fn, robust + l));
     return PR_OK;
 }
-struct MeshPlan;                     // the hypotheses of a mixed batch grouped by mesh (pr_refine.cpp)
+// ---- mixed batches (pr_*_multi): the hypotheses of several meshes in one call ---------------------------------------------------
+// The hypotheses grouped by mesh: a stable counting sort of the caller's indices.  Every mesh that has hypotheses is one group (in mesh
+// order); the batch runs in group order and its outputs go back to the caller's order.  Results do not depend on how a batch is composed
+// (each hypothesis equals its single-pose run), so the grouped batch gives every hypothesis what the single-mesh call gives it.
+struct MeshPlan {
+    std::vector<uint32_t> order;          // position in the grouped batch -> the caller's index
+    std::vector<uint32_t> box;            // position -> its group (= which of the groups' model boxes it uses)
+    std::vector<pr_mesh_ref> mesh;        // group -> mesh
+    std::vector<uint32_t> start;          // group -> first position; one more entry: the batch size
+};
+// No HIP call in here (nor in MeshArg and Batch below): tools/job_sanitize.cpp runs them under ASan / UBSan.
+inline int plan_meshes(const char *fn, const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index, size_t P, MeshPlan &pl)
+{
+    if (!meshes || n_meshes == 0 || !mesh_index) { set_error("%s: bad arguments (mesh table or mesh index missing)", fn); return PR_ERR_INVALID; }
+    for (uint32_t m = 0; m < n_meshes; ++m)
+        if (!meshes[m].tris_dev && meshes[m].n_tris > 0) { set_error("%s: mesh %u has %zu triangles and no array", fn, m, meshes[m].n_tris); return PR_ERR_INVALID; }
+    std::vector<uint32_t> first(n_meshes + 1, 0);
+    for (size_t i = 0; i < P; ++i) {
+        if (mesh_index[i] >= n_meshes) { set_error("%s: mesh_index[%zu] = %u, but there are %u meshes", fn, i, mesh_index[i], n_meshes); return PR_ERR_INVALID; }
+        first[mesh_index[i] + 1]++;
+    }
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        if (first[m + 1] > 0) { pl.mesh.push_back(meshes[m]); pl.start.push_back(first[m]); }
+        first[m + 1] += first[m];
+    }
+    pl.start.push_back((uint32_t)P);
+    std::vector<uint32_t> group_of(n_meshes, 0);
+    for (uint32_t k = 0, m = 0; m < n_meshes; ++m) if (first[m + 1] > first[m]) group_of[m] = k++;
+    pl.order.resize(P); pl.box.resize(P);
+    for (size_t i = 0; i < P; ++i) { const uint32_t j = first[mesh_index[i]]++; pl.order[j] = (uint32_t)i; pl.box[j] = group_of[mesh_index[i]]; }
+    return PR_OK;
+}
+// the mesh as the C arguments name it: one triangle buffer for every hypothesis, or a mesh table and every hypothesis' index into it
+struct MeshArg {
+    const pr_triangle *tris = nullptr; size_t n_tris = 0;
+    bool multi = false; const pr_mesh_ref *meshes = nullptr; uint32_t n_meshes = 0; const uint32_t *mesh_index = nullptr;
+    static MeshArg one(const pr_triangle *tris_dev, size_t n_tris) { MeshArg a; a.tris = tris_dev; a.n_tris = n_tris; return a; }
+    static MeshArg table(const pr_mesh_ref *meshes, uint32_t n_meshes, const uint32_t *mesh_index_host) { MeshArg a; a.multi = true; a.meshes = meshes; a.n_meshes = n_meshes; a.mesh_index = mesh_index_host; return a; }
+};
+// what model_boxes and render_chunk (pr_refine.cpp) draw: one mesh for every hypothesis, or a mixed batch in its plan's order
+struct MeshSource { const pr_triangle *tris = nullptr; size_t n_tris = 0; const MeshPlan *plan = nullptr; };
+// What every core runs on: the hypotheses in RUN order -- a mesh table's grouped by mesh, one mesh's as the caller has them -- and the way between that
+// order and the caller's.  One mesh has no plan (it is not a one-group plan: its path keeps the single-mesh launches) and all four operations
+// are the identity for it: gather hands the caller's pointer back, temp the caller's array, and a scatter of an array onto itself copies nothing.
+struct Batch {
+    bool mixed = false; MeshPlan pl;                             // a mesh table: the plan
+    MeshSource src;                                              // as model_boxes and render_chunk take it
+    size_t P = 0;
+    const pr_mat4 *poses = nullptr;                              // in run order: the grouped copy, or the caller's pointer
+    std::vector<pr_mat4> grouped;
+    // a mesh table's checks and the grouping -- the one caller of plan_meshes -- and the poses in run order
+    int make(const char *fn, const MeshArg &mesh, const pr_mat4 *poses_host, size_t n)
+    {
+        mixed = mesh.multi; P = n; src = MeshSource{ mesh.tris, mesh.n_tris, nullptr };
+        if (mixed) { PR_TRY(plan_meshes(fn, mesh.meshes, mesh.n_meshes, mesh.mesh_index, n, pl)); src.plan = &pl; }
+        poses = gather(poses_host, grouped);
+        return PR_OK;
+    }
+    uint32_t caller(size_t j) const { return mixed ? pl.order[j] : (uint32_t)j; }          // position -> the caller's index ...
+    const uint32_t *order() const { return mixed ? pl.order.data() : nullptr; }            // ... as a table for the device (null: the identity)
+    std::vector<uint32_t> inverse() const { std::vector<uint32_t> where(P); for (size_t j = 0; j < P; ++j) where[caller(j)] = (uint32_t)j; return where; }   // the caller's index -> position
+    // a per-hypothesis input in the caller's order -> run order (`store` keeps the copy)
+    template <class T> const T *gather(const T *in, std::vector<T> &store) const
+    {
+        if (!mixed) return in;
+        store.resize(P);
+        for (size_t j = 0; j < P; ++j) store[j] = in[caller(j)];
+        return store.data();
+    }
+    // where `count` records of a core land: a mixed batch's in a temporary, scattered once the call has succeeded (nothing reaches a caller's
+    // array before); one mesh's straight in the caller's array
+    template <class T> T *temp(std::vector<T> &store, size_t count, T *out) const { if (!mixed) return out; store.resize(count); return store.data(); }
+    // per-hypothesis records back to the caller's order: `rows` blocks of P (the pyramid's [level][hypothesis]); out: null = not wanted
+    template <class T> void scatter(const T *run, T *out, size_t rows = 1) const
+    {
+        if (!out || out == run) return;
+        for (size_t r = 0; r < rows; ++r)
+            for (size_t j = 0; j < P; ++j) out[r * P + caller(j)] = run[r * P + j];
+    }
+    // a P x P matrix back: rows and columns
+    template <class T> void scatter_matrix(const T *run, T *out) const
+    {
+        if (!out || out == run) return;
+        for (size_t a = 0; a < P; ++a)
+            for (size_t b = 0; b < P; ++b) out[(size_t)caller(a) * P + caller(b)] = run[a * P + b];
+    }
+    Batch() = default;
+    Batch(const Batch &) = delete;                               // (src.plan and poses point into pl and grouped)
+};
 struct RefineJob {
-    const pr_triangle *tris = nullptr; size_t n_tris = 0;        // one mesh for every hypothesis ...
-    const MeshPlan *plan = nullptr;                              // ... or a mixed batch in its plan's order (synchronous calls only: the plan lives on the entry point's stack)
+    MeshSource mesh;                                             // one mesh, or a mixed batch in its plan's order (Batch::src; synchronous calls only: the batch lives on the entry point's stack)
     uint32_t W = 0, H = 0; pr_mat4 proj{}; float K[9] = { 0 };
     int scene_kind = 0; pr_scene_proj_crop sp{}; pr_scene_nn sn{}; pr_scene_grid sg{}; pr_criteria crit{}; pr_roi roi{ 0, 0, 0, 0 };
     pr_result *results_dev = nullptr;
@@ -281,7 +368,7 @@ inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, 
     if (!frame_size_ok(W, H) || !roi_ok(roi, W, H)) return PR_ERR_INVALID;
     if (crit.max_iteration < 0) { set_error("max_iteration must be >= 0"); return PR_ERR_INVALID; }
     job = RefineJob();
-    job.tris = tris_dev; job.n_tris = n_tris; job.W = W; job.H = H; job.proj = *proj; std::memcpy(job.K, K, sizeof job.K);
+    job.mesh = MeshSource{ tris_dev, n_tris, nullptr }; job.W = W; job.H = H; job.proj = *proj; std::memcpy(job.K, K, sizeof job.K);
     job.scene_kind = scene_kind; job.crit = crit; job.roi = roi; job.results_dev = results_dev;
     if (scene_kind == PR_SCENE_NN) job.sn = *static_cast<const pr_scene_nn *>(scene);
     else if (scene_kind == PR_SCENE_GRID) job.sg = *static_cast<const pr_scene_grid *>(scene);
@@ -290,13 +377,12 @@ inline int make_job(const char *fn, const pr_triangle *tris_dev, size_t n_tris, 
     if (robust) for (uint32_t l = 0; l < n_levels; ++l) job.robust[l] = robust[n_robust == 1 ? 0 : l];
     return PR_OK;
 }
-// ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_cover, pr_score_contours, pr_score_normals, pr_compose_detections and their _multi forms) ----
+// ---- the description of one scoring call (pr_score_poses, pr_score_overlap, pr_score_cover, pr_score_contours, pr_score_normals, pr_compose_detections and their _multi forms; pr_contour_information[_multi]) ----
 // What the caller asked for, as the entry point got it; score_run (pr_refine.cpp) takes it from there.  Every member is set by the entry point.
 enum ScoreKind { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose, kScoreCover, kScoreContourFit };
 struct ScoreRequest {
     const char *fn; ScoreKind kind;                              // the entry point's name (for messages) and what it returns besides the scores
-    const pr_triangle *tris; size_t n_tris;                      // one mesh for every hypothesis ...
-    bool multi; const pr_mesh_ref *meshes; uint32_t n_meshes; const uint32_t *mesh_index;      // ... or (multi) a mesh table and every hypothesis' index into it
+    MeshArg mesh;                                                // one mesh for every hypothesis, or a mesh table and every hypothesis' index into it
     const pr_mat4 *poses; uint32_t P, W, H; const pr_mat4 *proj; pr_roi roi;
     const void *scene; bool scene_i32; int32_t tau;
     pr_pose_score *scores;                                       // host, P records (kScoreContourFit: may be null)
@@ -306,7 +392,7 @@ struct ScoreRequest {
     const uint32_t *nearest; const prk::FitMeta *fit_meta; pr_contour_fit *fit; pr_pose_info *fit_info;      // kScoreContourFit (with jump and K): device nearest-edge map and P host centres (in the order of poses) in, P + P host records out
     uint16_t *labels_dev; int32_t *depth_dev; pr_pose_visible *visible; pr_frame_explained *frame;     // kScoreCompose: two optional device images, host records
     const uint32_t *cov_order; prk::CoverRule cov_rule; pr_pose_cover *cover; pr_cover_frame *cover_frame; uint32_t *selected, *n_selected;      // kScoreCover: the walk in (cov_rule.n_order indices), P + 1 host records and the selected list out
-    const MeshPlan *plan; const uint32_t *order;                 // score_run's, null from the entry point: the grouped batch (position -> caller's index)
+    const Batch *batch;                                          // score_run's, null from the entry point: the batch score_core runs on (poses: in its order)
 };
 // pr_score_overlap's own condition
 inline int overlap_args_ok(const char *fn, uint32_t P, const uint32_t *overlap_host)
@@ -352,7 +438,7 @@ inline int fit_intrinsics_ok(const char *fn, const float *K)
     if (K[0] == 0.0f || K[4] == 0.0f) { set_error("%s: K[0] and K[4] must not be 0", fn); return PR_ERR_INVALID; }
     return PR_OK;
 }
-// Every check of a request that needs no device, in one order for all fourteen entry points (the mesh table of a mixed batch: plan_meshes).  No HIP
+// Every check of a request that needs no device, in one order for all fourteen entry points (the mesh table of a mixed batch: Batch::make).  No HIP
 // call in here: tools/job_sanitize.cpp runs it under ASan / UBSan.  A request without hypotheses needs no arrays.
 inline int score_request_ok(const ScoreRequest &r)
 {
@@ -361,7 +447,7 @@ inline int score_request_ok(const ScoreRequest &r)
     if (r.kind == kScoreCompose) PR_TRY(compose_args_ok(fn, r.P));
     if (r.kind == kScoreCover) PR_TRY(cover_args_ok(r));
     if (r.tau < 0) { set_error("%s: tau_mm must be >= 0 (got %d)", fn, (int)r.tau); return PR_ERR_INVALID; }
-    if (!r.proj || r.W == 0 || r.H == 0 || (r.P && (!r.poses || !r.scene || (!r.scores && r.kind != kScoreContourFit) || (!r.multi && !r.tris && r.n_tris > 0)))) {
+    if (!r.proj || r.W == 0 || r.H == 0 || (r.P && (!r.poses || !r.scene || (!r.scores && r.kind != kScoreContourFit) || (!r.mesh.multi && !r.mesh.tris && r.mesh.n_tris > 0)))) {
         set_error("%s: bad arguments", fn); return PR_ERR_INVALID;
     }
     if (!frame_size_ok(r.W, r.H)) return PR_ERR_INVALID;
@@ -953,6 +1039,21 @@ inline int info_scene_ok(const char *fn, int scene_kind, const void *scene)
     if (!scene) { set_error("%s: bad arguments (scene is null)", fn); return PR_ERR_INVALID; }
     if (scene_kind == PR_SCENE_GRID) PR_TRY(grid_desc_ok(fn, static_cast<const pr_scene_grid *>(scene), /*built=*/true));
     return PR_OK;
+}
+// c_i = pose_i applied to its mesh's centre, in float64, millimetres to metres as the cloud extraction converts them, rounded to float32; rad_i = its
+// mesh's radius.  mesh_of: every pose's index into centers_model / radii (null: one mesh).  pr_pose_information and pr_contour_information both
+// call THIS: combine_information adds their matrices, so their centres must be the same bits.
+inline void camera_centers(const pr_mat4 *poses, const uint32_t *mesh_of, uint32_t P, const float *centers_model, const float *radii, float *centers, float *rad)
+{
+    for (uint32_t j = 0; j < P; ++j) {
+        const uint32_t m = mesh_of ? mesh_of[j] : 0u;
+        const float *M = poses[j].m, *cm = centers_model + 3 * (size_t)m;
+        for (int a = 0; a < 3; ++a) {
+            const double v = (((double)M[4 * a] * (double)cm[0] + (double)M[4 * a + 1] * (double)cm[1]) + (double)M[4 * a + 2] * (double)cm[2]) + (double)M[4 * a + 3];
+            centers[3 * (size_t)j + a] = (float)(v / 1000.0);
+        }
+        rad[j] = radii[m];
+    }
 }
 inline int info_center_radius_ok(const char *fn, const float *centers, const float *radii, uint32_t n)
 {

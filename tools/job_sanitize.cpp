@@ -1,6 +1,6 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
 // Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok, render_args_ok and vsd_args_ok with null and
-// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), and pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance).  None of them calls HIP, so nothing of the runtime is linked.
+// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), the mixed-batch layer (plan_meshes on a worked example and on every table it refuses; Batch: gather, scatter, the pyramid's rows, the P x P matrix, the inverse, the one-mesh identity; camera_centers bit for bit against the expression it replaced), and pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance).  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
 namespace prh { void set_error(const char *, ...) {} }
@@ -61,7 +61,7 @@ int main()
         refused(tris, 5, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, r);
     // what must pass, and what the job then holds
     CHECK(make_job("job_sanitize", nullptr, 0, 640, 480, &proj, K, PR_SCENE_PROJ, &sp, crit, none, rdev, job) == PR_OK);      // an empty model has no array
-    CHECK(job.tris == nullptr && job.n_tris == 0 && job.plan == nullptr && job.W == 640 && job.H == 480 && job.results_dev == rdev && job.K[4] == 500.0f);
+    CHECK(job.mesh.tris == nullptr && job.mesh.n_tris == 0 && job.mesh.plan == nullptr && job.W == 640 && job.H == 480 && job.results_dev == rdev && job.K[4] == 500.0f);
     CHECK(job.scene() == &job.sp && job.sp.view.width == 640 && job.sp.tl_x == 0 && job.sp.tl_y == 0);
     CHECK(make_job("job_sanitize", tris, 5, 8192, 2048, &proj, K, PR_SCENE_PROJ_CROP, &sc, pr_criteria{ 1e-5f, 1e-5f, 0 }, pr_roi{ 630, 470, 10, 10 }, nullptr, job) == PR_OK);
     CHECK(job.scene() == &job.sp && job.sp.tl_x == 7 && job.sp.tl_y == 9 && job.roi.x == 630 && job.crit.max_iteration == 0 && job.results_dev == nullptr);
@@ -110,9 +110,8 @@ int main()
     for (ScoreKind kind : { kScorePoses, kScoreOverlap, kScoreContours, kScoreNormals, kScoreCompose })
         for (bool multi : { false, true }) {
             ScoreRequest ok{};
-            ok.fn = "job_sanitize"; ok.kind = kind; ok.multi = multi; ok.poses = poses; ok.P = 70; ok.W = 640; ok.H = 480; ok.proj = &proj; ok.roi = pr_roi{ 630, 470, 10, 10 };
+            ok.fn = "job_sanitize"; ok.kind = kind; ok.mesh = multi ? MeshArg::table(table, 2, index) : MeshArg::one(tris, 5); ok.poses = poses; ok.P = 70; ok.W = 640; ok.H = 480; ok.proj = &proj; ok.roi = pr_roi{ 630, 470, 10, 10 };
             ok.scene = dev; ok.scene_i32 = true; ok.tau = 0; ok.scores = scores;
-            if (multi) { ok.meshes = table; ok.n_meshes = 2; ok.mesh_index = index; } else { ok.tris = tris; ok.n_tris = 5; }
             if (kind == kScoreOverlap) ok.overlap = matrix;
             if (kind == kScoreContours) { ok.jump = 0; ok.edge_dist = edges; ok.contours = contours; }       // (no matrix: it is optional here)
             if (kind == kScoreNormals) { ok.K = K; ok.step = PR_NORMAL_MAX_STEP; ok.jump = 0; ok.cos_min = 1.0f; ok.normals = normals; }       // (no matrix: it is optional here)
@@ -132,7 +131,7 @@ int main()
             refused_with([](ScoreRequest &r) { r.W = 8193; r.H = 1; });
             refused_with([](ScoreRequest &r) { r.W = 0xffffffffu; r.H = 0xffffffffu; });
             refused_with([](ScoreRequest &r) { r.W = 0; });
-            if (!multi) refused_with([](ScoreRequest &r) { r.tris = nullptr; });
+            if (!multi) refused_with([](ScoreRequest &r) { r.mesh.tris = nullptr; });
             if (kind == kScoreOverlap) refused_with([](ScoreRequest &r) { r.overlap = nullptr; });
             if (kind == kScoreOverlap) refused_with([](ScoreRequest &r) { r.P = PR_OVERLAP_MAX_POSES + 1; });
             if (kind == kScoreContours) {
@@ -382,6 +381,114 @@ int main()
         CHECK(info_covariance(&pi, &pe, 2.0, 1.0e-6, cov, &rank, &s2) == PR_OK && rank == 3 && s2 == 4.0);
         CHECK(cov[0] == 0.0 && cov[6] == 0.0 && cov[11] == 0.0 && cov[15] == 4.0 * (1.0 / 1.0e-3) && cov[18] == 4.0 * (1.0 / 0.5) && cov[20] == 4.0 && cov[1] == 0.0 && cov[19] == 0.0);
         CHECK(info_covariance(&pi, &pe, 0.0, 0.0, cov, &rank, &s2) == PR_OK && rank == 4 && s2 == (1.0e-4 / 100.0) * 100.0 / 94.0);
+    }
+    // mixed batches.  plan_meshes: 3 meshes, 7 hypotheses, mesh 1 unused -- the groups in mesh order, the order stable within a group
+    const pr_mesh_ref m3[3] = { { tris, 5 }, { nullptr, 0 }, { reinterpret_cast<const pr_triangle *>(uintptr_t(0x11000)), 9 } };
+    const uint32_t idx7[7] = { 2, 0, 2, 0, 2, 2, 0 }, order7[7] = { 1, 3, 6, 0, 2, 4, 5 };
+    {
+        MeshPlan pl;
+        CHECK(plan_meshes("job_sanitize", m3, 3, idx7, 7, pl) == PR_OK);
+        CHECK(pl.mesh.size() == 2 && pl.mesh[0].tris_dev == m3[0].tris_dev && pl.mesh[0].n_tris == 5 && pl.mesh[1].tris_dev == m3[2].tris_dev && pl.mesh[1].n_tris == 9);
+        CHECK(pl.start == (std::vector<uint32_t>{ 0, 3, 7 }));
+        CHECK(pl.order == std::vector<uint32_t>(order7, order7 + 7));
+        CHECK(pl.box == (std::vector<uint32_t>{ 0, 0, 0, 1, 1, 1, 1 }));
+        MeshPlan none_planned;                                                                             // no hypotheses, a valid table
+        CHECK(plan_meshes("job_sanitize", m3, 3, idx7, 0, none_planned) == PR_OK && none_planned.start == std::vector<uint32_t>{ 0 } && none_planned.order.empty() && none_planned.mesh.empty());
+        auto refused_plan = [&](const pr_mesh_ref *t, uint32_t n, const uint32_t *ix, size_t P) { MeshPlan p; CHECK(plan_meshes("job_sanitize", t, n, ix, P, p) == PR_ERR_INVALID); };
+        refused_plan(nullptr, 3, idx7, 7);
+        refused_plan(m3, 0, idx7, 7);
+        refused_plan(m3, 3, nullptr, 7);
+        { const pr_mesh_ref bad[3] = { m3[0], { nullptr, 4 }, m3[2] }; refused_plan(bad, 3, idx7, 7); }        // triangles and no array
+        { const uint32_t ix[7] = { 2, 0, 2, 3, 2, 2, 0 }; refused_plan(m3, 3, ix, 7); }                      // an index equal to n_meshes
+        { const uint32_t ix[7] = { 2, 0, 2, 0, 2, 2, 0xffffffffu }; refused_plan(m3, 3, ix, 7); }
+    }
+    // Batch on that plan, with tagged records: gather and scatter are inverse, the pyramid's rows land at l * P + caller, the matrix goes back by rows
+    // and columns, the inverse is the cover walk's; one mesh: every operation the identity, nothing copied
+    {
+        struct Rec { uint32_t tag; };
+        std::vector<pr_mat4> poses7(7);
+        for (uint32_t i = 0; i < 7; ++i) { identity16(poses7[i].m); poses7[i].m[3] = (float)i; }
+        Batch b;
+        CHECK(b.make("job_sanitize", MeshArg::table(m3, 3, idx7), poses7.data(), 7) == PR_OK);
+        CHECK(b.mixed && b.P == 7 && b.src.plan == &b.pl && b.src.tris == nullptr && b.src.n_tris == 0 && b.order() == b.pl.order.data() && b.poses == b.grouped.data());
+        for (uint32_t j = 0; j < 7; ++j) CHECK(b.caller(j) == order7[j] && b.poses[j].m[3] == (float)order7[j]);
+        std::vector<Rec> x(7), store, back(7, Rec{ 99 });
+        for (uint32_t i = 0; i < 7; ++i) x[i].tag = i;
+        const Rec *run = b.gather(x.data(), store);
+        CHECK(run == store.data() && run != x.data());
+        for (uint32_t j = 0; j < 7; ++j) CHECK(run[j].tag == order7[j]);
+        b.scatter(run, back.data());
+        for (uint32_t i = 0; i < 7; ++i) CHECK(back[i].tag == x[i].tag);                                   // scatter(gather(x)) == x
+        b.scatter(run, static_cast<Rec *>(nullptr));                                                        // an output nobody wants
+        std::vector<Rec> lv(3 * 7), lv_out(3 * 7, Rec{ 99 });
+        for (uint32_t l = 0; l < 3; ++l) for (uint32_t j = 0; j < 7; ++j) lv[l * 7 + j].tag = 100 * l + j;
+        b.scatter(lv.data(), lv_out.data(), 3);
+        for (uint32_t l = 0; l < 3; ++l) for (uint32_t j = 0; j < 7; ++j) CHECK(lv_out[l * 7 + order7[j]].tag == 100 * l + j);
+        std::vector<Rec> mat(49), mat_out(49, Rec{ 99 });
+        for (uint32_t k = 0; k < 49; ++k) mat[k].tag = k;
+        b.scatter_matrix(mat.data(), mat_out.data());
+        for (uint32_t a = 0; a < 7; ++a) for (uint32_t c = 0; c < 7; ++c) CHECK(mat_out[order7[a] * 7 + order7[c]].tag == a * 7 + c);
+        const std::vector<uint32_t> where = b.inverse();
+        CHECK(where.size() == 7);
+        for (uint32_t j = 0; j < 7; ++j) CHECK(where[order7[j]] == j);
+        std::vector<Rec> tmp;
+        CHECK(b.temp(tmp, 49, back.data()) == tmp.data() && tmp.size() == 49);
+        Batch bad;                                                                                          // a refused table leaves the error
+        CHECK(bad.make("job_sanitize", MeshArg::table(m3, 0, idx7), poses7.data(), 7) == PR_ERR_INVALID);
+        Batch one;
+        CHECK(one.make("job_sanitize", MeshArg::one(tris, 5), poses7.data(), 7) == PR_OK);
+        CHECK(!one.mixed && one.poses == poses7.data() && one.grouped.empty() && one.src.tris == tris && one.src.n_tris == 5 && one.src.plan == nullptr && one.order() == nullptr);
+        for (uint32_t j = 0; j < 7; ++j) CHECK(one.caller(j) == j && one.inverse()[j] == j);
+        std::vector<Rec> unused;
+        CHECK(one.gather(x.data(), unused) == x.data() && unused.empty());                                  // the caller's pointer, no copy
+        CHECK(one.temp(unused, 49, mat.data()) == mat.data() && unused.empty());
+        one.scatter(x.data(), x.data()); one.scatter_matrix(mat.data(), mat.data());                        // onto themselves: nothing moves
+        for (uint32_t i = 0; i < 7; ++i) CHECK(x[i].tag == i);
+        for (uint32_t k = 0; k < 49; ++k) CHECK(mat[k].tag == k);
+        one.scatter(lv.data(), lv_out.data(), 3);                                                           // another array: a plain copy
+        for (uint32_t k = 0; k < 21; ++k) CHECK(lv_out[k].tag == lv[k].tag);
+    }
+    // camera_centers against the expression as pr_pose_information and pr_contour_information each wrote it out before they shared it, bit for bit
+    {
+        auto reference = [](const float *M, const float *cm, int a) {
+            const double v = (((double)M[4 * a] * (double)cm[0] + (double)M[4 * a + 1] * (double)cm[1]) + (double)M[4 * a + 2] * (double)cm[2]) + (double)M[4 * a + 3];
+            return (float)(v / 1000.0);
+        };
+        auto same_bits = [](float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; };
+        std::vector<pr_mat4> ps(3);
+        for (uint32_t i = 0; i < 3; ++i) {                                                                  // rotations about (1, 2, 3) by 0.7 + i rad, translations in mm
+            const double th = 0.7 + i, n = std::sqrt(14.0), u[3] = { 1 / n, 2 / n, 3 / n }, c = std::cos(th), s = std::sin(th);
+            const double R[9] = { c + u[0] * u[0] * (1 - c), u[0] * u[1] * (1 - c) - u[2] * s, u[0] * u[2] * (1 - c) + u[1] * s,
+                                  u[1] * u[0] * (1 - c) + u[2] * s, c + u[1] * u[1] * (1 - c), u[1] * u[2] * (1 - c) - u[0] * s,
+                                  u[2] * u[0] * (1 - c) - u[1] * s, u[2] * u[1] * (1 - c) + u[0] * s, c + u[2] * u[2] * (1 - c) };
+            identity16(ps[i].m);
+            for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) ps[i].m[4 * r + k] = (float)R[3 * r + k]; ps[i].m[4 * r + 3] = 31.7f * (r + 1) - 100.3f * i + 801.9f * (r == 2); }
+        }
+        const float cm2[6] = { 12.34f, -56.78f, 9.1011f, -3.3f, 44.125f, 70.7f }, rr2[2] = { 0.05f, 0.125f };
+        float c[9], rad[3];
+        camera_centers(ps.data(), nullptr, 1, cm2, rr2, c, rad);                                             // one pose, one mesh
+        for (int a = 0; a < 3; ++a) CHECK(same_bits(c[a], reference(ps[0].m, cm2, a)) && c[a] != 0.0f);
+        CHECK(rad[0] == rr2[0]);
+        const uint32_t ix[3] = { 1, 0, 1 };
+        const pr_mesh_ref m2[2] = { m3[0], m3[2] };
+        camera_centers(ps.data(), ix, 3, cm2, rr2, c, rad);                                                  // the caller's order (pr_contour_information_multi)
+        for (uint32_t j = 0; j < 3; ++j) {
+            for (int a = 0; a < 3; ++a) CHECK(same_bits(c[3 * j + a], reference(ps[j].m, cm2 + 3 * ix[j], a)));
+            CHECK(rad[j] == rr2[ix[j]]);
+        }
+        CHECK(info_center_radius_ok("job_sanitize", c, rad, 3) == PR_OK);
+        Batch b;                                                                                            // the plan's order (pr_pose_information_multi)
+        CHECK(b.make("job_sanitize", MeshArg::table(m2, 2, ix), ps.data(), 3) == PR_OK && b.pl.order == (std::vector<uint32_t>{ 1, 0, 2 }));
+        std::vector<uint32_t> mesh_of;
+        camera_centers(b.poses, b.gather(ix, mesh_of), 3, cm2, rr2, c, rad);
+        for (uint32_t j = 0; j < 3; ++j) {
+            const uint32_t o = b.pl.order[j], m = ix[o];
+            for (int a = 0; a < 3; ++a) CHECK(same_bits(c[3 * j + a], reference(ps[o].m, cm2 + 3 * m, a)));
+            CHECK(rad[j] == rr2[m]);
+        }
+        ps[1].m[6] = NAN;                                                                                   // a pose with a NaN entry: a centre the checks refuse
+        camera_centers(ps.data(), ix, 3, cm2, rr2, c, rad);
+        CHECK(std::isnan(c[3 * 1 + 1]) && same_bits(c[0], reference(ps[0].m, cm2 + 3, 0)) && info_center_radius_ok("job_sanitize", c, rad, 3) == PR_ERR_INVALID);
     }
     std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;

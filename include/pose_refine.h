@@ -942,6 +942,106 @@ int  pr_pose_penetration_multi(const pr_mesh_ref *meshes, uint32_t n_meshes, con
 int  pr_select_disjoint(const uint32_t *order, uint32_t n_order, const pr_pair_solid *pairs, uint32_t n_poses, uint32_t num, uint32_t den,
                         uint32_t *selected_out, uint32_t *n_selected);
 
+/* ---- hypotheses from the scene: point-pair-feature (PPF) voting (Drost et al. 2010) --------------------------------------------------------
+ * Everything above starts from poses somebody supplies.  These entry points make that list from a depth frame and a mesh alone: the model's
+ * oriented surface points are hashed once by the feature of every ordered pair, every scene reference point pairs with the other scene
+ * points, looks up the model pairs with the same feature and votes for (model point, rotation angle); the peaks of a reference's accumulator
+ * are poses.  Votes are integer counts, so every accumulator is exact in any order.  All lengths in mm, normals as they are (not normalised
+ * here).  Every integer below is fixed by this text; float32 arithmetic without contraction, + - * / and the correctly rounded sqrtf only, no
+ * trigonometric function per pair: angles are binned by comparisons against the tables pr_ppf_describe computes ONCE, on the host, in double
+ * (device and references read the tables of the descriptor and never recompute them -- the rule of pr_scene_grid.inv_cell).
+ *   dot(a, b) = (ax*bx + ay*by) + az*bz;   len(a) = sqrtf(dot(a, a));   a value is "good" when it is finite, a length when also > 0.
+ *   frame of an oriented point (p, n): e = the coordinate axis of the smallest |component| of n (the lowest index on a tie);  w = e x n
+ *     (e = x: (0, -nz, ny), y: (nz, 0, -nx), z: (-ny, nx, 0));  u = w / len(w), component by component;  v = n x u =
+ *     (ny*uz - nz*uy, nz*ux - nx*uz, nx*uy - ny*ux).  No frame (and no pair) when len(w) is not good.
+ *   ordered pair, reference (p_r, n_r) with frame (u, v) and other point (p_i, n_i):  d = p_i - p_r, L = len(d), t = L * inv_dist_step;
+ *     c1 = dot(n_r, d) / L, c2 = dot(n_i, d) / L, c3 = dot(n_r, n_i);  y = dot(d, u), z = dot(d, v), r = sqrtf(y*y + z*z);  the pair's
+ *     angle is the unit vector (y / r, z / r).  The pair is SKIPPED unless L and r are good, t < n_dist and c1, c2, c3 are finite (a point
+ *     paired with itself or with a coincident one has L == 0).
+ *   angle bin of c: the number of k in 1 .. n_angle-1 with c <= cos_edge[k] (0 .. n_angle-1; clamps by itself for |c| slightly above 1).
+ *   key = ((b_d*A + b1)*A + b2)*A + b3, b_d = (int)t, b1..b3 the angle bins of c1..c3, A = n_angle;  key < n_keys = n_dist * A^3.
+ *   vote angle alpha = (scene pair's angle) - (model pair's angle), the rotation about the frames' common x axis (the normal) that carries the
+ *     model pair's other point onto the scene pair's, as a complex product of the unit vectors (cs, ss) and (cm, sm):
+ *     ca = cs*cm + ss*sm, sa = ss*cm - cs*sm, q = sqrtf(ca*ca + sa*sa) (no vote unless good), cn = ca / q,
+ *     h = the number of k in 1 .. n_alpha/2-1 with cn <= alpha_edge[k];  bin = h when sa >= 0.0f, else n_alpha-1-h.
+ *     The boundary rule: sa == 0 of either sign is the UPPER half-plane, so alpha = 0 falls into bin 0 and alpha = pi into bin n_alpha/2-1;
+ *     bin b covers [b, b+1) * 2 pi / n_alpha up to the rounding of cn, its centre is (b + 0.5) * 2 pi / n_alpha.
+ *   pose of a peak (model point m, scene point s, alpha bin b), in DOUBLE from the float32 inputs, rounded to float32 once:  for either
+ *     oriented point nh = n / sqrt(dot(n, n)), e chosen as above on the float32 n, w = e x nh, u = w / sqrt(dot(w, w)), v = nh x u,
+ *     B = rows (nh, u, v);  with (c, s) = (alpha_cos[b], alpha_sin[b]):  M = rows (Bm_0, c*Bm_1 - s*Bm_2, s*Bm_1 + c*Bm_2),
+ *     R[i][j] = (Bs[0][i]*M[0][j] + Bs[1][i]*M[1][j]) + Bs[2][i]*M[2][j]  (R = Bs^T Rx(centre) Bm),  t[i] = p_s[i] - dot(R[i], p_m);
+ *     the matrix is [R t; 0 0 0 1].
+ * pr_ppf_describe: dist_step = dist_step_mm, inv_dist_step = 1.0f / dist_step, n_dist = ceil(diameter / dist_step) in double (1 ..
+ * PR_PPF_MAX_DIST_BINS), n_angle 2 .. PR_PPF_MAX_ANGLE_BINS with cos_edge[k] = (float)cos(k pi / n_angle), k = 0 .. n_angle, n_alpha even, 2 ..
+ * PR_PPF_MAX_ALPHA_BINS, with alpha_edge[k] = (float)cos(k 2 pi / n_alpha), k = 0 .. n_alpha/2 (the edges in [0, pi]) and the double cosine
+ * and sine of every bin centre.  PR_ERR_INVALID with nothing written for anything else (a non-finite or non-positive length, a null out).
+ * Host only.  Every entry point below that takes a descriptor checks it against these rules (not the tables' values).
+ * pr_ppf_model_sample (host only): oriented points of a mesh at spacing step_mm.  Per triangle, N = max(1, ceil(longest edge / step)) and the
+ * lattice v0 + (i/N)(v1 - v0) + (j/N)(v2 - v0), i = 0 .. N, j = 0 .. N-i (i outer), in double, rounded to float32; of the points of all
+ * triangles in (triangle, lattice) order the FIRST in every voxel (floor(coordinate / step) per axis, in double, of the rounded point) is kept.
+ * The normal is (v1 - v0) x (v2 - v0) normalised in double, negated when flip_normals, rounded; triangles whose normal has no good length are
+ * skipped.  points_out / normals_out: room for PR_PPF_MAX_MODEL_POINTS; *n_out = the number of points found; more than the cap (the walk stops
+ * there, *n_out = the cap + 1), a triangle that needs more than 10^6 subdivisions, a non-finite or non-positive step or a null pointer:
+ * PR_ERR_INVALID (the caller coarsens the step).
+ * pr_ppf_model_build_dev: the direct-addressed table of the model, no hash function: offsets_dev_out[n_keys + 1] and one 12-byte entry per
+ * ordered pair (ref, other), ref != other, that is not skipped, in bucket key: entries [offsets[key], offsets[key+1]).  The SET of a bucket
+ * is fixed by the text above, the order inside it is not (votes do not depend on it).  entries_dev_out: room for n_model * (n_model - 1).
+ * *n_entries_out = offsets[n_keys].  1 <= n_model <= PR_PPF_MAX_MODEL_POINTS.
+ * pr_ppf_scene_points_dev: the pixels (x, y) with x % stride == 0 and y % stride == 0 of a pr_scene_proj (dense pcd and normal, metres) whose
+ * normal has a non-zero component and whose pcd z is > 0, compacted in row-major pixel order: point = pcd * 1000.0f per component, normal as it
+ * is.  points_dev_out / normals_dev_out: room for PR_PPF_MAX_SCENE_POINTS.  *n_out = the number kept; more than the cap: PR_ERR_INVALID with
+ * nothing emitted (raise the stride).  stride 1 .. PR_PPF_MAX_STRIDE.  The same frame gives the same bytes.
+ * pr_ppf_vote: reference j = scene point ref_first + j * ref_stride, j < n_refs (all < n_scene).  Its accumulator acc[m * n_alpha + bin]
+ * counts, over every scene point i that forms a pair with it and every entry (m, other, cm, sm) of that pair's bucket, one vote in the bin
+ * above.  n_model * n_alpha <= PR_PPF_MAX_CELLS (the accumulator lives in one workgroup's LDS).  Peaks: the n_peaks (1 .. PR_PPF_MAX_PEAKS) first
+ * cells in the order (votes descending, cell index ascending) among the cells with votes > 0; peaks_host[j * n_peaks + k], an unused slot has
+ * votes = 0, model_ref = alpha_bin = 0 and an all-zero pose.  n_pairs: the scene points that formed a pair with the reference.  poses_host:
+ * the pose of every peak by the formula above, from one read-back of the peaks and the references; model_points_host / model_normals_host are
+ * the sampler's HOST arrays.  acc_dev_out (may be NULL; tests and tools): n_refs x n_model x n_alpha uint32.  No float atomics anywhere.
+ * The device entry points are synchronous, on the calling thread's context; a batch pending on an asynchronous slot is not disturbed.  Every
+ * argument is checked BEFORE any device is touched (PR_ERR_INVALID also on a machine without one): a bad descriptor, a cap exceeded, a null
+ * pointer, n_peaks outside 1 .. 4, ref_stride == 0, a reference at or beyond n_scene.  n_refs == 0: PR_OK, nothing written.
+ * pr_ppf_peak_pose: the formula for one peak, host only.  PR_ERR_INVALID (nothing written) for a null pointer, alpha_bin >= n_alpha or a
+ * normal without a frame.
+ * Not offered: votes spread to neighbouring bins, averaged cluster poses, a _multi form, an asynchronous form, colour or edge point pairs,
+ * keeping a scene sample between calls. */
+#define PR_PPF_MAX_DIST_BINS    64
+#define PR_PPF_MAX_ANGLE_BINS   32
+#define PR_PPF_MAX_ALPHA_BINS   64
+#define PR_PPF_MAX_KEYS         (1u << 21)
+#define PR_PPF_MAX_MODEL_POINTS 2048
+#define PR_PPF_MAX_SCENE_POINTS 16384
+#define PR_PPF_MAX_CELLS        32768        /* n_model * n_alpha: 128 KiB of the CU's 160 KiB of LDS */
+#define PR_PPF_MAX_PEAKS        4
+#define PR_PPF_MAX_STRIDE       256
+typedef struct {
+    float    diameter, dist_step, inv_dist_step;
+    uint32_t n_dist, n_angle, n_alpha, n_keys, flip_model_normals;
+    float    cos_edge[PR_PPF_MAX_ANGLE_BINS + 1];         /* [0 .. n_angle], the rest 0                                          */
+    float    alpha_edge[PR_PPF_MAX_ALPHA_BINS / 2 + 1];   /* [0 .. n_alpha/2], the rest 0                                        */
+    double   alpha_cos[PR_PPF_MAX_ALPHA_BINS];            /* bin centres; only the pose formula reads them                       */
+    double   alpha_sin[PR_PPF_MAX_ALPHA_BINS];
+} pr_ppf_params;               /* 1320 B */
+typedef struct { uint32_t pair; float cos_m, sin_m; } pr_ppf_entry;      /* 12 B; pair = ref << 16 | other                        */
+typedef struct {
+    uint32_t votes;
+    uint16_t model_ref, alpha_bin;
+    uint32_t scene_ref;        /* index into the scene points                                                                    */
+    uint32_t n_pairs;
+} pr_ppf_peak;                 /* 16 B */
+int  pr_ppf_describe(float diameter_mm, float dist_step_mm, uint32_t n_angle, uint32_t n_alpha, int flip_model_normals, pr_ppf_params *out);
+int  pr_ppf_model_sample(const pr_triangle *tris_host, size_t n_tris, float step_mm, int flip_normals, pr_vec3 *points_out, pr_vec3 *normals_out,
+                         uint32_t *n_out);
+int  pr_ppf_model_build_dev(const pr_ppf_params *params, const pr_vec3 *points_dev, const pr_vec3 *normals_dev, uint32_t n_model,
+                            uint32_t *offsets_dev_out, pr_ppf_entry *entries_dev_out, uint32_t *n_entries_out);
+int  pr_ppf_scene_points_dev(const pr_scene_proj *scene, uint32_t stride, pr_vec3 *points_dev_out, pr_vec3 *normals_dev_out, uint32_t *n_out);
+int  pr_ppf_vote(const pr_ppf_params *params, const uint32_t *offsets_dev, const pr_ppf_entry *entries_dev, const pr_vec3 *model_points_host,
+                 const pr_vec3 *model_normals_host, uint32_t n_model, const pr_vec3 *scene_points_dev, const pr_vec3 *scene_normals_dev,
+                 uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks, pr_ppf_peak *peaks_host,
+                 pr_mat4 *poses_host, uint32_t *acc_dev_out /* may be NULL */);
+int  pr_ppf_peak_pose(const pr_ppf_params *params, const pr_vec3 *model_point, const pr_vec3 *model_normal, const pr_vec3 *scene_point,
+                      const pr_vec3 *scene_normal, uint32_t alpha_bin, pr_mat4 *pose_out);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 
@@ -999,7 +1099,9 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *   "nn_lds_nodes"     [1024]  stackless query: leading nodes staged in LDS;  "nn_lds_records" [0]: the same for 64-byte records
  *   "profile"          [0]     see below;  "sample_period" [32]: profile 2 times one call in this many
  *   "scene_cache"      [1]     keep derived scene data between calls (see "Caches" at the top)
- *   "pose_dist_chunk"  (read-only) model points a workgroup of pr_pose_distance stages at a time: where its point loop has its seams */
+ *   "pose_dist_chunk"  (read-only) model points a workgroup of pr_pose_distance stages at a time: where its point loop has its seams
+ *   "ppf_walk"         [1]     pr_ppf_vote: 1 = a wavefront walks the buckets of its 64 scene pairs together (entry t of their concatenation goes to lane
+ *                              t % 64, so lanes stay busy whatever the bucket lengths), 0 = every lane walks its own pair's bucket.  Same bytes either way */
 int  pr_set_option(const char *name, int value);
 int  pr_get_option(const char *name, int *value);
 /* HIP-event timing of the correspondence kernel on the library stream: option "profile" = 1 times every launch (all calls run

@@ -65,6 +65,12 @@ POSE_INFO = np.dtype([("n_points", "<u4"), ("n_valid", "<u4"), ("n_zero_weight",
 POSE_EIG = np.dtype([("lambda", "<f8", (6,)), ("V", "<f8", (6, 6)), ("sweeps", "<u4"), ("reserved", "<u4")])
 INFO_MAX_SWEEPS = 16                     # PR_INFO_MAX_SWEEPS
 assert POSE_INFO.itemsize == 272 and POSE_EIG.itemsize == 344
+# pr_ppf_entry / pr_ppf_peak: an ordered model pair in its bucket, a peak of a scene reference's accumulator (pr_ppf_model_build_dev, pr_ppf_vote)
+PPF_ENTRY = np.dtype([("pair", "<u4"), ("cos_m", "<f4"), ("sin_m", "<f4")])
+PPF_PEAK = np.dtype([("votes", "<u4"), ("model_ref", "<u2"), ("alpha_bin", "<u2"), ("scene_ref", "<u4"), ("n_pairs", "<u4")])
+PPF_MAX_DIST_BINS, PPF_MAX_ANGLE_BINS, PPF_MAX_ALPHA_BINS, PPF_MAX_KEYS = 64, 32, 64, 1 << 21        # PR_PPF_MAX_*
+PPF_MAX_MODEL_POINTS, PPF_MAX_SCENE_POINTS, PPF_MAX_CELLS, PPF_MAX_PEAKS, PPF_MAX_STRIDE = 2048, 16384, 32768, 4, 256
+assert PPF_ENTRY.itemsize == 12 and PPF_PEAK.itemsize == 16
 POSE_DIST_CHUNK = 256                    # PR_POSE_DIST_CHUNK (pr_tuning.h; the library reports its own as option "pose_dist_chunk")
 assert KDNODE.itemsize == 52 and RESULT.itemsize == 72 and SCORE.itemsize == 32 and CONTOUR.itemsize == 32
 assert COVER.itemsize == 16 and COVER_FRAME.itemsize == 16 and CONTOUR_FIT.itemsize == 32
@@ -97,6 +103,16 @@ ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY, ROBUST_CAUCHY = 0, 1, 2, 3      # PR_RO
 class RobustDesc(C.Structure):
     """pr_robust: an M-estimator weight on the ICP residual (pr_robust_describe fills it: inv_c is computed there, once)."""
     _fields_ = [("kind", C.c_uint32), ("c", C.c_float), ("inv_c", C.c_float), ("reserved", C.c_uint32)]
+
+
+class PPFParams(C.Structure):
+    """pr_ppf_params: the point-pair-feature descriptor (pr_ppf_describe fills it: the bin edges and centres are computed there, once)."""
+    _fields_ = [("diameter", C.c_float), ("dist_step", C.c_float), ("inv_dist_step", C.c_float), ("n_dist", C.c_uint32), ("n_angle", C.c_uint32),
+                ("n_alpha", C.c_uint32), ("n_keys", C.c_uint32), ("flip_model_normals", C.c_uint32), ("cos_edge", C.c_float * 33),
+                ("alpha_edge", C.c_float * 33), ("alpha_cos", C.c_double * 64), ("alpha_sin", C.c_double * 64)]
+
+
+assert C.sizeof(PPFParams) == 1320
 
 
 class MeshRef(C.Structure):
@@ -231,6 +247,12 @@ SIGNATURES = {
     "pr_compose_detections_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, Roi, _vp, _i32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "pr_pose_distance": (_i32, [_vp, _u32, _vp, _u32, _vp, _u32, _i32, _vp, _u32, _vp, _vp]),
     "pr_cluster_greedy": (_i32, [_vp, _u32, _vp, _u32, C.c_float, _vp, C.POINTER(_u32), _vp]),
+    "pr_ppf_describe": (_i32, [C.c_float, C.c_float, _u32, _u32, _i32, _vp]),
+    "pr_ppf_model_sample": (_i32, [_vp, _sz, C.c_float, _i32, _vp, _vp, C.POINTER(_u32)]),
+    "pr_ppf_model_build_dev": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "pr_ppf_scene_points_dev": (_i32, [_vp, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "pr_ppf_vote": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "pr_ppf_peak_pose": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_render_span": (_i32, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, Roi, _vp, _vp]),

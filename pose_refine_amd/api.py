@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -1424,6 +1424,143 @@ def merge_duplicates(order, dist, max_disp_mm: float):
     rep = rep[:len(dm)].astype(np.int64)
     rep[rep == 0xffffffff] = -1
     return kept[:n.value].astype(np.int64), rep
+
+
+# ------------------------------------------------------------------------------------------------
+# hypotheses from the scene: point-pair-feature voting (pr_ppf_*; the definition is in include/pose_refine.h)
+# ------------------------------------------------------------------------------------------------
+def ppf_describe(diameter_mm: float, dist_step_mm: float, n_angle: int = 15, n_alpha: int = 30, flip_model_normals: bool = False) -> PPFParams:
+    """``pr_ppf_describe`` (host only): the descriptor with its bin-edge and bin-centre tables."""
+    pp = PPFParams()
+    check(_lib.load().pr_ppf_describe(float(diameter_mm), float(dist_step_mm), int(n_angle), int(n_alpha), int(bool(flip_model_normals)), C.addressof(pp)))
+    return pp
+
+
+def ppf_model_sample(tris, step_mm: float, flip_normals: bool = False):
+    """``pr_ppf_model_sample`` (host only): (points float32[n, 3], normals float32[n, 3]) of a mesh at spacing ``step_mm``: one lattice point per
+    occupied voxel.  More than ``PPF_MAX_MODEL_POINTS`` raises PoseRefineError(PR_ERR_INVALID): coarsen the step."""
+    t = _f32(tris.tris if isinstance(tris, Model) else tris, (-1, 3, 3))
+    pts = np.zeros((PPF_MAX_MODEL_POINTS, 3), np.float32)
+    nrm = np.zeros((PPF_MAX_MODEL_POINTS, 3), np.float32)
+    n = C.c_uint32(0)
+    check(_lib.load().pr_ppf_model_sample(ptr(t) if len(t) else None, len(t), float(step_mm), int(bool(flip_normals)), ptr(pts), ptr(nrm), C.byref(n)))
+    return pts[:n.value].copy(), nrm[:n.value].copy()
+
+
+def ppf_peak_pose(params: PPFParams, model_point, model_normal, scene_point, scene_normal, alpha_bin: int) -> np.ndarray:
+    """``pr_ppf_peak_pose`` (host only): the float32 4x4 pose of one peak."""
+    a = [_f32(v, 3) for v in (model_point, model_normal, scene_point, scene_normal)]
+    out = np.zeros((4, 4), np.float32)
+    check(_lib.load().pr_ppf_peak_pose(C.addressof(params), ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3]), int(alpha_bin), ptr(out)))
+    return out
+
+
+class PPFModel:
+    """The point-pair-feature model of one mesh: its oriented sample points (host, made on construction -- no device needed) and, on the device
+    from the first use on, the direct-addressed pair table of ``pr_ppf_model_build_dev``.  ``step_mm`` defaults to 0.05 of the diameter (the
+    diagonal of the vertices' box), ``dist_step_mm`` to ``step_mm``.  ``flip_normals=False`` is right for meshes wound like obj_06, whose
+    face normals point outwards: the scene's normals point towards the camera, and so does the outward normal of a visible face."""
+
+    def __init__(self, tris, step_mm: Optional[float] = None, n_angle: int = 15, n_alpha: int = 30, dist_step_mm: Optional[float] = None,
+                 flip_normals: bool = False):
+        t = _f32(tris.tris if isinstance(tris, Model) else tris, (-1, 3, 3))
+        v = t.reshape(-1, 3).astype(np.float64)
+        self.diameter = float(np.float32(np.linalg.norm(v.max(0) - v.min(0)))) if len(v) else 0.0
+        self.step_mm = float(np.float32(0.05 * self.diameter if step_mm is None else step_mm))
+        self.dist_step_mm = float(np.float32(self.step_mm if dist_step_mm is None else dist_step_mm))
+        self.params = ppf_describe(self.diameter, self.dist_step_mm, n_angle, n_alpha, flip_normals)
+        self.points, self.normals = ppf_model_sample(t, self.step_mm, flip_normals)
+        if len(self.points) == 0:
+            raise ValueError("PPFModel: the mesh has no sample points")
+        if len(self.points) * n_alpha > PPF_MAX_CELLS:
+            raise ValueError(f"PPFModel: {len(self.points)} points x {n_alpha} alpha bins exceed PPF_MAX_CELLS = {PPF_MAX_CELLS}: coarsen step_mm")
+        self._points_dev = self._normals_dev = self.offsets = self.entries = None
+        self.n_entries = 0
+
+    def device_points(self) -> DeviceVector:
+        """The sample points on the device (3 float32 each): also the points ``generate_hypotheses`` merges duplicates over."""
+        if self._points_dev is None:
+            self._points_dev = DeviceVector.from_host(self.points.reshape(-1))
+            self._normals_dev = DeviceVector.from_host(self.normals.reshape(-1))
+        return self._points_dev
+
+    def build(self) -> "PPFModel":
+        """``pr_ppf_model_build_dev``, once: ``offsets`` (n_keys + 1 uint32) and ``entries`` (PPF_ENTRY) on the device."""
+        if self.offsets is None:
+            n = len(self.points)
+            pts = self.device_points()
+            offsets = DeviceVector(self.params.n_keys + 1, np.uint32)
+            entries = DeviceVector(max(1, n * (n - 1)), PPF_ENTRY)
+            ne = C.c_uint32(0)
+            check(_lib.load().pr_ppf_model_build_dev(C.addressof(self.params), pts.data(), self._normals_dev.data(), n, offsets.data(), entries.data(), C.byref(ne)))
+            self.offsets, self.entries, self.n_entries = offsets, entries, ne.value
+        return self
+
+    def table(self):
+        """(offsets uint32[n_keys + 1], entries PPF_ENTRY[n_entries]) read back from the device (tests and tools)."""
+        self.build()
+        return self.offsets.to_host(), self.entries.to_host()[:self.n_entries]
+
+
+def ppf_scene_points(scene: "Scene_projective", stride: int):
+    """``pr_ppf_scene_points_dev``: (points, normals, n) -- two DeviceVectors with room for ``PPF_MAX_SCENE_POINTS`` points (3 float32 each), the
+    first ``n`` filled: every ``stride``-th column and row of a full-frame projective scene with a normal and a depth, in mm, row-major."""
+    if scene.kind != SCENE_PROJ:
+        raise ValueError("ppf_scene_points takes a full-frame Scene_projective")
+    pts = DeviceVector(PPF_MAX_SCENE_POINTS * 3, np.float32)
+    nrm = DeviceVector(PPF_MAX_SCENE_POINTS * 3, np.float32)
+    d = scene.desc()
+    n = C.c_uint32(0)
+    check(_lib.load().pr_ppf_scene_points_dev(C.addressof(d), int(stride), pts.data(), nrm.data(), C.byref(n)))
+    return pts, nrm, n.value
+
+
+def ppf_vote(ppf_model: PPFModel, scene_points: DeviceVector, scene_normals: DeviceVector, n_scene: int, ref_first: int = 0, ref_stride: int = 1,
+             n_refs: Optional[int] = None, n_peaks: int = 1, want_acc: bool = False):
+    """``pr_ppf_vote``: (peaks PPF_PEAK[n_refs, n_peaks], poses float32[n_refs, n_peaks, 4, 4]) of the references ``ref_first + j * ref_stride``
+    (``n_refs=None``: as many as fit); with ``want_acc`` also the accumulators, uint32[n_refs, n_model, n_alpha] (tests and tools)."""
+    ppf_model.build()
+    if n_refs is None:
+        n_refs = 0 if ref_first >= n_scene or ref_stride < 1 else (n_scene - 1 - ref_first) // ref_stride + 1
+    n_model, n_alpha = len(ppf_model.points), ppf_model.params.n_alpha
+    peaks = np.zeros((n_refs, n_peaks), PPF_PEAK)
+    poses = np.zeros((n_refs, n_peaks, 4, 4), np.float32)
+    acc = DeviceVector(max(1, n_refs * n_model * n_alpha), np.uint32) if want_acc else None
+    check(_lib.load().pr_ppf_vote(C.addressof(ppf_model.params), ppf_model.offsets.data(), ppf_model.entries.data(), ptr(ppf_model.points), ptr(ppf_model.normals),
+                                  n_model, scene_points.data(), scene_normals.data(), int(n_scene), int(ref_first), int(ref_stride), int(n_refs), int(n_peaks),
+                                  ptr(peaks), ptr(poses), acc.data() if want_acc else None))
+    if want_acc:
+        return peaks, poses, acc.to_host()[:n_refs * n_model * n_alpha].reshape(n_refs, n_model, n_alpha)
+    return peaks, poses
+
+
+def generate_hypotheses(ppf_model: PPFModel, scene: "Scene_projective", stride: int = 4, ref_stride: int = 5, n_peaks: int = 1, max_hypotheses: int = 256,
+                        merge_mm: Optional[float] = None):
+    """Pose hypotheses from a frame and a mesh alone: sample the scene (``stride``), vote with every ``ref_stride``-th sample as a reference, order
+    the peaks by votes (descending, then by index), merge duplicates with ``pose_distance_matrix`` + ``merge_duplicates`` over the model's sample
+    points (``merge_mm`` defaults to ``dist_step_mm``), add the votes of each merged group onto its representative and order again.  Returns
+    (poses float32[n, 4, 4], votes int64[n]), n <= ``max_hypotheses``: ready for ``refine_batch`` and ``score_poses``.  The vote sum is only the
+    order in which hypotheses are handed on; ``rank_hypotheses`` stays the one definition of better after scoring."""
+    pts, nrm, n_scene = ppf_scene_points(scene, stride)
+    if n_scene == 0:
+        return np.zeros((0, 4, 4), np.float32), np.zeros(0, np.int64)
+    n_refs = (n_scene - 1) // ref_stride + 1
+    if n_refs * n_peaks > POSE_DIST_MAX_POSES:
+        raise ValueError(f"{n_refs} references x {n_peaks} peaks exceed POSE_DIST_MAX_POSES = {POSE_DIST_MAX_POSES}: raise stride or ref_stride")
+    peaks, poses = ppf_vote(ppf_model, pts, nrm, n_scene, 0, ref_stride, n_refs, n_peaks)
+    votes = peaks["votes"].reshape(-1).astype(np.int64)
+    poses = poses.reshape(-1, 4, 4)
+    live = np.flatnonzero(votes > 0)
+    if len(live) == 0:
+        return np.zeros((0, 4, 4), np.float32), np.zeros(0, np.int64)
+    votes, poses = votes[live], np.ascontiguousarray(poses[live])
+    order = np.argsort(-votes, kind="stable")
+    dist = pose_distance_matrix(ppf_model.device_points(), poses)
+    kept, rep = merge_duplicates(order, dist, ppf_model.dist_step_mm if merge_mm is None else merge_mm)
+    total = np.zeros(len(votes), np.int64)
+    np.add.at(total, rep, votes)
+    kept = kept[np.argsort(-total[kept], kind="stable")][:max_hypotheses]
+    return poses[kept], total[kept]
 
 
 # ------------------------------------------------------------------------------------------------

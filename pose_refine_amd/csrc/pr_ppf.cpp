@@ -1,0 +1,243 @@
+// pr_ppf.cpp -- pr_ppf_*: the descriptor and its tables, the model sampler and the pose formula on the host, the launches of ppf.hip
+#include <unordered_set>
+
+#include "pr_runtime.h"
+#include "ppf.h"
+
+namespace prr {
+
+// a descriptor as a caller hands it over: pr_ppf_describe's rules (not the tables' values).  No HIP call in here.
+static int ppf_params_ok(const char *fn, const pr_ppf_params *pp)
+{
+    if (!pp) { set_error("%s: null pr_ppf_params", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(pp->dist_step) || !(pp->dist_step > 0.0f) || !std::isfinite(pp->diameter) || !(pp->diameter > 0.0f)) {
+        set_error("%s: pr_ppf_params: diameter and dist_step must be finite and positive (got %g, %g)", fn, (double)pp->diameter, (double)pp->dist_step); return PR_ERR_INVALID;
+    }
+    if (!(pp->inv_dist_step == 1.0f / pp->dist_step)) { set_error("%s: pr_ppf_params: inv_dist_step is not 1.0f / dist_step (pr_ppf_describe computes it)", fn); return PR_ERR_INVALID; }
+    if (pp->n_dist == 0 || pp->n_dist > PR_PPF_MAX_DIST_BINS) { set_error("%s: pr_ppf_params: n_dist must be 1 .. PR_PPF_MAX_DIST_BINS = %d (got %u)", fn, PR_PPF_MAX_DIST_BINS, pp->n_dist); return PR_ERR_INVALID; }
+    if (pp->n_angle < 2 || pp->n_angle > PR_PPF_MAX_ANGLE_BINS) { set_error("%s: pr_ppf_params: n_angle must be 2 .. PR_PPF_MAX_ANGLE_BINS = %d (got %u)", fn, PR_PPF_MAX_ANGLE_BINS, pp->n_angle); return PR_ERR_INVALID; }
+    if (pp->n_alpha < 2 || pp->n_alpha > PR_PPF_MAX_ALPHA_BINS || (pp->n_alpha & 1u)) { set_error("%s: pr_ppf_params: n_alpha must be even, 2 .. PR_PPF_MAX_ALPHA_BINS = %d (got %u)", fn, PR_PPF_MAX_ALPHA_BINS, pp->n_alpha); return PR_ERR_INVALID; }
+    if (pp->n_keys != pp->n_dist * pp->n_angle * pp->n_angle * pp->n_angle || pp->n_keys > PR_PPF_MAX_KEYS) { set_error("%s: pr_ppf_params: n_keys is not n_dist * n_angle^3 <= PR_PPF_MAX_KEYS (got %u)", fn, pp->n_keys); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+static ppf::Tables tables_of(const pr_ppf_params *pp) { ppf::Tables t; std::memcpy(&t, pp, sizeof t); return t; }
+
+// the pose formula's frame, in double from the float32 normal: rows (nh, u, v)
+static bool frame_d(const pr_vec3 &n, double B[3][3])
+{
+    const double nx = n.x, ny = n.y, nz = n.z;
+    const double ln = std::sqrt((nx * nx + ny * ny) + nz * nz);
+    if (!(ln > 0.0) || !std::isfinite(ln)) return false;
+    const double hx = nx / ln, hy = ny / ln, hz = nz / ln;
+    const float ax = std::fabs(n.x), ay = std::fabs(n.y), az = std::fabs(n.z);
+    double wx, wy, wz;
+    if (ax <= ay && ax <= az) { wx = 0.0; wy = -hz; wz = hy; }
+    else if (ay <= az)        { wx = hz; wy = 0.0; wz = -hx; }
+    else                      { wx = -hy; wy = hx; wz = 0.0; }
+    const double lw = std::sqrt((wx * wx + wy * wy) + wz * wz);
+    if (!(lw > 0.0) || !std::isfinite(lw)) return false;
+    const double ux = wx / lw, uy = wy / lw, uz = wz / lw;
+    B[0][0] = hx; B[0][1] = hy; B[0][2] = hz;
+    B[1][0] = ux; B[1][1] = uy; B[1][2] = uz;
+    B[2][0] = hy * uz - hz * uy; B[2][1] = hz * ux - hx * uz; B[2][2] = hx * uy - hy * ux;
+    return true;
+}
+static bool peak_pose(const pr_ppf_params *pp, const pr_vec3 &pm, const pr_vec3 &nm, const pr_vec3 &ps, const pr_vec3 &ns, uint32_t bin, pr_mat4 *out)
+{
+    double Bm[3][3], Bs[3][3], M[3][3];
+    if (!frame_d(nm, Bm) || !frame_d(ns, Bs)) return false;
+    const double c = pp->alpha_cos[bin], s = pp->alpha_sin[bin];
+    for (int j = 0; j < 3; ++j) { M[0][j] = Bm[0][j]; M[1][j] = c * Bm[1][j] - s * Bm[2][j]; M[2][j] = s * Bm[1][j] + c * Bm[2][j]; }
+    const double p[3] = { pm.x, pm.y, pm.z }, q[3] = { ps.x, ps.y, ps.z };
+    std::memset(out, 0, sizeof *out);
+    for (int i = 0; i < 3; ++i) {
+        double R[3];
+        for (int j = 0; j < 3; ++j) { R[j] = (Bs[0][i] * M[0][j] + Bs[1][i] * M[1][j]) + Bs[2][i] * M[2][j]; out->m[i * 4 + j] = (float)R[j]; }
+        out->m[i * 4 + 3] = (float)(q[i] - ((R[0] * p[0] + R[1] * p[1]) + R[2] * p[2]));
+    }
+    out->m[15] = 1.0f;
+    return true;
+}
+
+// a word (or a few) of the device into the pinned block, and wait: the totals of a build or a sample
+static int read_words(const void *dev, uint32_t n_words)
+{
+    PR_TRY(g->h_ppf.ensure(sizeof(uint32_t) * n_words));
+    HIP_TRY(prk::launch_copy_words32(dev, g->h_ppf.dev, n_words, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return PR_OK;
+}
+
+}  // namespace prr
+
+using namespace prr;
+
+extern "C" {
+
+int pr_ppf_describe(float diameter_mm, float dist_step_mm, uint32_t n_angle, uint32_t n_alpha, int flip_model_normals, pr_ppf_params *out)
+{
+    const char *fn = "pr_ppf_describe";
+    pr_ppf_params pp;
+    std::memset(&pp, 0, sizeof pp);
+    pp.diameter = diameter_mm; pp.dist_step = dist_step_mm; pp.inv_dist_step = 1.0f / dist_step_mm;
+    pp.n_angle = n_angle; pp.n_alpha = n_alpha; pp.flip_model_normals = flip_model_normals ? 1u : 0u;
+    if (!out) { set_error("%s: null out", fn); return PR_ERR_INVALID; }
+    if (std::isfinite(diameter_mm) && std::isfinite(dist_step_mm) && diameter_mm > 0.0f && dist_step_mm > 0.0f) {
+        const double nd = std::ceil((double)diameter_mm / (double)dist_step_mm);
+        pp.n_dist = nd <= (double)PR_PPF_MAX_DIST_BINS ? (uint32_t)nd : PR_PPF_MAX_DIST_BINS + 1u;
+    }
+    if (pp.n_angle <= PR_PPF_MAX_ANGLE_BINS) pp.n_keys = pp.n_dist * n_angle * n_angle * n_angle;
+    PR_TRY(ppf_params_ok(fn, &pp));
+    const double pi = 3.14159265358979323846;
+    for (uint32_t k = 0; k <= n_angle; ++k) pp.cos_edge[k] = (float)std::cos((double)k * pi / (double)n_angle);
+    for (uint32_t k = 0; k <= n_alpha / 2; ++k) pp.alpha_edge[k] = (float)std::cos((double)k * (2.0 * pi) / (double)n_alpha);
+    for (uint32_t b = 0; b < n_alpha; ++b) {
+        const double a = ((double)b + 0.5) * (2.0 * pi) / (double)n_alpha;
+        pp.alpha_cos[b] = std::cos(a); pp.alpha_sin[b] = std::sin(a);
+    }
+    *out = pp;
+    return PR_OK;
+}
+
+int pr_ppf_model_sample(const pr_triangle *tris_host, size_t n_tris, float step_mm, int flip_normals, pr_vec3 *points_out, pr_vec3 *normals_out, uint32_t *n_out)
+{
+    const char *fn = "pr_ppf_model_sample";
+    if ((!tris_host && n_tris > 0) || !points_out || !normals_out || !n_out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    if (!std::isfinite(step_mm) || !(step_mm > 0.0f)) { set_error("%s: step_mm must be finite and positive (got %g)", fn, (double)step_mm); return PR_ERR_INVALID; }
+    const double step = step_mm;
+    struct Key { int64_t x, y, z; bool operator==(const Key &o) const { return x == o.x && y == o.y && z == o.z; } };
+    struct KeyHash { size_t operator()(const Key &k) const { return (size_t)((uint64_t)k.x * 0x9e3779b97f4a7c15ull ^ (uint64_t)k.y * 0xc2b2ae3d27d4eb4full ^ (uint64_t)k.z * 0x165667b19e3779f9ull); } };
+    std::unordered_set<Key, KeyHash> seen;
+    uint32_t n = 0;
+    for (size_t t = 0; t < n_tris; ++t) {
+        const pr_triangle &tr = tris_host[t];
+        const double a[3] = { tr.v0.x, tr.v0.y, tr.v0.z }, e1[3] = { (double)tr.v1.x - a[0], (double)tr.v1.y - a[1], (double)tr.v1.z - a[2] },
+                     e2[3] = { (double)tr.v2.x - a[0], (double)tr.v2.y - a[1], (double)tr.v2.z - a[2] }, e3[3] = { e2[0] - e1[0], e2[1] - e1[1], e2[2] - e1[2] };
+        double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+        const double ln = std::sqrt((nx * nx + ny * ny) + nz * nz);
+        if (!(ln > 0.0) || !std::isfinite(ln)) continue;             // degenerate
+        nx /= ln; ny /= ln; nz /= ln;
+        if (flip_normals) { nx = -nx; ny = -ny; nz = -nz; }
+        const double l1 = std::sqrt((e1[0] * e1[0] + e1[1] * e1[1]) + e1[2] * e1[2]), l2 = std::sqrt((e2[0] * e2[0] + e2[1] * e2[1]) + e2[2] * e2[2]),
+                     l3 = std::sqrt((e3[0] * e3[0] + e3[1] * e3[1]) + e3[2] * e3[2]);
+        const double nsub = std::ceil(std::max(l1, std::max(l2, l3)) / step);
+        if (!(nsub <= 1e6)) { set_error("%s: triangle %zu needs more than 10^6 subdivisions at step %g", fn, t, step); return PR_ERR_INVALID; }
+        const int64_t N = std::max<int64_t>(1, (int64_t)nsub);
+        for (int64_t i = 0; i <= N; ++i)
+            for (int64_t j = 0; j <= N - i; ++j) {
+                const double fi = (double)i / (double)N, fj = (double)j / (double)N;
+                const pr_vec3 p = { (float)((a[0] + fi * e1[0]) + fj * e2[0]), (float)((a[1] + fi * e1[1]) + fj * e2[1]), (float)((a[2] + fi * e1[2]) + fj * e2[2]) };
+                const Key k = { (int64_t)std::floor((double)p.x / step), (int64_t)std::floor((double)p.y / step), (int64_t)std::floor((double)p.z / step) };
+                if (!seen.insert(k).second) continue;
+                if (n == PR_PPF_MAX_MODEL_POINTS) {                   // (the walk ends here: a fine step on a large mesh would go on for a long time)
+                    *n_out = n + 1;
+                    set_error("%s: more than PR_PPF_MAX_MODEL_POINTS = %d points at step %g (coarsen the step)", fn, PR_PPF_MAX_MODEL_POINTS, step); return PR_ERR_INVALID;
+                }
+                points_out[n] = p; normals_out[n] = pr_vec3{ (float)nx, (float)ny, (float)nz };
+                ++n;
+            }
+    }
+    *n_out = n;
+    return PR_OK;
+}
+
+int pr_ppf_peak_pose(const pr_ppf_params *params, const pr_vec3 *model_point, const pr_vec3 *model_normal, const pr_vec3 *scene_point,
+                     const pr_vec3 *scene_normal, uint32_t alpha_bin, pr_mat4 *pose_out)
+{
+    const char *fn = "pr_ppf_peak_pose";
+    PR_TRY(ppf_params_ok(fn, params));
+    if (!model_point || !model_normal || !scene_point || !scene_normal || !pose_out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    if (alpha_bin >= params->n_alpha) { set_error("%s: alpha_bin %u, but n_alpha = %u", fn, alpha_bin, params->n_alpha); return PR_ERR_INVALID; }
+    pr_mat4 m;
+    if (!peak_pose(params, *model_point, *model_normal, *scene_point, *scene_normal, alpha_bin, &m)) { set_error("%s: a normal without a frame", fn); return PR_ERR_INVALID; }
+    *pose_out = m;
+    return PR_OK;
+}
+
+int pr_ppf_model_build_dev(const pr_ppf_params *params, const pr_vec3 *points_dev, const pr_vec3 *normals_dev, uint32_t n_model,
+                           uint32_t *offsets_dev_out, pr_ppf_entry *entries_dev_out, uint32_t *n_entries_out)
+{
+    const char *fn = "pr_ppf_model_build_dev";
+    PR_TRY(ppf_params_ok(fn, params));                              // before any device use
+    if (n_model == 0 || n_model > PR_PPF_MAX_MODEL_POINTS) { set_error("%s: n_model must be 1 .. PR_PPF_MAX_MODEL_POINTS = %d (got %u)", fn, PR_PPF_MAX_MODEL_POINTS, n_model); return PR_ERR_INVALID; }
+    if (!points_dev || !normals_dev || !offsets_dev_out || !n_entries_out || (!entries_dev_out && n_model > 1)) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    PR_ENTER();
+    const ppf::Tables tb = tables_of(params);
+    PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * tb.n_keys));
+    HIP_TRY(prk::launch_ppf_model_build(tb, points_dev, normals_dev, n_model, g->ppf_tmp.as<uint32_t>(), offsets_dev_out, entries_dev_out, g->stream));
+    g_writes.note(offsets_dev_out, sizeof(uint32_t) * ((size_t)tb.n_keys + 1));
+    g_writes.note(entries_dev_out, sizeof(pr_ppf_entry) * (size_t)n_model * (n_model - 1));
+    PR_TRY(read_words(offsets_dev_out + tb.n_keys, 1));
+    *n_entries_out = *g->h_ppf.as<uint32_t>();
+    return PR_OK;
+}
+
+int pr_ppf_scene_points_dev(const pr_scene_proj *scene, uint32_t stride, pr_vec3 *points_dev_out, pr_vec3 *normals_dev_out, uint32_t *n_out)
+{
+    const char *fn = "pr_ppf_scene_points_dev";
+    if (!scene || !scene->pcd || !scene->normal || !points_dev_out || !normals_dev_out || !n_out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    if (stride == 0 || stride > PR_PPF_MAX_STRIDE) { set_error("%s: stride must be 1 .. PR_PPF_MAX_STRIDE = %d (got %u)", fn, PR_PPF_MAX_STRIDE, stride); return PR_ERR_INVALID; }
+    if (scene->width == 0 || scene->height == 0) { set_error("%s: bad arguments (an empty frame)", fn); return PR_ERR_INVALID; }
+    if (!frame_size_ok(scene->width, scene->height)) return PR_ERR_INVALID;
+    PR_ENTER();
+    const uint32_t W = (uint32_t)scene->width, H = (uint32_t)scene->height, gh = (H + stride - 1) / stride;
+    PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * (2 * (size_t)gh + 1)));
+    uint32_t *row_count = g->ppf_tmp.as<uint32_t>(), *row_off = row_count + gh;
+    const float *pcd = reinterpret_cast<const float *>(scene->pcd), *normal = reinterpret_cast<const float *>(scene->normal);
+    HIP_TRY(prk::launch_ppf_scene_count(pcd, normal, W, H, stride, row_count, row_off, g->stream));
+    PR_TRY(read_words(row_off + gh, 1));
+    const uint32_t n = *g->h_ppf.as<uint32_t>();
+    *n_out = n;
+    if (n > PR_PPF_MAX_SCENE_POINTS) { set_error("%s: %u points at stride %u, at most PR_PPF_MAX_SCENE_POINTS = %d (raise the stride)", fn, n, stride, PR_PPF_MAX_SCENE_POINTS); return PR_ERR_INVALID; }
+    if (n == 0) return PR_OK;
+    HIP_TRY(prk::launch_ppf_scene_emit(pcd, normal, W, H, stride, row_off, points_dev_out, normals_dev_out, g->stream));
+    g_writes.note(points_dev_out, sizeof(pr_vec3) * n);
+    g_writes.note(normals_dev_out, sizeof(pr_vec3) * n);
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return PR_OK;
+}
+
+int pr_ppf_vote(const pr_ppf_params *params, const uint32_t *offsets_dev, const pr_ppf_entry *entries_dev, const pr_vec3 *model_points_host,
+                const pr_vec3 *model_normals_host, uint32_t n_model, const pr_vec3 *scene_points_dev, const pr_vec3 *scene_normals_dev,
+                uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks, pr_ppf_peak *peaks_host,
+                pr_mat4 *poses_host, uint32_t *acc_dev_out)
+{
+    const char *fn = "pr_ppf_vote";
+    PR_TRY(ppf_params_ok(fn, params));                              // every check before any device use
+    if (n_model == 0 || n_model > PR_PPF_MAX_MODEL_POINTS) { set_error("%s: n_model must be 1 .. PR_PPF_MAX_MODEL_POINTS = %d (got %u)", fn, PR_PPF_MAX_MODEL_POINTS, n_model); return PR_ERR_INVALID; }
+    if (n_model * params->n_alpha > PR_PPF_MAX_CELLS) { set_error("%s: n_model * n_alpha = %u, at most PR_PPF_MAX_CELLS = %d (one workgroup's LDS)", fn, n_model * params->n_alpha, PR_PPF_MAX_CELLS); return PR_ERR_INVALID; }
+    if (n_scene == 0 || n_scene > PR_PPF_MAX_SCENE_POINTS) { set_error("%s: n_scene must be 1 .. PR_PPF_MAX_SCENE_POINTS = %d (got %u)", fn, PR_PPF_MAX_SCENE_POINTS, n_scene); return PR_ERR_INVALID; }
+    if (n_peaks == 0 || n_peaks > PR_PPF_MAX_PEAKS) { set_error("%s: n_peaks must be 1 .. PR_PPF_MAX_PEAKS = %d (got %u)", fn, PR_PPF_MAX_PEAKS, n_peaks); return PR_ERR_INVALID; }
+    if (ref_stride == 0) { set_error("%s: ref_stride must not be 0", fn); return PR_ERR_INVALID; }
+    if (ref_first >= n_scene || (n_refs > 0 && (uint64_t)ref_first + (uint64_t)(n_refs - 1) * ref_stride >= n_scene)) {
+        set_error("%s: references %u + j * %u, j < %u, but there are %u scene points", fn, ref_first, ref_stride, n_refs, n_scene); return PR_ERR_INVALID;
+    }
+    if (n_refs == 0) return PR_OK;
+    if (!offsets_dev || !entries_dev || !model_points_host || !model_normals_host || !scene_points_dev || !scene_normals_dev || !peaks_host || !poses_host) {
+        set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID;
+    }
+    PR_ENTER();
+    const ppf::Tables tb = tables_of(params);
+    const size_t n_pk = (size_t)n_refs * n_peaks, pk_bytes = sizeof(pr_ppf_peak) * n_pk, bytes = pk_bytes + sizeof(prk::PpfRef) * n_refs;      // multiples of 4 both
+    PR_TRY(g->ppf_out.ensure(bytes));
+    PR_TRY(g->h_ppf.ensure(bytes));
+    pr_ppf_peak *peaks_d = g->ppf_out.as<pr_ppf_peak>();
+    prk::PpfRef *refs_d = reinterpret_cast<prk::PpfRef *>(g->ppf_out.as<unsigned char>() + pk_bytes);
+    HIP_TRY(prk::launch_ppf_vote(tb, offsets_dev, entries_dev, n_model, scene_points_dev, scene_normals_dev, n_scene, ref_first, ref_stride, n_refs, n_peaks,
+                                 peaks_d, refs_d, acc_dev_out, opt.ppf_walk != 0, g->stream));
+    if (acc_dev_out) g_writes.note(acc_dev_out, sizeof(uint32_t) * (size_t)n_refs * n_model * tb.n_alpha);
+    HIP_TRY(prk::launch_copy_words32(g->ppf_out.p, g->h_ppf.dev, (uint32_t)(bytes / sizeof(uint32_t)), g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    const pr_ppf_peak *pk = g->h_ppf.as<pr_ppf_peak>();
+    const prk::PpfRef *rf = reinterpret_cast<const prk::PpfRef *>(g->h_ppf.as<unsigned char>() + pk_bytes);
+    for (size_t i = 0; i < n_pk; ++i) {
+        peaks_host[i] = pk[i];
+        std::memset(&poses_host[i], 0, sizeof(pr_mat4));
+        const prk::PpfRef &r = rf[i / n_peaks];
+        if (pk[i].votes && pk[i].model_ref < n_model)
+            (void)peak_pose(params, model_points_host[pk[i].model_ref], model_normals_host[pk[i].model_ref], r.p, r.n, pk[i].alpha_bin, &poses_host[i]);
+    }
+    return PR_OK;
+}
+
+}  // extern "C"

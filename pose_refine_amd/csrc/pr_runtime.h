@@ -165,6 +165,7 @@ struct Options {
     int mesh_order = 1;              // asynchronous fused path: raster the library's spatially ordered copy of the triangle buffer (ensure_model_box); 0 = the caller's buffer
     int tight_box = 1;               // asynchronous fused path: pixel boxes from the mesh's projected vertices (pose_tight_box_kernel over the library's list of distinct vertices, ensure_model_box) instead of the projected corners of its box; 0 = the latter
     int box_bands = 1;               // asynchronous fused path: a hypothesis' depth box interleaves four image rows column by column (pose_box.h, band_box: a 64-byte segment is a 4x4-pixel patch, fewer atomic requests per raster wave instruction); 0 = row-major boxes.  Same results either way
+    int ppf_walk = 1;                // pr_ppf_vote: 1 = wave-cooperative bucket walk (a wavefront expands the buckets of its 64 scene pairs over its lanes), 0 = a lane per pair.  Same votes either way (profiles/ppf/README.md)
     int scene_cache = 1;             // keep the packed projective scene / kd traversal records of the latest scene between calls (pr_scene_invalidate)
 };
 extern Options opt;
@@ -769,6 +770,8 @@ struct Ctx {
     PinBuf h_cmp;                    // the records on their way to the caller, then the index table on its way to the device
     DevBuf pd_mats, pd_part, pd_rec; // pr_pose_distance: rows 0..2 of every A S_k (double) followed by those of every B (float); the partials of a launch; its records
     PinBuf h_pd_mats, h_pd_rec;      // the matrices on their way in, the records on their way out
+    DevBuf ppf_tmp, ppf_out;         // pr_ppf_*: bucket counts / cursors of a model build or the row counts and offsets of a scene sample; the peaks and references of a vote
+    PinBuf h_ppf;                    // ... and a build's or sample's total, a vote's peaks and references, on their way to the caller
     DevBuf vsd_rec;                  // pr_pose_vsd: the records of a chunk's pairs
     PinBuf h_vsd;                    // ... on their way to the caller
     DevBuf solid_far, solid_rec;     // pr_render_span / pr_pose_penetration: the far plane of the boxes in g->depth (same offsets); the P x P pair records

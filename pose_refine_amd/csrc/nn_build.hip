@@ -83,15 +83,15 @@ __global__ __launch_bounds__(256) void nn_records_kernel(const int4 *__restrict_
 //   the root box and rounded OUTWARDS (checked with the very dequantisation arithmetic the query uses).  A looser box can
 //   only make the search visit a subtree it could have skipped -- a subtree whose every point is farther than the current
 //   best -- so winners, distances and tie-breaks are those of the exact boxes.
-__global__ void nn_frame_kernel(const float4 *__restrict__ bmin, const float4 *__restrict__ bmax, uint32_t *__restrict__ info, float wide_margin)
+__global__ void nn_frame_kernel(const float4 *__restrict__ bmin, const float4 *__restrict__ bmax, NNInfo *__restrict__ info, float wide_margin)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const float lo[3] = { bmin[0].x, bmin[0].y, bmin[0].z }, hi[3] = { bmax[0].x, bmax[0].y, bmax[0].z };
     for (int a = 0; a < 3; ++a) {
         float sc = (hi[a] - lo[a]) / 65535.0f * 1.000001f;
         if (!(sc > 1e-30f)) sc = 1e-30f;
-        info[2 + a] = __float_as_uint(lo[a]);
-        info[5 + a] = __float_as_uint(sc);
+        info->qmin[a] = __float_as_uint(lo[a]);
+        info->qscale[a] = __float_as_uint(sc);
     }
     // the wide records use ONE scale for the three axes (the longest edge of the root box): a box test then is integer differences in
     // that unit and one sum of squares, no per-axis dequantisation (nn_tree_wide_kernel)
@@ -102,19 +102,19 @@ __global__ void nn_frame_kernel(const float4 *__restrict__ bmin, const float4 *_
     float edge = fmaxf(fmaxf(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]) + 2.0f * wide_margin;
     float wsc = edge / 65535.0f * 1.000001f;
     if (!(wsc > 1e-30f)) wsc = 1e-30f;
-    for (int a = 0; a < 3; ++a) info[16 + a] = __float_as_uint(lo[a] - wide_margin);      // ([12] is the scene fingerprint's word)
-    info[19] = __float_as_uint(wsc);
+    for (int a = 0; a < 3; ++a) info->wmin[a] = __float_as_uint(lo[a] - wide_margin);
+    info->wscale = __float_as_uint(wsc);
     // The integer box test of the walk relies on a unit being at least one ulp of the largest coordinate (then a stored corner sits within
     // half a unit of its real-number position and the query's interval, a unit wider on both sides, covers it): a scene far from the origin
-    // of its coordinate system with a tiny extent does not qualify and keeps the binary walk (info[20] = 0).
+    // of its coordinate system with a tiny extent does not qualify and keeps the binary walk (wide_frame_ok = 0).
     float cmax = 0.0f;
     for (int a = 0; a < 3; ++a) cmax = fmaxf(cmax, fmaxf(fabsf(lo[a] - wide_margin), fabsf(hi[a] + wide_margin)));
-    info[20] = (cmax * 1.1920929e-7f <= wsc && cmax < 1e30f) ? 1u : 0u;
-    info[1] = 1u;
+    info->wide_frame_ok = (cmax * 1.1920929e-7f <= wsc && cmax < 1e30f) ? 1u : 0u;
+    info->rec32_valid = 1u;
 }
 __global__ __launch_bounds__(256) void nn_records32_kernel(const int4 *__restrict__ topo, const float4 *__restrict__ bmin,
                                                            const float4 *__restrict__ bmax, uint32_t n_nodes, uint4 *__restrict__ rec32,
-                                                           uint2 *__restrict__ desc, uint32_t *__restrict__ info)
+                                                           uint2 *__restrict__ desc, NNInfo *__restrict__ info)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_nodes) return;
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void nn_records32_kernel(const int4 *__restric
             const int ch = ok ? (c ? t.z : t.y) : 0;
             const float lo[3] = { bmin[ch].x, bmin[ch].y, bmin[ch].z }, hi[3] = { bmax[ch].x, bmax[ch].y, bmax[ch].z };
             for (int a = 0; a < 3; ++a) {
-                const float qmin = __uint_as_float(info[2 + a]), qs = __uint_as_float(info[5 + a]);
+                const float qmin = __uint_as_float(info->qmin[a]), qs = __uint_as_float(info->qscale[a]);
                 float fl = floorf((lo[a] - qmin) / qs) - 1.0f;
                 uint32_t ql = fl > 0.0f ? (fl < 65535.0f ? (uint32_t)fl : 65535u) : 0u;
                 while (ql > 0 && !(nn_deq(ql, qmin, qs) <= lo[a])) --ql;
@@ -156,18 +156,18 @@ __global__ __launch_bounds__(256) void nn_records32_kernel(const int4 *__restric
     rec32[(size_t)i * 2] = make_uint4(w[0], w[1], w[2], w[3]);
     rec32[(size_t)i * 2 + 1] = make_uint4(w[4], w[5], w[6], w[7]);
     desc[i] = make_uint2(w[0], w[1]);
-    if (!ok) info[1] = 0u;                                       // any node that does not fit: the 64-byte records are used instead
+    if (!ok) info->rec32_valid = 0u;                             // any node that does not fit: the 64-byte records are used instead
 }
 
 // ---- wide records (query_nn_wide) ---------------------------------------------------------------------------------------------
 // Box of a binary node as 6 uint16 in the root-box frame, rounded outwards and checked with the dequantisation the query uses.
-__device__ __forceinline__ bool wide_quant_box(const float4 lo4, const float4 hi4, const uint32_t *__restrict__ info, uint32_t (&u)[3])
+__device__ __forceinline__ bool wide_quant_box(const float4 lo4, const float4 hi4, const NNInfo *__restrict__ info, uint32_t (&u)[3])
 {
     const float lo[3] = { lo4.x, lo4.y, lo4.z }, hi[3] = { hi4.x, hi4.y, hi4.z };
     uint32_t q[6];
     bool ok = true;
     for (int a = 0; a < 3; ++a) {
-        const float qmin = __uint_as_float(info[16 + a]), qs = __uint_as_float(info[19]);     // the wide records' frame: one scale for all axes
+        const float qmin = __uint_as_float(info->wmin[a]), qs = __uint_as_float(info->wscale);     // the wide records' frame: one scale for all axes
         const float fl = floorf((lo[a] - qmin) / qs) - 1.0f;
         uint32_t ql = fl > 0.0f ? (fl < 65535.0f ? (uint32_t)fl : 65535u) : 0u;
         while (ql > 0 && !(nn_deq_fma(ql, qmin, qs) <= lo[a])) --ql;
@@ -188,18 +188,18 @@ __device__ __forceinline__ bool wide_quant_box(const float4 lo4, const float4 hi
 // scan of those counts numbers the next level's wide nodes (deterministic: a wide node's index does not depend on timing) and the records'
 // references are rewritten; then (D) `layout`, once the last level is through.  `wq[k]` = binary root of wide node k, `cnt[k]` = its count.
 // The level's range lives in a control record double-buffered by level parity ({begin, end, bad}; level 0 is {0, 1, frame unusable}); a tree
-// whose links are out of order (child index <= parent index) or that does not fit sets `bad`, and info[8] stays 0.  The host launches eight
-// levels and the layout kernel before its one synchronisation; info[8] = 2 tells it that the tree is deeper (it launches eight more).
+// whose links are out of order (child index <= parent index) or that does not fit sets `bad`, and wide_state stays kWideNone.  The host launches eight
+// levels and the layout kernel before its one synchronisation; wide_state = kWideMoreLevels tells it that the tree is deeper (it launches eight more).
 constexpr uint32_t kWideChunk = 1024;
 struct WideLevel { uint32_t begin, end, bad, pad; };
-__device__ __forceinline__ WideLevel wide_level_state(const WideLevel *__restrict__ ctrl, uint32_t level, const uint32_t *__restrict__ info)
+__device__ __forceinline__ WideLevel wide_level_state(const WideLevel *__restrict__ ctrl, uint32_t level, const NNInfo *__restrict__ info)
 {
-    if (level == 0u) return WideLevel{ 0u, 1u, (info[1] == 1u && info[20] == 1u) ? 0u : 1u, 0u };
+    if (level == 0u) return WideLevel{ 0u, 1u, (info->rec32_valid == 1u && info->wide_frame_ok == 1u) ? 0u : 1u, 0u };
     return ctrl[level & 1u];
 }
 __global__ __launch_bounds__(256) void nn_wide_open_kernel(const int4 *__restrict__ topo, const float4 *__restrict__ bmin, const float4 *__restrict__ bmax, uint32_t n_nodes,
                                                            uint4 *__restrict__ wide, const uint32_t *__restrict__ wq, uint32_t *__restrict__ cnt, const WideLevel *__restrict__ ctrl,
-                                                           uint32_t *__restrict__ bad_flag, uint32_t *__restrict__ chunk_sum /* this level's */, uint32_t level, uint32_t n_points, const uint32_t *__restrict__ info)
+                                                           uint32_t *__restrict__ bad_flag, uint32_t *__restrict__ chunk_sum /* this level's */, uint32_t level, uint32_t n_points, const NNInfo *__restrict__ info)
 {
     const WideLevel st = wide_level_state(ctrl, level, info);
     if (st.bad || st.begin >= st.end) return;
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void nn_wide_open_kernel(const int4 *__restric
 }
 __global__ __launch_bounds__(1024) void nn_wide_number_kernel(uint4 *__restrict__ wide, uint32_t cap_wide, uint32_t *__restrict__ wq, const uint32_t *__restrict__ cnt,
                                                               const WideLevel *__restrict__ ctrl, WideLevel *__restrict__ ctrl_next, const uint32_t *__restrict__ bad_flag,
-                                                              const uint32_t *__restrict__ sums, uint32_t *__restrict__ sums_next, uint32_t level, const uint32_t *__restrict__ info)
+                                                              const uint32_t *__restrict__ sums, uint32_t *__restrict__ sums_next, uint32_t level, const NNInfo *__restrict__ info)
 {
     __shared__ uint32_t s_a[16], s_b[16];
     const WideLevel st = wide_level_state(ctrl, level, info);
@@ -313,11 +313,11 @@ __global__ __launch_bounds__(1024) void nn_wide_number_kernel(uint4 *__restrict_
 // (D) the layout the task walk reads (kWidePaired): a wide node is two 64-byte halves, one per lane of a task; a half holds its four
 // slots as two PAIRS -- per pair six words {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z}, each word = first slot | second slot << 16, so that
 // one packed 16-bit instruction works on both boxes -- followed by the four references.
-__global__ __launch_bounds__(256) void nn_wide_layout_kernel(uint4 *__restrict__ wide, const WideLevel *__restrict__ ctrl, uint32_t levels, uint32_t *__restrict__ info)
+__global__ __launch_bounds__(256) void nn_wide_layout_kernel(uint4 *__restrict__ wide, const WideLevel *__restrict__ ctrl, uint32_t levels, NNInfo *__restrict__ info)
 {
     const WideLevel st = wide_level_state(ctrl, levels, info);     // (levels >= 1: the record the last `number` launch wrote)
     const bool done = st.begin >= st.end, ok = !st.bad && done;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { info[8] = ok ? 1u : ((!st.bad && !done) ? 2u : 0u); info[9] = st.end; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { info->wide_state = ok ? kWideValid : ((!st.bad && !done) ? kWideMoreLevels : kWideNone); info->n_wide = st.end; }
     if (!ok) return;
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < st.end; k += gridDim.x * 256) {
         uint4 sl[8];
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void nn_wide_layout_kernel(uint4 *__restrict__
 
 // wide levels [first, first + count), then the layout; scratch = nn_wide_scratch_words(n_nodes) words
 hipError_t launch_nn_wide_levels(const int4 *topo, const float4 *bmin, const float4 *bmax, uint32_t n_nodes, uint32_t n_points, uint4 *wide, uint32_t *scratch,
-                                 uint32_t *info, uint32_t first, uint32_t count, hipStream_t s)
+                                 NNInfo *info, uint32_t first, uint32_t count, hipStream_t s)
 {
     const uint32_t cap = (uint32_t)nn_wide_capacity(n_nodes), chunks = (cap / kWideChunk + 3u) & ~1u;
     uint32_t *wq = scratch, *cnt = scratch + cap, *sums = scratch + ((2u * cap + 3u) & ~3u), *bad_flag = sums + 2u * chunks;      // (the control records 16-byte aligned: chunks is even)
@@ -362,15 +362,15 @@ hipError_t launch_nn_wide_levels(const int4 *topo, const float4 *bmin, const flo
 }
 
 hipError_t launch_build_nn_accel(const pr_kdnode *nodes, uint32_t n_nodes, const pr_vec3 *pcd, uint32_t n_points,
-                                 int4 *topo, float4 *bmin, float4 *bmax, float4 *pts, float4 *rec, uint4 *rec32, uint2 *desc, uint32_t *info, hipStream_t s,
+                                 int4 *topo, float4 *bmin, float4 *bmax, float4 *pts, float4 *rec, uint4 *rec32, uint2 *desc, NNInfo *info, hipStream_t s,
                                  float wide_margin)
 {
     const uint32_t m = (n_nodes > n_points) ? n_nodes : n_points;
     if (m == 0) return hipSuccess;
     hipLaunchKernelGGL(nn_accel_kernel, dim3((m + 255) / 256), dim3(256), 0, s, nodes, n_nodes, pcd, n_points, topo, bmin, bmax, pts);
-    hipError_t e = hipMemsetAsync(info, 0, 24 * sizeof(uint32_t), s);
+    hipError_t e = hipMemsetAsync(info, 0, sizeof(NNInfo), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(nn_records_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, s, topo, bmin, bmax, n_nodes, rec, info);
+    hipLaunchKernelGGL(nn_records_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, s, topo, bmin, bmax, n_nodes, rec, &info->depth);
     hipLaunchKernelGGL(nn_frame_kernel, dim3(1), dim3(64), 0, s, bmin, bmax, info, wide_margin);
     hipLaunchKernelGGL(nn_records32_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, s, topo, bmin, bmax, n_nodes, rec32, desc, info);
     return hipGetLastError();

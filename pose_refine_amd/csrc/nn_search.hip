@@ -678,17 +678,17 @@ __global__ __launch_bounds__(256, PR_WIDE_WAVES) void nn_tree_wide_kernel(IcpBat
     }
 }
 
-// scene points -> grid cells.  cell_idx starts at -1; a second claim on a cell, or a point outside the image, clears info[0].
+// scene points -> grid cells.  cell_idx starts at -1; a second claim on a cell, or a point outside the image, clears *usable.
 __global__ __launch_bounds__(256) void nn_grid_claim_kernel(const pr_vec3 *__restrict__ pcd, uint32_t n_points, SceneNNDev g, int32_t *__restrict__ cell_idx,
-                                                            uint32_t *__restrict__ info)
+                                                            uint32_t *__restrict__ usable)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_points) return;
     const pr_vec3 p = pcd[i];
     int px, py;
-    if (!(p.z > 0 && grid_pixel(g, p.x, p.y, p.z, px, py) && px >= 0 && px < (int)g.gw && py >= 0 && py < (int)g.gh)) { info[0] = 0u; return; }
+    if (!(p.z > 0 && grid_pixel(g, p.x, p.y, p.z, px, py) && px >= 0 && px < (int)g.gw && py >= 0 && py < (int)g.gh)) { *usable = 0u; return; }
     const int cell = py * (int)g.gw + px;
-    if (atomicCAS(&cell_idx[cell], -1, (int)i) != -1) info[0] = 0u;
+    if (atomicCAS(&cell_idx[cell], -1, (int)i) != -1) *usable = 0u;
 }
 // one coarser level: cell (bx, by) takes the occupied child cell nearest its centre (children = 4 x 4 cells of the finer level)
 __global__ __launch_bounds__(256) void nn_grid_coarsen_kernel(const float4 *__restrict__ fine, int fw, int fh, float4 *__restrict__ coarse, int cw, int ch)
@@ -756,17 +756,17 @@ hipError_t launch_nn_search(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_
 }
 
 hipError_t launch_build_nn_grid(const pr_vec3 *pcd, uint32_t n_points, uint32_t gw, uint32_t gh, float fx, float fy, float cx, float cy,
-                                int32_t *cell_idx, float4 *grid, uint32_t *info, hipStream_t s)
+                                int32_t *cell_idx, float4 *grid, uint32_t *usable, hipStream_t s)
 {
     const uint32_t cells = gw * gh;
     if (cells == 0 || n_points == 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(cell_idx, 0xff, sizeof(int32_t) * cells, s);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(info, 1, sizeof(uint32_t), s);                 // non-zero: usable so far
+    e = hipMemsetAsync(usable, 1, sizeof(uint32_t), s);                // non-zero: usable so far
     if (e != hipSuccess) return e;
     SceneNNDev g{};
     g.gw = gw; g.gh = gh; g.gfx = fx; g.gfy = fy; g.gcx = cx; g.gcy = cy;
-    hipLaunchKernelGGL(nn_grid_claim_kernel, dim3((n_points + 255) / 256), dim3(256), 0, s, pcd, n_points, g, cell_idx, info);
+    hipLaunchKernelGGL(nn_grid_claim_kernel, dim3((n_points + 255) / 256), dim3(256), 0, s, pcd, n_points, g, cell_idx, usable);
     hipLaunchKernelGGL(nn_grid_fill_kernel, dim3((cells + 255) / 256), dim3(256), 0, s, pcd, cell_idx, cells, grid);
     int fw = (int)gw, fh = (int)gh;
     float4 *fine = grid;

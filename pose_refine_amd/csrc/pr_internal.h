@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <vector>
 
@@ -182,6 +183,29 @@ struct BatchCheck {
     const uint32_t *fa, *fb, *fc; unsigned long long na, nb, nc; const uint32_t *fp_expected;
     uint32_t *flag;
 };
+// The caller's arrays a scene cache is derived from, as every fingerprint of them reads them: 32-bit words, IN THIS ORDER (the hashes mix the
+// array's ordinal in, so a site that listed them differently would find every batch stale).  A kd-tree scene's order is not its struct's.
+struct SceneSources {
+    const void *p[3]; size_t bytes[3];                           // unused entries: null, 0
+    const uint32_t *words(int k) const { return static_cast<const uint32_t *>(p[k]); }
+    unsigned long long n_words(int k) const { return (unsigned long long)(bytes[k] / 4); }
+};
+inline SceneSources scene_sources(const pr_scene_proj &s)
+{
+    const size_t b = (size_t)s.width * s.height * sizeof(pr_vec3);
+    return SceneSources{ { s.pcd, s.normal, nullptr }, { b, b, 0 } };
+}
+inline SceneSources scene_sources(const pr_scene_nn &s)
+{
+    const size_t b = (size_t)s.n_points * sizeof(pr_vec3);
+    return SceneSources{ { s.pcd, s.nodes, s.normal }, { b, (size_t)s.n_nodes * sizeof(pr_kdnode), b } };
+}
+// the scene half of a batch's check: the arrays, and the sampled fingerprint taken when their cached form was built (FpWords::sample, below)
+inline void check_sources(BatchCheck &chk, const SceneSources &src, const uint32_t *expected)
+{
+    chk.fa = src.words(0); chk.na = src.n_words(0); chk.fb = src.words(1); chk.nb = src.n_words(1); chk.fc = src.words(2); chk.nc = src.n_words(2);
+    chk.fp_expected = expected;
+}
 // Asynchronous path, option tight_box (pose_tight_box_kernel): bbox[i], the loose box the host uploaded, overwritten by its intersection with the
 // hull of the projected vertices `verts` ({x, y, z, 0}: the mesh's distinct vertices); then, per sub-batch, the packed offsets of those boxes.
 hipError_t launch_tight_boxes(const float4 *verts, uint32_t n_verts, const pr_mat4 *poses_dev, uint32_t n_poses, const pr_mat4 &proj,
@@ -354,11 +378,11 @@ hipError_t launch_robust_terms_grid(pr_vec3 *cloud, uint32_t n, const float *upd
 // one iteration of pose_iteration_wave per hypothesis on given sums (pr_debug_pose_iteration): one wavefront each
 hipError_t launch_pose_iteration_debug(const float *sums, const uint32_t *n_points, uint32_t n, pr_criteria crit, uint32_t iter, pr_result *state,
                                        float *update, uint32_t *finished, hipStream_t s);
-// info[0] = 1 when every scene point owns a grid cell (the grid may be used), 0 otherwise
+// *usable (one device word of its own, no part of NNInfo) = non-zero when every scene point owns a grid cell (the grid may be used), 0 otherwise
 // grid: gw*gh cells followed by the three pyramid levels (nn_grid_cells(gw, gh) cells in all)
 size_t nn_grid_cells(uint32_t gw, uint32_t gh);
 hipError_t launch_build_nn_grid(const pr_vec3 *pcd, uint32_t n_points, uint32_t gw, uint32_t gh, float fx, float fy, float cx, float cy,
-                                int32_t *cell_idx, float4 *grid, uint32_t *info, hipStream_t s);
+                                int32_t *cell_idx, float4 *grid, uint32_t *usable, hipStream_t s);
 hipError_t launch_icp_finalize(const float *partial, const PoseMeta *meta, uint32_t nblk,
                                uint32_t steps, float *sums, uint32_t n_poses, hipStream_t s);
 // PR_SOLVE_DEVICE: finalize + convergence test + 6x6 solve + state update in one kernel
@@ -390,23 +414,43 @@ hipError_t launch_nn_gather(const T *depth, uint32_t W, uint32_t H, float fx, fl
 template <typename T>
 hipError_t launch_scene_proj_prepare(const T *depth, uint32_t W, uint32_t H, float fx, float fy, float cx, float cy, pr_vec3 *pcd, pr_vec3 *normal, hipStream_t s);
 hipError_t launch_raw2depth_mask(const int32_t *raw, size_t n, uint16_t *depth16, uint8_t *mask8, hipStream_t s);
-// sampled hash of up to three arrays (null = absent): check = false stores it in *expected, check = true sets *flag = 1 if it differs
-hipError_t launch_scene_fingerprint(const void *a, size_t a_bytes, const void *b, size_t b_bytes, const void *c, size_t c_bytes,
-                                    uint32_t *expected, uint32_t *flag, bool check, hipStream_t s);
-hipError_t launch_scene_fingerprint_full(const void *a, size_t a_bytes, const void *b, size_t b_bytes, const void *c, size_t c_bytes, uint32_t *sum, hipStream_t s);
+// The fingerprints a scene cache keeps of its source arrays, the same four words in both caches (NNInfo::fp, ProjTail::fp of pr_runtime.h).
+// sample: 4096 words per array, taken at the build (launch_scene_fingerprint); every asynchronous batch compares it inside its raster launch
+// (BatchCheck::fp_expected).  full: every word, taken at the build; call: the same of a synchronous call's cache hit (launch_scene_fingerprint_full),
+// read back beside `full` (fingerprint_differs, pr_scene.cpp).
+struct FpWords { uint32_t sample, reserved, full, call; };
+static_assert(sizeof(FpWords) == 16 && offsetof(FpWords, call) == offsetof(FpWords, full) + 4, "FpWords: four words, full and call side by side");
+hipError_t launch_scene_fingerprint(const SceneSources &src, uint32_t *sample, hipStream_t s);
+hipError_t launch_scene_fingerprint_full(const SceneSources &src, uint32_t *sum, hipStream_t s);
 hipError_t launch_pack_proj_scene(const pr_vec3 *pcd, const pr_vec3 *normal, float4 *rec, size_t n, float *colf, float *rowf,
                                   uint32_t width, uint32_t height, float fx, float fy, float cx, float cy, uint32_t tl_x, uint32_t tl_y,
                                   uint32_t *exact, hipStream_t s);
-// info[0] = tree depth, info[1] = 1 when the 32-byte records are valid, info[2..7] = qmin[3], qscale[3] (float bits)
-// wide records (nn_wide_build: launch_nn_wide_levels): info[8] = 1 when they are valid, 2 when the tree has more wide levels than were launched,
-// info[9] = number of wide nodes; wide: nn_wide_capacity(n_nodes) lines of 128 bytes, scratch: nn_wide_scratch_words(n_nodes) words
+// The 24 control words of a set of kd-tree records: written by nn_build.hip's kernels, read back whole by the host (NNDerived::info), handed
+// out as 24 words by pr_debug_nn_records -- the positions are part of that interface.  Floats are kept as bit patterns.
+enum : uint32_t { kWideNone = 0, kWideValid = 1, kWideMoreLevels = 2 };     // NNInfo::wide_state; more levels: the tree has more wide levels than were launched
+struct NNInfo {
+    uint32_t depth;             // [0] longest root-to-node path; >= 0x7fffffff: the links are inconsistent (nn_records_kernel)
+    uint32_t rec32_valid;       // [1] 1: the 32-byte records express the tree
+    uint32_t qmin[3], qscale[3];   // [2..7] their frame
+    uint32_t wide_state;        // [8] kWideNone / kWideValid / kWideMoreLevels
+    uint32_t n_wide;            // [9] wide nodes
+    uint32_t reserved0[2];
+    FpWords fp;                 // [12..15]
+    uint32_t wmin[3], wscale;   // [16..19] frame of the wide records
+    uint32_t wide_frame_ok;     // [20] 1: a unit of that frame is at least one ulp of the largest coordinate -- the wide walk may run (nn_frame_kernel)
+    uint32_t reserved1[3];
+};
+static_assert(sizeof(NNInfo) == 96 && offsetof(NNInfo, depth) == 0 && offsetof(NNInfo, rec32_valid) == 4 && offsetof(NNInfo, qmin) == 8 &&
+              offsetof(NNInfo, qscale) == 20 && offsetof(NNInfo, wide_state) == 32 && offsetof(NNInfo, n_wide) == 36 && offsetof(NNInfo, fp) == 48 &&
+              offsetof(NNInfo, wmin) == 64 && offsetof(NNInfo, wscale) == 76 && offsetof(NNInfo, wide_frame_ok) == 80, "NNInfo: the documented word positions");
+// wide: nn_wide_capacity(n_nodes) lines of 128 bytes, scratch: nn_wide_scratch_words(n_nodes) words
 inline size_t nn_wide_capacity(uint32_t n_nodes) { return (size_t)n_nodes / 2 + 2; }
 inline size_t nn_wide_scratch_words(uint32_t n_nodes) { const size_t cap = nn_wide_capacity(n_nodes); return 2 * cap + 4 + 2 * (cap / 1024 + 4) + 4 + 8; }   // wq, cnt, chunk sums x 2, flag, control records x 2
 hipError_t launch_build_nn_accel(const pr_kdnode *nodes, uint32_t n_nodes, const pr_vec3 *pcd, uint32_t n_points,
-                                 int4 *topo, float4 *bmin, float4 *bmax, float4 *pts, float4 *rec, uint4 *rec32, uint2 *desc, uint32_t *info, hipStream_t s,
-                                 float wide_margin = 0.0f);   // wide_margin: how far beyond the root box the wide records' frame reaches (the acceptance radius)
+                                 int4 *topo, float4 *bmin, float4 *bmax, float4 *pts, float4 *rec, uint4 *rec32, uint2 *desc, NNInfo *info, hipStream_t s,
+                                 float wide_margin = 0.0f);   // clears *info first; wide_margin: how far beyond the root box the wide records' frame reaches (the acceptance radius)
 hipError_t launch_nn_wide_levels(const int4 *topo, const float4 *bmin, const float4 *bmax, uint32_t n_nodes, uint32_t n_points, uint4 *wide, uint32_t *scratch,
-                                 uint32_t *info, uint32_t first, uint32_t count, hipStream_t s);
+                                 NNInfo *info, uint32_t first, uint32_t count, hipStream_t s);
 
 }  // namespace prk
 

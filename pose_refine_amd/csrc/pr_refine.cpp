@@ -1004,21 +1004,10 @@ prk::BatchCheck batch_check(const Slot &sl, const RefineJob &job, const SceneSel
     chk.caller = job.mesh.tris; chk.mesh_hash = g->mesh_hash;
     chk.flag = flag_dev;
     if (!opt.scene_cache) return chk;
-    if (job.scene_kind == PR_SCENE_NN) {
-        const pr_scene_nn *sn = &job.sn;
-        chk.fa = reinterpret_cast<const uint32_t *>(sn->pcd); chk.na = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
-        chk.fb = reinterpret_cast<const uint32_t *>(sn->nodes); chk.nb = (size_t)sn->n_nodes * sizeof(pr_kdnode) / 4;
-        chk.fc = reinterpret_cast<const uint32_t *>(sn->normal); chk.nc = (size_t)sn->n_points * sizeof(pr_vec3) / 4;
-        chk.fp_expected = g->nn_sets[sc.nn_set].nndepth.as<uint32_t>() + 12;
-    } else if (sl.packed.valid) {
-        const pr_scene_proj *sp = &job.sp.view;
-        const size_t n = (size_t)sp->width * sp->height;
-        const size_t tables = ((sp->width + sp->height) * sizeof(float) + 15) & ~(size_t)15;
-        const uint32_t *exact_dev = reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(sl.packed.rec.as<float4>() + n) + tables);
-        chk.fa = reinterpret_cast<const uint32_t *>(sp->pcd); chk.na = n * sizeof(pr_vec3) / 4;
-        chk.fb = reinterpret_cast<const uint32_t *>(sp->normal); chk.nb = n * sizeof(pr_vec3) / 4;
-        chk.fp_expected = exact_dev + 1;
-    }
+    if (job.scene_kind == PR_SCENE_NN)
+        prk::check_sources(chk, prk::scene_sources(job.sn), &g->nn_sets[sc.nn_set].nndepth.as<prk::NNInfo>()->fp.sample);
+    else if (sl.packed.valid)
+        prk::check_sources(chk, prk::scene_sources(job.sp.view), &sl.packed.at<ProjTail>(packed_layout(job.sp.view.width, job.sp.view.height).tail)->fp.sample);
     return chk;
 }
 // What the phases of one asynchronous batch share: the batch, its plan and where its parts live on the device.

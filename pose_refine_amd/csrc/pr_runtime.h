@@ -176,8 +176,20 @@ extern Options opt;
 inline uint32_t pose_groups_for(int scene_kind) { (void)scene_kind; return opt.pose_groups > 0 ? (uint32_t)opt.pose_groups : 2u; }
 
 // packed projective scene (one 16-byte record per pixel + the two back-projection tables) of the latest scene it was built for
+// Its one allocation, in bytes: [w * h] float4 | colf[w] | rowf[h] | (on 16 bytes) ProjTail.  No HIP call in here: tools/job_sanitize.cpp checks it.
+struct ProjTail { uint32_t exact; prk::FpWords fp; uint32_t pad[3]; };   // exact: the pcd array is what dep2pcd produces (pack_proj_scene_kernel); fp: of pcd and normal
+static_assert(sizeof(ProjTail) == 32, "ProjTail: the 32 bytes behind the tables");
+struct PackedLayout { size_t colf, rowf, tail, bytes; };
+inline PackedLayout packed_layout(size_t w, size_t h)
+{
+    PackedLayout l{};
+    l.colf = w * h * sizeof(float4); l.rowf = l.colf + w * sizeof(float);
+    l.tail = l.colf + (((w + h) * sizeof(float) + 15) & ~(size_t)15); l.bytes = l.tail + sizeof(ProjTail);
+    return l;
+}
 struct PackedCache {
-    DevBuf rec;                      // [n] float4, colf[w], rowf[h], then five words: exact flag, sampled fingerprint of the source arrays, its verdict, full fingerprint, a call's full fingerprint
+    DevBuf rec;                      // as packed_layout(w, h) lays it out
+    template <class T> T *at(size_t offset) const { return reinterpret_cast<T *>(static_cast<unsigned char *>(rec.p) + offset); }
     const void *pcd = nullptr, *normal = nullptr;
     uint64_t w = 0, h = 0; float k[4] = { 0, 0, 0, 0 }; uint32_t tl[2] = { 0, 0 };
     uint64_t gen = 0;
@@ -639,6 +651,36 @@ inline uint32_t release_pass_for(size_t n_tris, uint32_t nq, uint32_t cloud_hint
     if (scene_kind == PR_SCENE_NN) auto_overlap = 0u;
     return std::min(last_pass, auto_overlap);
 }
+// ---- kd-tree scenes: the two policies of make_scene (pr_scene.cpp).  No HIP call in here: tools/job_sanitize.cpp runs them under ASan / UBSan. ----
+// Which of the sets of derived records a scene takes.  The caller states per set: valid; hit = it holds this scene and nothing says it is stale;
+// same_arrays = it was derived from this scene's pcd and nodes arrays; in_flight = a batch in flight reads it; used = the clock of its latest use.
+// In this order: the first hit; else a victim -- the first valid set of the same arrays (this scene, rewritten), the first invalid one, the least
+// recently used one that no batch in flight reads, the least recently used of all (its readers then drain first).
+struct NNSetFacts { bool valid, hit, same_arrays, in_flight; uint64_t used; };
+struct NNSetPick { int set; bool hit; };
+inline NNSetPick pick_nn_set(const NNSetFacts *f, int n)
+{
+    for (int i = 0; i < n; ++i) if (f[i].hit) return { i, true };
+    for (int i = 0; i < n; ++i) if (f[i].valid && f[i].same_arrays) return { i, false };
+    for (int i = 0; i < n; ++i) if (!f[i].valid) return { i, false };
+    int pick = -1;
+    for (int i = 0; i < n; ++i) if (!f[i].in_flight && (pick < 0 || f[i].used < f[pick].used)) pick = i;
+    if (pick < 0) { pick = 0; for (int i = 1; i < n; ++i) if (f[i].used < f[pick].used) pick = i; }
+    return { pick, false };
+}
+// How a set's records are searched, from its control words and the options nn_lds_nodes, nn_lds_records, nn_stack, nn_compact, nn_wide.
+// Pending far children on the stack never exceed the tree depth; deeper trees use the stackless walk.  The caller has refused an inconsistent tree (depth >= 0x7fffffff).
+struct NNRoute { uint32_t lds_nodes, stack_depth; bool compact, wide; };   // compact: the 32-byte records (SceneNNDev::rec32); wide: the wide records as well
+inline NNRoute nn_route(const prk::NNInfo &info, uint32_t n_nodes, int nn_lds_nodes, int nn_lds_records, int nn_stack, int nn_compact, int nn_wide)
+{
+    NNRoute r{};
+    r.lds_nodes = std::min<uint32_t>(std::min((uint32_t)std::max(0, nn_lds_nodes), n_nodes), 8192);      // <= 128 KiB of LDS
+    if (nn_stack) r.stack_depth = (info.depth <= 16) ? 16u : ((info.depth <= 24) ? 24u : 0u);
+    if (r.stack_depth) r.lds_nodes = std::min<uint32_t>({ (uint32_t)std::max(0, nn_lds_records), n_nodes, (65536u - r.stack_depth * 2048u) / 64u });   // stacks + records <= 64 KiB
+    r.compact = r.stack_depth && nn_compact && info.rec32_valid == 1u;
+    r.wide = r.compact && nn_wide && info.wide_state == prk::kWideValid && info.n_wide > 0u;
+    return r;
+}
 // ---- profiling spans: pooled HIP events around launches, turned into the context's accounts -------------------------------------------
 // One recorder for the context's own stream (SpanGuard) and one per asynchronous slot (a TIMED batch, option profile = 3).  A span is a start /
 // stop pair in enqueue order; a kd-tree pass may carry three marks between its four kernels.  drain() -- once the stream has been waited for --
@@ -726,7 +768,7 @@ constexpr int kNNSets = 2;
 struct NNDerived {
     DevBuf topo, bmin, bmax, pts, nnrec, nnrec32, nndesc, nnwide, nnwq, nndepth, nn_cells, nn_grid;
     const void *pcd = nullptr, *normal = nullptr, *nodes = nullptr; uint32_t n_points = 0, n_nodes = 0; uint64_t gen = 0; bool valid = false;
-    uint32_t info[24] = { 0 };
+    prk::NNInfo info{};                                          // the host's copy of the control words in nndepth
     float frame_margin = 0.0f;                                   // the acceptance radius (x 1.01) the wide records' frame was built for: a larger radius rebuilds
     bool grid_valid = false, grid_usable = false; uint32_t gw = 0, gh = 0; float gk[4] = { 0, 0, 0, 0 };
     uint64_t used = 0;                                           // Ctx::nn_clock of the latest call that chose this set
@@ -963,8 +1005,6 @@ constexpr uint32_t kCounterPasses = 64;
 struct Camera { uint32_t w = 0, h = 0; float fx = 0, fy = 0, cx = 0, cy = 0; };
 
 // ---- functions of the other translation units (pr_scene / pr_icp / pr_refine / pr_comm / pr_context) ---------------------------------
-int fingerprint_differs(const void *a, size_t ab, const void *b, size_t bb, const void *c, size_t cb, uint32_t *slot, hipStream_t st, bool &differs);
-int ensure_packed(PackedCache &pc, const pr_scene_proj &s, uint32_t tl_x, uint32_t tl_y, hipStream_t st, bool verify_now = false);
 int make_scene(int kind, const void *scene, bool want_packed, SceneSel &out, PackedCache *pc_in = nullptr, hipStream_t st = nullptr, const Camera *cam = nullptr,
                bool verify_now = true);
 int kd_build_dev(pr_vec3 *pcd, pr_vec3 *nrm, uint32_t n, int max_leaf, pr_kdnode *nodes, size_t cap, uint32_t *n_nodes);

@@ -7,206 +7,206 @@ namespace prr {
 // (option scene_cache, WriteLog above), rebuilt otherwise.  A rebuild also learns (one 4-byte read-back) whether the pcd array
 // is exactly what dep2pcd produces -- only then may the packed form stand in for it.
 // Synchronous callers (pr_icp_*, the synchronous fused path -- everything the C++ adapters of the reference's API reach) check a cache hit on the
-// spot, and since round 6 against a fingerprint of EVERY word of the source arrays (`slot[2]`, taken when the cache was built; `slot[3]` is this
+// spot, and since round 6 against a fingerprint of EVERY word of the source arrays (`fp->full`, taken when the cache was built; `fp->call` is this
 // call's): the reference reads the caller's arrays at every call (depth_scene.h:29-48), so an in-place edit through a pointer the adapters handed
 // out must be seen even when nobody announced it.  ~20 us per call; the asynchronous path compares the 4096-word SAMPLE
-// (`slot[0]`, verdict in `slot[1]`) inside its raster launch and documents pr_invalidate for edits the sample cannot see.
-int fingerprint_differs(const void *a, size_t ab, const void *b, size_t bb, const void *c, size_t cb, uint32_t *slot, hipStream_t st, bool &differs)
+// (`fp->sample`) inside its raster launch, which raises the batch's flag (BatchCheck), and documents pr_invalidate for edits the sample cannot see.
+static int fingerprint_differs(const prk::SceneSources &src, prk::FpWords *fp, hipStream_t st, bool &differs)
 {
-    HIP_TRY(prk::launch_scene_fingerprint_full(a, ab, b, bb, c, cb, slot + 3, st));
+    HIP_TRY(prk::launch_scene_fingerprint_full(src, &fp->call, st));
     // both words come back through a kernel's stores into pinned memory (no copy command on the per-batch path: see drive_host's result block)
     uint32_t v[2] = { 0u, 1u };
-    PR_TRY(read_back_words(slot + 2, v, 2, st));
+    PR_TRY(read_back_words(&fp->full, v, 2, st));                 // full, call
     differs = v[0] != v[1];
     return PR_OK;
 }
-int ensure_packed(PackedCache &pc, const pr_scene_proj &s, uint32_t tl_x, uint32_t tl_y, hipStream_t st, bool verify_now)
+static int ensure_packed(PackedCache &pc, const pr_scene_proj &s, uint32_t tl_x, uint32_t tl_y, hipStream_t st, bool verify_now)
 {
     const size_t n = (size_t)s.width * s.height;
     const float k[4] = { s.K[0], s.K[4], s.K[2], s.K[5] };
+    const prk::SceneSources src = prk::scene_sources(s);
+    const PackedLayout lay = packed_layout(s.width, s.height);
     const bool same = pc.valid && pc.pcd == s.pcd && pc.normal == s.normal && pc.w == s.width && pc.h == s.height &&
                       std::memcmp(pc.k, k, sizeof k) == 0 && pc.tl[0] == tl_x && pc.tl[1] == tl_y;
-    if (same && opt.scene_cache && !g_writes.written_since(pc.gen, s.pcd, n * sizeof(pr_vec3)) &&
-        !g_writes.written_since(pc.gen, s.normal, n * sizeof(pr_vec3))) {
+    if (same && opt.scene_cache && !g_writes.written_since(pc.gen, s.pcd, src.bytes[0]) && !g_writes.written_since(pc.gen, s.normal, src.bytes[1])) {
         bool stale = false;
-        if (verify_now) {
-            const size_t tb = ((s.width + s.height) * sizeof(float) + 15) & ~(size_t)15;
-            uint32_t *ex = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(pc.rec.as<float4>() + n) + tb);
-            PR_TRY(fingerprint_differs(s.pcd, n * sizeof(pr_vec3), s.normal, n * sizeof(pr_vec3), nullptr, 0, ex + 1, st, stale));
-        }
+        if (verify_now) PR_TRY(fingerprint_differs(src, &pc.at<ProjTail>(lay.tail)->fp, st, stale));
         if (!stale) { pc.gen = g_writes.now(); return PR_OK; }
     }
     pc.valid = false;
     const uint64_t gen = g_writes.now();
-    const size_t tables = ((s.width + s.height) * sizeof(float) + 15) & ~(size_t)15;
-    PR_TRY(pc.rec.ensure(n * sizeof(float4) + tables + 32));      // behind the tables: [0] exact flag [1] sampled fingerprint [2] its verdict (asynchronous check) [3] full fingerprint [4] a call's full fingerprint
-    float *colf = reinterpret_cast<float *>(pc.rec.as<float4>() + n);
-    float *rowf = colf + s.width;
-    uint32_t *exact_dev = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(colf) + tables);
-    HIP_TRY(prk::launch_pack_proj_scene(s.pcd, s.normal, pc.rec.as<float4>(), n, colf, rowf, (uint32_t)s.width, (uint32_t)s.height,
-                                        k[0], k[1], k[2], k[3], tl_x, tl_y, exact_dev, st));
-    HIP_TRY(prk::launch_scene_fingerprint(s.pcd, n * sizeof(pr_vec3), s.normal, n * sizeof(pr_vec3), nullptr, 0, exact_dev + 1, nullptr, false, st));
-    HIP_TRY(prk::launch_scene_fingerprint_full(s.pcd, n * sizeof(pr_vec3), s.normal, n * sizeof(pr_vec3), nullptr, 0, exact_dev + 3, st));
+    PR_TRY(pc.rec.ensure(lay.bytes));
+    ProjTail *tail = pc.at<ProjTail>(lay.tail);
+    HIP_TRY(prk::launch_pack_proj_scene(s.pcd, s.normal, pc.rec.as<float4>(), n, pc.at<float>(lay.colf), pc.at<float>(lay.rowf), (uint32_t)s.width, (uint32_t)s.height,
+                                        k[0], k[1], k[2], k[3], tl_x, tl_y, &tail->exact, st));
+    HIP_TRY(prk::launch_scene_fingerprint(src, &tail->fp.sample, st));
+    HIP_TRY(prk::launch_scene_fingerprint_full(src, &tail->fp.full, st));
     uint32_t exact = 0;
-    PR_TRY(read_back_words(exact_dev, &exact, 1, st));
+    PR_TRY(read_back_words(&tail->exact, &exact, 1, st));
     pc.pcd = s.pcd; pc.normal = s.normal; pc.w = s.width; pc.h = s.height; std::memcpy(pc.k, k, sizeof k); pc.tl[0] = tl_x; pc.tl[1] = tl_y;
     pc.gen = gen; pc.exact = exact != 0; pc.valid = true;
     return PR_OK;
 }
 
-void drain_all_slots();
+// ---- make_scene by scene kind ---------------------------------------------------------------------------------------------------------
+// projective, whole frame or crop: the caller's arrays, and (want_packed) their packed copy in `pc`, built or verified on `st`
+static int scene_proj(int kind, const void *scene, bool want_packed, SceneSel &out, PackedCache &pc, hipStream_t st, bool verify_now)
+{
+    const pr_scene_proj *s = static_cast<const pr_scene_proj *>(scene);       // pr_scene_proj_crop starts with the plain view
+    if (!s || !s->pcd || !s->normal || s->width == 0 || s->height == 0) { set_error("invalid pr_scene_proj"); return PR_ERR_INVALID; }
+    if (s->width > 0x7fffffffull || s->height > 0x7fffffffull) { set_error("pr_scene_proj: frame too large"); return PR_ERR_INVALID; }
+    uint32_t tl_x = 0, tl_y = 0;
+    if (kind == PR_SCENE_PROJ_CROP) { const pr_scene_proj_crop *c = static_cast<const pr_scene_proj_crop *>(scene); tl_x = c->tl_x; tl_y = c->tl_y; }
+    out.kind = PR_SCENE_PROJ;
+    out.aos = prk::SceneProjAoS{ (uint32_t)s->width, (uint32_t)s->height, s->max_dist_diff, s->K[0], s->K[4], s->K[2], s->K[5],
+                                 (float)tl_x, (float)tl_y, s->pcd, s->normal };
+    out.packed = false;
+    if (!want_packed) return PR_OK;
+    PR_TRY(ensure_packed(pc, *s, tl_x, tl_y, st, verify_now));
+    if (!pc.exact) return PR_OK;                                // the caller's pcd is not dep2pcd's -- use the arrays as they are
+    const PackedLayout lay = packed_layout(s->width, s->height);
+    out.packed = true;
+    out.pk = prk::SceneProjPacked{ (uint32_t)s->width, (uint32_t)s->height, s->max_dist_diff, s->K[0], s->K[4], s->K[2], s->K[5],
+                                   (float)tl_x, (float)tl_y, pc.rec.as<float4>(), pc.at<float>(lay.colf), pc.at<float>(lay.rowf) };
+    return PR_OK;
+}
+
+// kd-tree scenes.  Everything below runs on g->stream, whatever stream the caller named.
+static bool set_in_flight(int set) { for (Slot &o : g->slots) if (o.pending && !o.delivered && o.nn_set == set) return true; return false; }
+static void drain_readers(int set) { for (Slot &o : g->slots) if (o.pending && !o.delivered && o.nn_set == set) slot_drain(o); }
+// the records of `s` into set `nc`: the traversal arrays (which clears the control words), then the fingerprints, then the wide records
+static int derive_nn_set(NNDerived &nc, const pr_scene_nn &s)
+{
+    nc.valid = false; nc.grid_valid = false;
+    const uint64_t gen = g_writes.now();
+    const float margin = s.max_dist_diff * 1.01f;
+    PR_TRY(nc.topo.ensure((size_t)s.n_nodes * sizeof(int4)));
+    PR_TRY(nc.bmin.ensure((size_t)s.n_nodes * sizeof(float4)));
+    PR_TRY(nc.bmax.ensure((size_t)s.n_nodes * sizeof(float4)));
+    PR_TRY(nc.pts.ensure(((size_t)s.n_points + 16u) * sizeof(float4)));   // + 16: a leaf task of the walk reads its ten slots whatever the leaf holds (nn_tree_wide_kernel)
+    PR_TRY(nc.nnrec.ensure((size_t)s.n_nodes * 4 * sizeof(float4)));
+    PR_TRY(nc.nndepth.ensure(sizeof(prk::NNInfo)));
+    PR_TRY(nc.nnrec32.ensure((size_t)s.n_nodes * 2 * sizeof(uint4)));
+    PR_TRY(nc.nndesc.ensure((size_t)s.n_nodes * sizeof(uint2)));
+    // wide records: one 128-byte line per wide node
+    PR_TRY(nc.nnwide.ensure(prk::nn_wide_capacity(s.n_nodes) * 128));
+    PR_TRY(nc.nnwq.ensure(prk::nn_wide_scratch_words(s.n_nodes) * sizeof(uint32_t)));
+    prk::NNInfo *info = nc.nndepth.as<prk::NNInfo>();
+    const prk::SceneSources src = prk::scene_sources(s);
+    HIP_TRY(prk::launch_build_nn_accel(s.nodes, s.n_nodes, s.pcd, s.n_points, nc.topo.as<int4>(), nc.bmin.as<float4>(), nc.bmax.as<float4>(), nc.pts.as<float4>(),
+                                       nc.nnrec.as<float4>(), nc.nnrec32.as<uint4>(), nc.nndesc.as<uint2>(), info, g->stream, margin));
+    HIP_TRY(prk::launch_scene_fingerprint(src, &info->fp.sample, g->stream));
+    HIP_TRY(prk::launch_scene_fingerprint_full(src, &info->fp.full, g->stream));
+    // the wide records, eight levels per synchronisation (8^8 wide nodes: deeper only for a lopsided tree)
+    for (uint32_t level = 0; ; level += 8) {
+        HIP_TRY(prk::launch_nn_wide_levels(nc.topo.as<int4>(), nc.bmin.as<float4>(), nc.bmax.as<float4>(), s.n_nodes, s.n_points, nc.nnwide.as<uint4>(),
+                                           nc.nnwq.as<uint32_t>(), info, level, 8, g->stream));
+        PR_TRY(read_back_words(info, &nc.info, (uint32_t)(sizeof nc.info / sizeof(uint32_t)), g->stream));
+        if (nc.info.wide_state != prk::kWideMoreLevels) break;
+        if (level + 8 >= 64) { nc.info.wide_state = prk::kWideNone; break; }    // (as before: more than 64 wide levels -> the binary records)
+    }
+    nc.pcd = s.pcd; nc.normal = s.normal; nc.nodes = s.nodes; nc.n_points = s.n_points; nc.n_nodes = s.n_nodes; nc.gen = gen; nc.valid = true;
+    nc.frame_margin = margin;
+    return PR_OK;
+}
+// Pixel grid of the scene points under the hypotheses' camera (fused paths), or under the camera the scene says it was made with: built into set
+// `set` unless it holds that camera's.  Usable when every scene point owns a cell -- a Scene_nn made from a depth image with these
+// intrinsics -- else the tree alone.
+static int ensure_nn_grid(int set, const pr_scene_nn &s, const Camera &cam)
+{
+    NNDerived &nc = g->nn_sets[set];
+    const float gk[4] = { cam.fx, cam.fy, cam.cx, cam.cy };
+    if (nc.grid_valid && nc.gw == cam.w && nc.gh == cam.h && std::memcmp(nc.gk, gk, sizeof gk) == 0) return PR_OK;
+    drain_readers(set);
+    const size_t cells = (size_t)cam.w * cam.h;
+    PR_TRY(nc.nn_cells.ensure(cells * sizeof(int32_t) + 16));
+    PR_TRY(nc.nn_grid.ensure(prk::nn_grid_cells(cam.w, cam.h) * sizeof(float4)));
+    uint32_t *flag = reinterpret_cast<uint32_t *>(nc.nn_cells.as<int32_t>() + cells);
+    HIP_TRY(prk::launch_build_nn_grid(s.pcd, s.n_points, cam.w, cam.h, gk[0], gk[1], gk[2], gk[3], nc.nn_cells.as<int32_t>(), nc.nn_grid.as<float4>(), flag, g->stream));
+    uint32_t usable = 0;
+    PR_TRY(read_back_words(flag, &usable, 1, g->stream));
+    nc.grid_valid = true; nc.grid_usable = usable != 0; nc.gw = cam.w; nc.gh = cam.h; std::memcpy(nc.gk, gk, sizeof gk);
+    return PR_OK;
+}
+// what the searches take (SceneSel::nn): the set's arrays as the route uses them; the grid's fields stay empty
+static prk::SceneNNDev nn_dev(const NNDerived &nc, const pr_scene_nn &s, const NNRoute &route)
+{
+    prk::SceneNNDev d{};
+    d.max_dist_diff = s.max_dist_diff;
+    d.topo = nc.topo.as<int4>(); d.bmin = nc.bmin.as<float4>(); d.bmax = nc.bmax.as<float4>(); d.pts = nc.pts.as<float4>();
+    d.pcd = s.pcd; d.normal = s.normal; d.n_nodes = s.n_nodes;
+    d.lds_nodes = route.lds_nodes; d.rec = nc.nnrec.as<float4>(); d.stack_depth = route.stack_depth; d.desc = nc.nndesc.as<uint2>();
+    if (route.compact) {
+        d.rec32 = nc.nnrec32.as<uint4>();
+        std::memcpy(d.qmin, nc.info.qmin, sizeof d.qmin); std::memcpy(d.qscale, nc.info.qscale, sizeof d.qscale);
+    }
+    if (route.wide) {
+        d.wide = nc.nnwide.as<uint4>(); d.n_wide = nc.info.n_wide;
+        std::memcpy(d.wmin, nc.info.wmin, sizeof d.wmin); std::memcpy(&d.wscale, &nc.info.wscale, sizeof d.wscale);
+    }
+    return d;
+}
+static int scene_nn(const void *scene, SceneSel &out, const Camera *cam, bool verify_now)
+{
+    const pr_scene_nn *s = static_cast<const pr_scene_nn *>(scene);
+    if (!s || !s->pcd || !s->normal || !s->nodes || s->n_nodes == 0 || s->n_points == 0) { set_error("invalid pr_scene_nn"); return PR_ERR_INVALID; }
+    const prk::SceneSources src = prk::scene_sources(*s);
+    // which of the sets of derived records (pick_nn_set has the rules)
+    NNSetFacts facts[kNNSets];
+    for (int i = 0; i < kNNSets; ++i) {
+        const NNDerived &d = g->nn_sets[i];
+        const bool same_arrays = d.pcd == s->pcd && d.nodes == s->nodes;
+        const bool matches = d.valid && same_arrays && d.normal == s->normal && d.n_points == s->n_points && d.n_nodes == s->n_nodes &&
+                             s->max_dist_diff * 1.01f <= d.frame_margin;      // (a smaller radius keeps its pruning inside the larger frame; a larger one would lose it outside the old)
+        const bool hit = matches && opt.scene_cache && !g_writes.written_since(d.gen, s->pcd, src.bytes[0]) && !g_writes.written_since(d.gen, s->nodes, src.bytes[1]);
+        facts[i] = NNSetFacts{ d.valid, hit, same_arrays, set_in_flight(i), d.used };
+    }
+    const NNSetPick pick = pick_nn_set(facts, kNNSets);
+    NNDerived &nc = g->nn_sets[pick.set];
+    bool hit = pick.hit;
+    if (hit && verify_now) {                                    // (a hit that turns out stale is rebuilt in the same set)
+        bool stale = false;
+        PR_TRY(fingerprint_differs(src, &nc.nndepth.as<prk::NNInfo>()->fp, g->stream, stale));
+        hit = !stale;
+    }
+    nc.used = ++g->nn_clock;
+    out.nn_set = pick.set;
+    if (hit) nc.gen = g_writes.now();                           // (the normals are read through the caller's pointer, never copied)
+    else {
+        drain_readers(pick.set);                                // (a batch in flight that reads this very set: it finishes first)
+        PR_TRY(derive_nn_set(nc, *s));
+    }
+    if (nc.info.depth >= 0x7fffffffu) { nc.valid = false; set_error("pr_scene_nn: the nodes do not form a consistent tree (child / parent links disagree or point outside the array)"); return PR_ERR_INVALID; }
+    const NNRoute route = nn_route(nc.info, s->n_nodes, opt.nn_lds_nodes, opt.nn_lds_records, opt.nn_stack, opt.nn_compact, opt.nn_wide);
+    out.nn = nn_dev(nc, *s, route);
+    // a bare ICP call has no camera of its own: the scene's hint, if it carries one (pose_refine.h)
+    Camera hinted;
+    if (!cam && s->cam_magic == PR_SCENE_NN_CAM_MAGIC && s->cam_w && s->cam_h && s->cam_fx > 0.0f && s->cam_fy > 0.0f) { hinted = Camera{ s->cam_w, s->cam_h, s->cam_fx, s->cam_fy, s->cam_cx, s->cam_cy }; cam = &hinted; }
+    if (!(cam && opt.nn_grid && route.compact && (size_t)cam->w * cam->h <= ((size_t)1 << 24))) return PR_OK;
+    PR_TRY(ensure_nn_grid(pick.set, *s, *cam));
+    if (nc.grid_usable) {
+        out.nn.grid = nc.nn_grid.as<float4>(); out.nn.gw = cam->w; out.nn.gh = cam->h; out.nn.gfx = cam->fx; out.nn.gfy = cam->fy; out.nn.gcx = cam->cx; out.nn.gcy = cam->cy;
+        const size_t w4 = (cam->w + 3) / 4, h4 = (cam->h + 3) / 4, w16 = (w4 + 3) / 4, h16 = (h4 + 3) / 4;
+        out.nn.pyr4 = out.nn.grid + (size_t)cam->w * cam->h; out.nn.pyr16 = out.nn.pyr4 + w4 * h4; out.nn.pyr64 = out.nn.pyr16 + w16 * h16;
+    }
+    return PR_OK;
+}
+// closest-point grid: the caller's two arrays as they are: nothing is derived from them and nothing is kept by address
+static int scene_grid(const void *scene, SceneSel &out)
+{
+    const pr_scene_grid *s = static_cast<const pr_scene_grid *>(scene);
+    PR_TRY(grid_desc_ok("pr_scene_grid", s, /*built=*/true));
+    out.grid = prk::SceneGridDev{ { s->origin[0], s->origin[1], s->origin[2] }, s->cell, s->inv_cell, { s->dim[0], s->dim[1], s->dim[2] }, s->max_dist_diff,
+                                  s->cell_point, reinterpret_cast<const float4 *>(s->rec) };
+    return PR_OK;
+}
 int make_scene(int kind, const void *scene, bool want_packed, SceneSel &out, PackedCache *pc_in, hipStream_t st, const Camera *cam,
                bool verify_now)
 {
-    PackedCache &pc = pc_in ? *pc_in : g->packed;
-    if (!st) st = g->stream;
     out.kind = kind;
-    if (kind == PR_SCENE_PROJ || kind == PR_SCENE_PROJ_CROP) {
-        const pr_scene_proj *s = static_cast<const pr_scene_proj *>(scene);       // pr_scene_proj_crop starts with the plain view
-        if (!s || !s->pcd || !s->normal || s->width == 0 || s->height == 0) { set_error("invalid pr_scene_proj"); return PR_ERR_INVALID; }
-        if (s->width > 0x7fffffffull || s->height > 0x7fffffffull) { set_error("pr_scene_proj: frame too large"); return PR_ERR_INVALID; }
-        uint32_t tl_x = 0, tl_y = 0;
-        if (kind == PR_SCENE_PROJ_CROP) { const pr_scene_proj_crop *c = static_cast<const pr_scene_proj_crop *>(scene); tl_x = c->tl_x; tl_y = c->tl_y; }
-        out.kind = PR_SCENE_PROJ;
-        out.aos = prk::SceneProjAoS{ (uint32_t)s->width, (uint32_t)s->height, s->max_dist_diff, s->K[0], s->K[4], s->K[2], s->K[5],
-                                     (float)tl_x, (float)tl_y, s->pcd, s->normal };
-        out.packed = false;
-        if (want_packed) {
-            PR_TRY(ensure_packed(pc, *s, tl_x, tl_y, st, verify_now));
-            if (pc.exact) {                                         // else: the caller's pcd is not dep2pcd's -- use the arrays as they are
-                const size_t n = (size_t)s->width * s->height;
-                float *colf = reinterpret_cast<float *>(pc.rec.as<float4>() + n);
-                out.packed = true;
-                out.pk = prk::SceneProjPacked{ (uint32_t)s->width, (uint32_t)s->height, s->max_dist_diff, s->K[0], s->K[4], s->K[2], s->K[5],
-                                               (float)tl_x, (float)tl_y, pc.rec.as<float4>(), colf, colf + s->width };
-            }
-        }
-        return PR_OK;
-    }
-    if (kind == PR_SCENE_NN) {
-        const pr_scene_nn *s = static_cast<const pr_scene_nn *>(scene);
-        if (!s || !s->pcd || !s->normal || !s->nodes || s->n_nodes == 0 || s->n_points == 0) { set_error("invalid pr_scene_nn"); return PR_ERR_INVALID; }
-        // which of the sets of derived records: one that holds this scene and is still good, else a victim -- a stale set of the same arrays, an
-        // empty one, the least recently used one that no batch in flight reads; only when every set is being read does a slot have to drain first
-        auto matches = [&](const NNDerived &d) {
-            return d.valid && d.pcd == s->pcd && d.normal == s->normal && d.nodes == s->nodes && d.n_points == s->n_points && d.n_nodes == s->n_nodes &&
-                   s->max_dist_diff * 1.01f <= d.frame_margin;       // (a smaller radius keeps its pruning inside the larger frame; a larger one would lose it outside the old)
-        };
-        auto in_flight = [&](int set) { for (Slot &o : g->slots) if (o.pending && !o.delivered && o.nn_set == set) return true; return false; };
-        auto drain_readers = [&](int set) { for (Slot &o : g->slots) if (o.pending && !o.delivered && o.nn_set == set) slot_drain(o); };
-        int pick = -1;
-        bool hit = false;
-        for (int i = 0; i < kNNSets && pick < 0; ++i) {
-            const NNDerived &d = g->nn_sets[i];
-            if (matches(d) && opt.scene_cache && !g_writes.written_since(d.gen, s->pcd, (size_t)s->n_points * sizeof(pr_vec3)) &&
-                !g_writes.written_since(d.gen, s->nodes, (size_t)s->n_nodes * sizeof(pr_kdnode))) { pick = i; hit = true; }
-        }
-        if (hit && verify_now) {
-            bool stale = false;
-            PR_TRY(fingerprint_differs(s->pcd, (size_t)s->n_points * sizeof(pr_vec3), s->nodes, (size_t)s->n_nodes * sizeof(pr_kdnode), s->normal,
-                                       (size_t)s->n_points * sizeof(pr_vec3), g->nn_sets[pick].nndepth.as<uint32_t>() + 12, g->stream, stale));
-            hit = !stale;
-        }
-        if (!hit) {
-            if (pick < 0) for (int i = 0; i < kNNSets && pick < 0; ++i) { const NNDerived &d = g->nn_sets[i]; if (d.valid && d.pcd == s->pcd && d.nodes == s->nodes) pick = i; }   // this scene's arrays, rewritten
-            if (pick < 0) for (int i = 0; i < kNNSets && pick < 0; ++i) if (!g->nn_sets[i].valid) pick = i;
-            if (pick < 0) { for (int i = 0; i < kNNSets; ++i) if (!in_flight(i) && (pick < 0 || g->nn_sets[i].used < g->nn_sets[pick].used)) pick = i; }
-            if (pick < 0) { pick = 0; for (int i = 1; i < kNNSets; ++i) if (g->nn_sets[i].used < g->nn_sets[pick].used) pick = i; }
-        }
-        NNDerived &nc = g->nn_sets[pick];
-        nc.used = ++g->nn_clock;
-        out.nn_set = pick;
-        if (hit) {
-            nc.gen = g_writes.now();                                // (the normals are read through the caller's pointer, never copied)
-        } else {
-            drain_readers(pick);                                    // (a batch in flight that reads this very set: it finishes first)
-            nc.valid = false; nc.grid_valid = false;
-            const uint64_t gen = g_writes.now();
-            PR_TRY(nc.topo.ensure((size_t)s->n_nodes * sizeof(int4)));
-            PR_TRY(nc.bmin.ensure((size_t)s->n_nodes * sizeof(float4)));
-            PR_TRY(nc.bmax.ensure((size_t)s->n_nodes * sizeof(float4)));
-            PR_TRY(nc.pts.ensure(((size_t)s->n_points + 16u) * sizeof(float4)));   // + 16: a leaf task of the walk reads its ten slots whatever the leaf holds (nn_tree_wide_kernel)
-            PR_TRY(nc.nnrec.ensure((size_t)s->n_nodes * 4 * sizeof(float4)));
-            PR_TRY(nc.nndepth.ensure(24 * sizeof(uint32_t)));      // [0] depth [1] rec32 valid [2..7] rec32 frame [8] wide valid [9] wide nodes [12] sampled fingerprint [13] its verdict [14] full fingerprint [15] a call's full fingerprint [16..19] wide frame
-            PR_TRY(nc.nnrec32.ensure((size_t)s->n_nodes * 2 * sizeof(uint4)));
-            PR_TRY(nc.nndesc.ensure((size_t)s->n_nodes * sizeof(uint2)));
-            // wide records: one 128-byte line per wide node
-            PR_TRY(nc.nnwide.ensure(prk::nn_wide_capacity(s->n_nodes) * 128));
-            PR_TRY(nc.nnwq.ensure(prk::nn_wide_scratch_words(s->n_nodes) * sizeof(uint32_t)));
-            HIP_TRY(prk::launch_build_nn_accel(s->nodes, s->n_nodes, s->pcd, s->n_points, nc.topo.as<int4>(), nc.bmin.as<float4>(),
-                                               nc.bmax.as<float4>(), nc.pts.as<float4>(), nc.nnrec.as<float4>(), nc.nnrec32.as<uint4>(),
-                                               nc.nndesc.as<uint2>(), nc.nndepth.as<uint32_t>(), g->stream, s->max_dist_diff * 1.01f));
-            HIP_TRY(prk::launch_scene_fingerprint(s->pcd, (size_t)s->n_points * sizeof(pr_vec3), s->nodes, (size_t)s->n_nodes * sizeof(pr_kdnode), s->normal,
-                                                  (size_t)s->n_points * sizeof(pr_vec3), nc.nndepth.as<uint32_t>() + 12, nullptr, false, g->stream));
-            HIP_TRY(prk::launch_scene_fingerprint_full(s->pcd, (size_t)s->n_points * sizeof(pr_vec3), s->nodes, (size_t)s->n_nodes * sizeof(pr_kdnode), s->normal,
-                                                       (size_t)s->n_points * sizeof(pr_vec3), nc.nndepth.as<uint32_t>() + 14, g->stream));
-            // the wide records, eight levels per synchronisation (8^8 wide nodes: deeper only for a lopsided tree)
-            for (uint32_t level = 0; ; level += 8) {
-                HIP_TRY(prk::launch_nn_wide_levels(nc.topo.as<int4>(), nc.bmin.as<float4>(), nc.bmax.as<float4>(), s->n_nodes, s->n_points, nc.nnwide.as<uint4>(),
-                                                   nc.nnwq.as<uint32_t>(), nc.nndepth.as<uint32_t>(), level, 8, g->stream));
-                PR_TRY(read_back_words(nc.nndepth.p, nc.info, (uint32_t)(sizeof nc.info / sizeof(uint32_t)), g->stream));
-                if (nc.info[8] != 2u) break;
-                if (level + 8 >= 64) { nc.info[8] = 0u; break; }    // (as before: more than 64 wide levels -> the binary records)
-            }
-            nc.pcd = s->pcd; nc.normal = s->normal; nc.nodes = s->nodes; nc.n_points = s->n_points; nc.n_nodes = s->n_nodes; nc.gen = gen; nc.valid = true;
-            nc.frame_margin = s->max_dist_diff * 1.01f;
-        }
-        const uint32_t *info = nc.info;
-        const uint32_t depth = info[0];
-        if (depth >= 0x7fffffffu) { nc.valid = false; set_error("pr_scene_nn: the nodes do not form a consistent tree (child / parent links disagree or point outside the array)"); return PR_ERR_INVALID; }
-        uint32_t lds = (uint32_t)std::max(0, opt.nn_lds_nodes);
-        lds = std::min(lds, s->n_nodes);
-        lds = std::min<uint32_t>(lds, 8192);                      // <= 128 KiB of LDS
-        // pending far children on the stack never exceed the tree depth; deeper trees use the stackless walk
-        uint32_t stack = 0;
-        if (opt.nn_stack) stack = (depth <= 16) ? 16u : ((depth <= 24) ? 24u : 0u);
-        if (stack) lds = std::min<uint32_t>({ (uint32_t)std::max(0, opt.nn_lds_records), s->n_nodes, (65536u - stack * 2048u) / 64u });   // stacks + records <= 64 KiB
-        out.nn = prk::SceneNNDev{ s->max_dist_diff, nc.topo.as<int4>(), nc.bmin.as<float4>(), nc.bmax.as<float4>(), nc.pts.as<float4>(),
-                                  s->pcd, s->normal, s->n_nodes, lds, nc.nnrec.as<float4>(), stack, nullptr, { 0, 0, 0 }, { 0, 0, 0 }, nc.nndesc.as<uint2>() };
-        if (stack && opt.nn_compact && info[1] == 1u) {
-            out.nn.rec32 = nc.nnrec32.as<uint4>();
-            for (int a = 0; a < 3; ++a) { std::memcpy(&out.nn.qmin[a], &info[2 + a], 4); std::memcpy(&out.nn.qscale[a], &info[5 + a], 4); }
-            if (opt.nn_wide && info[8] == 1u && info[9] > 0u) {
-                out.nn.wide = nc.nnwide.as<uint4>(); out.nn.n_wide = info[9];
-                for (int a = 0; a < 3; ++a) std::memcpy(&out.nn.wmin[a], &info[16 + a], 4);
-                std::memcpy(&out.nn.wscale, &info[19], 4);
-            }
-        }
-        // a bare ICP call has no camera of its own: the scene's hint, if it carries one (pose_refine.h)
-        Camera hinted;
-        if (!cam && s->cam_magic == PR_SCENE_NN_CAM_MAGIC && s->cam_w && s->cam_h && s->cam_fx > 0.0f && s->cam_fy > 0.0f) { hinted = Camera{ s->cam_w, s->cam_h, s->cam_fx, s->cam_fy, s->cam_cx, s->cam_cy }; cam = &hinted; }
-        // pixel grid of the scene points under the hypotheses' camera (fused paths), or under the camera the scene says it was made with.  Usable
-        // when every scene point owns a cell -- a Scene_nn made from a depth image with these intrinsics -- else the tree alone.
-        if (cam && opt.nn_grid && out.nn.rec32 && (size_t)cam->w * cam->h <= ((size_t)1 << 24)) {
-            const float gk[4] = { cam->fx, cam->fy, cam->cx, cam->cy };
-            if (!(nc.grid_valid && nc.gw == cam->w && nc.gh == cam->h && std::memcmp(nc.gk, gk, sizeof gk) == 0)) {
-                drain_readers(pick);
-                const size_t cells = (size_t)cam->w * cam->h;
-                PR_TRY(nc.nn_cells.ensure(cells * sizeof(int32_t) + 16));
-                PR_TRY(nc.nn_grid.ensure(prk::nn_grid_cells(cam->w, cam->h) * sizeof(float4)));
-                uint32_t *flag = reinterpret_cast<uint32_t *>(nc.nn_cells.as<int32_t>() + cells);
-                HIP_TRY(prk::launch_build_nn_grid(s->pcd, s->n_points, cam->w, cam->h, gk[0], gk[1], gk[2], gk[3], nc.nn_cells.as<int32_t>(),
-                                                  nc.nn_grid.as<float4>(), flag, g->stream));
-                uint32_t usable = 0;
-                PR_TRY(read_back_words(flag, &usable, 1, g->stream));
-                nc.grid_valid = true; nc.grid_usable = usable != 0; nc.gw = cam->w; nc.gh = cam->h; std::memcpy(nc.gk, gk, sizeof gk);
-            }
-            if (nc.grid_usable) {
-                out.nn.grid = nc.nn_grid.as<float4>(); out.nn.gw = cam->w; out.nn.gh = cam->h; out.nn.gfx = gk[0]; out.nn.gfy = gk[1]; out.nn.gcx = gk[2]; out.nn.gcy = gk[3];
-                const size_t w4 = (cam->w + 3) / 4, h4 = (cam->h + 3) / 4, w16 = (w4 + 3) / 4, h16 = (h4 + 3) / 4;
-                out.nn.pyr4 = out.nn.grid + (size_t)cam->w * cam->h; out.nn.pyr16 = out.nn.pyr4 + w4 * h4; out.nn.pyr64 = out.nn.pyr16 + w16 * h16;
-            }
-        }
-        return PR_OK;
-    }
-    if (kind == PR_SCENE_GRID) {
-        // the caller's two arrays as they are: nothing is derived from them and nothing is kept by address
-        const pr_scene_grid *s = static_cast<const pr_scene_grid *>(scene);
-        PR_TRY(grid_desc_ok("pr_scene_grid", s, /*built=*/true));
-        out.grid = prk::SceneGridDev{ { s->origin[0], s->origin[1], s->origin[2] }, s->cell, s->inv_cell, { s->dim[0], s->dim[1], s->dim[2] }, s->max_dist_diff,
-                                      s->cell_point, reinterpret_cast<const float4 *>(s->rec) };
-        return PR_OK;
-    }
+    if (kind == PR_SCENE_PROJ || kind == PR_SCENE_PROJ_CROP) return scene_proj(kind, scene, want_packed, out, pc_in ? *pc_in : g->packed, st ? st : g->stream, verify_now);
+    if (kind == PR_SCENE_NN) return scene_nn(scene, out, cam, verify_now);
+    if (kind == PR_SCENE_GRID) return scene_grid(scene, out);
     set_error("unknown scene kind %d", kind);
     return PR_ERR_INVALID;
 }
@@ -374,7 +374,7 @@ int pr_debug_nn_records(const pr_scene_nn *scene, uint32_t cam_w, uint32_t cam_h
     const NNDerived &nc = g->nn_sets[sc.nn_set];
     const prk::SceneNNDev &nn = sc.nn;
     const size_t n_nodes = nc.n_nodes, n_points = nc.n_points;
-    const size_t n_wide = std::min<size_t>(nc.info[9], prk::nn_wide_capacity(nc.n_nodes));
+    const size_t n_wide = std::min<size_t>(nc.info.n_wide, prk::nn_wide_capacity(nc.n_nodes));
     // the grid of THIS camera (without one make_scene may still have built the grid of the scene's own hint: not what was asked for)
     const bool grid = cam_k && nc.grid_valid && nc.gw == cam_w && nc.gh == cam_h && std::memcmp(nc.gk, cam_k, sizeof nc.gk) == 0 && nc.nn_cells.p && nc.nn_grid.p;
     const size_t cells = grid ? (size_t)cam_w * cam_h : 0, grid_cells = grid ? prk::nn_grid_cells(cam_w, cam_h) : 0;
@@ -390,7 +390,7 @@ int pr_debug_nn_records(const pr_scene_nn *scene, uint32_t cam_w, uint32_t cam_h
         if (e == hipSuccess && c.dst && c.src && c.bytes) e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     if (e != hipSuccess) { (void)hipGetLastError(); set_error("pr_debug_nn_records: %s", hipGetErrorString(e)); return PR_ERR_HIP; }
-    if (out->info) std::memcpy(out->info, nc.info, sizeof nc.info);   // (the host's copy: what make_scene itself decides on)
+    if (out->info) std::memcpy(out->info, &nc.info, sizeof nc.info);  // (the host's copy: what make_scene itself decides on; 24 words, prk::NNInfo)
     return PR_OK;
 }
 

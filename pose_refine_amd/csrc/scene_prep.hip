@@ -140,28 +140,22 @@ __global__ __launch_bounds__(256) void pack_proj_scene_kernel(const pr_vec3 *__r
 // out again) would leave a stale cache behind.  Every asynchronous batch therefore re-reads 4096 words of each source array, spread over
 // the whole array, and compares their hash with the one taken when the cache was built: a frame that changed as a whole cannot pass, and
 // the batch is then repeated with fresh caches (refine_wait, like a stale model box).  A sampled check is not a proof -- an edit confined
-// to words it does not look at still needs pr_invalidate, as pose_refine.h says.
+// to words it does not look at still needs pr_invalidate, as pose_refine.h says.  This kernel takes the hash when the cache is built
+// (FpWords::sample); the per-batch comparison rides on the raster launch (BatchCheck, raster.hip).
 __global__ __launch_bounds__(256) void scene_fingerprint_kernel(const uint32_t *__restrict__ a, unsigned long long na, const uint32_t *__restrict__ b,
                                                                 unsigned long long nb, const uint32_t *__restrict__ c, unsigned long long nc,
-                                                                uint32_t *__restrict__ expected, uint32_t *__restrict__ flag, int check)
+                                                                uint32_t *__restrict__ sample)
 {
     __shared__ uint32_t part[4];
     uint32_t h = fingerprint_lane(a, na, b, nb, c, nc);
     for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off);
     if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = h;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t v = part[0] + part[1] + part[2] + part[3];
-        if (check) { if (*expected != v) *flag = 1u; }
-        else *expected = v;
-    }
+    if (threadIdx.x == 0) *sample = part[0] + part[1] + part[2] + part[3];
 }
-hipError_t launch_scene_fingerprint(const void *a, size_t a_bytes, const void *b, size_t b_bytes, const void *c, size_t c_bytes,
-                                    uint32_t *expected, uint32_t *flag, bool check, hipStream_t s)
+hipError_t launch_scene_fingerprint(const SceneSources &src, uint32_t *sample, hipStream_t s)
 {
-    hipLaunchKernelGGL(scene_fingerprint_kernel, dim3(1), dim3(256), 0, s, static_cast<const uint32_t *>(a), (unsigned long long)(a_bytes / 4),
-                       static_cast<const uint32_t *>(b), (unsigned long long)(b_bytes / 4), static_cast<const uint32_t *>(c), (unsigned long long)(c_bytes / 4),
-                       expected, flag, check ? 1 : 0);
+    hipLaunchKernelGGL(scene_fingerprint_kernel, dim3(1), dim3(256), 0, s, src.words(0), src.n_words(0), src.words(1), src.n_words(1), src.words(2), src.n_words(2), sample);
     return hipGetLastError();
 }
 
@@ -189,14 +183,13 @@ __global__ __launch_bounds__(256) void scene_fingerprint_full_kernel(const uint3
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(sum, part[0] + part[1] + part[2] + part[3]);
 }
-hipError_t launch_scene_fingerprint_full(const void *a, size_t a_bytes, const void *b, size_t b_bytes, const void *c, size_t c_bytes, uint32_t *sum, hipStream_t s)
+hipError_t launch_scene_fingerprint_full(const SceneSources &src, uint32_t *sum, hipStream_t s)
 {
-    const size_t words = a_bytes / 4 + b_bytes / 4 + c_bytes / 4;
+    const size_t words = src.n_words(0) + src.n_words(1) + src.n_words(2);
     const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(1024, (words + 256 * 16 - 1) / (256 * 16)));
     hipError_t e = hipMemsetAsync(sum, 0, sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(scene_fingerprint_full_kernel, dim3(grid), dim3(256), 0, s, static_cast<const uint32_t *>(a), (unsigned long long)(a_bytes / 4),
-                       static_cast<const uint32_t *>(b), (unsigned long long)(b_bytes / 4), static_cast<const uint32_t *>(c), (unsigned long long)(c_bytes / 4), sum);
+    hipLaunchKernelGGL(scene_fingerprint_full_kernel, dim3(grid), dim3(256), 0, s, src.words(0), src.n_words(0), src.words(1), src.n_words(1), src.words(2), src.n_words(2), sum);
     return hipGetLastError();
 }
 

@@ -207,6 +207,33 @@ def test_one_scene_object_reinitialised_under_its_own_batch_in_flight(gpu, model
     assert res.tobytes() == want[6 % 3][0].tobytes()
 
 
+@pytest.mark.device_solve
+def test_unchanged_cropped_scene_is_never_found_stale(gpu, model, scenario, gscenes):
+    """Every asynchronous batch compares the sampled fingerprint of the scene arrays with the word kept behind the packed cache's tables
+    (ProjTail, pr_runtime.h), over the same list of arrays in the same order as the build.  A list in another order, or a tail word at
+    another offset, would flag every batch and run it twice: three batches on an unchanged cropped scene repeat nothing and return the same bytes.
+    (A whole-frame projective scene: test_scene_rewritten_behind_the_librarys_back_is_noticed's last batch; kd-tree scenes:
+    test_kdtree_scenes_that_change_every_frame_keep_both_slots_running.)  The window's width + height is odd: the tail sits behind padding."""
+    K, proj = scenario["K"], scenario["proj"]
+    ys, xs = np.nonzero(scenario["depth"][1])
+    w, h = int(xs.max() - xs.min() + 1) | 1, (int(ys.max() - ys.min() + 1) + 1) & ~1      # odd, even
+    x0, y0 = min(int(xs.min()), W - w), min(int(ys.min()), H - h)
+    scene = gscenes["proj"].crop((x0, y0, w, h))
+    poses = synth.hypotheses(8)
+    crit = api.ICPConvergenceCriteria(0.0, 0.0, 4)
+    repeated = api.stats()[0]
+    got = []
+    for k in range(3):
+        api.refine_submit(k & 1, model, poses, W, H, proj, K, scene, crit)
+        if k:
+            got.append(api.refine_wait((k - 1) & 1))
+    got.append(api.refine_wait(0))
+    assert api.stats()[0] == repeated
+    assert (w + h) % 4 != 0 and got[0][0]["fitness"].max() > 0.0
+    for res, sizes in got[1:]:
+        assert res.tobytes() == got[0][0].tobytes() and np.array_equal(sizes, got[0][1])
+
+
 def sampled_words(n_words):
     """The word positions fingerprint_lane (csrc/pr_device.h) looks at in an array of n_words 32-bit words: one per stripe of n / 4096."""
     stripe = n_words // 4096

@@ -1,6 +1,7 @@
 """The pure host parts of the refine drivers under ASan / UBSan: tools/job_sanitize.cpp -- the packed layouts (box_area, box_slot, cloud_slot),
 the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for), the byte rule of a timed pass (icp_span_bytes), the
-mixed-batch layer (plan_meshes, Batch, camera_centers), beside the job, request and workspace checks it already held -- built with the command in its own first line as a stand-alone program and run.  Nothing is
+mixed-batch layer (plan_meshes, Batch, camera_centers), the scene caches (the control words NNInfo, FpWords and ProjTail at their documented
+positions, packed_layout, the source lists, the set choice pick_nn_set and the route choice nn_route of make_scene), beside the job, request and workspace checks it already held -- built with the command in its own first line as a stand-alone program and run.  Nothing is
 loaded into this process and no device is needed."""
 import os
 import shlex

@@ -1,6 +1,6 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
 // Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok, render_args_ok and vsd_args_ok with null and
-// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), the mixed-batch layer (plan_meshes on a worked example and on every table it refuses; Batch: gather, scatter, the pyramid's rows, the P x P matrix, the inverse, the one-mesh identity; camera_centers bit for bit against the expression it replaced), and pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance).  None of them calls HIP, so nothing of the runtime is linked.
+// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), the mixed-batch layer (plan_meshes on a worked example and on every table it refuses; Batch: gather, scatter, the pyramid's rows, the P x P matrix, the inverse, the one-mesh identity; camera_centers bit for bit against the expression it replaced), pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance), and the scene caches (the control words NNInfo and the fingerprint words FpWords / ProjTail at their documented positions, packed_layout, the source lists scene_sources / check_sources, pick_nn_set rule by rule, nn_route at every clamp).  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
 namespace prh { void set_error(const char *, ...) {} }
@@ -489,6 +489,106 @@ int main()
         ps[1].m[6] = NAN;                                                                                   // a pose with a NaN entry: a centre the checks refuse
         camera_centers(ps.data(), ix, 3, cm2, rr2, c, rad);
         CHECK(std::isnan(c[3 * 1 + 1]) && same_bits(c[0], reference(ps[0].m, cm2 + 3, 0)) && info_center_radius_ok("job_sanitize", c, rad, 3) == PR_ERR_INVALID);
+    }
+    // scene caches.  The control words of a kd-tree set at the positions pr_debug_nn_records hands them out at; the fingerprint words of both caches
+    {
+        using prk::NNInfo;
+        const size_t word_of[][2] = { { offsetof(NNInfo, depth), 0 }, { offsetof(NNInfo, rec32_valid), 1 }, { offsetof(NNInfo, qmin), 2 }, { offsetof(NNInfo, qscale), 5 },
+                                      { offsetof(NNInfo, wide_state), 8 }, { offsetof(NNInfo, n_wide), 9 }, { offsetof(NNInfo, fp), 12 }, { offsetof(NNInfo, wmin), 16 },
+                                      { offsetof(NNInfo, wscale), 19 }, { offsetof(NNInfo, wide_frame_ok), 20 } };
+        for (const auto &w : word_of) CHECK(w[0] == 4 * w[1]);
+        CHECK(sizeof(NNInfo) == 24 * 4 && offsetof(NNInfo, fp) == 48 && sizeof(NNInfo::qmin) == 12 && sizeof(NNInfo::qscale) == 12 && sizeof(NNInfo::wmin) == 12);
+        CHECK(offsetof(prk::FpWords, sample) == 0 && offsetof(prk::FpWords, full) == 8 && offsetof(prk::FpWords, call) == 12 && sizeof(prk::FpWords) == 16);
+        CHECK(prk::kWideNone == 0 && prk::kWideValid == 1 && prk::kWideMoreLevels == 2);
+        CHECK(sizeof(ProjTail) == 32 && offsetof(ProjTail, exact) == 0 && offsetof(ProjTail, fp) == 4);      // tail words 1..4
+        // the packed projective cache: records, two tables, the tail on 16 bytes; carved from a block of that size, every part's last element is inside it
+        for (auto [w, h] : { std::pair<size_t, size_t>{ 1, 1 }, { 3, 2 }, { 640, 480 }, { 8192, 2048 } }) {
+            const PackedLayout l = packed_layout(w, h);
+            const size_t n = w * h, tables = ((w + h) * 4 + 15) / 16 * 16;
+            CHECK(l.colf == n * 16 && l.rowf == l.colf + 4 * w && l.tail % 16 == 0 && l.tail == n * 16 + tables && l.tail >= l.rowf + 4 * h && l.bytes == l.tail + 32);
+            PackedCache pc;
+            pc.rec.p = std::malloc(l.bytes);
+            CHECK(pc.rec.p != nullptr);
+            if (!pc.rec.p) continue;
+            pc.rec.as<float4>()[n - 1] = float4{ 1, 2, 3, 4 }; pc.at<float>(l.colf)[w - 1] = 5.0f; pc.at<float>(l.rowf)[h - 1] = 6.0f;
+            ProjTail *t = pc.at<ProjTail>(l.tail);
+            *t = ProjTail{ 7u, { 8u, 0u, 9u, 10u }, { 0u, 0u, 0u } };
+            CHECK(reinterpret_cast<uintptr_t>(t) % alignof(ProjTail) == 0 && pc.rec.as<float4>()[n - 1].w == 4.0f && pc.at<float>(l.colf)[w - 1] == 5.0f && pc.at<float>(l.rowf)[h - 1] == 6.0f);
+            CHECK(pc.at<uint32_t>(l.tail)[0] == 7u && pc.at<uint32_t>(l.tail)[1] == 8u && pc.at<uint32_t>(l.tail)[3] == 9u && pc.at<uint32_t>(l.tail)[4] == 10u);
+            std::free(pc.rec.p); pc.rec.p = nullptr;
+        }
+    }
+    // the source arrays of a scene cache, in the order every fingerprint mixes them in: projective pcd, normal; kd-tree pcd, NODES, normal
+    {
+        const pr_vec3 *pcd = reinterpret_cast<const pr_vec3 *>(uintptr_t(0x20000)), *nrm = reinterpret_cast<const pr_vec3 *>(uintptr_t(0x30000));
+        const pr_kdnode *nodes = reinterpret_cast<const pr_kdnode *>(uintptr_t(0x40000));
+        pr_scene_proj p32{}; p32.width = 3; p32.height = 2; p32.pcd = pcd; p32.normal = nrm;
+        const prk::SceneSources a = prk::scene_sources(p32);
+        CHECK(a.p[0] == pcd && a.p[1] == nrm && a.p[2] == nullptr && a.bytes[0] == 72 && a.bytes[1] == 72 && a.bytes[2] == 0);
+        CHECK(a.words(0) == reinterpret_cast<const uint32_t *>(pcd) && a.n_words(0) == 18 && a.n_words(1) == 18 && a.n_words(2) == 0 && a.words(2) == nullptr);
+        pr_scene_proj big{}; big.width = 8192; big.height = 2048; big.pcd = pcd; big.normal = nrm;
+        CHECK(prk::scene_sources(big).bytes[0] == 201326592u && prk::scene_sources(big).n_words(1) == 50331648u);
+        pr_scene_nn t{}; t.pcd = pcd; t.normal = nrm; t.nodes = nodes; t.n_points = 11; t.n_nodes = 5;
+        const prk::SceneSources b = prk::scene_sources(t);
+        CHECK(b.p[0] == pcd && b.p[1] == nodes && b.p[2] == nrm && b.bytes[0] == 132 && b.bytes[1] == 260 && b.bytes[2] == 132);
+        CHECK(b.n_words(0) == 33 && b.n_words(1) == 65 && b.n_words(2) == 33);
+        pr_scene_nn full{}; full.pcd = pcd; full.normal = nrm; full.nodes = nodes; full.n_points = 0xffffffffu; full.n_nodes = 0xffffffffu;      // no 32-bit product
+        CHECK(prk::scene_sources(full).bytes[0] == 12ull * 0xffffffffull && prk::scene_sources(full).bytes[1] == 52ull * 0xffffffffull && prk::scene_sources(full).n_words(1) == 13ull * 0xffffffffull);
+        const uint32_t *expected = reinterpret_cast<const uint32_t *>(uintptr_t(0x50000));
+        prk::BatchCheck chk{};
+        prk::check_sources(chk, b, expected);
+        CHECK(chk.fa == a.words(0) && chk.fb == reinterpret_cast<const uint32_t *>(nodes) && chk.fc == a.words(1) && chk.na == 33 && chk.nb == 65 && chk.nc == 33 && chk.fp_expected == expected);
+        CHECK(chk.keys == nullptr && chk.flag == nullptr && chk.caller == nullptr);                        // nothing else is touched
+        prk::check_sources(chk, a, expected + 1);
+        CHECK(chk.fb == a.words(1) && chk.fc == nullptr && chk.na == 18 && chk.nb == 18 && chk.nc == 0 && chk.fp_expected == expected + 1);
+    }
+    // which set of kd-tree records a scene takes (pick_nn_set): facts = { valid, hit, same arrays, in flight, used }; every rule on a table that the
+    // rules behind it would answer differently
+    {
+        auto pick = [](std::initializer_list<NNSetFacts> f) { return pick_nn_set(f.begin(), (int)f.size()); };
+        auto is = [](NNSetPick p, int set, bool hit) { return p.set == set && p.hit == hit; };
+        CHECK(is(pick({ { true, false, true, false, 1 }, { true, true, true, false, 9 } }), 1, true));        // 1. a hit -- before a same-arrays set with a lower index
+        CHECK(is(pick({ { true, true, true, false, 9 }, { true, true, true, false, 1 } }), 0, true));         //    both hit: the first
+        CHECK(is(pick({ { true, false, false, false, 1 }, { true, false, true, true, 9 } }), 1, false));      // 2. valid and of the same arrays, although in flight and used last
+        CHECK(is(pick({ { true, false, false, false, 1 }, { false, false, false, false, 2 }, { false, false, true, false, 3 } }), 1, false));      //    (an invalid set's arrays do not count)
+        CHECK(is(pick({ { true, false, false, false, 1 }, { false, false, false, true, 9 } }), 1, false));    // 3. the first invalid one
+        CHECK(is(pick({ { false, false, false, false, 9 }, { false, false, false, false, 1 } }), 0, false));
+        CHECK(is(pick({ { true, false, false, true, 1 }, { true, false, false, false, 9 } }), 1, false));     // 4. least recently used among those no batch reads
+        CHECK(is(pick({ { true, false, false, false, 9 }, { true, false, false, false, 1 } }), 1, false));
+        CHECK(is(pick({ { true, false, false, false, 1 }, { true, false, false, false, 9 } }), 0, false));
+        CHECK(is(pick({ { true, false, false, true, 1 }, { true, false, false, false, 9 }, { true, false, false, false, 5 } }), 2, false));
+        CHECK(is(pick({ { true, false, false, true, 9 }, { true, false, false, true, 1 } }), 1, false));      // 5. every set in flight: plain least recently used
+        CHECK(is(pick({ { true, false, false, true, 1 }, { true, false, false, true, 9 } }), 0, false));
+        CHECK(is(pick({ { true, false, false, true, 4 }, { true, false, false, true, 4 } }), 0, false));
+        CHECK(is(pick({ { true, false, false, false, 1 } }), 0, false) && is(pick({ { false, false, false, false, 0 } }), 0, false));
+    }
+    // how a set is searched (nn_route): the expected values are the parent expressions' results, written out
+    {
+        auto info_of = [](uint32_t depth, uint32_t rec32_valid = 1, uint32_t wide_state = prk::kWideValid, uint32_t n_wide = 100) {
+            prk::NNInfo i{}; i.depth = depth; i.rec32_valid = rec32_valid; i.wide_state = wide_state; i.n_wide = n_wide; i.wide_frame_ok = 1; return i;
+        };
+        auto is = [](NNRoute r, uint32_t lds, uint32_t stack, bool compact, bool wide) { return r.lds_nodes == lds && r.stack_depth == stack && r.compact == compact && r.wide == wide; };
+        // the options' defaults (1024, 0, 1, 1, 1) by depth: 16 entries up to 16, 24 up to 24, the stackless walk beyond
+        CHECK(is(nn_route(info_of(0), 5000, 1024, 0, 1, 1, 1), 0, 16, true, true) && is(nn_route(info_of(16), 5000, 1024, 0, 1, 1, 1), 0, 16, true, true));
+        CHECK(is(nn_route(info_of(17), 5000, 1024, 0, 1, 1, 1), 0, 24, true, true) && is(nn_route(info_of(24), 5000, 1024, 0, 1, 1, 1), 0, 24, true, true));
+        CHECK(is(nn_route(info_of(25), 5000, 1024, 0, 1, 1, 1), 1024, 0, false, false) && is(nn_route(info_of(4096), 5000, 1024, 0, 1, 1, 1), 1024, 0, false, false));
+        CHECK(is(nn_route(info_of(10), 5000, 1024, 0, 0, 1, 1), 1024, 0, false, false));                     // nn_stack off: no compact records either
+        CHECK(is(nn_route(info_of(10), 5000, 1024, 0, -1, -1, -1), 0, 16, true, true));                      // (the three switches: non-zero is on)
+        // compact records invalid; the wide state's three values; no wide nodes; the two options
+        CHECK(is(nn_route(info_of(10, 0), 5000, 1024, 0, 1, 1, 1), 0, 16, false, false) && is(nn_route(info_of(10, 2), 5000, 1024, 0, 1, 1, 1), 0, 16, false, false));
+        CHECK(is(nn_route(info_of(10, 1, prk::kWideNone), 5000, 1024, 0, 1, 1, 1), 0, 16, true, false) && is(nn_route(info_of(10, 1, prk::kWideMoreLevels), 5000, 1024, 0, 1, 1, 1), 0, 16, true, false));
+        CHECK(is(nn_route(info_of(10, 1, prk::kWideValid, 0), 5000, 1024, 0, 1, 1, 1), 0, 16, true, false) && is(nn_route(info_of(10, 1, prk::kWideValid, 1), 5000, 1024, 0, 1, 1, 1), 0, 16, true, true));
+        CHECK(is(nn_route(info_of(10), 5000, 1024, 0, 1, 1, 0), 0, 16, true, false) && is(nn_route(info_of(10), 5000, 1024, 0, 1, 0, 1), 0, 16, false, false));
+        // stackless: nn_lds_nodes, at most the tree, at most 8192
+        CHECK(is(nn_route(info_of(30), 1023, 1024, 0, 1, 1, 1), 1023, 0, false, false) && is(nn_route(info_of(30), 1025, 1024, 0, 1, 1, 1), 1024, 0, false, false));
+        CHECK(is(nn_route(info_of(30), 8191, 20000, 0, 1, 1, 1), 8191, 0, false, false) && is(nn_route(info_of(30), 8193, 20000, 0, 1, 1, 1), 8192, 0, false, false));
+        CHECK(is(nn_route(info_of(30), 50000, 2147483647, 0, 1, 1, 1), 8192, 0, false, false) && is(nn_route(info_of(30), 50000, -5, 7, 1, 1, 1), 0, 0, false, false));
+        CHECK(is(nn_route(info_of(30), 50000, -2147483647 - 1, 7, 0, 1, 1), 0, 0, false, false));
+        // stack: nn_lds_records, at most the tree, at most what the stacks leave of 64 KiB -- 512 records beside 16 entries, 256 beside 24
+        CHECK(is(nn_route(info_of(16), 5000, 1024, 64, 1, 1, 1), 64, 16, true, true) && is(nn_route(info_of(16), 5000, 1024, -1, 1, 1, 1), 0, 16, true, true));
+        CHECK(is(nn_route(info_of(16), 511, 1024, 100000, 1, 1, 1), 511, 16, true, true) && is(nn_route(info_of(16), 513, 1024, 100000, 1, 1, 1), 512, 16, true, true));
+        CHECK(is(nn_route(info_of(24), 255, 1024, 100000, 1, 1, 1), 255, 24, true, true) && is(nn_route(info_of(24), 257, 1024, 2147483647, 1, 1, 1), 256, 24, true, true));
+        CHECK(is(nn_route(info_of(24), 1, 0, 100000, 1, 1, 1), 1, 24, true, true));
     }
     std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;

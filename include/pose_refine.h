@@ -1003,8 +1003,19 @@ int  pr_select_disjoint(const uint32_t *order, uint32_t n_order, const pr_pair_s
  * pointer, n_peaks outside 1 .. 4, ref_stride == 0, a reference at or beyond n_scene.  n_refs == 0: PR_OK, nothing written.
  * pr_ppf_peak_pose: the formula for one peak, host only.  PR_ERR_INVALID (nothing written) for a null pointer, alpha_bin >= n_alpha or a
  * normal without a frame.
- * Not offered: votes spread to neighbouring bins, averaged cluster poses, a _multi form, an asynchronous form, colour or edge point pairs,
- * keeping a scene sample between calls. */
+ * pr_ppf_vote_multi: a table of models (at most PR_PPF_MAX_MODELS) over one scene sample, in one call: the outputs are those of pr_ppf_vote
+ * called once per model with the same scene arguments, concatenated in table order -- peaks_host[(k * n_refs + j) * n_peaks + p] and poses_host
+ * likewise for model k, reference j, peak p; acc_dev_out (may be NULL): model k's n_refs * n_model_k * n_alpha_k words, starting at the sum of
+ * the sizes of the models before it.  Every byte equals the single call's; the same model listed twice gives the same bytes twice.  A
+ * pr_ppf_model names a model as pr_ppf_vote's arguments do: the descriptor (host), pr_ppf_model_build_dev's two outputs, the sampler's host arrays
+ * and n_model; models may differ in every field of their descriptors and in n_model.  A model with n_model == 1 has no pairs and returns no peak
+ * (entries_dev may be NULL for it).  n_models == 0 or n_refs == 0: PR_OK, nothing written, no device used.  Checked before any device is touched,
+ * PR_ERR_INVALID with nothing written: n_models > PR_PPF_MAX_MODELS, a model that fails pr_ppf_vote's checks of a descriptor, n_model or
+ * PR_PPF_MAX_CELLS (the message names the model's index), reserved != 0, a null pointer, and pr_ppf_vote's checks of the scene, the peaks and the
+ * references.  One launch -- a workgroup per (model, reference), its dynamic LDS sized by the table's largest n_model * n_alpha -- one stream
+ * synchronise and one read-back per call; option "ppf_walk" selects the bucket walk as in pr_ppf_vote.
+ * Not offered: votes spread to neighbouring bins, averaged cluster poses, an asynchronous form, colour or edge point pairs, keeping a scene
+ * sample between calls, a mixed pr_pose_distance for merging the hypotheses of several models in one call. */
 #define PR_PPF_MAX_DIST_BINS    64
 #define PR_PPF_MAX_ANGLE_BINS   32
 #define PR_PPF_MAX_ALPHA_BINS   64
@@ -1041,6 +1052,17 @@ int  pr_ppf_vote(const pr_ppf_params *params, const uint32_t *offsets_dev, const
                  pr_mat4 *poses_host, uint32_t *acc_dev_out /* may be NULL */);
 int  pr_ppf_peak_pose(const pr_ppf_params *params, const pr_vec3 *model_point, const pr_vec3 *model_normal, const pr_vec3 *scene_point,
                       const pr_vec3 *scene_normal, uint32_t alpha_bin, pr_mat4 *pose_out);
+#define PR_PPF_MAX_MODELS 32
+typedef struct {
+    const pr_ppf_params *params;                           /* host                                                              */
+    const uint32_t      *offsets_dev;                      /* pr_ppf_model_build_dev's outputs                                  */
+    const pr_ppf_entry  *entries_dev;                      /* may be NULL when n_model == 1                                     */
+    const pr_vec3       *points_host, *normals_host;       /* the sampler's arrays, for the pose formula                        */
+    uint32_t             n_model, reserved;                /* reserved = 0                                                      */
+} pr_ppf_model;                /* 48 B */
+int  pr_ppf_vote_multi(const pr_ppf_model *models, uint32_t n_models, const pr_vec3 *scene_points_dev, const pr_vec3 *scene_normals_dev,
+                       uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks, pr_ppf_peak *peaks_host,
+                       pr_mat4 *poses_host, uint32_t *acc_dev_out /* may be NULL */);
 
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
@@ -1100,7 +1122,7 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *   "profile"          [0]     see below;  "sample_period" [32]: profile 2 times one call in this many
  *   "scene_cache"      [1]     keep derived scene data between calls (see "Caches" at the top)
  *   "pose_dist_chunk"  (read-only) model points a workgroup of pr_pose_distance stages at a time: where its point loop has its seams
- *   "ppf_walk"         [1]     pr_ppf_vote: 1 = a wavefront walks the buckets of its 64 scene pairs together (entry t of their concatenation goes to lane
+ *   "ppf_walk"         [1]     pr_ppf_vote[_multi]: 1 = a wavefront walks the buckets of its 64 scene pairs together (entry t of their concatenation goes to lane
  *                              t % 64, so lanes stay busy whatever the bucket lengths), 0 = every lane walks its own pair's bucket.  Same bytes either way */
 int  pr_set_option(const char *name, int value);
 int  pr_get_option(const char *name, int *value);

@@ -113,6 +113,16 @@ class PPFParams(C.Structure):
 
 
 assert C.sizeof(PPFParams) == 1320
+PPF_MAX_MODELS = 32                      # PR_PPF_MAX_MODELS
+
+
+class PPFModelDesc(C.Structure):
+    """pr_ppf_model: one model of pr_ppf_vote_multi's table (the descriptor and the sample on the host, the pair table on the device)."""
+    _fields_ = [("params", C.c_void_p), ("offsets_dev", C.c_void_p), ("entries_dev", C.c_void_p), ("points_host", C.c_void_p), ("normals_host", C.c_void_p),
+                ("n_model", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(PPFModelDesc) == 48
 
 
 class MeshRef(C.Structure):
@@ -253,6 +263,7 @@ SIGNATURES = {
     "pr_ppf_scene_points_dev": (_i32, [_vp, _u32, _vp, _vp, C.POINTER(_u32)]),
     "pr_ppf_vote": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pr_ppf_peak_pose": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "pr_ppf_vote_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_render_span": (_i32, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, Roi, _vp, _vp]),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -1548,6 +1548,13 @@ def generate_hypotheses(ppf_model: PPFModel, scene: "Scene_projective", stride: 
     if n_refs * n_peaks > POSE_DIST_MAX_POSES:
         raise ValueError(f"{n_refs} references x {n_peaks} peaks exceed POSE_DIST_MAX_POSES = {POSE_DIST_MAX_POSES}: raise stride or ref_stride")
     peaks, poses = ppf_vote(ppf_model, pts, nrm, n_scene, 0, ref_stride, n_refs, n_peaks)
+    return _merged_hypotheses(ppf_model, peaks, poses, max_hypotheses, merge_mm)
+
+
+def _merged_hypotheses(ppf_model: PPFModel, peaks, poses, max_hypotheses: int, merge_mm: Optional[float]):
+    """The tail of ``generate_hypotheses`` and, per model, of ``generate_hypotheses_multi``: one model's peaks and poses (any leading shape) to its
+    list -- the peaks with votes in the order (votes descending, index ascending), duplicates merged over the model's own sample points, the
+    votes of a group summed onto its representative, ordered again, cut to ``max_hypotheses``."""
     votes = peaks["votes"].reshape(-1).astype(np.int64)
     poses = poses.reshape(-1, 4, 4)
     live = np.flatnonzero(votes > 0)
@@ -1561,6 +1568,59 @@ def generate_hypotheses(ppf_model: PPFModel, scene: "Scene_projective", stride: 
     np.add.at(total, rep, votes)
     kept = kept[np.argsort(-total[kept], kind="stable")][:max_hypotheses]
     return poses[kept], total[kept]
+
+
+def ppf_vote_multi(ppf_models, scene_points: DeviceVector, scene_normals: DeviceVector, n_scene: int, ref_first: int = 0, ref_stride: int = 1,
+                   n_refs: Optional[int] = None, n_peaks: int = 1, want_acc: bool = False):
+    """``pr_ppf_vote_multi``: a list of ``PPFModel`` over one scene sample in one call -- (peaks PPF_PEAK[n_models, n_refs, n_peaks], poses
+    float32[n_models, n_refs, n_peaks, 4, 4]), slice k byte for byte what ``ppf_vote(ppf_models[k], ...)`` returns; with ``want_acc`` also a list of
+    the models' accumulators, uint32[n_refs, n_model_k, n_alpha_k] (tests and tools).  Every model's table is built on first use."""
+    models = list(ppf_models)
+    if len(models) > PPF_MAX_MODELS:
+        raise ValueError(f"ppf_vote_multi: {len(models)} models, at most PPF_MAX_MODELS = {PPF_MAX_MODELS}")
+    for m in models:
+        m.build()
+    if n_refs is None:
+        n_refs = 0 if ref_first >= n_scene or ref_stride < 1 else (n_scene - 1 - ref_first) // ref_stride + 1
+    table = (PPFModelDesc * max(1, len(models)))()
+    for k, m in enumerate(models):                                  # (the models themselves keep the host arrays and the device tables alive)
+        table[k] = PPFModelDesc(C.addressof(m.params), m.offsets.data(), m.entries.data(), ptr(m.points), ptr(m.normals), len(m.points), 0)
+    peaks = np.zeros((len(models), n_refs, n_peaks), PPF_PEAK)
+    poses = np.zeros((len(models), n_refs, n_peaks, 4, 4), np.float32)
+    cells = [len(m.points) * m.params.n_alpha for m in models]
+    acc = DeviceVector(max(1, n_refs * sum(cells)), np.uint32) if want_acc else None
+    check(_lib.load().pr_ppf_vote_multi(C.addressof(table), len(models), scene_points.data(), scene_normals.data(), int(n_scene), int(ref_first), int(ref_stride),
+                                        int(n_refs), int(n_peaks), ptr(peaks), ptr(poses), acc.data() if want_acc else None))
+    if not want_acc:
+        return peaks, poses
+    flat, at, accs = acc.to_host(), 0, []
+    for m, c in zip(models, cells):
+        accs.append(flat[at:at + n_refs * c].reshape(n_refs, len(m.points), m.params.n_alpha))
+        at += n_refs * c
+    return peaks, poses, accs
+
+
+def generate_hypotheses_multi(ppf_models, scene: "Scene_projective", stride: int = 4, ref_stride: int = 5, n_peaks: int = 1, max_hypotheses: int = 256,
+                              merge_mm: Optional[float] = None):
+    """``generate_hypotheses`` for several meshes in one frame: one scene sample, ONE vote call (``ppf_vote_multi``), then per model exactly
+    ``generate_hypotheses``' ordering, merge (over that model's own sample points, at its ``dist_step_mm`` unless ``merge_mm`` is given) and vote
+    summing.  Returns (mesh_index int32[n], poses float32[n, 4, 4], votes int64[n]) grouped by model in table order, votes descending within a
+    model, at most ``max_hypotheses`` per model: the slice of model k equals ``generate_hypotheses(ppf_models[k], scene, ...)`` byte for byte, and
+    (mesh_index, poses) go straight to ``refine_batch_multi`` / ``score_poses_multi`` with the models' meshes in the same order."""
+    models = list(ppf_models)
+    if len(models) == 0:
+        raise ValueError("generate_hypotheses_multi: no models")
+    empty = (np.zeros(0, np.int32), np.zeros((0, 4, 4), np.float32), np.zeros(0, np.int64))
+    pts, nrm, n_scene = ppf_scene_points(scene, stride)
+    if n_scene == 0:
+        return empty
+    n_refs = (n_scene - 1) // ref_stride + 1
+    if n_refs * n_peaks > POSE_DIST_MAX_POSES:                      # per model: every model's merge is a pose_distance_matrix of its own
+        raise ValueError(f"{n_refs} references x {n_peaks} peaks exceed POSE_DIST_MAX_POSES = {POSE_DIST_MAX_POSES}: raise stride or ref_stride")
+    peaks, poses = ppf_vote_multi(models, pts, nrm, n_scene, 0, ref_stride, n_refs, n_peaks)
+    lists = [_merged_hypotheses(m, peaks[k], poses[k], max_hypotheses, merge_mm) for k, m in enumerate(models)]
+    return (np.concatenate([np.full(len(v), k, np.int32) for k, (_, v) in enumerate(lists)]), np.concatenate([p for p, _ in lists]),
+            np.concatenate([v for _, v in lists]))
 
 
 # ------------------------------------------------------------------------------------------------

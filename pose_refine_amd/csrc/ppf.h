@@ -103,5 +103,18 @@ struct PpfRef { pr_vec3 p, n; };             // a reference as the vote kernel r
 hipError_t launch_ppf_vote(const ppf::Tables &tb, const uint32_t *offsets, const pr_ppf_entry *entries, uint32_t n_model, const pr_vec3 *points,
                            const pr_vec3 *normals, uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks,
                            pr_ppf_peak *peaks, PpfRef *refs, uint32_t *acc_out, bool cooperative, hipStream_t s);
+// pr_ppf_vote_multi: one model of the table as the kernel reads it (staged per call: pinned block -> device by launch_stage_words, whole 16-byte words)
+struct PpfModelRec {
+    ppf::Tables tb;
+    const uint32_t *offsets; const pr_ppf_entry *entries;
+    uint32_t n_model, peak_base;             // peak_base: the model's first peak, = its index in the caller's table * n_refs * n_peaks (the rows of the launch are in another order)
+    uint64_t acc_base;                       // the model's first accumulator word: n_refs * the cells of the models before it
+    uint64_t pad;
+};
+static_assert(sizeof(PpfModelRec) == 336 && sizeof(PpfModelRec) % 16 == 0, "PpfModelRec: whole 16-byte words");
+// grid (n_refs, n_models); max_cells: the largest n_model * n_alpha of the table (the launch's dynamic LDS); refs: n_refs records, written once
+hipError_t launch_ppf_vote_multi(const PpfModelRec *models, uint32_t n_models, uint32_t max_cells, const pr_vec3 *points, const pr_vec3 *normals, uint32_t n_scene,
+                                 uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks, pr_ppf_peak *peaks, PpfRef *refs, uint32_t *acc_out,
+                                 bool cooperative, hipStream_t s);
 
 }  // namespace prk

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(64) void ppf_scene_emit_kernel(const float *__restr
     }
 }
 
-// ---- voting: one workgroup per scene reference, its accumulator votes[n_model * n_alpha] in LDS -----------------------------------------------
+// ---- voting: one workgroup per scene reference (and model), its accumulator votes[n_model * n_alpha] in LDS -----------------------------------
 // Lanes run over the scene's other points; each forms the pair's key and angle and reads its bucket's bounds; every entry of the bucket is one
 // integer LDS atomic.  Bucket lengths vary by orders of magnitude, so there are two walks (option "ppf_walk", same votes):
 //   kCoop false: a lane walks its own pair's bucket -- a wavefront takes as long as its longest bucket;
@@ -103,11 +103,13 @@ __global__ __launch_bounds__(64) void ppf_scene_emit_kernel(const float *__restr
 // Then n_peaks rounds of a workgroup arg-max in the order (votes descending, cell ascending): the largest count by an LDS atomicMax, the lowest
 // cell that holds it by an atomicMin; the winner's cell is zeroed for the next round.
 struct PpfWaveStage { uint32_t start[64], lo[64]; float c[64], s[64]; };      // 1 KB per wavefront
+// The whole of a workgroup's work, for both kernels below: reference j = blockIdx.x against one model (tb, offsets, entries, n_model); peaks,
+// refs and acc_out are that model's (peaks[j * n_peaks + k], acc_out[j * n_cells + c]), the reference is stored when write_ref.
 template <bool kCoop>
-__global__ __launch_bounds__(kPpfVoteThreads) void ppf_vote_kernel(const ppf::Tables tb, const uint32_t *__restrict__ offsets, const pr_ppf_entry *__restrict__ entries,
-                                                               uint32_t n_model, const pr_vec3 *__restrict__ points, const pr_vec3 *__restrict__ normals,
-                                                               uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_peaks,
-                                                               pr_ppf_peak *__restrict__ peaks, PpfRef *__restrict__ refs, uint32_t *__restrict__ acc_out)
+__device__ __forceinline__ void ppf_vote_workgroup(const ppf::Tables &tb, const uint32_t *__restrict__ offsets, const pr_ppf_entry *__restrict__ entries,
+                                                   uint32_t n_model, const pr_vec3 *__restrict__ points, const pr_vec3 *__restrict__ normals,
+                                                   uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_peaks,
+                                                   pr_ppf_peak *__restrict__ peaks, PpfRef *__restrict__ refs, uint32_t *__restrict__ acc_out, bool write_ref)
 {
     extern __shared__ uint32_t votes[];                            // n_model * n_alpha
     __shared__ float cos_edge[PR_PPF_MAX_ANGLE_BINS + 1], alpha_edge[PR_PPF_MAX_ALPHA_BINS / 2 + 1];
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(kPpfVoteThreads) void ppf_vote_kernel(const ppf::Ta
     if ((threadIdx.x & 63u) == 0) atomicAdd(&n_pairs_s, n_pairs);
     __syncthreads();
     if (acc_out) for (uint32_t c = threadIdx.x; c < n_cells; c += kPpfVoteThreads) acc_out[(size_t)blockIdx.x * n_cells + c] = votes[c];
-    if (threadIdx.x == 0) refs[blockIdx.x] = PpfRef{ pr, nr };
+    if (write_ref && threadIdx.x == 0) refs[blockIdx.x] = PpfRef{ pr, nr };
 
     for (uint32_t k = 0; k < n_peaks; ++k) {
         if (threadIdx.x == 0) { best_votes = 0; best_cell = 0xFFFFFFFFu; }
@@ -189,6 +191,26 @@ __global__ __launch_bounds__(kPpfVoteThreads) void ppf_vote_kernel(const ppf::Ta
         }
         __syncthreads();
     }
+}
+template <bool kCoop>
+__global__ __launch_bounds__(kPpfVoteThreads) void ppf_vote_kernel(const ppf::Tables tb, const uint32_t *__restrict__ offsets, const pr_ppf_entry *__restrict__ entries,
+                                                               uint32_t n_model, const pr_vec3 *__restrict__ points, const pr_vec3 *__restrict__ normals,
+                                                               uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_peaks,
+                                                               pr_ppf_peak *__restrict__ peaks, PpfRef *__restrict__ refs, uint32_t *__restrict__ acc_out)
+{
+    ppf_vote_workgroup<kCoop>(tb, offsets, entries, n_model, points, normals, n_scene, ref_first, ref_stride, n_peaks, peaks, refs, acc_out, true);
+}
+// A table of models over one scene sample: workgroup (x, y) = (reference, model).  The model's record comes from the device table the entry point
+// staged (a wave-uniform address: scalar loads), its edge tables go from there into LDS as above; the dynamic LDS of the launch is the largest
+// model's accumulator, a workgroup uses its own model's n_model * n_alpha words of it.  The references are the same for every model: row 0 stores them.
+template <bool kCoop>
+__global__ __launch_bounds__(kPpfVoteThreads) void ppf_vote_multi_kernel(const PpfModelRec *__restrict__ models, const pr_vec3 *__restrict__ points,
+                                                                     const pr_vec3 *__restrict__ normals, uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride,
+                                                                     uint32_t n_peaks, pr_ppf_peak *__restrict__ peaks, PpfRef *__restrict__ refs, uint32_t *__restrict__ acc_out)
+{
+    const PpfModelRec &m = models[blockIdx.y];
+    ppf_vote_workgroup<kCoop>(m.tb, m.offsets, m.entries, m.n_model, points, normals, n_scene, ref_first, ref_stride, n_peaks, peaks + m.peak_base, refs,
+                              acc_out ? acc_out + m.acc_base : nullptr, blockIdx.y == 0);
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------------------
@@ -229,6 +251,18 @@ hipError_t launch_ppf_vote(const ppf::Tables &tb, const uint32_t *offsets, const
     if (!lds_opt_in(reinterpret_cast<const void *>(fn), cooperative ? 1 : 0, PR_PPF_MAX_CELLS * sizeof(uint32_t))) return hipErrorInvalidValue;
     const uint32_t lds = n_model * tb.n_alpha * (uint32_t)sizeof(uint32_t);
     hipLaunchKernelGGL(fn, dim3(n_refs), dim3(kPpfVoteThreads), lds, s, tb, offsets, entries, n_model, points, normals, n_scene, ref_first,
+                       ref_stride, n_peaks, peaks, refs, acc_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppf_vote_multi(const PpfModelRec *models, uint32_t n_models, uint32_t max_cells, const pr_vec3 *points, const pr_vec3 *normals, uint32_t n_scene,
+                                 uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks, pr_ppf_peak *peaks, PpfRef *refs, uint32_t *acc_out,
+                                 bool cooperative, hipStream_t s)
+{
+    auto *fn = cooperative ? ppf_vote_multi_kernel<true> : ppf_vote_multi_kernel<false>;
+    if (!lds_opt_in(reinterpret_cast<const void *>(fn), cooperative ? 3 : 2, PR_PPF_MAX_CELLS * sizeof(uint32_t))) return hipErrorInvalidValue;
+    // dynamic LDS is one size per launch: the largest model's accumulator (a small model next to a large one reserves the large one's)
+    hipLaunchKernelGGL(fn, dim3(n_refs, n_models), dim3(kPpfVoteThreads), max_cells * (uint32_t)sizeof(uint32_t), s, models, points, normals, n_scene, ref_first,
                        ref_stride, n_peaks, peaks, refs, acc_out);
     return hipGetLastError();
 }

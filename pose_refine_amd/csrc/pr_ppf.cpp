@@ -21,6 +21,25 @@ static int ppf_params_ok(const char *fn, const pr_ppf_params *pp)
     return PR_OK;
 }
 static ppf::Tables tables_of(const pr_ppf_params *pp) { ppf::Tables t; std::memcpy(&t, pp, sizeof t); return t; }
+// what pr_ppf_vote and pr_ppf_vote_multi ask of a model (fn: the entry point, for the table's models with the model's index behind it) ...
+static int vote_model_ok(const char *fn, const pr_ppf_params *pp, uint32_t n_model)
+{
+    PR_TRY(ppf_params_ok(fn, pp));
+    if (n_model == 0 || n_model > PR_PPF_MAX_MODEL_POINTS) { set_error("%s: n_model must be 1 .. PR_PPF_MAX_MODEL_POINTS = %d (got %u)", fn, PR_PPF_MAX_MODEL_POINTS, n_model); return PR_ERR_INVALID; }
+    if (n_model * pp->n_alpha > PR_PPF_MAX_CELLS) { set_error("%s: n_model * n_alpha = %u, at most PR_PPF_MAX_CELLS = %d (one workgroup's LDS)", fn, n_model * pp->n_alpha, PR_PPF_MAX_CELLS); return PR_ERR_INVALID; }
+    return PR_OK;
+}
+// ... and of the scene sample, the peaks and the references.  No HIP call in either.
+static int vote_refs_ok(const char *fn, uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks)
+{
+    if (n_scene == 0 || n_scene > PR_PPF_MAX_SCENE_POINTS) { set_error("%s: n_scene must be 1 .. PR_PPF_MAX_SCENE_POINTS = %d (got %u)", fn, PR_PPF_MAX_SCENE_POINTS, n_scene); return PR_ERR_INVALID; }
+    if (n_peaks == 0 || n_peaks > PR_PPF_MAX_PEAKS) { set_error("%s: n_peaks must be 1 .. PR_PPF_MAX_PEAKS = %d (got %u)", fn, PR_PPF_MAX_PEAKS, n_peaks); return PR_ERR_INVALID; }
+    if (ref_stride == 0) { set_error("%s: ref_stride must not be 0", fn); return PR_ERR_INVALID; }
+    if (ref_first >= n_scene || (n_refs > 0 && (uint64_t)ref_first + (uint64_t)(n_refs - 1) * ref_stride >= n_scene)) {
+        set_error("%s: references %u + j * %u, j < %u, but there are %u scene points", fn, ref_first, ref_stride, n_refs, n_scene); return PR_ERR_INVALID;
+    }
+    return PR_OK;
+}
 
 // the pose formula's frame, in double from the float32 normal: rows (nh, u, v)
 static bool frame_d(const pr_vec3 &n, double B[3][3])
@@ -57,6 +76,19 @@ static bool peak_pose(const pr_ppf_params *pp, const pr_vec3 &pm, const pr_vec3 
     }
     out->m[15] = 1.0f;
     return true;
+}
+
+// one model's n_pk = n_refs * n_peaks peaks as read back (pk, with the references rf) to the caller, each with its pose (an unused slot: all zero)
+static void peaks_out(const pr_ppf_params *pp, const pr_vec3 *model_points, const pr_vec3 *model_normals, uint32_t n_model, const pr_ppf_peak *pk,
+                      const prk::PpfRef *rf, size_t n_pk, uint32_t n_peaks, pr_ppf_peak *peaks_host, pr_mat4 *poses_host)
+{
+    for (size_t i = 0; i < n_pk; ++i) {
+        peaks_host[i] = pk[i];
+        std::memset(&poses_host[i], 0, sizeof(pr_mat4));
+        const prk::PpfRef &r = rf[i / n_peaks];
+        if (pk[i].votes && pk[i].model_ref < n_model)
+            (void)peak_pose(pp, model_points[pk[i].model_ref], model_normals[pk[i].model_ref], r.p, r.n, pk[i].alpha_bin, &poses_host[i]);
+    }
 }
 
 // a word (or a few) of the device into the pinned block, and wait: the totals of a build or a sample
@@ -203,15 +235,8 @@ int pr_ppf_vote(const pr_ppf_params *params, const uint32_t *offsets_dev, const 
                 pr_mat4 *poses_host, uint32_t *acc_dev_out)
 {
     const char *fn = "pr_ppf_vote";
-    PR_TRY(ppf_params_ok(fn, params));                              // every check before any device use
-    if (n_model == 0 || n_model > PR_PPF_MAX_MODEL_POINTS) { set_error("%s: n_model must be 1 .. PR_PPF_MAX_MODEL_POINTS = %d (got %u)", fn, PR_PPF_MAX_MODEL_POINTS, n_model); return PR_ERR_INVALID; }
-    if (n_model * params->n_alpha > PR_PPF_MAX_CELLS) { set_error("%s: n_model * n_alpha = %u, at most PR_PPF_MAX_CELLS = %d (one workgroup's LDS)", fn, n_model * params->n_alpha, PR_PPF_MAX_CELLS); return PR_ERR_INVALID; }
-    if (n_scene == 0 || n_scene > PR_PPF_MAX_SCENE_POINTS) { set_error("%s: n_scene must be 1 .. PR_PPF_MAX_SCENE_POINTS = %d (got %u)", fn, PR_PPF_MAX_SCENE_POINTS, n_scene); return PR_ERR_INVALID; }
-    if (n_peaks == 0 || n_peaks > PR_PPF_MAX_PEAKS) { set_error("%s: n_peaks must be 1 .. PR_PPF_MAX_PEAKS = %d (got %u)", fn, PR_PPF_MAX_PEAKS, n_peaks); return PR_ERR_INVALID; }
-    if (ref_stride == 0) { set_error("%s: ref_stride must not be 0", fn); return PR_ERR_INVALID; }
-    if (ref_first >= n_scene || (n_refs > 0 && (uint64_t)ref_first + (uint64_t)(n_refs - 1) * ref_stride >= n_scene)) {
-        set_error("%s: references %u + j * %u, j < %u, but there are %u scene points", fn, ref_first, ref_stride, n_refs, n_scene); return PR_ERR_INVALID;
-    }
+    PR_TRY(vote_model_ok(fn, params, n_model));                     // every check before any device use
+    PR_TRY(vote_refs_ok(fn, n_scene, ref_first, ref_stride, n_refs, n_peaks));
     if (n_refs == 0) return PR_OK;
     if (!offsets_dev || !entries_dev || !model_points_host || !model_normals_host || !scene_points_dev || !scene_normals_dev || !peaks_host || !poses_host) {
         set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID;
@@ -230,13 +255,66 @@ int pr_ppf_vote(const pr_ppf_params *params, const uint32_t *offsets_dev, const 
     HIP_TRY(hipStreamSynchronize(g->stream));
     const pr_ppf_peak *pk = g->h_ppf.as<pr_ppf_peak>();
     const prk::PpfRef *rf = reinterpret_cast<const prk::PpfRef *>(g->h_ppf.as<unsigned char>() + pk_bytes);
-    for (size_t i = 0; i < n_pk; ++i) {
-        peaks_host[i] = pk[i];
-        std::memset(&poses_host[i], 0, sizeof(pr_mat4));
-        const prk::PpfRef &r = rf[i / n_peaks];
-        if (pk[i].votes && pk[i].model_ref < n_model)
-            (void)peak_pose(params, model_points_host[pk[i].model_ref], model_normals_host[pk[i].model_ref], r.p, r.n, pk[i].alpha_bin, &poses_host[i]);
+    peaks_out(params, model_points_host, model_normals_host, n_model, pk, rf, n_pk, n_peaks, peaks_host, poses_host);
+    return PR_OK;
+}
+
+int pr_ppf_vote_multi(const pr_ppf_model *models, uint32_t n_models, const pr_vec3 *scene_points_dev, const pr_vec3 *scene_normals_dev, uint32_t n_scene,
+                      uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks, pr_ppf_peak *peaks_host, pr_mat4 *poses_host,
+                      uint32_t *acc_dev_out)
+{
+    const char *fn = "pr_ppf_vote_multi";
+    if (n_models > PR_PPF_MAX_MODELS) { set_error("%s: %u models, at most PR_PPF_MAX_MODELS = %d", fn, n_models, PR_PPF_MAX_MODELS); return PR_ERR_INVALID; }      // every check before any device use
+    if (n_models && !models) { set_error("%s: bad arguments (a null model table)", fn); return PR_ERR_INVALID; }
+    uint32_t max_cells = 0;
+    for (uint32_t k = 0; k < n_models; ++k) {
+        char who[64];
+        std::snprintf(who, sizeof who, "%s: model %u", fn, k);
+        PR_TRY(vote_model_ok(who, models[k].params, models[k].n_model));
+        if (models[k].reserved != 0) { set_error("%s: reserved must be 0", who); return PR_ERR_INVALID; }
+        max_cells = std::max(max_cells, models[k].n_model * models[k].params->n_alpha);
     }
+    PR_TRY(vote_refs_ok(fn, n_scene, ref_first, ref_stride, n_refs, n_peaks));
+    if (n_models == 0 || n_refs == 0) return PR_OK;
+    for (uint32_t k = 0; k < n_models; ++k)
+        if (!models[k].offsets_dev || (!models[k].entries_dev && models[k].n_model > 1) || !models[k].points_host || !models[k].normals_host) {
+            set_error("%s: model %u: bad arguments (a null pointer)", fn, k); return PR_ERR_INVALID;
+        }
+    if (!scene_points_dev || !scene_normals_dev || !peaks_host || !poses_host) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
+    PR_ENTER();
+    // one device block and its pinned twin: the model records (staged to the device) | the peaks of all models | the references (both read back)
+    const size_t n_pk = (size_t)n_refs * n_peaks, tab_bytes = sizeof(prk::PpfModelRec) * n_models, pk_bytes = sizeof(pr_ppf_peak) * n_pk * n_models,
+                 back_bytes = pk_bytes + sizeof(prk::PpfRef) * n_refs;                                                                  // multiples of 4 both
+    PR_TRY(g->ppf_out.ensure(tab_bytes + back_bytes));
+    PR_TRY(g->h_ppf.ensure(tab_bytes + back_bytes));
+    // The rows of the launch are the models by n_model, largest first: a model's pair table, and with it a workgroup's walk, grows with n_model^2, and
+    // a launch that ends with its longest workgroups has a long tail (profiles/ppf_multi/README.md: the same table takes 1.48 ms in the caller's
+    // order, 1.19 ms largest first, 1.54 ms largest last).  A record carries its model's place in the outputs, so the row order is free.
+    uint32_t row[PR_PPF_MAX_MODELS];
+    uint64_t acc_base[PR_PPF_MAX_MODELS], acc_words = 0;
+    for (uint32_t k = 0; k < n_models; ++k) {
+        row[k] = k; acc_base[k] = acc_words;
+        acc_words += (uint64_t)n_refs * models[k].n_model * models[k].params->n_alpha;
+    }
+    std::stable_sort(row, row + n_models, [&](uint32_t a, uint32_t b) { return models[a].n_model > models[b].n_model; });
+    prk::PpfModelRec *rec = g->h_ppf.as<prk::PpfModelRec>();
+    for (uint32_t r = 0; r < n_models; ++r) {
+        const pr_ppf_model &m = models[row[r]];
+        rec[r] = prk::PpfModelRec{ tables_of(m.params), m.offsets_dev, m.entries_dev, m.n_model, (uint32_t)(row[r] * n_pk), acc_base[row[r]], 0 };
+    }
+    unsigned char *d = g->ppf_out.as<unsigned char>(), *h = g->h_ppf.as<unsigned char>(), *hm = g->h_ppf.dev_as<unsigned char>();
+    HIP_TRY(prk::launch_stage_words(hm, d, tab_bytes, g->stream));
+    HIP_TRY(prk::launch_ppf_vote_multi(reinterpret_cast<const prk::PpfModelRec *>(d), n_models, max_cells, scene_points_dev, scene_normals_dev, n_scene, ref_first,
+                                       ref_stride, n_refs, n_peaks, reinterpret_cast<pr_ppf_peak *>(d + tab_bytes), reinterpret_cast<prk::PpfRef *>(d + tab_bytes + pk_bytes),
+                                       acc_dev_out, opt.ppf_walk != 0, g->stream));
+    if (acc_dev_out) g_writes.note(acc_dev_out, sizeof(uint32_t) * acc_words);
+    HIP_TRY(prk::launch_copy_words32(d + tab_bytes, hm + tab_bytes, (uint32_t)(back_bytes / sizeof(uint32_t)), g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    const pr_ppf_peak *pk = reinterpret_cast<const pr_ppf_peak *>(h + tab_bytes);
+    const prk::PpfRef *rf = reinterpret_cast<const prk::PpfRef *>(h + tab_bytes + pk_bytes);
+    for (uint32_t k = 0; k < n_models; ++k)
+        peaks_out(models[k].params, models[k].points_host, models[k].normals_host, models[k].n_model, pk + k * n_pk, rf, n_pk, n_peaks, peaks_host + k * n_pk,
+                  poses_host + k * n_pk);
     return PR_OK;
 }
 

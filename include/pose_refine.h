@@ -1064,6 +1064,89 @@ int  pr_ppf_vote_multi(const pr_ppf_model *models, uint32_t n_models, const pr_v
                        uint32_t n_scene, uint32_t ref_first, uint32_t ref_stride, uint32_t n_refs, uint32_t n_peaks, pr_ppf_peak *peaks_host,
                        pr_mat4 *poses_host, uint32_t *acc_dev_out /* may be NULL */);
 
+/* ---- support planes: the dominant planes of a depth frame, peeled one after another ---------------------------------------------------------
+ * The voting above assumes a frame in which the object is most of what there is.  A real frame has a table, a bin floor or a wall behind the
+ * parts: at stride 4 it holds more samples than PR_PPF_MAX_SCENE_POINTS, most pairs are plane-plane pairs, and the refiner feels the plane.
+ * These entry points find the planes, label their pixels and clear them from the depth frame; the cleared frame goes unchanged into
+ * pr_scene_proj_prepare_dev, pr_scene_nn_prepare_dev, the sampler above and the scorers.  The method is a consensus over candidates that already
+ * carry a normal: ONE oriented scene point defines a plane, so a candidate costs nothing to make and the work is counting its support.  Every
+ * integer below is fixed by this text; per-sample arithmetic is float32 without contraction in the stated order, + - * only, no transcendental
+ * function; the refit is exact integer arithmetic up to one conversion to double.  dot(a, b) = (ax*bx + ay*by) + az*bz as above; a pixel "has a
+ * normal" when a component of its normal is != 0.
+ *   sample: the pixels (x, y) with x % stride == 0 and y % stride == 0 of a full-frame pr_scene_proj (dense pcd and normal, metres) that have
+ *     a normal, pcd z > 0 and pcd.z * 1000.0f <= 65535.0f, in row-major order: point = pcd * 1000.0f per component (mm), normal as it is, and the
+ *     pixel's index y * width + x.  More than PR_PLANE_MAX_SAMPLES: PR_ERR_INVALID with nothing written (raise the stride).
+ *   candidates: candidate c is sample c * cand_stride, c < n_candidates = ceil(n_samples / cand_stride).  More than PR_PLANE_MAX_CANDIDATES:
+ *     PR_ERR_INVALID with nothing written (raise cand_stride).  A sample is ALIVE while its pixel's label is 0.
+ *   the normal test of (a, b):  cos_min == -2.0f (the test is off), or dot(a, b) >= cos_min.
+ *   support of an alive candidate (p_c, n_c): the number of alive samples (p_j, m_j), itself included, with
+ *     r = dot(n_c, p_j - p_c) (the difference component by component first), fabsf(r) <= tau_mm, and the normal test of (n_c, m_j).
+ *     A dead candidate has support 0.
+ *   winner of a round: the largest support, the lowest candidate index on a tie.  Support below min_support (or no support at all), or a
+ *     refit that pr_plane_from_moments refuses, ends the peel: fewer planes than asked for, not an error.
+ *   refit: over the winner's inliers (the same two tests) q = (int64) rint((double) coordinate * 16.0) per coordinate and the ten moments
+ *     n, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz as exact 64-bit integer sums (any order gives the same bytes; no float atomics anywhere).
+ *     pr_plane_from_moments: the scatter matrix C_ab = n * S_ab - S_a * S_b exactly in 128-bit integers, each entry converted to double once
+ *     (n^2 times the covariance, in 1/16 mm units); cyclic Jacobi in float64 on the symmetric 3 x 3 with V = I at the start: at most
+ *     PR_PLANE_MAX_SWEEPS sweeps; before each, off = the largest |C[i][j]|, i < j, diag = the largest |C[i][i]|, stop when off <= 2^-56 * diag;
+ *     a sweep rotates (p, q) = (0,1), (0,2), (1,2) by pr_info_eig's rotation (skipped when C[p][q] == 0: theta = (C[q][q] - C[p][p]) /
+ *     (2 C[p][q]), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) with sign(0) = +1, c = 1 / sqrt(t^2 + 1), s = t c; C[p][p] -= t C[p][q],
+ *     C[q][q] += t C[p][q], C[p][q] = 0; for the third index k: (C[k][p], C[k][q]) <- (c C[k][p] - s C[k][q], s C[k][p] + c C[k][q]), mirrored;
+ *     for every row k of V likewise).  lambda[i] = C[i][i]; the plane's eigenvalue is the smallest, the lowest index on a tie; its column of V,
+ *     divided by sqrt(dot) of itself, is the normal nu.  offset = dot(nu, (Sx, Sy, Sz)) / n / 16 in double (mm; dot as above), and the plane is
+ *     the points with dot(nu, p) == offset.  Orientation, towards the camera: offset <= 0 -- when offset > 0, or offset == 0 and the first
+ *     non-zero component of nu is positive, nu and offset are negated.  rms = sqrt(max(lambda_min, 0)) / n / 16 (mm).  PR_ERR_INVALID for
+ *     n < 3, an all-zero scatter matrix or a column without a length.  pr_plane holds normal and offset_mm ROUNDED ONCE to float32.
+ *     eig_out (may be NULL, as rms_mm_out): the plane's eigenvalue first, then the other two in index order.
+ *   labels, one uint8 per pixel of the full-resolution frame: pcd z <= 0: PR_PLANE_NO_DEPTH.  Otherwise, in round k = 1, 2, ... with the
+ *     round's float32 plane (nu, offset): h = dot(nu, pcd * 1000.0f) - offset (the products per component first); a pixel whose label is
+ *     still 0 takes k when fabsf(h) <= label_tau_mm and, if it has a normal, the normal test of (nu, its normal) holds; else, in round 1 only
+ *     and when drop_behind is set, PR_PLANE_BEHIND when h < -label_tau_mm (farther from the camera than plane 1: under the table, behind the
+ *     wall); else it stays 0.  Round k + 1 runs over the samples that are still alive.
+ *   cleared depth: depth_out[i] = labels[i] == 0 ? depth_in[i] : 0 (int32 or uint16 by depth_is_i32); depth_out may be depth_in.
+ * pr_plane_describe (host only): fills and checks the parameters.  PR_ERR_INVALID with nothing written: stride 0 or > PR_PPF_MAX_STRIDE,
+ * cand_stride 0, a tau that is not finite or < 0, cos_min neither -2 nor in [-1, 1], min_support < 3, n_planes outside 1 ..
+ * PR_PLANE_MAX_PLANES, a null out.  Every entry point below checks its pr_plane_params against these rules.
+ * pr_scene_planes_dev: planes_host[PR_PLANE_MAX_PLANES is enough; n_planes are needed], *n_found of them filled (candidate and support: the
+ * winner; labelled / behind: the pixels the round gave k / PR_PLANE_BEHIND).  moments_host (may be NULL): 10 int64 per found plane.
+ * support_dev_out (may be NULL; tests and tools): n_planes rows of PR_PLANE_MAX_CANDIDATES uint32, row k the supports of round k + 1 in its
+ * first n_candidates words; everything else 0 (the row of a round that ended the peel is kept, the rows behind it are 0).
+ * labels_dev_out: width * height uint8.  depth_dev_out may be NULL (no cleared depth).  Synchronous, on the calling thread's context; one
+ * stream synchronise and one small pinned read-back for the sample's size, one per round and one at the end; no hipMemcpy on the path.  An
+ * empty sample: PR_OK, *n_found = 0, every measured pixel labelled 0, the depth copied.  Checked before any device is touched: the
+ * parameters, null pointers, the frame's size.  The same frame gives the same bytes.
+ * pr_scene_planes_host: the same over host arrays (pcd and normal as pr_scene_proj_prepare leaves them), from the same shared code: the CPU
+ * twin the device is held to; it runs without a GPU.  support_out: host, same layout.
+ * Not offered: connected components of what is left, RANSAC over point triples (a candidate is one oriented point), cylinders and spheres, an
+ * asynchronous form, a refit iterated to convergence. */
+#define PR_PLANE_MAX_SAMPLES    65536
+#define PR_PLANE_MAX_CANDIDATES 4096
+#define PR_PLANE_MAX_PLANES     4
+#define PR_PLANE_MAX_SWEEPS     16
+#define PR_PLANE_BEHIND         254
+#define PR_PLANE_NO_DEPTH       255
+typedef struct {
+    uint32_t stride, cand_stride;
+    float    tau_mm, label_tau_mm, cos_min;
+    uint32_t min_support, n_planes, drop_behind;
+} pr_plane_params;             /* 32 B */
+typedef struct {
+    float    normal[3], offset_mm;     /* dot(normal, p_mm) == offset_mm, offset_mm <= 0                                              */
+    uint32_t candidate, support;       /* the winner and its support                                                                  */
+    uint32_t labelled, behind;         /* pixels of the frame this round labelled k / PR_PLANE_BEHIND                                 */
+    float    rms_mm;
+    uint32_t reserved[3];
+} pr_plane;                    /* 48 B */
+int  pr_plane_describe(uint32_t stride, uint32_t cand_stride, float tau_mm, float label_tau_mm, float cos_min, uint32_t min_support, uint32_t n_planes,
+                       int drop_behind, pr_plane_params *out);
+int  pr_plane_from_moments(const int64_t moments[10], double normal_out[3], double *offset_mm_out, double *rms_mm_out, double eig_out[3]);
+int  pr_scene_planes_dev(const pr_scene_proj *scene, const void *depth_dev, int depth_is_i32, const pr_plane_params *params, uint8_t *labels_dev_out,
+                         void *depth_dev_out /* may be NULL */, pr_plane *planes_host, int64_t *moments_host /* may be NULL */,
+                         uint32_t *support_dev_out /* may be NULL */, uint32_t *n_found);
+int  pr_scene_planes_host(const float *pcd, const float *normal, const void *depth, int depth_is_i32, size_t width, size_t height,
+                          const pr_plane_params *params, uint8_t *labels_out, void *depth_out /* may be NULL */, pr_plane *planes_out,
+                          int64_t *moments_out /* may be NULL */, uint32_t *support_out /* may be NULL */, uint32_t *n_found);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

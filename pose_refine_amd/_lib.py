@@ -125,6 +125,22 @@ class PPFModelDesc(C.Structure):
 assert C.sizeof(PPFModelDesc) == 48
 
 
+# pr_plane: one dominant plane of a frame (pr_scene_planes_dev / _host); pr_plane_params: what pr_plane_describe fills
+PLANE = np.dtype([("normal", "<f4", (3,)), ("offset_mm", "<f4"), ("candidate", "<u4"), ("support", "<u4"), ("labelled", "<u4"), ("behind", "<u4"),
+                  ("rms_mm", "<f4"), ("reserved", "<u4", (3,))])
+PLANE_MAX_SAMPLES, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_BEHIND, PLANE_NO_DEPTH = 65536, 4096, 4, 254, 255        # PR_PLANE_*
+assert PLANE.itemsize == 48
+
+
+class PlaneParamsDesc(C.Structure):
+    """pr_plane_params: the sample, the support and label tests and the number of planes of a peel (pr_plane_describe checks and fills it)."""
+    _fields_ = [("stride", C.c_uint32), ("cand_stride", C.c_uint32), ("tau_mm", C.c_float), ("label_tau_mm", C.c_float), ("cos_min", C.c_float),
+                ("min_support", C.c_uint32), ("n_planes", C.c_uint32), ("drop_behind", C.c_uint32)]
+
+
+assert C.sizeof(PlaneParamsDesc) == 32
+
+
 class MeshRef(C.Structure):
     """pr_mesh_ref: one mesh of a mixed batch (pr_*_multi)."""
     _fields_ = [("tris_dev", C.c_void_p), ("n_tris", C.c_size_t)]
@@ -264,6 +280,10 @@ SIGNATURES = {
     "pr_ppf_vote": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pr_ppf_peak_pose": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "pr_ppf_vote_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "pr_plane_describe": (_i32, [_u32, _u32, C.c_float, C.c_float, C.c_float, _u32, _u32, _i32, _vp]),
+    "pr_plane_from_moments": (_i32, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
+    "pr_scene_planes_dev": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "pr_scene_planes_host": (_i32, [_vp, _vp, _vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
     "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_render_span": (_i32, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, Roi, _vp, _vp]),

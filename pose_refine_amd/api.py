@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -1621,6 +1621,96 @@ def generate_hypotheses_multi(ppf_models, scene: "Scene_projective", stride: int
     lists = [_merged_hypotheses(m, peaks[k], poses[k], max_hypotheses, merge_mm) for k, m in enumerate(models)]
     return (np.concatenate([np.full(len(v), k, np.int32) for k, (_, v) in enumerate(lists)]), np.concatenate([p for p, _ in lists]),
             np.concatenate([v for _, v in lists]))
+
+
+# ------------------------------------------------------------------------------------------------
+# support planes: the dominant planes of a frame, their labels and the cleared depth (pr_plane_* / pr_scene_planes_*; the definition is in include/pose_refine.h)
+# ------------------------------------------------------------------------------------------------
+def PlaneParams(stride: int = 4, cand_stride: int = 16, tau_mm: float = 3.0, label_tau_mm: float = 6.0, cos_min: float = 0.9, min_support: int = 500,
+                n_planes: int = 1, drop_behind: bool = True) -> PlaneParamsDesc:
+    """``pr_plane_describe`` (host only): the parameters of a peel, checked.  The defaults are for a 640 x 480 frame in mm with a table or a wall:
+    every 4th pixel a sample, every 16th sample a candidate, 3 mm to support a candidate and 6 mm to take a fitted plane's label, normals within
+    about 26 degrees (``cos_min=-2`` switches the normal test off), at least 500 supporting samples, and what lies behind plane 1 dropped."""
+    pp = PlaneParamsDesc()
+    check(_lib.load().pr_plane_describe(int(stride), int(cand_stride), float(tau_mm), float(label_tau_mm), float(cos_min), int(min_support), int(n_planes),
+                                        int(bool(drop_behind)), C.addressof(pp)))
+    return pp
+
+
+def _plane_params(params, kw) -> PlaneParamsDesc:
+    if params is not None and kw:
+        raise ValueError("pass either params or keyword parameters")
+    return params if params is not None else PlaneParams(**kw)
+
+
+def plane_from_moments(moments):
+    """``pr_plane_from_moments`` (host only): (normal float64[3], offset_mm, rms_mm, eig float64[3]) of the ten int64 moments n, Sx, Sy, Sz, Sxx, Sxy,
+    Sxz, Syy, Syz, Szz on the 1/16 mm grid.  ``eig[0]`` is the plane's eigenvalue (the smallest), the other two follow in index order."""
+    m = np.ascontiguousarray(moments, dtype=np.int64).reshape(10)
+    nrm, eig = np.zeros(3, np.float64), np.zeros(3, np.float64)
+    off, rms = C.c_double(0.0), C.c_double(0.0)
+    check(_lib.load().pr_plane_from_moments(ptr(m), ptr(nrm), C.byref(off), C.byref(rms), ptr(eig)))
+    return nrm, off.value, rms.value, eig
+
+
+def scene_planes(scene: "Scene_projective", scene_depth, params: Optional[PlaneParamsDesc] = None, depth_out: Optional[DeviceVector] = None,
+                 want_moments: bool = False, want_supports: bool = False, **kw):
+    """``pr_scene_planes_dev``: the dominant planes of a full-frame projective scene and its depth frame (a DeviceVector or a host image, uint16 or
+    int32).  Returns (planes PLANE[n_found], labels DeviceVector uint8[width * height], cleared DeviceVector of the depth's dtype): ``labels`` holds
+    the round (1-based) that took a pixel, ``PLANE_BEHIND``, ``PLANE_NO_DEPTH`` or 0; ``cleared`` is the depth with every labelled pixel set to 0 --
+    it goes as it is into ``init_Scene_projective_device``, ``init_Scene_nn_device`` and the scorers.  ``depth_out``: where the cleared depth goes
+    (the input itself is allowed).  ``want_moments`` adds int64[n_found, 10], ``want_supports`` the support table uint32[n_planes, PLANE_MAX_CANDIDATES]
+    (tests and tools; a row's first n_candidates words are used).  Parameters: a ``PlaneParams`` or its keywords."""
+    if scene.kind != SCENE_PROJ:
+        raise ValueError("scene_planes takes a full-frame Scene_projective")
+    pp = _plane_params(params, kw)
+    W, H = scene.width, scene.height
+    sd = _scene_depth_dev(scene_depth, W, H)
+    out = depth_out if depth_out is not None else DeviceVector(W * H, sd.dtype)
+    if out.dtype != sd.dtype or out.size() != W * H:
+        raise ValueError("depth_out must have the depth's dtype and size")
+    labels = DeviceVector(W * H, np.uint8)
+    planes = np.zeros(PLANE_MAX_PLANES, PLANE)
+    moments = np.zeros((PLANE_MAX_PLANES, 10), np.int64)
+    sup = DeviceVector(pp.n_planes * PLANE_MAX_CANDIDATES, np.uint32) if want_supports else None
+    d = scene.desc()
+    n = C.c_uint32(0)
+    check(_lib.load().pr_scene_planes_dev(C.addressof(d), sd.data(), int(sd.dtype == np.int32), C.addressof(pp), labels.data(), out.data(), ptr(planes),
+                                          ptr(moments), sup.data() if want_supports else None, C.byref(n)))
+    res = [planes[:n.value].copy(), labels, out]
+    if want_moments:
+        res.append(moments[:n.value].copy())
+    if want_supports:
+        res.append(sup.to_host().reshape(pp.n_planes, PLANE_MAX_CANDIDATES))
+    return tuple(res)
+
+
+def scene_planes_host(pcd, normal, scene_depth, width: int, height: int, params: Optional[PlaneParamsDesc] = None, want_moments: bool = False,
+                      want_supports: bool = False, **kw):
+    """``pr_scene_planes_host``: ``scene_planes`` over host arrays (pcd and normal float32[height * width, 3] as ``init_Scene_projective_cuda`` keeps
+    them in ``pcd_host`` / ``normal_host``, the depth image uint16 or int32), on the CPU, from the same definition.  Returns (planes, labels
+    uint8[height, width], cleared depth[height, width]) and on request moments and the support table uint32[n_planes, PLANE_MAX_CANDIDATES]; runs without a GPU."""
+    pp = _plane_params(params, kw)
+    p, m = _f32(pcd, (-1, 3)), _f32(normal, (-1, 3))
+    dep = np.ascontiguousarray(scene_depth)
+    if dep.dtype not in (np.uint16, np.int32):
+        raise ValueError("scene depth must be CV_16U or CV_32S")
+    if len(p) != width * height or len(m) != width * height or dep.size != width * height:
+        raise ValueError(f"pcd, normal and depth must hold {width} x {height} pixels")
+    labels = np.zeros((height, width), np.uint8)
+    cleared = np.zeros((height, width), dep.dtype)
+    planes = np.zeros(PLANE_MAX_PLANES, PLANE)
+    moments = np.zeros((PLANE_MAX_PLANES, 10), np.int64)
+    sup = np.zeros((pp.n_planes, PLANE_MAX_CANDIDATES), np.uint32)
+    n = C.c_uint32(0)
+    check(_lib.load().pr_scene_planes_host(ptr(p), ptr(m), ptr(dep), int(dep.dtype == np.int32), width, height, C.addressof(pp), ptr(labels), ptr(cleared),
+                                           ptr(planes), ptr(moments), ptr(sup) if want_supports else None, C.byref(n)))
+    res = [planes[:n.value].copy(), labels, cleared]
+    if want_moments:
+        res.append(moments[:n.value].copy())
+    if want_supports:
+        res.append(sup)
+    return tuple(res)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -814,6 +814,8 @@ struct Ctx {
     PinBuf h_pd_mats, h_pd_rec;      // the matrices on their way in, the records on their way out
     DevBuf ppf_tmp, ppf_out;         // pr_ppf_*: bucket counts / cursors of a model build or the row counts and offsets of a scene sample; the peaks and references of a vote (pr_ppf_vote_multi: behind the table's model records)
     PinBuf h_ppf;                    // ... and a build's or sample's total, a vote's peaks and references, on their way to the caller (pr_ppf_vote_multi: behind the model records on their way to the device)
+    DevBuf plane_tmp;                // pr_scene_planes_dev: the rounds' records, the row counts and offsets of the sample, the samples, the support table (unless the caller's)
+    PinBuf h_plane;                  // ... the sample's size, then the rounds' records on their way to the caller
     DevBuf vsd_rec;                  // pr_pose_vsd: the records of a chunk's pairs
     PinBuf h_vsd;                    // ... on their way to the caller
     DevBuf solid_far, solid_rec;     // pr_render_span / pr_pose_penetration: the far plane of the boxes in g->depth (same offsets); the P x P pair records

@@ -1188,6 +1188,10 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *                              holds a 4x4-pixel patch and the raster's depth atomics make fewer requests; 0 = row-major boxes.  Same results either
  *                              way ("stat_band_batches", read-only: asynchronous batches of this process that ran on banded boxes; "box_pack",
  *                              read-only: the ints a box's slot is rounded up to)
+ *   "resident_loop"    [1]     asynchronous path, projective scene, device solve with "fused_solve", no timed call: every pass of a sub-batch runs in
+ *                              ONE launch, a 1024-lane workgroup per hypothesis that meets once per pass in LDS; 0 = one launch per pass and pose group
+ *                              everywhere.  Same results either way.  A plan whose blocks would need more than 64 KiB of LDS (over 127 blocks per hypothesis)
+ *                              keeps the multi-launch loop ("stat_resident_batches", read-only: sub-batches of this process whose loop ran as one launch)
  *   "nn_stack"         [1]     kd-tree query: per-lane LDS stack (1) or the reference's stackless walk (0)
  *   "nn_compact"       [1]     stack query on 32-byte node records with 16-bit outward-rounded boxes (0: exact 64-byte records)
  *   "host_worker"      [1]     host solve: a batch given to pr_refine_submit runs on a library-owned helper thread of its slot (private context: its own

@@ -140,10 +140,12 @@ __device__ __forceinline__ void accumulate_point(Acc29 &acc, float sx, float sy,
     else if constexpr (kRobust) (void)accumulate_weighted(acc, sx, sy, sz, c, rb);
     else accumulate(acc, sx, sy, sz, c);
 }
+// `tib`: the lane's place in the 256-lane block of the canonical tree.  icp_pass_kernel's workgroup IS that block (vb_accumulate below);
+// icp_loop_cu_kernel hands a (virtual block, wavefront) pair to any of its sixteen wavefronts: tib = 64 * wavefront-of-the-block + lane.
 template <class Scene, bool kNN, int kStack, bool kScoreOnly = false, bool kRobust = false>
-__device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, uint32_t n, uint32_t first, uint32_t steps, bool xf,
-                                              const float (&M)[12], const Scene &scene, const int4 *lds_topo, int *stk_node, float *stk_lb,
-                                              uint32_t *nn_prev = nullptr, bool nn_seeded = false, const RobustW &rb = RobustW{})
+__device__ __forceinline__ void vb_accumulate_at(uint32_t tib, float (&acc_out)[29], float *cl, uint32_t n, uint32_t first, uint32_t steps, bool xf,
+                                                 const float (&M)[12], const Scene &scene, const int4 *lds_topo, int *stk_node, float *stk_lb,
+                                                 uint32_t *nn_prev = nullptr, bool nn_seeded = false, const RobustW &rb = RobustW{})
 {
     (void)nn_prev; (void)nn_seeded; (void)rb;
     struct { uint32_t steps; } b{ steps };
@@ -159,7 +161,7 @@ __device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, u
     // rate of exactly those gathers (TA busy 64 %, VALU 54 %: profiles/r02/sq_proj_*.md), not by issue slots or HBM.
     auto point_of = [&](uint32_t j0, uint32_t i) { return j0 + i * kBlockThreads; };
     auto load_step = [&](uint32_t s, float (&p)[12], uint32_t &j0, uint32_t &cnt) {
-        j0 = first + s * kPointsPerStep + threadIdx.x;
+        j0 = first + s * kPointsPerStep + tib;
         cnt = (j0 >= n) ? 0u : (((n - j0 + kBlockThreads - 1u) / kBlockThreads < kPointsPerLane) ? (n - j0 + kBlockThreads - 1u) / kBlockThreads : kPointsPerLane);
         // unconditional loads (a lane past the end re-reads the cloud's last point and never uses it: `i < cnt` gates every use)
         const uint32_t last = n - 1u;                                // n >= 1 here: the workgroup has points
@@ -293,14 +295,20 @@ __device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, u
 #endif
     acc_export(acc, acc_out);
 }
+template <class Scene, bool kNN, int kStack, bool kScoreOnly = false, bool kRobust = false>
+__device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, uint32_t n, uint32_t first, uint32_t steps, bool xf,
+                                              const float (&M)[12], const Scene &scene, const int4 *lds_topo, int *stk_node, float *stk_lb,
+                                              uint32_t *nn_prev = nullptr, bool nn_seeded = false, const RobustW &rb = RobustW{})
+{
+    vb_accumulate_at<Scene, kNN, kStack, kScoreOnly, kRobust>(threadIdx.x, acc_out, cl, n, first, steps, xf, M, scene, lds_topo, stk_node, stk_lb, nn_prev, nn_seeded, rb);
+}
 
-// canonical tree, second half: wave (balanced pairwise over lanes) -> ((w0+w1)+w2)+w3.  Returns, in threads 0..28, the
-// workgroup sum of component threadIdx.x.  Contains one __syncthreads().
+// canonical tree, second half, the wavefront's part: balanced pairwise over the 64 lanes.  `row` (LDS, kAccStride floats) receives the
+// wavefront's 29 sums; `lane` is the lane in the wavefront.  No barrier in here.
 template <bool kScoreOnly = false>
-__device__ __forceinline__ float vb_reduce(float (&acc)[29], float (*wsum)[kAccStride])
+__device__ __forceinline__ void wave_reduce(float (&acc)[29], uint32_t lane, float *row)
 {
     constexpr int kFirst = kScoreOnly ? 27 : 0;                  // score-only passes carry zeros in sums 0..26
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #if PR_PASS_TAIL_PRIO
     __builtin_amdgcn_s_setprio(PR_PASS_TAIL_PRIO);               // a wavefront in its reduction tail goes first: its workgroup retires sooner and frees its slots
 #endif
@@ -345,8 +353,8 @@ __device__ __forceinline__ float vb_reduce(float (&acc)[29], float (*wsum)[kAccS
         }
         if (lane >= 48) {
             const uint32_t t = 63u - lane;
-            wsum[wave][t] = p4[0];
-            if (16u + t < 29u) wsum[wave][16u + t] = p4[1];
+            row[t] = p4[0];
+            if (16u + t < 29u) row[16u + t] = p4[1];
         }
     } else
     {
@@ -362,9 +370,16 @@ __device__ __forceinline__ float vb_reduce(float (&acc)[29], float (*wsum)[kAccS
 #undef PR_TREE_LEVEL
     if (lane == 63) {
 #pragma unroll
-        for (int i = 0; i < 29; ++i) wsum[wave][i] = acc[i];
+        for (int i = 0; i < 29; ++i) row[i] = acc[i];
     }
     }
+}
+// ... and the block's: wave_reduce of its four wavefronts -> ((w0+w1)+w2)+w3.  Returns, in threads 0..28, the
+// workgroup sum of component threadIdx.x.  Contains one __syncthreads().
+template <bool kScoreOnly = false>
+__device__ __forceinline__ float vb_reduce(float (&acc)[29], float (*wsum)[kAccStride])
+{
+    wave_reduce<kScoreOnly>(acc, threadIdx.x & 63, wsum[threadIdx.x >> 6]);
     __syncthreads();
     float t = 0.0f;
     if (threadIdx.x < 29) t = ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];

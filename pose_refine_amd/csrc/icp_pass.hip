@@ -90,6 +90,120 @@ __device__ __forceinline__ float sum_partials(const float *partial, uint32_t pos
     return total;
 }
 
+// ================================================================================================
+//  The whole loop of a hypothesis in ONE workgroup (option "resident_loop", asynchronous fused path, packed projective scene, device solve):
+//  grid = hypotheses, 1024 lanes = 16 wavefronts on one compute unit, all passes in one launch.  What the multi-launch loop pays per pass --
+//  a launch, a ragged last round of workgroups, partial sums and an arrival ticket through memory, a PoseMeta round trip -- becomes two
+//  LDS barriers.  No workgroup waits for another one: a batch larger than the chip runs in rounds.
+//  Unit of work: item 4 * vb + w = wavefront w of virtual block vb of the canonical tree (vb_accumulate_at with tib = 64 w + lane), always
+//  taken by wavefront (4 * vb + w) mod 16.  The mapping never changes, so a lane only reads cloud points that it wrote itself (or that
+//  were there before the launch): the cloud stays in memory, moved and written back per pass exactly as icp_pass_kernel does, no fence.
+//  Per pass: every wavefront leaves the 29 sums of its items in LDS row [vb][w] (wave_reduce) | barrier | wavefront 0 forms
+//  ((w0+w1)+w2)+w3 per block, adds the blocks in block order from 0.0f (sum_partials' sequence), runs pose_iteration_wave and leaves the
+//  update and the finished flag in LDS | barrier | everyone reads them.  Trip count and early exit are read from LDS behind the second
+//  barrier, so every wavefront -- also one without items -- meets both barriers of every pass.
+//  DevIcpState stays in the LDS header over the loop (only wavefront 0 touches it; registers are left to the point work) and is stored once;
+//  PoseMeta is left as the multi-launch loop leaves it (kSkip, the last update).  Same source per point, same tree: the same bytes.
+//  LDS (dynamic): b.nblk * 4 rows of kAccStride floats, then kLoopHeader words: [0..11] update, [12] finished, [16..35] DevIcpState.
+// ================================================================================================
+constexpr uint32_t kLoopLanes = 1024, kLoopWaves = kLoopLanes / 64, kLoopHeader = 64;
+// (Measured and not kept: the two barriers with a fence on LDS alone, so that a wavefront does not wait for its cloud stores before it meets the
+// others -- 330.2-332.9 k against 329.7-332.5 k poses/s for __syncthreads, five alternating runs on one box.)
+static_assert(sizeof(DevIcpState) == 20 * sizeof(uint32_t), "the LDS header holds DevIcpState as 20 words");
+size_t icp_loop_cu_lds_bytes(uint32_t nblk) { return ((size_t)nblk * 4 * kAccStride + kLoopHeader) * sizeof(float); }
+
+template <class Scene>
+__global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel(IcpBatch b, Scene scene)
+{
+    extern __shared__ __attribute__((aligned(16))) float loop_lds[];
+    const uint32_t pose = blockIdx.x;
+    const PoseMeta &pm = b.meta[pose];                           // uniform address: one 64-byte scalar load
+    const int32_t st0 = pm.state;
+    const uint32_t n = pm.count;
+    if (st0 == kSkip || n == 0) return;                          // (whole workgroup, ahead of every barrier)
+    const uint32_t ppb = b.steps * kPointsPerStep;
+    const uint32_t items = ((n + ppb - 1) / ppb) * 4u;           // <= 4 * b.nblk: the cloud fits its pixel box
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float *hdr = loop_lds + (size_t)b.nblk * 4 * kAccStride;
+    uint32_t *hdw = reinterpret_cast<uint32_t *>(hdr);
+    float *cl = reinterpret_cast<float *>(b.cloud + pm.start);
+    bool xf = (st0 == kRunWithTransform) && !b.pre_transformed;
+    float M[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) M[i] = xf ? pm.xform[i] : 0.0f;
+    if (wave == 0 && lane < 20) hdw[16 + lane] = reinterpret_cast<const uint32_t *>(b.st + pose)[lane];
+
+    const uint32_t last_it = (uint32_t)b.crit.max_iteration;
+    uint32_t it = 0;
+    for (;; ++it) {
+        const bool score_only = it == last_it;                   // uniform: the final pass needs sums 27 and 28 only
+        for (uint32_t item = wave; item < items; item += kLoopWaves) {
+            const uint32_t vb = item >> 2, tib = ((item & 3u) << 6) | lane;
+            float acc[29];
+            float *row = loop_lds + (size_t)item * kAccStride;
+            if (score_only) {
+                vb_accumulate_at<Scene, false, 0, true>(tib, acc, cl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                wave_reduce<true>(acc, lane, row);
+            } else {
+                vb_accumulate_at<Scene, false, 0>(tib, acc, cl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                wave_reduce(acc, lane, row);
+            }
+        }
+        __syncthreads();                                         // every item's row is in LDS
+        if (wave == 0) {
+            float total = 0.0f;
+            if (lane < 29) {
+                const float *r = loop_lds + lane;
+                for (uint32_t i = 0; i < items; i += 4u, r += 4 * kAccStride)
+                    total += ((r[0] + r[kAccStride]) + r[2 * kAccStride]) + r[3 * kAccStride];
+            }
+            DevIcpState s;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s.T[i] = hdr[16 + i];
+            s.fitness = hdr[32]; s.rmse = hdr[33]; s.done = (int32_t)hdw[34]; s.passes = (int32_t)hdw[35];
+            float E[16];
+            const bool finished = pose_iteration_wave(total, n, s, b.crit, it, E);
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) hdr[16 + i] = s.T[i];
+                hdr[32] = s.fitness; hdr[33] = s.rmse; hdw[35] = (uint32_t)s.passes;
+                if (!finished) {
+#pragma unroll
+                    for (int i = 0; i < 12; ++i) hdr[i] = E[i];
+                }
+                hdw[12] = (finished || it >= last_it) ? 1u : 0u;
+            }
+        }
+        __syncthreads();                                         // update and flag are in LDS; the rows have been read
+        if (__builtin_amdgcn_readfirstlane(hdw[12]) != 0u) break;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) M[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hdr[i])));
+        xf = true;
+    }
+    if (threadIdx.x == 0) {                                      // what the multi-launch loop leaves in memory
+        DevIcpState s;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s.T[i] = hdr[16 + i];
+        s.fitness = hdr[32]; s.rmse = hdr[33]; s.done = 1; s.passes = (int32_t)hdw[35];
+        b.st[pose] = s;
+        PoseMeta *wm = const_cast<PoseMeta *>(b.meta) + pose;
+        if (it > 0) {                                            // the update of the last pass that did not finish
+#pragma unroll
+            for (int i = 0; i < 12; ++i) wm->xform[i] = hdr[i];
+        }
+        wm->state = kSkip;
+    }
+}
+hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s)
+{
+    if (n_poses == 0 || b.nblk == 0) return hipSuccess;
+    const size_t lds = icp_loop_cu_lds_bytes(b.nblk);
+    if (lds > kLoopCuLdsBudget || b.robust_kind != PR_ROBUST_NONE) return hipErrorInvalidValue;   // (the caller keeps such batches on the multi-launch loop)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(icp_loop_cu_kernel<SceneProjPacked>), dim3(n_poses), dim3(kLoopLanes), lds, s, b, sc);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(64) void icp_finalize_kernel(const float *__restrict__ partial, const PoseMeta *__restrict__ meta,
                                                           uint32_t nblk, uint32_t ppb, float *__restrict__ sums)
 {

@@ -56,6 +56,7 @@ WriteLog g_writes;
 std::atomic<uint64_t> g_flag_overtook{ 0 };
 std::atomic<uint64_t> g_tight_batches{ 0 };
 std::atomic<uint64_t> g_band_batches{ 0 };
+std::atomic<uint64_t> g_resident_batches{ 0 };
 Options opt;
 std::mutex g_reg_mu;
 std::vector<Ctx *> g_shared;         // index = device ordinal
@@ -305,6 +306,7 @@ int pr_set_option(const char *name, int value)
     else if (n == "host_poll") opt.host_poll = value ? 1 : 0;
     else if (n == "graph") opt.use_graph = value ? 1 : 0;
     else if (n == "fused_solve") opt.fused_solve = value ? 1 : 0;
+    else if (n == "resident_loop") opt.resident_loop = value ? 1 : 0;
     else if (n == "sub_batch") opt.sub_batch = std::min(32768, std::max(32, value));    // (the hypothesis index is the y dimension of the launches)
     else if (n == "overlap_pass") opt.overlap_pass = std::max(-1, value);
     else if (n == "pose_groups") opt.pose_groups = std::min(4, std::max(0, value));
@@ -355,6 +357,8 @@ int pr_get_option(const char *name, int *value)
     else if (n == "eager_streams") *value = opt.eager_streams;
     else if (n == "graph") *value = opt.use_graph;
     else if (n == "fused_solve") *value = opt.fused_solve;
+    else if (n == "resident_loop") *value = opt.resident_loop;
+    else if (n == "stat_resident_batches") *value = (int)std::min<uint64_t>(g_resident_batches.load(), 0x7fffffffull);     // read-only
     else if (n == "sub_batch") *value = opt.sub_batch;
     else if (n == "overlap_pass") *value = opt.overlap_pass;
     else if (n == "pose_groups") *value = opt.pose_groups;

@@ -356,6 +356,11 @@ hipError_t launch_pyramid_emit(const int32_t *depth, uint32_t n_poses, uint32_t 
 
 hipError_t launch_icp_pass_proj_aos(const IcpBatch &b, const SceneProjAoS &sc, uint32_t n_poses, hipStream_t s);
 hipError_t launch_icp_pass_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s);
+// every pass of the loop in one launch, one 1024-lane workgroup per hypothesis (icp_loop_cu_kernel: fused device solve, no robust weight); its dynamic
+// LDS grows with b.nblk, and a batch whose plan needs more than the budget stays on the multi-launch loop
+constexpr size_t kLoopCuLdsBudget = 64u << 10;
+size_t icp_loop_cu_lds_bytes(uint32_t nblk);
+hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s);
 hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s);
 // split form of the kd-tree pass: search (pending transform applied, winners written to b.nn_prev) + gather/accumulate pass
 // marks (or null): three events recorded after the search, the bound and the walk kernel (timed batches; n_poses <= 32768)

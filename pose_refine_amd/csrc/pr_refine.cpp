@@ -1112,6 +1112,25 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
     b.cloud = sl.cloud.as<pr_vec3>(); b.partial = sl.partial.as<float>(); b.nblk = pl.nblk; b.grid_x = pl.grid_x; b.steps = pl.steps;
     if (nn_prev) nn_carve(b, nn_prev, nl);
     const uint32_t last_pass = (uint32_t)job.crit.max_iteration;
+    // Option resident_loop: every pass of the sub-batch in ONE launch on the slot's stream, a 1024-lane workgroup per hypothesis (icp_loop_cu_kernel) --
+    // no pose groups, no arrival counters, no partial sums in memory.  Packed projective scene and fused device solve only (this path carries no
+    // robust weight); a timed batch keeps its per-launch events, and a plan whose blocks would not fit the kernel's LDS keeps the multi-launch loop.
+    // The other slot's render is released AHEAD of the launch and runs beside the loop (PR_RESIDENT_RELEASE_AHEAD, pr_tuning.h: behind it measured
+    // 302 against 332 k poses/s); overlap_pass has no pass to name here and keeps its meaning for the multi-launch loop.
+    if (opt.resident_loop && opt.fused_solve && !timed && job.scene_kind == PR_SCENE_PROJ && sc.kind == PR_SCENE_PROJ && sc.packed
+        && prk::icp_loop_cu_lds_bytes(pl.nblk) <= prk::kLoopCuLdsBudget) {
+        b.meta = meta; b.st = dstate; b.crit = job.crit; b.fused = 1;
+        const bool release = q0 + pl.sub >= P;
+#if PR_RESIDENT_RELEASE_AHEAD
+        if (release) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
+#endif
+        HIP_TRY(prk::launch_icp_loop_cu_proj_packed(b, sc.pk, nq, st));
+#if !PR_RESIDENT_RELEASE_AHEAD
+        if (release) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
+#endif
+        g_resident_batches.fetch_add(1);
+        return PR_OK;
+    }
     auto pass = [&](const prk::IcpBatch &bb, uint32_t p0, uint32_t np, hipStream_t gs) -> int {
         if (!timed) { HIP_TRY(launch_pass(bb, sc, np, gs)); return PR_OK; }
         const size_t e0 = sl.spans.begin(st);                    // (one group: gs == st)

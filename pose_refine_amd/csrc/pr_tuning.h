@@ -8,6 +8,19 @@
 #define PR_SLOTS 2                                              // asynchronous slots per context (pr_refine_submit's slot argument: 0 .. PR_SLOTS - 1)
 #endif
 
+#ifndef PR_RESIDENT_RELEASE_AHEAD
+#define PR_RESIDENT_RELEASE_AHEAD 1                             // option resident_loop: the other slot's render is released ahead of the loop's one launch (1: it runs beside the loop) or behind it (0).  Same box, three alternating 100-step runs: ahead 332.4 / 332.7 / 331.7 k, behind 301.2 / 302.7 / 301.5 k, multi-launch 284.4 / 284.1 / 280.2 k poses/s (profiles/resident_cu/README.md)
+#endif
+
+#ifndef PR_LOOP_CU_WAVES
+#define PR_LOOP_CU_WAVES 0                                      // register budget of icp_loop_cu_kernel in waves per SIMD (its sixteen wavefronts are four per SIMD); 0: the compiler's own choice, 124 VGPRs and no scratch.  5 (96 VGPRs, room for a fifth wavefront of another kernel) spills 33 registers to 104 bytes of scratch per lane and runs 304.9 / 304.9 / 306.6 k against 324.2 / 325.0 / 325.5 k poses/s on one box: not used
+#endif
+#if PR_LOOP_CU_WAVES
+#define PR_LOOP_CU_ATTR __attribute__((amdgpu_waves_per_eu(PR_LOOP_CU_WAVES, PR_LOOP_CU_WAVES)))
+#else
+#define PR_LOOP_CU_ATTR
+#endif
+
 // ---- correspondence pass (icp_pass.hip) --------------------------------------------------------------------------------------------
 #ifndef PR_PASS_WAVES
 #define PR_PASS_WAVES 1                                         // __launch_bounds__ minimum waves per SIMD of icp_pass_kernel: 4, 5 waves run within 0.2 % of the compiler's own choice (round 6: 277.8 / 277.1 k against 278.0 / 277.5 k); 6 spills the accumulators: 162 k

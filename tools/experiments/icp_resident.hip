@@ -1,5 +1,6 @@
 // icp_resident.hip -- NOT built into the library: round 6's RESIDENT form of the projective ICP loop, the record of an experiment that lost.
 // (It was compiled inside icp_pass.hip, behind option "resident" in refine_submit_async: one launch per sub-batch instead of 21 x 2.)
+// The form that won later -- all blocks of a hypothesis in ONE 1024-lane workgroup, the meeting in LDS, the cloud in memory -- is icp_loop_cu_kernel (icp_pass.hip, profiles/resident_cu/README.md).
 //
 // Idea: workgroup (hypothesis, block) keeps its 3072 cloud points in registers over all 21 passes -- the cloud is read once and never written (24 B per
 // point and pass less through the fabric), no launch chain -- and the workgroups of a hypothesis meet once per pass through memory.

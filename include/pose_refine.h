@@ -1117,7 +1117,7 @@ int  pr_ppf_vote_multi(const pr_ppf_model *models, uint32_t n_models, const pr_v
  * parameters, null pointers, the frame's size.  The same frame gives the same bytes.
  * pr_scene_planes_host: the same over host arrays (pcd and normal as pr_scene_proj_prepare leaves them), from the same shared code: the CPU
  * twin the device is held to; it runs without a GPU.  support_out: host, same layout.
- * Not offered: connected components of what is left, RANSAC over point triples (a candidate is one oriented point), cylinders and spheres, an
+ * Not offered: RANSAC over point triples (a candidate is one oriented point), cylinders and spheres, an
  * asynchronous form, a refit iterated to convergence. */
 #define PR_PLANE_MAX_SAMPLES    65536
 #define PR_PLANE_MAX_CANDIDATES 4096
@@ -1146,6 +1146,65 @@ int  pr_scene_planes_dev(const pr_scene_proj *scene, const void *depth_dev, int 
 int  pr_scene_planes_host(const float *pcd, const float *normal, const void *depth, int depth_is_i32, size_t width, size_t height,
                           const pr_plane_params *params, uint8_t *labels_out, void *depth_out /* may be NULL */, pr_plane *planes_out,
                           int64_t *moments_out /* may be NULL */, uint32_t *support_out /* may be NULL */, uint32_t *n_found);
+
+/* ---- scene segments: the depth-connected components of a frame -----------------------------------------------------------------------------
+ * With the support planes cleared, what is left of a frame is a handful of parts with nothing measured between them.  These entry points cut the
+ * frame into its connected blobs: a label image, one record per blob with its pixel box, and a depth frame that keeps chosen blobs only.  That
+ * frame goes unchanged into pr_scene_proj_prepare_dev, pr_scene_nn_prepare_dev, the PPF sampler and the scorers, and the box (pr_segment_roi) is
+ * the pr_roi that pr_refine_batch_roi, pr_refine_pyramid*, the scorers and pr_compose_detections take.  Integers only; every output byte is fixed
+ * by this text, on the device and on the host.
+ *   frame: width x height depths, uint16 or int32 (depth_is_i32), 1 <= width, height <= 65535 and width * height <= 2^26; otherwise
+ *     PR_ERR_INVALID.  A pixel's index is y * width + x.
+ *   measured pixel: depth > 0 (a negative int32 is not measured).
+ *   link: two measured pixels that are 4-neighbours (left / right / up / down) are linked when |d_a - d_b| <= jump_mm, the difference formed
+ *     without overflow (the larger minus the smaller, as unsigned 32-bit integers).
+ *   component: a class of the transitive closure of the links; its ROOT is the lowest pixel index in it.  *n_components counts all of them.
+ *   qualifying component: pixels >= min_pixels.  More than PR_SEGMENT_MAX_ROOTS qualifying components: PR_ERR_INVALID with no output written
+ *     (raise min_pixels).
+ *   order: the qualifying components by pixels descending, the lower root first on a tie; n_found = min(qualifying, max_segments), and segment
+ *     k (1-based) is the k-th of that order.
+ *   labels, one uint16 per pixel: 0 where nothing is measured, k in 1 .. n_found on the pixels of segment k, PR_SEGMENT_DROPPED on the measured
+ *     pixels of every other component (too small, or beyond max_segments).
+ *   pr_segment, one per found segment: root, pixels, the inclusive pixel box x0 <= x <= x1, y0 <= y <= y1, the smallest and largest depth, and the
+ *     exact sums of x, y and depth over its pixels; reserved = 0.
+ * pr_segment_describe (host only): fills and checks the parameters.  PR_ERR_INVALID with nothing written: min_pixels == 0, max_segments outside
+ * 1 .. PR_SEGMENT_MAX, jump_mm > 2^31 - 1, a null out.  Every entry point below checks its pr_segment_params against these rules (and reserved == 0).
+ * pr_scene_segments_dev: depth_dev and labels_dev_out (width * height uint16) on the device; roots_dev_out (may be NULL; tests and tools): one
+ * uint32 per pixel, the root of the pixel's component, 0xFFFFFFFF where nothing is measured.  segments_host: room for max_segments records,
+ * *n_found of them filled.  n_qualifying and n_components may be NULL.  Synchronous, on the calling thread's context: two stream synchronises and
+ * two pinned read-backs (the qualifying roots, then the records), no hipMemcpy on the path; the number of launches and synchronisations does not
+ * depend on the frame's content.  Checked before any device is touched: the parameters, null pointers, the frame's size.  The same frame gives
+ * the same bytes on every call.
+ * pr_scene_segments_host: the same over host arrays, from the same shared code: the CPU twin the device is held to; it runs without a GPU.
+ * pr_segment_depth_dev: depth_out[i] = (labels[i] < n_keep && keep_host[labels[i]]) ? depth_in[i] : 0 over n_px pixels (int32 or uint16 by
+ * depth_is_i32); keep_host: n_keep bytes indexed by label, n_keep <= PR_SEGMENT_MAX + 1; labels 0 and PR_SEGMENT_DROPPED are never kept;
+ * depth_out may be depth_in.  n_px == 0 or > 2^26, n_keep > PR_SEGMENT_MAX + 1, a null pointer (keep_host may be NULL when n_keep == 0): PR_ERR_INVALID.
+ * pr_segment_roi (host only): the segment's box grown by margin pixels on every side and clipped to the frame, as a pr_roi (x, y, width, height).
+ * PR_ERR_INVALID for a null pointer, a frame outside the limits above or a box that does not lie in the frame.
+ * Not offered: 8-connectivity, a 3-D Euclidean or normal criterion for a link, an asynchronous form. */
+#define PR_SEGMENT_MAX        4096
+#define PR_SEGMENT_MAX_ROOTS  65536
+#define PR_SEGMENT_DROPPED    65535
+typedef struct {
+    uint32_t jump_mm, min_pixels, max_segments, reserved;
+} pr_segment_params;           /* 16 B */
+typedef struct {
+    uint32_t root, pixels;             /* the component's lowest pixel index; its pixel count                                         */
+    uint16_t x0, y0, x1, y1;           /* the inclusive pixel box                                                                     */
+    uint32_t depth_min, depth_max;
+    uint64_t sum_x, sum_y, sum_depth;  /* exact                                                                                       */
+    uint64_t reserved[2];
+} pr_segment;                  /* 64 B */
+int  pr_segment_describe(uint32_t jump_mm, uint32_t min_pixels, uint32_t max_segments, pr_segment_params *out);
+int  pr_scene_segments_dev(const void *depth_dev, int depth_is_i32, size_t width, size_t height, const pr_segment_params *params,
+                           uint16_t *labels_dev_out, uint32_t *roots_dev_out /* may be NULL */, pr_segment *segments_host, uint32_t *n_found,
+                           uint32_t *n_qualifying /* may be NULL */, uint32_t *n_components /* may be NULL */);
+int  pr_scene_segments_host(const void *depth, int depth_is_i32, size_t width, size_t height, const pr_segment_params *params, uint16_t *labels_out,
+                            uint32_t *roots_out /* may be NULL */, pr_segment *segments_out, uint32_t *n_found, uint32_t *n_qualifying /* may be NULL */,
+                            uint32_t *n_components /* may be NULL */);
+int  pr_segment_depth_dev(const uint16_t *labels_dev, const void *depth_in_dev, int depth_is_i32, size_t n_px, const uint8_t *keep_host, uint32_t n_keep,
+                          void *depth_out_dev);
+int  pr_segment_roi(const pr_segment *segment, size_t width, size_t height, uint32_t margin, pr_roi *roi_out);
 
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);

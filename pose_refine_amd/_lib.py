@@ -141,6 +141,21 @@ class PlaneParamsDesc(C.Structure):
 assert C.sizeof(PlaneParamsDesc) == 32
 
 
+# pr_segment: one depth-connected component of a frame (pr_scene_segments_dev / _host); pr_segment_params: what pr_segment_describe fills
+SEGMENT = np.dtype([("root", "<u4"), ("pixels", "<u4"), ("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2"), ("depth_min", "<u4"), ("depth_max", "<u4"),
+                    ("sum_x", "<u8"), ("sum_y", "<u8"), ("sum_depth", "<u8"), ("reserved", "<u8", (2,))])
+SEGMENT_MAX, SEGMENT_MAX_ROOTS, SEGMENT_DROPPED = 4096, 65536, 65535        # PR_SEGMENT_*
+assert SEGMENT.itemsize == 64
+
+
+class SegmentParamsDesc(C.Structure):
+    """pr_segment_params: the link threshold, the smallest component kept and the number of segments of a call (pr_segment_describe checks and fills it)."""
+    _fields_ = [("jump_mm", C.c_uint32), ("min_pixels", C.c_uint32), ("max_segments", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(SegmentParamsDesc) == 16
+
+
 class MeshRef(C.Structure):
     """pr_mesh_ref: one mesh of a mixed batch (pr_*_multi)."""
     _fields_ = [("tris_dev", C.c_void_p), ("n_tris", C.c_size_t)]
@@ -284,6 +299,11 @@ SIGNATURES = {
     "pr_plane_from_moments": (_i32, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "pr_scene_planes_dev": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
     "pr_scene_planes_host": (_i32, [_vp, _vp, _vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32)]),
+    "pr_segment_describe": (_i32, [_u32, _u32, _u32, _vp]),
+    "pr_scene_segments_dev": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "pr_scene_segments_host": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "pr_segment_depth_dev": (_i32, [_vp, _vp, _i32, _sz, _vp, _u32, _vp]),
+    "pr_segment_roi": (_i32, [_vp, _sz, _sz, _u32, C.POINTER(Roi)]),
     "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_render_span": (_i32, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, Roi, _vp, _vp]),

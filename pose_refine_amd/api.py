@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SEGMENT, SEGMENT_DROPPED, SEGMENT_MAX, SEGMENT_MAX_ROOTS, SegmentParamsDesc, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -1711,6 +1711,96 @@ def scene_planes_host(pcd, normal, scene_depth, width: int, height: int, params:
     if want_supports:
         res.append(sup)
     return tuple(res)
+
+
+# ------------------------------------------------------------------------------------------------
+# scene segments: the depth-connected components of a frame, their labels, boxes and the depth of chosen ones (pr_segment_* / pr_scene_segments_*; the definition is in include/pose_refine.h)
+# ------------------------------------------------------------------------------------------------
+def SegmentParams(jump_mm: int = 10, min_pixels: int = 256, max_segments: int = 64) -> SegmentParamsDesc:
+    """``pr_segment_describe`` (host only): the parameters of a labelling, checked.  The defaults are for a 640 x 480 frame in mm whose support planes
+    are cleared: 4-neighbours within 10 mm of depth belong together, a blob of fewer than 256 pixels is dropped, the 64 largest blobs get a label."""
+    sp = SegmentParamsDesc()
+    check(_lib.load().pr_segment_describe(int(jump_mm), int(min_pixels), int(max_segments), C.addressof(sp)))
+    return sp
+
+
+def _segment_params(params, kw) -> SegmentParamsDesc:
+    if params is not None and kw:
+        raise ValueError("pass either params or keyword parameters")
+    return params if params is not None else SegmentParams(**kw)
+
+
+def scene_segments(scene_depth, width: int, height: int, params: Optional[SegmentParamsDesc] = None, want_roots: bool = False, **kw):
+    """``pr_scene_segments_dev``: the depth-connected components of a depth frame (a DeviceVector or a host image, uint16 or int32; typically
+    ``scene_planes``' cleared depth).  Returns (segments SEGMENT[n_found], labels DeviceVector uint16[width * height], counts): ``labels`` holds 0
+    where nothing is measured, k for the k-th largest component and ``SEGMENT_DROPPED`` for the rest; ``counts`` is (n_found, n_qualifying,
+    n_components).  ``want_roots`` adds, before the counts, a DeviceVector uint32[width * height] with every pixel's root (tests and tools).
+    Parameters: a ``SegmentParams`` or its keywords."""
+    sp = _segment_params(params, kw)
+    sd = _scene_depth_dev(scene_depth, width, height)
+    labels = DeviceVector(width * height, np.uint16)
+    roots = DeviceVector(width * height, np.uint32) if want_roots else None
+    segs = np.zeros(sp.max_segments, SEGMENT)
+    n, nq, nc = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().pr_scene_segments_dev(sd.data(), int(sd.dtype == np.int32), width, height, C.addressof(sp), labels.data(), roots.data() if want_roots else None,
+                                            ptr(segs), C.byref(n), C.byref(nq), C.byref(nc)))
+    res = [segs[:n.value].copy(), labels]
+    if want_roots:
+        res.append(roots)
+    res.append((n.value, nq.value, nc.value))
+    return tuple(res)
+
+
+def scene_segments_host(depth, width: int, height: int, params: Optional[SegmentParamsDesc] = None, want_roots: bool = False, **kw):
+    """``pr_scene_segments_host``: ``scene_segments`` over a host image (uint16 or int32), on the CPU, from the same definition.  Returns (segments,
+    labels uint16[height, width][, roots uint32[height, width]], counts); runs without a GPU."""
+    sp = _segment_params(params, kw)
+    dep = np.ascontiguousarray(depth)
+    if dep.dtype not in (np.uint16, np.int32):
+        raise ValueError("scene depth must be CV_16U or CV_32S")
+    if dep.size != width * height:
+        raise ValueError(f"depth must hold {width} x {height} pixels")
+    labels = np.zeros((height, width), np.uint16)
+    roots = np.zeros((height, width), np.uint32) if want_roots else None
+    segs = np.zeros(sp.max_segments, SEGMENT)
+    n, nq, nc = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().pr_scene_segments_host(ptr(dep), int(dep.dtype == np.int32), width, height, C.addressof(sp), ptr(labels), ptr(roots) if want_roots else None,
+                                             ptr(segs), C.byref(n), C.byref(nq), C.byref(nc)))
+    res = [segs[:n.value].copy(), labels]
+    if want_roots:
+        res.append(roots)
+    res.append((n.value, nq.value, nc.value))
+    return tuple(res)
+
+
+def segment_depth(labels: DeviceVector, scene_depth, keep, depth_out: Optional[DeviceVector] = None) -> DeviceVector:
+    """``pr_segment_depth_dev``: the depth frame with everything but the segments ``keep`` (a label or a list of labels, 1-based) set to 0; it goes as it
+    is into ``init_Scene_projective_device``, ``init_Scene_nn_device``, the PPF sampler and the scorers.  ``depth_out``: where it goes (the input
+    itself is allowed); default a new DeviceVector of the depth's dtype."""
+    n_px = labels.size()
+    sd = _scene_depth_dev(scene_depth, n_px, 1)
+    if labels.dtype != np.uint16:
+        raise ValueError("labels must be uint16")
+    out = depth_out if depth_out is not None else DeviceVector(n_px, sd.dtype)
+    if out.dtype != sd.dtype or out.size() != n_px:
+        raise ValueError("depth_out must have the depth's dtype and size")
+    ks = [int(k) for k in np.atleast_1d(np.asarray(keep)).reshape(-1)]
+    if any(k < 1 or k > SEGMENT_MAX for k in ks):
+        raise ValueError(f"a kept label must be 1 .. SEGMENT_MAX = {SEGMENT_MAX}")
+    table = np.zeros((max(ks) if ks else 0) + 1, np.uint8)
+    table[ks] = 1
+    check(_lib.load().pr_segment_depth_dev(labels.data(), sd.data(), int(sd.dtype == np.int32), n_px, ptr(table), len(table), out.data()))
+    return out
+
+
+def segment_roi(segment, width: int, height: int, margin: int = 0):
+    """``pr_segment_roi`` (host only): a SEGMENT record's pixel box grown by ``margin`` and clipped to the frame, as the (x, y, width, height) tuple
+    every ``roi`` argument takes."""
+    rec = np.zeros(1, SEGMENT)
+    rec[0] = segment
+    r = Roi()
+    check(_lib.load().pr_segment_roi(ptr(rec), width, height, int(margin), C.byref(r)))
+    return (r.x, r.y, r.width, r.height)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -178,6 +178,15 @@ __global__ __launch_bounds__(256) void d2c_pack_starts_kernel(const uint32_t *__
     __shared__ uint32_t carry;
     block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return cloud_slot(counts[i]); }, [&](uint32_t i, uint32_t start) { meta[i].start = start; });
 }
+// THE scan of a frame stage's counts (rows of a sample, chunks of a root list, keys of a pair table), one workgroup: offsets = their exclusive
+// scan, offsets[n] = the total, which also goes to *total_out where one is given; clear: the counts are zeroed on the way (they become cursors)
+__global__ __launch_bounds__(256) void scan_counts_kernel(uint32_t *__restrict__ counts, uint32_t n, uint32_t *__restrict__ offsets, uint32_t *__restrict__ total_out, bool clear)
+{
+    __shared__ uint32_t buf[256], carry;
+    const uint32_t total = block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return counts[i]; },
+                                                [&](uint32_t i, uint32_t v) { offsets[i] = v; if (clear) counts[i] = 0; });
+    if (threadIdx.x == 0) { offsets[n] = total; if (total_out) *total_out = total; }
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void d2c_emit_kernel(const T *__restrict__ depth, size_t img_stride, uint32_t width,
@@ -271,6 +280,11 @@ hipError_t launch_d2c_scan(const uint32_t *row_count, uint32_t gh, uint32_t *row
 {
     if (n_img == 0) return hipSuccess;
     hipLaunchKernelGGL(d2c_scan_kernel, dim3(n_img), dim3(256), 0, s, row_count, gh, row_off, counts);
+    return hipGetLastError();
+}
+hipError_t launch_scan_counts(uint32_t *counts, uint32_t n, uint32_t *offsets, uint32_t *total_out, bool clear, hipStream_t s)
+{
+    hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(256), 0, s, counts, n, offsets, total_out, clear);
     return hipGetLastError();
 }
 hipError_t launch_d2c_pack_starts(const uint32_t *counts, uint32_t n, PoseMeta *meta, hipStream_t s)

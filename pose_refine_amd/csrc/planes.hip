@@ -11,41 +11,25 @@ constexpr uint32_t kPlaneThreads = 256;
 constexpr uint32_t kPlaneTile = 256;                             // samples staged per turn: one per thread
 static_assert(kPlaneTile == kPlaneThreads, "plane_support_kernel: one staged sample per thread");
 
-// ---- the sample: one wavefront per sampled row (ppf.hip's compaction with the range test and the pixel index) ------------------------------
+// ---- the sample: one wavefront per sampled row (wave_compact_count / wave_compact_place over its sampled columns) ---------------------------
 __global__ __launch_bounds__(64) void plane_sample_count_kernel(const float *__restrict__ pcd, const float *__restrict__ normal, uint32_t width, uint32_t stride,
                                                                 uint32_t *__restrict__ row_count)
 {
-    const uint32_t gw = (width + stride - 1) / stride;
     const size_t row = (size_t)blockIdx.x * stride * width;
-    uint32_t n = 0;
-    for (uint32_t c = threadIdx.x; c < gw; c += 64) n += planes::sample_keep(pcd, normal, row + (size_t)c * stride) ? 1u : 0u;
-    n = wave_sum_u32(n);
+    const uint32_t n = wave_compact_count((width + stride - 1) / stride, threadIdx.x, [&](uint32_t c) { return planes::sample_keep(pcd, normal, row + (size_t)c * stride); });
     if (threadIdx.x == 0) row_count[blockIdx.x] = n;
-}
-__global__ __launch_bounds__(256) void plane_scan_kernel(const uint32_t *__restrict__ counts, uint32_t n, uint32_t *__restrict__ offsets)
-{
-    __shared__ uint32_t buf[256], carry;
-    const uint32_t total = block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return counts[i]; }, [&](uint32_t i, uint32_t v) { offsets[i] = v; });
-    if (threadIdx.x == 0) offsets[n] = total;
 }
 __global__ __launch_bounds__(64) void plane_sample_emit_kernel(const float *__restrict__ pcd, const float *__restrict__ normal, uint32_t width, uint32_t stride,
                                                                const uint32_t *__restrict__ row_off, PlaneSample *__restrict__ points, pr_vec3 *__restrict__ normals)
 {
-    const uint32_t gw = (width + stride - 1) / stride;
     const size_t row = (size_t)blockIdx.x * stride * width;
-    uint32_t base = row_off[blockIdx.x];
-    for (uint32_t c0 = 0; c0 < gw; c0 += 64) {                     // 64 columns at a time, in order: a lane's slot = the kept lanes below it
-        const uint32_t c = c0 + threadIdx.x;
-        const size_t px = row + (size_t)c * stride;
-        const bool keep = c < gw && planes::sample_keep(pcd, normal, px);
-        const unsigned long long m = __ballot(keep);
-        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << threadIdx.x) - 1ull));
-        if (keep && pos < PR_PLANE_MAX_SAMPLES) {
-            points[pos] = PlaneSample{ pcd[px * 3] * 1000.0f, pcd[px * 3 + 1] * 1000.0f, pcd[px * 3 + 2] * 1000.0f, (uint32_t)px };
-            normals[pos] = pr_vec3{ normal[px * 3], normal[px * 3 + 1], normal[px * 3 + 2] };
-        }
-        base += (uint32_t)__popcll(m);
-    }
+    wave_compact_place((width + stride - 1) / stride, threadIdx.x, row_off[blockIdx.x], [&](uint32_t c) { return planes::sample_keep(pcd, normal, row + (size_t)c * stride); },
+                       [&](uint32_t c, bool kept, uint32_t pos) {
+                           if (!kept || pos >= PR_PLANE_MAX_SAMPLES) return;
+                           const size_t px = row + (size_t)c * stride;
+                           points[pos] = PlaneSample{ pcd[px * 3] * 1000.0f, pcd[px * 3 + 1] * 1000.0f, pcd[px * 3 + 2] * 1000.0f, (uint32_t)px };
+                           normals[pos] = pr_vec3{ normal[px * 3], normal[px * 3 + 1], normal[px * 3 + 2] };
+                       });
 }
 
 __global__ __launch_bounds__(kPlaneThreads) void plane_init_kernel(const float *__restrict__ pcd, uint32_t n_px, uint8_t *__restrict__ labels, uint32_t *__restrict__ round_words,
@@ -183,8 +167,7 @@ hipError_t launch_plane_sample_count(const float *pcd, const float *normal, uint
 {
     const uint32_t gh = (height + stride - 1) / stride;
     hipLaunchKernelGGL(plane_sample_count_kernel, dim3(gh), dim3(64), 0, s, pcd, normal, width, stride, row_count);
-    hipLaunchKernelGGL(plane_scan_kernel, dim3(1), dim3(256), 0, s, (const uint32_t *)row_count, gh, row_off);      // row_off[gh] = the total
-    return hipGetLastError();
+    return launch_scan_counts(row_count, gh, row_off, nullptr, false, s);      // row_off[gh] = the total
 }
 
 hipError_t launch_plane_sample_emit(const float *pcd, const float *normal, uint32_t width, uint32_t height, uint32_t stride, const uint32_t *row_off,
@@ -228,8 +211,10 @@ hipError_t launch_plane_label(const pr_plane_params &pp, uint32_t k, const float
 hipError_t launch_plane_clear_depth(const uint8_t *labels, const void *depth_in, void *depth_out, bool depth_i32, uint32_t n_px, hipStream_t s)
 {
     const dim3 grid((n_px + kPlaneThreads - 1) / kPlaneThreads);
-    if (depth_i32) hipLaunchKernelGGL(plane_clear_depth_kernel<int32_t>, grid, dim3(kPlaneThreads), 0, s, labels, static_cast<const int32_t *>(depth_in), static_cast<int32_t *>(depth_out), n_px);
-    else hipLaunchKernelGGL(plane_clear_depth_kernel<uint16_t>, grid, dim3(kPlaneThreads), 0, s, labels, static_cast<const uint16_t *>(depth_in), static_cast<uint16_t *>(depth_out), n_px);
+    for_depth_type(depth_i32, [&](auto *tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        hipLaunchKernelGGL(plane_clear_depth_kernel<T>, grid, dim3(kPlaneThreads), 0, s, labels, static_cast<const T *>(depth_in), static_cast<T *>(depth_out), n_px);
+    });
     return hipGetLastError();
 }
 

@@ -48,16 +48,7 @@ __global__ __launch_bounds__(kPpfThreads) void ppf_model_pairs_kernel(const ppf:
     }
 }
 
-// offsets = exclusive scan of counts, offsets[n] = the total; the counts are zeroed on the way (they become the fill's cursors)
-__global__ __launch_bounds__(256) void ppf_scan_kernel(uint32_t *__restrict__ counts, uint32_t n, uint32_t *__restrict__ offsets, bool clear)
-{
-    __shared__ uint32_t buf[256], carry;
-    const uint32_t total = block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return counts[i]; },
-                                                [&](uint32_t i, uint32_t v) { offsets[i] = v; if (clear) counts[i] = 0; });
-    if (threadIdx.x == 0) offsets[n] = total;
-}
-
-// ---- the scene sample: one wavefront per sampled row ------------------------------------------------------------------------------------
+// ---- the scene sample: one wavefront per sampled row (wave_compact_count / wave_compact_place over its sampled columns) ---------------------
 __device__ __forceinline__ bool scene_keep(const float *__restrict__ pcd, const float *__restrict__ normal, size_t px)
 {
     const float nx = normal[px * 3], ny = normal[px * 3 + 1], nz = normal[px * 3 + 2];
@@ -66,31 +57,21 @@ __device__ __forceinline__ bool scene_keep(const float *__restrict__ pcd, const 
 __global__ __launch_bounds__(64) void ppf_scene_count_kernel(const float *__restrict__ pcd, const float *__restrict__ normal, uint32_t width, uint32_t stride,
                                                              uint32_t *__restrict__ row_count)
 {
-    const uint32_t gw = (width + stride - 1) / stride;
     const size_t row = (size_t)blockIdx.x * stride * width;
-    uint32_t n = 0;
-    for (uint32_t c = threadIdx.x; c < gw; c += 64) n += scene_keep(pcd, normal, row + (size_t)c * stride) ? 1u : 0u;
-    n = wave_sum_u32(n);
+    const uint32_t n = wave_compact_count((width + stride - 1) / stride, threadIdx.x, [&](uint32_t c) { return scene_keep(pcd, normal, row + (size_t)c * stride); });
     if (threadIdx.x == 0) row_count[blockIdx.x] = n;
 }
 __global__ __launch_bounds__(64) void ppf_scene_emit_kernel(const float *__restrict__ pcd, const float *__restrict__ normal, uint32_t width, uint32_t stride,
                                                             const uint32_t *__restrict__ row_off, pr_vec3 *__restrict__ points, pr_vec3 *__restrict__ normals)
 {
-    const uint32_t gw = (width + stride - 1) / stride;
     const size_t row = (size_t)blockIdx.x * stride * width;
-    uint32_t base = row_off[blockIdx.x];
-    for (uint32_t c0 = 0; c0 < gw; c0 += 64) {                     // 64 columns at a time, in order: a lane's slot = the kept lanes below it
-        const uint32_t c = c0 + threadIdx.x;
-        const size_t px = row + (size_t)c * stride;
-        const bool keep = c < gw && scene_keep(pcd, normal, px);
-        const unsigned long long m = __ballot(keep);
-        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << threadIdx.x) - 1ull));
-        if (keep && pos < PR_PPF_MAX_SCENE_POINTS) {
-            points[pos] = pr_vec3{ pcd[px * 3] * 1000.0f, pcd[px * 3 + 1] * 1000.0f, pcd[px * 3 + 2] * 1000.0f };
-            normals[pos] = pr_vec3{ normal[px * 3], normal[px * 3 + 1], normal[px * 3 + 2] };
-        }
-        base += (uint32_t)__popcll(m);
-    }
+    wave_compact_place((width + stride - 1) / stride, threadIdx.x, row_off[blockIdx.x], [&](uint32_t c) { return scene_keep(pcd, normal, row + (size_t)c * stride); },
+                       [&](uint32_t c, bool kept, uint32_t pos) {
+                           if (!kept || pos >= PR_PPF_MAX_SCENE_POINTS) return;
+                           const size_t px = row + (size_t)c * stride;
+                           points[pos] = pr_vec3{ pcd[px * 3] * 1000.0f, pcd[px * 3 + 1] * 1000.0f, pcd[px * 3 + 2] * 1000.0f };
+                           normals[pos] = pr_vec3{ normal[px * 3], normal[px * 3 + 1], normal[px * 3 + 2] };
+                       });
 }
 
 // ---- voting: one workgroup per scene reference (and model), its accumulator votes[n_model * n_alpha] in LDS -----------------------------------
@@ -220,7 +201,7 @@ hipError_t launch_ppf_model_build(const ppf::Tables &tb, const pr_vec3 *points, 
     const uint32_t n_pairs = n_model * n_model, grid = (n_pairs + kPpfThreads - 1) / kPpfThreads;
     hipLaunchKernelGGL(ppf_zero_kernel, dim3(cap_grid((tb.n_keys + kPpfThreads - 1) / kPpfThreads)), dim3(kPpfThreads), 0, s, counts, tb.n_keys);
     hipLaunchKernelGGL(ppf_model_pairs_kernel<false>, dim3(grid), dim3(kPpfThreads), 0, s, tb, points, normals, n_model, counts, (const uint32_t *)nullptr, (pr_ppf_entry *)nullptr);
-    hipLaunchKernelGGL(ppf_scan_kernel, dim3(1), dim3(256), 0, s, counts, tb.n_keys, offsets, true);
+    { hipError_t e = launch_scan_counts(counts, tb.n_keys, offsets, nullptr, true, s); if (e != hipSuccess) return e; }      // the counts become the fill's cursors
     hipLaunchKernelGGL(ppf_model_pairs_kernel<true>, dim3(grid), dim3(kPpfThreads), 0, s, tb, points, normals, n_model, counts, (const uint32_t *)offsets, entries);
     return hipGetLastError();
 }
@@ -230,8 +211,7 @@ hipError_t launch_ppf_scene_count(const float *pcd, const float *normal, uint32_
 {
     const uint32_t gh = (height + stride - 1) / stride;
     hipLaunchKernelGGL(ppf_scene_count_kernel, dim3(gh), dim3(64), 0, s, pcd, normal, width, stride, row_count);
-    hipLaunchKernelGGL(ppf_scan_kernel, dim3(1), dim3(256), 0, s, row_count, gh, row_off, false);      // row_off[gh] = the total
-    return hipGetLastError();
+    return launch_scan_counts(row_count, gh, row_off, nullptr, false, s);      // row_off[gh] = the total
 }
 
 hipError_t launch_ppf_scene_emit(const float *pcd, const float *normal, uint32_t width, uint32_t height, uint32_t stride, const uint32_t *row_off,

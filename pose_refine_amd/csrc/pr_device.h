@@ -94,9 +94,40 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x)
            (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 
+// Ordered compaction by one wavefront: THE count / emit loop of the frame stages (the PPF and plane samples, the segment roots, the kd-tree
+// scene gather).  One step takes 64 items, a lane each: a kept lane's slot is base + the kept lanes below it, and the step's count moves the
+// base on.  lane = the lane in its wavefront (a workgroup of several wavefronts runs one loop per wavefront); every lane takes every step.
+struct WaveSlot { uint32_t pos, kept; };
+__device__ __forceinline__ WaveSlot wave_compact_step(bool keep, uint32_t lane, uint32_t base)
+{
+    const unsigned long long m = __ballot(keep);
+    return WaveSlot{ base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), (uint32_t)__popcll(m) };
+}
+// items 0 .. n-1 in ascending order, 64 at a time: the number keep(i) holds for, the same in every lane
+template <class Keep>
+__device__ __forceinline__ uint32_t wave_compact_count(uint32_t n, uint32_t lane, Keep &&keep)
+{
+    uint32_t total = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64) total += wave_compact_step(i0 + lane < n && keep(i0 + lane), lane, 0).kept;
+    return total;
+}
+// the same walk with the slots: visit(i, kept, pos) for every i < n (pos means something where kept); returns base + the number kept
+template <class Keep, class Visit>
+__device__ __forceinline__ uint32_t wave_compact_place(uint32_t n, uint32_t lane, uint32_t base, Keep &&keep, Visit &&visit)
+{
+    for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        const bool kept = i < n && keep(i);
+        const WaveSlot s = wave_compact_step(kept, lane, base);
+        if (i < n) visit(i, kept, s.pos);
+        base += s.kept;
+    }
+    return base;
+}
+
 // Exclusive scan of n values in chunks of 256 with a carry, by one 256-lane workgroup (Hillis-Steele per chunk): out(i, value(0) + ... + value(i - 1))
 // for every i < n; returns the total in every lane.  THE scan of the render -> cloud stage: the row offsets of an image (d2c_scan_kernel,
-// d2c_scan_init_kernel), the starts of the packed clouds (d2c_pack_starts_kernel), the offsets of the packed boxes (box_pack_offsets_kernel).
+// d2c_scan_init_kernel), the starts of the packed clouds (d2c_pack_starts_kernel), the offsets of the packed boxes (box_pack_offsets_kernel), the counts of a frame stage (scan_counts_kernel).
 // buf: 256 words of LDS, carry: one more.
 template <class Value, class Out>
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t n, uint32_t *buf, uint32_t *carry, Value &&value, Out &&out)

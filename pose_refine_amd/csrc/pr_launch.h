@@ -28,8 +28,16 @@ static inline hipError_t for_pose_launches(uint32_t n, Fn fn)
     }
     return hipSuccess;
 }
+// fn(tag) with a null pointer of the depth image's element type, int32_t or uint16_t: a kernel template over that type is launched from one
+// statement -- [&](auto *tag) { using T = std::remove_pointer_t<decltype(tag)>; ... kernel<T> ... static_cast<const T *>(depth) ... }
+template <class Fn>
+static inline void for_depth_type(bool depth_i32, Fn fn)
+{
+    if (depth_i32) fn(static_cast<int32_t *>(nullptr)); else fn(static_cast<uint16_t *>(nullptr));
+}
 
-// row scans of the depth -> cloud stage (d2c.hip), called from the render and scene launchers of other files
+// row scans of the depth -> cloud stage and the count scan of the frame stages (d2c.hip), called from the launchers of other files
+hipError_t launch_scan_counts(uint32_t *counts, uint32_t n, uint32_t *offsets, uint32_t *total_out, bool clear, hipStream_t s);
 hipError_t launch_d2c_scan(const uint32_t *row_count, uint32_t gh, uint32_t *row_off, uint32_t *counts, uint32_t n_img, hipStream_t s);
 hipError_t launch_d2c_scan_init(const uint32_t *row_count, uint32_t gh, uint32_t *row_off, uint32_t *counts, uint32_t n_img,
                                 PoseMeta *meta, DevIcpState *st, uint32_t *arrive, hipStream_t s);

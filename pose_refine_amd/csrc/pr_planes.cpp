@@ -4,6 +4,7 @@
 
 #include "pr_runtime.h"
 #include "planes.h"
+#include "jacobi.h"
 
 namespace prr {
 
@@ -22,11 +23,6 @@ static int plane_params_ok(const char *fn, const pr_plane_params *pp)
     if (pp->drop_behind > 1) { set_error("%s: pr_plane_params: drop_behind must be 0 or 1", fn); return PR_ERR_INVALID; }
     return PR_OK;
 }
-static int frame_ok(const char *fn, size_t W, size_t H)
-{
-    if (W == 0 || H == 0) { set_error("%s: bad arguments (an empty frame)", fn); return PR_ERR_INVALID; }
-    return frame_size_ok(W, H) ? PR_OK : PR_ERR_INVALID;
-}
 // the two caps, with the entry point's name in the message
 static int sample_caps_ok(const char *fn, const pr_plane_params *pp, uint32_t n, uint32_t *n_cand)
 {
@@ -36,28 +32,6 @@ static int sample_caps_ok(const char *fn, const pr_plane_params *pp, uint32_t n,
     return PR_OK;
 }
 
-// pr_info_eig's rotation on a 3 x 3 (pr_pose_info.cpp), statement for statement: include/pose_refine.h specifies it
-static void jacobi_rotate3(double (&A)[3][3], double (&V)[3][3], int p, int q)
-{
-    const double apq = A[p][q];
-    if (apq == 0.0) return;
-    const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-    const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-    A[p][p] -= t * apq;
-    A[q][q] += t * apq;
-    A[p][q] = 0.0; A[q][p] = 0.0;
-    const int k = 3 - p - q;
-    const double akp = A[k][p], akq = A[k][q];
-    const double np = c * akp - s * akq, nq = s * akp + c * akq;
-    A[k][p] = np; A[p][k] = np;
-    A[k][q] = nq; A[q][k] = nq;
-    for (int r = 0; r < 3; ++r) {
-        const double vrp = V[r][p], vrq = V[r][q];
-        V[r][p] = c * vrp - s * vrq;
-        V[r][q] = s * vrp + c * vrq;
-    }
-}
 struct PlaneFit { double n[3], offset, rms, eig[3]; };
 // false: fewer than 3 points, an all-zero scatter matrix or an eigenvector without a length (the reason in *why)
 static bool plane_fit(const int64_t m[10], PlaneFit *out, const char **why)
@@ -75,15 +49,7 @@ static bool plane_fit(const int64_t m[10], PlaneFit *out, const char **why)
             V[i][j] = (i == j) ? 1.0 : 0.0;
         }
     if (!any) { *why = "an all-zero scatter matrix (the points coincide)"; return false; }
-    for (uint32_t sweeps = 0; sweeps < PR_PLANE_MAX_SWEEPS; ++sweeps) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < 3; ++i) {
-            diag = std::fmax(diag, std::fabs(A[i][i]));
-            for (int j = i + 1; j < 3; ++j) off = std::fmax(off, std::fabs(A[i][j]));
-        }
-        if (off <= 0x1p-56 * diag) break;
-        jacobi_rotate3(A, V, 0, 1); jacobi_rotate3(A, V, 0, 2); jacobi_rotate3(A, V, 1, 2);
-    }
+    (void)jacobi_eigen(A, V, PR_PLANE_MAX_SWEEPS);
     int lo = 0;
     for (int i = 1; i < 3; ++i) if (A[i][i] < A[lo][lo]) lo = i;
     const double vx = V[0][lo], vy = V[1][lo], vz = V[2][lo];
@@ -244,10 +210,8 @@ int pr_scene_planes_dev(const pr_scene_proj *scene, const void *depth_dev, int d
     uint32_t *support = support_dev_out ? support_dev_out : reinterpret_cast<uint32_t *>(d + rounds_bytes + rows_bytes + pts_bytes + nrm_bytes);
 
     HIP_TRY(prk::launch_plane_sample_count(pcd, normal, W, H, pp.stride, row_count, row_off, g->stream));
-    HIP_TRY(prk::launch_copy_words32(row_off + gh, g->h_plane.dev, 1, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    const uint32_t n = *g->h_plane.as<uint32_t>();
-    uint32_t n_cand = 0;
+    uint32_t n = 0, n_cand = 0;
+    PR_TRY(read_back_words(row_off + gh, &n, 1, g->stream));
     PR_TRY(sample_caps_ok(fn, &pp, n, &n_cand));
     *n_found = 0;
     HIP_TRY(prk::launch_plane_init(pcd, n_px, labels_dev_out, rounds, pp.n_planes, support, pp.n_planes * PR_PLANE_MAX_CANDIDATES, g->stream));

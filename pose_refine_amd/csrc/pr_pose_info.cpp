@@ -3,6 +3,7 @@
 // Jacobi, restated) and pr_info_step.  The fused entry points (pr_pose_information, _multi) live in pr_refine.cpp beside refine_core.
 #include "pr_runtime.h"
 #include "pose_info.h"
+#include "jacobi.h"
 
 namespace prr {
 
@@ -119,30 +120,7 @@ static int info_combine(const pr_pose_info *a, double wa, const pr_pose_info *b,
     return PR_OK;
 }
 
-// pose_info_eigen_kernel's decomposition (pose_info.hip), statement for statement: include/pose_refine.h specifies it
-static void jacobi_rotate(double (&A)[6][6], double (&V)[6][6], int p, int q)
-{
-    const double apq = A[p][q];
-    if (apq == 0.0) return;
-    const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-    const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-    A[p][p] -= t * apq;
-    A[q][q] += t * apq;
-    A[p][q] = 0.0; A[q][p] = 0.0;
-    for (int k = 0; k < 6; ++k) {
-        if (k == p || k == q) continue;
-        const double akp = A[k][p], akq = A[k][q];
-        const double np = c * akp - s * akq, nq = s * akp + c * akq;
-        A[k][p] = np; A[p][k] = np;
-        A[k][q] = nq; A[q][k] = nq;
-    }
-    for (int k = 0; k < 6; ++k) {
-        const double vkp = V[k][p], vkq = V[k][q];
-        V[k][p] = c * vkp - s * vkq;
-        V[k][q] = s * vkp + c * vkq;
-    }
-}
+// pose_info_eigen_kernel's decomposition (pose_info.hip): the solve is jacobi.h's, the ordering and the signs are below
 static int info_eig(const pr_pose_info *info, pr_pose_eig *eig_out)
 {
     if (!info || !eig_out) { set_error("pr_info_eig: bad arguments (info or eig_out is null)"); return PR_ERR_INVALID; }
@@ -152,17 +130,7 @@ static int info_eig(const pr_pose_info *info, pr_pose_eig *eig_out)
         for (int j = i; j < 6; ++j) { A[i][j] = info->H[k]; A[j][i] = info->H[k]; ++k; }
     for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    uint32_t sweeps = 0;
-    for (; sweeps < PR_INFO_MAX_SWEEPS; ++sweeps) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < 6; ++i) {
-            diag = std::fmax(diag, std::fabs(A[i][i]));
-            for (int j = i + 1; j < 6; ++j) off = std::fmax(off, std::fabs(A[i][j]));
-        }
-        if (off <= 0x1p-56 * diag) break;
-        for (int p = 0; p < 5; ++p)
-            for (int q = p + 1; q < 6; ++q) jacobi_rotate(A, V, p, q);
-    }
+    const uint32_t sweeps = jacobi_eigen(A, V, PR_INFO_MAX_SWEEPS);
     double lam[6];
     for (int i = 0; i < 6; ++i) lam[i] = A[i][i];
     // ascending order by the kernel's fixed 12-comparator network (strict: equal eigenvalues keep their places)

@@ -91,15 +91,6 @@ static void peaks_out(const pr_ppf_params *pp, const pr_vec3 *model_points, cons
     }
 }
 
-// a word (or a few) of the device into the pinned block, and wait: the totals of a build or a sample
-static int read_words(const void *dev, uint32_t n_words)
-{
-    PR_TRY(g->h_ppf.ensure(sizeof(uint32_t) * n_words));
-    HIP_TRY(prk::launch_copy_words32(dev, g->h_ppf.dev, n_words, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return PR_OK;
-}
-
 }  // namespace prr
 
 using namespace prr;
@@ -199,9 +190,7 @@ int pr_ppf_model_build_dev(const pr_ppf_params *params, const pr_vec3 *points_de
     HIP_TRY(prk::launch_ppf_model_build(tb, points_dev, normals_dev, n_model, g->ppf_tmp.as<uint32_t>(), offsets_dev_out, entries_dev_out, g->stream));
     g_writes.note(offsets_dev_out, sizeof(uint32_t) * ((size_t)tb.n_keys + 1));
     g_writes.note(entries_dev_out, sizeof(pr_ppf_entry) * (size_t)n_model * (n_model - 1));
-    PR_TRY(read_words(offsets_dev_out + tb.n_keys, 1));
-    *n_entries_out = *g->h_ppf.as<uint32_t>();
-    return PR_OK;
+    return read_back_words(offsets_dev_out + tb.n_keys, n_entries_out, 1, g->stream);
 }
 
 int pr_ppf_scene_points_dev(const pr_scene_proj *scene, uint32_t stride, pr_vec3 *points_dev_out, pr_vec3 *normals_dev_out, uint32_t *n_out)
@@ -209,16 +198,15 @@ int pr_ppf_scene_points_dev(const pr_scene_proj *scene, uint32_t stride, pr_vec3
     const char *fn = "pr_ppf_scene_points_dev";
     if (!scene || !scene->pcd || !scene->normal || !points_dev_out || !normals_dev_out || !n_out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
     if (stride == 0 || stride > PR_PPF_MAX_STRIDE) { set_error("%s: stride must be 1 .. PR_PPF_MAX_STRIDE = %d (got %u)", fn, PR_PPF_MAX_STRIDE, stride); return PR_ERR_INVALID; }
-    if (scene->width == 0 || scene->height == 0) { set_error("%s: bad arguments (an empty frame)", fn); return PR_ERR_INVALID; }
-    if (!frame_size_ok(scene->width, scene->height)) return PR_ERR_INVALID;
+    PR_TRY(frame_ok(fn, scene->width, scene->height));
     PR_ENTER();
     const uint32_t W = (uint32_t)scene->width, H = (uint32_t)scene->height, gh = (H + stride - 1) / stride;
     PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * (2 * (size_t)gh + 1)));
     uint32_t *row_count = g->ppf_tmp.as<uint32_t>(), *row_off = row_count + gh;
     const float *pcd = reinterpret_cast<const float *>(scene->pcd), *normal = reinterpret_cast<const float *>(scene->normal);
     HIP_TRY(prk::launch_ppf_scene_count(pcd, normal, W, H, stride, row_count, row_off, g->stream));
-    PR_TRY(read_words(row_off + gh, 1));
-    const uint32_t n = *g->h_ppf.as<uint32_t>();
+    uint32_t n = 0;
+    PR_TRY(read_back_words(row_off + gh, &n, 1, g->stream));
     *n_out = n;
     if (n > PR_PPF_MAX_SCENE_POINTS) { set_error("%s: %u points at stride %u, at most PR_PPF_MAX_SCENE_POINTS = %d (raise the stride)", fn, n, stride, PR_PPF_MAX_SCENE_POINTS); return PR_ERR_INVALID; }
     if (n == 0) return PR_OK;

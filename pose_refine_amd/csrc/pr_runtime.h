@@ -208,6 +208,12 @@ inline bool frame_size_ok(size_t W, size_t H)
     if (W > 8192 || H > 8192 || W * H > ((size_t)1 << 24)) { set_error("frames larger than 8192 on a side or 2^24 pixels are not supported (got %zux%zu)", W, H); return false; }
     return true;
 }
+// a frame as the frame stages' entry points take it (fn: the entry point's name): not empty, and of a size frame_size_ok lets pass
+inline int frame_ok(const char *fn, size_t W, size_t H)
+{
+    if (W == 0 || H == 0) { set_error("%s: bad arguments (an empty frame)", fn); return PR_ERR_INVALID; }
+    return frame_size_ok(W, H) ? PR_OK : PR_ERR_INVALID;
+}
 inline bool roi_ok(pr_roi roi, uint32_t W, uint32_t H)
 {
     if (roi.width <= 0 || roi.height <= 0) return true;            // no ROI

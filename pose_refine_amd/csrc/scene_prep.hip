@@ -79,9 +79,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void nn_gather_count_kernel(const T *__restrict__ depth, uint32_t W, uint32_t H, uint32_t *__restrict__ row_count)
 {
     const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= H) return;
-    uint32_t cnt = 0;
-    for (uint32_t x0 = 0; x0 < W; x0 += 64) { const uint32_t x = x0 + lane; cnt += (uint32_t)__popcll(__ballot(x < W && depth_as_u16<T>(depth[(size_t)row * W + x]) > 0)); }
+    if (row >= H) return;                                          // (a whole wavefront: a row each)
+    const uint32_t cnt = wave_compact_count(W, lane, [&](uint32_t x) { return depth_as_u16<T>(depth[(size_t)row * W + x]) > 0; });
     if (lane == 0) row_count[row] = cnt;
 }
 template <typename T>
@@ -92,19 +91,19 @@ __global__ __launch_bounds__(256) void nn_gather_emit_kernel(const T *__restrict
     const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= H) return;
     uint32_t done = row_off[row];
+    // on wave_compact_step, not wave_compact_place: the depth the test reads is the point's z, and a keep test and a visitor apart load it
+    // twice (the compiler does not merge the two: one more load per point and six more VGPRs, profiles/frame_compact/README.md)
     for (uint32_t x0 = 0; x0 < W; x0 += 64) {
         const uint32_t x = x0 + lane;
         uint16_t d = 0;
         if (x < W) d = depth_as_u16<T>(depth[(size_t)row * W + x]);
-        const bool v = d > 0;
-        const unsigned long long m = __ballot(v);
-        if (v) {
-            const uint32_t k = done + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const WaveSlot slot = wave_compact_step(d > 0, lane, done);
+        if (d > 0) {
             const float z = (float)(int)d / 1000.0f;
             pr_vec3 p; p.x = ((float)x - cx) / fx * z; p.y = ((float)row - cy) / fy * z; p.z = z;
-            pcd[k] = p; nrm[k] = normal_full[(size_t)row * W + x];
+            pcd[slot.pos] = p; nrm[slot.pos] = normal_full[(size_t)row * W + x];
         }
-        done += (uint32_t)__popcll(m);
+        done += slot.kept;
     }
 }
 

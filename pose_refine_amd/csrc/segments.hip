@@ -174,31 +174,27 @@ __global__ __launch_bounds__(kSegBlock) void segment_flatten_kernel(uint32_t n_p
     }
 }
 
-// ---- the qualifying roots in root order: a wavefront per chunk of kSegChunk pixel indices (planes.hip's count, scan, emit) -------------------
+// ---- the qualifying roots in root order: a wavefront per chunk of kSegChunk pixel indices (count, scan, emit) --------------------------------
 __global__ __launch_bounds__(64) void segment_root_count_kernel(const uint32_t *__restrict__ parent, const uint32_t *__restrict__ count, uint32_t n_px, uint32_t min_pixels,
                                                                 uint32_t *__restrict__ chunk_count, SegControl *__restrict__ ctl)
 {
     const uint32_t first = blockIdx.x * kSegChunk;
-    uint32_t n_roots = 0, n_keep = 0;
-    for (uint32_t o = threadIdx.x; o < kSegChunk; o += 64) {
+    uint32_t n_roots = 0;                                          // this lane's roots, qualifying or not: the keep test meets them all
+    const uint32_t n_keep = wave_compact_count(kSegChunk, threadIdx.x, [&](uint32_t o) {
         const uint32_t i = first + o;
         const bool is_root = i < n_px && parent[i] == i;
         n_roots += is_root ? 1u : 0u;
-        n_keep += (is_root && count[i] >= min_pixels) ? 1u : 0u;
-    }
-    n_roots = wave_sum_u32(n_roots); n_keep = wave_sum_u32(n_keep);
+        return is_root && count[i] >= min_pixels;
+    });
+    n_roots = wave_sum_u32(n_roots);
     if (threadIdx.x == 0) {
         chunk_count[blockIdx.x] = n_keep;
         if (n_roots) atomicAdd(&ctl->n_components, n_roots);
     }
 }
-__global__ __launch_bounds__(256) void segment_scan_kernel(const uint32_t *__restrict__ counts, uint32_t n, uint32_t *__restrict__ offsets, SegControl *__restrict__ ctl)
-{
-    __shared__ uint32_t buf[256], carry;
-    const uint32_t total = block_exclusive_scan(n, buf, &carry, [&](uint32_t i) { return counts[i]; }, [&](uint32_t i, uint32_t v) { offsets[i] = v; });
-    if (threadIdx.x == 0) { offsets[n] = total; ctl->n_qualifying = total; }
-}
-// count[root] becomes the root's position in the list (kNone: it does not qualify, or the list is full -- the call fails then)
+// count[root] becomes the root's position in the list (kNone: it does not qualify, or the list is full -- the call fails then).  On
+// wave_compact_step, not wave_compact_place: a root that is not kept is rewritten as well, and the test and the stores share one load of
+// parent[i] and count[i], which a keep test and a visitor apart would each make.
 __global__ __launch_bounds__(64) void segment_root_emit_kernel(const uint32_t *__restrict__ parent, uint32_t *__restrict__ count, uint32_t n_px, uint32_t min_pixels,
                                                                const uint32_t *__restrict__ chunk_off, SegRoot *__restrict__ roots)
 {
@@ -209,12 +205,11 @@ __global__ __launch_bounds__(64) void segment_root_emit_kernel(const uint32_t *_
         const bool is_root = i < n_px && parent[i] == i;
         const uint32_t pixels = is_root ? count[i] : 0u;
         const bool keep = is_root && pixels >= min_pixels;
-        const unsigned long long m = __ballot(keep);
-        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << threadIdx.x) - 1ull));
-        const bool stored = keep && pos < PR_SEGMENT_MAX_ROOTS;
-        if (stored) roots[pos] = SegRoot{ i, pixels };
-        if (is_root) count[i] = stored ? pos : kNone;
-        base += (uint32_t)__popcll(m);
+        const WaveSlot slot = wave_compact_step(keep, threadIdx.x, base);
+        const bool stored = keep && slot.pos < PR_SEGMENT_MAX_ROOTS;
+        if (stored) roots[slot.pos] = SegRoot{ i, pixels };
+        if (is_root) count[i] = stored ? slot.pos : kNone;
+        base += slot.kept;
     }
 }
 // the control words and the stored roots into the pinned block, by a grid that does not depend on how many there are
@@ -319,8 +314,10 @@ hipError_t launch_segment_init(SegControl *ctl, segments::Acc *acc, uint32_t n_a
 hipError_t launch_segment_tiles(const void *depth, bool depth_i32, uint32_t width, uint32_t height, uint32_t jump, uint32_t *parent, uint32_t *count, hipStream_t s)
 {
     const dim3 grid((width + kSegTileW - 1) / kSegTileW, (height + kSegTileH - 1) / kSegTileH), block(kSegTileW, kSegTileH);
-    if (depth_i32) hipLaunchKernelGGL(segment_tile_kernel<int32_t>, grid, block, 0, s, static_cast<const int32_t *>(depth), width, height, jump, parent, count);
-    else hipLaunchKernelGGL(segment_tile_kernel<uint16_t>, grid, block, 0, s, static_cast<const uint16_t *>(depth), width, height, jump, parent, count);
+    for_depth_type(depth_i32, [&](auto *tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        hipLaunchKernelGGL(segment_tile_kernel<T>, grid, block, 0, s, static_cast<const T *>(depth), width, height, jump, parent, count);
+    });
     return hipGetLastError();
 }
 
@@ -329,8 +326,10 @@ hipError_t launch_segment_seams(const void *depth, bool depth_i32, uint32_t widt
     const uint32_t n_vertical = ((width + kSegTileW - 1) / kSegTileW - 1) * height, n_total = n_vertical + ((height + kSegTileH - 1) / kSegTileH - 1) * width;
     if (n_total == 0) return hipSuccess;                           // one tile: no seam (the frame's size decides, not its content)
     const dim3 grid((n_total + kSegThreads - 1) / kSegThreads);
-    if (depth_i32) hipLaunchKernelGGL(segment_seam_kernel<int32_t>, grid, dim3(kSegThreads), 0, s, static_cast<const int32_t *>(depth), width, height, jump, n_vertical, n_total, parent);
-    else hipLaunchKernelGGL(segment_seam_kernel<uint16_t>, grid, dim3(kSegThreads), 0, s, static_cast<const uint16_t *>(depth), width, height, jump, n_vertical, n_total, parent);
+    for_depth_type(depth_i32, [&](auto *tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        hipLaunchKernelGGL(segment_seam_kernel<T>, grid, dim3(kSegThreads), 0, s, static_cast<const T *>(depth), width, height, jump, n_vertical, n_total, parent);
+    });
     return hipGetLastError();
 }
 
@@ -346,7 +345,7 @@ hipError_t launch_segment_compact(const uint32_t *parent, uint32_t *count, uint3
 {
     const uint32_t n_chunks = (n_px + kSegChunk - 1) / kSegChunk;
     hipLaunchKernelGGL(segment_root_count_kernel, dim3(n_chunks), dim3(64), 0, s, parent, (const uint32_t *)count, n_px, min_pixels, chunk_count, ctl);
-    hipLaunchKernelGGL(segment_scan_kernel, dim3(1), dim3(256), 0, s, (const uint32_t *)chunk_count, n_chunks, chunk_off, ctl);
+    { hipError_t e = launch_scan_counts(chunk_count, n_chunks, chunk_off, &ctl->n_qualifying, false, s); if (e != hipSuccess) return e; }
     hipLaunchKernelGGL(segment_root_emit_kernel, dim3(n_chunks), dim3(64), 0, s, parent, count, n_px, min_pixels, (const uint32_t *)chunk_off, roots);
     hipLaunchKernelGGL(segment_export_kernel, dim3(2 * PR_SEGMENT_MAX_ROOTS / kSegThreads), dim3(kSegThreads), 0, s, (const SegControl *)ctl, (const SegRoot *)roots,
                        static_cast<uint32_t *>(out_mapped));
@@ -357,8 +356,10 @@ hipError_t launch_segment_relabel(const void *depth, bool depth_i32, uint32_t wi
                                   const uint16_t *rank_label, uint32_t n_found, uint16_t *labels, uint32_t *roots_out, segments::Acc *acc, hipStream_t s)
 {
     const dim3 grid((width + kSegTileW - 1) / kSegTileW, (height + kSegTileH - 1) / kSegTileH), block(kSegTileW, kSegTileH);
-    if (depth_i32) hipLaunchKernelGGL(segment_relabel_kernel<int32_t>, grid, block, 0, s, static_cast<const int32_t *>(depth), width, height, parent, slot, rank_label, n_found, labels, roots_out, acc);
-    else hipLaunchKernelGGL(segment_relabel_kernel<uint16_t>, grid, block, 0, s, static_cast<const uint16_t *>(depth), width, height, parent, slot, rank_label, n_found, labels, roots_out, acc);
+    for_depth_type(depth_i32, [&](auto *tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        hipLaunchKernelGGL(segment_relabel_kernel<T>, grid, block, 0, s, static_cast<const T *>(depth), width, height, parent, slot, rank_label, n_found, labels, roots_out, acc);
+    });
     return hipGetLastError();
 }
 
@@ -366,8 +367,10 @@ hipError_t launch_segment_depth(const uint16_t *labels, const void *depth_in, vo
                                 uint32_t n_keep, hipStream_t s)
 {
     const dim3 grid((n_px + kSegThreads - 1) / kSegThreads);
-    if (depth_i32) hipLaunchKernelGGL(segment_depth_kernel<int32_t>, grid, dim3(kSegThreads), 0, s, labels, static_cast<const int32_t *>(depth_in), static_cast<int32_t *>(depth_out), n_px, keep_bits, n_keep);
-    else hipLaunchKernelGGL(segment_depth_kernel<uint16_t>, grid, dim3(kSegThreads), 0, s, labels, static_cast<const uint16_t *>(depth_in), static_cast<uint16_t *>(depth_out), n_px, keep_bits, n_keep);
+    for_depth_type(depth_i32, [&](auto *tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        hipLaunchKernelGGL(segment_depth_kernel<T>, grid, dim3(kSegThreads), 0, s, labels, static_cast<const T *>(depth_in), static_cast<T *>(depth_out), n_px, keep_bits, n_keep);
+    });
     return hipGetLastError();
 }
 

@@ -46,7 +46,7 @@ def test_model_table_equals_reference(gpu, n_angle):
 
 
 # ---- the scene sample -----------------------------------------------------------------------------------------------------------------------
-def _synthetic_scene(w=64, h=48, seed=5):
+def _synthetic_scene(w=64, h=48, seed=5, blank_row=None):
     rng = np.random.default_rng(seed)
     pcd = rng.uniform(-0.3, 0.3, (h, w, 3)).astype(np.float32)
     pcd[..., 2] = rng.uniform(0.2, 0.9, (h, w)).astype(np.float32)
@@ -60,6 +60,9 @@ def _synthetic_scene(w=64, h=48, seed=5):
     nrm[0, 0] = [0, 0, -1]; pcd[0, 0] = [0.1, 0.1, 0.5]             # the first pixel kept
     nrm[9, 12] = [0, 1e-30, 0]                                      # one non-zero component is a normal
     pcd[9, 12] = [0.0, 0.0, 0.25]
+    if blank_row is not None:
+        pcd[blank_row] = 0                                          # a sampled row that keeps nothing
+        nrm[blank_row] = 0
     sc = api.Scene_projective()
     sc.width, sc.height, sc.K = w, h, synth.K_TEST
     sc.pcd_buffer = api.DeviceVector.from_host(pcd.reshape(-1))
@@ -67,10 +70,14 @@ def _synthetic_scene(w=64, h=48, seed=5):
     return sc, pcd, nrm
 
 
+# 64 x 48: a row is one 64-column step; 130 x 37: two full steps and a ragged third of two lanes at stride 1, 44 and 33 sampled columns at strides 3
+# and 4, a height that neither divides; 70 x 300: 300 row counts, a carry across the scan's 256-chunk.  Row 12 of the two larger frames (sampled at
+# every stride) is blank.
 @pytest.mark.parametrize("stride", [1, 3, 4])
-def test_scene_sample_equals_reference(gpu, stride):
-    sc, pcd, nrm = _synthetic_scene()
-    want_p, want_n = R.scene_points(pcd, nrm, 64, 48, stride)
+@pytest.mark.parametrize("w,h", [(64, 48), (130, 37), (70, 300)])
+def test_scene_sample_equals_reference(gpu, w, h, stride):
+    sc, pcd, nrm = _synthetic_scene(w, h, blank_row=None if (w, h) == (64, 48) else 12)
+    want_p, want_n = R.scene_points(pcd, nrm, w, h, stride)
     pts, nr, n = api.ppf_scene_points(sc, stride)
     assert n == len(want_p) > 0
     got_p, got_n = pts.to_host()[:3 * n].reshape(n, 3), nr.to_host()[:3 * n].reshape(n, 3)

@@ -1206,6 +1206,78 @@ int  pr_segment_depth_dev(const uint16_t *labels_dev, const void *depth_in_dev, 
                           void *depth_out_dev);
 int  pr_segment_roi(const pr_segment *segment, size_t width, size_t height, uint32_t margin, pr_roi *roi_out);
 
+/* ---- depth conditioning: fuse frames, drop flying pixels, median, fill holes -----------------------------------------------------------------
+ * The stage in front of all the others, for a frame that comes from a camera and not from a renderer: the values a sensor reports between
+ * foreground and background at a depth jump (flying pixels), per-pixel noise and holes.  The cleaned frame keeps the caller's depth type and
+ * goes unchanged into pr_scene_proj_prepare_dev, pr_scene_nn_prepare_dev, pr_scene_planes_dev, pr_scene_segments_dev, the PPF sampler and every
+ * scorer.  Integers only; every output byte is fixed by this text, on the device and on the host.  Every output value is one of the input
+ * values, so the depth type never overflows.
+ *   frame: width x height depths, uint16 or int32 (depth_is_i32), 1 <= width, height <= 65535 and width * height <= 2^26; otherwise
+ *     PR_ERR_INVALID.  A pixel's index is y * width + x.  A pixel outside the frame is not measured.
+ *   D0[p]: the depth as an unsigned 32-bit value; a non-positive int32 is 0, which means not measured (pr_scene_segments_dev's rule).
+ *   lower median of a non-empty multiset of k values: element (k - 1) / 2 (integer division) of its ascending order.
+ *   |a - b|: the larger minus the smaller, as unsigned 32-bit integers (no overflow).
+ * pr_depth_fuse_dev: the per-pixel median over 1 <= n_frames <= PR_DEPTH_FUSE_MAX frames of ONE view, 1 <= min_frames <= n_frames.  Per pixel: M =
+ * the multiset of the D0 values that are not 0 over the frames, count = |M| (count_out_dev, one uint8 per pixel, may be NULL), out = the lower
+ * median of M when count >= min_frames, else 0.  frames: a HOST array of n_frames device pointers (they travel as kernel arguments; two entries may
+ * be the same pointer); n_px: 1 .. 2^26 pixels.  depth_out_dev may be one of the frames: the operation is element-wise, every value of a pixel is
+ * read before the pixel is written.  One launch, one stream synchronise, no hipMemcpy.  PR_ERR_INVALID with nothing written: a null table, entry or
+ * output, n_frames, min_frames or n_px outside their limits.
+ * pr_depth_filter_dev: four stages; each reads only the stage before it, over the whole frame, so the result depends on no order.
+ *   tol(d) = tol_mm + floor(d * tol_permille / 1000), the product formed in 64 bits; the sum fits 32 bits.
+ *   gate:   G[p] = D0[p] when D0[p] != 0, D0[p] >= min_mm and (max_mm == 0 or D0[p] <= max_mm); otherwise 0.
+ *   flying: support(p) = the number of the 8 neighbours q of p inside the frame with G[q] != 0 and |G[q] - G[p]| <= tol(G[p]) (a corner pixel has
+ *     three neighbours, a border pixel five).  F[p] = G[p] when G[p] != 0 and (fly_min_support == 0 or support(p) >= fly_min_support); otherwise 0.
+ *   median, where F[p] != 0: S = { F[q] : q in the frame, |qx - px| <= radius, |qy - py| <= radius, F[q] != 0, |F[q] - F[p]| <= tol(F[p]) } (S holds
+ *     F[p]); out[p] = the lower median of S.  radius == 0: out[p] = F[p].  Values across a depth jump are never mixed.
+ *   fill, only where D0[p] == 0 (a gated or flying pixel is never filled back) and fill_min > 0: C = { F[q] : q in the window, F[q] != 0 }.  When
+ *     |C| >= fill_min: m = the lower median of C, A = { c in C : |c - m| <= tol(m) }, out[p] = m when |A| >= fill_min, else 0.  Filled values
+ *     feed no other pixel.
+ *   every other pixel: out[p] = 0.
+ *   flags (flags_dev_out, one uint8 per pixel, may be NULL), exclusive and exhaustive: PR_DEPTH_UNMEASURED D0 == 0, out == 0; PR_DEPTH_KEPT
+ *     out == D0 != 0; PR_DEPTH_SMOOTHED D0 != 0, out != 0, out != D0; PR_DEPTH_GATED D0 != 0, G == 0; PR_DEPTH_FLYING G != 0, F == 0;
+ *     PR_DEPTH_FILLED D0 == 0, out != 0.
+ *   pr_depth_filter_counts (counts_host, may be NULL): n[c] = the number of pixels with flag c; reserved = 0.
+ * pr_depth_filter_describe (host only): fills and checks the parameters.  PR_ERR_INVALID with nothing written: min_mm, max_mm or tol_mm above
+ * 2^31 - 1; max_mm != 0 and min_mm > max_mm; tol_permille > 1000; fly_min_support > 8; radius > PR_DEPTH_FILTER_MAX_RADIUS; fill_min != 0 with
+ * radius == 0 or fill_min > (2 radius + 1)^2 - 1; a null out.  Every entry point checks its parameters against these rules (and reserved == 0).
+ * depth_out_dev must not be depth_in_dev (a stencil): PR_ERR_INVALID.  Parameters, null pointers and the frame's size are checked before any
+ * device is touched, and a refused call writes no output.  Synchronous, on the calling thread's context: the control words cleared, the stencil
+ * kernel, one stream synchronise and one pinned read-back of the counts, no hipMemcpy on the path; the same frame gives the same bytes on every call.
+ * pr_depth_fuse_host / pr_depth_filter_host: the same over host arrays, from the same shared code: the CPU twins the device is held to.
+ * Not offered: a bilateral or mean filter (values would no longer be input values), speckle removal (pr_scene_segments_dev with min_pixels does
+ * that), an asynchronous form, fusion of frames from different views. */
+#define PR_DEPTH_FUSE_MAX           8
+#define PR_DEPTH_FILTER_MAX_RADIUS  2
+#define PR_DEPTH_UNMEASURED  0
+#define PR_DEPTH_KEPT        1
+#define PR_DEPTH_SMOOTHED    2
+#define PR_DEPTH_GATED       3
+#define PR_DEPTH_FLYING      4
+#define PR_DEPTH_FILLED      5
+typedef struct {
+    uint32_t min_mm, max_mm;           /* the range gate; max_mm == 0: no upper gate                                                  */
+    uint32_t tol_mm, tol_permille;     /* tol(d) = tol_mm + floor(d * tol_permille / 1000)                                            */
+    uint32_t fly_min_support;          /* 0 .. 8 supporting neighbours needed to keep a pixel; 0 = stage off                          */
+    uint32_t radius;                   /* 0 .. 2: the window's half-width; 0 = no median and no fill                                  */
+    uint32_t fill_min;                 /* 0 = off; else 1 .. (2 radius + 1)^2 - 1 neighbours needed to fill a hole                    */
+    uint32_t reserved;
+} pr_depth_filter_params;      /* 32 B */
+typedef struct {
+    uint32_t n[6];                     /* pixels per flag code PR_DEPTH_UNMEASURED .. PR_DEPTH_FILLED                                 */
+    uint32_t reserved[2];
+} pr_depth_filter_counts;      /* 32 B */
+int  pr_depth_filter_describe(uint32_t min_mm, uint32_t max_mm, uint32_t tol_mm, uint32_t tol_permille, uint32_t fly_min_support, uint32_t radius,
+                              uint32_t fill_min, pr_depth_filter_params *out);
+int  pr_depth_fuse_dev(const void *const *frames /* host array of n_frames device pointers */, uint32_t n_frames, int depth_is_i32, size_t n_px,
+                       uint32_t min_frames, void *depth_out_dev, uint8_t *count_out_dev /* may be NULL */);
+int  pr_depth_fuse_host(const void *const *frames /* host array of n_frames host pointers */, uint32_t n_frames, int depth_is_i32, size_t n_px,
+                        uint32_t min_frames, void *depth_out, uint8_t *count_out /* may be NULL */);
+int  pr_depth_filter_dev(const void *depth_in_dev, int depth_is_i32, size_t width, size_t height, const pr_depth_filter_params *params,
+                         void *depth_out_dev, uint8_t *flags_dev_out /* may be NULL */, pr_depth_filter_counts *counts_host /* may be NULL */);
+int  pr_depth_filter_host(const void *depth_in, int depth_is_i32, size_t width, size_t height, const pr_depth_filter_params *params,
+                          void *depth_out, uint8_t *flags_out /* may be NULL */, pr_depth_filter_counts *counts_out /* may be NULL */);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

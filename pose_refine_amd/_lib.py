@@ -156,6 +156,25 @@ class SegmentParamsDesc(C.Structure):
 assert C.sizeof(SegmentParamsDesc) == 16
 
 
+# pr_depth_filter_params: what pr_depth_filter_describe fills; pr_depth_filter_counts: the pixels per flag code of a pr_depth_filter_dev / _host call
+DEPTH_FUSE_MAX, DEPTH_FILTER_MAX_RADIUS = 8, 2                              # PR_DEPTH_FUSE_MAX, PR_DEPTH_FILTER_MAX_RADIUS
+DEPTH_UNMEASURED, DEPTH_KEPT, DEPTH_SMOOTHED, DEPTH_GATED, DEPTH_FLYING, DEPTH_FILLED = range(6)      # PR_DEPTH_*: a pixel's flag
+
+
+class DepthFilterParamsDesc(C.Structure):
+    """pr_depth_filter_params: the range gate, the tolerance, the support a pixel needs, the window and the fill threshold (pr_depth_filter_describe checks and fills it)."""
+    _fields_ = [("min_mm", C.c_uint32), ("max_mm", C.c_uint32), ("tol_mm", C.c_uint32), ("tol_permille", C.c_uint32), ("fly_min_support", C.c_uint32),
+                ("radius", C.c_uint32), ("fill_min", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DepthFilterCounts(C.Structure):
+    """pr_depth_filter_counts: n[c] = the pixels whose flag is c."""
+    _fields_ = [("n", C.c_uint32 * 6), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(DepthFilterParamsDesc) == 32 and C.sizeof(DepthFilterCounts) == 32
+
+
 class MeshRef(C.Structure):
     """pr_mesh_ref: one mesh of a mixed batch (pr_*_multi)."""
     _fields_ = [("tris_dev", C.c_void_p), ("n_tris", C.c_size_t)]
@@ -304,6 +323,11 @@ SIGNATURES = {
     "pr_scene_segments_host": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "pr_segment_depth_dev": (_i32, [_vp, _vp, _i32, _sz, _vp, _u32, _vp]),
     "pr_segment_roi": (_i32, [_vp, _sz, _sz, _u32, C.POINTER(Roi)]),
+    "pr_depth_filter_describe": (_i32, [_u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "pr_depth_fuse_dev": (_i32, [_vp, _u32, _i32, _sz, _u32, _vp, _vp]),
+    "pr_depth_fuse_host": (_i32, [_vp, _u32, _i32, _sz, _u32, _vp, _vp]),
+    "pr_depth_filter_dev": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "pr_depth_filter_host": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp]),
     "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_render_span": (_i32, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, Roi, _vp, _vp]),

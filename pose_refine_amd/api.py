@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SEGMENT, SEGMENT_DROPPED, SEGMENT_MAX, SEGMENT_MAX_ROOTS, SegmentParamsDesc, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (COMM_ID_BYTES, DEPTH_FILLED, DEPTH_FILTER_MAX_RADIUS, DEPTH_FLYING, DEPTH_FUSE_MAX, DEPTH_GATED, DEPTH_KEPT, DEPTH_SMOOTHED, DEPTH_UNMEASURED, DepthFilterCounts, DepthFilterParamsDesc, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SEGMENT, SEGMENT_DROPPED, SEGMENT_MAX, SEGMENT_MAX_ROOTS, SegmentParamsDesc, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -1801,6 +1801,108 @@ def segment_roi(segment, width: int, height: int, margin: int = 0):
     r = Roi()
     check(_lib.load().pr_segment_roi(ptr(rec), width, height, int(margin), C.byref(r)))
     return (r.x, r.y, r.width, r.height)
+
+
+# ------------------------------------------------------------------------------------------------
+# depth conditioning: fuse frames of one view, drop flying pixels, median, fill holes (pr_depth_fuse_* / pr_depth_filter_*; the definition is in include/pose_refine.h)
+# ------------------------------------------------------------------------------------------------
+def DepthFilterParams(min_mm: int = 0, max_mm: int = 0, tol_mm: int = 0, tol_permille: int = 0, fly_min_support: int = 0, radius: int = 0,
+                      fill_min: int = 0) -> DepthFilterParamsDesc:
+    """``pr_depth_filter_describe`` (host only): the parameters of a filter call, checked.  Every stage is off by default: no gate (``min_mm`` 0,
+    ``max_mm`` 0 = no upper gate), no flying-pixel test (``fly_min_support`` 0), no median and no fill (``radius`` 0, ``fill_min`` 0).
+    ``tol(d) = tol_mm + d * tol_permille // 1000`` is the depth difference within which two pixels count as one surface."""
+    dp = DepthFilterParamsDesc()
+    check(_lib.load().pr_depth_filter_describe(int(min_mm), int(max_mm), int(tol_mm), int(tol_permille), int(fly_min_support), int(radius), int(fill_min),
+                                               C.addressof(dp)))
+    return dp
+
+
+def _depth_filter_params(params, kw) -> DepthFilterParamsDesc:
+    if params is not None and kw:
+        raise ValueError("pass either params or keyword parameters")
+    return params if params is not None else DepthFilterParams(**kw)
+
+
+def _host_depth(depth, n_px: int) -> np.ndarray:
+    dep = np.ascontiguousarray(depth)
+    if dep.dtype not in (np.uint16, np.int32):
+        raise ValueError("scene depth must be CV_16U or CV_32S")
+    if dep.size != n_px:
+        raise ValueError(f"depth holds {dep.size} values, expected {n_px}")
+    return dep
+
+
+def depth_filter(depth, width: int, height: int, params: Optional[DepthFilterParamsDesc] = None, depth_out: Optional[DeviceVector] = None,
+                 want_flags: bool = False, **kw):
+    """``pr_depth_filter_dev``: a depth frame (a DeviceVector or a host image, uint16 or int32) with its range gate applied, its flying pixels
+    removed, an edge-preserving median over what is left and its holes filled.  Returns (cleaned DeviceVector of the depth's dtype[, flags
+    DeviceVector uint8[width * height]], counts): ``flags`` (``want_flags``) holds every pixel's ``DEPTH_*`` code, ``counts`` is a tuple of the six
+    codes' pixel counts.  The cleaned frame goes as it is into ``init_Scene_projective_device``, ``init_Scene_nn_device``, ``scene_planes``,
+    ``scene_segments``, ``generate_hypotheses`` and the scorers.  ``depth_out``: where it goes (never the input: the filter is a stencil); default
+    a new DeviceVector.  Parameters: a ``DepthFilterParams`` or its keywords."""
+    dp = _depth_filter_params(params, kw)
+    sd = _scene_depth_dev(depth, width, height)
+    out = depth_out if depth_out is not None else DeviceVector(width * height, sd.dtype)
+    if out.dtype != sd.dtype or out.size() != width * height:
+        raise ValueError("depth_out must have the depth's dtype and size")
+    flags = DeviceVector(width * height, np.uint8) if want_flags else None
+    cnt = DepthFilterCounts()
+    check(_lib.load().pr_depth_filter_dev(sd.data(), int(sd.dtype == np.int32), width, height, C.addressof(dp), out.data(), flags.data() if want_flags else None,
+                                          C.addressof(cnt)))
+    res = [out]
+    if want_flags:
+        res.append(flags)
+    res.append(tuple(cnt.n))
+    return tuple(res)
+
+
+def depth_filter_host(depth, width: int, height: int, params: Optional[DepthFilterParamsDesc] = None, want_flags: bool = False, **kw):
+    """``pr_depth_filter_host``: ``depth_filter`` over a host image (uint16 or int32), on the CPU, from the same definition.  Returns (cleaned
+    depth[height, width][, flags uint8[height, width]], counts); runs without a GPU."""
+    dp = _depth_filter_params(params, kw)
+    dep = _host_depth(depth, width * height)
+    out = np.zeros((height, width), dep.dtype)
+    flags = np.zeros((height, width), np.uint8) if want_flags else None
+    cnt = DepthFilterCounts()
+    check(_lib.load().pr_depth_filter_host(ptr(dep), int(dep.dtype == np.int32), width, height, C.addressof(dp), ptr(out), ptr(flags) if want_flags else None,
+                                           C.addressof(cnt)))
+    res = [out]
+    if want_flags:
+        res.append(flags)
+    res.append(tuple(cnt.n))
+    return tuple(res)
+
+
+def depth_fuse(frames, width: int, height: int, min_frames: int = 1, depth_out: Optional[DeviceVector] = None, want_count: bool = False):
+    """``pr_depth_fuse_dev``: the per-pixel lower median over 1 .. ``DEPTH_FUSE_MAX`` depth frames of ONE view (DeviceVectors or host images of one
+    dtype, uint16 or int32), taken over the frames that measured the pixel; 0 where fewer than ``min_frames`` did.  Returns the fused DeviceVector,
+    with ``want_count`` (fused, count DeviceVector uint8[width * height]).  ``depth_out``: where it goes (one of the frames is allowed)."""
+    fs = [_scene_depth_dev(f, width, height) for f in frames]
+    if not fs or any(f.dtype != fs[0].dtype for f in fs):
+        raise ValueError("depth_fuse takes at least one frame, all of one dtype")
+    n_px = width * height
+    out = depth_out if depth_out is not None else DeviceVector(n_px, fs[0].dtype)
+    if out.dtype != fs[0].dtype or out.size() != n_px:
+        raise ValueError("depth_out must have the frames' dtype and size")
+    count = DeviceVector(n_px, np.uint8) if want_count else None
+    table = (C.c_void_p * len(fs))(*[f.data() for f in fs])
+    check(_lib.load().pr_depth_fuse_dev(C.addressof(table), len(fs), int(fs[0].dtype == np.int32), n_px, int(min_frames), out.data(),
+                                        count.data() if want_count else None))
+    return (out, count) if want_count else out
+
+
+def depth_fuse_host(frames, width: int, height: int, min_frames: int = 1, want_count: bool = False):
+    """``pr_depth_fuse_host``: ``depth_fuse`` over host images, on the CPU, from the same definition.  Returns the fused depth[height, width], with
+    ``want_count`` (fused, count uint8[height, width]); runs without a GPU."""
+    n_px = width * height
+    fs = [_host_depth(f, n_px) for f in frames]
+    if not fs or any(f.dtype != fs[0].dtype for f in fs):
+        raise ValueError("depth_fuse_host takes at least one frame, all of one dtype")
+    out = np.zeros((height, width), fs[0].dtype)
+    count = np.zeros((height, width), np.uint8) if want_count else None
+    table = (C.c_void_p * len(fs))(*[ptr(f) for f in fs])
+    check(_lib.load().pr_depth_fuse_host(C.addressof(table), len(fs), int(fs[0].dtype == np.int32), n_px, int(min_frames), ptr(out), ptr(count) if want_count else None))
+    return (out, count) if want_count else out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1323,6 +1323,10 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *                              ONE launch, a 1024-lane workgroup per hypothesis that meets once per pass in LDS; 0 = one launch per pass and pose group
  *                              everywhere.  Same results either way.  A plan whose blocks would need more than 64 KiB of LDS (over 127 blocks per hypothesis)
  *                              keeps the multi-launch loop ("stat_resident_batches", read-only: sub-batches of this process whose loop ran as one launch)
+ *   "loop_lds_blocks"  [-1]    "resident_loop": blocks of "points_per_block" points at the head of every cloud that the workgroup keeps in its compute unit's LDS
+ *                              over the whole loop instead of moving them through memory every pass; -1 = as many as fit in 160 KiB behind the loop's own
+ *                              rows (four of 3072 points), 0 = none, n > 0 = at most n.  Same results either way ("stat_loop_lds_blocks", read-only: the
+ *                              number the most recent such launch ran with)
  *   "nn_stack"         [1]     kd-tree query: per-lane LDS stack (1) or the reference's stackless walk (0)
  *   "nn_compact"       [1]     stack query on 32-byte node records with 16-bit outward-rounded boxes (0: exact 64-byte records)
  *   "host_worker"      [1]     host solve: a batch given to pr_refine_submit runs on a library-owned helper thread of its slot (private context: its own

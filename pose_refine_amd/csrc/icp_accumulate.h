@@ -142,8 +142,13 @@ __device__ __forceinline__ void accumulate_point(Acc29 &acc, float sx, float sy,
 }
 // `tib`: the lane's place in the 256-lane block of the canonical tree.  icp_pass_kernel's workgroup IS that block (vb_accumulate below);
 // icp_loop_cu_kernel hands a (virtual block, wavefront) pair to any of its sixteen wavefronts: tib = 64 * wavefront-of-the-block + lane.
-template <class Scene, bool kNN, int kStack, bool kScoreOnly = false, bool kRobust = false>
-__device__ __forceinline__ void vb_accumulate_at(uint32_t tib, float (&acc_out)[29], float *cl, uint32_t n, uint32_t first, uint32_t steps, bool xf,
+// `src` / `dst`: where the lane's points come from and where the moved points go, as byte-for-byte images of the cloud (12-byte records, point j at
+// j * 12).  Everyone but the resident loop passes the cloud in memory for both.  icp_loop_cu_kernel keeps the head of a cloud in LDS and names the
+// pair PER CALL SITE (memory -> memory, memory -> LDS with kStoreAlways, LDS -> LDS): after inlining each site's loads and stores have one address
+// space, known at compile time -- never a run-time choice between an LDS and a memory pointer, which would turn them into flat instructions.
+// kStoreAlways: the points are stored to `dst` also when no update is pending (the first fill of the LDS image).
+template <class Scene, bool kNN, int kStack, bool kScoreOnly = false, bool kRobust = false, bool kStoreAlways = false>
+__device__ __forceinline__ void vb_accumulate_at(uint32_t tib, float (&acc_out)[29], const float *src, float *dst, uint32_t n, uint32_t first, uint32_t steps, bool xf,
                                                  const float (&M)[12], const Scene &scene, const int4 *lds_topo, int *stk_node, float *stk_lb,
                                                  uint32_t *nn_prev = nullptr, bool nn_seeded = false, const RobustW &rb = RobustW{})
 {
@@ -168,13 +173,14 @@ __device__ __forceinline__ void vb_accumulate_at(uint32_t tib, float (&acc_out)[
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i) {
             const uint32_t j = point_of(j0, i);
-            const pr_vec3 v = ld_off<pr_vec3>(cl, (j < last ? j : last) * 12u);
+            const pr_vec3 v = ld_off<pr_vec3>(src, (j < last ? j : last) * 12u);
             p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z;
         }
     };
     auto process_step = [&](float (&p)[12], uint32_t j0, uint32_t cnt) {
         if (cnt == 0) return;
-        if ((!kNN || kStack != -1) && xf) {                      // icp.cu:142-153 transform_pcd_cuda, fused (never in the winners pass: nn_search_kernel has moved the cloud -- said at compile time, so that no conditional store stands between the point loads and the winner loads)
+        const bool moved = (!kNN || kStack != -1) && xf, put = kStoreAlways || moved;
+        if (moved) {                                             // icp.cu:142-153 transform_pcd_cuda, fused (never in the winners pass: nn_search_kernel has moved the cloud -- said at compile time, so that no conditional store stands between the point loads and the winner loads)
             // rows 0 and 1 of the update side by side in packed instructions (same per-element operations, same order:
             // ((m0*x + m1*y) + m2*z) + m3), row 2 scalar
             const float2v Mx{ M[0], M[4] }, My{ M[1], M[5] }, Mz{ M[2], M[6] }, Mt{ M[3], M[7] };
@@ -189,18 +195,20 @@ __device__ __forceinline__ void vb_accumulate_at(uint32_t tib, float (&acc_out)[
                 p[3 * i + 1] = t.y;
                 p[3 * i + 2] = M[8] * x + M[9] * y + M[10] * z + M[11];
             }
+        }
 #if !PR_PASS_LATE_STORE
+        if (put) {
 #pragma unroll
             for (uint32_t i = 0; i < 4; ++i)
-                if (i < cnt) st_off<pr_vec3>(cl, point_of(j0, i) * 12u, pr_vec3{ p[3 * i], p[3 * i + 1], p[3 * i + 2] });
-#endif
+                if (i < cnt) st_off<pr_vec3>(dst, point_of(j0, i) * 12u, pr_vec3{ p[3 * i], p[3 * i + 1], p[3 * i + 2] });
         }
+#endif
         auto store_back = [&]() {
 #if PR_PASS_LATE_STORE
-            if ((!kNN || kStack != -1) && xf) {
+            if (put) {
 #pragma unroll
                 for (uint32_t i = 0; i < 4; ++i)
-                    if (i < cnt) st_off<pr_vec3>(cl, point_of(j0, i) * 12u, pr_vec3{ p[3 * i], p[3 * i + 1], p[3 * i + 2] });
+                    if (i < cnt) st_off<pr_vec3>(dst, point_of(j0, i) * 12u, pr_vec3{ p[3 * i], p[3 * i + 1], p[3 * i + 2] });
             }
 #endif
         };
@@ -300,7 +308,7 @@ __device__ __forceinline__ void vb_accumulate(float (&acc_out)[29], float *cl, u
                                               const float (&M)[12], const Scene &scene, const int4 *lds_topo, int *stk_node, float *stk_lb,
                                               uint32_t *nn_prev = nullptr, bool nn_seeded = false, const RobustW &rb = RobustW{})
 {
-    vb_accumulate_at<Scene, kNN, kStack, kScoreOnly, kRobust>(threadIdx.x, acc_out, cl, n, first, steps, xf, M, scene, lds_topo, stk_node, stk_lb, nn_prev, nn_seeded, rb);
+    vb_accumulate_at<Scene, kNN, kStack, kScoreOnly, kRobust>(threadIdx.x, acc_out, cl, cl, n, first, steps, xf, M, scene, lds_topo, stk_node, stk_lb, nn_prev, nn_seeded, rb);
 }
 
 // canonical tree, second half, the wavefront's part: balanced pairwise over the 64 lanes.  `row` (LDS, kAccStride floats) receives the

@@ -104,13 +104,41 @@ __device__ __forceinline__ float sum_partials(const float *partial, uint32_t pos
 //  barrier, so every wavefront -- also one without items -- meets both barriers of every pass.
 //  DevIcpState stays in the LDS header over the loop (only wavefront 0 touches it; registers are left to the point work) and is stored once;
 //  PoseMeta is left as the multi-launch loop leaves it (kSkip, the last update).  Same source per point, same tree: the same bytes.
-//  LDS (dynamic): b.nblk * 4 rows of kAccStride floats, then kLoopHeader words: [0..11] update, [12] finished, [16..35] DevIcpState.
+//  LDS (dynamic): b.nblk * 4 rows of kAccStride floats, then kLoopHeader words: [0..11] update, [12] finished, [16..35] DevIcpState, then
+//  the LDS image of the cloud's head (option "loop_lds_blocks").
+//  The head of the cloud in LDS: the workgroup has its compute unit to itself (sixteen wavefronts of 124+ VGPRs are the whole register file),
+//  so the LDS beyond rows and header is free.  Points [0, b.lds_blocks * ppb) -- whole blocks, items 0 .. 4 * b.lds_blocks - 1 -- are loaded from
+//  memory in pass 0 (pending transform applied exactly where the other items apply it), stored to LDS whether moved or not, and from pass 1 on
+//  read from LDS, moved and written to LDS: their 12 + 12 bytes per point and pass never reach the fabric, and the first of a step's two
+//  dependent trips (point, then scene gather) is an LDS access.  The other items run as before.  The item -> wavefront -> lane mapping is
+//  fixed, so a lane reads only LDS words that it stored itself in its own pass 0 or later -- no barrier beyond the two of a pass, and a
+//  workgroup that follows another one on the compute unit never sees what that one left.  The one exception is the clamp: a lane past the end
+//  of the cloud reads the cloud's LAST point and never uses it.  Blocks are resident whole, so for a lane of a resident block that index, below the
+//  lane's own, is inside the image, and its owner stored it ahead of pass 0's first barrier (pass 0 itself reads memory); a later pass may
+//  read it while the owner rewrites it -- the value is discarded, as in memory.
+//  Layout: 12-byte records, point j at byte 12 j, the cloud's own layout -- the lane's byte offset serves both address spaces.  Banks: the
+//  accesses are ds_read2_b32 + ds_read_b32 (and their writes), banked (a / 4) mod 32 per 32-lane half; adjacent lanes hold adjacent points,
+//  word 3 t + k for lane t, and 3 is odd, so the 32 lanes of a half fall on 32 different banks: conflict-free, six LDS cycles per point
+//  and wavefront, the same as three planes of floats would cost, without three base registers.
+//  The cloud in MEMORY is left stale for the resident points (nothing is flushed): a slot's cloud buffer is private scratch that only the emit
+//  writes and only the loop of the same sub-batch reads, and the next sub-batch's emit overwrites it (AsyncBatch::sub_batch, pr_refine.cpp).
 // ================================================================================================
 constexpr uint32_t kLoopLanes = 1024, kLoopWaves = kLoopLanes / 64, kLoopHeader = 64;
 // (Measured and not kept: the two barriers with a fence on LDS alone, so that a wavefront does not wait for its cloud stores before it meets the
 // others -- 330.2-332.9 k against 329.7-332.5 k poses/s for __syncthreads, five alternating runs on one box.)
 static_assert(sizeof(DevIcpState) == 20 * sizeof(uint32_t), "the LDS header holds DevIcpState as 20 words");
 size_t icp_loop_cu_lds_bytes(uint32_t nblk) { return ((size_t)nblk * 4 * kAccStride + kLoopHeader) * sizeof(float); }
+// blocks of a cloud's head that the kernel keeps in LDS behind rows and header: as many whole blocks of steps * 1024 points as the compute unit's
+// LDS holds, at most the plan's nblk and at most `cap` (option "loop_lds_blocks": negative = no cap)
+uint32_t icp_loop_cu_lds_blocks(uint32_t nblk, uint32_t steps, int cap)
+{
+    const size_t fixed = icp_loop_cu_lds_bytes(nblk), block = (size_t)steps * kPointsPerStep * sizeof(pr_vec3);
+    if (fixed > kLoopCuLdsBudget || block == 0) return 0;
+    const size_t fit = (kLoopCuLdsTotal - fixed) / block;
+    uint32_t r = (uint32_t)(fit < nblk ? fit : nblk);
+    if (cap >= 0 && (uint32_t)cap < r) r = (uint32_t)cap;
+    return r;
+}
 
 template <class Scene>
 __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel(IcpBatch b, Scene scene)
@@ -128,6 +156,8 @@ __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel
     float *hdr = loop_lds + (size_t)b.nblk * 4 * kAccStride;
     uint32_t *hdw = reinterpret_cast<uint32_t *>(hdr);
     float *cl = reinterpret_cast<float *>(b.cloud + pm.start);
+    float *lcl = hdr + kLoopHeader;                              // the LDS image of points [0, b.lds_blocks * ppb) of the cloud
+    const uint32_t lds_items = b.lds_blocks * 4u;
     bool xf = (st0 == kRunWithTransform) && !b.pre_transformed;
     float M[12];
 #pragma unroll
@@ -142,11 +172,18 @@ __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel
             const uint32_t vb = item >> 2, tib = ((item & 3u) << 6) | lane;
             float acc[29];
             float *row = loop_lds + (size_t)item * kAccStride;
+            // where the item's points live (uniform): memory, or the LDS image -- filled from memory in pass 0, moved in place from then on.
+            // Three call sites per pass kind, each with one address space for its loads and one for its stores.
+            const bool in_lds = item < lds_items;
             if (score_only) {
-                vb_accumulate_at<Scene, false, 0, true>(tib, acc, cl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                if (!in_lds) vb_accumulate_at<Scene, false, 0, true>(tib, acc, cl, cl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                else if (it == 0) vb_accumulate_at<Scene, false, 0, true, false, true>(tib, acc, cl, lcl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                else vb_accumulate_at<Scene, false, 0, true>(tib, acc, lcl, lcl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
                 wave_reduce<true>(acc, lane, row);
             } else {
-                vb_accumulate_at<Scene, false, 0>(tib, acc, cl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                if (!in_lds) vb_accumulate_at<Scene, false, 0>(tib, acc, cl, cl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                else if (it == 0) vb_accumulate_at<Scene, false, 0, false, false, true>(tib, acc, cl, lcl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
+                else vb_accumulate_at<Scene, false, 0>(tib, acc, lcl, lcl, n, vb * ppb, b.steps, xf, M, scene, nullptr, nullptr, nullptr, nullptr, xf);
                 wave_reduce(acc, lane, row);
             }
         }
@@ -195,12 +232,23 @@ __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel
         wm->state = kSkip;
     }
 }
-hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s)
+hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s, uint32_t *lds_blocks_used)
 {
+    if (lds_blocks_used) *lds_blocks_used = 0;
     if (n_poses == 0 || b.nblk == 0) return hipSuccess;
-    const size_t lds = icp_loop_cu_lds_bytes(b.nblk);
+    size_t lds = icp_loop_cu_lds_bytes(b.nblk);
     if (lds > kLoopCuLdsBudget || b.robust_kind != PR_ROBUST_NONE) return hipErrorInvalidValue;   // (the caller keeps such batches on the multi-launch loop)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(icp_loop_cu_kernel<SceneProjPacked>), dim3(n_poses), dim3(kLoopLanes), lds, s, b, sc);
+    // b.lds_blocks is the caller's wish; what is launched never exceeds what icp_loop_cu_lds_blocks allows, and falls to none (the kernel
+    // as it was) when the device refuses dynamic LDS beyond 64 KiB
+    IcpBatch bb = b;
+    const uint32_t most = icp_loop_cu_lds_blocks(b.nblk, b.steps, -1);
+    if (bb.lds_blocks > most) bb.lds_blocks = most;
+    const size_t image = (size_t)bb.lds_blocks * b.steps * kPointsPerStep * sizeof(pr_vec3);
+    const auto fn = icp_loop_cu_kernel<SceneProjPacked>;
+    if (lds + image > kLoopCuLdsBudget && !lds_opt_in(reinterpret_cast<const void *>(fn), 0, (uint32_t)kLoopCuLdsTotal)) bb.lds_blocks = 0;
+    if (bb.lds_blocks) lds += image;
+    if (lds_blocks_used) *lds_blocks_used = bb.lds_blocks;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(icp_loop_cu_kernel<SceneProjPacked>), dim3(n_poses), dim3(kLoopLanes), lds, s, bb, sc);
     return hipGetLastError();
 }
 

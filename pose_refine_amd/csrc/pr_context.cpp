@@ -57,6 +57,7 @@ std::atomic<uint64_t> g_flag_overtook{ 0 };
 std::atomic<uint64_t> g_tight_batches{ 0 };
 std::atomic<uint64_t> g_band_batches{ 0 };
 std::atomic<uint64_t> g_resident_batches{ 0 };
+std::atomic<uint32_t> g_loop_lds_blocks{ 0 };
 Options opt;
 std::mutex g_reg_mu;
 std::vector<Ctx *> g_shared;         // index = device ordinal
@@ -307,6 +308,7 @@ int pr_set_option(const char *name, int value)
     else if (n == "graph") opt.use_graph = value ? 1 : 0;
     else if (n == "fused_solve") opt.fused_solve = value ? 1 : 0;
     else if (n == "resident_loop") opt.resident_loop = value ? 1 : 0;
+    else if (n == "loop_lds_blocks") opt.loop_lds_blocks = std::max(-1, value);
     else if (n == "sub_batch") opt.sub_batch = std::min(32768, std::max(32, value));    // (the hypothesis index is the y dimension of the launches)
     else if (n == "overlap_pass") opt.overlap_pass = std::max(-1, value);
     else if (n == "pose_groups") opt.pose_groups = std::min(4, std::max(0, value));
@@ -358,6 +360,8 @@ int pr_get_option(const char *name, int *value)
     else if (n == "graph") *value = opt.use_graph;
     else if (n == "fused_solve") *value = opt.fused_solve;
     else if (n == "resident_loop") *value = opt.resident_loop;
+    else if (n == "loop_lds_blocks") *value = opt.loop_lds_blocks;
+    else if (n == "stat_loop_lds_blocks") *value = (int)g_loop_lds_blocks.load();     // read-only
     else if (n == "stat_resident_batches") *value = (int)std::min<uint64_t>(g_resident_batches.load(), 0x7fffffffull);     // read-only
     else if (n == "sub_batch") *value = opt.sub_batch;
     else if (n == "overlap_pass") *value = opt.overlap_pass;

@@ -72,6 +72,7 @@ struct IcpBatch {
     // when robust_kind != PR_ROBUST_NONE.  (Behind every older member: their offsets in the kernel argument stay what they were.)
     uint32_t        robust_kind;
     float           robust_c, robust_inv_c;
+    uint32_t        lds_blocks; // icp_loop_cu_kernel only: blocks of every cloud's head kept in LDS over the loop (icp_loop_cu_lds_blocks); 0 = none
 };
 // the weight as the per-point audit kernels take it
 struct RobustArgs { uint32_t kind; float c, inv_c; float *corr; };   // corr: null, or n x 8 floats {dx, dy, dz, valid, nx, ny, nz, w}
@@ -360,7 +361,12 @@ hipError_t launch_icp_pass_proj_packed(const IcpBatch &b, const SceneProjPacked 
 // LDS grows with b.nblk, and a batch whose plan needs more than the budget stays on the multi-launch loop
 constexpr size_t kLoopCuLdsBudget = 64u << 10;
 size_t icp_loop_cu_lds_bytes(uint32_t nblk);
-hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s);
+// ... and behind rows and header the kernel keeps the first b.lds_blocks blocks of every cloud in LDS over the whole loop, up to the compute unit's
+// 160 KiB (icp_loop_cu_lds_blocks: how many fit, at most nblk and at most `cap`, negative = no cap; 0 for a plan over the budget above).
+// *lds_blocks_used receives the number the launch really ran with: 0 when the device refuses the LDS opt-in.
+constexpr size_t kLoopCuLdsTotal = 160u << 10;
+uint32_t icp_loop_cu_lds_blocks(uint32_t nblk, uint32_t steps, int cap);
+hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s, uint32_t *lds_blocks_used = nullptr);
 hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s);
 // split form of the kd-tree pass: search (pending transform applied, winners written to b.nn_prev) + gather/accumulate pass
 // marks (or null): three events recorded after the search, the bound and the walk kernel (timed batches; n_poses <= 32768)

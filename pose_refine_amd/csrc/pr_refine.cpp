@@ -1124,7 +1124,12 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
 #if PR_RESIDENT_RELEASE_AHEAD
         if (release) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
 #endif
-        HIP_TRY(prk::launch_icp_loop_cu_proj_packed(b, sc.pk, nq, st));
+        // Option loop_lds_blocks: the head of every cloud stays in the workgroup's LDS over the loop.  Those points of sl.cloud are stale afterwards,
+        // and nobody looks: the slot's cloud buffer is written by the emit above and read by this launch only (the next sub-batch's emit overwrites it).
+        b.lds_blocks = prk::icp_loop_cu_lds_blocks(pl.nblk, pl.steps, opt.loop_lds_blocks);
+        uint32_t lds_blocks_used = 0;
+        HIP_TRY(prk::launch_icp_loop_cu_proj_packed(b, sc.pk, nq, st, &lds_blocks_used));
+        g_loop_lds_blocks.store(lds_blocks_used);
 #if !PR_RESIDENT_RELEASE_AHEAD
         if (release) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
 #endif

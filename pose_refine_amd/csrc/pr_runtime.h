@@ -125,6 +125,7 @@ extern WriteLog g_writes;
 extern std::atomic<uint64_t> g_tight_batches;     // asynchronous batches whose pixel boxes came from pose_tight_box_kernel (process-wide; read-only option "stat_tight_batches": tests tell the tight path from the loose one by it)
 extern std::atomic<uint64_t> g_band_batches;      // asynchronous batches whose depth boxes were banded (option box_bands; read-only option "stat_band_batches": tests tell the banded path from the row-major one by it)
 extern std::atomic<uint64_t> g_resident_batches;  // asynchronous sub-batches whose whole loop ran as one launch (option resident_loop; read-only option "stat_resident_batches": tests tell the resident route from the multi-launch one by it)
+extern std::atomic<uint32_t> g_loop_lds_blocks;   // blocks of every cloud's head that the most recent resident launch kept in LDS (option loop_lds_blocks; read-only option "stat_loop_lds_blocks": tests tell a launch with an LDS image from one that quietly ran without)
 extern std::atomic<uint64_t> g_flag_overtook;    // PR_SOLVE_HOST: group flags that reached the host before all of their rows (process-wide; expected 0; read-only option "stat_flag_overtook")
 
 // ---- process-wide options (pr_set_option): plain ints, shared by every context ---------------------
@@ -160,6 +161,7 @@ struct Options {
     int sub_batch = 512;             // asynchronous fused path: hypotheses per sub-batch (cache residency of the clouds)
     int fused_solve = 1;             // PR_SOLVE_DEVICE: the workgroup delivering a hypothesis' last partial sum also runs its finalize + solve (no second launch per iteration)
     int resident_loop = 1;           // asynchronous fused path, packed projective scene, fused device solve, untimed: all passes of a sub-batch in ONE launch, a 1024-lane workgroup per hypothesis (icp_loop_cu_kernel, icp_pass.hip); 0 = the multi-launch loop everywhere.  Same bytes either way (profiles/resident_cu/README.md has the measurement)
+    int loop_lds_blocks = -1;        // resident loop: blocks of every cloud's head kept in the workgroup's LDS over the whole loop instead of moving through memory every pass; -1 = as many as fit in the compute unit's 160 KiB behind rows and header (four of 3072 points), 0 = none (every instruction path of a pass is then the one without the option), n > 0 = at most n.  Same bytes either way (profiles/loop_lds/README.md has the measurement)
     int use_graph = 1;             // PR_SOLVE_DEVICE, single pose group only (the runtime serialises the branches of a captured multi-stream
                                      // graph, which forfeits the overlap): capture the whole iteration loop in a hipGraph and replay it
     int eager_streams = 1;           // asynchronous path: create the streams of both slots in one run (see slot_streams)

@@ -13,8 +13,14 @@
 #endif
 
 #ifndef PR_LOOP_CU_WAVES
-#define PR_LOOP_CU_WAVES 0                                      // register budget of icp_loop_cu_kernel in waves per SIMD (its sixteen wavefronts are four per SIMD); 0: the compiler's own choice, 124 VGPRs and no scratch.  5 (96 VGPRs, room for a fifth wavefront of another kernel) spills 33 registers to 104 bytes of scratch per lane and runs 304.9 / 304.9 / 306.6 k against 324.2 / 325.0 / 325.5 k poses/s on one box: not used
+#define PR_LOOP_CU_WAVES 0                                      // register budget of icp_loop_cu_kernel in waves per SIMD (its sixteen wavefronts are four per SIMD); 0: the compiler's own choice, 126 VGPRs and no scratch (124 before the LDS image below).  5 (96 VGPRs, room for a fifth wavefront of another kernel) spills 33 registers to 104 bytes of scratch per lane and runs 304.9 / 304.9 / 306.6 k against 324.2 / 325.0 / 325.5 k poses/s on one box: not used
 #endif
+// (Option loop_lds_blocks, a run-time option and no knob here: icp_loop_cu_kernel keeps the first blocks of every cloud -- four of 3072 points, 56 % of the headline's points -- in the 155 KiB of
+// LDS its compute unit has left, so their 12 + 12 bytes per pass stay off the fabric.  Same box, parent and change alternating, five 100-step runs: 340.8-342.7 k against 331.1-332.2 k poses/s
+// (+3.1 %, every run above every run of the parent), loop_lds_blocks=0 330.5-331.6 k; the kernel 622 against 644 us per launch.  Its fabric reads fall from 1399 to 694 MB and its writes from 1278
+// to 730 MB per launch: HALF the traffic buys 3 % of the time.  The 32.5 against 38.4 us of the multi-launch pass without its stores (below) did not carry over to
+// this kernel: its pass is not the sum of its memory traffic.  What is left of a pass (29.6 us against a VALU floor of about 11) is then the scene gathers' rate and the wait for the slowest of
+// sixteen wavefronts -- read from the earlier counters (TA busy 64 %, profiles/r02), not measured again here.  profiles/loop_lds/README.md)
 #if PR_LOOP_CU_WAVES
 #define PR_LOOP_CU_ATTR __attribute__((amdgpu_waves_per_eu(PR_LOOP_CU_WAVES, PR_LOOP_CU_WAVES)))
 #else

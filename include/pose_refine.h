@@ -1336,11 +1336,20 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *                              order; a query whose minimum is attained by more than one point is repeated by the ordered binary walk (0: binary walk only)
  *   "nn_seed"          [1]     compact records: start every search from the previous pass' / previous point's winner distance
  *   "nn_split"         [1]     compact records: the search runs in a kernel of its own (adjacent lanes = adjacent cloud points, a workgroup
- *                              takes "nn_run" [8] chunks of 256 points) and the pass gathers its winners in canonical order
+ *                              takes "nn_run" [8] chunks of 256 points: 1..8, other values are clamped and read back clamped) and the pass gathers
+ *                              its winners in canonical order
  *   "nn_count"         [0]     instrumented runs: the search kernel counts its work (pr_nn_counters)
  *   "nn_grid"          [1]     fused refinement with a kd-tree scene made from a depth image: scene points are also indexed by pixel
  *                              (first bounds, and an exact window scan once the bound is a few pixels wide)
- *   "nn_lds_nodes"     [1024]  stackless query: leading nodes staged in LDS;  "nn_lds_records" [0]: the same for 64-byte records
+ *   "nn_lds_nodes"     [1024]  stackless query inside the pass (plain and robust): leading nodes of the tree staged in LDS, 16 bytes each; negative = 0, at
+ *                              most the tree, at most 8192 (128 KiB).  More than 4064 (64 KiB less the pass kernel's 512 static bytes) needs the device's
+ *                              opt-in for dynamic LDS beyond 64 KiB, asked for once per device; where it is refused the launch stages 4064 and runs
+ *   "nn_lds_records"   [0]     the same for the 64-byte records of the stack query without compact records: at most 504 beside 16-entry stacks, 248 beside
+ *                              24-entry ones (stacks, records and the 512 static bytes together are 64 KiB: no opt-in on this route)
+ *   "stat_nn_lds_nodes", "stat_nn_stack_depth"  (read-only) what the most recent kd-tree search INSIDE a pass (no "nn_split" search kernel) ran with,
+ *                              after every limit above: entries or records staged (0 with compact records) and stack entries per lane, 0 = the
+ *                              stackless walk.  "stat_nn_pass_launches" (read-only) counts those launches in this process; a replayed graph
+ *                              reports what it captured and counts nothing.  Same results at every setting
  *   "profile"          [0]     see below;  "sample_period" [32]: profile 2 times one call in this many
  *   "scene_cache"      [1]     keep derived scene data between calls (see "Caches" at the top)
  *   "pose_dist_chunk"  (read-only) model points a workgroup of pr_pose_distance stages at a time: where its point loop has its seams

@@ -346,16 +346,44 @@ hipError_t launch_icp_pass_proj_aos(const IcpBatch &b, const SceneProjAoS &sc, u
 // addresser: 0.84 against 0.82 ms per 21 launches, 272 / 263 k against 277 / 276 k poses/s on one box.  Not kept.)
 hipError_t launch_icp_pass_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s)
 { return b.robust_kind != PR_ROBUST_NONE ? launch_pass<SceneProjPacked, false, 0, true>(b, sc, n_poses, 0, s) : launch_pass<SceneProjPacked, false>(b, sc, n_poses, 0, s); }
-hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s)
+// the stackless walk (plain or robust instantiation, opt-in slots 1 and 2): the staged count never exceeds the tree or kNNLdsNodesMax whatever the
+// caller's record says, and falls to kNNLdsNodesPlain when the device refuses dynamic LDS beyond 64 KiB
+template <bool kRobust>
+static hipError_t launch_pass_nn_stackless(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s, NNPassRan *ran)
+{
+    SceneNNDev ss = sc;
+    ss.lds_nodes = sc.topo_nodes;                                // (sc.lds_nodes counts 64-byte records when sc.stack_depth selects a stack walk: the robust pass of such a scene)
+    if (ss.lds_nodes > ss.n_nodes) ss.lds_nodes = ss.n_nodes;
+    if (ss.lds_nodes > kNNLdsNodesMax) ss.lds_nodes = kNNLdsNodesMax;
+    const auto fn = icp_pass_kernel<SceneNNDev, true, 0, kRobust>;
+    if (ss.lds_nodes > kNNLdsNodesPlain && !lds_opt_in(reinterpret_cast<const void *>(fn), kRobust ? 2 : 1, kNNLdsNodesMax * (uint32_t)sizeof(int4))) ss.lds_nodes = kNNLdsNodesPlain;
+    if (ran) *ran = NNPassRan{ ss.lds_nodes, 0u };
+    return launch_pass<SceneNNDev, true, 0, kRobust>(b, ss, n_poses, (size_t)ss.lds_nodes * sizeof(int4), s);
+}
+// the per-lane-stack walk on exact 64-byte records: stacks + staged records + the kernel's static LDS stay within 64 KiB (nn_route's cap, held here too)
+template <int kDepth>
+static hipError_t launch_pass_nn_stack_exact(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s, NNPassRan *ran)
+{
+    constexpr uint32_t stacks = (uint32_t)kDepth * kBlockThreads * 8u, most = ((64u << 10) - kPassStaticLds - stacks) / 64u;
+    SceneNNDev ss = sc;
+    if (ss.lds_nodes > ss.n_nodes) ss.lds_nodes = ss.n_nodes;
+    if (ss.lds_nodes > most) ss.lds_nodes = most;
+    if (ran) *ran = NNPassRan{ ss.lds_nodes, (uint32_t)kDepth };
+    return launch_pass<SceneNNDev, true, kDepth>(b, ss, n_poses, (size_t)stacks + (size_t)ss.lds_nodes * 64, s);
+}
+hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s, NNPassRan *ran)
 {
     // a robust pass that searches in the pass (a scene without compact records: with them the driver takes the split route) walks stackless,
     // the one in-pass walk instantiated with the weight; every walk returns the same winners
-    if (b.robust_kind != PR_ROBUST_NONE) return launch_pass<SceneNNDev, true, 0, true>(b, sc, n_poses, (size_t)sc.lds_nodes * sizeof(int4), s);
-    if (sc.stack_depth == 16 && sc.rec32) return launch_pass<SceneNNDev, true, 16 + 0x100>(b, sc, n_poses, (size_t)16 * kBlockThreads * 8, s);
-    if (sc.stack_depth == 24 && sc.rec32) return launch_pass<SceneNNDev, true, 24 + 0x100>(b, sc, n_poses, (size_t)24 * kBlockThreads * 8, s);
-    if (sc.stack_depth == 16) return launch_pass<SceneNNDev, true, 16>(b, sc, n_poses, (size_t)16 * kBlockThreads * 8 + (size_t)sc.lds_nodes * 64, s);
-    if (sc.stack_depth == 24) return launch_pass<SceneNNDev, true, 24>(b, sc, n_poses, (size_t)24 * kBlockThreads * 8 + (size_t)sc.lds_nodes * 64, s);
-    return launch_pass<SceneNNDev, true, 0>(b, sc, n_poses, (size_t)sc.lds_nodes * sizeof(int4), s);
+    if (b.robust_kind != PR_ROBUST_NONE) return launch_pass_nn_stackless<true>(b, sc, n_poses, s, ran);
+    if ((sc.stack_depth == 16 || sc.stack_depth == 24) && sc.rec32) {                         // compact records: the stacks alone
+        if (ran) *ran = NNPassRan{ 0u, sc.stack_depth };
+        if (sc.stack_depth == 16) return launch_pass<SceneNNDev, true, 16 + 0x100>(b, sc, n_poses, (size_t)16 * kBlockThreads * 8, s);
+        return launch_pass<SceneNNDev, true, 24 + 0x100>(b, sc, n_poses, (size_t)24 * kBlockThreads * 8, s);
+    }
+    if (sc.stack_depth == 16) return launch_pass_nn_stack_exact<16>(b, sc, n_poses, s, ran);
+    if (sc.stack_depth == 24) return launch_pass_nn_stack_exact<24>(b, sc, n_poses, s, ran);
+    return launch_pass_nn_stackless<false>(b, sc, n_poses, s, ran);
 }
 
 hipError_t launch_icp_pass_nn_winners(const IcpBatch &b, const SceneNNWinners &sc, uint32_t n_poses, hipStream_t s)

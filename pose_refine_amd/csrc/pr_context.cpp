@@ -58,6 +58,8 @@ std::atomic<uint64_t> g_tight_batches{ 0 };
 std::atomic<uint64_t> g_band_batches{ 0 };
 std::atomic<uint64_t> g_resident_batches{ 0 };
 std::atomic<uint32_t> g_loop_lds_blocks{ 0 };
+std::atomic<uint32_t> g_nn_lds_nodes{ 0 }, g_nn_stack_depth{ 0 };
+std::atomic<uint64_t> g_nn_pass_launches{ 0 };
 Options opt;
 std::mutex g_reg_mu;
 std::vector<Ctx *> g_shared;         // index = device ordinal
@@ -301,7 +303,7 @@ int pr_set_option(const char *name, int value)
     else if (n == "nn_seed") opt.nn_seed = value ? 1 : 0;
     else if (n == "nn_stack") opt.nn_stack = value ? 1 : 0;
     else if (n == "nn_split") opt.nn_split = value ? 1 : 0;
-    else if (n == "nn_run") opt.nn_run = std::min(256, std::max(1, value));
+    else if (n == "nn_run") opt.nn_run = std::min(8, std::max(1, value));               // (what launch_nn_search takes: pose_refine.h)
     else if (n == "nn_grid") opt.nn_grid = value ? 1 : 0;
     else if (n == "nn_count") opt.nn_count = value ? 1 : 0;
     else if (n == "host_poll") opt.host_poll = value ? 1 : 0;
@@ -362,6 +364,9 @@ int pr_get_option(const char *name, int *value)
     else if (n == "resident_loop") *value = opt.resident_loop;
     else if (n == "loop_lds_blocks") *value = opt.loop_lds_blocks;
     else if (n == "stat_loop_lds_blocks") *value = (int)g_loop_lds_blocks.load();     // read-only
+    else if (n == "stat_nn_lds_nodes") *value = (int)g_nn_lds_nodes.load();           // read-only
+    else if (n == "stat_nn_stack_depth") *value = (int)g_nn_stack_depth.load();       // read-only
+    else if (n == "stat_nn_pass_launches") *value = (int)(g_nn_pass_launches.load() & 0x7fffffffull);   // read-only (wraps: tests take differences)
     else if (n == "stat_resident_batches") *value = (int)std::min<uint64_t>(g_resident_batches.load(), 0x7fffffffull);     // read-only
     else if (n == "sub_batch") *value = opt.sub_batch;
     else if (n == "overlap_pass") *value = opt.overlap_pass;

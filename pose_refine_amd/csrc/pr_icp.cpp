@@ -24,7 +24,10 @@ hipError_t launch_pass(const prk::IcpBatch &b, const SceneSel &sc, uint32_t P, h
             const prk::SceneNNWinners w{ sc.nn.max_dist_diff, sc.nn.pts, sc.nn.normal, b.nn_prev };
             return prk::launch_icp_pass_nn_winners(bb, w, P, st);
         }
-        return prk::launch_icp_pass_nn(b, sc.nn, P, st);
+        prk::NNPassRan ran{};
+        const hipError_t e = prk::launch_icp_pass_nn(b, sc.nn, P, st, &ran);
+        g_nn_lds_nodes.store(ran.lds_nodes); g_nn_stack_depth.store(ran.stack_depth); g_nn_pass_launches.fetch_add(1);
+        return e;
     }
     if (sc.kind == PR_SCENE_GRID) return prk::launch_icp_pass_grid(b, sc.grid, P, st);
     if (sc.packed) return prk::launch_icp_pass_proj_packed(b, sc.pk, P, st);
@@ -99,7 +102,9 @@ int cached_graph(const GraphKey &key, Enqueue &&enqueue, CachedGraph *&hit)
         CachedGraph c; c.key = key;
         HIP_TRY(hipStreamSynchronize(g->stream));
         HIP_TRY(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
+        const uint64_t nn_before = g_nn_pass_launches.load();
         int rc = enqueue();
+        if (g_nn_pass_launches.load() != nn_before) { c.nn_pass = true; c.nn_lds_nodes = g_nn_lds_nodes.load(); c.nn_stack_depth = g_nn_stack_depth.load(); }
         hipError_t ce = hipStreamEndCapture(g->stream, &c.graph);
         if (rc != PR_OK || ce != hipSuccess) { destroy_graph(c); if (rc == PR_OK) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce)); rc = PR_ERR_HIP; } return rc; }
         HIP_TRY(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
@@ -174,6 +179,7 @@ int drive_device(IcpRun &r)
         CachedGraph *hit = nullptr;
         PR_TRY(cached_graph(key, [&] { return enqueue_all(/*host_checks=*/false); }, hit));
         HIP_TRY(hipGraphLaunch(hit->exec, g->stream));
+        if (hit->nn_pass) { g_nn_lds_nodes.store(hit->nn_lds_nodes); g_nn_stack_depth.store(hit->nn_stack_depth); }
     } else
         PR_TRY(enqueue_all(/*host_checks=*/true));
     HIP_TRY(hipStreamSynchronize(g->stream));

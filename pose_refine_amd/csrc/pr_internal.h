@@ -126,6 +126,7 @@ struct SceneNNDev {
     // instrumented runs (option "nn_count"): per ICP pass (IcpBatch::iter) a row of eight 64-bit counters, the columns of enum NNCounter
     // (nn_search.hip): kCntQueries, kCntWindow, kCntTree, kCntDescents, kCntNodes, kCntLeaves, kCntLeafPoints, kCntCells; else null
     unsigned long long *counters;
+    uint32_t topo_nodes;        // host side only: lds_nodes of a stackless launch over this scene (option nn_lds_nodes), whatever walk stack_depth selects
 };
 // kd-tree scene after the search kernel has run: the correspondence pass only gathers the winners (no search, no transform)
 struct SceneNNWinners {
@@ -367,7 +368,16 @@ size_t icp_loop_cu_lds_bytes(uint32_t nblk);
 constexpr size_t kLoopCuLdsTotal = 160u << 10;
 uint32_t icp_loop_cu_lds_blocks(uint32_t nblk, uint32_t steps, int cap);
 hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s, uint32_t *lds_blocks_used = nullptr);
-hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s);
+// The in-pass kd-tree walks stage sc.lds_nodes leading nodes in dynamic LDS beside icp_pass_kernel's kPassStaticLds static bytes.  The stack
+// walks stay within 64 KiB by nn_route's cap.  The stackless walks (plain and robust) may ask for up to kNNLdsNodesMax 16-byte entries:
+// beyond kNNLdsNodesPlain the launcher opts the kernel in per device, and where the device refuses it stages kNNLdsNodesPlain and runs.
+// *ran receives what was launched: the staged count (0 for compact records: nothing is staged beside their stacks) and the stack entries
+// per lane (0 = stackless).
+constexpr uint32_t kPassStaticLds = 4 * kAccStride * (uint32_t)sizeof(float);                 // wsum
+constexpr uint32_t kNNLdsNodesMax = 8192;                                                     // 128 KiB
+constexpr uint32_t kNNLdsNodesPlain = ((64u << 10) - kPassStaticLds) / 16u;                   // 4064: static + dynamic <= 64 KiB, no opt-in
+struct NNPassRan { uint32_t lds_nodes, stack_depth; };
+hipError_t launch_icp_pass_nn(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, hipStream_t s, NNPassRan *ran = nullptr);
 // split form of the kd-tree pass: search (pending transform applied, winners written to b.nn_prev) + gather/accumulate pass
 // marks (or null): three events recorded after the search, the bound and the walk kernel (timed batches; n_poses <= 32768)
 hipError_t launch_nn_search(const IcpBatch &b, const SceneNNDev &sc, uint32_t n_poses, uint32_t max_points, uint32_t run, hipStream_t s, hipEvent_t *marks = nullptr);

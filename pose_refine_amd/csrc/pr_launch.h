@@ -9,11 +9,14 @@ namespace prk {
 // device, so that a process driving several GPUs (one host thread each) opts in on every one of them.
 static bool lds_opt_in(const void *fn, int slot, uint32_t bytes)
 {
-    static std::atomic<uint64_t> done[4];                         // bit = device ordinal (<= 64 devices), one word per kernel slot
+    static std::atomic<uint64_t> done[8];                         // bit = device ordinal (<= 64 devices), one word per kernel slot
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
     if (done[slot].load(std::memory_order_acquire) & (1ull << dev)) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        (void)hipGetLastError();                                 // a refusal is the caller's to handle (a smaller launch): it must not surface as that launch's error
+        return false;
+    }
     done[slot].fetch_or(1ull << dev, std::memory_order_release);
     return true;
 }

@@ -126,7 +126,12 @@ extern std::atomic<uint64_t> g_tight_batches;     // asynchronous batches whose 
 extern std::atomic<uint64_t> g_band_batches;      // asynchronous batches whose depth boxes were banded (option box_bands; read-only option "stat_band_batches": tests tell the banded path from the row-major one by it)
 extern std::atomic<uint64_t> g_resident_batches;  // asynchronous sub-batches whose whole loop ran as one launch (option resident_loop; read-only option "stat_resident_batches": tests tell the resident route from the multi-launch one by it)
 extern std::atomic<uint32_t> g_loop_lds_blocks;   // blocks of every cloud's head that the most recent resident launch kept in LDS (option loop_lds_blocks; read-only option "stat_loop_lds_blocks": tests tell a launch with an LDS image from one that quietly ran without)
-extern std::atomic<uint64_t> g_flag_overtook;    // PR_SOLVE_HOST: group flags that reached the host before all of their rows (process-wide; expected 0; read-only option "stat_flag_overtook")
+// what the most recent in-pass kd-tree launch (launch_icp_pass_nn: enqueued, or replayed in a cached graph) ran with, after nn_route and the launcher's own limits:
+// nodes staged in LDS and stack entries per lane, 0 = the stackless walk (read-only options "stat_nn_lds_nodes", "stat_nn_stack_depth": tests tell a walk that
+// read staged nodes from one that quietly staged none, or took another route); g_nn_pass_launches counts those launches (a captured graph notes whether it holds one)
+extern std::atomic<uint32_t> g_nn_lds_nodes, g_nn_stack_depth;
+extern std::atomic<uint64_t> g_nn_pass_launches;
+extern std::atomic<uint64_t> g_flag_overtook;   // PR_SOLVE_HOST: group flags that reached the host before all of their rows (process-wide; expected 0; read-only option "stat_flag_overtook")
 
 // ---- process-wide options (pr_set_option): plain ints, shared by every context ---------------------
 constexpr int kSlots = PR_SLOTS;            // asynchronous slots per context (pr_tuning.h)
@@ -138,8 +143,8 @@ struct Options {
     int steps = 3;                   // 1024-point steps per workgroup -> 3072 points per workgroup (round 3: 3-5 % faster than 2048 / 4096).  Round 6, with the write-back issued behind the gathers, option points_per_block = 4096 pipelines 2 % better (286.5 / 287.3 k against 280.6 / 281.4 k, 100 steps, same box; 273.6 against 271.6 k at 20 steps; 5120: 282 k, 6144: 277 k, 8192: 242-262 k; kd-tree and host solve within noise) but a LONE 256-hypothesis launch takes 39.6 instead of 37.7 us (six longer chains per hypothesis instead of eight): the default stays, the option is there (it selects another summation tree: a quarter of the bench's hypotheses end in a different basin, the oracle follows)
     int profile = 0;
     int sample_period = 32;          // profile 2: one timed (synchronous, single-group) call in this many
-    int nn_lds_nodes = 1024;
-    int nn_lds_records = 0;          // stack traversal: leading 64-byte node records staged in LDS; measured 0/64/128/256/512 -> 42.2/41.6/45.2/45.4/58.2 ms per step (occupancy lost to the extra LDS outweighs the saved L1 lookups)
+    int nn_lds_nodes = 1024;         // stackless walk in the pass: leading 16-byte topology entries staged in LDS (<= tree, <= 8192; beyond 4064 by the per-device opt-in of launch_icp_pass_nn)
+    int nn_lds_records = 0;          // stack traversal: leading 64-byte node records staged in LDS; measured 0/64/128/256/512 -> 42.2/41.6/45.2/45.4/58.2 ms per step (occupancy lost to the extra LDS outweighs the saved L1 lookups).  Capped at 504 / 248 records beside 16- / 24-entry stacks (nn_route); tests/test_nn_lds_gpu.py runs 0, 1, 64, 127, 247-249, 255-257, 503-505 and 511-513
     int nn_seed = 1;                 // compact kd records: start every search from the previous pass' winner distance
     int nn_compact = 1;              // stack traversal: 32-byte node records with 16-bit outward-rounded child boxes (half the L1 traffic)
     int blocking_wait = 0;           // pr_refine_wait sleeps on the slot's event instead of spinning (set before the first asynchronous batch)
@@ -680,13 +685,15 @@ inline NNSetPick pick_nn_set(const NNSetFacts *f, int n)
 }
 // How a set's records are searched, from its control words and the options nn_lds_nodes, nn_lds_records, nn_stack, nn_compact, nn_wide.
 // Pending far children on the stack never exceed the tree depth; deeper trees use the stackless walk.  The caller has refused an inconsistent tree (depth >= 0x7fffffff).
-struct NNRoute { uint32_t lds_nodes, stack_depth; bool compact, wide; };   // compact: the 32-byte records (SceneNNDev::rec32); wide: the wide records as well
+// topo_nodes: what a stackless walk of this set stages whatever the route says -- a robust pass without compact records walks stackless beside any stack_depth.
+struct NNRoute { uint32_t lds_nodes, stack_depth; bool compact, wide; uint32_t topo_nodes; };   // compact: the 32-byte records (SceneNNDev::rec32); wide: the wide records as well
 inline NNRoute nn_route(const prk::NNInfo &info, uint32_t n_nodes, int nn_lds_nodes, int nn_lds_records, int nn_stack, int nn_compact, int nn_wide)
 {
     NNRoute r{};
-    r.lds_nodes = std::min<uint32_t>(std::min((uint32_t)std::max(0, nn_lds_nodes), n_nodes), 8192);      // <= 128 KiB of LDS
+    r.lds_nodes = r.topo_nodes = std::min<uint32_t>(std::min((uint32_t)std::max(0, nn_lds_nodes), n_nodes), prk::kNNLdsNodesMax);      // <= 128 KiB of LDS (beyond 64 KiB: launch_icp_pass_nn opts in)
     if (nn_stack) r.stack_depth = (info.depth <= 16) ? 16u : ((info.depth <= 24) ? 24u : 0u);
-    if (r.stack_depth) r.lds_nodes = std::min<uint32_t>({ (uint32_t)std::max(0, nn_lds_records), n_nodes, (65536u - r.stack_depth * 2048u) / 64u });   // stacks + records <= 64 KiB
+    // stacks + records + the pass kernel's static LDS <= 64 KiB: 504 records beside 16 entries, 248 beside 24 (no opt-in on this route)
+    if (r.stack_depth) r.lds_nodes = std::min<uint32_t>({ (uint32_t)std::max(0, nn_lds_records), n_nodes, (65536u - prk::kPassStaticLds - r.stack_depth * 2048u) / 64u });
     r.compact = r.stack_depth && nn_compact && info.rec32_valid == 1u;
     r.wide = r.compact && nn_wide && info.wide_state == prk::kWideValid && info.n_wide > 0u;
     return r;
@@ -766,6 +773,7 @@ struct GraphKey {                    // every value a captured launch depends on
 struct CachedGraph {
     GraphKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
     uint64_t stamp = 0;
+    bool nn_pass = false; uint32_t nn_lds_nodes = 0, nn_stack_depth = 0;     // an in-pass kd-tree launch was captured: what it ran with (a replay reports it again)
 };
 inline void destroy_graph(CachedGraph &c)
 {

@@ -135,7 +135,7 @@ static prk::SceneNNDev nn_dev(const NNDerived &nc, const pr_scene_nn &s, const N
     d.max_dist_diff = s.max_dist_diff;
     d.topo = nc.topo.as<int4>(); d.bmin = nc.bmin.as<float4>(); d.bmax = nc.bmax.as<float4>(); d.pts = nc.pts.as<float4>();
     d.pcd = s.pcd; d.normal = s.normal; d.n_nodes = s.n_nodes;
-    d.lds_nodes = route.lds_nodes; d.rec = nc.nnrec.as<float4>(); d.stack_depth = route.stack_depth; d.desc = nc.nndesc.as<uint2>();
+    d.lds_nodes = route.lds_nodes; d.topo_nodes = route.topo_nodes; d.rec = nc.nnrec.as<float4>(); d.stack_depth = route.stack_depth; d.desc = nc.nndesc.as<uint2>();
     if (route.compact) {
         d.rec32 = nc.nnrec32.as<uint4>();
         std::memcpy(d.qmin, nc.info.qmin, sizeof d.qmin); std::memcpy(d.qscale, nc.info.qscale, sizeof d.qscale);

@@ -58,6 +58,22 @@ class BruteForce:
         return np.array([len(t) for t in self.ties])
 
 
+def inside_count(queries, pts, max_dist, stride=16, chunk_elems=1 << 22):
+    """How many queries have a scene point at squared distance < max_dist^2 in the reference's float32 arithmetic: BruteForce(...).inside.sum()
+    without the minimum.  A query is inside as soon as ANY point is, so every stride-th point settles most queries and all points the rest."""
+    q = np.ascontiguousarray(queries, F32).reshape(-1, 3)
+    pts = np.ascontiguousarray(pts, F32).reshape(-1, 3)
+    accept = F32(max_dist) * F32(max_dist)
+    inside = np.zeros(len(q), bool)
+    for cand in (pts[::stride], pts):
+        todo = np.flatnonzero(~inside)
+        step = max(1, chunk_elems // max(1, len(cand)))
+        for a in range(0, len(todo), step):
+            sel = todo[a:a + step]
+            inside[sel] = (sq_dist(q[sel], cand) < accept).any(1)
+    return int(inside.sum())
+
+
 def gap_ulps(bf):
     """Runner-up gap of every query in ulps of its minimum (0 for an exact tie)."""
     with np.errstate(over="ignore", invalid="ignore"):
@@ -151,9 +167,10 @@ class Family:
     """A scene with the clouds to query it with.  Depth families: `depth` (int32 or uint16) + `K`, scene made from the image; the fused
     families also carry `tris` + `poses` (+ `K_fused`, the hypotheses' camera).  Point families (no camera): `pts`, `nrm`."""
 
-    def __init__(self, name, clouds, max_dist=0.1, depth=None, K=None, pts=None, nrm=None, tris=None, poses=None, K_fused=None, max_leaf=10):
+    def __init__(self, name, clouds, max_dist=0.1, depth=None, K=None, pts=None, nrm=None, tris=None, poses=None, K_fused=None, max_leaf=10, nodes=None):
         self.name, self.clouds, self.max_dist, self.depth, self.K = name, clouds, max_dist, depth, K
         self.pts, self.nrm, self.tris, self.poses, self.K_fused, self.max_leaf = pts, nrm, tris, poses, K_fused, max_leaf
+        self.nodes = nodes                                          # a hand-made tree over `pts` in their stored order (the vine), else built
         if depth is not None:
             self.H, self.W = depth.shape
 
@@ -167,7 +184,7 @@ class Family:
     def oracle_scene(self):
         if self.depth is not None:
             return O.NNScene(self.depth, self.K, self.max_dist, self.max_leaf)
-        return O.NNScene.from_points(self.pts, self.nrm, self.max_dist, self.max_leaf)
+        return O.NNScene.from_points(self.pts, self.nrm, self.max_dist, self.max_leaf, nodes=self.nodes)
 
 
 def render_clouds(tris, poses, K, W, H):
@@ -310,6 +327,97 @@ def degenerate(kind):
 
 
 DEGENERATE = ("coplanar", "collinear", "repeated", "far40", "far60")
+
+
+VINE_LEAVES, VINE_TIE_LEVELS = 64, (4, 11, 30)
+
+
+def tree_depth(nodes):
+    """Longest root-to-node path, following the child links from node 0 (every node must be reached exactly once, through its own parent)."""
+    depth = np.full(len(nodes), -1, np.int64)
+    depth[0] = 0
+    todo = [0]
+    while todo:
+        i = todo.pop()
+        for c in (int(nodes[i]["child1"]), int(nodes[i]["child2"])):
+            if c >= 0:
+                assert depth[c] < 0 and int(nodes[c]["parent"]) == i, (i, c)
+                depth[c] = depth[i] + 1
+                todo.append(c)
+    assert (depth >= 0).all()
+    return int(depth.max())
+
+
+def vine():
+    """A hand-made tree deeper than any stack: 64 leaves of 1 to 10 points, every internal node splits ONE leaf off the rest along a cycling
+    dimension, on either side (127 nodes, 63 levels of internal nodes above the last pair of leaves).  Nodes are numbered as the builder numbers
+    them (children side by side, behind their parent; child1 below the plane), a node's points are [left, right), internal boxes are the tight
+    boxes of their points, split = (left_max + right_min) / 2 in float32.  At VINE_TIE_LEVELS the leaf's largest and the rest's smallest
+    coordinate are the same float (points ON the plane, on both sides); leaf 0 holds one point twice.  All box corners are multiples of 2^-10."""
+    rng = np.random.default_rng(81)
+    sizes = rng.integers(1, 11, VINE_LEAVES)
+    sizes[[0, 5, 12, 31]] = (10, 7, 6, 8)                          # (the duplicate's leaf and the leaves behind a tie level hold several points)
+    sizes[[1, 62]] = (1, 10)
+    below = rng.integers(0, 2, VINE_LEAVES - 1).astype(bool)       # the leaf is child1 (below the plane) / child2
+    unit = 1.0 / 1024.0
+    slab, gap = 8 * unit, 2 * unit
+    lo, hi = np.array([-0.25, -0.25, 0.25]), np.array([0.25, 0.25, 0.75])
+    n = int(sizes.sum())
+    pts = np.zeros((n, 3), F32)
+    nodes = np.zeros(2 * VINE_LEAVES - 1, O.KDNODE)
+    nodes["parent"] = nodes["child1"] = nodes["child2"] = -1
+    L, R, cur, count, pending = 0, n, 0, 1, None
+    for k in range(VINE_LEAVES):
+        last = k == VINE_LEAVES - 1
+        m, d = int(sizes[k]), k % 3
+        blo, bhi = lo.copy(), hi.copy()
+        if not last:
+            if below[k]:
+                bhi[d] = lo[d] + slab
+            else:
+                blo[d] = hi[d] - slab
+        p = rng.uniform(blo, bhi, size=(m, 3)).astype(F32)
+        L0, R0 = L, R
+        if pending is not None:                                      # the level above was a tie level: one point of the rest lies on its plane
+            p[0, pending[0]] = pending[1]
+            pending = None
+        if last:
+            a, b, leaf = L, R, cur
+            assert b - a == m
+        else:
+            tie = k in VINE_TIE_LEVELS
+            if below[k]:
+                lo[d] = bhi[d] + (0.0 if tie else gap)
+                plane = F32(bhi[d])
+                a, b = L, L + m; L += m
+            else:
+                hi[d] = blo[d] - (0.0 if tie else gap)
+                plane = F32(blo[d])
+                a, b = R - m, R; R -= m
+            if tie:
+                p[-1, d] = plane
+                pending = (d, plane)
+            c1, c2 = count, count + 1
+            count += 2
+            leaf, nxt = (c1, c2) if below[k] else (c2, c1)
+            nodes[cur]["child1"], nodes[cur]["child2"], nodes[cur]["split_dim"] = c1, c2, d
+            nodes[cur]["left"], nodes[cur]["right"] = L0, R0
+            nodes[c1]["parent"] = nodes[c2]["parent"] = cur
+            cur = nxt
+        pts[a:b] = p
+        nodes[leaf]["left"], nodes[leaf]["right"] = a, b
+    first = 0 if below[0] else n - int(sizes[0])                     # the duplicate pair, in leaf 0 (ten points)
+    pts[first + 1] = pts[first]
+    for i in range(len(nodes) - 1, -1, -1):                          # boxes and split values from the points: children before parents
+        q = pts[nodes[i]["left"]:nodes[i]["right"]]
+        nodes[i]["bbox"] = np.stack([q.min(0), q.max(0)], 1).reshape(-1)
+        if nodes[i]["child1"] >= 0:
+            d = int(nodes[i]["split_dim"])
+            left_max = nodes[nodes[i]["child1"]]["bbox"][2 * d + 1]
+            right_min = nodes[nodes[i]["child2"]]["bbox"][2 * d]
+            nodes[i]["split_v"] = (F32(left_max) + F32(right_min)) / F32(2.0)
+    pts = np.ascontiguousarray(pts)
+    return Family("vine", _near_clouds(pts, rng, 0.004), pts=pts, nrm=_normals(rng, n), nodes=nodes)
 
 
 def wide_frame_ok(nodes, max_dist):

@@ -125,3 +125,62 @@ def test_far_scenes_straddle_the_wide_frame_test():
     got = {k: R.wide_frame_ok(R.degenerate(k).oracle_scene().nodes, 0.1) for k in ("far40", "far60")}
     assert got == {"far40": True, "far60": False}
     assert R.wide_frame_ok(R.degenerate("coplanar").oracle_scene().nodes, 0.1)
+
+
+def test_vine_is_a_consistent_tree_deeper_than_any_stack():
+    """The hand-made vine: 127 nodes over 64 leaves of 1 to 10 points; links, point ranges and boxes agree; left_max <= split <= right_min at
+    every internal node, with equality at the tie levels; one point is held twice; its depth, from the links, is beyond the 24-entry stacks."""
+    fam = R.vine()
+    nodes, pts = fam.nodes, fam.pts
+    assert len(nodes) == 2 * R.VINE_LEAVES - 1 == 127 and R.tree_depth(nodes) == R.VINE_LEAVES - 1 > 24
+    leaf = nodes["child1"] < 0
+    assert leaf.sum() == R.VINE_LEAVES and np.array_equal(leaf, nodes["child2"] < 0)
+    sizes = (nodes["right"] - nodes["left"])[leaf]
+    assert sizes.min() == 1 and sizes.max() == 10 and sizes.sum() == len(pts) == nodes[0]["right"] and nodes[0]["left"] == 0 and nodes[0]["parent"] == -1
+    covered = np.zeros(len(pts), np.int64)
+    for nd in nodes[leaf]:
+        covered[nd["left"]:nd["right"]] += 1
+    assert (covered == 1).all()                                     # the leaves tile the point array
+    ties = 0
+    for i, nd in enumerate(nodes):
+        q = pts[nd["left"]:nd["right"]]
+        assert np.array_equal(nd["bbox"], np.stack([q.min(0), q.max(0)], 1).reshape(-1)), i
+        if leaf[i]:
+            continue
+        a, b, d = nodes[nd["child1"]], nodes[nd["child2"]], int(nd["split_dim"])
+        assert nd["child2"] == nd["child1"] + 1 > i and a["parent"] == b["parent"] == i
+        assert (a["left"], a["right"], b["right"]) == (nd["left"], b["left"], nd["right"]) and a["left"] < a["right"] < b["right"]
+        assert leaf[nd["child1"]] or leaf[nd["child2"]]            # one leaf is split off per level
+        left_max, right_min = pts[a["left"]:a["right"], d].max(), pts[b["left"]:b["right"], d].min()
+        assert left_max <= nd["split_v"] <= right_min, (i, left_max, nd["split_v"], right_min)
+        ties += int(left_max == right_min)
+    assert ties == len(R.VINE_TIE_LEVELS)
+    assert len(np.unique(pts, axis=0)) == len(pts) - 1              # the duplicate pair
+
+
+def test_vine_walk_equals_brute_force():
+    """The oracle's stackless walk over the vine returns brute force's distance, a point of its tie set and the same acceptance, on the
+    vine's 2000 queries and on the scene points themselves (distance 0: the duplicate pair ties)."""
+    fam = R.vine()
+    oscene = fam.oracle_scene()
+    assert oscene.nodes.tobytes() == fam.nodes.tobytes() and oscene.pcd.tobytes() == fam.pts.tobytes()
+    q = fam.clouds[0]
+    assert len(q) == 2000
+    bf = R.BruteForce(q, oscene.pcd, fam.max_dist)
+    assert R.check_oracle_against_brute_force(oscene, q, bf) == len(q) > 0
+    assert bf.inside.mean() >= 0.5
+    own = R.BruteForce(fam.pts, oscene.pcd, fam.max_dist)
+    assert R.check_oracle_against_brute_force(oscene, fam.pts, own) == len(fam.pts)
+    assert (own.d2 == 0).all() and (own.n_ties() > 1).sum() == 2
+
+
+@pytest.mark.parametrize("max_dist", [0.1, 0.003])
+def test_inside_count_is_brute_forces_count(max_dist):
+    """R.inside_count (the strided shortcut the GPU tests count first-pass inliers with) equals BruteForce's count, with every query inside
+    and with queries on both sides of the radius."""
+    fam = R.degenerate("coplanar")
+    q = fam.clouds[0]
+    bf = R.BruteForce(q, fam.pts, max_dist)
+    assert R.inside_count(q, fam.pts, max_dist) == int(bf.inside.sum())
+    if max_dist < 0.01:
+        assert 50 < bf.inside.sum() < len(q) - 50

@@ -584,10 +584,17 @@ int main()
         CHECK(is(nn_route(info_of(30), 8191, 20000, 0, 1, 1, 1), 8191, 0, false, false) && is(nn_route(info_of(30), 8193, 20000, 0, 1, 1, 1), 8192, 0, false, false));
         CHECK(is(nn_route(info_of(30), 50000, 2147483647, 0, 1, 1, 1), 8192, 0, false, false) && is(nn_route(info_of(30), 50000, -5, 7, 1, 1, 1), 0, 0, false, false));
         CHECK(is(nn_route(info_of(30), 50000, -2147483647 - 1, 7, 0, 1, 1), 0, 0, false, false));
-        // stack: nn_lds_records, at most the tree, at most what the stacks leave of 64 KiB -- 512 records beside 16 entries, 256 beside 24
+        // stack: nn_lds_records, at most the tree, at most what the stacks and the pass kernel's 512 static bytes leave of 64 KiB -- 504 records beside 16 entries, 248 beside 24
         CHECK(is(nn_route(info_of(16), 5000, 1024, 64, 1, 1, 1), 64, 16, true, true) && is(nn_route(info_of(16), 5000, 1024, -1, 1, 1, 1), 0, 16, true, true));
-        CHECK(is(nn_route(info_of(16), 511, 1024, 100000, 1, 1, 1), 511, 16, true, true) && is(nn_route(info_of(16), 513, 1024, 100000, 1, 1, 1), 512, 16, true, true));
-        CHECK(is(nn_route(info_of(24), 255, 1024, 100000, 1, 1, 1), 255, 24, true, true) && is(nn_route(info_of(24), 257, 1024, 2147483647, 1, 1, 1), 256, 24, true, true));
+        CHECK(is(nn_route(info_of(16), 503, 1024, 100000, 1, 1, 1), 503, 16, true, true) && is(nn_route(info_of(16), 505, 1024, 100000, 1, 1, 1), 504, 16, true, true));
+        CHECK(is(nn_route(info_of(16), 5000, 1024, 503, 1, 1, 1), 503, 16, true, true) && is(nn_route(info_of(16), 5000, 1024, 512, 1, 1, 1), 504, 16, true, true));
+        CHECK(is(nn_route(info_of(24), 247, 1024, 100000, 1, 1, 1), 247, 24, true, true) && is(nn_route(info_of(24), 249, 1024, 2147483647, 1, 1, 1), 248, 24, true, true));
+        CHECK(is(nn_route(info_of(24), 5000, 1024, 256, 1, 1, 1), 248, 24, true, true));
+        CHECK(16u * 2048u + 504u * 64u + prk::kPassStaticLds == 65536u && 24u * 2048u + 248u * 64u + prk::kPassStaticLds == 65536u);
+        // topo_nodes: the stackless count beside any route (the robust pass of a scene without compact records), and what needs no opt-in
+        CHECK(nn_route(info_of(16), 5000, 1024, 64, 1, 1, 1).topo_nodes == 1024 && nn_route(info_of(16), 20000, 9000, 64, 1, 0, 1).topo_nodes == 8192 && nn_route(info_of(30), 700, 1024, 64, 1, 1, 1).topo_nodes == 700);
+        CHECK(nn_route(info_of(24), 5000, -3, 64, 1, 1, 1).topo_nodes == 0 && nn_route(info_of(30), 50000, 8191, 0, 1, 1, 1).topo_nodes == 8191);
+        CHECK(prk::kNNLdsNodesPlain == 4064u && prk::kNNLdsNodesPlain * 16u + prk::kPassStaticLds == 65536u && prk::kNNLdsNodesMax == 8192u);
         CHECK(is(nn_route(info_of(24), 1, 0, 100000, 1, 1, 1), 1, 24, true, true));
     }
     std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");

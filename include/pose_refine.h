@@ -1278,6 +1278,73 @@ int  pr_depth_filter_dev(const void *depth_in_dev, int depth_is_i32, size_t widt
 int  pr_depth_filter_host(const void *depth_in, int depth_is_i32, size_t width, size_t height, const pr_depth_filter_params *params,
                           void *depth_out, uint8_t *flags_out /* may be NULL */, pr_depth_filter_counts *counts_out /* may be NULL */);
 
+/* ---- scenes from point clouds: exact k nearest neighbours over the scene's own kd-tree, and a PCA normal per point -------------------------
+ * Every other preparation starts from a depth frame; a sensor that delivers points (a scanner, a LiDAR, a merged or cropped cloud) has no pixel
+ * grid for pr_get_normal's stencil.  These entries make the one missing array -- a normal per scene point -- from the points and the tree alone,
+ * after which the scene is a pr_scene_nn with cam_magic = 0 like any other.  No counterpart in the reference.
+ *
+ * Neighbours of scene point i.  The scene is n >= 1 points in tree order; points must be finite (the entries do not check).  All float32
+ * arithmetic is without contraction.
+ *   candidates:   every j in [0, n), i itself included
+ *   d2(i, j)    = ((dx*dx + dy*dy) + dz*dz) with dx = p_j.x - p_i.x, dy and dz likewise: the search's own expression and order (pcd_scene.h:88-91)
+ *   admissible:   d2 <= r2, where r2 = max_radius * max_radius is computed ONCE in float32 by pr_cloud_describe (max_radius = INFINITY: no limit)
+ *   the list:     the m_i = min(k, number admissible) smallest keys (d2, j), compared lexicographically, in ascending order -- a tie in distance
+ *                 goes to the lower index, so the result does not depend on the order in which the tree is visited.  1 <= k <= PR_KNN_MAX_K.
+ *   outputs:      idx[i*k + t] = the t-th neighbour, PR_KNN_NONE for t >= m_i;  d2[i*k + t] = its d2, 0.0f for an unused slot;  count[i] = m_i
+ * The search is the ordered stackless walk of Scene_nn::query with `best` replaced by the current bound: r2 until the list holds k entries, then the
+ * k-th d2; a far child is entered iff the distance to its box is <= the bound (<=, not <: an equal distance with a lower index still displaces).
+ * The box distance adds its x, y, z terms in d2's order, which is what keeps it a lower bound of the float32 d2.
+ *
+ * Normal of point i, from its list.  float64 throughout, in list order, every product formed and then added (no contraction):
+ *   c     = (sum over t of (double)p_jt) / m_i, per component
+ *   S     = the six sums of (p_jt - c)(p_jt - c)^T: xx, xy, xz, yy, yz, zz (not divided by m_i)
+ *   eigen:  the cyclic Jacobi of pr_plane_from_moments on S (V = I, PR_PLANE_MAX_SWEEPS, the 2^-56 stop), statement for statement
+ *   lo    = the index of the smallest diagonal entry (the lowest index on a tie), mid = the same rule over the two that remain, hi = the last
+ *   n     = column lo of V, negated iff ((n.x*v.x + n.y*v.y) + n.z*v.z) < 0 with v = (double)viewpoint - (double)p_i; each component rounded to
+ *           float32 once
+ * The point gets the normal (0, 0, 0) -- this library's "no normal" everywhere -- when m_i < min_neighbours (min_neighbours >= 3), or when
+ * lambda_mid <= line_ratio * lambda_hi: the neighbours coincide or lie on a line (an all-zero S is that case too).  0 <= line_ratio < 1.
+ * variation[i] (optional) = (float)(lambda_lo / ((lambda_lo + lambda_mid) + lambda_hi)), the surface variation; 0 where there is no normal.
+ * pr_cloud_counts: the points, those with a normal, those with too few neighbours, the degenerate ones (the last three add up to the first).
+ *
+ * pr_cloud_describe: host only; PR_ERR_INVALID for k outside 1 .. PR_KNN_MAX_K, a max_radius that is NaN or not positive, min_neighbours < 3, a
+ * line_ratio outside [0, 1) or a viewpoint that is not finite.
+ * pr_cloud_knn_dev: over any built kd-tree scene (scene->normal is not read); d2_dev and count_dev may be NULL.  One lane per
+ * scene point; its list lives in LDS as [entry][lane].
+ * pr_cloud_normals_dev: the same walk with the normal formed in the same kernel from the list in LDS.  normal_dev_out may be the scene's own
+ * normal array (the kernel reads points and tree only); the write is announced like every write through this library, so no cached form of a
+ * scene that holds those normals survives it.  variation_dev_out and counts_out may be NULL.
+ * pr_scene_nn_from_cloud_dev: pr_kdtree_build_dev on the points (reordered in place), then the normals in tree order; the caller fills a
+ * pr_scene_nn with cam_magic = 0 from the three buffers.  nodes_dev_out: cap_nodes entries (2 n + 1 always suffice).
+ * pr_cloud_knn_host / pr_cloud_normals_host: the same source on host points and a host pr_kdnode array (pr_kdtree_build), byte for byte.
+ * pr_ppf_cloud_points_dev: the scene sample of the PPF vote from a kd-tree scene -- the points 0, stride, 2 stride, ... of tree order whose
+ * normal has a non-zero component, in index order, point = pcd * 1000.0f per component, normal as it is.  Room for PR_PPF_MAX_SCENE_POINTS;
+ * more than that: PR_ERR_INVALID with nothing emitted and *n_out = the number found (raise the stride).  stride >= 1.
+ * Not offered: voxel down-sampling or merging of clouds, transforms between sensor frames, radius-only (unbounded k) neighbourhoods. */
+#define PR_KNN_MAX_K  32
+#define PR_KNN_NONE   0xFFFFFFFFu
+typedef struct {
+    uint32_t k;                /* 1 .. PR_KNN_MAX_K                                                                                   */
+    uint32_t min_neighbours;   /* >= 3: fewer admissible neighbours give no normal                                                    */
+    float    max_radius;       /* metres (the scene's unit), > 0; INFINITY: no limit                                                  */
+    float    r2;               /* max_radius * max_radius in float32, computed once by pr_cloud_describe                              */
+    float    line_ratio;       /* [0, 1): lambda_mid <= line_ratio * lambda_hi gives no normal                                        */
+    float    viewpoint[3];     /* normals face it                                                                                     */
+} pr_cloud_params;             /* 32 B */
+typedef struct { uint32_t points, with_normal, too_few, degenerate; } pr_cloud_counts;      /* 16 B */
+int  pr_cloud_describe(uint32_t k, float max_radius, uint32_t min_neighbours, float line_ratio, const float viewpoint[3], pr_cloud_params *out);
+int  pr_cloud_knn_dev(const pr_scene_nn *scene, const pr_cloud_params *params, uint32_t *idx_dev, float *d2_dev /* may be NULL */,
+                      uint32_t *count_dev /* may be NULL */);
+int  pr_cloud_normals_dev(const pr_scene_nn *scene, const pr_cloud_params *params, pr_vec3 *normal_dev_out, float *variation_dev_out /* may be NULL */,
+                          pr_cloud_counts *counts_out /* may be NULL */);
+int  pr_scene_nn_from_cloud_dev(pr_vec3 *pcd_dev, size_t n_points, int max_leaf, const pr_cloud_params *params, pr_vec3 *normal_dev_out,
+                                pr_kdnode *nodes_dev_out, size_t cap_nodes, uint32_t *n_nodes, pr_cloud_counts *counts_out /* may be NULL */);
+int  pr_cloud_knn_host(const pr_vec3 *pcd, size_t n_points, const pr_kdnode *nodes, size_t n_nodes, const pr_cloud_params *params, uint32_t *idx_out,
+                       float *d2_out /* may be NULL */, uint32_t *count_out /* may be NULL */);
+int  pr_cloud_normals_host(const pr_vec3 *pcd, size_t n_points, const pr_kdnode *nodes, size_t n_nodes, const pr_cloud_params *params,
+                           pr_vec3 *normal_out, float *variation_out /* may be NULL */, pr_cloud_counts *counts_out /* may be NULL */);
+int  pr_ppf_cloud_points_dev(const pr_scene_nn *scene, uint32_t stride, pr_vec3 *points_dev_out, pr_vec3 *normals_dev_out, uint32_t *n_out);
+
 /* ---- sharding of a hypothesis batch over ranks (contiguous blocks) ---------------- */
 void pr_shard_range(uint32_t n_items, uint32_t rank, uint32_t world, uint32_t *first, uint32_t *count);
 

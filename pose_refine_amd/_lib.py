@@ -175,6 +175,24 @@ class DepthFilterCounts(C.Structure):
 assert C.sizeof(DepthFilterParamsDesc) == 32 and C.sizeof(DepthFilterCounts) == 32
 
 
+# pr_cloud_params: what pr_cloud_describe fills; pr_cloud_counts: the points of a pr_cloud_normals_* call per outcome
+KNN_MAX_K, KNN_NONE = 32, 0xFFFFFFFF                                        # PR_KNN_MAX_K, PR_KNN_NONE
+
+
+class CloudParamsDesc(C.Structure):
+    """pr_cloud_params: the neighbourhood (k, max_radius and its square), when a point gets no normal, and the viewpoint normals face (pr_cloud_describe checks and fills it)."""
+    _fields_ = [("k", C.c_uint32), ("min_neighbours", C.c_uint32), ("max_radius", C.c_float), ("r2", C.c_float), ("line_ratio", C.c_float),
+                ("viewpoint", C.c_float * 3)]
+
+
+class CloudCounts(C.Structure):
+    """pr_cloud_counts: the points, those with a normal, those with too few neighbours, the degenerate ones."""
+    _fields_ = [("points", C.c_uint32), ("with_normal", C.c_uint32), ("too_few", C.c_uint32), ("degenerate", C.c_uint32)]
+
+
+assert C.sizeof(CloudParamsDesc) == 32 and C.sizeof(CloudCounts) == 16
+
+
 class MeshRef(C.Structure):
     """pr_mesh_ref: one mesh of a mixed batch (pr_*_multi)."""
     _fields_ = [("tris_dev", C.c_void_p), ("n_tris", C.c_size_t)]
@@ -328,6 +346,13 @@ SIGNATURES = {
     "pr_depth_fuse_host": (_i32, [_vp, _u32, _i32, _sz, _u32, _vp, _vp]),
     "pr_depth_filter_dev": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp]),
     "pr_depth_filter_host": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "pr_cloud_describe": (_i32, [_u32, C.c_float, _u32, C.c_float, _vp, _vp]),
+    "pr_cloud_knn_dev": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "pr_cloud_normals_dev": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "pr_scene_nn_from_cloud_dev": (_i32, [_vp, _sz, _i32, _vp, _vp, _vp, _sz, C.POINTER(_u32), _vp]),
+    "pr_cloud_knn_host": (_i32, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "pr_cloud_normals_host": (_i32, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "pr_ppf_cloud_points_dev": (_i32, [_vp, _u32, _vp, _vp, C.POINTER(_u32)]),
     "pr_pose_vsd": (_i32, [_vp, _sz, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_pose_vsd_multi": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp, C.c_float, _vp, _u32, _vp]),
     "pr_render_span": (_i32, [_vp, _sz, _vp, _sz, _sz, _sz, _vp, Roi, _vp, _vp]),

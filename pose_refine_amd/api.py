@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (COMM_ID_BYTES, DEPTH_FILLED, DEPTH_FILTER_MAX_RADIUS, DEPTH_FLYING, DEPTH_FUSE_MAX, DEPTH_GATED, DEPTH_KEPT, DEPTH_SMOOTHED, DEPTH_UNMEASURED, DepthFilterCounts, DepthFilterParamsDesc, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SEGMENT, SEGMENT_DROPPED, SEGMENT_MAX, SEGMENT_MAX_ROOTS, SegmentParamsDesc, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
+from ._lib import (CloudCounts, CloudParamsDesc, COMM_ID_BYTES, DEPTH_FILLED, DEPTH_FILTER_MAX_RADIUS, DEPTH_FLYING, DEPTH_FUSE_MAX, DEPTH_GATED, DEPTH_KEPT, DEPTH_SMOOTHED, DEPTH_UNMEASURED, DepthFilterCounts, DepthFilterParamsDesc, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, KNN_MAX_K, KNN_NONE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SEGMENT, SEGMENT_DROPPED, SEGMENT_MAX, SEGMENT_MAX_ROOTS, SegmentParamsDesc, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
 
 
@@ -530,6 +530,37 @@ class Scene_nn:
         self.camera = (float(k[0]), float(k[4]), float(k[2]), float(k[5]), int(width), int(height))
         self._n_points, self._n_nodes = npts.value, nnodes.value
         self.pcd_host = self.normal_host = self.nodes_host = None
+        return self
+
+    def init_Scene_nn_cloud(self, points, k: int = 16, max_radius: float = float("inf"), viewpoint=(0.0, 0.0, 0.0), max_leaf: int = 10,
+                            max_dist_diff: float = 0.1, min_neighbours: int = 3, line_ratio: float = 1e-4):
+        """A scene from an unorganised point cloud (``pr_scene_nn_from_cloud_dev``; no counterpart in the reference): ``points`` is an (n, 3)
+        float32 host array or a ``DeviceVector`` of 3 n floats, in metres, finite.  The kd-tree is built on the device (the points are reordered:
+        a ``DeviceVector`` handed in is adopted and reordered in place), then every point gets the PCA normal of its ``k`` nearest neighbours
+        within ``max_radius``, facing ``viewpoint``; a point with fewer than ``min_neighbours`` neighbours, or whose neighbours lie on a line
+        (``line_ratio``), keeps (0, 0, 0) and takes no part in ICP or voting.  ``self.cloud_counts`` holds the four counts.  No camera: the
+        scene carries no pixel-grid hint."""
+        params = CloudParams(k, max_radius, min_neighbours, line_ratio, viewpoint)
+        if isinstance(points, DeviceVector):
+            if points.size() == 0 or points.size() % 3 or points.dtype != np.float32:
+                raise ValueError("points: a DeviceVector of 3 n float32 values, n >= 1")
+            self.pcd_buffer = points
+        else:
+            host = _f32(points)
+            if host.ndim != 2 or host.shape[1] != 3 or len(host) == 0:
+                raise ValueError("points: an (n, 3) float32 array, n >= 1")
+            self.pcd_buffer = DeviceVector.from_host(host.reshape(-1))
+        n = self.pcd_buffer.size() // 3
+        self.normal_buffer = DeviceVector(n * 3, np.float32)
+        self.nodes = DeviceVector(2 * n + 1, KDNODE)
+        nnodes, counts = C.c_uint32(), CloudCounts()
+        check(_lib.load().pr_scene_nn_from_cloud_dev(self.pcd_buffer.data(), n, max_leaf, C.addressof(params), self.normal_buffer.data(), self.nodes.data(),
+                                                     2 * n + 1, C.byref(nnodes), C.addressof(counts)))
+        self.max_dist_diff = max_dist_diff
+        self.camera = None
+        self._n_points, self._n_nodes = n, nnodes.value
+        self.pcd_host = self.normal_host = self.nodes_host = None
+        self.cloud_counts = _cloud_counts(counts)
         return self
 
     def desc(self) -> SceneNNDesc:
@@ -1515,6 +1546,19 @@ def ppf_scene_points(scene: "Scene_projective", stride: int):
     return pts, nrm, n.value
 
 
+def ppf_cloud_points(scene: "Scene_nn", stride: int):
+    """``pr_ppf_cloud_points_dev``: ``ppf_scene_points`` for a kd-tree scene (one made from a point cloud above all) -- (points, normals, n): the
+    points 0, ``stride``, 2 ``stride``, ... of tree order that have a normal, in index order, in mm."""
+    if scene.kind != SCENE_NN:
+        raise ValueError("ppf_cloud_points takes a Scene_nn")
+    pts = DeviceVector(PPF_MAX_SCENE_POINTS * 3, np.float32)
+    nrm = DeviceVector(PPF_MAX_SCENE_POINTS * 3, np.float32)
+    d = scene.desc()
+    n = C.c_uint32(0)
+    check(_lib.load().pr_ppf_cloud_points_dev(C.addressof(d), int(stride), pts.data(), nrm.data(), C.byref(n)))
+    return pts, nrm, n.value
+
+
 def ppf_vote(ppf_model: PPFModel, scene_points: DeviceVector, scene_normals: DeviceVector, n_scene: int, ref_first: int = 0, ref_stride: int = 1,
              n_refs: Optional[int] = None, n_peaks: int = 1, want_acc: bool = False):
     """``pr_ppf_vote``: (peaks PPF_PEAK[n_refs, n_peaks], poses float32[n_refs, n_peaks, 4, 4]) of the references ``ref_first + j * ref_stride``
@@ -1535,13 +1579,15 @@ def ppf_vote(ppf_model: PPFModel, scene_points: DeviceVector, scene_normals: Dev
 
 
 def generate_hypotheses(ppf_model: PPFModel, scene: "Scene_projective", stride: int = 4, ref_stride: int = 5, n_peaks: int = 1, max_hypotheses: int = 256,
-                        merge_mm: Optional[float] = None):
+                        merge_mm: Optional[float] = None, scene_sample=None):
     """Pose hypotheses from a frame and a mesh alone: sample the scene (``stride``), vote with every ``ref_stride``-th sample as a reference, order
     the peaks by votes (descending, then by index), merge duplicates with ``pose_distance_matrix`` + ``merge_duplicates`` over the model's sample
     points (``merge_mm`` defaults to ``dist_step_mm``), add the votes of each merged group onto its representative and order again.  Returns
     (poses float32[n, 4, 4], votes int64[n]), n <= ``max_hypotheses``: ready for ``refine_batch`` and ``score_poses``.  The vote sum is only the
-    order in which hypotheses are handed on; ``rank_hypotheses`` stays the one definition of better after scoring."""
-    pts, nrm, n_scene = ppf_scene_points(scene, stride)
+    order in which hypotheses are handed on; ``rank_hypotheses`` stays the one definition of better after scoring.  ``scene_sample``: a
+    ``(points, normals, n)`` triple as ``ppf_scene_points`` / ``ppf_cloud_points`` return it, taken in place of sampling ``scene`` (which may then
+    be None, and ``stride`` is not read)."""
+    pts, nrm, n_scene = ppf_scene_points(scene, stride) if scene_sample is None else scene_sample
     if n_scene == 0:
         return np.zeros((0, 4, 4), np.float32), np.zeros(0, np.int64)
     n_refs = (n_scene - 1) // ref_stride + 1
@@ -1601,17 +1647,18 @@ def ppf_vote_multi(ppf_models, scene_points: DeviceVector, scene_normals: Device
 
 
 def generate_hypotheses_multi(ppf_models, scene: "Scene_projective", stride: int = 4, ref_stride: int = 5, n_peaks: int = 1, max_hypotheses: int = 256,
-                              merge_mm: Optional[float] = None):
+                              merge_mm: Optional[float] = None, scene_sample=None):
     """``generate_hypotheses`` for several meshes in one frame: one scene sample, ONE vote call (``ppf_vote_multi``), then per model exactly
     ``generate_hypotheses``' ordering, merge (over that model's own sample points, at its ``dist_step_mm`` unless ``merge_mm`` is given) and vote
     summing.  Returns (mesh_index int32[n], poses float32[n, 4, 4], votes int64[n]) grouped by model in table order, votes descending within a
     model, at most ``max_hypotheses`` per model: the slice of model k equals ``generate_hypotheses(ppf_models[k], scene, ...)`` byte for byte, and
-    (mesh_index, poses) go straight to ``refine_batch_multi`` / ``score_poses_multi`` with the models' meshes in the same order."""
+    (mesh_index, poses) go straight to ``refine_batch_multi`` / ``score_poses_multi`` with the models' meshes in the same order.
+    ``scene_sample``: as in ``generate_hypotheses``."""
     models = list(ppf_models)
     if len(models) == 0:
         raise ValueError("generate_hypotheses_multi: no models")
     empty = (np.zeros(0, np.int32), np.zeros((0, 4, 4), np.float32), np.zeros(0, np.int64))
-    pts, nrm, n_scene = ppf_scene_points(scene, stride)
+    pts, nrm, n_scene = ppf_scene_points(scene, stride) if scene_sample is None else scene_sample
     if n_scene == 0:
         return empty
     n_refs = (n_scene - 1) // ref_stride + 1
@@ -1621,6 +1668,91 @@ def generate_hypotheses_multi(ppf_models, scene: "Scene_projective", stride: int
     lists = [_merged_hypotheses(m, peaks[k], poses[k], max_hypotheses, merge_mm) for k, m in enumerate(models)]
     return (np.concatenate([np.full(len(v), k, np.int32) for k, (_, v) in enumerate(lists)]), np.concatenate([p for p, _ in lists]),
             np.concatenate([v for _, v in lists]))
+
+
+# ------------------------------------------------------------------------------------------------
+# scenes from point clouds: exact k nearest neighbours over the scene's kd-tree and a PCA normal per point (pr_cloud_*; the definition is in include/pose_refine.h)
+# ------------------------------------------------------------------------------------------------
+def CloudParams(k: int = 16, max_radius: float = float("inf"), min_neighbours: int = 3, line_ratio: float = 1e-4, viewpoint=(0.0, 0.0, 0.0)) -> CloudParamsDesc:
+    """``pr_cloud_describe``: the checked parameter block of ``cloud_knn`` / ``cloud_normals`` and their host twins."""
+    out = CloudParamsDesc()
+    vp = _f32(viewpoint, -1)
+    if vp.size != 3:
+        raise ValueError("viewpoint: three coordinates")
+    check(_lib.load().pr_cloud_describe(int(k), float(max_radius), int(min_neighbours), float(line_ratio), ptr(vp), C.addressof(out)))
+    return out
+
+
+def _cloud_params(params, kw) -> CloudParamsDesc:
+    if params is not None and kw:
+        raise ValueError("give either a CloudParams block or keyword parameters, not both")
+    return params if params is not None else CloudParams(**kw)
+
+
+def _cloud_counts(c: CloudCounts) -> dict:
+    return {"points": int(c.points), "with_normal": int(c.with_normal), "too_few": int(c.too_few), "degenerate": int(c.degenerate)}
+
+
+def cloud_knn(scene: "Scene_nn", params: Optional[CloudParamsDesc] = None, **kw):
+    """``pr_cloud_knn_dev``: the exact ``k`` nearest neighbours of every point of a kd-tree scene among the scene's own points (itself included),
+    within ``max_radius`` -- (idx uint32[n, k], d2 float32[n, k], count uint32[n]) read back from the device; unused slots hold ``KNN_NONE`` / 0."""
+    if scene.kind != SCENE_NN:
+        raise ValueError("cloud_knn takes a Scene_nn")
+    p = _cloud_params(params, kw)
+    d = scene.desc()
+    n, k = int(d.n_points), int(p.k)
+    idx, d2, cnt = DeviceVector(n * k, np.uint32), DeviceVector(n * k, np.float32), DeviceVector(n, np.uint32)
+    check(_lib.load().pr_cloud_knn_dev(C.addressof(d), C.addressof(p), idx.data(), d2.data(), cnt.data()))
+    return idx.to_host().reshape(n, k), d2.to_host().reshape(n, k), cnt.to_host()
+
+
+def cloud_normals(scene: "Scene_nn", params: Optional[CloudParamsDesc] = None, normal_out: Optional[DeviceVector] = None, want_variation: bool = False,
+                  in_place: bool = False, **kw):
+    """``pr_cloud_normals_dev``: the PCA normal of every point of a kd-tree scene from its k nearest neighbours -- (normals, variation, counts):
+    a ``DeviceVector`` of 3 n floats (``normal_out`` if given; the scene's own normal array with ``in_place``), the surface variation as a
+    ``DeviceVector`` of n floats or None, and the four counts as a dict."""
+    if scene.kind != SCENE_NN:
+        raise ValueError("cloud_normals takes a Scene_nn")
+    p = _cloud_params(params, kw)
+    d = scene.desc()
+    n = int(d.n_points)
+    out = scene.normal_buffer if in_place else (normal_out if normal_out is not None else DeviceVector(n * 3, np.float32))
+    if out.size() < n * 3:
+        raise ValueError(f"normal_out holds {out.size()} floats, the scene needs {n * 3}")
+    var = DeviceVector(n, np.float32) if want_variation else None
+    counts = CloudCounts()
+    check(_lib.load().pr_cloud_normals_dev(C.addressof(d), C.addressof(p), out.data(), var.data() if var is not None else None, C.addressof(counts)))
+    return out, var, _cloud_counts(counts)
+
+
+def kdtree_build_host(points, max_leaf: int = 10):
+    """``pr_kdtree_build`` on host points: (points float32[n, 3] in tree order, nodes KDNODE[n_nodes]) -- what the host twins below take, and
+    byte for byte what ``pr_kdtree_build_dev`` makes of the same points."""
+    pts = np.array(points, np.float32, order="C").reshape(-1, 3)
+    nrm = np.zeros_like(pts)
+    nodes = np.zeros(2 * len(pts) + 1, KDNODE)
+    nn = C.c_uint32()
+    check(_lib.load().pr_kdtree_build(ptr(pts), ptr(nrm), len(pts), int(max_leaf), ptr(nodes), len(nodes), C.byref(nn)))
+    return pts, np.ascontiguousarray(nodes[:nn.value])
+
+
+def cloud_knn_host(points, nodes, params: Optional[CloudParamsDesc] = None, **kw):
+    """``pr_cloud_knn_host``: ``cloud_knn`` on the CPU over host points in tree order and their ``KDNODE`` array (``kdtree_build_host``)."""
+    p = _cloud_params(params, kw)
+    pts, nd = _f32(points).reshape(-1, 3), np.ascontiguousarray(nodes, KDNODE)
+    n, k = len(pts), int(p.k)
+    idx, d2, cnt = np.zeros((n, k), np.uint32), np.zeros((n, k), np.float32), np.zeros(n, np.uint32)
+    check(_lib.load().pr_cloud_knn_host(ptr(pts), n, ptr(nd), len(nd), C.addressof(p), ptr(idx), ptr(d2), ptr(cnt)))
+    return idx, d2, cnt
+
+
+def cloud_normals_host(points, nodes, params: Optional[CloudParamsDesc] = None, **kw):
+    """``pr_cloud_normals_host``: (normals float32[n, 3], variation float32[n], counts dict) on the CPU, byte for byte ``cloud_normals``."""
+    p = _cloud_params(params, kw)
+    pts, nd = _f32(points).reshape(-1, 3), np.ascontiguousarray(nodes, KDNODE)
+    nrm, var, counts = np.zeros((len(pts), 3), np.float32), np.zeros(len(pts), np.float32), CloudCounts()
+    check(_lib.load().pr_cloud_normals_host(ptr(pts), len(pts), ptr(nd), len(nd), C.addressof(p), ptr(nrm), ptr(var), C.addressof(counts)))
+    return nrm, var, _cloud_counts(counts)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -5,11 +5,18 @@
 #include <cmath>
 #include <cstdint>
 
+// (one source for the host and for kernels that run the same solve per lane: cloud.h)
+#if defined(__HIP__)
+#define JACOBI_FN __host__ __device__ inline
+#else
+#define JACOBI_FN inline
+#endif
+
 namespace prr {
 
 // one rotation that zeroes A[p][q]; V takes it along (its columns become the eigenvectors)
 template <int N>
-inline void jacobi_rotate(double (&A)[N][N], double (&V)[N][N], int p, int q)
+JACOBI_FN void jacobi_rotate(double (&A)[N][N], double (&V)[N][N], int p, int q)
 {
     const double apq = A[p][q];
     if (apq == 0.0) return;
@@ -36,7 +43,7 @@ inline void jacobi_rotate(double (&A)[N][N], double (&V)[N][N], int p, int q)
 // sweeps over all pairs p < q in row-major order until the largest off-diagonal is at most 2^-56 of the largest diagonal (tested before each
 // sweep) or max_sweeps are done; returns the number of sweeps done
 template <int N>
-inline uint32_t jacobi_eigen(double (&A)[N][N], double (&V)[N][N], uint32_t max_sweeps)
+JACOBI_FN uint32_t jacobi_eigen(double (&A)[N][N], double (&V)[N][N], uint32_t max_sweeps)
 {
     uint32_t sweeps = 0;
     for (; sweeps < max_sweeps; ++sweeps) {

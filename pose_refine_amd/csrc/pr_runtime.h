@@ -836,6 +836,7 @@ struct Ctx {
     PinBuf h_plane;                  // ... the sample's size, then the rounds' records on their way to the caller
     DevBuf seg_tmp;                  // pr_scene_segments_dev: control words, records, the rank table, the qualifying roots, chunk counts and offsets, the forest and the per-root counts; pr_segment_depth_dev: the keep bits
     PinBuf h_seg;                    // ... the control words and roots on their way to the host, the rank table on its way to the device, the records on their way to the caller
+    DevBuf cloud_tmp;                // pr_cloud_normals_dev / pr_scene_nn_from_cloud_dev: the tally of the points per status
     DevBuf dfilt_tmp;                // pr_depth_filter_dev: the control words (the pixels per flag code)
     PinBuf h_dfilt;                  // ... on their way to the caller
     DevBuf vsd_rec;                  // pr_pose_vsd: the records of a chunk's pairs

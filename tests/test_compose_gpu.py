@@ -12,7 +12,8 @@ from pose_refine_amd import _lib, api, synth
 from compose_ref import Composite, assert_composites_equal, check_invariants, compose_ref
 from gpu_common import W, H, pathological_hypotheses
 from select_ref import PLANTED_SELECTION, planted_frame
-from verify_ref import assert_records_repeat, launch_split_case
+from seam_cases import assert_records_take, assert_seam_visible, seam_index
+from verify_ref import launch_split_case
 
 pytestmark = pytest.mark.gpu
 
@@ -388,17 +389,20 @@ def test_planted_frame_end_to_end(gpu, model, scenario):
 def test_batch_of_two_box_launches(gpu):
     """verify_ref.launch_split_case at 32768 + 5 hypotheses (below PR_COMPOSE_MAX_POSES): the launches over the boxes are split in two, and
     the second's keys carry indices above 32767.  Ties go to the lower index, so every label is below 8 and every later duplicate owns
-    nothing; the records behind the split are the reference's."""
+    nothing; the records behind the split are the reference's.  Behind the split every hypothesis takes the next pose
+    (seam_cases.seam_index), and the reference is composed from the stack so indexed: hypothesis 32768 + j never expects hypothesis j's."""
     c = launch_split_case()
     P = c["P"]
     assert P <= api.COMPOSE_MAX_POSES
-    poses = c["poses"][np.arange(P) % 8]
-    want = compose_ref((c["renders"][i % 8] for i in range(P)), c["scene"], c["tau"])
+    idx = seam_index(P, 8)
+    poses = c["poses"][idx]
+    want = compose_ref((c["renders"][idx[i]] for i in range(P)), c["scene"], c["tau"])
     out = api.compose_detections(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"], c["tau"])
     got, scores = _got(out, c["W"], c["H"])
     assert_composites_equal(got, want)
     check_invariants(got, scores)
-    assert_records_repeat(scores, c["scores"])
+    assert_seam_visible(c["scores"], idx)
+    assert_records_take(scores, c["scores"], idx)
     drawn = got.labels != api.COMPOSE_NONE
     assert drawn.any() and (got.labels[drawn] < 8).all()
     assert not got.visible["owned"][8:].any() and got.visible["owned"][:8].sum() == got.frame["covered"] > 0

@@ -13,6 +13,7 @@ from contour_ref import NO_EDGE, edge_distance_ref, structured_scene
 from gpu_common import H, W, raw_h2d
 from pose_refine_amd import _lib, api, synth
 from test_contour_fit_host import assert_plate_conditions
+from seam_cases import assert_records_take, assert_seam_visible, seam_index
 from verify_ref import launch_split_case
 
 pytestmark = pytest.mark.gpu
@@ -257,9 +258,13 @@ def test_chunked_batch_matches_small_batches(gpu, model, centre):
 
 
 def test_batch_of_two_box_launches(gpu):
-    """32768 + 5 hypotheses in one depth chunk: the launches over their boxes are split in two.  Every record is its pose's, the ones behind the split included."""
+    """32768 + 5 hypotheses in one depth chunk: the launches over their boxes are split in two.  Every record is its pose's, the ones behind the split
+    included.  Behind the split every hypothesis takes the next pose (seam_cases.seam_index): the first eight records are held to the reference, and
+    every other one to the record of its pose among them, so hypothesis 32768 + j never expects hypothesis j's."""
     c = launch_split_case()
-    poses = c["poses"][np.arange(c["P"]) % 8]
+    idx = seam_index(c["P"], 8)
+    assert np.array_equal(idx[:8], np.arange(8))
+    poses = c["poses"][idx]
     K = np.array([60.0, 0, 23.5, 0, 60.0, 15.5, 0, 0, 1], F32)
     cm, rho = np.zeros(3, F32), 0.08
     nd = api.scene_edge_nearest(c["scene"], c["W"], c["H"], c["jump"], 3)
@@ -268,8 +273,8 @@ def test_batch_of_two_box_launches(gpu):
     cs = CF.centers(c["poses"], cm)
     assert_records(fit[:8], info[:8], CF.fit_records(c["renders"], c["scene"], N, c["tau"], c["jump"], K, cs, rho), cs, rho, "split")
     for rec in (scores, fit, info):
-        g = np.ascontiguousarray(rec).view(np.uint8).reshape(len(rec), -1)
-        assert np.array_equal(g, g[np.arange(len(rec)) % 8])
+        assert_seam_visible(rec[:8], idx)
+        assert_records_take(rec, rec[:8], idx)
     assert scores[:8].tobytes() == c["scores"].tobytes() and fit["used"][:8].sum() > 0
 
 

@@ -9,7 +9,8 @@ import oracle_lib as O
 from pose_refine_amd import _lib, api, synth
 from gpu_common import W, H, raw_h2d
 from contour_ref import (NO_EDGE, assert_contours_equal, contour_ref, edge_distance_ref, edges, jump_only, structured_scene)
-from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
+from seam_cases import assert_records_take, assert_seam_visible, seam_index
+from verify_ref import assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -422,11 +423,14 @@ def test_chunked_batch_matches_small_batches(gpu, model):
 
 def test_batch_of_two_box_launches(gpu):
     """32768 + 5 hypotheses in one depth chunk: the launches over their boxes are split in two (grid.y is limited).  Every score and contour
-    record is the reference's for its pose, the ones behind the split included; int32 scene, no overlap matrix."""
+    record is the reference's for its pose, the ones behind the split included; int32 scene, no overlap matrix.  Behind the split every
+    hypothesis takes the next pose (seam_cases.seam_index), so hypothesis 32768 + j never expects hypothesis j's records."""
     c = launch_split_case()
-    poses = c["poses"][np.arange(c["P"]) % 8]
+    idx = seam_index(c["P"], 8)
+    poses = c["poses"][idx]
     ed = api.scene_edge_distance(c["scene"], c["W"], c["H"], c["jump"], c["radius"])
     assert np.array_equal(_dist_host(ed, c["H"], c["W"]), c["dist"])
     scores, got = api.score_contours(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"], c["tau"], c["jump"], ed)
-    assert_records_repeat(got, c["contours"])
-    assert_records_repeat(scores, c["scores"])
+    assert_seam_visible(c["contours"], idx)
+    assert_records_take(got, c["contours"], idx)
+    assert_records_take(scores, c["scores"], idx)

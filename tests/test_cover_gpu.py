@@ -15,7 +15,8 @@ from cover_ref import (ACCEPTED, EMPTY, KEEP_ALL, NOT_IN_ORDER, PLANTED_FRESH, R
 from gpu_common import W, H, pathological_hypotheses
 from pose_refine_amd import _lib, api, synth
 from select_ref import PLANTED_SELECTION, planted_frame, shift
-from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
+from seam_cases import assert_records_take, assert_seam_visible, seam_index
+from verify_ref import assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -418,16 +419,20 @@ def test_more_hypotheses_than_the_overlap_matrix_allows(gpu, scenario):
 def test_batch_of_two_box_launches(gpu, reverse):
     """verify_ref.launch_split_case at 32768 + 5 hypotheses: the launches over the boxes are split in two, each with its own support bits,
     planes and records.  In natural order the first of every pose claims its pixels; reversed, the walk starts behind the split.  The
-    selected list and every record are the reference's, the states of the hypotheses behind the split included."""
+    selected list and every record are the reference's, the states of the hypotheses behind the split included.  Behind the split every
+    hypothesis takes the next pose (seam_cases.seam_index), and the reference is recomputed from the stack so indexed: hypothesis 32768 + j
+    never expects hypothesis j's score or support."""
     c = launch_split_case()
     P = c["P"]
-    poses = c["poses"][np.arange(P) % 8]
+    idx = seam_index(P, 8)
+    poses = c["poses"][idx]
     sup8, n = supports_of(c["renders"], c["scene"], c["tau"])
-    sup = [sup8[i % 8] for i in range(P)]
+    sup = [sup8[idx[i]] for i in range(P)]
     order = np.arange(P)[::-1] if reverse else np.arange(P)
     want = cover_ref(sup, n, order, 1, 4, 1, KEEP_ALL)
     sc, cov, frame, sel = api.score_cover(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"], c["tau"], order, (1, 4), 1, None)
-    assert_records_repeat(sc, c["scores"])
+    assert_seam_visible(c["scores"], idx)
+    assert_records_take(sc, c["scores"], idx)
     assert_cover_equal((cov, frame, sel), want)
     assert len(sel) >= 3 and ((np.asarray(sel) >= 32768).any() if reverse else (np.asarray(sel) < 8).all())
     behind = cov["state"][32768:]

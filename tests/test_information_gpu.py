@@ -11,12 +11,14 @@ import pytest
 import grid_ref
 import info_ref as I
 import robust_ref as R
+import seam_cases as S
 import truth_cases as TC
 import truth_ref as T
 from gpu_common import H, W
 from pass_sums_ref import window
 from pose_refine_amd import _lib, api, synth
 from test_pass_sums_gpu import options, ragged
+from verify_ref import launch_split_case
 
 pytestmark = pytest.mark.gpu
 
@@ -264,3 +266,74 @@ def test_calls_leave_their_neighbours_alone(gpu, model, scenario, gscenes):
     api.icp_information(d, [0, 3073], gscenes["nn"], [centre_of(cloud)], [RHO])
     after, asizes = api.refine_batch(*args, crit)
     assert before.tobytes() == after.tobytes() and np.array_equal(bsizes, asizes)
+
+
+# ---- 7. the 32768-cloud launch seam ---------------------------------------------------------------------------------------------------------------
+def _info_rows(info, eig):
+    return np.concatenate([S.byte_rows(info), S.byte_rows(eig)], axis=1)
+
+
+def _seam_kit(name):
+    sc = S.device_scenes()
+    if name == "grid":
+        return Kit(sc["grid"], grid_host=sc["grid_host"])
+    return Kit(sc["proj" if name in ("proj", "packed") else "nn"], packed=name == "packed")
+
+
+@pytest.mark.parametrize("name", ["proj", "packed", "nn", "nn-walk", "grid"])
+def test_batch_of_two_launches(gpu, name):
+    """32768 + 5 clouds in one call: the information pass runs in two pieces, each with its own staged records and its own part of the output.
+    The clouds are the eight emitted clouds of verify_ref.launch_split_case through seam_cases.seam_index -- behind the seam every cloud, centre
+    and radius is the next one -- so cloud 32768 + j never expects cloud j's record.  The eight-cloud call is held to info_ref; every record and
+    eigen-decomposition of the large call is that of its cloud in the eight-cloud call, byte for byte."""
+    kit = _seam_kit(name.split("-")[0])
+    clouds = S.split_clouds()
+    centers8 = np.array([centre_of(x) for x in clouds], F32)
+    radii8 = np.array([0.05 + 0.01 * k for k in range(8)], F32)
+    rb = api.Robust(api.ROBUST_HUBER, 0.004)
+    with options(**({"nn_compact": 0} if name == "nn-walk" else {})):  # without compact records every lane walks the tree itself
+        flat8, offs8 = ragged(clouds)
+        info8, eig8 = kit.information(flat8, offs8, centers8, radii8, robust=rb)
+        for k, cl in enumerate(clouds):
+            assert_record(info8[k], I.record(cl, kit.associate(cl), rb, centers8[k], radii8[k]), (name, k))
+            assert_eig(info8[k], eig8[k], (name, k))
+        assert (info8["n_valid"] > 0).sum() >= 6
+        idx = S.seam_index(S.P, 8)
+        rows8 = _info_rows(info8, eig8)
+        S.assert_seam_visible(rows8, idx)
+        flat, offs = ragged([clouds[k] for k in idx])
+        info, eig = kit.information(flat, offs, centers8[idx], radii8[idx], robust=rb)
+    S.seam_report(("information", name), [len(x) for x in clouds], np.stack([info["n_points"], info["n_valid"]], 1), idx)
+    S.assert_records_take(_info_rows(info, eig), rows8, idx)
+
+
+def test_fused_and_mixed_batches_of_two_launches(gpu):
+    """pose_information and pose_information_multi at 32768 + 5 hypotheses (the box and a copy scaled by 0.8, in runs of five): the eight-hypothesis
+    calls are held to info_ref on the oracle's clouds; every record of the large calls is that of its mesh and pose, byte for byte."""
+    import oracle_lib as O
+    c, sc = launch_split_case(), S.device_scenes()
+    meshes = [c["tris"], S.small_mesh(c["tris"])]
+    cms, rads = np.array([[0, 0, 0], [3, -2, 1]], F32), np.array([0.08, 0.064], F32)
+    kit = Kit(sc["proj"], packed=True)
+    args = (c["W"], c["H"], c["proj"], S.SPLIT_K, sc["proj"])
+    per_mesh = []
+    for m in (0, 1):
+        info8, eig8, sizes8 = api.pose_information(meshes[m], c["poses"], *args, center=cms[m], radius=float(rads[m]))
+        centers = camera_centres(c["poses"], cms[m])
+        assert np.array_equal(info8["c"], centers) and (info8["rho"] == rads[m]).all()
+        for k, depth in enumerate(O.render(meshes[m], c["poses"], c["W"], c["H"], c["proj"])):
+            cl = O.depth2cloud(depth, S.SPLIT_K)
+            assert sizes8[k] == len(cl)
+            assert_record(info8[k], I.record(cl, kit.associate(cl), None, centers[k], rads[m]), ("fused", m, k))
+            assert_eig(info8[k], eig8[k], ("fused", m, k))
+        per_mesh.append(np.concatenate([_info_rows(info8, eig8), S.byte_rows(sizes8)], axis=1))
+    idx, mi = S.seam_index(S.P, 8), S.mesh_runs(S.P)
+    S.assert_seam_visible(per_mesh[0], idx)
+    info, eig, sizes = api.pose_information(meshes[0], c["poses"][idx], *args, center=cms[0], radius=float(rads[0]))
+    S.seam_report("pose_information", per_mesh[0][:, -4:].copy().view(np.uint32).reshape(-1), np.stack([sizes, info["n_valid"]], 1), idx)
+    S.assert_records_take(np.concatenate([_info_rows(info, eig), S.byte_rows(sizes)], axis=1), per_mesh[0], idx)
+    table, take = S.mixed_table(per_mesh, mi, idx)
+    S.assert_seam_visible(table, take)
+    info, eig, sizes = api.pose_information_multi(meshes, mi, c["poses"][idx], *args, centers=cms, radii=rads)
+    S.seam_report("pose_information_multi", [t[:, -4:].copy().view(np.uint32).reshape(-1).tolist() for t in per_mesh], np.stack([sizes, info["n_valid"]], 1), take)
+    S.assert_records_take(np.concatenate([_info_rows(info, eig), S.byte_rows(sizes)], axis=1), table, take)

@@ -7,8 +7,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import seam_cases as S
 from pose_refine_amd import _lib, api, synth
 from gpu_common import W, H, TOL_T, inliers, random_mesh
+from verify_ref import launch_split_case
 
 pytestmark = pytest.mark.gpu
 
@@ -272,3 +274,64 @@ def test_threads_with_private_contexts(gpu, scenario, gscenes, hyps):
     assert not errs, errs
     for k in range(2):
         _assert_refine_equal(out[k], want[k])
+
+
+# ---- the 32768-hypothesis launch seams of mixed batches ------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def seam_batch(gpu):
+    """verify_ref.launch_split_case with two meshes (the box and a copy scaled by 0.8) in runs of five hypotheses, one of which straddles the seam;
+    behind the seam every hypothesis takes the next pose (seam_cases.seam_index)."""
+    c = launch_split_case()
+    meshes = [c["tris"], S.small_mesh(c["tris"])]
+    idx, mi = S.seam_index(S.P, 8), S.mesh_runs(S.P)
+    return dict(c=c, meshes=meshes, idx=idx, mi=mi, poses=c["poses"][idx], renders=[O.render(t, c["poses"], c["W"], c["H"], c["proj"]) for t in meshes])
+
+
+def test_render_batch_of_two_launches(seam_batch):
+    """render_multi: fill and count run in pieces around one raster launch over all groups.  Every image is the oracle's render of its mesh and pose."""
+    b, c = seam_batch, seam_batch["c"]
+    per_mesh = [api.render_host(t, c["poses"], c["W"], c["H"], c["proj"]) for t in b["meshes"]]
+    for m in (0, 1):
+        assert np.array_equal(per_mesh[m], b["renders"][m]), m
+    table, take = S.mixed_table(per_mesh, b["mi"], b["idx"])
+    S.assert_seam_visible(table, take)
+    got = api.render_multi(b["meshes"], b["mi"], b["poses"], c["W"], c["H"], c["proj"]).to_host().reshape(S.P, -1)
+    S.seam_report("render_multi", [(r > 0).sum((1, 2)).tolist() for r in per_mesh], (got > 0).sum(1), take)
+    S.assert_records_take(got, table, take)
+
+
+def test_score_batch_of_two_launches(seam_batch):
+    b, c = seam_batch, seam_batch["c"]
+    from verify_ref import assert_scores_equal, score_ref
+    per_mesh = [api.score_poses(t, c["poses"], c["W"], c["H"], c["proj"], c["scene"], c["tau"]) for t in b["meshes"]]
+    for m in (0, 1):
+        assert_scores_equal(per_mesh[m], score_ref(b["renders"][m], c["scene"], c["tau"]))
+    table, take = S.mixed_table(per_mesh, b["mi"], b["idx"])
+    S.assert_seam_visible(table, take)
+    got = api.score_poses_multi(b["meshes"], b["mi"], b["poses"], c["W"], c["H"], c["proj"], c["scene"], c["tau"])
+    S.seam_report("score_poses_multi", [s["visible"].tolist() for s in per_mesh], np.stack([got["visible"], got["inlier"]], 1), take)
+    S.assert_records_take(got, table, take)
+
+
+@pytest.mark.parametrize("solve", [api.SOLVE_HOST, pytest.param(api.SOLVE_DEVICE, marks=pytest.mark.device_solve)])
+def test_refine_batch_of_two_launches(seam_batch, solve):
+    b, c = seam_batch, seam_batch["c"]
+    scene = S.device_scenes()["proj"]
+    ppb = api.get_option("points_per_block")
+    api.set_option("solve", solve)
+    try:
+        per_mesh = []
+        for m in (0, 1):
+            res, sizes = api.refine_batch(b["meshes"][m], c["poses"], c["W"], c["H"], c["proj"], S.SPLIT_K, scene, api.ICPConvergenceCriteria(*S.CRIT))
+            ores, osizes = S.refine_ref("proj", ppb, small=bool(m))
+            assert np.array_equal(sizes, osizes) and np.array_equal(res["fitness"], ores["fitness"]), m
+            assert np.allclose(res["T"], ores["T"], rtol=0, atol=TOL_T), m
+            per_mesh.append(S.refine_rows((res, sizes)))
+        table, take = S.mixed_table(per_mesh, b["mi"], b["idx"])
+        S.assert_seam_visible(table, take)
+        got = api.refine_batch_multi(b["meshes"], b["mi"], b["poses"], c["W"], c["H"], c["proj"], S.SPLIT_K, scene, api.ICPConvergenceCriteria(*S.CRIT))
+        S.seam_report(("refine_batch_multi", solve), [t[:, -4:].copy().view(np.uint32).reshape(-1).tolist() for t in per_mesh],
+                      np.stack([got[1], got[0]["fitness"]], 1), take)
+        S.assert_records_take(S.refine_rows(got), table, take)
+    finally:
+        api.set_option("solve", api.SOLVE_HOST)

@@ -8,7 +8,8 @@ import oracle_lib as O
 from pose_refine_amd import _lib, api, synth
 from gpu_common import raw_h2d
 from normals_ref import assert_identities, assert_normals_equal, normals_ref
-from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
+from seam_cases import assert_records_take, assert_seam_visible, seam_index
+from verify_ref import assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -281,12 +282,15 @@ def test_chunked_batch_matches_small_batches(gpu, model):
 
 def test_batch_of_two_box_launches(gpu):
     """32768 + 5 hypotheses in one depth chunk: the launches over their boxes are split in two (grid.y is limited), and the second starts at
-    its own records.  Every score and normal record is the reference's for its pose, the ones behind the split included; uint16 scene."""
+    its own records.  Every score and normal record is the reference's for its pose, the ones behind the split included; uint16 scene.
+    Behind the split every hypothesis takes the next pose (seam_cases.seam_index), so hypothesis 32768 + j never expects hypothesis j's records."""
     c = launch_split_case()
-    poses = c["poses"][np.arange(c["P"]) % 8]
+    idx = seam_index(c["P"], 8)
+    poses = c["poses"][idx]
     scene = np.ascontiguousarray(c["scene"].astype(np.uint16))
     want = normals_ref(c["renders"], c["scene"], c["tau"], SPLIT_K, 1, c["jump"], COS30)
     assert want["tested"].sum() > 0 and len(set(want["tested"].tolist())) > 4      # records that tell the poses apart
+    assert_seam_visible(want, idx)
     scores, got = api.score_normals(c["tris"], poses, c["W"], c["H"], c["proj"], scene, c["tau"], SPLIT_K, 1, c["jump"], COS30)
-    assert_records_repeat(got, want)
-    assert_records_repeat(scores, c["scores"])
+    assert_records_take(got, want, idx)
+    assert_records_take(scores, c["scores"], idx)

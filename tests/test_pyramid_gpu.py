@@ -8,8 +8,11 @@ import pytest
 
 import oracle_lib as O
 import pyramid_ref as R
+import seam_cases as S
 from pose_refine_amd import _lib, api, synth
 from gpu_common import W, H, TOL_T, inliers
+from test_nn_exact_gpu import options
+from verify_ref import launch_split_case
 
 pytestmark = pytest.mark.gpu
 
@@ -319,5 +322,81 @@ def test_refine_batch_is_unchanged_by_pyramid_calls(gpu, model, scenario, gscene
         mid = _pyr(model, poses, scenario, gscenes[kind], api.PYRAMID_DEFAULT)     # with a batch pending on a slot
         assert _same_bytes(api.refine_wait(0), before)
         assert _same_bytes(mid, _pyr(model, poses, scenario, gscenes[kind], api.PYRAMID_DEFAULT))
+    finally:
+        api.set_option("solve", api.SOLVE_HOST)
+
+
+# ---- 8: the 32768-hypothesis launch seams ----------------------------------------------------------------------------------------
+def _split_pyr(c, tris, poses, scene, levels):
+    return api.refine_pyramid(tris, poses, c["W"], c["H"], c["proj"], S.SPLIT_K, scene, levels, return_levels=True)
+
+
+def _eight_against_ref(c, kind, levels, what, small=False):
+    """The eight-hypothesis call on the split case, held to pyramid_ref by this file's rule; returned as one row of bytes per hypothesis."""
+    tris = S.small_mesh(c["tris"]) if small else c["tris"]
+    eight = _split_pyr(c, tris, c["poses"], S.device_scenes()[kind], levels)
+    _assert_against_ref(eight, S.pyramid_ref_records(kind, tuple(levels), api.get_option("points_per_block"), small), what)
+    return eight, S.pyramid_rows(eight)
+
+
+SOLVES = [api.SOLVE_HOST, pytest.param(api.SOLVE_DEVICE, marks=pytest.mark.device_solve)]
+
+
+@pytest.mark.parametrize("kind", ["proj", "nn"])
+@pytest.mark.parametrize("solve", SOLVES)
+def test_batch_of_two_launches(gpu, solve, kind):
+    """32768 + 5 hypotheses of verify_ref.launch_split_case, two levels: the count and emit launches run in two pieces, and the level loops
+    (host and device solve) over more than 32768 clouds.  Behind the seam every hypothesis takes the next pose (seam_cases.seam_index); every
+    hypothesis' whole output -- record, level records, level sizes -- is that of its pose in the eight-hypothesis call, byte for byte."""
+    c = launch_split_case()
+    api.set_option("solve", solve)
+    try:
+        eight, rows8 = _eight_against_ref(c, kind, S.PYR2, (solve, kind))
+        idx = S.seam_index(S.P, 8)
+        S.assert_seam_visible(rows8, idx)
+        # the level loops cut a batch into pose groups (two by default) and launch the pass per group: one group (pose_groups 1) puts all 32773
+        # hypotheses on one pass launch, which then runs in two pieces itself; the count, scan and emit launches cross their seams either way
+        for groups in (1, 0):
+            with options(pose_groups=groups):
+                got = _split_pyr(c, c["tris"], c["poses"][idx], S.device_scenes()[kind], S.PYR2)
+            S.seam_report(("pyramid", solve, kind, "pose_groups", groups), eight[2], got[2].T, idx)
+            S.assert_records_take(S.pyramid_rows(got), rows8, idx)
+    finally:
+        api.set_option("solve", api.SOLVE_HOST)
+
+
+@pytest.mark.parametrize("solve,kind", [(api.SOLVE_HOST, "proj"), pytest.param(api.SOLVE_DEVICE, "nn", marks=pytest.mark.device_solve)])
+def test_row_scan_of_two_launches(gpu, solve, kind):
+    """8200 hypotheses x 4 levels: the row scan runs over 32800 (level, hypothesis) images in two pieces, the second of which starts at
+    hypothesis 8168 of the last level; the count and emit launches are single.  The index steps there, so neighbours across the seam differ."""
+    c = launch_split_case()
+    api.set_option("solve", solve)
+    try:
+        eight, rows8 = _eight_against_ref(c, kind, S.PYR4, (solve, kind, "scan"))
+        idx = S.seam_index(S.SCAN_P, 8, S.SCAN_SEAM)
+        assert len(S.PYR4) * S.SCAN_P > S.SEAM == 3 * S.SCAN_P + S.SCAN_SEAM
+        S.assert_seam_visible(rows8, idx, S.SCAN_SEAM)
+        got = _split_pyr(c, c["tris"], c["poses"][idx], S.device_scenes()[kind], S.PYR4)
+        S.seam_report(("row scan", solve, kind), eight[2], got[2].T, idx, S.SCAN_SEAM)
+        S.assert_records_take(S.pyramid_rows(got), rows8, idx, S.SCAN_SEAM)
+    finally:
+        api.set_option("solve", api.SOLVE_HOST)
+
+
+@pytest.mark.parametrize("solve", SOLVES)
+def test_mixed_batch_of_two_launches(gpu, solve):
+    """32768 + 5 hypotheses of two meshes (the box and a copy scaled by 0.8) in runs of five, one of which straddles the seam: every hypothesis'
+    whole output is that of its pose in the eight-hypothesis single-mesh call of its mesh."""
+    c = launch_split_case()
+    meshes = [c["tris"], S.small_mesh(c["tris"])]
+    api.set_option("solve", solve)
+    try:
+        per_mesh = [_eight_against_ref(c, "proj", S.PYR2, (solve, "mesh", m), small=bool(m)) for m in (0, 1)]
+        idx, mi = S.seam_index(S.P, 8), S.mesh_runs(S.P)
+        table, take = S.mixed_table([rows for _, rows in per_mesh], mi, idx)
+        S.assert_seam_visible(table, take)
+        got = api.refine_pyramid_multi(meshes, mi, c["poses"][idx], c["W"], c["H"], c["proj"], S.SPLIT_K, S.device_scenes()["proj"], S.PYR2, return_levels=True)
+        S.seam_report(("mixed pyramid", solve), [e[2][-1].tolist() for e, _ in per_mesh], got[2].T, take)
+        S.assert_records_take(S.pyramid_rows(got), table, take)
     finally:
         api.set_option("solve", api.SOLVE_HOST)

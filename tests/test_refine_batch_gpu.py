@@ -11,8 +11,11 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import seam_cases as S
 from pose_refine_amd import _lib, api, synth
 from gpu_common import *  # noqa: F401,F403 -- W, H, TOL_T, inliers, raw_h2d, make_scene, random_mesh ...
+from test_nn_exact_gpu import options
+from verify_ref import launch_split_case
 
 pytestmark = pytest.mark.gpu
 
@@ -313,3 +316,66 @@ def test_packed_clouds_and_boxes_at_their_capacity_bound(gpu, W, H):
         ares, asizes = api.refine_wait(b)
         assert np.array_equal(asizes, osizes) and np.array_equal(ares["fitness"], ores["fitness"])
         assert np.array_equal(ares["T"], res["T"])
+
+
+# ---- the 32768-hypothesis launch seams of the synchronous route -----------------------------------------------------------------------
+def _seam_refine(scene, poses, robust=None):
+    c = launch_split_case()
+    return api.refine_batch(c["tris"], poses, c["W"], c["H"], c["proj"], S.SPLIT_K, scene, api.ICPConvergenceCriteria(*S.CRIT), robust=robust)
+
+
+def _eight_against_ref(name, robust):
+    """The eight-hypothesis call on verify_ref.launch_split_case, held to the CPU reference of its scene by the rule of that scene's file: the
+    oracle (kd-tree), grid_ref.icp_loop (grid), robust_ref.loop over the library's own correspondences (robust weights)."""
+    import grid_ref
+    import robust_ref
+    c, sc = launch_split_case(), S.device_scenes()
+    ppb = api.get_option("points_per_block")
+    res, sizes = _seam_refine(sc[name], c["poses"], robust)
+    clouds = S.split_clouds()
+    assert np.array_equal(sizes, [len(x) for x in clouds])
+    if name == "nn":
+        ores, osizes = S.refine_ref("nn", ppb)
+        assert np.array_equal(sizes, osizes) and np.array_equal(res["fitness"], ores["fitness"])
+        assert np.allclose(res["inlier_rmse"], ores["inlier_rmse"], rtol=1e-6, atol=0) and np.allclose(res["T"], ores["T"], rtol=0, atol=TOL_T)
+        return res, sizes
+    for i, cl in enumerate(clouds):
+        if name == "grid":
+            T, rmse, fit, _ = grid_ref.icp_loop(cl, *sc["grid_host"], S.CRIT, ppb)
+        else:
+            none = api.Robust(api.ROBUST_NONE)
+
+            def associate(cloud):
+                _, corr = api.debug_robust_terms(api.DeviceVector.from_host(np.ascontiguousarray(cloud, np.float32).reshape(-1)), sc[name], none)
+                return corr[:, 0:3].copy(), corr[:, 4:7].copy(), corr[:, 3] == 1.0
+            T, rmse, fit, _ = robust_ref.loop(cl, associate, robust, S.CRIT, ppb)
+        assert res[i]["fitness"] == np.float32(fit) and res[i]["inlier_rmse"] == np.float32(rmse), (name, i)
+        assert inliers(res[i]["fitness"], len(cl)) == inliers(fit, len(cl)), (name, i)
+        assert np.allclose(res[i]["T"], T, rtol=0, atol=TOL_T), (name, i, np.abs(res[i]["T"] - T).max())
+    return res, sizes
+
+
+@pytest.mark.parametrize("name,solve,robust", [
+    ("grid", api.SOLVE_HOST, None), pytest.param("grid", api.SOLVE_DEVICE, None, marks=pytest.mark.device_solve), ("nn", api.SOLVE_HOST, None),
+    pytest.param("proj", api.SOLVE_DEVICE, (api.ROBUST_HUBER, 0.005), marks=pytest.mark.device_solve)], ids=["grid-host", "grid-device", "kdtree-host", "huber-device"])
+def test_batch_of_two_launches_synchronous_route(gpu, name, solve, robust):
+    """32768 + 5 hypotheses of verify_ref.launch_split_case in one call: the depth chunk is the whole batch, so the pass launchers themselves run
+    in two pieces -- the grid pass, the kd-tree search with its layout, and the device-solve loop that grid scenes and robust weights take.
+    Behind the seam every hypothesis takes the next pose (seam_cases.seam_index); record and cloud size are those of its pose in the
+    eight-hypothesis call, byte for byte."""
+    rb = api.Robust(*robust) if robust else None
+    api.set_option("solve", solve)
+    try:
+        eight = _eight_against_ref(name, rb)
+        rows8 = S.refine_rows(eight)
+        idx = S.seam_index(S.P, 8)
+        S.assert_seam_visible(rows8, idx)
+        # either driver cuts a batch into pose groups (two by default) and launches the pass per group: 32773 hypotheses in ONE group (pose_groups 1)
+        # is what puts more than 32768 on a pass launch; with the default, the launches in front of the loop cross their seams and the groups' do not
+        for groups in (1, 0):
+            with options(pose_groups=groups):
+                got = _seam_refine(S.device_scenes()[name], launch_split_case()["poses"][idx], rb)
+            S.seam_report((name, solve, robust, "pose_groups", groups), eight[1], np.stack([got[1], got[0]["fitness"]], 1), idx)
+            S.assert_records_take(S.refine_rows(got), rows8, idx)
+    finally:
+        api.set_option("solve", api.SOLVE_HOST)

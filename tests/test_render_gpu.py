@@ -188,24 +188,28 @@ def test_degenerate_intrinsics(gpu, name, Kd):
 
 def test_render_launch_split_full_frames(gpu):
     """32768 + 5 full frames: pr_render and pr_render_span split their raster over two launches (grid.y is limited).  verify_ref.launch_split_case's
-    8 distinct poses repeated: image i is render i % 8 in the near plane and solid_ref.span_ref's far surface of pose i % 8 in the far plane -- on
-    both sides of the split, at its last and first image, and at the batch's last.  (span_ref's far plane of these 8 poses holds 123 to 667 pixels
-    with far > near each: an unwritten far plane cannot pass.)"""
+    8 distinct poses repeated, behind the split each hypothesis with the next pose (seam_cases.seam_index): image i is render idx[i] in the near
+    plane and solid_ref.span_ref's far surface of pose idx[i] in the far plane -- on both sides of the split, at its last and first image, and
+    at the batch's last; the first image of the second launch is not the first image of the first.  (span_ref's far plane of these 8 poses
+    holds 123 to 667 pixels with far > near each: an unwritten far plane cannot pass.)"""
+    from seam_cases import assert_seam_visible, seam_index
     from solid_ref import span_ref
     from verify_ref import launch_split_case
     c = launch_split_case()
     w, h, P = c["W"], c["H"], c["P"]
     assert P == 32768 + 5
-    poses = c["poses"][np.arange(P) % 8]
+    idx = seam_index(P, 8)
+    poses = c["poses"][idx]
     ref_near, ref_far = span_ref(c["tris"], c["poses"], c["proj"], w, h)
     assert np.array_equal(ref_near, c["renders"]) and all((ref_far[k] > ref_near[k]).sum() > 100 for k in range(8))
     m = api.Model(tris=c["tris"])
 
     def check(plane, ref):
+        assert_seam_visible(ref, idx)
         got = plane.to_host().reshape(P, h, w)
         for i in (0, 1, 32767, 32768, 32769, 32772):
-            assert np.array_equal(got[i], ref[i % 8]), i
-        assert got[0].tobytes() == got[32768].tobytes()              # the first image of either launch
+            assert np.array_equal(got[i], ref[idx[i]]), i
+        assert got[32768].tobytes() == ref[idx[32768]].tobytes() and got[32768].tobytes() != got[0].tobytes()      # the first image of either launch
 
     check(api.render(m, poses, w, h, c["proj"]), c["renders"])
     near, far = api.render_span(m, poses, w, h, c["proj"])

@@ -9,7 +9,8 @@ import pytest
 import oracle_lib as O
 from pose_refine_amd import _lib, api, synth
 from gpu_common import W, H, raw_h2d
-from verify_ref import assert_records_repeat, assert_scores_equal, launch_split_case, score_ref
+from seam_cases import assert_records_take, assert_seam_visible, seam_index
+from verify_ref import assert_scores_equal, launch_split_case, score_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -247,8 +248,10 @@ def test_chunked_batch_matches_small_batches(gpu, model):
 
 def test_batch_of_two_box_launches(gpu):
     """32768 + 5 hypotheses in one depth chunk: the launch over their boxes is split in two (grid.y is limited).  Every record is the
-    reference's for its pose, the ones behind the split included; uint16 scene."""
+    reference's for its pose, the ones behind the split included; uint16 scene.  Behind the split every hypothesis takes the next pose
+    (seam_cases.seam_index): a piece that read hypothesis j's pose or box for 32768 + j would give another record."""
     c = launch_split_case()
-    poses = c["poses"][np.arange(c["P"]) % 8]
-    got = api.score_poses(c["tris"], poses, c["W"], c["H"], c["proj"], c["scene"].astype(np.uint16), c["tau"])
-    assert_records_repeat(got, c["scores"])
+    idx = seam_index(c["P"], 8)
+    got = api.score_poses(c["tris"], c["poses"][idx], c["W"], c["H"], c["proj"], c["scene"].astype(np.uint16), c["tau"])
+    assert_seam_visible(c["scores"], idx)
+    assert_records_take(got, c["scores"], idx)

@@ -10,6 +10,7 @@ import oracle_lib as O
 import vsd_ref as R
 from pose_refine_amd import _lib, api, synth
 from gpu_common import W, H
+from seam_cases import assert_records_take, assert_seam_visible, seam_index
 from verify_ref import assert_records_repeat
 
 pytestmark = pytest.mark.gpu
@@ -138,12 +139,14 @@ def test_one_truth_for_many_estimates(gpu):
 
 
 def test_batch_of_two_launches(gpu):
-    """32768 + 5 pairs in one depth chunk: the launch over the pairs is split in two (grid.y is limited); uint16 scene."""
+    """32768 + 5 pairs in one depth chunk: the launch over the pairs is split in two (grid.y is limited); uint16 scene.  Behind the split every
+    pair is the next of the 32 (seam_cases.seam_index), so pair 32768 + j never expects pair j's record."""
     c = R.small_case()
     want = R.vsd_ref(c["r_est"], c["r_gt"], c["scene"], c["K"], c["delta"], c["taus"])
-    idx = np.arange(32768 + 5) % 32
+    idx = seam_index(32768 + 5, 32)
+    assert_seam_visible(want, idx)
     got = api.pose_vsd(c["tris"], c["est"][idx], c["gt"][idx], c["W"], c["H"], c["proj"], c["scene"].astype(np.uint16), c["K"], c["delta"], c["taus"])
-    assert_records_repeat(got, want)
+    assert_records_take(got, want, idx)
 
 
 def test_chunked_batch(gpu):

@@ -1387,13 +1387,24 @@ int pr_gather_results(const pr_result *send_dev, uint32_t n_local, uint32_t n_to
  *                              way ("stat_band_batches", read-only: asynchronous batches of this process that ran on banded boxes; "box_pack",
  *                              read-only: the ints a box's slot is rounded up to)
  *   "resident_loop"    [1]     asynchronous path, projective scene, device solve with "fused_solve", no timed call: every pass of a sub-batch runs in
- *                              ONE launch, a 1024-lane workgroup per hypothesis that meets once per pass in LDS; 0 = one launch per pass and pose group
+ *                              ONE launch, a workgroup per hypothesis that meets once per pass in LDS -- 512 lanes, two workgroups to a compute unit, for a sub-batch
+ *                              with at least one hypothesis per compute unit, 1024 lanes for a smaller one ("loop_waves"); 0 = one launch per pass and pose group
  *                              everywhere.  Same results either way.  A plan whose blocks would need more than 64 KiB of LDS (over 127 blocks per hypothesis)
  *                              keeps the multi-launch loop ("stat_resident_batches", read-only: sub-batches of this process whose loop ran as one launch)
  *   "loop_lds_blocks"  [-1]    "resident_loop": blocks of "points_per_block" points at the head of every cloud that the workgroup keeps in its compute unit's LDS
  *                              over the whole loop instead of moving them through memory every pass; -1 = as many as fit in 160 KiB behind the loop's own
  *                              rows (four of 3072 points), 0 = none, n > 0 = at most n.  Same results either way ("stat_loop_lds_blocks", read-only: the
  *                              number the most recent such launch ran with)
+ *   "loop_lds_tables"  [-1]    "resident_loop": the scene's column and row tables (width + height floats) are copied once per hypothesis into the
+ *                              workgroup's LDS, behind the loop's rows and ahead of the cloud's blocks ("loop_lds_blocks" gets what is left), and two
+ *                              of the three scene reads per point and pass come from there; 0 = from memory, 1 = in LDS whenever they fit beside the
+ *                              rows, -1 = the library's choice (in LDS for 8-wave workgroups, in memory for 16-wave ones); other values are clamped
+ *                              to -1 .. 1.  Same results either way ("stat_loop_lds_tables", read-only: the bytes of tables the most recent such
+ *                              launch kept in LDS, 0 when it read them from memory)
+ *   "loop_waves"       [0]     "resident_loop": wavefronts per workgroup, 16 (1024 lanes, one workgroup per compute unit) or 8 (512 lanes, two per
+ *                              compute unit, each within 80 KiB of LDS); 0 = the library's choice, which is 16 for a sub-batch with fewer hypotheses
+ *                              than the device has compute units; any other value is refused.  Same results either way ("stat_loop_waves",
+ *                              read-only: what the most recent such launch ran with)
  *   "nn_stack"         [1]     kd-tree query: per-lane LDS stack (1) or the reference's stackless walk (0)
  *   "nn_compact"       [1]     stack query on 32-byte node records with 16-bit outward-rounded boxes (0: exact 64-byte records)
  *   "host_worker"      [1]     host solve: a batch given to pr_refine_submit runs on a library-owned helper thread of its slot (private context: its own

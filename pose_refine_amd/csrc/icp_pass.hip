@@ -92,11 +92,17 @@ __device__ __forceinline__ float sum_partials(const float *partial, uint32_t pos
 
 // ================================================================================================
 //  The whole loop of a hypothesis in ONE workgroup (option "resident_loop", asynchronous fused path, packed projective scene, device solve):
-//  grid = hypotheses, 1024 lanes = 16 wavefronts on one compute unit, all passes in one launch.  What the multi-launch loop pays per pass --
+//  grid = hypotheses, all passes in one launch, in one of two workgroup sizes (option "loop_waves"): 1024 lanes = 16 wavefronts, one workgroup
+//  per compute unit (icp_loop_cu_kernel), or 512 lanes = 8 wavefronts, two workgroups per compute unit (icp_loop_cu8_kernel).  The library takes
+//  the 8-wave form for a sub-batch with at least one hypothesis per compute unit and the 16-wave form for a smaller one, which cannot fill the
+//  chip and keeps the lower latency.  Between the two barriers of a pass one wavefront adds the rows and solves while the others of its workgroup
+//  wait -- 4.5 us of a pass, measured -- and the wavefronts of a second, independent hypothesis on the same compute unit use that time; so do the
+//  idle rounds of a cloud whose items do not divide by the wavefronts.  HIP promises nothing about where a workgroup lands, and nothing here
+//  depends on it: no workgroup waits for another one.  What the multi-launch loop pays per pass --
 //  a launch, a ragged last round of workgroups, partial sums and an arrival ticket through memory, a PoseMeta round trip -- becomes two
 //  LDS barriers.  No workgroup waits for another one: a batch larger than the chip runs in rounds.
 //  Unit of work: item 4 * vb + w = wavefront w of virtual block vb of the canonical tree (vb_accumulate_at with tib = 64 w + lane), always
-//  taken by wavefront (4 * vb + w) mod 16.  The mapping never changes, so a lane only reads cloud points that it wrote itself (or that
+//  taken by wavefront (4 * vb + w) mod kWaves (16 or 8).  The mapping never changes, so a lane only reads cloud points that it wrote itself (or that
 //  were there before the launch): the cloud stays in memory, moved and written back per pass exactly as icp_pass_kernel does, no fence.
 //  Per pass: every wavefront leaves the 29 sums of its items in LDS row [vb][w] (wave_reduce) | barrier | wavefront 0 forms
 //  ((w0+w1)+w2)+w3 per block, adds the blocks in block order from 0.0f (sum_partials' sequence), runs pose_iteration_wave and leaves the
@@ -105,7 +111,12 @@ __device__ __forceinline__ float sum_partials(const float *partial, uint32_t pos
 //  DevIcpState stays in the LDS header over the loop (only wavefront 0 touches it; registers are left to the point work) and is stored once;
 //  PoseMeta is left as the multi-launch loop leaves it (kSkip, the last update).  Same source per point, same tree: the same bytes.
 //  LDS (dynamic): b.nblk * 4 rows of kAccStride floats, then kLoopHeader words: [0..11] update, [12] finished, [16..35] DevIcpState, then
-//  the LDS image of the cloud's head (option "loop_lds_blocks").
+//  (kTables, option "loop_lds_tables") the scene's colf and rowf tables, width + height floats, then the LDS image of the cloud's head (option
+//  "loop_lds_blocks") -- within 160 KiB for the 16-wave form and 80 KiB for the 8-wave one (icp_loop_cu_layout).
+//  The tables in LDS: filled once at the start of the kernel by the whole workgroup, one more barrier ahead of pass 0 (behind the early return,
+//  which is the whole workgroup's); from then on two of the three gathers per point and pass (gather_issue(SceneProjPackedLds), proj_query.h)
+//  are ds_read_b32 instead of trips through the texture addresser, whose rate is what a pass waits for.  The record gather stays in memory.
+//  With and without tables are two instantiations, not a branch per gather.
 //  The head of the cloud in LDS: the workgroup has its compute unit to itself (sixteen wavefronts of 124+ VGPRs are the whole register file),
 //  so the LDS beyond rows and header is free.  Points [0, b.lds_blocks * ppb) -- whole blocks, items 0 .. 4 * b.lds_blocks - 1 -- are loaded from
 //  memory in pass 0 (pending transform applied exactly where the other items apply it), stored to LDS whether moved or not, and from pass 1 on
@@ -139,10 +150,46 @@ uint32_t icp_loop_cu_lds_blocks(uint32_t nblk, uint32_t steps, int cap)
     if (cap >= 0 && (uint32_t)cap < r) r = (uint32_t)cap;
     return r;
 }
-
-template <class Scene>
-__global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel(IcpBatch b, Scene scene)
+// words of the two tables in LDS (option "loop_lds_tables"): width + height floats, rounded up to four so that the cloud image behind them keeps
+// its 16-byte alignment
+__host__ __device__ constexpr uint32_t loop_table_words(uint32_t width, uint32_t height) { return (width + height + 3u) & ~3u; }
+// The whole layout for a workgroup of `waves` wavefronts (16: the compute unit's 160 KiB; 8: half of it, so that two workgroups fit): rows and
+// header, then the tables of a width x height scene (0 x 0: none asked for), then whole blocks -- returned -- in what is left, at most nblk, at
+// most `cap`.  *fixed_bytes: rows, header and the tables that were granted.  Tables first, whole blocks after: the tables are granted whenever
+// they fit beside rows and header.  Rows and header over the 64 KiB budget: nothing (the launch is refused).
+uint32_t icp_loop_cu_layout(uint32_t nblk, uint32_t steps, int cap, uint32_t width, uint32_t height, uint32_t waves, uint32_t *fixed_bytes)
 {
+    const size_t limit = waves >= kLoopWaves ? kLoopCuLdsTotal : kLoopCuLdsTotal / 2;
+    const size_t rows = icp_loop_cu_lds_bytes(nblk), block = (size_t)steps * kPointsPerStep * sizeof(pr_vec3);
+    size_t tables = (size_t)loop_table_words(width, height) * sizeof(float);
+    if (fixed_bytes) *fixed_bytes = (uint32_t)rows;
+    if (rows > kLoopCuLdsBudget || rows > limit || block == 0) return 0;
+    auto blocks_behind = [&](size_t fixed) {
+        const size_t fit = (limit - fixed) / block;
+        uint32_t r = (uint32_t)(fit < nblk ? fit : nblk);
+        if (cap >= 0 && (uint32_t)cap < r) r = (uint32_t)cap;
+        return r;
+    };
+    if (rows + tables > limit) tables = 0;
+    if (fixed_bytes) *fixed_bytes = (uint32_t)(rows + tables);
+    return blocks_behind(rows + tables);
+}
+
+// the scene as the point work of the loop sees it: the kernel's argument, or (kTables) the same scene with its two tables read from `tab` in LDS
+template <bool kTables> struct LoopScene;
+template <> struct LoopScene<false> {
+    using type = SceneProjPacked;
+    static __device__ __forceinline__ const type &make(const SceneProjPacked &sc, const float *) { return sc; }
+};
+template <> struct LoopScene<true> {
+    using type = SceneProjPackedLds;
+    static __device__ __forceinline__ type make(const SceneProjPacked &sc, const float *tab) { return type{ sc, tab, tab + sc.width }; }
+};
+
+template <uint32_t kWaves, bool kTables>
+__device__ __forceinline__ void icp_loop_cu_body(const IcpBatch &b, const SceneProjPacked &scene_arg)
+{
+    using Scene = typename LoopScene<kTables>::type;
     extern __shared__ __attribute__((aligned(16))) float loop_lds[];
     const uint32_t pose = blockIdx.x;
     const PoseMeta &pm = b.meta[pose];                           // uniform address: one 64-byte scalar load
@@ -156,19 +203,33 @@ __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel
     float *hdr = loop_lds + (size_t)b.nblk * 4 * kAccStride;
     uint32_t *hdw = reinterpret_cast<uint32_t *>(hdr);
     float *cl = reinterpret_cast<float *>(b.cloud + pm.start);
-    float *lcl = hdr + kLoopHeader;                              // the LDS image of points [0, b.lds_blocks * ppb) of the cloud
+    float *tab = hdr + kLoopHeader;                              // kTables: colf[0 .. width), rowf[0 .. height), rounded up to four words
+    float *lcl = tab + (kTables ? loop_table_words(scene_arg.width, scene_arg.height) : 0u);   // the LDS image of points [0, b.lds_blocks * ppb) of the cloud
     const uint32_t lds_items = b.lds_blocks * 4u;
     bool xf = (st0 == kRunWithTransform) && !b.pre_transformed;
     float M[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) M[i] = xf ? pm.xform[i] : 0.0f;
     if (wave == 0 && lane < 20) hdw[16 + lane] = reinterpret_cast<const uint32_t *>(b.st + pose)[lane];
+    if constexpr (kTables) {                                     // once per hypothesis and loop: every gather of every pass reads the copy
+        const uint32_t w = scene_arg.width, wh = w + scene_arg.height;
+        for (uint32_t i = threadIdx.x; i < wh; i += kWaves * 64u) tab[i] = i < w ? scene_arg.colf[i] : scene_arg.rowf[i - w];
+        __syncthreads();
+    }
+    const Scene scene = LoopScene<kTables>::make(scene_arg, tab);
+#if PR_LOOP_CU_PROBE
+    uint64_t probe_serial = 0, probe_total = 0;
+#endif
 
     const uint32_t last_it = (uint32_t)b.crit.max_iteration;
     uint32_t it = 0;
     for (;; ++it) {
         const bool score_only = it == last_it;                   // uniform: the final pass needs sums 27 and 28 only
-        for (uint32_t item = wave; item < items; item += kLoopWaves) {
+#if PR_LOOP_CU_PROBE
+        const uint64_t probe_t0 = wall_clock64();
+        uint64_t probe_t1 = 0;
+#endif
+        for (uint32_t item = wave; item < items; item += kWaves) {
             const uint32_t vb = item >> 2, tib = ((item & 3u) << 6) | lane;
             float acc[29];
             float *row = loop_lds + (size_t)item * kAccStride;
@@ -188,6 +249,9 @@ __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel
             }
         }
         __syncthreads();                                         // every item's row is in LDS
+#if PR_LOOP_CU_PROBE
+        probe_t1 = wall_clock64();
+#endif
         if (wave == 0) {
             float total = 0.0f;
             if (lane < 29) {
@@ -212,7 +276,13 @@ __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel
                 hdw[12] = (finished || it >= last_it) ? 1u : 0u;
             }
         }
+#if PR_LOOP_CU_PROBE
+        probe_serial += wall_clock64() - probe_t1;               // wavefront 0: the stretch between the two barriers
+#endif
         __syncthreads();                                         // update and flag are in LDS; the rows have been read
+#if PR_LOOP_CU_PROBE
+        probe_total += wall_clock64() - probe_t0;
+#endif
         if (__builtin_amdgcn_readfirstlane(hdw[12]) != 0u) break;
 #pragma unroll
         for (int i = 0; i < 12; ++i) M[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hdr[i])));
@@ -230,26 +300,51 @@ __global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel
             for (int i = 0; i < 12; ++i) wm->xform[i] = hdr[i];
         }
         wm->state = kSkip;
+#if PR_LOOP_CU_PROBE
+        // four floats per hypothesis in the slot's partial buffer (unused on this route): ticks of the 100 MHz wall clock between the barriers and
+        // over whole passes, the passes, the items
+        float *pr = b.partial + (size_t)pose * 4;
+        pr[0] = (float)probe_serial; pr[1] = (float)probe_total; pr[2] = (float)(it + 1u); pr[3] = (float)items;
+#endif
     }
 }
-hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s, uint32_t *lds_blocks_used)
+// 16 wavefronts: the compute unit is the workgroup's own.  8 wavefronts: two workgroups share one -- the cap on the registers (four waves per SIMD,
+// at most 128 VGPRs) is what lets the second one in; without it the compiler may take up to 256 and one workgroup would fill the compute unit again.
+template <bool kTables>
+__global__ __launch_bounds__(kLoopLanes) PR_LOOP_CU_ATTR void icp_loop_cu_kernel(IcpBatch b, SceneProjPacked scene) { icp_loop_cu_body<kLoopWaves, kTables>(b, scene); }
+template <bool kTables>
+__global__ __launch_bounds__(kLoopLanes / 2) __attribute__((amdgpu_waves_per_eu(4, 4))) void icp_loop_cu8_kernel(IcpBatch b, SceneProjPacked scene) { icp_loop_cu_body<kLoopWaves / 2, kTables>(b, scene); }
+hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s, LoopCuForm form, LoopCuUsed *used)
 {
-    if (lds_blocks_used) *lds_blocks_used = 0;
+    if (used) *used = LoopCuUsed{ 0, 0, 0 };
     if (n_poses == 0 || b.nblk == 0) return hipSuccess;
-    size_t lds = icp_loop_cu_lds_bytes(b.nblk);
-    if (lds > kLoopCuLdsBudget || b.robust_kind != PR_ROBUST_NONE) return hipErrorInvalidValue;   // (the caller keeps such batches on the multi-launch loop)
-    // b.lds_blocks is the caller's wish; what is launched never exceeds what icp_loop_cu_lds_blocks allows, and falls to none (the kernel
-    // as it was) when the device refuses dynamic LDS beyond 64 KiB
+    const size_t rows = icp_loop_cu_lds_bytes(b.nblk);
+    if (rows > kLoopCuLdsBudget || b.robust_kind != PR_ROBUST_NONE) return hipErrorInvalidValue;   // (the caller keeps such batches on the multi-launch loop)
+    const uint32_t waves = form.waves == kLoopWaves / 2 ? kLoopWaves / 2 : kLoopWaves;
+    // b.lds_blocks is the caller's wish; what is launched never exceeds what icp_loop_cu_layout allows, and falls to none -- and the tables to
+    // memory where they do not fit the 64 KiB either -- when the device refuses dynamic LDS beyond 64 KiB
+    // the tables by the library's choice (form.tables < 0): in LDS for the 8-wave form, in memory for the 16-wave one (pr_tuning.h has the runs)
+    const bool want_tables = form.tables < 0 ? waves != kLoopWaves : form.tables != 0;
     IcpBatch bb = b;
-    const uint32_t most = icp_loop_cu_lds_blocks(b.nblk, b.steps, -1);
-    if (bb.lds_blocks > most) bb.lds_blocks = most;
-    const size_t image = (size_t)bb.lds_blocks * b.steps * kPointsPerStep * sizeof(pr_vec3);
-    const auto fn = icp_loop_cu_kernel<SceneProjPacked>;
-    if (lds + image > kLoopCuLdsBudget && !lds_opt_in(reinterpret_cast<const void *>(fn), 0, (uint32_t)kLoopCuLdsTotal)) bb.lds_blocks = 0;
-    if (bb.lds_blocks) lds += image;
-    if (lds_blocks_used) *lds_blocks_used = bb.lds_blocks;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(icp_loop_cu_kernel<SceneProjPacked>), dim3(n_poses), dim3(kLoopLanes), lds, s, bb, sc);
-    return hipGetLastError();
+    uint32_t fixed = 0;
+    bb.lds_blocks = icp_loop_cu_layout(b.nblk, b.steps, (int)(b.lds_blocks < b.nblk ? b.lds_blocks : b.nblk), want_tables ? sc.width : 0u, want_tables ? sc.height : 0u, waves, &fixed);
+    const size_t block = (size_t)b.steps * kPointsPerStep * sizeof(pr_vec3);
+    bool tables = fixed > rows;
+    const void *fn = waves == kLoopWaves ? (tables ? reinterpret_cast<const void *>(icp_loop_cu_kernel<true>) : reinterpret_cast<const void *>(icp_loop_cu_kernel<false>))
+                                         : (tables ? reinterpret_cast<const void *>(icp_loop_cu8_kernel<true>) : reinterpret_cast<const void *>(icp_loop_cu8_kernel<false>));
+    const int slot = waves == kLoopWaves ? (tables ? 3 : 0) : (tables ? 5 : 4);
+    const size_t limit = waves == kLoopWaves ? kLoopCuLdsTotal : kLoopCuLdsTotal / 2;
+    if (fixed + bb.lds_blocks * block > kLoopCuLdsBudget && !lds_opt_in(fn, slot, (uint32_t)limit)) {
+        bb.lds_blocks = 0;
+        if (fixed > kLoopCuLdsBudget) {                          // (the form without tables is another kernel, and fits without asking)
+            tables = false; fixed = (uint32_t)rows;
+            fn = waves == kLoopWaves ? reinterpret_cast<const void *>(icp_loop_cu_kernel<false>) : reinterpret_cast<const void *>(icp_loop_cu8_kernel<false>);
+        }
+    }
+    const size_t lds = fixed + bb.lds_blocks * block;
+    if (used) *used = LoopCuUsed{ bb.lds_blocks, waves, tables ? fixed - (uint32_t)rows : 0u };
+    void *args[] = { &bb, const_cast<SceneProjPacked *>(&sc) };
+    return hipLaunchKernel(fn, dim3(n_poses), dim3(waves * 64u), args, lds, s);
 }
 
 __global__ __launch_bounds__(64) void icp_finalize_kernel(const float *__restrict__ partial, const PoseMeta *__restrict__ meta,

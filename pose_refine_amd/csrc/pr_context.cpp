@@ -58,6 +58,8 @@ std::atomic<uint64_t> g_tight_batches{ 0 };
 std::atomic<uint64_t> g_band_batches{ 0 };
 std::atomic<uint64_t> g_resident_batches{ 0 };
 std::atomic<uint32_t> g_loop_lds_blocks{ 0 };
+std::atomic<uint32_t> g_loop_waves{ 0 };
+std::atomic<uint32_t> g_loop_lds_tables{ 0 };
 std::atomic<uint32_t> g_nn_lds_nodes{ 0 }, g_nn_stack_depth{ 0 };
 std::atomic<uint64_t> g_nn_pass_launches{ 0 };
 Options opt;
@@ -311,6 +313,8 @@ int pr_set_option(const char *name, int value)
     else if (n == "fused_solve") opt.fused_solve = value ? 1 : 0;
     else if (n == "resident_loop") opt.resident_loop = value ? 1 : 0;
     else if (n == "loop_lds_blocks") opt.loop_lds_blocks = std::max(-1, value);
+    else if (n == "loop_lds_tables") opt.loop_lds_tables = std::min(1, std::max(-1, value));
+    else if (n == "loop_waves") { if (value != 0 && value != 8 && value != 16) { set_error("loop_waves must be 0, 8 or 16"); return PR_ERR_INVALID; } opt.loop_waves = value; }
     else if (n == "sub_batch") opt.sub_batch = std::min(32768, std::max(32, value));    // (the hypothesis index is the y dimension of the launches)
     else if (n == "overlap_pass") opt.overlap_pass = std::max(-1, value);
     else if (n == "pose_groups") opt.pose_groups = std::min(4, std::max(0, value));
@@ -364,6 +368,10 @@ int pr_get_option(const char *name, int *value)
     else if (n == "resident_loop") *value = opt.resident_loop;
     else if (n == "loop_lds_blocks") *value = opt.loop_lds_blocks;
     else if (n == "stat_loop_lds_blocks") *value = (int)g_loop_lds_blocks.load();     // read-only
+    else if (n == "loop_lds_tables") *value = opt.loop_lds_tables;
+    else if (n == "stat_loop_lds_tables") *value = (int)g_loop_lds_tables.load();     // read-only
+    else if (n == "loop_waves") *value = opt.loop_waves;
+    else if (n == "stat_loop_waves") *value = (int)g_loop_waves.load();               // read-only
     else if (n == "stat_nn_lds_nodes") *value = (int)g_nn_lds_nodes.load();           // read-only
     else if (n == "stat_nn_stack_depth") *value = (int)g_nn_stack_depth.load();       // read-only
     else if (n == "stat_nn_pass_launches") *value = (int)(g_nn_pass_launches.load() & 0x7fffffffull);   // read-only (wraps: tests take differences)

@@ -92,6 +92,12 @@ struct SceneProjPacked {
     const float4 *rec;
     const float *colf, *rowf;   // colf[x] = ((float)(x + tl_x) - cx)/fx, rowf[y] = ((float)(y + tl_y) - cy)/fy
 };
+// the same scene with the two tables copied into the workgroup's LDS (icp_loop_cu_kernel, option "loop_lds_tables"): a type of its own, built inside
+// the kernel from its LDS array, so that after inlining the table loads of gather_issue are LDS loads at every call site and never flat ones
+struct SceneProjPackedLds {
+    SceneProjPacked pk;         // pk.colf / pk.rowf are not read through this type
+    const float *colf, *rowf;   // LDS: pk.width and pk.height floats
+};
 // kd-tree scene: reference arrays + the traversal structure derived from them (build_nn_accel)
 struct SceneNNDev {
     float max_dist_diff;
@@ -367,7 +373,13 @@ size_t icp_loop_cu_lds_bytes(uint32_t nblk);
 // *lds_blocks_used receives the number the launch really ran with: 0 when the device refuses the LDS opt-in.
 constexpr size_t kLoopCuLdsTotal = 160u << 10;
 uint32_t icp_loop_cu_lds_blocks(uint32_t nblk, uint32_t steps, int cap);
-hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s, uint32_t *lds_blocks_used = nullptr);
+// The full layout (options "loop_lds_tables", "loop_waves"): rows and header, the scene's colf / rowf tables (width + height floats), then whole
+// blocks, within 160 KiB for a 16-wave workgroup and 80 KiB for an 8-wave one, of which two share a compute unit.  Returns the blocks, *fixed_bytes
+// = rows + header + tables granted (a width and height of 0: no tables asked for).  Tables first, whole blocks after.
+uint32_t icp_loop_cu_layout(uint32_t nblk, uint32_t steps, int cap, uint32_t width, uint32_t height, uint32_t waves, uint32_t *fixed_bytes);
+struct LoopCuForm { uint32_t waves; int tables; };                  // wavefronts per workgroup (16 or 8); tables in LDS: 0 no, 1 yes, -1 the library's choice
+struct LoopCuUsed { uint32_t lds_blocks, waves, table_bytes; };     // what the launch really ran with
+hipError_t launch_icp_loop_cu_proj_packed(const IcpBatch &b, const SceneProjPacked &sc, uint32_t n_poses, hipStream_t s, LoopCuForm form, LoopCuUsed *used = nullptr);
 // The in-pass kd-tree walks stage sc.lds_nodes leading nodes in dynamic LDS beside icp_pass_kernel's kPassStaticLds static bytes.  The stack
 // walks stay within 64 KiB by nn_route's cap.  The stackless walks (plain and robust) may ask for up to kNNLdsNodesMax 16-byte entries:
 // beyond kNNLdsNodesPlain the launcher opts the kernel in per device, and where the device refuses it stages kNNLdsNodesPlain and runs.

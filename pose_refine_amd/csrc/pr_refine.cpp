@@ -1112,7 +1112,7 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
     b.cloud = sl.cloud.as<pr_vec3>(); b.partial = sl.partial.as<float>(); b.nblk = pl.nblk; b.grid_x = pl.grid_x; b.steps = pl.steps;
     if (nn_prev) nn_carve(b, nn_prev, nl);
     const uint32_t last_pass = (uint32_t)job.crit.max_iteration;
-    // Option resident_loop: every pass of the sub-batch in ONE launch on the slot's stream, a 1024-lane workgroup per hypothesis (icp_loop_cu_kernel) --
+    // Option resident_loop: every pass of the sub-batch in ONE launch on the slot's stream, a 1024- or 512-lane workgroup per hypothesis (icp_loop_cu_kernel) --
     // no pose groups, no arrival counters, no partial sums in memory.  Packed projective scene and fused device solve only (this path carries no
     // robust weight); a timed batch keeps its per-launch events, and a plan whose blocks would not fit the kernel's LDS keeps the multi-launch loop.
     // The other slot's render is released AHEAD of the launch and runs beside the loop (PR_RESIDENT_RELEASE_AHEAD, pr_tuning.h: behind it measured
@@ -1127,9 +1127,14 @@ int AsyncBatch::sub_batch(uint32_t q0, uint32_t nq)
         // Option loop_lds_blocks: the head of every cloud stays in the workgroup's LDS over the loop.  Those points of sl.cloud are stale afterwards,
         // and nobody looks: the slot's cloud buffer is written by the emit above and read by this launch only (the next sub-batch's emit overwrites it).
         b.lds_blocks = prk::icp_loop_cu_lds_blocks(pl.nblk, pl.steps, opt.loop_lds_blocks);
-        uint32_t lds_blocks_used = 0;
-        HIP_TRY(prk::launch_icp_loop_cu_proj_packed(b, sc.pk, nq, st, &lds_blocks_used));
-        g_loop_lds_blocks.store(lds_blocks_used);
+        // Option loop_waves: 8-wave workgroups, two to a compute unit, only for a sub-batch that fills the chip (one hypothesis per compute unit
+        // at least); a smaller one keeps the sixteen wavefronts and their lower latency.  Option loop_lds_tables: colf / rowf in LDS.
+        const uint32_t waves = opt.loop_waves ? (uint32_t)opt.loop_waves : (nq >= (uint32_t)g->n_cus ? PR_LOOP_CU_FULL_CHIP_WAVES : 16u);
+        prk::LoopCuUsed used{};
+        HIP_TRY(prk::launch_icp_loop_cu_proj_packed(b, sc.pk, nq, st, prk::LoopCuForm{ waves, opt.loop_lds_tables }, &used));
+        g_loop_lds_blocks.store(used.lds_blocks);
+        g_loop_waves.store(used.waves);
+        g_loop_lds_tables.store(used.table_bytes);
 #if !PR_RESIDENT_RELEASE_AHEAD
         if (release) { HIP_TRY(hipEventRecord(sl.progress, st)); sl.progress_valid = true; }
 #endif
@@ -1809,5 +1814,17 @@ int pr_refine_wait(int slot)
     trace_mark("pr_refine_wait: exit");
     return rc;
 }
+
+#if PR_LOOP_CU_PROBE
+// measuring builds only (pr_tuning.h): four floats per hypothesis that the resident loop of the slot's last sub-batch left in its partial buffer
+int pr_loop_probe_read(int slot, float *out, uint32_t n_poses)
+{
+    PR_ENTER();
+    if (slot < 0 || slot >= kSlots || !out) return PR_ERR_INVALID;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, g->slots[slot].partial.as<float>(), sizeof(float) * 4 * n_poses, hipMemcpyDeviceToHost));
+    return PR_OK;
+}
+#endif
 
 }  // extern "C"

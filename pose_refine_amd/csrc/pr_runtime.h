@@ -125,6 +125,8 @@ extern WriteLog g_writes;
 extern std::atomic<uint64_t> g_tight_batches;     // asynchronous batches whose pixel boxes came from pose_tight_box_kernel (process-wide; read-only option "stat_tight_batches": tests tell the tight path from the loose one by it)
 extern std::atomic<uint64_t> g_band_batches;      // asynchronous batches whose depth boxes were banded (option box_bands; read-only option "stat_band_batches": tests tell the banded path from the row-major one by it)
 extern std::atomic<uint64_t> g_resident_batches;  // asynchronous sub-batches whose whole loop ran as one launch (option resident_loop; read-only option "stat_resident_batches": tests tell the resident route from the multi-launch one by it)
+extern std::atomic<uint32_t> g_loop_waves;        // wavefronts per workgroup of the most recent resident launch (option loop_waves; read-only option "stat_loop_waves")
+extern std::atomic<uint32_t> g_loop_lds_tables;   // bytes of colf / rowf that the most recent resident launch kept in LDS, 0 when it read them from memory (option loop_lds_tables; read-only option "stat_loop_lds_tables")
 extern std::atomic<uint32_t> g_loop_lds_blocks;   // blocks of every cloud's head that the most recent resident launch kept in LDS (option loop_lds_blocks; read-only option "stat_loop_lds_blocks": tests tell a launch with an LDS image from one that quietly ran without)
 // what the most recent in-pass kd-tree launch (launch_icp_pass_nn: enqueued, or replayed in a cached graph) ran with, after nn_route and the launcher's own limits:
 // nodes staged in LDS and stack entries per lane, 0 = the stackless walk (read-only options "stat_nn_lds_nodes", "stat_nn_stack_depth": tests tell a walk that
@@ -165,7 +167,9 @@ struct Options {
                                      // they do not; kd-tree scenes: pass 0)
     int sub_batch = 512;             // asynchronous fused path: hypotheses per sub-batch (cache residency of the clouds)
     int fused_solve = 1;             // PR_SOLVE_DEVICE: the workgroup delivering a hypothesis' last partial sum also runs its finalize + solve (no second launch per iteration)
-    int resident_loop = 1;           // asynchronous fused path, packed projective scene, fused device solve, untimed: all passes of a sub-batch in ONE launch, a 1024-lane workgroup per hypothesis (icp_loop_cu_kernel, icp_pass.hip); 0 = the multi-launch loop everywhere.  Same bytes either way (profiles/resident_cu/README.md has the measurement)
+    int resident_loop = 1;           // asynchronous fused path, packed projective scene, fused device solve, untimed: all passes of a sub-batch in ONE launch, a workgroup per hypothesis (icp_loop_cu_kernel, 1024 lanes, or icp_loop_cu8_kernel, 512 lanes and two to a compute unit, for a sub-batch of at least one hypothesis per compute unit: option loop_waves; icp_pass.hip); 0 = the multi-launch loop everywhere.  Same bytes either way (profiles/resident_cu/README.md has the measurement)
+    int loop_lds_tables = -1;        // resident loop: the scene's colf / rowf tables (width + height floats) copied once per hypothesis into the workgroup's LDS behind rows and header and ahead of the cloud's blocks, so that two of the three gathers per point and pass are LDS reads; 0 = read from memory (the kernel without the option), 1 = in LDS whenever they fit beside rows and header, -1 = the library's choice: in LDS for the 8-wave form, in memory for the 16-wave one.  Same bytes either way (profiles/loop_share/README.md has the measurement)
+    int loop_waves = 0;              // resident loop: wavefronts per workgroup, 16 (one workgroup per compute unit) or 8 (two); 0 = the library's choice: 16 for a sub-batch with fewer hypotheses than the device has compute units, PR_LOOP_CU_FULL_CHIP_WAVES (pr_tuning.h) from there on.  Same bytes either way
     int loop_lds_blocks = -1;        // resident loop: blocks of every cloud's head kept in the workgroup's LDS over the whole loop instead of moving through memory every pass; -1 = as many as fit in the compute unit's 160 KiB behind rows and header (four of 3072 points), 0 = none (every instruction path of a pass is then the one without the option), n > 0 = at most n.  Same bytes either way (profiles/loop_lds/README.md has the measurement)
     int use_graph = 1;             // PR_SOLVE_DEVICE, single pose group only (the runtime serialises the branches of a captured multi-stream
                                      // graph, which forfeits the overlap): capture the whole iteration loop in a hipGraph and replay it

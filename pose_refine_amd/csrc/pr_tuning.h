@@ -21,6 +21,21 @@
 // to 730 MB per launch: HALF the traffic buys 3 % of the time.  The 32.5 against 38.4 us of the multi-launch pass without its stores (below) did not carry over to
 // this kernel: its pass is not the sum of its memory traffic.  What is left of a pass (29.6 us against a VALU floor of about 11) is then the scene gathers' rate and the wait for the slowest of
 // sixteen wavefronts -- read from the earlier counters (TA busy 64 %, profiles/r02), not measured again here.  profiles/loop_lds/README.md)
+// (Options loop_waves and loop_lds_tables, profiles/loop_share/README.md.  Same box, five forms alternating, five 100-step runs each, poses/s:
+//   parent commit                                      338.9-339.9 k
+//   16 waves, tables in memory (the parent's kernel)   338.6-340.7 k   with the parent
+//   16 waves, tables in LDS                            340.1-342.2 k   every run above the parent's, medians 0.5 % apart = 1.7 x the parent's spread: under the rule of two spreads, not the default
+//   8 waves, tables in memory                          354.4-355.0 k   +4.5 %: kept as loop_waves = 8, loop_lds_tables = 0
+//   8 waves, tables in LDS                             358.3-360.8 k   +6.0 %: kept, the library's choice for a sub-batch that fills the chip
+// (the headline's plan is 33 blocks, from its largest pixel box: 17 152 bytes of rows and header, three blocks of 3072 points resident at 16 waves and one at
+// 8, with or without the 4480 bytes of tables -- on this plan the tables cost no block.)
+// Between the barriers of a pass wavefront 0 works alone for 4.5 us of 26.7 (17 %, the probe below); a second hypothesis on the compute unit uses it.)
+#ifndef PR_LOOP_CU_FULL_CHIP_WAVES
+#define PR_LOOP_CU_FULL_CHIP_WAVES 8u                           // option loop_waves = 0: wavefronts per workgroup of icp_loop_cu_kernel for a sub-batch with at least one hypothesis per compute unit (8: two workgroups share a compute unit; 16: one)
+#endif
+#ifndef PR_LOOP_CU_PROBE
+#define PR_LOOP_CU_PROBE 0                                      // 1: wavefront 0 of icp_loop_cu_kernel sums wall-clock ticks between the two barriers of a pass and over whole passes and leaves them per hypothesis in the slot's partial buffer (pr_loop_probe_read, tools/loop_share.py).  A measuring build, never the shipped one
+#endif
 #if PR_LOOP_CU_WAVES
 #define PR_LOOP_CU_ATTR __attribute__((amdgpu_waves_per_eu(PR_LOOP_CU_WAVES, PR_LOOP_CU_WAVES)))
 #else

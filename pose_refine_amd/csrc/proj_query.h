@@ -138,6 +138,23 @@ __device__ __forceinline__ bool gather_finish(const SceneProjPacked &s, bool in_
     c.dx = g.b0 * dz; c.dy = g.b1 * dz; c.dz = dz; c.nx = g.a0; c.ny = g.a1; c.nz = g.a2;
     return true;
 }
+// The packed scene with colf / rowf in LDS: the same pixel, the same indices (an out-of-image point reads entry 0 of both tables and discards it), the
+// same record from memory -- only the two table words come from the workgroup's copy.  Banks: adjacent lanes hold adjacent pixels of the rendered
+// hypothesis, so colf[px] falls on consecutive words (conflict-free within a row of the box) and rowf[py] is one address for most of a wavefront
+// (a broadcast); a wavefront that spans a row change reads two addresses of rowf.
+__device__ __forceinline__ bool gather_issue(const SceneProjPackedLds &s, float sx, float sy, float sz, bool live, Gathered &g)
+{
+    uint32_t idx = 0u; int px = 0, py = 0;
+    const bool in_img = live && proj_pixel(sx, sy, sz, s.pk.fx, s.pk.fy, s.pk.cx, s.pk.cy, s.pk.tlx, s.pk.tly, s.pk.width, s.pk.height, idx, px, py);
+    const float4 r = ld_off<float4>(s.pk.rec, idx * 16u);                              // {nx, ny, nz, z}
+    g.a0 = r.x; g.a1 = r.y; g.a2 = r.z; g.a3 = r.w;
+    g.b0 = ld_off<float>(s.colf, (uint32_t)px * 4u); g.b1 = ld_off<float>(s.rowf, (uint32_t)py * 4u); g.b2 = 0.0f;
+    return in_img;
+}
+__device__ __forceinline__ bool gather_finish(const SceneProjPackedLds &s, bool in_img, float sz, const Gathered &g, Corr &c)
+{
+    return gather_finish(s.pk, in_img, sz, g, c);
+}
 // never instantiated for the kd-tree scenes (they have their own loops)
 __device__ __forceinline__ bool gather_issue(const SceneNNDev &, float, float, float, bool, Gathered &) { return false; }
 __device__ __forceinline__ bool gather_finish(const SceneNNDev &, bool, float, const Gathered &, Corr &) { return false; }

@@ -1246,7 +1246,7 @@ int  pr_segment_roi(const pr_segment *segment, size_t width, size_t height, uint
  * kernel, one stream synchronise and one pinned read-back of the counts, no hipMemcpy on the path; the same frame gives the same bytes on every call.
  * pr_depth_fuse_host / pr_depth_filter_host: the same over host arrays, from the same shared code: the CPU twins the device is held to.
  * Not offered: a bilateral or mean filter (values would no longer be input values), speckle removal (pr_scene_segments_dev with min_pixels does
- * that), an asynchronous form, fusion of frames from different views. */
+ * that), an asynchronous form.  Frames from different views are brought into one view by pr_depth_reproject_dev (below), not here. */
 #define PR_DEPTH_FUSE_MAX           8
 #define PR_DEPTH_FILTER_MAX_RADIUS  2
 #define PR_DEPTH_UNMEASURED  0
@@ -1277,6 +1277,98 @@ int  pr_depth_filter_dev(const void *depth_in_dev, int depth_is_i32, size_t widt
                          void *depth_out_dev, uint8_t *flags_dev_out /* may be NULL */, pr_depth_filter_counts *counts_host /* may be NULL */);
 int  pr_depth_filter_host(const void *depth_in, int depth_is_i32, size_t width, size_t height, const pr_depth_filter_params *params,
                           void *depth_out, uint8_t *flags_out /* may be NULL */, pr_depth_filter_counts *counts_out /* may be NULL */);
+
+/* ---- reprojection: depth frames of other cameras and bare point clouds into the depth frame of one target camera ---------------------------
+ * Every stage above takes a depth frame of ONE camera.  A rig of calibrated depth cameras, a depth camera beside the colour camera in whose frame
+ * a detector's boxes and masks live, and a scanner or LiDAR that delivers points have no such frame.  This stage makes it: up to
+ * PR_REPROJECT_MAX_SOURCES sources, each a depth frame of another camera or a bare cloud, go sample by sample through a rigid transform and a
+ * pinhole into a z-buffer of the target camera.  The output is a depth frame of the caller's depth type and goes unchanged into everything
+ * that takes one.  All float32 arithmetic is without contraction, with correctly rounded division; from the depth and the footprint on, integers
+ * only; every output byte is fixed by this text, on the device and on the host.
+ *   target: width x height pixels, 1 <= width, height <= 65535 and width * height <= 2^26; intrinsics fx, fy, cx, cy (finite, fx, fy > 0); depth
+ *     type uint16 or int32 (depth_is_i32).  A pixel's index is y * width + x; its centre is at its integer coordinates (pr_depth2cloud's rule).
+ *   sources: a HOST table of 1 <= n_sources <= PR_REPROJECT_MAX_SOURCES pr_reproject_source records (they travel as kernel arguments; two may share a
+ *     pointer).  kind PR_SRC_DEPTH_U16 / PR_SRC_DEPTH_I32: data = width x height depths (the target's limits), intrinsics fx, fy, cx, cy (finite,
+ *     fx, fy > 0), n_points = 0.  kind PR_SRC_CLOUD: data = 1 <= n_points <= 2^26 pr_vec3 in metres; width, height and the intrinsics are not read.
+ *     data is aligned to its element (2 or 4 bytes).  T: row-major 4 x 4 float32, source camera to target camera, finite, its last row exactly
+ *     (0, 0, 0, 1), the translation in metres.  reserved = 0.
+ *   sample of a frame source, pixel (x, y): D0 = the depth as unsigned 32-bit, a non-positive int32 is 0.  D0 == 0: no sample.  D0 > 2^28 - 1:
+ *     the sample is counted `range`.  Otherwise z = (float)D0 / 1000.0f, p = (((float)x - cx) / fx * z, ((float)y - cy) / fy * z, z): the
+ *     expression of pr_depth2cloud, so the cloud it makes of the frame gives the same samples bit for bit.
+ *   sample of a cloud source: p = the point; a component that is not finite: counted `invalid`.
+ *   transform: q.c = ((T[c][0] * p.x + T[c][1] * p.y) + T[c][2] * p.z) + T[c][3] for c = 0, 1, 2.  Counted `invalid` unless q is finite and q.z > 0.
+ *   depth: df = floorf(q.z * 1000.0f + 0.5f).  Counted `range` unless lo <= df <= hi, compared exactly (df is an integer value or +inf), with
+ *     lo = max(1, min_mm) and hi = the smallest of max_mm (when non-zero), 65535 for a uint16 output and 2^28 - 1.  d = (uint32_t)df.
+ *   footprint: splat s in { 1, 2, 3 } is the side of the square of pixels a sample writes; h = 0.5f * (float)(2 - s), exactly 0.5, 0 or -0.5.
+ *     u = q.x / q.z * fx + cx, v = q.y / q.z * fy + cy (the target's intrinsics); x0f = floorf(u + h), y0f = floorf(v + h).  Counted `outside` unless
+ *     x0f > -4.0f && x0f < (float)width and likewise in y, compared in float before any conversion (a NaN fails).  The square is x0 .. x0 + s - 1
+ *     by y0 .. y0 + s - 1, clipped to the frame; an empty intersection is counted `outside`.  s = 1: the nearest pixel; s = 2: the four pixels
+ *     around the continuous position; s = 3: the nearest pixel and its 8 neighbours.
+ *   z-buffer: key = (d << 3) | source_index (unsigned 32-bit); KEY[p] = the minimum over every sample whose square holds p: the nearest surface,
+ *     the lowest source index on a tie.  A minimum depends on no order of sources, samples or launches.  Z[p] = KEY[p] >> 3, 0 where no sample
+ *     landed; S[p] = KEY[p] & 7.
+ *   visibility (optional; it takes out background seen through the gaps between foreground samples, which a sparse cloud or a magnifying
+ *     reprojection leaves and which pr_depth_filter_dev cannot remove, those pixels being measured): tol(d) = tol_mm + floor(d * tol_permille / 1000)
+ *     (depth conditioning's).  front(p) = the number of pixels q != p inside the frame with |qx - px| <= occl_radius, |qy - py| <= occl_radius,
+ *     Z[q] != 0 and Z[q] + tol(Z[p]) < Z[p].  A measured pixel is hidden when occl_min_front > 0 and front(p) >= occl_min_front.  The stage reads
+ *     only Z, over the whole frame.
+ *   out[p] = Z[p] where Z[p] != 0 and p is not hidden, else 0 (a hidden pixel is a hole for pr_depth_filter_dev's fill).
+ *   source_dev_out (one uint8 per pixel, may be NULL): S[p] of a kept pixel, PR_REPROJECT_HIDDEN of a hidden one, PR_REPROJECT_NONE where nothing
+ *     landed.
+ *   pr_reproject_counts (counts_host, may be NULL): per source samples, invalid, range, outside, drawn = samples - invalid - range - outside, and
+ *     won = the kept pixels with that S; per frame covered (Z != 0), hidden, kept = covered - hidden; entries of sources beyond n_sources and
+ *     reserved = 0.
+ * pr_reproject_describe (host only): fills and checks the parameters.  PR_ERR_INVALID with nothing written: splat outside 1 .. 3; min_mm, max_mm or
+ * tol_mm above 2^31 - 1; max_mm != 0 and min_mm > max_mm; tol_permille > 1000; occl_radius > PR_REPROJECT_MAX_RADIUS; occl_min_front != 0 with
+ * occl_radius == 0 or occl_min_front > (2 occl_radius + 1)^2 - 1; a null out.  Every entry point checks its parameters against these rules (and
+ * reserved == 0).
+ * pr_depth_reproject_dev: PR_ERR_INVALID, with nothing written and before any device is touched, for a null table, entry pointer, parameter block
+ * or output; counts, sizes or an alignment outside the limits above; an unknown kind; intrinsics that are not finite or not positive; a T that is
+ * not finite or whose last row is not (0, 0, 0, 1); depth_out_dev equal to a source pointer.  Synchronous, on the calling thread's context:
+ * three launches (the library-owned key plane set to 0xFFFFFFFF and the control words cleared; the scatter, an atomic minimum per pixel of a
+ * sample's square; the resolve, a workgroup per 64 x 16 tile), one stream synchronise and one pinned read-back of the counts, which the tile that
+ * finishes last writes; no hipMemset or hipMemcpy on the path.  The same call gives the same bytes every time.
+ * pr_depth_reproject_host: the same over host arrays, from the same shared code: the CPU twin the device is held to.
+ * Order of use: condition every source in its own view first (pr_depth_filter_dev with the flying-pixel stage: a flying pixel reprojected into
+ * another view becomes a streak), reproject, then pr_depth_filter_dev with fill_min on the result closes rounding gaps and hidden pixels.
+ * Not offered: triangulated (meshed) reprojection, lens distortion, colour, an asynchronous form. */
+#define PR_REPROJECT_MAX_SOURCES  8
+#define PR_REPROJECT_MAX_RADIUS   2
+#define PR_SRC_DEPTH_U16  0
+#define PR_SRC_DEPTH_I32  1
+#define PR_SRC_CLOUD      2
+#define PR_REPROJECT_HIDDEN  254
+#define PR_REPROJECT_NONE    255
+typedef struct {
+    const void *data;                  /* the frame's depths or the cloud's pr_vec3 (device memory for _dev, host memory for _host)   */
+    uint64_t n_points;                 /* a cloud's points; 0 for a frame                                                             */
+    uint32_t kind;                     /* PR_SRC_*                                                                                    */
+    uint32_t width, height;            /* a frame's size; not read for a cloud                                                        */
+    uint32_t reserved;
+    float    fx, fy, cx, cy;           /* a frame's intrinsics; not read for a cloud                                                  */
+    float    T[16];                    /* row-major, source camera to target camera                                                   */
+} pr_reproject_source;         /* 112 B */
+typedef struct {
+    uint32_t splat;                    /* 1 .. 3: the side of a sample's square                                                       */
+    uint32_t min_mm, max_mm;           /* the gate on the reprojected depth; max_mm == 0: no upper gate but the depth type's          */
+    uint32_t tol_mm, tol_permille;     /* tol(d) = tol_mm + floor(d * tol_permille / 1000)                                            */
+    uint32_t occl_radius;              /* 0 .. 2: the visibility window's half-width                                                  */
+    uint32_t occl_min_front;           /* 0 = off; else 1 .. (2 occl_radius + 1)^2 - 1 nearer neighbours that hide a pixel            */
+    uint32_t reserved;
+} pr_reproject_params;         /* 32 B */
+typedef struct {
+    struct { uint32_t samples, invalid, range, outside, drawn, won, reserved[2]; } source[PR_REPROJECT_MAX_SOURCES];      /* 32 B each */
+    uint32_t covered, hidden, kept;
+    uint32_t reserved[5];
+} pr_reproject_counts;         /* 288 B */
+int  pr_reproject_describe(uint32_t splat, uint32_t min_mm, uint32_t max_mm, uint32_t tol_mm, uint32_t tol_permille, uint32_t occl_radius,
+                           uint32_t occl_min_front, pr_reproject_params *out);
+int  pr_depth_reproject_dev(const pr_reproject_source *sources /* host table, device data pointers */, uint32_t n_sources, size_t width, size_t height,
+                            float fx, float fy, float cx, float cy, int depth_is_i32, const pr_reproject_params *params, void *depth_out_dev,
+                            uint8_t *source_dev_out /* may be NULL */, pr_reproject_counts *counts_host /* may be NULL */);
+int  pr_depth_reproject_host(const pr_reproject_source *sources /* host table, host data pointers */, uint32_t n_sources, size_t width, size_t height,
+                             float fx, float fy, float cx, float cy, int depth_is_i32, const pr_reproject_params *params, void *depth_out,
+                             uint8_t *source_out /* may be NULL */, pr_reproject_counts *counts_out /* may be NULL */);
 
 /* ---- scenes from point clouds: exact k nearest neighbours over the scene's own kd-tree, and a PCA normal per point -------------------------
  * Every other preparation starts from a depth frame; a sensor that delivers points (a scanner, a LiDAR, a merged or cropped cloud) has no pixel
@@ -1320,7 +1412,8 @@ int  pr_depth_filter_host(const void *depth_in, int depth_is_i32, size_t width, 
  * pr_ppf_cloud_points_dev: the scene sample of the PPF vote from a kd-tree scene -- the points 0, stride, 2 stride, ... of tree order whose
  * normal has a non-zero component, in index order, point = pcd * 1000.0f per component, normal as it is.  Room for PR_PPF_MAX_SCENE_POINTS;
  * more than that: PR_ERR_INVALID with nothing emitted and *n_out = the number found (raise the stride).  stride >= 1.
- * Not offered: voxel down-sampling or merging of clouds, transforms between sensor frames, radius-only (unbounded k) neighbourhoods. */
+ * Not offered: voxel down-sampling, radius-only (unbounded k) neighbourhoods.  Clouds are merged, and moved between sensor frames, on their way
+ * into a depth frame by pr_depth_reproject_dev (above); a merged cloud as such is not offered. */
 #define PR_KNN_MAX_K  32
 #define PR_KNN_NONE   0xFFFFFFFFu
 typedef struct {

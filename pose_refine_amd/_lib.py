@@ -175,6 +175,38 @@ class DepthFilterCounts(C.Structure):
 assert C.sizeof(DepthFilterParamsDesc) == 32 and C.sizeof(DepthFilterCounts) == 32
 
 
+# pr_reproject_source: one source of a pr_depth_reproject_* call; pr_reproject_params: what pr_reproject_describe fills; pr_reproject_counts: what became of the samples
+REPROJECT_MAX_SOURCES, REPROJECT_MAX_RADIUS = 8, 2                          # PR_REPROJECT_MAX_SOURCES, PR_REPROJECT_MAX_RADIUS
+SRC_DEPTH_U16, SRC_DEPTH_I32, SRC_CLOUD = range(3)                          # PR_SRC_*: a source's kind
+REPROJECT_HIDDEN, REPROJECT_NONE = 254, 255                                 # PR_REPROJECT_*: the source image's codes beside a source index
+
+
+class ReprojectSourceDesc(C.Structure):
+    """pr_reproject_source: a depth frame of another camera or a bare cloud, and its rigid transform into the target camera."""
+    _fields_ = [("data", C.c_void_p), ("n_points", C.c_uint64), ("kind", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("reserved", C.c_uint32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("T", C.c_float * 16)]
+
+
+class ReprojectParamsDesc(C.Structure):
+    """pr_reproject_params: the footprint, the gate on the reprojected depth, the tolerance and the visibility window (pr_reproject_describe checks and fills it)."""
+    _fields_ = [("splat", C.c_uint32), ("min_mm", C.c_uint32), ("max_mm", C.c_uint32), ("tol_mm", C.c_uint32), ("tol_permille", C.c_uint32),
+                ("occl_radius", C.c_uint32), ("occl_min_front", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ReprojectSourceCounts(C.Structure):
+    """One source's entry of pr_reproject_counts."""
+    _fields_ = [("samples", C.c_uint32), ("invalid", C.c_uint32), ("range", C.c_uint32), ("outside", C.c_uint32), ("drawn", C.c_uint32), ("won", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class ReprojectCounts(C.Structure):
+    """pr_reproject_counts: per source what became of its samples and the pixels it won; per frame the covered, hidden and kept pixels."""
+    _fields_ = [("source", ReprojectSourceCounts * 8), ("covered", C.c_uint32), ("hidden", C.c_uint32), ("kept", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+assert C.sizeof(ReprojectSourceDesc) == 112 and C.sizeof(ReprojectParamsDesc) == 32 and C.sizeof(ReprojectCounts) == 288
+
+
 # pr_cloud_params: what pr_cloud_describe fills; pr_cloud_counts: the points of a pr_cloud_normals_* call per outcome
 KNN_MAX_K, KNN_NONE = 32, 0xFFFFFFFF                                        # PR_KNN_MAX_K, PR_KNN_NONE
 
@@ -346,6 +378,9 @@ SIGNATURES = {
     "pr_depth_fuse_host": (_i32, [_vp, _u32, _i32, _sz, _u32, _vp, _vp]),
     "pr_depth_filter_dev": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp]),
     "pr_depth_filter_host": (_i32, [_vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "pr_reproject_describe": (_i32, [_u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
+    "pr_depth_reproject_dev": (_i32, [_vp, _u32, _sz, _sz, C.c_float, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp, _vp, _vp]),
+    "pr_depth_reproject_host": (_i32, [_vp, _u32, _sz, _sz, C.c_float, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp, _vp, _vp]),
     "pr_cloud_describe": (_i32, [_u32, C.c_float, _u32, C.c_float, _vp, _vp]),
     "pr_cloud_knn_dev": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "pr_cloud_normals_dev": (_i32, [_vp, _vp, _vp, _vp, _vp]),

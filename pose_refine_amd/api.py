@@ -26,6 +26,8 @@ import numpy as np
 from . import _lib
 from ._lib import (CloudCounts, CloudParamsDesc, COMM_ID_BYTES, DEPTH_FILLED, DEPTH_FILTER_MAX_RADIUS, DEPTH_FLYING, DEPTH_FUSE_MAX, DEPTH_GATED, DEPTH_KEPT, DEPTH_SMOOTHED, DEPTH_UNMEASURED, DepthFilterCounts, DepthFilterParamsDesc, COMPOSE_MAX_POSES, COMPOSE_NONE, CONTOUR, CONTOUR_FIT, CONTOUR_MAX_RADIUS, EDGE_NONE, COVER, COVER_ACCEPTED, COVER_EMPTY, COVER_FRAME, COVER_NOT_IN_ORDER, COVER_NO_POSITION, COVER_REASON_CAP, COVER_REASON_THRESHOLD, COVER_REJECTED, COVER_STATE_MASK, Criteria, FRAME, KDNODE, KNN_MAX_K, KNN_NONE, MeshRef, NORMAL, NORMAL_MAX_STEP, PAIR_SOLID, PENETRATION_MAX_POSES, PLANE, PLANE_BEHIND, PLANE_MAX_CANDIDATES, PLANE_MAX_PLANES, PLANE_MAX_SAMPLES, PLANE_NO_DEPTH, PlaneParamsDesc, POSE_DIST, POSE_DIST_MAX_POSES, POSE_DIST_MAX_SYMS, PPF_ENTRY, PPF_MAX_CELLS, PPF_MAX_MODEL_POINTS, PPF_MAX_MODELS, PPF_MAX_PEAKS, PPF_MAX_SCENE_POINTS, PPF_PEAK, PPFModelDesc, PPFParams, PyramidLevel as _PyramidLevel, RESULT, ROBUST_CAUCHY, ROBUST_HUBER, ROBUST_NONE, ROBUST_TUKEY, RobustDesc, Roi, SCENE_GRID, SCENE_NN, SCENE_PROJ, SCENE_PROJ_CROP, SCORE, SEGMENT, SEGMENT_DROPPED, SEGMENT_MAX, SEGMENT_MAX_ROOTS, SegmentParamsDesc, SOLVE_DEVICE, SOLVE_HOST, VISIBLE, VSD, VSD_MAX_TAUS,
                    PoseRefineError, SceneGridDesc, SceneNNDesc, SceneProjCropDesc, SceneProjDesc, check, ptr)
+from ._lib import (REPROJECT_HIDDEN, REPROJECT_MAX_RADIUS, REPROJECT_MAX_SOURCES, REPROJECT_NONE, SRC_CLOUD, SRC_DEPTH_I32, SRC_DEPTH_U16,  # noqa: F401
+                   ReprojectCounts, ReprojectParamsDesc, ReprojectSourceDesc)
 
 
 def _f32(a, shape=None):
@@ -2035,6 +2037,153 @@ def depth_fuse_host(frames, width: int, height: int, min_frames: int = 1, want_c
     table = (C.c_void_p * len(fs))(*[ptr(f) for f in fs])
     check(_lib.load().pr_depth_fuse_host(C.addressof(table), len(fs), int(fs[0].dtype == np.int32), n_px, int(min_frames), ptr(out), ptr(count) if want_count else None))
     return (out, count) if want_count else out
+
+
+# ------------------------------------------------------------------------------------------------
+# reprojection: depth frames of other cameras and bare clouds into the depth frame of one camera (pr_depth_reproject_*; the definition is in include/pose_refine.h)
+# ------------------------------------------------------------------------------------------------
+def ReprojectParams(splat: int = 1, min_mm: int = 0, max_mm: int = 0, tol_mm: int = 0, tol_permille: int = 0, occl_radius: int = 0,
+                    occl_min_front: int = 0) -> ReprojectParamsDesc:
+    """``pr_reproject_describe`` (host only): the parameters of a reprojection, checked.  ``splat`` 1 .. 3 is the side of the square of pixels a
+    sample writes; ``min_mm`` / ``max_mm`` gate the reprojected depth (``max_mm`` 0: no gate but the depth type's); the visibility stage is off by
+    default (``occl_min_front`` 0): with ``occl_radius`` 1 .. 2 a pixel is hidden when ``occl_min_front`` pixels of its window are nearer by more
+    than ``tol(d) = tol_mm + d * tol_permille // 1000``."""
+    rp = ReprojectParamsDesc()
+    check(_lib.load().pr_reproject_describe(int(splat), int(min_mm), int(max_mm), int(tol_mm), int(tol_permille), int(occl_radius), int(occl_min_front),
+                                            C.addressof(rp)))
+    return rp
+
+
+def _pinhole(K):
+    k = _f32(K, -1)
+    if k.size != 9:
+        raise ValueError("K must be a 3 x 3 intrinsic matrix")
+    return float(k[0]), float(k[4]), float(k[2]), float(k[5])
+
+
+class ReprojectSource:
+    """One source of ``depth_reproject``: ``ReprojectSource.frame`` or ``ReprojectSource.cloud``.  ``T`` is the 4 x 4 transform from the source's
+    camera to the target's, translation in metres; default the identity."""
+
+    def __init__(self, kind: int, data, T=None, width: int = 0, height: int = 0, K=None, n_points: int = 0, offset_bytes: int = 0):
+        self.kind, self.data, self.width, self.height, self.n_points, self.offset_bytes = kind, data, int(width), int(height), int(n_points), int(offset_bytes)
+        self.pinhole = _pinhole(K) if K is not None else (0.0, 0.0, 0.0, 0.0)
+        self.T = _f32(np.eye(4) if T is None else T, -1)
+        if self.T.size != 16:
+            raise ValueError("T must be a 4 x 4 matrix")
+
+    @classmethod
+    def frame(cls, depth, width: int, height: int, K, T=None, offset_elems: int = 0) -> "ReprojectSource":
+        """A depth frame (a DeviceVector or a host image, uint16 or int32) of ``width`` x ``height`` pixels with intrinsics ``K``; ``offset_elems``
+        selects an image of a stack, as in ``depth2cloud``."""
+        dt = depth.dtype
+        if dt not in (np.uint16, np.int32):
+            raise ValueError("a frame source must be CV_16U or CV_32S")
+        n = depth.size() if isinstance(depth, DeviceVector) else depth.size
+        if offset_elems < 0 or n - offset_elems < width * height or (offset_elems == 0 and n != width * height):
+            raise ValueError(f"a buffer of {n} values holds no {width} x {height} frame at element {offset_elems}")
+        return cls(SRC_DEPTH_I32 if dt == np.int32 else SRC_DEPTH_U16, depth, T, width, height, K, offset_bytes=offset_elems * dt.itemsize)
+
+    @classmethod
+    def cloud(cls, points, T=None, offset_points: int = 0) -> "ReprojectSource":
+        """A bare cloud: an (n, 3) float32 host array or a DeviceVector of 3 n floats, in metres, from point ``offset_points`` on."""
+        if isinstance(points, DeviceVector):
+            if points.dtype != np.float32 or points.size() % 3:
+                raise ValueError("a cloud source must hold 3 n float32 values")
+            n = points.size() // 3
+        else:
+            points = _f32(points, (-1, 3))
+            n = len(points)
+        if not 0 <= offset_points < max(n, 1):
+            raise ValueError(f"a cloud of {n} points has no point {offset_points}")
+        return cls(SRC_CLOUD, points, T, n_points=n - offset_points, offset_bytes=offset_points * 12)
+
+    def desc(self, data_ptr: int) -> ReprojectSourceDesc:
+        fx, fy, cx, cy = self.pinhole
+        return ReprojectSourceDesc(data_ptr + self.offset_bytes, self.n_points, self.kind, self.width, self.height, 0, fx, fy, cx, cy, (C.c_float * 16)(*self.T))
+
+
+def _reproject_params(params, kw) -> ReprojectParamsDesc:
+    if params is not None and kw:
+        raise ValueError("pass either params or keyword parameters")
+    return params if params is not None else ReprojectParams(**kw)
+
+
+def _reproject_counts(cnt: ReprojectCounts, n_sources: int) -> dict:
+    per = [dict(samples=s.samples, invalid=s.invalid, range=s.range, outside=s.outside, drawn=s.drawn, won=s.won) for s in list(cnt.source)[:n_sources]]
+    return dict(sources=per, covered=cnt.covered, hidden=cnt.hidden, kept=cnt.kept)
+
+
+def _reproject_table(sources, on_device: bool):
+    """(the pr_reproject_source table, what its pointers point into)"""
+    srcs = list(sources)
+    if not 1 <= len(srcs) <= REPROJECT_MAX_SOURCES or not all(isinstance(s, ReprojectSource) for s in srcs):
+        raise ValueError(f"depth_reproject takes 1 .. {REPROJECT_MAX_SOURCES} ReprojectSource objects")
+    table, keep = (ReprojectSourceDesc * len(srcs))(), []
+    for i, s in enumerate(srcs):
+        if on_device:
+            dev = s.data if isinstance(s.data, DeviceVector) else DeviceVector.from_host(np.ascontiguousarray(s.data).reshape(-1))
+            keep.append(dev)
+            table[i] = s.desc(dev.data())
+        else:
+            if isinstance(s.data, DeviceVector):
+                raise ValueError("depth_reproject_host takes host arrays")
+            arr = np.ascontiguousarray(s.data)
+            keep.append(arr)
+            table[i] = s.desc(ptr(arr))
+    return table, keep
+
+
+def depth_reproject(sources, width: int, height: int, K, dtype=np.uint16, params: Optional[ReprojectParamsDesc] = None, depth_out: Optional[DeviceVector] = None,
+                    want_source: bool = False, **kw):
+    """``pr_depth_reproject_dev``: 1 .. ``REPROJECT_MAX_SOURCES`` sources -- depth frames of other cameras and bare clouds (``ReprojectSource``) --
+    through their rigid transforms and the pinhole ``K`` into the z-buffered ``width`` x ``height`` depth frame of one target camera.  Returns (depth
+    DeviceVector of ``dtype``[, source DeviceVector uint8[width * height]], counts): ``source`` (``want_source``) holds, per pixel, the index of the
+    source that won it, ``REPROJECT_HIDDEN`` or ``REPROJECT_NONE``; ``counts`` is a dict of the per-source records (samples, invalid, range, outside,
+    drawn, won) and the frame's covered, hidden and kept pixels.  The frame goes as it is into ``depth_filter`` (whose fill closes rounding gaps
+    and hidden pixels), ``init_Scene_projective_device``, ``scene_planes``, ``scene_segments`` and the scorers.  Parameters: a ``ReprojectParams`` or
+    its keywords."""
+    rp = _reproject_params(params, kw)
+    dt = np.dtype(dtype)
+    if dt not in (np.uint16, np.int32):
+        raise ValueError("the target depth must be CV_16U or CV_32S")
+    table, keep = _reproject_table(sources, True)
+    out = depth_out if depth_out is not None else DeviceVector(width * height, dt)
+    if out.dtype != dt or out.size() != width * height:
+        raise ValueError("depth_out must have the target's dtype and size")
+    src = DeviceVector(width * height, np.uint8) if want_source else None
+    cnt = ReprojectCounts()
+    fx, fy, cx, cy = _pinhole(K)
+    check(_lib.load().pr_depth_reproject_dev(C.addressof(table), len(table), width, height, fx, fy, cx, cy, int(dt == np.int32), C.addressof(rp), out.data(),
+                                             src.data() if want_source else None, C.addressof(cnt)))
+    del keep
+    counts = _reproject_counts(cnt, len(table))
+    return (out, src, counts) if want_source else (out, counts)
+
+
+def depth_reproject_host(sources, width: int, height: int, K, dtype=np.uint16, params: Optional[ReprojectParamsDesc] = None, want_source: bool = False, **kw):
+    """``pr_depth_reproject_host``: ``depth_reproject`` over host arrays, on the CPU, from the same definition.  Returns (depth[height, width][,
+    source uint8[height, width]], counts); runs without a GPU."""
+    rp = _reproject_params(params, kw)
+    dt = np.dtype(dtype)
+    if dt not in (np.uint16, np.int32):
+        raise ValueError("the target depth must be CV_16U or CV_32S")
+    table, keep = _reproject_table(sources, False)
+    out = np.zeros((height, width), dt)
+    src = np.zeros((height, width), np.uint8) if want_source else None
+    cnt = ReprojectCounts()
+    fx, fy, cx, cy = _pinhole(K)
+    check(_lib.load().pr_depth_reproject_host(C.addressof(table), len(table), width, height, fx, fy, cx, cy, int(dt == np.int32), C.addressof(rp), ptr(out),
+                                              ptr(src) if want_source else None, C.addressof(cnt)))
+    del keep
+    counts = _reproject_counts(cnt, len(table))
+    return (out, src, counts) if want_source else (out, counts)
+
+
+def cloud_to_depth(points, width: int, height: int, K, T=None, **kw):
+    """``depth_reproject`` of one cloud source: the depth frame a camera with intrinsics ``K`` at ``T`` (cloud to camera) sees of a bare cloud --
+    what an ``init_Scene_nn_cloud`` user hands to the scorers, ``scene_planes`` and ``scene_segments``.  Keywords and results as ``depth_reproject``."""
+    return depth_reproject([ReprojectSource.cloud(points, T)], width, height, K, **kw)
 
 
 # ------------------------------------------------------------------------------------------------

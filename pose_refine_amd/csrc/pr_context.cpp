@@ -78,9 +78,9 @@ void ctx_teardown(Ctx *c)        // c->mu held (or c unreachable); the calling t
     hipStreamSynchronize(c->stream);
     for (Slot &sl : c->slots) slot_release(sl);
     for (DevBuf *b : { &c->aabb, &c->aabb_keys, &c->bbox, &c->poses, &c->depth, &c->row_count, &c->row_off, &c->counts, &c->cloud, &c->meta, &c->partial,
-                       &c->sums, &c->packed.rec, &c->nn_prev, &c->dstate, &c->dresults, &c->arrive, &c->conv16, &c->conv8, &c->kd_scratch, &c->kd_tmp, &c->nn_full, &c->gather_tmp, &c->nn_counters, &c->scores, &c->multi, &c->ov_bits, &c->ov_box, &c->ov_mat, &c->cov_state, &c->cov_claimed, &c->mesh_sorted, &c->mesh_verts, &c->contours, &c->normals, &c->cmp_keys, &c->cmp_box, &c->cmp_rec, &c->edge_bits, &c->edge_rows, &c->lvl_rows, &c->lvl_counts, &c->lvl_carry, &c->pd_mats, &c->pd_part, &c->pd_rec, &c->ppf_tmp, &c->ppf_out, &c->plane_tmp, &c->seg_tmp, &c->dfilt_tmp, &c->cloud_tmp, &c->vsd_rec, &c->solid_far, &c->solid_rec, &c->info_meta, &c->info_part }) b->release();
+                       &c->sums, &c->packed.rec, &c->nn_prev, &c->dstate, &c->dresults, &c->arrive, &c->conv16, &c->conv8, &c->kd_scratch, &c->kd_tmp, &c->nn_full, &c->gather_tmp, &c->nn_counters, &c->scores, &c->multi, &c->ov_bits, &c->ov_box, &c->ov_mat, &c->cov_state, &c->cov_claimed, &c->mesh_sorted, &c->mesh_verts, &c->contours, &c->normals, &c->cmp_keys, &c->cmp_box, &c->cmp_rec, &c->edge_bits, &c->edge_rows, &c->lvl_rows, &c->lvl_counts, &c->lvl_carry, &c->pd_mats, &c->pd_part, &c->pd_rec, &c->ppf_tmp, &c->ppf_out, &c->plane_tmp, &c->seg_tmp, &c->dfilt_tmp, &c->reproj_tmp, &c->cloud_tmp, &c->vsd_rec, &c->solid_far, &c->solid_rec, &c->info_meta, &c->info_part }) b->release();
     for (NNDerived &d : c->nn_sets) d.release();
-    for (PinBuf *b : { &c->h_sums, &c->h_meta, &c->h_counts, &c->h_results, &c->h_dstate, &c->h_poses, &c->h_flags, &c->h_scores, &c->h_multi, &c->h_ov, &c->h_cov, &c->h_contours, &c->h_normals, &c->h_lvl_carry, &c->h_cmp, &c->h_pd_mats, &c->h_pd_rec, &c->h_ppf, &c->h_plane, &c->h_seg, &c->h_dfilt, &c->h_vsd, &c->h_solid, &c->h_info_meta, &c->h_info_out }) b->release();
+    for (PinBuf *b : { &c->h_sums, &c->h_meta, &c->h_counts, &c->h_results, &c->h_dstate, &c->h_poses, &c->h_flags, &c->h_scores, &c->h_multi, &c->h_ov, &c->h_cov, &c->h_contours, &c->h_normals, &c->h_lvl_carry, &c->h_cmp, &c->h_pd_mats, &c->h_pd_rec, &c->h_ppf, &c->h_plane, &c->h_seg, &c->h_dfilt, &c->h_reproj, &c->h_vsd, &c->h_solid, &c->h_info_meta, &c->h_info_out }) b->release();
     c->packed = PackedCache();
     for (auto &gr : c->graphs) destroy_graph(gr);
     c->graphs.clear();

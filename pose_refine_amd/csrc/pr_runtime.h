@@ -843,6 +843,8 @@ struct Ctx {
     DevBuf cloud_tmp;                // pr_cloud_normals_dev / pr_scene_nn_from_cloud_dev: the tally of the points per status
     DevBuf dfilt_tmp;                // pr_depth_filter_dev: the control words (the pixels per flag code)
     PinBuf h_dfilt;                  // ... on their way to the caller
+    DevBuf reproj_tmp;               // pr_depth_reproject_dev: the key plane of the target and, behind it, the control words
+    PinBuf h_reproj;                 // ... which the last resolve tile leaves here
     DevBuf vsd_rec;                  // pr_pose_vsd: the records of a chunk's pairs
     PinBuf h_vsd;                    // ... on their way to the caller
     DevBuf solid_far, solid_rec;     // pr_render_span / pr_pose_penetration: the far plane of the boxes in g->depth (same offsets); the P x P pair records

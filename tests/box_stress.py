@@ -7,14 +7,20 @@ strong perspective, every frame border, exotic intrinsics, mesh coordinates far 
 all -- on a 160 x 120 frame, with the oracle's FULL-FRAME renders of them (oracle_lib.render knows no boxes) as the reference everything is
 held to.  Deterministic: fixed seeds, and `assert_classes` states what the committed seeds must yield.
 
-Also the helpers test_tight_box.py introduced (area, inside, drawn_box, numpy_tight_box), which both host files import from here."""
+Also the helpers test_tight_box.py introduced (area, inside, drawn_box, numpy_tight_box), which both host files import from here, and what
+the references of the pair kernels and the contour fit (solid_ref, vsd_ref, select_ref, contour_fit_ref: they take renders and know no
+boxes either) give on the same batches, computed once, with `assert_pair_classes` for what those must contain."""
 import functools
 
 import numpy as np
 
 import oracle_lib as O
+from contour_fit_ref import centers, fit_records, nearest_ref
 from gpu_common import random_mesh, random_pose
 from pose_refine_amd import api
+from select_ref import overlap_ref
+from solid_ref import INT_MAX, INT_MIN, pairs_ref, span_ref
+from vsd_ref import SMALL_TAUS, vsd_ref
 
 W, H = 160, 120
 NONE = (0, 0, 0, 0)
@@ -313,6 +319,126 @@ def assert_classes(batches):
     assert c["nothing"] >= 2, c
     assert all(c["offset_decades"].get(d, 0) > 0 for d in (3, 4, 5, 6, 7)), c             # every offset decade is present and draws something
     assert 4 * c["nothing"] <= c["hypotheses"], c                 # ... and the set is not mostly empty
+    return c
+
+
+# ---- the pair kernels and the contour fit: references over the same renders ---------------------------------------------------------------
+VSD_DELTA = 15.0
+FIT_TJR = (0, 10, 0)                                              # the (tau, jump, radius) of test_contour_fit_gpu.TJR at which used, occluded AND miss occur (assert_pair_classes)
+FIT_TJR_WIDE = (5, 10, 4)                                         # ... and one with a window, whose nearest edge lies across the box edge (no miss: the noise makes an edge everywhere)
+SLACKS = (0, 50)
+
+
+def vsd_pairing(n):
+    """The truth of estimate i is hypothesis perm[i]: the batch rolled by 7, so the shuffled families meet (whole-frame against few-pixel,
+    nothing against something, straddle against far)."""
+    return np.roll(np.arange(n), 7)
+
+
+def one_truths(index):
+    """(a hypothesis whose box is the frame, one that draws nothing) of batch `index` for the one-truth form: on the mesh batches the
+    `close` pose with a whole-frame tight box that draws most and a `nothing` pose, elsewhere the hypotheses that draw most and least."""
+    b = stress_batches()[index]
+    n = drawn_count(b["R"])
+    fam = np.array(b["families"])
+    if "close" in b["families"] and "nothing" in b["families"]:
+        close = np.flatnonzero((fam == "close") & (batch_boxes(index)[0] == np.array([0, 0, W - 1, H - 1])).all(1))
+        return int(close[np.argmax(n[close])]), int(np.flatnonzero(fam == "nothing")[0])
+    return int(np.argmax(n)), int(np.argmin(n))
+
+
+@functools.lru_cache(maxsize=None)
+def span_planes(index):
+    """(near, far) of batch `index` as the pair kernel reads them (solid_ref.span_ref, raw: INT_MAX / INT_MIN where nothing is drawn)."""
+    b = stress_batches()[index]
+    return span_ref(b["tris"], b["poses"], b["proj"], W, H, raw=True)
+
+
+def returned_planes(index):
+    """(near, far) as pr_render_span returns them: 0 where nothing is drawn (span_ref with raw=False)."""
+    near, far = span_planes(index)
+    return np.where(near == INT_MAX, 0, near), np.where(far == INT_MIN, 0, far)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_records(index, slack):
+    return pairs_ref(*span_planes(index), slack)
+
+
+def interleaved(first, second):
+    """Two (n, ...) arrays as one (2 n, ...): first[i] at 2 i, second[i] at 2 i + 1."""
+    out = np.empty((2 * len(first),) + first.shape[1:], first.dtype)
+    out[0::2], out[1::2] = first, second
+    return out
+
+
+def model_centres(index):
+    """(centres float32[P, 3] in the camera frame, radius): api._model_center_radius of the batch's mesh, moved by each pose."""
+    b = stress_batches()[index]
+    cm, rho = api._model_center_radius(api.Model(tris=b["tris"]), None, None)
+    return centers(b["poses"], cm), rho
+
+
+@functools.lru_cache(maxsize=None)
+def nearest_map(index, jump, radius):
+    return nearest_ref(stress_batches()[index]["scene"], jump, radius)
+
+
+@functools.lru_cache(maxsize=None)
+def fit_reference(index, tjr, roi=NONE):
+    """contour_fit_ref.fit_records of batch `index` over the oracle's renders (inside `roi`)."""
+    b = stress_batches()[index]
+    tau, jump, radius = tjr
+    cs, rho = model_centres(index)
+    r = b["R"] if roi == NONE else roi_renders(index, roi)
+    return fit_records(r, b["scene"], nearest_map(index, jump, radius), tau, jump, b["K"], cs, rho, roi)
+
+
+@functools.lru_cache(maxsize=None)
+def vsd_reference(index, with_k=True):
+    b = stress_batches()[index]
+    return vsd_ref(b["R"], b["R"][vsd_pairing(len(b["R"]))], b["scene"], b["K"] if with_k else None, VSD_DELTA, SMALL_TAUS)
+
+
+def pair_class_counts(batches):
+    """What the references hold on soup + shell (the two mesh batches): pairs are unordered and off the diagonal."""
+    c = dict(both=0, inter=0, zero_rows=0, behind_camera=0, banded=0, small_boxes=0, overlap=0, vsd_inter=0, vsd_far0=0, vsd_zero=0, vsd_one_side=0,
+             fit_used=0, fit_occluded=0, fit_miss=0, fit_wide_used=0)
+    for k, b in enumerate(batches):
+        for rec in fit_reference(k, FIT_TJR):
+            c["fit_used"] += rec["used"]; c["fit_occluded"] += rec["occluded"]; c["fit_miss"] += rec["miss"]
+        c["fit_wide_used"] += sum(rec["used"] for rec in fit_reference(k, FIT_TJR_WIDE))
+        if b["name"] not in ("soup", "shell"):
+            continue
+        n = len(b["R"])
+        upper = np.triu(np.ones((n, n), bool), 1)
+        pairs = pair_records(k, 0)
+        c["both"] += int(((pairs["both"] > 0) & upper).sum())
+        c["inter"] += int(((pairs["inter"] > 0) & upper).sum())
+        c["zero_rows"] += int((~pairs.view(np.uint8).reshape(n, -1).any(1)).sum())
+        c["behind_camera"] += int((b["R"] < 0).any((1, 2)).sum())
+        c["banded"] += sum(area(t) > 8192 for t in batch_boxes(k)[0])           # more than one LDS band in the pair kernel (kSolidTilePx, solid.hip)
+        boxes = [box_of_image(r > 0, H) for r in b["R"]]
+        c["small_boxes"] += sum(d is not None and 1 <= area(d) <= 25 for d in boxes)
+        c["overlap"] += int(((overlap_ref(b["R"], b["scene"], TAU) > 0) & upper).sum())
+        v, drawn, perm = vsd_reference(k), drawn_count(b["R"]), vsd_pairing(n)
+        c["vsd_inter"] += int((v["inter"] > 0).sum())
+        c["vsd_far0"] += int((v["far"][:, 0] > 0).sum())
+        c["vsd_zero"] += sum(rec.tobytes() == bytes(rec.nbytes) for rec in v)
+        c["vsd_one_side"] += int(((drawn == 0) != (drawn[perm] == 0)).sum())
+    return c
+
+
+def assert_pair_classes(batches):
+    """What the set must contain for the tests of the pair kernels and the contour fit to mean anything: floors well below what the
+    committed seeds give (profiles/box_stress/README.md).  Returns the counts."""
+    c = pair_class_counts(batches)
+    assert c["both"] >= 1000 and c["inter"] >= 300, c             # pairs that share pixels, and space
+    assert c["zero_rows"] >= 4 and c["behind_camera"] >= 4, c
+    assert c["banded"] >= 8 and c["small_boxes"] >= 4, c          # several LDS bands beside boxes of a few pixels
+    assert c["overlap"] >= 300, c
+    assert c["vsd_inter"] >= 40 and c["vsd_far0"] >= 40 and c["vsd_zero"] >= 8 and c["vsd_one_side"] >= 8, c
+    assert min(c["fit_used"], c["fit_occluded"], c["fit_miss"]) > 0 and c["fit_wide_used"] > 0, c
     return c
 
 

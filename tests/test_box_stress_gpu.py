@@ -3,21 +3,32 @@ perspective, every frame border, exotic intrinsics, mesh coordinates far from th
 one batch.  Everything is held to R, the oracle's FULL-FRAME renders of the batch (oracle_lib.render knows no boxes), never to another route
 of the library: the box image itself (compose_detections' front depth of one hypothesis is its packed box unpacked into the frame), the
 scoring kinds that walk the boxes, the fused refine path synchronously and on the slots with loose and tight boxes, mixed batches and the
-pyramid.  A pixel box that is one pixel too small, or a packed-box address that is off, faults nothing: it changes a count here."""
+pyramid; then the kernels that combine TWO boxes (VSD over the union, interpenetration over the intersection and in LDS bands, the overlap
+matrix), the span render's far plane, the contour fit and the fused information pass.  A pixel box that is one pixel too small, or a
+packed-box address that is off, faults nothing: it changes a count here."""
 import numpy as np
 import pytest
 
+import contour_fit_ref as CF
+import info_ref
 import oracle_lib as O
 import pyramid_ref
-from box_stress import H, NONE, ROIS, TAU, W, drawn_count, roi_renders, stress_batches
+from box_stress import (FIT_TJR, FIT_TJR_WIDE, H, NONE, ROIS, SLACKS, TAU, VSD_DELTA, W, drawn_count, fit_reference, interleaved, model_centres, nearest_map,
+                        one_truths, pair_records, returned_planes, roi_renders, span_planes, stress_batches, vsd_pairing, vsd_reference)
 from compose_ref import Composite, assert_composites_equal, check_invariants, compose_ref
 from contour_ref import assert_contours_equal, contour_ref, edge_distance_ref
 from cover_ref import KEEP_ALL, assert_cover_equal, cover_ref, supports_of
 from gpu_common import TOL_T, inliers
 from normals_ref import assert_identities, assert_normals_equal, normals_ref
 from pose_refine_amd import api
+from select_ref import overlap_ref
+from solid_ref import check_invariants as check_pair_invariants, pairs_ref, span_ref_multi
+from test_contour_fit_gpu import assert_records
+from test_information_gpu import Kit, assert_record
+from test_select_gpu import _assert_overlap
 from test_tight_box_gpu import same, tight_batches
 from verify_ref import assert_scores_equal, score_ref
+from vsd_ref import SMALL_TAUS, assert_vsd_equal, vsd_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -353,3 +364,174 @@ def test_pyramid(gpu, batches, models, solve):
                 assert np.allclose(got_l["T"], want_l["T"], rtol=0, atol=TOL_T), (b["name"], what, worst)
     finally:
         api.set_option("solve", api.SOLVE_HOST)
+
+
+# ---- two boxes at once: visible surface discrepancy over the union of a pair's boxes ---------------------------------------------------------
+def _soup_and_shell(batches):
+    a, s = batches[0], batches[1]
+    assert a["name"] == "soup" and s["name"] == "shell" and np.array_equal(a["K"], s["K"]) and len(a["poses"]) == len(s["poses"])
+    return a, s
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("with_k", [True, False])
+def test_pose_vsd(gpu, batches, models, with_k, dtype):
+    """Estimate i against hypothesis perm[i] of the same batch (box_stress.vsd_pairing), then every estimate against one truth whose box is the
+    frame and against one that draws nothing: every record byte for byte vsd_ref's over the oracle's renders."""
+    for k, (b, m) in enumerate(zip(batches, models)):
+        scene, K, R = _scene(b, dtype), (b["K"] if with_k else None), b["R"]
+        perm = vsd_pairing(len(R))
+        got = api.pose_vsd(m, b["poses"], b["poses"][perm], W, H, b["proj"], scene, K, VSD_DELTA, SMALL_TAUS)
+        assert_vsd_equal(got, vsd_reference(k, with_k))
+        for t in one_truths(k):
+            got = api.pose_vsd(m, b["poses"], b["poses"][t], W, H, b["proj"], scene, K, VSD_DELTA, SMALL_TAUS)
+            assert_vsd_equal(got, _cached(("vsd one", k, t, with_k), lambda: vsd_ref(R, R[t], b["scene"], K, VSD_DELTA, SMALL_TAUS)))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_pose_vsd_mixed_batch_of_soup_and_shell(gpu, batches, models, dtype):
+    """Soup and shell pairs interleaved: pair i is held to the renders of its own mesh."""
+    a, s = _soup_and_shell(batches)
+    perm = vsd_pairing(len(a["poses"]))
+    est, gt = interleaved(a["poses"], s["poses"]), interleaved(a["poses"][perm], s["poses"][perm])
+    r_est, r_gt = interleaved(a["R"], s["R"]), interleaved(a["R"][perm], s["R"][perm])
+    idx = np.arange(len(est)) % 2
+    for K in (a["K"], None):
+        got = api.pose_vsd_multi(models[:2], idx, est, gt, W, H, a["proj"], _scene(a, dtype), K, VSD_DELTA, SMALL_TAUS)
+        assert_vsd_equal(got, vsd_ref(r_est, r_gt, a["scene"], K, VSD_DELTA, SMALL_TAUS))
+
+
+# ---- ... interpenetration over the intersection of two boxes, in LDS bands; the far plane ----------------------------------------------------
+def _planes_of(m, poses, proj):
+    near, far = api.render_span(m, poses, W, H, proj)
+    return near.to_host().reshape(len(poses), H, W), far.to_host().reshape(len(poses), H, W)
+
+
+def _assert_pairs(got, want, what):
+    assert got.dtype == api.PAIR_SOLID and got.shape == want.shape, what
+    for f in api.PAIR_SOLID.names:
+        bad = np.argwhere(got[f] != want[f])
+        assert len(bad) == 0, (what, f, len(bad), bad[:5].tolist(), [(int(got[f][i, j]), int(want[f][i, j])) for i, j in bad[:5]])
+    assert got.tobytes() == want.tobytes(), what
+    check_pair_invariants(got)
+
+
+def test_render_span_near_and_far_plane(gpu, batches, models):
+    """Both planes of pr_render_span on every batch: the near plane is R (negative depths and all), the far plane solid_ref's maximum
+    composite -- also where fragments lie behind the camera."""
+    behind = 0
+    for k, (b, m) in enumerate(zip(batches, models)):
+        near, far = _planes_of(m, b["poses"], b["proj"])
+        want_near, want_far = returned_planes(k)
+        for got, want, plane in ((near, want_near, "near"), (far, want_far, "far")):
+            bad = np.argwhere(got != want)
+            assert len(bad) == 0, (b["name"], plane, len(bad), bad[:5].tolist(), got[tuple(bad[:5].T)], want[tuple(bad[:5].T)])
+        assert np.array_equal(near, b["R"]), b["name"]
+        behind += int((near < 0).any((1, 2)).sum())
+    assert behind >= 4
+
+
+@pytest.mark.parametrize("slack", SLACKS)
+def test_pose_penetration(gpu, batches, models, slack):
+    for k, (b, m) in enumerate(zip(batches, models)):
+        _assert_pairs(api.pose_penetration(m, b["poses"], W, H, b["proj"], slack), pair_records(k, slack), (b["name"], slack))
+
+
+def test_pose_penetration_mixed_batch_of_soup_and_shell(gpu, batches, models):
+    a, s = _soup_and_shell(batches)
+    poses = interleaved(a["poses"], s["poses"])
+    idx = np.arange(len(poses)) % 2
+    near, far = span_ref_multi([a["tris"], s["tris"]], idx, poses, a["proj"], W, H)
+    assert np.array_equal(near[0::2], span_planes(0)[0]) and np.array_equal(far[1::2], span_planes(1)[1])
+    for slack in SLACKS:
+        _assert_pairs(api.pose_penetration_multi(models[:2], idx, poses, W, H, a["proj"], slack), pairs_ref(near, far, slack), ("mixed", slack))
+
+
+# ---- ... the overlap matrix over the saved boxes of all P hypotheses -----------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("roi", [NONE] + ROIS)
+def test_score_overlap(gpu, batches, models, roi, dtype):
+    shared = 0
+    for k, (b, m) in enumerate(zip(batches, models)):
+        r, want_sc = _score_ref(k, b, roi)
+        want_ov = _cached(("overlap", k, roi), lambda: overlap_ref(r, b["scene"], TAU, roi))
+        sc, ov = api.score_overlap(m, b["poses"], W, H, b["proj"], _scene(b, dtype), TAU, roi=roi)
+        _assert_overlap(sc, ov, want_sc, want_ov)
+        assert sc.tobytes() == want_sc.tobytes(), b["name"]
+        shared += int(np.count_nonzero(np.triu(want_ov, 1)))
+    assert shared >= 100
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_score_overlap_mixed_batch_of_soup_and_shell(gpu, batches, models, dtype):
+    a, s = _soup_and_shell(batches)
+    poses, R = interleaved(a["poses"], s["poses"]), interleaved(a["R"], s["R"])
+    idx = np.arange(len(poses)) % 2
+    sc, ov = api.score_overlap_multi(models[:2], idx, poses, W, H, a["proj"], _scene(a, dtype), TAU)
+    _assert_overlap(sc, ov, score_ref(R, a["scene"], TAU), _cached(("overlap mixed",), lambda: overlap_ref(R, a["scene"], TAU)))
+    assert ov[0::2, 1::2].any()                                   # hypotheses of different meshes do share inliers
+
+
+# ---- the contour fit: 4-neighbours across the box edge and the window edge -----------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("tjr", [FIT_TJR, FIT_TJR_WIDE])
+def test_contour_information(gpu, batches, models, tjr, dtype):
+    """The nearest-edge map bit for bit; the integer fields of every record exactly and the 30 sums within contour_fit_ref.fit_bound of the
+    reference over the oracle's renders -- on the offset meshes too, whose model centre lies 10^3 .. 10^7 mm from the origin (the centre
+    enters the sums only through c = pose applied to it, which the offset poses bring back in front of the camera)."""
+    tau, jump, radius = tjr
+    worst = 0.0
+    for k, (b, m) in enumerate(zip(batches, models)):
+        scene = _scene(b, dtype)
+        nd = api.scene_edge_nearest(scene, W, H, jump, radius)
+        assert np.array_equal(nd.to_host().reshape(H, W), nearest_map(k, jump, radius)), b["name"]
+        cs, rho = model_centres(k)
+        for roi in (NONE, ROIS[1]):
+            sc, fit, info = api.contour_information(m, b["poses"], W, H, b["proj"], b["K"], scene, tau, jump, nd, roi=roi if roi != NONE else None)
+            worst = max(worst, assert_records(fit, info, fit_reference(k, tjr, roi), cs, rho, (b["name"], tjr, roi)))
+            assert_scores_equal(sc, _cached(("score", k, roi, tau), lambda: score_ref(b["R"] if roi == NONE else roi_renders(k, roi), b["scene"], tau, roi)))
+    print(tjr, np.dtype(dtype).name, "largest error / bound", worst)
+
+
+def test_contour_information_mixed_batch_of_soup_and_shell(gpu, batches, models):
+    a, s = _soup_and_shell(batches)
+    poses = interleaved(a["poses"], s["poses"])
+    idx = np.arange(len(poses)) % 2
+    tau, jump, radius = FIT_TJR_WIDE
+    nd = api.scene_edge_nearest(a["scene"], W, H, jump, radius)
+    N = nearest_map(0, jump, radius)
+    _, fit, info = api.contour_information_multi(models[:2], idx, poses, W, H, a["proj"], a["K"], a["scene"], tau, jump, nd)
+    for mi, b in enumerate((a, s)):
+        cs, rho = model_centres(mi)
+        refs = fit_reference(0, FIT_TJR_WIDE) if mi == 0 else _cached(("fit shell on soup",), lambda: CF.fit_records(b["R"], a["scene"], N, tau, jump, a["K"], cs, rho))
+        assert_records(fit[mi::2], info[mi::2], refs, cs, rho, ("mixed", b["name"]))
+
+
+# ---- the fused information pass: its clouds are what render + emit leave in the boxes ---------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_pose_information_cloud_sizes(gpu, batches, models, dtype):
+    for k, (b, m) in enumerate(zip(batches, models)):
+        info, _, sizes = api.pose_information(m, b["poses"], W, H, b["proj"], b["K"], _scenes(k, b, "proj", dtype)[0], want_eig=False)
+        assert np.array_equal(sizes, _drawn(b)), (b["name"], np.flatnonzero(sizes != _drawn(b))[:10])
+        assert np.array_equal(info["n_points"], _drawn(b)), b["name"]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("k", [0, 1], ids=["soup", "shell"])
+def test_pose_information_records(gpu, batches, models, k, dtype):
+    """Every hypothesis that draws a pixel: the record against info_ref.record on the oracle's cloud of the oracle's render (fragments behind
+    the camera are no points), the correspondences the library's own, within info_ref.sum_bound."""
+    b, m = batches[k], models[k]
+    gs = _scenes(k, b, "proj", dtype)[0]
+    info, _, sizes = api.pose_information(m, b["poses"], W, H, b["proj"], b["K"], gs, want_eig=False)
+    cs, rho = model_centres(k)
+    assert np.array_equal(info["c"], cs) and (info["rho"] == np.float32(rho)).all()
+    kit = Kit(gs, packed=True)
+    worst, held = 0.0, 0
+    for i in np.flatnonzero(_drawn(b) >= 1):
+        cloud = O.depth2cloud(np.maximum(b["R"][i], 0), b["K"])
+        assert len(cloud) == sizes[i], (b["name"], i)
+        worst = max(worst, assert_record(info[i], info_ref.record(cloud, kit.associate(cloud), None, cs[i], rho), (b["name"], i, b["families"][i])))
+        held += 1
+    print(b["name"], np.dtype(dtype).name, held, "records, largest error / bound", worst)
+    assert held >= 40 and info["n_valid"].sum() > 10000

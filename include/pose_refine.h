@@ -40,7 +40,10 @@
  * (depth_scene.h:29-48).  Asynchronous batches (pr_refine_submit) compare a SAMPLE of 4096 words per array inside their raster launch (a mismatch
  * repeats the batch with fresh caches, pr_stats): a frame replaced as a whole is noticed, an edit confined to words the sample does not look at
  * needs pr_invalidate.  A write THROUGH this library into a range that a batch still in flight on the calling context reads (its scene arrays, its
- * mesh, its result block) waits for that batch first: a scene object may be re-initialised while its previous frame's batch is running.
+ * mesh, its result block) waits for that batch first: a scene object may be re-initialised while its previous frame's batch is running.  The outputs
+ * of the frame stages (pr_depth_fuse_dev, pr_depth_filter_dev, pr_depth_reproject_dev, pr_scene_planes_dev, pr_scene_segments_dev,
+ * pr_segment_depth_dev, the pr_ppf_* samplers, tables and accumulators) are ordered like every other write through the library: a stage whose
+ * output overlaps such a range waits for the batch before its first kernel that writes is launched.
  */
 #ifndef POSE_REFINE_H
 #define POSE_REFINE_H

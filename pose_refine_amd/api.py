@@ -1672,6 +1672,36 @@ def generate_hypotheses_multi(ppf_models, scene: "Scene_projective", stride: int
             np.concatenate([v for _, v in lists]))
 
 
+# What the frame stages' wrappers (clouds, planes, segments, depth conditioning, reprojection) share.
+def _params(params, kw, factory):
+    """A stage's checked parameter block: the caller's, or ``factory`` (``CloudParams``, ``PlaneParams``, ...) over the keywords."""
+    if params is not None and kw:
+        raise ValueError("pass either a parameter block or keyword parameters, not both")
+    return params if params is not None else factory(**kw)
+
+
+def _host_depth(depth, n_px: int) -> np.ndarray:
+    dep = np.ascontiguousarray(depth)
+    if dep.dtype not in (np.uint16, np.int32):
+        raise ValueError("scene depth must be CV_16U or CV_32S")
+    if dep.size != n_px:
+        raise ValueError(f"depth holds {dep.size} values, expected {n_px}")
+    return dep
+
+
+def _depth_out(depth_out: Optional[DeviceVector], n_px: int, dtype) -> DeviceVector:
+    """Where a stage's depth goes: the caller's ``depth_out``, checked, or a new DeviceVector."""
+    out = depth_out if depth_out is not None else DeviceVector(n_px, dtype)
+    if out.dtype != dtype or out.size() != n_px:
+        raise ValueError(f"depth_out must have the depth's dtype and size ({np.dtype(dtype)}, {n_px} values)")
+    return out
+
+
+def _with_extras(base, extras, tail=()) -> tuple:
+    """A stage's result tuple, device or host form: ``base``, the value of every wanted ``(want, value)`` pair of ``extras``, ``tail``."""
+    return tuple(base) + tuple(v for want, v in extras if want) + tuple(tail)
+
+
 # ------------------------------------------------------------------------------------------------
 # scenes from point clouds: exact k nearest neighbours over the scene's kd-tree and a PCA normal per point (pr_cloud_*; the definition is in include/pose_refine.h)
 # ------------------------------------------------------------------------------------------------
@@ -1685,12 +1715,6 @@ def CloudParams(k: int = 16, max_radius: float = float("inf"), min_neighbours: i
     return out
 
 
-def _cloud_params(params, kw) -> CloudParamsDesc:
-    if params is not None and kw:
-        raise ValueError("give either a CloudParams block or keyword parameters, not both")
-    return params if params is not None else CloudParams(**kw)
-
-
 def _cloud_counts(c: CloudCounts) -> dict:
     return {"points": int(c.points), "with_normal": int(c.with_normal), "too_few": int(c.too_few), "degenerate": int(c.degenerate)}
 
@@ -1700,7 +1724,7 @@ def cloud_knn(scene: "Scene_nn", params: Optional[CloudParamsDesc] = None, **kw)
     within ``max_radius`` -- (idx uint32[n, k], d2 float32[n, k], count uint32[n]) read back from the device; unused slots hold ``KNN_NONE`` / 0."""
     if scene.kind != SCENE_NN:
         raise ValueError("cloud_knn takes a Scene_nn")
-    p = _cloud_params(params, kw)
+    p = _params(params, kw, CloudParams)
     d = scene.desc()
     n, k = int(d.n_points), int(p.k)
     idx, d2, cnt = DeviceVector(n * k, np.uint32), DeviceVector(n * k, np.float32), DeviceVector(n, np.uint32)
@@ -1715,7 +1739,7 @@ def cloud_normals(scene: "Scene_nn", params: Optional[CloudParamsDesc] = None, n
     ``DeviceVector`` of n floats or None, and the four counts as a dict."""
     if scene.kind != SCENE_NN:
         raise ValueError("cloud_normals takes a Scene_nn")
-    p = _cloud_params(params, kw)
+    p = _params(params, kw, CloudParams)
     d = scene.desc()
     n = int(d.n_points)
     out = scene.normal_buffer if in_place else (normal_out if normal_out is not None else DeviceVector(n * 3, np.float32))
@@ -1740,7 +1764,7 @@ def kdtree_build_host(points, max_leaf: int = 10):
 
 def cloud_knn_host(points, nodes, params: Optional[CloudParamsDesc] = None, **kw):
     """``pr_cloud_knn_host``: ``cloud_knn`` on the CPU over host points in tree order and their ``KDNODE`` array (``kdtree_build_host``)."""
-    p = _cloud_params(params, kw)
+    p = _params(params, kw, CloudParams)
     pts, nd = _f32(points).reshape(-1, 3), np.ascontiguousarray(nodes, KDNODE)
     n, k = len(pts), int(p.k)
     idx, d2, cnt = np.zeros((n, k), np.uint32), np.zeros((n, k), np.float32), np.zeros(n, np.uint32)
@@ -1750,7 +1774,7 @@ def cloud_knn_host(points, nodes, params: Optional[CloudParamsDesc] = None, **kw
 
 def cloud_normals_host(points, nodes, params: Optional[CloudParamsDesc] = None, **kw):
     """``pr_cloud_normals_host``: (normals float32[n, 3], variation float32[n], counts dict) on the CPU, byte for byte ``cloud_normals``."""
-    p = _cloud_params(params, kw)
+    p = _params(params, kw, CloudParams)
     pts, nd = _f32(points).reshape(-1, 3), np.ascontiguousarray(nodes, KDNODE)
     nrm, var, counts = np.zeros((len(pts), 3), np.float32), np.zeros(len(pts), np.float32), CloudCounts()
     check(_lib.load().pr_cloud_normals_host(ptr(pts), len(pts), ptr(nd), len(nd), C.addressof(p), ptr(nrm), ptr(var), C.addressof(counts)))
@@ -1769,12 +1793,6 @@ def PlaneParams(stride: int = 4, cand_stride: int = 16, tau_mm: float = 3.0, lab
     check(_lib.load().pr_plane_describe(int(stride), int(cand_stride), float(tau_mm), float(label_tau_mm), float(cos_min), int(min_support), int(n_planes),
                                         int(bool(drop_behind)), C.addressof(pp)))
     return pp
-
-
-def _plane_params(params, kw) -> PlaneParamsDesc:
-    if params is not None and kw:
-        raise ValueError("pass either params or keyword parameters")
-    return params if params is not None else PlaneParams(**kw)
 
 
 def plane_from_moments(moments):
@@ -1797,12 +1815,10 @@ def scene_planes(scene: "Scene_projective", scene_depth, params: Optional[PlaneP
     (tests and tools; a row's first n_candidates words are used).  Parameters: a ``PlaneParams`` or its keywords."""
     if scene.kind != SCENE_PROJ:
         raise ValueError("scene_planes takes a full-frame Scene_projective")
-    pp = _plane_params(params, kw)
+    pp = _params(params, kw, PlaneParams)
     W, H = scene.width, scene.height
     sd = _scene_depth_dev(scene_depth, W, H)
-    out = depth_out if depth_out is not None else DeviceVector(W * H, sd.dtype)
-    if out.dtype != sd.dtype or out.size() != W * H:
-        raise ValueError("depth_out must have the depth's dtype and size")
+    out = _depth_out(depth_out, W * H, sd.dtype)
     labels = DeviceVector(W * H, np.uint8)
     planes = np.zeros(PLANE_MAX_PLANES, PLANE)
     moments = np.zeros((PLANE_MAX_PLANES, 10), np.int64)
@@ -1811,12 +1827,8 @@ def scene_planes(scene: "Scene_projective", scene_depth, params: Optional[PlaneP
     n = C.c_uint32(0)
     check(_lib.load().pr_scene_planes_dev(C.addressof(d), sd.data(), int(sd.dtype == np.int32), C.addressof(pp), labels.data(), out.data(), ptr(planes),
                                           ptr(moments), sup.data() if want_supports else None, C.byref(n)))
-    res = [planes[:n.value].copy(), labels, out]
-    if want_moments:
-        res.append(moments[:n.value].copy())
-    if want_supports:
-        res.append(sup.to_host().reshape(pp.n_planes, PLANE_MAX_CANDIDATES))
-    return tuple(res)
+    return _with_extras((planes[:n.value].copy(), labels, out),
+                        ((want_moments, moments[:n.value].copy()), (want_supports, sup.to_host().reshape(pp.n_planes, PLANE_MAX_CANDIDATES) if want_supports else None)))
 
 
 def scene_planes_host(pcd, normal, scene_depth, width: int, height: int, params: Optional[PlaneParamsDesc] = None, want_moments: bool = False,
@@ -1824,13 +1836,11 @@ def scene_planes_host(pcd, normal, scene_depth, width: int, height: int, params:
     """``pr_scene_planes_host``: ``scene_planes`` over host arrays (pcd and normal float32[height * width, 3] as ``init_Scene_projective_cuda`` keeps
     them in ``pcd_host`` / ``normal_host``, the depth image uint16 or int32), on the CPU, from the same definition.  Returns (planes, labels
     uint8[height, width], cleared depth[height, width]) and on request moments and the support table uint32[n_planes, PLANE_MAX_CANDIDATES]; runs without a GPU."""
-    pp = _plane_params(params, kw)
+    pp = _params(params, kw, PlaneParams)
     p, m = _f32(pcd, (-1, 3)), _f32(normal, (-1, 3))
-    dep = np.ascontiguousarray(scene_depth)
-    if dep.dtype not in (np.uint16, np.int32):
-        raise ValueError("scene depth must be CV_16U or CV_32S")
-    if len(p) != width * height or len(m) != width * height or dep.size != width * height:
-        raise ValueError(f"pcd, normal and depth must hold {width} x {height} pixels")
+    dep = _host_depth(scene_depth, width * height)
+    if len(p) != width * height or len(m) != width * height:
+        raise ValueError(f"pcd and normal must hold {width} x {height} pixels")
     labels = np.zeros((height, width), np.uint8)
     cleared = np.zeros((height, width), dep.dtype)
     planes = np.zeros(PLANE_MAX_PLANES, PLANE)
@@ -1839,12 +1849,7 @@ def scene_planes_host(pcd, normal, scene_depth, width: int, height: int, params:
     n = C.c_uint32(0)
     check(_lib.load().pr_scene_planes_host(ptr(p), ptr(m), ptr(dep), int(dep.dtype == np.int32), width, height, C.addressof(pp), ptr(labels), ptr(cleared),
                                            ptr(planes), ptr(moments), ptr(sup) if want_supports else None, C.byref(n)))
-    res = [planes[:n.value].copy(), labels, cleared]
-    if want_moments:
-        res.append(moments[:n.value].copy())
-    if want_supports:
-        res.append(sup)
-    return tuple(res)
+    return _with_extras((planes[:n.value].copy(), labels, cleared), ((want_moments, moments[:n.value].copy()), (want_supports, sup)))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1858,19 +1863,13 @@ def SegmentParams(jump_mm: int = 10, min_pixels: int = 256, max_segments: int = 
     return sp
 
 
-def _segment_params(params, kw) -> SegmentParamsDesc:
-    if params is not None and kw:
-        raise ValueError("pass either params or keyword parameters")
-    return params if params is not None else SegmentParams(**kw)
-
-
 def scene_segments(scene_depth, width: int, height: int, params: Optional[SegmentParamsDesc] = None, want_roots: bool = False, **kw):
     """``pr_scene_segments_dev``: the depth-connected components of a depth frame (a DeviceVector or a host image, uint16 or int32; typically
     ``scene_planes``' cleared depth).  Returns (segments SEGMENT[n_found], labels DeviceVector uint16[width * height], counts): ``labels`` holds 0
     where nothing is measured, k for the k-th largest component and ``SEGMENT_DROPPED`` for the rest; ``counts`` is (n_found, n_qualifying,
     n_components).  ``want_roots`` adds, before the counts, a DeviceVector uint32[width * height] with every pixel's root (tests and tools).
     Parameters: a ``SegmentParams`` or its keywords."""
-    sp = _segment_params(params, kw)
+    sp = _params(params, kw, SegmentParams)
     sd = _scene_depth_dev(scene_depth, width, height)
     labels = DeviceVector(width * height, np.uint16)
     roots = DeviceVector(width * height, np.uint32) if want_roots else None
@@ -1878,33 +1877,21 @@ def scene_segments(scene_depth, width: int, height: int, params: Optional[Segmen
     n, nq, nc = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     check(_lib.load().pr_scene_segments_dev(sd.data(), int(sd.dtype == np.int32), width, height, C.addressof(sp), labels.data(), roots.data() if want_roots else None,
                                             ptr(segs), C.byref(n), C.byref(nq), C.byref(nc)))
-    res = [segs[:n.value].copy(), labels]
-    if want_roots:
-        res.append(roots)
-    res.append((n.value, nq.value, nc.value))
-    return tuple(res)
+    return _with_extras((segs[:n.value].copy(), labels), ((want_roots, roots),), ((n.value, nq.value, nc.value),))
 
 
 def scene_segments_host(depth, width: int, height: int, params: Optional[SegmentParamsDesc] = None, want_roots: bool = False, **kw):
     """``pr_scene_segments_host``: ``scene_segments`` over a host image (uint16 or int32), on the CPU, from the same definition.  Returns (segments,
     labels uint16[height, width][, roots uint32[height, width]], counts); runs without a GPU."""
-    sp = _segment_params(params, kw)
-    dep = np.ascontiguousarray(depth)
-    if dep.dtype not in (np.uint16, np.int32):
-        raise ValueError("scene depth must be CV_16U or CV_32S")
-    if dep.size != width * height:
-        raise ValueError(f"depth must hold {width} x {height} pixels")
+    sp = _params(params, kw, SegmentParams)
+    dep = _host_depth(depth, width * height)
     labels = np.zeros((height, width), np.uint16)
     roots = np.zeros((height, width), np.uint32) if want_roots else None
     segs = np.zeros(sp.max_segments, SEGMENT)
     n, nq, nc = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     check(_lib.load().pr_scene_segments_host(ptr(dep), int(dep.dtype == np.int32), width, height, C.addressof(sp), ptr(labels), ptr(roots) if want_roots else None,
                                              ptr(segs), C.byref(n), C.byref(nq), C.byref(nc)))
-    res = [segs[:n.value].copy(), labels]
-    if want_roots:
-        res.append(roots)
-    res.append((n.value, nq.value, nc.value))
-    return tuple(res)
+    return _with_extras((segs[:n.value].copy(), labels), ((want_roots, roots),), ((n.value, nq.value, nc.value),))
 
 
 def segment_depth(labels: DeviceVector, scene_depth, keep, depth_out: Optional[DeviceVector] = None) -> DeviceVector:
@@ -1915,9 +1902,7 @@ def segment_depth(labels: DeviceVector, scene_depth, keep, depth_out: Optional[D
     sd = _scene_depth_dev(scene_depth, n_px, 1)
     if labels.dtype != np.uint16:
         raise ValueError("labels must be uint16")
-    out = depth_out if depth_out is not None else DeviceVector(n_px, sd.dtype)
-    if out.dtype != sd.dtype or out.size() != n_px:
-        raise ValueError("depth_out must have the depth's dtype and size")
+    out = _depth_out(depth_out, n_px, sd.dtype)
     ks = [int(k) for k in np.atleast_1d(np.asarray(keep)).reshape(-1)]
     if any(k < 1 or k > SEGMENT_MAX for k in ks):
         raise ValueError(f"a kept label must be 1 .. SEGMENT_MAX = {SEGMENT_MAX}")
@@ -1951,21 +1936,6 @@ def DepthFilterParams(min_mm: int = 0, max_mm: int = 0, tol_mm: int = 0, tol_per
     return dp
 
 
-def _depth_filter_params(params, kw) -> DepthFilterParamsDesc:
-    if params is not None and kw:
-        raise ValueError("pass either params or keyword parameters")
-    return params if params is not None else DepthFilterParams(**kw)
-
-
-def _host_depth(depth, n_px: int) -> np.ndarray:
-    dep = np.ascontiguousarray(depth)
-    if dep.dtype not in (np.uint16, np.int32):
-        raise ValueError("scene depth must be CV_16U or CV_32S")
-    if dep.size != n_px:
-        raise ValueError(f"depth holds {dep.size} values, expected {n_px}")
-    return dep
-
-
 def depth_filter(depth, width: int, height: int, params: Optional[DepthFilterParamsDesc] = None, depth_out: Optional[DeviceVector] = None,
                  want_flags: bool = False, **kw):
     """``pr_depth_filter_dev``: a depth frame (a DeviceVector or a host image, uint16 or int32) with its range gate applied, its flying pixels
@@ -1974,37 +1944,27 @@ def depth_filter(depth, width: int, height: int, params: Optional[DepthFilterPar
     codes' pixel counts.  The cleaned frame goes as it is into ``init_Scene_projective_device``, ``init_Scene_nn_device``, ``scene_planes``,
     ``scene_segments``, ``generate_hypotheses`` and the scorers.  ``depth_out``: where it goes (never the input: the filter is a stencil); default
     a new DeviceVector.  Parameters: a ``DepthFilterParams`` or its keywords."""
-    dp = _depth_filter_params(params, kw)
+    dp = _params(params, kw, DepthFilterParams)
     sd = _scene_depth_dev(depth, width, height)
-    out = depth_out if depth_out is not None else DeviceVector(width * height, sd.dtype)
-    if out.dtype != sd.dtype or out.size() != width * height:
-        raise ValueError("depth_out must have the depth's dtype and size")
+    out = _depth_out(depth_out, width * height, sd.dtype)
     flags = DeviceVector(width * height, np.uint8) if want_flags else None
     cnt = DepthFilterCounts()
     check(_lib.load().pr_depth_filter_dev(sd.data(), int(sd.dtype == np.int32), width, height, C.addressof(dp), out.data(), flags.data() if want_flags else None,
                                           C.addressof(cnt)))
-    res = [out]
-    if want_flags:
-        res.append(flags)
-    res.append(tuple(cnt.n))
-    return tuple(res)
+    return _with_extras((out,), ((want_flags, flags),), (tuple(cnt.n),))
 
 
 def depth_filter_host(depth, width: int, height: int, params: Optional[DepthFilterParamsDesc] = None, want_flags: bool = False, **kw):
     """``pr_depth_filter_host``: ``depth_filter`` over a host image (uint16 or int32), on the CPU, from the same definition.  Returns (cleaned
     depth[height, width][, flags uint8[height, width]], counts); runs without a GPU."""
-    dp = _depth_filter_params(params, kw)
+    dp = _params(params, kw, DepthFilterParams)
     dep = _host_depth(depth, width * height)
     out = np.zeros((height, width), dep.dtype)
     flags = np.zeros((height, width), np.uint8) if want_flags else None
     cnt = DepthFilterCounts()
     check(_lib.load().pr_depth_filter_host(ptr(dep), int(dep.dtype == np.int32), width, height, C.addressof(dp), ptr(out), ptr(flags) if want_flags else None,
                                            C.addressof(cnt)))
-    res = [out]
-    if want_flags:
-        res.append(flags)
-    res.append(tuple(cnt.n))
-    return tuple(res)
+    return _with_extras((out,), ((want_flags, flags),), (tuple(cnt.n),))
 
 
 def depth_fuse(frames, width: int, height: int, min_frames: int = 1, depth_out: Optional[DeviceVector] = None, want_count: bool = False):
@@ -2015,9 +1975,7 @@ def depth_fuse(frames, width: int, height: int, min_frames: int = 1, depth_out: 
     if not fs or any(f.dtype != fs[0].dtype for f in fs):
         raise ValueError("depth_fuse takes at least one frame, all of one dtype")
     n_px = width * height
-    out = depth_out if depth_out is not None else DeviceVector(n_px, fs[0].dtype)
-    if out.dtype != fs[0].dtype or out.size() != n_px:
-        raise ValueError("depth_out must have the frames' dtype and size")
+    out = _depth_out(depth_out, n_px, fs[0].dtype)
     count = DeviceVector(n_px, np.uint8) if want_count else None
     table = (C.c_void_p * len(fs))(*[f.data() for f in fs])
     check(_lib.load().pr_depth_fuse_dev(C.addressof(table), len(fs), int(fs[0].dtype == np.int32), n_px, int(min_frames), out.data(),
@@ -2103,12 +2061,6 @@ class ReprojectSource:
         return ReprojectSourceDesc(data_ptr + self.offset_bytes, self.n_points, self.kind, self.width, self.height, 0, fx, fy, cx, cy, (C.c_float * 16)(*self.T))
 
 
-def _reproject_params(params, kw) -> ReprojectParamsDesc:
-    if params is not None and kw:
-        raise ValueError("pass either params or keyword parameters")
-    return params if params is not None else ReprojectParams(**kw)
-
-
 def _reproject_counts(cnt: ReprojectCounts, n_sources: int) -> dict:
     per = [dict(samples=s.samples, invalid=s.invalid, range=s.range, outside=s.outside, drawn=s.drawn, won=s.won) for s in list(cnt.source)[:n_sources]]
     return dict(sources=per, covered=cnt.covered, hidden=cnt.hidden, kept=cnt.kept)
@@ -2143,28 +2095,25 @@ def depth_reproject(sources, width: int, height: int, K, dtype=np.uint16, params
     drawn, won) and the frame's covered, hidden and kept pixels.  The frame goes as it is into ``depth_filter`` (whose fill closes rounding gaps
     and hidden pixels), ``init_Scene_projective_device``, ``scene_planes``, ``scene_segments`` and the scorers.  Parameters: a ``ReprojectParams`` or
     its keywords."""
-    rp = _reproject_params(params, kw)
+    rp = _params(params, kw, ReprojectParams)
     dt = np.dtype(dtype)
     if dt not in (np.uint16, np.int32):
         raise ValueError("the target depth must be CV_16U or CV_32S")
     table, keep = _reproject_table(sources, True)
-    out = depth_out if depth_out is not None else DeviceVector(width * height, dt)
-    if out.dtype != dt or out.size() != width * height:
-        raise ValueError("depth_out must have the target's dtype and size")
+    out = _depth_out(depth_out, width * height, dt)
     src = DeviceVector(width * height, np.uint8) if want_source else None
     cnt = ReprojectCounts()
     fx, fy, cx, cy = _pinhole(K)
     check(_lib.load().pr_depth_reproject_dev(C.addressof(table), len(table), width, height, fx, fy, cx, cy, int(dt == np.int32), C.addressof(rp), out.data(),
                                              src.data() if want_source else None, C.addressof(cnt)))
     del keep
-    counts = _reproject_counts(cnt, len(table))
-    return (out, src, counts) if want_source else (out, counts)
+    return _with_extras((out,), ((want_source, src),), (_reproject_counts(cnt, len(table)),))
 
 
 def depth_reproject_host(sources, width: int, height: int, K, dtype=np.uint16, params: Optional[ReprojectParamsDesc] = None, want_source: bool = False, **kw):
     """``pr_depth_reproject_host``: ``depth_reproject`` over host arrays, on the CPU, from the same definition.  Returns (depth[height, width][,
     source uint8[height, width]], counts); runs without a GPU."""
-    rp = _reproject_params(params, kw)
+    rp = _params(params, kw, ReprojectParams)
     dt = np.dtype(dtype)
     if dt not in (np.uint16, np.int32):
         raise ValueError("the target depth must be CV_16U or CV_32S")
@@ -2176,8 +2125,7 @@ def depth_reproject_host(sources, width: int, height: int, K, dtype=np.uint16, p
     check(_lib.load().pr_depth_reproject_host(C.addressof(table), len(table), width, height, fx, fy, cx, cy, int(dt == np.int32), C.addressof(rp), ptr(out),
                                               ptr(src) if want_source else None, C.addressof(cnt)))
     del keep
-    counts = _reproject_counts(cnt, len(table))
-    return (out, src, counts) if want_source else (out, counts)
+    return _with_extras((out,), ((want_source, src),), (_reproject_counts(cnt, len(table)),))
 
 
 def cloud_to_depth(points, width: int, height: int, K, T=None, **kw):

@@ -18,7 +18,7 @@ OUT = os.environ.get("PR_BUILD_OUT") or os.path.join(HERE, "lib", "libpose_refin
 # one translation unit per stage of the path (kernels + their launchers), the C ABI and the host-side code; headers = shared device code
 SOURCES = ["raster.hip", "d2c.hip", "pyramid.hip", "icp_pass.hip", "icp_debug.hip", "grid_scene.hip", "nn_search.hip", "nn_build.hip", "kd_build.hip", "scene_prep.hip", "verify.hip", "select.hip", "cover.hip", "contour.hip", "contour_fit.hip", "normals.hip", "compose.hip", "pose_dist.hip", "vsd.hip", "solid.hip", "pose_info.hip", "ppf.hip", "planes.hip", "segments.hip", "depth_filter.hip", "reproject.hip", "cloud.hip",
            "pr_context.cpp", "pr_scene.cpp", "pr_icp.cpp", "pr_refine.cpp", "pr_pose_dist.cpp", "pr_pose_info.cpp", "pr_ppf.cpp", "pr_planes.cpp", "pr_segments.cpp", "pr_depth_filter.cpp", "pr_reproject.cpp", "pr_cloud.cpp", "pr_comm.cpp", "pr_host.cpp"]
-HEADERS = ["pr_internal.h", "pr_runtime.h", "pr_solver.inl", "pose_box.h", "pr_tuning.h", "pr_device.h", "pr_launch.h", "proj_query.h", "nn_query.h", "icp_accumulate.h",
+HEADERS = ["pr_internal.h", "pr_runtime.h", "frame_stage.h", "pr_solver.inl", "pose_box.h", "pr_tuning.h", "pr_device.h", "pr_launch.h", "proj_query.h", "nn_query.h", "icp_accumulate.h",
            "icp_solve_device.h", "score_walk.h", "pose_info.h", "contour_fit.h", "ppf.h", "planes.h", "segments.h", "depth_filter.h", "reproject.h", "cloud.h", "jacobi.h"]
 DEPS = SOURCES + HEADERS + [os.path.join(ROOT, "include", "pose_refine.h")]
 OBJ_DIR = os.path.join(HERE, "lib", "obj") if not os.environ.get("PR_BUILD_OUT") else os.environ["PR_BUILD_OUT"] + ".obj"

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "pr_runtime.h"
+#include "frame_stage.h"
 #include "cloud.h"
 
 namespace prr {
@@ -221,17 +222,17 @@ int pr_ppf_cloud_points_dev(const pr_scene_nn *scene, uint32_t stride, pr_vec3 *
     PR_TRY(cloud_size_ok(fn, scene->n_points));
     PR_ENTER();
     const uint32_t n_pts = scene->n_points, n_chunks = ((n_pts - 1) / stride + 1 + prk::kCloudChunk - 1) / prk::kCloudChunk;
-    PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * (2 * (size_t)n_chunks + 1)));
-    uint32_t *chunk_count = g->ppf_tmp.as<uint32_t>(), *chunk_off = chunk_count + n_chunks;
-    HIP_TRY(prk::launch_cloud_sample_count(scene->normal, n_pts, stride, chunk_count, chunk_off, g->stream));
+    PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * ScanRows::words(n_chunks)));
+    const ScanRows chunks(g->ppf_tmp.p, 0, n_chunks);
+    HIP_TRY(prk::launch_cloud_sample_count(scene->normal, n_pts, stride, chunks.count, chunks.off, g->stream));
     uint32_t n = 0;
-    PR_TRY(read_back_words(chunk_off + n_chunks, &n, 1, g->stream));
+    PR_TRY(read_back_words(chunks.total, &n, 1, g->stream));
     *n_out = n;
     if (n > PR_PPF_MAX_SCENE_POINTS) { set_error("%s: %u points at stride %u, at most PR_PPF_MAX_SCENE_POINTS = %d (raise the stride)", fn, n, stride, PR_PPF_MAX_SCENE_POINTS); return PR_ERR_INVALID; }
     if (n == 0) return PR_OK;
-    HIP_TRY(prk::launch_cloud_sample_emit(scene->pcd, scene->normal, n_pts, stride, chunk_off, points_dev_out, normals_dev_out, g->stream));
-    g_writes.note(points_dev_out, sizeof(pr_vec3) * n);
-    g_writes.note(normals_dev_out, sizeof(pr_vec3) * n);
+    note_write(points_dev_out, sizeof(pr_vec3) * n);
+    note_write(normals_dev_out, sizeof(pr_vec3) * n);
+    HIP_TRY(prk::launch_cloud_sample_emit(scene->pcd, scene->normal, n_pts, stride, chunks.off, points_dev_out, normals_dev_out, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return PR_OK;
 }

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "pr_runtime.h"
+#include "frame_stage.h"
 #include "depth_filter.h"
 
 namespace prr {
@@ -11,25 +12,10 @@ namespace prr {
 static int filter_params_ok(const char *fn, const pr_depth_filter_params *p)
 {
     if (!p) { set_error("%s: null pr_depth_filter_params", fn); return PR_ERR_INVALID; }
-    if (p->min_mm > 0x7FFFFFFFu || p->max_mm > 0x7FFFFFFFu || p->tol_mm > 0x7FFFFFFFu) {
-        set_error("%s: pr_depth_filter_params: min_mm, max_mm and tol_mm must not exceed 2^31 - 1 (got %u, %u, %u)", fn, p->min_mm, p->max_mm, p->tol_mm); return PR_ERR_INVALID;
-    }
-    if (p->max_mm != 0 && p->min_mm > p->max_mm) { set_error("%s: pr_depth_filter_params: min_mm = %u lies above max_mm = %u", fn, p->min_mm, p->max_mm); return PR_ERR_INVALID; }
-    if (p->tol_permille > 1000) { set_error("%s: pr_depth_filter_params: tol_permille must not exceed 1000 (got %u)", fn, p->tol_permille); return PR_ERR_INVALID; }
+    PR_TRY(gate_ok(fn, "pr_depth_filter_params", p->min_mm, p->max_mm, p->tol_mm, p->tol_permille));
     if (p->fly_min_support > 8) { set_error("%s: pr_depth_filter_params: fly_min_support must be 0 .. 8 (got %u)", fn, p->fly_min_support); return PR_ERR_INVALID; }
-    if (p->radius > PR_DEPTH_FILTER_MAX_RADIUS) { set_error("%s: pr_depth_filter_params: radius must be 0 .. PR_DEPTH_FILTER_MAX_RADIUS = %d (got %u)", fn, PR_DEPTH_FILTER_MAX_RADIUS, p->radius); return PR_ERR_INVALID; }
-    const uint32_t side = 2 * p->radius + 1;
-    if (p->fill_min != 0 && (p->radius == 0 || p->fill_min > side * side - 1)) {
-        set_error("%s: pr_depth_filter_params: fill_min = %u needs radius >= 1 and must not exceed (2 radius + 1)^2 - 1 = %u", fn, p->fill_min, side * side - 1); return PR_ERR_INVALID;
-    }
+    PR_TRY(window_ok(fn, "pr_depth_filter_params", "radius", p->radius, PR_DEPTH_FILTER_MAX_RADIUS, "fill_min", p->fill_min));
     if (p->reserved != 0) { set_error("%s: pr_depth_filter_params: reserved must be 0", fn); return PR_ERR_INVALID; }
-    return PR_OK;
-}
-static int filter_frame_ok(const char *fn, size_t W, size_t H)
-{
-    if (W == 0 || H == 0 || W > 65535 || H > 65535 || W * H > ((size_t)1 << 26)) {
-        set_error("%s: a frame is 1 .. 65535 on a side and at most 2^26 pixels (got %zux%zu)", fn, W, H); return PR_ERR_INVALID;
-    }
     return PR_OK;
 }
 static int filter_args_ok(const char *fn, const void *in, size_t W, size_t H, const pr_depth_filter_params *p, const void *out)
@@ -37,14 +23,14 @@ static int filter_args_ok(const char *fn, const void *in, size_t W, size_t H, co
     PR_TRY(filter_params_ok(fn, p));
     if (!in || !out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
     if (in == out) { set_error("%s: depth_out must not be depth_in (the filter is a stencil)", fn); return PR_ERR_INVALID; }
-    return filter_frame_ok(fn, W, H);
+    return depth_frame_ok(fn, "a frame", W, H);
 }
 static int fuse_args_ok(const char *fn, const void *const *frames, uint32_t n_frames, size_t n_px, uint32_t min_frames, const void *out)
 {
     if (!frames || !out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
     if (n_frames == 0 || n_frames > PR_DEPTH_FUSE_MAX) { set_error("%s: n_frames must be 1 .. PR_DEPTH_FUSE_MAX = %d (got %u)", fn, PR_DEPTH_FUSE_MAX, n_frames); return PR_ERR_INVALID; }
     if (min_frames == 0 || min_frames > n_frames) { set_error("%s: min_frames must be 1 .. n_frames = %u (got %u)", fn, n_frames, min_frames); return PR_ERR_INVALID; }
-    if (n_px == 0 || n_px > ((size_t)1 << 26)) { set_error("%s: n_px must be 1 .. 2^26 (got %zu)", fn, n_px); return PR_ERR_INVALID; }
+    PR_TRY(depth_frame_ok(fn, n_px));
     for (uint32_t f = 0; f < n_frames; ++f) if (!frames[f]) { set_error("%s: frames[%u] is null", fn, f); return PR_ERR_INVALID; }
     return PR_OK;
 }
@@ -108,8 +94,7 @@ int pr_depth_filter_describe(uint32_t min_mm, uint32_t max_mm, uint32_t tol_mm, 
 int pr_depth_fuse_host(const void *const *frames, uint32_t n_frames, int depth_is_i32, size_t n_px, uint32_t min_frames, void *depth_out, uint8_t *count_out)
 {
     PR_TRY(fuse_args_ok("pr_depth_fuse_host", frames, n_frames, n_px, min_frames, depth_out));
-    if (depth_is_i32) fuse_host(frames, n_frames, n_px, min_frames, static_cast<int32_t *>(depth_out), count_out);
-    else fuse_host(frames, n_frames, n_px, min_frames, static_cast<uint16_t *>(depth_out), count_out);
+    with_depth(depth_out, depth_is_i32 != 0, [&](auto *out) { fuse_host(frames, n_frames, n_px, min_frames, out, count_out); });
     return PR_OK;
 }
 
@@ -120,9 +105,9 @@ int pr_depth_fuse_dev(const void *const *frames, uint32_t n_frames, int depth_is
     PR_ENTER();
     prk::FuseFrames ff;
     for (uint32_t f = 0; f < prk::kDepthFuseMax; ++f) ff.p[f] = frames[f < n_frames ? f : 0];
+    note_write(depth_out_dev, n_px * depth_bytes(depth_is_i32 != 0));
+    if (count_out_dev) note_write(count_out_dev, n_px);
     HIP_TRY(prk::launch_depth_fuse(ff, n_frames, depth_is_i32 != 0, (uint32_t)n_px, min_frames, depth_out_dev, count_out_dev, g->stream));
-    g_writes.note(depth_out_dev, n_px * (depth_is_i32 ? 4 : 2));
-    if (count_out_dev) g_writes.note(count_out_dev, n_px);
     HIP_TRY(hipStreamSynchronize(g->stream));
     return PR_OK;
 }
@@ -131,8 +116,10 @@ int pr_depth_filter_host(const void *depth_in, int depth_is_i32, size_t width, s
                          uint8_t *flags_out, pr_depth_filter_counts *counts_out)
 {
     PR_TRY(filter_args_ok("pr_depth_filter_host", depth_in, width, height, params, depth_out));
-    if (depth_is_i32) filter_host_r(static_cast<const int32_t *>(depth_in), (uint32_t)width, (uint32_t)height, *params, static_cast<int32_t *>(depth_out), flags_out, counts_out);
-    else filter_host_r(static_cast<const uint16_t *>(depth_in), (uint32_t)width, (uint32_t)height, *params, static_cast<uint16_t *>(depth_out), flags_out, counts_out);
+    with_depth(depth_out, depth_is_i32 != 0, [&](auto *out) {
+        using T = std::remove_pointer_t<decltype(out)>;
+        filter_host_r(static_cast<const T *>(depth_in), (uint32_t)width, (uint32_t)height, *params, out, flags_out, counts_out);
+    });
     return PR_OK;
 }
 
@@ -146,10 +133,10 @@ int pr_depth_filter_dev(const void *depth_in_dev, int depth_is_i32, size_t width
     PR_TRY(g->dfilt_tmp.ensure(sizeof(prk::FilterControl)));
     PR_TRY(g->h_dfilt.ensure(sizeof(prk::FilterControl)));
     prk::FilterControl *ctl = g->dfilt_tmp.as<prk::FilterControl>();
+    note_write(depth_out_dev, n_px * depth_bytes(depth_is_i32 != 0));
+    if (flags_dev_out) note_write(flags_dev_out, n_px);
     HIP_TRY(prk::launch_depth_filter_init(ctl, g->stream));
     HIP_TRY(prk::launch_depth_filter(depth_in_dev, depth_is_i32 != 0, (uint32_t)width, (uint32_t)height, *params, depth_out_dev, flags_dev_out, ctl, g->stream));
-    g_writes.note(depth_out_dev, n_px * (depth_is_i32 ? 4 : 2));
-    if (flags_dev_out) g_writes.note(flags_dev_out, n_px);
     HIP_TRY(prk::launch_copy_words32(ctl, g->h_dfilt.dev, (uint32_t)(sizeof(prk::FilterControl) / sizeof(uint32_t)), g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     const prk::FilterControl got = *g->h_dfilt.as<prk::FilterControl>();

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "pr_runtime.h"
+#include "frame_stage.h"
 #include "planes.h"
 #include "jacobi.h"
 
@@ -176,10 +177,10 @@ int pr_scene_planes_host(const float *pcd, const float *normal, const void *dept
         *n_found = k + 1;
     }
     if (depth_out)
-        for (size_t i = 0; i < n_px; ++i) {
-            if (depth_is_i32) static_cast<int32_t *>(depth_out)[i] = labels_out[i] == 0 ? static_cast<const int32_t *>(depth)[i] : 0;
-            else static_cast<uint16_t *>(depth_out)[i] = labels_out[i] == 0 ? static_cast<const uint16_t *>(depth)[i] : (uint16_t)0;
-        }
+        with_depth(depth_out, depth_is_i32 != 0, [&](auto *out) {
+            using T = std::remove_pointer_t<decltype(out)>;
+            for (size_t i = 0; i < n_px; ++i) out[i] = labels_out[i] == 0 ? static_cast<const T *>(depth)[i] : (T)0;
+        });
     return PR_OK;
 }
 
@@ -196,28 +197,26 @@ int pr_scene_planes_dev(const pr_scene_proj *scene, const void *depth_dev, int d
     const pr_plane_params pp = *params;
     const uint32_t W = (uint32_t)scene->width, H = (uint32_t)scene->height, n_px = W * H, gh = (H + pp.stride - 1) / pp.stride;
     const float *pcd = reinterpret_cast<const float *>(scene->pcd), *normal = reinterpret_cast<const float *>(scene->normal);
-    // one device block: the rounds' records | row counts and offsets | the samples' points | their normals | the support table (unless the caller's), a row of PR_PLANE_MAX_CANDIDATES words per round
-    const size_t rounds_bytes = sizeof(prk::PlaneRound) * pp.n_planes, rows_bytes = (sizeof(uint32_t) * (2 * (size_t)gh + 1) + 15) & ~(size_t)15,
-                 pts_bytes = sizeof(prk::PlaneSample) * PR_PLANE_MAX_SAMPLES, nrm_bytes = sizeof(pr_vec3) * PR_PLANE_MAX_SAMPLES,
-                 sup_bytes = support_dev_out ? 0 : sizeof(uint32_t) * (size_t)pp.n_planes * PR_PLANE_MAX_CANDIDATES;
-    PR_TRY(g->plane_tmp.ensure(rounds_bytes + rows_bytes + pts_bytes + nrm_bytes + sup_bytes));
-    PR_TRY(g->h_plane.ensure(rounds_bytes));
-    unsigned char *d = g->plane_tmp.as<unsigned char>();
-    prk::PlaneRound *rounds = reinterpret_cast<prk::PlaneRound *>(d);
-    uint32_t *row_count = reinterpret_cast<uint32_t *>(d + rounds_bytes), *row_off = row_count + gh;
-    prk::PlaneSample *pts = reinterpret_cast<prk::PlaneSample *>(d + rounds_bytes + rows_bytes);
-    pr_vec3 *nrm = reinterpret_cast<pr_vec3 *>(d + rounds_bytes + rows_bytes + pts_bytes);
-    uint32_t *support = support_dev_out ? support_dev_out : reinterpret_cast<uint32_t *>(d + rounds_bytes + rows_bytes + pts_bytes + nrm_bytes);
+    const PlaneBlock l(pp.n_planes, gh, !support_dev_out);
+    PR_TRY(g->plane_tmp.ensure(l.b.bytes()));
+    PR_TRY(g->h_plane.ensure(sizeof(prk::PlaneRound) * pp.n_planes));
+    void *d = g->plane_tmp.p;
+    prk::PlaneRound *rounds = at<prk::PlaneRound>(d, l.rounds);
+    const ScanRows rows(d, l.rows, gh);
+    prk::PlaneSample *pts = at<prk::PlaneSample>(d, l.pts);
+    pr_vec3 *nrm = at<pr_vec3>(d, l.nrm);
+    uint32_t *support = support_dev_out ? support_dev_out : at<uint32_t>(d, l.support);
 
-    HIP_TRY(prk::launch_plane_sample_count(pcd, normal, W, H, pp.stride, row_count, row_off, g->stream));
+    HIP_TRY(prk::launch_plane_sample_count(pcd, normal, W, H, pp.stride, rows.count, rows.off, g->stream));
     uint32_t n = 0, n_cand = 0;
-    PR_TRY(read_back_words(row_off + gh, &n, 1, g->stream));
-    PR_TRY(sample_caps_ok(fn, &pp, n, &n_cand));
+    PR_TRY(read_back_words(rows.total, &n, 1, g->stream));
+    PR_TRY(sample_caps_ok(fn, &pp, n, &n_cand));                    // the last check that refuses: nothing of the caller's is written before
     *n_found = 0;
+    note_write(labels_dev_out, n_px);
+    if (support_dev_out) note_write(support_dev_out, sizeof(uint32_t) * (size_t)pp.n_planes * PR_PLANE_MAX_CANDIDATES);
+    if (depth_dev_out) note_write(depth_dev_out, (size_t)n_px * depth_bytes(depth_is_i32 != 0));
     HIP_TRY(prk::launch_plane_init(pcd, n_px, labels_dev_out, rounds, pp.n_planes, support, pp.n_planes * PR_PLANE_MAX_CANDIDATES, g->stream));
-    g_writes.note(labels_dev_out, n_px);
-    if (support_dev_out) g_writes.note(support_dev_out, sizeof(uint32_t) * (size_t)pp.n_planes * PR_PLANE_MAX_CANDIDATES);
-    if (n > 0) HIP_TRY(prk::launch_plane_sample_emit(pcd, normal, W, H, pp.stride, row_off, pts, nrm, g->stream));
+    if (n > 0) HIP_TRY(prk::launch_plane_sample_emit(pcd, normal, W, H, pp.stride, rows.off, pts, nrm, g->stream));
     const uint32_t round_words = (uint32_t)(sizeof(prk::PlaneRound) / sizeof(uint32_t));
     uint32_t found = 0;
     for (uint32_t k = 0; k < pp.n_planes && n > 0; ++k) {
@@ -230,10 +229,7 @@ int pr_scene_planes_dev(const pr_scene_proj *scene, const void *depth_dev, int d
         HIP_TRY(prk::launch_plane_label(pp, k + 1, plane, pcd, normal, n_px, labels_dev_out, rounds + k, g->stream));
         found = k + 1;
     }
-    if (depth_dev_out) {
-        HIP_TRY(prk::launch_plane_clear_depth(labels_dev_out, depth_dev, depth_dev_out, depth_is_i32 != 0, n_px, g->stream));
-        g_writes.note(depth_dev_out, (size_t)n_px * (depth_is_i32 ? 4 : 2));
-    }
+    if (depth_dev_out) HIP_TRY(prk::launch_plane_clear_depth(labels_dev_out, depth_dev, depth_dev_out, depth_is_i32 != 0, n_px, g->stream));
     if (found) HIP_TRY(prk::launch_copy_words32(rounds, g->h_plane.dev, found * round_words, g->stream));      // the label passes' counts
     HIP_TRY(hipStreamSynchronize(g->stream));
     for (uint32_t k = 0; k < found; ++k) {

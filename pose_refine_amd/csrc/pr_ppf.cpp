@@ -2,6 +2,7 @@
 #include <unordered_set>
 
 #include "pr_runtime.h"
+#include "frame_stage.h"
 #include "ppf.h"
 
 namespace prr {
@@ -187,9 +188,9 @@ int pr_ppf_model_build_dev(const pr_ppf_params *params, const pr_vec3 *points_de
     PR_ENTER();
     const ppf::Tables tb = tables_of(params);
     PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * tb.n_keys));
+    note_write(offsets_dev_out, sizeof(uint32_t) * ((size_t)tb.n_keys + 1));
+    note_write(entries_dev_out, sizeof(pr_ppf_entry) * (size_t)n_model * (n_model - 1));
     HIP_TRY(prk::launch_ppf_model_build(tb, points_dev, normals_dev, n_model, g->ppf_tmp.as<uint32_t>(), offsets_dev_out, entries_dev_out, g->stream));
-    g_writes.note(offsets_dev_out, sizeof(uint32_t) * ((size_t)tb.n_keys + 1));
-    g_writes.note(entries_dev_out, sizeof(pr_ppf_entry) * (size_t)n_model * (n_model - 1));
     return read_back_words(offsets_dev_out + tb.n_keys, n_entries_out, 1, g->stream);
 }
 
@@ -201,18 +202,18 @@ int pr_ppf_scene_points_dev(const pr_scene_proj *scene, uint32_t stride, pr_vec3
     PR_TRY(frame_ok(fn, scene->width, scene->height));
     PR_ENTER();
     const uint32_t W = (uint32_t)scene->width, H = (uint32_t)scene->height, gh = (H + stride - 1) / stride;
-    PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * (2 * (size_t)gh + 1)));
-    uint32_t *row_count = g->ppf_tmp.as<uint32_t>(), *row_off = row_count + gh;
+    PR_TRY(g->ppf_tmp.ensure(sizeof(uint32_t) * ScanRows::words(gh)));
+    const ScanRows rows(g->ppf_tmp.p, 0, gh);
     const float *pcd = reinterpret_cast<const float *>(scene->pcd), *normal = reinterpret_cast<const float *>(scene->normal);
-    HIP_TRY(prk::launch_ppf_scene_count(pcd, normal, W, H, stride, row_count, row_off, g->stream));
+    HIP_TRY(prk::launch_ppf_scene_count(pcd, normal, W, H, stride, rows.count, rows.off, g->stream));
     uint32_t n = 0;
-    PR_TRY(read_back_words(row_off + gh, &n, 1, g->stream));
+    PR_TRY(read_back_words(rows.total, &n, 1, g->stream));
     *n_out = n;
     if (n > PR_PPF_MAX_SCENE_POINTS) { set_error("%s: %u points at stride %u, at most PR_PPF_MAX_SCENE_POINTS = %d (raise the stride)", fn, n, stride, PR_PPF_MAX_SCENE_POINTS); return PR_ERR_INVALID; }
     if (n == 0) return PR_OK;
-    HIP_TRY(prk::launch_ppf_scene_emit(pcd, normal, W, H, stride, row_off, points_dev_out, normals_dev_out, g->stream));
-    g_writes.note(points_dev_out, sizeof(pr_vec3) * n);
-    g_writes.note(normals_dev_out, sizeof(pr_vec3) * n);
+    note_write(points_dev_out, sizeof(pr_vec3) * n);
+    note_write(normals_dev_out, sizeof(pr_vec3) * n);
+    HIP_TRY(prk::launch_ppf_scene_emit(pcd, normal, W, H, stride, rows.off, points_dev_out, normals_dev_out, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return PR_OK;
 }
@@ -231,19 +232,17 @@ int pr_ppf_vote(const pr_ppf_params *params, const uint32_t *offsets_dev, const 
     }
     PR_ENTER();
     const ppf::Tables tb = tables_of(params);
-    const size_t n_pk = (size_t)n_refs * n_peaks, pk_bytes = sizeof(pr_ppf_peak) * n_pk, bytes = pk_bytes + sizeof(prk::PpfRef) * n_refs;      // multiples of 4 both
-    PR_TRY(g->ppf_out.ensure(bytes));
-    PR_TRY(g->h_ppf.ensure(bytes));
-    pr_ppf_peak *peaks_d = g->ppf_out.as<pr_ppf_peak>();
-    prk::PpfRef *refs_d = reinterpret_cast<prk::PpfRef *>(g->ppf_out.as<unsigned char>() + pk_bytes);
+    const VoteBlock l(0, n_refs, n_peaks);            // the device block and its pinned twin
+    PR_TRY(g->ppf_out.ensure(l.b.bytes()));
+    PR_TRY(g->h_ppf.ensure(l.b.bytes()));
+    void *d = g->ppf_out.p, *h = g->h_ppf.p;
+    if (acc_dev_out) note_write(acc_dev_out, sizeof(uint32_t) * (size_t)n_refs * n_model * tb.n_alpha);
     HIP_TRY(prk::launch_ppf_vote(tb, offsets_dev, entries_dev, n_model, scene_points_dev, scene_normals_dev, n_scene, ref_first, ref_stride, n_refs, n_peaks,
-                                 peaks_d, refs_d, acc_dev_out, opt.ppf_walk != 0, g->stream));
-    if (acc_dev_out) g_writes.note(acc_dev_out, sizeof(uint32_t) * (size_t)n_refs * n_model * tb.n_alpha);
-    HIP_TRY(prk::launch_copy_words32(g->ppf_out.p, g->h_ppf.dev, (uint32_t)(bytes / sizeof(uint32_t)), g->stream));
+                                 at<pr_ppf_peak>(d, l.peaks), at<prk::PpfRef>(d, l.refs), acc_dev_out, opt.ppf_walk != 0, g->stream));
+    HIP_TRY(prk::launch_copy_words32(at<pr_ppf_peak>(d, l.peaks), at<pr_ppf_peak>(g->h_ppf.dev, l.peaks), l.back_words(), g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    const pr_ppf_peak *pk = g->h_ppf.as<pr_ppf_peak>();
-    const prk::PpfRef *rf = reinterpret_cast<const prk::PpfRef *>(g->h_ppf.as<unsigned char>() + pk_bytes);
-    peaks_out(params, model_points_host, model_normals_host, n_model, pk, rf, n_pk, n_peaks, peaks_host, poses_host);
+    peaks_out(params, model_points_host, model_normals_host, n_model, at<pr_ppf_peak>(h, l.peaks), at<prk::PpfRef>(h, l.refs), (size_t)n_refs * n_peaks, n_peaks, peaks_host,
+              poses_host);
     return PR_OK;
 }
 
@@ -270,11 +269,10 @@ int pr_ppf_vote_multi(const pr_ppf_model *models, uint32_t n_models, const pr_ve
         }
     if (!scene_points_dev || !scene_normals_dev || !peaks_host || !poses_host) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
     PR_ENTER();
-    // one device block and its pinned twin: the model records (staged to the device) | the peaks of all models | the references (both read back)
-    const size_t n_pk = (size_t)n_refs * n_peaks, tab_bytes = sizeof(prk::PpfModelRec) * n_models, pk_bytes = sizeof(pr_ppf_peak) * n_pk * n_models,
-                 back_bytes = pk_bytes + sizeof(prk::PpfRef) * n_refs;                                                                  // multiples of 4 both
-    PR_TRY(g->ppf_out.ensure(tab_bytes + back_bytes));
-    PR_TRY(g->h_ppf.ensure(tab_bytes + back_bytes));
+    const VoteBlock l(n_models, n_refs, n_peaks);     // the device block and its pinned twin
+    const size_t n_pk = (size_t)n_refs * n_peaks;
+    PR_TRY(g->ppf_out.ensure(l.b.bytes()));
+    PR_TRY(g->h_ppf.ensure(l.b.bytes()));
     // The rows of the launch are the models by n_model, largest first: a model's pair table, and with it a workgroup's walk, grows with n_model^2, and
     // a launch that ends with its longest workgroups has a long tail (profiles/ppf_multi/README.md: the same table takes 1.48 ms in the caller's
     // order, 1.19 ms largest first, 1.54 ms largest last).  A record carries its model's place in the outputs, so the row order is free.
@@ -285,21 +283,20 @@ int pr_ppf_vote_multi(const pr_ppf_model *models, uint32_t n_models, const pr_ve
         acc_words += (uint64_t)n_refs * models[k].n_model * models[k].params->n_alpha;
     }
     std::stable_sort(row, row + n_models, [&](uint32_t a, uint32_t b) { return models[a].n_model > models[b].n_model; });
-    prk::PpfModelRec *rec = g->h_ppf.as<prk::PpfModelRec>();
+    void *d = g->ppf_out.p, *h = g->h_ppf.p, *hm = g->h_ppf.dev;
+    prk::PpfModelRec *rec = at<prk::PpfModelRec>(h, l.models);
     for (uint32_t r = 0; r < n_models; ++r) {
         const pr_ppf_model &m = models[row[r]];
         rec[r] = prk::PpfModelRec{ tables_of(m.params), m.offsets_dev, m.entries_dev, m.n_model, (uint32_t)(row[r] * n_pk), acc_base[row[r]], 0 };
     }
-    unsigned char *d = g->ppf_out.as<unsigned char>(), *h = g->h_ppf.as<unsigned char>(), *hm = g->h_ppf.dev_as<unsigned char>();
-    HIP_TRY(prk::launch_stage_words(hm, d, tab_bytes, g->stream));
-    HIP_TRY(prk::launch_ppf_vote_multi(reinterpret_cast<const prk::PpfModelRec *>(d), n_models, max_cells, scene_points_dev, scene_normals_dev, n_scene, ref_first,
-                                       ref_stride, n_refs, n_peaks, reinterpret_cast<pr_ppf_peak *>(d + tab_bytes), reinterpret_cast<prk::PpfRef *>(d + tab_bytes + pk_bytes),
-                                       acc_dev_out, opt.ppf_walk != 0, g->stream));
-    if (acc_dev_out) g_writes.note(acc_dev_out, sizeof(uint32_t) * acc_words);
-    HIP_TRY(prk::launch_copy_words32(d + tab_bytes, hm + tab_bytes, (uint32_t)(back_bytes / sizeof(uint32_t)), g->stream));
+    if (acc_dev_out) note_write(acc_dev_out, sizeof(uint32_t) * acc_words);
+    HIP_TRY(prk::launch_stage_words(at<prk::PpfModelRec>(hm, l.models), at<prk::PpfModelRec>(d, l.models), l.peaks - l.models, g->stream));
+    HIP_TRY(prk::launch_ppf_vote_multi(at<prk::PpfModelRec>(d, l.models), n_models, max_cells, scene_points_dev, scene_normals_dev, n_scene, ref_first, ref_stride, n_refs,
+                                       n_peaks, at<pr_ppf_peak>(d, l.peaks), at<prk::PpfRef>(d, l.refs), acc_dev_out, opt.ppf_walk != 0, g->stream));
+    HIP_TRY(prk::launch_copy_words32(at<pr_ppf_peak>(d, l.peaks), at<pr_ppf_peak>(hm, l.peaks), l.back_words(), g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    const pr_ppf_peak *pk = reinterpret_cast<const pr_ppf_peak *>(h + tab_bytes);
-    const prk::PpfRef *rf = reinterpret_cast<const prk::PpfRef *>(h + tab_bytes + pk_bytes);
+    const pr_ppf_peak *pk = at<pr_ppf_peak>(h, l.peaks);
+    const prk::PpfRef *rf = at<prk::PpfRef>(h, l.refs);
     for (uint32_t k = 0; k < n_models; ++k)
         peaks_out(models[k].params, models[k].points_host, models[k].normals_host, models[k].n_model, pk + k * n_pk, rf, n_pk, n_peaks, peaks_host + k * n_pk,
                   poses_host + k * n_pk);

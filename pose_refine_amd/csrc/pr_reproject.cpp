@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "pr_runtime.h"
+#include "frame_stage.h"
 #include "depth_filter.h"
 #include "reproject.h"
 
@@ -13,20 +14,11 @@ static int reproject_params_ok(const char *fn, const pr_reproject_params *p)
 {
     if (!p) { set_error("%s: null pr_reproject_params", fn); return PR_ERR_INVALID; }
     if (p->splat < 1 || p->splat > 3) { set_error("%s: pr_reproject_params: splat must be 1 .. 3 (got %u)", fn, p->splat); return PR_ERR_INVALID; }
-    if (p->min_mm > 0x7FFFFFFFu || p->max_mm > 0x7FFFFFFFu || p->tol_mm > 0x7FFFFFFFu) {
-        set_error("%s: pr_reproject_params: min_mm, max_mm and tol_mm must not exceed 2^31 - 1 (got %u, %u, %u)", fn, p->min_mm, p->max_mm, p->tol_mm); return PR_ERR_INVALID;
-    }
-    if (p->max_mm != 0 && p->min_mm > p->max_mm) { set_error("%s: pr_reproject_params: min_mm = %u lies above max_mm = %u", fn, p->min_mm, p->max_mm); return PR_ERR_INVALID; }
-    if (p->tol_permille > 1000) { set_error("%s: pr_reproject_params: tol_permille must not exceed 1000 (got %u)", fn, p->tol_permille); return PR_ERR_INVALID; }
-    if (p->occl_radius > PR_REPROJECT_MAX_RADIUS) { set_error("%s: pr_reproject_params: occl_radius must be 0 .. PR_REPROJECT_MAX_RADIUS = %d (got %u)", fn, PR_REPROJECT_MAX_RADIUS, p->occl_radius); return PR_ERR_INVALID; }
-    const uint32_t side = 2 * p->occl_radius + 1;
-    if (p->occl_min_front != 0 && (p->occl_radius == 0 || p->occl_min_front > side * side - 1)) {
-        set_error("%s: pr_reproject_params: occl_min_front = %u needs occl_radius >= 1 and must not exceed (2 occl_radius + 1)^2 - 1 = %u", fn, p->occl_min_front, side * side - 1); return PR_ERR_INVALID;
-    }
+    PR_TRY(gate_ok(fn, "pr_reproject_params", p->min_mm, p->max_mm, p->tol_mm, p->tol_permille));
+    PR_TRY(window_ok(fn, "pr_reproject_params", "occl_radius", p->occl_radius, PR_REPROJECT_MAX_RADIUS, "occl_min_front", p->occl_min_front));
     if (p->reserved != 0) { set_error("%s: pr_reproject_params: reserved must be 0", fn); return PR_ERR_INVALID; }
     return PR_OK;
 }
-static bool reproject_frame_ok(size_t W, size_t H) { return W != 0 && H != 0 && W <= 65535 && H <= 65535 && W * H <= ((size_t)1 << 26); }
 static bool pinhole_ok(float fx, float fy, float cx, float cy) { return std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy) && fx > 0.0f && fy > 0.0f; }
 static int reproject_args_ok(const char *fn, const pr_reproject_source *src, uint32_t n_sources, size_t W, size_t H, float fx, float fy, float cx, float cy,
                              const pr_reproject_params *p, const void *out)
@@ -34,7 +26,7 @@ static int reproject_args_ok(const char *fn, const pr_reproject_source *src, uin
     PR_TRY(reproject_params_ok(fn, p));
     if (!src || !out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
     if (n_sources == 0 || n_sources > PR_REPROJECT_MAX_SOURCES) { set_error("%s: n_sources must be 1 .. PR_REPROJECT_MAX_SOURCES = %d (got %u)", fn, PR_REPROJECT_MAX_SOURCES, n_sources); return PR_ERR_INVALID; }
-    if (!reproject_frame_ok(W, H)) { set_error("%s: the target is 1 .. 65535 on a side and at most 2^26 pixels (got %zux%zu)", fn, W, H); return PR_ERR_INVALID; }
+    PR_TRY(depth_frame_ok(fn, "the target", W, H));
     if (!pinhole_ok(fx, fy, cx, cy)) { set_error("%s: the target's intrinsics must be finite with fx, fy > 0", fn); return PR_ERR_INVALID; }
     for (uint32_t i = 0; i < n_sources; ++i) {
         const pr_reproject_source &s = src[i];
@@ -43,10 +35,12 @@ static int reproject_args_ok(const char *fn, const pr_reproject_source *src, uin
         if (s.reserved != 0) { set_error("%s: sources[%u].reserved must be 0", fn, i); return PR_ERR_INVALID; }
         const uintptr_t at = reinterpret_cast<uintptr_t>(s.data);
         if (s.kind == PR_SRC_DEPTH_U16 || s.kind == PR_SRC_DEPTH_I32) {
-            if (!reproject_frame_ok(s.width, s.height)) { set_error("%s: sources[%u]: a frame is 1 .. 65535 on a side and at most 2^26 pixels (got %ux%u)", fn, i, s.width, s.height); return PR_ERR_INVALID; }
+            char what[40];
+            std::snprintf(what, sizeof what, "sources[%u]: a frame", i);
+            PR_TRY(depth_frame_ok(fn, what, s.width, s.height));
             if (s.n_points != 0) { set_error("%s: sources[%u]: n_points of a frame must be 0", fn, i); return PR_ERR_INVALID; }
             if (!pinhole_ok(s.fx, s.fy, s.cx, s.cy)) { set_error("%s: sources[%u]: the intrinsics must be finite with fx, fy > 0", fn, i); return PR_ERR_INVALID; }
-            if (at % (s.kind == PR_SRC_DEPTH_I32 ? 4u : 2u)) { set_error("%s: sources[%u].data is not aligned to its element", fn, i); return PR_ERR_INVALID; }
+            if (at % depth_bytes(s.kind == PR_SRC_DEPTH_I32)) { set_error("%s: sources[%u].data is not aligned to its element", fn, i); return PR_ERR_INVALID; }
         } else if (s.kind == PR_SRC_CLOUD) {
             if (s.n_points == 0 || s.n_points > ((uint64_t)1 << 26)) { set_error("%s: sources[%u]: a cloud holds 1 .. 2^26 points (got %llu)", fn, i, (unsigned long long)s.n_points); return PR_ERR_INVALID; }
             if (at % 4u) { set_error("%s: sources[%u].data is not aligned to its element", fn, i); return PR_ERR_INVALID; }
@@ -74,9 +68,8 @@ static void scatter_point(const rpj::Rigid &T, const rpj::Target &t, uint32_t so
         for (int x = sp.x0; x < sp.x1; ++x) { uint32_t &k = keys[(size_t)y * t.width + (size_t)x]; k = key < k ? key : k; }
 }
 template <class D>
-static void scatter_frame_host(const pr_reproject_source &s, uint32_t source, const rpj::Target &t, std::vector<uint32_t> &keys, uint32_t (&n)[4])
+static void scatter_frame_host(const D *d, const pr_reproject_source &s, uint32_t source, const rpj::Target &t, std::vector<uint32_t> &keys, uint32_t (&n)[4])
 {
-    const D *d = static_cast<const D *>(s.data);
     const rpj::Rigid T = rigid_of(s);
     for (uint32_t y = 0; y < s.height; ++y)
         for (uint32_t x = 0; x < s.width; ++x) {
@@ -135,8 +128,7 @@ int pr_depth_reproject_host(const pr_reproject_source *sources, uint32_t n_sourc
     for (uint32_t i = 0; i < n_sources; ++i) {
         const pr_reproject_source &s = sources[i];
         uint32_t n[4] = { 0u, 0u, 0u, 0u };
-        if (s.kind == PR_SRC_DEPTH_U16) scatter_frame_host<uint16_t>(s, i, t, keys, n);
-        else if (s.kind == PR_SRC_DEPTH_I32) scatter_frame_host<int32_t>(s, i, t, keys, n);
+        if (s.kind != PR_SRC_CLOUD) with_depth(s.data, s.kind == PR_SRC_DEPTH_I32, [&](auto *d) { scatter_frame_host(d, s, i, t, keys, n); });
         else {
             const pr_vec3 *pts = static_cast<const pr_vec3 *>(s.data);
             const rpj::Rigid T = rigid_of(s);
@@ -145,12 +137,12 @@ int pr_depth_reproject_host(const pr_reproject_source *sources, uint32_t n_sourc
         c.source[i].samples = n[0]; c.source[i].invalid = n[rpj::kInvalid]; c.source[i].range = n[rpj::kRange]; c.source[i].outside = n[rpj::kOutside];
         c.source[i].drawn = n[0] - n[1] - n[2] - n[3];
     }
-    const auto resolve = [&](auto *out) {
-        if (params->occl_radius == 0) resolve_host<std::remove_pointer_t<decltype(out)>, 0>(keys, W, H, *params, out, source_out, c);
-        else if (params->occl_radius == 1) resolve_host<std::remove_pointer_t<decltype(out)>, 1>(keys, W, H, *params, out, source_out, c);
-        else resolve_host<std::remove_pointer_t<decltype(out)>, 2>(keys, W, H, *params, out, source_out, c);
-    };
-    if (depth_is_i32) resolve(static_cast<int32_t *>(depth_out)); else resolve(static_cast<uint16_t *>(depth_out));
+    with_depth(depth_out, depth_is_i32 != 0, [&](auto *out) {
+        using O = std::remove_pointer_t<decltype(out)>;
+        if (params->occl_radius == 0) resolve_host<O, 0>(keys, W, H, *params, out, source_out, c);
+        else if (params->occl_radius == 1) resolve_host<O, 1>(keys, W, H, *params, out, source_out, c);
+        else resolve_host<O, 2>(keys, W, H, *params, out, source_out, c);
+    });
     if (counts_out) *counts_out = c;
     return PR_OK;
 }
@@ -176,18 +168,19 @@ int pr_depth_reproject_dev(const pr_reproject_source *sources, uint32_t n_source
     }
     for (uint32_t i = n_sources; i < rpj::kMaxSources; ++i) { ss.s[i] = ss.s[0]; ss.s[i].n = 0u; ss.s[i].first_block = blocks; }      // (not read: no workgroup is theirs)
     ss.n_sources = n_sources; ss.n_blocks = blocks;
-    // the key plane and the control words behind it
-    const size_t ctl_at = ((size_t)n_px * sizeof(uint32_t) + 255u) & ~(size_t)255u;
-    PR_TRY(g->reproj_tmp.ensure(ctl_at + sizeof(prk::ReprojControl)));
+    // one device block: the key plane | (on 256 bytes) the control words
+    Block b;
+    const size_t keys_at = b.take<uint32_t>(n_px), ctl_at = b.take<prk::ReprojControl>(1, 256);
+    PR_TRY(g->reproj_tmp.ensure(b.bytes()));
     PR_TRY(g->h_reproj.ensure(sizeof(prk::ReprojControl)));
-    uint32_t *keys = g->reproj_tmp.as<uint32_t>();
-    prk::ReprojControl *ctl = reinterpret_cast<prk::ReprojControl *>(g->reproj_tmp.as<char>() + ctl_at);
+    uint32_t *keys = at<uint32_t>(g->reproj_tmp.p, keys_at);
+    prk::ReprojControl *ctl = at<prk::ReprojControl>(g->reproj_tmp.p, ctl_at);
     g->h_reproj.as<prk::ReprojControl>()->done = 0u;             // (what an earlier call left there is not taken for this call's)
+    note_write(depth_out_dev, (size_t)n_px * depth_bytes(depth_is_i32 != 0));
+    if (source_dev_out) note_write(source_dev_out, n_px);
     HIP_TRY(prk::launch_reproject_clear(keys, n_px, ctl, g->stream));
     HIP_TRY(prk::launch_reproject_scatter(ss, t, keys, ctl, g->stream));
     HIP_TRY(prk::launch_reproject_resolve(keys, W, H, *params, depth_is_i32 != 0, depth_out_dev, source_dev_out, ctl, g->h_reproj.dev_as<prk::ReprojControl>(), g->stream));
-    g_writes.note(depth_out_dev, (size_t)n_px * (depth_is_i32 ? 4 : 2));
-    if (source_dev_out) g_writes.note(source_dev_out, n_px);
     HIP_TRY(hipStreamSynchronize(g->stream));
     const prk::ReprojControl got = *g->h_reproj.as<prk::ReprojControl>();
     const uint32_t n_tiles = ((W + 63u) / 64u) * ((H + 15u) / 16u);

@@ -1,5 +1,6 @@
 // pr_scene.cpp -- scene caches (packed projective record, kd-tree traversal records, pixel grid) and device-side scene preparation
 #include "pr_runtime.h"
+#include "frame_stage.h"
 
 namespace prr {
 
@@ -278,8 +279,9 @@ int pr_scene_proj_prepare_dev(const void *depth_dev, int depth_is_i32, const flo
     PR_ENTER();
     if (!depth_dev || !K || !pcd_dev_out || !normal_dev_out || width == 0 || height == 0) { set_error("pr_scene_proj_prepare_dev: bad arguments"); return PR_ERR_INVALID; }
     note_write(pcd_dev_out, width * height * sizeof(pr_vec3)); note_write(normal_dev_out, width * height * sizeof(pr_vec3));
-    if (depth_is_i32) HIP_TRY(prk::launch_scene_proj_prepare<int32_t>(static_cast<const int32_t *>(depth_dev), (uint32_t)width, (uint32_t)height, K[0], K[4], K[2], K[5], pcd_dev_out, normal_dev_out, g->stream));
-    else HIP_TRY(prk::launch_scene_proj_prepare<uint16_t>(static_cast<const uint16_t *>(depth_dev), (uint32_t)width, (uint32_t)height, K[0], K[4], K[2], K[5], pcd_dev_out, normal_dev_out, g->stream));
+    HIP_TRY(with_depth(depth_dev, depth_is_i32 != 0, [&](auto *depth) {
+        return prk::launch_scene_proj_prepare(depth, (uint32_t)width, (uint32_t)height, K[0], K[4], K[2], K[5], pcd_dev_out, normal_dev_out, g->stream);
+    }));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return PR_OK;
 }
@@ -299,10 +301,9 @@ int pr_scene_nn_prepare_dev(const void *depth_dev, int depth_is_i32, const float
     PR_ENTER();
     if (!depth_dev || !K || !pcd_dev_out || !normal_dev_out || !nodes_dev_out || width <= 0 || height <= 0) { set_error("pr_scene_nn_prepare_dev: bad arguments"); return PR_ERR_INVALID; }
     note_write(pcd_dev_out, (size_t)width * height * sizeof(pr_vec3)); note_write(normal_dev_out, (size_t)width * height * sizeof(pr_vec3)); note_write(nodes_dev_out, cap_nodes * sizeof(pr_kdnode));
-    if (depth_is_i32) return scene_nn_prepare_dev_t<int32_t>(static_cast<const int32_t *>(depth_dev), K, (uint32_t)width, (uint32_t)height, max_leaf,
-                                                             pcd_dev_out, normal_dev_out, nodes_dev_out, cap_nodes, n_points, n_nodes);
-    return scene_nn_prepare_dev_t<uint16_t>(static_cast<const uint16_t *>(depth_dev), K, (uint32_t)width, (uint32_t)height, max_leaf,
-                                            pcd_dev_out, normal_dev_out, nodes_dev_out, cap_nodes, n_points, n_nodes);
+    return with_depth(depth_dev, depth_is_i32 != 0, [&](auto *depth) {
+        return scene_nn_prepare_dev_t(depth, K, (uint32_t)width, (uint32_t)height, max_leaf, pcd_dev_out, normal_dev_out, nodes_dev_out, cap_nodes, n_points, n_nodes);
+    });
 }
 
 // pr_scene_grid over the box [lo, hi]: pure host code.  dim[a] = floor((hi[a] - lo[a]) * inv_cell) + 1 in float32, so that hi itself -- and with it the

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "pr_runtime.h"
+#include "frame_stage.h"
 #include "segments.h"
 
 namespace prr {
@@ -15,13 +16,6 @@ static int segment_params_ok(const char *fn, const pr_segment_params *sp)
     if (sp->min_pixels == 0) { set_error("%s: pr_segment_params: min_pixels must not be 0", fn); return PR_ERR_INVALID; }
     if (sp->max_segments == 0 || sp->max_segments > PR_SEGMENT_MAX) { set_error("%s: pr_segment_params: max_segments must be 1 .. PR_SEGMENT_MAX = %d (got %u)", fn, PR_SEGMENT_MAX, sp->max_segments); return PR_ERR_INVALID; }
     if (sp->reserved != 0) { set_error("%s: pr_segment_params: reserved must be 0", fn); return PR_ERR_INVALID; }
-    return PR_OK;
-}
-static int segment_frame_ok(const char *fn, size_t W, size_t H)
-{
-    if (W == 0 || H == 0 || W > 65535 || H > 65535 || W * H > ((size_t)1 << 26)) {
-        set_error("%s: a frame is 1 .. 65535 on a side and at most 2^26 pixels (got %zux%zu)", fn, W, H); return PR_ERR_INVALID;
-    }
     return PR_OK;
 }
 static int segment_cap_ok(const char *fn, uint32_t n_qualifying, uint32_t min_pixels)
@@ -110,10 +104,7 @@ static int segments_host(const char *fn, const T *depth, uint32_t W, uint32_t H,
     return PR_OK;
 }
 
-// the pinned block of a call: the control words and the roots | the rank table | the records
-constexpr size_t kSegPinRoots = sizeof(prk::SegControl) + sizeof(prk::SegRoot) * PR_SEGMENT_MAX_ROOTS, kSegRankBytes = sizeof(uint16_t) * PR_SEGMENT_MAX_ROOTS,
-                 kSegPinBytes = kSegPinRoots + kSegRankBytes + sizeof(segments::Acc) * PR_SEGMENT_MAX;
-constexpr size_t kSegKeepBytes = ((PR_SEGMENT_MAX + 1 + 31) / 32 * sizeof(uint32_t) + 15) & ~(size_t)15;      // pr_segment_depth_dev's keep bits, whole 16-byte words
+constexpr size_t kSegKeepBytes = 16 * ((PR_SEGMENT_MAX + 1 + 127) / 128);      // pr_segment_depth_dev's keep bits, whole 16-byte words (128 labels each)
 
 }  // namespace prr
 
@@ -137,9 +128,10 @@ int pr_scene_segments_host(const void *depth, int depth_is_i32, size_t width, si
     const char *fn = "pr_scene_segments_host";
     PR_TRY(segment_params_ok(fn, params));
     if (!depth || !labels_out || !segments_out || !n_found) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
-    PR_TRY(segment_frame_ok(fn, width, height));
-    if (depth_is_i32) return segments_host(fn, static_cast<const int32_t *>(depth), (uint32_t)width, (uint32_t)height, *params, labels_out, roots_out, segments_out, n_found, n_qualifying, n_components);
-    return segments_host(fn, static_cast<const uint16_t *>(depth), (uint32_t)width, (uint32_t)height, *params, labels_out, roots_out, segments_out, n_found, n_qualifying, n_components);
+    PR_TRY(depth_frame_ok(fn, "a frame", width, height));
+    return with_depth(depth, depth_is_i32 != 0, [&](auto *d) {
+        return segments_host(fn, d, (uint32_t)width, (uint32_t)height, *params, labels_out, roots_out, segments_out, n_found, n_qualifying, n_components);
+    });
 }
 
 int pr_scene_segments_dev(const void *depth_dev, int depth_is_i32, size_t width, size_t height, const pr_segment_params *params, uint16_t *labels_dev_out,
@@ -148,45 +140,43 @@ int pr_scene_segments_dev(const void *depth_dev, int depth_is_i32, size_t width,
     const char *fn = "pr_scene_segments_dev";
     PR_TRY(segment_params_ok(fn, params));                          // every check before any device use
     if (!depth_dev || !labels_dev_out || !segments_host || !n_found) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
-    PR_TRY(segment_frame_ok(fn, width, height));
+    PR_TRY(depth_frame_ok(fn, "a frame", width, height));
     PR_ENTER();
     const pr_segment_params sp = *params;
     const uint32_t W = (uint32_t)width, H = (uint32_t)height, n_px = W * H, n_chunks = (n_px + prk::kSegChunk - 1) / prk::kSegChunk;
     const bool i32 = depth_is_i32 != 0;
-    // one device block: control words | the records | the rank table | the qualifying roots | chunk counts and offsets | the forest | the per-root counts
-    const size_t acc_off = sizeof(prk::SegControl), rank_off = acc_off + sizeof(segments::Acc) * sp.max_segments, roots_off = rank_off + kSegRankBytes,
-                 chunk_off_b = roots_off + sizeof(prk::SegRoot) * PR_SEGMENT_MAX_ROOTS, parent_off = chunk_off_b + ((sizeof(uint32_t) * (2 * (size_t)n_chunks + 1) + 15) & ~(size_t)15),
-                 count_off = parent_off + sizeof(uint32_t) * (size_t)n_px;
-    PR_TRY(g->seg_tmp.ensure(count_off + sizeof(uint32_t) * (size_t)n_px));
-    PR_TRY(g->h_seg.ensure(kSegPinBytes));
-    unsigned char *d = g->seg_tmp.as<unsigned char>(), *hp = g->h_seg.as<unsigned char>(), *hd = g->h_seg.dev_as<unsigned char>();
-    prk::SegControl *ctl = reinterpret_cast<prk::SegControl *>(d);
-    segments::Acc *acc = reinterpret_cast<segments::Acc *>(d + acc_off);
-    uint16_t *rank_dev = reinterpret_cast<uint16_t *>(d + rank_off);
-    prk::SegRoot *roots = reinterpret_cast<prk::SegRoot *>(d + roots_off);
-    uint32_t *chunk_count = reinterpret_cast<uint32_t *>(d + chunk_off_b), *chunk_off = chunk_count + n_chunks;
-    uint32_t *parent = reinterpret_cast<uint32_t *>(d + parent_off), *count = reinterpret_cast<uint32_t *>(d + count_off);
+    const SegBlock l(sp.max_segments, n_chunks, n_px);
+    const SegPinned pin;
+    PR_TRY(g->seg_tmp.ensure(l.b.bytes()));
+    PR_TRY(g->h_seg.ensure(pin.b.bytes()));
+    void *d = g->seg_tmp.p, *hp = g->h_seg.p, *hd = g->h_seg.dev;
+    prk::SegControl *ctl = at<prk::SegControl>(d, l.ctl);
+    segments::Acc *acc = at<segments::Acc>(d, l.acc);
+    uint16_t *rank_dev = at<uint16_t>(d, l.rank);
+    prk::SegRoot *roots = at<prk::SegRoot>(d, l.roots);
+    const ScanRows chunks(d, l.chunks, n_chunks);
+    uint32_t *parent = at<uint32_t>(d, l.parent), *count = at<uint32_t>(d, l.count);
 
     HIP_TRY(prk::launch_segment_init(ctl, acc, sp.max_segments, g->stream));
     HIP_TRY(prk::launch_segment_tiles(depth_dev, i32, W, H, sp.jump_mm, parent, count, g->stream));
     HIP_TRY(prk::launch_segment_seams(depth_dev, i32, W, H, sp.jump_mm, parent, g->stream));
     HIP_TRY(prk::launch_segment_flatten(W, H, parent, count, g->stream));
-    HIP_TRY(prk::launch_segment_compact(parent, count, n_px, sp.min_pixels, chunk_count, chunk_off, roots, ctl, hd, g->stream));
+    HIP_TRY(prk::launch_segment_compact(parent, count, n_px, sp.min_pixels, chunks.count, chunks.off, roots, ctl, hd, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    const prk::SegControl c = *reinterpret_cast<const prk::SegControl *>(hp);
+    const prk::SegControl c = *at<prk::SegControl>(hp, pin.ctl);
     PR_TRY(segment_cap_ok(fn, c.n_qualifying, sp.min_pixels));      // nothing of the caller's written before
-    const prk::SegRoot *list = reinterpret_cast<const prk::SegRoot *>(hp + sizeof(prk::SegControl));
+    const prk::SegRoot *list = at<prk::SegRoot>(hp, pin.roots);
     std::vector<uint32_t> order;
-    const uint32_t found = rank_roots(list, c.n_qualifying, sp.max_segments, order, reinterpret_cast<uint16_t *>(hp + kSegPinRoots));
+    const uint32_t found = rank_roots(list, c.n_qualifying, sp.max_segments, order, at<uint16_t>(hp, pin.rank));
+    note_write(labels_dev_out, sizeof(uint16_t) * (size_t)n_px);
+    if (roots_dev_out) note_write(roots_dev_out, sizeof(uint32_t) * (size_t)n_px);
     // (the same launches whatever the frame holds: at least one word of the table and one record travel)
-    HIP_TRY(prk::launch_stage_words(hd + kSegPinRoots, rank_dev, std::max<size_t>(sizeof(uint16_t) * c.n_qualifying, 16), g->stream));
+    HIP_TRY(prk::launch_stage_words(at<unsigned char>(hd, pin.rank), rank_dev, std::max<size_t>(sizeof(uint16_t) * c.n_qualifying, 16), g->stream));
     HIP_TRY(prk::launch_segment_relabel(depth_dev, i32, W, H, parent, count, rank_dev, found, labels_dev_out, roots_dev_out, acc, g->stream));
-    g_writes.note(labels_dev_out, sizeof(uint16_t) * (size_t)n_px);
-    if (roots_dev_out) g_writes.note(roots_dev_out, sizeof(uint32_t) * (size_t)n_px);
     const uint32_t acc_words = (uint32_t)(sizeof(segments::Acc) / sizeof(uint32_t));
-    HIP_TRY(prk::launch_copy_words32(acc, hd + kSegPinRoots + kSegRankBytes, acc_words * std::max(found, 1u), g->stream));
+    HIP_TRY(prk::launch_copy_words32(acc, at<unsigned char>(hd, pin.acc), acc_words * std::max(found, 1u), g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    const segments::Acc *got = reinterpret_cast<const segments::Acc *>(hp + kSegPinRoots + kSegRankBytes);
+    const segments::Acc *got = at<segments::Acc>(hp, pin.acc);
     for (uint32_t k = 0; k < found; ++k) {
         if (got[k].pixels != list[order[k]].pixels) { set_error("%s: segment %u gathered %u pixels, its component has %u", fn, k + 1, got[k].pixels, list[order[k]].pixels); return PR_ERR_HIP; }
         segments_host[k] = segments::record(list[order[k]].root, got[k]);
@@ -202,17 +192,17 @@ int pr_segment_depth_dev(const uint16_t *labels_dev, const void *depth_in_dev, i
 {
     const char *fn = "pr_segment_depth_dev";
     if (!labels_dev || !depth_in_dev || !depth_out_dev || (n_keep && !keep_host)) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
-    if (n_px == 0 || n_px > ((size_t)1 << 26)) { set_error("%s: n_px must be 1 .. 2^26 (got %zu)", fn, n_px); return PR_ERR_INVALID; }
+    PR_TRY(depth_frame_ok(fn, n_px));
     if (n_keep > PR_SEGMENT_MAX + 1) { set_error("%s: n_keep must not exceed PR_SEGMENT_MAX + 1 = %d (got %u)", fn, PR_SEGMENT_MAX + 1, n_keep); return PR_ERR_INVALID; }
     PR_ENTER();
     PR_TRY(g->seg_tmp.ensure(kSegKeepBytes));
-    PR_TRY(g->h_seg.ensure(kSegPinBytes));
+    PR_TRY(g->h_seg.ensure(SegPinned().b.bytes()));
     uint32_t *bits = g->h_seg.as<uint32_t>();
     std::memset(bits, 0, kSegKeepBytes);
     for (uint32_t k = 1; k < n_keep; ++k) if (keep_host[k]) bits[k >> 5] |= 1u << (k & 31u);      // label 0 is never kept
     HIP_TRY(prk::launch_stage_words(g->h_seg.dev, g->seg_tmp.p, kSegKeepBytes, g->stream));
+    note_write(depth_out_dev, n_px * depth_bytes(depth_is_i32 != 0));
     HIP_TRY(prk::launch_segment_depth(labels_dev, depth_in_dev, depth_out_dev, depth_is_i32 != 0, (uint32_t)n_px, g->seg_tmp.as<uint32_t>(), n_keep, g->stream));
-    g_writes.note(depth_out_dev, n_px * (depth_is_i32 ? 4 : 2));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return PR_OK;
 }
@@ -221,7 +211,7 @@ int pr_segment_roi(const pr_segment *segment, size_t width, size_t height, uint3
 {
     const char *fn = "pr_segment_roi";
     if (!segment || !roi_out) { set_error("%s: bad arguments (a null pointer)", fn); return PR_ERR_INVALID; }
-    PR_TRY(segment_frame_ok(fn, width, height));
+    PR_TRY(depth_frame_ok(fn, "a frame", width, height));
     if (segment->x0 > segment->x1 || segment->y0 > segment->y1 || segment->x1 >= width || segment->y1 >= height) {
         set_error("%s: the box [%u, %u] x [%u, %u] does not lie in a %zux%zu frame", fn, segment->x0, segment->x1, segment->y0, segment->y1, width, height); return PR_ERR_INVALID;
     }

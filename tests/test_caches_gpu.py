@@ -207,6 +207,53 @@ def test_one_scene_object_reinitialised_under_its_own_batch_in_flight(gpu, model
     assert res.tobytes() == want[6 % 3][0].tobytes()
 
 
+FRAME_STAGES = ["depth_fuse", "depth_filter", "depth_reproject", "scene_planes", "segment_depth"]
+
+
+@pytest.mark.device_solve
+@pytest.mark.parametrize("stage", FRAME_STAGES)
+@pytest.mark.parametrize("kind", ["proj", "nn"])
+def test_frame_stage_output_over_a_scene_of_a_batch_in_flight(gpu, model, scenario, kind, stage):
+    """The frame stages' outputs are ordered like every other write through the library (note_write, pr_runtime.h): a stage whose ``depth_out`` lies
+    over the point array of the scene a pending batch reads waits for that batch, then writes.  The batch returns the synchronous call's bytes, the
+    range holds what the same stage call writes into a buffer of its own, and no batch is repeated.  (Before the stages announced their writes
+    ahead of their launches this was a race; a pass of a race proves nothing, so the order of note_write and the launches is also a matter of
+    reading csrc/pr_*.cpp.)"""
+    K, proj = scenario["K"], scenario["proj"]
+    poses = synth.hypotheses(64)
+    crit = api.ICPConvergenceCriteria(0.0, 0.0, 8)
+    base = scenario["depth"][1].astype(np.int32)
+    later = base.copy()
+    later[later > 0] += 4
+    d_a, d_b = api.DeviceVector.from_host(base.reshape(-1)), api.DeviceVector.from_host(later.reshape(-1))
+    fresh = (lambda: api.Scene_projective().init_Scene_projective_device(d_a, K, W, H)) if kind == "proj" else (lambda: api.Scene_nn().init_Scene_nn_device(d_a, K, W, H))
+    S = fresh()
+    want = api.refine_batch(model, poses, W, H, proj, K, S, crit)
+    other = api.Scene_projective().init_Scene_projective_device(d_b, K, W, H)      # scene_planes' own scene: another object
+    labels = api.scene_segments(d_a, W, H, min_pixels=16)[1]
+    run = {
+        "depth_fuse": lambda out: api.depth_fuse([d_a, d_b], W, H, depth_out=out),
+        "depth_filter": lambda out: api.depth_filter(d_b, W, H, depth_out=out, radius=1, fill_min=5)[0],
+        "depth_reproject": lambda out: api.depth_reproject([api.ReprojectSource.frame(d_b, W, H, K)], W, H, K, dtype=np.int32, depth_out=out)[0],
+        "scene_planes": lambda out: api.scene_planes(other, d_b, depth_out=out, min_support=50)[2],
+        "segment_depth": lambda out: api.segment_depth(labels, d_a, [1], depth_out=out),
+    }[stage]
+    own = run(None).to_host()                                       # what the stage writes into a buffer of its own
+    assert own.dtype == np.int32 and own.size == W * H and own.any()
+    over = api.DeviceVector(W * H, np.int32, _adopt=S.pcd_buffer.data())      # the first W * H words of the scene's point array
+    repeated = api.stats()[0]
+    try:
+        api.refine_submit(0, model, poses, W, H, proj, K, S, crit)
+        run(over)                                                   # batch 0 in flight
+        res, sizes = api.refine_wait(0)
+        got = over.to_host()
+    finally:
+        over._ptr, over.count = None, 0                             # detached: the scene object frees its array itself
+    assert res.tobytes() == want[0].tobytes() and np.array_equal(sizes, want[1])
+    assert got.tobytes() == own.tobytes()
+    assert api.stats()[0] == repeated
+
+
 @pytest.mark.device_solve
 def test_unchanged_cropped_scene_is_never_found_stale(gpu, model, scenario, gscenes):
     """Every asynchronous batch compares the sampled fingerprint of the scene arrays with the word kept behind the packed cache's tables

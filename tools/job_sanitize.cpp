@@ -1,8 +1,9 @@
 // build: g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ipose_refine_amd/csrc tools/job_sanitize.cpp -o job_sanitize;  ./job_sanitize
 // Sanitizer harness for the host-only helpers of the fused batch path and the scoring path (pr_runtime.h): make_job, score_request_ok, render_args_ok and vsd_args_ok with null and
-// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), the mixed-batch layer (plan_meshes on a worked example and on every table it refuses; Batch: gather, scatter, the pyramid's rows, the P x P matrix, the inverse, the one-mesh identity; camera_centers bit for bit against the expression it replaced), pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance), and the scene caches (the control words NNInfo and the fingerprint words FpWords / ProjTail at their documented positions, packed_layout, the source lists scene_sources / check_sources, pick_nn_set rule by rule, nn_route at every clamp).  None of them calls HIP, so nothing of the runtime is linked.
+// out-of-range arguments, the layouts of a slot's pinned blocks (SlotIn, SlotOut) and of the kd-tree workspace (nn_layout, nn_carve), the pose-group split; the packed layouts (box_area, box_slot, cloud_slot), the plan of an asynchronous batch (plan_async), the overlap rule (release_pass_for) the byte rule of a timed pass (icp_span_bytes), the mixed-batch layer (plan_meshes on a worked example and on every table it refuses; Batch: gather, scatter, the pyramid's rows, the P x P matrix, the inverse, the one-mesh identity; camera_centers bit for bit against the expression it replaced), pose observability's argument checks and covariance (info_scene_ok, info_center_radius_ok, info_covariance), and the scene caches (the control words NNInfo and the fingerprint words FpWords / ProjTail at their documented positions, packed_layout, the source lists scene_sources / check_sources, pick_nn_set rule by rule, nn_route at every clamp), and the frame stages' shared rules and layouts (frame_stage.h: depth_frame_ok, gate_ok, window_ok, with_depth, Block, ScanRows and the blocks of the planes, segments and PPF votes at their smallest and largest parameters).  None of them calls HIP, so nothing of the runtime is linked.
 #include <cstdio>
 #include "pr_runtime.h"
+#include "frame_stage.h"
 namespace prh { void set_error(const char *, ...) {} }
 using namespace prr;
 static long fails = 0;
@@ -596,6 +597,70 @@ int main()
         CHECK(nn_route(info_of(24), 5000, -3, 64, 1, 1, 1).topo_nodes == 0 && nn_route(info_of(30), 50000, 8191, 0, 1, 1, 1).topo_nodes == 8191);
         CHECK(prk::kNNLdsNodesPlain == 4064u && prk::kNNLdsNodesPlain * 16u + prk::kPassStaticLds == 65536u && prk::kNNLdsNodesMax == 8192u);
         CHECK(is(nn_route(info_of(24), 1, 0, 100000, 1, 1, 1), 1, 24, true, true));
+    }
+    // ---- the frame stages' shared rules and block layouts (frame_stage.h) ----
+    {
+        const char *fn = "job_sanitize";
+        const size_t good[][2] = { { 1, 1 }, { 65535, 1 }, { 1, 65535 }, { 8192, 8192 }, { 65535, 1024 } };
+        const size_t bad[][2] = { { 0, 7 }, { 7, 0 }, { 65536, 1 }, { 1, 65536 }, { 65535, 1025 }, { 8193, 8192 } };
+        for (const auto &s : good) CHECK(depth_frame_ok(fn, "a frame", s[0], s[1]) == PR_OK);
+        for (const auto &s : bad) CHECK(depth_frame_ok(fn, "a frame", s[0], s[1]) == PR_ERR_INVALID);
+        CHECK(depth_frame_ok(fn, 1) == PR_OK && depth_frame_ok(fn, (size_t)1 << 26) == PR_OK);
+        CHECK(depth_frame_ok(fn, 0) == PR_ERR_INVALID && depth_frame_ok(fn, ((size_t)1 << 26) + 1) == PR_ERR_INVALID);
+        // the gate: each limit from both sides
+        const uint32_t top = 0x7FFFFFFFu;
+        CHECK(gate_ok(fn, "b", 0, 0, 0, 0) == PR_OK && gate_ok(fn, "b", top, top, top, 1000) == PR_OK);
+        CHECK(gate_ok(fn, "b", top + 1, 0, 0, 0) == PR_ERR_INVALID && gate_ok(fn, "b", 0, top + 1, 0, 0) == PR_ERR_INVALID && gate_ok(fn, "b", 0, 0, top + 1, 0) == PR_ERR_INVALID);
+        CHECK(gate_ok(fn, "b", 500, 500, 0, 0) == PR_OK && gate_ok(fn, "b", 501, 500, 0, 0) == PR_ERR_INVALID && gate_ok(fn, "b", 501, 0, 0, 0) == PR_OK);      // max_mm 0: no upper gate
+        CHECK(gate_ok(fn, "b", 0, 0, 0, 1001) == PR_ERR_INVALID);
+        // the window: the radius at its limit, a count without a window, the count at (2 r + 1)^2 - 1
+        CHECK(window_ok(fn, "b", "r", 0, 2, "c", 0) == PR_OK && window_ok(fn, "b", "r", 2, 2, "c", 0) == PR_OK && window_ok(fn, "b", "r", 3, 2, "c", 0) == PR_ERR_INVALID);
+        CHECK(window_ok(fn, "b", "r", 0, 2, "c", 1) == PR_ERR_INVALID && window_ok(fn, "b", "r", 1, 2, "c", 1) == PR_OK);
+        CHECK(window_ok(fn, "b", "r", 1, 2, "c", 8) == PR_OK && window_ok(fn, "b", "r", 1, 2, "c", 9) == PR_ERR_INVALID);
+        CHECK(window_ok(fn, "b", "r", 2, 2, "c", 24) == PR_OK && window_ok(fn, "b", "r", 2, 2, "c", 25) == PR_ERR_INVALID);
+        // the dispatch hands the pointer on unchanged, typed by the flag
+        int32_t wide[2] = { 5, 6 };
+        CHECK(with_depth(static_cast<const void *>(wide), true, [&](auto *p) { return sizeof *p == 4 && (const void *)p == wide; }));
+        CHECK(with_depth(static_cast<void *>(wide), false, [&](auto *p) { return sizeof *p == 2 && (void *)p == wide; }));
+        CHECK(depth_bytes(true) == 4 && depth_bytes(false) == 2);
+        // a block's parts: each on its alignment, in order, none overlapping, bytes() the end of the last one
+        struct Part { size_t at, bytes, align; };
+        const auto parts_ok = [&](std::initializer_list<Part> parts, size_t total) {
+            size_t end = 0;
+            for (const Part &p : parts) { CHECK(p.at % p.align == 0 && p.at >= end && p.at - end < p.align); end = p.at + p.bytes; }
+            CHECK(end == total);
+        };
+        { Block b; CHECK(b.take<uint32_t>(3) == 0 && b.take<uint8_t>(1, 1) == 12 && b.take<uint64_t>(0) == 16 && b.take<uint16_t>(1, 256) == 256 && b.bytes() == 258); }
+        { uint32_t words[8] = {}; const ScanRows r(words, 4, 3); CHECK(ScanRows::words(3) == 7 && r.count == words + 1 && r.off == words + 4 && r.total == words + 7); }
+        for (uint32_t n_planes : { 1u, (uint32_t)PR_PLANE_MAX_PLANES })
+            for (uint32_t rows : { 1u, 8192u })                       // a frame of one row; 8192 rows at stride 1
+                for (bool own : { false, true }) {
+                    const PlaneBlock l(n_planes, rows, own);
+                    parts_ok({ { l.rounds, sizeof(prk::PlaneRound) * n_planes, 16 }, { l.rows, 4 * (2 * (size_t)rows + 1), 16 }, { l.pts, sizeof(prk::PlaneSample) * PR_PLANE_MAX_SAMPLES, 16 },
+                               { l.nrm, sizeof(pr_vec3) * PR_PLANE_MAX_SAMPLES, 16 }, { l.support, own ? 4 * (size_t)n_planes * PR_PLANE_MAX_CANDIDATES : 0, 16 } }, l.b.bytes());
+                }
+        for (uint32_t max_segments : { 1u, (uint32_t)PR_SEGMENT_MAX })
+            for (uint32_t n_px : { 1u, 1u << 26 }) {
+                const uint32_t n_chunks = (n_px + prk::kSegChunk - 1) / prk::kSegChunk;
+                const SegBlock l(max_segments, n_chunks, n_px);
+                parts_ok({ { l.ctl, sizeof(prk::SegControl), 16 }, { l.acc, sizeof(segments::Acc) * max_segments, 16 }, { l.rank, 2 * (size_t)PR_SEGMENT_MAX_ROOTS, 16 },
+                           { l.roots, sizeof(prk::SegRoot) * PR_SEGMENT_MAX_ROOTS, 16 }, { l.chunks, 4 * (2 * (size_t)n_chunks + 1), 16 }, { l.parent, 4 * (size_t)n_px, 16 },
+                           { l.count, 4 * (size_t)n_px, 4 } }, l.b.bytes());
+            }
+        {
+            const SegPinned l;
+            parts_ok({ { l.ctl, sizeof(prk::SegControl), 16 }, { l.roots, sizeof(prk::SegRoot) * PR_SEGMENT_MAX_ROOTS, 16 }, { l.rank, 2 * (size_t)PR_SEGMENT_MAX_ROOTS, 16 },
+                       { l.acc, sizeof(segments::Acc) * PR_SEGMENT_MAX, 16 } }, l.b.bytes());
+            CHECK(l.ctl == 0 && l.roots == sizeof(prk::SegControl));      // the compaction writes the control words and the roots as one run
+        }
+        for (uint32_t n_models : { 0u, 1u, (uint32_t)PR_PPF_MAX_MODELS })      // 0: pr_ppf_vote's block, without a table
+            for (uint32_t n_refs : { 1u, (uint32_t)PR_PPF_MAX_SCENE_POINTS })
+                for (uint32_t n_peaks : { 1u, (uint32_t)PR_PPF_MAX_PEAKS }) {
+                    const VoteBlock l(n_models, n_refs, n_peaks);
+                    const size_t pk = sizeof(pr_ppf_peak) * n_refs * n_peaks * (n_models ? n_models : 1);
+                    parts_ok({ { l.models, sizeof(prk::PpfModelRec) * n_models, 16 }, { l.peaks, pk, 16 }, { l.refs, sizeof(prk::PpfRef) * n_refs, 16 } }, l.b.bytes());
+                    CHECK(l.back_words() * sizeof(uint32_t) == l.b.bytes() - l.peaks && (l.peaks - l.models) % 16 == 0);
+                }
     }
     std::printf("job_sanitize: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;
